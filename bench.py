@@ -13,8 +13,13 @@ LOCAL_RANK / WORLD_SIZE in the environment), or plainly as `python bench.py --gp
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` as a CHILD process before it has
 touched the GPU (never an exec after device init), relays the child's output and exits with its return code.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-events]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-events] [--dump-outputs DIR]
 prints ONE JSON line on rank 0.
+
+--dump-outputs DIR: after the K timed steps rank 0 writes what the LAST timed step returned to DIR/<name>.npy (`dump_outputs`):
+`mel` and `mel_lengths` of synthesise() (N>1: `mel` is the all-gathered batch, `mel_lengths` this rank's shard = its first
+rows), `audio` with --with-vocoder.  Weights, ids and noise are seeded, so the same arguments give the same inputs in every
+run and two builds can be compared array for array.
 """
 import argparse
 import importlib
@@ -74,6 +79,7 @@ GEMM_MODES = {0: ("f32", "v_mfma_f32_32x32x2_f32 on fp32 operands", 1, PEAK_F32_
               17: ("bf16 storage, fp32 accumulate (BASELINE configs[2] dtype: 2-byte bfloat16 activation / weight planes; text encoder fp32-equivalent)",
                    "v_mfma_f32_16x16x32_bf16 / 32x32x16_bf16, 1 product per MAC", 1, PEAK_16BIT_MFMA_TFLOPS)}
 BATCH, N_TOKENS, N_STEPS_ODE, SOLVER = 32, 128, 10, "euler"
+DUMP_BUDGET_BYTES = 64 << 20     # --dump-outputs: all files together stay below this
 
 
 def algorithmic_flops(hp, batch, t_pad, tx, nfe):
@@ -157,6 +163,23 @@ def cpu_baseline(hp, sd, synthetic):
                       f"B=1 median of 5 runs ({', '.join(f'{t:.2f}' for t in t1)} s for {f1} frames) = value_b1"}
 
 
+def dump_outputs(outdir, outputs):
+    """Write every tensor of ``outputs`` (name -> tensor) as ``outdir/<name>.npy``: floating point as float32 (float64 stays),
+    integers as float64 (exact for lengths).  Each array gets an equal share of DUMP_BUDGET_BYTES; a larger one is stored as
+    a 1-D sample of its flattened elements at sorted indices drawn by a fixed-seed generator, the same indices in every run."""
+    import numpy as np
+    outdir = Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(outputs), 1)
+    for name, t in outputs.items():
+        t = t.detach().cpu()
+        a = t.to(torch.float32 if t.is_floating_point() and t.dtype != torch.float64 else torch.float64).numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(outdir / f"{name}.npy", a)
+
+
 def main():
     global BATCH, SOLVER, N_STEPS_ODE
     ap = argparse.ArgumentParser()
@@ -174,6 +197,8 @@ def main():
                          "with its measured mel error")
     ap.add_argument("--solver", default=SOLVER)
     ap.add_argument("--n-timesteps", type=int, default=N_STEPS_ODE)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
     if args.arithmetic == "f16-storage":
         os.environ["MTTS_GEMM_TERMS"] = "16"
@@ -243,12 +268,13 @@ def main():
         vocoder = inference.load_vocoder("vocos", state_dict=synthetic.make_vocos_state_dict(seed=11))
 
     def step():
-        mel = model.synthesise(x, x_len, n_timesteps=N_STEPS_ODE, speaker=0)["mel"]
+        out = model.synthesise(x, x_len, n_timesteps=N_STEPS_ODE, speaker=0)
+        res = {"mel": out["mel"], "mel_lengths": out["mel_lengths"]}
         if vocoder is not None:
-            vocoder(mel)                     # [B, 256 * T_valid] samples at 24 kHz; the metric stays mel frames
+            res["audio"] = vocoder(out["mel"])   # [B, 256 * T_valid] samples at 24 kHz; the metric stays mel frames
         if world > 1:
-            mel = dp.all_gather_mels(mel, world)
-        return mel
+            res["mel"] = dp.all_gather_mels(out["mel"], world)
+        return res
 
     def barrier():
         if world > 1:
@@ -260,9 +286,12 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        mel = step()
+        res = step()
     barrier()
     el = time.perf_counter() - t0
+    mel = res["mel"]
+    if args.dump_outputs and rank == 0:     # before any later pass of this script runs the model again
+        dump_outputs(args.dump_outputs, res)
     if world > 1:
         t = torch.tensor([el], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 from conftest import ROOT
 
 
@@ -35,3 +37,62 @@ def test_single_process_default_does_not_spawn():
 def test_child_failure_is_relayed():
     res = _run(["--gpus", "2", "--no-such-flag"])
     assert res.returncode != 0
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", ROOT / "bench.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)             # importing does not launch anything: the self-launch sits under __main__
+    return mod
+
+
+def test_dump_outputs_dtypes_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per output, float32 / float64 only, integers exact, and an array beyond its share of the
+    budget stored as the same seeded sample in every call."""
+    import numpy as np
+    import torch
+    bench = _bench_module()
+    g = torch.Generator().manual_seed(0)
+    mel = torch.randn(3, 5, 7, generator=g)
+    half = torch.randn(4, 6, generator=g).to(torch.bfloat16)
+    lens = torch.tensor([7, 5, 2 ** 40 + 1], dtype=torch.int64)
+    bench.dump_outputs(tmp_path / "a", {"mel": mel, "half": half, "mel_lengths": lens})
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["half", "mel", "mel_lengths"]
+    assert got["mel"].dtype == np.float32 and np.array_equal(got["mel"], mel.numpy())
+    assert got["half"].dtype == np.float32 and np.array_equal(got["half"], half.float().numpy())
+    assert got["mel_lengths"].dtype == np.float64 and got["mel_lengths"].astype(np.int64).tolist() == lens.tolist()
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 40 * 4)      # a share of 40 floats per array
+    big = torch.arange(1000, dtype=torch.float32).reshape(10, 100)
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, {"big": big, "small": mel[0, 0]})
+    b, c = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert b.shape == (40,) and np.array_equal(b, c)                 # the same sample both times
+    assert np.all(np.diff(b) > 0) and set(b.tolist()) <= set(range(1000))   # sorted, distinct elements of the array
+    assert np.array_equal(np.load(tmp_path / "b" / "small.npy"), mel[0, 0].numpy())
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "b").iterdir()) <= bench.DUMP_BUDGET_BYTES
+
+
+@pytest.mark.gpu
+def test_dump_outputs_of_the_timed_path_repeat(tmp_path):
+    """Two runs of the same bench command write the same arrays: what synthesise() returned in the last timed step, from
+    seeded weights, ids and noise (small batch; the JSON line reports the timed step count it was given)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MTTS_BENCH_DRYRUN")}
+    outs = []
+    for d in ("a", "b"):
+        res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+                              "--no-cpu-baseline", "--no-events", "--dump-outputs", str(tmp_path / d)],
+                             env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 2 and line["config"]["per_gpu_batch"] == 2
+        outs.append({f.stem: np.load(f) for f in (tmp_path / d).iterdir()})
+    a, b = outs
+    assert sorted(a) == sorted(b) == ["mel", "mel_lengths"]
+    assert a["mel"].dtype == np.float32 and a["mel"].ndim == 3 and a["mel"].shape[:2] == (2, 100)
+    assert a["mel_lengths"].dtype == np.float64 and a["mel_lengths"].max() == a["mel"].shape[-1]
+    assert np.isfinite(a["mel"]).all() and a["mel"].std() > 0
+    assert np.array_equal(a["mel"], b["mel"]) and np.array_equal(a["mel_lengths"], b["mel_lengths"])
