@@ -460,8 +460,6 @@ static int pack_all(mtts_ctx* c, bool dry = false) {
     Packer P(c);
     P.dry = dry;
     auto S = [](const std::string& a, int i, const std::string& b) { return a + std::to_string(i) + b; };
-    const int taps3[3] = {-1, 0, 1};
-    (void)taps3;
 
     // ---------------- text encoder (reference text_encoder.py:319-373)
     EncW& E = c->enc;
@@ -689,19 +687,27 @@ struct DecBufs {
     int B = 0, T = 0, nl = 0;
     std::vector<int> Tl;                 // frames per level
     std::vector<float*> mask;            // [B*T_l]
-    std::vector<float*> bufA, bufB, skip;
-    float *Y = nullptr, *Hh = nullptr, *Rr = nullptr, *QKV = nullptr, *ATT = nullptr, *FF = nullptr;
-    float *mean = nullptr, *rstd = nullptr, *gnp = nullptr, *lnp = nullptr;
-    float* gns = nullptr;                // GroupNorm tile statistics left by the conv GEMMs' epilogues (P16 decoder)
-    _Float16* X16 = nullptr;             // P16 image of the residual stream x (the LayerNorm'd projections' LDS-DMA source)
-    // P16 decoder (decoder_eval_p16): every conv / projection input exists as a P16 image, written by its producer
+    // The flow of the call (p16_decoder): between two launches an activation is either fp32 rows or an image its producer
+    // wrote for its consumers -- P16, or H16 in the 16-bit storage mode.  The slots of this group hold whichever the flow uses
+    // (an image has at most the bytes of the fp32 rows); everything else is fp32 in both flows.
     bool p16 = false;
-    std::vector<_Float16*> A16, B16, S16;   // twins of bufA / bufB / skip per level (masked rows)
-    _Float16 *H16 = nullptr, *XM16 = nullptr;   // Block1D output (conv2 / final projection input); masked x|mu|0 state
+    int ew = 2;                          // halves per image element: 2 = P16 (head + residual), 1 = H16 (16-bit storage mode)
+    std::vector<float*> bufA, bufB, skip;   // per level: the two slots the blocks alternate between; the down path's output
+    float *H = nullptr;                  // Block1D output (conv2 / final projection input), already masked
+    float *QKV = nullptr, *ATT = nullptr, *FF = nullptr;
+    float *Y = nullptr, *Rr = nullptr;   // conv output the GroupNorm reads; 1x1 residual conv output
+    float *mean = nullptr, *rstd = nullptr, *gnp = nullptr, *lnp = nullptr;
+    // image flow only
+    float* X = nullptr;                  // the residual stream x of the ResNet + transformer blocks in flight (stream())
+    float* XM = nullptr;                 // masked x | mu | 0 state
+    float* gns = nullptr;                // GroupNorm tile statistics left by the conv GEMMs' epilogues
+    // Where a ResNet and its transformer blocks keep their residual stream, unmasked, while their launches update it in place:
+    // the image flow in X (the last launch writes the masked copy into the destination slot), fp32 rows in the destination slot
+    // itself.
+    float* stream(float* dst) const { return p16 ? X : dst; }
     float *xmu = nullptr, *xmu2 = nullptr, *vel[4] = {nullptr, nullptr, nullptr, nullptr};
     float *TS = nullptr, *T1 = nullptr, *T2 = nullptr, *T3 = nullptr, *TB = nullptr;
     int ldx = 0, ldv = 0;
-    int ew = 2;                          // halves per image element: 2 = P16 (head + residual), 1 = H16 (16-bit storage mode)
     // frame tables (kernels.h FrameTableArgs), per level: null when every utterance owns all T rows
     int T_true = 0;                      // the reference's padded length; T above is the rows per utterance actually held
     bool folded = false;
@@ -715,21 +721,15 @@ struct DecBufs {
     bool qkv_ready = false;              // the previous block's chain launch already left this block's q|k|v image in QKV
 };
 
-// Transformer blocks of width C run on P16 images (gemm_p16.hip, attention P16 I/O) when the context computes in the
-// fp16-split mode and the shapes allow whole 32-channel groups and 64-wide heads; MTTS_P16=0 (read at mtts_create) keeps
-// the fp32-operand path.
-static bool p16_blocks(const mtts_ctx* c, int C) {
-    const mtts_config& g = c->cfg;
-    return c->p16_on && c->gemm_terms == 2 && (C % 64) == 0 && g.dec_head_dim == 64;
-}
-
-// The whole estimator runs on P16 images (decoder_eval_p16) when every level qualifies and there is at least one transformer
-// block per ResNet (the ResNet output then always feeds a LayerNorm'd projection first).
+// The estimator runs on images (gemm_p16.hip, attention P16 I/O) when the context computes in the fp16-split mode, every level
+// has whole 64-channel slices and 64-wide heads, and there is at least one transformer block per ResNet (the ResNet output then
+// always feeds a LayerNorm'd projection first); MTTS_P16=0 (read at mtts_create) keeps fp32 rows.  Any other estimator runs
+// every block on fp32 rows.
 static bool p16_decoder(const mtts_ctx* c) {
     const mtts_config& g = c->cfg;
-    if (g.dec_n_blocks < 1 || (g.n_feats & 1)) return false;
+    if (!c->p16_on || c->gemm_terms != 2 || g.dec_head_dim != 64 || g.dec_n_blocks < 1 || (g.n_feats & 1)) return false;
     for (int l = 0; l < g.dec_levels; ++l)
-        if (!p16_blocks(c, g.dec_channels[l])) return false;
+        if (g.dec_channels[l] % 64) return false;
     return true;
 }
 
@@ -741,6 +741,8 @@ static int plan_decoder(const mtts_ctx* c, int B, int T, int max_evals, int n_st
     for (int i = 0; i < d.nl; ++i) cmax = std::max(cmax, g.dec_channels[i]);
     const int inner = g.dec_heads * g.dec_head_dim;
     const size_t M0 = (size_t)B * T;
+    d.p16 = p16_decoder(c);
+    d.ew = (d.p16 && c->half16) ? 1 : 2;
     d.Tl.resize(d.nl);
     d.mask.resize(d.nl); d.bufA.resize(d.nl); d.bufB.resize(d.nl); d.skip.resize(d.nl);
     (void)ws.bytes(256);                 // header: the call's range flag (begin_call)
@@ -757,26 +759,16 @@ static int plan_decoder(const mtts_ctx* c, int B, int T, int max_evals, int n_st
         d.bufB[l] = ws.f(Ml * cmax);
         d.skip[l] = ws.f(Ml * cmax);
     }
-    d.Y = ws.f(M0 * cmax); d.Hh = ws.f(M0 * cmax); d.Rr = ws.f(M0 * cmax);
+    d.Y = ws.f(M0 * cmax); d.H = ws.f(M0 * cmax); d.Rr = ws.f(M0 * cmax);
     d.QKV = ws.f(M0 * 3 * inner); d.ATT = ws.f(M0 * inner); d.FF = ws.f(M0 * 4 * cmax);
     d.mean = ws.f(M0); d.rstd = ws.f(M0);
     d.lnp = ws.f(M0 * (size_t)((cmax + 63) / 64) * 2);
-    d.X16 = reinterpret_cast<_Float16*>(ws.f(M0 * round_up(cmax, 32)));
-    d.p16 = p16_decoder(c);
     if (d.p16) {
-        d.A16.resize(d.nl); d.B16.resize(d.nl); d.S16.resize(d.nl);
-        for (int l = 0; l < d.nl; ++l) {
-            const size_t Ml = (size_t)B * d.Tl[l];
-            d.A16[l] = reinterpret_cast<_Float16*>(ws.f(Ml * cmax));
-            d.B16[l] = reinterpret_cast<_Float16*>(ws.f(Ml * cmax));
-            d.S16[l] = reinterpret_cast<_Float16*>(ws.f(Ml * cmax));
-        }
-        d.H16 = reinterpret_cast<_Float16*>(ws.f(M0 * cmax));
-        d.XM16 = reinterpret_cast<_Float16*>(ws.f(M0 * round_up(2 * g.n_feats, 64)));
+        d.X = ws.f(M0 * round_up(cmax, 32));
+        d.XM = ws.f(M0 * round_up(2 * g.n_feats, 64));
+        d.gns = ws.f((M0 / 32 + 2) * 2 * (size_t)((cmax + 63) / 64) * 8);
     }
     d.gnp = ws.f((size_t)B * gn_chunks_max(T) * 8 * 2);
-    d.gns = ws.f((M0 / 32 + 2) * 2 * (size_t)((cmax + 63) / 64) * 8);
-    d.ew = (d.p16 && c->half16) ? 1 : 2;
     d.ldx = round_up(2 * g.n_feats, c->half16 ? 64 : GEMM_BK);
     d.ldv = round_up(g.n_feats, 4);
     d.xmu = ws.f(M0 * d.ldx);
@@ -812,276 +804,59 @@ static int time_embed(mtts_ctx* c, DecBufs& d, const TimeVals& tv, int nt, hipSt
     return 0;
 }
 
-// ResnetBlock1D.forward (reference decoder.py:58-63) on channels-last rows; input = up to two channel segments.
-static int resnet_block(mtts_ctx* c, DecBufs& d, const ResnetW& r, const float* in0, int ld0, int c0, const float* in1, int ld1,
-                        int c1, int lvl, const float* tbias, float* out, bool emit_stats, hipStream_t s) {
-    const int B = d.B, T = d.Tl[lvl], C = r.cout;
-    const float* mask = d.mask[lvl];
-    GemmArgs a;
-    panel_args(c, r.conv1, a); rows_plain(a, B, T); taps_centered(a, 3);
-    a.a0 = in0; a.lda0 = ld0; a.c0 = c0; a.a1 = in1; a.lda1 = ld1; a.c1 = c1; a.a_mask = mask;
-    a.out = d.Y; a.ldc = C;
-    RET_IF(run_gemm(c, a, s));
-    LAUNCH(c, 2, 0, s, launch_gn_partial(d.Y, B, T, C, 8, d.gnp, s, d.nr(lvl)));
-    GnApplyArgs g1;
-    g1.y = d.Y; g1.partial = d.gnp; g1.gamma = W(c, r.gn1_g.off); g1.beta = W(c, r.gn1_b.off); g1.mask = mask; g1.nrows = d.nr(lvl);
-    if (d.folded) { g1.nextra = d.ne(lvl); g1.bias_stats = W(c, r.gn1_bs.off); }
-    g1.chbias = tbias; g1.out = d.Hh; g1.B = B; g1.T = T; g1.C = C;
-    RET_IF(run_gn_apply(c, g1, s));
-    GemmArgs b;
-    panel_args(c, r.conv2, b); rows_plain(b, B, T); taps_centered(b, 3);
-    b.a0 = d.Hh; b.lda0 = C; b.c0 = C; b.out = d.Y; b.ldc = C;      // Hh is already masked
-    RET_IF(run_gemm(c, b, s));
-    LAUNCH(c, 2, 0, s, launch_gn_partial(d.Y, B, T, C, 8, d.gnp, s, d.nr(lvl)));
-    GemmArgs rc;
-    panel_args(c, r.res, rc); rows_plain(rc, B, T);
-    rc.a0 = in0; rc.lda0 = ld0; rc.c0 = c0; rc.a1 = in1; rc.lda1 = ld1; rc.c1 = c1; rc.a_mask = mask;
-    rc.out = d.Rr; rc.ldc = C;
-    RET_IF(run_gemm(c, rc, s));
-    GnApplyArgs g2;
-    g2.y = d.Y; g2.partial = d.gnp; g2.gamma = W(c, r.gn2_g.off); g2.beta = W(c, r.gn2_b.off); g2.mask = mask; g2.nrows = d.nr(lvl);
-    if (d.folded) { g2.nextra = d.ne(lvl); g2.bias_stats = W(c, r.gn2_bs.off); }
-    g2.res = d.Rr; g2.ldr = C; g2.out = out; g2.B = B; g2.T = T; g2.C = C;
-    if (emit_stats && (C % 64) == 0) {       // for the first transformer block: LayerNorm moments and, in P16 mode, x's image
-        g2.stats_out = d.lnp;
-        if (p16_blocks(c, C)) { g2.out16 = d.X16; g2.ld16 = d.ew * C; }
-    }
-    RET_IF(run_gn_apply(c, g2, s));
-    return 0;
-}
-
-// BasicTransformerBlock.forward (reference transformer.py:230-303, self-attention only), in place on x [B*T, C].
-// LayerNorm statistics travel with the data: the GEMM that writes x (attention out-projection, second FF projection)
-// leaves per-row partial moments of its 64-column slices behind (stats_out) and the next projection merges them in its
-// prologue; the ResNet block's last kernel (gn_apply) does the same for the first LayerNorm after it.  The row_stats
-// kernel only runs for widths that are not a multiple of 64 (the tiny test model).
-// last16 / last16_mask (P16 decoder): where the LAST block of a run leaves the masked P16 image of x for the convs.
-static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, float* x, int C, int lvl, bool have_stats, bool emit_stats,
-                             hipStream_t s, _Float16* last16 = nullptr) {
-    const mtts_config& g = c->cfg;
-    const int B = d.B, T = d.Tl[lvl], M = B * T, inner = g.dec_heads * g.dec_head_dim;
-    const bool fuse = (C % 64) == 0;
-    if (p16_blocks(c, C) && have_stats) {
-        // P16 flow: q|k|v, the attention output and the FF hidden layer exist only as P16 images (same bytes as fp32, in the
-        // same buffers); x stays fp32 (the residual stream) with a P16 copy for the two LayerNorm'd projections.
-        _Float16* QKV16 = reinterpret_cast<_Float16*>(d.QKV);
-        _Float16* ATT16 = reinterpret_cast<_Float16*>(d.ATT);
-        _Float16* FF16 = reinterpret_cast<_Float16*>(d.FF);
-        // the row-local part as one launch (tblock_chain.hip) when the stream was packed and the batch is large enough that a
-        // workgroup per QB rows fills the chip: every workgroup streams ALL of the chain's weights (~7 MB at width 384), which
-        // only pays when their cost is shared by many rows per CU
-        static const int chain_only = [] { const char* e = getenv("MTTS_CHAIN_ONLY"); return !e ? 0 : (e[0] == 'f' ? 1 : 2); }();   // diagnostic
-        const bool chain = t.chain_frags > 0 && d.p16 && !c->half_now && M >= c->chain_min_rows && (emit_stats ? t.chain_nqkv > 0 : true) &&
-                           (chain_only == 0 || (chain_only == 1) == emit_stats);
-        if (!d.qkv_ready) {
-            GemmArgs q;
-            panel_args(c, t.qkv, q); rows_plain(q, B, T);
-            q.a16_0 = d.X16; q.lda16_0 = d.ew * C; q.c0 = C; q.a_part = d.lnp; q.a_nparts = C / 64;
-            q.out16 = QKV16; q.ld16 = 3 * d.ew * inner; q.out_lscale = 1.0f;
-            RET_IF(run_gemm(c, q, s));
-        }
-        d.qkv_ready = false;
-        AttnArgs at;
-        at.qkv16 = QKV16; at.ld16 = 3 * d.ew * inner; at.out16 = ATT16; at.ldo16 = d.ew * inner; at.mask = d.kb(lvl);
-        at.B = B; at.T = T; at.H = g.dec_heads; at.D = g.dec_head_dim;
-        at.scale = 1.0f / sqrtf((float)g.dec_head_dim); at.mask_mode = 0; at.klen = d.nr(lvl); at.fast16 = c->fast16;
-        RET_IF(run_attn(c, at, s));
-        // below that row count: the pair form -- two workgroups of one XCD per 48-row tile, each streaming half of the FeedForward
-        // and of the q|k|v passes -- while all of them (and the prefetchers) are resident at once
-        const int tiles48 = (M + 47) / 48;
-        static const int pair_min = [] { const char* e = getenv("MTTS_CHAIN_PAIR_MIN_ROWS"); return e ? atoi(e) : 3000; }();      // (3864 rows: -0.3..0.5 ms per step, 2576 rows: +0.3; profiles/r03_pair_ab.log)
-        const bool pair = !chain && c->pair_on && t.chain_pair_frags > 0 && d.p16 && !c->half_now && d.pair_flag && M >= pair_min &&
-                          16 * ((tiles48 + 7) / 8) + 16 <= 256 && (emit_stats ? t.chain_nqkv > 0 : true);
-        if (chain || pair) {
-            ChainArgs a;
-            a.M = M; a.C = C; a.inner = inner;
-            a.att16 = ATT16; a.ld_att = 2 * inner;
-            a.x16 = d.X16; a.ld_x = 2 * C;
-            a.wstream = reinterpret_cast<const _Float16*>(W(c, t.chain)); a.stream_frags = t.chain_frags;
-            a.consts = W(c, t.chain_consts);
-            if (emit_stats) {                 // another block follows: its q|k|v leaves this launch, x stays unmasked
-                const TBlockW& nx = c->dec.tb[t.next];
-                a.b_qkv = W(c, nx.qkv.b); a.wsum_qkv = W(c, nx.qkv.wsum); a.n_qkv = nx.qkv.N;
-                a.qkv16 = QKV16; a.ld_qkv = 2 * nx.qkv.N;
-                a.x_out = d.X16; a.ld_out = 2 * C;
-                d.qkv_ready = true;
-            } else if (last16) { a.x_out = last16; a.ld_out = 2 * C; a.x_out_mask = d.mask[lvl]; }
-            else { a.x_out = d.X16; a.ld_out = 2 * C; }
-            a.ch = t.chain_ch;
-            { int pf_unused = 0; chain_plan(M, a.ch, c->chain_qb, &a.qb, &pf_unused); }
-            if (pair) {
-                a.pair = 1; a.qb = 48;
-                a.wstream = reinterpret_cast<const _Float16*>(W(c, t.chain_pair)); a.stream_frags = t.chain_pair_frags;
-                a.pair_part = d.FF;              // (the tiled path's hidden image: unused by a chain launch)
-                a.pair_flag = d.pair_flag;
-                a.pair_epoch = ++c->pair_epoch;
-                if (c->pair_epoch == 0) a.pair_epoch = ++c->pair_epoch;
-            }
-#ifdef MTTS_CHAIN_VERIFY
-            RET_IF(run_chain_verified(c, a, FF16, s));
-#else
-            RET_IF(run_chain(c, a, s));
-#endif
-            return 0;
-        }
-        GemmArgs o;
-        panel_args(c, t.out, o); rows_plain(o, B, T);
-        o.a16_0 = ATT16; o.lda16_0 = d.ew * inner; o.c0 = inner;
-        o.out16 = d.X16; o.ld16 = d.ew * C; o.stats_out = d.lnp;
-        if (d.p16) { o.res16 = d.X16; o.ldr16 = d.ew * C; }      // P16 decoder: the residual stream exists only as its image
-        else { o.res = x; o.ldr = C; o.out = x; o.ldc = C; }
-        RET_IF(run_gemm(c, o, s));
-        GemmArgs f1;
-        panel_args(c, t.ff1, f1); rows_plain(f1, B, T);
-        f1.a16_0 = d.X16; f1.lda16_0 = d.ew * C; f1.c0 = C; f1.a_part = d.lnp; f1.a_nparts = C / 64; f1.act = ACT_SNAKE;
-        f1.p0 = W(c, t.alpha_exp.off); f1.p1 = W(c, t.inv_beta.off); f1.out16 = FF16; f1.ld16 = 4 * d.ew * C;
-        RET_IF(run_gemm(c, f1, s));
-        GemmArgs f2;
-        panel_args(c, t.ff2, f2); rows_plain(f2, B, T);
-        f2.a16_0 = FF16; f2.lda16_0 = 4 * d.ew * C; f2.c0 = 4 * C;
-        if (d.p16) { f2.res16 = d.X16; f2.ldr16 = d.ew * C; }
-        else { f2.res = x; f2.ldr = C; f2.out = x; f2.ldc = C; }
-        if (emit_stats) { f2.stats_out = d.lnp; f2.out16 = d.X16; f2.ld16 = d.ew * C; }
-        else if (last16) { f2.out16 = last16; f2.ld16 = d.ew * C; f2.out16_mask = d.mask[lvl]; }
-        RET_IF(run_gemm(c, f2, s));
-        return 0;
-    }
-    GemmArgs q;
-    panel_args(c, t.qkv, q); rows_plain(q, B, T);
-    q.a0 = x; q.lda0 = C; q.c0 = C; q.out = d.QKV; q.ldc = 3 * inner;
-    if (fuse && have_stats) { q.a_part = d.lnp; q.a_nparts = C / 64; }
-    else {
-        LAUNCH(c, 2, 0, s, launch_row_stats(x, M, C, C, 1e-5f, d.mean, d.rstd, s));
-        q.a_mean = d.mean; q.a_rstd = d.rstd;
-    }
-    RET_IF(run_gemm(c, q, s));
-    AttnArgs at;
-    at.qkv = d.QKV; at.mask = d.kb(lvl); at.out = d.ATT; at.B = B; at.T = T; at.H = g.dec_heads; at.D = g.dec_head_dim;
-    at.scale = 1.0f / sqrtf((float)g.dec_head_dim); at.mask_mode = 0; at.klen = d.nr(lvl); at.fast16 = c->fast16;
-    RET_IF(run_attn(c, at, s));
-    GemmArgs o;
-    panel_args(c, t.out, o); rows_plain(o, B, T);
-    o.a0 = d.ATT; o.lda0 = inner; o.c0 = inner; o.res = x; o.ldr = C; o.out = x; o.ldc = C;
-    if (fuse) o.stats_out = d.lnp;
-    RET_IF(run_gemm(c, o, s));
-    GemmArgs f1;
-    panel_args(c, t.ff1, f1); rows_plain(f1, B, T);
-    f1.a0 = x; f1.lda0 = C; f1.c0 = C; f1.act = ACT_SNAKE;
-    f1.p0 = W(c, t.alpha_exp.off); f1.p1 = W(c, t.inv_beta.off); f1.out = d.FF; f1.ldc = 4 * C;
-    if (fuse) { f1.a_part = d.lnp; f1.a_nparts = C / 64; }
-    else {
-        LAUNCH(c, 2, 0, s, launch_row_stats(x, M, C, C, 1e-5f, d.mean, d.rstd, s));
-        f1.a_mean = d.mean; f1.a_rstd = d.rstd;
-    }
-    RET_IF(run_gemm(c, f1, s));
-    GemmArgs f2;
-    panel_args(c, t.ff2, f2); rows_plain(f2, B, T);
-    f2.a0 = d.FF; f2.lda0 = 4 * C; f2.c0 = 4 * C; f2.res = x; f2.ldr = C; f2.out = x; f2.ldc = C;
-    if (fuse && emit_stats) f2.stats_out = d.lnp;
-    RET_IF(run_gemm(c, f2, s));
-    return 0;
-}
-
-struct FinalOut {   // where the masked velocity goes: out = v * scale (+ res)
-    float* out; int ldc; const float* res; int ldr; float scale;
+// An activation between two launches: c channels per row at p, in the representation of the call's flow (rows of ld floats, or
+// an image with rows of ld halves), and the frame mask of its level when the reference multiplies by it before a conv reads the
+// activation (null: not masked there, or already masked by its producer's own arithmetic in both flows).
+struct Actv {
+    const void* p = nullptr;
+    int ld = 0, c = 0;
+    const float* mask = nullptr;
 };
+static Actv actv(const DecBufs& d, const float* slot, int c, const float* mask = nullptr) {
+    return Actv{slot, d.p16 ? d.ew * c : c, c, mask};
+}
+static _Float16* image(float* slot) { return reinterpret_cast<_Float16*>(slot); }
 
-// Decoder.forward (reference decoder.py:359-426) for evaluation `ev` (row of the precomputed time biases).
-// xin: channels-last state [B*T, ldx] holding x | mu.
-static int decoder_eval_p16(mtts_ctx* c, DecBufs& d, const float* xin, int ev, const FinalOut& fo, hipStream_t s);
-static int decoder_eval(mtts_ctx* c, DecBufs& d, const float* xin, int ev, const FinalOut& fo, hipStream_t s) {
+// The bind helpers below are the only place that knows the two representations and who multiplies by the frame mask: fp32 rows
+// are stored unmasked and the GEMM that reads them multiplies (a_mask); an image goes into the consumer's tiles by LDS-DMA as it
+// is, so its producer stores it masked (out16_mask).  Both use the mask of the activation's own level.
+static void bind_in(const DecBufs& d, GemmArgs& a, int seg, const Actv& x) {       // x as input segment 0 / 1
     if (d.p16) {
-        c->half_now = d.ew == 1;          // 16-bit storage mode: the estimator's images are H16 (kernels.h GemmArgs::half16)
-        const int r = decoder_eval_p16(c, d, xin, ev, fo, s);
-        c->half_now = false;
-        return r;
+        (seg ? a.a16_1 : a.a16_0) = static_cast<const _Float16*>(x.p);
+        (seg ? a.lda16_1 : a.lda16_0) = x.ld;
+    } else {
+        (seg ? a.a1 : a.a0) = static_cast<const float*>(x.p);
+        (seg ? a.lda1 : a.lda0) = x.ld;
+        if (x.mask) a.a_mask = x.mask;
     }
-    const mtts_config& g = c->cfg;
-    const DecW& D = c->dec;
-    const int nl = d.nl, nb = g.dec_n_blocks, B = d.B;
-    const float* tb = d.TB + (size_t)ev * D.tb_total;
-    size_t ri = 0, ti = 0;
-    const float* cur = xin;
-    int cur_ld = d.ldx, cur_c = 2 * g.n_feats;
-    // ---- down path
-    for (int l = 0; l < nl; ++l) {
-        const ResnetW& r = D.res[ri++];
-        RET_IF(resnet_block(c, d, r, cur, cur_ld, cur_c, nullptr, 0, 0, l, tb + r.tb_off, d.skip[l], nb > 0, s));
-        for (int j = 0; j < nb; ++j) RET_IF(transformer_block(c, d, D.tb[ti++], d.skip[l], r.cout, l, true, j + 1 < nb, s));
-        GemmArgs a;
-        panel_args(c, D.down[l], a);
-        taps_centered(a, 3);
-        a.a0 = d.skip[l]; a.lda0 = r.cout; a.c0 = r.cout; a.a_mask = d.mask[l];
-        a.B = B; a.T_in = d.Tl[l];
-        if (l < nl - 1) {   // Downsample1D: Conv1d(k3, s2, p1) (reference decoder.py:66-72)
-            a.T_out = d.Tl[l + 1]; a.in_stride = 2; a.out_T = d.Tl[l + 1];
-            a.out = d.bufA[l + 1];
-        } else {            // last level: Conv1d(k3, p1) (reference decoder.py:252-254)
-            a.T_out = d.Tl[l]; a.out_T = d.Tl[l];
-            a.out = d.bufA[l];
-        }
-        a.ldc = r.cout;
-        RET_IF(run_gemm(c, a, s));
-        cur = a.out; cur_ld = r.cout; cur_c = r.cout;
-    }
-    // ---- mid blocks at the coarsest level
-    const int lm = nl - 1;
-    for (int i = 0; i < g.dec_mid_blocks; ++i) {
-        const ResnetW& r = D.res[ri++];
-        float* dst = (cur == d.bufA[lm]) ? d.bufB[lm] : d.bufA[lm];
-        RET_IF(resnet_block(c, d, r, cur, cur_ld, cur_c, nullptr, 0, 0, lm, tb + r.tb_off, dst, nb > 0, s));
-        for (int j = 0; j < nb; ++j) RET_IF(transformer_block(c, d, D.tb[ti++], dst, r.cout, lm, true, j + 1 < nb, s));
-        cur = dst; cur_ld = r.cout; cur_c = r.cout;
-    }
-    // ---- up path
-    for (int i = 0; i < nl; ++i) {
-        const int l = nl - 1 - i;
-        const ResnetW& r = D.res[ri++];
-        const int cskip = g.dec_channels[l];
-        float* dst = (cur == d.bufA[l]) ? d.bufB[l] : d.bufA[l];
-        RET_IF(resnet_block(c, d, r, cur, cur_ld, cur_c, d.skip[l], cskip, cskip, l, tb + r.tb_off, dst, nb > 0, s));
-        for (int j = 0; j < nb; ++j) RET_IF(transformer_block(c, d, D.tb[ti++], dst, r.cout, l, true, j + 1 < nb, s));
-        if (i < nl - 1) {   // Upsample1D: ConvTranspose1d(k4, s2, p1) as two phase GEMMs (reference decoder.py:146)
-            float* up = d.bufA[l - 1];
-            for (int ph = 0; ph < 2; ++ph) {
-                GemmArgs a;
-                panel_args(c, ph == 0 ? D.up_even[i] : D.up_odd[i], a);
-                a.a0 = dst; a.lda0 = r.cout; a.c0 = r.cout; a.a_mask = d.mask[l];
-                a.B = B; a.T_in = d.Tl[l]; a.T_out = d.Tl[l]; a.in_stride = 1;
-                a.tap_off[0] = ph == 0 ? 0 : 1;
-                a.tap_off[1] = ph == 0 ? -1 : 0;
-                a.out = up; a.ldc = r.cout; a.out_T = d.Tl[l - 1]; a.out_stride = 2; a.out_off = ph;
-                RET_IF(run_gemm(c, a, s));
-            }
-            cur = up;
-        } else {
-            GemmArgs a;
-            panel_args(c, D.up_last, a); rows_plain(a, B, d.Tl[l]); taps_centered(a, 3);
-            a.a0 = dst; a.lda0 = r.cout; a.c0 = r.cout; a.a_mask = d.mask[l];
-            float* o2 = (dst == d.bufA[l]) ? d.bufB[l] : d.bufA[l];
-            a.out = o2; a.ldc = r.cout;
-            RET_IF(run_gemm(c, a, s));
-            cur = o2;
-        }
-        cur_ld = r.cout; cur_c = r.cout;
-    }
-    // ---- final Block1D + 1x1 projection + mask (reference decoder.py:423-426)
-    const int C0 = g.dec_channels[0], T = d.T;
-    GemmArgs a;
-    panel_args(c, D.final_conv, a); rows_plain(a, B, T); taps_centered(a, 3);
-    a.a0 = cur; a.lda0 = cur_ld; a.c0 = C0; a.a_mask = d.mask[0]; a.out = d.Y; a.ldc = C0;
-    RET_IF(run_gemm(c, a, s));
-    LAUNCH(c, 2, 0, s, launch_gn_partial(d.Y, B, T, C0, 8, d.gnp, s, d.nr(0)));
-    GnApplyArgs ga;
-    ga.y = d.Y; ga.partial = d.gnp; ga.gamma = W(c, D.fgn_g.off); ga.beta = W(c, D.fgn_b.off); ga.mask = d.mask[0]; ga.nrows = d.nr(0);
-    if (d.folded) { ga.nextra = d.ne(0); ga.bias_stats = W(c, D.fgn_bs.off); }
-    ga.out = d.Hh; ga.B = B; ga.T = T; ga.C = C0;
-    RET_IF(run_gn_apply(c, ga, s));
-    GemmArgs p;
-    panel_args(c, D.final_proj, p); rows_plain(p, B, T);
-    p.a0 = d.Hh; p.lda0 = C0; p.c0 = C0; p.out_mask = d.mask[0];
-    p.out = fo.out; p.ldc = fo.ldc; p.res = fo.res; p.ldr = fo.ldr; p.out_scale = fo.scale;
-    RET_IF(run_gemm(c, p, s));
+    (seg ? a.c1 : a.c0) = x.c;
+}
+// lscale: residual scale of an image (GemmArgs::out_lscale)
+static void bind_out(const DecBufs& d, GemmArgs& a, float* slot, int c, const float* mask = nullptr, float lscale = 2048.0f) {
+    if (d.p16) { a.out16 = image(slot); a.ld16 = d.ew * c; a.out16_mask = mask; a.out_lscale = lscale; }
+    else { a.out = slot; a.ldc = c; }
+}
+static void bind_out(const DecBufs& d, GnApplyArgs& g, float* slot, int c) {
+    if (d.p16) { g.out16 = image(slot); g.ld16 = d.ew * c; }
+    else g.out = slot;
+}
+static void bind_res(const DecBufs& d, GemmArgs& a, float* slot, int c) {     // residual of the epilogue
+    if (d.p16) { a.res16 = image(slot); a.ldr16 = d.ew * c; }
+    else { a.res = slot; a.ldr = c; }
+}
+static void bind_attn(const DecBufs& d, AttnArgs& at, float* qkv, float* out, int inner) {
+    if (d.p16) { at.qkv16 = image(qkv); at.ld16 = 3 * d.ew * inner; at.out16 = image(out); at.ldo16 = d.ew * inner; }
+    else { at.qkv = qkv; at.out = out; }
+}
+// The ODE state xin [B*T, ldx] = x | mu as the first ResNet's input: it sees x * mask (reference decoder.py:379).  fp32 rows are
+// read in place; the image flow converts them once per evaluation (masked x | mu | zero padding up to the conv's K).
+static int bind_state(mtts_ctx* c, DecBufs& d, const float* xin, Actv& x, hipStream_t s) {
+    const int nf2 = 2 * c->cfg.n_feats;
+    x = Actv{xin, d.ldx, nf2, d.mask[0]};
+    if (!d.p16) return 0;
+    if (c->dec.res[0].conv1.ktap != d.ldx) { set_error("P16 decoder: unexpected ResNet input width"); return -1; }
+    LAUNCH(c, 2, 0, s, launch_to_p16(xin, d.ldx, d.mask[0], d.B * d.T, d.ldx, nf2, image(d.XM), d.ew * d.ldx, 2048.0f, s, c->cur_flag, d.ew == 1, d.ew == 1 && c->bf16));
+    x = actv(d, d.XM, d.ldx);
     return 0;
 }
 
@@ -1095,157 +870,262 @@ static int gn_fuse_rows(const GemmArgs& a, int C, int G, int T) {
     return T >= rows ? rows : 0;
 }
 
-// ---- P16 decoder: the same network with every GEMM on pre-split operands (gemm_p16.hip).  Each producer writes the P16
-// image its consumers read (already multiplied by the frame mask where the reference masks the input): GroupNorm-apply,
-// the GEMM epilogues, and one conversion pass for the ODE state.  fp32 copies exist only where an fp32 consumer remains
-// (GroupNorm statistics of the conv outputs, the residual stream x, the ResNet skip sum).
-static int resnet_block_p16(mtts_ctx* c, DecBufs& d, const ResnetW& r, const _Float16* in0, int c0, const _Float16* in1, int c1,
-                            int lvl, const float* tbias, float* out, hipStream_t s) {
+// A Block1D's conv (input already bound) into the fp32 rows Y, and the GroupNorm statistics of Y: from the conv's epilogue when
+// gn_fuse_rows allows (g.tile_rows != 0 then), else by a pass over Y.  Fills everything of the gn_apply that follows except its
+// time bias, residual and output.
+static int conv_gn_stats(mtts_ctx* c, DecBufs& d, GemmArgs& a, int lvl, const Vec& gamma, const Vec& beta, const Vec& bias_stats,
+                         GnApplyArgs& g, hipStream_t s) {
+    const int B = a.B, T = a.T_out, C = a.N;
+    a.out = d.Y; a.ldc = C;
+    const int fr = gn_fuse_rows(a, C, 8, T);
+    if (fr) { a.gn_stats = d.gns; a.gn_groups = 8; a.gn_nrows = d.nr(lvl); g.tile_stats = d.gns; g.tile_rows = fr; }
+    RET_IF(run_gemm(c, a, s));
+    if (!fr) LAUNCH(c, 2, 0, s, launch_gn_partial(d.Y, B, T, C, 8, d.gnp, s, d.nr(lvl)));
+    g.y = d.Y; g.partial = d.gnp; g.gamma = W(c, gamma.off); g.beta = W(c, beta.off); g.mask = d.mask[lvl]; g.nrows = d.nr(lvl);
+    if (d.folded) { g.nextra = d.ne(lvl); g.bias_stats = W(c, bias_stats.off); }
+    g.B = B; g.T = T; g.C = C;
+    return 0;
+}
+
+// ResnetBlock1D.forward (reference decoder.py:58-63) on channels-last rows; input = up to two channel segments (in1.p null: one).
+// The output is the residual stream of the transformer blocks that follow, d.stream(dst); emit_stats: with its LayerNorm moments.
+static int resnet_block(mtts_ctx* c, DecBufs& d, const ResnetW& r, const Actv& in0, const Actv& in1, int lvl, const float* tbias,
+                        float* dst, bool emit_stats, hipStream_t s) {
     const int B = d.B, T = d.Tl[lvl], C = r.cout;
-    const float* mask = d.mask[lvl];
+    float* x = d.stream(dst);
     GemmArgs a;
     panel_args(c, r.conv1, a); rows_plain(a, B, T); taps_centered(a, 3);
-    a.a16_0 = in0; a.lda16_0 = d.ew * c0; a.c0 = c0; a.a16_1 = in1; a.lda16_1 = d.ew * c1; a.c1 = c1;
-    a.out = d.Y; a.ldc = C;
-    const int fr1 = gn_fuse_rows(a, C, 8, T);
-    if (fr1) { a.gn_stats = d.gns; a.gn_groups = 8; a.gn_nrows = d.nr(lvl); }
-    RET_IF(run_gemm(c, a, s));
-    if (!fr1) LAUNCH(c, 2, 0, s, launch_gn_partial(d.Y, B, T, C, 8, d.gnp, s, d.nr(lvl)));
+    bind_in(d, a, 0, in0);
+    if (in1.p) bind_in(d, a, 1, in1);
     GnApplyArgs g1;
-    if (fr1) { g1.tile_stats = d.gns; g1.tile_rows = fr1; }
-    g1.y = d.Y; g1.partial = d.gnp; g1.gamma = W(c, r.gn1_g.off); g1.beta = W(c, r.gn1_b.off); g1.mask = mask; g1.nrows = d.nr(lvl);
-    if (d.folded) { g1.nextra = d.ne(lvl); g1.bias_stats = W(c, r.gn1_bs.off); }
-    g1.chbias = tbias; g1.out16 = d.H16; g1.ld16 = d.ew * C; g1.B = B; g1.T = T; g1.C = C;      // already masked
+    RET_IF(conv_gn_stats(c, d, a, lvl, r.gn1_g, r.gn1_b, r.gn1_bs, g1, s));
+    g1.chbias = tbias;
+    bind_out(d, g1, d.H, C);
     RET_IF(run_gn_apply(c, g1, s));
     GemmArgs b;
     panel_args(c, r.conv2, b); rows_plain(b, B, T); taps_centered(b, 3);
-    b.a16_0 = d.H16; b.lda16_0 = d.ew * C; b.c0 = C; b.out = d.Y; b.ldc = C;
-    const int fr2 = gn_fuse_rows(b, C, 8, T);
-    if (fr2) { b.gn_stats = d.gns; b.gn_groups = 8; b.gn_nrows = d.nr(lvl); }
-    RET_IF(run_gemm(c, b, s));
-    if (!fr2) LAUNCH(c, 2, 0, s, launch_gn_partial(d.Y, B, T, C, 8, d.gnp, s, d.nr(lvl)));
+    bind_in(d, b, 0, actv(d, d.H, C));
+    GnApplyArgs g2;
+    RET_IF(conv_gn_stats(c, d, b, lvl, r.gn2_g, r.gn2_b, r.gn2_bs, g2, s));
     GemmArgs rc;
     panel_args(c, r.res, rc); rows_plain(rc, B, T);
-    rc.a16_0 = in0; rc.lda16_0 = d.ew * c0; rc.c0 = c0; rc.a16_1 = in1; rc.lda16_1 = d.ew * c1; rc.c1 = c1;
-    (void)out;                                                        // no fp32 copy: x lives on as its image only
+    bind_in(d, rc, 0, in0);
+    if (in1.p) bind_in(d, rc, 1, in1);
     static const bool tail_on = [] { const char* e = getenv("MTTS_GN_TAIL"); return !(e && e[0] == '0'); }();   // A/B runs
-    if (tail_on && fr2 && T >= 2 * gemm_p16_wave_rows(rc)) {      // a workgroup's rows in at most two utterances
+    if (tail_on && g2.tile_rows && T >= 2 * gemm_p16_wave_rows(rc)) {      // a workgroup's rows in at most two utterances
         // The 1x1 residual conv finishes the block: its epilogue adds Mish(GroupNorm(conv2 output)) * mask from the tile
         // statistics conv2 left, and writes x's image + LayerNorm moments -- no gn_apply pass, no residual round trip.
-        rc.gnr_y = d.Y; rc.gnr_stats = d.gns; rc.gnr_tile_rows = fr2; rc.gnr_groups = 8;
-        rc.gnr_gamma = W(c, r.gn2_g.off); rc.gnr_beta = W(c, r.gn2_b.off); rc.gnr_mask = mask;
-        if (d.folded) { rc.gnr_nextra = d.ne(lvl); rc.gnr_bias_stats = W(c, r.gn2_bs.off); }
-        rc.out16 = d.X16; rc.ld16 = d.ew * C; rc.stats_out = d.lnp;
+        rc.gnr_y = d.Y; rc.gnr_stats = d.gns; rc.gnr_tile_rows = g2.tile_rows; rc.gnr_groups = 8;
+        rc.gnr_gamma = g2.gamma; rc.gnr_beta = g2.beta; rc.gnr_mask = g2.mask;
+        rc.gnr_nextra = g2.nextra; rc.gnr_bias_stats = g2.bias_stats;
+        bind_out(d, rc, x, C);
+        rc.stats_out = d.lnp;
         RET_IF(run_gemm(c, rc, s));
         return 0;
     }
     rc.out = d.Rr; rc.ldc = C;
     RET_IF(run_gemm(c, rc, s));
-    GnApplyArgs g2;
-    if (fr2) { g2.tile_stats = d.gns; g2.tile_rows = fr2; }
-    g2.y = d.Y; g2.partial = d.gnp; g2.gamma = W(c, r.gn2_g.off); g2.beta = W(c, r.gn2_b.off); g2.mask = mask; g2.nrows = d.nr(lvl);
-    if (d.folded) { g2.nextra = d.ne(lvl); g2.bias_stats = W(c, r.gn2_bs.off); }
-    g2.res = d.Rr; g2.ldr = C; g2.B = B; g2.T = T; g2.C = C;
-    g2.stats_out = d.lnp; g2.out16 = d.X16; g2.ld16 = d.ew * C;          // unmasked: the first transformer block's LayerNorm input
+    g2.res = d.Rr; g2.ldr = C;
+    bind_out(d, g2, x, C);
+    if (emit_stats && (C % 64) == 0) g2.stats_out = d.lnp;       // for the first transformer block's LayerNorm
     RET_IF(run_gn_apply(c, g2, s));
     return 0;
 }
 
-static int decoder_eval_p16(mtts_ctx* c, DecBufs& d, const float* xin, int ev, const FinalOut& fo, hipStream_t s) {
+// BasicTransformerBlock.forward (reference transformer.py:230-303, self-attention only), in place on the residual stream
+// x = d.stream(dst) [B*T, C].  LayerNorm statistics travel with the data: the launch that writes x (the ResNet block's last one,
+// the attention out-projection, the second FF projection) leaves per-row partial moments of its 64-column slices behind
+// (stats_out) and the next projection merges them in its prologue.  A width that is not a multiple of 64 has no such slices:
+// the row_stats kernel runs in front of each LayerNorm'd projection instead.
+// emit_stats: another block of the run follows; the last block's last launch leaves the run's result in dst.
+static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, int C, int lvl, bool emit_stats, float* dst, hipStream_t s) {
+    const mtts_config& g = c->cfg;
+    const int B = d.B, T = d.Tl[lvl], M = B * T, inner = g.dec_heads * g.dec_head_dim;
+    const bool fuse = (C % 64) == 0;
+    float* x = d.stream(dst);
+    auto layernorm_in = [&](GemmArgs& p) -> int {       // p reads LayerNorm(x) (the affine is folded into its panel)
+        bind_in(d, p, 0, actv(d, x, C));
+        if (fuse) { p.a_part = d.lnp; p.a_nparts = C / 64; return 0; }
+        LAUNCH(c, 2, 0, s, launch_row_stats(x, M, C, C, 1e-5f, d.mean, d.rstd, s));
+        p.a_mean = d.mean; p.a_rstd = d.rstd;
+        return 0;
+    };
+    // the row-local part as one launch (tblock_chain.hip) when the stream was packed and the batch is large enough that a
+    // workgroup per QB rows fills the chip: every workgroup streams ALL of the chain's weights (~7 MB at width 384), which
+    // only pays when their cost is shared by many rows per CU
+    static const int chain_only = [] { const char* e = getenv("MTTS_CHAIN_ONLY"); return !e ? 0 : (e[0] == 'f' ? 1 : 2); }();   // diagnostic
+    const bool chain = t.chain_frags > 0 && d.p16 && !c->half_now && M >= c->chain_min_rows && (emit_stats ? t.chain_nqkv > 0 : true) &&
+                       (chain_only == 0 || (chain_only == 1) == emit_stats);
+    if (!d.qkv_ready) {
+        GemmArgs q;
+        panel_args(c, t.qkv, q); rows_plain(q, B, T);
+        RET_IF(layernorm_in(q));
+        bind_out(d, q, d.QKV, 3 * inner, nullptr, 1.0f);      // (the attention kernel reads unscaled residuals)
+        RET_IF(run_gemm(c, q, s));
+    }
+    d.qkv_ready = false;
+    AttnArgs at;
+    bind_attn(d, at, d.QKV, d.ATT, inner);
+    at.mask = d.kb(lvl); at.B = B; at.T = T; at.H = g.dec_heads; at.D = g.dec_head_dim;
+    at.scale = 1.0f / sqrtf((float)g.dec_head_dim); at.mask_mode = 0; at.klen = d.nr(lvl); at.fast16 = c->fast16;
+    RET_IF(run_attn(c, at, s));
+    // below that row count: the pair form -- two workgroups of one XCD per 48-row tile, each streaming half of the FeedForward
+    // and of the q|k|v passes -- while all of them (and the prefetchers) are resident at once
+    const int tiles48 = (M + 47) / 48;
+    static const int pair_min = [] { const char* e = getenv("MTTS_CHAIN_PAIR_MIN_ROWS"); return e ? atoi(e) : 3000; }();      // (3864 rows: -0.3..0.5 ms per step, 2576 rows: +0.3; profiles/r03_pair_ab.log)
+    const bool pair = !chain && c->pair_on && t.chain_pair_frags > 0 && d.p16 && !c->half_now && d.pair_flag && M >= pair_min &&
+                      16 * ((tiles48 + 7) / 8) + 16 <= 256 && (emit_stats ? t.chain_nqkv > 0 : true);
+    if (chain || pair) {                  // (image flow, P16: rows of 2 halves per channel)
+        ChainArgs a;
+        a.M = M; a.C = C; a.inner = inner;
+        a.att16 = image(d.ATT); a.ld_att = 2 * inner;
+        a.x16 = image(x); a.ld_x = 2 * C;
+        a.wstream = reinterpret_cast<const _Float16*>(W(c, t.chain)); a.stream_frags = t.chain_frags;
+        a.consts = W(c, t.chain_consts);
+        a.ld_out = 2 * C;
+        if (emit_stats) {                 // another block follows: its q|k|v leaves this launch, x stays unmasked
+            const TBlockW& nx = c->dec.tb[t.next];
+            a.b_qkv = W(c, nx.qkv.b); a.wsum_qkv = W(c, nx.qkv.wsum); a.n_qkv = nx.qkv.N;
+            a.qkv16 = image(d.QKV); a.ld_qkv = 2 * nx.qkv.N;
+            a.x_out = image(x);
+            d.qkv_ready = true;
+        } else { a.x_out = image(dst); a.x_out_mask = d.mask[lvl]; }
+        a.ch = t.chain_ch;
+        { int pf_unused = 0; chain_plan(M, a.ch, c->chain_qb, &a.qb, &pf_unused); }
+        if (pair) {
+            a.pair = 1; a.qb = 48;
+            a.wstream = reinterpret_cast<const _Float16*>(W(c, t.chain_pair)); a.stream_frags = t.chain_pair_frags;
+            a.pair_part = d.FF;              // (the tiled path's hidden image: unused by a chain launch)
+            a.pair_flag = d.pair_flag;
+            a.pair_epoch = ++c->pair_epoch;
+            if (c->pair_epoch == 0) a.pair_epoch = ++c->pair_epoch;
+        }
+#ifdef MTTS_CHAIN_VERIFY
+        RET_IF(run_chain_verified(c, a, image(d.FF), s));
+#else
+        RET_IF(run_chain(c, a, s));
+#endif
+        return 0;
+    }
+    GemmArgs o;
+    panel_args(c, t.out, o); rows_plain(o, B, T);
+    bind_in(d, o, 0, actv(d, d.ATT, inner));
+    bind_res(d, o, x, C);
+    bind_out(d, o, x, C);
+    if (fuse) o.stats_out = d.lnp;
+    RET_IF(run_gemm(c, o, s));
+    GemmArgs f1;
+    panel_args(c, t.ff1, f1); rows_plain(f1, B, T);
+    RET_IF(layernorm_in(f1));
+    f1.act = ACT_SNAKE; f1.p0 = W(c, t.alpha_exp.off); f1.p1 = W(c, t.inv_beta.off);
+    bind_out(d, f1, d.FF, 4 * C);
+    RET_IF(run_gemm(c, f1, s));
+    GemmArgs f2;
+    panel_args(c, t.ff2, f2); rows_plain(f2, B, T);
+    bind_in(d, f2, 0, actv(d, d.FF, 4 * C));
+    bind_res(d, f2, x, C);
+    if (emit_stats) {
+        bind_out(d, f2, x, C);
+        if (fuse) f2.stats_out = d.lnp;
+    } else bind_out(d, f2, dst, C, d.mask[lvl]);
+    RET_IF(run_gemm(c, f2, s));
+    return 0;
+}
+
+struct FinalOut {   // where the masked velocity goes: out = v * scale (+ res)
+    float* out; int ldc; const float* res; int ldr; float scale;
+};
+
+// Decoder.forward (reference decoder.py:359-426) for evaluation `ev` (row of the precomputed time biases).
+// xin: channels-last state [B*T, ldx] holding x | mu.
+static int unet_eval(mtts_ctx* c, DecBufs& d, const float* xin, int ev, const FinalOut& fo, hipStream_t s) {
     const mtts_config& g = c->cfg;
     const DecW& D = c->dec;
     const int nl = d.nl, nb = g.dec_n_blocks, B = d.B;
     const float* tb = d.TB + (size_t)ev * D.tb_total;
     size_t ri = 0, ti = 0;
-    // masked x | mu | zero padding as a P16 image (reference decoder.py:379: the first ResNet sees x * mask)
-    LAUNCH(c, 2, 0, s, launch_to_p16(xin, d.ldx, d.mask[0], B * d.T, d.ldx, 2 * g.n_feats, d.XM16, d.ew * d.ldx, 2048.0f, s, c->cur_flag, d.ew == 1, d.ew == 1 && c->bf16));
-    const _Float16* cur = d.XM16;
-    int cur_c = d.ldx;
+    Actv cur;
+    RET_IF(bind_state(c, d, xin, cur, s));
+    auto other = [&](const Actv& x, int l) { return x.p == d.bufA[l] ? d.bufB[l] : d.bufA[l]; };
     // ---- down path
     for (int l = 0; l < nl; ++l) {
         const ResnetW& r = D.res[ri++];
-        if (r.conv1.ktap != cur_c) { set_error("P16 decoder: unexpected ResNet input width"); return -1; }
-        RET_IF(resnet_block_p16(c, d, r, cur, cur_c, nullptr, 0, l, tb + r.tb_off, d.skip[l], s));
-        for (int j = 0; j < nb; ++j)
-            RET_IF(transformer_block(c, d, D.tb[ti++], d.skip[l], r.cout, l, true, j + 1 < nb, s, d.S16[l]));
+        RET_IF(resnet_block(c, d, r, cur, Actv(), l, tb + r.tb_off, d.skip[l], nb > 0, s));
+        for (int j = 0; j < nb; ++j) RET_IF(transformer_block(c, d, D.tb[ti++], r.cout, l, j + 1 < nb, d.skip[l], s));
         GemmArgs a;
         panel_args(c, D.down[l], a);
         taps_centered(a, 3);
-        a.a16_0 = d.S16[l]; a.lda16_0 = d.ew * r.cout; a.c0 = r.cout;
+        bind_in(d, a, 0, actv(d, d.skip[l], r.cout, d.mask[l]));
         a.B = B; a.T_in = d.Tl[l];
         const int lo = l < nl - 1 ? l + 1 : l;
-        if (l < nl - 1) { a.T_out = d.Tl[l + 1]; a.in_stride = 2; a.out_T = d.Tl[l + 1]; }   // Downsample1D (reference decoder.py:66-72)
-        else { a.T_out = d.Tl[l]; a.out_T = d.Tl[l]; }                                          // last level: Conv1d(k3, p1)
-        a.out16 = d.A16[lo]; a.ld16 = d.ew * r.cout; a.out16_mask = d.mask[lo];
+        if (l < nl - 1) { a.T_out = d.Tl[lo]; a.in_stride = 2; a.out_T = d.Tl[lo]; }      // Downsample1D: Conv1d(k3, s2, p1) (reference decoder.py:66-72)
+        else { a.T_out = d.Tl[l]; a.out_T = d.Tl[l]; }                                    // last level: Conv1d(k3, p1) (reference decoder.py:252-254)
+        bind_out(d, a, d.bufA[lo], r.cout, d.mask[lo]);
         RET_IF(run_gemm(c, a, s));
-        cur = d.A16[lo]; cur_c = r.cout;
+        cur = actv(d, d.bufA[lo], r.cout, d.mask[lo]);
     }
     // ---- mid blocks at the coarsest level
     const int lm = nl - 1;
-    float* xbuf = d.bufA[lm];
-    _Float16* x16 = d.B16[lm];
     for (int i = 0; i < g.dec_mid_blocks; ++i) {
         const ResnetW& r = D.res[ri++];
-        RET_IF(resnet_block_p16(c, d, r, cur, cur_c, nullptr, 0, lm, tb + r.tb_off, xbuf, s));
-        for (int j = 0; j < nb; ++j) RET_IF(transformer_block(c, d, D.tb[ti++], xbuf, r.cout, lm, true, j + 1 < nb, s, x16));
-        cur = x16; cur_c = r.cout;
-        x16 = (x16 == d.B16[lm]) ? d.A16[lm] : d.B16[lm];
+        float* dst = other(cur, lm);
+        RET_IF(resnet_block(c, d, r, cur, Actv(), lm, tb + r.tb_off, dst, nb > 0, s));
+        for (int j = 0; j < nb; ++j) RET_IF(transformer_block(c, d, D.tb[ti++], r.cout, lm, j + 1 < nb, dst, s));
+        cur = actv(d, dst, r.cout, d.mask[lm]);
     }
     // ---- up path
     for (int i = 0; i < nl; ++i) {
         const int l = nl - 1 - i;
         const ResnetW& r = D.res[ri++];
-        const int cskip = g.dec_channels[l];
-        float* xb = d.bufA[l];
-        _Float16* dst16 = (cur == d.B16[l]) ? d.A16[l] : d.B16[l];
-        RET_IF(resnet_block_p16(c, d, r, cur, cur_c, d.S16[l], cskip, l, tb + r.tb_off, xb, s));
-        for (int j = 0; j < nb; ++j) RET_IF(transformer_block(c, d, D.tb[ti++], xb, r.cout, l, true, j + 1 < nb, s, dst16));
+        float* dst = other(cur, l);
+        RET_IF(resnet_block(c, d, r, cur, actv(d, d.skip[l], g.dec_channels[l], d.mask[l]), l, tb + r.tb_off, dst, nb > 0, s));
+        for (int j = 0; j < nb; ++j) RET_IF(transformer_block(c, d, D.tb[ti++], r.cout, l, j + 1 < nb, dst, s));
+        cur = actv(d, dst, r.cout, d.mask[l]);
         if (i < nl - 1) {   // Upsample1D: ConvTranspose1d(k4, s2, p1) as two phase GEMMs (reference decoder.py:146)
-            _Float16* up16 = d.A16[l - 1];
             for (int ph = 0; ph < 2; ++ph) {
                 GemmArgs a;
                 panel_args(c, ph == 0 ? D.up_even[i] : D.up_odd[i], a);
-                a.a16_0 = dst16; a.lda16_0 = d.ew * r.cout; a.c0 = r.cout;
+                bind_in(d, a, 0, cur);
                 a.B = B; a.T_in = d.Tl[l]; a.T_out = d.Tl[l]; a.in_stride = 1;
                 a.tap_off[0] = ph == 0 ? 0 : 1;
                 a.tap_off[1] = ph == 0 ? -1 : 0;
-                a.out16 = up16; a.ld16 = d.ew * r.cout; a.out16_mask = d.mask[l - 1];
+                bind_out(d, a, d.bufA[l - 1], r.cout, d.mask[l - 1]);
                 a.out_T = d.Tl[l - 1]; a.out_stride = 2; a.out_off = ph;
                 RET_IF(run_gemm(c, a, s));
             }
-            cur = up16;
+            cur = actv(d, d.bufA[l - 1], r.cout, d.mask[l - 1]);
         } else {
             GemmArgs a;
             panel_args(c, D.up_last, a); rows_plain(a, B, d.Tl[l]); taps_centered(a, 3);
-            a.a16_0 = dst16; a.lda16_0 = d.ew * r.cout; a.c0 = r.cout;
-            _Float16* o16 = (dst16 == d.A16[l]) ? d.B16[l] : d.A16[l];
-            a.out16 = o16; a.ld16 = d.ew * r.cout; a.out16_mask = d.mask[l];
+            bind_in(d, a, 0, cur);
+            float* o2 = other(cur, l);
+            bind_out(d, a, o2, r.cout, d.mask[l]);
             RET_IF(run_gemm(c, a, s));
-            cur = o16;
+            cur = actv(d, o2, r.cout, d.mask[l]);
         }
-        cur_c = r.cout;
     }
     // ---- final Block1D + 1x1 projection + mask (reference decoder.py:423-426)
     const int C0 = g.dec_channels[0], T = d.T;
     GemmArgs a;
     panel_args(c, D.final_conv, a); rows_plain(a, B, T); taps_centered(a, 3);
-    a.a16_0 = cur; a.lda16_0 = d.ew * C0; a.c0 = C0; a.out = d.Y; a.ldc = C0;
-    const int frf = gn_fuse_rows(a, C0, 8, T);
-    if (frf) { a.gn_stats = d.gns; a.gn_groups = 8; a.gn_nrows = d.nr(0); }
-    RET_IF(run_gemm(c, a, s));
-    if (!frf) LAUNCH(c, 2, 0, s, launch_gn_partial(d.Y, B, T, C0, 8, d.gnp, s, d.nr(0)));
+    bind_in(d, a, 0, cur);
     GnApplyArgs ga;
-    if (frf) { ga.tile_stats = d.gns; ga.tile_rows = frf; }
-    ga.y = d.Y; ga.partial = d.gnp; ga.gamma = W(c, D.fgn_g.off); ga.beta = W(c, D.fgn_b.off); ga.mask = d.mask[0]; ga.nrows = d.nr(0);
-    if (d.folded) { ga.nextra = d.ne(0); ga.bias_stats = W(c, D.fgn_bs.off); }
-    ga.out16 = d.H16; ga.ld16 = d.ew * C0; ga.B = B; ga.T = T; ga.C = C0;
+    RET_IF(conv_gn_stats(c, d, a, 0, D.fgn_g, D.fgn_b, D.fgn_bs, ga, s));
+    bind_out(d, ga, d.H, C0);
     RET_IF(run_gn_apply(c, ga, s));
     GemmArgs p;
     panel_args(c, D.final_proj, p); rows_plain(p, B, T);
-    p.a16_0 = d.H16; p.lda16_0 = d.ew * C0; p.c0 = C0; p.out_mask = d.mask[0];
+    bind_in(d, p, 0, actv(d, d.H, C0));
+    p.out_mask = d.mask[0];
     p.out = fo.out; p.ldc = fo.ldc; p.res = fo.res; p.ldr = fo.ldr; p.out_scale = fo.scale;
     RET_IF(run_gemm(c, p, s));
     return 0;
+}
+static int decoder_eval(mtts_ctx* c, DecBufs& d, const float* xin, int ev, const FinalOut& fo, hipStream_t s) {
+    c->half_now = d.ew == 1;          // 16-bit storage mode: the estimator's images are H16 (kernels.h GemmArgs::half16)
+    const int r = unet_eval(c, d, xin, ev, fo, s);
+    c->half_now = false;
+    return r;
 }
 
 // Level masks and frame tables of one call.  y_len == null: any float mask [B, T] (reference decoder.py:390 mask[:, :, ::2]),
