@@ -210,6 +210,16 @@ int mtts_gemm_p16(const float* d_a, int lda, int B, int T_in, int C, int ntaps, 
                   const float* d_res, int ldr, const float* d_out_mask, float out_scale, float* d_out, int ldc,
                   float* d_out16_f32, float out_lscale, float* d_stats_out, int force_bm, void* d_scratch, void* stream);
 
+/* One-launch Block1D (csrc/resnet_conv.hip): Conv1d(C -> N, k3, p1) -> GroupNorm(8) -> Mish -> * mask [-> + chbias -> * mask] on
+ * channels-last rows x [B*T, C] (converted to a P16 image in d_scratch), result decoded from its P16 image into d_out [B*T, N].
+ * N = 384, 65 <= T <= 384, C % 32 == 0; c1 > 0 reads the last c1 channels as a second input segment.  d_nrows / d_nextra /
+ * d_bias_stats as the model's frame tables (null: all T rows, no closed-form rows).  d_w is the torch Conv1d weight [N, C, 3],
+ * d_wpacked mtts_gemm_packed_bytes(N, C, 3) bytes.  Replaces Block1D of the reference decoder (decoder.py:32-45). */
+int64_t mtts_conv_gn_scratch_bytes(int B, int T, int C, int N);
+int mtts_conv_gn(const float* d_x, int B, int T, int C, int c1, const float* d_w, void* d_wpacked, const float* d_bias, int N,
+                 const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias, const int* d_nrows,
+                 const int* d_nextra, const float* d_bias_stats, float eps, float* d_out, void* d_scratch, void* stream);
+
 /* Self-attention over packed [B*T, 3*H*D] q|k|v rows -> [B*T, H*D].  mask_mode 0: additive float key bias
  * (diffusers semantics, reference transformer.py:253-258); 1: boolean query*key mask (reference
  * text_encoder.py:228-235,306).  d_mask [B,T] float 0/1. */

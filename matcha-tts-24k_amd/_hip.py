@@ -19,7 +19,7 @@ from .hparams import PathHParams
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = Path(os.environ["MTTS_HIP_LIB"]) if os.environ.get("MTTS_HIP_LIB") else HERE / "libmtts_hip.so"   # override: A/B of two builds
-SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "norm_glue.hip", "vocos.hip", "model.hip"]
+SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "model.hip"]
 HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", HERE.parent / "include" / "mtts.h"]
 SOLVERS = {"euler": 0, "midpoint": 1, "rk4": 2}
 
@@ -147,6 +147,8 @@ def load() -> C.CDLL:
         "mtts_gemm_packed_bytes": (i64, [i32, i32, i32]),
         "mtts_attention_p16": (i32, [vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp]),
         "mtts_gemm_p16_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
+        "mtts_conv_gn_scratch_bytes": (i64, [i32, i32, i32, i32]),
+        "mtts_conv_gn": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
         "mtts_gemm_p16": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp,
                                 i32, vp, f32, vp, i32, vp, f32, vp, i32, vp, vp]),
         "mtts_gemm_f32": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp,
@@ -575,6 +577,19 @@ def gemm_p16(a, w, bias=None, *, B, T_in, T_out=None, tap_off=None, in_stride=1,
                             res.shape[1] if res is not None else 0, ptr(out_mask), float(out_scale), ptr(out), N,
                             ptr(out16), float(lscale), ptr(stats), force_bm, scratch.data_ptr(), stream_ptr()))
     return {"out": out, "out16": out16, "stats": stats}
+
+
+def conv_gn(x, w, bias, gamma, beta, mask, *, B, T, c1=0, chbias=None, nrows=None, nextra=None, bias_stats=None, eps=1e-5):
+    """One-launch Block1D (csrc/resnet_conv.hip): x [B*T, C] fp32, w Conv1d [N, C, 3]; returns Mish(GroupNorm8(conv(x))) * mask
+    (+ chbias, * mask) as fp32 [B*T, N], decoded from the P16 image the kernel writes."""
+    lib = load()
+    N, Cc = w.shape[0], w.shape[1]
+    packed = torch.empty(lib.mtts_gemm_packed_bytes(N, Cc, 3), dtype=torch.uint8, device=x.device)
+    scratch = torch.empty(lib.mtts_conv_gn_scratch_bytes(B, T, Cc, N), dtype=torch.uint8, device=x.device)
+    out = torch.empty(B * T, N, dtype=torch.float32, device=x.device)
+    check(lib.mtts_conv_gn(ptr(x), B, T, Cc, c1, ptr(w.contiguous()), packed.data_ptr(), ptr(bias), N, ptr(gamma), ptr(beta), ptr(mask),
+                           ptr(chbias), ptr(nrows), ptr(nextra), ptr(bias_stats), float(eps), ptr(out), scratch.data_ptr(), stream_ptr()))
+    return out
 
 
 def _host(t):

@@ -170,6 +170,39 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 static inline double attn_flops(const AttnArgs& a) { return 4.0 * double(a.B) * a.H * double(a.T) * a.T * a.D; }
 static inline double attn_bytes(const AttnArgs& a) { return 4.0 * double(a.B) * a.T * 4.0 * a.H * a.D; }
 
+// ---- a Block1D of a ResNet block as one launch (resnet_conv.hip): Conv1d(k3, p1) over P16 images -> GroupNorm(8) -> Mish -> mask
+// [-> + chbias -> mask], written as a P16 image; one workgroup per (utterance, GroupNorm group).
+constexpr int CONV_GN_CPG = 48;          // channels per group the kernel is built for (width 384)
+constexpr int CONV_GN_MIN_ROWS = 65;     // rows per utterance it serves: below, the tiled launches are at least as good
+constexpr int CONV_GN_SPLIT_ROWS = 192;  //   ... up to here two K-splitting wave sets on 4 x 48 rows, beyond it eight waves on 8 x 48 rows
+constexpr int CONV_GN_MAX_ROWS = 384;    //   ... its row capacity
+struct ConvGnArgs {
+    const _Float16* a16_0 = nullptr;  // conv input: up to two channel segments of P16 images, rows [B*T], already masked
+    const _Float16* a16_1 = nullptr;
+    int lda16_0 = 0, lda16_1 = 0;     // row strides in halves
+    int c0 = 0, c1 = 0;               // channels per segment (% 32 == 0); the panel's K per tap is c0 + c1
+    const void* w16 = nullptr;        // P16 planes of the conv panel [Np][3 * (c0 + c1)], as GemmArgs::w16
+    const float* bias = nullptr;      // [N]
+    int B = 0, T = 0, N = 0;          // N = 8 * CONV_GN_CPG output channels
+    const float* gamma = nullptr; const float* beta = nullptr;
+    const float* mask = nullptr;      // [B*T]
+    const float* chbias = nullptr;    // [N] time-embedding bias or null
+    const int* nrows = nullptr;       // as GnApplyArgs
+    const int* nextra = nullptr;
+    const float* bias_stats = nullptr;
+    float eps = 1e-5f;
+    _Float16* out16 = nullptr; int ld16 = 0;
+    const float* out16_mask = nullptr;
+    unsigned int* range_flag = nullptr;
+};
+bool conv_gn_supported(int T, int N);
+hipError_t launch_conv_gn(const ConvGnArgs& a, hipStream_t s);
+static inline double conv_gn_flops(const ConvGnArgs& a) { return 2.0 * double(a.B) * a.T * a.N * 3.0 * (a.c0 + a.c1); }
+static inline double conv_gn_bytes(const ConvGnArgs& a) {
+    const double M = double(a.B) * a.T, kin = a.c0 + a.c1;
+    return 4.0 * (M * kin + double(a.N) * 3.0 * kin + M * a.N);
+}
+
 // ---- transformer-block chain (tblock_chain.hip): the row-local part of a BasicTransformerBlock as ONE launch.
 // Behind the attention everything up to the next attention is row-local (reference transformer.py:261-301): out-projection +
 // residual, LayerNorm, FeedForward (Linear - SnakeBeta - Linear) + residual and, when another block follows, its LayerNorm'd

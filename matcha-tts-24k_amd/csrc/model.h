@@ -102,6 +102,8 @@ struct mtts_ctx {
     bool chain_on = true;         // transformer blocks' row-local part as one launch (tblock_chain.hip; MTTS_CHAIN=0 at mtts_create disables)
     int chain_ch = 256;           // hidden chunk of the chain's FeedForward at width 384 (MTTS_CHAIN_CH at mtts_create: 128 / 256)
     int chain_qb = 0;             // rows per workgroup (MTTS_CHAIN_QB at mtts_create; 0 = by shape)
+    int resnet_fuse = 3;          // Block1D as one conv + GroupNorm + Mish launch where it applies (resnet_conv.hip): bit 0 the first Block1D of a ResNet block and the decoder's final one, bit 1 the second, bit 2 lifts the batch gate (MTTS_RESNET_FUSE at mtts_create; 0 = the tiled launches)
+    int resnet_fuse_rows = mtts::CONV_GN_MAX_ROWS;   // ... up to this many rows per utterance (MTTS_RESNET_FUSE_ROWS at mtts_create: A/B runs)
     bool pair_on = true;          // pair form of the chain launch for levels below chain_min_rows (MTTS_CHAIN_PAIR=0 at mtts_create disables)
     unsigned int pair_epoch = 0;  // flag value of the latest pair launch (unique per launch)
     int chain_min_rows = 5761;    // (= where the pair form's residency bound, 120 tiles of 48 rows, ends) estimator rows (B * T of a level) from which the chain replaces the four GEMM launches (MTTS_CHAIN_MIN_ROWS):

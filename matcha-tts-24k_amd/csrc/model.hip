@@ -291,6 +291,13 @@ static int run_gn_apply(mtts_ctx* c, const GnApplyArgs& a0, hipStream_t s) {
     return 0;
 }
 // The sticky range flag of a call = the first word of its workspace, cleared here (include/mtts.h "range guard").
+static int run_conv_gn(mtts_ctx* c, const ConvGnArgs& a0, hipStream_t s) {
+    ConvGnArgs a = a0;
+    a.range_flag = c->cur_flag;
+    LAUNCHB(c, 0, conv_gn_flops(a), conv_gn_bytes(a), s, launch_conv_gn(a, s));
+    return 0;
+}
+
 static int begin_call(mtts_ctx* c, void* d_ws, hipStream_t s) {
     c->cur_flag = static_cast<unsigned int*>(d_ws);
     // a kernel, not hipMemsetAsync: a captured memset node of one HIP graph was seen to write another instantiated graph's
@@ -887,6 +894,31 @@ static int conv_gn_stats(mtts_ctx* c, DecBufs& d, GemmArgs& a, int lvl, const Ve
     return 0;
 }
 
+// Where the one-launch Block1D pays (measured): its grid is 8 B workgroups of one per CU, so it needs a batch
+// that fills the 256 CUs once -- at B = 64 (two rounds) the tiled launches win by 0.5-1.0 ms per step -- and not much less: the
+// short form (<= 192 rows) from half the chip (B = 16: -0.35 ms), the long form only near a full chip (B = 16: +0.35 ms, B = 32:
+// -0.5 ms).  Bit 2 of MTTS_RESNET_FUSE lifts the batch gate (tests run small batches).
+static bool block1d_fusable(const mtts_ctx* c, const DecBufs& d, int T, int C) {
+    if (!d.p16 || c->half_now || c->fast16 || !conv_gn_supported(T, C) || T > c->resnet_fuse_rows) return false;
+    if (c->resnet_fuse & 4) return true;
+    const int wgs = 8 * d.B;
+    return wgs <= 256 && wgs >= (T <= CONV_GN_SPLIT_ROWS ? 128 : 192);
+}
+
+// A Block1D as one launch (resnet_conv.hip): the conv `a` (input and panel already bound) -> GroupNorm -> Mish -> mask [-> + chbias
+// -> mask] into the image slot `dst`.
+static int block1d_fused(mtts_ctx* c, DecBufs& d, const GemmArgs& a, int lvl, const Vec& gamma, const Vec& beta, const Vec& bias_stats,
+                         const float* chbias, float* dst, hipStream_t s) {
+    ConvGnArgs f;
+    f.a16_0 = a.a16_0; f.lda16_0 = a.lda16_0; f.c0 = a.c0;
+    f.a16_1 = a.a16_1; f.lda16_1 = a.lda16_1; f.c1 = a.c1;
+    f.w16 = a.w16; f.bias = a.bias; f.B = a.B; f.T = a.T_out; f.N = a.N;
+    f.gamma = W(c, gamma.off); f.beta = W(c, beta.off); f.mask = d.mask[lvl]; f.chbias = chbias; f.nrows = d.nr(lvl);
+    if (d.folded) { f.nextra = d.ne(lvl); f.bias_stats = W(c, bias_stats.off); }
+    f.out16 = image(dst); f.ld16 = d.ew * a.N;
+    return run_conv_gn(c, f, s);
+}
+
 // ResnetBlock1D.forward (reference decoder.py:58-63) on channels-last rows; input = up to two channel segments (in1.p null: one).
 // The output is the residual stream of the transformer blocks that follow, d.stream(dst); emit_stats: with its LayerNorm moments.
 static int resnet_block(mtts_ctx* c, DecBufs& d, const ResnetW& r, const Actv& in0, const Actv& in1, int lvl, const float* tbias,
@@ -897,20 +929,39 @@ static int resnet_block(mtts_ctx* c, DecBufs& d, const ResnetW& r, const Actv& i
     panel_args(c, r.conv1, a); rows_plain(a, B, T); taps_centered(a, 3);
     bind_in(d, a, 0, in0);
     if (in1.p) bind_in(d, a, 1, in1);
-    GnApplyArgs g1;
-    RET_IF(conv_gn_stats(c, d, a, lvl, r.gn1_g, r.gn1_b, r.gn1_bs, g1, s));
-    g1.chbias = tbias;
-    bind_out(d, g1, d.H, C);
-    RET_IF(run_gn_apply(c, g1, s));
+    const bool fusable = block1d_fusable(c, d, T, C);
+    if (fusable && (c->resnet_fuse & 1)) {
+        // the first Block1D as ONE launch (resnet_conv.hip): a workgroup per (utterance, GroupNorm group) owns its statistics, so
+        // neither the conv's fp32 rows nor a gn_apply pass exist.  Width 384 at 65..384 rows per utterance (both levels of the
+        // benchmark shape); every other shape keeps the launches below.
+        RET_IF(block1d_fused(c, d, a, lvl, r.gn1_g, r.gn1_b, r.gn1_bs, tbias, d.H, s));
+    } else {
+        GnApplyArgs g1;
+        RET_IF(conv_gn_stats(c, d, a, lvl, r.gn1_g, r.gn1_b, r.gn1_bs, g1, s));
+        g1.chbias = tbias;
+        bind_out(d, g1, d.H, C);
+        RET_IF(run_gn_apply(c, g1, s));
+    }
     GemmArgs b;
     panel_args(c, r.conv2, b); rows_plain(b, B, T); taps_centered(b, 3);
     bind_in(d, b, 0, actv(d, d.H, C));
-    GnApplyArgs g2;
-    RET_IF(conv_gn_stats(c, d, b, lvl, r.gn2_g, r.gn2_b, r.gn2_bs, g2, s));
     GemmArgs rc;
     panel_args(c, r.res, rc); rows_plain(rc, B, T);
     bind_in(d, rc, 0, in0);
     if (in1.p) bind_in(d, rc, 1, in1);
+    if (fusable && (c->resnet_fuse & 2)) {
+        // the second Block1D the same way, its masked result as an image in the slot the conv's fp32 rows would take; the 1x1
+        // residual conv adds it as its image residual and leaves x with its LayerNorm moments: no fp32 rows, no statistics
+        // entries to merge in the residual conv's prologue
+        RET_IF(block1d_fused(c, d, b, lvl, r.gn2_g, r.gn2_b, r.gn2_bs, nullptr, d.Y, s));
+        bind_res(d, rc, d.Y, C);
+        bind_out(d, rc, x, C);
+        if (emit_stats && (C % 64) == 0) rc.stats_out = d.lnp;
+        RET_IF(run_gemm(c, rc, s));
+        return 0;
+    }
+    GnApplyArgs g2;
+    RET_IF(conv_gn_stats(c, d, b, lvl, r.gn2_g, r.gn2_b, r.gn2_bs, g2, s));
     static const bool tail_on = [] { const char* e = getenv("MTTS_GN_TAIL"); return !(e && e[0] == '0'); }();   // A/B runs
     if (tail_on && g2.tile_rows && T >= 2 * gemm_p16_wave_rows(rc)) {      // a workgroup's rows in at most two utterances
         // The 1x1 residual conv finishes the block: its epilogue adds Mish(GroupNorm(conv2 output)) * mask from the tile
@@ -1109,10 +1160,14 @@ static int unet_eval(mtts_ctx* c, DecBufs& d, const float* xin, int ev, const Fi
     GemmArgs a;
     panel_args(c, D.final_conv, a); rows_plain(a, B, T); taps_centered(a, 3);
     bind_in(d, a, 0, cur);
-    GnApplyArgs ga;
-    RET_IF(conv_gn_stats(c, d, a, 0, D.fgn_g, D.fgn_b, D.fgn_bs, ga, s));
-    bind_out(d, ga, d.H, C0);
-    RET_IF(run_gn_apply(c, ga, s));
+    if ((c->resnet_fuse & 1) && block1d_fusable(c, d, T, C0)) {
+        RET_IF(block1d_fused(c, d, a, 0, D.fgn_g, D.fgn_b, D.fgn_bs, nullptr, d.H, s));
+    } else {
+        GnApplyArgs ga;
+        RET_IF(conv_gn_stats(c, d, a, 0, D.fgn_g, D.fgn_b, D.fgn_bs, ga, s));
+        bind_out(d, ga, d.H, C0);
+        RET_IF(run_gn_apply(c, ga, s));
+    }
     GemmArgs p;
     panel_args(c, D.final_proj, p); rows_plain(p, B, T);
     bind_in(d, p, 0, actv(d, d.H, C0));
@@ -1205,6 +1260,8 @@ mtts_ctx* mtts_create(const mtts_config* cfg) {
     { const char* e = getenv("MTTS_CHAIN_QB"); c->chain_qb = e ? atoi(e) : 0; }
     { const char* e = getenv("MTTS_CHAIN_MIN_ROWS"); if (e) c->chain_min_rows = atoi(e); }
     { const char* e = getenv("MTTS_CHAIN_PAIR"); c->pair_on = !(e && e[0] == '0'); }
+    { const char* e = getenv("MTTS_RESNET_FUSE"); if (e) c->resnet_fuse = atoi(e) & 7; }
+    { const char* e = getenv("MTTS_RESNET_FUSE_ROWS"); if (e) c->resnet_fuse_rows = atoi(e); }
     if (c->pair_on) {          // the pair form's residency bound assumes the whole 256-CU chip: a partitioned or smaller device runs without it
         int dev = 0;
         hipDeviceProp_t prop;
@@ -1708,6 +1765,36 @@ int mtts_gemm_p16(const float* d_a, int lda, int B, int T_in, int C, int ntaps, 
     a.out_T = T_out; a.out_stride = 1; a.out_off = 0; a.force_bm = force_bm;
     HIP_OK(launch_gemm(a, s));
     if (d_out16_f32) HIP_OK(launch_from_p16(o16, 2 * N, B * T_out, N, out_lscale, d_out16_f32, N, s));
+    return 0;
+}
+
+// Test entry for the one-launch Block1D (resnet_conv.hip): x [B*T, C] fp32 (already masked by the caller where the model would)
+// is converted to its P16 image in d_scratch, the Conv1d(k3) weight is packed and split as for mtts_gemm_p16, the P16 output is
+// decoded back to fp32 [B*T, N].  c1 > 0: the last c1 channels of x form a second input segment (the up path's skip concat).
+int64_t mtts_conv_gn_scratch_bytes(int B, int T, int C, int N) { return (int64_t)B * T * (C + N) * 4 + 1024; }
+int mtts_conv_gn(const float* d_x, int B, int T, int C, int c1, const float* d_w, void* d_wpacked, const float* d_bias, int N,
+                 const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias, const int* d_nrows,
+                 const int* d_nextra, const float* d_bias_stats, float eps, float* d_out, void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!d_x || !d_w || !d_wpacked || !d_scratch || !d_out) { set_error("null buffer"); return -1; }
+    if (C <= 0 || (C % 32) || c1 < 0 || (c1 % 32) || c1 >= C) { set_error("mtts_conv_gn: C and c1 must be multiples of 32, c1 < C"); return -1; }
+    if (!conv_gn_supported(T, N)) { set_error("mtts_conv_gn: unsupported shape (N = 384, 65 <= T <= 384)"); return -1; }
+    const int Np = round_up(N, GEMM_BN), Kp = 3 * C;
+    const size_t npanel = (size_t)Np * Kp;
+    float* planes = static_cast<float*>(d_wpacked) + ((npanel + 63) & ~size_t(63));
+    HIP_OK(launch_pack_weight(d_w, N, C, 3, static_cast<float*>(d_wpacked), s));
+    HIP_OK(launch_split_panel_f16(static_cast<const float*>(d_wpacked), npanel, planes, s));
+    _Float16* a16 = static_cast<_Float16*>(d_scratch);
+    _Float16* o16 = a16 + (size_t)B * T * C * 2;
+    HIP_OK(launch_to_p16(d_x, C, nullptr, B * T, C, C, a16, 2 * C, 2048.0f, s));
+    ConvGnArgs a;
+    a.a16_0 = a16; a.lda16_0 = 2 * C; a.c0 = C - c1;
+    if (c1) { a.a16_1 = a16 + 2 * (C - c1); a.lda16_1 = 2 * C; a.c1 = c1; }
+    a.w16 = planes; a.bias = d_bias; a.B = B; a.T = T; a.N = N;
+    a.gamma = d_gamma; a.beta = d_beta; a.mask = d_mask; a.chbias = d_chbias; a.nrows = d_nrows; a.nextra = d_nextra; a.bias_stats = d_bias_stats;
+    a.eps = eps; a.out16 = o16; a.ld16 = 2 * N;
+    HIP_OK(launch_conv_gn(a, s));
+    HIP_OK(launch_from_p16(o16, 2 * N, B * T, N, 2048.0f, d_out, N, s));
     return 0;
 }
 
