@@ -309,6 +309,40 @@ int64_t mtts_vocos_workspace_bytes(mtts_vocos* v, int B, int T);
 int mtts_vocos_decode(mtts_vocos* v, const float* d_mel, int B, int T, float* d_audio, void* d_ws, int64_t ws_bytes,
                       void* stream);
 
+/* Vocos.decode of a RAGGED batch -- what the reference computes when it calls vocos_wrapper.py:8-9 once per utterance on
+ * mel[b, :, :len_b] (its server does, reference server.py:116): d_lengths = device int64 [B], frames per utterance, 1 <= len_b <= T.
+ * Row b of d_audio [B, hop*(T-1)] holds the hop*(len_b - 1) samples of that utterance (every k7 convolution of the head zero-pads
+ * at len_b, the iSTFT and its window envelope end at frame len_b - 1) followed by zeros; len_b == 1 gives no samples.  The padded
+ * part of d_mel is never read as data.  A row of T frames equals mtts_vocos_decode's row bit for bit.
+ * The lengths are checked on the device, without a host synchronisation in front of the decode: the call enqueues and returns.
+ * mtts_vocos_ragged_status(d_ws, stream) waits for the stream and reports the first length outside [1, T] through
+ * mtts_last_error (the row and the value); mtts_waveform_finish marks the same rows with out_length -1, so a caller that goes
+ * on to it needs no wait of its own.  A row with a bad length is decoded as if the length were clamped into [0, T]: nothing
+ * is read or written outside the buffers.  Workspace: mtts_vocos_ragged_workspace_bytes. */
+int64_t mtts_vocos_ragged_workspace_bytes(mtts_vocos* v, int B, int T);
+int mtts_vocos_decode_ragged(mtts_vocos* v, const float* d_mel, const int64_t* d_lengths, int B, int T, float* d_audio,
+                             void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_vocos_ragged_status(const void* d_ws, void* stream);
+
+/* ---------------------------------------------------------------- waveform finish (ragged batch) */
+
+/* to_waveform's peak normalisation -- reference matcha/inference.py:260-264 -- and trim_trailing_silence's length --
+ * reference matcha/inference.py:268-287 -- for every row of d_audio [B][ld] (fp32, rows 16-byte aligned: ld % 4 == 0) on the
+ * device, no host synchronisation.  Row b has `valid` samples: d_lengths[b] when hop == 0, hop * (d_lengths[b] - 1) when
+ * hop > 0 (d_lengths = the frame counts given to mtts_vocos_decode_ragged).
+ *   peak  = max |a| over the valid samples (NaN propagates, as torch's max).  If peak > 1 every valid sample becomes
+ *           a / peak * 0.95 in fp32, in that order, in place, and d_scale[b] = 0.95 / peak; else the row is untouched and
+ *           d_scale[b] = 1.
+ *   trim  : windows of int(0.01 * sample_rate) samples anchored at sample 0 of the row as normalised (the remainder is never
+ *           examined); rms = sqrt(mean(a^2)); the trailing run of windows with rms < 10^(threshold_db / 20) (strict, compared in
+ *           fp32; a NaN window ends the run) is dropped: d_out_lengths[b] = valid - run * window.  All full windows may go.
+ *           The samples are not moved: the caller keeps the first d_out_lengths[b] of the row.
+ * A row whose length is outside its row (samples outside [0, ld], frames outside [1, ld / hop + 1]) is left alone and gets
+ * d_out_lengths[b] = -1.  Two calls on the same input give the same bits.  Workspace: mtts_waveform_workspace_bytes. */
+int64_t mtts_waveform_workspace_bytes(int64_t ld, int B, int sample_rate);
+int mtts_waveform_finish(float* d_audio, int64_t ld, const int64_t* d_lengths, int hop, int B, int sample_rate,
+                         double threshold_db, float* d_scale, int64_t* d_out_lengths, void* d_ws, int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- arithmetic and its range guard */
 
 /* Range guard of the default arithmetic.  The fp16 two-term split represents an operand x as h + l / 2^11 with h = fp16(x):

@@ -18,6 +18,7 @@ The class is transport-agnostic: an HTTP handler submits and awaits the future (
 """
 from __future__ import annotations
 
+import os
 import threading
 import time
 from concurrent.futures import Future
@@ -70,10 +71,12 @@ class FrameBudgetBatcher:
     def __init__(self, model, max_batch: int = 32, max_tokens: int = 8192, max_wait_ms: float = 2.0,
                  run_batch: Optional[Callable[[List[Request]], List[Dict[str, Any]]]] = None, vocoder=None):
         """``vocoder``: a ``load_vocoder("vocos")`` object; results then also carry ``"audio"`` = the reference handler's
-        ``trim_trailing_silence(to_waveform(mel, vocoder))`` (reference inference.py:246, server.py:116), computed per request on
-        its exact-length mel (the vocoder's k7 convolutions would otherwise see a neighbour-dependent padded tail)."""
+        ``trim_trailing_silence(to_waveform(mel, vocoder))`` (reference inference.py:246, server.py:116) of that request's own
+        mel.  The whole batch goes through ``inference.to_waveforms`` (ragged decode + finish on the device, one copy, one
+        synchronisation); ``MTTS_WAVE_BATCH=0``, read here per batcher, restores the per-request loop on exact-length mels."""
         self.model = model
         self.vocoder = vocoder
+        self.wave_batch = os.environ.get("MTTS_WAVE_BATCH", "1") != "0"
         self.max_batch = int(max_batch)
         self.max_tokens = int(max_tokens)
         self.max_wait = float(max_wait_ms) / 1e3
@@ -158,7 +161,11 @@ class FrameBudgetBatcher:
                                     length_scale=[r.length_scale for r in batch], per_request_padding=True)
         lens = out["mel_lengths"].tolist()
         res = [{"mel": out["mel"][b, :, :int(lens[b])], "mel_length": int(lens[b])} for b in range(B)]
-        if self.vocoder is not None:
+        if self.vocoder is not None and self.wave_batch:
+            from .inference import to_waveforms
+            for r, a in zip(res, to_waveforms(out["mel"], out["mel_lengths"], self.vocoder)):
+                r["audio"] = a
+        elif self.vocoder is not None:
             from .inference import _waveform_on_device, trim_trailing_silence
             for r in res:
                 r["audio"] = trim_trailing_silence(_waveform_on_device(r["mel"][None], self.vocoder).squeeze()).cpu()

@@ -328,9 +328,10 @@ struct GnApplyArgs {
 hipError_t launch_gn_apply(const GnApplyArgs& a, hipStream_t s);
 
 // channels-first [B,C,T] <-> channels-last [B,T,ld] moves
-// dst[b*T + t, col_off + c] = src[b,c,t] (+ add[b,c,t]) for t < T; the source rows are T_src long (T_src = 0: T)
+// dst[b*T + t, col_off + c] = src[b,c,t] (+ add[b,c,t]) for t < T; the source rows are T_src long (T_src = 0: T).
+// lengths (optional, device [B]): rows at t >= lengths[b] are written as zero and their source is not read.
 hipError_t launch_cf_to_cl(const float* src, const float* add, int B, int C, int T, float* dst, int ld, int col_off, hipStream_t s,
-                           int T_src = 0);
+                           int T_src = 0, const int64_t* lengths = nullptr);
 // dst[b,c,t] = src[b,t,c] * scale + shift for t < T_out
 hipError_t launch_cl_to_cf(const float* src, int ld, int B, int C, int T, float* dst, int T_out, float scale, float shift, hipStream_t s);
 hipError_t launch_fill_cols(float* dst, int M, int ld, int col0, int ncols, float v, hipStream_t s);
@@ -375,12 +376,34 @@ hipError_t launch_align_pool(const float* mu_x, const int32_t* cum, const int64_
                              float* mu_y, float* y_mask, int64_t* y_len, hipStream_t s);
 
 // ---- Vocos head (vocos.hip)
-// y = LayerNorm_C(depthwise_conv_k7(x) + bias) * gamma + beta on channels-last rows [B*T, C]; w7 is [7][C]
+// y = LayerNorm_C(depthwise_conv_k7(x) + bias) * gamma + beta on channels-last rows [B*T, C]; w7 is [7][C].
+// lengths (optional, device [B], frames): utterance b ends at lengths[b]; taps beyond it are zero padding.  Null = T for all.
 hipError_t launch_dwconv7_ln(const float* x, const float* w7, const float* bias, const float* gamma, const float* beta, float eps,
-                             int B, int T, int C, float* y, hipStream_t s);
+                             int B, int T, int C, float* y, hipStream_t s, const int64_t* lengths = nullptr);
 // in place on rows [M, ld]: (log-magnitude m_k, phase p_k) at columns (k, off + k) -> (Re, Im) = min(exp(m),clip) * (cos p, sin p)
 hipError_t launch_spec_polar(float* x, int M, int ld, int nbins, int off, float clip, hipStream_t s);
-// overlap-add of windowed frames [B*T, n_fft] (hop) with the squared-window envelope, centre trim: audio [B, hop*(T-1)]
-hipError_t launch_istft_ola(const float* frames, const float* window, int B, int T, int n_fft, int hop, float* audio, hipStream_t s);
+// overlap-add of windowed frames [B*T, n_fft] (hop) with the squared-window envelope, centre trim: audio [B, hop*(T-1)].
+// lengths (optional, device [B], frames): row b is the iSTFT of its first lengths[b] frames, hop*(lengths[b]-1) samples, then zeros.
+hipError_t launch_istft_ola(const float* frames, const float* window, int B, int T, int n_fft, int hop, float* audio, hipStream_t s,
+                            const int64_t* lengths = nullptr);
+// status[0..2] = (1 + first row with a length outside [1, T] or 0, that length, T); device-side check of a ragged call's lengths
+hipError_t launch_vocos_lengths_check(const int64_t* lengths, int B, int T, int* status, hipStream_t s);
+
+// ---- waveform finish (waveform.hip): per-row peak normalisation and trailing-silence trim lengths, see include/mtts.h
+struct WaveFinishArgs {
+    float* audio = nullptr;            // [B][ld], modified in place where a row's peak is above 1
+    int64_t ld = 0;                    // row stride in samples (multiple of 4, rows 16-byte aligned)
+    const int64_t* lengths = nullptr;  // [B]: samples (hop == 0) or frames (hop > 0: hop * (frames - 1) samples)
+    int hop = 0;
+    int B = 0;
+    int win = 0;                       // samples per RMS window
+    float thr = 0.f;                   // amplitude threshold
+    float* scale = nullptr;            // [B]
+    int64_t* out_lengths = nullptr;    // [B]
+    float* peaks = nullptr;            // workspace [B][nchunks]
+    float* rms = nullptr;              // workspace [B][ld / win]
+};
+constexpr int WAVE_CHUNK = 8192;       // samples per workgroup of the peak pass
+hipError_t launch_wave_finish(const WaveFinishArgs& a, hipStream_t s);
 
 }  // namespace mtts

@@ -2139,9 +2139,12 @@ static int vocos_pack(mtts_vocos* v) {
     return 0;
 }
 
-struct VocosBufs { float *MEL, *X, *Y, *H, *SPEC, *FR; };
-static void vocos_plan(const mtts_vocos* v, int B, int T, WS& ws, VocosBufs& b) {
+struct VocosBufs { float *MEL, *X, *Y, *H, *SPEC, *FR; int* STATUS; };
+// ragged: the status words of the lengths check FIRST (mtts_vocos_ragged_status reads them at the workspace's base), then the
+// buffers of the plain call
+static void vocos_plan(const mtts_vocos* v, int B, int T, WS& ws, VocosBufs& b, bool ragged = false) {
     const size_t M = (size_t)B * T;
+    b.STATUS = ragged ? static_cast<int*>(ws.bytes(4 * sizeof(int))) : nullptr;
     b.MEL = ws.f(M * round_up(v->n_mels, 4));
     b.X = ws.f(M * v->dim); b.Y = ws.f(M * v->dim); b.H = ws.f(M * v->inter);
     b.SPEC = ws.f(M * v->ld_spec); b.FR = ws.f(M * v->n_fft);
@@ -2190,20 +2193,31 @@ int64_t mtts_vocos_workspace_bytes(mtts_vocos* v, int B, int T) {
     return (int64_t)ws.off + 256;
 }
 
-// Vocos.decode (reference matcha/vocos24k/vocos_wrapper.py:8-9): mel [B, n_mels, T] -> audio [B, hop*(T-1)]
-int mtts_vocos_decode(mtts_vocos* v, const float* d_mel, int B, int T, float* d_audio, void* d_ws, int64_t ws_bytes, void* stream) {
+}  // extern "C"
+
+// Vocos.decode (reference matcha/vocos24k/vocos_wrapper.py:8-9): mel [B, n_mels, T] -> audio [B, hop*(T-1)].
+// d_lengths (device int64 [B], frames; null = every row has T): row b is decoded as the reference decodes mel[b, :, :len_b] on
+// its own -- every k7 conv (embed: zeroed mel rows; eight depthwise: length-aware taps) zero-pads at len_b, the iSTFT ends at
+// frame len_b - 1 -- and the row is zero past hop * (len_b - 1).  The per-row kernels (pointwise GEMMs, LayerNorms, head, polar,
+// inverse DFT) run on all B * T rows; rows at t >= len_b are computed and never read by a valid row.
+static int vocos_decode(mtts_vocos* v, const float* d_mel, const int64_t* d_lengths, int B, int T, float* d_audio, void* d_ws,
+                        int64_t ws_bytes, void* stream, const char* who) {
     if (!v) { set_error("null context"); return -1; }
     mtts_ctx* c = &v->base;
     RET_IF(check_ready(c));
-    if (T < 2) { set_error("mtts_vocos_decode: need at least 2 frames"); return -1; }
+    if (!d_mel || !d_audio || !d_ws || B <= 0) { set_error(std::string(who) + ": bad argument"); return -1; }
+    if (T < 2) { set_error(std::string(who) + ": need at least 2 frames"); return -1; }
     hipStream_t s = static_cast<hipStream_t>(stream);
     WS ws(d_ws, (size_t)ws_bytes);
     VocosBufs b;
-    vocos_plan(v, B, T, ws, b);
+    vocos_plan(v, B, T, ws, b, d_lengths != nullptr);
     if (ws.overflow) { set_error("vocos workspace too small"); return -1; }
     const VocosW& Wt = v->w;
     const int C = v->dim, M = B * T, ldm = round_up(v->n_mels, 4), nb = v->n_fft / 2 + 1;
-    LAUNCH(c, 2, 0, s, launch_cf_to_cl(d_mel, nullptr, B, v->n_mels, T, b.MEL, ldm, 0, s));
+    if (d_lengths) LAUNCH(c, 2, 0, s, launch_vocos_lengths_check(d_lengths, B, T, b.STATUS, s));
+    // ragged: the transpose writes the rows at t >= len_b as zero, so the embed conv's taps beyond an utterance's end read its
+    // zero padding.  (The GEMM's a_mask would multiply instead: one more launch for the mask, and NaN * 0 in a padded mel.)
+    LAUNCH(c, 2, 0, s, launch_cf_to_cl(d_mel, nullptr, B, v->n_mels, T, b.MEL, ldm, 0, s, 0, d_lengths));
     {   // embed: Conv1d(n_mels -> dim, k7, pad 3), then LayerNorm(eps 1e-6)
         GemmArgs a;
         panel_args(c, Wt.embed, a); rows_plain(a, B, T); taps_centered(a, 7);
@@ -2216,7 +2230,7 @@ int mtts_vocos_decode(mtts_vocos* v, const float* d_mel, int B, int T, float* d_
     }
     for (int i = 0; i < v->layers; ++i) {   // ConvNeXtBlock: x += gamma * pwconv2(GELU(pwconv1(LN(dwconv(x)))))
         LAUNCH(c, 2, 0, s, launch_dwconv7_ln(b.X, W(c, Wt.dw_w[i].off), W(c, Wt.dw_b[i].off), W(c, Wt.ln_g[i].off), W(c, Wt.ln_b[i].off),
-                                             1e-6f, B, T, C, b.Y, s));
+                                             1e-6f, B, T, C, b.Y, s, d_lengths));
         GemmArgs p1;
         panel_args(c, Wt.pw1[i], p1); rows_plain(p1, B, T);
         p1.a0 = b.Y; p1.lda0 = C; p1.c0 = C; p1.act = ACT_GELU; p1.out = b.H; p1.ldc = v->inter;
@@ -2240,8 +2254,76 @@ int mtts_vocos_decode(mtts_vocos* v, const float* d_mel, int B, int T, float* d_
         panel_args(c, Wt.basis, d); rows_plain(d, B, T);
         d.a0 = b.SPEC; d.lda0 = v->ld_spec; d.c0 = v->ld_spec; d.out = b.FR; d.ldc = v->n_fft;
         RET_IF(run_gemm(c, d, s));
-        LAUNCH(c, 2, 0, s, launch_istft_ola(b.FR, W(c, Wt.window.off), B, T, v->n_fft, v->hop, d_audio, s));
+        LAUNCH(c, 2, 0, s, launch_istft_ola(b.FR, W(c, Wt.window.off), B, T, v->n_fft, v->hop, d_audio, s, d_lengths));
     }
+    return 0;
+}
+
+extern "C" {
+
+int mtts_vocos_decode(mtts_vocos* v, const float* d_mel, int B, int T, float* d_audio, void* d_ws, int64_t ws_bytes, void* stream) {
+    return vocos_decode(v, d_mel, nullptr, B, T, d_audio, d_ws, ws_bytes, stream, "mtts_vocos_decode");
+}
+
+int64_t mtts_vocos_ragged_workspace_bytes(mtts_vocos* v, int B, int T) {
+    if (!v) { set_error("null context"); return -1; }
+    if (B <= 0 || T < 2) { set_error("mtts_vocos_ragged_workspace_bytes: bad shape"); return -1; }
+    WS ws(nullptr, 0);
+    VocosBufs b;
+    vocos_plan(v, B, T, ws, b, true);
+    return (int64_t)ws.off + 256;
+}
+int mtts_vocos_decode_ragged(mtts_vocos* v, const float* d_mel, const int64_t* d_lengths, int B, int T, float* d_audio, void* d_ws,
+                             int64_t ws_bytes, void* stream) {
+    if (!d_lengths) { set_error("mtts_vocos_decode_ragged: null lengths"); return -1; }
+    return vocos_decode(v, d_mel, d_lengths, B, T, d_audio, d_ws, ws_bytes, stream, "mtts_vocos_decode_ragged");
+}
+// The lengths check's verdict (the status words at the base of the ragged call's workspace).  This is the one place that waits
+// for the stream: callers that go on to mtts_waveform_finish read its out_lengths instead (-1 marks the same rows).
+int mtts_vocos_ragged_status(const void* d_ws, void* stream) {
+    if (!d_ws) { set_error("mtts_vocos_ragged_status: null workspace"); return -1; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int st[3] = {0, 0, 0};
+    HIP_OK(hipMemcpyAsync(st, d_ws, sizeof(st), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    if (st[0] != 0) {
+        set_error("mtts_vocos_decode_ragged: lengths[" + std::to_string(st[0] - 1) + "] = " + std::to_string(st[1]) +
+                  " is outside [1, T = " + std::to_string(st[2]) + "]");
+        return -1;
+    }
+    return 0;
+}
+
+// ---- waveform finish (waveform.hip)
+static int wave_window(int sample_rate) { return (int)(0.01 * (double)sample_rate); }       // reference inference.py:270
+int64_t mtts_waveform_workspace_bytes(int64_t ld, int B, int sample_rate) {
+    const int win = wave_window(sample_rate);
+    if (ld < 0 || B <= 0 || win <= 0) { set_error("mtts_waveform_workspace_bytes: bad shape"); return -1; }
+    WS ws(nullptr, 0);
+    ws.f((size_t)B * ((ld + WAVE_CHUNK - 1) / WAVE_CHUNK + 1));
+    ws.f((size_t)B * (ld / win + 1));
+    return (int64_t)ws.off + 256;
+}
+int mtts_waveform_finish(float* d_audio, int64_t ld, const int64_t* d_lengths, int hop, int B, int sample_rate, double threshold_db,
+                         float* d_scale, int64_t* d_out_lengths, void* d_ws, int64_t ws_bytes, void* stream) {
+    WaveFinishArgs a;
+    a.win = wave_window(sample_rate);
+    if (!d_audio || !d_lengths || !d_scale || !d_out_lengths || !d_ws || B <= 0 || B > 65535 || ld < 0 || hop < 0 || a.win <= 0) {
+        set_error("mtts_waveform_finish: bad argument");
+        return -1;
+    }
+    if ((ld & 3) || (reinterpret_cast<uintptr_t>(d_audio) & 15)) {
+        set_error("mtts_waveform_finish: rows must be 16-byte aligned (ld a multiple of 4 samples)");
+        return -1;
+    }
+    WS ws(d_ws, (size_t)ws_bytes);
+    a.peaks = ws.f((size_t)B * ((ld + WAVE_CHUNK - 1) / WAVE_CHUNK + 1));
+    a.rms = ws.f((size_t)B * (ld / a.win + 1));
+    if (ws.overflow) { set_error("mtts_waveform_finish: workspace too small"); return -1; }
+    a.audio = d_audio; a.ld = ld; a.lengths = d_lengths; a.hop = hop; a.B = B;
+    a.thr = (float)std::pow(10.0, threshold_db / 20.0);         // reference inference.py:271; torch compares the fp32 RMS in fp32
+    a.scale = d_scale; a.out_lengths = d_out_lengths;
+    HIP_OK(launch_wave_finish(a, static_cast<hipStream_t>(stream)));
     return 0;
 }
 

@@ -402,16 +402,20 @@ hipError_t launch_gn_apply(const GnApplyArgs& a, hipStream_t s) {
 
 // ------------------------------------------------------------------------------------------------ layout moves
 // dst[b, t, col_off + c] = src[b, c, t] (+ add[b, c, t])        [B,C,T] -> rows of [B*T, ld]
+// RAGGED: utterance b has lengths[b] frames; later rows are written as zero without reading the source (a select, not a
+// multiply: whatever the padding holds, NaN included, stays out)
+template <bool RAGGED>
 __global__ void cf_to_cl_kernel(const float* __restrict__ src, const float* __restrict__ add, int C, int T, int T_src,
-                                float* __restrict__ dst, int ld, int col_off) {
+                                float* __restrict__ dst, int ld, int col_off, const int64_t* __restrict__ lengths) {
     __shared__ float tile[32][33];
     const int b = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
     const int tx = threadIdx.x, ty = threadIdx.y;
+    const int64_t t_end = RAGGED ? lengths[b] : (int64_t)T;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int c = c0 + ty + 8 * k, t = t0 + tx;
         float v = 0.f;
-        if (c < C && t < T) {
+        if (c < C && t < T && (!RAGGED || (int64_t)t < t_end)) {
             const size_t i = ((size_t)b * C + c) * T_src + t;
             v = src[i];
             if (add) v += add[i];
@@ -426,10 +430,14 @@ __global__ void cf_to_cl_kernel(const float* __restrict__ src, const float* __re
     }
 }
 hipError_t launch_cf_to_cl(const float* src, const float* add, int B, int C, int T, float* dst, int ld, int col_off, hipStream_t s,
-                           int T_src) {
+                           int T_src, const int64_t* lengths) {
     if (T_src == 0) T_src = T;
     if (!src || !dst || B <= 0 || C <= 0 || T <= 0 || T_src < T) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(cf_to_cl_kernel, dim3((T + 31) / 32, (C + 31) / 32, B), dim3(32, 8), 0, s, src, add, C, T, T_src, dst, ld, col_off);
+    const dim3 grid((T + 31) / 32, (C + 31) / 32, B);
+    if (lengths)
+        hipLaunchKernelGGL(cf_to_cl_kernel<true>, grid, dim3(32, 8), 0, s, src, add, C, T, T_src, dst, ld, col_off, lengths);
+    else
+        hipLaunchKernelGGL(cf_to_cl_kernel<false>, grid, dim3(32, 8), 0, s, src, add, C, T, T_src, dst, ld, col_off, lengths);
     return hipGetLastError();
 }
 

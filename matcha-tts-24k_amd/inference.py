@@ -281,6 +281,56 @@ def to_waveform(mel, vocoder):
     return _waveform_on_device(mel, vocoder).cpu().squeeze()
 
 
+@torch.inference_mode()
+def finish_waveforms(audio, lengths, hop=0, silence_threshold_db=-60.0):
+    """Peak normalisation (reference inference.py:260-264) and the trim length of ``trim_trailing_silence`` (reference
+    inference.py:268-287) for every row of ``audio`` [B, L] on the device, in place, without a host synchronisation
+    (``mtts_waveform_finish``).  ``lengths`` [B]: valid samples per row, or frames when ``hop`` is given (row b then has
+    ``hop * (frames - 1)`` samples, as ``Vocos.decode(mel, lengths)`` leaves them).  Returns device tensors
+    ``(out_lengths int64 [B], scale float32 [B])``: the caller keeps ``audio[b, :out_lengths[b]]``; -1 marks a row whose length
+    is outside its row."""
+    from . import _hip
+    lib = _hip.load()
+    if audio.dim() != 2 or audio.dtype != torch.float32 or not audio.is_cuda or not audio.is_contiguous():
+        raise RuntimeError("finish_waveforms: audio must be a contiguous float32 [B, L] tensor on a HIP device")
+    B, L = audio.shape
+    lengths = torch.as_tensor(lengths).to(device=audio.device, dtype=torch.long).contiguous()
+    if lengths.shape != (B,):
+        raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+    need = lib.mtts_waveform_workspace_bytes(L, B, SAMPLE_RATE)
+    if need < 0:
+        _hip.check(-1)
+    ws = torch.empty(need, dtype=torch.uint8, device=audio.device)
+    scale = torch.empty(B, dtype=torch.float32, device=audio.device)
+    out_lengths = torch.empty(B, dtype=torch.long, device=audio.device)
+    _hip.check(lib.mtts_waveform_finish(_hip.ptr(audio), L, _hip.ptr(lengths), int(hop), B, SAMPLE_RATE, float(silence_threshold_db),
+                                        _hip.ptr(scale), _hip.ptr(out_lengths), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
+    return out_lengths, scale
+
+
+@torch.inference_mode()
+def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0):
+    """``trim_trailing_silence(to_waveform(mel[b:b+1, :, :len_b], vocoder))`` (reference inference.py:246) for every row of a
+    ragged batch in one device pass: ragged Vocos decode, per-row peak normalisation, per-row trim lengths, then ONE copy of the
+    audio and one of the [B] lengths -- one synchronisation for the whole batch.  Returns a list of B 1-D host tensors
+    (``trim=False``: normalised but not trimmed, i.e. ``to_waveform`` per row); they are views of the batch's one host buffer."""
+    model = vocoder.model if hasattr(vocoder, "model") else vocoder
+    if mel.dim() == 2:
+        mel = mel[None]
+    B, _, T = mel.shape
+    mel_lengths = torch.as_tensor(mel_lengths).to(device=mel.device, dtype=torch.long)
+    hop = model.cfg["hop"]
+    audio = model.decode(mel, mel_lengths, check=False)
+    out_lengths, _ = finish_waveforms(audio, mel_lengths, hop=hop, silence_threshold_db=silence_threshold_db)
+    meta = torch.stack([out_lengths, mel_lengths]).cpu()              # waits for the stream: the batch's one synchronisation
+    host = audio.cpu()
+    keep, frames = meta[0].tolist(), meta[1].tolist()
+    for b in range(B):
+        if keep[b] < 0:
+            raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
+    return [host[b, : (keep[b] if trim else hop * (frames[b] - 1))] for b in range(B)]
+
+
 def trim_trailing_silence(audio, silence_threshold_db=-60.0):
     """reference inference.py:268-287, window for window: 10 ms windows anchored at sample 0 (the ``len % window`` remainder is
     never examined), RMS per window, count the run of trailing windows with ``rms < threshold`` (strict; a NaN window stops the

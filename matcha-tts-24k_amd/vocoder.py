@@ -3,7 +3,7 @@ reference matcha/vocos24k/vocos_wrapper.py:3-16) and for ``vocos.Vocos.decode``.
 
 The reference fetches pretrained weights by name from the HF hub (``charactr/vocos-mel-24khz``); there is no network
 here, so ``load_model`` reads a local state dict (``VOCOS_CHECKPOINT`` or an explicit path) in the vocos package's
-key layout.  Arithmetic runs in libmtts_hip.so (``mtts_vocos_decode``); there is no CPU path.
+key layout.  Arithmetic runs in libmtts_hip.so (``mtts_vocos_decode``, ``mtts_vocos_decode_ragged``); there is no CPU path.
 """
 from __future__ import annotations
 
@@ -23,7 +23,7 @@ DEFAULT_CFG = dict(n_mels=100, dim=512, inter=1536, layers=8, n_fft=1024, hop=25
 
 
 class Vocos(ParamTree):
-    """Parameter holder under the vocos state-dict names + ``decode(mel)``."""
+    """Parameter holder under the vocos state-dict names + ``decode(mel, lengths=None)``."""
 
     def __init__(self, **cfg):
         super().__init__()
@@ -75,9 +75,26 @@ class Vocos(ParamTree):
             object.__setattr__(self, "_dirty", False)
         return lib
 
+    def _workspace(self, need: int, device) -> torch.Tensor:
+        key = _hip.stream_ptr()                     # one grow-only scratch buffer per stream (see HipModel._workspace)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = None
+            self._ws.pop(key, None)
+            ws = torch.empty(need, dtype=torch.uint8, device=device)
+            self._ws[key] = ws
+        return ws
+
     @torch.inference_mode()
-    def decode(self, mel: torch.Tensor) -> torch.Tensor:
-        """mel [B, n_mels, T] (or [n_mels, T]) -> audio [B, hop*(T-1)]."""
+    def decode(self, mel: torch.Tensor, lengths=None, check: bool = True) -> torch.Tensor:
+        """mel [B, n_mels, T] (or [n_mels, T]) -> audio [B, hop*(T-1)].
+
+        ``lengths`` ([B] frames, tensor or sequence): a ragged batch.  Row b is what ``decode(mel[b:b+1, :, :len_b])`` gives
+        (to rounding), followed by zeros; the padded part of ``mel`` is not read as data.  Without it every row is decoded
+        over all T frames, which changes the last ~27 frames of an utterance shorter than T (seven-tap convolutions, nine deep).
+        A length outside [1, T] raises, naming the row; the lengths are checked on the device after the decode has been
+        enqueued, and ``check=False`` leaves that wait to the caller (``inference.to_waveforms`` reads the verdict with its
+        one copy)."""
         lib = self._ready()
         if mel.dim() == 2:
             mel = mel[None]
@@ -85,16 +102,23 @@ class Vocos(ParamTree):
             raise RuntimeError("matcha-tts-24k_amd: mel is not on a HIP device; there is no CPU path")
         mel = mel.detach().to(torch.float32).contiguous()
         B, _, T = mel.shape
-        need = lib.mtts_vocos_workspace_bytes(self._ctx, B, T)
-        key = _hip.stream_ptr()                     # one grow-only scratch buffer per stream (see HipModel._workspace)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = None
-            self._ws.pop(key, None)
-            ws = torch.empty(need, dtype=torch.uint8, device=mel.device)
-            self._ws[key] = ws
         audio = torch.empty(B, self.cfg["hop"] * (T - 1), dtype=torch.float32, device=mel.device)
-        _hip.check(lib.mtts_vocos_decode(self._ctx, _hip.ptr(mel), B, T, _hip.ptr(audio), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
+        if lengths is None:
+            need = lib.mtts_vocos_workspace_bytes(self._ctx, B, T)
+            ws = self._workspace(need, mel.device)
+            _hip.check(lib.mtts_vocos_decode(self._ctx, _hip.ptr(mel), B, T, _hip.ptr(audio), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
+            return audio
+        lengths = torch.as_tensor(lengths).to(device=mel.device, dtype=torch.long).contiguous()
+        if lengths.shape != (B,):
+            raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+        need = lib.mtts_vocos_ragged_workspace_bytes(self._ctx, B, T)
+        if need < 0:
+            _hip.check(-1)
+        ws = self._workspace(need, mel.device)
+        _hip.check(lib.mtts_vocos_decode_ragged(self._ctx, _hip.ptr(mel), _hip.ptr(lengths), B, T, _hip.ptr(audio), ws.data_ptr(),
+                                                ws.numel(), _hip.stream_ptr()))
+        if check and lib.mtts_vocos_ragged_status(ws.data_ptr(), _hip.stream_ptr()) != 0:
+            raise ValueError("mtts: " + lib.mtts_last_error().decode("utf-8", "replace"))
         return audio
 
     def __del__(self):
@@ -112,8 +136,11 @@ class VocosWrapper(nn.Module):
         super().__init__()
         self.model = model
 
-    def forward(self, mel):
-        return self.model.decode(mel)
+    def forward(self, mel, lengths=None):
+        """``lengths`` ([B] frames): ragged batch, see ``Vocos.decode``."""
+        if lengths is None:
+            return self.model.decode(mel)
+        return self.model.decode(mel, lengths)
 
 
 def load_model(device="cuda", checkpoint: Optional[str] = None, state_dict: Optional[Dict[str, torch.Tensor]] = None):
