@@ -410,11 +410,10 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
     const int b128 = (a.T + 127) / 128, b64 = (a.T + 63) / 64;
     const long blocks128 = (long)b128 * a.H * a.B;
     const double waste128 = 1.0 - (double)a.T / (b128 * 128.0);
-    static const int env_nw = [] { const char* e = getenv("MTTS_ATTN_NW"); return e ? atoi(e) : 0; }();     // A/B runs only
     // (or when 64-query blocks would pad to the same row count anyway -- T = 322: 3 x 128 = 6 x 64 -- and the grid still has
     // two workgroups per CU: half as many workgroups re-stage each head's keys and values)
     const bool same_rows = b128 * 128 == b64 * 64 && blocks128 >= 512;
-    const bool use128 = env_nw == 4 || (env_nw == 0 && ((blocks128 >= 768 && waste128 < 0.1) || same_rows));
+    const bool use128 = (blocks128 >= 768 && waste128 < 0.1) || same_rows;
     {
         static thread_local std::string tag;
         const bool one = a.half16 || (p16 && a.fast16);
@@ -422,9 +421,8 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
         g_kernel_tag = tag.c_str();
     }
     // short sequences (65..192 keys: the estimator's half-length level) on P16 / H16 images: one workgroup per (utterance, head),
-    // all keys staged once (KR = 192); MTTS_ATTN_WHOLE=0 keeps the tiled kernel (A/B runs)
-    static const bool whole_on = [] { const char* e = getenv("MTTS_ATTN_WHOLE"); return !(e && e[0] == '0'); }();
-    if (p16 && whole_on && env_nw == 0 && a.T > 64 && a.T <= 192) {
+    // all keys staged once (KR = 192)
+    if (p16 && a.T > 64 && a.T <= 192) {
         static thread_local std::string wtag;
         const bool one = a.half16 || a.fast16;
         wtag = std::string("attention_f32_kernel<6, true, ") + tf(one) + ", " + tf(a.half16) + ", " + tf(a.half16 && a.bf16) + ", 192>";

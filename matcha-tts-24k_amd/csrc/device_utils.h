@@ -45,15 +45,12 @@ __device__ __forceinline__ void raise_range_flag(unsigned int* flag, bool bad) {
     if (bad && flag) atomicOr(flag, 1u);
 }
 
-// sin(y)^2 for the SnakeBeta epilogue: 3-constant Cody-Waite reduction by pi/2 to r in [-pi/4, pi/4] and the minimax sine
-// kernel; in odd quadrants sin(y)^2 = cos(r)^2 = 1 - sin(r)^2, so one polynomial serves both (sin(r)^2 <= 1/2: the
-// subtraction is benign).  ~1 ulp of sinf(y)^2 for |y| < 1e4 (arguments here are O(10)), a quarter of the library sinf.
-// sin(y)^2 = (1 - cos(2y)) / 2 with the hardware cosine (v_cos_f32 takes revolutions; v_fract_f32 reduces the argument first):
-// 4 VALU instructions instead of the ~16 of the polynomial below.  The FeedForward's first projection spends half of its
-// workgroup lifetime in this epilogue (profiles/r02_kstamp.log).  Absolute error of v_cos_f32 ~1e-6, i.e. ~5e-7 on sin^2 (the
-// polynomial: ~1e-7): the mel error against the goldens is unchanged (5.6e-5 / 3.4e-5 / 4.1e-5) and the
-// kernel test against fp64 holds its 1e-5.  -DMTTS_SNAKE_POLY builds the polynomial (3-constant Cody-Waite + minimax sine).
-__device__ __forceinline__ float sin_sq_hw(float y) {
+// sin(y)^2 for the SnakeBeta epilogue = (1 - cos(2y)) / 2 with the hardware cosine (v_cos_f32 takes revolutions; v_fract_f32
+// reduces the argument first): 4 VALU instructions instead of the ~16 of a Cody-Waite reduction with a minimax sine polynomial.
+// The FeedForward's first projection spends half of its workgroup lifetime in this epilogue (profiles/r02_kstamp.log).  Absolute
+// error of v_cos_f32 ~1e-6, i.e. ~5e-7 on sin^2 (the polynomial: ~1e-7): the mel error against the goldens is unchanged (5.6e-5 /
+// 3.4e-5 / 4.1e-5) and the kernel test against fp64 holds its 1e-5.
+__device__ __forceinline__ float sin_sq(float y) {
     const float t = __builtin_amdgcn_fractf(y * 0.31830988618379067154f);     // 2y / (2 pi), reduced to [0, 1)
     return fmaf(-0.5f, __builtin_amdgcn_cosf(t), 0.5f);
 }
@@ -63,43 +60,17 @@ __device__ __forceinline__ float snake_hw(float x, float s0, float s1_half) {
     const float t = __builtin_amdgcn_fractf((x * s0) * 0.31830988618379067154f);
     return __builtin_fmaf(-s1_half, __builtin_amdgcn_cosf(t), x + s1_half);
 }
-__device__ __forceinline__ float sin_sq_poly(float y);
-__device__ __forceinline__ float sin_sq(float y) {
-#ifdef MTTS_SNAKE_POLY
-    return sin_sq_poly(y);
-#else
-    return sin_sq_hw(y);
-#endif
-}
-__device__ __forceinline__ float sin_sq_poly(float y) {
-    const float n = rintf(y * 0.63661977236758134308f);
-    float r = fmaf(n, -1.5707962513e+00f, y);       // pi/2 split: hi, mid, lo
-    r = fmaf(n, -7.5497894159e-08f, r);
-    r = fmaf(n, -5.3903029534e-15f, r);
-    const float z = r * r;
-    // sin(r) = r + r*z*(S1 + z*(S2 + z*(S3 + z*S4)))
-    const float sp = fmaf(z, fmaf(z, fmaf(z, 2.7183114939e-06f, -1.9839334836e-04f), 8.3333298564e-03f), -1.6666665459e-01f);
-    const float sn = fmaf(r * z, sp, r);
-    const float s2 = sn * sn;
-    return (((int)n) & 1) ? 1.0f - s2 : s2;
-}
 
 // Mish(x) = x tanh(softplus(x)) = x w / (w + 2), w = e^x (e^x + 2)   (reference decoder.py:32-45, nn.Mish)
 // Hardware exponential and reciprocal (v_exp_f32 on x log2 e, v_rcp_f32: ~1 ulp each, relative error of Mish ~3e-7) instead of
 // expf and an IEEE division: ~8 instead of ~30 vector instructions per element.  The fused Block1D tail of the ResNet GEMM
 // runs this on 16-32 elements per lane with one wave per SIMD (profiles/r02_kstamp_insitu.log: its first 16-row chunk cost
-// 8-10k cycles); mel error against the goldens unchanged.  -DMTTS_MISH_LIBM builds the libm form.
+// 8-10k cycles); mel error against the goldens unchanged.
 __device__ __forceinline__ float mish_f(float x) {
     if (x > 20.f) return x;
-#ifdef MTTS_MISH_LIBM
-    const float n = expf(x);
-    const float w = n * (n + 2.f);
-    return x * (w / (w + 2.f));
-#else
     const float n = __builtin_amdgcn_exp2f(x * 1.44269504088896340736f);
     const float w = n * (n + 2.f);
     return x * (w * __builtin_amdgcn_rcpf(w + 2.f));
-#endif
 }
 
 __device__ __forceinline__ float act_apply(float c, int act, float p0, float p1) {

@@ -598,11 +598,7 @@ __device__ __forceinline__ void gemm_epilogue_rows8(const GemmArgs& p, const Epi
                     if constexpr (ACT == 1) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {                                                          // SnakeBeta
-#ifdef MTTS_SNAKE_POLY
-                            o[h][e] = o[h][e] + s1[h][e] * sin_sq(o[h][e] * s0[h][e]);
-#else
                             o[h][e] = snake_hw(o[h][e], s0[h][e], s1h[h][e]);
-#endif
                         }
                     } else if constexpr (ACT == 2) {
 #pragma unroll

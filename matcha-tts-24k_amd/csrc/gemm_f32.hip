@@ -489,9 +489,7 @@ hipError_t launch_gemm(const GemmArgs& a, hipStream_t s) {
         const int rounds = (tiles + 511) / 512;
         return (double)tiles / (rounds * 512.0) * ((double)M / (((M + bm - 1) / bm) * bm));
     };
-    static const int env_bm = [] { const char* e = getenv("MTTS_GEMM_BM"); return e ? atoi(e) : 0; }();   // A/B runs only
-    const int force = a.force_bm ? a.force_bm : env_bm;
-    if (force == 64 || (force == 0 && 0.97 * fill(64) > fill(128))) return launch_terms<64>(a, s);
+    if (a.force_bm == 64 || (a.force_bm == 0 && 0.97 * fill(64) > fill(128))) return launch_terms<64>(a, s);
     return launch_terms<128>(a, s);
 }
 

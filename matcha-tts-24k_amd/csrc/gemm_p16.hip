@@ -391,12 +391,6 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void gemm_p16_kernel(con
     const bool epi_wave = EPI_SPLIT || ks == 0;               // does this wave run an epilogue
     EpiPre<BM> pre;
     pre.valid = false;
-#ifndef MTTS_EPI_PRE
-#define MTTS_EPI_PRE 2
-#endif
-#if MTTS_EPI_PRE == 1
-    if (epi_wave) epi_prefetch<BM, EPI_PASS>(p, pre, M, m0, n0, wm, wn, lane, epi_row0);
-#endif
     EpiCols cols;
     if constexpr (BM == 64) {
         if (epi_wave) {
@@ -426,9 +420,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void gemm_p16_kernel(con
     }
     if constexpr (NST == 2) {
         issue(0);
-#if MTTS_EPI_PRE == 2
         if (epi_wave) epi_prefetch<BM, EPI_PASS>(p, pre, M, m0, n0, wm, wn, lane, epi_row0);
-#endif
         ln_stats();
         gnr_prologue();
         __syncthreads();                       // (emits vmcnt(0): the first tile has landed)
@@ -446,7 +438,6 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void gemm_p16_kernel(con
         MTTS_STAMP(7);                         // (diagnostic: setup done, first tile about to be requested)
 #endif
         for (int t = 0; t < D && t < nk; ++t) issue(t);
-#if MTTS_EPI_PRE == 2
         // the residual image tile of a 64-row tile: requested right behind the first D tiles; its R loads sit in the
         // vector-memory counter between tile D-1 and tile D, so the first D counted waits allow R more (loads retire in order).
         // The counts depend on that ORDER: the empty asm statements keep the compiler from moving these plain loads across the
@@ -454,8 +445,7 @@ __global__ __launch_bounds__(256 * KS, KS == 1 ? 2 : 1) void gemm_p16_kernel(con
         asm volatile("" ::: "memory");
         if (epi_wave) epi_prefetch<BM, EPI_PASS>(p, pre, M, m0, n0, wm, wn, lane, epi_row0);
         asm volatile("" ::: "memory");
-#endif
-        const int pre_r = (BM == 64 && MTTS_EPI_PRE == 2 && pre.valid) ? (p.half16 ? EPI_PASS : 2 * EPI_PASS) : 0;
+        const int pre_r = (BM == 64 && pre.valid) ? (p.half16 ? EPI_PASS : 2 * EPI_PASS) : 0;
         ln_stats();
         gnr_prologue();
         int st = 0;
@@ -568,7 +558,7 @@ static hipError_t launch_p16_variant(const GemmArgs& a, hipStream_t s) {
 // Block-tile height and pipeline depth for a shape (also what gemm_p16_wave_rows reports to callers that must match it).
 // Height by grid fill, as launch_gemm: 2 resident workgroups per CU for either height (LDS 70 / 49 KB).  Small grids (serving
 // shapes, B <= 8): 64-row tiles on the prefetch ring -- 4 stages at <= 1 workgroup per CU (96 KB of LDS), 3 stages at <= 2
-// (72 KB).  MTTS_P16_RING=0 keeps the two-stage kernel, 2 puts every 64-row grid on the ring; MTTS_GEMM_BM forces a height.
+// (72 KB).  GemmArgs::force_bm takes a shape off the ring: the two-stage kernel at that height.
 static int p16_choose(const GemmArgs& a, int& nst) {
     const int M = a.B * a.T_out;
     const int nt = (a.N + GEMM_BN - 1) / GEMM_BN;
@@ -577,17 +567,13 @@ static int p16_choose(const GemmArgs& a, int& nst) {
         const int rounds = (tiles + 511) / 512;
         return (double)tiles / (rounds * 512.0) * ((double)M / (((M + bm - 1) / bm) * bm));
     };
-    static const int ring_mode = [] { const char* e = getenv("MTTS_P16_RING"); return e ? atoi(e) : 1; }();
-    static const int env_bm = [] { const char* e = getenv("MTTS_GEMM_BM"); return e ? atoi(e) : 0; }();
     const int tiles64 = ((M + 63) / 64) * nt;
     nst = 2;
-    if (ring_mode != 0 && a.force_bm == 0 && tiles64 <= 512) {
+    if (a.force_bm == 0 && tiles64 <= 512) {
         nst = tiles64 <= 256 ? 4 : 3;      // (a 6-stage ring for the one-round grids measured the same: r02)
         return 64;
     }
-    const int force = a.force_bm ? a.force_bm : env_bm;
-    const bool bm64 = force == 64 || (force == 0 && 0.97 * fill(64) > fill(128));
-    if (bm64 && ring_mode == 2) nst = 3;
+    const bool bm64 = a.force_bm == 64 || (a.force_bm == 0 && 0.97 * fill(64) > fill(128));
     return bm64 ? 64 : 128;
 }
 int gemm_p16_wave_rows(const GemmArgs& a) {
@@ -648,7 +634,7 @@ hipError_t launch_gemm_p16(const GemmArgs& a_in, hipStream_t s) {
         b.kstamp = g_kstamp;
         g_kstamp = nullptr;
         const int nk_all = a.ntaps * a.ktap / kq;
-        const bool sk = bm == 64 && nst == 4 && nk_all >= 4 && (nk_all % 2) == 0 && !(getenv("MTTS_P16_SPLITK") && atoi(getenv("MTTS_P16_SPLITK")) == 0);
+        const bool sk = bm == 64 && nst == 4 && nk_all >= 4 && (nk_all % 2) == 0;
         const int info[8] = {a.B * a.T_out, a.N, a.ntaps * a.ktap, bm, sk ? 3 : nst, sk ? 2 : 1, a.ntaps,
                              (ln ? 1 : 0) | (a.res16 ? 2 : 0) | (a.out16 ? 4 : 0) | (a.out ? 8 : 0) | (a.gn_stats ? 16 : 0) | (a.gnr_y ? 32 : 0) |
                                  (a.act == ACT_SNAKE ? 64 : 0) | (a.stats_out ? 128 : 0)};
@@ -665,10 +651,9 @@ hipError_t launch_gemm_p16(const GemmArgs& a_in, hipStream_t s) {
             return hipErrorInvalidValue;
     }
     if (bm == 64) {
-        // one workgroup per CU or fewer: split the K axis between two wave sets when it divides (MTTS_P16_SPLITK=0: the 4-stage ring)
-        static const int splitk = [] { const char* e = getenv("MTTS_P16_SPLITK"); return e ? atoi(e) : 1; }();
+        // one workgroup per CU or fewer: split the K axis between two wave sets when it divides, else the 4-stage ring
         const int nk_all = a.ntaps * a.ktap / kq;
-        if (nst == 4 && splitk && nk_all >= 4 && (nk_all % 2) == 0) {
+        if (nst == 4 && nk_all >= 4 && (nk_all % 2) == 0) {
             if (a.half16 && a.bf16) return ln ? launch_p16_splitk<true, 3>(a, s) : launch_p16_splitk<false, 3>(a, s);
             if (a.half16) return ln ? launch_p16_splitk<true, 2>(a, s) : launch_p16_splitk<false, 2>(a, s);
             if (a.fast16) return ln ? launch_p16_splitk<true, 1>(a, s) : launch_p16_splitk<false, 1>(a, s);

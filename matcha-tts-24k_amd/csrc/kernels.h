@@ -3,7 +3,6 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 namespace mtts {
 
@@ -13,6 +12,9 @@ constexpr int GEMM_BK = 32;
 constexpr int MAX_TAPS = 7;
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
+
+// Compute units of the chip the launch plans are made for (MI355X, unpartitioned): one workgroup per CU is "one round".
+constexpr int CHIP_CUS = 256;
 
 // Name of the kernel instantiation the last launcher call on this thread chose, spelled as rocprofv3 prints it (e.g.
 // "gemm_p16_kernel<64, false, 3, 0, true, false, 2>"): the per-launch event pass (mtts_prof_*) stores it with each record, so a
@@ -243,7 +245,9 @@ struct ChainArgs {
     unsigned int* pair_flag = nullptr;
     unsigned int pair_epoch = 0;         // a value no earlier launch on these flags used
     int pf_wgs = 0;                      // extra workgroups (lowest ids) that only touch the weight stream ahead of the others; 8 = one per XCD, 16 = two (the model's default; the pair form takes 16: one per XCD and half)
-    unsigned long long* kstamp = nullptr;// diagnostic builds only (-DMTTS_CHAIN_STAMP): 16 phase stamps of workgroup 0
+    // diagnostic builds only (-DMTTS_CHAIN_STAMP, tools/chain_stamps.py): s_memtime stamps -- 16 phase stamps of workgroup 0, then
+    // (start, end) per workgroup, prefetchers included.  No output value depends on them.
+    unsigned long long* kstamp = nullptr;
 };
 // fragments per wave of the stream for (C, inner, hidden chunk, q|k|v width), incl. the padding the register ring may run into
 long chain_stream_frags(int C, int inner, int ch, int n_qkv);
@@ -286,13 +290,10 @@ hipError_t launch_layernorm(const LayerNormArgs& a, hipStream_t s);
 // (B = 1, T = 640: 80 workgroups of 4 row passes instead of 20 of 16 -- these kernels are latency-bound there).
 constexpr int GN_CHUNK = 32;       // largest chunk
 constexpr int GN_CHUNK_MIN = 8;
-static inline int gn_min_blocks() {
-    static const int v = [] { const char* e = getenv("MTTS_GN_BLOCKS"); return e ? atoi(e) : 2048; }();     // env: A/B runs only
-    return v;
-}
+constexpr int GN_MIN_BLOCKS = 2048;   // workgroups from which the 32-row chunk is kept (above)
 static inline int gn_chunk_rows(int B, int T) {
     int rows = GN_CHUNK;
-    while (rows > GN_CHUNK_MIN && (long)B * ((T + rows - 1) / rows) < gn_min_blocks()) rows >>= 1;
+    while (rows > GN_CHUNK_MIN && (long)B * ((T + rows - 1) / rows) < GN_MIN_BLOCKS) rows >>= 1;
     return rows;
 }
 static inline int gn_chunks(int B, int T) { const int r = gn_chunk_rows(B, T); return (T + r - 1) / r; }

@@ -79,6 +79,30 @@ struct VocosW {
     std::vector<Panel> pw1, pw2;
 };
 
+// The library's run-time switches with their defaults.  read_switches() (model.hip) is the only reader of the environment:
+// mtts_create keeps its result in the context, which never looks at the environment again; the context-free test entries
+// (mtts_chain_plan, mtts_tblock_chain*, mtts_gemm_terms(NULL), mtts_gemm_f32 with terms < 0) call it per call.
+struct Switches {
+    int gemm_terms = 2;         // MTTS_GEMM_TERMS 0 / 2 / 3 / 6: GEMM arithmetic of new contexts (gemm_f32.hip) -- 2 fp16 two-term split with scaled
+                                // residual, 6 bf16 three-term split (both fp32-equivalent), 0 native fp32 MFMA, 3 bf16 two-term split (looser, opt-in)
+    int arith16 = 0;            // MTTS_GEMM_TERMS 1 / 16 / 17: gemm_terms 2 with that 16-bit mode of the estimator (include/mtts.h mtts_set_arithmetic)
+    bool p16_on = true;         // MTTS_P16=0: fp16-split mode without P16 images between the kernels
+    bool chain_on = true;       // MTTS_CHAIN=0: a transformer block's row-local part as four GEMM launches instead of the chain launch (tblock_chain.hip)
+    int chain_ch = 256;         // MTTS_CHAIN_CH 128 / 256: hidden chunk of the chain's FeedForward at width 384
+    int chain_qb = 0;           // MTTS_CHAIN_QB: rows per workgroup of the chain launch (0 = by shape, chain_plan)
+    int chain_min_rows = 5761;  // MTTS_CHAIN_MIN_ROWS: estimator rows (B * T of a level) from which the chain replaces the four GEMM launches = where the pair
+                                // form's residency bound (120 tiles of 48 rows) ends; at width 384 -- 10304 rows: 138 vs ~160 us per block, 5152 rows:
+                                // 100 vs ~92 us (profiles/r03_chain_*)
+    bool pair_on = true;        // MTTS_CHAIN_PAIR=0: no pair form of the chain launch below chain_min_rows (mtts_create also clears it on less than the whole chip)
+    int pair_min_rows = 3000;   // MTTS_CHAIN_PAIR_MIN_ROWS: rows from which the pair form is taken (3864 rows: -0.3..0.5 ms per step, 2576 rows: +0.3;
+                                // profiles/r03_pair_ab.log)
+    int chain_pf = 16;          // MTTS_CHAIN_PF 0..64: prefetch workgroups of the chain launch, two per XCD (one alone takes ~93 us for the 7 MB stream and
+                                // is the tail of the launches without a q|k|v phase: 16 instead of 8 = -0.15 ms of GEMM time per step); 0: none
+    int resnet_fuse = 3;        // MTTS_RESNET_FUSE: Block1D as one conv + GroupNorm + Mish launch where it applies (resnet_conv.hip) -- bit 0 the first Block1D
+                                // of a ResNet block and the decoder's final one, bit 1 the second, bit 2 lifts the batch gate; 0 = the tiled launches
+};
+Switches read_switches();
+
 struct ProfRec { hipEvent_t e0, e1; int klass; double flops, bytes; std::string tag; };      // tag: a copy (launchers reuse their buffers)
 
 }  // namespace mtts
@@ -97,17 +121,9 @@ struct mtts_ctx {
                                   // single fp16 planes, one MFMA per MAC (BASELINE config #3); everything else as for terms 2
     bool bf16 = false;            // ... with bfloat16 planes (mtts_set_arithmetic(ctx, 17) / MTTS_GEMM_TERMS=17; half16 is set as well)
     bool half_now = false;        // set while the estimator's launches are being enqueued in that mode
-    bool fast16 = false;          // MTTS_GEMM_TERMS=1 at mtts_create: the estimator's P16 kernels multiply the fp16 heads only
-    bool p16_on = true;           // fp16-split mode: activations as P16 images between kernels (MTTS_P16=0 at mtts_create disables)
-    bool chain_on = true;         // transformer blocks' row-local part as one launch (tblock_chain.hip; MTTS_CHAIN=0 at mtts_create disables)
-    int chain_ch = 256;           // hidden chunk of the chain's FeedForward at width 384 (MTTS_CHAIN_CH at mtts_create: 128 / 256)
-    int chain_qb = 0;             // rows per workgroup (MTTS_CHAIN_QB at mtts_create; 0 = by shape)
-    int resnet_fuse = 3;          // Block1D as one conv + GroupNorm + Mish launch where it applies (resnet_conv.hip): bit 0 the first Block1D of a ResNet block and the decoder's final one, bit 1 the second, bit 2 lifts the batch gate (MTTS_RESNET_FUSE at mtts_create; 0 = the tiled launches)
-    int resnet_fuse_rows = mtts::CONV_GN_MAX_ROWS;   // ... up to this many rows per utterance (MTTS_RESNET_FUSE_ROWS at mtts_create: A/B runs)
-    bool pair_on = true;          // pair form of the chain launch for levels below chain_min_rows (MTTS_CHAIN_PAIR=0 at mtts_create disables)
+    bool fast16 = false;          // mtts_set_arithmetic(ctx, 1) / MTTS_GEMM_TERMS=1: the estimator's P16 kernels multiply the fp16 heads only
+    mtts::Switches sw;            // the run-time switches as mtts_create read them
     unsigned int pair_epoch = 0;  // flag value of the latest pair launch (unique per launch)
-    int chain_min_rows = 5761;    // (= where the pair form's residency bound, 120 tiles of 48 rows, ends) estimator rows (B * T of a level) from which the chain replaces the four GEMM launches (MTTS_CHAIN_MIN_ROWS):
-                                  // measured at width 384 -- 10304 rows: 138 vs ~160 us per block; 5152 rows: 100 vs ~92 us (profiles/r03_chain_*)
     mtts::DecW dec;
     mtts::EncW enc;
     // one thread at a time: the path's entry points hold this while they enqueue (per-call state above: cur_flag, half_now,

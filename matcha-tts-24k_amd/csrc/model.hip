@@ -13,6 +13,26 @@ static thread_local std::string g_err;
 void set_error(const std::string& m) { g_err = m; }
 const char* get_error() { return g_err.c_str(); }
 
+// The only reader of the environment (model.h Switches).  A value outside a switch's domain leaves its default.
+Switches read_switches() {
+    Switches w;
+    auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    auto on = [](const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); };
+    const int terms = num("MTTS_GEMM_TERMS", w.gemm_terms);
+    if (terms == 0 || terms == 2 || terms == 3 || terms == 6) w.gemm_terms = terms;
+    if (terms == 1 || terms == 16 || terms == 17) w.arith16 = terms;
+    w.p16_on = on("MTTS_P16");
+    w.chain_on = on("MTTS_CHAIN");
+    if (num("MTTS_CHAIN_CH", w.chain_ch) == 128) w.chain_ch = 128;
+    w.chain_qb = num("MTTS_CHAIN_QB", w.chain_qb);
+    w.chain_min_rows = num("MTTS_CHAIN_MIN_ROWS", w.chain_min_rows);
+    w.pair_on = on("MTTS_CHAIN_PAIR");
+    w.pair_min_rows = num("MTTS_CHAIN_PAIR_MIN_ROWS", w.pair_min_rows);
+    w.chain_pf = std::min(std::max(num("MTTS_CHAIN_PF", w.chain_pf), 0), 64);
+    w.resnet_fuse = num("MTTS_RESNET_FUSE", w.resnet_fuse) & 7;
+    return w;
+}
+
 #define HIP_OK(expr)                                                                        \
     do {                                                                                    \
         hipError_t _e = (expr);                                                             \
@@ -73,215 +93,26 @@ static int run_attn(mtts_ctx* c, const AttnArgs& a0, hipStream_t s) {
     LAUNCHB(c, 1, attn_flops(a), attn_bytes(a), s, launch_attention(a, s));
     return 0;
 }
-// prefetch workgroups of the chain launch (tblock_chain.hip): two per XCD (one alone takes ~93 us for the 7 MB stream and is the tail
-// of the launches without a q|k|v phase: 16 instead of 8 = -0.15 ms of GEMM time per step); MTTS_CHAIN_PF=<n> (0: none) for A/B runs
-static int chain_prefetch_wgs() {
-    static const int n = [] { const char* e = getenv("MTTS_CHAIN_PF"); const int v = e ? atoi(e) : 16; return v < 0 ? 0 : (v > 64 ? 64 : v); }();
-    return n;
-}
-// Launch plan of a chain launch over M rows (hidden chunk ch; qb_forced = MTTS_CHAIN_QB or 0): rows per workgroup and prefetch
-// workgroups.  32-row workgroups while they -- with the prefetchers -- are one round of the 256 CUs (a 32-row workgroup lives 99 us, a
-// 48-row one 116 us: both are bound by the 7 MB they stream, profiles/r03_chain_prefetch_stamps.log), the largest shape beyond; no
-// prefetchers when they would push a one-round grid into a second round.
-static void chain_plan(int M, int ch, int qb_forced, int* qb, int* pf) {
-    const int qb_big = ch == 256 ? 48 : 64, want = chain_prefetch_wgs();
-    const bool fits32 = (M + 31) / 32 + want <= 256;
+// Launch plan of a chain launch over M rows (hidden chunk ch; qb_forced = Switches::chain_qb or 0; want = Switches::chain_pf): rows
+// per workgroup and prefetch workgroups.  32-row workgroups while they -- with the prefetchers -- are one round of the chip's CUs (a
+// 32-row workgroup lives 99 us, a 48-row one 116 us: both are bound by the 7 MB they stream, profiles/r03_chain_prefetch_stamps.log),
+// the largest shape beyond; no prefetchers when they would push a one-round grid into a second round.
+static void chain_plan(int M, int ch, int qb_forced, int want, int* qb, int* pf) {
+    const int qb_big = ch == 256 ? 48 : 64;
+    const bool fits32 = (M + 31) / 32 + want <= CHIP_CUS;
     *qb = (qb_forced == 32 || qb_forced == qb_big) ? qb_forced : (fits32 ? 32 : qb_big);
     const int nwg = (M + *qb - 1) / *qb;
     *pf = want;
-    if (nwg <= 256 && nwg + *pf > 256) *pf = (want >= 8 && nwg + 8 <= 256) ? 8 : 0;
+    if (nwg <= CHIP_CUS && nwg + *pf > CHIP_CUS) *pf = (want >= 8 && nwg + 8 <= CHIP_CUS) ? 8 : 0;
 }
 static int run_chain(mtts_ctx* c, const ChainArgs& a0, hipStream_t s) {
     ChainArgs a = a0;
     a.range_flag = c->cur_flag;
-    { int qb_unused = 0; chain_plan(a.M, a.ch, a.qb, &qb_unused, &a.pf_wgs); }
-    if (a.pair) a.pf_wgs = chain_prefetch_wgs() ? 16 : 0;      // two per XCD, one per half (the model admits pair grids up to 240 workgroups)
+    { int qb_unused = 0; chain_plan(a.M, a.ch, a.qb, c->sw.chain_pf, &qb_unused, &a.pf_wgs); }
+    if (a.pair) a.pf_wgs = c->sw.chain_pf ? 16 : 0;      // two per XCD, one per half (the model admits pair grids up to 240 workgroups)
     LAUNCHB(c, 0, chain_flops(a), chain_bytes(a), s, launch_tblock_chain(a, s));
     return 0;
 }
-#ifdef MTTS_CHAIN_VERIFY
-// Diagnostic builds (tools/build_variant.sh ... -DMTTS_CHAIN_VERIFY): a chain launch that does not update its inputs in place is
-// run a second time into a scratch image and the two results are compared on the device -- per launch slot
-// [differing 16-byte chunks, first row, last row, first chunk, last chunk, rows, 0, 0] (mtts_debug_verify_read).
-constexpr int VERIFY_SLOTS = 8192;
-static int* g_verify = nullptr;
-static int g_verify_n = 0;
-__global__ void chain_verify_kernel(const uint4* a, const uint4* b, int rows, int cpr, int* out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)rows * cpr) return;
-    const uint4 x = a[i], y = b[i];
-    if (x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w) {
-        const int row = (int)(i / cpr), ch = (int)(i % cpr);
-        atomicAdd(out, 1); atomicMin(out + 1, row); atomicMax(out + 2, row); atomicMin(out + 3, ch); atomicMax(out + 4, ch);
-    }
-}
-// the first launch whose executions 1 and 2 differ: both images kept for inspection (mtts_debug_verify_snapshot)
-static int* g_snap_flag = nullptr;
-static uint4 *g_snap_a = nullptr, *g_snap_b = nullptr;
-static size_t g_snap_bytes = 0;
-__global__ void verify_claim_kernel(const int* slot, int* flag, int id) { if (slot[0] > 0 && flag[0] == 0) flag[0] = id; }
-__global__ void verify_copy_kernel(const int* flag, int id, const uint4* a, const uint4* b, uint4* sa, uint4* sb, long n) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (flag[0] != id || i >= n) return;
-    sa[i] = a[i]; sb[i] = b[i];
-}
-extern "C" int mtts_debug_verify_snapshot(void* host_a, void* host_b, size_t bytes) {
-    if (!g_snap_flag) return 0;
-    (void)hipDeviceSynchronize();
-    int id = 0;
-    (void)hipMemcpy(&id, g_snap_flag, sizeof(int), hipMemcpyDeviceToHost);
-    if (id == 0 || bytes < g_snap_bytes) return 0;
-    (void)hipMemcpy(host_a, g_snap_a, g_snap_bytes, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(host_b, g_snap_b, g_snap_bytes, hipMemcpyDeviceToHost);
-    (void)hipMemset(g_snap_flag, 0, sizeof(int));
-    return id;
-}
-#ifdef MTTS_CHAIN_DUMP
-// LDS dumps of executions 1 and 2 (tblock_chain.hip CH_DUMP), compared per section: [x0, ct, x1, srow, h0, x2, 0, 0] per launch
-static char *g_dump_a = nullptr, *g_dump_b = nullptr;
-static int* g_sect = nullptr;
-__global__ void dump_compare_kernel(const uint4* a, const uint4* b, long n, int wg_chunks, int e0, int e1, int e2, int e3, int e4, int* out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint4 x = a[i], y = b[i];
-    if (x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w) {
-        const int o = (int)(i % wg_chunks);
-        const int sec = o < e0 ? 0 : o < e1 ? 1 : o < e2 ? 2 : o < e3 ? 3 : o < e4 ? 4 : 5;
-        atomicAdd(out + sec, 1);
-        if (sec == 1) atomicMin(out + 6, o - e0);       // first differing chunk of the constants
-        if (sec == 3) atomicMin(out + 7, o - e2);
-    }
-}
-extern "C" int mtts_debug_verify_sections(int* out, int max_launches) {
-    if (!g_sect) return 0;
-    (void)hipDeviceSynchronize();
-    (void)hipMemcpy(out, g_sect, (size_t)max_launches * 8 * sizeof(int), hipMemcpyDeviceToHost);
-    std::vector<int> h((size_t)VERIFY_SLOTS * 4, 0);
-    for (int k = 0; k < VERIFY_SLOTS / 2; ++k) { h[8 * k + 6] = 1 << 30; h[8 * k + 7] = 1 << 30; }
-    (void)hipMemcpy(g_sect, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice);
-    return 1;
-}
-#endif
-#ifdef MTTS_CHAIN_PROBE
-static unsigned int *g_probe_a = nullptr, *g_probe_b = nullptr, *g_probe_sa = nullptr, *g_probe_sb = nullptr;
-static int g_probe_wgs = 0;
-__global__ void probe_keep_kernel(const int* flag, int id, const unsigned int* a, const unsigned int* b, unsigned int* sa, unsigned int* sb, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (flag[0] != id || i >= n) return;
-    sa[i] = a[i]; sb[i] = b[i];
-}
-extern "C" int mtts_debug_probe_read(unsigned int* host_a, unsigned int* host_b, int max_wgs) {
-    if (!g_probe_sa) return 0;
-    (void)hipDeviceSynchronize();
-    const int n = g_probe_wgs < max_wgs ? g_probe_wgs : max_wgs;
-    (void)hipMemcpy(host_a, g_probe_sa, (size_t)n * 8 * 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(host_b, g_probe_sb, (size_t)n * 8 * 4, hipMemcpyDeviceToHost);
-    return n;
-}
-#endif
-static void verify_reset() {
-    std::vector<int> h((size_t)VERIFY_SLOTS * 8, 0);
-    for (int k = 0; k < VERIFY_SLOTS; ++k) { h[8 * k + 1] = 1 << 30; h[8 * k + 3] = 1 << 30; h[8 * k + 2] = -1; h[8 * k + 4] = -1; }
-    if (!g_verify) (void)hipMalloc(&g_verify, h.size() * sizeof(int));
-    (void)hipMemcpy(g_verify, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice);
-    g_verify_n = 0;
-}
-static int run_chain_verified(mtts_ctx* c, const ChainArgs& a0, _Float16* scratch, hipStream_t s) {
-    ChainArgs a = a0;
-    if (!g_verify) verify_reset();
-#ifdef MTTS_CHAIN_DUMP
-    {
-        const size_t wgb = 3 * (size_t)(a.qb * a.C * 4) + 18 * a.C * 4 + 2 * a.qb * 4 + a.qb * a.ch * 4, nwgs = (a.M + a.qb - 1) / a.qb;
-        if (!g_dump_a) {
-            (void)hipMalloc(&g_dump_a, wgb * nwgs); (void)hipMalloc(&g_dump_b, wgb * nwgs);
-            (void)hipMalloc(&g_sect, (size_t)VERIFY_SLOTS * 4 * sizeof(int));
-            std::vector<int> h((size_t)VERIFY_SLOTS * 4, 0);
-            for (int k = 0; k < VERIFY_SLOTS / 2; ++k) { h[8 * k + 6] = 1 << 30; h[8 * k + 7] = 1 << 30; }
-            (void)hipMemcpy(g_sect, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice);
-        }
-        if (a.x_out != a.x16) a.kstamp = reinterpret_cast<unsigned long long*>(g_dump_a);
-    }
-#endif
-#ifdef MTTS_CHAIN_PROBE
-    {
-        const int nwgs = (a.M + a.qb - 1) / a.qb;
-        if (!g_probe_a) {
-            g_probe_wgs = nwgs;
-            (void)hipMalloc(&g_probe_a, (size_t)nwgs * 32); (void)hipMalloc(&g_probe_b, (size_t)nwgs * 32);
-            (void)hipMalloc(&g_probe_sa, (size_t)nwgs * 32); (void)hipMalloc(&g_probe_sb, (size_t)nwgs * 32);
-        }
-        if (a.x_out != a.x16 && nwgs == g_probe_wgs) {
-            (void)hipMemsetAsync(g_probe_a, 0, (size_t)nwgs * 32, s); (void)hipMemsetAsync(g_probe_b, 0, (size_t)nwgs * 32, s);
-            a.kstamp = reinterpret_cast<unsigned long long*>(g_probe_a);
-        }
-    }
-#endif
-    RET_IF(run_chain(c, a, s));
-    if (a.pair) return 0;            // (a pair launch's flags carry one epoch: it cannot simply be executed again)
-    if (a.x_out == a.x16 || g_verify_n + 2 > VERIFY_SLOTS) return 0;
-    ChainArgs b = a, b3 = a;
-    b.x_out = scratch;
-    b3.x_out = scratch + (size_t)a.M * 2 * a.C;
-    b3.kstamp = nullptr;
-#ifdef MTTS_CHAIN_PROBE
-    if (a.kstamp) b.kstamp = reinterpret_cast<unsigned long long*>(g_probe_b);
-#endif
-#ifdef MTTS_CHAIN_DUMP
-    const int xt = a.qb * a.C * 4, ctb = 18 * a.C * 4, sr = 2 * a.qb * 4, ht = a.qb * a.ch * 4;
-    const size_t wg_bytes = 3 * (size_t)xt + ctb + sr + ht, nwg = (a.M + a.qb - 1) / a.qb;
-    if (!g_dump_a) {
-        (void)hipMalloc(&g_dump_a, wg_bytes * nwg); (void)hipMalloc(&g_dump_b, wg_bytes * nwg);
-        (void)hipMalloc(&g_sect, (size_t)VERIFY_SLOTS * 4 * sizeof(int));
-        std::vector<int> h((size_t)VERIFY_SLOTS * 4, 0);
-        for (int k = 0; k < VERIFY_SLOTS / 2; ++k) { h[8 * k + 6] = 1 << 30; h[8 * k + 7] = 1 << 30; }
-        (void)hipMemcpy(g_sect, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice);
-    }
-    b.kstamp = reinterpret_cast<unsigned long long*>(g_dump_b);
-#endif
-    RET_IF(run_chain(c, b, s));
-    RET_IF(run_chain(c, b3, s));
-    const int cpr = a.C / 4;         // 16-byte chunks per image row
-    const long n = (long)a.M * cpr;
-    // two slots per launch: execution 1 vs 2, execution 2 vs 3
-    int* slot = g_verify + 8 * (size_t)g_verify_n++;
-    hipLaunchKernelGGL(chain_verify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                       reinterpret_cast<const uint4*>(a.x_out), reinterpret_cast<const uint4*>(b.x_out), a.M, cpr, slot);
-    if (!g_snap_flag) {
-        g_snap_bytes = (size_t)n * 16;
-        (void)hipMalloc(&g_snap_flag, sizeof(int)); (void)hipMemset(g_snap_flag, 0, sizeof(int));
-        (void)hipMalloc(&g_snap_a, g_snap_bytes); (void)hipMalloc(&g_snap_b, g_snap_bytes);
-    }
-    if ((size_t)n * 16 == g_snap_bytes) {
-        hipLaunchKernelGGL(verify_claim_kernel, dim3(1), dim3(1), 0, s, slot, g_snap_flag, g_verify_n);
-        hipLaunchKernelGGL(verify_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g_snap_flag, g_verify_n,
-                           reinterpret_cast<const uint4*>(a.x_out), reinterpret_cast<const uint4*>(b.x_out), g_snap_a, g_snap_b, n);
-#ifdef MTTS_CHAIN_PROBE
-        if (a.kstamp) hipLaunchKernelGGL(probe_keep_kernel, dim3((unsigned)((g_probe_wgs * 8 + 255) / 256)), dim3(256), 0, s, g_snap_flag, g_verify_n,
-                                         g_probe_a, g_probe_b, g_probe_sa, g_probe_sb, g_probe_wgs * 8);
-#endif
-    }
-#ifdef MTTS_CHAIN_DUMP
-    {
-        const int wgc = (int)(wg_bytes / 16), e0 = xt / 16, e1 = e0 + ctb / 16, e2 = e1 + xt / 16, e3 = e2 + sr / 16, e4 = e3 + ht / 16;
-        const long nd = (long)wgc * (long)nwg;
-        hipLaunchKernelGGL(dump_compare_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, s, reinterpret_cast<const uint4*>(g_dump_a),
-                           reinterpret_cast<const uint4*>(g_dump_b), nd, wgc, e0, e1, e2, e3, e4, g_sect + 8 * (size_t)(g_verify_n / 2));
-    }
-#endif
-    slot = g_verify + 8 * (size_t)g_verify_n++;
-    hipLaunchKernelGGL(chain_verify_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                       reinterpret_cast<const uint4*>(b.x_out), reinterpret_cast<const uint4*>(b3.x_out), a.M, cpr, slot);
-    return 0;
-}
-extern "C" int mtts_debug_verify_read(int* out, int max_slots) {
-    if (!g_verify) return 0;
-    (void)hipDeviceSynchronize();
-    const int n = g_verify_n < max_slots ? g_verify_n : max_slots;
-    (void)hipMemcpy(out, g_verify, (size_t)n * 8 * sizeof(int), hipMemcpyDeviceToHost);
-    verify_reset();
-    return n;
-}
-#endif
 static int run_gn_apply(mtts_ctx* c, const GnApplyArgs& a0, hipStream_t s) {
     GnApplyArgs a = a0;
     a.range_flag = c->cur_flag;
@@ -618,12 +449,12 @@ static int pack_all(mtts_ctx* c, bool dry = false) {
         D.tmlp = p;
     }
     // fragment streams of the transformer blocks' row-local chains (tblock_chain.hip): fp16-split arithmetic, P16 flow only
-    if (P.ok && c->chain_on && c->gemm_terms == 2 && !c->half16 && !c->fast16 && c->p16_on && g.dec_head_dim == 64) {
+    if (P.ok && c->sw.chain_on && c->gemm_terms == 2 && !c->half16 && !c->fast16 && c->sw.p16_on && g.dec_head_dim == 64) {
         const int nb = g.dec_n_blocks;
         for (size_t k = 0; k < D.tb.size(); ++k) {
             TBlockW& t = D.tb[k];
             const int C = t.out.N, nq = ((int)(k % nb) + 1 < nb) ? D.tb[k + 1].qkv.N : 0;
-            const int ch = (C == 384 && c->chain_ch == 256) ? 256 : 128;
+            const int ch = (C == 384 && c->sw.chain_ch == 256) ? 256 : 128;
             if (!chain_supported(C, inner, nq) || t.ff1.N != 4 * C || t.ff1.ktap != C || t.ff2.ktap != 4 * C || t.out.ktap != inner) continue;
             if (nq && D.tb[k + 1].qkv.ktap != C) continue;
             t.chain_frags = chain_stream_frags(C, inner, ch, nq);
@@ -631,7 +462,7 @@ static int pack_all(mtts_ctx* c, bool dry = false) {
             t.chain_nqkv = nq;
             t.next = nq ? (int)k + 1 : -1;
             t.chain = P.alloc((size_t)t.chain_frags * CHAIN_WAVES * 256);
-            if (c->pair_on && chain_supported_pair(C, inner, ch, nq)) {
+            if (c->sw.pair_on && chain_supported_pair(C, inner, ch, nq)) {
                 t.chain_pair_frags = chain_stream_frags_pair(C, inner, ch, nq);
                 t.chain_pair = P.alloc((size_t)t.chain_pair_frags * 2 * CHAIN_WAVES * 256);
                 if (!dry) chain_stream_pack_pair(C, inner, ch, nq, &c->image[t.out.w], &c->image[t.ff1.w], &c->image[t.ff2.w],
@@ -659,15 +490,6 @@ static int pack_all(mtts_ctx* c, bool dry = false) {
 }
 
 static inline const float* W(const mtts_ctx* c, size_t off) { return c->d_image + off; }
-
-// GEMM arithmetic of new contexts (gemm_f32.hip): 2 (default) fp16 two-term split with scaled residual, 6 bf16 three-term
-// split (both fp32-equivalent), 0 native fp32 MFMA, 3 bf16 two-term split (looser, opt-in).  MTTS_GEMM_TERMS overrides.
-static int default_gemm_terms() {
-    const char* e = getenv("MTTS_GEMM_TERMS");
-    if (!e) return 2;
-    const int t = atoi(e);
-    return (t == 0 || t == 2 || t == 3 || t == 6) ? t : 2;
-}
 
 static void panel_args(const mtts_ctx* c, const Panel& p, GemmArgs& a) {
     a.w = W(c, p.w);
@@ -734,7 +556,7 @@ struct DecBufs {
 // every block on fp32 rows.
 static bool p16_decoder(const mtts_ctx* c) {
     const mtts_config& g = c->cfg;
-    if (!c->p16_on || c->gemm_terms != 2 || g.dec_head_dim != 64 || g.dec_n_blocks < 1 || (g.n_feats & 1)) return false;
+    if (!c->sw.p16_on || c->gemm_terms != 2 || g.dec_head_dim != 64 || g.dec_n_blocks < 1 || (g.n_feats & 1)) return false;
     for (int l = 0; l < g.dec_levels; ++l)
         if (g.dec_channels[l] % 64) return false;
     return true;
@@ -868,11 +690,10 @@ static int bind_state(mtts_ctx* c, DecBufs& d, const float* xin, Actv& x, hipStr
 }
 
 // GroupNorm statistics from the conv GEMM's epilogue instead of a gn_partial pass over its output (gemm_epilogue.h): entries per
-// wave tile and utterance part, so an utterance must be at least one wave tile long, and groups of >= 32 channels;
-// MTTS_GN_FUSE=0 keeps the separate pass (A/B runs).  Returns the wave-tile height (the consumers' tile_rows) or 0.
+// wave tile and utterance part, so an utterance must be at least one wave tile long, and groups of >= 32 channels.
+// Returns the wave-tile height (the consumers' tile_rows) or 0.
 static int gn_fuse_rows(const GemmArgs& a, int C, int G, int T) {
-    static const bool on = [] { const char* e = getenv("MTTS_GN_FUSE"); return !(e && e[0] == '0'); }();
-    if (!on || !a.a16_0 || a.fast16 || (C % 64) || (C % G) || (C / G) < 32 || ((C / G) & 7)) return 0;
+    if (!a.a16_0 || a.fast16 || (C % 64) || (C % G) || (C / G) < 32 || ((C / G) & 7)) return 0;
     const int rows = gemm_p16_wave_rows(a);
     return T >= rows ? rows : 0;
 }
@@ -895,14 +716,14 @@ static int conv_gn_stats(mtts_ctx* c, DecBufs& d, GemmArgs& a, int lvl, const Ve
 }
 
 // Where the one-launch Block1D pays (measured): its grid is 8 B workgroups of one per CU, so it needs a batch
-// that fills the 256 CUs once -- at B = 64 (two rounds) the tiled launches win by 0.5-1.0 ms per step -- and not much less: the
+// that fills the chip's CUs once -- at B = 64 (two rounds) the tiled launches win by 0.5-1.0 ms per step -- and not much less: the
 // short form (<= 192 rows) from half the chip (B = 16: -0.35 ms), the long form only near a full chip (B = 16: +0.35 ms, B = 32:
 // -0.5 ms).  Bit 2 of MTTS_RESNET_FUSE lifts the batch gate (tests run small batches).
 static bool block1d_fusable(const mtts_ctx* c, const DecBufs& d, int T, int C) {
-    if (!d.p16 || c->half_now || c->fast16 || !conv_gn_supported(T, C) || T > c->resnet_fuse_rows) return false;
-    if (c->resnet_fuse & 4) return true;
+    if (!d.p16 || c->half_now || c->fast16 || !conv_gn_supported(T, C)) return false;
+    if (c->sw.resnet_fuse & 4) return true;
     const int wgs = 8 * d.B;
-    return wgs <= 256 && wgs >= (T <= CONV_GN_SPLIT_ROWS ? 128 : 192);
+    return wgs <= CHIP_CUS && wgs >= (T <= CONV_GN_SPLIT_ROWS ? 128 : 192);
 }
 
 // A Block1D as one launch (resnet_conv.hip): the conv `a` (input and panel already bound) -> GroupNorm -> Mish -> mask [-> + chbias
@@ -930,7 +751,7 @@ static int resnet_block(mtts_ctx* c, DecBufs& d, const ResnetW& r, const Actv& i
     bind_in(d, a, 0, in0);
     if (in1.p) bind_in(d, a, 1, in1);
     const bool fusable = block1d_fusable(c, d, T, C);
-    if (fusable && (c->resnet_fuse & 1)) {
+    if (fusable && (c->sw.resnet_fuse & 1)) {
         // the first Block1D as ONE launch (resnet_conv.hip): a workgroup per (utterance, GroupNorm group) owns its statistics, so
         // neither the conv's fp32 rows nor a gn_apply pass exist.  Width 384 at 65..384 rows per utterance (both levels of the
         // benchmark shape); every other shape keeps the launches below.
@@ -949,7 +770,7 @@ static int resnet_block(mtts_ctx* c, DecBufs& d, const ResnetW& r, const Actv& i
     panel_args(c, r.res, rc); rows_plain(rc, B, T);
     bind_in(d, rc, 0, in0);
     if (in1.p) bind_in(d, rc, 1, in1);
-    if (fusable && (c->resnet_fuse & 2)) {
+    if (fusable && (c->sw.resnet_fuse & 2)) {
         // the second Block1D the same way, its masked result as an image in the slot the conv's fp32 rows would take; the 1x1
         // residual conv adds it as its image residual and leaves x with its LayerNorm moments: no fp32 rows, no statistics
         // entries to merge in the residual conv's prologue
@@ -962,8 +783,7 @@ static int resnet_block(mtts_ctx* c, DecBufs& d, const ResnetW& r, const Actv& i
     }
     GnApplyArgs g2;
     RET_IF(conv_gn_stats(c, d, b, lvl, r.gn2_g, r.gn2_b, r.gn2_bs, g2, s));
-    static const bool tail_on = [] { const char* e = getenv("MTTS_GN_TAIL"); return !(e && e[0] == '0'); }();   // A/B runs
-    if (tail_on && g2.tile_rows && T >= 2 * gemm_p16_wave_rows(rc)) {      // a workgroup's rows in at most two utterances
+    if (g2.tile_rows && T >= 2 * gemm_p16_wave_rows(rc)) {      // a workgroup's rows in at most two utterances
         // The 1x1 residual conv finishes the block: its epilogue adds Mish(GroupNorm(conv2 output)) * mask from the tile
         // statistics conv2 left, and writes x's image + LayerNorm moments -- no gn_apply pass, no residual round trip.
         rc.gnr_y = d.Y; rc.gnr_stats = d.gns; rc.gnr_tile_rows = g2.tile_rows; rc.gnr_groups = 8;
@@ -1004,9 +824,7 @@ static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, int C, i
     // the row-local part as one launch (tblock_chain.hip) when the stream was packed and the batch is large enough that a
     // workgroup per QB rows fills the chip: every workgroup streams ALL of the chain's weights (~7 MB at width 384), which
     // only pays when their cost is shared by many rows per CU
-    static const int chain_only = [] { const char* e = getenv("MTTS_CHAIN_ONLY"); return !e ? 0 : (e[0] == 'f' ? 1 : 2); }();   // diagnostic
-    const bool chain = t.chain_frags > 0 && d.p16 && !c->half_now && M >= c->chain_min_rows && (emit_stats ? t.chain_nqkv > 0 : true) &&
-                       (chain_only == 0 || (chain_only == 1) == emit_stats);
+    const bool chain = t.chain_frags > 0 && d.p16 && !c->half_now && M >= c->sw.chain_min_rows && (emit_stats ? t.chain_nqkv > 0 : true);
     if (!d.qkv_ready) {
         GemmArgs q;
         panel_args(c, t.qkv, q); rows_plain(q, B, T);
@@ -1023,9 +841,8 @@ static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, int C, i
     // below that row count: the pair form -- two workgroups of one XCD per 48-row tile, each streaming half of the FeedForward
     // and of the q|k|v passes -- while all of them (and the prefetchers) are resident at once
     const int tiles48 = (M + 47) / 48;
-    static const int pair_min = [] { const char* e = getenv("MTTS_CHAIN_PAIR_MIN_ROWS"); return e ? atoi(e) : 3000; }();      // (3864 rows: -0.3..0.5 ms per step, 2576 rows: +0.3; profiles/r03_pair_ab.log)
-    const bool pair = !chain && c->pair_on && t.chain_pair_frags > 0 && d.p16 && !c->half_now && d.pair_flag && M >= pair_min &&
-                      16 * ((tiles48 + 7) / 8) + 16 <= 256 && (emit_stats ? t.chain_nqkv > 0 : true);
+    const bool pair = !chain && c->sw.pair_on && t.chain_pair_frags > 0 && d.p16 && !c->half_now && d.pair_flag && M >= c->sw.pair_min_rows &&
+                      16 * ((tiles48 + 7) / 8) + 16 <= CHIP_CUS && (emit_stats ? t.chain_nqkv > 0 : true);
     if (chain || pair) {                  // (image flow, P16: rows of 2 halves per channel)
         ChainArgs a;
         a.M = M; a.C = C; a.inner = inner;
@@ -1042,7 +859,7 @@ static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, int C, i
             d.qkv_ready = true;
         } else { a.x_out = image(dst); a.x_out_mask = d.mask[lvl]; }
         a.ch = t.chain_ch;
-        { int pf_unused = 0; chain_plan(M, a.ch, c->chain_qb, &a.qb, &pf_unused); }
+        { int pf_unused = 0; chain_plan(M, a.ch, c->sw.chain_qb, c->sw.chain_pf, &a.qb, &pf_unused); }
         if (pair) {
             a.pair = 1; a.qb = 48;
             a.wstream = reinterpret_cast<const _Float16*>(W(c, t.chain_pair)); a.stream_frags = t.chain_pair_frags;
@@ -1051,12 +868,7 @@ static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, int C, i
             a.pair_epoch = ++c->pair_epoch;
             if (c->pair_epoch == 0) a.pair_epoch = ++c->pair_epoch;
         }
-#ifdef MTTS_CHAIN_VERIFY
-        RET_IF(run_chain_verified(c, a, image(d.FF), s));
-#else
-        RET_IF(run_chain(c, a, s));
-#endif
-        return 0;
+        return run_chain(c, a, s);
     }
     GemmArgs o;
     panel_args(c, t.out, o); rows_plain(o, B, T);
@@ -1160,7 +972,7 @@ static int unet_eval(mtts_ctx* c, DecBufs& d, const float* xin, int ev, const Fi
     GemmArgs a;
     panel_args(c, D.final_conv, a); rows_plain(a, B, T); taps_centered(a, 3);
     bind_in(d, a, 0, cur);
-    if ((c->resnet_fuse & 1) && block1d_fusable(c, d, T, C0)) {
+    if ((c->sw.resnet_fuse & 1) && block1d_fusable(c, d, T, C0)) {
         RET_IF(block1d_fused(c, d, a, 0, D.fgn_g, D.fgn_b, D.fgn_bs, nullptr, d.H, s));
     } else {
         GnApplyArgs ga;
@@ -1252,20 +1064,13 @@ mtts_ctx* mtts_create(const mtts_config* cfg) {
     if (!why.empty()) { set_error(why); return nullptr; }
     mtts_ctx* c = new mtts_ctx();
     c->cfg = g;
-    c->gemm_terms = default_gemm_terms();
-    { const char* e = getenv("MTTS_GEMM_TERMS"); c->fast16 = e && atoi(e) == 1; c->half16 = e && (atoi(e) == 16 || atoi(e) == 17); c->bf16 = e && atoi(e) == 17; }   // 1 / 16 / 17: 16-bit modes (include/mtts.h)
-    { const char* e = getenv("MTTS_P16"); c->p16_on = !(e && e[0] == '0'); }
-    { const char* e = getenv("MTTS_CHAIN"); c->chain_on = !(e && e[0] == '0'); }
-    { const char* e = getenv("MTTS_CHAIN_CH"); c->chain_ch = (e && atoi(e) == 128) ? 128 : 256; }
-    { const char* e = getenv("MTTS_CHAIN_QB"); c->chain_qb = e ? atoi(e) : 0; }
-    { const char* e = getenv("MTTS_CHAIN_MIN_ROWS"); if (e) c->chain_min_rows = atoi(e); }
-    { const char* e = getenv("MTTS_CHAIN_PAIR"); c->pair_on = !(e && e[0] == '0'); }
-    { const char* e = getenv("MTTS_RESNET_FUSE"); if (e) c->resnet_fuse = atoi(e) & 7; }
-    { const char* e = getenv("MTTS_RESNET_FUSE_ROWS"); if (e) c->resnet_fuse_rows = atoi(e); }
-    if (c->pair_on) {          // the pair form's residency bound assumes the whole 256-CU chip: a partitioned or smaller device runs without it
+    c->sw = read_switches();
+    c->gemm_terms = c->sw.gemm_terms;
+    c->fast16 = c->sw.arith16 == 1; c->half16 = c->sw.arith16 >= 16; c->bf16 = c->sw.arith16 == 17;
+    if (c->sw.pair_on) {       // the pair form's residency bound assumes the whole chip: a partitioned or smaller device runs without it
         int dev = 0;
         hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount < 256) c->pair_on = false;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount < CHIP_CUS) c->sw.pair_on = false;
         (void)hipGetLastError();             // (no device at all -- the CPU-side packing tests -- leaves the setting as it is)
     }
     return c;
@@ -1320,7 +1125,7 @@ int mtts_weights_signature(mtts_ctx* c, char* buf, int64_t n) {
     const int v[] = {MTTS_ABI_VERSION, MTTS_IMAGE_REVISION, g.n_feats, g.n_spks, g.spk_emb_dim, g.n_vocab, g.enc_channels, g.enc_filter,
                      g.enc_heads, g.enc_layers, g.enc_kernel, g.prenet_layers, g.prenet_kernel, g.dp_filter, g.dp_kernel, g.dp_layers,
                      g.dec_levels, g.dec_channels[0], g.dec_channels[1], g.dec_channels[2], g.dec_channels[3], g.dec_head_dim, g.dec_heads,
-                     g.dec_n_blocks, g.dec_mid_blocks, c->gemm_terms, c->half16, c->bf16, c->fast16, c->p16_on, c->chain_on, c->chain_ch, c->pair_on};
+                     g.dec_n_blocks, g.dec_mid_blocks, c->gemm_terms, c->half16, c->bf16, c->fast16, c->sw.p16_on, c->sw.chain_on, c->sw.chain_ch, c->sw.pair_on};
     std::string sig = "mtts";
     for (int x : v) sig += "-" + std::to_string(x);
     if ((int64_t)sig.size() + 1 > n) { set_error("mtts_weights_signature: buffer too small"); return -1; }
@@ -1395,7 +1200,7 @@ int mtts_decoder_forward(mtts_ctx* c, const float* d_x, const float* d_mask, con
     RET_IF(plan_decoder(c, B, T, MAX_EVALS, 2, 4, ws, d));
     if (ws.overflow) { set_error("decoder workspace too small"); return -1; }
     RET_IF(begin_call(c, d_ws, s));
-    if (c->pair_on) HIP_OK(launch_fill_cols(reinterpret_cast<float*>(d.pair_flag), 1, 512, 0, 512, 0.f, s));
+    if (c->sw.pair_on) HIP_OK(launch_fill_cols(reinterpret_cast<float*>(d.pair_flag), 1, 512, 0, 512, 0.f, s));
     const int nf = c->cfg.n_feats;
     RET_IF(build_frames(c, d, d_mask, nullptr, T, s));
     LAUNCH(c, 2, 0, s, launch_fill_cols(d.xmu, B * T, d.ldx, 2 * nf, d.ldx - 2 * nf, 0.f, s));
@@ -1428,7 +1233,7 @@ static int solve_core(mtts_ctx* c, const float* d_x0, const float* d_mu, const f
     RET_IF(plan_decoder(c, B, T, MAX_EVALS, 2, 4, ws, d));
     if (ws.overflow) { set_error("decoder workspace too small"); return -1; }
     RET_IF(begin_call(c, d_ws, s));
-    if (c->pair_on) HIP_OK(launch_fill_cols(reinterpret_cast<float*>(d.pair_flag), 1, 512, 0, 512, 0.f, s));
+    if (c->sw.pair_on) HIP_OK(launch_fill_cols(reinterpret_cast<float*>(d.pair_flag), 1, 512, 0, 512, 0.f, s));
     const int nf = c->cfg.n_feats, M = B * T;
     RET_IF(build_frames(c, d, d_mask, d_y_len, T_src, s));
     // state rows: x | mu | zero pad.  z = mu + noise when use_mu_prior (reference flow_matching.py:52-55)
@@ -1593,7 +1398,7 @@ int mtts_text_encoder_forward(mtts_ctx* c, const int64_t* d_x, const int64_t* d_
         // FFN: conv k5 -> ReLU -> mask -> conv k5.  The second conv is the encoder's long-K GEMM (K = 5 x filter) on a grid
         // far under one round of workgroups: in the fp16-split mode the hidden layer is handed over as a masked P16 image
         // (written by the first conv's epilogue) so that it runs on gemm_p16.hip's prefetch ring (198 -> ~80 us at B = 32).
-        const bool ffn_p16 = c->p16_on && c->gemm_terms == 2 && (g.enc_filter % 32) == 0;
+        const bool ffn_p16 = c->sw.p16_on && c->gemm_terms == 2 && (g.enc_filter % 32) == 0;
         _Float16* F16 = reinterpret_cast<_Float16*>(e.F1);        // same bytes as the fp32 hidden layer
         GemmArgs f1;
         panel_args(c, E.ffn1[l], f1); rows_plain(f1, B, Tx); taps_centered(f1, g.enc_kernel);
@@ -1695,7 +1500,7 @@ int mtts_gemm_f32(const float* d_a, int lda, int B, int T_in, int C, int ntaps, 
                   int terms, void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (ntaps < 1 || ntaps > MAX_TAPS) { set_error("ntaps out of range"); return -1; }
-    if (terms < 0) terms = default_gemm_terms();
+    if (terms < 0) terms = read_switches().gemm_terms;
     if (terms != 0 && terms != 2 && terms != 3 && terms != 6) { set_error("terms must be 0, 2, 3 or 6"); return -1; }
     const size_t npanel = (size_t)round_up(N, GEMM_BN) * ntaps * round_up(C, GEMM_BK);
     float* planes = static_cast<float*>(d_wpacked) + ((npanel + 63) & ~size_t(63));
@@ -1860,7 +1665,7 @@ int mtts_groupnorm_mish(const float* d_y, const float* d_gamma, const float* d_b
 // the model's launch plan for M rows (test entry; no GPU): rows per workgroup and prefetch workgroups
 int mtts_chain_plan(int M, int ch, int* qb, int* prefetch_wgs) {
     if (M <= 0 || (ch != 128 && ch != 256) || !qb || !prefetch_wgs) { set_error("mtts_chain_plan: bad argument"); return -1; }
-    chain_plan(M, ch, 0, qb, prefetch_wgs);
+    chain_plan(M, ch, 0, read_switches().chain_pf, qb, prefetch_wgs);
     return 0;
 }
 int64_t mtts_chain_stream_frags(int C, int inner, int ch, int n_qkv) {
@@ -1956,7 +1761,7 @@ static int tblock_chain_entry(bool pair, const float* d_att, const float* d_x, i
     if (n_qkv) { a.wsum_qkv = d_c + 18 * C; a.b_qkv = d_c + 18 * C + n_qkv; a.n_qkv = n_qkv; a.qkv16 = q16; a.ld_qkv = 2 * n_qkv; }
     a.x_out = xo16; a.ld_out = 2 * C; a.x_out_mask = d_out_mask;
     a.qb = qb; a.ch = ch;
-    a.pf_wgs = chain_prefetch_wgs();
+    a.pf_wgs = read_switches().chain_pf;
     if (pair) { a.pair = 1; a.pair_part = d_part; a.pair_flag = d_flag; a.pair_epoch = 1; a.pf_wgs = a.pf_wgs ? 16 : 0; }
 #ifdef MTTS_CHAIN_STAMP
     a.kstamp = reinterpret_cast<unsigned long long*>(d_qkv_out);      // (diagnostic build: the stamps land in the q|k|v output buffer)
@@ -2001,7 +1806,7 @@ int mtts_tblock_chain_pair_timed(const float* d_att, const float* d_x, int M, in
 }
 
 // ------------------------------------------------------------------------------------------------ measurement
-int mtts_gemm_terms(mtts_ctx* c) { return c ? (c->bf16 ? 17 : c->half16 ? 16 : c->fast16 ? 1 : c->gemm_terms) : default_gemm_terms(); }
+int mtts_gemm_terms(mtts_ctx* c) { return c ? (c->bf16 ? 17 : c->half16 ? 16 : c->fast16 ? 1 : c->gemm_terms) : read_switches().gemm_terms; }
 
 int mtts_prof_enable(mtts_ctx* c, int on) {
     if (!c) { set_error("null context"); return -1; }
@@ -2157,7 +1962,7 @@ mtts_vocos* mtts_vocos_create(int n_mels, int dim, int inter, int layers, int n_
         return nullptr;
     }
     mtts_vocos* v = new mtts_vocos();
-    v->base.gemm_terms = default_gemm_terms();
+    v->base.gemm_terms = read_switches().gemm_terms;
     v->n_mels = n_mels; v->dim = dim; v->inter = inter; v->layers = layers; v->n_fft = n_fft; v->hop = hop;
     return v;
 }

@@ -270,18 +270,6 @@ __global__ __launch_bounds__(64 * CHAIN_NW, 1) void tblock_chain_kernel(const Ch
 #endif
         return;
     }
-#ifdef MTTS_CHAIN_DUMP
-    // diagnostic: copies of the LDS regions at the phase boundaries, per workgroup [x0 | ct | x1 | srow | h0 | x2] (p.kstamp = base)
-    constexpr int DUMP_WG = 3 * K::XT_BYTES + K::CT_FLOATS * 4 + 2 * QB * 4 + K::HT_BYTES;
-    auto dump = [&](int sect_off, const char* src, int bytes) {
-        if (!p.kstamp) return;
-        char* dst = reinterpret_cast<char*>(p.kstamp) + (size_t)wg * DUMP_WG + sect_off;
-        for (int o = tid * 16; o < bytes; o += 64 * CHAIN_NW * 16) *reinterpret_cast<u32x4*>(dst + o) = *reinterpret_cast<const u32x4*>(src + o);
-    };
-#define CH_DUMP(off, src, bytes) dump(off, src, bytes)
-#else
-#define CH_DUMP(off, src, bytes) do { } while (0)
-#endif
 
     // ---- the wave's weight stream through a register ring: fragment f of the current position sits in ring[f % R].
     // wpos: (uniform) address of the fragment that is the current position.
@@ -456,8 +444,6 @@ __global__ __launch_bounds__(64 * CHAIN_NW, 1) void tblock_chain_kernel(const Ch
         zero_acc();
         __syncthreads();
         CH_STAMP(1);
-        CH_DUMP(0, XT, K::XT_BYTES);
-        CH_DUMP(K::XT_BYTES, reinterpret_cast<const char*>(CT), K::CT_FLOATS * 4);
         for (int s0 = 0; s0 < nk0; s0 += PER0) {
 #pragma unroll
             for (int u = 0; u < PER0; ++u) {
@@ -479,14 +465,12 @@ __global__ __launch_bounds__(64 * CHAIN_NW, 1) void tblock_chain_kernel(const Ch
         CH_STAMP(2);
         rows_to_xt(CT + 16 * C);
         __syncthreads();
-        CH_DUMP(K::XT_BYTES + K::CT_FLOATS * 4, XT, K::XT_BYTES);
     } else {
         __syncthreads();                                  // the x tile is in LDS
     }
     ln_stats();
     __syncthreads();
     CH_STAMP(3);
-    CH_DUMP(2 * K::XT_BYTES + K::CT_FLOATS * 4, reinterpret_cast<const char*>(srow), 2 * QB * 4);
 
     // ================================================================ phase 1: FeedForward (reference transformer.py:278-301,104-120)
     zero_acc();
@@ -549,7 +533,6 @@ __global__ __launch_bounds__(64 * CHAIN_NW, 1) void tblock_chain_kernel(const Ch
             }
             __syncthreads();
             if (jj < 2) CH_STAMP(5 + 3 * jj);
-            if (jj == 0) CH_DUMP(2 * K::XT_BYTES + K::CT_FLOATS * 4 + 2 * QB * 4, HT, K::HT_BYTES);
             // ---- FF2: out^T += W2[:, chunk] . hidden chunk^T
 #pragma unroll
             for (int s = 0; s < KG2; ++s) step_wide((F1 + s * FW) % R, HT, s, F1 + s * FW, 0);
@@ -631,7 +614,6 @@ __global__ __launch_bounds__(64 * CHAIN_NW, 1) void tblock_chain_kernel(const Ch
         rows_to_xt(CT + 17 * C);
     }
     __syncthreads();
-    CH_DUMP(2 * K::XT_BYTES + K::CT_FLOATS * 4 + 2 * QB * 4 + K::HT_BYTES, XT, K::XT_BYTES);
 
     // ---- the block's output rows: LDS image -> global image, whole 16-byte chunks, coalesced
     {
@@ -699,32 +681,6 @@ __global__ __launch_bounds__(64 * CHAIN_NW, 1) void tblock_chain_kernel(const Ch
     }
     raise_range_flag(p.range_flag, rmax > 65504.f);
     CH_STAMP(12);
-#ifdef MTTS_CHAIN_PROBE
-    // diagnostic: per workgroup [HW_ID, XCC_ID, hash of the constants in LDS, hash of the kernel arguments as this wave holds them,
-    // hash of the row statistics, -, -, -] (p.kstamp = base, zeroed by the host)
-    if (p.kstamp) {
-        unsigned int* rec = reinterpret_cast<unsigned int*>(p.kstamp) + (size_t)wg * 8;
-        unsigned int hc = 0, hs = 0;
-        for (int i = tid; i < K::CT_FLOATS; i += 64 * CHAIN_NW) hc ^= (__float_as_uint(CT[i]) + 0x9e3779b9u * (unsigned)i) * 2654435761u;
-        for (int i = tid; i < 2 * QB; i += 64 * CHAIN_NW) hs ^= (__float_as_uint(srow[i]) + 0x9e3779b9u * (unsigned)i) * 2654435761u;
-        atomicXor(rec + 2, hc);
-        atomicXor(rec + 4, hs);
-        if (lane == 0) {
-            const unsigned long long ptrs[10] = {(unsigned long long)p.att16, (unsigned long long)p.x16, (unsigned long long)p.wstream, (unsigned long long)p.b_out,
-                (unsigned long long)p.b1, (unsigned long long)p.wsum1, (unsigned long long)p.p0, (unsigned long long)p.p1, (unsigned long long)p.b2,
-                (unsigned long long)p.x_out_mask};
-            unsigned long long h = (unsigned long long)p.M * 1315423911ull + (unsigned long long)p.stream_frags;
-            for (int i = 0; i < 10; ++i) h = (h ^ ptrs[i]) * 1099511628211ull;
-            atomicXor(rec + 3, (unsigned int)(h ^ (h >> 32)) * (1u + 0u * wave));      // all 8 waves: equal hashes cancel pairwise -> 0 when they agree
-            atomicAdd(rec + 5, (unsigned int)(h ^ (h >> 32)) == 0u ? 0u : 1u);
-            if (wave == 0) {
-                rec[0] = __builtin_amdgcn_s_getreg((4) | (0 << 6) | (31 << 11));      // HW_ID
-                rec[1] = __builtin_amdgcn_s_getreg((20) | (0 << 6) | (31 << 11));     // XCC_ID
-                rec[6] = (unsigned int)(h ^ (h >> 32));
-            }
-        }
-    }
-#endif
 }
 
 template <int C, int QB, int CH>
@@ -742,7 +698,7 @@ static hipError_t launch_chain_shape(const ChainArgs& a, hipStream_t s) {
     g_kernel_tag = tag.c_str();
     const int tiles = (a.M + QB - 1) / QB;
     const int wgs = a.pair ? 16 * ((tiles + 7) / 8) : tiles;
-    if (a.pair && (wgs + a.pf_wgs > 256 || (a.pf_wgs != 0 && a.pf_wgs != 16))) return hipErrorInvalidValue;      // both halves of every pair must be resident at once
+    if (a.pair && (wgs + a.pf_wgs > CHIP_CUS || (a.pf_wgs != 0 && a.pf_wgs != 16))) return hipErrorInvalidValue;      // both halves of every pair must be resident at once
     hipLaunchKernelGGL(kern, dim3(wgs + (a.pf_wgs > 0 ? a.pf_wgs : 0)), dim3(64 * CHAIN_NW), K::LDS_BYTES, s, a);
     return hipGetLastError();
 }

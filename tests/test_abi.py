@@ -25,6 +25,22 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.mtts_abi_version() == 2
 
 
+def test_no_debug_exports_and_one_reader_of_the_environment(lib):
+    """The shipped library carries no diagnostic entry points (mtts_debug_hold, the stand-in for a thread inside an entry point in
+    test_context_refuses_concurrent_use, is the one exception), and the C++ sources read the environment in ONE place
+    (read_switches, csrc/model.hip): a getenv inside a launcher is a process-wide latch or a per-launch cost."""
+    import subprocess
+    hip = sub("_hip")
+    out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--dyn-syms", "--wide", str(hip.LIB)], check=True, capture_output=True, text=True).stdout
+    rows = [line.split() for line in out.splitlines()]
+    exported = {r[7].split("@")[0] for r in rows if len(r) == 8 and r[0].rstrip(":").isdigit() and r[6] != "UND"}
+    assert "mtts_create" in exported
+    assert sorted(n for n in exported if n.startswith("mtts_debug_")) == ["mtts_debug_hold"]
+    readers = sorted(f.name for f in (ROOT / "matcha-tts-24k_amd" / "csrc").iterdir() if "getenv" in f.read_text())
+    assert readers == ["model.hip"], readers
+    assert (ROOT / "matcha-tts-24k_amd" / "csrc" / "model.hip").read_text().count("Switches read_switches()") == 1
+
+
 def test_context_rejects_bad_configs_and_missing_tensors(lib, hparams):
     hip = sub("_hip")
     h = hip.HipModel(hparams.tiny())

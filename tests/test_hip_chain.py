@@ -114,7 +114,7 @@ def test_chain_masked_rows_and_exact_row_independence(hip):
 
 
 def test_prefetch_workgroups_do_not_change_results(hip):
-    """The chain launch's prefetch workgroups (MTTS_CHAIN_PF, read once per process; default 8) only touch the weight stream:
+    """The chain launch's prefetch workgroups (MTTS_CHAIN_PF, read by the test entry at every call; default 16) only touch the weight stream:
     0, 8 and 24 of them give bitwise the same outputs (one subprocess per setting), a partly filled last workgroup included."""
     import hashlib, os, subprocess, sys
     from conftest import ROOT

@@ -99,7 +99,7 @@ def main():
     ap.add_argument("--per-shape", type=int, default=2)
     ap.add_argument("--build", action="store_true")
     ap.add_argument("--batch", type=int, default=32)
-    ap.add_argument("--flags", default="", help="extra compile flags for --build, e.g. -DMTTS_EPI_ROLL")
+    ap.add_argument("--flags", default="", help="extra compile flags for --build, e.g. -DMTTS_KSTAMP_SETUP")
     ap.add_argument("--name", default="kstamp", help="tools/ab/<name>.so")
     ap.add_argument("--nostamp", action="store_true", help="--build without -DMTTS_KSTAMP")
     ap.add_argument("--thrash", action="store_true", help="run the other shapes' kernels between the repeats (cold instruction cache)")

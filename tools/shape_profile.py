@@ -2,7 +2,7 @@
 """Per-shape table of one bench step on the GPU box: every launch of the library's event pass grouped by
 (class, algorithmic FLOPs, compulsory bytes) = one GEMM / attention shape.
     python tools/shape_profile.py [--batch 32] [--steps 3] [--solver euler] [--n-timesteps 10]
-Environment switches of the library (MTTS_FOLD, MTTS_FOLD_ALIGN, MTTS_GEMM_BM, ...) apply as usual."""
+Environment switches of the library (MTTS_FOLD, MTTS_FOLD_ALIGN, MTTS_CHAIN, ...) apply as usual."""
 import argparse
 import collections
 import importlib
