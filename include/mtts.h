@@ -28,7 +28,7 @@ extern "C" {
 
 #define MTTS_ABI_VERSION 2
 /* bumped whenever the packed weight image changes layout (invalidates mtts_export_weights caches) */
-#define MTTS_IMAGE_REVISION 5
+#define MTTS_IMAGE_REVISION 6
 
 typedef struct mtts_ctx mtts_ctx;
 
@@ -277,6 +277,31 @@ int mtts_tblock_chain_pair_timed(const float* d_att, const float* d_x, int M, in
                                  const float* h_w1, const float* h_b1, const float* h_p0, const float* h_p1, const float* h_w2,
                                  const float* h_b2, const float* h_w_qkv, const float* h_b_qkv, int n_qkv, const float* d_out_mask,
                                  int qb, int ch, float* d_x_out, float* d_qkv_out, void* d_scratch, void* stream, int repeat, float* h_ms);
+
+/* The same chain for the 16-bit storage modes (csrc/tblock_chain_h16.hip; mtts_set_arithmetic 16 / 17): H16 images (one plane,
+ * rows of C 2-byte values) in and out, ONE v_mfma_f32_16x16x32_f16 / _bf16 per MAC, fp32 accumulation, LayerNorm moments and
+ * SnakeBeta in fp32; every value that crosses a phase is rounded once to the 16-bit type.  bf16 != 0: bfloat16 planes (round to
+ * nearest even, no range guard); 0: fp16 planes (saturating at +-65504).  Single-workgroup form only.
+ * Shapes: C in {128, 256, 384}; inner a multiple of 128, <= C (0: FeedForward only); ch 128, or 256 with C = 384; n_qkv % 32 == 0.
+ * Host-only: the one-plane fragment stream, same order and 1 KiB lane-major fragments as mtts_chain_stream_pack with ONE fragment per
+ * tile and a ring padding of 4 * C/128 fragments.  h_dst: mtts_chain_stream_frags_h16(...) * 8 * 512 values; *saturates (may be NULL)
+ * is set to 1 when an fp16 weight lies beyond +-65504, else left alone. */
+int64_t mtts_chain_stream_frags_h16(int C, int inner, int ch, int n_qkv);
+int mtts_chain_stream_pack_h16(int C, int inner, int ch, int n_qkv, const float* h_w_out, const float* h_w1, const float* h_w2,
+                               const float* h_w_qkv, int bf16, uint16_t* h_dst, int* saturates);
+/* Unit entry: fp32 rows in, fp32 rows out (the 16-bit values the kernel wrote, widened); operands as mtts_tblock_chain.  The row sums
+ * that LayerNorm needs are taken from the ROUNDED panels.  qb: rows per workgroup (32 / 64; 96 with C = 384, ch = 256);
+ * pf_wgs: prefetch workgroups (0..64).  _timed: `repeat` further launches between two events, *h_ms = their mean duration. */
+int64_t mtts_tblock_chain_h16_scratch_bytes(int M, int C, int inner, int n_qkv, int ch);
+int mtts_tblock_chain_h16(const float* d_att, const float* d_x, int M, int C, int inner, const float* h_w_out, const float* h_b_out,
+                          const float* h_w1, const float* h_b1, const float* h_p0, const float* h_p1, const float* h_w2,
+                          const float* h_b2, const float* h_w_qkv, const float* h_b_qkv, int n_qkv, const float* d_out_mask, int bf16,
+                          int qb, int ch, int pf_wgs, float* d_x_out, float* d_qkv_out, void* d_scratch, void* stream);
+int mtts_tblock_chain_h16_timed(const float* d_att, const float* d_x, int M, int C, int inner, const float* h_w_out, const float* h_b_out,
+                                const float* h_w1, const float* h_b1, const float* h_p0, const float* h_p1, const float* h_w2,
+                                const float* h_b2, const float* h_w_qkv, const float* h_b_qkv, int n_qkv, const float* d_out_mask,
+                                int bf16, int qb, int ch, int pf_wgs, float* d_x_out, float* d_qkv_out, void* d_scratch, void* stream,
+                                int repeat, float* h_ms);
 
 /* Row statistics for LayerNorm over C (biased variance, eps inside rsqrt): mean[M], rstd[M]. */
 int mtts_row_stats(const float* d_x, int M, int C, int ld, float eps, float* d_mean, float* d_rstd, void* stream);

@@ -19,7 +19,7 @@ from .hparams import PathHParams
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = Path(os.environ["MTTS_HIP_LIB"]) if os.environ.get("MTTS_HIP_LIB") else HERE / "libmtts_hip.so"   # override: A/B of two builds
-SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "model.hip"]
+SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "model.hip"]
 HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", HERE.parent / "include" / "mtts.h"]
 SOLVERS = {"euler": 0, "midpoint": 1, "rk4": 2}
 
@@ -165,6 +165,12 @@ def load() -> C.CDLL:
                                           i32, C.POINTER(C.c_float)]),
         "mtts_tblock_chain_pair_timed": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp,
                                           i32, C.POINTER(C.c_float)]),
+        "mtts_chain_stream_frags_h16": (i64, [i32, i32, i32, i32]),
+        "mtts_chain_stream_pack_h16": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(C.c_int)]),
+        "mtts_tblock_chain_h16_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
+        "mtts_tblock_chain_h16": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "mtts_tblock_chain_h16_timed": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp,
+                                              i32, C.POINTER(C.c_float)]),
         "mtts_row_stats": (i32, [vp, i32, i32, i32, f32, vp, vp, vp]),
         "mtts_channel_layernorm": (i32, [vp, i32, i32, i32, vp, vp, f32, i32, vp, vp, vp, vp]),
         "mtts_groupnorm_scratch_bytes": (i64, [i32, i32, i32]),
@@ -624,6 +630,33 @@ def tblock_chain(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, b_qkv
     check((lib.mtts_tblock_chain_pair_timed if pair else lib.mtts_tblock_chain_timed)(ptr(att), ptr(x), M, Cc, inner, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8], hp[9],
                                       n_qkv, ptr(out_mask), qb, ch, ptr(x_out), ptr(qkv), scratch.data_ptr(), stream_ptr(), repeat,
                                       C.byref(ms)))
+    torch.cuda.synchronize()
+    if repeat:
+        return x_out, qkv, ms.value
+    return x_out, qkv
+
+
+def tblock_chain_h16(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, b_qkv=None, out_mask=None, bf16=False, qb=64, ch=128,
+                     pf_wgs=0, repeat=0):
+    """The same chain in the 16-bit storage modes' arithmetic (csrc/tblock_chain_h16.hip, include/mtts.h mtts_tblock_chain_h16): the
+    fp32 operands are rounded to fp16 (or bfloat16) images, the kernel's 16-bit outputs come back widened to fp32.  Returns
+    (x_out, qkv or None[, ms per launch when ``repeat``])."""
+    lib = load()
+    M, Cc = x.shape
+    inner = att.shape[1] if att is not None else 0
+    n_qkv = w_qkv.shape[0] if w_qkv is not None else 0
+    n = lib.mtts_tblock_chain_h16_scratch_bytes(M, Cc, inner, n_qkv, ch)
+    if n < 0:
+        raise RuntimeError("mtts_tblock_chain_h16: unsupported shape")
+    scratch = torch.empty(n, dtype=torch.uint8, device=x.device)
+    x_out = torch.empty(M, Cc, dtype=torch.float32, device=x.device)
+    qkv = torch.empty(M, n_qkv, dtype=torch.float32, device=x.device) if n_qkv else None
+    keep = [_host(t) for t in (w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv, b_qkv)]
+    hp = [k[1] for k in keep]
+    ms = C.c_float(0.0)
+    check(lib.mtts_tblock_chain_h16_timed(ptr(att), ptr(x), M, Cc, inner, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8], hp[9],
+                                          n_qkv, ptr(out_mask), int(bool(bf16)), qb, ch, pf_wgs, ptr(x_out), ptr(qkv), scratch.data_ptr(),
+                                          stream_ptr(), repeat, C.byref(ms)))
     torch.cuda.synchronize()
     if repeat:
         return x_out, qkv, ms.value

@@ -268,6 +268,50 @@ static inline double chain_bytes(const ChainArgs& a) {
     return 4.0 * (double(a.M) * (a.inner + 2.0 * a.C + a.n_qkv) + double(a.C) * a.inner + 8.0 * double(a.C) * a.C + double(a.C) * a.n_qkv);
 }
 
+// ---- the same chain for the 16-bit storage modes (tblock_chain_h16.hip): H16 images in and out (GemmArgs::half16: one plane, rows
+// of C halves), a one-plane fragment stream (2 bytes per weight), one MFMA per MAC; bf16 selects bfloat16 planes (GemmArgs::bf16).
+// Single-workgroup form only: the launcher rejects pair != 0.
+struct ChainH16Args {
+    int M = 0;                           // rows (B * T); a workgroup takes qb consecutive ones
+    int C = 0;                           // width of the residual stream (128, 256 or 384)
+    int inner = 0;                       // attention width (heads * 64, a multiple of 128); 0: no out-projection phase
+    const void* att16 = nullptr;         // H16 image of the attention output [M][ld_att halves]
+    int ld_att = 0;
+    const void* x16 = nullptr;           // H16 image of the residual stream [M][ld_x halves]
+    int ld_x = 0;
+    const void* wstream = nullptr;       // chain_h16_stream_pack: [8 waves][frags][64 lanes][8 values of 2 bytes]
+    long stream_frags = 0;               // fragments per wave incl. the tail padding
+    const float* consts = nullptr;       // 18 C floats, as ChainArgs::consts (row sums of the ROUNDED first FeedForward panel)
+    const float* b_qkv = nullptr;        // [n_qkv] or null: no q|k|v phase
+    const float* wsum_qkv = nullptr;     // row sums of the rounded q|k|v panel
+    int n_qkv = 0;
+    void* x_out = nullptr;               // H16 image of the block's output rows [M][ld_out halves] (may alias x16)
+    int ld_out = 0;
+    const float* x_out_mask = nullptr;   // [M] or null: rows of x_out whose entry is 0 are written as zeros
+    void* qkv16 = nullptr;               // H16 image of the next block's q|k|v [M][ld_qkv halves]
+    int ld_qkv = 0;
+    float eps = 1e-5f;
+    unsigned int* range_flag = nullptr;  // fp16 planes only: sticky flag for produced values beyond +-65504
+    int qb = 0, ch = 0;                  // rows per workgroup (32 / 64 / 96) and hidden chunk (128 / 256) the stream was packed for
+    bool bf16 = false;
+    int pair = 0;                        // must be 0
+    int pf_wgs = 0;                      // prefetch workgroups (ChainArgs::pf_wgs)
+};
+bool chain_h16_supported(int C, int inner, int ch, int n_qkv);
+long chain_h16_stream_frags(int C, int inner, int ch, int n_qkv);        // fragments (1 KiB) per wave, incl. the ring's tail padding
+// as chain_stream_pack, one plane: fp16 (saturating at +-65504, reported through *saturates) or bfloat16 (round to nearest even).
+// dst: chain_h16_stream_frags(...) * 8 * 512 values
+void chain_h16_stream_pack(int C, int inner, int ch, int n_qkv, const float* w_out, const float* w1, const float* w2, const float* w_qkv,
+                           bool bf16, uint16_t* dst, bool* saturates);
+hipError_t launch_tblock_chain_h16(const ChainH16Args& a, hipStream_t s);
+hipError_t launch_from_h16(const void* x, int ld16, int M, int C, bool bf16, float* out, int ld, hipStream_t s);      // H16 image -> fp32 rows
+static inline double chain_h16_flops(const ChainH16Args& a) {
+    return 2.0 * double(a.M) * (double(a.C) * a.inner + 8.0 * double(a.C) * a.C + double(a.C) * a.n_qkv);
+}
+static inline double chain_h16_bytes(const ChainH16Args& a) {      // compulsory bytes, 2 per element
+    return 2.0 * (double(a.M) * (a.inner + 2.0 * a.C + a.n_qkv) + double(a.C) * a.inner + 8.0 * double(a.C) * a.C + double(a.C) * a.n_qkv);
+}
+
 // ---- normalisation / activation / glue (norm_glue.hip)
 hipError_t launch_row_stats(const float* x, int M, int C, int ld, float eps, float* mean, float* rstd, hipStream_t s);
 

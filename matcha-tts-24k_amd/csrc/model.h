@@ -45,6 +45,7 @@ struct TBlockW {
     int next = -1;             // index of the block whose q|k|v the chain computes
     size_t chain_pair = 0;     // the same chain as TWO half streams per wave (kernels.h ChainArgs::pair), offset in floats
     long chain_pair_frags = 0; // fragments per (half, wave); 0 = not packed
+    bool chain_h16 = false;    // 16-bit storage modes: `chain` is a ONE-plane stream (kernels.h ChainH16Args; tblock_chain_h16.hip), fp16 or bfloat16
 };
 struct DecW {
     Vec freqs;
@@ -98,6 +99,12 @@ struct Switches {
                                 // profiles/r03_pair_ab.log)
     int chain_pf = 16;          // MTTS_CHAIN_PF 0..64: prefetch workgroups of the chain launch, two per XCD (one alone takes ~93 us for the 7 MB stream and
                                 // is the tail of the launches without a q|k|v phase: 16 instead of 8 = -0.15 ms of GEMM time per step); 0: none
+    bool chain16_on = true;     // MTTS_CHAIN16=0: the 16-bit storage modes keep the four tiled H16 launches per transformer block (MTTS_CHAIN=0 does the same);
+                                // 1: the one-plane chain launch (tblock_chain_h16.hip) at or above chain16_min_rows
+    int chain16_min_rows = 5000;// MTTS_CHAIN16_MIN_ROWS: estimator rows (B * T of a level) from which the one-plane chain replaces the four tiled H16 launches:
+                                // at width 384 the launch alone takes 47 / 63 / 100 us at 5152 / 10304 / 20608 rows; B = 8 (5152 / 2576 rows) is within the run-to-run
+                                // spread either way, B = 16 -0.3..0.5 ms, B = 32 -2.3 ms per step (profiles/r06_chain_h16.md)
+    int chain16_qb = 0;         // MTTS_CHAIN16_QB 32 / 64 / 96: rows per workgroup of the one-plane chain (0 = by shape, chain16_plan)
     int resnet_fuse = 3;        // MTTS_RESNET_FUSE: Block1D as one conv + GroupNorm + Mish launch where it applies (resnet_conv.hip) -- bit 0 the first Block1D
                                 // of a ResNet block and the decoder's final one, bit 1 the second, bit 2 lifts the batch gate; 0 = the tiled launches
 };

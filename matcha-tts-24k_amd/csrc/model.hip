@@ -29,6 +29,9 @@ Switches read_switches() {
     w.pair_on = on("MTTS_CHAIN_PAIR");
     w.pair_min_rows = num("MTTS_CHAIN_PAIR_MIN_ROWS", w.pair_min_rows);
     w.chain_pf = std::min(std::max(num("MTTS_CHAIN_PF", w.chain_pf), 0), 64);
+    w.chain16_on = on("MTTS_CHAIN16");
+    w.chain16_min_rows = num("MTTS_CHAIN16_MIN_ROWS", w.chain16_min_rows);
+    { const int qb = num("MTTS_CHAIN16_QB", 0); if (qb == 32 || qb == 64 || qb == 96) w.chain16_qb = qb; }
     w.resnet_fuse = num("MTTS_RESNET_FUSE", w.resnet_fuse) & 7;
     return w;
 }
@@ -111,6 +114,30 @@ static int run_chain(mtts_ctx* c, const ChainArgs& a0, hipStream_t s) {
     { int qb_unused = 0; chain_plan(a.M, a.ch, a.qb, c->sw.chain_pf, &qb_unused, &a.pf_wgs); }
     if (a.pair) a.pf_wgs = c->sw.chain_pf ? 16 : 0;      // two per XCD, one per half (the model admits pair grids up to 240 workgroups)
     LAUNCHB(c, 0, chain_flops(a), chain_bytes(a), s, launch_tblock_chain(a, s));
+    return 0;
+}
+// Launch plan of the one-plane chain (tblock_chain_h16.hip) over M rows at width C: the smallest workgroup height whose grid -- with
+// the prefetchers -- is ONE round of the chip's CUs (a workgroup's lifetime is set by the stream it pulls, not by its rows), the
+// tallest one beyond; 96-row workgroups exist at width 384 with hidden chunk 256 only, and chunk 128 there has 64-row ones only.
+// qb_forced = Switches::chain16_qb or 0.
+static void chain16_plan(int M, int C, int ch, int qb_forced, int want, int* qb, int* pf) {
+    const bool tall = C == 384 && ch == 256;
+    const int cand[3] = {32, 64, 96};
+    const int ncand = tall ? 3 : 2;
+    *qb = cand[ncand - 1];
+    for (int i = 0; i < ncand; ++i)
+        if ((M + cand[i] - 1) / cand[i] + want <= CHIP_CUS) { *qb = cand[i]; break; }
+    if (qb_forced == 32 || qb_forced == 64 || (qb_forced == 96 && tall)) *qb = qb_forced;
+    if (C == 384 && ch == 128) *qb = 64;
+    const int nwg = (M + *qb - 1) / *qb;
+    *pf = want;
+    if (nwg <= CHIP_CUS && nwg + *pf > CHIP_CUS) *pf = (want >= 8 && nwg + 8 <= CHIP_CUS) ? 8 : 0;
+}
+static int run_chain_h16(mtts_ctx* c, const ChainH16Args& a0, hipStream_t s) {
+    ChainH16Args a = a0;
+    a.range_flag = c->cur_flag;
+    chain16_plan(a.M, a.C, a.ch, c->sw.chain16_qb, c->sw.chain_pf, &a.qb, &a.pf_wgs);
+    LAUNCHB(c, 0, chain_h16_flops(a), chain_h16_bytes(a), s, launch_tblock_chain_h16(a, s));
     return 0;
 }
 static int run_gn_apply(mtts_ctx* c, const GnApplyArgs& a0, hipStream_t s) {
@@ -484,6 +511,38 @@ static int pack_all(mtts_ctx* c, bool dry = false) {
             }
         }
     }
+    // 16-bit storage modes: the same chains as ONE-plane streams (tblock_chain_h16.hip), fp16 or bfloat16 by c->bf16.  Nothing
+    // two-plane is packed in these modes and nothing one-plane in the default one.
+    if (P.ok && c->sw.chain_on && c->sw.chain16_on && c->gemm_terms == 2 && c->half16 && c->sw.p16_on && g.dec_head_dim == 64) {
+        const int nb = g.dec_n_blocks;
+        for (size_t k = 0; k < D.tb.size(); ++k) {
+            TBlockW& t = D.tb[k];
+            const int C = t.out.N, nq = ((int)(k % nb) + 1 < nb) ? D.tb[k + 1].qkv.N : 0;
+            const int ch = (C == 384 && c->sw.chain_ch == 256) ? 256 : 128;
+            if (!chain_h16_supported(C, inner, ch, nq) || t.ff1.N != 4 * C || t.ff1.ktap != C || t.ff2.ktap != 4 * C || t.out.ktap != inner) continue;
+            if (nq && D.tb[k + 1].qkv.ktap != C) continue;
+            t.chain_frags = chain_h16_stream_frags(C, inner, ch, nq);
+            t.chain_ch = ch;
+            t.chain_nqkv = nq;
+            t.chain_h16 = true;
+            t.next = nq ? (int)k + 1 : -1;
+            t.chain = P.alloc((size_t)t.chain_frags * CHAIN_WAVES * 256);
+            t.chain_consts = P.alloc((size_t)18 * C);
+            if (!dry) {
+                bool sat = false;
+                chain_h16_stream_pack(C, inner, ch, nq, &c->image[t.out.w], &c->image[t.ff1.w], &c->image[t.ff2.w],
+                                      nq ? &c->image[D.tb[k + 1].qkv.w] : nullptr, c->bf16, reinterpret_cast<uint16_t*>(&c->image[t.chain]), &sat);
+                if (sat) c->weights_saturate = true;
+                float* cc = &c->image[t.chain_consts];          // (ff1.wsum: row sums of the ROUNDED panel in these modes, add_planes)
+                std::memcpy(cc, &c->image[t.ff1.wsum], (size_t)4 * C * sizeof(float));
+                std::memcpy(cc + 4 * C, &c->image[t.ff1.b], (size_t)4 * C * sizeof(float));
+                std::memcpy(cc + 8 * C, &c->image[t.alpha_exp.off], (size_t)4 * C * sizeof(float));
+                std::memcpy(cc + 12 * C, &c->image[t.inv_beta.off], (size_t)4 * C * sizeof(float));
+                std::memcpy(cc + 16 * C, &c->image[t.out.b], (size_t)C * sizeof(float));
+                std::memcpy(cc + 17 * C, &c->image[t.ff2.b], (size_t)C * sizeof(float));
+            }
+        }
+    }
     if (!P.ok) { set_error(P.why); return -1; }
     c->packed = true;
     return 0;
@@ -824,7 +883,10 @@ static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, int C, i
     // the row-local part as one launch (tblock_chain.hip) when the stream was packed and the batch is large enough that a
     // workgroup per QB rows fills the chip: every workgroup streams ALL of the chain's weights (~7 MB at width 384), which
     // only pays when their cost is shared by many rows per CU
-    const bool chain = t.chain_frags > 0 && d.p16 && !c->half_now && M >= c->sw.chain_min_rows && (emit_stats ? t.chain_nqkv > 0 : true);
+    const bool chain = t.chain_frags > 0 && !t.chain_h16 && d.p16 && !c->half_now && M >= c->sw.chain_min_rows && (emit_stats ? t.chain_nqkv > 0 : true);
+    // 16-bit storage modes: the one-plane chain (tblock_chain_h16.hip) from chain16_min_rows rows on; below, the four tiled launches
+    const bool chain16 = t.chain_frags > 0 && t.chain_h16 && d.p16 && c->half_now && d.ew == 1 && M >= c->sw.chain16_min_rows &&
+                         (emit_stats ? t.chain_nqkv > 0 : true);
     if (!d.qkv_ready) {
         GemmArgs q;
         panel_args(c, t.qkv, q); rows_plain(q, B, T);
@@ -841,8 +903,26 @@ static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, int C, i
     // below that row count: the pair form -- two workgroups of one XCD per 48-row tile, each streaming half of the FeedForward
     // and of the q|k|v passes -- while all of them (and the prefetchers) are resident at once
     const int tiles48 = (M + 47) / 48;
-    const bool pair = !chain && c->sw.pair_on && t.chain_pair_frags > 0 && d.p16 && !c->half_now && d.pair_flag && M >= c->sw.pair_min_rows &&
+    const bool pair = !chain && !chain16 && c->sw.pair_on && t.chain_pair_frags > 0 && d.p16 && !c->half_now && d.pair_flag && M >= c->sw.pair_min_rows &&
                       16 * ((tiles48 + 7) / 8) + 16 <= CHIP_CUS && (emit_stats ? t.chain_nqkv > 0 : true);
+    if (chain16) {                        // (image flow, H16: one 2-byte value per channel)
+        ChainH16Args a;
+        a.M = M; a.C = C; a.inner = inner; a.bf16 = c->bf16;
+        a.att16 = image(d.ATT); a.ld_att = inner;
+        a.x16 = image(x); a.ld_x = C;
+        a.wstream = W(c, t.chain); a.stream_frags = t.chain_frags;
+        a.consts = W(c, t.chain_consts);
+        a.ld_out = C;
+        if (emit_stats) {                 // another block follows: its q|k|v leaves this launch, x stays unmasked
+            const TBlockW& nx = c->dec.tb[t.next];
+            a.b_qkv = W(c, nx.qkv.b); a.wsum_qkv = W(c, nx.qkv.wsum); a.n_qkv = nx.qkv.N;
+            a.qkv16 = image(d.QKV); a.ld_qkv = nx.qkv.N;
+            a.x_out = image(x);
+            d.qkv_ready = true;
+        } else { a.x_out = image(dst); a.x_out_mask = d.mask[lvl]; }
+        a.ch = t.chain_ch;
+        return run_chain_h16(c, a, s);
+    }
     if (chain || pair) {                  // (image flow, P16: rows of 2 halves per channel)
         ChainArgs a;
         a.M = M; a.C = C; a.inner = inner;
@@ -1125,7 +1205,7 @@ int mtts_weights_signature(mtts_ctx* c, char* buf, int64_t n) {
     const int v[] = {MTTS_ABI_VERSION, MTTS_IMAGE_REVISION, g.n_feats, g.n_spks, g.spk_emb_dim, g.n_vocab, g.enc_channels, g.enc_filter,
                      g.enc_heads, g.enc_layers, g.enc_kernel, g.prenet_layers, g.prenet_kernel, g.dp_filter, g.dp_kernel, g.dp_layers,
                      g.dec_levels, g.dec_channels[0], g.dec_channels[1], g.dec_channels[2], g.dec_channels[3], g.dec_head_dim, g.dec_heads,
-                     g.dec_n_blocks, g.dec_mid_blocks, c->gemm_terms, c->half16, c->bf16, c->fast16, c->sw.p16_on, c->sw.chain_on, c->sw.chain_ch, c->sw.pair_on};
+                     g.dec_n_blocks, g.dec_mid_blocks, c->gemm_terms, c->half16, c->bf16, c->fast16, c->sw.p16_on, c->sw.chain_on, c->sw.chain_ch, c->sw.pair_on, c->sw.chain16_on};
     std::string sig = "mtts";
     for (int x : v) sig += "-" + std::to_string(x);
     if ((int64_t)sig.size() + 1 > n) { set_error("mtts_weights_signature: buffer too small"); return -1; }
@@ -1803,6 +1883,107 @@ int mtts_tblock_chain_pair_timed(const float* d_att, const float* d_x, int M, in
                                  float* d_qkv_out, void* d_scratch, void* stream, int repeat, float* h_ms) {
     return tblock_chain_entry(true, d_att, d_x, M, C, inner, h_w_out, h_b_out, h_w1, h_b1, h_p0, h_p1, h_w2, h_b2, h_w_qkv, h_b_qkv, n_qkv,
                               d_out_mask, qb, ch, d_x_out, d_qkv_out, d_scratch, stream, repeat, h_ms);
+}
+
+// ---- the one-plane chain of the 16-bit storage modes (tblock_chain_h16.hip): host-only stream functions and the unit entry
+int64_t mtts_chain_stream_frags_h16(int C, int inner, int ch, int n_qkv) {
+    if (!chain_h16_supported(C, inner, ch, n_qkv)) { set_error("mtts_chain_stream_frags_h16: unsupported shape"); return -1; }
+    return chain_h16_stream_frags(C, inner, ch, n_qkv);
+}
+int mtts_chain_stream_pack_h16(int C, int inner, int ch, int n_qkv, const float* h_w_out, const float* h_w1, const float* h_w2,
+                               const float* h_w_qkv, int bf16, uint16_t* h_dst, int* saturates) {
+    if (!chain_h16_supported(C, inner, ch, n_qkv) || !h_w1 || !h_w2 || !h_dst || (inner && !h_w_out) || (n_qkv && !h_w_qkv)) {
+        set_error("mtts_chain_stream_pack_h16: unsupported shape or null panel");
+        return -1;
+    }
+    bool sat = false;
+    chain_h16_stream_pack(C, inner, ch, n_qkv, h_w_out, h_w1, h_w2, h_w_qkv, bf16 != 0, h_dst, &sat);
+    if (sat && saturates) *saturates = 1;
+    return 0;
+}
+int64_t mtts_tblock_chain_h16_scratch_bytes(int M, int C, int inner, int n_qkv, int ch) {
+    if (M <= 0 || !chain_h16_supported(C, inner, ch, n_qkv)) return -1;
+    const int64_t stream = (int64_t)chain_h16_stream_frags(C, inner, ch, n_qkv) * CHAIN_WAVES * 1024;
+    return stream + (int64_t)M * 2 * (inner + 2 * C + n_qkv) + 4 * (int64_t)(2 * n_qkv + 18 * C) + 4096;
+}
+// row sums of a panel rounded to the stream's 16-bit type (what the kernel multiplies with)
+static double rounded_row_sum(const float* w, int K, bool bf16) {
+    double a = 0.0;
+    for (int k = 0; k < K; ++k) a += bf16 ? (double)(float)(__bf16)w[k] : (double)(float)(_Float16)fminf(fmaxf(w[k], -65504.f), 65504.f);
+    return a;
+}
+int mtts_tblock_chain_h16_timed(const float* d_att, const float* d_x, int M, int C, int inner, const float* h_w_out, const float* h_b_out,
+                                const float* h_w1, const float* h_b1, const float* h_p0, const float* h_p1, const float* h_w2,
+                                const float* h_b2, const float* h_w_qkv, const float* h_b_qkv, int n_qkv, const float* d_out_mask,
+                                int bf16, int qb, int ch, int pf_wgs, float* d_x_out, float* d_qkv_out, void* d_scratch, void* stream,
+                                int repeat, float* h_ms) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!h_w_qkv) n_qkv = 0;
+    if (M <= 0 || !chain_h16_supported(C, inner, ch, n_qkv) || !d_x || !h_w1 || !h_w2 || !h_p0 || !h_p1 || !d_scratch || !d_x_out || (inner && (!d_att || !h_w_out)) ||
+        (n_qkv && !d_qkv_out)) {
+        set_error("mtts_tblock_chain_h16: unsupported shape or null buffer");
+        return -1;
+    }
+    const bool bf = bf16 != 0;
+    const long frags = chain_h16_stream_frags(C, inner, ch, n_qkv);
+    std::vector<uint16_t> hs((size_t)frags * CHAIN_WAVES * 512);
+    chain_h16_stream_pack(C, inner, ch, n_qkv, h_w_out, h_w1, h_w2, h_w_qkv, bf, hs.data(), nullptr);
+    std::vector<float> hc((size_t)18 * C + 2 * (size_t)n_qkv, 0.f);         // wsum1 | b1 | p0 | p1 | b_out | b2 | wsum_qkv | b_qkv
+    for (int n = 0; n < 4 * C; ++n) {
+        hc[n] = (float)rounded_row_sum(h_w1 + (size_t)n * C, C, bf);
+        hc[4 * C + n] = h_b1 ? h_b1[n] : 0.f;
+        hc[8 * C + n] = h_p0[n];
+        hc[12 * C + n] = h_p1[n];
+    }
+    for (int n = 0; n < C; ++n) { hc[16 * C + n] = (inner && h_b_out) ? h_b_out[n] : 0.f; hc[17 * C + n] = h_b2 ? h_b2[n] : 0.f; }
+    for (int n = 0; n < n_qkv; ++n) {
+        hc[18 * C + n] = (float)rounded_row_sum(h_w_qkv + (size_t)n * C, C, bf);
+        hc[18 * C + n_qkv + n] = h_b_qkv ? h_b_qkv[n] : 0.f;
+    }
+    char* sc = static_cast<char*>(d_scratch);
+    void* d_stream = sc; sc += hs.size() * 2;
+    float* d_c = reinterpret_cast<float*>(sc); sc += hc.size() * 4;
+    sc = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(sc) + 255) & ~uintptr_t(255));
+    _Float16* att16 = reinterpret_cast<_Float16*>(sc); sc += (size_t)M * inner * 2;
+    _Float16* x16 = reinterpret_cast<_Float16*>(sc); sc += (size_t)M * C * 2;
+    _Float16* xo16 = reinterpret_cast<_Float16*>(sc); sc += (size_t)M * C * 2;
+    _Float16* q16 = reinterpret_cast<_Float16*>(sc); sc += (size_t)M * n_qkv * 2;
+    HIP_OK(hipMemcpyAsync(d_stream, hs.data(), hs.size() * 2, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(d_c, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));                      // (the host vectors go out of scope)
+    if (inner) HIP_OK(launch_to_p16(d_att, inner, nullptr, M, inner, inner, att16, inner, 1.0f, s, nullptr, true, bf));
+    HIP_OK(launch_to_p16(d_x, C, nullptr, M, C, C, x16, C, 1.0f, s, nullptr, true, bf));
+    ChainH16Args a;
+    a.M = M; a.C = C; a.inner = inner; a.att16 = att16; a.ld_att = inner; a.x16 = x16; a.ld_x = C; a.bf16 = bf;
+    a.wstream = d_stream; a.stream_frags = frags;
+    a.consts = d_c;
+    if (n_qkv) { a.wsum_qkv = d_c + 18 * C; a.b_qkv = d_c + 18 * C + n_qkv; a.n_qkv = n_qkv; a.qkv16 = q16; a.ld_qkv = n_qkv; }
+    a.x_out = xo16; a.ld_out = C; a.x_out_mask = d_out_mask;
+    a.qb = qb; a.ch = ch; a.pf_wgs = pf_wgs;
+    HIP_OK(launch_tblock_chain_h16(a, s));
+    if (repeat > 0 && h_ms) {                             // measurement: `repeat` further launches between two events
+        hipEvent_t e0, e1;
+        HIP_OK(hipEventCreate(&e0));
+        HIP_OK(hipEventCreate(&e1));
+        HIP_OK(hipEventRecord(e0, s));
+        for (int i = 0; i < repeat; ++i) HIP_OK(launch_tblock_chain_h16(a, s));
+        HIP_OK(hipEventRecord(e1, s));
+        HIP_OK(hipEventSynchronize(e1));
+        HIP_OK(hipEventElapsedTime(h_ms, e0, e1));
+        *h_ms /= (float)repeat;
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    HIP_OK(launch_from_h16(xo16, C, M, C, bf, d_x_out, C, s));
+    if (n_qkv) HIP_OK(launch_from_h16(q16, n_qkv, M, n_qkv, bf, d_qkv_out, n_qkv, s));
+    return 0;
+}
+int mtts_tblock_chain_h16(const float* d_att, const float* d_x, int M, int C, int inner, const float* h_w_out, const float* h_b_out,
+                          const float* h_w1, const float* h_b1, const float* h_p0, const float* h_p1, const float* h_w2,
+                          const float* h_b2, const float* h_w_qkv, const float* h_b_qkv, int n_qkv, const float* d_out_mask, int bf16,
+                          int qb, int ch, int pf_wgs, float* d_x_out, float* d_qkv_out, void* d_scratch, void* stream) {
+    return mtts_tblock_chain_h16_timed(d_att, d_x, M, C, inner, h_w_out, h_b_out, h_w1, h_b1, h_p0, h_p1, h_w2, h_b2, h_w_qkv, h_b_qkv, n_qkv,
+                                       d_out_mask, bf16, qb, ch, pf_wgs, d_x_out, d_qkv_out, d_scratch, stream, 0, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ measurement

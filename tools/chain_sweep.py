@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Time the transformer-block chain kernel alone (mtts_tblock_chain_timed) over row counts and workgroup shapes.
-    python tools/chain_sweep.py [--rows 64,512,2048,5152,10304] [--cfg 64:128,32:128,48:256,32:256] [--no-qkv]"""
+    python tools/chain_sweep.py [--rows 64,512,2048,5152,10304] [--cfg 64:128,32:128,48:256,32:256] [--no-qkv]
+    python tools/chain_sweep.py --h16 [--bf16] [--pf 16] --rows 2576,5152,10304,20608 --cfg 32:256,64:256,96:256
+(--h16: the one-plane kernel of the 16-bit storage modes, mtts_tblock_chain_h16_timed)"""
 import argparse, importlib, sys
 from pathlib import Path
 import torch
@@ -16,6 +18,9 @@ def main():
     ap.add_argument("--no-qkv", action="store_true")
     ap.add_argument("--repeat", type=int, default=20)
     ap.add_argument("--pair", action="store_true", help="the pair form (two workgroups per row tile)")
+    ap.add_argument("--h16", action="store_true", help="the one-plane chain of the 16-bit storage modes (csrc/tblock_chain_h16.hip)")
+    ap.add_argument("--bf16", action="store_true", help="--h16 with bfloat16 planes")
+    ap.add_argument("--pf", type=int, default=16, help="--h16: prefetch workgroups")
     a = ap.parse_args()
     C, inner, nq = 384, 384, 0 if a.no_qkv else 1152
     g = torch.Generator().manual_seed(1)
@@ -31,8 +36,12 @@ def main():
         qb, ch = (int(v) for v in cfg.split(":"))
         for M in (int(v) for v in a.rows.split(",")):
             att, x = r(M, inner).cuda(), (r(M, C) * 2 + 0.3).cuda()
-            _, _, ms = hip.tblock_chain(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=wq, b_qkv=bq, qb=qb, ch=ch, repeat=a.repeat, pair=a.pair)
-            wbytes = 4.0 * (C * inner + 8 * C * C + C * nq)
+            if a.h16:
+                _, _, ms = hip.tblock_chain_h16(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=wq, b_qkv=bq, bf16=a.bf16, qb=qb, ch=ch,
+                                                pf_wgs=a.pf, repeat=a.repeat)
+            else:
+                _, _, ms = hip.tblock_chain(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=wq, b_qkv=bq, qb=qb, ch=ch, repeat=a.repeat, pair=a.pair)
+            wbytes = (2.0 if a.h16 else 4.0) * (C * inner + 8 * C * C + C * nq)
             print(f"{M:6d} {qb:3d} {ch:4d} {(M + qb - 1) // qb:5d} {ms * 1e3:8.1f} {flop_row * M / ms / 1e9:7.1f} {wbytes / ms / 1e6:22.1f}")
 
 
