@@ -368,6 +368,53 @@ int64_t mtts_waveform_workspace_bytes(int64_t ld, int B, int sample_rate);
 int mtts_waveform_finish(float* d_audio, int64_t ld, const int64_t* d_lengths, int hop, int B, int sample_rate,
                          double threshold_db, float* d_scale, int64_t* d_out_lengths, void* d_ws, int64_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- voice enrolment: log-mel front end and style encoder */
+
+/* Waveform -> normalised log-mel of a ragged batch of clips -- reference matcha/vocos24k/mel_extractor.py:6-41 (torchaudio
+ * MelSpectrogram(sample_rate, n_fft, win_length = n_fft, hop_length = hop, n_mels, center=True with reflect padding, power=1,
+ * mel_scale="htk", norm=None, f_min 0, f_max sample_rate / 2) of the clip trimmed to a multiple of hop, then log(clamp(., 1e-7)))
+ * followed by (x - mel_mean) / mel_std -- reference matcha/utils/model.py normalize as matcha/utils/precompute_mels.py:100-113
+ * applies it (hop 128 there = the style encoder's "fine" mel; mel_mean 0 and mel_std 1 give the extractor's own output).
+ * The object owns its tables (Hann-windowed DFT basis, HTK filterbank: built in fp64 at create, no device needed) and their device
+ * copy, which the first mtts_melfe_forward makes on the current device (one allocation and a blocking copy: not inside a stream
+ * capture).  n_fft: a multiple of 32 in [64, 2048].
+ *   d_audio [B][ld] fp32 in [-1, 1], d_lengths [B] int64 samples (held inside [0, ld]) ->
+ *   d_mel [B][n_mels][T_max] fp32, zero at frames >= d_mel_lengths[b] = (len_b / hop) + 1 (held to T_max).
+ * T_max >= max_b len_b / hop + 1 keeps every frame.  A clip of at most n_fft / 2 samples after trimming has no reflect padding
+ * (torch raises there): it gets d_mel_lengths[b] = 0 and a zero row; callers check lengths on the host where they have them.
+ * A clip's rows do not depend on the batch it is in (bit for bit).  Nothing is read outside [0, len_b) of a row.
+ * mtts_melfe_basis / _filterbank copy the host tables out: [n_fft][2 * bins] (cos columns then -sin columns, bins = n_fft / 2 + 1
+ * = mtts_melfe_n_bins) and [bins][n_mels]. */
+typedef struct mtts_melfe mtts_melfe;
+mtts_melfe* mtts_melfe_create(int sample_rate, int n_fft, int n_mels);
+void mtts_melfe_destroy(mtts_melfe* m);
+int mtts_melfe_n_bins(mtts_melfe* m);
+int mtts_melfe_basis(mtts_melfe* m, float* h_out, int64_t numel);
+int mtts_melfe_filterbank(mtts_melfe* m, float* h_out, int64_t numel);
+int64_t mtts_melfe_workspace_bytes(mtts_melfe* m, int B, int64_t ld, int hop);
+int mtts_melfe_forward(mtts_melfe* m, const float* d_audio, int64_t ld, const int64_t* d_lengths, int B, int hop, float mel_mean,
+                       float mel_std, float* d_mel, int T_max, int64_t* d_mel_lengths, void* d_ws, int64_t ws_bytes, void* stream);
+
+/* StyleEncoder.forward -- reference matcha/models/style_encoder.py:42-72 (n_layers x { x * mask -> Conv1d(k5, pad 2) -> ReLU },
+ * masked_mean_pool :36-39, proj_enc and proj_dur) -- on a ragged batch of normalised mels, plus the average over the clips of a
+ * voice -- reference matcha/add_speaker.py:60-62.  Tensors are registered under the reference's names ("convs.0.weight",
+ * "convs.0.bias", ..., "proj_enc.weight", "proj_enc.bias", "proj_dur.weight", "proj_dur.bias"); weights and workspace as for
+ * mtts_vocos_*.  n_feats and hidden: multiples of 4.
+ *   d_mel [B][n_feats][T] fp32, d_mel_lengths [B] int64 frames (held inside [0, T]; frames beyond are not read) ->
+ *   d_group == NULL: d_e_enc / d_e_dur [B][spk_emb_dim], one row per clip;
+ *   d_group [B] int32 (clip -> voice; values outside [0, n_groups) are left out): [n_groups][spk_emb_dim], the mean of the rows of
+ *   each voice's clips (a voice without clips gets the zero row).
+ * Every sum has a fixed order: a clip's row does not depend on the batch it is in, and two calls give the same bits. */
+typedef struct mtts_style mtts_style;
+mtts_style* mtts_style_create(int n_feats, int hidden, int n_layers, int spk_emb_dim);
+void mtts_style_destroy(mtts_style* v);
+int mtts_style_set_tensor(mtts_style* v, const char* key, const float* h_data, int64_t numel);
+int64_t mtts_style_weights_bytes(mtts_style* v);
+int mtts_style_upload_weights(mtts_style* v, void* d_weights, int64_t bytes);
+int64_t mtts_style_workspace_bytes(mtts_style* v, int B, int T);
+int mtts_style_forward(mtts_style* v, const float* d_mel, const int64_t* d_mel_lengths, int B, int T, const int32_t* d_group,
+                       int n_groups, float* d_e_enc, float* d_e_dur, void* d_ws, int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- arithmetic and its range guard */
 
 /* Range guard of the default arithmetic.  The fp16 two-term split represents an operand x as h + l / 2^11 with h = fp16(x):

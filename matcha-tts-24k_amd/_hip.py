@@ -19,7 +19,7 @@ from .hparams import PathHParams
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = Path(os.environ["MTTS_HIP_LIB"]) if os.environ.get("MTTS_HIP_LIB") else HERE / "libmtts_hip.so"   # override: A/B of two builds
-SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "model.hip"]
+SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "style_encoder.hip", "model.hip"]
 HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", HERE.parent / "include" / "mtts.h"]
 SOLVERS = {"euler": 0, "midpoint": 1, "rk4": 2}
 
@@ -187,6 +187,20 @@ def load() -> C.CDLL:
         "mtts_vocos_ragged_status": (i32, [vp, vp]),
         "mtts_waveform_workspace_bytes": (i64, [i64, i32, i32]),
         "mtts_waveform_finish": (i32, [vp, i64, vp, i32, i32, i32, C.c_double, vp, vp, vp, i64, vp]),
+        "mtts_melfe_create": (vp, [i32, i32, i32]),
+        "mtts_melfe_destroy": (None, [vp]),
+        "mtts_melfe_n_bins": (i32, [vp]),
+        "mtts_melfe_basis": (i32, [vp, vp, i64]),
+        "mtts_melfe_filterbank": (i32, [vp, vp, i64]),
+        "mtts_melfe_workspace_bytes": (i64, [vp, i32, i64, i32]),
+        "mtts_melfe_forward": (i32, [vp, vp, i64, vp, i32, i32, f32, f32, vp, i32, vp, vp, i64, vp]),
+        "mtts_style_create": (vp, [i32, i32, i32, i32]),
+        "mtts_style_destroy": (None, [vp]),
+        "mtts_style_set_tensor": (i32, [vp, C.c_char_p, vp, i64]),
+        "mtts_style_weights_bytes": (i64, [vp]),
+        "mtts_style_upload_weights": (i32, [vp, vp, i64]),
+        "mtts_style_workspace_bytes": (i64, [vp, i32, i32]),
+        "mtts_style_forward": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i64, vp]),
         "mtts_gemm_terms": (i32, [vp]),
         "mtts_set_arithmetic": (i32, [vp, i32]),
         "mtts_weights_saturate": (i32, [vp]),

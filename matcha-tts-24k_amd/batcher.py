@@ -33,6 +33,7 @@ class Request:
     ids: Sequence[int]                      # phoneme ids of one utterance
     speaker: int = 0
     voice_mix: Optional[Sequence[Tuple[int, float]]] = None    # [(id, weight), ...] as reference server.py:96-101; overrides speaker
+    speaker_embedding: Optional[Tuple[torch.Tensor, torch.Tensor]] = None   # (e_enc, e_dur) rows of an enrolled voice (enroll_voice); overrides both
     solver: str = "midpoint"
     n_timesteps: int = 4
     scale_correction: float = 1.0
@@ -155,7 +156,8 @@ class FrameBudgetBatcher:
         x_len = torch.tensor([len(r.ids) for r in batch], dtype=torch.long)
         head = batch[0]
         self.model.decoder.solver = head.solver
-        emb = self.model.speaker_rows([list(r.voice_mix) if r.voice_mix is not None else r.speaker for r in batch])
+        emb = self.model.speaker_rows([tuple(r.speaker_embedding) if r.speaker_embedding is not None else
+                                       list(r.voice_mix) if r.voice_mix is not None else r.speaker for r in batch])
         out = self.model.synthesise(x.to(dev), x_len.to(dev), head.n_timesteps, speaker_embeddings=emb,
                                     scale_correction=[r.scale_correction for r in batch],
                                     length_scale=[r.length_scale for r in batch], per_request_padding=True)

@@ -166,3 +166,20 @@ def main(argv=None):
 
 if __name__ == "__main__":
     main()
+
+
+def convert_style_checkpoint(ckpt_path, out_dir) -> Path:
+    """The same one-shot conversion for a ``StyleEncoderLightningModule`` checkpoint (reference matcha/models/style_encoder.py:75;
+    or a plain ``StyleEncoder`` state dict): ``<out>/style_encoder.safetensors`` holds the encoder's own tensors under their
+    un-prefixed names (``convs.N.weight/bias``, ``proj_enc.*``, ``proj_dur.*``; the frozen Matcha model inside the checkpoint is
+    dropped) and ``<out>/style_encoder.json`` its four sizes.  ``style.load_style_encoder`` reads the directory back."""
+    from safetensors.torch import save_file
+    from . import style as S
+    ckpt = torch.load(str(ckpt_path), map_location="cpu", weights_only=False)
+    sd = S.select_style_tensors(ckpt["state_dict"] if "state_dict" in ckpt else ckpt)
+    cfg = S.style_cfg_from_state_dict(sd)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    save_file(sd, str(out / S.STYLE_WEIGHTS), metadata={"format": "matcha-tts-24k_amd-style", "version": str(S.STYLE_FORMAT_VERSION)})
+    (out / S.STYLE_HPARAMS).write_text(json.dumps({"format_version": S.STYLE_FORMAT_VERSION, "style_encoder": cfg}, indent=1, sort_keys=True))
+    return out

@@ -434,6 +434,14 @@ hipError_t launch_istft_ola(const float* frames, const float* window, int B, int
 // status[0..2] = (1 + first row with a length outside [1, T] or 0, that length, T); device-side check of a ragged call's lengths
 hipError_t launch_vocos_lengths_check(const int64_t* lengths, int B, int T, int* status, hipStream_t s);
 
+// ---- style encoder (style_encoder.hip; reference matcha/models/style_encoder.py:36-72)
+// mel [B, C, T] -> masked channels-last rows x [B*T][ld] (frames at t >= lengths[b] and channels >= C zero) + the prefix mask [B*T]
+hipError_t launch_style_prep(const float* mel, const int64_t* lengths, int B, int C, int T, float* x, int ld, float* mask, hipStream_t s);
+// masked mean over time of h [B*T][C], the two projections (pw [2E][C] = proj_enc rows then proj_dur rows, pb [2E]) and, with
+// group [B] (clip -> output row, others ignored), the mean over each group's clips: e_enc / e_dur [n_out][E]; group null: n_out == B
+hipError_t launch_style_pool_proj(const float* h, const int64_t* lengths, int B, int T, int C, int E, const float* pw, const float* pb,
+                                  const int* group, int n_out, float* e_enc, float* e_dur, hipStream_t s);
+
 // ---- waveform finish (waveform.hip): per-row peak normalisation and trailing-silence trim lengths, see include/mtts.h
 struct WaveFinishArgs {
     float* audio = nullptr;            // [B][ld], modified in place where a row's peak is above 1

@@ -80,6 +80,11 @@ struct VocosW {
     std::vector<Panel> pw1, pw2;
 };
 
+struct StyleW {
+    std::vector<Panel> convs;      // Conv1d(k5, pad 2) of each layer
+    Vec proj_w, proj_b;            // [2 E][hidden] = proj_enc rows then proj_dur rows, [2 E]
+};
+
 // The library's run-time switches with their defaults.  read_switches() (model.hip) is the only reader of the environment:
 // mtts_create keeps its result in the context, which never looks at the environment again; the context-free test entries
 // (mtts_chain_plan, mtts_tblock_chain*, mtts_gemm_terms(NULL), mtts_gemm_f32 with terms < 0) call it per call.
@@ -150,4 +155,11 @@ struct mtts_vocos {
     int n_mels = 100, dim = 512, inter = 1536, layers = 8, n_fft = 1024, hop = 256;
     int ld_spec = 0, im_off = 0;     // head output row: [Re/logmag 0..n_fft/2 | pad | Im/phase at im_off.. | pad]
     mtts::VocosW w;
+};
+
+// Style encoder (reference matcha/models/style_encoder.py:42-72): its own weight image and context, as the Vocos head.
+struct mtts_style {
+    mtts_ctx base;
+    int n_feats = 100, hidden = 256, layers = 4, emb = 96;
+    mtts::StyleW w;
 };

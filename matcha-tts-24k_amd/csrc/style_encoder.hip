@@ -1,0 +1,101 @@
+// Kernels of the style encoder's forward pass that are not GEMMs (gfx950): reference matcha/models/style_encoder.py:36-72
+// (StyleEncoder.forward, masked_mean_pool) and the clip average of matcha/add_speaker.py:60-62.  The Conv1d(k5) + ReLU stack
+// runs on gemm_f32_kernel (five taps, ReLU and the prefix mask in its epilogue); the launch sequence is in model.hip
+// (mtts_style_forward).
+#include "kernels.h"
+
+namespace mtts {
+
+// Frames of clip b that exist: lengths[b] held inside [0, T], so no index derived from it leaves the buffers.
+__device__ __forceinline__ int style_frames(const int64_t* __restrict__ lengths, int b, int T) {
+    const int64_t n = lengths[b];
+    return n < 0 ? 0 : (n > (int64_t)T ? T : (int)n);
+}
+
+// mel [B, C, T] -> rows x [B*T][ld] (channels [C, ld) zero) times the prefix mask (style_encoder.py:69 `x * mel_mask`; frames at
+// t >= lengths[b] are written as zero and their source is not read), and the mask itself as floats [B*T] for the convs' epilogues.
+__global__ __launch_bounds__(256) void style_prep_kernel(const float* __restrict__ mel, const int64_t* __restrict__ lengths, int C, int T,
+                                                         float* __restrict__ x, int ld, float* __restrict__ mask) {
+    __shared__ float tl[32][33];
+    const int b = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int n = style_frames(lengths, b, T);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int c = c0 + ty + 8 * i, t = t0 + tx;
+        tl[ty + 8 * i][tx] = (c < C && t < n) ? mel[((size_t)b * C + c) * T + t] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int t = t0 + ty + 8 * i, c = c0 + tx;
+        if (t < T && c < ld) x[((size_t)b * T + t) * ld + c] = tl[tx][ty + 8 * i];
+    }
+    if (blockIdx.y == 0 && ty == 0 && t0 + tx < T) mask[(size_t)b * T + t0 + tx] = (t0 + tx < n) ? 1.f : 0.f;
+}
+hipError_t launch_style_prep(const float* mel, const int64_t* lengths, int B, int C, int T, float* x, int ld, float* mask, hipStream_t s) {
+    if (!mel || !lengths || !x || !mask || B <= 0 || B > 65535 || C <= 0 || T <= 0 || ld < C) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(style_prep_kernel, dim3((T + 31) / 32, (ld + 31) / 32, B), dim3(256), 0, s, mel, lengths, C, T, x, ld, mask);
+    return hipGetLastError();
+}
+
+// Masked mean over time, both projections and the clip average, one workgroup per output row.
+//   pooled_b[c] = sum_{t < len_b} h[b, t, c] / max(len_b, 1)                  (style_encoder.py:36-39; rows at t >= len_b are not read)
+//   row_b       = [proj_enc | proj_dur](pooled_b)                             (style_encoder.py:72)
+//   out_g       = mean of row_b over the clips with group[b] == g             (add_speaker.py:60-62);  group == null: out_b = row_b
+// 1024 threads = 4 time slices x 256 channels; slice s adds frames s, s + 4, ... in order and the four partial sums are combined
+// in a fixed order, the projections' dot products go lane-strided with a butterfly, a group's clips are added in batch order:
+// every sum has one order, so two runs and any batch give the same bits for a clip.
+__global__ __launch_bounds__(1024) void style_pool_proj_kernel(const float* __restrict__ h, const int64_t* __restrict__ lengths, int B, int T,
+                                                               int C, int E, const float* __restrict__ pw, const float* __restrict__ pb,
+                                                               const int* __restrict__ group, float* __restrict__ e_enc,
+                                                               float* __restrict__ e_dur) {
+    extern __shared__ float sm[];          // part [4][C] | pooled [C] | acc [2E]
+    float* part = sm;
+    float* pooled = sm + 4 * C;
+    float* acc = pooled + C;
+    const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int o = tid; o < 2 * E; o += 1024) acc[o] = 0.f;
+    int count = 0;
+    for (int b = group ? 0 : g; b < (group ? B : g + 1); ++b) {
+        if (group && group[b] != g) continue;       // uniform over the workgroup
+        const int n = style_frames(lengths, b, T);
+        const float* hb = h + (size_t)b * T * C;
+        const int slice = tid >> 8;
+        for (int c = tid & 255; c < C; c += 256) {
+            float s = 0.f;
+            for (int t = slice; t < n; t += 4) s += hb[(size_t)t * C + c];
+            part[slice * C + c] = s;
+        }
+        __syncthreads();
+        const float inv_n = 1.0f / (float)(n > 1 ? n : 1);
+        for (int c = tid; c < C; c += 1024) pooled[c] = (((part[c] + part[C + c]) + part[2 * C + c]) + part[3 * C + c]) * inv_n;
+        __syncthreads();
+        for (int o = wave; o < 2 * E; o += 16) {
+            float s = 0.f;
+            for (int k = lane; k < C; k += 64) s += pooled[k] * pw[(size_t)o * C + k];
+#pragma unroll
+            for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d);
+            if (lane == 0) acc[o] += s + pb[o];
+        }
+        __syncthreads();
+        ++count;
+    }
+    const float inv = (group && count > 1) ? 1.0f / (float)count : 1.0f;
+    for (int o = tid; o < 2 * E; o += 1024) {
+        const float v = group ? acc[o] * inv : acc[o];
+        if (o < E) e_enc[(size_t)g * E + o] = v;
+        else e_dur[(size_t)g * E + o - E] = v;
+    }
+}
+hipError_t launch_style_pool_proj(const float* h, const int64_t* lengths, int B, int T, int C, int E, const float* pw, const float* pb,
+                                  const int* group, int n_out, float* e_enc, float* e_dur, hipStream_t s) {
+    if (!h || !lengths || !pw || !pb || !e_enc || !e_dur || B <= 0 || T <= 0 || C <= 0 || E <= 0 || n_out <= 0) return hipErrorInvalidValue;
+    if (!group && n_out != B) return hipErrorInvalidValue;
+    const size_t lds = (size_t)(5 * C + 2 * E) * sizeof(float);
+    if (lds > 48 * 1024) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(style_pool_proj_kernel, dim3(n_out), dim3(1024), lds, s, h, lengths, B, T, C, E, pw, pb, group, e_enc, e_dur);
+    return hipGetLastError();
+}
+
+}  // namespace mtts

@@ -15,6 +15,7 @@ from __future__ import annotations
 import math
 from typing import Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -136,13 +137,19 @@ class MatchaTTSInfer(nn.Module):
 
     @torch.inference_mode()
     def speaker_rows(self, voices):
-        """One (e_enc, e_dur) row per entry of ``voices``: an int speaker id, or a voice mix ``[(id, weight), ...]`` combined as
-        ``mix_speakers`` does (reference inference.py:57-76).  Returns two [len(voices), spk_emb_dim] device tensors."""
+        """One (e_enc, e_dur) row per entry of ``voices``: an int speaker id, a voice mix ``[(id, weight), ...]`` combined as
+        ``mix_speakers`` does (reference inference.py:57-76), or a pre-computed ``(e_enc, e_dur)`` pair of tensors (an enrolled
+        voice, ``enroll_voice``).  Returns two [len(voices), spk_emb_dim] device tensors."""
         dev = next(self.parameters()).device
         hip = self._rt.ready()
         enc, dur = [], []
         for v in voices:
-            if isinstance(v, (list, tuple)):
+            if isinstance(v, (list, tuple)) and len(v) == 2 and torch.is_tensor(v[0]) and torch.is_tensor(v[1]):
+                # a pre-computed (e_enc, e_dur) pair, e.g. one voice of ``enroll_voice``
+                e, d = (t.detach().to(device=dev, dtype=torch.float32).reshape(1, -1) for t in v)
+                if e.shape[1] != self.hp.spk_emb_dim or d.shape[1] != self.hp.spk_emb_dim:
+                    raise ValueError(f"an enrolled voice is a pair of rows of {self.hp.spk_emb_dim} values")
+            elif isinstance(v, (list, tuple)):
                 e, d = self.mix_speakers(v)
             else:
                 ids = torch.tensor([int(v)], device=dev, dtype=torch.long)
@@ -150,6 +157,66 @@ class MatchaTTSInfer(nn.Module):
             enc.append(e)
             dur.append(d)
         return torch.cat(enc, 0), torch.cat(dur, 0)
+
+    @torch.inference_mode()
+    def enroll_voice(self, clips, style_encoder, sample_rate: int = 24000):
+        """Speaker rows from audio -- the reference's offline chain matcha/vocos24k/mel_extractor.py (audio -> log-mel),
+        matcha/utils/precompute_mels.py:100-113 (normalise with this model's mel statistics, hop 128), StyleEncoder.forward and
+        matcha/add_speaker.py:40-62 (average over the clips) -- as one front-end call and one encoder call on the device.
+
+        ``clips``: a list of 1-D waveforms (host or device, 24 kHz mono in [-1, 1]) of ONE voice -> ``(e_enc, e_dur)`` of shape
+        [1, spk_emb_dim]; or a list of such lists for several voices -> [n_voices, spk_emb_dim].  The rows are what
+        ``synthesise(speaker_embeddings=...)``, ``speaker_rows`` and ``add_speaker`` take.  Resampling is not done here."""
+        from . import mel as M
+        from .style import FINE_HOP
+        if int(sample_rate) != 24000:
+            raise ValueError("clips must be 24 kHz mono (resample before enrolling)")
+        if len(clips) == 0:
+            raise ValueError("no clips")
+        voices = [clips] if torch.is_tensor(clips[0]) or isinstance(clips[0], np.ndarray) else list(clips)
+        dev = next(self.parameters()).device
+        self._rt.ready()                                   # mel statistics come from the loaded checkpoint's buffers
+        flat, group = [], []
+        for g, vc in enumerate(voices):
+            if len(vc) == 0:
+                raise ValueError(f"voice {g} has no clips")
+            for c in vc:
+                c = torch.as_tensor(c)
+                if c.dim() != 1:
+                    raise ValueError("a clip is a 1-D waveform (mono)")
+                flat.append(c.to(torch.float32))
+                group.append(g)
+        lengths = [int(c.numel()) for c in flat]
+        ld = (max(lengths) + 3) // 4 * 4
+        audio = torch.zeros(len(flat), ld, dtype=torch.float32, device=dev)
+        for b, c in enumerate(flat):
+            audio[b, :lengths[b]].copy_(c)
+        n_feats = style_encoder.cfg["n_feats"]
+        if n_feats != self.hp.n_feats or style_encoder.cfg["spk_emb_dim"] != self.hp.spk_emb_dim:
+            raise ValueError("the style encoder's n_feats / spk_emb_dim do not match this model")
+        mel, mel_len = M.extract(audio, lengths, FINE_HOP, self._rt.mel_mean, self._rt.mel_std, sample_rate=24000, n_mels=n_feats)
+        return style_encoder(mel, lengths=mel_len, group=group, n_groups=len(voices))
+
+    def add_speaker(self, e_enc, e_dur) -> int:
+        """Append a voice to both speaker tables (reference matcha/add_speaker.py:65-70) and return its id.  The table size is a
+        create-time parameter of the device context, so the next call builds a new context and repacks the weights (one host
+        packing pass); graphs captured on the old context are dropped.  For serving, passing the rows per request
+        (``speaker_embeddings=`` / the batcher's ``speaker_embedding``) touches neither weights nor graphs."""
+        import dataclasses
+        E = self.hp.spk_emb_dim
+        for name, row in (("speaker_embeddings_enc", e_enc), ("speaker_embeddings_dur", e_dur)):
+            tree = getattr(self, name)
+            w = tree.weight
+            r = torch.as_tensor(row).detach().reshape(1, -1).to(device=w.device, dtype=w.dtype)
+            if r.shape[1] != E:
+                raise ValueError(f"{name}: a speaker row has {E} values, got {r.shape[1]}")
+            tree.weight = nn.Parameter(torch.cat([w.detach(), r], 0), requires_grad=False)
+        hp = dataclasses.replace(self.hp, n_spks=self.hp.n_spks + 1)
+        object.__setattr__(self, "hp", hp)
+        rt = self._rt
+        rt.hp, rt.hip, rt.wide, rt.use_wide, rt.dirty = hp, None, None, False, True
+        self.decoder._graphs.clear()
+        return hp.n_spks - 1
 
     @torch.inference_mode()
     def _synthesise(self, x, x_lengths, n_timesteps, speaker=0, voice_mix=None, scale_correction=1.0, length_scale=1.0,

@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""Enrol a voice from wav files: clips -> (e_enc, e_dur) speaker rows, the reference's matcha/add_speaker.py on the device.
+
+    python tools/enroll.py --matcha CKPT --style-encoder CKPT_OR_DIR --out voice.npz clip1.wav clip2.wav ...
+    python tools/enroll.py --synthetic 10          # ten synthetic 5 s clips on random weights (profiling / smoke, no files needed)
+
+Clips must be 24 kHz mono PCM wav (8 / 16 / 32 bit); they are read with the standard library's ``wave`` module.  The output .npz
+holds ``e_enc`` and ``e_dur`` ([spk_emb_dim] each): pass them as ``synthesise(speaker_embeddings=...)``, as a batcher
+request's ``speaker_embedding``, or to ``MatchaTTSInfer.add_speaker``."""
+import argparse
+import importlib
+import sys
+import wave
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+PKG = "matcha-tts-24k_amd"
+
+
+def read_wav(path) -> torch.Tensor:
+    with wave.open(str(path), "rb") as w:
+        if w.getframerate() != 24000 or w.getnchannels() != 1:
+            raise ValueError(f"{path}: need 24 kHz mono, got {w.getframerate()} Hz x {w.getnchannels()} channels (resample first)")
+        width, raw = w.getsampwidth(), w.readframes(w.getnframes())
+    if width == 2:
+        a = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
+    elif width == 4:
+        a = np.frombuffer(raw, dtype="<i4").astype(np.float32) / 2147483648.0
+    elif width == 1:
+        a = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
+    else:
+        raise ValueError(f"{path}: unsupported PCM sample width {width}")
+    return torch.from_numpy(a.copy())
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("wavs", nargs="*")
+    ap.add_argument("--matcha", help="Matcha checkpoint (Lightning .ckpt or converted directory): supplies mel_mean / mel_std")
+    ap.add_argument("--style-encoder", help="style-encoder checkpoint (.ckpt or converted directory)")
+    ap.add_argument("--out", default="voice.npz")
+    ap.add_argument("--synthetic", type=int, default=0, help="N synthetic 5 s clips on random weights instead of files")
+    ap.add_argument("--repeat", type=int, default=1, help="run the enrolment this many times (profiling)")
+    args = ap.parse_args()
+    inf = importlib.import_module(PKG + ".inference")
+    style = importlib.import_module(PKG + ".style")
+    if args.synthetic:
+        hparams, synthetic = importlib.import_module(PKG + ".hparams"), importlib.import_module(PKG + ".synthetic")
+        hp = hparams.prod_v20(n_spks=2)
+        model = inf.MatchaTTSInfer(**hp.as_reference_kwargs())
+        model.load_state_dict(synthetic.make_state_dict(hp, seed=7), strict=True)
+        model = model.to("cuda").eval()
+        torch.manual_seed(0)
+        enc = style.StyleEncoder(**style.DEFAULT_CFG).to("cuda").eval()
+        t = torch.arange(5 * 24000, dtype=torch.float32) / 24000.0
+        clips = [(0.4 * torch.sin(2 * np.pi * (120.0 + 20.0 * i) * t) + 0.05 * torch.randn(t.numel())).clamp(-1, 1) for i in range(args.synthetic)]
+    else:
+        if not (args.matcha and args.style_encoder and args.wavs):
+            ap.error("give --matcha, --style-encoder and at least one wav (or --synthetic N)")
+        model = inf.load_matcha("matcha", args.matcha)
+        enc = style.load_style_encoder(args.style_encoder)
+        clips = [read_wav(p) for p in args.wavs]
+    for _ in range(max(args.repeat, 1)):
+        e_enc, e_dur = model.enroll_voice(clips, enc)
+    torch.cuda.synchronize()
+    np.savez(args.out, e_enc=e_enc[0].cpu().numpy(), e_dur=e_dur[0].cpu().numpy())
+    print(f"[enroll] {len(clips)} clips -> {args.out}: e_enc |max| {e_enc.abs().max().item():.4f}, e_dur |max| {e_dur.abs().max().item():.4f}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
