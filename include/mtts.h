@@ -124,6 +124,18 @@ int mtts_durations_per_utterance(const float* d_logw, const float* d_x_mask, con
                                  const float* d_length_scale, int B, int Tx, float* d_durations, int32_t* d_cum,
                                  int64_t* d_y_fine_lengths, void* stream);
 
+/* Durations the caller brings instead of the predictor's (a measured alignment from mtts_mas, a copied rhythm): the tail of
+ * reference inference.py:127-146 with the predictor's term replaced,
+ *   d = clamp_min(round(d_dur * length_scale), 0) * mask        (a zero is allowed: mtts_align_pool skips a token without frames)
+ * and the same inclusive cumulative sum and fine length clamp_min(sum, 1) as mtts_durations (one scan, shared).  scale_correction
+ * has no part in it: it corrects the predictor.  d_dur [B,Tx] f32 (fine frames); d_length_scale: device float [B] or NULL
+ * (then length_scale holds for all).  d_given_rows: device int32 [B] or NULL; row b with d_given_rows[b] == 0 keeps what
+ * d_durations already holds -- call mtts_durations first, then this, and one batch mixes given and predicted rows without a host
+ * read.  Feeding mtts_durations' own d_durations back with length_scale 1 reproduces its d_cum and d_y_fine_lengths exactly. */
+int mtts_durations_given(const float* d_dur, const float* d_x_mask, float length_scale, const float* d_length_scale,
+                         const int32_t* d_given_rows, int B, int Tx, float* d_durations, int32_t* d_cum,
+                         int64_t* d_y_fine_lengths, void* stream);
+
 /* generate_path + matmul + downsample + sequence_mask -- reference inference.py:146-167,
  * utils/model.py:7-9,24-40,57-68.  T_pad = fix_len_compatibility(max fine length) (host decides it).
  * Outputs: d_mu_y [B,n_feats,T_pad], d_y_mask [B,1,T_pad], d_y_lengths [B] int64. */
@@ -414,6 +426,37 @@ int mtts_style_upload_weights(mtts_style* v, void* d_weights, int64_t bytes);
 int64_t mtts_style_workspace_bytes(mtts_style* v, int B, int T);
 int mtts_style_forward(mtts_style* v, const float* d_mel, const int64_t* d_mel_lengths, int B, int T, const int32_t* d_group,
                        int n_groups, float* d_e_enc, float* d_e_dur, void* d_ws, int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- forced alignment (Monotonic Alignment Search) */
+
+/* Which fine mel frames belong to which token -- the alignment of the reference's training forward, matcha/models/matcha_tts.py:
+ * 184-201 (log_prior of the text encoder's mu_x against the ground-truth mel at hop 128, in fp32 on purpose :90-101, then
+ * maximum_path; Kim et al. 2020, Glow-TTS, algorithm 1).  Ragged: utterance b has d_x_lengths[b] <= Tx tokens and
+ * d_y_lengths[b] <= Tm frames (device int64 [B]); Tx <= 1024, Tm >= Tx.
+ *
+ * mtts_mas_logprior: d_lp[b][x][y] = -0.5 |y[b,:,y]|^2 + <mu_x[b,:,x], y[b,:,y]> - 0.5 |mu_x[b,:,x]|^2, the diagonal-Gaussian
+ *   log-likelihood without its constant (reference matcha_tts.py:184-195), evaluated as -0.5 sum_f (y - mu)^2 in fp32; d_mu_x
+ *   [B][F][Tx], d_y [B][F][Tm] (the normalised mel), d_lp [B][Tx][Tm] (the reference's layout), zero beyond an utterance's lengths.
+ * mtts_mas: the search.  d_lp [B][Tx][Tm], or NULL to compute it from d_mu_x / d_y (never written to memory in this layout).
+ *   v[0][0] = lp[0][0], v[x][y] = lp[x][y] + max(v[x][y-1], v[x-1][y-1]) inside the band max(0, Tx_b - (Tm_b - y)) <= x <=
+ *   min(y, Tx_b - 1), -1e9 outside; walking back from (Tx_b - 1, Tm_b - 1), at frame y on token x the path steps to x - 1 iff
+ *   x > 0 and (x == y or v[x-1][y-1] > v[x][y-1]): ties stay on the token.  One add and one compare per cell, in frame order:
+ *   the outputs equal a NumPy fp32 restatement bit for bit.
+ *   d_durations [B][Tx] int32: frames on each token (>= 1 on valid tokens, 0 beyond, summing to Tm_b);
+ *   d_path [B][Tx][Tm] fp32 0/1 or NULL (what maximum_path returns); d_score [B] or NULL (v at the end cell).
+ *   Cells beyond an utterance's own lengths are never read as data; an utterance's result does not depend on its batch.
+ *   The lengths are checked on the device without a host read: an utterance with Tx_b < 1, Tx_b > Tx, Tm_b > Tm or Tm_b < Tx_b
+ *   (no monotone path gives every token a frame) gets zero outputs, the others are unaffected, and mtts_mas_status(d_ws, stream)
+ *   -- the one entry here that waits for the stream -- reports the first such utterance through mtts_last_error.
+ * Stream-ordered, no allocation, safe under HIP graph capture (mtts_mas_status excepted).  Workspace: mtts_mas_workspace_bytes,
+ * 16-byte aligned.  What the host can see (null pointers, B < 1, Tx > 1024, Tm < Tx, a small workspace) returns -1. */
+int64_t mtts_mas_workspace_bytes(int B, int Tx, int Tm);
+int mtts_mas_logprior(const float* d_mu_x, const float* d_y, const int64_t* d_x_lengths, const int64_t* d_y_lengths, int B, int F,
+                      int Tx, int Tm, float* d_lp, void* stream);
+int mtts_mas(const float* d_lp, const float* d_mu_x, const float* d_y, const int64_t* d_x_lengths, const int64_t* d_y_lengths,
+             int B, int F, int Tx, int Tm, int32_t* d_durations, float* d_path, float* d_score, void* d_ws, int64_t ws_bytes,
+             void* stream);
+int mtts_mas_status(const void* d_ws, void* stream);
 
 /* ---------------------------------------------------------------- arithmetic and its range guard */
 

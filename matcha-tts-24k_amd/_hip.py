@@ -19,7 +19,7 @@ from .hparams import PathHParams
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = Path(os.environ["MTTS_HIP_LIB"]) if os.environ.get("MTTS_HIP_LIB") else HERE / "libmtts_hip.so"   # override: A/B of two builds
-SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "style_encoder.hip", "model.hip"]
+SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "style_encoder.hip", "mas.hip", "model.hip"]
 HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", HERE.parent / "include" / "mtts.h"]
 SOLVERS = {"euler": 0, "midpoint": 1, "rk4": 2}
 
@@ -137,6 +137,7 @@ def load() -> C.CDLL:
         "mtts_speaker_embedding": (i32, [vp, i32, vp, i32, vp, vp]),
         "mtts_durations": (i32, [vp, vp, f32, f32, i32, i32, vp, vp, vp, vp]),
         "mtts_durations_per_utterance": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "mtts_durations_given": (i32, [vp, vp, f32, vp, vp, i32, i32, vp, vp, vp, vp]),
         "mtts_align_pool": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
         "mtts_set_frame_limits": (i32, [vp, vp]),
         "mtts_decoder_workspace_bytes": (i64, [vp, i32, i32]),
@@ -201,6 +202,10 @@ def load() -> C.CDLL:
         "mtts_style_upload_weights": (i32, [vp, vp, i64]),
         "mtts_style_workspace_bytes": (i64, [vp, i32, i32]),
         "mtts_style_forward": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i64, vp]),
+        "mtts_mas_workspace_bytes": (i64, [i32, i32, i32]),
+        "mtts_mas_logprior": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
+        "mtts_mas": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
+        "mtts_mas_status": (i32, [vp, vp]),
         "mtts_gemm_terms": (i32, [vp]),
         "mtts_set_arithmetic": (i32, [vp, i32]),
         "mtts_weights_saturate": (i32, [vp]),
@@ -370,6 +375,9 @@ class HipModel:
         n = fn(self.ctx, a, b)
         if n < 0:
             check(-1)
+        return self._grow(kind, n)
+
+    def _grow(self, kind: str, n: int) -> torch.Tensor:
         key = (kind, stream_ptr())
         ws = self._ws.get(key)
         if ws is None or ws.numel() < n:
@@ -464,6 +472,91 @@ class HipModel:
         check(self.lib.mtts_durations(ptr(logw), ptr(x_mask), float(scale_correction), float(length_scale), B, Tx, ptr(dur),
                                       ptr(cum), ptr(yfl), stream_ptr()))
         return dur, cum, yfl
+
+    def durations_given(self, given, x_mask, length_scale=1.0, given_rows=None, out=None):
+        """Durations the caller brings (``given`` [B, Tx], fine frames, float or int) instead of the predictor's:
+        ``clamp_min(round(given * length_scale), 0) * mask`` and the scan of ``durations`` (mtts_durations_given).  ``given_rows``
+        (bool / int [B]) + ``out`` (the ``durations`` tensor of a ``durations`` call): rows not marked keep the predictor's."""
+        x_mask = self._f32(x_mask)
+        B, _, Tx = x_mask.shape
+        given = self._f32(given)
+        if given.shape != (B, Tx):
+            raise ValueError(f"durations must have shape ({B}, {Tx}), got {tuple(given.shape)}")
+        rows = None
+        if given_rows is not None:
+            if out is None:
+                raise ValueError("given_rows needs out= (the predictor's durations of the other rows)")
+            rows = torch.as_tensor(given_rows).to(device=given.device, dtype=torch.int32).contiguous()
+            if rows.shape != (B,):
+                raise ValueError("given_rows needs one flag per utterance")
+        dur = torch.empty(B, Tx, dtype=torch.float32, device=given.device) if out is None else out
+        cum = torch.empty(B, Tx, dtype=torch.int32, device=given.device)
+        yfl = torch.empty(B, dtype=torch.int64, device=given.device)
+        ls, ls_b = 1.0, None
+        if isinstance(length_scale, (int, float)):
+            ls = float(length_scale)
+        else:
+            ls_b = torch.as_tensor(length_scale, dtype=torch.float32).reshape(-1)
+            ls_b = (ls_b.expand(B) if ls_b.numel() == 1 else ls_b).to(given.device).contiguous()
+            if ls_b.numel() != B:
+                raise ValueError("per-utterance scale factors need one value per utterance")
+        check(self.lib.mtts_durations_given(ptr(given), ptr(x_mask), ls, ptr(ls_b), ptr(rows), B, Tx, ptr(dur), ptr(cum), ptr(yfl),
+                                            stream_ptr()))
+        return dur, cum, yfl
+
+    def mas_logprior(self, mu_x, y, x_lengths, y_lengths):
+        """Diagonal-Gaussian log-prior [B, Tx, Tm] of every (token, frame) pair in fp32 (mtts_mas_logprior)."""
+        mu_x, y = self._f32(mu_x), self._f32(y)
+        B, F, Tx = mu_x.shape
+        Tm = y.shape[2]
+        if y.shape[:2] != (B, F):
+            raise ValueError(f"y must be [{B}, {F}, Tm], got {tuple(y.shape)}")
+        xl = x_lengths.detach().to(device=mu_x.device, dtype=torch.int64).contiguous()
+        yl = y_lengths.detach().to(device=mu_x.device, dtype=torch.int64).contiguous()
+        lp = torch.empty(B, Tx, Tm, dtype=torch.float32, device=mu_x.device)
+        check(self.lib.mtts_mas_logprior(ptr(mu_x), ptr(y), ptr(xl), ptr(yl), B, F, Tx, Tm, ptr(lp), stream_ptr()))
+        return lp
+
+    def mas(self, x_lengths, y_lengths, lp=None, mu_x=None, y=None, return_path=False, check_lengths=True):
+        """Monotonic Alignment Search (mtts_mas) on a given log-prior ``lp`` [B, Tx, Tm], or on ``mu_x`` [B, F, Tx] and ``y``
+        [B, F, Tm] through the log-prior kernel.  Returns ``(durations int32 [B, Tx], score [B], path [B, Tx, Tm] or None)``.
+        ``check_lengths``: read the device's verdict on the lengths (one synchronisation) and raise ``ValueError``; pass False
+        inside a HIP graph capture and call ``mas_status`` after the replay."""
+        if lp is not None:
+            lp = self._f32(lp)
+            B, Tx, Tm = lp.shape
+            F, dev = 0, lp.device
+        else:
+            mu_x, y = self._f32(mu_x), self._f32(y)
+            B, F, Tx = mu_x.shape
+            Tm, dev = y.shape[2], mu_x.device
+            if y.shape[:2] != (B, F):
+                raise ValueError(f"y must be [{B}, {F}, Tm], got {tuple(y.shape)}")
+        xl = x_lengths.detach().to(device=dev, dtype=torch.int64).contiguous()
+        yl = y_lengths.detach().to(device=dev, dtype=torch.int64).contiguous()
+        if xl.shape != (B,) or yl.shape != (B,):
+            raise ValueError("x_lengths and y_lengths need one entry per utterance")
+        n = self.lib.mtts_mas_workspace_bytes(B, Tx, Tm)
+        if n < 0:
+            check(-1)
+        if self.device is None:
+            self.device = dev
+        ws = self._grow("mas", n)
+        dur = torch.empty(B, Tx, dtype=torch.int32, device=dev)
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+        path = torch.empty(B, Tx, Tm, dtype=torch.float32, device=dev) if return_path else None
+        check(self.lib.mtts_mas(ptr(lp), ptr(mu_x), ptr(y), ptr(xl), ptr(yl), B, F, Tx, Tm, ptr(dur), ptr(path), ptr(score),
+                                ws.data_ptr(), ws.numel(), stream_ptr()))
+        if check_lengths:
+            self.mas_status()
+        return dur, score, path
+
+    def mas_status(self) -> None:
+        """Wait for this stream's latest ``mas`` call and raise ``ValueError`` naming the first utterance whose lengths the
+        device refused (mtts_mas_status)."""
+        ws = self._last_ws.get(("mas", stream_ptr()))
+        if ws is not None and self.lib.mtts_mas_status(ws.data_ptr(), stream_ptr()) != 0:
+            raise ValueError(self.lib.mtts_last_error().decode("utf-8", "replace"))
 
     def align_pool(self, mu_x, cum, y_fine_lengths, t_pad: int):
         mu_x = self._f32(mu_x)

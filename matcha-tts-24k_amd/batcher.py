@@ -7,7 +7,7 @@ of the batch equals the batch-of-one result (to rounding: tile shapes, hence sum
 
 ``FrameBudgetBatcher`` is the queue + grouping policy:
   * requests are grouped by what must be uniform inside one call (solver, n_timesteps); voices, their duration scale
-    corrections and client speeds are per-utterance inputs (mtts_durations_per_utterance);
+    corrections, client speeds and given durations are per-utterance inputs (mtts_durations_per_utterance, mtts_durations_given);
   * a batch takes the oldest waiting request and then the waiting requests of the same group that are closest to it in token
     count (padding wastes MFMA work: the estimator's cost is ~linear in padded frames), up to ``max_batch`` utterances and
     ``max_tokens`` padded tokens (B * longest), the frame budget idea of the reference's training sampler
@@ -38,12 +38,24 @@ class Request:
     n_timesteps: int = 4
     scale_correction: float = 1.0
     length_scale: float = 1.0
+    durations: Optional[Sequence[float]] = None    # fine frames per token (e.g. ``align(...)["durations"]``) instead of the predictor's; length_scale still applies
     future: Future = field(default_factory=Future, repr=False)
     t_submit: float = field(default_factory=time.monotonic, repr=False)
 
     @property
     def group(self) -> Tuple[Any, ...]:
         return (self.solver, int(self.n_timesteps))
+
+
+def duration_rows(batch: List[Request]) -> Optional[List[Optional[Sequence[float]]]]:
+    """What ``synthesise(durations=...)`` takes for a batch: one entry per request (None = the predictor), or None when no request
+    brings durations.  Pure function: unit-tested on the CPU."""
+    if all(r.durations is None for r in batch):
+        return None
+    for r in batch:
+        if r.durations is not None and len(r.durations) != len(r.ids):
+            raise ValueError(f"a request's durations need one value per token ({len(r.ids)}), got {len(r.durations)}")
+    return [r.durations for r in batch]
 
 
 def plan_batch(waiting: List[Request], max_batch: int, max_tokens: int) -> List[int]:
@@ -97,6 +109,7 @@ class FrameBudgetBatcher:
         if len(ids) > self.max_tokens:
             raise ValueError(f"utterance of {len(ids)} tokens exceeds the batch budget of {self.max_tokens}")
         r = Request(ids=list(ids), **kw)
+        duration_rows([r])                  # (a wrong count fails its own request here, not the batch it would have joined)
         with self._cv:
             if self._stop:
                 raise RuntimeError("batcher is closed")
@@ -160,7 +173,8 @@ class FrameBudgetBatcher:
                                        list(r.voice_mix) if r.voice_mix is not None else r.speaker for r in batch])
         out = self.model.synthesise(x.to(dev), x_len.to(dev), head.n_timesteps, speaker_embeddings=emb,
                                     scale_correction=[r.scale_correction for r in batch],
-                                    length_scale=[r.length_scale for r in batch], per_request_padding=True)
+                                    length_scale=[r.length_scale for r in batch], per_request_padding=True,
+                                    durations=duration_rows(batch))
         lens = out["mel_lengths"].tolist()
         res = [{"mel": out["mel"][b, :, :int(lens[b])], "mel_length": int(lens[b])} for b in range(B)]
         if self.vocoder is not None and self.wave_batch:

@@ -397,6 +397,9 @@ hipError_t launch_bcast_rows(const float* src, int B, int T, int C, const float*
 hipError_t launch_rope(float* qkv, int B, int T, int H, int D, int d_rope, const float* cos_t, const float* sin_t, hipStream_t s);
 hipError_t launch_durations(const float* logw, const float* mask, float scale_correction, float length_scale, int B, int Tx, float* dur,
                             int32_t* cum, int64_t* yfl, hipStream_t s, const float* sc_b = nullptr, const float* ls_b = nullptr);
+// durations the caller brings: dur = max(round(given * ls), 0) * mask on the rows given_rows marks (null: all; others keep dur), same scan
+hipError_t launch_durations_given(const float* given, const float* mask, float length_scale, const float* ls_b, const int32_t* given_rows,
+                                  int B, int Tx, float* dur, int32_t* cum, int64_t* yfl, hipStream_t s);
 // level mask of the U-Net: dst[b, t] = src[b, t * stride], t < T_dst (reference decoder.py:390 mask[:, :, ::2])
 hipError_t launch_mask_down(const float* src, int B, int T_src, int stride, float* dst, int T_dst, hipStream_t s);
 // Per-level frame tables of one estimator call (norm_glue.hip).  Level l has T[l] rows per utterance.

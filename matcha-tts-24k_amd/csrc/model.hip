@@ -1560,6 +1560,15 @@ int mtts_durations_per_utterance(const float* d_logw, const float* d_x_mask, con
     return 0;
 }
 
+int mtts_durations_given(const float* d_dur, const float* d_x_mask, float length_scale, const float* d_length_scale, const int32_t* d_given_rows,
+                         int B, int Tx, float* d_durations, int32_t* d_cum, int64_t* d_y_fine_lengths, void* stream) {
+    if (!d_dur || !d_x_mask || !d_durations || !d_cum || !d_y_fine_lengths) { set_error("mtts_durations_given: null argument"); return -1; }
+    if (B < 1 || Tx < 1) { set_error("mtts_durations_given: bad shape"); return -1; }
+    HIP_OK(launch_durations_given(d_dur, d_x_mask, length_scale, d_length_scale, d_given_rows, B, Tx, d_durations, d_cum, d_y_fine_lengths,
+                                  static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int mtts_align_pool(const float* d_mu_x, const int32_t* d_cum, const int64_t* d_y_fine_lengths, int B, int n_feats, int Tx, int T_pad,
                     float* d_mu_y, float* d_y_mask, int64_t* d_y_lengths, void* stream) {
     HIP_OK(launch_align_pool(d_mu_x, d_cum, d_y_fine_lengths, B, n_feats, Tx, T_pad, d_mu_y, d_y_mask, d_y_lengths,

@@ -663,6 +663,26 @@ hipError_t launch_rope(float* qkv, int B, int T, int H, int D, int d_rope, const
     return hipGetLastError();
 }
 
+// The scan shared by the two duration kernels: thread tid holds the sum s of its chunk [i0, i1) of dur; inclusive cumsum of the
+// row as int32, fine length = max(sum, 1).  256 threads, Hillis-Steele over the chunk sums.
+__device__ __forceinline__ void durations_scan(int s, int tid, int i0, int i1, const float* dur_row, int32_t* cum_row, int64_t* yfl_b,
+                                               int* part) {
+    part[tid] = s;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        int v = tid >= o ? part[tid - o] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int run = tid ? part[tid - 1] : 0;
+    for (int i = i0; i < i1; ++i) {
+        run += (int)dur_row[i];
+        cum_row[i] = run;
+    }
+    if (tid == 255) *yfl_b = max(part[255], 1);
+}
+
 // Durations (reference inference.py:127-146): d = round(((exp(logw) - 2) * mask) * sc * ls).clamp(min=1) * mask,
 // inclusive cumsum as int32, fine length = max(sum, 1).  One workgroup per utterance, serial-chunk + block scan.
 __global__ __launch_bounds__(256) void durations_kernel(const float* __restrict__ logw, const float* __restrict__ mask, float sc, float ls,
@@ -685,20 +705,40 @@ __global__ __launch_bounds__(256) void durations_kernel(const float* __restrict_
         dur[(size_t)b * Tx + i] = d;
         s += (int)d;
     }
-    part[tid] = s;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {      // Hillis-Steele inclusive scan
-        int v = tid >= o ? part[tid - o] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = tid ? part[tid - 1] : 0;
+    durations_scan(s, tid, i0, i1, dur + (size_t)b * Tx, cum + (size_t)b * Tx, yfl + b, part);
+}
+
+// Durations the caller brings (a measured alignment, mtts_mas; a copied rhythm): d = max(round(given * ls), 0) * mask -- a zero is
+// allowed, align_pool skips a token without frames -- then the scan of durations_kernel.  given_rows (optional, [B]): row b with
+// given_rows[b] == 0 keeps what dur already holds (the predictor's durations of a mixed batch) and is only scanned again.
+__global__ __launch_bounds__(256) void durations_given_kernel(const float* __restrict__ given, const float* __restrict__ mask, float ls,
+                                                              const float* __restrict__ ls_b, const int32_t* __restrict__ given_rows,
+                                                              int Tx, float* __restrict__ dur, int32_t* __restrict__ cum,
+                                                              int64_t* __restrict__ yfl) {
+    __shared__ int part[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    if (ls_b) ls = ls_b[b];
+    const bool take = !given_rows || given_rows[b] != 0;
+    const int per = (Tx + 255) / 256;
+    const int i0 = tid * per, i1 = min(Tx, i0 + per);
+    int s = 0;
     for (int i = i0; i < i1; ++i) {
-        run += (int)dur[(size_t)b * Tx + i];
-        cum[(size_t)b * Tx + i] = run;
+        float d;
+        if (take) {
+            d = fmaxf(rintf(given[(size_t)b * Tx + i] * ls), 0.0f) * mask[(size_t)b * Tx + i];
+            dur[(size_t)b * Tx + i] = d;
+        } else {
+            d = dur[(size_t)b * Tx + i];
+        }
+        s += (int)d;
     }
-    if (tid == 255) yfl[b] = max(part[255], 1);
+    durations_scan(s, tid, i0, i1, dur + (size_t)b * Tx, cum + (size_t)b * Tx, yfl + b, part);
+}
+hipError_t launch_durations_given(const float* given, const float* mask, float ls, const float* ls_b, const int32_t* given_rows, int B, int Tx,
+                                  float* dur, int32_t* cum, int64_t* yfl, hipStream_t s) {
+    if (!given || !mask || !dur || !cum || !yfl || B <= 0 || Tx <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(durations_given_kernel, dim3(B), dim3(256), 0, s, given, mask, ls, ls_b, given_rows, Tx, dur, cum, yfl);
+    return hipGetLastError();
 }
 hipError_t launch_durations(const float* logw, const float* mask, float sc, float ls, int B, int Tx, float* dur, int32_t* cum,
                             int64_t* yfl, hipStream_t s, const float* sc_b, const float* ls_b) {

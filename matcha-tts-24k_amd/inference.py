@@ -104,10 +104,10 @@ class MatchaTTSInfer(nn.Module):
     range_policy = "rerun"
 
     def synthesise(self, x, x_lengths, n_timesteps, speaker=0, voice_mix=None, scale_correction=1.0, length_scale=1.0,
-                   debug=False, z=None, sync_max=None, per_request_padding=False, speaker_embeddings=None):
+                   debug=False, z=None, sync_max=None, per_request_padding=False, speaker_embeddings=None, durations=None):
         """``_synthesise`` + the range guard: one read of the sticky device flag per call (a stream synchronisation)."""
         args = (x, x_lengths, n_timesteps, speaker, voice_mix, scale_correction, length_scale, debug, z, sync_max, per_request_padding,
-                speaker_embeddings)
+                speaker_embeddings, durations)
         rt = self._rt
         if rt.use_wide:                       # a previous call or the weights already needed the wide arithmetic
             return self._synthesise(*args)
@@ -218,9 +218,117 @@ class MatchaTTSInfer(nn.Module):
         self.decoder._graphs.clear()
         return hp.n_spks - 1
 
+    @staticmethod
+    def _given_durations(hip, given, logw, x_mask, scale_correction, length_scale):
+        """``hip.durations_given`` for ``synthesise(durations=...)``: a [B, Tx] tensor, or B rows of which some are None -- those
+        get the predictor's durations first (one ``hip.durations`` call for the batch) and the given rows overwrite them on the
+        device before the scan."""
+        B, _, Tx = x_mask.shape
+        dev = x_mask.device
+        if torch.is_tensor(given):
+            if given.dim() == 1:
+                given = given[None]
+            return hip.durations_given(given.to(dev), x_mask, length_scale)
+        if len(given) != B:
+            raise ValueError(f"durations need one row per utterance ({B}), got {len(given)}")
+        host = torch.zeros(B, Tx, dtype=torch.float32)
+        for b, row in enumerate(given):
+            if row is None:
+                continue
+            row = torch.as_tensor(row).detach().to("cpu", torch.float32).reshape(-1)
+            if row.numel() > Tx:
+                raise ValueError(f"durations[{b}] has {row.numel()} values for {Tx} tokens")
+            host[b, :row.numel()] = row
+        rows = [row is not None for row in given]
+        if all(rows):
+            return hip.durations_given(host.to(dev), x_mask, length_scale)
+        predicted, _, _ = hip.durations(logw, x_mask, scale_correction, length_scale)
+        return hip.durations_given(host.to(dev), x_mask, length_scale, given_rows=rows, out=predicted)
+
+    @torch.inference_mode()
+    def align(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0, voice_mix=None,
+              speaker_embeddings=None, return_path=False):
+        """Forced alignment of text to a recording: per-token durations in fine frames (hop 128) by Monotonic Alignment Search of
+        the text encoder's ``mu_x`` against the recording's normalised fine mel -- the alignment of the reference's training
+        forward (matcha/models/matcha_tts.py:184-201), here for inference-time use: ``synthesise(durations=...)`` re-times or
+        re-voices with the speaker's own rhythm, and ``scale_correction`` is the number the reference's ``VOICES`` table holds per
+        voice ("measured after training, by comparing generated speech to ground truth", reference inference.py:131-133).
+
+        The recording: ``audio`` -- 24 kHz mono clips, a list of 1-D waveforms (host or device) or a [B, L] tensor with
+        ``audio_lengths`` -- whose fine mel is extracted as ``enroll_voice`` does; or ``mel_fine`` [B, n_feats, Tm], already
+        normalised with this model's mel statistics, with ``mel_fine_lengths`` (default: all Tm).  Speaker arguments as for
+        ``synthesise``.  Returns ``durations`` (int32 [B, Tx]), ``predicted_durations`` (the predictor's raw
+        ``(exp(logw) - 2) * mask``), ``scale_correction`` ([B]: aligned total / predicted total), ``score`` ([B]: the path's
+        log-prior sum), ``mel_fine_lengths`` and, with ``return_path``, ``path`` ([B, Tx, Tm] 0/1).  One synchronisation per call
+        (the lengths' verdict and the range flag); ``ValueError`` names an utterance with fewer frames than tokens."""
+        rt = self._rt
+        hip = rt.ready()
+        out = self._align(x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path)
+        if rt.use_wide or hip.gemm_terms() not in (1, 2, 16, 17) or self.range_policy == "ignore":
+            return out
+        if not (hip.weights_saturate() or bool(hip.range_flags()[0].item())):       # (the stream is already drained: no second wait)
+            return out
+        if self.range_policy == "raise":
+            raise FloatingPointError("matcha-tts-24k_amd: an operand left the fp16 range (|x| > 65504) in the default split "
+                                     "arithmetic; set model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
+        rt.use_wide = True                     # sticky, as in synthesise
+        return self._align(x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path)
+
+    def _align(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path):
+        hip = self._rt.ready()
+        dev = x.device
+        B, Tx = x.shape
+        if (audio is None) == (mel_fine is None):
+            raise ValueError("align needs either audio= or mel_fine=")
+        if mel_fine is None:
+            from . import mel as M
+            from .style import FINE_HOP
+            clips = [audio[b] for b in range(audio.shape[0])] if torch.is_tensor(audio) and audio.dim() == 2 else (
+                [audio] if torch.is_tensor(audio) or isinstance(audio, np.ndarray) else list(audio))
+            if len(clips) != B:
+                raise ValueError(f"align needs one clip per utterance ({B}), got {len(clips)}")
+            clips = [torch.as_tensor(c).to(torch.float32) for c in clips]
+            if any(c.dim() != 1 for c in clips):
+                raise ValueError("a clip is a 1-D waveform (24 kHz mono)")
+            lengths = [int(c.numel()) for c in clips] if audio_lengths is None else [int(v) for v in torch.as_tensor(audio_lengths).tolist()]
+            ld = (max(int(c.numel()) for c in clips) + 3) // 4 * 4
+            wave = torch.zeros(B, ld, dtype=torch.float32, device=dev)
+            for b, c in enumerate(clips):
+                wave[b, :c.numel()].copy_(c)
+            mel_fine, mel_fine_lengths = M.extract(wave, lengths, FINE_HOP, self._rt.mel_mean, self._rt.mel_std, sample_rate=24000,
+                                                   n_mels=self.hp.n_feats)
+        else:
+            if mel_fine.dim() != 3 or mel_fine.shape[0] != B or mel_fine.shape[1] != self.hp.n_feats:
+                raise ValueError(f"mel_fine must be [{B}, {self.hp.n_feats}, Tm], got {tuple(mel_fine.shape)}")
+            mel_fine = mel_fine.to(dev)
+            if mel_fine_lengths is None:
+                mel_fine_lengths = torch.full((B,), mel_fine.shape[2], dtype=torch.long, device=dev)
+        mel_fine_lengths = torch.as_tensor(mel_fine_lengths).to(device=dev, dtype=torch.long)
+        if mel_fine.shape[2] < Tx:              # (the padded shapes: the device checks each utterance's own lengths)
+            mel_fine = torch.nn.functional.pad(mel_fine, (0, Tx - mel_fine.shape[2]))
+
+        if speaker_embeddings is not None:
+            e_enc, e_dur = speaker_embeddings
+        elif voice_mix is not None:
+            e_enc, e_dur = self.mix_speakers(voice_mix)
+        else:
+            ids = torch.as_tensor(speaker, dtype=torch.long, device=dev).reshape(-1)
+            e_enc, e_dur = hip.speaker_embedding(0, ids), hip.speaker_embedding(1, ids)
+        if e_enc.shape[0] not in (1, B):
+            raise ValueError("speaker must be an int or a LongTensor with one id per utterance")
+        mu_x, logw, x_mask = self.encoder(x, x_lengths, e_enc, e_dur)
+        durations, score, path = hip.mas(x_lengths, mel_fine_lengths, mu_x=mu_x, y=mel_fine, return_path=return_path)
+        predicted = ((torch.exp(logw) - 2) * x_mask).squeeze(1)
+        out = {"durations": durations, "predicted_durations": predicted,
+               "scale_correction": durations.sum(1).to(torch.float32) / predicted.sum(1), "score": score,
+               "mel_fine_lengths": mel_fine_lengths}
+        if return_path:
+            out["path"] = path
+        return out
+
     @torch.inference_mode()
     def _synthesise(self, x, x_lengths, n_timesteps, speaker=0, voice_mix=None, scale_correction=1.0, length_scale=1.0,
-                    debug=False, z=None, sync_max=None, per_request_padding=False, speaker_embeddings=None):
+                    debug=False, z=None, sync_max=None, per_request_padding=False, speaker_embeddings=None, durations=None):
         """Text ids -> mel (reference inference.py:78-183).  Returns ``{"mel": [B, n_feats, T_valid_max]}`` (+ the
         reference's debug tensors when ``debug``).
 
@@ -232,7 +340,11 @@ class MatchaTTSInfer(nn.Module):
         attention key set and the noise shape, from the longest utterance of the call, so a request's mel depends on what
         it is batched with.  With this flag every utterance is padded (logically) to its OWN length: each row of a ragged
         batch equals the batch-of-one result for that request to rounding (what a dynamic batcher in front of the reference's
-        one-request-at-a-time server needs); one extra host read of the B fine lengths."""
+        one-request-at-a-time server needs); one extra host read of the B fine lengths.
+        ``durations``: fine frames per token to speak with instead of the duration predictor's -- a [B, Tx] tensor (e.g.
+        ``align(...)["durations"]``, or this method's own debug ``phoneme_durations``, which reproduces the default call bit for
+        bit), or a list of B rows where None leaves a row to the predictor (the batcher's mix).  ``scale_correction`` corrects the
+        predictor and is ignored on given rows; ``length_scale`` still multiplies.  A zero drops a token."""
         hip = self._rt.ready()
         dev = x.device
         B = x.shape[0]
@@ -247,7 +359,10 @@ class MatchaTTSInfer(nn.Module):
             raise ValueError("speaker must be an int or a LongTensor with one id per utterance")
 
         mu_x, logw, x_mask = self.encoder(x, x_lengths, e_enc, e_dur)
-        durations, cum, y_fine_lengths = hip.durations(logw, x_mask, scale_correction, length_scale)
+        if durations is None:
+            durations, cum, y_fine_lengths = hip.durations(logw, x_mask, scale_correction, length_scale)
+        else:
+            durations, cum, y_fine_lengths = self._given_durations(hip, durations, logw, x_mask, scale_correction, length_scale)
         # the one host sync of the path, as in the reference (utils/model.py:19: .item())
         max_fine = int(y_fine_lengths.max().item())
         if sync_max is not None:
