@@ -19,8 +19,8 @@ from .hparams import PathHParams
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = Path(os.environ["MTTS_HIP_LIB"]) if os.environ.get("MTTS_HIP_LIB") else HERE / "libmtts_hip.so"   # override: A/B of two builds
-SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "style_encoder.hip", "mas.hip", "model.hip"]
-HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", HERE.parent / "include" / "mtts.h"]
+SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "style_encoder.hip", "mas.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
+HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", CSRC / "host.h", HERE.parent / "include" / "mtts.h"]
 SOLVERS = {"euler": 0, "midpoint": 1, "rk4": 2}
 
 
@@ -95,7 +95,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         return obj
 
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 1)) as pool:
+    with ThreadPoolExecutor(max_workers=min(len(srcs), os.cpu_count() or 1, 16)) as pool:
         objs = list(pool.map(compile_one, srcs))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *[str(o) for o in objs], "-o", str(LIB)]
     if verbose:
@@ -243,6 +243,77 @@ def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 def stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
+
+
+class DeviceComponent:
+    """What the module mirrors of the library's weighted objects other than the path's context share (``vocoder.Vocos``,
+    ``style.StyleEncoder``; mixed in ahead of their ``nn.Module`` base): the handle, its weight image on the device, dirty tracking and
+    one grow-only workspace per stream.  A subclass gives ``_abi`` (prefix of its ``_create / _set_tensor / _weights_bytes /
+    _upload_weights / _destroy`` functions), ``_what`` (its name in error texts), ``_create_args()`` and calls ``_init_component()``
+    at the end of its ``__init__``; ``_tensors()`` is what gets registered (default: the state dict)."""
+    _abi = ""
+    _what = ""
+
+    def _init_component(self):
+        for k, v in (("_ctx", None), ("_weights", None), ("_ws", {}), ("_dirty", True)):
+            object.__setattr__(self, k, v)
+
+    def _create_args(self):
+        raise NotImplementedError
+
+    def _tensors(self) -> Dict[str, torch.Tensor]:
+        return dict(self.state_dict())
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        out = super().load_state_dict(state_dict, strict=strict, assign=assign)
+        object.__setattr__(self, "_dirty", True)
+        return out
+
+    def _apply(self, fn, *a, **k):
+        r = super()._apply(fn, *a, **k)
+        object.__setattr__(self, "_dirty", True)
+        return r
+
+    def _ready(self):
+        lib = load()
+        if self._ctx is None:
+            ctx = getattr(lib, self._abi + "_create")(*self._create_args())
+            if not ctx:
+                raise RuntimeError(self._abi + "_create: " + lib.mtts_last_error().decode())
+            object.__setattr__(self, "_ctx", ctx)
+        if self._dirty:
+            p = next(self.parameters())
+            if not p.is_cuda:
+                raise RuntimeError(f"matcha-tts-24k_amd: the {self._what} must be on a HIP device; there is no CPU path")
+            for k, v in self._tensors().items():
+                a = np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy())
+                check(getattr(lib, self._abi + "_set_tensor")(self._ctx, k.encode(), a.ctypes.data, a.size))
+            n = getattr(lib, self._abi + "_weights_bytes")(self._ctx)
+            if n < 0:
+                check(-1)
+            w = torch.empty(n, dtype=torch.uint8, device=p.device)
+            check(getattr(lib, self._abi + "_upload_weights")(self._ctx, w.data_ptr(), n))
+            object.__setattr__(self, "_weights", w)
+            self._ws.clear()
+            object.__setattr__(self, "_dirty", False)
+        return lib
+
+    def _workspace(self, need: int, device) -> torch.Tensor:
+        key = stream_ptr()                          # one grow-only scratch buffer per stream (see HipModel._workspace)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = None
+            self._ws.pop(key, None)
+            ws = torch.empty(need, dtype=torch.uint8, device=device)
+            self._ws[key] = ws
+        return ws
+
+    def __del__(self):
+        try:
+            if self._ctx:
+                getattr(load(), self._abi + "_destroy")(self._ctx)
+        except Exception:
+            pass
 
 
 def rope_tables(d: int, n: int = 4000):

@@ -1,5 +1,6 @@
-// Host-side model of the path: packed weights, workspace planning and the launch sequences of
-// TextEncoder.forward, Decoder.forward and BASECFM.solve (reference files cited at each function in model.hip).
+// Host-side data model of the path: packed weights, run-time switches and the contexts behind the opaque handles of
+// include/mtts.h.  The launch sequences of TextEncoder.forward, Decoder.forward and BASECFM.solve are in encoder.hip and
+// decoder.hip (reference files cited at each function), the packing in pack.hip.
 #pragma once
 #include <atomic>
 #include <map>
@@ -119,47 +120,57 @@ struct ProfRec { hipEvent_t e0, e1; int klass; double flops, bytes; std::string 
 
 }  // namespace mtts
 
-struct mtts_ctx {
-    mtts_config cfg;
+// What the three weighted objects (mtts_ctx, mtts_vocos, mtts_style) share, and all that the packer (host.h Packer) and the launch
+// wrappers (host.h run_gemm, LAUNCH) may depend on: the weight image and its life cycle, the arithmetic the panels are packed for,
+// the state of the call being enqueued, the profiler.
+namespace mtts {
+struct Component {
     std::map<std::string, std::vector<float>> raw;
     std::vector<float> image;     // host staging of the packed device image
     float* d_image = nullptr;     // caller-owned device buffer
     bool packed = false, uploaded = false;
-    int gemm_terms = 6;           // 0: fp32 MFMA, 6 / 3: split-bf16 MFMA, 2: split-fp16 (MTTS_GEMM_TERMS; see gemm_f32.hip)
-    unsigned int* cur_flag = nullptr;   // range flag of the call being enqueued: first word of its workspace (include/mtts.h)
     bool weights_saturate = false;      // fp16-split mode: a weight beyond +-65504 was met while packing
-    const int* d_tlen = nullptr;  // per-utterance frame limits of the next estimator calls (mtts_set_frame_limits), device [B]
+    int gemm_terms = 6;           // 0: fp32 MFMA, 6 / 3: split-bf16 MFMA, 2: split-fp16 (MTTS_GEMM_TERMS; see gemm_f32.hip)
     bool half16 = false;          // 16-bit storage mode (mtts_set_arithmetic(ctx, 16) / MTTS_GEMM_TERMS=16): the estimator's images are
                                   // single fp16 planes, one MFMA per MAC (BASELINE config #3); everything else as for terms 2
     bool bf16 = false;            // ... with bfloat16 planes (mtts_set_arithmetic(ctx, 17) / MTTS_GEMM_TERMS=17; half16 is set as well)
-    bool half_now = false;        // set while the estimator's launches are being enqueued in that mode
     bool fast16 = false;          // mtts_set_arithmetic(ctx, 1) / MTTS_GEMM_TERMS=1: the estimator's P16 kernels multiply the fp16 heads only
+    unsigned int* cur_flag = nullptr;   // range flag of the call being enqueued: first word of its workspace (include/mtts.h)
+    bool half_now = false;        // set while the estimator's launches are being enqueued in that mode
+    // profiling
+    bool prof_on = false;
+    std::vector<ProfRec> prof;
+    std::vector<hipEvent_t> ev_pool;
+    size_t ev_used = 0;
+    Component() = default;
+    Component(const Component&) = delete;
+    Component& operator=(const Component&) = delete;
+    ~Component() { for (hipEvent_t e : ev_pool) (void)hipEventDestroy(e); }
+};
+}  // namespace mtts
+
+struct mtts_ctx : mtts::Component {
+    mtts_config cfg;
+    const int* d_tlen = nullptr;  // per-utterance frame limits of the next estimator calls (mtts_set_frame_limits), device [B]
     mtts::Switches sw;            // the run-time switches as mtts_create read them
     unsigned int pair_epoch = 0;  // flag value of the latest pair launch (unique per launch)
     mtts::DecW dec;
     mtts::EncW enc;
-    // one thread at a time: the path's entry points hold this while they enqueue (per-call state above: cur_flag, half_now,
+    // one thread at a time: the path's entry points hold this while they enqueue (per-call state: cur_flag, half_now,
     // d_tlen, prof); a second thread's call fails instead of interleaving its launches with another call's flag pointer
     std::atomic<bool> in_use{false};
-    // profiling
-    bool prof_on = false;
-    std::vector<mtts::ProfRec> prof;
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
 };
 
 // Vocos-24k head: its own weight image and context (the reference loads it as a separate object,
-// reference matcha/inference.py:223-231).  `base` carries the tensor registry, the packed image and the profiler.
-struct mtts_vocos {
-    mtts_ctx base;
+// reference matcha/inference.py:223-231).
+struct mtts_vocos : mtts::Component {
     int n_mels = 100, dim = 512, inter = 1536, layers = 8, n_fft = 1024, hop = 256;
     int ld_spec = 0, im_off = 0;     // head output row: [Re/logmag 0..n_fft/2 | pad | Im/phase at im_off.. | pad]
     mtts::VocosW w;
 };
 
 // Style encoder (reference matcha/models/style_encoder.py:42-72): its own weight image and context, as the Vocos head.
-struct mtts_style {
-    mtts_ctx base;
+struct mtts_style : mtts::Component {
     int n_feats = 100, hidden = 256, layers = 4, emb = 96;
     mtts::StyleW w;
 };

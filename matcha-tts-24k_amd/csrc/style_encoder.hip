@@ -1,8 +1,8 @@
 // Kernels of the style encoder's forward pass that are not GEMMs (gfx950): reference matcha/models/style_encoder.py:36-72
 // (StyleEncoder.forward, masked_mean_pool) and the clip average of matcha/add_speaker.py:60-62.  The Conv1d(k5) + ReLU stack
-// runs on gemm_f32_kernel (five taps, ReLU and the prefix mask in its epilogue); the launch sequence is in model.hip
+// runs on gemm_f32_kernel (five taps, ReLU and the prefix mask in its epilogue); the launch sequence is behind the kernels
 // (mtts_style_forward).
-#include "kernels.h"
+#include "host.h"
 
 namespace mtts {
 
@@ -99,3 +99,114 @@ hipError_t launch_style_pool_proj(const float* h, const int64_t* lengths, int B,
 }
 
 }  // namespace mtts
+
+using namespace mtts;
+
+// ================================================================================================ style encoder
+// StyleEncoder (reference matcha/models/style_encoder.py:42-72): n_layers x { x * mask -> Conv1d(k5, pad 2) -> ReLU }, masked mean
+// over time, Linear(hidden -> spk_emb_dim) twice.  Tensors are registered under the reference's names ("convs.0.weight", ...,
+// "proj_enc.weight", "proj_dur.bias").
+static int style_pack(mtts_style* v) {
+    Component* c = v;
+    c->image.clear();
+    Packer P(c);
+    StyleW& W = v->w;
+    W = StyleW();
+    int cin = v->n_feats;
+    for (int i = 0; i < v->layers; ++i) {
+        const std::string p = "convs." + std::to_string(i) + ".";
+        W.convs.push_back(P.panel(p + "weight", p + "bias", 1, v->hidden, cin, 5));
+        cin = v->hidden;
+    }
+    const auto* we = P.get("proj_enc.weight", (size_t)v->emb * v->hidden);
+    const auto* be = P.get("proj_enc.bias", v->emb);
+    const auto* wd = P.get("proj_dur.weight", (size_t)v->emb * v->hidden);
+    const auto* bd = P.get("proj_dur.bias", v->emb);
+    if (we && be && wd && bd) {
+        const size_t n = (size_t)v->emb * v->hidden;
+        W.proj_w.off = P.alloc(2 * n); W.proj_w.n = (int)(2 * n);
+        W.proj_b.off = P.alloc(2 * v->emb); W.proj_b.n = 2 * v->emb;
+        std::memcpy(&c->image[W.proj_w.off], we->data(), n * sizeof(float));
+        std::memcpy(&c->image[W.proj_w.off + n], wd->data(), n * sizeof(float));
+        std::memcpy(&c->image[W.proj_b.off], be->data(), v->emb * sizeof(float));
+        std::memcpy(&c->image[W.proj_b.off + v->emb], bd->data(), v->emb * sizeof(float));
+    }
+    if (!P.ok) { set_error(P.why); return -1; }
+    c->packed = true;
+    return 0;
+}
+
+struct StyleBufs { float *X, *MASK, *H0, *H1; };
+static void style_plan(const mtts_style* v, int B, int T, WS& ws, StyleBufs& b) {
+    const size_t M = (size_t)B * T;
+    b.X = ws.f(M * round_up(v->n_feats, 4));
+    b.MASK = ws.f(M);
+    b.H0 = ws.f(M * v->hidden);
+    b.H1 = ws.f(M * v->hidden);
+}
+
+extern "C" {
+
+mtts_style* mtts_style_create(int n_feats, int hidden, int n_layers, int spk_emb_dim) {
+    if (n_feats <= 0 || (n_feats & 3) || hidden <= 0 || (hidden & 3) || n_layers < 1 || n_layers > 64 || spk_emb_dim <= 0 ||
+        (size_t)(5 * hidden + 2 * spk_emb_dim) * sizeof(float) > 48 * 1024) {
+        set_error("mtts_style_create: unsupported shape (n_feats and hidden multiples of 4, 1..64 layers, 5 * hidden + 2 * spk_emb_dim <= 12288)");
+        return nullptr;
+    }
+    mtts_style* v = new mtts_style();
+    v->gemm_terms = read_switches().gemm_terms;
+    v->n_feats = n_feats; v->hidden = hidden; v->layers = n_layers; v->emb = spk_emb_dim;
+    return v;
+}
+void mtts_style_destroy(mtts_style* v) { delete v; }
+int mtts_style_set_tensor(mtts_style* v, const char* key, const float* h, int64_t numel) {
+    if (!v) { set_error("null context"); return -1; }
+    return set_tensor(v, key, h, numel);
+}
+int64_t mtts_style_weights_bytes(mtts_style* v) { return weights_bytes(v, style_pack); }
+int mtts_style_upload_weights(mtts_style* v, void* d_weights, int64_t bytes) {
+    return upload_weights(v, style_pack, "mtts_style_upload_weights", d_weights, bytes);
+}
+int64_t mtts_style_workspace_bytes(mtts_style* v, int B, int T) {
+    if (!v) { set_error("null context"); return -1; }
+    if (B <= 0 || T <= 0) { set_error("mtts_style_workspace_bytes: bad shape"); return -1; }
+    WS ws(nullptr, 0);
+    StyleBufs b;
+    style_plan(v, B, T, ws, b);
+    return (int64_t)ws.off + 256;
+}
+// StyleEncoder.forward on a ragged batch + the clip average: n_layers + 2 launches (mask and transpose, the convs, pool and project).
+int mtts_style_forward(mtts_style* v, const float* d_mel, const int64_t* d_mel_lengths, int B, int T, const int32_t* d_group, int n_groups,
+                       float* d_e_enc, float* d_e_dur, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!v) { set_error("null context"); return -1; }
+    Component* c = v;
+    RET_IF(check_ready(c));
+    if (!d_mel || !d_mel_lengths || !d_e_enc || !d_e_dur || !d_ws || B <= 0 || B > 65535 || T <= 0 || (int64_t)B * T > (int64_t)1 << 30 ||
+        (d_group && n_groups <= 0)) {
+        set_error("mtts_style_forward: bad argument");
+        return -1;
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    WS ws(d_ws, (size_t)ws_bytes);
+    StyleBufs b;
+    style_plan(v, B, T, ws, b);
+    if (ws.overflow) { set_error("mtts_style_forward: workspace too small"); return -1; }
+    const int ldx = round_up(v->n_feats, 4);
+    LAUNCH(c, 2, 0, s, launch_style_prep(d_mel, d_mel_lengths, B, v->n_feats, T, b.X, ldx, b.MASK, s));
+    const float* in = b.X;
+    int ldin = ldx, cin = v->n_feats;
+    float* out = b.H0;
+    for (int i = 0; i < v->layers; ++i) {       // relu(conv(x * mask)); the mask of the NEXT layer's input is this epilogue's out_mask
+        GemmArgs a;
+        panel_args(c, v->w.convs[i], a); rows_plain(a, B, T); taps_centered(a, 5);
+        a.a0 = in; a.lda0 = ldin; a.c0 = cin; a.act = ACT_RELU; a.out_mask = b.MASK; a.out = out; a.ldc = v->hidden;
+        RET_IF(run_gemm(c, a, s));
+        in = out; ldin = v->hidden; cin = v->hidden;
+        out = (out == b.H0) ? b.H1 : b.H0;
+    }
+    LAUNCH(c, 2, 0, s, launch_style_pool_proj(in, d_mel_lengths, B, T, v->hidden, v->emb, W(c, v->w.proj_w.off), W(c, v->w.proj_b.off),
+                                              d_group, d_group ? n_groups : B, d_e_enc, d_e_dur, s));
+    return 0;
+}
+
+}  // extern "C"

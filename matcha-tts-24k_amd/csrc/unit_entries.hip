@@ -1,0 +1,427 @@
+// Context-free test entries of the kernels (include/mtts.h "single kernels"): each converts fp32 operands to what its kernel
+// reads, packs weights as the model does, launches, and converts back.  Nothing in the production path calls into this file.
+#include "host.h"
+
+using namespace mtts;
+
+// ---- what the unit entries of the two chain kernels share (tblock_chain.hip: P16 images, 2 halves per element; tblock_chain_h16.hip:
+// H16 images, 1 half per element, fp16 or bfloat16)
+// row sums of a panel as the kernel multiplies it: exact for the two-plane stream, rounded to the one-plane stream's 16-bit type
+static double plain_row_sum(const float* w, int K, bool) {
+    double a = 0.0;
+    for (int k = 0; k < K; ++k) a += (double)w[k];
+    return a;
+}
+static double rounded_row_sum(const float* w, int K, bool bf16) {
+    double a = 0.0;
+    for (int k = 0; k < K; ++k) a += bf16 ? (double)(float)(__bf16)w[k] : (double)(float)(_Float16)fminf(fmaxf(w[k], -65504.f), 65504.f);
+    return a;
+}
+// the chain kernels' column constants: wsum1 | b1 | p0 | p1 | b_out | b2 | wsum_qkv | b_qkv
+static std::vector<float> chain_entry_consts(int C, int inner, int n_qkv, const float* h_b_out, const float* h_w1, const float* h_b1,
+                                             const float* h_p0, const float* h_p1, const float* h_b2, const float* h_w_qkv,
+                                             const float* h_b_qkv, double (*row_sum)(const float*, int, bool), bool bf16) {
+    std::vector<float> hc((size_t)18 * C + 2 * (size_t)n_qkv, 0.f);
+    for (int n = 0; n < 4 * C; ++n) {
+        hc[n] = (float)row_sum(h_w1 + (size_t)n * C, C, bf16);
+        hc[4 * C + n] = h_b1 ? h_b1[n] : 0.f;
+        hc[8 * C + n] = h_p0[n];
+        hc[12 * C + n] = h_p1[n];
+    }
+    for (int n = 0; n < C; ++n) { hc[16 * C + n] = (inner && h_b_out) ? h_b_out[n] : 0.f; hc[17 * C + n] = h_b2 ? h_b2[n] : 0.f; }
+    for (int n = 0; n < n_qkv; ++n) {
+        hc[18 * C + n] = (float)row_sum(h_w_qkv + (size_t)n * C, C, bf16);
+        hc[18 * C + n_qkv + n] = h_b_qkv ? h_b_qkv[n] : 0.f;
+    }
+    return hc;
+}
+// Scratch carve-up (stream | constants | images of the attention output, x, x_out and q|k|v; `tail`: 256-aligned, what the pair form
+// adds), upload of stream and constants, conversion of the fp32 operands to images, and the fields ChainArgs and ChainH16Args share.
+struct ChainEntryBufs { _Float16 *xo16, *q16; char* tail; };
+template <class Args>
+static int chain_entry_begin(Args& a, ChainEntryBufs& b, int ew, bool bf16, const std::vector<uint16_t>& hs, long frags,
+                             const std::vector<float>& hc, const float* d_att, const float* d_x, int M, int C, int inner, int n_qkv,
+                             const float* d_out_mask, int qb, int ch, void* d_scratch, hipStream_t s) {
+    const bool h16 = ew == 1;
+    const float lscale = h16 ? 1.0f : 2048.0f;
+    char* sc = static_cast<char*>(d_scratch);
+    void* d_stream = sc; sc += hs.size() * 2;
+    float* d_c = reinterpret_cast<float*>(sc); sc += hc.size() * 4;
+    sc = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(sc) + 255) & ~uintptr_t(255));
+    _Float16* att16 = reinterpret_cast<_Float16*>(sc); sc += (size_t)M * inner * 2 * ew;
+    _Float16* x16 = reinterpret_cast<_Float16*>(sc); sc += (size_t)M * C * 2 * ew;
+    b.xo16 = reinterpret_cast<_Float16*>(sc); sc += (size_t)M * C * 2 * ew;
+    b.q16 = reinterpret_cast<_Float16*>(sc); sc += (size_t)M * n_qkv * 2 * ew;
+    b.tail = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(sc) + 255) & ~uintptr_t(255));
+    HIP_OK(hipMemcpyAsync(d_stream, hs.data(), hs.size() * 2, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(d_c, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));                      // (the host vectors go out of scope)
+    if (inner) HIP_OK(launch_to_p16(d_att, inner, nullptr, M, inner, inner, att16, ew * inner, lscale, s, nullptr, h16, h16 && bf16));
+    HIP_OK(launch_to_p16(d_x, C, nullptr, M, C, C, x16, ew * C, lscale, s, nullptr, h16, h16 && bf16));
+    a.M = M; a.C = C; a.inner = inner; a.att16 = att16; a.ld_att = ew * inner; a.x16 = x16; a.ld_x = ew * C;
+    a.wstream = static_cast<decltype(a.wstream)>(d_stream); a.stream_frags = frags;
+    a.consts = d_c;
+    if (n_qkv) { a.wsum_qkv = d_c + 18 * C; a.b_qkv = d_c + 18 * C + n_qkv; a.n_qkv = n_qkv; a.qkv16 = b.q16; a.ld_qkv = ew * n_qkv; }
+    a.x_out = b.xo16; a.ld_out = ew * C; a.x_out_mask = d_out_mask;
+    a.qb = qb; a.ch = ch;
+    return 0;
+}
+// After the entry's own first launch: the measurement (`repeat` further launches between two events; relaunch(i) enqueues the
+// i-th), then the output images back to fp32.
+template <class Relaunch>
+static int chain_entry_finish(const ChainEntryBufs& b, int ew, bool bf16, int M, int C, int n_qkv, float* d_x_out, float* d_qkv_out,
+                              hipStream_t s, int repeat, float* h_ms, Relaunch relaunch) {
+    if (repeat > 0 && h_ms) {
+        hipEvent_t e0, e1;
+        HIP_OK(hipEventCreate(&e0));
+        HIP_OK(hipEventCreate(&e1));
+        HIP_OK(hipEventRecord(e0, s));
+        for (int i = 0; i < repeat; ++i) HIP_OK(relaunch(i));
+        HIP_OK(hipEventRecord(e1, s));
+        HIP_OK(hipEventSynchronize(e1));
+        HIP_OK(hipEventElapsedTime(h_ms, e0, e1));
+        *h_ms /= (float)repeat;
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    }
+    if (ew == 1) {
+        HIP_OK(launch_from_h16(b.xo16, C, M, C, bf16, d_x_out, C, s));
+        if (n_qkv && d_qkv_out) HIP_OK(launch_from_h16(b.q16, n_qkv, M, n_qkv, bf16, d_qkv_out, n_qkv, s));
+        return 0;
+    }
+    HIP_OK(launch_from_p16(b.xo16, 2 * C, M, C, 2048.0f, d_x_out, C, s));
+    if (n_qkv && d_qkv_out) HIP_OK(launch_from_p16(b.q16, 2 * n_qkv, M, n_qkv, 1.0f, d_qkv_out, n_qkv, s));
+    return 0;
+}
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------------ single kernels
+int64_t mtts_gemm_packed_bytes(int N, int C, int ntaps) {   // fp32 panel + three bf16 planes
+    const int64_t n = (int64_t)round_up(N, GEMM_BN) * ntaps * round_up(C, GEMM_BK);
+    return n * 4 + ((3 * n + 1) / 2) * 4 + 256;
+}
+
+int mtts_gemm_f32(const float* d_a, int lda, int B, int T_in, int C, int ntaps, const int* h_tap_off, int in_stride, int T_out,
+                  const float* d_a_mask, const float* d_a_mean, const float* d_a_rstd, const float* d_a_part, int a_nparts,
+                  const float* d_w, void* d_wpacked, const float* d_bias, int N, int act, const float* d_p0, const float* d_p1,
+                  const float* d_res, int ldr, const float* d_out_mask, float out_scale, float* d_out, int ldc, float* d_stats_out,
+                  int terms, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ntaps < 1 || ntaps > MAX_TAPS) { set_error("ntaps out of range"); return -1; }
+    if (terms < 0) terms = read_switches().gemm_terms;
+    if (terms != 0 && terms != 2 && terms != 3 && terms != 6) { set_error("terms must be 0, 2, 3 or 6"); return -1; }
+    const size_t npanel = (size_t)round_up(N, GEMM_BN) * ntaps * round_up(C, GEMM_BK);
+    float* planes = static_cast<float*>(d_wpacked) + ((npanel + 63) & ~size_t(63));
+    if (d_w) {   // NULL: d_wpacked already packed by an earlier call
+        HIP_OK(launch_pack_weight(d_w, N, C, ntaps, static_cast<float*>(d_wpacked), s));
+        if (terms == 2) HIP_OK(launch_split_panel_f16(static_cast<const float*>(d_wpacked), npanel, planes, s));
+        else HIP_OK(launch_split_panel(static_cast<const float*>(d_wpacked), npanel, planes, s));
+    }
+    GemmArgs a;
+    a.a0 = d_a; a.lda0 = lda; a.c0 = C; a.ktap = round_up(C, GEMM_BK); a.ntaps = ntaps;
+    for (int j = 0; j < ntaps; ++j) a.tap_off[j] = h_tap_off ? h_tap_off[j] : 0;
+    a.in_stride = in_stride; a.B = B; a.T_in = T_in; a.T_out = T_out;
+    a.a_mask = d_a_mask; a.a_mean = d_a_mean; a.a_rstd = d_a_rstd; a.a_part = d_a_part; a.a_nparts = a_nparts;
+    a.stats_out = d_stats_out;
+    a.w = static_cast<const float*>(d_wpacked); a.w16 = planes; a.terms = terms; a.bias = d_bias; a.N = N; a.act = act; a.p0 = d_p0; a.p1 = d_p1;
+    a.res = d_res; a.ldr = ldr; a.out_mask = d_out_mask; a.out_scale = out_scale; a.out = d_out; a.ldc = ldc;
+    a.out_T = T_out; a.out_stride = 1; a.out_off = 0;
+    HIP_OK(launch_gemm(a, s));
+    return 0;
+}
+
+// Test entry for the P16 GEMM (gemm_p16.hip): the fp32 operand is converted to its P16 image (optionally masked) in
+// d_scratch, the panel is packed as for mtts_gemm_f32 (terms = 2) and its row sums are computed for the LayerNorm algebra;
+// the optional P16 output is decoded back to fp32 into d_out16_f32.
+int64_t mtts_gemm_p16_scratch_bytes(int B, int T_in, int C, int T_out, int N) {
+    return (int64_t)B * T_in * C * 4 + (int64_t)B * T_out * round_up(N, 32) * 4 + (int64_t)round_up(N, GEMM_BN) * 4 + 1024;
+}
+__global__ void panel_rowsum_kernel(const float* __restrict__ panel, int Np, int Kp, float* __restrict__ out) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n >= Np) return;
+    double acc = 0.0;
+    for (int k = 0; k < Kp; ++k) acc += (double)panel[(size_t)n * Kp + k];
+    out[n] = (float)acc;
+}
+int mtts_gemm_p16(const float* d_a, int lda, int B, int T_in, int C, int ntaps, const int* h_tap_off, int in_stride, int T_out,
+                  const float* d_a_mask, const float* d_a_mean, const float* d_a_rstd, const float* d_a_part, int a_nparts,
+                  const float* d_w, void* d_wpacked, const float* d_bias, int N, int act, const float* d_p0, const float* d_p1,
+                  const float* d_res, int ldr, const float* d_out_mask, float out_scale, float* d_out, int ldc,
+                  float* d_out16_f32, float out_lscale, float* d_stats_out, int force_bm, void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ntaps < 1 || ntaps > MAX_TAPS) { set_error("ntaps out of range"); return -1; }
+    if (C % GEMM_BK) { set_error("P16 operands need C % 32 == 0"); return -1; }
+    if (!d_w || !d_wpacked || !d_scratch) { set_error("null buffer"); return -1; }
+    const int Np = round_up(N, GEMM_BN), Kp = ntaps * C;
+    const size_t npanel = (size_t)Np * Kp;
+    float* planes = static_cast<float*>(d_wpacked) + ((npanel + 63) & ~size_t(63));
+    HIP_OK(launch_pack_weight(d_w, N, C, ntaps, static_cast<float*>(d_wpacked), s));
+    HIP_OK(launch_split_panel_f16(static_cast<const float*>(d_wpacked), npanel, planes, s));
+    char* sc = static_cast<char*>(d_scratch);
+    _Float16* a16 = reinterpret_cast<_Float16*>(sc);
+    sc += (size_t)B * T_in * C * 4;
+    _Float16* o16 = reinterpret_cast<_Float16*>(sc);
+    sc += (size_t)B * T_out * round_up(N, 32) * 4;
+    float* wsum = reinterpret_cast<float*>(sc);
+    HIP_OK(launch_to_p16(d_a, lda, d_a_mask, B * T_in, C, C, a16, 2 * C, 2048.0f, s));
+    hipLaunchKernelGGL(panel_rowsum_kernel, dim3((Np + 127) / 128), dim3(128), 0, s, static_cast<const float*>(d_wpacked), Np, Kp, wsum);
+    HIP_OK(hipGetLastError());
+    GemmArgs a;
+    a.a16_0 = a16; a.lda16_0 = 2 * C; a.c0 = C; a.ktap = C; a.ntaps = ntaps;
+    for (int j = 0; j < ntaps; ++j) a.tap_off[j] = h_tap_off ? h_tap_off[j] : 0;
+    a.in_stride = in_stride; a.B = B; a.T_in = T_in; a.T_out = T_out;
+    a.a_mean = d_a_mean; a.a_rstd = d_a_rstd; a.a_part = d_a_part; a.a_nparts = a_nparts; a.wsum = wsum;
+    a.stats_out = d_stats_out;
+    a.w16 = planes; a.terms = 2; a.bias = d_bias; a.N = N; a.act = act; a.p0 = d_p0; a.p1 = d_p1;
+    a.res = d_res; a.ldr = ldr; a.out_mask = d_out_mask; a.out_scale = out_scale; a.out = d_out; a.ldc = ldc;
+    if (d_out16_f32) { a.out16 = o16; a.ld16 = 2 * N; a.out_lscale = out_lscale; }
+    a.out_T = T_out; a.out_stride = 1; a.out_off = 0; a.force_bm = force_bm;
+    HIP_OK(launch_gemm(a, s));
+    if (d_out16_f32) HIP_OK(launch_from_p16(o16, 2 * N, B * T_out, N, out_lscale, d_out16_f32, N, s));
+    return 0;
+}
+
+// Test entry for the one-launch Block1D (resnet_conv.hip): x [B*T, C] fp32 (already masked by the caller where the model would)
+// is converted to its P16 image in d_scratch, the Conv1d(k3) weight is packed and split as for mtts_gemm_p16, the P16 output is
+// decoded back to fp32 [B*T, N].  c1 > 0: the last c1 channels of x form a second input segment (the up path's skip concat).
+int64_t mtts_conv_gn_scratch_bytes(int B, int T, int C, int N) { return (int64_t)B * T * (C + N) * 4 + 1024; }
+int mtts_conv_gn(const float* d_x, int B, int T, int C, int c1, const float* d_w, void* d_wpacked, const float* d_bias, int N,
+                 const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias, const int* d_nrows,
+                 const int* d_nextra, const float* d_bias_stats, float eps, float* d_out, void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!d_x || !d_w || !d_wpacked || !d_scratch || !d_out) { set_error("null buffer"); return -1; }
+    if (C <= 0 || (C % 32) || c1 < 0 || (c1 % 32) || c1 >= C) { set_error("mtts_conv_gn: C and c1 must be multiples of 32, c1 < C"); return -1; }
+    if (!conv_gn_supported(T, N)) { set_error("mtts_conv_gn: unsupported shape (N = 384, 65 <= T <= 384)"); return -1; }
+    const int Np = round_up(N, GEMM_BN), Kp = 3 * C;
+    const size_t npanel = (size_t)Np * Kp;
+    float* planes = static_cast<float*>(d_wpacked) + ((npanel + 63) & ~size_t(63));
+    HIP_OK(launch_pack_weight(d_w, N, C, 3, static_cast<float*>(d_wpacked), s));
+    HIP_OK(launch_split_panel_f16(static_cast<const float*>(d_wpacked), npanel, planes, s));
+    _Float16* a16 = static_cast<_Float16*>(d_scratch);
+    _Float16* o16 = a16 + (size_t)B * T * C * 2;
+    HIP_OK(launch_to_p16(d_x, C, nullptr, B * T, C, C, a16, 2 * C, 2048.0f, s));
+    ConvGnArgs a;
+    a.a16_0 = a16; a.lda16_0 = 2 * C; a.c0 = C - c1;
+    if (c1) { a.a16_1 = a16 + 2 * (C - c1); a.lda16_1 = 2 * C; a.c1 = c1; }
+    a.w16 = planes; a.bias = d_bias; a.B = B; a.T = T; a.N = N;
+    a.gamma = d_gamma; a.beta = d_beta; a.mask = d_mask; a.chbias = d_chbias; a.nrows = d_nrows; a.nextra = d_nextra; a.bias_stats = d_bias_stats;
+    a.eps = eps; a.out16 = o16; a.ld16 = 2 * N;
+    HIP_OK(launch_conv_gn(a, s));
+    HIP_OK(launch_from_p16(o16, 2 * N, B * T, N, 2048.0f, d_out, N, s));
+    return 0;
+}
+
+int mtts_attention_f32(const float* d_qkv, const float* d_mask, int B, int T, int H, int D, float scale, int mask_mode, float* d_out,
+                       void* stream) {
+    AttnArgs a;
+    a.qkv = d_qkv; a.mask = d_mask; a.out = d_out; a.B = B; a.T = T; a.H = H; a.D = D; a.scale = scale; a.mask_mode = mask_mode;
+    HIP_OK(launch_attention(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+// Test entry for the attention kernel's P16 I/O: q|k|v converted to a P16 image with unscaled residuals in d_scratch
+// (>= 16*B*T*H*64 bytes), the P16 output decoded back to fp32.  D must be 64.
+int mtts_attention_p16(const float* d_qkv, const float* d_mask, int B, int T, int H, int D, float scale, int mask_mode, float* d_out,
+                       void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (D != 64 || !d_scratch) { set_error("P16 attention needs D == 64 and a scratch buffer"); return -1; }
+    const int M = B * T, C3 = 3 * H * D;
+    _Float16* q16 = static_cast<_Float16*>(d_scratch);
+    _Float16* o16 = q16 + (size_t)M * 2 * C3;
+    HIP_OK(launch_to_p16(d_qkv, C3, nullptr, M, C3, C3, q16, 2 * C3, 1.0f, s));
+    AttnArgs a;
+    a.qkv16 = q16; a.ld16 = 2 * C3; a.out16 = o16; a.ldo16 = 2 * H * D; a.mask = d_mask;
+    a.B = B; a.T = T; a.H = H; a.D = D; a.scale = scale; a.mask_mode = mask_mode;
+    HIP_OK(launch_attention(a, s));
+    HIP_OK(launch_from_p16(o16, 2 * H * D, M, H * D, a.out_lscale, d_out, H * D, s));
+    return 0;
+}
+
+int mtts_row_stats(const float* d_x, int M, int C, int ld, float eps, float* d_mean, float* d_rstd, void* stream) {
+    HIP_OK(launch_row_stats(d_x, M, C, ld, eps, d_mean, d_rstd, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int mtts_channel_layernorm(const float* d_x, int B, int T, int C, const float* d_gamma, const float* d_beta, float eps, int act,
+                           const float* d_film, const float* d_mask, float* d_y, void* stream) {
+    if (B <= 0 || T <= 0) { set_error("mtts_channel_layernorm: empty batch"); return -1; }
+    if (act != ACT_NONE && act != ACT_SILU) { set_error("mtts_channel_layernorm: act must be 0 (none) or 2 (SiLU)"); return -1; }
+    LayerNormArgs a;
+    a.x = d_x; a.ldx = C; a.y = d_y; a.ldy = C; a.M = B * T; a.C = C; a.T = T; a.gamma = d_gamma; a.beta = d_beta; a.eps = eps;
+    a.act = act; a.film = d_film; a.mask = d_mask;
+    HIP_OK(launch_layernorm(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int64_t mtts_groupnorm_scratch_bytes(int B, int T, int G) { return (int64_t)B * gn_chunks_max(T) * G * 2 * (int64_t)sizeof(float); }
+
+int mtts_groupnorm_mish(const float* d_y, const float* d_gamma, const float* d_beta, const float* d_mask, int B, int T, int C, int G,
+                        float eps, float* d_out, void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    HIP_OK(launch_gn_partial(d_y, B, T, C, G, static_cast<float*>(d_scratch), s));
+    GnApplyArgs a;
+    a.y = d_y; a.partial = static_cast<const float*>(d_scratch); a.gamma = d_gamma; a.beta = d_beta; a.mask = d_mask;
+    a.out = d_out; a.B = B; a.T = T; a.C = C; a.G = G; a.eps = eps;
+    HIP_OK(launch_gn_apply(a, s));
+    return 0;
+}
+
+// Test entry for the transformer-block chain (tblock_chain.hip).  fp32 operands are converted to P16 images in d_scratch, the fp32
+// panels (LayerNorm affines already folded: w1 / b1 for the FeedForward, w_qkv / b_qkv for the following block) are packed into a
+// fragment stream on the host, and the P16 outputs are decoded back to fp32.  w_qkv == NULL: no q|k|v phase; inner == 0: no
+// out-projection (the FeedForward alone on d_x).  h_* pointers are HOST memory, d_* device memory.
+// the model's launch plan for M rows (test entry; no GPU): rows per workgroup and prefetch workgroups
+int mtts_chain_plan(int M, int ch, int* qb, int* prefetch_wgs) {
+    if (M <= 0 || (ch != 128 && ch != 256) || !qb || !prefetch_wgs) { set_error("mtts_chain_plan: bad argument"); return -1; }
+    chain_plan(M, ch, 0, read_switches().chain_pf, qb, prefetch_wgs);
+    return 0;
+}
+int64_t mtts_chain_stream_frags(int C, int inner, int ch, int n_qkv) {
+    if (!chain_supported(C, inner, n_qkv) || (ch != 128 && ch != 256)) { set_error("mtts_chain_stream_frags: unsupported shape"); return -1; }
+    return chain_stream_frags(C, inner, ch, n_qkv);
+}
+int mtts_chain_stream_pack(int C, int inner, int ch, int n_qkv, const float* h_w_out, const float* h_w1, const float* h_w2,
+                           const float* h_w_qkv, uint16_t* h_dst) {
+    if (!chain_supported(C, inner, n_qkv) || (ch != 128 && ch != 256) || !h_w1 || !h_w2 || !h_dst || (inner && !h_w_out) || (n_qkv && !h_w_qkv)) {
+        set_error("mtts_chain_stream_pack: unsupported shape or null panel");
+        return -1;
+    }
+    chain_stream_pack(C, inner, ch, n_qkv, h_w_out, h_w1, h_w2, h_w_qkv, h_dst, nullptr);
+    return 0;
+}
+// pair form: fragments per (half, wave), and the packing of the 2 x 8 streams (host only)
+int64_t mtts_chain_stream_frags_pair(int C, int inner, int ch, int n_qkv) {
+    if (!chain_supported_pair(C, inner, ch, n_qkv) || (ch != 128 && ch != 256)) { set_error("mtts_chain_stream_frags_pair: unsupported shape"); return -1; }
+    return chain_stream_frags_pair(C, inner, ch, n_qkv);
+}
+int mtts_chain_stream_pack_pair(int C, int inner, int ch, int n_qkv, const float* h_w_out, const float* h_w1, const float* h_w2,
+                                const float* h_w_qkv, uint16_t* h_dst) {
+    if (!chain_supported_pair(C, inner, ch, n_qkv) || (ch != 128 && ch != 256) || !h_w_out || !h_w1 || !h_w2 || !h_dst || (n_qkv && !h_w_qkv)) {
+        set_error("mtts_chain_stream_pack_pair: unsupported shape or null panel");
+        return -1;
+    }
+    chain_stream_pack_pair(C, inner, ch, n_qkv, h_w_out, h_w1, h_w2, h_w_qkv, h_dst, nullptr);
+    return 0;
+}
+int64_t mtts_tblock_chain_scratch_bytes(int M, int C, int inner, int n_qkv, int ch) {
+    if (!chain_supported(C, inner, n_qkv)) return -1;
+    int64_t stream = (int64_t)chain_stream_frags(C, inner, ch, n_qkv) * CHAIN_WAVES * 1024;
+    if (chain_supported_pair(C, inner, ch, n_qkv)) stream = std::max<int64_t>(stream, (int64_t)chain_stream_frags_pair(C, inner, ch, n_qkv) * 2 * CHAIN_WAVES * 1024);
+    const int64_t pair_scratch = 2 * ((int64_t)M + 64) * C * 4 + 2 * ((int64_t)M / 32 + 2) * 4 + 512;       // partial sums + flags of the pair form
+    return stream + (int64_t)M * 4 * (inner + 2 * C + n_qkv) + 4 * (int64_t)(2 * n_qkv + 18 * C) + 4096 + pair_scratch;
+}
+int mtts_tblock_chain(const float* d_att, const float* d_x, int M, int C, int inner, const float* h_w_out, const float* h_b_out,
+                      const float* h_w1, const float* h_b1, const float* h_p0, const float* h_p1, const float* h_w2, const float* h_b2,
+                      const float* h_w_qkv, const float* h_b_qkv, int n_qkv, const float* d_out_mask, int qb, int ch, float* d_x_out,
+                      float* d_qkv_out, void* d_scratch, void* stream) {
+    return mtts_tblock_chain_timed(d_att, d_x, M, C, inner, h_w_out, h_b_out, h_w1, h_b1, h_p0, h_p1, h_w2, h_b2, h_w_qkv, h_b_qkv, n_qkv,
+                                   d_out_mask, qb, ch, d_x_out, d_qkv_out, d_scratch, stream, 0, nullptr);
+}
+static int tblock_chain_entry(bool pair, const float* d_att, const float* d_x, int M, int C, int inner, const float* h_w_out, const float* h_b_out,
+                              const float* h_w1, const float* h_b1, const float* h_p0, const float* h_p1, const float* h_w2, const float* h_b2,
+                              const float* h_w_qkv, const float* h_b_qkv, int n_qkv, const float* d_out_mask, int qb, int ch, float* d_x_out,
+                              float* d_qkv_out, void* d_scratch, void* stream, int repeat, float* h_ms) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!h_w_qkv) n_qkv = 0;
+    if (!chain_supported(C, inner, n_qkv) || !d_x || !h_w1 || !h_w2 || !d_scratch || !d_x_out) { set_error("mtts_tblock_chain: unsupported shape or null buffer"); return -1; }
+    if (pair && !chain_supported_pair(C, inner, ch, n_qkv)) { set_error("mtts_tblock_chain_pair: unsupported shape"); return -1; }
+    const long frags = pair ? chain_stream_frags_pair(C, inner, ch, n_qkv) : chain_stream_frags(C, inner, ch, n_qkv);
+    std::vector<uint16_t> hs((size_t)frags * (pair ? 2 : 1) * CHAIN_WAVES * 512);
+    if (pair) chain_stream_pack_pair(C, inner, ch, n_qkv, h_w_out, h_w1, h_w2, h_w_qkv, hs.data(), nullptr);
+    else chain_stream_pack(C, inner, ch, n_qkv, h_w_out, h_w1, h_w2, h_w_qkv, hs.data(), nullptr);
+    const std::vector<float> hc = chain_entry_consts(C, inner, n_qkv, h_b_out, h_w1, h_b1, h_p0, h_p1, h_b2, h_w_qkv, h_b_qkv, plain_row_sum, false);
+    ChainArgs a;
+    ChainEntryBufs b;
+    RET_IF(chain_entry_begin(a, b, 2, false, hs, frags, hc, d_att, d_x, M, C, inner, n_qkv, d_out_mask, qb, ch, d_scratch, s));
+    a.pf_wgs = read_switches().chain_pf;
+    if (pair) {                                           // partial sums + flags of the pair form
+        float* d_part = reinterpret_cast<float*>(b.tail);
+        unsigned int* d_flag = reinterpret_cast<unsigned int*>(b.tail + 2 * ((size_t)M + 64) * C * 4);
+        HIP_OK(hipMemsetAsync(d_flag, 0, 2 * ((size_t)M / 32 + 2) * 4, s));
+        a.pair = 1; a.pair_part = d_part; a.pair_flag = d_flag; a.pair_epoch = 1; a.pf_wgs = a.pf_wgs ? 16 : 0;
+    }
+#ifdef MTTS_CHAIN_STAMP
+    a.kstamp = reinterpret_cast<unsigned long long*>(d_qkv_out);      // (diagnostic build: the stamps land in the q|k|v output buffer)
+#endif
+    HIP_OK(launch_tblock_chain(a, s));
+#ifdef MTTS_CHAIN_STAMP
+    HIP_OK(hipStreamSynchronize(s));
+    return 0;
+#endif
+    return chain_entry_finish(b, 2, false, M, C, n_qkv, d_x_out, d_qkv_out, s, repeat, h_ms, [&](int i) {
+        if (pair) a.pair_epoch = 2 + i;
+        return launch_tblock_chain(a, s);
+    });
+}
+
+int mtts_tblock_chain_timed(const float* d_att, const float* d_x, int M, int C, int inner, const float* h_w_out, const float* h_b_out,
+                            const float* h_w1, const float* h_b1, const float* h_p0, const float* h_p1, const float* h_w2, const float* h_b2,
+                            const float* h_w_qkv, const float* h_b_qkv, int n_qkv, const float* d_out_mask, int qb, int ch, float* d_x_out,
+                            float* d_qkv_out, void* d_scratch, void* stream, int repeat, float* h_ms) {
+    return tblock_chain_entry(false, d_att, d_x, M, C, inner, h_w_out, h_b_out, h_w1, h_b1, h_p0, h_p1, h_w2, h_b2, h_w_qkv, h_b_qkv, n_qkv,
+                              d_out_mask, qb, ch, d_x_out, d_qkv_out, d_scratch, stream, repeat, h_ms);
+}
+// the pair form of the same launch (two workgroups per row tile; ChainArgs::pair): qb = 48 or 32, at most 120 row tiles
+int mtts_tblock_chain_pair_timed(const float* d_att, const float* d_x, int M, int C, int inner, const float* h_w_out, const float* h_b_out,
+                                 const float* h_w1, const float* h_b1, const float* h_p0, const float* h_p1, const float* h_w2, const float* h_b2,
+                                 const float* h_w_qkv, const float* h_b_qkv, int n_qkv, const float* d_out_mask, int qb, int ch, float* d_x_out,
+                                 float* d_qkv_out, void* d_scratch, void* stream, int repeat, float* h_ms) {
+    return tblock_chain_entry(true, d_att, d_x, M, C, inner, h_w_out, h_b_out, h_w1, h_b1, h_p0, h_p1, h_w2, h_b2, h_w_qkv, h_b_qkv, n_qkv,
+                              d_out_mask, qb, ch, d_x_out, d_qkv_out, d_scratch, stream, repeat, h_ms);
+}
+
+// ---- the one-plane chain of the 16-bit storage modes (tblock_chain_h16.hip): host-only stream functions and the unit entry
+int64_t mtts_chain_stream_frags_h16(int C, int inner, int ch, int n_qkv) {
+    if (!chain_h16_supported(C, inner, ch, n_qkv)) { set_error("mtts_chain_stream_frags_h16: unsupported shape"); return -1; }
+    return chain_h16_stream_frags(C, inner, ch, n_qkv);
+}
+int mtts_chain_stream_pack_h16(int C, int inner, int ch, int n_qkv, const float* h_w_out, const float* h_w1, const float* h_w2,
+                               const float* h_w_qkv, int bf16, uint16_t* h_dst, int* saturates) {
+    if (!chain_h16_supported(C, inner, ch, n_qkv) || !h_w1 || !h_w2 || !h_dst || (inner && !h_w_out) || (n_qkv && !h_w_qkv)) {
+        set_error("mtts_chain_stream_pack_h16: unsupported shape or null panel");
+        return -1;
+    }
+    bool sat = false;
+    chain_h16_stream_pack(C, inner, ch, n_qkv, h_w_out, h_w1, h_w2, h_w_qkv, bf16 != 0, h_dst, &sat);
+    if (sat && saturates) *saturates = 1;
+    return 0;
+}
+int64_t mtts_tblock_chain_h16_scratch_bytes(int M, int C, int inner, int n_qkv, int ch) {
+    if (M <= 0 || !chain_h16_supported(C, inner, ch, n_qkv)) return -1;
+    const int64_t stream = (int64_t)chain_h16_stream_frags(C, inner, ch, n_qkv) * CHAIN_WAVES * 1024;
+    return stream + (int64_t)M * 2 * (inner + 2 * C + n_qkv) + 4 * (int64_t)(2 * n_qkv + 18 * C) + 4096;
+}
+int mtts_tblock_chain_h16_timed(const float* d_att, const float* d_x, int M, int C, int inner, const float* h_w_out, const float* h_b_out,
+                                const float* h_w1, const float* h_b1, const float* h_p0, const float* h_p1, const float* h_w2,
+                                const float* h_b2, const float* h_w_qkv, const float* h_b_qkv, int n_qkv, const float* d_out_mask,
+                                int bf16, int qb, int ch, int pf_wgs, float* d_x_out, float* d_qkv_out, void* d_scratch, void* stream,
+                                int repeat, float* h_ms) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!h_w_qkv) n_qkv = 0;
+    if (M <= 0 || !chain_h16_supported(C, inner, ch, n_qkv) || !d_x || !h_w1 || !h_w2 || !h_p0 || !h_p1 || !d_scratch || !d_x_out || (inner && (!d_att || !h_w_out)) ||
+        (n_qkv && !d_qkv_out)) {
+        set_error("mtts_tblock_chain_h16: unsupported shape or null buffer");
+        return -1;
+    }
+    const bool bf = bf16 != 0;
+    const long frags = chain_h16_stream_frags(C, inner, ch, n_qkv);
+    std::vector<uint16_t> hs((size_t)frags * CHAIN_WAVES * 512);
+    chain_h16_stream_pack(C, inner, ch, n_qkv, h_w_out, h_w1, h_w2, h_w_qkv, bf, hs.data(), nullptr);
+    const std::vector<float> hc = chain_entry_consts(C, inner, n_qkv, h_b_out, h_w1, h_b1, h_p0, h_p1, h_b2, h_w_qkv, h_b_qkv, rounded_row_sum, bf);
+    ChainH16Args a;
+    ChainEntryBufs b;
+    RET_IF(chain_entry_begin(a, b, 1, bf, hs, frags, hc, d_att, d_x, M, C, inner, n_qkv, d_out_mask, qb, ch, d_scratch, s));
+    a.bf16 = bf; a.pf_wgs = pf_wgs;
+    HIP_OK(launch_tblock_chain_h16(a, s));
+    return chain_entry_finish(b, 1, bf, M, C, n_qkv, d_x_out, d_qkv_out, s, repeat, h_ms, [&](int) { return launch_tblock_chain_h16(a, s); });
+}
+int mtts_tblock_chain_h16(const float* d_att, const float* d_x, int M, int C, int inner, const float* h_w_out, const float* h_b_out,
+                          const float* h_w1, const float* h_b1, const float* h_p0, const float* h_p1, const float* h_w2,
+                          const float* h_b2, const float* h_w_qkv, const float* h_b_qkv, int n_qkv, const float* d_out_mask, int bf16,
+                          int qb, int ch, int pf_wgs, float* d_x_out, float* d_qkv_out, void* d_scratch, void* stream) {
+    return mtts_tblock_chain_h16_timed(d_att, d_x, M, C, inner, h_w_out, h_b_out, h_w1, h_b1, h_p0, h_p1, h_w2, h_b2, h_w_qkv, h_b_qkv, n_qkv,
+                                       d_out_mask, bf16, qb, ch, pf_wgs, d_x_out, d_qkv_out, d_scratch, stream, 0, nullptr);
+}
+
+}  // extern "C"

@@ -8,8 +8,8 @@
 // Streaming passes (the audio is read twice and written at most once, 16 bytes per lane where the window length allows); a row
 // is spread over the grid, never owned by one workgroup (an utterance can be 1.8 M samples and B can be 1).
 // Every reduction has a fixed shape -- lane-strided partials, xor-shuffle tree, maxima that do not depend on order, window sums
-// in fp64 over exact squares -- so two runs give the same bits.
-#include "kernels.h"
+// in fp64 over exact squares -- so two runs give the same bits.  The C ABI (mtts_waveform_*) is behind the kernels.
+#include "host.h"
 
 namespace mtts {
 
@@ -159,3 +159,42 @@ hipError_t launch_wave_finish(const WaveFinishArgs& a, hipStream_t s) {
 }
 
 }  // namespace mtts
+
+using namespace mtts;
+
+extern "C" {
+
+// ---- waveform finish (waveform.hip)
+static int wave_window(int sample_rate) { return (int)(0.01 * (double)sample_rate); }       // reference inference.py:270
+int64_t mtts_waveform_workspace_bytes(int64_t ld, int B, int sample_rate) {
+    const int win = wave_window(sample_rate);
+    if (ld < 0 || B <= 0 || win <= 0) { set_error("mtts_waveform_workspace_bytes: bad shape"); return -1; }
+    WS ws(nullptr, 0);
+    ws.f((size_t)B * ((ld + WAVE_CHUNK - 1) / WAVE_CHUNK + 1));
+    ws.f((size_t)B * (ld / win + 1));
+    return (int64_t)ws.off + 256;
+}
+int mtts_waveform_finish(float* d_audio, int64_t ld, const int64_t* d_lengths, int hop, int B, int sample_rate, double threshold_db,
+                         float* d_scale, int64_t* d_out_lengths, void* d_ws, int64_t ws_bytes, void* stream) {
+    WaveFinishArgs a;
+    a.win = wave_window(sample_rate);
+    if (!d_audio || !d_lengths || !d_scale || !d_out_lengths || !d_ws || B <= 0 || B > 65535 || ld < 0 || hop < 0 || a.win <= 0) {
+        set_error("mtts_waveform_finish: bad argument");
+        return -1;
+    }
+    if ((ld & 3) || (reinterpret_cast<uintptr_t>(d_audio) & 15)) {
+        set_error("mtts_waveform_finish: rows must be 16-byte aligned (ld a multiple of 4 samples)");
+        return -1;
+    }
+    WS ws(d_ws, (size_t)ws_bytes);
+    a.peaks = ws.f((size_t)B * ((ld + WAVE_CHUNK - 1) / WAVE_CHUNK + 1));
+    a.rms = ws.f((size_t)B * (ld / a.win + 1));
+    if (ws.overflow) { set_error("mtts_waveform_finish: workspace too small"); return -1; }
+    a.audio = d_audio; a.ld = ld; a.lengths = d_lengths; a.hop = hop; a.B = B;
+    a.thr = (float)std::pow(10.0, threshold_db / 20.0);         // reference inference.py:271; torch compares the fp32 RMS in fp32
+    a.scale = d_scale; a.out_lengths = d_out_lengths;
+    HIP_OK(launch_wave_finish(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+}  // extern "C"

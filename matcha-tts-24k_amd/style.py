@@ -12,7 +12,6 @@ import json
 from pathlib import Path
 from typing import Dict, Optional, Tuple
 
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -26,8 +25,9 @@ STYLE_FORMAT_VERSION = 1
 FINE_HOP = 128          # hop of the "fine" mel the style encoder is trained on (reference precompute_mels.py:100-113)
 
 
-class StyleEncoder(nn.Module):
+class StyleEncoder(_hip.DeviceComponent, nn.Module):
     """``forward(mel, mel_mask_or_lengths) -> (e_enc, e_dur)`` -- reference style_encoder.py:60-72."""
+    _abi, _what = "mtts_style", "style encoder"
 
     def __init__(self, n_feats: int = 100, hidden_channels: int = 256, n_layers: int = 4, spk_emb_dim: int = 96):
         super().__init__()
@@ -41,48 +41,17 @@ class StyleEncoder(nn.Module):
         self.proj_dur = nn.Linear(hidden_channels, spk_emb_dim)
         for p in self.parameters():
             p.requires_grad_(False)
-        object.__setattr__(self, "_ctx", None)
-        object.__setattr__(self, "_weights", None)
-        object.__setattr__(self, "_ws", {})
-        object.__setattr__(self, "_dirty", True)
+        self._init_component()
+
+    def _create_args(self):
+        c = self.cfg
+        return c["n_feats"], c["hidden_channels"], c["n_layers"], c["spk_emb_dim"]
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         # a StyleEncoderLightningModule checkpoint prefixes these with "style_encoder." and also carries the frozen Matcha model
         if any(k.startswith("style_encoder.") for k in state_dict):
             state_dict = {k[len("style_encoder."):]: v for k, v in state_dict.items() if k.startswith("style_encoder.")}
-        out = super().load_state_dict(state_dict, strict=strict, assign=assign)
-        object.__setattr__(self, "_dirty", True)
-        return out
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        object.__setattr__(self, "_dirty", True)
-        return r
-
-    def _ready(self):
-        lib = _hip.load()
-        c = self.cfg
-        if self._ctx is None:
-            ctx = lib.mtts_style_create(c["n_feats"], c["hidden_channels"], c["n_layers"], c["spk_emb_dim"])
-            if not ctx:
-                raise RuntimeError("mtts_style_create: " + lib.mtts_last_error().decode())
-            object.__setattr__(self, "_ctx", ctx)
-        if self._dirty:
-            p = next(self.parameters())
-            if not p.is_cuda:
-                raise RuntimeError("matcha-tts-24k_amd: the style encoder must be on a HIP device; there is no CPU path")
-            for k, v in self.state_dict().items():
-                a = np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy())
-                _hip.check(lib.mtts_style_set_tensor(self._ctx, k.encode(), a.ctypes.data, a.size))
-            n = lib.mtts_style_weights_bytes(self._ctx)
-            if n < 0:
-                _hip.check(-1)
-            w = torch.empty(n, dtype=torch.uint8, device=p.device)
-            _hip.check(lib.mtts_style_upload_weights(self._ctx, w.data_ptr(), n))
-            object.__setattr__(self, "_weights", w)
-            self._ws.clear()
-            object.__setattr__(self, "_dirty", False)
-        return lib
+        return super().load_state_dict(state_dict, strict=strict, assign=assign)
 
     @torch.inference_mode()
     def forward(self, mel: torch.Tensor, mel_mask=None, lengths=None, group=None, n_groups: Optional[int] = None
@@ -114,21 +83,10 @@ class StyleEncoder(nn.Module):
         need = lib.mtts_style_workspace_bytes(self._ctx, B, T)
         if need < 0:
             _hip.check(-1)
-        key = _hip.stream_ptr()
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = torch.empty(need, dtype=torch.uint8, device=mel.device)
-            self._ws[key] = ws
+        ws = self._workspace(need, mel.device)
         _hip.check(lib.mtts_style_forward(self._ctx, _hip.ptr(mel), _hip.ptr(lengths), B, T, _hip.ptr(d_group), n_out if d_group is not None else 0,
                                           _hip.ptr(e_enc), _hip.ptr(e_dur), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
         return e_enc, e_dur
-
-    def __del__(self):
-        try:
-            if self._ctx:
-                _hip.load().mtts_style_destroy(self._ctx)
-        except Exception:
-            pass
 
 
 def style_cfg_from_state_dict(sd: Dict[str, torch.Tensor]) -> Dict[str, int]:

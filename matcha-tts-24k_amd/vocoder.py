@@ -10,7 +10,6 @@ from __future__ import annotations
 import os
 from typing import Dict, Optional
 
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -22,8 +21,9 @@ from .synthetic import vocos_spec
 DEFAULT_CFG = dict(n_mels=100, dim=512, inter=1536, layers=8, n_fft=1024, hop=256)
 
 
-class Vocos(ParamTree):
+class Vocos(_hip.DeviceComponent, ParamTree):
     """Parameter holder under the vocos state-dict names + ``decode(mel, lengths=None)``."""
+    _abi, _what = "mtts_vocos", "vocoder"
 
     def __init__(self, **cfg):
         super().__init__()
@@ -31,59 +31,21 @@ class Vocos(ParamTree):
         c = self.cfg
         for key, shape, kind in vocos_spec(n_mels=c["n_mels"], dim=c["dim"], inter=c["inter"], layers=c["layers"], n_fft=c["n_fft"]):
             self.attach(key, shape, kind)
-        object.__setattr__(self, "_ctx", None)
-        object.__setattr__(self, "_weights", None)
-        object.__setattr__(self, "_ws", {})
-        object.__setattr__(self, "_dirty", True)
+        self._init_component()
+
+    def _create_args(self):
+        c = self.cfg
+        return c["n_mels"], c["dim"], c["inter"], c["layers"], c["n_fft"], c["hop"]
+
+    def _tensors(self):
+        tensors = dict(self.state_dict())
+        tensors["aux.window"] = torch.hann_window(self.cfg["n_fft"], dtype=torch.float32)   # as torch.istft's caller passes it
+        return tensors
 
     def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
         # the published checkpoint also carries feature-extractor buffers and the iSTFT window; only the decoder is used
         sd = {k: v for k, v in state_dict.items() if k.startswith(("backbone.", "head.out."))}
-        out = super().load_state_dict(sd, strict=strict, assign=assign)
-        object.__setattr__(self, "_dirty", True)
-        return out
-
-    def _apply(self, fn, *a, **k):
-        r = super()._apply(fn, *a, **k)
-        object.__setattr__(self, "_dirty", True)
-        return r
-
-    def _ready(self):
-        lib = _hip.load()
-        c = self.cfg
-        if self._ctx is None:
-            ctx = lib.mtts_vocos_create(c["n_mels"], c["dim"], c["inter"], c["layers"], c["n_fft"], c["hop"])
-            if not ctx:
-                raise RuntimeError("mtts_vocos_create: " + lib.mtts_last_error().decode())
-            object.__setattr__(self, "_ctx", ctx)
-        if self._dirty:
-            p = next(self.parameters())
-            if not p.is_cuda:
-                raise RuntimeError("matcha-tts-24k_amd: the vocoder must be on a HIP device; there is no CPU path")
-            tensors = dict(self.state_dict())
-            tensors["aux.window"] = torch.hann_window(c["n_fft"], dtype=torch.float32)   # as torch.istft's caller passes it
-            for k, v in tensors.items():
-                a = np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy())
-                _hip.check(lib.mtts_vocos_set_tensor(self._ctx, k.encode(), a.ctypes.data, a.size))
-            n = lib.mtts_vocos_weights_bytes(self._ctx)
-            if n < 0:
-                _hip.check(-1)
-            w = torch.empty(n, dtype=torch.uint8, device=p.device)
-            _hip.check(lib.mtts_vocos_upload_weights(self._ctx, w.data_ptr(), n))
-            object.__setattr__(self, "_weights", w)
-            self._ws.clear()
-            object.__setattr__(self, "_dirty", False)
-        return lib
-
-    def _workspace(self, need: int, device) -> torch.Tensor:
-        key = _hip.stream_ptr()                     # one grow-only scratch buffer per stream (see HipModel._workspace)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = None
-            self._ws.pop(key, None)
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-            self._ws[key] = ws
-        return ws
+        return super().load_state_dict(sd, strict=strict, assign=assign)
 
     @torch.inference_mode()
     def decode(self, mel: torch.Tensor, lengths=None, check: bool = True) -> torch.Tensor:
@@ -120,13 +82,6 @@ class Vocos(ParamTree):
         if check and lib.mtts_vocos_ragged_status(ws.data_ptr(), _hip.stream_ptr()) != 0:
             raise ValueError("mtts: " + lib.mtts_last_error().decode("utf-8", "replace"))
         return audio
-
-    def __del__(self):
-        try:
-            if self._ctx:
-                _hip.load().mtts_vocos_destroy(self._ctx)
-        except Exception:
-            pass
 
 
 class VocosWrapper(nn.Module):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Phase stamps of workgroup 0 of the chain kernel (diagnostic build: tools/build_variant.sh chain_stamp "-DMTTS_CHAIN_STAMP"
-tblock_chain.hip model.hip; run with MTTS_HIP_LIB=$PWD/tools/ab/chain_stamp.so)."""
+tblock_chain.hip unit_entries.hip; run with MTTS_HIP_LIB=$PWD/tools/ab/chain_stamp.so)."""
 import importlib, sys
 from pathlib import Path
 import torch

@@ -26,7 +26,7 @@ def build(extra=(), name="kstamp", nostamp=False):
     if nostamp:                                                # an A/B library without the stamps (bench.py under MTTS_HIP_LIB)
         cmd.remove("-DMTTS_KSTAMP")
     subprocess.run(cmd, check=True)
-    others = [str(pk / "build" / f"{n}.o") for n in ("gemm_f32", "attention_f32", "norm_glue", "vocos", "model")]
+    others = [str(o) for o in sorted((pk / "build").glob("*.o")) if o.stem != "gemm_p16"]          # every other unit as build() left it
     out = ROOT / "tools" / "ab" / f"{name}.so"
     out.parent.mkdir(exist_ok=True)
     subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", obj, *others, "-o", str(out)], check=True)
