@@ -13,8 +13,14 @@ LOCAL_RANK / WORLD_SIZE in the environment), or plainly as `python bench.py --gp
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` as a CHILD process before it has
 touched the GPU (never an exec after device init), relays the child's output and exits with its return code.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--no-events] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-events]]
 prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed steps, the dump if asked for, the
+result line (`roofline` and `cpu_baseline` are null in it).  --full adds, after the timed steps and the dump, everything else
+the benchmark measures: the per-kernel HIP-event pass (`roofline`; skipped by --no-events), with a reduced-precision
+--arithmetic its mel error against the fp32-equivalent path (`precision`), and the CPU oracle timed on the host cores
+(`cpu_baseline`, most of a minute; skipped by --no-cpu-baseline).  The headline keys are the same in both kinds of run.
 
 --dump-outputs DIR: after the K timed steps rank 0 writes what the LAST timed step returned to DIR/<name>.npy (`dump_outputs`):
 `mel` and `mel_lengths` of synthesise() (N>1: `mel` is the all-gathered batch, `mel_lengths` this rank's shard = its first
@@ -186,15 +192,18 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-events", action="store_true", help="skip the per-kernel HIP-event pass (roofline = null)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel HIP-event pass (roofline), the precision comparison of a "
+                         "reduced-precision --arithmetic and the CPU baseline; off by default: a plain run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (cpu_baseline = null)")
+    ap.add_argument("--no-events", action="store_true", help="with --full: skip the per-kernel HIP-event pass (roofline = null)")
     ap.add_argument("--batch", type=int, default=BATCH, help="per-GPU batch (default 32 = BASELINE configs[1]; other values are labelled)")
     ap.add_argument("--with-vocoder", action="store_true",
                     help="NON-DEFAULT: append the Vocos-24k head (random-init weights) to every step: mel -> waveform (configs[3] style)")
     ap.add_argument("--arithmetic", default=None, choices=["f32", "f16-storage", "bf16-storage"],
                     help="f32 (default): fp32-equivalent split arithmetic = configs[1]; f16-storage / bf16-storage: BASELINE configs[2]'s "
                          "16-bit storage mode with fp16 / bfloat16 planes (per-rank shape of the 8-way job: 32 utterances per GPU), labelled "
-                         "with its measured mel error")
+                         "with its measured mel error under --full")
     ap.add_argument("--solver", default=SOLVER)
     ap.add_argument("--n-timesteps", type=int, default=N_STEPS_ODE)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -302,7 +311,7 @@ def main():
 
     terms = model.hip.gemm_terms()
     roofline = None
-    if rank == 0 and not args.no_events:
+    if rank == 0 and args.full and not args.no_events:
         # same steps again with a HIP event pair around every kernel launch, recorded on the launch stream
         hip = model.hip
         hip.prof_enable(True)
@@ -348,7 +357,7 @@ def main():
         }
 
     precision = None
-    if rank == 0 and terms in (1, 16, 17):
+    if rank == 0 and args.full and terms in (1, 16, 17):
         # reduced-precision arithmetic: its mel error against this library's fp32-equivalent path (itself 4e-5 from the
         # reference goldens, tests/test_hip_path.py) on the first utterances of the batch, same ids and the same noise
         nb = min(4, BATCH)
@@ -367,7 +376,7 @@ def main():
         del ref_model
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(hp, sd, synthetic)
 
     if rank == 0:

@@ -39,6 +39,12 @@ def test_child_failure_is_relayed():
     assert res.returncode != 0
 
 
+def test_full_is_accepted_alone_and_with_its_skip_options():
+    for extra in (["--full"], ["--full", "--no-cpu-baseline", "--no-events"]):
+        res = _run(["--gpus", "1", "--steps", "1", "--warmup", "0", *extra])
+        assert res.returncode == 0, res.stderr[-2000:]
+
+
 def _bench_module():
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench", ROOT / "bench.py")
@@ -96,3 +102,27 @@ def test_dump_outputs_of_the_timed_path_repeat(tmp_path):
     assert a["mel_lengths"].dtype == np.float64 and a["mel_lengths"].max() == a["mel"].shape[-1]
     assert np.isfinite(a["mel"]).all() and a["mel"].std() > 0
     assert np.array_equal(a["mel"], b["mel"]) and np.array_equal(a["mel_lengths"], b["mel_lengths"])
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_the_headline_only_and_full_adds_the_rest(tmp_path):
+    """A plain run leaves `roofline` and `cpu_baseline` null (no pass of the model beyond warm-up and the timed steps); --full
+    fills `roofline` from the per-kernel event pass, after the dump: same headline keys and the same arrays as the plain run."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MTTS_BENCH_DRYRUN")}
+    lines, outs = {}, {}
+    for kind, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        res = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
+                              "--dump-outputs", str(tmp_path / kind), *extra], env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines[kind] = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+        outs[kind] = {f.stem: np.load(f) for f in (tmp_path / kind).iterdir()}
+    plain, full = lines["plain"], lines["full"]
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None and "precision" not in plain
+    assert full["roofline"]["launches_per_step"] > 0 and full["roofline"]["gemm_ms_per_step"] > 0 and full["cpu_baseline"] is None
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert plain[k] == full[k]
+    for line in (plain, full):
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 2 and line["warmup"] == 1
+    assert sorted(outs["plain"]) == sorted(outs["full"]) == ["mel", "mel_lengths"]
+    assert all(np.array_equal(outs["plain"][n], outs["full"][n]) for n in outs["plain"])

@@ -3,7 +3,7 @@
 sets=$1; shift
 for i in 1 2; do
   for kv in $sets; do
-    env $kv python bench.py --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    env $kv python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$kv', 'ms/step', d['ms_per_step'], 'gemm ms', r['gemm_ms_per_step'], 'attn', r['attention']['ms_per_step'], 'elem', r['elementwise_ms_per_step'])"
