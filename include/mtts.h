@@ -186,6 +186,29 @@ int mtts_cfm_solve_folded(mtts_ctx* ctx, const float* d_x0, const float* d_mu, c
                           const float* h_t_span, int n_steps, int solver, int B, int T, int T_fold, float* d_out, int T_out,
                           float out_scale, float out_shift, void* d_ws, int64_t ws_bytes, void* stream);
 
+/* ONE step of that solve for B utterances that sit at DIFFERENT points of their own grids -- the iteration a serving scheduler
+ * batches at (batcher.StepBatcher): requests join and leave between two calls.  BASECFM.solve (reference flow_matching.py:60-63)
+ * hands the whole grid to torchdiffeq, whose fixed-grid loop is `for t0, t1 in zip(grid[:-1], grid[1:]): dt = t1 - t0;
+ * y = y + step(f, t0, dt, t1, y)`; this entry is one pass of that loop body with (t0, t1) per utterance: the time embedding is made
+ * for stages * B times, every ResNet block adds its utterance's own bias row, and the update takes its utterance's own dt.
+ *   State: pools d_z_pool, d_mu_pool [S, n_feats, T_cap] (fp32, channels first, like mtts_cfm_solve's d_x0 / d_mu; with
+ *   use_mu_prior the caller stores z = mu + noise).  Utterance b of the step lives in slot d_slots[b] (device int32 [B], distinct,
+ *   in [0, S)); frames [0, T_fold) of its z are replaced by the state after the step, everything else in the pools is left as
+ *   it is.  h_slots is the host's copy of the same B indices: it is what this call validates (the device copy is not read back;
+ *   kernels skip a slot outside [0, S) should the two disagree).
+ *   d_t0, d_t1 (device fp32 [B]): the grid interval of utterance b.  dt = t1 - t0 in fp32, stage times t0 (euler); t0,
+ *   t0 + 0.5f * dt (midpoint); t0, t0 + dt * (1/3), t0 + dt * (2/3), t1 (rk4, 3/8 rule) -- torchdiffeq's arithmetic, as
+ *   mtts_cfm_solve computes it on the host, so n calls over t_span[i], t_span[i + 1] reproduce the one-call solve.
+ *   d_y_lengths (device int64 [B]), y_max, T_fold: folded padding of THIS step's batch as for mtts_cfm_solve_folded, with T_cap in
+ *   the place of T: mtts_fold_rows(ctx, y_max, 1) <= T_fold <= T_cap, T_fold a multiple of 2^(levels-1).  mtts_set_frame_limits
+ *   composes (d_t_len[b] = the reference's padded length of utterance b, in this step's order); without it that length is T_cap.
+ *   Workspace: mtts_decoder_workspace_bytes(ctx, B, T_fold).  Range guard, pair time-out word and mtts_prof_* as for any
+ *   estimator call.  Returns -1 (mtts_last_error) without touching the pools for: a slot out of range or named twice, B > S,
+ *   y_max > T_cap, a T_fold that breaks the rules above, an unknown solver. */
+int mtts_cfm_step(mtts_ctx* ctx, float* d_z_pool, const float* d_mu_pool, int S, int T_cap, const int32_t* d_slots,
+                  const int32_t* h_slots, const float* d_t0, const float* d_t1, const int64_t* d_y_lengths, int y_max, int solver,
+                  int B, int T_fold, void* d_ws, int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- single kernels (parity tests, building blocks) */
 
 /* C[M,N] = epilogue(prologue(A)[M,K] * W[N,K]^T): the fp32-MFMA GEMM every Linear/Conv1d of the path runs on.
@@ -231,6 +254,12 @@ int64_t mtts_conv_gn_scratch_bytes(int B, int T, int C, int N);
 int mtts_conv_gn(const float* d_x, int B, int T, int C, int c1, const float* d_w, void* d_wpacked, const float* d_bias, int N,
                  const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias, const int* d_nrows,
                  const int* d_nextra, const float* d_bias_stats, float eps, float* d_out, void* d_scratch, void* stream);
+/* ... with one time-embedding bias row per utterance (mtts_cfm_step): d_chbias [B][chbias_stride], chbias_stride >= N, % 4 == 0;
+ * utterance b adds the first N values of its row.  mtts_conv_gn is this kernel with one row for the batch (stride 0). */
+int mtts_conv_gn_rows(const float* d_x, int B, int T, int C, int c1, const float* d_w, void* d_wpacked, const float* d_bias, int N,
+                      const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias, int chbias_stride,
+                      const int* d_nrows, const int* d_nextra, const float* d_bias_stats, float eps, float* d_out, void* d_scratch,
+                      void* stream);
 
 /* Self-attention over packed [B*T, 3*H*D] q|k|v rows -> [B*T, H*D].  mask_mode 0: additive float key bias
  * (diffusers semantics, reference transformer.py:253-258); 1: boolean query*key mask (reference
@@ -329,6 +358,10 @@ int mtts_channel_layernorm(const float* d_x, int B, int T, int C, const float* d
 int64_t mtts_groupnorm_scratch_bytes(int B, int T, int G);
 int mtts_groupnorm_mish(const float* d_y, const float* d_gamma, const float* d_beta, const float* d_mask, int B, int T,
                         int C, int G, float eps, float* d_out, void* d_scratch, void* stream);
+/* ... followed by the ResNet block's time-embedding bias -- reference decoder.py:60: (h + mlp(t)) * mask -- with one bias row per
+ * utterance: d_chbias [B][chbias_stride] (chbias_stride >= C, % 4 == 0), or one row [C] for the batch with chbias_stride = 0. */
+int mtts_groupnorm_mish_rows(const float* d_y, const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias,
+                             int chbias_stride, int B, int T, int C, int G, float eps, float* d_out, void* d_scratch, void* stream);
 
 /* ---------------------------------------------------------------- Vocos-24k head */
 

@@ -145,11 +145,13 @@ def load() -> C.CDLL:
         "mtts_cfm_solve": (i32, [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, i32, f32, f32, vp, i64, vp]),
         "mtts_fold_rows": (i32, [vp, i32, i32]),
         "mtts_cfm_solve_folded": (i32, [vp, vp, vp, vp, i32, i32, vp, i32, i32, i32, i32, i32, vp, i32, f32, f32, vp, i64, vp]),
+        "mtts_cfm_step": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, i64, vp]),
         "mtts_gemm_packed_bytes": (i64, [i32, i32, i32]),
         "mtts_attention_p16": (i32, [vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp]),
         "mtts_gemm_p16_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
         "mtts_conv_gn_scratch_bytes": (i64, [i32, i32, i32, i32]),
         "mtts_conv_gn": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
+        "mtts_conv_gn_rows": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, f32, vp, vp, vp]),
         "mtts_gemm_p16": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp,
                                 i32, vp, f32, vp, i32, vp, f32, vp, i32, vp, vp]),
         "mtts_gemm_f32": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp,
@@ -176,6 +178,7 @@ def load() -> C.CDLL:
         "mtts_channel_layernorm": (i32, [vp, i32, i32, i32, vp, vp, f32, i32, vp, vp, vp, vp]),
         "mtts_groupnorm_scratch_bytes": (i64, [i32, i32, i32]),
         "mtts_groupnorm_mish": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]),
+        "mtts_groupnorm_mish_rows": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp]),
         "mtts_vocos_create": (vp, [i32, i32, i32, i32, i32, i32]),
         "mtts_vocos_destroy": (None, [vp]),
         "mtts_vocos_set_tensor": (i32, [vp, C.c_char_p, vp, i64]),
@@ -475,6 +478,12 @@ class HipModel:
             return torch.zeros(1, dtype=torch.int32, device=self.device)
         return self._last_ws[("dec", sp)][4:8].view(torch.int32)
 
+    def call_flags(self, kind: str) -> Optional[torch.Tensor]:
+        """The first two header words (range flag, pair time-out) of this stream's latest ``kind`` ("enc" / "dec") workspace as a device
+        int32 view, or None when no such call ran: what a caller accumulates over several calls without reading any of them."""
+        ws = self._last_ws.get((kind, stream_ptr()))
+        return None if ws is None else ws[:8].view(torch.int32)
+
     def weights_saturate(self) -> bool:
         r = self.lib.mtts_weights_saturate(self.ctx)
         if r < 0:
@@ -693,6 +702,43 @@ class HipModel:
                                       ws.data_ptr(), ws.numel(), stream_ptr()))
         return out
 
+    def cfm_step(self, z_pool, mu_pool, slots, t0, t1, y_lengths, y_max: int, t_fold: int, solver: str, slots_dev=None,
+                 ws: Optional[torch.Tensor] = None) -> None:
+        """One solver step of the utterances in ``slots`` (a host sequence of distinct slot indices), each over its own grid
+        interval, in place on ``z_pool`` (mtts_cfm_step).  ``z_pool`` / ``mu_pool``: fp32 [S, n_feats, T_cap] on the device.
+        ``t0`` / ``t1``: fp32 [B] and ``y_lengths``: int64 [B] on the device, in the order of ``slots``; host sequences are copied
+        over.  ``slots_dev``: the int32 [B] device copy of ``slots`` when the caller already has one.  Frame limits
+        (``set_frame_limits``) compose as for ``cfm_solve``."""
+        if solver not in SOLVERS:
+            raise ValueError(f"unsupported solver {solver!r} (euler, midpoint, rk4)")
+        for name, pool in (("z_pool", z_pool), ("mu_pool", mu_pool)):
+            if pool.dtype != torch.float32 or pool.dim() != 3 or not pool.is_cuda or not pool.is_contiguous():
+                raise RuntimeError(f"mtts: {name} must be a contiguous fp32 [S, n_feats, T_cap] tensor on the HIP device")
+        if z_pool.shape != mu_pool.shape or z_pool.shape[1] != self.hp.n_feats:
+            raise RuntimeError("mtts: z_pool and mu_pool must both be [S, n_feats, T_cap]")
+        S, _, T_cap = z_pool.shape
+        h_slots = np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+        B = int(h_slots.shape[0])
+        dev = z_pool.device
+        if slots_dev is None:
+            slots_dev = torch.from_numpy(h_slots).to(dev)
+
+        def on_device(v, dtype):
+            v = v if torch.is_tensor(v) else torch.as_tensor(np.asarray(v), dtype=dtype)
+            v = v.detach().to(device=dev, dtype=dtype).contiguous()
+            if v.numel() != B:
+                raise ValueError(f"mtts: a step of {B} slots needs {B} values per argument, got {v.numel()}")
+            return v
+        t0, t1, y_lengths = on_device(t0, torch.float32), on_device(t1, torch.float32), on_device(y_lengths, torch.int64)
+        if slots_dev.dtype != torch.int32 or slots_dev.numel() != B:
+            raise RuntimeError("mtts: slots_dev must be an int32 tensor with one entry per slot")
+        if ws is None:
+            ws = self._workspace("dec", B, int(t_fold))
+        else:
+            self._last_ws[("dec", stream_ptr())] = ws
+        check(self.lib.mtts_cfm_step(self.ctx, ptr(z_pool), ptr(mu_pool), S, T_cap, ptr(slots_dev), h_slots.ctypes.data, ptr(t0), ptr(t1),
+                                     ptr(y_lengths), int(y_max), SOLVERS[solver], B, int(t_fold), ws.data_ptr(), ws.numel(), stream_ptr()))
+
     # ------------------------------------------------------------------ measurement
     def gemm_terms(self) -> int:
         return self.lib.mtts_gemm_terms(self.ctx)
@@ -872,6 +918,30 @@ def channel_layernorm(x, gamma, beta, B, T, *, act=0, film=None, mask=None, eps=
     check(lib.mtts_channel_layernorm(ptr(x), B, T, x.shape[1], ptr(gamma), ptr(beta), float(eps), act, ptr(film), ptr(mask), ptr(y),
                                      stream_ptr()))
     return y
+
+
+def conv_gn_rows(x, w, bias, gamma, beta, mask, chbias, *, B, T, c1=0, nrows=None, nextra=None, bias_stats=None, eps=1e-5):
+    """``conv_gn`` with one time-embedding bias row per utterance: chbias [B, stride >= N] (mtts_conv_gn_rows)."""
+    lib = load()
+    N, Cc = w.shape[0], w.shape[1]
+    packed = torch.empty(lib.mtts_gemm_packed_bytes(N, Cc, 3), dtype=torch.uint8, device=x.device)
+    scratch = torch.empty(lib.mtts_conv_gn_scratch_bytes(B, T, Cc, N), dtype=torch.uint8, device=x.device)
+    out = torch.empty(B * T, N, dtype=torch.float32, device=x.device)
+    check(lib.mtts_conv_gn_rows(ptr(x), B, T, Cc, c1, ptr(w.contiguous()), packed.data_ptr(), ptr(bias), N, ptr(gamma), ptr(beta), ptr(mask),
+                                ptr(chbias), chbias.shape[1], ptr(nrows), ptr(nextra), ptr(bias_stats), float(eps), ptr(out),
+                                scratch.data_ptr(), stream_ptr()))
+    return out
+
+
+def groupnorm_mish_rows(y, gamma, beta, mask, chbias, B, T, G=8, eps=1e-5):
+    """``groupnorm_mish`` + the time-embedding bias: chbias [B, stride >= C] (one row per utterance) or [C] (one for the batch)."""
+    lib = load()
+    Cc = y.shape[1]
+    scratch = torch.empty(lib.mtts_groupnorm_scratch_bytes(B, T, G), dtype=torch.uint8, device=y.device)
+    out = torch.empty_like(y)
+    check(lib.mtts_groupnorm_mish_rows(ptr(y), ptr(gamma), ptr(beta), ptr(mask), ptr(chbias), chbias.shape[1] if chbias.dim() == 2 else 0,
+                                       B, T, Cc, G, eps, ptr(out), scratch.data_ptr(), stream_ptr()))
+    return out
 
 
 def groupnorm_mish(y, gamma, beta, mask, B, T, G=8, eps=1e-5):

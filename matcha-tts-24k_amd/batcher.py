@@ -15,6 +15,9 @@ of the batch equals the batch-of-one result (to rounding: tile shapes, hence sum
   * one worker thread drives the model (the HIP context is not re-entrant: model.decoder.solver is per-call state).
 
 The class is transport-agnostic: an HTTP handler submits and awaits the future (``submit(...).result()``), see INTEGRATION.md.
+
+``StepBatcher`` (below, opt-in) has the same contract and schedules at the solver step instead of the request: requests join a
+running ODE solve at the next step and leave after their last one (include/mtts.h mtts_cfm_step).
 """
 from __future__ import annotations
 
@@ -161,28 +164,379 @@ class FrameBudgetBatcher:
             self.batches_run += 1
 
     def _run_on_model(self, batch: List[Request]) -> List[Dict[str, Any]]:
-        dev = next(iter(self.model.state_dict().values())).device       # where load_matcha / .to() put the model
-        B, n_max = len(batch), max(len(r.ids) for r in batch)
-        x = torch.zeros(B, n_max, dtype=torch.long)
-        for b, r in enumerate(batch):
-            x[b, :len(r.ids)] = torch.as_tensor(r.ids, dtype=torch.long)
-        x_len = torch.tensor([len(r.ids) for r in batch], dtype=torch.long)
-        head = batch[0]
-        self.model.decoder.solver = head.solver
-        emb = self.model.speaker_rows([tuple(r.speaker_embedding) if r.speaker_embedding is not None else
-                                       list(r.voice_mix) if r.voice_mix is not None else r.speaker for r in batch])
-        out = self.model.synthesise(x.to(dev), x_len.to(dev), head.n_timesteps, speaker_embeddings=emb,
-                                    scale_correction=[r.scale_correction for r in batch],
-                                    length_scale=[r.length_scale for r in batch], per_request_padding=True,
-                                    durations=duration_rows(batch))
-        lens = out["mel_lengths"].tolist()
-        res = [{"mel": out["mel"][b, :, :int(lens[b])], "mel_length": int(lens[b])} for b in range(B)]
-        if self.vocoder is not None and self.wave_batch:
-            from .inference import to_waveforms
-            for r, a in zip(res, to_waveforms(out["mel"], out["mel_lengths"], self.vocoder)):
-                r["audio"] = a
-        elif self.vocoder is not None:
-            from .inference import _waveform_on_device, trim_trailing_silence
-            for r in res:
-                r["audio"] = trim_trailing_silence(_waveform_on_device(r["mel"][None], self.vocoder).squeeze()).cpu()
-        return res
+        return synthesise_batch(self.model, batch, self.vocoder, self.wave_batch)
+
+
+def request_inputs(model, batch: List[Request]):
+    """Padded ids, lengths and speaker rows of a batch of requests on the model's device."""
+    dev = next(iter(model.state_dict().values())).device       # where load_matcha / .to() put the model
+    B, n_max = len(batch), max(len(r.ids) for r in batch)
+    x = torch.zeros(B, n_max, dtype=torch.long)
+    for b, r in enumerate(batch):
+        x[b, :len(r.ids)] = torch.as_tensor(r.ids, dtype=torch.long)
+    x_len = torch.tensor([len(r.ids) for r in batch], dtype=torch.long)
+    emb = model.speaker_rows([tuple(r.speaker_embedding) if r.speaker_embedding is not None else
+                              list(r.voice_mix) if r.voice_mix is not None else r.speaker for r in batch])
+    return x.to(dev), x_len.to(dev), emb
+
+
+def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_batch: bool) -> None:
+    """``res[b]["audio"]`` for a batch of finished mels (``mel`` [B, n_feats, T], ``mel_lengths`` [B]; ``res[b]["mel"]`` the exact-length rows)."""
+    if vocoder is not None and wave_batch:
+        from .inference import to_waveforms
+        for r, a in zip(res, to_waveforms(mel, mel_lengths, vocoder)):
+            r["audio"] = a
+    elif vocoder is not None:
+        from .inference import _waveform_on_device, trim_trailing_silence
+        for r in res:
+            r["audio"] = trim_trailing_silence(_waveform_on_device(r["mel"][None], vocoder).squeeze()).cpu()
+
+
+def synthesise_batch(model, batch: List[Request], vocoder=None, wave_batch: bool = True) -> List[Dict[str, Any]]:
+    """One ``synthesise(per_request_padding=True)`` call for requests of one group, and their waveforms."""
+    B = len(batch)
+    x, x_len, emb = request_inputs(model, batch)
+    head = batch[0]
+    model.decoder.solver = head.solver
+    out = model.synthesise(x, x_len, head.n_timesteps, speaker_embeddings=emb,
+                           scale_correction=[r.scale_correction for r in batch],
+                           length_scale=[r.length_scale for r in batch], per_request_padding=True,
+                           durations=duration_rows(batch))
+    lens = out["mel_lengths"].tolist()
+    res = [{"mel": out["mel"][b, :, :int(lens[b])], "mel_length": int(lens[b])} for b in range(B)]
+    waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch)
+    return res
+
+
+# ====================================================================================================== step-level batching
+# FrameBudgetBatcher schedules at the request: a batch is formed, its WHOLE solve runs, then the queue is looked at again -- a
+# request that arrives just after a solve started waits for it, then runs nearly alone itself.  StepBatcher schedules at the
+# solver step (the iteration of this model, 1-4 estimator evaluations): every iteration it admits who is waiting into free slots,
+# advances everybody who is active by ONE step -- each request at its own point (t0, t1) of its own grid, include/mtts.h
+# mtts_cfm_step -- and lets those leave that made their last step.  What a request gets back is unchanged: per-request padding
+# makes a row of a ragged batch equal its batch-of-one result (to rounding), and with one time per utterance that holds for
+# rows at different times too, so requests with different n_timesteps share launches (only the solver must be common).
+
+def step_grid(n_timesteps: int) -> List[Tuple[float, float]]:
+    """The ``(t0, t1)`` of a request's steps: neighbours of ``t_span = linspace(0, 1, n + 1)`` in fp32 as ``CFM.forward`` builds it
+    (the values are exact fp32 numbers; ``dt = t1 - t0`` is taken in fp32 on the device, torchdiffeq's fixed-grid loop).  Pure."""
+    if int(n_timesteps) < 1:
+        raise ValueError("n_timesteps must be at least 1")
+    t = torch.linspace(0, 1, int(n_timesteps) + 1, dtype=torch.float32).tolist()
+    return list(zip(t[:-1], t[1:]))
+
+
+class SlotBook:
+    """Which slots of the pool are free; lowest index first, so a small pool region stays warm.  Pure bookkeeping."""
+
+    def __init__(self, n_slots: int):
+        self.n_slots = int(n_slots)
+        self._free = list(range(self.n_slots))
+        self._held: set = set()
+
+    @property
+    def n_free(self) -> int:
+        return len(self._free)
+
+    def take(self) -> int:
+        if not self._free:
+            raise RuntimeError("no free slot")
+        s = min(self._free)
+        self._free.remove(s)
+        self._held.add(s)
+        return s
+
+    def release(self, slot: int) -> None:
+        if slot not in self._held:
+            raise RuntimeError(f"slot {slot} is not held")
+        self._held.remove(slot)
+        self._free.append(slot)
+
+
+def plan_admission(waiting: List[Request], n_active: int, active_longest: int, n_free_slots: int, max_batch: int, max_tokens: int) -> List[int]:
+    """Indices (into ``waiting``, arrival order) of the requests that join at this iteration: oldest first, while a slot is free, the
+    active set stays within ``max_batch`` requests and within the ``max_tokens`` budget of padded tokens (requests x longest, as
+    ``plan_batch``).  A request that does not fit the budget is skipped, not waited for, unless nothing is active (the head then
+    always goes, alone if need be).  Pure function."""
+    chosen: List[int] = []
+    n, longest = int(n_active), int(active_longest)
+    for i, r in enumerate(waiting):
+        if len(chosen) >= n_free_slots or n >= max_batch:
+            break
+        cand = max(longest, len(r.ids))
+        if n > 0 and cand * (n + 1) > max_tokens:
+            continue
+        chosen.append(i)
+        n, longest = n + 1, cand
+    return chosen
+
+
+def next_solver(active_solvers: Sequence[str], last: Optional[str]) -> Optional[str]:
+    """Round-robin over the solvers that have active requests: the one after ``last`` in sorted order.  Pure function."""
+    names = sorted(set(active_solvers))
+    if not names:
+        return None
+    later = [s for s in names if last is not None and s > last]
+    return later[0] if later else names[0]
+
+
+@dataclass
+class StepEntry:
+    """One active request: where its state lives and where it is on its grid."""
+    request: Request
+    slot: int
+    grid: List[Tuple[float, float]]
+    i: int = 0                       # steps done
+    y_len: int = 0                   # valid mel frames
+    t_len: int = 0                   # its own padded length (per-request padding)
+
+    @property
+    def t0(self) -> float:
+        return self.grid[self.i][0]
+
+    @property
+    def t1(self) -> float:
+        return self.grid[self.i][1]
+
+    @property
+    def done(self) -> bool:
+        return self.i >= len(self.grid)
+
+
+class StepBatcher:
+    """Same contract as ``FrameBudgetBatcher`` -- ``submit(ids, **kw) -> Future`` of ``{"mel", "mel_length"[, "audio"]}`` -- scheduled
+    at the solver step.  One worker thread drives the model.  Per iteration: admit (text encoder, durations and ``align_pool`` of the
+    newcomers as one small ragged batch, then into free slots), one step for all active requests of one solver (round-robin over
+    solvers), and the requests that made their last step leave (mel read out, the finishers' waveforms as one ``to_waveforms``
+    batch).  A request whose folded rows exceed ``slot_frames`` runs through ``synthesise`` as a batch of its own.
+
+    ``run_step(solver, entries)`` replaces the device step (tests); admission and read-out then touch no device either."""
+
+    def __init__(self, model, max_batch: int = 32, max_tokens: int = 16384, n_slots: Optional[int] = None, slot_frames: int = 2048,
+                 run_step: Optional[Callable[[str, List[StepEntry]], None]] = None, vocoder=None):
+        self.model = model
+        self.vocoder = vocoder
+        self.wave_batch = os.environ.get("MTTS_WAVE_BATCH", "1") != "0"
+        self.max_batch = int(max_batch)
+        self.max_tokens = int(max_tokens)
+        self.slot_frames = int(slot_frames)
+        self.slots = SlotBook(int(n_slots) if n_slots is not None else self.max_batch)
+        self._fake = run_step is not None
+        self._run_step = run_step or self._step_on_model
+        self._pool = None
+        self._flags = None                  # device int32 [3]: encoder range flag, estimator range flag, pair time-out, OR-ed over calls
+        self._waiting: List[Request] = []
+        self._active: List[StepEntry] = []
+        self._last_solver: Optional[str] = None
+        self._cv = threading.Condition()
+        self._stop = False
+        self.batches_run = 0                # iterations that ran a step
+        self.utterance_steps = 0            # requests x steps served: utterance_steps / batches_run = mean utterances per step
+        self.whole_solves = 0               # requests that did not fit a slot
+        self.busy_s = 0.0
+        self.phase_s = {"admit": 0.0, "step": 0.0, "leave": 0.0}     # where busy_s went (host wall time; "leave" holds the iteration's wait)
+        self._thread = threading.Thread(target=self._loop, name="mtts-step-batcher", daemon=True)
+        self._thread.start()
+
+    # ------------------------------------------------------------------ producer side
+    def submit(self, ids: Sequence[int], **kw) -> Future:
+        if len(ids) == 0:
+            raise ValueError("empty utterance")
+        if len(ids) > self.max_tokens:
+            raise ValueError(f"utterance of {len(ids)} tokens exceeds the batch budget of {self.max_tokens}")
+        r = Request(ids=list(ids), **kw)
+        duration_rows([r])
+        step_grid(r.n_timesteps)
+        with self._cv:
+            if self._stop:
+                raise RuntimeError("batcher is closed")
+            self._waiting.append(r)
+            self._cv.notify()
+        return r.future
+
+    def close(self) -> None:
+        """Stop taking requests; everything submitted before is served."""
+        with self._cv:
+            self._stop = True
+            self._cv.notify()
+        self._thread.join()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # ------------------------------------------------------------------ worker
+    def _loop(self) -> None:
+        with torch.inference_mode():        # (thread-local: everything the worker touches on the device is inference state)
+            self._serve()
+
+    def _serve(self) -> None:
+        while True:
+            with self._cv:
+                while not self._waiting and not self._active and not self._stop:
+                    self._cv.wait()
+                if self._stop and not self._waiting and not self._active:
+                    return
+                longest = max((len(e.request.ids) for e in self._active), default=0)
+                take = plan_admission(self._waiting, len(self._active), longest, self.slots.n_free, self.max_batch, self.max_tokens)
+                newcomers = [self._waiting[i] for i in take]
+                for i in reversed(take):
+                    del self._waiting[i]
+            t_run = time.monotonic()
+            if newcomers:
+                try:
+                    self._active.extend(self._admit(newcomers))
+                except BaseException as e:  # noqa: BLE001 - the newcomers' waiters must be released; who is mid-solve goes on
+                    self._fail(newcomers, e)
+            t_admitted = time.monotonic()
+            self.phase_s["admit"] += t_admitted - t_run
+            solver = next_solver([e.request.solver for e in self._active], self._last_solver)
+            if solver is not None:
+                entries = [e for e in self._active if e.request.solver == solver]
+                try:
+                    self._run_step(solver, entries)
+                    t_stepped = time.monotonic()
+                    self.phase_s["step"] += t_stepped - t_admitted
+                    for e in entries:
+                        e.i += 1
+                    self.batches_run += 1
+                    self.utterance_steps += len(entries)
+                    self._last_solver = solver
+                    finished = [e for e in entries if e.done]
+                    if finished:
+                        self._finish(finished)
+                        self.phase_s["leave"] += time.monotonic() - t_stepped
+                except BaseException as e:  # noqa: BLE001 - every waiter must be released: the pool's state is void
+                    self._abort(e)
+            self.busy_s += time.monotonic() - t_run
+
+    @staticmethod
+    def _fail(requests: List[Request], exc: BaseException) -> None:
+        for r in requests:
+            if not r.future.done():
+                r.future.set_exception(exc)
+
+    def _abort(self, exc: BaseException) -> None:
+        """Fail every active request and free its slot."""
+        self._fail([e.request for e in self._active], exc)
+        for e in self._active:
+            self.slots.release(e.slot)
+        self._active = []
+
+    def _leave(self, entries: List[StepEntry]) -> None:
+        gone = {id(e) for e in entries}
+        self._active = [e for e in self._active if id(e) not in gone]
+        for e in entries:
+            self.slots.release(e.slot)
+
+    # ------------------------------------------------------------------ admission
+    def _admit(self, newcomers: List[Request]) -> List[StepEntry]:
+        if self._fake:
+            return [StepEntry(r, self.slots.take(), step_grid(r.n_timesteps), y_len=len(r.ids), t_len=2 * len(r.ids)) for r in newcomers]
+        return self._admit_on_model(newcomers)
+
+    def _admit_on_model(self, newcomers: List[Request]) -> List[StepEntry]:
+        from .inference import fix_len_compatibility
+        model = self.model
+        hip = model._rt.ready()
+        x, x_len, (e_enc, e_dur) = request_inputs(model, newcomers)
+        mu_x, logw, x_mask = model.encoder(x, x_len, e_enc, e_dur)
+        sc, ls = [r.scale_correction for r in newcomers], [r.length_scale for r in newcomers]
+        given = duration_rows(newcomers)
+        if given is None:
+            _, cum, y_fine = hip.durations(logw, x_mask, sc, ls)
+        else:
+            _, cum, y_fine = model._given_durations(hip, given, logw, x_mask, sc, ls)
+        self._note_flags(hip, "enc")
+        fine = [int(v) for v in y_fine.tolist()]                 # the one host read of an admission (as synthesise)
+        t_pad = fix_len_compatibility(max(fine))
+        mu_y, _, _ = hip.align_pool(mu_x, cum, y_fine, t_pad)
+        if self._pool is None:
+            self._pool = model.decoder.step_pool(self.slots.n_slots, self.slot_frames, mu_y.device)
+        entries, oversize = [], []
+        for b, r in enumerate(newcomers):
+            y_len = max((fine[b] + 1) // 2, 1)                   # (align_pool's y_lengths)
+            if model.decoder.step_rows(y_len) > self.slot_frames:
+                oversize.append(r)
+                continue
+            e = StepEntry(r, self.slots.take(), step_grid(r.n_timesteps), y_len=y_len, t_len=fix_len_compatibility(max(fine[b], 1)))
+            model.decoder.step_prepare(self._pool, e.slot, mu_y[b], e.t_len)
+            entries.append(e)
+        for r in oversize:                                       # longer than a slot: the whole-solve path, a batch of its own
+            try:
+                r.future.set_result(synthesise_batch(model, [r], self.vocoder, self.wave_batch)[0])
+            except BaseException as exc:  # noqa: BLE001
+                self._fail([r], exc)
+            self.whole_solves += 1
+        return entries
+
+    # ------------------------------------------------------------------ one step
+    def _step_on_model(self, solver: str, entries: List[StepEntry]) -> None:
+        dec = self.model.decoder
+        dec.step_advance(self._pool, [e.slot for e in entries], [e.t0 for e in entries], [e.t1 for e in entries],
+                         [e.y_len for e in entries], [e.t_len for e in entries], solver=solver)
+        self._note_flags(self.model._rt.ready(), "dec")
+
+    def _note_flags(self, hip, kind: str) -> None:
+        """OR this stream's latest call's header words into the batcher's sticky copy (a call clears its own flag when it begins); no
+        synchronisation.  Nothing to note on the arithmetics that cannot saturate or under ``range_policy = 'ignore'``."""
+        if not self._guarded(hip):
+            return
+        w = hip.call_flags(kind)
+        if w is None:
+            return
+        if self._flags is None:
+            self._flags = torch.zeros(3, dtype=torch.int32, device=w.device)
+        dst = self._flags[0:1] if kind == "enc" else self._flags[1:3]
+        torch.maximum(dst, w[0:1] if kind == "enc" else w[0:2], out=dst)
+
+    def _guarded(self, hip) -> bool:
+        rt = self.model._rt
+        return not rt.use_wide and hip.gemm_terms() in (1, 2, 16, 17) and self.model.range_policy != "ignore"
+
+    # ------------------------------------------------------------------ leaving
+    def _finish(self, finished: List[StepEntry]) -> None:
+        if self._fake:
+            self._leave(finished)
+            for e in finished:
+                e.request.future.set_result({"mel": None, "mel_length": e.y_len})
+            return
+        model, rt = self.model, self.model._rt
+        hip = rt.ready()
+        if self._guarded(hip) and self._flags is not None:
+            flags = self._flags.tolist()                         # the iteration's one synchronisation
+            self._flags.zero_()
+            if flags[2]:
+                raise RuntimeError("matcha-tts-24k_amd: a pair-form chain launch timed out waiting for its partner workgroup (another "
+                                   "kernel held CUs during the launch?); set MTTS_CHAIN_PAIR=0")
+            if flags[0] or flags[1] or hip.weights_saturate():
+                if model.range_policy == "raise":
+                    raise FloatingPointError("matcha-tts-24k_amd: an operand left the fp16 range (|x| > 65504) in the default split "
+                                             "arithmetic; set model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
+                # rerun: the model switches to the wide arithmetic (sticky, as synthesise) and everybody who is active starts over
+                rt.use_wide = True
+                again = [e.request for e in self._active]
+                self._leave(list(self._active))
+                with self._cv:
+                    self._waiting[:0] = again
+                return
+        mel_std, mel_mean = rt.mel_std, rt.mel_mean
+        res = []
+        for e in finished:
+            res.append({"mel": model.decoder.step_read(self._pool, e.slot, e.y_len, mel_std, mel_mean), "mel_length": e.y_len})
+        self._leave(finished)
+        if self.vocoder is not None:
+            t_max = max(e.y_len for e in finished)
+            mel = torch.zeros(len(finished), res[0]["mel"].shape[0], t_max, device=res[0]["mel"].device)
+            for b, r in enumerate(res):
+                mel[b, :, :r["mel_length"]] = r["mel"]
+            lengths = torch.tensor([r["mel_length"] for r in res], dtype=torch.long, device=mel.device)
+            try:
+                waveforms_into(res, mel, lengths, self.vocoder, self.wave_batch)
+            except BaseException as exc:  # noqa: BLE001 - the finishers only: who is mid-solve is not affected
+                self._fail([e.request for e in finished], exc)
+                return
+        for e, r in zip(finished, res):
+            e.request.future.set_result(r)

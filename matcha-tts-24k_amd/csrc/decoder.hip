@@ -94,6 +94,11 @@ struct DecBufs {
     const float* kb(int l) const { return folded ? kbias[l] : mask[l]; }
     bool tables = false;
     unsigned int* pair_flag = nullptr;   // pair form of the chain launch: one flag per (row tile, half), zeroed per call
+    // One time per utterance (mtts_cfm_step): TB then holds a bias row per (stage, utterance), row stage * B + b, and the ResNets'
+    // bias consumers step tb_stride floats per utterance (0: one row per evaluation for the whole batch).
+    int tb_stride = 0;
+    float *step_tv = nullptr, *step_dt = nullptr;        // [4 * B] stage times, [B] dt
+    float *rs_full = nullptr, *rs_half = nullptr;        // [B*T] mask * dt, mask * dt/2: the final projection's row factors
     bool qkv_ready = false;              // the previous block's chain launch already left this block's q|k|v image in QKV
 };
 
@@ -108,6 +113,9 @@ static bool p16_decoder(const mtts_ctx* c) {
         if (g.dec_channels[l] % 64) return false;
     return true;
 }
+
+// Rows of the time-embedding buffers: the evaluations of a whole solve, or the (stage, utterance) pairs of one rk4 step of B utterances.
+static int step_time_rows(int B) { return std::max(MAX_EVALS, 4 * B); }
 
 static int plan_decoder(const mtts_ctx* c, int B, int T, int max_evals, int n_state, int n_vel, WS& ws, DecBufs& d) {
     const mtts_config& g = c->cfg;
@@ -154,16 +162,20 @@ static int plan_decoder(const mtts_ctx* c, int B, int T, int max_evals, int n_st
     d.TS = ws.f((size_t)max_evals * 2 * g.n_feats);
     d.T1 = ws.f((size_t)max_evals * temb); d.T2 = ws.f((size_t)max_evals * temb); d.T3 = ws.f((size_t)max_evals * temb);
     d.TB = ws.f((size_t)max_evals * c->dec.tb_total);
+    d.step_tv = ws.f((size_t)4 * B); d.step_dt = ws.f(B);
+    d.rs_full = ws.f(M0); d.rs_half = ws.f(M0);
     return 0;
 }
 
 // SinusoidalPosEmb + TimestepEmbedding + every ResNet's Linear(Mish(t)) for all evaluation times at once
 // (reference decoder.py:14-29,107-119,51,60): they depend on t only, so the whole ODE grid is done before the loop.
-static int time_embed(mtts_ctx* c, DecBufs& d, const TimeVals& tv, int nt, hipStream_t s) {
+// tv == null: the nt times are d_tv in device memory (one per stage and utterance of a solver step).
+static int time_embed(mtts_ctx* c, DecBufs& d, const TimeVals* tv, const float* d_tv, int nt, hipStream_t s) {
     const mtts_config& g = c->cfg;
     const DecW& D = c->dec;
     const int cin0 = 2 * g.n_feats, temb = g.dec_channels[0] * 4;
-    LAUNCH(c, 2, 0, s, launch_time_sinusoid(W(c, D.freqs.off), tv, nt, cin0 / 2, 1000.0f, d.TS, s));
+    if (tv) LAUNCH(c, 2, 0, s, launch_time_sinusoid(W(c, D.freqs.off), *tv, nt, cin0 / 2, 1000.0f, d.TS, s));
+    else LAUNCH(c, 2, 0, s, launch_time_sinusoid_dev(W(c, D.freqs.off), d_tv, nt, cin0 / 2, 1000.0f, d.TS, s));
     GemmArgs a;
     panel_args(c, D.t1, a); rows_plain(a, nt, 1);
     a.a0 = d.TS; a.lda0 = cin0; a.c0 = cin0; a.act = ACT_SILU; a.out = d.T1; a.ldc = temb;
@@ -281,7 +293,7 @@ static int block1d_fused(mtts_ctx* c, DecBufs& d, const GemmArgs& a, int lvl, co
     f.a16_0 = a.a16_0; f.lda16_0 = a.lda16_0; f.c0 = a.c0;
     f.a16_1 = a.a16_1; f.lda16_1 = a.lda16_1; f.c1 = a.c1;
     f.w16 = a.w16; f.bias = a.bias; f.B = a.B; f.T = a.T_out; f.N = a.N;
-    f.gamma = W(c, gamma.off); f.beta = W(c, beta.off); f.mask = d.mask[lvl]; f.chbias = chbias; f.nrows = d.nr(lvl);
+    f.gamma = W(c, gamma.off); f.beta = W(c, beta.off); f.mask = d.mask[lvl]; f.chbias = chbias; f.chbias_stride = d.tb_stride; f.nrows = d.nr(lvl);
     if (d.folded) { f.nextra = d.ne(lvl); f.bias_stats = W(c, bias_stats.off); }
     f.out16 = image(dst); f.ld16 = d.ew * a.N;
     return run_conv_gn(c, f, s);
@@ -306,7 +318,7 @@ static int resnet_block(mtts_ctx* c, DecBufs& d, const ResnetW& r, const Actv& i
     } else {
         GnApplyArgs g1;
         RET_IF(conv_gn_stats(c, d, a, lvl, r.gn1_g, r.gn1_b, r.gn1_bs, g1, s));
-        g1.chbias = tbias;
+        g1.chbias = tbias; g1.chbias_stride = d.tb_stride;
         bind_out(d, g1, d.H, C);
         RET_IF(run_gn_apply(c, g1, s));
     }
@@ -457,9 +469,11 @@ static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, int C, i
 
 struct FinalOut {   // where the masked velocity goes: out = v * scale (+ res)
     float* out; int ldc; const float* res; int ldr; float scale;
+    const float* row_scale = nullptr;   // [B*T] mask[row] * scale of the row's utterance instead of mask and scale (one dt per utterance)
 };
 
-// Decoder.forward (reference decoder.py:359-426) for evaluation `ev` (row of the precomputed time biases).
+// Decoder.forward (reference decoder.py:359-426) for evaluation `ev` (row of the precomputed time biases; with one time per
+// utterance, d.tb_stride != 0, the row of utterance 0).
 // xin: channels-last state [B*T, ldx] holding x | mu.
 static int unet_eval(mtts_ctx* c, DecBufs& d, const float* xin, int ev, const FinalOut& fo, hipStream_t s) {
     const mtts_config& g = c->cfg;
@@ -543,8 +557,8 @@ static int unet_eval(mtts_ctx* c, DecBufs& d, const float* xin, int ev, const Fi
     GemmArgs p;
     panel_args(c, D.final_proj, p); rows_plain(p, B, T);
     bind_in(d, p, 0, actv(d, d.H, C0));
-    p.out_mask = d.mask[0];
-    p.out = fo.out; p.ldc = fo.ldc; p.res = fo.res; p.ldr = fo.ldr; p.out_scale = fo.scale;
+    p.out_mask = fo.row_scale ? fo.row_scale : d.mask[0];
+    p.out = fo.out; p.ldc = fo.ldc; p.res = fo.res; p.ldr = fo.ldr; p.out_scale = fo.row_scale ? 1.0f : fo.scale;
     RET_IF(run_gemm(c, p, s));
     return 0;
 }
@@ -587,7 +601,7 @@ int64_t mtts_decoder_workspace_bytes(mtts_ctx* c, int B, int T) {
     if (!c || (!c->packed && pack_all(c))) return -1;
     WS ws(nullptr, 0);
     DecBufs d;
-    if (plan_decoder(c, B, T, MAX_EVALS, 2, 4, ws, d)) return -1;
+    if (plan_decoder(c, B, T, step_time_rows(B), 2, 4, ws, d)) return -1;
     return (int64_t)ws.off + 256;
 }
 
@@ -604,7 +618,7 @@ int mtts_decoder_forward(mtts_ctx* c, const float* d_x, const float* d_mask, con
     hipStream_t s = static_cast<hipStream_t>(stream);
     WS ws(d_ws, (size_t)ws_bytes);
     DecBufs d;
-    RET_IF(plan_decoder(c, B, T, MAX_EVALS, 2, 4, ws, d));
+    RET_IF(plan_decoder(c, B, T, step_time_rows(B), 2, 4, ws, d));
     if (ws.overflow) { set_error("decoder workspace too small"); return -1; }
     RET_IF(begin_call(c, d_ws, s));
     if (c->sw.pair_on) HIP_OK(launch_fill_cols(reinterpret_cast<float*>(d.pair_flag), 1, 512, 0, 512, 0.f, s));
@@ -615,7 +629,7 @@ int mtts_decoder_forward(mtts_ctx* c, const float* d_x, const float* d_mask, con
     LAUNCH(c, 2, 0, s, launch_cf_to_cl(d_mu, nullptr, B, nf, T, d.xmu, d.ldx, nf, s));
     TimeVals tv;
     tv.t[0] = t;
-    RET_IF(time_embed(c, d, tv, 1, s));
+    RET_IF(time_embed(c, d, &tv, nullptr, 1, s));
     FinalOut fo{d.vel[0], d.ldv, nullptr, 0, 1.0f};
     RET_IF(decoder_eval(c, d, d.xmu, 0, fo, s));
     LAUNCH(c, 2, 0, s, launch_cl_to_cf(d.vel[0], d.ldv, B, nf, T, d_out, T, 1.0f, 0.0f, s));
@@ -637,7 +651,7 @@ static int solve_core(mtts_ctx* c, const float* d_x0, const float* d_mu, const f
     hipStream_t s = static_cast<hipStream_t>(stream);
     WS ws(d_ws, (size_t)ws_bytes);
     DecBufs d;
-    RET_IF(plan_decoder(c, B, T, MAX_EVALS, 2, 4, ws, d));
+    RET_IF(plan_decoder(c, B, T, step_time_rows(B), 2, 4, ws, d));
     if (ws.overflow) { set_error("decoder workspace too small"); return -1; }
     RET_IF(begin_call(c, d_ws, s));
     if (c->sw.pair_on) HIP_OK(launch_fill_cols(reinterpret_cast<float*>(d.pair_flag), 1, 512, 0, 512, 0.f, s));
@@ -663,7 +677,7 @@ static int solve_core(mtts_ctx* c, const float* d_x0, const float* d_mu, const f
             tv.t[ne++] = t0; tv.t[ne++] = t0 + dt * third; tv.t[ne++] = t0 + dt * two_thirds; tv.t[ne++] = t1;
         }
     }
-    RET_IF(time_embed(c, d, tv, ne, s));
+    RET_IF(time_embed(c, d, &tv, nullptr, ne, s));
 
     int ev = 0;
     for (int i = 0; i < n_steps; ++i) {
@@ -718,6 +732,76 @@ int mtts_cfm_solve_folded(mtts_ctx* c, const float* d_x0, const float* d_mu, con
     }
     return solve_core(c, d_x0, d_mu, nullptr, d_y_lengths, add_mu, h_t_span, n_steps, solver, B, T, T_fold, d_out, T_out, out_scale,
                       out_shift, d_ws, ws_bytes, stream);
+}
+
+// One solver step of B utterances of a slot pool, each at its own point (t0, t1) of its own grid (include/mtts.h).  The sequence of
+// solve_core for ONE grid interval, with what solve_core takes per call taken per utterance: the stage times (launch_step_tables ->
+// time_embed on stages * B rows -> a bias row per utterance in every ResNet, DecBufs::tb_stride), dt (the final projection's row
+// factors; ode_combine per utterance for rk4), and the state rows, which come from and return to the pool every step.
+int mtts_cfm_step(mtts_ctx* c, float* d_z_pool, const float* d_mu_pool, int S, int T_cap, const int32_t* d_slots, const int32_t* h_slots,
+                  const float* d_t0, const float* d_t1, const int64_t* d_y_lengths, int y_max, int solver, int B, int T_fold, void* d_ws,
+                  int64_t ws_bytes, void* stream) {
+    CTX_GUARD(c);
+    RET_IF(check_ready(c));
+    if (!d_z_pool || !d_mu_pool || !d_slots || !h_slots || !d_t0 || !d_t1 || !d_y_lengths || !d_ws) { set_error("mtts_cfm_step: null argument"); return -1; }
+    const int stages = solver == MTTS_SOLVER_EULER ? 1 : solver == MTTS_SOLVER_MIDPOINT ? 2 : solver == MTTS_SOLVER_RK4 ? 4 : 0;
+    if (!stages) { set_error("unsupported solver"); return -1; }
+    if (S < 1 || T_cap < 1 || B < 1 || B > S) { set_error("mtts_cfm_step: need 1 <= B <= S slots of T_cap >= 1 frames"); return -1; }
+    if (y_max < 1 || y_max > T_cap) { set_error("mtts_cfm_step: an utterance of y_max frames does not fit a slot of T_cap frames"); return -1; }
+    if (T_fold > T_cap || T_fold < mtts_fold_rows(c, y_max, 1)) {
+        set_error("mtts_cfm_step: T_fold must hold ceil(y_max / 2^l) + 1 rows at every level and not exceed T_cap (mtts_fold_rows)");
+        return -1;
+    }
+    if (T_fold % (1 << (c->cfg.dec_levels - 1))) {
+        set_error("mtts_cfm_step: T_fold must be a multiple of 2^(levels-1) (mtts_fold_rows returns such counts)");
+        return -1;
+    }
+    {
+        std::vector<char> taken((size_t)S, 0);
+        for (int b = 0; b < B; ++b) {
+            const int32_t sl = h_slots[b];
+            if (sl < 0 || sl >= S) { set_error("mtts_cfm_step: slot index out of range"); return -1; }
+            if (taken[sl]) { set_error("mtts_cfm_step: a slot appears twice in one step"); return -1; }
+            taken[sl] = 1;
+        }
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int T = T_fold;
+    WS ws(d_ws, (size_t)ws_bytes);
+    DecBufs d;
+    RET_IF(plan_decoder(c, B, T, step_time_rows(B), 2, 4, ws, d));
+    if (ws.overflow) { set_error("decoder workspace too small"); return -1; }
+    RET_IF(begin_call(c, d_ws, s));
+    if (c->sw.pair_on) HIP_OK(launch_fill_cols(reinterpret_cast<float*>(d.pair_flag), 1, 512, 0, 512, 0.f, s));
+    const int nf = c->cfg.n_feats, M = B * T;
+    RET_IF(build_frames(c, d, nullptr, d_y_lengths, T_cap, s));
+    float* states[2] = {d.xmu, d.xmu2};
+    for (int k = 0; k < (stages > 1 ? 2 : 1); ++k) {
+        LAUNCH(c, 2, 0, s, launch_fill_cols(states[k], M, d.ldx, 2 * nf, d.ldx - 2 * nf, 0.f, s));
+        LAUNCH(c, 2, 0, s, launch_slots_to_cl(d_mu_pool, d_slots, S, T_cap, B, nf, T, states[k], d.ldx, nf, s));
+    }
+    LAUNCH(c, 2, 0, s, launch_slots_to_cl(d_z_pool, d_slots, S, T_cap, B, nf, T, d.xmu, d.ldx, 0, s));
+    LAUNCH(c, 2, 0, s, launch_step_tables(d_t0, d_t1, d.mask[0], B, T, stages, d.step_tv, d.step_dt, d.rs_full, d.rs_half, s));
+    RET_IF(time_embed(c, d, nullptr, d.step_tv, stages * B, s));
+    d.tb_stride = (int)c->dec.tb_total;
+    if (solver == MTTS_SOLVER_EULER) {
+        FinalOut fo{d.xmu, d.ldx, d.xmu, d.ldx, 1.0f, d.rs_full};
+        RET_IF(decoder_eval(c, d, d.xmu, 0, fo, s));
+    } else if (solver == MTTS_SOLVER_MIDPOINT) {
+        FinalOut f1{d.xmu2, d.ldx, d.xmu, d.ldx, 1.0f, d.rs_half};
+        RET_IF(decoder_eval(c, d, d.xmu, 0, f1, s));
+        FinalOut f2{d.xmu, d.ldx, d.xmu, d.ldx, 1.0f, d.rs_full};
+        RET_IF(decoder_eval(c, d, d.xmu2, B, f2, s));
+    } else {
+        for (int k = 0; k < 4; ++k) {
+            FinalOut fk{d.vel[k], d.ldv, nullptr, 0, 1.0f};
+            RET_IF(decoder_eval(c, d, k == 0 ? d.xmu : d.xmu2, k * B, fk, s));
+            float* dst = k < 3 ? d.xmu2 : d.xmu;
+            LAUNCH(c, 2, 0, s, launch_ode_combine_rows(k + 1, d.step_dt, T, d.xmu, d.ldx, d.vel[0], d.vel[1], d.vel[2], d.vel[3], d.ldv, dst, d.ldx, M, nf, s));
+        }
+    }
+    LAUNCH(c, 2, 0, s, launch_cl_to_slots(d.xmu, d.ldx, B, nf, T, d_z_pool, d_slots, S, T_cap, s));
+    return 0;
 }
 
 }  // extern "C"

@@ -189,6 +189,7 @@ struct ConvGnArgs {
     const float* gamma = nullptr; const float* beta = nullptr;
     const float* mask = nullptr;      // [B*T]
     const float* chbias = nullptr;    // [N] time-embedding bias or null
+    int chbias_stride = 0;            // floats between the bias rows of two utterances (% 4 == 0); 0 = one row for the batch
     const int* nrows = nullptr;       // as GnApplyArgs
     const int* nextra = nullptr;
     const float* bias_stats = nullptr;
@@ -350,6 +351,7 @@ struct GnApplyArgs {
     const float* gamma = nullptr; const float* beta = nullptr;
     const float* mask = nullptr;      // [B*T]
     const float* chbias = nullptr;    // [C] (time-embedding bias of the ResNet block) or null
+    int chbias_stride = 0;            // floats between the bias rows of two utterances (% 4 == 0); 0 = one row for the batch
     const float* res = nullptr; int ldr = 0;
     float* out = nullptr;
     float* stats_out = nullptr;       // [B*T][C/64][2] LayerNorm partial moments of the output rows (C % 64 == 0)
@@ -379,16 +381,34 @@ hipError_t launch_cf_to_cl(const float* src, const float* add, int B, int C, int
                            int T_src = 0, const int64_t* lengths = nullptr);
 // dst[b,c,t] = src[b,t,c] * scale + shift for t < T_out
 hipError_t launch_cl_to_cf(const float* src, int ld, int B, int C, int T, float* dst, int T_out, float scale, float shift, hipStream_t s);
+// The same moves between a slot pool [S, C, T_pool] and the rows of this step's utterances (mtts_cfm_step): utterance b lives in
+// slot slots[b] (device int32 [B]).  A slot outside [0, S) is neither read (its rows are written as zero) nor written.
+//   load:  dst[b*T + t, col_off + c] = pool[slots[b], c, t]        store: pool[slots[b], c, t] = src[b*T + t, c]        (t < T <= T_pool)
+hipError_t launch_slots_to_cl(const float* pool, const int32_t* slots, int S, int T_pool, int B, int C, int T, float* dst, int ld,
+                              int col_off, hipStream_t s);
+hipError_t launch_cl_to_slots(const float* src, int ld, int B, int C, int T, float* pool, const int32_t* slots, int S, int T_pool,
+                              hipStream_t s);
 hipError_t launch_fill_cols(float* dst, int M, int ld, int col0, int ncols, float v, hipStream_t s);
 
 // elementwise helpers
 constexpr int MAX_EVALS = 256;
 struct TimeVals { float t[MAX_EVALS]; };
 hipError_t launch_time_sinusoid(const float* freqs, const TimeVals& tv, int nt, int half, float scale, float* out, hipStream_t s);
+// the same for nt times in device memory (no bound on nt)
+hipError_t launch_time_sinusoid_dev(const float* freqs, const float* d_t, int nt, int half, float scale, float* out, hipStream_t s);
 hipError_t launch_unary(const float* x, float* y, int64_t n, int act_mish, hipStream_t s);
 // ODE state updates on the x columns of the channels-last state; stage semantics in norm_glue.hip
 hipError_t launch_ode_combine(int stage, float dt, const float* y, int ldy, const float* k1, const float* k2, const float* k3,
                               const float* k4, int ldk, float* out, int ldo, int M, int C, hipStream_t s);
+// ... with one dt per utterance: row r of the M = B * T rows takes dt_b[r / T] (device [B])
+hipError_t launch_ode_combine_rows(int stage, const float* dt_b, int T, const float* y, int ldy, const float* k1, const float* k2,
+                                   const float* k3, const float* k4, int ldk, float* out, int ldo, int M, int C, hipStream_t s);
+// Per-utterance times of one solver step (mtts_cfm_step), from t0[b], t1[b] in device memory, dt = t1 - t0 in fp32 as torchdiffeq's
+// fixed-grid loop takes it: the stage times tv[k * B + b] (stages 1 euler: t0; 2 midpoint: t0, t0 + 0.5 dt; 4 rk4: t0,
+// t0 + dt/3, t0 + dt 2/3, t1), dt_b[b] = dt, and the final projection's row factors rs_full[row] = mask[row] * dt,
+// rs_half[row] = mask[row] * (0.5 dt) (GemmArgs::out_mask; the mask is 0/1, so each rounds like mask * out_scale).
+hipError_t launch_step_tables(const float* t0, const float* t1, const float* mask, int B, int T, int stages, float* tv, float* dt_b,
+                              float* rs_full, float* rs_half, hipStream_t s);
 
 // text-encoder glue
 hipError_t launch_embedding(const int64_t* ids, const float* table, int rows, int C, float scale, const float* mask, float* out, int ld, hipStream_t s);

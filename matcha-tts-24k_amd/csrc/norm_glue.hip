@@ -315,7 +315,7 @@ __global__ void gn_apply_kernel(const GnApplyArgs p) {
     const f32x4 gm = *reinterpret_cast<const f32x4*>(p.gamma + c4 * 4);
     const f32x4 bt = *reinterpret_cast<const f32x4*>(p.beta + c4 * 4);
     f32x4 cb = {0.f, 0.f, 0.f, 0.f};
-    if (p.chbias) cb = *reinterpret_cast<const f32x4*>(p.chbias + c4 * 4);
+    if (p.chbias) cb = *reinterpret_cast<const f32x4*>(p.chbias + (size_t)b * p.chbias_stride + c4 * 4);     // (stride != 0: utterance b's own row)
     const int t0 = chunk * p.chunk_rows;
     const int rows = min(p.chunk_rows, p.T - t0);
     // U rows per pass, every load of the pass issued before the first use (the loop is a pure stream: without this each
@@ -394,6 +394,7 @@ hipError_t launch_gn_apply(const GnApplyArgs& a, hipStream_t s) {
     if (a.out16 && ((a.C & 31) || a.ld16 < (a.half16 ? 1 : 2) * a.C || (a.ld16 & 3))) return hipErrorInvalidValue;
     if (a.tile_stats && (a.tile_rows <= 0 || a.T < a.tile_rows || (a.C & 63) || (a.C / a.G) < 32)) return hipErrorInvalidValue;
     if ((a.nextra != nullptr) != (a.bias_stats != nullptr)) return hipErrorInvalidValue;
+    if (a.chbias_stride < 0 || (a.chbias_stride & 3)) return hipErrorInvalidValue;
     GnApplyArgs b = a;
     b.chunk_rows = gn_chunk_rows(a.B, a.T);
     hipLaunchKernelGGL(gn_apply_kernel, dim3(gn_chunks(a.B, a.T), a.B), gn_block(a.C), 0, s, b);
@@ -465,6 +466,59 @@ hipError_t launch_cl_to_cf(const float* src, int ld, int B, int C, int T, float*
     return hipGetLastError();
 }
 
+// The two moves above between a slot pool [S, C, T_pool] and the rows of the utterances of one solver step: utterance b <-> slot
+// slots[b].  A slot outside [0, S) is not touched (load: zero rows).
+__global__ void slots_to_cl_kernel(const float* __restrict__ pool, const int32_t* __restrict__ slots, int S, int T_pool, int C, int T,
+                                   float* __restrict__ dst, int ld, int col_off) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int slot = slots[b];
+    const bool live = (unsigned)slot < (unsigned)S;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = c0 + ty + 8 * k, t = t0 + tx;
+        tile[ty + 8 * k][tx] = (live && c < C && t < T) ? pool[((size_t)slot * C + c) * T_pool + t] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int t = t0 + ty + 8 * k, c = c0 + tx;
+        if (c < C && t < T) dst[((size_t)b * T + t) * ld + col_off + c] = tile[tx][ty + 8 * k];
+    }
+}
+hipError_t launch_slots_to_cl(const float* pool, const int32_t* slots, int S, int T_pool, int B, int C, int T, float* dst, int ld,
+                              int col_off, hipStream_t s) {
+    if (!pool || !slots || !dst || S <= 0 || B <= 0 || C <= 0 || T <= 0 || T > T_pool || col_off < 0 || col_off + C > ld) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(slots_to_cl_kernel, dim3((T + 31) / 32, (C + 31) / 32, B), dim3(32, 8), 0, s, pool, slots, S, T_pool, C, T, dst, ld, col_off);
+    return hipGetLastError();
+}
+__global__ void cl_to_slots_kernel(const float* __restrict__ src, int ld, int C, int T, float* __restrict__ pool,
+                                   const int32_t* __restrict__ slots, int S, int T_pool) {
+    __shared__ float tile[32][33];
+    const int b = blockIdx.z, t0 = blockIdx.x * 32, c0 = blockIdx.y * 32;
+    const int tx = threadIdx.x, ty = threadIdx.y;
+    const int slot = slots[b];
+    if ((unsigned)slot >= (unsigned)S) return;         // (uniform per workgroup)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int t = t0 + ty + 8 * k, c = c0 + tx;
+        tile[ty + 8 * k][tx] = (c < C && t < T) ? src[((size_t)b * T + t) * ld + c] : 0.f;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int c = c0 + ty + 8 * k, t = t0 + tx;
+        if (c < C && t < T) pool[((size_t)slot * C + c) * T_pool + t] = tile[tx][ty + 8 * k];
+    }
+}
+hipError_t launch_cl_to_slots(const float* src, int ld, int B, int C, int T, float* pool, const int32_t* slots, int S, int T_pool,
+                              hipStream_t s) {
+    if (!src || !pool || !slots || S <= 0 || B <= 0 || C <= 0 || T <= 0 || T > T_pool || C > ld) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(cl_to_slots_kernel, dim3((T + 31) / 32, (C + 31) / 32, B), dim3(32, 8), 0, s, src, ld, C, T, pool, slots, S, T_pool);
+    return hipGetLastError();
+}
+
 __global__ void fill_cols_kernel(float* dst, int M, int ld, int col0, int ncols, float v) {
     const size_t n = (size_t)M * ncols;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
@@ -495,6 +549,54 @@ hipError_t launch_time_sinusoid(const float* freqs, const TimeVals& tv, int nt, 
     return hipGetLastError();
 }
 
+__global__ void time_sinusoid_dev_kernel(const float* __restrict__ freqs, const float* __restrict__ tdev, int half, float scale,
+                                        float* __restrict__ out) {
+    const int i = blockIdx.x;
+    const float st = scale * tdev[i];
+    for (int j = threadIdx.x; j < half; j += blockDim.x) {
+        const float arg = st * freqs[j];
+        out[(size_t)i * 2 * half + j] = sinf(arg);
+        out[(size_t)i * 2 * half + half + j] = cosf(arg);
+    }
+}
+hipError_t launch_time_sinusoid_dev(const float* freqs, const float* d_t, int nt, int half, float scale, float* out, hipStream_t s) {
+    if (!freqs || !d_t || !out || nt <= 0 || half <= 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(time_sinusoid_dev_kernel, dim3(nt), dim3(128), 0, s, freqs, d_t, half, scale, out);
+    return hipGetLastError();
+}
+
+// Per-utterance times of one solver step (kernels.h launch_step_tables): one thread per (utterance, row).
+__global__ void step_tables_kernel(const float* __restrict__ t0, const float* __restrict__ t1, const float* __restrict__ mask, int B,
+                                   int T, int stages, float* __restrict__ tv, float* __restrict__ dt_b, float* __restrict__ rs_full,
+                                   float* __restrict__ rs_half) {
+    const int b = blockIdx.y;
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const float a = t0[b], e = t1[b], dt = e - a;
+    if (t == 0) {
+        dt_b[b] = dt;
+        tv[b] = a;
+        if (stages == 2) tv[B + b] = a + 0.5f * dt;
+        if (stages == 4) {
+            const float third = 1.0f / 3.0f, two_thirds = 2.0f / 3.0f;
+            tv[B + b] = a + dt * third;
+            tv[2 * B + b] = a + dt * two_thirds;
+            tv[3 * B + b] = e;
+        }
+    }
+    if (t < T) {
+        const float m = mask[(size_t)b * T + t];
+        rs_full[(size_t)b * T + t] = m * dt;
+        rs_half[(size_t)b * T + t] = m * (0.5f * dt);
+    }
+}
+hipError_t launch_step_tables(const float* t0, const float* t1, const float* mask, int B, int T, int stages, float* tv, float* dt_b,
+                              float* rs_full, float* rs_half, hipStream_t s) {
+    if (!t0 || !t1 || !mask || !tv || !dt_b || !rs_full || !rs_half || B <= 0 || T <= 0 || (stages != 1 && stages != 2 && stages != 4))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(step_tables_kernel, dim3((T + 255) / 256, B), dim3(256), 0, s, t0, t1, mask, B, T, stages, tv, dt_b, rs_full, rs_half);
+    return hipGetLastError();
+}
+
 __global__ void unary_kernel(const float* __restrict__ x, float* __restrict__ y, size_t n, int act_mish) {
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         y[i] = act_mish ? mish_f(x[i]) : silu_f(x[i]);
@@ -509,13 +611,16 @@ hipError_t launch_unary(const float* x, float* y, int64_t n, int act_mish, hipSt
 //   stage 1: y + dt*k1*(1/3)            stage 2: y + dt*(k2 - k1*(1/3))
 //   stage 3: y + dt*(k1 - k2 + k3)      stage 4: y + (k1 + 3*(k2+k3) + k4)*dt*0.125
 //   stage 0: y + dt*k1  (plain axpy)
-__global__ void ode_combine_kernel(int stage, float dt, const float* __restrict__ y, int ldy, const float* __restrict__ k1,
-                                   const float* __restrict__ k2, const float* __restrict__ k3, const float* __restrict__ k4,
-                                   int ldk, float* __restrict__ out, int ldo, int M, int C) {
+// PER_UTT: dt = dt_b[r / T] of row r's utterance (one solver step of utterances at different points of their grids, mtts_cfm_step)
+template <bool PER_UTT>
+__global__ void ode_combine_kernel(int stage, float dt, const float* __restrict__ dt_b, int T, const float* __restrict__ y, int ldy,
+                                   const float* __restrict__ k1, const float* __restrict__ k2, const float* __restrict__ k3,
+                                   const float* __restrict__ k4, int ldk, float* __restrict__ out, int ldo, int M, int C) {
     const float third = 1.0f / 3.0f;   // torchdiffeq _one_third, rounded to fp32 when it meets an fp32 tensor
     const size_t n = (size_t)M * C;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         const size_t r = i / C, c = i % C;
+        if constexpr (PER_UTT) dt = dt_b[r / T];
         const float yv = y[r * ldy + c];
         const size_t ik = r * ldk + c;
         float v;
@@ -533,8 +638,16 @@ hipError_t launch_ode_combine(int stage, float dt, const float* y, int ldy, cons
                               const float* k4, int ldk, float* out, int ldo, int M, int C, hipStream_t s) {
     if (!y || !k1 || !out || M <= 0 || C <= 0) return hipErrorInvalidValue;
     const size_t n = (size_t)M * C;
-    hipLaunchKernelGGL(ode_combine_kernel, dim3((unsigned)min((n + 255) / 256, (size_t)2048)), dim3(256), 0, s, stage, dt, y, ldy, k1,
-                       k2, k3, k4, ldk, out, ldo, M, C);
+    hipLaunchKernelGGL(ode_combine_kernel<false>, dim3((unsigned)min((n + 255) / 256, (size_t)2048)), dim3(256), 0, s, stage, dt, nullptr, 1,
+                       y, ldy, k1, k2, k3, k4, ldk, out, ldo, M, C);
+    return hipGetLastError();
+}
+hipError_t launch_ode_combine_rows(int stage, const float* dt_b, int T, const float* y, int ldy, const float* k1, const float* k2,
+                                   const float* k3, const float* k4, int ldk, float* out, int ldo, int M, int C, hipStream_t s) {
+    if (!y || !k1 || !out || !dt_b || T <= 0 || M <= 0 || (M % T) || C <= 0) return hipErrorInvalidValue;
+    const size_t n = (size_t)M * C;
+    hipLaunchKernelGGL(ode_combine_kernel<true>, dim3((unsigned)min((n + 255) / 256, (size_t)2048)), dim3(256), 0, s, stage, 0.f, dt_b, T,
+                       y, ldy, k1, k2, k3, k4, ldk, out, ldo, M, C);
     return hipGetLastError();
 }
 

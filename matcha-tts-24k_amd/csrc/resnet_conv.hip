@@ -207,7 +207,10 @@ __global__ __launch_bounds__(512, 1) void conv_gn_kernel(const ConvGnArgs p) {
     const f32x4 gm0 = *reinterpret_cast<const f32x4*>(p.gamma + c0g), gm1 = *reinterpret_cast<const f32x4*>(p.gamma + c0g + 4);
     const f32x4 bt0 = *reinterpret_cast<const f32x4*>(p.beta + c0g), bt1 = *reinterpret_cast<const f32x4*>(p.beta + c0g + 4);
     f32x4 cb0 = {0.f, 0.f, 0.f, 0.f}, cb1 = cb0;
-    if (p.chbias) { cb0 = *reinterpret_cast<const f32x4*>(p.chbias + c0g); cb1 = *reinterpret_cast<const f32x4*>(p.chbias + c0g + 4); }
+    if (p.chbias) {        // (chbias_stride != 0: utterance b's own row -- one time per utterance, mtts_cfm_step)
+        const float* cbp = p.chbias + (size_t)b * p.chbias_stride + c0g;
+        cb0 = *reinterpret_cast<const f32x4*>(cbp); cb1 = *reinterpret_cast<const f32x4*>(cbp + 4);
+    }
     const int nr = p.nrows ? max(0, min(T, p.nrows[b])) : T;          // rows that enter the statistics
     float x_ne = 0.f, x_bm = 0.f, x_bq = 0.f;
     if (p.nextra) { x_ne = (float)p.nextra[b]; x_bm = p.bias_stats[2 * g]; x_bq = p.bias_stats[2 * g + 1]; }
@@ -302,6 +305,7 @@ hipError_t launch_conv_gn(const ConvGnArgs& a, hipStream_t s) {
     if (a.lda16_0 < 2 * a.c0 || (a.lda16_0 & 7) || (a.a16_1 && (a.lda16_1 < 2 * a.c1 || (a.lda16_1 & 7)))) return hipErrorInvalidValue;
     if (a.ld16 < 2 * a.N || (a.ld16 & 7)) return hipErrorInvalidValue;
     if ((a.nextra != nullptr) != (a.bias_stats != nullptr)) return hipErrorInvalidValue;
+    if (a.chbias_stride < 0 || (a.chbias_stride & 3)) return hipErrorInvalidValue;
     const bool split = a.T <= CONV_GN_SPLIT_ROWS;
     static bool configured[2] = {false, false};
     const void* kern = split ? reinterpret_cast<const void*>(conv_gn_kernel<2>) : reinterpret_cast<const void*>(conv_gn_kernel<1>);

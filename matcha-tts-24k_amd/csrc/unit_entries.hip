@@ -186,9 +186,10 @@ int mtts_gemm_p16(const float* d_a, int lda, int B, int T_in, int C, int ntaps, 
 // is converted to its P16 image in d_scratch, the Conv1d(k3) weight is packed and split as for mtts_gemm_p16, the P16 output is
 // decoded back to fp32 [B*T, N].  c1 > 0: the last c1 channels of x form a second input segment (the up path's skip concat).
 int64_t mtts_conv_gn_scratch_bytes(int B, int T, int C, int N) { return (int64_t)B * T * (C + N) * 4 + 1024; }
-int mtts_conv_gn(const float* d_x, int B, int T, int C, int c1, const float* d_w, void* d_wpacked, const float* d_bias, int N,
-                 const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias, const int* d_nrows,
-                 const int* d_nextra, const float* d_bias_stats, float eps, float* d_out, void* d_scratch, void* stream) {
+static int conv_gn_entry(const float* d_x, int B, int T, int C, int c1, const float* d_w, void* d_wpacked, const float* d_bias, int N,
+                         const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias, int chbias_stride,
+                         const int* d_nrows, const int* d_nextra, const float* d_bias_stats, float eps, float* d_out, void* d_scratch,
+                         void* stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (!d_x || !d_w || !d_wpacked || !d_scratch || !d_out) { set_error("null buffer"); return -1; }
     if (C <= 0 || (C % 32) || c1 < 0 || (c1 % 32) || c1 >= C) { set_error("mtts_conv_gn: C and c1 must be multiples of 32, c1 < C"); return -1; }
@@ -205,11 +206,26 @@ int mtts_conv_gn(const float* d_x, int B, int T, int C, int c1, const float* d_w
     a.a16_0 = a16; a.lda16_0 = 2 * C; a.c0 = C - c1;
     if (c1) { a.a16_1 = a16 + 2 * (C - c1); a.lda16_1 = 2 * C; a.c1 = c1; }
     a.w16 = planes; a.bias = d_bias; a.B = B; a.T = T; a.N = N;
-    a.gamma = d_gamma; a.beta = d_beta; a.mask = d_mask; a.chbias = d_chbias; a.nrows = d_nrows; a.nextra = d_nextra; a.bias_stats = d_bias_stats;
+    a.gamma = d_gamma; a.beta = d_beta; a.mask = d_mask; a.chbias = d_chbias; a.chbias_stride = chbias_stride; a.nrows = d_nrows; a.nextra = d_nextra; a.bias_stats = d_bias_stats;
     a.eps = eps; a.out16 = o16; a.ld16 = 2 * N;
     HIP_OK(launch_conv_gn(a, s));
     HIP_OK(launch_from_p16(o16, 2 * N, B * T, N, 2048.0f, d_out, N, s));
     return 0;
+}
+int mtts_conv_gn(const float* d_x, int B, int T, int C, int c1, const float* d_w, void* d_wpacked, const float* d_bias, int N,
+                 const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias, const int* d_nrows,
+                 const int* d_nextra, const float* d_bias_stats, float eps, float* d_out, void* d_scratch, void* stream) {
+    return conv_gn_entry(d_x, B, T, C, c1, d_w, d_wpacked, d_bias, N, d_gamma, d_beta, d_mask, d_chbias, 0, d_nrows, d_nextra, d_bias_stats,
+                         eps, d_out, d_scratch, stream);
+}
+// ... with one time-embedding bias row per utterance: d_chbias [B][chbias_stride], the first N values of a row are read
+int mtts_conv_gn_rows(const float* d_x, int B, int T, int C, int c1, const float* d_w, void* d_wpacked, const float* d_bias, int N,
+                      const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias, int chbias_stride,
+                      const int* d_nrows, const int* d_nextra, const float* d_bias_stats, float eps, float* d_out, void* d_scratch,
+                      void* stream) {
+    if (!d_chbias || chbias_stride < N) { set_error("mtts_conv_gn_rows: needs a bias row of at least N values per utterance"); return -1; }
+    return conv_gn_entry(d_x, B, T, C, c1, d_w, d_wpacked, d_bias, N, d_gamma, d_beta, d_mask, d_chbias, chbias_stride, d_nrows, d_nextra,
+                         d_bias_stats, eps, d_out, d_scratch, stream);
 }
 
 int mtts_attention_f32(const float* d_qkv, const float* d_mask, int B, int T, int H, int D, float scale, int mask_mode, float* d_out,
@@ -262,6 +278,20 @@ int mtts_groupnorm_mish(const float* d_y, const float* d_gamma, const float* d_b
     HIP_OK(launch_gn_partial(d_y, B, T, C, G, static_cast<float*>(d_scratch), s));
     GnApplyArgs a;
     a.y = d_y; a.partial = static_cast<const float*>(d_scratch); a.gamma = d_gamma; a.beta = d_beta; a.mask = d_mask;
+    a.out = d_out; a.B = B; a.T = T; a.C = C; a.G = G; a.eps = eps;
+    HIP_OK(launch_gn_apply(a, s));
+    return 0;
+}
+// ... followed by the ResNet block's time-embedding bias, (out + chbias[b]) * mask (reference decoder.py:60), one row per utterance:
+// d_chbias [B][chbias_stride] (chbias_stride = 0: one row [C] for the batch)
+int mtts_groupnorm_mish_rows(const float* d_y, const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias,
+                             int chbias_stride, int B, int T, int C, int G, float eps, float* d_out, void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!d_chbias || (chbias_stride && chbias_stride < C)) { set_error("mtts_groupnorm_mish_rows: needs a bias row of at least C values per utterance"); return -1; }
+    HIP_OK(launch_gn_partial(d_y, B, T, C, G, static_cast<float*>(d_scratch), s));
+    GnApplyArgs a;
+    a.y = d_y; a.partial = static_cast<const float*>(d_scratch); a.gamma = d_gamma; a.beta = d_beta; a.mask = d_mask;
+    a.chbias = d_chbias; a.chbias_stride = chbias_stride;
     a.out = d_out; a.B = B; a.T = T; a.C = C; a.G = G; a.eps = eps;
     HIP_OK(launch_gn_apply(a, s));
     return 0;

@@ -103,6 +103,21 @@ class Estimator(_PathModule):
         return self._rt.ready().decoder_forward(x, mask, mu, float(t))
 
 
+class StepPool:
+    """The slot pools of ``CFM.step_*``: ``z`` (ODE state, updated in place) and ``mu`` [n_slots, n_feats, slot_frames] on the device."""
+
+    def __init__(self, z: torch.Tensor, mu: torch.Tensor):
+        self.z, self.mu = z, mu
+
+    @property
+    def n_slots(self) -> int:
+        return int(self.z.shape[0])
+
+    @property
+    def slot_frames(self) -> int:
+        return int(self.z.shape[2])
+
+
 class CFM(nn.Module):
     """``decoder(mu, mask, n_timesteps)`` / ``.solve(x, t_span, mu, mask)`` -- reference flow_matching.py:25-63,110-117.
 
@@ -257,6 +272,58 @@ class CFM(nn.Module):
         self.graph_replays += 1
         n_out = rows if t_out is None else int(t_out)
         return e["out"][:, :, :n_out].clone()
+
+    # ------------------------------------------------------------------ one solver step at a time (batcher.StepBatcher)
+    def step_pool(self, n_slots: int, slot_frames: int, device) -> "StepPool":
+        """State of up to ``n_slots`` requests between the steps of their solves: ``z`` / ``mu`` [n_slots, n_feats, slot_frames]
+        (include/mtts.h mtts_cfm_step)."""
+        nf = self.n_feats // 2
+        return StepPool(torch.zeros(n_slots, nf, slot_frames, device=device), torch.zeros(n_slots, nf, slot_frames, device=device))
+
+    def step_rows(self, y_len: int) -> int:
+        """Frames a slot must hold for a request of ``y_len`` valid frames (its folded rows, ``fold_plan``)."""
+        return self._rt.ready().fold_rows(max(int(y_len), 1), self.fold_align)
+
+    @torch.inference_mode()
+    def step_prepare(self, pool: "StepPool", slot: int, mu: torch.Tensor, t_len: int) -> None:
+        """Put a request at t = 0 into ``slot``: ``mu`` [n_feats, >= t_len] is its row of ``align_pool`` and ``t_len`` its own padded
+        length; the noise is ``noise_per_request``'s draw for it (the seed-42 draw of shape [1, n_feats, t_len]).  Whatever the
+        slot held before is overwritten."""
+        w = min(int(t_len), pool.z.shape[2], mu.shape[-1])
+        noise = self.noise(mu[None, :, :int(t_len)])[0, :, :w]
+        pool.z[slot].zero_()
+        pool.mu[slot].zero_()
+        pool.mu[slot, :, :w].copy_(mu[:, :w])
+        pool.z[slot, :, :w].copy_(noise + mu[:, :w] if self.use_mu_prior else noise)
+
+    @torch.inference_mode()
+    def step_advance(self, pool: "StepPool", slots, t0, t1, y_lengths, t_len, solver: Optional[str] = None) -> None:
+        """One solver step for the requests in ``slots`` (host ints), request i over its own grid interval (t0[i], t1[i]) with
+        ``y_lengths[i]`` valid frames and the padded length ``t_len[i]`` (per-request padding), in place on the pool.  All host
+        sequences: they travel to the device as one buffer."""
+        import numpy as np
+        hip = self._rt.ready()
+        B = len(slots)
+        y_max = max(max(int(v) for v in y_lengths), 1)
+        t_fold = hip.fold_rows(y_max, self.fold_align)
+        # one host -> device copy per step: y_lengths (int64) | slots | t_len (int32) | t0 | t1 (fp32)
+        buf = np.empty(24 * B, dtype=np.uint8)
+        buf[:8 * B].view(np.int64)[:] = np.asarray(y_lengths, dtype=np.int64)
+        buf[8 * B:12 * B].view(np.int32)[:] = np.asarray(slots, dtype=np.int32)
+        buf[12 * B:16 * B].view(np.int32)[:] = np.asarray(t_len, dtype=np.int32)
+        buf[16 * B:20 * B].view(np.float32)[:] = np.asarray(t0, dtype=np.float32)
+        buf[20 * B:].view(np.float32)[:] = np.asarray(t1, dtype=np.float32)
+        d = torch.from_numpy(buf).pin_memory().to(pool.z.device, non_blocking=True)     # (pinned: the host does not wait for the stream)
+        hip.set_frame_limits(d[12 * B:16 * B].view(torch.int32))
+        try:
+            hip.cfm_step(pool.z, pool.mu, list(slots), d[16 * B:20 * B].view(torch.float32), d[20 * B:].view(torch.float32),
+                         d[:8 * B].view(torch.int64), y_max, t_fold, solver or self.solver, slots_dev=d[8 * B:12 * B].view(torch.int32))
+        finally:
+            hip.set_frame_limits(None)
+
+    def step_read(self, pool: "StepPool", slot: int, y_len: int, out_scale: float = 1.0, out_shift: float = 0.0) -> torch.Tensor:
+        """``state[:, :y_len] * out_scale + out_shift`` of a slot (a new tensor: the slot may be given away)."""
+        return pool.z[slot, :, :int(y_len)] * out_scale + out_shift
 
     def solve(self, x, t_span, mu, mask):
         return self._rt.ready().cfm_solve(x, mu, mask, t_span, self.solver)

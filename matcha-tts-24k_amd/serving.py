@@ -68,7 +68,8 @@ class SpeechService:
     """``await service.speak(text, voice, speed, steps, solver)`` -> 1-D waveform tensor on the host.
 
     ``phonemize(text, language) -> list of phoneme ids`` is the reference's front end (``process_text``); ``batcher`` a
-    ``FrameBudgetBatcher`` built with ``vocoder=`` so that results carry ``"audio"``."""
+    ``FrameBudgetBatcher`` or a ``StepBatcher`` (same ``submit`` contract; the second schedules at the solver step, so requests with
+    different ``steps`` share launches) built with ``vocoder=`` so that results carry ``"audio"``."""
 
     def __init__(self, batcher, phonemize: Callable[[str, str], Sequence[int]], max_text_length: int = MAX_TEXT_LENGTH):
         self.batcher = batcher

@@ -88,6 +88,8 @@ def run_level(batcher, inference, hp, users, min_seconds, seed, time_scale=1.0, 
         t.start()
     time.sleep(warm_seconds)
     b0, busy0, t0 = batcher.batches_run, batcher.busy_s, time.monotonic()
+    us0 = getattr(batcher, "utterance_steps", None)          # StepBatcher: a "batch" is one solver step
+    ph0 = dict(getattr(batcher, "phase_s", {}))
     while True:
         time.sleep(0.25)
         el = time.monotonic() - t0
@@ -98,19 +100,22 @@ def run_level(batcher, inference, hp, users, min_seconds, seed, time_scale=1.0, 
     state["stop"] = True
     el = time.monotonic() - t0
     nb, busy = max(batcher.batches_run - b0, 1), batcher.busy_s - busy0
+    ph1 = dict(getattr(batcher, "phase_s", {}))              # (with busy: the worker goes on serving while the users are joined)
     for t in threads:
         t.join(timeout=30)
     with lock:
         n = len(lat)
-        return {"users": users, "time_scale": time_scale, "equivalent_users": round(users / time_scale), "seconds": round(el, 1),
-                "requests": n, "requests_per_s": round(n / el, 2), "mean_batch": round(n / nb, 2),
+        mean_batch = n / nb if us0 is None else (batcher.utterance_steps - us0) / nb
+        phases = {"worker_phase_fraction": {k: round((v - ph0[k]) / el, 3) for k, v in ph1.items()}} if ph0 else {}
+        return {**phases, "users": users, "time_scale": time_scale, "equivalent_users": round(users / time_scale), "seconds": round(el, 1),
+                "requests": n, "requests_per_s": round(n / el, 2), "mean_batch": round(mean_batch, 2),
                 "p50_latency_s": percentile(lat, 0.5), "p95_latency_s": percentile(lat, 0.95),
                 "p50_latency_per_audio_s": percentile(lat_per_s, 0.5), "p95_latency_per_audio_s": percentile(lat_per_s, 0.95),
                 "audio_s_per_s": round(sum(audio_s) / el, 1), "mean_audio_s": round(sum(audio_s) / max(n, 1), 2),
                 "worker_busy_fraction": round(min(busy / el, 1.0), 3)}
 
 
-def build(dev, with_vocoder=True, n_spks=15, max_batch=32, max_tokens=16384, max_wait_ms=2.0):
+def build(dev, with_vocoder=True, n_spks=15, max_batch=32, max_tokens=16384, max_wait_ms=2.0, batcher="frame"):
     hparams = importlib.import_module(PKG + ".hparams")
     synthetic = importlib.import_module(PKG + ".synthetic")
     inference = importlib.import_module(PKG + ".inference")
@@ -120,7 +125,10 @@ def build(dev, with_vocoder=True, n_spks=15, max_batch=32, max_tokens=16384, max
     model.load_state_dict(synthetic.make_state_dict(hp, seed=7), strict=True)
     model = model.to(dev).eval()
     vocoder = inference.load_vocoder("vocos", state_dict=synthetic.make_vocos_state_dict(seed=11)) if with_vocoder else None
-    b = batcher_mod.FrameBudgetBatcher(model, max_batch=max_batch, max_tokens=max_tokens, max_wait_ms=max_wait_ms, vocoder=vocoder)
+    if batcher == "step":        # scheduled at the solver step: requests join and leave a running solve (mean_batch = utterances per step)
+        b = batcher_mod.StepBatcher(model, max_batch=max_batch, max_tokens=max_tokens, vocoder=vocoder)
+    else:
+        b = batcher_mod.FrameBudgetBatcher(model, max_batch=max_batch, max_tokens=max_tokens, max_wait_ms=max_wait_ms, vocoder=vocoder)
     return hp, inference, model, b
 
 
@@ -135,9 +143,11 @@ def main():
     ap.add_argument("--max-batch", type=int, default=32)
     ap.add_argument("--max-wait-ms", type=float, default=2.0)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--batcher", choices=("frame", "step"), default="frame",
+                    help="frame: FrameBudgetBatcher (a batch runs its whole solve); step: StepBatcher (requests join and leave at every solver step)")
     args = ap.parse_args()
     dev = torch.device("cuda")
-    hp, inference, model, batcher = build(dev, not args.no_vocoder, max_batch=args.max_batch, max_wait_ms=args.max_wait_ms)
+    hp, inference, model, batcher = build(dev, not args.no_vocoder, max_batch=args.max_batch, max_wait_ms=args.max_wait_ms, batcher=args.batcher)
     rows = []
     try:
         # warm-up outside every window: first-use costs (workspace growth, lazily configured kernels, graph captures of the common
@@ -149,7 +159,7 @@ def main():
             r = run_level(batcher, inference, hp, int(u), args.seconds, args.seed, time_scale=float(ts), min_requests=args.min_requests,
                           max_seconds=args.max_seconds)
             r.update(config="configs[4]: closed-loop users (reference psr/load_test.py), 33 TEXT_SAMPLES lengths x 2.3 tokens/char, "
-                            f"midpoint/4, dynamic batching max_batch={args.max_batch}, per-request padding, "
+                            f"midpoint/4, dynamic batching ({args.batcher}) max_batch={args.max_batch}, per-request padding, "
                             + ("Vocos head + trim on device" if not args.no_vocoder else "mel only"),
                      data="synthetic ids, random-init weights", n_gpus=1)
             rows.append(r)
