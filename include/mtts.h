@@ -344,6 +344,89 @@ int mtts_tblock_chain_h16_timed(const float* d_att, const float* d_x, int M, int
                                 int bf16, int qb, int ch, int pf_wgs, float* d_x_out, float* d_qkv_out, void* d_scratch, void* stream,
                                 int repeat, float* h_ms);
 
+/* ---- The estimator's other kernels in the 16-bit storage modes (mtts_set_arithmetic 16 / 17), one unit entry per kernel: the
+ * one-plane ("H16") instantiations of csrc/gemm_p16.hip (MODE 2 fp16 / 3 bfloat16), csrc/attention_f32.hip (HALF, BF),
+ * gn_apply_kernel's H16 store and the fp32 <-> H16 conversions.  An H16 image is ONE plane of 16-bit values, rows of C values
+ * (C % 64 == 0: a 128-byte line holds 64 channels).  fp32 rows in are rounded to images by the library's conversion kernel (round
+ * to nearest even; fp16 clamps to +-65504 first and raises the range flag, bfloat16 keeps the fp32 range and never raises it);
+ * images out come back widened to fp32, i.e. exactly the 16-bit values the kernel stored.  bf16 != 0: bfloat16 planes, else fp16.
+ * d_range_flag (may be NULL): one device word, OR-ed with 1 when a value an fp16 producer stores lies beyond +-65504 (the stored
+ * value is the clamp); the caller clears it.  Host code only: every kernel launched is an instantiation the model launches. */
+
+/* Name of the kernel instantiation the last launcher call on this thread chose, as rocprofv3 prints it ("" when untagged):
+ * "gemm_p16_kernel<BM, LN, stages, MODE, M16, GN, KS>", "attention_f32_kernel<NW, P16, ONE, HALF, BF, KR>".  Host only. */
+const char* mtts_last_kernel_tag(void);
+
+/* Host only: an fp32 panel of n values as the 16-bit weight plane of these modes (fp16: clamp to +-65504, then round to nearest
+ * even; bfloat16: round to nearest even), same element order.  What the packer stores beside every panel. */
+int mtts_panel_h16_host(const float* h_panel, int64_t n, int bf16, uint16_t* h_plane);
+
+/* fp32 rows [M][ld] -> H16 image d_image [M][ld16 values] (times d_mask[row] when given, BEFORE rounding; columns [C_valid, C) are
+ * written as zeros) -> fp32 rows d_out [M][C].  d_image is the caller's, so the stored bits can be compared. */
+int mtts_to_h16_roundtrip(const float* d_x, int ld, const float* d_mask, int M, int C, int C_valid, int ld16, int bf16, void* d_image,
+                          float* d_out, unsigned int* d_range_flag, void* stream);
+
+/* H16 GEMM: the counterpart of mtts_gemm_p16 with every epilogue feature the decoder uses in these modes.  The argument block
+ * mirrors the kernel interface (csrc/kernels.h GemmArgs); pointers named d_ are device memory, h_ host memory, all optional ones
+ * may be NULL.  Refused before any launch (-1, mtts_last_error): C or c1 not a multiple of 64, bf16 without half16, half16 unset,
+ * res16 together with res, gn_stats with anything but a bias-only epilogue, null buffers. */
+typedef struct mtts_gemm_h16_args {
+    /* A operand: fp32 rows [B*T_in][lda], rounded to an H16 image (times d_a_mask[row] first).  c1 > 0: the last c1 channels form a
+     * second channel segment (the up path's skip concat: GemmArgs::a16_1 / c1) */
+    const float* d_a; int32_t lda; int32_t C; int32_t c1; const float* d_a_mask;
+    int32_t B, T_in, T_out, ntaps; const int32_t* h_tap_off; int32_t in_stride;      /* as mtts_gemm_f32 */
+    /* LayerNorm in the epilogue (ntaps == 1): mean / rstd arrays, or partial moments [rows][a_nparts][2] (a d_stats_out) */
+    const float* d_a_mean; const float* d_a_rstd; const float* d_a_part; int32_t a_nparts;
+    /* B operand: the UNPACKED torch weight on the host, Linear [N][C] or Conv1d [N][C][ntaps]; packed, rounded to the 16-bit plane
+     * (mtts_panel_h16_host) and summed per row (LayerNorm algebra, sums of the ROUNDED weights) here */
+    const float* h_w; const float* d_bias; int32_t N;
+    int32_t act; const float* d_p0; const float* d_p1;                                /* as mtts_gemm_f32 */
+    const float* d_res; int32_t ldr;                                                 /* fp32 residual rows */
+    /* residual as an H16 image: 1 = a separate image made from d_res16_f32 [out rows][N]; 2 = IN PLACE, the output image itself
+     * (GemmArgs::res16 == out16, the residual-stream update; needs out16_preload) */
+    int32_t res16_mode; const float* d_res16_f32;
+    const float* d_out_mask; float out_scale;
+    const float* d_out16_mask;                                                      /* multiplies the H16 copy only */
+    float* d_out;                                                                   /* fp32 result [out rows][N] or NULL */
+    /* the H16 result widened to fp32 [out rows][N] or NULL.  out16_preload != 0: the image is first filled from this buffer
+     * (lossless for values of the 16-bit type), so rows a launch does not write keep their value across calls */
+    float* d_out16_f32; int32_t out16_preload;
+    /* output row = b * out_T + t * out_stride + out_off (out_T == 0: plain rows); out rows = B * out_T */
+    int32_t out_T, out_stride, out_off;
+    float* d_stats_out;                                                             /* [out rows][N/64][2] LayerNorm moments */
+    /* GroupNorm statistics from the epilogue (GemmArgs::gn_stats): entries of 4 floats per wave tile, part and group slice;
+     * 2 * ceil(M / wave_rows + 1) * (N/64) * 2 entries at most.  d_gn_nrows [B] or NULL */
+    float* d_gn_stats; int32_t gn_groups; const int32_t* d_gn_nrows;
+    /* Block1D tail in the epilogue (GemmArgs::gnr_*): out += Mish(GroupNorm(d_gnr_y)) * d_gnr_mask from a producer's d_gn_stats */
+    const float* d_gnr_y; const float* d_gnr_stats; int32_t gnr_tile_rows, gnr_groups;
+    const float* d_gnr_gamma; const float* d_gnr_beta; const float* d_gnr_mask; float gnr_eps;
+    const int32_t* d_gnr_nextra; const float* d_gnr_bias_stats;
+    int32_t force_bm;                                                               /* 0, 64 or 128 */
+    int32_t half16, bf16;                                                           /* half16 must be 1 */
+    uint32_t* d_range_flag;
+    /* written by the call: the instantiation launched and the rows of its wave tile (what a gn_stats consumer is told) */
+    int32_t wave_rows; char tag[124];
+} mtts_gemm_h16_args;
+int64_t mtts_gemm_h16_scratch_bytes(const mtts_gemm_h16_args* g);
+int mtts_gemm_h16(mtts_gemm_h16_args* g, void* d_scratch, void* stream);
+/* Host only: rows of the wave tile the launcher will choose for these shapes (32 or 64). */
+int mtts_gemm_h16_wave_rows(int B, int T_out, int N, int force_bm);
+
+/* H16 attention: as mtts_attention_p16 on H16 images of q|k|v and of the output.  d_klen [B] (may be NULL): keys of utterance b
+ * are rows [0, klen[b]); with folded padding d_mask then holds the additive key bias itself (ln(n_pad) on the one row that stands
+ * for n_pad padded frames).  d_scratch >= 8 * B*T*H*64 bytes.  The kernel rounds probabilities and the output to 16 bits. */
+int mtts_attention_h16(const float* d_qkv, const float* d_mask, const int* d_klen, int B, int T, int H, int D, float scale, int mask_mode,
+                       int bf16, float* d_out, unsigned int* d_range_flag, void* d_scratch, void* stream);
+
+/* GroupNorm + Mish + mask [+ chbias, mask] written as an H16 image (d_out16_f32, times d_out16_mask[row]) and optionally as fp32
+ * rows (d_out).  Statistics: d_tile_stats / tile_rows (a mtts_gemm_h16 d_gn_stats and its wave_rows), or a statistics pass over
+ * d_y (d_nrows [B]: rows that enter it).  d_nextra / d_bias_stats: folded padding, as GnApplyArgs. */
+int64_t mtts_groupnorm_h16_scratch_bytes(int B, int T, int C, int G);
+int mtts_groupnorm_mish_h16(const float* d_y, const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias,
+                            int chbias_stride, int B, int T, int C, int G, float eps, const float* d_tile_stats, int tile_rows,
+                            const int* d_nrows, const int* d_nextra, const float* d_bias_stats, const float* d_out16_mask, int bf16,
+                            float* d_out, float* d_out16_f32, unsigned int* d_range_flag, void* d_scratch, void* stream);
+
 /* Row statistics for LayerNorm over C (biased variance, eps inside rsqrt): mean[M], rstd[M]. */
 int mtts_row_stats(const float* d_x, int M, int C, int ld, float eps, float* d_mean, float* d_rstd, void* stream);
 

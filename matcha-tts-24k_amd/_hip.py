@@ -32,6 +32,33 @@ class MttsConfig(C.Structure):
             "dec_head_dim", "dec_heads", "dec_n_blocks", "dec_mid_blocks")]
 
 
+class MttsGemmH16Args(C.Structure):
+    """include/mtts.h mtts_gemm_h16_args, field for field."""
+    _fields_ = [
+        ("d_a", C.c_void_p), ("lda", C.c_int32), ("C", C.c_int32), ("c1", C.c_int32), ("d_a_mask", C.c_void_p),
+        ("B", C.c_int32), ("T_in", C.c_int32), ("T_out", C.c_int32), ("ntaps", C.c_int32), ("h_tap_off", C.c_void_p),
+        ("in_stride", C.c_int32),
+        ("d_a_mean", C.c_void_p), ("d_a_rstd", C.c_void_p), ("d_a_part", C.c_void_p), ("a_nparts", C.c_int32),
+        ("h_w", C.c_void_p), ("d_bias", C.c_void_p), ("N", C.c_int32),
+        ("act", C.c_int32), ("d_p0", C.c_void_p), ("d_p1", C.c_void_p),
+        ("d_res", C.c_void_p), ("ldr", C.c_int32),
+        ("res16_mode", C.c_int32), ("d_res16_f32", C.c_void_p),
+        ("d_out_mask", C.c_void_p), ("out_scale", C.c_float),
+        ("d_out16_mask", C.c_void_p),
+        ("d_out", C.c_void_p),
+        ("d_out16_f32", C.c_void_p), ("out16_preload", C.c_int32),
+        ("out_T", C.c_int32), ("out_stride", C.c_int32), ("out_off", C.c_int32),
+        ("d_stats_out", C.c_void_p),
+        ("d_gn_stats", C.c_void_p), ("gn_groups", C.c_int32), ("d_gn_nrows", C.c_void_p),
+        ("d_gnr_y", C.c_void_p), ("d_gnr_stats", C.c_void_p), ("gnr_tile_rows", C.c_int32), ("gnr_groups", C.c_int32),
+        ("d_gnr_gamma", C.c_void_p), ("d_gnr_beta", C.c_void_p), ("d_gnr_mask", C.c_void_p), ("gnr_eps", C.c_float),
+        ("d_gnr_nextra", C.c_void_p), ("d_gnr_bias_stats", C.c_void_p),
+        ("force_bm", C.c_int32),
+        ("half16", C.c_int32), ("bf16", C.c_int32),
+        ("d_range_flag", C.c_void_p),
+        ("wave_rows", C.c_int32), ("tag", C.c_char * 124)]
+
+
 def _deps(src: Path, seen=None):
     """The source and the local headers it includes, transitively (quoted #include lines)."""
     import re
@@ -174,6 +201,16 @@ def load() -> C.CDLL:
         "mtts_tblock_chain_h16": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
         "mtts_tblock_chain_h16_timed": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp,
                                               i32, C.POINTER(C.c_float)]),
+        "mtts_last_kernel_tag": (C.c_char_p, []),
+        "mtts_panel_h16_host": (i32, [vp, i64, i32, vp]),
+        "mtts_to_h16_roundtrip": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "mtts_gemm_h16_scratch_bytes": (i64, [C.POINTER(MttsGemmH16Args)]),
+        "mtts_gemm_h16": (i32, [C.POINTER(MttsGemmH16Args), vp, vp]),
+        "mtts_gemm_h16_wave_rows": (i32, [i32, i32, i32, i32]),
+        "mtts_attention_h16": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp]),
+        "mtts_groupnorm_h16_scratch_bytes": (i64, [i32, i32, i32, i32]),
+        "mtts_groupnorm_mish_h16": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp,
+                                          vp, vp]),
         "mtts_row_stats": (i32, [vp, i32, i32, i32, f32, vp, vp, vp]),
         "mtts_channel_layernorm": (i32, [vp, i32, i32, i32, vp, vp, f32, i32, vp, vp, vp, vp]),
         "mtts_groupnorm_scratch_bytes": (i64, [i32, i32, i32]),
@@ -885,6 +922,131 @@ def tblock_chain_h16(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, b
     if repeat:
         return x_out, qkv, ms.value
     return x_out, qkv
+
+
+def last_kernel_tag() -> str:
+    """The kernel instantiation the last launcher call on this thread chose (include/mtts.h mtts_last_kernel_tag)."""
+    return load().mtts_last_kernel_tag().decode()
+
+
+def panel_h16_host(panel, bf16=False):
+    """Host only: an fp32 array as the 16-bit weight plane of the storage modes (uint16 bits, same shape)."""
+    lib = load()
+    a = np.ascontiguousarray(panel, dtype=np.float32)
+    out = np.empty(a.shape, dtype=np.uint16)
+    check(lib.mtts_panel_h16_host(a.ctypes.data, a.size, int(bool(bf16)), out.ctypes.data))
+    return out
+
+
+def _flag(device):
+    return torch.zeros(1, dtype=torch.int32, device=device)
+
+
+def to_h16_roundtrip(x, mask=None, *, C_valid=None, ld16=None, bf16=False, Cc=None):
+    """fp32 rows -> H16 image -> fp32 rows (include/mtts.h mtts_to_h16_roundtrip).  Returns a dict: ``out`` [M, C] fp32, ``bits``
+    [M, ld16] int16 (the image as stored; columns beyond C are untouched 0x7e7e fill), ``flag`` (the range-flag word)."""
+    lib = load()
+    M = x.shape[0]
+    Cc = x.shape[1] if Cc is None else Cc
+    C_valid = Cc if C_valid is None else C_valid
+    ld16 = Cc if ld16 is None else ld16
+    image = torch.full((M, ld16), 0x7e7e, dtype=torch.int16, device=x.device)
+    out = torch.empty(M, Cc, dtype=torch.float32, device=x.device)
+    flag = _flag(x.device)
+    check(lib.mtts_to_h16_roundtrip(ptr(x), x.stride(0), ptr(mask), M, Cc, C_valid, ld16, int(bool(bf16)), ptr(image), ptr(out), ptr(flag),
+                                    stream_ptr()))
+    return {"out": out, "bits": image, "flag": int(flag.item())}
+
+
+def gemm_h16(a, w, bias=None, *, B, T_in, T_out=None, tap_off=None, in_stride=1, c1=0, a_mask=None, a_mean=None, a_rstd=None, a_part=None,
+             act=0, p0=None, p1=None, res=None, res16=None, inplace=None, out_mask=None, out_scale=1.0, out16_mask=None,
+             want_f32=True, want_h16=False, out=None, out16=None, out_T=0, out_stride=1, out_off=0, stats_out=False, gn_groups=0,
+             gn_nrows=None, gnr=None, force_bm=0, bf16=False, half16=True):
+    """H16 GEMM (csrc/gemm_p16.hip MODE 2 / 3; include/mtts.h mtts_gemm_h16).  a [B*T_in, C] fp32 is rounded to its H16 image first; w
+    Linear [N, C] or Conv1d [N, C, k] anywhere.  ``res16``: residual rows that travel as an H16 image; ``inplace``: rows [out rows, N]
+    that are BOTH the residual image and the output image (the residual-stream update).  ``out`` / ``out16``: buffers of an earlier
+    call to write into (strided output rows).  ``gnr``: dict(y, stats, tile_rows, groups, gamma, beta, mask[, nextra, bias_stats,
+    eps]) = the Block1D tail.  Returns a dict: out, out16, stats, gn_stats, wave_rows, tag, flag."""
+    lib = load()
+    dev = a.device
+    N, Cc = w.shape[0], w.shape[1]
+    ntaps = w.shape[2] if w.dim() == 3 else 1
+    T_out = T_in if T_out is None else T_out
+    rows = B * (out_T if out_T else T_out)
+    taps = (C.c_int32 * ntaps)(*(tap_off if tap_off is not None else [j - ntaps // 2 for j in range(ntaps)]))
+    hw, hw_ptr = _host(w)
+    g = MttsGemmH16Args()
+    g.d_a, g.lda, g.C, g.c1, g.d_a_mask = ptr(a), a.stride(0), Cc, c1, ptr(a_mask)
+    g.B, g.T_in, g.T_out, g.ntaps, g.h_tap_off, g.in_stride = B, T_in, T_out, ntaps, C.cast(taps, C.c_void_p), in_stride
+    g.d_a_mean, g.d_a_rstd, g.d_a_part, g.a_nparts = ptr(a_mean), ptr(a_rstd), ptr(a_part), a_part.shape[1] if a_part is not None else 0
+    g.h_w, g.d_bias, g.N = hw_ptr, ptr(bias), N
+    g.act, g.d_p0, g.d_p1 = act, ptr(p0), ptr(p1)
+    g.d_res, g.ldr = ptr(res), res.shape[1] if res is not None else 0
+    if out is None and want_f32:
+        out = torch.empty(rows, N, dtype=torch.float32, device=dev)
+    preload = out16 is not None
+    if inplace is not None:
+        out16, preload = inplace.clone(), True
+        g.res16_mode = 2
+    elif res16 is not None:
+        g.res16_mode, g.d_res16_f32 = 1, ptr(res16)
+    if out16 is None and want_h16:
+        out16 = torch.empty(rows, N, dtype=torch.float32, device=dev)
+    g.d_out_mask, g.out_scale, g.d_out16_mask = ptr(out_mask), float(out_scale), ptr(out16_mask)
+    g.d_out, g.d_out16_f32, g.out16_preload = ptr(out), ptr(out16), int(preload)
+    g.out_T, g.out_stride, g.out_off = out_T, out_stride, out_off
+    stats = torch.empty(rows, N // 64, 2, dtype=torch.float32, device=dev) if stats_out else None
+    g.d_stats_out = ptr(stats)
+    gn_stats = None
+    if gn_groups:
+        gn_stats = torch.zeros(2 * ((B * T_out + 31) // 32 + 1) * (N // 64) * 2, 4, dtype=torch.float32, device=dev)
+        g.d_gn_stats, g.gn_groups, g.d_gn_nrows = ptr(gn_stats), gn_groups, ptr(gn_nrows)
+    if gnr is not None:
+        g.d_gnr_y, g.d_gnr_stats, g.gnr_tile_rows, g.gnr_groups = ptr(gnr["y"]), ptr(gnr["stats"]), gnr["tile_rows"], gnr["groups"]
+        g.d_gnr_gamma, g.d_gnr_beta, g.d_gnr_mask, g.gnr_eps = ptr(gnr["gamma"]), ptr(gnr["beta"]), ptr(gnr["mask"]), float(gnr.get("eps", 1e-5))
+        g.d_gnr_nextra, g.d_gnr_bias_stats = ptr(gnr.get("nextra")), ptr(gnr.get("bias_stats"))
+    g.force_bm, g.half16, g.bf16 = force_bm, int(bool(half16)), int(bool(bf16))
+    flag = _flag(dev)
+    g.d_range_flag = ptr(flag)
+    n = lib.mtts_gemm_h16_scratch_bytes(C.byref(g))
+    if n < 0:
+        check(-1)
+    scratch = torch.empty(n, dtype=torch.uint8, device=dev)
+    check(lib.mtts_gemm_h16(C.byref(g), scratch.data_ptr(), stream_ptr()))
+    return {"out": out, "out16": out16, "stats": stats, "gn_stats": gn_stats, "wave_rows": g.wave_rows, "tag": g.tag.decode(),
+            "flag": int(flag.item())}
+
+
+def attention_h16(qkv, mask, B, T, H, D, scale, mask_mode=0, *, klen=None, bf16=False):
+    """H16 attention (csrc/attention_f32.hip HALF / BF; include/mtts.h mtts_attention_h16).  Returns a dict: out, tag, flag."""
+    lib = load()
+    out = torch.empty(B * T, H * D, dtype=torch.float32, device=qkv.device)
+    scratch = torch.empty(8 * B * T * H * D + 256, dtype=torch.uint8, device=qkv.device)
+    flag = _flag(qkv.device)
+    check(lib.mtts_attention_h16(ptr(qkv), ptr(mask), ptr(klen), B, T, H, D, float(scale), mask_mode, int(bool(bf16)), ptr(out), ptr(flag),
+                                 scratch.data_ptr(), stream_ptr()))
+    tag = last_kernel_tag()
+    return {"out": out, "tag": tag, "flag": int(flag.item())}
+
+
+def groupnorm_mish_h16(y, gamma, beta, mask, B, T, *, G=8, chbias=None, tile_stats=None, tile_rows=0, nrows=None, nextra=None,
+                       bias_stats=None, out16_mask=None, bf16=False, want_f32=True, eps=1e-5):
+    """GroupNorm + Mish + mask [+ chbias, mask] with an H16 image out (gn_apply_kernel's H16 store; mtts_groupnorm_mish_h16).
+    chbias [B, stride >= C] or [C].  Returns a dict: out (fp32 rows), out16 (the image widened), flag."""
+    lib = load()
+    Cc = y.shape[1]
+    n = lib.mtts_groupnorm_h16_scratch_bytes(B, T, Cc, G)
+    if n < 0:
+        check(-1)
+    scratch = torch.empty(n, dtype=torch.uint8, device=y.device)
+    out = torch.empty_like(y) if want_f32 else None
+    out16 = torch.empty_like(y)
+    flag = _flag(y.device)
+    check(lib.mtts_groupnorm_mish_h16(ptr(y), ptr(gamma), ptr(beta), ptr(mask), ptr(chbias),
+                                      chbias.shape[1] if chbias is not None and chbias.dim() == 2 else 0, B, T, Cc, G, float(eps),
+                                      ptr(tile_stats), tile_rows, ptr(nrows), ptr(nextra), ptr(bias_stats), ptr(out16_mask), int(bool(bf16)),
+                                      ptr(out), ptr(out16), ptr(flag), scratch.data_ptr(), stream_ptr()))
+    return {"out": out, "out16": out16, "flag": int(flag.item())}
 
 
 def attention_f32(qkv, mask, B, T, H, D, scale, mask_mode):
