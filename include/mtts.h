@@ -156,6 +156,25 @@ int mtts_set_frame_limits(mtts_ctx* ctx, const int32_t* d_t_len);
 int64_t mtts_decoder_workspace_bytes(mtts_ctx* ctx, int B, int T);
 int mtts_decoder_forward(mtts_ctx* ctx, const float* d_x, const float* d_mask, const float* d_mu, float t, int B, int T,
                          float* d_out, void* d_ws, int64_t ws_bytes, void* stream);
+/* The same evaluation with ONE TIME PER UTTERANCE, d_t = device fp32 [B] -- what BASECFM.compute_loss asks of the estimator
+ * (reference flow_matching.py:97, t of shape [B]).  It is mtts_decoder_forward with the time embedding made for B rows and every
+ * ResNet block adding its utterance's own bias row, as mtts_cfm_step does for stages * B rows.  Same workspace size. */
+int mtts_decoder_forward_rows(mtts_ctx* ctx, const float* d_x, const float* d_mask, const float* d_mu, const float* d_t, int B, int T,
+                              float* d_out, void* d_ws, int64_t ws_bytes, void* stream);
+
+/* BASECFM.compute_loss -- reference matcha/models/components/flow_matching.py:65-107 -- forward only, with its two random draws
+ * given by the caller: d_t device fp32 [B] (the reference draws torch.rand([B])), d_noise [B,n_feats,T] (randn_like(x1)).
+ *   x0 = noise (+ mu if add_mu: use_mu_prior);  y_t = (1 - (1 - sigma_min) t_b) * x0 + t_b * x1;  u = x1 - (1 - sigma_min) * x0,
+ *   in that operation order, with (1 - sigma_min) rounded to fp32 once as the reference's Python scalar is;
+ *   pred = estimator(y_t, mask, mu, t): ONE evaluation, utterance b at time t_b;
+ *   d_sq_sum[b] = sum over (f, t) of (pred * mask - u * mask)^2                       (fp32 [B])
+ * The reference's loss is sum_b d_sq_sum[b] / (sum(mask) * n_feats); utterance b's own is d_sq_sum[b] / (sum(mask[b]) * n_feats).
+ * u is never stored; y_t is written straight into the estimator's state rows.  d_pred [B,n_feats,T] or NULL: the estimator's
+ * output (already masked by Decoder.forward), for parity tests.  d_x1, d_mu [B,n_feats,T]; d_mask [B,1,T].
+ * Every sum has a fixed order (no floating-point atomics): two calls give the same bits.  mtts_set_frame_limits composes; range
+ * guard, pair time-out word and mtts_prof_* as for any estimator call.  Workspace: mtts_decoder_workspace_bytes(ctx, B, T). */
+int mtts_cfm_loss(mtts_ctx* ctx, const float* d_x1, const float* d_mu, const float* d_mask, const float* d_noise, const float* d_t,
+                  int add_mu, float sigma_min, int B, int T, float* d_sq_sum, float* d_pred, void* d_ws, int64_t ws_bytes, void* stream);
 
 /* BASECFM.solve -- reference matcha/models/components/flow_matching.py:60-63 + torchdiffeq fixed-grid odeint
  * (euler / midpoint / rk4 = 3/8 rule) over the grid h_t_span[0..n_steps].
@@ -573,6 +592,37 @@ int mtts_mas(const float* d_lp, const float* d_mu_x, const float* d_y, const int
              int B, int F, int Tx, int Tm, int32_t* d_durations, float* d_path, float* d_score, void* d_ws, int64_t ws_bytes,
              void* stream);
 int mtts_mas_status(const void* d_ws, void* stream);
+
+/* ---------------------------------------------------------------- scoring a recording (prior and duration losses) */
+
+/* The two alignment-based sums of the reference's training forward, matcha/models/matcha_tts.py:108-145, per utterance and without
+ * the [Tx, Tm] path: frame y of utterance b belongs to the first token whose inclusive cumulative duration exceeds y (the rule of
+ * mtts_align_pool), so mu_y_fine[:, y] = mu_x[:, tok(y)] is read in place.
+ *   d_prior_sum[b] = sum_{f, y < Tm_b} huber(y_fine[b,f,y] - mu_x[b,f,tok(y)], delta_prior)      (matcha_tts.py:124,143-145)
+ *   d_dur_sum[b]   = sum_{x < Tx_b}    huber(logw[b,x] - log(2 + durations[b,x]), delta_dur)     (matcha_tts.py:117,128)
+ *   huber(d, delta) = 0.5 d^2 for |d| < delta, else delta (|d| - 0.5 delta)                      (torch.nn.functional.huber_loss)
+ * The reference multiplies log(2 + durations) by x_mask and sums over all Tx tokens; logw is already masked by the text encoder, so
+ * a padded token contributes huber(0 - 0) = 0 there and is simply not visited here.  The reference's batch figures are
+ * sum_b d_dur_sum[b] / sum_b Tx_b and sum_b d_prior_sum[b] / sum_b Tm_b (its y_fine_mask has one row, not n_feats).
+ * d_mu_x [B,F,Tx]; d_logw [B,1,Tx]; d_durations int32 [B,Tx] (mtts_mas); d_y_fine [B,F,Tm] normalised fine mel; lengths device int64
+ * [B].  Optional outputs (NULL to skip): d_prior_frame [B,Tm] = the sum over f per frame, d_dur_err [B,Tx] = the signed difference
+ * logw - log(2 + durations); both zero beyond an utterance's lengths.
+ * Everything is fp32 and every sum has a fixed order (no floating-point atomics): an utterance's outputs do not depend on the batch
+ * or the padded shapes it comes in, and two calls give the same bits.  mtts_score_serial_run(which, F, Tx, Tm): the longest chain
+ * of serial additions in the prior (0), duration (1) and flow-matching (2, with F = n_feats, Tm = T) sums, what an error bound
+ * against fp64 is derived from.
+ * The lengths and durations are checked on the device without a host read: an utterance with Tx_b < 1, Tx_b > Tx, Tm_b > Tm,
+ * Tm_b < Tx_b, a negative duration or durations that do not sum to Tm_b gets zero outputs, the others are unaffected, and
+ * mtts_score_status(d_ws, stream) -- the one entry here that waits for the stream -- reports the first such utterance through
+ * mtts_last_error.  No context needed.  Stream-ordered, no allocation.  Workspace: mtts_score_workspace_bytes, 16-byte aligned.
+ * What the host can see (null pointers, B < 1, F < 1, Tx > 1024, Tm < Tx, a threshold <= 0, a small workspace) returns -1. */
+int64_t mtts_score_workspace_bytes(int B, int Tx, int Tm);
+int mtts_score_serial_run(int which, int F, int Tx, int Tm);
+int mtts_score_prior_dur(const float* d_mu_x, const float* d_logw, const int32_t* d_durations, const float* d_y_fine,
+                         const int64_t* d_x_lengths, const int64_t* d_y_fine_lengths, int B, int F, int Tx, int Tm, float delta_prior,
+                         float delta_dur, float* d_prior_sum, float* d_dur_sum, float* d_prior_frame, float* d_dur_err, void* d_ws,
+                         int64_t ws_bytes, void* stream);
+int mtts_score_status(const void* d_ws, void* stream);
 
 /* ---------------------------------------------------------------- arithmetic and its range guard */
 

@@ -19,7 +19,7 @@ from .hparams import PathHParams
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = Path(os.environ["MTTS_HIP_LIB"]) if os.environ.get("MTTS_HIP_LIB") else HERE / "libmtts_hip.so"   # override: A/B of two builds
-SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "style_encoder.hip", "mas.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
+SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "style_encoder.hip", "mas.hip", "score.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
 HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", CSRC / "host.h", HERE.parent / "include" / "mtts.h"]
 SOLVERS = {"euler": 0, "midpoint": 1, "rk4": 2}
 
@@ -246,6 +246,12 @@ def load() -> C.CDLL:
         "mtts_mas_logprior": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "mtts_mas": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
         "mtts_mas_status": (i32, [vp, vp]),
+        "mtts_decoder_forward_rows": (i32, [vp, vp, vp, vp, vp, i32, i32, vp, vp, i64, vp]),
+        "mtts_cfm_loss": (i32, [vp, vp, vp, vp, vp, vp, i32, f32, i32, i32, vp, vp, vp, i64, vp]),
+        "mtts_score_workspace_bytes": (i64, [i32, i32, i32]),
+        "mtts_score_serial_run": (i32, [i32, i32, i32, i32]),
+        "mtts_score_prior_dur": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, i64, vp]),
+        "mtts_score_status": (i32, [vp, vp]),
         "mtts_gemm_terms": (i32, [vp]),
         "mtts_set_arithmetic": (i32, [vp, i32]),
         "mtts_weights_saturate": (i32, [vp]),
@@ -701,6 +707,78 @@ class HipModel:
         check(self.lib.mtts_decoder_forward(self.ctx, ptr(x), ptr(mask), ptr(mu), float(t), B, T, ptr(out), ws.data_ptr(),
                                             ws.numel(), stream_ptr()))
         return out
+
+    def decoder_forward_rows(self, x, mask, mu, t):
+        """``Decoder.forward`` with one time per utterance: ``t`` fp32 [B] (a device tensor, or a host sequence that is copied
+        over) -- mtts_decoder_forward_rows."""
+        x, mask, mu = self._f32(x), self._f32(mask), self._f32(mu)
+        B, nf, T = x.shape
+        t = torch.as_tensor(t, dtype=torch.float32).detach().to(device=x.device).reshape(-1).contiguous()
+        if t.numel() != B:
+            raise ValueError(f"t needs one time per utterance ({B}), got {t.numel()}")
+        out = torch.empty_like(x)
+        ws = self._workspace("dec", B, T)
+        check(self.lib.mtts_decoder_forward_rows(self.ctx, ptr(x), ptr(mask), ptr(mu), ptr(t), B, T, ptr(out), ws.data_ptr(),
+                                                 ws.numel(), stream_ptr()))
+        return out
+
+    def cfm_loss(self, x1, mu, mask, noise, t, add_mu: bool, sigma_min: float, return_pred: bool = False):
+        """The flow-matching loss's per-utterance sums ``sq_sum`` [B] (mtts_cfm_loss): target rows, one estimator evaluation at
+        ``t`` [B], masked squared error against ``u``.  Returns ``(sq_sum, pred or None)``."""
+        x1, mu, mask, noise = self._f32(x1), self._f32(mu), self._f32(mask), self._f32(noise)
+        B, nf, T = x1.shape
+        if mu.shape != x1.shape or noise.shape != x1.shape or mask.shape != (B, 1, T):
+            raise ValueError("cfm_loss: x1, mu, noise must be [B, n_feats, T] and mask [B, 1, T]")
+        t = torch.as_tensor(t, dtype=torch.float32).detach().to(device=x1.device).reshape(-1).contiguous()
+        if t.numel() != B:
+            raise ValueError(f"t needs one time per utterance ({B}), got {t.numel()}")
+        sq = torch.empty(B, dtype=torch.float32, device=x1.device)
+        pred = torch.empty_like(x1) if return_pred else None
+        ws = self._workspace("dec", B, T)
+        check(self.lib.mtts_cfm_loss(self.ctx, ptr(x1), ptr(mu), ptr(mask), ptr(noise), ptr(t), int(bool(add_mu)), float(sigma_min),
+                                     B, T, ptr(sq), ptr(pred), ws.data_ptr(), ws.numel(), stream_ptr()))
+        return sq, pred
+
+    def score_prior_dur(self, mu_x, logw, durations, y_fine, x_lengths, y_fine_lengths, delta_prior: float, delta_dur: float,
+                        return_frames: bool = False, check_lengths: bool = True):
+        """Prior and duration Huber sums per utterance (mtts_score_prior_dur).  Returns ``(prior_sum [B], dur_sum [B], prior_frame
+        [B, Tm] or None, dur_err [B, Tx] or None)``.  ``check_lengths``: read the device's verdict (one synchronisation) and raise
+        ``ValueError``; otherwise call ``score_status`` later."""
+        mu_x, logw, y_fine = self._f32(mu_x), self._f32(logw), self._f32(y_fine)
+        B, F, Tx = mu_x.shape
+        Tm, dev = y_fine.shape[2], mu_x.device
+        if y_fine.shape[:2] != (B, F) or logw.numel() != B * Tx:
+            raise ValueError(f"score_prior_dur: y_fine must be [{B}, {F}, Tm] and logw [{B}, 1, {Tx}]")
+        durations = durations.detach().to(device=dev, dtype=torch.int32).contiguous()
+        if durations.shape != (B, Tx):
+            raise ValueError(f"durations must have shape ({B}, {Tx}), got {tuple(durations.shape)}")
+        xl = x_lengths.detach().to(device=dev, dtype=torch.int64).contiguous()
+        yl = y_fine_lengths.detach().to(device=dev, dtype=torch.int64).contiguous()
+        if xl.shape != (B,) or yl.shape != (B,):
+            raise ValueError("x_lengths and y_fine_lengths need one entry per utterance")
+        n = self.lib.mtts_score_workspace_bytes(B, Tx, Tm)
+        if n < 0:
+            check(-1)
+        if self.device is None:
+            self.device = dev
+        ws = self._grow("score", n)
+        prior = torch.empty(B, dtype=torch.float32, device=dev)
+        dur = torch.empty(B, dtype=torch.float32, device=dev)
+        frame = torch.empty(B, Tm, dtype=torch.float32, device=dev) if return_frames else None
+        err = torch.empty(B, Tx, dtype=torch.float32, device=dev) if return_frames else None
+        check(self.lib.mtts_score_prior_dur(ptr(mu_x), ptr(logw), ptr(durations), ptr(y_fine), ptr(xl), ptr(yl), B, F, Tx, Tm,
+                                            float(delta_prior), float(delta_dur), ptr(prior), ptr(dur), ptr(frame), ptr(err),
+                                            ws.data_ptr(), ws.numel(), stream_ptr()))
+        if check_lengths:
+            self.score_status()
+        return prior, dur, frame, err
+
+    def score_status(self) -> None:
+        """Wait for this stream's latest ``score_prior_dur`` call and raise ``ValueError`` naming the first utterance the device
+        refused (mtts_score_status)."""
+        ws = self._last_ws.get(("score", stream_ptr()))
+        if ws is not None and self.lib.mtts_score_status(ws.data_ptr(), stream_ptr()) != 0:
+            raise ValueError(self.lib.mtts_last_error().decode("utf-8", "replace"))
 
     def fold_rows(self, y_max: int, align: int) -> int:
         """Rows per utterance the folded estimator needs for valid lengths up to y_max (mtts_fold_rows)."""

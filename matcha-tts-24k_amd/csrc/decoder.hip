@@ -611,8 +611,10 @@ int mtts_set_frame_limits(mtts_ctx* c, const int32_t* d_t_len) {
     return 0;
 }
 
-int mtts_decoder_forward(mtts_ctx* c, const float* d_x, const float* d_mask, const float* d_mu, float t, int B, int T,
-                         float* d_out, void* d_ws, int64_t ws_bytes, void* stream) {
+// Decoder.forward with one time for the batch (d_t == null: t) or one per utterance (d_t: device fp32 [B]; the time embedding is
+// made for B rows and every ResNet block adds its utterance's own bias row, as in mtts_cfm_step).
+static int decoder_forward_core(mtts_ctx* c, const float* d_x, const float* d_mask, const float* d_mu, float t, const float* d_t, int B,
+                                int T, float* d_out, void* d_ws, int64_t ws_bytes, void* stream) {
     CTX_GUARD(c);
     RET_IF(check_ready(c));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -627,12 +629,61 @@ int mtts_decoder_forward(mtts_ctx* c, const float* d_x, const float* d_mask, con
     LAUNCH(c, 2, 0, s, launch_fill_cols(d.xmu, B * T, d.ldx, 2 * nf, d.ldx - 2 * nf, 0.f, s));
     LAUNCH(c, 2, 0, s, launch_cf_to_cl(d_x, nullptr, B, nf, T, d.xmu, d.ldx, 0, s));
     LAUNCH(c, 2, 0, s, launch_cf_to_cl(d_mu, nullptr, B, nf, T, d.xmu, d.ldx, nf, s));
-    TimeVals tv;
-    tv.t[0] = t;
-    RET_IF(time_embed(c, d, &tv, nullptr, 1, s));
+    if (d_t) {
+        RET_IF(time_embed(c, d, nullptr, d_t, B, s));
+        d.tb_stride = (int)c->dec.tb_total;
+    } else {
+        TimeVals tv;
+        tv.t[0] = t;
+        RET_IF(time_embed(c, d, &tv, nullptr, 1, s));
+    }
     FinalOut fo{d.vel[0], d.ldv, nullptr, 0, 1.0f};
     RET_IF(decoder_eval(c, d, d.xmu, 0, fo, s));
     LAUNCH(c, 2, 0, s, launch_cl_to_cf(d.vel[0], d.ldv, B, nf, T, d_out, T, 1.0f, 0.0f, s));
+    return 0;
+}
+
+int mtts_decoder_forward(mtts_ctx* c, const float* d_x, const float* d_mask, const float* d_mu, float t, int B, int T,
+                         float* d_out, void* d_ws, int64_t ws_bytes, void* stream) {
+    return decoder_forward_core(c, d_x, d_mask, d_mu, t, nullptr, B, T, d_out, d_ws, ws_bytes, stream);
+}
+
+int mtts_decoder_forward_rows(mtts_ctx* c, const float* d_x, const float* d_mask, const float* d_mu, const float* d_t, int B, int T,
+                              float* d_out, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_x || !d_mask || !d_mu || !d_t || !d_out || !d_ws) { set_error("mtts_decoder_forward_rows: null argument"); return -1; }
+    if (B < 1 || T < 1) { set_error("mtts_decoder_forward_rows: need B >= 1 and T >= 1"); return -1; }
+    return decoder_forward_core(c, d_x, d_mask, d_mu, 0.f, d_t, B, T, d_out, d_ws, ws_bytes, stream);
+}
+
+// BASECFM.compute_loss (reference flow_matching.py:65-107) without its two random draws: the flow-matching input as state rows
+// (cfm_target_kernel), ONE estimator evaluation with utterance b at time d_t[b], and the masked squared error against
+// u = x1 - (1 - sigma_min) x0 per utterance (cfm_loss_kernel; its partials borrow the conv scratch, idle once the estimator is done).
+int mtts_cfm_loss(mtts_ctx* c, const float* d_x1, const float* d_mu, const float* d_mask, const float* d_noise, const float* d_t,
+                  int add_mu, float sigma_min, int B, int T, float* d_sq_sum, float* d_pred, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_x1 || !d_mu || !d_mask || !d_noise || !d_t || !d_sq_sum || !d_ws) { set_error("mtts_cfm_loss: null argument"); return -1; }
+    if (B < 1 || T < 1) { set_error("mtts_cfm_loss: need B >= 1 and T >= 1"); return -1; }
+    if (!(sigma_min >= 0.f) || !(sigma_min < 1.f)) { set_error("mtts_cfm_loss: sigma_min must be in [0, 1)"); return -1; }
+    CTX_GUARD(c);
+    RET_IF(check_ready(c));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    WS ws(d_ws, (size_t)ws_bytes);
+    DecBufs d;
+    RET_IF(plan_decoder(c, B, T, step_time_rows(B), 2, 4, ws, d));
+    if (ws.overflow) { set_error("decoder workspace too small"); return -1; }
+    RET_IF(begin_call(c, d_ws, s));
+    if (c->sw.pair_on) HIP_OK(launch_fill_cols(reinterpret_cast<float*>(d.pair_flag), 1, 512, 0, 512, 0.f, s));
+    const int nf = c->cfg.n_feats;
+    const double elems = (double)B * T * nf;
+    RET_IF(build_frames(c, d, d_mask, nullptr, T, s));
+    LAUNCHB(c, 2, 0, 4.0 * (3.0 * elems + (double)B * T * d.ldx), s,
+            launch_cfm_target(d_x1, d_noise, d_mu, d_t, add_mu, sigma_min, B, nf, T, d.xmu, d.ldx, s));
+    RET_IF(time_embed(c, d, nullptr, d_t, B, s));
+    d.tb_stride = (int)c->dec.tb_total;
+    FinalOut fo{d.vel[0], d.ldv, nullptr, 0, 1.0f};
+    RET_IF(decoder_eval(c, d, d.xmu, 0, fo, s));
+    LAUNCHB(c, 2, 0, 4.0 * ((add_mu ? 3.0 : 2.0) * elems + (double)B * T * d.ldv + (d_pred ? elems : 0.0)), s,
+            launch_cfm_loss(d.vel[0], d.ldv, d_x1, d_noise, d_mu, d_mask, add_mu, sigma_min, B, nf, T, d.Y, d_pred, s));
+    LAUNCH(c, 2, 0, s, launch_cfm_loss_finish(d.Y, B, nf, T, d_sq_sum, s));
     return 0;
 }
 

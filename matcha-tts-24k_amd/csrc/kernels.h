@@ -443,6 +443,17 @@ hipError_t launch_frame_tables(const FrameTableArgs& a, hipStream_t s);
 hipError_t launch_align_pool(const float* mu_x, const int32_t* cum, const int64_t* yfl, int B, int nf, int Tx, int T_pad,
                              float* mu_y, float* y_mask, int64_t* y_len, hipStream_t s);
 
+// ---- flow-matching loss (score.hip; reference flow_matching.py:65-107), one time per utterance in t_b (device [B])
+// dst[b*T + t] = y_t | mu | 0 (rows of ld floats): y_t = (1 - (1 - sigma_min) t_b) x0 + t_b x1, x0 = noise (+ mu)
+hipError_t launch_cfm_target(const float* x1, const float* noise, const float* mu, const float* t_b, int add_mu, float sigma_min, int B,
+                             int C, int T, float* dst, int ld, hipStream_t s);
+// partial[b][tile] = sum of ((vel - u) mask)^2 over a 32 x 32 tile, u = x1 - (1 - sigma_min) x0; pred (optional) = vel as [B, C, T];
+// then sq_sum[b] = the partials in order.  cfm_loss_partials: floats of `partial`.
+int64_t cfm_loss_partials(int B, int C, int T);
+hipError_t launch_cfm_loss(const float* vel, int ldv, const float* x1, const float* noise, const float* mu, const float* mask, int add_mu,
+                           float sigma_min, int B, int C, int T, float* partial, float* pred, hipStream_t s);
+hipError_t launch_cfm_loss_finish(const float* partial, int B, int C, int T, float* sq_sum, hipStream_t s);
+
 // ---- Vocos head (vocos.hip)
 // y = LayerNorm_C(depthwise_conv_k7(x) + bias) * gamma + beta on channels-last rows [B*T, C]; w7 is [7][C].
 // lengths (optional, device [B], frames): utterance b ends at lengths[b]; taps beyond it are zero padding.  Null = T for all.

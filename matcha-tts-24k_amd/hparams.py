@@ -70,6 +70,10 @@ class PathHParams:
     solver: str = "midpoint"
     use_mu_prior: bool = False
     sigma_min: float = 1e-4
+    # Huber thresholds of the training forward's prior and duration losses (reference matcha/models/matcha_tts.py:128,143;
+    # configs/model/matcha.yaml:18-19); only ``MatchaTTSInfer.score`` reads them
+    prior_loss_threshold: float = 0.03
+    duration_loss_threshold: float = 1.0
     encoder: EncoderHParams = field(default_factory=EncoderHParams)
     decoder: DecoderHParams = field(default_factory=DecoderHParams)
 
@@ -99,11 +103,14 @@ class PathHParams:
                          num_mid_blocks=self.decoder.num_mid_blocks, num_heads=self.decoder.num_heads),
             cfm=NS(name="CFM", solver=self.solver, sigma_min=self.sigma_min, use_mu_prior=self.use_mu_prior),
             data_statistics=dict(mel_mean=self.mel_mean, mel_std=self.mel_std),
+            prior_loss_threshold=self.prior_loss_threshold, duration_loss_threshold=self.duration_loss_threshold,
         )
 
 
-def from_reference_kwargs(n_spks, n_feats, encoder, decoder, cfm, data_statistics, spk_emb_dim, **_) -> PathHParams:
-    """Flatten the constructor arguments of reference ``MatchaTTSInfer.__init__`` (inference.py:45)."""
+def from_reference_kwargs(n_spks, n_feats, encoder, decoder, cfm, data_statistics, spk_emb_dim, prior_loss_threshold=None,
+                          duration_loss_threshold=None, **_) -> PathHParams:
+    """Flatten the constructor arguments of reference ``MatchaTTSInfer.__init__`` (inference.py:45) and, when the checkpoint's
+    ``hyper_parameters`` carry them, the two loss thresholds of ``MatchaTTS.__init__`` (matcha_tts.py:29-30)."""
     ep = cfg_get(encoder, "encoder_params")
     dp = cfg_get(encoder, "duration_predictor_params")
     if not cfg_get(ep, "prenet", True):
@@ -138,8 +145,18 @@ def from_reference_kwargs(n_spks, n_feats, encoder, decoder, cfm, data_statistic
         solver=str(cfg_get(cfm, "solver", "midpoint")),
         use_mu_prior=bool(cfg_get(cfm, "use_mu_prior", False)),
         sigma_min=float(cfg_get(cfm, "sigma_min", 1e-4)),
+        prior_loss_threshold=0.03 if prior_loss_threshold is None else float(prior_loss_threshold),
+        duration_loss_threshold=1.0 if duration_loss_threshold is None else float(duration_loss_threshold),
         encoder=enc, decoder=dec,
     )
+
+
+def loss_thresholds(hyper_parameters) -> Tuple[float, float]:
+    """``(prior_loss_threshold, duration_loss_threshold)`` of a checkpoint's ``hyper_parameters`` (dict / DictConfig / namespace);
+    the defaults of reference configs/model/matcha.yaml:18-19 where a key is missing (v20 sets 0.15 / 0.3)."""
+    p = cfg_get(hyper_parameters, "prior_loss_threshold")
+    d = cfg_get(hyper_parameters, "duration_loss_threshold")
+    return (0.03 if p is None else float(p)), (1.0 if d is None else float(d))
 
 
 def prod_v20(n_spks: int = 1) -> PathHParams:
@@ -148,6 +165,7 @@ def prod_v20(n_spks: int = 1) -> PathHParams:
     return PathHParams(
         n_spks=n_spks, n_feats=100, spk_emb_dim=96,
         mel_mean=-4.684777, mel_std=6.512275, solver="euler", use_mu_prior=True,
+        prior_loss_threshold=0.15, duration_loss_threshold=0.3,
         encoder=EncoderHParams(),
         decoder=DecoderHParams(),
     )

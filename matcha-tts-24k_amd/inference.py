@@ -51,9 +51,11 @@ def fix_len_compatibility(length: int, num_downsamplings_in_unet: int = 1) -> in
 class MatchaTTSInfer(nn.Module):
     """Inference model: speaker tables + text encoder + CFM decoder (reference inference.py:44-183)."""
 
-    def __init__(self, n_spks, n_feats, encoder, decoder, cfm, data_statistics, spk_emb_dim, **_):
+    def __init__(self, n_spks, n_feats, encoder, decoder, cfm, data_statistics, spk_emb_dim, prior_loss_threshold=None,
+                 duration_loss_threshold=None, **_):
         super().__init__()
-        hp = from_reference_kwargs(n_spks, n_feats, encoder, decoder, cfm, data_statistics, spk_emb_dim)
+        hp = from_reference_kwargs(n_spks, n_feats, encoder, decoder, cfm, data_statistics, spk_emb_dim,
+                                   prior_loss_threshold=prior_loss_threshold, duration_loss_threshold=duration_loss_threshold)
         self._init_from_hparams(hp)
 
     @classmethod
@@ -324,6 +326,163 @@ class MatchaTTSInfer(nn.Module):
                "mel_fine_lengths": mel_fine_lengths}
         if return_path:
             out["path"] = path
+        return out
+
+    @torch.inference_mode()
+    def score(self, x, x_lengths, audio=None, audio_lengths=None, mel=None, mel_lengths=None, mel_fine=None, mel_fine_lengths=None,
+              speaker=0, voice_mix=None, speaker_embeddings=None, t=None, noise=None, per_request_padding=False, return_frames=False):
+        """How well does this model, with this voice, explain this recording: the three numbers of the reference's training forward
+        (``MatchaTTS.forward``, matcha/models/matcha_tts.py:64-164), forward pass only, on the device.
+
+        ``dur_loss``: Huber distance between the predictor's ``logw`` and ``log(2 + MAS durations)``; ``prior_loss``: Huber distance
+        between the recording's fine mel and ``mu_x`` expanded along the MAS path; ``diff_loss``: the conditional-flow-matching loss
+        of ``BASECFM.compute_loss`` (flow_matching.py:65-107), one estimator evaluation at time ``t[b]`` per utterance.  The Huber
+        thresholds are the checkpoint's (``hp.prior_loss_threshold``, ``hp.duration_loss_threshold``).
+
+        The recording: ``audio`` as for ``align`` -- both mels are extracted (hop 256 and hop 128) and padded as the reference's
+        collate pads them (matcha/data/text_mel_datamodule.py:481-499) -- or ``mel`` [B, n_feats, T] and ``mel_fine`` [B, n_feats,
+        Tm], normalised with this model's mel statistics, with their lengths (default: the whole tensors).  Speaker arguments as
+        for ``synthesise``.  ``t``: [B] (default ``torch.rand``) or a grid [K, B] -- K evaluations with the same ``noise``
+        ([B, n_feats, T], default ``randn``); a single random ``t`` is a very noisy estimate, a fixed grid is what makes two voices
+        comparable.  ``per_request_padding``: the estimator treats every utterance as padded to its own length (one more host read).
+
+        Returns 0-dim ``dur_loss``, ``prior_loss``, ``diff_loss`` with the reference's batch normalisation (``/ sum(x_lengths)``,
+        ``/ sum(y_fine_mask)``, ``/ (sum(y_mask) * n_feats)``; ``diff_loss`` is [K] for a grid), the same three ``*_per_utterance``
+        ([B]; [K, B]), the raw sums ``dur_sum``, ``prior_sum``, ``sq_sum``, ``durations`` (int32 [B, Tx]), ``mas_score`` [B],
+        ``mel_lengths``, ``mel_fine_lengths`` and, with ``return_frames``, ``prior_frame`` [B, Tm] and ``dur_err`` [B, Tx].  One
+        synchronisation per call; ``ValueError`` names an utterance with fewer frames than tokens."""
+        rt = self._rt
+        hip = rt.ready()
+        dev = x.device
+        rec = self._score_recording(x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths)
+        B, nf, T = rec[0].shape
+        if noise is None:
+            noise = torch.randn(B, nf, T, dtype=torch.float32, device=dev)
+        elif tuple(noise.shape) != (B, nf, T):
+            raise ValueError(f"noise must be [{B}, {nf}, {T}] (the padded coarse mel), got {tuple(noise.shape)}")
+        t = torch.rand(B, device=dev) if t is None else torch.as_tensor(t, dtype=torch.float32).to(dev)
+        if t.dim() not in (1, 2) or t.shape[-1] != B:
+            raise ValueError(f"t must be [{B}] or [K, {B}], got {tuple(t.shape)}")
+        args = (x, x_lengths, rec, speaker, voice_mix, speaker_embeddings, t, noise.to(dev), per_request_padding, return_frames)
+        was_wide = rt.use_wide
+        out = self._score(*args)
+        flags = out.pop("_flags")              # (host copy: the stream is already drained, no second wait)
+        if was_wide or hip.gemm_terms() not in (1, 2, 16, 17) or self.range_policy == "ignore":
+            return out
+        if not (hip.weights_saturate() or bool(flags[:2].any())):
+            return out
+        if self.range_policy == "raise":
+            raise FloatingPointError("matcha-tts-24k_amd: an operand left the fp16 range (|x| > 65504) in the default split "
+                                     "arithmetic; set model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
+        rt.use_wide = True                     # sticky, as in synthesise
+        out = self._score(*args)
+        out.pop("_flags", None)
+        return out
+
+    def _score_recording(self, x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths):
+        """(mel [B, nf, T], mel_lengths, mel_fine [B, nf, Tm], mel_fine_lengths, host coarse lengths or None) padded like the
+        reference's collate: T = fix_len_compatibility(longest coarse mel), Tm = 2 T (more only if a given tensor is longer or
+        there are more tokens than that)."""
+        dev = x.device
+        B, Tx = x.shape
+        nf = self.hp.n_feats
+        host_len = None
+        if audio is not None:
+            if mel is not None or mel_fine is not None:
+                raise ValueError("score needs either audio= or mel= and mel_fine=")
+            from . import mel as M
+            from .style import FINE_HOP
+            clips = [audio[b] for b in range(audio.shape[0])] if torch.is_tensor(audio) and audio.dim() == 2 else (
+                [audio] if torch.is_tensor(audio) or isinstance(audio, np.ndarray) else list(audio))
+            if len(clips) != B:
+                raise ValueError(f"score needs one clip per utterance ({B}), got {len(clips)}")
+            clips = [torch.as_tensor(c).to(torch.float32) for c in clips]
+            if any(c.dim() != 1 for c in clips):
+                raise ValueError("a clip is a 1-D waveform (24 kHz mono)")
+            lengths = [int(c.numel()) for c in clips] if audio_lengths is None else [int(v) for v in torch.as_tensor(audio_lengths).tolist()]
+            ld = (max(int(c.numel()) for c in clips) + 3) // 4 * 4
+            wave = torch.zeros(B, ld, dtype=torch.float32, device=dev)
+            for b, c in enumerate(clips):
+                wave[b, :c.numel()].copy_(c)
+            kw = dict(sample_rate=24000, n_mels=nf)
+            mel_fine, mel_fine_lengths = M.extract(wave, lengths, FINE_HOP, self._rt.mel_mean, self._rt.mel_std, **kw)
+            mel, mel_lengths = M.extract(wave, lengths, STD_RES_HOP_LENGTH, self._rt.mel_mean, self._rt.mel_std, **kw)
+            host_len = [n // STD_RES_HOP_LENGTH + 1 for n in lengths]
+        elif mel is None or mel_fine is None:
+            raise ValueError("score needs either audio= or mel= and mel_fine=")
+        for name, m in (("mel", mel), ("mel_fine", mel_fine)):
+            if m.dim() != 3 or m.shape[0] != B or m.shape[1] != nf:
+                raise ValueError(f"{name} must be [{B}, {nf}, T], got {tuple(m.shape)}")
+        mel, mel_fine = mel.to(dev, torch.float32), mel_fine.to(dev, torch.float32)
+        if mel_lengths is None:
+            mel_lengths = torch.full((B,), mel.shape[2], dtype=torch.long, device=dev)
+        if mel_fine_lengths is None:
+            mel_fine_lengths = torch.full((B,), mel_fine.shape[2], dtype=torch.long, device=dev)
+        mel_lengths = torch.as_tensor(mel_lengths).to(device=dev, dtype=torch.long)
+        mel_fine_lengths = torch.as_tensor(mel_fine_lengths).to(device=dev, dtype=torch.long)
+        T = fix_len_compatibility(mel.shape[2])
+        Tm = max(2 * T, mel_fine.shape[2], Tx)
+        if mel.shape[2] < T:
+            mel = torch.nn.functional.pad(mel, (0, T - mel.shape[2]))
+        if mel_fine.shape[2] < Tm:
+            mel_fine = torch.nn.functional.pad(mel_fine, (0, Tm - mel_fine.shape[2]))
+        return mel.contiguous(), mel_lengths, mel_fine.contiguous(), mel_fine_lengths, host_len
+
+    def _score(self, x, x_lengths, rec, speaker, voice_mix, speaker_embeddings, t, noise, per_request_padding, return_frames):
+        hip = self._rt.ready()
+        dev = x.device
+        B, Tx = x.shape
+        mel, mel_lengths, mel_fine, mel_fine_lengths, host_len = rec
+        nf, T = mel.shape[1], mel.shape[2]
+        if speaker_embeddings is not None:
+            e_enc, e_dur = speaker_embeddings
+        elif voice_mix is not None:
+            e_enc, e_dur = self.mix_speakers(voice_mix)
+        else:
+            ids = torch.as_tensor(speaker, dtype=torch.long, device=dev).reshape(-1)
+            e_enc, e_dur = hip.speaker_embedding(0, ids), hip.speaker_embedding(1, ids)
+        if e_enc.shape[0] not in (1, B):
+            raise ValueError("speaker must be an int or a LongTensor with one id per utterance")
+        x_lengths = x_lengths.to(device=dev, dtype=torch.long)
+        hp = self.hp
+        mu_x, logw, x_mask = self.encoder(x, x_lengths, e_enc, e_dur)
+        durations, mas_score, _ = hip.mas(x_lengths, mel_fine_lengths, mu_x=mu_x, y=mel_fine, check_lengths=False)
+        prior_sum, dur_sum, prior_frame, dur_err = hip.score_prior_dur(
+            mu_x, logw, durations, mel_fine, x_lengths, mel_fine_lengths, hp.prior_loss_threshold, hp.duration_loss_threshold,
+            return_frames=return_frames, check_lengths=False)
+        # the coarse mu_y of matcha_tts.py:124,154: (mu_x @ path) pooled k3 s2 p1, from the same durations
+        _, cum, fine_total = hip.durations_given(durations, x_mask, 1.0)
+        mu_y, _, _ = hip.align_pool(mu_x, cum, fine_total, T)
+        y_mask = (torch.arange(T, device=dev)[None, :] < mel_lengths[:, None]).to(torch.float32)[:, None, :]
+        if per_request_padding:
+            own = host_len if host_len is not None else [int(v) for v in mel_lengths.tolist()]
+            hip.set_frame_limits(torch.tensor([min(fix_len_compatibility(max(v, 1)), T) for v in own], dtype=torch.int32, device=dev))
+        flags = None
+        try:
+            sq = []
+            for tk in (t if t.dim() == 2 else t[None]):
+                sq.append(hip.cfm_loss(mel, mu_y, y_mask, noise, tk.contiguous(), self.decoder.use_mu_prior, self.decoder.sigma_min)[0])
+                f = torch.cat([hip.range_flags(), hip.pair_timeouts()])
+                flags = f if flags is None else flags | f
+        finally:
+            if per_request_padding:
+                hip.set_frame_limits(None)
+        sq_sum = torch.stack(sq) if t.dim() == 2 else sq[0]
+        hip.mas_status()                       # the call's one wait; raises ValueError for an utterance the device refused
+        hip.score_status()
+        flags = flags.cpu()
+        if int(flags[2]):
+            raise RuntimeError("matcha-tts-24k_amd: a pair-form chain launch timed out waiting for its partner workgroup (another "
+                               "kernel held CUs during the launch?); set MTTS_CHAIN_PAIR=0")
+        n_tok, n_fine, n_coarse = x_lengths.to(torch.float32), mel_fine_lengths.to(torch.float32), y_mask.sum((1, 2))
+        out = {"dur_loss": dur_sum.sum() / n_tok.sum(), "prior_loss": prior_sum.sum() / n_fine.sum(),
+               "diff_loss": sq_sum.sum(-1) / (n_coarse.sum() * nf),
+               "dur_loss_per_utterance": dur_sum / n_tok, "prior_loss_per_utterance": prior_sum / n_fine,
+               "diff_loss_per_utterance": sq_sum / (n_coarse * nf),
+               "dur_sum": dur_sum, "prior_sum": prior_sum, "sq_sum": sq_sum, "durations": durations, "mas_score": mas_score,
+               "mel_lengths": mel_lengths, "mel_fine_lengths": mel_fine_lengths, "_flags": flags}
+        if return_frames:
+            out["prior_frame"], out["dur_err"] = prior_frame, dur_err
         return out
 
     @torch.inference_mode()

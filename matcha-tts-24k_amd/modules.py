@@ -325,6 +325,23 @@ class CFM(nn.Module):
         """``state[:, :y_len] * out_scale + out_shift`` of a slot (a new tensor: the slot may be given away)."""
         return pool.z[slot, :, :int(y_len)] * out_scale + out_shift
 
+    @torch.inference_mode()
+    def compute_loss(self, x1, mask, mu, t=None, noise=None):
+        """``BASECFM.compute_loss(x1, mask, mu)`` -- reference flow_matching.py:65-107 -- forward only, plus the two injection
+        points: ``t`` [B] (default ``torch.rand([B])``) and ``noise`` (default ``randn_like(x1)``), drawn on the device.  Returns
+        the batch loss ``sum_b sq_sum[b] / (sum(mask) * n_feats)`` as a 0-dim tensor that also carries ``.sq_sum`` [B] and
+        ``.per_utterance`` [B] (each utterance's sum over its own ``sum(mask[b]) * n_feats``)."""
+        hip = self._rt.ready()
+        B, nf, _ = x1.shape
+        t = torch.rand(B, device=x1.device) if t is None else torch.as_tensor(t, dtype=torch.float32).to(x1.device).reshape(-1)
+        noise = torch.randn_like(x1, dtype=torch.float32) if noise is None else noise
+        sq, _ = hip.cfm_loss(x1, mu, mask, noise, t, self.use_mu_prior, self.sigma_min)
+        frames = mask.to(torch.float32).sum((1, 2))
+        loss = sq.sum() / (frames.sum() * nf)
+        loss.sq_sum = sq
+        loss.per_utterance = sq / (frames * nf)
+        return loss
+
     def solve(self, x, t_span, mu, mask):
         return self._rt.ready().cfm_solve(x, mu, mask, t_span, self.solver)
 
