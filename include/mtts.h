@@ -446,6 +446,41 @@ int mtts_groupnorm_mish_h16(const float* d_y, const float* d_gamma, const float*
                             const int* d_nrows, const int* d_nextra, const float* d_bias_stats, const float* d_out16_mask, int bf16,
                             float* d_out, float* d_out16_f32, unsigned int* d_range_flag, void* d_scratch, void* stream);
 
+/* ---- The same kernels in the DEFAULT arithmetic, one unit entry per kernel: the two-plane ("P16") instantiations -- gemm_p16_kernel
+ * MODE 0 (fp16 head + scaled fp16 residual, three products per MAC; fast16 != 0: MODE 1, heads only), the <NW, true, false, false,
+ * false, KR> attention kernels, gn_apply_kernel's two-plane store and the fp32 <-> P16 conversions -- with every argument the decoder
+ * passes.  A P16 image holds, per row and 32-channel group, 32 heads h = fp16(clamp(x, +-65504)) then 32 residuals
+ * l = fp16((clamp(x) - h) * lscale): rows of 2 * C halves (C % 32 == 0), value h + l / lscale.  lscale is 2048 everywhere except the
+ * q|k|v image the attention kernel reads (1).  Images out come back as fp32 h + l / lscale, i.e. exactly the stored pair.
+ * d_range_flag as above.  Host code only: every kernel launched is an instantiation the model launches. */
+
+/* fp32 rows [M][ld] -> P16 image d_image [M][ld16 halves, >= 2 * C] (times d_mask[row] when given, BEFORE the split; columns
+ * [C_valid, C) are written as zeros) -> fp32 rows d_out [M][C].  d_image is the caller's, so the stored bits can be compared. */
+int mtts_to_p16_roundtrip(const float* d_x, int ld, const float* d_mask, int M, int C, int C_valid, int ld16, float lscale, void* d_image,
+                          float* d_out, unsigned int* d_range_flag, void* stream);
+
+/* P16 GEMM on the argument block of mtts_gemm_h16 (half16 and bf16 must be 0; "H16 image" reads "P16 image" throughout, C, c1 and an
+ * image's N are multiples of 32).  A, the residual image and a preloaded output image are split with lscale 2048 (the preload with
+ * out_lscale); the panel is packed, split on the device as mtts_gemm_p16 does, and summed per row as the model's packer does for this
+ * arithmetic (sums of the fp32 panel).  fast16: 1 = MODE 1 (refused with d_gn_stats).  out_lscale: residual scale of the output
+ * image, 2048 or 1 (what the attention kernel reads; not with res16_mode 2).  wave_rows and tag are written as by mtts_gemm_h16. */
+int64_t mtts_gemm_p16_args_scratch_bytes(const mtts_gemm_h16_args* g);
+int mtts_gemm_p16_args_run(mtts_gemm_h16_args* g, int fast16, float out_lscale, void* d_scratch, void* stream);
+
+/* P16 attention with everything the decoder passes: q|k|v image with unscaled residuals, d_klen and the key bias of folded padding
+ * as mtts_attention_h16, the output image with residual scale out_lscale (2048 or 1), fast16 (single fp16 product per MAC).
+ * d_scratch >= 16 * B*T*H*64 bytes.  The instantiation is read through mtts_last_kernel_tag. */
+int mtts_attention_p16_run(const float* d_qkv, const float* d_mask, const int* d_klen, int B, int T, int H, int D, float scale, int mask_mode,
+                           int fast16, float out_lscale, float* d_out, unsigned int* d_range_flag, void* d_scratch, void* stream);
+
+/* GroupNorm + Mish + mask [+ chbias, mask] written as a P16 image (d_out16_f32, times d_out16_mask[row]) and optionally as fp32
+ * rows (d_out); arguments as mtts_groupnorm_mish_h16 (tile statistics of a mtts_gemm_p16_args_run, or the statistics pass). */
+int64_t mtts_groupnorm_p16_scratch_bytes(int B, int T, int C, int G);
+int mtts_groupnorm_mish_p16(const float* d_y, const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias,
+                            int chbias_stride, int B, int T, int C, int G, float eps, const float* d_tile_stats, int tile_rows,
+                            const int* d_nrows, const int* d_nextra, const float* d_bias_stats, const float* d_out16_mask, float* d_out,
+                            float* d_out16_f32, unsigned int* d_range_flag, void* d_scratch, void* stream);
+
 /* Row statistics for LayerNorm over C (biased variance, eps inside rsqrt): mean[M], rstd[M]. */
 int mtts_row_stats(const float* d_x, int M, int C, int ld, float eps, float* d_mean, float* d_rstd, void* stream);
 

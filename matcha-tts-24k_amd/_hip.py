@@ -211,6 +211,13 @@ def load() -> C.CDLL:
         "mtts_groupnorm_h16_scratch_bytes": (i64, [i32, i32, i32, i32]),
         "mtts_groupnorm_mish_h16": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp,
                                           vp, vp]),
+        "mtts_to_p16_roundtrip": (i32, [vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
+        "mtts_gemm_p16_args_scratch_bytes": (i64, [C.POINTER(MttsGemmH16Args)]),
+        "mtts_gemm_p16_args_run": (i32, [C.POINTER(MttsGemmH16Args), i32, f32, vp, vp]),
+        "mtts_attention_p16_run": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, f32, vp, vp, vp, vp]),
+        "mtts_groupnorm_p16_scratch_bytes": (i64, [i32, i32, i32, i32]),
+        "mtts_groupnorm_mish_p16": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, vp, vp, vp,
+                                          vp, vp]),
         "mtts_row_stats": (i32, [vp, i32, i32, i32, f32, vp, vp, vp]),
         "mtts_channel_layernorm": (i32, [vp, i32, i32, i32, vp, vp, f32, i32, vp, vp, vp, vp]),
         "mtts_groupnorm_scratch_bytes": (i64, [i32, i32, i32]),
@@ -1045,6 +1052,19 @@ def gemm_h16(a, w, bias=None, *, B, T_in, T_out=None, tap_off=None, in_stride=1,
     that are BOTH the residual image and the output image (the residual-stream update).  ``out`` / ``out16``: buffers of an earlier
     call to write into (strided output rows).  ``gnr``: dict(y, stats, tile_rows, groups, gamma, beta, mask[, nextra, bias_stats,
     eps]) = the Block1D tail.  Returns a dict: out, out16, stats, gn_stats, wave_rows, tag, flag."""
+    return _gemm_block(lambda lib, g, scratch: lib.mtts_gemm_h16(C.byref(g), scratch, stream_ptr()), "mtts_gemm_h16_scratch_bytes", a, w, bias,
+                       B=B, T_in=T_in, T_out=T_out, tap_off=tap_off, in_stride=in_stride, c1=c1, a_mask=a_mask, a_mean=a_mean, a_rstd=a_rstd,
+                       a_part=a_part, act=act, p0=p0, p1=p1, res=res, res16=res16, inplace=inplace, out_mask=out_mask, out_scale=out_scale,
+                       out16_mask=out16_mask, want_f32=want_f32, want16=want_h16, out=out, out16=out16, out_T=out_T, out_stride=out_stride,
+                       out_off=out_off, stats_out=stats_out, gn_groups=gn_groups, gn_nrows=gn_nrows, gnr=gnr, force_bm=force_bm, bf16=bf16,
+                       half16=half16)
+
+
+def _gemm_block(run, scratch_fn, a, w, bias, *, B, T_in, T_out, tap_off, in_stride, c1, a_mask, a_mean, a_rstd, a_part, act, p0, p1, res, res16,
+                inplace, out_mask, out_scale, out16_mask, want_f32, want16, out, out16, out_T, out_stride, out_off, stats_out, gn_groups,
+                gn_nrows, gnr, force_bm, bf16, half16):
+    """What gemm_h16 and gemm_p16_args share: fill the argument block (include/mtts.h mtts_gemm_h16_args), allocate outputs and scratch,
+    call ``run(lib, block, scratch_ptr)``."""
     lib = load()
     dev = a.device
     N, Cc = w.shape[0], w.shape[1]
@@ -1068,7 +1088,7 @@ def gemm_h16(a, w, bias=None, *, B, T_in, T_out=None, tap_off=None, in_stride=1,
         g.res16_mode = 2
     elif res16 is not None:
         g.res16_mode, g.d_res16_f32 = 1, ptr(res16)
-    if out16 is None and want_h16:
+    if out16 is None and want16:
         out16 = torch.empty(rows, N, dtype=torch.float32, device=dev)
     g.d_out_mask, g.out_scale, g.d_out16_mask = ptr(out_mask), float(out_scale), ptr(out16_mask)
     g.d_out, g.d_out16_f32, g.out16_preload = ptr(out), ptr(out16), int(preload)
@@ -1086,11 +1106,11 @@ def gemm_h16(a, w, bias=None, *, B, T_in, T_out=None, tap_off=None, in_stride=1,
     g.force_bm, g.half16, g.bf16 = force_bm, int(bool(half16)), int(bool(bf16))
     flag = _flag(dev)
     g.d_range_flag = ptr(flag)
-    n = lib.mtts_gemm_h16_scratch_bytes(C.byref(g))
+    n = getattr(lib, scratch_fn)(C.byref(g))
     if n < 0:
         check(-1)
     scratch = torch.empty(n, dtype=torch.uint8, device=dev)
-    check(lib.mtts_gemm_h16(C.byref(g), scratch.data_ptr(), stream_ptr()))
+    check(run(lib, g, scratch.data_ptr()))
     return {"out": out, "out16": out16, "stats": stats, "gn_stats": gn_stats, "wave_rows": g.wave_rows, "tag": g.tag.decode(),
             "flag": int(flag.item())}
 
@@ -1123,6 +1143,71 @@ def groupnorm_mish_h16(y, gamma, beta, mask, B, T, *, G=8, chbias=None, tile_sta
     check(lib.mtts_groupnorm_mish_h16(ptr(y), ptr(gamma), ptr(beta), ptr(mask), ptr(chbias),
                                       chbias.shape[1] if chbias is not None and chbias.dim() == 2 else 0, B, T, Cc, G, float(eps),
                                       ptr(tile_stats), tile_rows, ptr(nrows), ptr(nextra), ptr(bias_stats), ptr(out16_mask), int(bool(bf16)),
+                                      ptr(out), ptr(out16), ptr(flag), scratch.data_ptr(), stream_ptr()))
+    return {"out": out, "out16": out16, "flag": int(flag.item())}
+
+
+def to_p16_roundtrip(x, mask=None, *, C_valid=None, ld16=None, lscale=2048.0, Cc=None):
+    """fp32 rows -> P16 image -> fp32 rows (include/mtts.h mtts_to_p16_roundtrip).  Returns a dict: ``out`` [M, C] fp32, ``bits``
+    [M, ld16] int16 (the image as stored: per 32-channel group 32 heads then 32 residuals; halves beyond 2 * C are untouched 0x7e7e
+    fill), ``flag`` (the range-flag word)."""
+    lib = load()
+    M = x.shape[0]
+    Cc = x.shape[1] if Cc is None else Cc
+    C_valid = Cc if C_valid is None else C_valid
+    ld16 = 2 * Cc if ld16 is None else ld16
+    image = torch.full((M, ld16), 0x7e7e, dtype=torch.int16, device=x.device)
+    out = torch.empty(M, Cc, dtype=torch.float32, device=x.device)
+    flag = _flag(x.device)
+    check(lib.mtts_to_p16_roundtrip(ptr(x), x.stride(0), ptr(mask), M, Cc, C_valid, ld16, float(lscale), ptr(image), ptr(out), ptr(flag),
+                                    stream_ptr()))
+    return {"out": out, "bits": image, "flag": int(flag.item())}
+
+
+def gemm_p16_args(a, w, bias=None, *, B, T_in, T_out=None, tap_off=None, in_stride=1, c1=0, a_mask=None, a_mean=None, a_rstd=None, a_part=None,
+                  act=0, p0=None, p1=None, res=None, res16=None, inplace=None, out_mask=None, out_scale=1.0, out16_mask=None,
+                  want_f32=True, want_p16=False, out=None, out16=None, out_T=0, out_stride=1, out_off=0, stats_out=False, gn_groups=0,
+                  gn_nrows=None, gnr=None, force_bm=0, fast16=False, out_lscale=2048.0, half16=False, bf16=False):
+    """P16 GEMM with every epilogue form of the decoder (csrc/gemm_p16.hip MODE 0, MODE 1 with ``fast16``; include/mtts.h
+    mtts_gemm_p16_args_run).  Arguments and result as ``gemm_h16`` with P16 images in place of H16 ones; ``out_lscale``: residual scale
+    of the output image (2048, or 1 for what the attention kernel reads)."""
+    return _gemm_block(lambda lib, g, scratch: lib.mtts_gemm_p16_args_run(C.byref(g), int(bool(fast16)), float(out_lscale), scratch, stream_ptr()),
+                       "mtts_gemm_p16_args_scratch_bytes", a, w, bias,
+                       B=B, T_in=T_in, T_out=T_out, tap_off=tap_off, in_stride=in_stride, c1=c1, a_mask=a_mask, a_mean=a_mean, a_rstd=a_rstd,
+                       a_part=a_part, act=act, p0=p0, p1=p1, res=res, res16=res16, inplace=inplace, out_mask=out_mask, out_scale=out_scale,
+                       out16_mask=out16_mask, want_f32=want_f32, want16=want_p16, out=out, out16=out16, out_T=out_T, out_stride=out_stride,
+                       out_off=out_off, stats_out=stats_out, gn_groups=gn_groups, gn_nrows=gn_nrows, gnr=gnr, force_bm=force_bm, bf16=bf16,
+                       half16=half16)
+
+
+def attention_p16_run(qkv, mask, B, T, H, D, scale, mask_mode=0, *, klen=None, fast16=False, out_lscale=2048.0):
+    """P16 attention as the decoder launches it (include/mtts.h mtts_attention_p16_run).  Returns a dict: out, tag, flag."""
+    lib = load()
+    out = torch.empty(B * T, H * D, dtype=torch.float32, device=qkv.device)
+    scratch = torch.empty(16 * B * T * H * D + 256, dtype=torch.uint8, device=qkv.device)
+    flag = _flag(qkv.device)
+    check(lib.mtts_attention_p16_run(ptr(qkv), ptr(mask), ptr(klen), B, T, H, D, float(scale), mask_mode, int(bool(fast16)), float(out_lscale),
+                                     ptr(out), ptr(flag), scratch.data_ptr(), stream_ptr()))
+    tag = last_kernel_tag()
+    return {"out": out, "tag": tag, "flag": int(flag.item())}
+
+
+def groupnorm_mish_p16(y, gamma, beta, mask, B, T, *, G=8, chbias=None, tile_stats=None, tile_rows=0, nrows=None, nextra=None,
+                       bias_stats=None, out16_mask=None, want_f32=True, eps=1e-5):
+    """GroupNorm + Mish + mask [+ chbias, mask] with a P16 image out (gn_apply_kernel's two-plane store; mtts_groupnorm_mish_p16).
+    chbias [B, stride >= C] or [C].  Returns a dict: out (fp32 rows), out16 (the image decoded), flag."""
+    lib = load()
+    Cc = y.shape[1]
+    n = lib.mtts_groupnorm_p16_scratch_bytes(B, T, Cc, G)
+    if n < 0:
+        check(-1)
+    scratch = torch.empty(n, dtype=torch.uint8, device=y.device)
+    out = torch.empty_like(y) if want_f32 else None
+    out16 = torch.empty_like(y)
+    flag = _flag(y.device)
+    check(lib.mtts_groupnorm_mish_p16(ptr(y), ptr(gamma), ptr(beta), ptr(mask), ptr(chbias),
+                                      chbias.shape[1] if chbias is not None and chbias.dim() == 2 else 0, B, T, Cc, G, float(eps),
+                                      ptr(tile_stats), tile_rows, ptr(nrows), ptr(nextra), ptr(bias_stats), ptr(out16_mask),
                                       ptr(out), ptr(out16), ptr(flag), scratch.data_ptr(), stream_ptr()))
     return {"out": out, "out16": out16, "flag": int(flag.item())}
 

@@ -94,6 +94,23 @@ static int chain_entry_finish(const ChainEntryBufs& b, int ew, bool bf16, int M,
     return 0;
 }
 
+// What the argument-block entries (mtts_gemm_h16, mtts_gemm_p16_args_run) share: the epilogue half of GemmArgs from the block; o16 /
+// r16 are the output and residual images, ew halves per image element (1 = H16, 2 = P16).
+static void block_epilogue(GemmArgs& a, const mtts_gemm_h16_args* g, _Float16* o16, _Float16* r16, int ew, int out_T, int out_stride, int out_off) {
+    const int N = g->N;
+    a.bias = g->d_bias; a.N = N; a.act = g->act; a.p0 = g->d_p0; a.p1 = g->d_p1;
+    a.res = g->d_res; a.ldr = g->ldr; a.out_mask = g->d_out_mask; a.out_scale = g->out_scale; a.out = g->d_out; a.ldc = N;
+    if (g->d_out16_f32) { a.out16 = o16; a.ld16 = ew * N; a.out16_mask = g->d_out16_mask; }
+    if (g->res16_mode == 1) { a.res16 = r16; a.ldr16 = ew * N; }
+    if (g->res16_mode == 2) { a.res16 = o16; a.ldr16 = ew * N; }
+    a.out_T = out_T; a.out_stride = out_stride; a.out_off = out_off;
+    a.stats_out = g->d_stats_out; a.force_bm = g->force_bm; a.range_flag = g->d_range_flag;
+    a.gn_stats = g->d_gn_stats; a.gn_groups = g->gn_groups; a.gn_nrows = g->d_gn_nrows;
+    a.gnr_y = g->d_gnr_y; a.gnr_stats = g->d_gnr_stats; a.gnr_tile_rows = g->gnr_tile_rows; a.gnr_groups = g->gnr_groups;
+    a.gnr_gamma = g->d_gnr_gamma; a.gnr_beta = g->d_gnr_beta; a.gnr_mask = g->d_gnr_mask; a.gnr_eps = g->gnr_eps > 0.f ? g->gnr_eps : 1e-5f;
+    a.gnr_nextra = g->d_gnr_nextra; a.gnr_bias_stats = g->d_gnr_bias_stats;
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------ single kernels
@@ -545,17 +562,7 @@ int mtts_gemm_h16(mtts_gemm_h16_args* g, void* d_scratch, void* stream) {
     a.in_stride = g->in_stride > 0 ? g->in_stride : 1; a.B = g->B; a.T_in = g->T_in; a.T_out = g->T_out;
     a.a_mean = g->d_a_mean; a.a_rstd = g->d_a_rstd; a.a_part = g->d_a_part; a.a_nparts = g->a_nparts; a.wsum = d_wsum;
     a.half16 = true; a.bf16 = bf; a.w16h = d_plane; a.terms = 2;
-    a.bias = g->d_bias; a.N = N; a.act = g->act; a.p0 = g->d_p0; a.p1 = g->d_p1;
-    a.res = g->d_res; a.ldr = g->ldr; a.out_mask = g->d_out_mask; a.out_scale = g->out_scale; a.out = g->d_out; a.ldc = N;
-    if (want16) { a.out16 = o16; a.ld16 = N; a.out16_mask = g->d_out16_mask; }
-    if (g->res16_mode == 1) { a.res16 = r16; a.ldr16 = N; }
-    if (g->res16_mode == 2) { a.res16 = o16; a.ldr16 = N; }
-    a.out_T = out_T; a.out_stride = out_stride; a.out_off = out_off;
-    a.stats_out = g->d_stats_out; a.force_bm = g->force_bm; a.range_flag = g->d_range_flag;
-    a.gn_stats = g->d_gn_stats; a.gn_groups = g->gn_groups; a.gn_nrows = g->d_gn_nrows;
-    a.gnr_y = g->d_gnr_y; a.gnr_stats = g->d_gnr_stats; a.gnr_tile_rows = g->gnr_tile_rows; a.gnr_groups = g->gnr_groups;
-    a.gnr_gamma = g->d_gnr_gamma; a.gnr_beta = g->d_gnr_beta; a.gnr_mask = g->d_gnr_mask; a.gnr_eps = g->gnr_eps > 0.f ? g->gnr_eps : 1e-5f;
-    a.gnr_nextra = g->d_gnr_nextra; a.gnr_bias_stats = g->d_gnr_bias_stats;
+    block_epilogue(a, g, o16, r16, 1, out_T, out_stride, out_off);
     g->wave_rows = gemm_p16_wave_rows(a);
     g_kernel_tag = nullptr;
     HIP_OK(launch_gemm(a, s));
@@ -612,6 +619,147 @@ int mtts_groupnorm_mish_h16(const float* d_y, const float* d_gamma, const float*
 int64_t mtts_groupnorm_h16_scratch_bytes(int B, int T, int C, int G) {
     if (B <= 0 || T <= 0 || C <= 0 || G <= 0) { set_error("mtts_groupnorm_h16_scratch_bytes: bad argument"); return -1; }
     return (int64_t)B * gn_chunks_max(T) * G * 2 * (int64_t)sizeof(float) + 256 + (int64_t)B * T * C * 2;
+}
+
+// ---- the two-plane (P16) instantiations of the same kernels: what the default arithmetic runs (gemm_p16_kernel MODE 0, MODE 1 with
+// fast16; the <*, true, false, false, false, *> attention kernels; gn_apply_kernel's two-plane store; to_p16 / from_p16), one entry per
+// kernel with every argument the decoder passes.  fp32 rows become P16 images by launch_to_p16 (residual scale 2048; 1 for the q|k|v
+// image the attention kernel reads), images come back through launch_from_p16 as h + l / lscale.  Host code only.
+int mtts_to_p16_roundtrip(const float* d_x, int ld, const float* d_mask, int M, int C, int C_valid, int ld16, float lscale, void* d_image,
+                          float* d_out, unsigned int* d_range_flag, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!d_x || !d_image || !d_out) { set_error("mtts_to_p16_roundtrip: null buffer"); return -1; }
+    if (M <= 0 || C <= 0 || (C % 32)) { set_error("mtts_to_p16_roundtrip: P16 operands need C % 32 == 0"); return -1; }
+    if (C_valid < 0 || C_valid > C || (C_valid & 3) || ld < C_valid || (ld & 3) || ld16 < 2 * C || (ld16 & 3)) { set_error("mtts_to_p16_roundtrip: bad stride or C_valid"); return -1; }
+    if (lscale != 2048.0f && lscale != 1.0f) { set_error("mtts_to_p16_roundtrip: lscale is 2048 or 1"); return -1; }
+    HIP_OK(launch_to_p16(d_x, ld, d_mask, M, C, C_valid, static_cast<_Float16*>(d_image), ld16, lscale, s, d_range_flag));
+    HIP_OK(launch_from_p16(static_cast<const _Float16*>(d_image), ld16, M, C, lscale, d_out, C, s));
+    return 0;
+}
+
+int64_t mtts_gemm_p16_args_scratch_bytes(const mtts_gemm_h16_args* g) {
+    if (!g || g->B <= 0 || g->T_in <= 0 || g->T_out <= 0 || g->N <= 0 || g->C <= 0 || g->ntaps < 1 || g->ntaps > MAX_TAPS) { set_error("mtts_gemm_p16_args_scratch_bytes: bad argument"); return -1; }
+    const int64_t out_rows = (int64_t)g->B * (g->out_T > 0 ? g->out_T : g->T_out);
+    const int64_t Np = round_up(g->N, GEMM_BN), Kp = (int64_t)g->ntaps * g->C;
+    return (int64_t)g->B * g->T_in * g->C * 4 + 2 * out_rows * round_up(g->N, 32) * 4 + 2 * Np * Kp * 4 + Np * 4 + 2048;
+}
+int mtts_gemm_p16_args_run(mtts_gemm_h16_args* g, int fast16, float out_lscale, void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!g) { set_error("mtts_gemm_p16_args_run: null argument block"); return -1; }
+    g->tag[0] = 0; g->wave_rows = 0;
+    if (!g->d_a || !g->h_w || !d_scratch || (!g->d_out && !g->d_out16_f32)) { set_error("mtts_gemm_p16_args_run: null buffer"); return -1; }
+    if (g->half16 || g->bf16) { set_error("mtts_gemm_p16_args_run: launches the two-plane instantiations only (half16 and bf16 must be 0)"); return -1; }
+    if (fast16 != 0 && fast16 != 1) { set_error("mtts_gemm_p16_args_run: fast16 is 0 or 1"); return -1; }
+    if (out_lscale != 2048.0f && out_lscale != 1.0f) { set_error("mtts_gemm_p16_args_run: out_lscale is 2048 or 1"); return -1; }
+    if (g->ntaps < 1 || g->ntaps > MAX_TAPS) { set_error("mtts_gemm_p16_args_run: ntaps out of range"); return -1; }
+    if (g->B <= 0 || g->T_in <= 0 || g->T_out <= 0 || g->N <= 0 || (g->N & 3)) { set_error("mtts_gemm_p16_args_run: bad shape"); return -1; }
+    if (g->C <= 0 || (g->C % 32) || g->c1 < 0 || (g->c1 % 32) || g->c1 >= g->C) { set_error("mtts_gemm_p16_args_run: P16 operands need C % 32 == 0 (and c1 % 32 == 0, c1 < C)"); return -1; }
+    if (g->lda < g->C || (g->lda & 3)) { set_error("mtts_gemm_p16_args_run: lda"); return -1; }
+    const bool want16 = g->d_out16_f32 != nullptr;
+    if ((want16 || g->res16_mode) && (g->N % 32)) { set_error("mtts_gemm_p16_args_run: a P16 output or residual image needs N % 32 == 0"); return -1; }
+    if (g->res16_mode < 0 || g->res16_mode > 2 || (g->res16_mode == 1 && !g->d_res16_f32) ||
+        (g->res16_mode == 2 && (!want16 || !g->out16_preload || out_lscale != 2048.0f))) {
+        set_error("mtts_gemm_p16_args_run: res16_mode 1 needs d_res16_f32, 2 (in place) needs d_out16_f32 with out16_preload and out_lscale 2048");
+        return -1;
+    }
+    if (g->res16_mode && g->d_res) { set_error("mtts_gemm_p16_args_run: res16 together with res"); return -1; }
+    const bool ln = g->d_a_mean || g->d_a_part;
+    if (g->d_gn_stats && fast16) { set_error("mtts_gemm_p16_args_run: gn_stats with fast16 (that mode keeps the separate statistics pass)"); return -1; }
+    if (g->d_gn_stats && (g->act != ACT_NONE || g->d_res || g->res16_mode || g->d_out_mask || g->out_scale != 1.0f || ln || g->gn_groups <= 0)) {
+        set_error("mtts_gemm_p16_args_run: gn_stats with an activation, residual, mask, scale or LayerNorm (bias-only epilogue; gn_groups > 0)");
+        return -1;
+    }
+    const int out_T = g->out_T > 0 ? g->out_T : g->T_out, out_stride = g->out_T > 0 ? g->out_stride : 1, out_off = g->out_T > 0 ? g->out_off : 0;
+    if (out_stride < 1 || out_off < 0 || (g->T_out - 1) * out_stride + out_off >= out_T) { set_error("mtts_gemm_p16_args_run: output rows leave [0, out_T)"); return -1; }
+    if (g->ntaps > 1 && !g->h_tap_off) { set_error("mtts_gemm_p16_args_run: a convolution needs its tap offsets"); return -1; }
+    const int C = g->C, c0 = C - g->c1, N = g->N, Np = round_up(N, GEMM_BN), Kp = g->ntaps * C;
+    const size_t npanel = (size_t)Np * Kp, out_rows = (size_t)g->B * out_T;
+    // host: the panel and its row sums as the model stores them in this arithmetic (pack.hip add_planes: sums of the fp32 panel)
+    std::vector<float> panel(npanel);
+    pack_weight_host(g->h_w, g->ntaps > 1 ? 1 : 0, N, C, g->ntaps, 0, nullptr, nullptr, panel.data(), C);
+    std::vector<float> wsum(Np);
+    for (int n = 0; n < Np; ++n) wsum[n] = (float)plain_row_sum(panel.data() + (size_t)n * Kp, Kp, false);
+    char* sc = static_cast<char*>(d_scratch);
+    auto carve = [&](size_t bytes) { char* q = sc; sc += (bytes + 255) & ~size_t(255); return q; };
+    _Float16* a16 = reinterpret_cast<_Float16*>(carve((size_t)g->B * g->T_in * C * 4));
+    _Float16* o16 = reinterpret_cast<_Float16*>(carve(out_rows * N * 4));
+    _Float16* r16 = reinterpret_cast<_Float16*>(carve(out_rows * N * 4));
+    float* d_panel = reinterpret_cast<float*>(carve(npanel * 4));
+    void* d_planes = carve(npanel * 4);
+    float* d_wsum = reinterpret_cast<float*>(carve((size_t)Np * 4));
+    HIP_OK(hipMemcpyAsync(d_panel, panel.data(), npanel * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(d_wsum, wsum.data(), (size_t)Np * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));                      // (the host vectors go out of scope)
+    HIP_OK(launch_split_panel_f16(d_panel, npanel, d_planes, s));
+    HIP_OK(launch_to_p16(g->d_a, g->lda, g->d_a_mask, g->B * g->T_in, C, C, a16, 2 * C, 2048.0f, s));
+    if (want16 && g->out16_preload) HIP_OK(launch_to_p16(g->d_out16_f32, N, nullptr, (int)out_rows, N, N, o16, 2 * N, out_lscale, s));
+    if (g->res16_mode == 1) HIP_OK(launch_to_p16(g->d_res16_f32, N, nullptr, (int)out_rows, N, N, r16, 2 * N, 2048.0f, s));
+    GemmArgs a;
+    a.a16_0 = a16; a.lda16_0 = 2 * C; a.c0 = c0; a.ktap = C; a.ntaps = g->ntaps;
+    if (g->c1) { a.a16_1 = a16 + 2 * c0; a.lda16_1 = 2 * C; a.c1 = g->c1; }
+    for (int j = 0; j < g->ntaps; ++j) a.tap_off[j] = g->h_tap_off ? g->h_tap_off[j] : 0;
+    a.in_stride = g->in_stride > 0 ? g->in_stride : 1; a.B = g->B; a.T_in = g->T_in; a.T_out = g->T_out;
+    a.a_mean = g->d_a_mean; a.a_rstd = g->d_a_rstd; a.a_part = g->d_a_part; a.a_nparts = g->a_nparts; a.wsum = d_wsum;
+    a.w16 = d_planes; a.terms = 2; a.fast16 = fast16 != 0; a.out_lscale = out_lscale;
+    block_epilogue(a, g, o16, r16, 2, out_T, out_stride, out_off);
+    g->wave_rows = gemm_p16_wave_rows(a);
+    g_kernel_tag = nullptr;
+    HIP_OK(launch_gemm(a, s));
+    if (g_kernel_tag) { std::strncpy(g->tag, g_kernel_tag, sizeof(g->tag) - 1); g->tag[sizeof(g->tag) - 1] = 0; }
+    if (want16) HIP_OK(launch_from_p16(o16, 2 * N, (int)out_rows, N, out_lscale, g->d_out16_f32, N, s));
+    return 0;
+}
+
+int mtts_attention_p16_run(const float* d_qkv, const float* d_mask, const int* d_klen, int B, int T, int H, int D, float scale, int mask_mode,
+                           int fast16, float out_lscale, float* d_out, unsigned int* d_range_flag, void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!d_qkv || !d_out || !d_scratch) { set_error("mtts_attention_p16_run: null buffer"); return -1; }
+    if (D != 64 || B <= 0 || T <= 0 || H <= 0) { set_error("mtts_attention_p16_run: P16 attention needs D == 64 and a non-empty batch"); return -1; }
+    if (mask_mode == 1 && !d_mask) { set_error("mtts_attention_p16_run: the boolean mask mode needs a mask"); return -1; }
+    if (fast16 != 0 && fast16 != 1) { set_error("mtts_attention_p16_run: fast16 is 0 or 1"); return -1; }
+    if (out_lscale != 2048.0f && out_lscale != 1.0f) { set_error("mtts_attention_p16_run: out_lscale is 2048 or 1"); return -1; }
+    const int M = B * T, C3 = 3 * H * D;
+    _Float16* q16 = static_cast<_Float16*>(d_scratch);
+    _Float16* o16 = q16 + (size_t)M * 2 * C3;
+    HIP_OK(launch_to_p16(d_qkv, C3, nullptr, M, C3, C3, q16, 2 * C3, 1.0f, s));
+    AttnArgs a;
+    a.qkv16 = q16; a.ld16 = 2 * C3; a.out16 = o16; a.ldo16 = 2 * H * D; a.out_lscale = out_lscale; a.mask = d_mask; a.klen = d_klen;
+    a.B = B; a.T = T; a.H = H; a.D = D; a.scale = scale; a.mask_mode = mask_mode; a.fast16 = fast16 != 0;
+    a.range_flag = d_range_flag;
+    g_kernel_tag = nullptr;
+    HIP_OK(launch_attention(a, s));
+    HIP_OK(launch_from_p16(o16, 2 * H * D, M, H * D, out_lscale, d_out, H * D, s));
+    return 0;
+}
+
+int64_t mtts_groupnorm_p16_scratch_bytes(int B, int T, int C, int G) {
+    if (B <= 0 || T <= 0 || C <= 0 || G <= 0) { set_error("mtts_groupnorm_p16_scratch_bytes: bad argument"); return -1; }
+    return (int64_t)B * gn_chunks_max(T) * G * 2 * (int64_t)sizeof(float) + 256 + (int64_t)B * T * C * 4;
+}
+int mtts_groupnorm_mish_p16(const float* d_y, const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias,
+                            int chbias_stride, int B, int T, int C, int G, float eps, const float* d_tile_stats, int tile_rows,
+                            const int* d_nrows, const int* d_nextra, const float* d_bias_stats, const float* d_out16_mask, float* d_out,
+                            float* d_out16_f32, unsigned int* d_range_flag, void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (!d_y || !d_gamma || !d_beta || !d_mask || !d_out16_f32 || !d_scratch) { set_error("mtts_groupnorm_mish_p16: null buffer"); return -1; }
+    if (B <= 0 || T <= 0 || C <= 0 || (C % 32) || G <= 0 || (C % G)) { set_error("mtts_groupnorm_mish_p16: P16 images need C % 32 == 0 (and C % G == 0)"); return -1; }
+    if (d_chbias && chbias_stride && chbias_stride < C) { set_error("mtts_groupnorm_mish_p16: a bias row per utterance has at least C values"); return -1; }
+    if ((d_nextra != nullptr) != (d_bias_stats != nullptr)) { set_error("mtts_groupnorm_mish_p16: nextra and bias_stats come together"); return -1; }
+    if (d_tile_stats && tile_rows <= 0) { set_error("mtts_groupnorm_mish_p16: tile_stats need tile_rows"); return -1; }
+    char* sc = static_cast<char*>(d_scratch);
+    float* partial = reinterpret_cast<float*>(sc);
+    sc += ((size_t)B * gn_chunks_max(T) * G * 2 * sizeof(float) + 255) & ~size_t(255);
+    _Float16* o16 = reinterpret_cast<_Float16*>(sc);
+    GnApplyArgs a;
+    a.y = d_y; a.gamma = d_gamma; a.beta = d_beta; a.mask = d_mask; a.chbias = d_chbias; a.chbias_stride = chbias_stride;
+    if (d_tile_stats) { a.tile_stats = d_tile_stats; a.tile_rows = tile_rows; }
+    else { HIP_OK(launch_gn_partial(d_y, B, T, C, G, partial, s, d_nrows)); a.partial = partial; a.nrows = d_nrows; }
+    a.nextra = d_nextra; a.bias_stats = d_bias_stats;
+    a.out = d_out; a.out16 = o16; a.ld16 = 2 * C; a.out16_mask = d_out16_mask; a.range_flag = d_range_flag;      // (half16 unset: the two-plane store)
+    a.B = B; a.T = T; a.C = C; a.G = G; a.eps = eps;
+    HIP_OK(launch_gn_apply(a, s));
+    HIP_OK(launch_from_p16(o16, 2 * C, B * T, C, 2048.0f, d_out16_f32, C, s));
+    return 0;
 }
 
 }  // extern "C"
