@@ -659,6 +659,69 @@ int mtts_score_prior_dur(const float* d_mu_x, const float* d_logw, const int32_t
                          int64_t ws_bytes, void* stream);
 int mtts_score_status(const void* d_ws, void* stream);
 
+/* ---------------------------------------------------------------- speaker-row gradients (fine-tuning a voice from recordings) */
+
+/* The gradient of the prior and duration Huber sums of mtts_score_prior_dur with respect to the two speaker rows, per utterance:
+ * what the reference's matcha/finetune_speaker.py trains (one row of speaker_embeddings_enc.weight and one of
+ * speaker_embeddings_dur.weight, everything else frozen).  What reaches the rows in the reference's training forward:
+ *   - not the flow-matching loss: mu_y is detached before decoder.compute_loss (matcha_tts.py:154-162) and the estimator has no
+ *     speaker input, so there is no decoder backward;
+ *   - e_dur through the duration predictor alone, whose input is x.detach() (text_encoder.py:404): per layer FiLM, the channel
+ *     LayerNorm (text_encoder.py:19-27), the ReLU and the k5 convolutions of layers >= 1 (text_encoder.py:101-112), then spk_proj^T;
+ *   - e_enc, concatenated behind the prenet (text_encoder.py:400), through proj_m (text_encoder.py:359-363,402), the post-LN encoder
+ *     layers (RoPE attention text_encoder.py:220-237, conv FFN :253-258, Encoder.forward :299-316) and a sum over tokens of the
+ *     speaker channels; no prenet, embedding or weight gradient;
+ *   - MAS runs under no_grad (matcha_tts.py:187): the durations are constants.
+ * This is the dropout-free (eval) gradient.
+ *
+ * Backward panels: the data gradient of a Linear is a GEMM with the transposed panel, that of a Conv1d(k, pad k/2) a GEMM with in /
+ * out channels swapped and the taps reversed: proj_m[2]^T, proj_m[0]^T; per encoder layer conv_o^T, conv_q|k|v^T, ffn.conv_2^T,
+ * ffn.conv_1^T; dp.conv_layers[1..]^T; spk_proj^T; and dp.proj's weight row (one output channel: its transpose is an outer product
+ * inside the seed kernel).  They are packed on demand from the registered tensors into a buffer of their own
+ * (mtts_spk_grad_weights_bytes / mtts_spk_grad_upload_weights; mtts_set_tensor invalidates them), not into the weight image, and run
+ * on the library's GEMM launchers in NATIVE FP32 MFMA (arithmetic 0) whatever the context's forward arithmetic is: gradients are
+ * small numbers and the fp16 two-term split loses bits below the fp16 normal range.
+ *
+ * mtts_spk_grad: a taped text-encoder forward (the launches of mtts_text_encoder_forward with the same arguments, intermediates kept
+ *   per layer: mu_x, logw and x_mask equal that entry's bit for bit and can be read back at mtts_spk_grad_tape_offset), the alignment
+ *   (d_durations_in int32 [B,Tx], or NULL: mtts_mas on this forward's mu_x, as the reference does), mtts_score_prior_dur's two sums
+ *   (d_prior_sum, d_dur_sum [B]: that entry's bits), the two loss-gradient seeds
+ *     d prior_sum_b / d mu_x[f,x] = - sum_{y on token x} huber'(y_fine[f,y] - mu_x[f,x], delta_prior)
+ *     d dur_sum_b / d logw[x]     = huber'(logw[x] - log(2 + dur[x]), delta_dur),        huber'(d, delta) = clamp(d, -delta, delta)
+ *   and the data-gradient walk back.  d_g_enc, d_g_dur [B, spk_emb_dim]: gradients of the PER-UTTERANCE sums; the reference's batch
+ *   loss gradients are sum_b g_dur[b] / sum_b Tx_b and sum_b g_enc[b] / sum_b Tm_b, which the caller forms.  d_durations_out int32
+ *   [B,Tx] or NULL.  Arguments d_x .. d_e_dur as for mtts_text_encoder_forward; d_y_fine [B,F,Tm] normalised fine mel.
+ *   Every sum has a fixed order, there are no floating-point atomics: an utterance's rows do not depend on its batch or the padded
+ *   shapes, and two calls give the same bits.  An utterance mtts_score_prior_dur refuses (lengths, durations) gets zero rows, the
+ *   others are unaffected, and mtts_spk_grad_status(d_ws, stream) -- the one entry here that waits for the stream -- names it.
+ *   Stream-ordered, no allocation.  Context guard and range-guard word (first word of d_ws) as the neighbouring entries.  Returns -1
+ *   (mtts_last_error) for null pointers, B < 1, Tx > 1024, Tm < Tx, a threshold <= 0, a small workspace, backward panels that are
+ *   not uploaded in d_grad_buf. */
+int64_t mtts_spk_grad_weights_bytes(mtts_ctx* ctx);
+int mtts_spk_grad_upload_weights(mtts_ctx* ctx, void* d_buf, int64_t bytes);
+int64_t mtts_spk_grad_workspace_bytes(mtts_ctx* ctx, int B, int Tx, int Tm);
+int64_t mtts_spk_grad_tape_offset(mtts_ctx* ctx, int B, int Tx, int Tm, int which);      /* byte offset in d_ws of 0 mu_x [B,F,Tx], 1 logw [B,Tx], 2 x_mask [B,Tx] */
+int mtts_spk_grad(mtts_ctx* ctx, const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur,
+                  const float* d_y_fine, const int64_t* d_y_fine_lengths, const int32_t* d_durations_in, float delta_prior,
+                  float delta_dur, int B, int Tx, int Tm, float* d_g_enc, float* d_g_dur, float* d_prior_sum, float* d_dur_sum,
+                  int32_t* d_durations_out, void* d_grad_buf, void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_spk_grad_status(const void* d_ws, void* stream);
+
+/* Kernel-level entries of the two backward kernels, fp32 rows in and out (no context).
+ * mtts_channel_layernorm_bwd: backward of mtts_channel_layernorm (text_encoder.py:19-27 + SiLU / FiLM / mask as that entry): d_x the
+ *   LayerNorm's input rows [B*T, C], d_dy the upstream gradient, d_dx the result; gate 1: d_x is a ReLU output and d_dx is gated by
+ *   (x > 0); d_dfilm [B, 2C] or NULL = (d gamma_b | d beta_b) summed over the T rows of each utterance in token order (needs d_film
+ *   and d_scratch of B*T*C floats).
+ * mtts_attention_rope_bwd: backward of the encoder's SDPA with rotary q / k (text_encoder.py:220-237): d_qkv [B*T, 3*H*D] rows AFTER
+ *   the rotation (q | k | v sections), d_o the attention output and d_do its gradient [B*T, H*D], d_lengths int64 [B] (boolean query x
+ *   key mask), d_cos / d_sin [>= T, D/2]; d_dqkv = the gradient with respect to q | k | v BEFORE the rotation, zero rows beyond an
+ *   utterance's length.  D a multiple of 8, <= 64; T <= 1024; d_scratch B*H*T*3 floats. */
+int mtts_channel_layernorm_bwd(const float* d_x, const float* d_dy, int B, int T, int C, const float* d_gamma, const float* d_beta, float eps,
+                               int act, const float* d_film, const float* d_mask, int gate, float* d_dx, float* d_dfilm, void* d_scratch,
+                               void* stream);
+int mtts_attention_rope_bwd(const float* d_qkv, const float* d_o, const float* d_do, const int64_t* d_lengths, int B, int T, int H, int D,
+                            float scale, const float* d_cos, const float* d_sin, float* d_dqkv, void* d_scratch, void* stream);
+
 /* ---------------------------------------------------------------- arithmetic and its range guard */
 
 /* Range guard of the default arithmetic.  The fp16 two-term split represents an operand x as h + l / 2^11 with h = fp16(x):

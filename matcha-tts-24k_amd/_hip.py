@@ -19,7 +19,7 @@ from .hparams import PathHParams
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = Path(os.environ["MTTS_HIP_LIB"]) if os.environ.get("MTTS_HIP_LIB") else HERE / "libmtts_hip.so"   # override: A/B of two builds
-SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "style_encoder.hip", "mas.hip", "score.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
+SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "style_encoder.hip", "mas.hip", "score.hip", "spk_grad.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
 HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", CSRC / "host.h", HERE.parent / "include" / "mtts.h"]
 SOLVERS = {"euler": 0, "midpoint": 1, "rk4": 2}
 
@@ -259,6 +259,14 @@ def load() -> C.CDLL:
         "mtts_score_serial_run": (i32, [i32, i32, i32, i32]),
         "mtts_score_prior_dur": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, i64, vp]),
         "mtts_score_status": (i32, [vp, vp]),
+        "mtts_spk_grad_weights_bytes": (i64, [vp]),
+        "mtts_spk_grad_upload_weights": (i32, [vp, vp, i64]),
+        "mtts_spk_grad_workspace_bytes": (i64, [vp, i32, i32, i32]),
+        "mtts_spk_grad_tape_offset": (i64, [vp, i32, i32, i32, i32]),
+        "mtts_spk_grad": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+        "mtts_spk_grad_status": (i32, [vp, vp]),
+        "mtts_channel_layernorm_bwd": (i32, [vp, vp, i32, i32, i32, vp, vp, f32, i32, vp, vp, i32, vp, vp, vp, vp]),
+        "mtts_attention_rope_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
         "mtts_gemm_terms": (i32, [vp]),
         "mtts_set_arithmetic": (i32, [vp, i32]),
         "mtts_weights_saturate": (i32, [vp]),
@@ -418,6 +426,8 @@ class HipModel:
         self.device: Optional[torch.device] = None
         self._ws: Dict[tuple, torch.Tensor] = {}
         self._last_ws: Dict[str, torch.Tensor] = {}     # workspace of the latest call per kind: its first word = range flag
+        self._grad_weights: Optional[torch.Tensor] = None   # backward panels of speaker_grad, uploaded on first use ...
+        self._grad_generation = -1                          # ... for this weight generation
 
     def __del__(self):
         try:
@@ -785,6 +795,72 @@ class HipModel:
         refused (mtts_score_status)."""
         ws = self._last_ws.get(("score", stream_ptr()))
         if ws is not None and self.lib.mtts_score_status(ws.data_ptr(), stream_ptr()) != 0:
+            raise ValueError(self.lib.mtts_last_error().decode("utf-8", "replace"))
+
+    def speaker_grad(self, x, x_lengths, e_enc, e_dur, y_fine, y_fine_lengths, delta_prior: float, delta_dur: float, durations=None,
+                     check_lengths: bool = True, return_tape: bool = False):
+        """Gradients of the per-utterance prior and duration Huber sums with respect to the speaker rows (mtts_spk_grad): a taped
+        text-encoder forward, MAS (``durations`` None) or the given int32 ``durations`` [B, Tx], the two sums and the backward walk.
+        Returns a dict: ``g_enc``, ``g_dur`` [B, spk_emb_dim], ``prior_sum``, ``dur_sum`` [B], ``durations`` int32 [B, Tx] and, with
+        ``return_tape``, views ``mu_x``, ``logw``, ``x_mask`` of this call's workspace (valid until the next call on this stream).
+        The backward panels are packed and uploaded on first use per weight generation.  ``check_lengths`` as ``score_prior_dur``."""
+        B, Tx = x.shape
+        dev = x.device
+        x = x.detach().to(torch.int64).contiguous()
+        xl = x_lengths.detach().to(device=dev, dtype=torch.int64).contiguous()
+        e_enc, e_dur = self._f32(e_enc), self._f32(e_dur)
+        if e_enc.shape[0] != B:
+            e_enc, e_dur = e_enc.expand(B, -1).contiguous(), e_dur.expand(B, -1).contiguous()
+        y_fine = self._f32(y_fine)
+        F, Tm, Sd = self.hp.n_feats, y_fine.shape[2], self.hp.spk_emb_dim
+        if y_fine.shape[:2] != (B, F):
+            raise ValueError(f"speaker_grad: y_fine must be [{B}, {F}, Tm], got {tuple(y_fine.shape)}")
+        yl = y_fine_lengths.detach().to(device=dev, dtype=torch.int64).contiguous()
+        if xl.shape != (B,) or yl.shape != (B,):
+            raise ValueError("x_lengths and y_fine_lengths need one entry per utterance")
+        if e_enc.shape != (B, Sd) or e_dur.shape != (B, Sd):
+            raise ValueError(f"speaker rows must be [{B}, {Sd}]")
+        dur_in = None
+        if durations is not None:
+            dur_in = durations.detach().to(device=dev, dtype=torch.int32).contiguous()
+            if dur_in.shape != (B, Tx):
+                raise ValueError(f"durations must have shape ({B}, {Tx}), got {tuple(dur_in.shape)}")
+        if self._grad_weights is None or self._grad_generation != self.generation:
+            nb = self.lib.mtts_spk_grad_weights_bytes(self.ctx)
+            if nb < 0:
+                check(-1)
+            buf = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            check(self.lib.mtts_spk_grad_upload_weights(self.ctx, buf.data_ptr(), nb))
+            self._grad_weights, self._grad_generation = buf, self.generation
+        n = self.lib.mtts_spk_grad_workspace_bytes(self.ctx, B, Tx, Tm)
+        if n < 0:
+            check(-1)
+        ws = self._grow("spk_grad", n)
+        g_enc = torch.empty(B, Sd, dtype=torch.float32, device=dev)
+        g_dur = torch.empty(B, Sd, dtype=torch.float32, device=dev)
+        prior = torch.empty(B, dtype=torch.float32, device=dev)
+        dsum = torch.empty(B, dtype=torch.float32, device=dev)
+        dur_out = torch.empty(B, Tx, dtype=torch.int32, device=dev)
+        check(self.lib.mtts_spk_grad(self.ctx, ptr(x), ptr(xl), ptr(e_enc), ptr(e_dur), ptr(y_fine), ptr(yl), ptr(dur_in), float(delta_prior),
+                                     float(delta_dur), B, Tx, Tm, ptr(g_enc), ptr(g_dur), ptr(prior), ptr(dsum), ptr(dur_out),
+                                     self._grad_weights.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()))
+        if check_lengths:
+            self.spk_grad_status()
+        out = {"g_enc": g_enc, "g_dur": g_dur, "prior_sum": prior, "dur_sum": dsum, "durations": dur_out}
+        if return_tape:
+            for which, (name, shape) in enumerate((("mu_x", (B, F, Tx)), ("logw", (B, 1, Tx)), ("x_mask", (B, 1, Tx)))):
+                off = self.lib.mtts_spk_grad_tape_offset(self.ctx, B, Tx, Tm, which)
+                if off < 0:
+                    check(-1)
+                count = B * Tx * (F if which == 0 else 1)
+                out[name] = ws[off:off + 4 * count].view(torch.float32).view(shape)
+        return out
+
+    def spk_grad_status(self) -> None:
+        """Wait for this stream's latest ``speaker_grad`` call and raise ``ValueError`` naming the first utterance the device refused
+        (mtts_spk_grad_status)."""
+        ws = self._last_ws.get(("spk_grad", stream_ptr()))
+        if ws is not None and self.lib.mtts_spk_grad_status(ws.data_ptr(), stream_ptr()) != 0:
             raise ValueError(self.lib.mtts_last_error().decode("utf-8", "replace"))
 
     def fold_rows(self, y_max: int, align: int) -> int:
@@ -1243,6 +1319,30 @@ def channel_layernorm(x, gamma, beta, B, T, *, act=0, film=None, mask=None, eps=
     check(lib.mtts_channel_layernorm(ptr(x), B, T, x.shape[1], ptr(gamma), ptr(beta), float(eps), act, ptr(film), ptr(mask), ptr(y),
                                      stream_ptr()))
     return y
+
+
+def channel_layernorm_bwd(x, dy, gamma, beta, B, T, *, act=0, film=None, mask=None, gate=0, eps=1e-5):
+    """Backward of ``channel_layernorm`` (mtts_channel_layernorm_bwd): returns ``(dx [B*T, C], dfilm [B, 2C] or None)``."""
+    lib = load()
+    dx = torch.empty_like(x)
+    Cc = x.shape[1]
+    dfilm = torch.empty(B, 2 * Cc, dtype=torch.float32, device=x.device) if film is not None else None
+    scratch = torch.empty(B * T * Cc, dtype=torch.float32, device=x.device) if film is not None else None
+    check(lib.mtts_channel_layernorm_bwd(ptr(x), ptr(dy), B, T, Cc, ptr(gamma), ptr(beta), float(eps), act, ptr(film), ptr(mask), gate,
+                                         ptr(dx), ptr(dfilm), ptr(scratch), stream_ptr()))
+    return dx, dfilm
+
+
+def attention_rope_bwd(qkv, o, do, lengths, B, T, H, D, scale, cos, sin):
+    """Backward of the encoder's rotary SDPA (mtts_attention_rope_bwd): ``qkv`` [B*T, 3*H*D] rows after the rotation -> the gradient
+    with respect to q | k | v before it."""
+    lib = load()
+    dqkv = torch.empty_like(qkv)
+    scratch = torch.empty(B * H * T * 3, dtype=torch.float32, device=qkv.device)
+    lengths = lengths.detach().to(device=qkv.device, dtype=torch.int64).contiguous()
+    check(lib.mtts_attention_rope_bwd(ptr(qkv), ptr(o), ptr(do), ptr(lengths), B, T, H, D, float(scale), ptr(cos), ptr(sin), ptr(dqkv),
+                                      ptr(scratch), stream_ptr()))
+    return dqkv
 
 
 def conv_gn_rows(x, w, bias, gamma, beta, mask, chbias, *, B, T, c1=0, nrows=None, nextra=None, bias_stats=None, eps=1e-5):

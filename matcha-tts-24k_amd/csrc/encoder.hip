@@ -30,6 +30,8 @@ int64_t mtts_encoder_workspace_bytes(mtts_ctx* c, int B, int Tx) {
 }
 
 // TextEncoder.forward (reference text_encoder.py:375-406)
+// (spk_grad.hip's taped forward repeats this launch sequence with per-layer buffers and must produce the same bits: a change here is
+// mirrored there; tests/test_hip_spk_grad.py compares the two bit for bit)
 int mtts_text_encoder_forward(mtts_ctx* c, const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur,
                               int B, int Tx, float* d_mu_x, float* d_logw, float* d_x_mask, void* d_ws, int64_t ws_bytes, void* stream) {
     CTX_GUARD(c);

@@ -135,6 +135,7 @@ struct Packer {
                       const std::vector<float>* col_shift = nullptr);
 };
 int pack_all(mtts_ctx* c, bool dry = false);
+int pack_spk_grad(mtts_ctx* c);      // spk_grad.hip: the backward panels, from the registered tensors
 
 // ------------------------------------------------------------------------------------------------ weight life cycle
 // The same for the path's context, the Vocos head and the style encoder; `pack` is the component's packing function and `who` the

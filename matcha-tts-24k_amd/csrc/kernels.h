@@ -443,6 +443,10 @@ hipError_t launch_frame_tables(const FrameTableArgs& a, hipStream_t s);
 hipError_t launch_align_pool(const float* mu_x, const int32_t* cum, const int64_t* yfl, int B, int nf, int Tx, int T_pad,
                              float* mu_y, float* y_mask, int64_t* y_len, hipStream_t s);
 
+// ---- scoring (score.hip): mtts_score_prior_dur's workspace is SCORE_HEADER_BYTES of status words (mtts_score_status), then the verdicts
+// int32 [B][2] = (0 ok / 1 lengths / 2 durations, duration total), which spk_grad.hip reads on the device
+constexpr int SCORE_HEADER_BYTES = 256;
+
 // ---- flow-matching loss (score.hip; reference flow_matching.py:65-107), one time per utterance in t_b (device [B])
 // dst[b*T + t] = y_t | mu | 0 (rows of ld floats): y_t = (1 - (1 - sigma_min) t_b) x0 + t_b x1, x0 = noise (+ mu)
 hipError_t launch_cfm_target(const float* x1, const float* noise, const float* mu, const float* t_b, int add_mu, float sigma_min, int B,

@@ -81,6 +81,16 @@ struct VocosW {
     std::vector<Panel> pw1, pw2;
 };
 
+// Backward panels of the speaker-row gradient (spk_grad.hip): transposed / tap-reversed copies of the text encoder's panels behind the
+// speaker rows, packed on demand into a buffer of their own (mtts_ctx::grad), never into the weight image.
+struct SpkGradW {
+    Panel pm2T, pm0T;
+    std::vector<Panel> oT, qkvT, ffn2T, ffn1T;
+    std::vector<Panel> dp_convT;   // [0] is empty: the first duration-predictor layer reads x.detach()
+    Panel filmT;                   // spk_proj transposed
+    Vec dp_proj;                   // the duration predictor's output projection [dp_filter] (one output channel: an outer product)
+};
+
 struct StyleW {
     std::vector<Panel> convs;      // Conv1d(k5, pad 2) of each layer
     Vec proj_w, proj_b;            // [2 E][hidden] = proj_enc rows then proj_dur rows, [2 E]
@@ -159,6 +169,9 @@ struct mtts_ctx : mtts::Component {
     // one thread at a time: the path's entry points hold this while they enqueue (per-call state: cur_flag, half_now,
     // d_tlen, prof); a second thread's call fails instead of interleaving its launches with another call's flag pointer
     std::atomic<bool> in_use{false};
+    // speaker-row gradient (spk_grad.hip): the backward panels' own image (native fp32 MFMA: gemm_terms 0) and their offsets
+    mtts::Component grad;
+    mtts::SpkGradW gradw;
 };
 
 // Vocos-24k head: its own weight image and context (the reference loads it as a separate object,

@@ -99,7 +99,10 @@ int mtts_weights_saturate(mtts_ctx* c) {
 
 void mtts_destroy(mtts_ctx* c) { delete c; }
 
-int mtts_set_tensor(mtts_ctx* c, const char* key, const float* h, int64_t numel) { return set_tensor(c, key, h, numel); }
+int mtts_set_tensor(mtts_ctx* c, const char* key, const float* h, int64_t numel) {
+    if (c) { c->grad.packed = false; c->grad.uploaded = false; }      // the backward panels (spk_grad.hip) are copies of these tensors
+    return set_tensor(c, key, h, numel);
+}
 
 int64_t mtts_weights_bytes(mtts_ctx* c) { return weights_bytes(c, pack_ctx); }
 

@@ -26,7 +26,6 @@ namespace mtts {
 constexpr int SCORE_FRAMES = 64;        // fine frames per workgroup of score_prior_dur_kernel
 constexpr int SCORE_FLANES = 16;        // feature lanes: thread (fl, yg) owns features fl, fl + 16, ... of frames 4 yg .. 4 yg + 3
 constexpr int SCORE_MAX_TX = 1024;      // tokens (the cumulative durations live in LDS), as mtts_mas
-constexpr int SCORE_HEADER_BYTES = 256;
 
 __device__ __forceinline__ float score_wave_sum(float v) {
 #pragma unroll

@@ -1,0 +1,860 @@
+// Speaker-row gradients: d(prior Huber sum) / d e_enc and d(duration Huber sum) / d e_dur per utterance, for fine-tuning a voice from
+// recordings (reference matcha/finetune_speaker.py: everything frozen but one row of each speaker table).
+//
+// What the reference's training forward lets reach the two rows (matcha/models/matcha_tts.py, components/text_encoder.py):
+//   * the flow-matching loss does not: mu_y is detached before decoder.compute_loss (matcha_tts.py:154-162) and the estimator has
+//     no speaker input -- no decoder backward exists here;
+//   * e_dur is seen by the duration predictor alone, whose input is x.detach() (text_encoder.py:404): FiLM, channel LayerNorm, ReLU
+//     and the k5 convolutions of layers >= 1, then spk_proj transposed;
+//   * e_enc is concatenated behind the prenet (text_encoder.py:400): proj_m, the post-LN encoder layers and a token sum of the
+//     speaker channels; no prenet, embedding or weight gradient;
+//   * MAS runs under no_grad (matcha_tts.py:187): durations are constants of the step.
+//
+//   taped forward        the launch sequence of mtts_text_encoder_forward (encoder.hip), same launchers and arguments, with the
+//                        intermediates of every layer kept in buffers of their own
+//   seed_mu / seed_logw  the two Huber derivatives, token-of-frame rule and verdicts of score.hip
+//   ln_bwd_kernel        channel LayerNorm backward (+ SiLU' on the way in, FiLM, row mask, ReLU gate on the way out)
+//   attn_bwd_q / _kv     RoPE attention backward: dq per query thread, dk / dv per key thread, inverse rotation at the store
+//   gate / colsum        SiLU' and ReLU gates, fixed-order sums over an utterance's tokens
+//
+// Backward arithmetic: the data-gradient GEMMs run on the existing launchers with transposed / tap-reversed panels in NATIVE FP32
+// MFMA (GemmArgs::terms 0) whatever the context's forward arithmetic is: gradients are small numbers, and the fp16 two-term split
+// loses bits below the fp16 normal range.  The panels live in a buffer of their own (mtts_spk_grad_upload_weights), not in the
+// weight image.  The attention backward is plain fp32 FMA, one thread per query (key) row with the other side broadcast from LDS,
+// not the matrix pipe: 10 B H Tx^2 D flops per layer (0.15 GFLOP at B = 32, Tx = 128, 6 heads of 48; 10 GFLOP at Tx = 1024).  Measured
+// at B = 32 x 128 tokens (profiles/r11_spk_grad.md) it takes 1.23 ms of a 5.4 ms call beside 2.17 ms for all backward GEMMs: latency of
+// 192 two-wave workgroups, not arithmetic.  Splitting a row's keys over several threads or a 16x16x4 fp32 MFMA tiling (fits D = 48) is
+// the open next step.
+//
+// Every sum has a FIXED ORDER and there are no floating-point atomics (the rule of score.hip and mas.hip): a thread's serial run in
+// key / query / frame / token order, a wave butterfly, four phases combined in order.  Partitions depend on absolute token indices
+// only, so an utterance's gradient does not depend on its batch or on the padded shapes.
+#include "host.h"
+
+#include <string>
+
+namespace mtts {
+
+constexpr int SG_MAX_TX = 1024;           // tokens, as mtts_mas / score.hip (cumulative durations in LDS)
+constexpr size_t SG_SCORE_OFF = 256;      // the score workspace (status header first) inside this call's workspace: plan_spk_grad
+                                          // carves it right behind the 256-byte call header; mtts_spk_grad refuses to run otherwise
+constexpr int SG_MAX_LAYERS = 16;         // encoder / duration-predictor layers the per-layer tape has room for
+
+__device__ __forceinline__ float sg_wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ float sg_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
+__device__ __forceinline__ float sg_silu_grad(float z) {
+    const float sg = sg_sigmoid(z);
+    return sg * (1.0f + z * (1.0f - sg));
+}
+__device__ __forceinline__ float sg_clamp(float d, float delta) { return fminf(fmaxf(d, -delta), delta); }
+
+// ---------------------------------------------------------------------------------------------- channel LayerNorm backward
+// forward (norm_glue.hip layernorm_kernel):  xh = (x - mean) rstd;  a = xh gamma + beta;  [a = silu(a)];  [y = a fg_b + fb_b];  [y *= mask]
+struct LnBwdArgs {
+    const float* x = nullptr; int ldx = 0;        // the LayerNorm's input rows
+    const float* dy = nullptr; int lddy = 0;      // upstream gradient
+    float* dx = nullptr; int lddx = 0;
+    int M = 0, C = 0, T = 1;
+    const float* gamma = nullptr; const float* beta = nullptr;   // null: 1 / 0
+    float eps = 1e-5f;
+    int act = ACT_NONE;                           // ACT_SILU: the forward applied SiLU behind the affine
+    const float* film = nullptr;                  // [B][2C] gamma | beta of the FiLM
+    float* film_prod = nullptr;                   // [M][C]: dy * a, whose token sum is d gamma_b (d beta_b is the token sum of dy)
+    const float* mask = nullptr;                  // [M]: rows with 0 get a zero gradient
+    int gate = ACT_NONE;                          // ACT_RELU: x is a ReLU output, dx *= (x > 0)
+};
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdArgs p) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (row >= p.M) return;
+    const float* xr = p.x + (size_t)row * p.ldx;
+    const float* dr = p.dy + (size_t)row * p.lddy;
+    float* out = p.dx + (size_t)row * p.lddx;
+    float* fp = p.film_prod ? p.film_prod + (size_t)row * p.C : nullptr;
+    if (p.mask && p.mask[row] == 0.f) {
+        for (int c = lane; c < p.C; c += 64) { out[c] = 0.f; if (fp) fp[c] = 0.f; }
+        return;
+    }
+    float s = 0.f;
+    for (int c = lane; c < p.C; c += 64) s += xr[c];
+    const float mu = sg_wave_sum(s) / (float)p.C;
+    float q = 0.f;
+    for (int c = lane; c < p.C; c += 64) { const float d = xr[c] - mu; q += d * d; }
+    const float rs = 1.0f / sqrtf(sg_wave_sum(q) / (float)p.C + p.eps);
+    const float* film = p.film ? p.film + (size_t)(row / p.T) * 2 * p.C : nullptr;
+    // g = d loss / d xh
+    auto grad_xh = [&](int c, float xh, bool store) {
+        const float ga = p.gamma ? p.gamma[c] : 1.0f;
+        float a = xh * ga + (p.beta ? p.beta[c] : 0.f);
+        float d = dr[c];
+        if (film) {
+            const float av = p.act == ACT_SILU ? a * sg_sigmoid(a) : a;
+            if (store && fp) fp[c] = d * av;
+            d *= film[c];
+        }
+        if (p.act == ACT_SILU) d *= sg_silu_grad(a);
+        return d * ga;
+    };
+    float s1 = 0.f, s2 = 0.f;
+    for (int c = lane; c < p.C; c += 64) {
+        const float xh = (xr[c] - mu) * rs;
+        const float g = grad_xh(c, xh, true);
+        s1 += g;
+        s2 += g * xh;
+    }
+    const float m1 = sg_wave_sum(s1) / (float)p.C, m2 = sg_wave_sum(s2) / (float)p.C;
+    for (int c = lane; c < p.C; c += 64) {
+        const float xv = xr[c];
+        const float xh = (xv - mu) * rs;
+        float d = rs * ((grad_xh(c, xh, false) - m1) - xh * m2);
+        if (p.gate == ACT_RELU && !(xv > 0.f)) d = 0.f;
+        out[c] = d;
+    }
+}
+static hipError_t launch_ln_bwd(const LnBwdArgs& a, hipStream_t s) {
+    if (!a.x || !a.dy || !a.dx || a.M <= 0 || a.C <= 0 || a.T <= 0 || a.ldx < a.C || a.lddy < a.C || a.lddx < a.C) return hipErrorInvalidValue;
+    if (a.film_prod && !a.film) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ln_bwd_kernel, dim3((a.M + 3) / 4), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- gates
+// mode 0: g *= silu'(ref);  1: g *= (ref > 0) * mask[row], ref fp32 rows;  2: the same with ref a P16 image (32 heads then 32
+// residuals per 32-channel group): a ReLU output is positive iff its head is, or the head is zero and the residual positive
+__global__ void gate_kernel(float* __restrict__ g, int ldg, int M, int C, int mode, const float* __restrict__ ref, int ldref,
+                            const _Float16* __restrict__ ref16, int ld16, const float* __restrict__ mask) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)M * C) return;
+    const int row = (int)(i / C), c = (int)(i % C);
+    float* gp = g + (size_t)row * ldg + c;
+    if (mode == 0) { *gp = *gp * sg_silu_grad(ref[(size_t)row * ldref + c]); return; }
+    bool on;
+    if (mode == 1) on = ref[(size_t)row * ldref + c] > 0.f;
+    else {
+        const _Float16* grp = ref16 + (size_t)row * ld16 + (c >> 5) * 64 + (c & 31);
+        const float h = (float)grp[0], r = (float)grp[32];
+        on = h > 0.f || (h == 0.f && r > 0.f);
+    }
+    if (mask && mask[row] == 0.f) on = false;
+    if (!on) *gp = 0.f;
+}
+static hipError_t launch_gate(float* g, int ldg, int M, int C, int mode, const float* ref, int ldref, const _Float16* ref16, int ld16,
+                              const float* mask, hipStream_t s) {
+    if (!g || M <= 0 || C <= 0 || ldg < C || (mode == 2 ? (!ref16 || ld16 < 2 * C || (C & 31)) : (!ref || ldref < C))) return hipErrorInvalidValue;
+    const size_t n = (size_t)M * C;
+    hipLaunchKernelGGL(gate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, g, ldg, M, C, mode, ref, ldref, ref16, ld16, mask);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- token sums
+// dst[b][dcol0 + c] (+)= sum over t < len_b of src[(b T + t) ld + col0 + c], c < C: four phases t = p, p + 4, ... in token order,
+// combined as ((p0 + p1) + p2) + p3.  len null: T.  verdict (score.hip, [B][2]) != 0: the utterance's sums are zero.
+__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ src, int ld, int col0, int C, int T, const int64_t* __restrict__ len,
+                                                     const int32_t* __restrict__ verdict, float* __restrict__ dst, int ldd, int dcol0, int accumulate) {
+    __shared__ float part[4][64];
+    const int b = blockIdx.y, cl = threadIdx.x & 63, ph = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + cl;
+    int n = T;
+    if (len) { const int64_t v = len[b]; n = v < 0 ? 0 : v > T ? T : (int)v; }
+    if (verdict && verdict[2 * b] != 0) n = 0;
+    float s = 0.f;
+    if (c < C)
+        for (int t = ph; t < n; t += 4) s += src[((size_t)b * T + t) * ld + col0 + c];
+    part[ph][cl] = s;
+    __syncthreads();
+    if (ph == 0 && c < C) {
+        const float v = ((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl];
+        float* d = dst + (size_t)b * ldd + dcol0 + c;
+        *d = accumulate ? *d + v : v;
+    }
+}
+static hipError_t launch_colsum(const float* src, int ld, int col0, int C, int B, int T, const int64_t* len, const int32_t* verdict, float* dst,
+                                int ldd, int dcol0, int accumulate, hipStream_t s) {
+    if (!src || !dst || B <= 0 || T <= 0 || C <= 0 || ld < col0 + C || ldd < dcol0 + C) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(colsum_kernel, dim3((C + 63) / 64, B), dim3(256), 0, s, src, ld, col0, C, T, len, verdict, dst, ldd, dcol0, accumulate);
+    return hipGetLastError();
+}
+
+__global__ void copy_i32_kernel(const int32_t* __restrict__ src, int32_t* __restrict__ dst, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = src[i];
+}
+
+// ---------------------------------------------------------------------------------------------- loss seeds
+// d prior_sum_b / d mu_x[f, x] = - sum over the frames y of token x of clamp(y_fine[f, y] - mu_x[f, x], +-delta), written as the
+// channels-last rows of proj_m's output [B Tx][ldm] (zero-filled beforehand: rows beyond an utterance and the padding columns stay
+// zero).  Workgroup (f, b); the frames of a token are [cum[x-1], cum[x]) of the inclusive cumulative durations, which is the
+// token-of-frame rule of score_prior_dur_kernel read the other way round; an utterance score.hip refused (verdict) gets no seed.
+__global__ __launch_bounds__(256) void seed_mu_kernel(const float* __restrict__ mu_x, const float* __restrict__ y, const int32_t* __restrict__ dur,
+                                                      const int64_t* __restrict__ x_len, const int32_t* __restrict__ verdict, int F, int Tx,
+                                                      int Tm, float delta, float* __restrict__ g, int ldm) {
+    __shared__ int cum[SG_MAX_TX];
+    __shared__ int scan[256];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    if (verdict[2 * b] != 0) return;              // (uniform per workgroup)
+    const int txb = (int)x_len[b];                // verdict 0: 1 <= x_len <= Tx, durations in [0, Tm] that sum to y_len <= Tm
+    const int32_t* db = dur + (size_t)b * Tx;
+    int v[4], run = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = 4 * tid + k;
+        run += x < txb ? db[x] : 0;
+        v[k] = run;
+    }
+    scan[tid] = run;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {
+        const int add = tid >= off ? scan[tid - off] : 0;
+        __syncthreads();
+        scan[tid] += add;
+        __syncthreads();
+    }
+    const int base = tid ? scan[tid - 1] : 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cum[4 * tid + k] = base + v[k];
+    __syncthreads();
+    const float* yr = y + ((size_t)b * F + f) * Tm;
+    const float* mr = mu_x + ((size_t)b * F + f) * Tx;
+    for (int x = tid; x < txb; x += 256) {
+        const int y0 = x ? cum[x - 1] : 0, y1 = min(cum[x], Tm);
+        const float m = mr[x];
+        float acc = 0.f;
+        for (int t = y0; t < y1; ++t) acc += sg_clamp(yr[t] - m, delta);
+        g[((size_t)b * Tx + x) * ldm + f] = -acc;
+    }
+}
+// d dur_sum_b / d logw[x] = clamp(logw[x] - log(2 + dur[x]), +-delta) for x < Tx_b of an accepted utterance, else 0, carried through
+// the duration predictor's output projection (Conv1d(F, 1, 1) over masked rows, masked): gd[row][c] = seed * w_proj[c].  The
+// projection has one output channel, so its transposed "GEMM" is this outer product -- exact, no K = 1 panel.
+__global__ void seed_logw_kernel(const float* __restrict__ logw, const int32_t* __restrict__ dur, const int64_t* __restrict__ x_len,
+                                 const int32_t* __restrict__ verdict, const float* __restrict__ w_proj, int Tx, int Fd, float delta,
+                                 float* __restrict__ gd) {
+    const int row = blockIdx.x, b = row / Tx, x = row % Tx;
+    float seed = 0.f;
+    if (verdict[2 * b] == 0 && x < (int)x_len[b]) seed = sg_clamp(logw[row] - logf(2.0f + (float)dur[row]), delta);
+    for (int c = threadIdx.x; c < Fd; c += blockDim.x) gd[(size_t)row * Fd + c] = seed * w_proj[c];
+}
+
+// ---------------------------------------------------------------------------------------------- RoPE attention backward
+// Encoder SDPA (reference text_encoder.py:220-237): boolean query x key mask, rotary on the first D / 2 dims of q and k.  Inputs are
+// the saved rows AFTER the rotation (qkv [B T][3 H D]: q | k | v sections, head h at h D), the attention output o and the upstream
+// gradient d_o [B T][H D].  With P = softmax(scale q k^T) over the keys j < len_b, Delta_i = <dO_i, O_i>:
+//   dS = P o (dO V^T - Delta),  dq = scale dS K,  dk = scale dS^T Q,  dv = P^T dO,
+// then the transposed rotation on dq and dk.  Rows at or beyond len_b get zeros and are never read as data.
+//   attn_bwd_q_kernel:  thread = query i; pass 1 the running maximum and sum over the keys in key order (kept for the second kernel
+//                       in stats [B][H][T][3] = (max, 1 / sum, Delta)), pass 2 dq in key order.  K / V tiles of 32 rows in LDS, read
+//                       by all threads at the same address (broadcast).
+//   attn_bwd_kv_kernel: thread = key j; dk, dv in query order from Q / dO tiles and the statistics.
+// Both recompute p = exp(s - max) / sum with the same expression, so the two kernels see the same probabilities.
+constexpr int AB_ROWS = 128, AB_TILE = 32;
+struct AttnBwdArgs {
+    const float* qkv; const float* o; const float* d_o; const int64_t* len;
+    int B, T, H, D;
+    float scale;
+    const float* cos_t; const float* sin_t;       // [>= T][D / 2]
+    float* dqkv; float* stats;
+};
+template <int D>
+__device__ __forceinline__ void unrope_store(const float (&acc)[D], int t, const float* cos_t, const float* sin_t, float* dst) {
+    constexpr int R = D / 2, HALF = R / 2;
+    float out[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) out[k] = acc[k];
+#pragma unroll
+    for (int k = 0; k < HALF; ++k) {
+        const float c0 = cos_t[(size_t)t * R + k], s0 = sin_t[(size_t)t * R + k];
+        const float c1 = cos_t[(size_t)t * R + k + HALF], s1 = sin_t[(size_t)t * R + k + HALF];
+        // forward: y_k = a c0 - b s0, y_{k+half} = b c1 + a s1
+        out[k] = acc[k] * c0 + acc[k + HALF] * s1;
+        out[k + HALF] = acc[k + HALF] * c1 - acc[k] * s0;
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) dst[k] = out[k];
+}
+template <int D>
+__global__ __launch_bounds__(AB_ROWS) void attn_bwd_q_kernel(const AttnBwdArgs p) {
+    __shared__ float Ks[AB_TILE][D];
+    __shared__ float Vs[AB_TILE][D];
+    const int b = blockIdx.z, h = blockIdx.y, tid = threadIdx.x;
+    const int i = blockIdx.x * AB_ROWS + tid;
+    const int64_t l64 = p.len[b];
+    const int len = l64 < 0 ? 0 : l64 > p.T ? p.T : (int)l64;
+    const int ldq = 3 * p.H * D, ldo = p.H * D;
+    const bool live = i < len;
+    const int nkeys = blockIdx.x * AB_ROWS < len ? len : 0;        // a workgroup whose rows all lie beyond the utterance only writes zeros
+    float q[D], go[D], acc[D];
+    float delta = 0.f;
+    if (live) {
+        const float* qr = p.qkv + ((size_t)b * p.T + i) * ldq + h * D;
+        const float* gr = p.d_o + ((size_t)b * p.T + i) * ldo + h * D;
+        const float* orow = p.o + ((size_t)b * p.T + i) * ldo + h * D;
+#pragma unroll
+        for (int k = 0; k < D; ++k) { q[k] = qr[k]; go[k] = gr[k]; delta = fmaf(go[k], orow[k], delta); }
+    } else {
+#pragma unroll
+        for (int k = 0; k < D; ++k) { q[k] = 0.f; go[k] = 0.f; }
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) acc[k] = 0.f;
+    float m = -INFINITY, l = 0.f;
+    for (int pass = 0; pass < 2; ++pass) {
+        const float inv = pass ? 1.0f / l : 0.f;
+        for (int j0 = 0; j0 < nkeys; j0 += AB_TILE) {
+            __syncthreads();
+            for (int e = tid; e < AB_TILE * D; e += AB_ROWS) {
+                const int jj = e / D, k = e % D;
+                const int j = j0 + jj;
+                const float* base = p.qkv + ((size_t)b * p.T + (j < len ? j : 0)) * ldq + h * D + k;
+                Ks[jj][k] = j < len ? base[p.H * D] : 0.f;
+                Vs[jj][k] = j < len ? base[2 * p.H * D] : 0.f;
+            }
+            __syncthreads();
+            const int nj = min(AB_TILE, len - j0);
+            for (int jj = 0; jj < nj; ++jj) {
+                float s = 0.f;
+#pragma unroll
+                for (int k = 0; k < D; ++k) s = fmaf(q[k], Ks[jj][k], s);
+                s *= p.scale;
+                if (pass == 0) {
+                    const float mn = fmaxf(m, s);
+                    l = l * expf(m - mn) + expf(s - mn);
+                    m = mn;
+                } else {
+                    const float pr = expf(s - m) * inv;
+                    float dp = 0.f;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) dp = fmaf(go[k], Vs[jj][k], dp);
+                    const float ds = pr * (dp - delta) * p.scale;
+#pragma unroll
+                    for (int k = 0; k < D; ++k) acc[k] = fmaf(ds, Ks[jj][k], acc[k]);
+                }
+            }
+        }
+    }
+    if (i < p.T) {
+        float* dst = p.dqkv + ((size_t)b * p.T + i) * ldq + h * D;
+        if (live) {
+            unrope_store<D>(acc, i, p.cos_t, p.sin_t, dst);
+            float* st = p.stats + (((size_t)b * p.H + h) * p.T + i) * 3;
+            st[0] = m; st[1] = 1.0f / l; st[2] = delta;
+        } else {
+#pragma unroll
+            for (int k = 0; k < D; ++k) dst[k] = 0.f;
+        }
+    }
+}
+template <int D>
+__global__ __launch_bounds__(AB_ROWS) void attn_bwd_kv_kernel(const AttnBwdArgs p) {
+    __shared__ float Qs[AB_TILE][D];
+    __shared__ float Gs[AB_TILE][D];
+    __shared__ float St[AB_TILE][3];
+    const int b = blockIdx.z, h = blockIdx.y, tid = threadIdx.x;
+    const int j = blockIdx.x * AB_ROWS + tid;
+    const int64_t l64 = p.len[b];
+    const int len = l64 < 0 ? 0 : l64 > p.T ? p.T : (int)l64;
+    const int ldq = 3 * p.H * D, ldo = p.H * D;
+    const bool live = j < len;
+    const int nqueries = blockIdx.x * AB_ROWS < len ? len : 0;     // as in attn_bwd_q_kernel
+    float kr[D], vr[D], dk[D], dv[D];
+    if (live) {
+        const float* base = p.qkv + ((size_t)b * p.T + j) * ldq + h * D;
+#pragma unroll
+        for (int k = 0; k < D; ++k) { kr[k] = base[p.H * D + k]; vr[k] = base[2 * p.H * D + k]; }
+    } else {
+#pragma unroll
+        for (int k = 0; k < D; ++k) { kr[k] = 0.f; vr[k] = 0.f; }
+    }
+#pragma unroll
+    for (int k = 0; k < D; ++k) { dk[k] = 0.f; dv[k] = 0.f; }
+    for (int i0 = 0; i0 < nqueries; i0 += AB_TILE) {
+        __syncthreads();
+        for (int e = tid; e < AB_TILE * D; e += AB_ROWS) {
+            const int ii = e / D, k = e % D;
+            const int i = i0 + ii;
+            const size_t r = (size_t)b * p.T + (i < len ? i : 0);
+            Qs[ii][k] = i < len ? p.qkv[r * ldq + h * D + k] : 0.f;
+            Gs[ii][k] = i < len ? p.d_o[r * ldo + h * D + k] : 0.f;
+        }
+        if (tid < AB_TILE * 3) {
+            const int ii = tid / 3, w = tid % 3;
+            const int i = i0 + ii;
+            St[ii][w] = i < len ? p.stats[(((size_t)b * p.H + h) * p.T + i) * 3 + w] : 0.f;
+        }
+        __syncthreads();
+        const int ni = min(AB_TILE, len - i0);
+        for (int ii = 0; ii < ni; ++ii) {
+            float s = 0.f, dp = 0.f;
+#pragma unroll
+            for (int k = 0; k < D; ++k) { s = fmaf(Qs[ii][k], kr[k], s); dp = fmaf(Gs[ii][k], vr[k], dp); }
+            s *= p.scale;
+            const float pr = expf(s - St[ii][0]) * St[ii][1];
+            const float ds = pr * (dp - St[ii][2]) * p.scale;
+#pragma unroll
+            for (int k = 0; k < D; ++k) { dv[k] = fmaf(pr, Gs[ii][k], dv[k]); dk[k] = fmaf(ds, Qs[ii][k], dk[k]); }
+        }
+    }
+    if (j < p.T) {
+        float* dst = p.dqkv + ((size_t)b * p.T + j) * ldq + h * D;
+        if (live) {
+            unrope_store<D>(dk, j, p.cos_t, p.sin_t, dst + p.H * D);
+#pragma unroll
+            for (int k = 0; k < D; ++k) dst[2 * p.H * D + k] = dv[k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < D; ++k) { dst[p.H * D + k] = 0.f; dst[2 * p.H * D + k] = 0.f; }
+        }
+    }
+}
+template <int D>
+static void attn_bwd_launch(const AttnBwdArgs& a, hipStream_t s) {
+    const dim3 grid((a.T + AB_ROWS - 1) / AB_ROWS, a.H, a.B);
+    hipLaunchKernelGGL(attn_bwd_q_kernel<D>, grid, dim3(AB_ROWS), 0, s, a);
+    hipLaunchKernelGGL(attn_bwd_kv_kernel<D>, grid, dim3(AB_ROWS), 0, s, a);
+}
+static bool attn_bwd_head_dim_ok(int D) { return D >= 8 && D <= 64 && D % 8 == 0; }
+static hipError_t launch_attn_bwd(const AttnBwdArgs& a, hipStream_t s) {
+    if (!a.qkv || !a.o || !a.d_o || !a.len || !a.cos_t || !a.sin_t || !a.dqkv || !a.stats || a.B <= 0 || a.B > 65535 || a.H <= 0 ||
+        a.H > 65535 || a.T <= 0 || a.T > SG_MAX_TX || !attn_bwd_head_dim_ok(a.D))
+        return hipErrorInvalidValue;
+    switch (a.D) {
+        case 8: attn_bwd_launch<8>(a, s); break;
+        case 16: attn_bwd_launch<16>(a, s); break;
+        case 24: attn_bwd_launch<24>(a, s); break;
+        case 32: attn_bwd_launch<32>(a, s); break;
+        case 40: attn_bwd_launch<40>(a, s); break;
+        case 48: attn_bwd_launch<48>(a, s); break;
+        case 56: attn_bwd_launch<56>(a, s); break;
+        default: attn_bwd_launch<64>(a, s); break;
+    }
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- backward panels (host)
+// The transposed weight of a Linear / Conv1d(k, pad k / 2) in torch layout: w [N][C][k] -> wt [C][N][k] with the taps reversed, so
+// that the data gradient is the same centred-tap GEMM with in / out channels swapped.  Cp >= C pads the NEW input channels (zeros).
+static std::vector<float> transposed(const std::vector<float>& w, int N, int C, int k, int Np = 0) {
+    Np = Np ? Np : N;
+    std::vector<float> t((size_t)C * Np * k, 0.f);
+    for (int n = 0; n < N; ++n)
+        for (int c = 0; c < C; ++c)
+            for (int j = 0; j < k; ++j) t[((size_t)c * Np + n) * k + j] = w[((size_t)n * C + c) * k + (k - 1 - j)];
+    return t;
+}
+
+int pack_spk_grad(mtts_ctx* c) {
+    const mtts_config& g = c->cfg;
+    Component& G = c->grad;
+    G.image.clear();
+    G.gemm_terms = 0;             // native fp32 MFMA for every backward GEMM (file header)
+    G.packed = false;
+    G.uploaded = false;
+    Packer P(&G);
+    SpkGradW& W = c->gradw;
+    W = SpkGradW();
+    const int nch = g.enc_channels, Sd = g.spk_emb_dim, Hd = nch + Sd, Fd = g.dp_filter, Ff = g.enc_filter;
+    auto raw = [&](const std::string& key, size_t numel) -> const std::vector<float>* {
+        auto it = c->raw.find(key);
+        if (it == c->raw.end()) { P.fail("missing tensor " + key); return nullptr; }
+        if (it->second.size() != numel) { P.fail("tensor " + key + " has an unexpected size"); return nullptr; }
+        return &it->second;
+    };
+    auto tpanel = [&](const std::string& key, int N, int C, int k, int Np = 0) {
+        const auto* w = raw(key, (size_t)N * C * k);
+        if (!w) return Panel();
+        const std::vector<float> t = transposed(*w, N, C, k, Np);
+        return P.panel_from(t.data(), nullptr, k == 1 ? 0 : 1, C, Np ? Np : N, k);
+    };
+    auto S = [](const std::string& a, int i, const std::string& b) { return a + std::to_string(i) + b; };
+    W.pm2T = tpanel("encoder.proj_m.2.weight", g.n_feats, nch, 1, round_up(g.n_feats, 4));
+    W.pm0T = tpanel("encoder.proj_m.0.weight", nch, Hd, 1);
+    for (int l = 0; l < g.enc_layers && P.ok; ++l) {
+        const std::string a = S("encoder.encoder.attn_layers.", l, "."), f = S("encoder.encoder.ffn_layers.", l, ".");
+        W.oT.push_back(tpanel(a + "conv_o.weight", Hd, Hd, 1));
+        const auto* wq = raw(a + "conv_q.weight", (size_t)Hd * Hd);
+        const auto* wk = raw(a + "conv_k.weight", (size_t)Hd * Hd);
+        const auto* wv = raw(a + "conv_v.weight", (size_t)Hd * Hd);
+        if (!wq || !wk || !wv) break;
+        std::vector<float> t((size_t)Hd * 3 * Hd);
+        const std::vector<float>* parts[3] = {wq, wk, wv};
+        for (int part = 0; part < 3; ++part)
+            for (int n = 0; n < Hd; ++n)
+                for (int cc = 0; cc < Hd; ++cc) t[(size_t)cc * 3 * Hd + part * Hd + n] = (*parts[part])[(size_t)n * Hd + cc];
+        W.qkvT.push_back(P.panel_from(t.data(), nullptr, 0, Hd, 3 * Hd, 1));
+        W.ffn2T.push_back(tpanel(f + "conv_2.weight", Hd, Ff, g.enc_kernel));
+        W.ffn1T.push_back(tpanel(f + "conv_1.weight", Ff, Hd, g.enc_kernel));
+    }
+    for (int i = 0; i < g.dp_layers && P.ok; ++i)       // (layer 0 reads x.detach(): no data gradient; an empty panel keeps the index)
+        W.dp_convT.push_back(i == 0 ? Panel() : tpanel(S("encoder.proj_w.conv_layers.", i, ".weight"), Fd, Fd, g.dp_kernel));
+    W.filmT = tpanel("encoder.proj_w.spk_proj.weight", 2 * Fd, Sd, 1);
+    if (const auto* w = raw("encoder.proj_w.proj.weight", Fd)) {
+        W.dp_proj.off = P.alloc(Fd);
+        W.dp_proj.n = Fd;
+        std::memcpy(&G.image[W.dp_proj.off], w->data(), Fd * sizeof(float));
+    }
+    if (!P.ok) { set_error("mtts_spk_grad weights: " + P.why); return -1; }
+    G.packed = true;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- plan
+struct SgBufs {
+    float *X0, *P1, *P2, *Y, *PMpre, *PM, *MU, *FILM, *D1, *D2, *mu_x, *logw, *xm;
+    float *Hin[SG_MAX_LAYERS + 1], *QKV[SG_MAX_LAYERS], *ATT[SG_MAX_LAYERS], *S1[SG_MAX_LAYERS], *H1[SG_MAX_LAYERS], *F1[SG_MAX_LAYERS],
+        *S2[SG_MAX_LAYERS], *DY[SG_MAX_LAYERS];       // per layer (fixed arrays: no host allocation in the launch path)
+    float *GA, *GB, *GF, *GQKV, *GATT, *stats, *GMU, *GPM, *GDA, *GDB, *FPROD, *DFILM;
+    int32_t* dur;
+    void *score, *mas;
+    size_t score_bytes = 0, mas_bytes = 0, off_score = 0, off_mu_x = 0, off_logw = 0, off_xm = 0;
+};
+static void plan_spk_grad(const mtts_ctx* c, int B, int Tx, int Tm, WS& ws, SgBufs& e) {
+    const mtts_config& g = c->cfg;
+    const size_t M = (size_t)B * Tx;
+    const int nch = g.enc_channels, Hd = nch + g.spk_emb_dim, F = g.dp_filter, ldm = round_up(g.n_feats, 4);
+    (void)ws.bytes(256);                 // header: the call's range flag (begin_call)
+    e.score_bytes = (size_t)mtts_score_workspace_bytes(B, Tx, Tm);
+    e.score = ws.bytes(e.score_bytes);   // must land at SG_SCORE_OFF, where mtts_spk_grad_status looks (checked by mtts_spk_grad)
+    e.off_score = ws.off - e.score_bytes;
+    e.mas_bytes = (size_t)mtts_mas_workspace_bytes(B, Tx, Tm);
+    e.mas = ws.bytes(e.mas_bytes);
+    e.mu_x = ws.f(M * g.n_feats); e.off_mu_x = ws.off - M * g.n_feats * sizeof(float);
+    e.logw = ws.f(M); e.off_logw = ws.off - M * sizeof(float);
+    e.xm = ws.f(M); e.off_xm = ws.off - M * sizeof(float);
+    e.dur = static_cast<int32_t*>(ws.bytes(M * sizeof(int32_t)));
+    e.X0 = ws.f(M * nch); e.P1 = ws.f(M * nch); e.P2 = ws.f(M * nch); e.Y = ws.f(M * nch);
+    e.PMpre = ws.f(M * nch); e.PM = ws.f(M * nch); e.MU = ws.f(M * ldm);
+    e.FILM = ws.f((size_t)B * 2 * F); e.D1 = ws.f(M * F); e.D2 = ws.f(M * F);
+    const int L = std::min(g.enc_layers, SG_MAX_LAYERS), Ld = std::min(g.dp_layers, SG_MAX_LAYERS);      // (more is refused: sg_layers_ok)
+    for (int l = 0; l <= L; ++l) e.Hin[l] = ws.f(M * Hd);
+    for (int l = 0; l < L; ++l) {
+        e.QKV[l] = ws.f(M * 3 * Hd); e.ATT[l] = ws.f(M * Hd); e.S1[l] = ws.f(M * Hd); e.H1[l] = ws.f(M * Hd);
+        e.F1[l] = ws.f(M * g.enc_filter); e.S2[l] = ws.f(M * Hd);
+    }
+    for (int i = 0; i < Ld; ++i) e.DY[i] = ws.f(M * F);
+    e.GA = ws.f(M * Hd); e.GB = ws.f(M * Hd); e.GF = ws.f(M * g.enc_filter); e.GQKV = ws.f(M * 3 * Hd); e.GATT = ws.f(M * Hd);
+    e.stats = ws.f((size_t)B * g.enc_heads * Tx * 3);
+    e.GMU = ws.f(M * ldm); e.GPM = ws.f(M * nch);
+    e.GDA = ws.f(M * F); e.GDB = ws.f(M * F); e.FPROD = ws.f(M * F); e.DFILM = ws.f((size_t)B * 2 * F);
+}
+static bool sg_layers_ok(const char* who, const mtts_ctx* c) {
+    if (c->cfg.enc_layers > SG_MAX_LAYERS || c->cfg.dp_layers > SG_MAX_LAYERS) {
+        set_error(std::string(who) + ": more than 16 encoder or duration-predictor layers");
+        return false;
+    }
+    return true;
+}
+static bool sg_shape_ok(const char* who, int B, int Tx, int Tm) {
+    if (B < 1 || B > 65535) { set_error(std::string(who) + ": B must be in [1, 65535]"); return false; }
+    if (Tx < 1 || Tx > SG_MAX_TX) { set_error(std::string(who) + ": Tx must be in [1, 1024]"); return false; }
+    if (Tm < Tx) { set_error(std::string(who) + ": Tm < Tx (no monotone path gives every token a frame)"); return false; }
+    if (Tm > (1 << 20)) { set_error(std::string(who) + ": Tm too large"); return false; }
+    return true;
+}
+
+}  // namespace mtts
+
+using namespace mtts;
+
+extern "C" {
+
+int64_t mtts_spk_grad_weights_bytes(mtts_ctx* c) {
+    if (!c) { set_error("mtts_spk_grad_weights_bytes: null context"); return -1; }
+    if (!c->grad.packed && pack_spk_grad(c)) return -1;
+    return (int64_t)(c->grad.image.size() * sizeof(float));
+}
+
+int mtts_spk_grad_upload_weights(mtts_ctx* c, void* d_buf, int64_t bytes) {
+    if (!c || !d_buf) { set_error("mtts_spk_grad_upload_weights: null argument"); return -1; }
+    if (!c->grad.packed && pack_spk_grad(c)) return -1;
+    Component& G = c->grad;
+    if ((size_t)bytes < G.image.size() * sizeof(float)) { set_error("mtts_spk_grad_upload_weights: buffer too small (mtts_spk_grad_weights_bytes)"); return -1; }
+    HIP_OK(hipMemcpy(d_buf, G.image.data(), G.image.size() * sizeof(float), hipMemcpyHostToDevice));
+    G.d_image = static_cast<float*>(d_buf);
+    G.uploaded = true;
+    return 0;
+}
+
+int64_t mtts_spk_grad_workspace_bytes(mtts_ctx* c, int B, int Tx, int Tm) {
+    if (!c) { set_error("mtts_spk_grad_workspace_bytes: null context"); return -1; }
+    if (!sg_shape_ok("mtts_spk_grad_workspace_bytes", B, Tx, Tm) || !sg_layers_ok("mtts_spk_grad_workspace_bytes", c)) return -1;
+    WS ws(nullptr, 0);
+    SgBufs e;
+    plan_spk_grad(c, B, Tx, Tm, ws, e);
+    return (int64_t)ws.off + 256;
+}
+
+// Byte offset inside the workspace of what the taped forward of the latest call left: which 0 mu_x [B][F][Tx], 1 logw [B][Tx],
+// 2 x_mask [B][Tx] (what mtts_text_encoder_forward returns, bit for bit).
+int64_t mtts_spk_grad_tape_offset(mtts_ctx* c, int B, int Tx, int Tm, int which) {
+    if (!c) { set_error("mtts_spk_grad_tape_offset: null context"); return -1; }
+    if (!sg_shape_ok("mtts_spk_grad_tape_offset", B, Tx, Tm) || !sg_layers_ok("mtts_spk_grad_tape_offset", c)) return -1;
+    if (which < 0 || which > 2) { set_error("mtts_spk_grad_tape_offset: which must be 0 (mu_x), 1 (logw) or 2 (x_mask)"); return -1; }
+    WS ws(nullptr, 0);
+    SgBufs e;
+    plan_spk_grad(c, B, Tx, Tm, ws, e);
+    return (int64_t)(which == 0 ? e.off_mu_x : which == 1 ? e.off_logw : e.off_xm);
+}
+
+int mtts_spk_grad(mtts_ctx* c, const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur,
+                  const float* d_y_fine, const int64_t* d_y_fine_lengths, const int32_t* d_durations_in, float delta_prior,
+                  float delta_dur, int B, int Tx, int Tm, float* d_g_enc, float* d_g_dur, float* d_prior_sum, float* d_dur_sum,
+                  int32_t* d_durations_out, void* d_grad_buf, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!c || !d_x || !d_x_lengths || !d_e_enc || !d_e_dur || !d_y_fine || !d_y_fine_lengths || !d_g_enc || !d_g_dur || !d_prior_sum ||
+        !d_dur_sum || !d_grad_buf || !d_ws) {
+        set_error("mtts_spk_grad: null argument");
+        return -1;
+    }
+    if (!sg_shape_ok("mtts_spk_grad", B, Tx, Tm) || !sg_layers_ok("mtts_spk_grad", c)) return -1;
+    if (!(delta_prior > 0.f) || !(delta_dur > 0.f)) { set_error("mtts_spk_grad: the Huber thresholds must be positive"); return -1; }
+    CTX_GUARD(c);
+    const mtts_config& g = c->cfg;
+    WS ws(d_ws, (size_t)ws_bytes);
+    SgBufs e;
+    plan_spk_grad(c, B, Tx, Tm, ws, e);
+    if (ws.overflow || ws_bytes < (int64_t)ws.off) { set_error("mtts_spk_grad: workspace too small (mtts_spk_grad_workspace_bytes)"); return -1; }
+    if (reinterpret_cast<uintptr_t>(d_ws) & 15) { set_error("mtts_spk_grad: workspace must be 16-byte aligned"); return -1; }
+    if (e.off_score != SG_SCORE_OFF) { set_error("mtts_spk_grad: the score workspace is not where mtts_spk_grad_status reads it"); return -1; }
+    if (!c->grad.packed || !c->grad.uploaded || c->grad.d_image != d_grad_buf) {
+        set_error("mtts_spk_grad: backward panels not uploaded (mtts_spk_grad_upload_weights into d_grad_buf)");
+        return -1;
+    }
+    RET_IF(check_ready(c));
+    const EncW& E = c->enc;
+    const SpkGradW& GW = c->gradw;
+    const Component* G = &c->grad;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int nch = g.enc_channels, Sd = g.spk_emb_dim, Hd = nch + Sd, F = g.dp_filter, M = B * Tx, nf = g.n_feats;
+    const int dh = Hd / g.enc_heads, d_rope = dh / 2, ldm = round_up(nf, 4), L = g.enc_layers;
+    if ((size_t)Tx * d_rope > (size_t)E.rope_cos.n) { set_error("Phonetic representation too long, exceeds RoPE cache size"); return -1; }
+    if (!attn_bwd_head_dim_ok(dh)) { set_error("mtts_spk_grad: the encoder's head dim must be a multiple of 8 (<= 64)"); return -1; }
+    RET_IF(begin_call(c, d_ws, s));
+    float* xm = e.xm;
+
+    // ================================================================ taped forward: encoder.hip's launches, buffers per layer
+    LAUNCH(c, 2, 0, s, launch_seq_mask(d_x_lengths, B, Tx, xm, s));
+    LAUNCH(c, 2, 0, s, launch_embedding(d_x, W(c, E.emb.off), M, nch, sqrtf((float)nch), xm, e.X0, nch, s));
+    const float* cur = e.X0;
+    for (int i = 0; i < g.prenet_layers; ++i) {
+        GemmArgs a;
+        panel_args(c, E.pre_conv[i], a); rows_plain(a, B, Tx); taps_centered(a, g.prenet_kernel);
+        a.a0 = cur; a.lda0 = nch; a.c0 = nch; a.a_mask = xm; a.out = e.Y; a.ldc = nch;
+        RET_IF(run_gemm(c, a, s));
+        float* dst = (i & 1) ? e.P2 : e.P1;
+        LayerNormArgs ln;
+        ln.x = e.Y; ln.ldx = nch; ln.y = dst; ln.ldy = nch; ln.M = M; ln.C = nch; ln.T = Tx;
+        ln.gamma = W(c, E.pre_g[i].off); ln.beta = W(c, E.pre_b[i].off); ln.act = ACT_SILU;
+        LAUNCH(c, 2, 0, s, launch_layernorm(ln, s));
+        cur = dst;
+    }
+    {
+        GemmArgs a;
+        panel_args(c, E.pre_proj, a); rows_plain(a, B, Tx);
+        a.a0 = cur; a.lda0 = nch; a.c0 = nch; a.out_mask = xm; a.res = e.X0; a.ldr = nch; a.out = e.Hin[0]; a.ldc = Hd;
+        RET_IF(run_gemm(c, a, s));
+    }
+    LAUNCH(c, 2, 0, s, launch_bcast_rows(d_e_enc, B, Tx, Sd, xm, e.Hin[0], Hd, nch, s));
+    const bool ffn_p16 = c->sw.p16_on && c->gemm_terms == 2 && (g.enc_filter % 32) == 0;
+    for (int l = 0; l < L; ++l) {
+        GemmArgs q;
+        panel_args(c, E.qkv[l], q); rows_plain(q, B, Tx);
+        q.a0 = e.Hin[l]; q.lda0 = Hd; q.c0 = Hd; q.out = e.QKV[l]; q.ldc = 3 * Hd;
+        RET_IF(run_gemm(c, q, s));
+        LAUNCH(c, 2, 0, s, launch_rope(e.QKV[l], B, Tx, g.enc_heads, dh, d_rope, W(c, E.rope_cos.off), W(c, E.rope_sin.off), s));
+        AttnArgs at;
+        at.qkv = e.QKV[l]; at.mask = xm; at.out = e.ATT[l]; at.B = B; at.T = Tx; at.H = g.enc_heads; at.D = dh;
+        at.scale = 1.0f / sqrtf((float)dh); at.mask_mode = 1;
+        RET_IF(run_attn(c, at, s));
+        GemmArgs o;
+        panel_args(c, E.o[l], o); rows_plain(o, B, Tx);
+        o.a0 = e.ATT[l]; o.lda0 = Hd; o.c0 = Hd; o.res = e.Hin[l]; o.ldr = Hd; o.out = e.S1[l]; o.ldc = Hd;
+        RET_IF(run_gemm(c, o, s));
+        LayerNormArgs n1;
+        n1.x = e.S1[l]; n1.ldx = Hd; n1.y = e.H1[l]; n1.ldy = Hd; n1.M = M; n1.C = Hd; n1.T = Tx;
+        n1.gamma = W(c, E.n1_g[l].off); n1.beta = W(c, E.n1_b[l].off); n1.mask = xm;
+        LAUNCH(c, 2, 0, s, launch_layernorm(n1, s));
+        _Float16* F16 = reinterpret_cast<_Float16*>(e.F1[l]);
+        GemmArgs f1;
+        panel_args(c, E.ffn1[l], f1); rows_plain(f1, B, Tx); taps_centered(f1, g.enc_kernel);
+        f1.a0 = e.H1[l]; f1.lda0 = Hd; f1.c0 = Hd; f1.act = ACT_RELU;
+        if (ffn_p16) { f1.out16 = F16; f1.ld16 = 2 * g.enc_filter; f1.out16_mask = xm; }
+        else { f1.out = e.F1[l]; f1.ldc = g.enc_filter; }
+        RET_IF(run_gemm(c, f1, s));
+        GemmArgs f2;
+        panel_args(c, E.ffn2[l], f2); rows_plain(f2, B, Tx); taps_centered(f2, g.enc_kernel);
+        if (ffn_p16) { f2.a16_0 = F16; f2.lda16_0 = 2 * g.enc_filter; f2.c0 = g.enc_filter; f2.fast16 = false; }
+        else { f2.a0 = e.F1[l]; f2.lda0 = g.enc_filter; f2.c0 = g.enc_filter; f2.a_mask = xm; }
+        f2.out_mask = xm; f2.res = e.H1[l]; f2.ldr = Hd; f2.out = e.S2[l]; f2.ldc = Hd;
+        RET_IF(run_gemm(c, f2, s));
+        LayerNormArgs n2 = n1;
+        n2.x = e.S2[l]; n2.y = e.Hin[l + 1];
+        n2.gamma = W(c, E.n2_g[l].off); n2.beta = W(c, E.n2_b[l].off);
+        LAUNCH(c, 2, 0, s, launch_layernorm(n2, s));
+    }
+    const float* Hout = e.Hin[L];
+    {
+        GemmArgs a;
+        panel_args(c, E.pm0, a); rows_plain(a, B, Tx);
+        a.a0 = Hout; a.lda0 = Hd; a.c0 = Hd; a.act = ACT_SILU; a.out = e.PM; a.ldc = nch;
+        RET_IF(run_gemm(c, a, s));
+        GemmArgs pre = a;               // the same product without the activation: proj_m's pre-SiLU rows for the backward
+        pre.act = ACT_NONE; pre.out = e.PMpre;
+        RET_IF(run_gemm(c, pre, s));
+        GemmArgs b;
+        panel_args(c, E.pm2, b); rows_plain(b, B, Tx);
+        b.a0 = e.PM; b.lda0 = nch; b.c0 = nch; b.out_mask = xm; b.out = e.MU; b.ldc = ldm;
+        RET_IF(run_gemm(c, b, s));
+        LAUNCH(c, 2, 0, s, launch_cl_to_cf(e.MU, ldm, B, nf, Tx, e.mu_x, Tx, 1.0f, 0.0f, s));
+    }
+    {
+        GemmArgs fm;
+        panel_args(c, E.film, fm); rows_plain(fm, B, 1);
+        fm.a0 = d_e_dur; fm.lda0 = Sd; fm.c0 = Sd; fm.out = e.FILM; fm.ldc = 2 * F;
+        RET_IF(run_gemm(c, fm, s));
+        const float* dcur = Hout;
+        int dc = Hd;
+        for (int i = 0; i < g.dp_layers; ++i) {
+            GemmArgs a;
+            panel_args(c, E.dp_conv[i], a); rows_plain(a, B, Tx); taps_centered(a, g.dp_kernel);
+            a.a0 = dcur; a.lda0 = dc; a.c0 = dc; a.a_mask = xm; a.act = ACT_RELU; a.out = e.DY[i]; a.ldc = F;
+            RET_IF(run_gemm(c, a, s));
+            float* dst = (i & 1) ? e.D2 : e.D1;
+            LayerNormArgs ln;
+            ln.x = e.DY[i]; ln.ldx = F; ln.y = dst; ln.ldy = F; ln.M = M; ln.C = F; ln.T = Tx;
+            ln.gamma = W(c, E.dp_g[i].off); ln.beta = W(c, E.dp_b[i].off); ln.film = e.FILM;
+            LAUNCH(c, 2, 0, s, launch_layernorm(ln, s));
+            dcur = dst;
+            dc = F;
+        }
+        GemmArgs p;
+        panel_args(c, E.dp_proj, p); rows_plain(p, B, Tx);
+        p.a0 = dcur; p.lda0 = dc; p.c0 = dc; p.a_mask = xm; p.out_mask = xm; p.out = e.logw; p.ldc = 1;
+        RET_IF(run_gemm(c, p, s));
+    }
+
+    // ================================================================ alignment (constant of the step) and the two sums
+    const int32_t* dur = d_durations_in;
+    if (!dur) {
+        int32_t* dst = d_durations_out ? d_durations_out : e.dur;
+        RET_IF(mtts_mas(nullptr, e.mu_x, d_y_fine, d_x_lengths, d_y_fine_lengths, B, nf, Tx, Tm, dst, nullptr, nullptr, e.mas,
+                        (int64_t)e.mas_bytes, stream));
+        dur = dst;
+    } else if (d_durations_out && d_durations_out != d_durations_in) {
+        hipLaunchKernelGGL(copy_i32_kernel, dim3((M + 255) / 256), dim3(256), 0, s, d_durations_in, d_durations_out, (size_t)M);
+        HIP_OK(hipGetLastError());
+    }
+    RET_IF(mtts_score_prior_dur(e.mu_x, e.logw, dur, d_y_fine, d_x_lengths, d_y_fine_lengths, B, nf, Tx, Tm, delta_prior, delta_dur,
+                                d_prior_sum, d_dur_sum, nullptr, nullptr, e.score, (int64_t)e.score_bytes, stream));
+    const int32_t* verdict = reinterpret_cast<const int32_t*>(static_cast<char*>(e.score) + SCORE_HEADER_BYTES);
+
+    // ================================================================ backward: prior sum -> e_enc
+    auto tgemm = [&](const Panel& p, const float* a0, int lda, int c0, int ntaps, const float* res, int ldr, const float* out_mask, float* out,
+                     int ldc, int rowsB, int rowsT) {
+        GemmArgs a;
+        panel_args(G, p, a); rows_plain(a, rowsB, rowsT);
+        if (ntaps > 1) taps_centered(a, ntaps);
+        a.a0 = a0; a.lda0 = lda; a.c0 = c0; a.res = res; a.ldr = ldr; a.out_mask = out_mask; a.out = out; a.ldc = ldc;
+        return run_gemm(c, a, s);
+    };
+    LAUNCH(c, 2, 0, s, launch_fill_cols(e.GMU, M, ldm, 0, ldm, 0.f, s));
+    hipLaunchKernelGGL(seed_mu_kernel, dim3(nf, B), dim3(256), 0, s, e.mu_x, d_y_fine, dur, d_x_lengths, verdict, nf, Tx, Tm, delta_prior,
+                       e.GMU, ldm);
+    HIP_OK(hipGetLastError());
+    RET_IF(tgemm(GW.pm2T, e.GMU, ldm, ldm, 1, nullptr, 0, nullptr, e.GPM, nch, B, Tx));
+    LAUNCH(c, 2, 0, s, launch_gate(e.GPM, nch, M, nch, 0, e.PMpre, nch, nullptr, 0, nullptr, s));
+    RET_IF(tgemm(GW.pm0T, e.GPM, nch, nch, 1, nullptr, 0, nullptr, e.GA, Hd, B, Tx));
+    for (int l = L - 1; l >= 0; --l) {
+        LnBwdArgs n2;
+        n2.x = e.S2[l]; n2.ldx = Hd; n2.dy = e.GA; n2.lddy = Hd; n2.dx = e.GB; n2.lddx = Hd; n2.M = M; n2.C = Hd; n2.T = Tx;
+        n2.gamma = W(c, E.n2_g[l].off); n2.beta = W(c, E.n2_b[l].off); n2.mask = xm;
+        LAUNCH(c, 2, 0, s, launch_ln_bwd(n2, s));
+        RET_IF(tgemm(GW.ffn2T[l], e.GB, Hd, Hd, g.enc_kernel, nullptr, 0, nullptr, e.GF, g.enc_filter, B, Tx));
+        LAUNCH(c, 2, 0, s, launch_gate(e.GF, g.enc_filter, M, g.enc_filter, ffn_p16 ? 2 : 1, e.F1[l], g.enc_filter,
+                                       reinterpret_cast<const _Float16*>(e.F1[l]), 2 * g.enc_filter, xm, s));
+        RET_IF(tgemm(GW.ffn1T[l], e.GF, g.enc_filter, g.enc_filter, g.enc_kernel, e.GB, Hd, nullptr, e.GA, Hd, B, Tx));
+        LnBwdArgs n1 = n2;
+        n1.x = e.S1[l]; n1.gamma = W(c, E.n1_g[l].off); n1.beta = W(c, E.n1_b[l].off);
+        LAUNCH(c, 2, 0, s, launch_ln_bwd(n1, s));
+        RET_IF(tgemm(GW.oT[l], e.GB, Hd, Hd, 1, nullptr, 0, nullptr, e.GATT, Hd, B, Tx));
+        AttnBwdArgs ab;
+        ab.qkv = e.QKV[l]; ab.o = e.ATT[l]; ab.d_o = e.GATT; ab.len = d_x_lengths; ab.B = B; ab.T = Tx; ab.H = g.enc_heads; ab.D = dh;
+        ab.scale = 1.0f / sqrtf((float)dh); ab.cos_t = W(c, E.rope_cos.off); ab.sin_t = W(c, E.rope_sin.off);
+        ab.dqkv = e.GQKV; ab.stats = e.stats;
+        LAUNCHB(c, 1, 10.0 * B * g.enc_heads * double(Tx) * Tx * dh, 0.0, s, launch_attn_bwd(ab, s));
+        RET_IF(tgemm(GW.qkvT[l], e.GQKV, 3 * Hd, 3 * Hd, 1, e.GB, Hd, nullptr, e.GA, Hd, B, Tx));
+    }
+    LAUNCH(c, 2, 0, s, launch_colsum(e.GA, Hd, nch, Sd, B, Tx, d_x_lengths, verdict, d_g_enc, Sd, 0, 0, s));
+
+    // ================================================================ backward: duration sum -> e_dur
+    hipLaunchKernelGGL(seed_logw_kernel, dim3(M), dim3(64), 0, s, e.logw, dur, d_x_lengths, verdict, G->d_image + GW.dp_proj.off, Tx, F,
+                       delta_dur, e.GDA);
+    HIP_OK(hipGetLastError());
+    bool first = true;
+    for (int i = g.dp_layers - 1; i >= 0; --i) {
+        LAUNCH(c, 2, 0, s, launch_colsum(e.GDA, F, 0, F, B, Tx, d_x_lengths, verdict, e.DFILM, 2 * F, F, first ? 0 : 1, s));
+        LnBwdArgs ln;
+        ln.x = e.DY[i]; ln.ldx = F; ln.dy = e.GDA; ln.lddy = F; ln.dx = e.GDB; ln.lddx = F; ln.M = M; ln.C = F; ln.T = Tx;
+        ln.gamma = W(c, E.dp_g[i].off); ln.beta = W(c, E.dp_b[i].off); ln.film = e.FILM; ln.film_prod = e.FPROD; ln.gate = ACT_RELU;
+        LAUNCH(c, 2, 0, s, launch_ln_bwd(ln, s));
+        LAUNCH(c, 2, 0, s, launch_colsum(e.FPROD, F, 0, F, B, Tx, d_x_lengths, verdict, e.DFILM, 2 * F, 0, first ? 0 : 1, s));
+        first = false;
+        if (i >= 1) RET_IF(tgemm(GW.dp_convT[i], e.GDB, F, F, g.dp_kernel, nullptr, 0, xm, e.GDA, F, B, Tx));
+    }
+    RET_IF(tgemm(GW.filmT, e.DFILM, 2 * F, 2 * F, 1, nullptr, 0, nullptr, d_g_dur, Sd, B, 1));
+    return 0;
+}
+
+// The verdict of the call's device-side checks (score.hip's, on this call's lengths and durations).  The one entry of this file that
+// waits for the stream.
+int mtts_spk_grad_status(const void* d_ws, void* stream) {
+    if (!d_ws) { set_error("mtts_spk_grad_status: null workspace"); return -1; }
+    if (mtts_score_status(static_cast<const char*>(d_ws) + SG_SCORE_OFF, stream) != 0) {
+        std::string m = get_error();
+        const std::string from = "mtts_score_prior_dur";
+        const size_t at = m.find(from);
+        if (at != std::string::npos) m.replace(at, from.size(), "mtts_spk_grad");
+        set_error(m);
+        return -1;
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- unit entries (kernel-level parity)
+// fp32 rows in and out.  d_dfilm [B][2C] (gamma | beta gradient per utterance over all T rows) needs d_film and d_scratch [B T][C].
+int mtts_channel_layernorm_bwd(const float* d_x, const float* d_dy, int B, int T, int C, const float* d_gamma, const float* d_beta, float eps,
+                               int act, const float* d_film, const float* d_mask, int gate, float* d_dx, float* d_dfilm, void* d_scratch,
+                               void* stream) {
+    if (!d_x || !d_dy || !d_dx) { set_error("mtts_channel_layernorm_bwd: null argument"); return -1; }
+    if (B <= 0 || T <= 0 || C <= 0) { set_error("mtts_channel_layernorm_bwd: empty batch"); return -1; }
+    if (act != ACT_NONE && act != ACT_SILU) { set_error("mtts_channel_layernorm_bwd: act must be 0 (none) or 2 (SiLU)"); return -1; }
+    if (gate != ACT_NONE && gate != ACT_RELU) { set_error("mtts_channel_layernorm_bwd: gate must be 0 (none) or 1 (ReLU)"); return -1; }
+    if (d_dfilm && (!d_film || !d_scratch)) { set_error("mtts_channel_layernorm_bwd: d_dfilm needs d_film and d_scratch"); return -1; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    LnBwdArgs a;
+    a.x = d_x; a.ldx = C; a.dy = d_dy; a.lddy = C; a.dx = d_dx; a.lddx = C; a.M = B * T; a.C = C; a.T = T; a.gamma = d_gamma; a.beta = d_beta;
+    a.eps = eps; a.act = act; a.film = d_film; a.film_prod = d_dfilm ? static_cast<float*>(d_scratch) : nullptr; a.mask = d_mask; a.gate = gate;
+    HIP_OK(launch_ln_bwd(a, s));
+    if (d_dfilm) {
+        HIP_OK(launch_colsum(static_cast<const float*>(d_scratch), C, 0, C, B, T, nullptr, nullptr, d_dfilm, 2 * C, 0, 0, s));
+        HIP_OK(launch_colsum(d_dy, C, 0, C, B, T, nullptr, nullptr, d_dfilm, 2 * C, C, 0, s));
+    }
+    return 0;
+}
+
+// d_qkv [B T][3 H D] rows AFTER the rotation, d_o / d_do [B T][H D], d_lengths int64 [B], d_cos / d_sin [>= T][D / 2] (rotary on the
+// first D / 2 dims); d_dqkv [B T][3 H D] = gradient with respect to q | k | v BEFORE the rotation; d_scratch [B][H][T][3] floats.
+int mtts_attention_rope_bwd(const float* d_qkv, const float* d_o, const float* d_do, const int64_t* d_lengths, int B, int T, int H, int D,
+                            float scale, const float* d_cos, const float* d_sin, float* d_dqkv, void* d_scratch, void* stream) {
+    if (!d_qkv || !d_o || !d_do || !d_lengths || !d_cos || !d_sin || !d_dqkv || !d_scratch) { set_error("mtts_attention_rope_bwd: null argument"); return -1; }
+    if (B < 1 || H < 1 || T < 1 || T > SG_MAX_TX) { set_error("mtts_attention_rope_bwd: need B, H >= 1 and 1 <= T <= 1024"); return -1; }
+    if (!attn_bwd_head_dim_ok(D)) { set_error("mtts_attention_rope_bwd: D must be a multiple of 8, <= 64"); return -1; }
+    AttnBwdArgs a;
+    a.qkv = d_qkv; a.o = d_o; a.d_o = d_do; a.len = d_lengths; a.B = B; a.T = T; a.H = H; a.D = D; a.scale = scale; a.cos_t = d_cos; a.sin_t = d_sin;
+    a.dqkv = d_dqkv; a.stats = static_cast<float*>(d_scratch);
+    HIP_OK(launch_attn_bwd(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+}  // extern "C"

@@ -276,19 +276,20 @@ class MatchaTTSInfer(nn.Module):
         rt.use_wide = True                     # sticky, as in synthesise
         return self._align(x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path)
 
-    def _align(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path):
-        hip = self._rt.ready()
+    def _fine_recording(self, x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="align"):
+        """The recording of ``align`` / ``speaker_grad`` as ``(mel_fine [B, n_feats, Tm >= Tx], mel_fine_lengths)`` on the device: the
+        fine mel of ``audio`` extracted as ``enroll_voice`` does, or the given normalised ``mel_fine``."""
         dev = x.device
         B, Tx = x.shape
         if (audio is None) == (mel_fine is None):
-            raise ValueError("align needs either audio= or mel_fine=")
+            raise ValueError(f"{who} needs either audio= or mel_fine=")
         if mel_fine is None:
             from . import mel as M
             from .style import FINE_HOP
             clips = [audio[b] for b in range(audio.shape[0])] if torch.is_tensor(audio) and audio.dim() == 2 else (
                 [audio] if torch.is_tensor(audio) or isinstance(audio, np.ndarray) else list(audio))
             if len(clips) != B:
-                raise ValueError(f"align needs one clip per utterance ({B}), got {len(clips)}")
+                raise ValueError(f"{who} needs one clip per utterance ({B}), got {len(clips)}")
             clips = [torch.as_tensor(c).to(torch.float32) for c in clips]
             if any(c.dim() != 1 for c in clips):
                 raise ValueError("a clip is a 1-D waveform (24 kHz mono)")
@@ -308,7 +309,13 @@ class MatchaTTSInfer(nn.Module):
         mel_fine_lengths = torch.as_tensor(mel_fine_lengths).to(device=dev, dtype=torch.long)
         if mel_fine.shape[2] < Tx:              # (the padded shapes: the device checks each utterance's own lengths)
             mel_fine = torch.nn.functional.pad(mel_fine, (0, Tx - mel_fine.shape[2]))
+        return mel_fine, mel_fine_lengths
 
+    def _align(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path):
+        hip = self._rt.ready()
+        dev = x.device
+        B, Tx = x.shape
+        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths)
         if speaker_embeddings is not None:
             e_enc, e_dur = speaker_embeddings
         elif voice_mix is not None:
@@ -327,6 +334,125 @@ class MatchaTTSInfer(nn.Module):
         if return_path:
             out["path"] = path
         return out
+
+    @torch.inference_mode()
+    def speaker_grad(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0, voice_mix=None,
+                     speaker_embeddings=None, durations=None):
+        """Gradient of the training forward's prior and duration losses with respect to the two speaker rows, per utterance, on the
+        device (``HipModel.speaker_grad``; include/mtts.h mtts_spk_grad): what the reference's matcha/finetune_speaker.py
+        back-propagates with everything but one row of each speaker table frozen.  The recording as for ``align``; speaker arguments
+        as for ``synthesise``; ``durations`` (int [B, Tx], fine frames) replaces the alignment search.
+
+        Returns ``g_enc``, ``g_dur`` [B, spk_emb_dim] (gradients of the per-utterance sums ``prior_sum``, ``dur_sum`` [B]),
+        ``durations`` (int32 [B, Tx]), ``mel_fine_lengths`` and the two batch losses ``dur_loss``, ``prior_loss`` as ``score``
+        reports them.  The gradients of those batch losses are ``g_dur.sum(0) / x_lengths.sum()`` and
+        ``g_enc.sum(0) / mel_fine_lengths.sum()``.  One synchronisation per call; ``ValueError`` names a refused utterance."""
+        rt = self._rt
+        hip = rt.ready()
+        args = (x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, durations)
+        out = self._speaker_grad(*args)
+        if rt.use_wide or hip.gemm_terms() not in (1, 2, 16, 17) or self.range_policy == "ignore":
+            return out
+        flag = hip.call_flags("spk_grad")
+        if not (hip.weights_saturate() or bool(flag[0].item())):       # (the stream is already drained: no second wait)
+            return out
+        if self.range_policy == "raise":
+            raise FloatingPointError("matcha-tts-24k_amd: an operand left the fp16 range (|x| > 65504) in the default split "
+                                     "arithmetic; set model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
+        rt.use_wide = True                     # sticky, as in synthesise
+        return self._speaker_grad(*args)
+
+    def _speaker_grad(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, durations):
+        hip = self._rt.ready()
+        dev = x.device
+        B, Tx = x.shape
+        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="speaker_grad")
+        if speaker_embeddings is not None:
+            e_enc, e_dur = speaker_embeddings
+        elif voice_mix is not None:
+            e_enc, e_dur = self.mix_speakers(voice_mix)
+        else:
+            ids = torch.as_tensor(speaker, dtype=torch.long, device=dev).reshape(-1)
+            e_enc, e_dur = hip.speaker_embedding(0, ids), hip.speaker_embedding(1, ids)
+        e_enc, e_dur = e_enc.to(dev).reshape(-1, self.hp.spk_emb_dim), e_dur.to(dev).reshape(-1, self.hp.spk_emb_dim)
+        if e_enc.shape[0] not in (1, B):
+            raise ValueError("speaker must be an int or a LongTensor with one id per utterance")
+        x_lengths = x_lengths.to(device=dev, dtype=torch.long)
+        hp = self.hp
+        out = hip.speaker_grad(x, x_lengths, e_enc, e_dur, mel_fine.to(torch.float32).contiguous(), mel_fine_lengths, hp.prior_loss_threshold,
+                               hp.duration_loss_threshold, durations=durations)
+        out["mel_fine_lengths"] = mel_fine_lengths
+        out["dur_loss"] = out["dur_sum"].sum() / x_lengths.to(torch.float32).sum()
+        out["prior_loss"] = out["prior_sum"].sum() / mel_fine_lengths.to(torch.float32).sum()
+        return out
+
+    @torch.inference_mode()
+    def finetune_speaker(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0,
+                         speaker_embeddings=None, steps=100, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, batch_size=None, shuffle_seed=0):
+        """Fine-tune one voice on its recordings: the reference's matcha/finetune_speaker.py (all parameters frozen but one row of
+        ``speaker_embeddings_enc.weight`` and one of ``speaker_embeddings_dur.weight``, trained with the ordinary training loss) as
+        ``steps`` device gradient calls and Adam updates of the two rows.
+
+        ``x`` [N, Tx], ``x_lengths`` [N] and the recordings (``audio`` or ``mel_fine``, as for ``align``) are the voice's utterances;
+        the start is ``speaker`` (an id) or ``speaker_embeddings=(e_enc, e_dur)`` (e.g. of ``enroll_voice``).  Each step runs one
+        ``speaker_grad`` over a batch (``batch_size`` utterances in the order of a ``shuffle_seed``-seeded permutation per epoch;
+        None: all of them), every utterance with the current rows and a freshly searched alignment (as the reference's forward
+        does), forms the reference's batch normalisation ``g_dur.sum(0) / sum(x_lengths)``, ``g_enc.sum(0) / sum(mel_fine_lengths)``
+        and applies one Adam step in torch on the device.  Adam without weight decay: the reference's AdamW puts ``nn.Embedding``
+        parameters in the no-decay group (matcha/models/baselightningmodule.py:29-59); ``lr`` defaults to
+        configs/model/optimizer/adamw.yaml.
+
+        Returns ``(e_enc, e_dur, history)``: the rows [1, spk_emb_dim] for ``synthesise(speaker_embeddings=...)``, a batcher request
+        or ``add_speaker``, and ``history`` = ``{"dur_loss": [...], "prior_loss": [...]}`` per step (before that step's update).
+
+        Two deviations from the reference.  It fine-tunes in train mode with dropout active; this is the dropout-free (eval)
+        gradient, deterministic.  The flow-matching loss is not evaluated: it cannot move the rows, because ``mu_y`` is detached
+        before ``decoder.compute_loss`` (matcha_tts.py:154-162) and the estimator has no speaker input."""
+        hip = self._rt.ready()
+        dev = x.device
+        N, Tx = x.shape
+        if int(steps) < 1:
+            raise ValueError("steps must be >= 1")
+        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="finetune_speaker")
+        x_lengths = x_lengths.to(device=dev, dtype=torch.long)
+        if speaker_embeddings is not None:
+            e_enc, e_dur = speaker_embeddings
+        else:
+            ids = torch.tensor([int(speaker)], device=dev, dtype=torch.long)
+            e_enc, e_dur = hip.speaker_embedding(0, ids), hip.speaker_embedding(1, ids)
+        E = self.hp.spk_emb_dim
+        rows = [torch.as_tensor(r).detach().to(device=dev, dtype=torch.float32).reshape(1, -1).clone() for r in (e_enc, e_dur)]
+        if any(r.shape[1] != E for r in rows):
+            raise ValueError(f"a speaker row has {E} values")
+        m = [torch.zeros_like(r) for r in rows]
+        v = [torch.zeros_like(r) for r in rows]
+        b1, b2 = float(betas[0]), float(betas[1])
+        bs = N if batch_size is None else max(1, min(int(batch_size), N))
+        gen = torch.Generator().manual_seed(int(shuffle_seed))
+        order, at = None, 0
+        history = {"dur_loss": [], "prior_loss": []}
+        for step in range(1, int(steps) + 1):
+            if bs == N:
+                idx = None
+            else:
+                if order is None or at + bs > N:
+                    order, at = torch.randperm(N, generator=gen), 0
+                idx = order[at:at + bs].to(dev)
+                at += bs
+            sel = (lambda t: t) if idx is None else (lambda t: t.index_select(0, idx))
+            out = self.speaker_grad(sel(x), sel(x_lengths), mel_fine=sel(mel_fine), mel_fine_lengths=sel(mel_fine_lengths),
+                                    speaker_embeddings=(rows[0], rows[1]))
+            grads = (out["g_enc"].sum(0, keepdim=True) / out["mel_fine_lengths"].to(torch.float32).sum(),
+                     out["g_dur"].sum(0, keepdim=True) / sel(x_lengths).to(torch.float32).sum())
+            history["dur_loss"].append(out["dur_loss"])
+            history["prior_loss"].append(out["prior_loss"])
+            for k, g in enumerate(grads):              # torch.optim.Adam, weight_decay 0
+                m[k] = b1 * m[k] + (1 - b1) * g
+                v[k] = b2 * v[k] + (1 - b2) * g * g
+                denom = (v[k] / (1 - b2 ** step)).sqrt() + eps
+                rows[k] = rows[k] - (lr / (1 - b1 ** step)) * m[k] / denom
+        history = {k: [float(t) for t in torch.stack(val).cpu()] for k, val in history.items()}
+        return rows[0], rows[1], history
 
     @torch.inference_mode()
     def score(self, x, x_lengths, audio=None, audio_lengths=None, mel=None, mel_lengths=None, mel_fine=None, mel_fine_lengths=None,
