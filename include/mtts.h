@@ -597,6 +597,60 @@ int64_t mtts_style_workspace_bytes(mtts_style* v, int B, int T);
 int mtts_style_forward(mtts_style* v, const float* d_mel, const int64_t* d_mel_lengths, int B, int T, const int32_t* d_group,
                        int n_groups, float* d_e_enc, float* d_e_dur, void* d_ws, int64_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- sample-rate conversion */
+
+/* A ragged batch of fp32 clips from orig_freq to new_freq: the windowed-sinc polyphase interpolation that
+ * torchaudio.functional.resample documents as its default (resampling_method "sinc_interp_hann", lowpass_filter_width 6, rolloff
+ * 0.99; the reference converts with it, matcha/utils/utmos_validate.py:78), restated from its formulae -- not pinned to the
+ * package.  With g = gcd(orig_freq, new_freq), o = orig_freq / g, n = new_freq / g, lpw = lowpass_filter_width:
+ *     base = min(o, n) * rolloff,  width = ceil(lpw * o / base),  taps = 2 * width + o
+ *     t = clamp((-p / n + (k - width) / o) * base, -lpw, lpw)                            phase p in [0, n), tap k in [0, taps)
+ *     K[p][k] = (t == 0 ? 1 : sin(pi t) / (pi t)) * cos(t pi / lpw / 2)^2 * (base / o)   in fp64, rounded once to fp32
+ *     out_len(L) = ceil(n L / o)
+ *     out[q n + p] = sum_k K[p][k] * x[q o + k - width]   with x = 0 outside [0, L), for q n + p < out_len(L)
+ * The fp32 table is the definition.  After the rounding the taps at the clamp are exact zeros, so each phase has a band of `band`
+ * consecutive taps (the widest first-to-last non-zero run of any phase) outside which it is zero; only the band is kept on the
+ * device and evaluated.
+ *
+ * The object owns the host table (built at create, no device needed) and the banded device copy, which the first
+ * mtts_resample_forward makes on the current device (one allocation and a blocking copy: not inside a stream capture; one object
+ * per device).  mtts_resampler_create returns NULL (mtts_last_error says why) for a rate outside [4000, 384000], equal rates,
+ * lowpass_filter_width < 1, rolloff outside (0, 1], a banded bank of more than MTTS_RESAMPLE_MAX_BANK floats (n * band: rate
+ * pairs with a small common divisor), or a rate pair whose bank, input span of one tile (about MTTS_RESAMPLE_TILE * o / n samples)
+ * and output tile exceed MTTS_RESAMPLE_LDS_BYTES of LDS (decimation by more than about 12).  Every pair of {8000, 11025, 16000,
+ * 22050, 24000, 32000, 44100, 48000, 96000} with 24000 is admitted.
+ *
+ * Host-only queries: mtts_resample_factors (any pointer may be NULL), mtts_resample_out_length = out_len(L), and
+ * mtts_resample_bank, which copies the dense fp32 table [n][taps] out.  mtts_resample_tile = MTTS_RESAMPLE_TILE as built.
+ *
+ * mtts_resample_forward: d_in [B][ld_in], d_out [B][ld_out] fp32 with 16-byte aligned rows (ld % 4 == 0, as
+ * mtts_waveform_finish requires), d_lengths device int64 [B].  Row b of d_out receives out_len(len_b) samples followed by zeros
+ * up to ld_out, and d_out_lengths[b] that count; len_b == 0 gives 0 samples.  One launch gridded over (output tile, clip).
+ *   Every output sample is ONE fp32 sum in a fixed order: s = 0, then s = s + K[p][k] * x[.] for k ascending over the phase's
+ *   band, the product and the sum each rounded to fp32 (no FMA), no atomics.  For finite input that has the bits of the dense sum
+ *   over k = 0 .. taps - 1 in ascending order.  A clip's samples therefore do not depend on the batch it is in, two calls give the
+ *   same bits, and a NumPy fp32 restatement in that order reproduces them bit for bit.
+ *   The lengths are checked on the device without a host read: a len_b outside [0, ld_in], or one whose out_len exceeds ld_out,
+ *   gives row b zero output and d_out_lengths[b] = -1; the other rows are unaffected.  Nothing is ever read outside [0, len_b) of
+ *   a row or written outside the row.  mtts_resample_status(d_ws, stream) -- the one entry here that waits for the stream --
+ *   reports the first refused row through mtts_last_error.
+ * Stream-ordered, no allocation, no synchronisation (mtts_resample_status excepted).  Workspace: mtts_resample_workspace_bytes,
+ * 16-byte aligned.  What the host can see (null pointers, B < 1, an ld that is no multiple of 4, a small workspace) returns -1. */
+#define MTTS_RESAMPLE_TILE 1024        /* output samples per workgroup */
+#define MTTS_RESAMPLE_MAX_BANK 6144    /* floats of the banded bank (n * band) the kernel keeps in LDS */
+#define MTTS_RESAMPLE_LDS_BYTES 65536  /* bank + first-tap table + one tile's input span + the output tile */
+typedef struct mtts_resampler mtts_resampler;
+mtts_resampler* mtts_resampler_create(int orig_freq, int new_freq, int lowpass_filter_width, double rolloff);
+void mtts_resampler_destroy(mtts_resampler* r);
+int mtts_resample_tile(void);
+int mtts_resample_factors(mtts_resampler* r, int* o, int* n, int* width, int* taps, int* band);
+int64_t mtts_resample_out_length(mtts_resampler* r, int64_t L);
+int mtts_resample_bank(mtts_resampler* r, float* h_K, int64_t numel);
+int64_t mtts_resample_workspace_bytes(mtts_resampler* r, int B, int64_t ld_in);
+int mtts_resample_forward(mtts_resampler* r, const float* d_in, int64_t ld_in, const int64_t* d_lengths, int B, float* d_out,
+                          int64_t ld_out, int64_t* d_out_lengths, void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_resample_status(const void* d_ws, void* stream);
+
 /* ---------------------------------------------------------------- forced alignment (Monotonic Alignment Search) */
 
 /* Which fine mel frames belong to which token -- the alignment of the reference's training forward, matcha/models/matcha_tts.py:

@@ -42,6 +42,7 @@ class Request:
     scale_correction: float = 1.0
     length_scale: float = 1.0
     durations: Optional[Sequence[float]] = None    # fine frames per token (e.g. ``align(...)["durations"]``) instead of the predictor's; length_scale still applies
+    sample_rate: int = 24000                # rate of the result's "audio" (with a vocoder); anything else is converted on the device and named in the result
     future: Future = field(default_factory=Future, repr=False)
     t_submit: float = field(default_factory=time.monotonic, repr=False)
 
@@ -180,16 +181,29 @@ def request_inputs(model, batch: List[Request]):
     return x.to(dev), x_len.to(dev), emb
 
 
-def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_batch: bool) -> None:
-    """``res[b]["audio"]`` for a batch of finished mels (``mel`` [B, n_feats, T], ``mel_lengths`` [B]; ``res[b]["mel"]`` the exact-length rows)."""
-    if vocoder is not None and wave_batch:
+def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_batch: bool, sample_rates: Optional[Sequence[int]] = None) -> None:
+    """``res[b]["audio"]`` for a batch of finished mels (``mel`` [B, n_feats, T], ``mel_lengths`` [B]; ``res[b]["mel"]`` the exact-length
+    rows).  ``sample_rates``: one rate per request (default 24 kHz); rows that ask for another rate are converted on the device after
+    the normalisation and the trim (``inference.to_waveforms``) and carry ``res[b]["sample_rate"]`` beside ``"audio"``.  A result at
+    24 kHz keeps exactly the keys it had before there was a choice."""
+    if vocoder is None:
+        return
+    rates = [24000] * len(res) if sample_rates is None else [int(v) for v in sample_rates]
+    if wave_batch:
         from .inference import to_waveforms
-        for r, a in zip(res, to_waveforms(mel, mel_lengths, vocoder)):
+        for r, a in zip(res, to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates)):
             r["audio"] = a
-    elif vocoder is not None:
-        from .inference import _waveform_on_device, trim_trailing_silence
-        for r in res:
-            r["audio"] = trim_trailing_silence(_waveform_on_device(r["mel"][None], vocoder).squeeze()).cpu()
+    else:
+        from .inference import _convert_rows, _waveform_on_device, trim_trailing_silence
+        for r, rate in zip(res, rates):
+            a = trim_trailing_silence(_waveform_on_device(r["mel"][None], vocoder).squeeze())
+            if rate != 24000 and a.numel() > 0:
+                conv, n = _convert_rows(a.reshape(1, -1), torch.tensor([a.numel()], dtype=torch.long, device=a.device), [rate])
+                a = conv[0, :int(n[0])]
+            r["audio"] = a.cpu()
+    for r, rate in zip(res, rates):
+        if rate != 24000:
+            r["sample_rate"] = rate
 
 
 def synthesise_batch(model, batch: List[Request], vocoder=None, wave_batch: bool = True) -> List[Dict[str, Any]]:
@@ -204,7 +218,7 @@ def synthesise_batch(model, batch: List[Request], vocoder=None, wave_batch: bool
                            durations=duration_rows(batch))
     lens = out["mel_lengths"].tolist()
     res = [{"mel": out["mel"][b, :, :int(lens[b])], "mel_length": int(lens[b])} for b in range(B)]
-    waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch)
+    waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch, [r.sample_rate for r in batch])
     return res
 
 
@@ -534,7 +548,7 @@ class StepBatcher:
                 mel[b, :, :r["mel_length"]] = r["mel"]
             lengths = torch.tensor([r["mel_length"] for r in res], dtype=torch.long, device=mel.device)
             try:
-                waveforms_into(res, mel, lengths, self.vocoder, self.wave_batch)
+                waveforms_into(res, mel, lengths, self.vocoder, self.wave_batch, [e.request.sample_rate for e in finished])
             except BaseException as exc:  # noqa: BLE001 - the finishers only: who is mid-solve is not affected
                 self._fail([e.request for e in finished], exc)
                 return

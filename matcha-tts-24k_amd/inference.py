@@ -161,18 +161,18 @@ class MatchaTTSInfer(nn.Module):
         return torch.cat(enc, 0), torch.cat(dur, 0)
 
     @torch.inference_mode()
-    def enroll_voice(self, clips, style_encoder, sample_rate: int = 24000):
+    def enroll_voice(self, clips, style_encoder, sample_rate=24000):
         """Speaker rows from audio -- the reference's offline chain matcha/vocos24k/mel_extractor.py (audio -> log-mel),
         matcha/utils/precompute_mels.py:100-113 (normalise with this model's mel statistics, hop 128), StyleEncoder.forward and
         matcha/add_speaker.py:40-62 (average over the clips) -- as one front-end call and one encoder call on the device.
 
-        ``clips``: a list of 1-D waveforms (host or device, 24 kHz mono in [-1, 1]) of ONE voice -> ``(e_enc, e_dur)`` of shape
+        ``clips``: a list of 1-D waveforms (host or device, mono in [-1, 1]) of ONE voice -> ``(e_enc, e_dur)`` of shape
         [1, spk_emb_dim]; or a list of such lists for several voices -> [n_voices, spk_emb_dim].  The rows are what
-        ``synthesise(speaker_embeddings=...)``, ``speaker_rows`` and ``add_speaker`` take.  Resampling is not done here."""
+        ``synthesise(speaker_embeddings=...)``, ``speaker_rows`` and ``add_speaker`` take.  ``sample_rate``: the clips' rate, an int
+        or one int per clip (in the order of the flattened list); clips at another rate than 24 kHz are converted on the device
+        first (``resample.resample``, one call per distinct rate)."""
         from . import mel as M
         from .style import FINE_HOP
-        if int(sample_rate) != 24000:
-            raise ValueError("clips must be 24 kHz mono (resample before enrolling)")
         if len(clips) == 0:
             raise ValueError("no clips")
         voices = [clips] if torch.is_tensor(clips[0]) or isinstance(clips[0], np.ndarray) else list(clips)
@@ -183,16 +183,9 @@ class MatchaTTSInfer(nn.Module):
             if len(vc) == 0:
                 raise ValueError(f"voice {g} has no clips")
             for c in vc:
-                c = torch.as_tensor(c)
-                if c.dim() != 1:
-                    raise ValueError("a clip is a 1-D waveform (mono)")
-                flat.append(c.to(torch.float32))
+                flat.append(c)
                 group.append(g)
-        lengths = [int(c.numel()) for c in flat]
-        ld = (max(lengths) + 3) // 4 * 4
-        audio = torch.zeros(len(flat), ld, dtype=torch.float32, device=dev)
-        for b, c in enumerate(flat):
-            audio[b, :lengths[b]].copy_(c)
+        audio, lengths = _recordings_24k(flat, dev, sample_rate)
         n_feats = style_encoder.cfg["n_feats"]
         if n_feats != self.hp.n_feats or style_encoder.cfg["spk_emb_dim"] != self.hp.spk_emb_dim:
             raise ValueError("the style encoder's n_feats / spk_emb_dim do not match this model")
@@ -249,15 +242,16 @@ class MatchaTTSInfer(nn.Module):
 
     @torch.inference_mode()
     def align(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0, voice_mix=None,
-              speaker_embeddings=None, return_path=False):
+              speaker_embeddings=None, return_path=False, sample_rate=24000):
         """Forced alignment of text to a recording: per-token durations in fine frames (hop 128) by Monotonic Alignment Search of
         the text encoder's ``mu_x`` against the recording's normalised fine mel -- the alignment of the reference's training
         forward (matcha/models/matcha_tts.py:184-201), here for inference-time use: ``synthesise(durations=...)`` re-times or
         re-voices with the speaker's own rhythm, and ``scale_correction`` is the number the reference's ``VOICES`` table holds per
         voice ("measured after training, by comparing generated speech to ground truth", reference inference.py:131-133).
 
-        The recording: ``audio`` -- 24 kHz mono clips, a list of 1-D waveforms (host or device) or a [B, L] tensor with
-        ``audio_lengths`` -- whose fine mel is extracted as ``enroll_voice`` does; or ``mel_fine`` [B, n_feats, Tm], already
+        The recording: ``audio`` -- mono clips, a list of 1-D waveforms (host or device) or a [B, L] tensor with
+        ``audio_lengths``, at ``sample_rate`` (an int or one int per clip; anything but 24 kHz is converted on the device first,
+        ``resample.resample``) -- whose fine mel is extracted as ``enroll_voice`` does; or ``mel_fine`` [B, n_feats, Tm], already
         normalised with this model's mel statistics, with ``mel_fine_lengths`` (default: all Tm).  Speaker arguments as for
         ``synthesise``.  Returns ``durations`` (int32 [B, Tx]), ``predicted_durations`` (the predictor's raw
         ``(exp(logw) - 2) * mask``), ``scale_correction`` ([B]: aligned total / predicted total), ``score`` ([B]: the path's
@@ -265,7 +259,8 @@ class MatchaTTSInfer(nn.Module):
         (the lengths' verdict and the range flag); ``ValueError`` names an utterance with fewer frames than tokens."""
         rt = self._rt
         hip = rt.ready()
-        out = self._align(x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path)
+        out = self._align(x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path,
+                          sample_rate)
         if rt.use_wide or hip.gemm_terms() not in (1, 2, 16, 17) or self.range_policy == "ignore":
             return out
         if not (hip.weights_saturate() or bool(hip.range_flags()[0].item())):       # (the stream is already drained: no second wait)
@@ -274,9 +269,10 @@ class MatchaTTSInfer(nn.Module):
             raise FloatingPointError("matcha-tts-24k_amd: an operand left the fp16 range (|x| > 65504) in the default split "
                                      "arithmetic; set model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
         rt.use_wide = True                     # sticky, as in synthesise
-        return self._align(x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path)
+        return self._align(x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path,
+                           sample_rate)
 
-    def _fine_recording(self, x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="align"):
+    def _fine_recording(self, x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="align", sample_rate=24000):
         """The recording of ``align`` / ``speaker_grad`` as ``(mel_fine [B, n_feats, Tm >= Tx], mel_fine_lengths)`` on the device: the
         fine mel of ``audio`` extracted as ``enroll_voice`` does, or the given normalised ``mel_fine``."""
         dev = x.device
@@ -290,14 +286,7 @@ class MatchaTTSInfer(nn.Module):
                 [audio] if torch.is_tensor(audio) or isinstance(audio, np.ndarray) else list(audio))
             if len(clips) != B:
                 raise ValueError(f"{who} needs one clip per utterance ({B}), got {len(clips)}")
-            clips = [torch.as_tensor(c).to(torch.float32) for c in clips]
-            if any(c.dim() != 1 for c in clips):
-                raise ValueError("a clip is a 1-D waveform (24 kHz mono)")
-            lengths = [int(c.numel()) for c in clips] if audio_lengths is None else [int(v) for v in torch.as_tensor(audio_lengths).tolist()]
-            ld = (max(int(c.numel()) for c in clips) + 3) // 4 * 4
-            wave = torch.zeros(B, ld, dtype=torch.float32, device=dev)
-            for b, c in enumerate(clips):
-                wave[b, :c.numel()].copy_(c)
+            wave, lengths = _recordings_24k(clips, dev, sample_rate, audio_lengths)
             mel_fine, mel_fine_lengths = M.extract(wave, lengths, FINE_HOP, self._rt.mel_mean, self._rt.mel_std, sample_rate=24000,
                                                    n_mels=self.hp.n_feats)
         else:
@@ -311,11 +300,12 @@ class MatchaTTSInfer(nn.Module):
             mel_fine = torch.nn.functional.pad(mel_fine, (0, Tx - mel_fine.shape[2]))
         return mel_fine, mel_fine_lengths
 
-    def _align(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path):
+    def _align(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path,
+               sample_rate=24000):
         hip = self._rt.ready()
         dev = x.device
         B, Tx = x.shape
-        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths)
+        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, sample_rate=sample_rate)
         if speaker_embeddings is not None:
             e_enc, e_dur = speaker_embeddings
         elif voice_mix is not None:
@@ -337,10 +327,10 @@ class MatchaTTSInfer(nn.Module):
 
     @torch.inference_mode()
     def speaker_grad(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0, voice_mix=None,
-                     speaker_embeddings=None, durations=None):
+                     speaker_embeddings=None, durations=None, sample_rate=24000):
         """Gradient of the training forward's prior and duration losses with respect to the two speaker rows, per utterance, on the
         device (``HipModel.speaker_grad``; include/mtts.h mtts_spk_grad): what the reference's matcha/finetune_speaker.py
-        back-propagates with everything but one row of each speaker table frozen.  The recording as for ``align``; speaker arguments
+        back-propagates with everything but one row of each speaker table frozen.  The recording (and ``sample_rate``) as for ``align``; speaker arguments
         as for ``synthesise``; ``durations`` (int [B, Tx], fine frames) replaces the alignment search.
 
         Returns ``g_enc``, ``g_dur`` [B, spk_emb_dim] (gradients of the per-utterance sums ``prior_sum``, ``dur_sum`` [B]),
@@ -349,7 +339,7 @@ class MatchaTTSInfer(nn.Module):
         ``g_enc.sum(0) / mel_fine_lengths.sum()``.  One synchronisation per call; ``ValueError`` names a refused utterance."""
         rt = self._rt
         hip = rt.ready()
-        args = (x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, durations)
+        args = (x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, durations, sample_rate)
         out = self._speaker_grad(*args)
         if rt.use_wide or hip.gemm_terms() not in (1, 2, 16, 17) or self.range_policy == "ignore":
             return out
@@ -362,11 +352,12 @@ class MatchaTTSInfer(nn.Module):
         rt.use_wide = True                     # sticky, as in synthesise
         return self._speaker_grad(*args)
 
-    def _speaker_grad(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, durations):
+    def _speaker_grad(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, durations,
+                      sample_rate=24000):
         hip = self._rt.ready()
         dev = x.device
         B, Tx = x.shape
-        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="speaker_grad")
+        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="speaker_grad", sample_rate=sample_rate)
         if speaker_embeddings is not None:
             e_enc, e_dur = speaker_embeddings
         elif voice_mix is not None:
@@ -388,12 +379,14 @@ class MatchaTTSInfer(nn.Module):
 
     @torch.inference_mode()
     def finetune_speaker(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0,
-                         speaker_embeddings=None, steps=100, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, batch_size=None, shuffle_seed=0):
+                         speaker_embeddings=None, steps=100, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, batch_size=None, shuffle_seed=0,
+                         sample_rate=24000):
         """Fine-tune one voice on its recordings: the reference's matcha/finetune_speaker.py (all parameters frozen but one row of
         ``speaker_embeddings_enc.weight`` and one of ``speaker_embeddings_dur.weight``, trained with the ordinary training loss) as
         ``steps`` device gradient calls and Adam updates of the two rows.
 
-        ``x`` [N, Tx], ``x_lengths`` [N] and the recordings (``audio`` or ``mel_fine``, as for ``align``) are the voice's utterances;
+        ``x`` [N, Tx], ``x_lengths`` [N] and the recordings (``audio`` at ``sample_rate``, or ``mel_fine``, as for ``align``; converted to
+        24 kHz and to the fine mel once, before the loop) are the voice's utterances;
         the start is ``speaker`` (an id) or ``speaker_embeddings=(e_enc, e_dur)`` (e.g. of ``enroll_voice``).  Each step runs one
         ``speaker_grad`` over a batch (``batch_size`` utterances in the order of a ``shuffle_seed``-seeded permutation per epoch;
         None: all of them), every utterance with the current rows and a freshly searched alignment (as the reference's forward
@@ -413,7 +406,7 @@ class MatchaTTSInfer(nn.Module):
         N, Tx = x.shape
         if int(steps) < 1:
             raise ValueError("steps must be >= 1")
-        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="finetune_speaker")
+        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="finetune_speaker", sample_rate=sample_rate)
         x_lengths = x_lengths.to(device=dev, dtype=torch.long)
         if speaker_embeddings is not None:
             e_enc, e_dur = speaker_embeddings
@@ -456,7 +449,8 @@ class MatchaTTSInfer(nn.Module):
 
     @torch.inference_mode()
     def score(self, x, x_lengths, audio=None, audio_lengths=None, mel=None, mel_lengths=None, mel_fine=None, mel_fine_lengths=None,
-              speaker=0, voice_mix=None, speaker_embeddings=None, t=None, noise=None, per_request_padding=False, return_frames=False):
+              speaker=0, voice_mix=None, speaker_embeddings=None, t=None, noise=None, per_request_padding=False, return_frames=False,
+              sample_rate=24000):
         """How well does this model, with this voice, explain this recording: the three numbers of the reference's training forward
         (``MatchaTTS.forward``, matcha/models/matcha_tts.py:64-164), forward pass only, on the device.
 
@@ -465,7 +459,7 @@ class MatchaTTSInfer(nn.Module):
         of ``BASECFM.compute_loss`` (flow_matching.py:65-107), one estimator evaluation at time ``t[b]`` per utterance.  The Huber
         thresholds are the checkpoint's (``hp.prior_loss_threshold``, ``hp.duration_loss_threshold``).
 
-        The recording: ``audio`` as for ``align`` -- both mels are extracted (hop 256 and hop 128) and padded as the reference's
+        The recording: ``audio`` (and ``sample_rate``) as for ``align`` -- both mels are extracted (hop 256 and hop 128) and padded as the reference's
         collate pads them (matcha/data/text_mel_datamodule.py:481-499) -- or ``mel`` [B, n_feats, T] and ``mel_fine`` [B, n_feats,
         Tm], normalised with this model's mel statistics, with their lengths (default: the whole tensors).  Speaker arguments as
         for ``synthesise``.  ``t``: [B] (default ``torch.rand``) or a grid [K, B] -- K evaluations with the same ``noise``
@@ -480,7 +474,7 @@ class MatchaTTSInfer(nn.Module):
         rt = self._rt
         hip = rt.ready()
         dev = x.device
-        rec = self._score_recording(x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths)
+        rec = self._score_recording(x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths, sample_rate)
         B, nf, T = rec[0].shape
         if noise is None:
             noise = torch.randn(B, nf, T, dtype=torch.float32, device=dev)
@@ -505,7 +499,7 @@ class MatchaTTSInfer(nn.Module):
         out.pop("_flags", None)
         return out
 
-    def _score_recording(self, x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths):
+    def _score_recording(self, x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths, sample_rate=24000):
         """(mel [B, nf, T], mel_lengths, mel_fine [B, nf, Tm], mel_fine_lengths, host coarse lengths or None) padded like the
         reference's collate: T = fix_len_compatibility(longest coarse mel), Tm = 2 T (more only if a given tensor is longer or
         there are more tokens than that)."""
@@ -522,14 +516,7 @@ class MatchaTTSInfer(nn.Module):
                 [audio] if torch.is_tensor(audio) or isinstance(audio, np.ndarray) else list(audio))
             if len(clips) != B:
                 raise ValueError(f"score needs one clip per utterance ({B}), got {len(clips)}")
-            clips = [torch.as_tensor(c).to(torch.float32) for c in clips]
-            if any(c.dim() != 1 for c in clips):
-                raise ValueError("a clip is a 1-D waveform (24 kHz mono)")
-            lengths = [int(c.numel()) for c in clips] if audio_lengths is None else [int(v) for v in torch.as_tensor(audio_lengths).tolist()]
-            ld = (max(int(c.numel()) for c in clips) + 3) // 4 * 4
-            wave = torch.zeros(B, ld, dtype=torch.float32, device=dev)
-            for b, c in enumerate(clips):
-                wave[b, :c.numel()].copy_(c)
+            wave, lengths = _recordings_24k(clips, dev, sample_rate, audio_lengths)
             kw = dict(sample_rate=24000, n_mels=nf)
             mel_fine, mel_fine_lengths = M.extract(wave, lengths, FINE_HOP, self._rt.mel_mean, self._rt.mel_std, **kw)
             mel, mel_lengths = M.extract(wave, lengths, STD_RES_HOP_LENGTH, self._rt.mel_mean, self._rt.mel_std, **kw)
@@ -673,6 +660,47 @@ class MatchaTTSInfer(nn.Module):
                 "mel_lengths": y_lengths, "mu_y": mu_y, "y_mask": y_mask, "logw": logw, "mu_x": mu_x}
 
 
+def _recordings_24k(clips, dev, sample_rate=24000, lengths=None):
+    """Clips -> ``(wave [B, ld] fp32 on ``dev``, lengths: list of B ints)`` at 24 kHz, ld a multiple of 4: the padded buffer the mel
+    front end takes.  ``clips``: 1-D waveforms (host or device); ``lengths``: samples to use of each (default: all);
+    ``sample_rate``: an int or one per clip.  Clips at another rate are padded into one buffer per distinct rate and converted on
+    the device (``resample.resample``, the given length as the row length); rows at 24 kHz are copied.  With every clip at 24 kHz
+    nothing but the copies is launched.  The converted lengths are ``ceil(24000 * len / rate)``, known without a host read."""
+    from . import resample as R
+    clips = [torch.as_tensor(c).to(torch.float32) for c in clips]
+    if any(c.dim() != 1 for c in clips):
+        raise ValueError("a clip is a 1-D waveform (mono)")
+    B = len(clips)
+    rates = R.rates_per_row(sample_rate, B)
+    lengths = [int(c.numel()) for c in clips] if lengths is None else [int(v) for v in torch.as_tensor(lengths).tolist()]
+    if len(lengths) != B:
+        raise ValueError(f"lengths need one entry per clip ({B}), got {len(lengths)}")
+    converted = {}                                         # rate -> (rows, out [len(rows), ld_r], kept samples per row)
+    for rate in sorted(set(rates) - {SAMPLE_RATE}):
+        rows = [b for b in range(B) if rates[b] == rate]
+        rs = R.resampler(rate, SAMPLE_RATE, dev)
+        src = torch.zeros(len(rows), (max(int(clips[b].numel()) for b in rows) + 3) // 4 * 4, dtype=torch.float32, device=dev)
+        for i, b in enumerate(rows):
+            if lengths[b] < 0 or lengths[b] > clips[b].numel():
+                raise ValueError(f"lengths[{b}] = {lengths[b]} is outside [0, {clips[b].numel()}]")
+            src[i, :clips[b].numel()].copy_(clips[b])
+        out, _ = rs(src, [lengths[b] for b in rows], check=False)      # (the lengths were checked above: no wait)
+        converted[rate] = (rows, out, [rs.out_length(lengths[b]) for b in rows])
+    width = [int(clips[b].numel()) for b in range(B)]
+    for rows, out, keep in converted.values():
+        for i, b in enumerate(rows):
+            width[b], lengths[b] = keep[i], keep[i]
+    ld = (max(width) + 3) // 4 * 4
+    wave = torch.zeros(B, ld, dtype=torch.float32, device=dev)
+    for b, c in enumerate(clips):
+        if rates[b] == SAMPLE_RATE:
+            wave[b, :c.numel()].copy_(c)
+    for rows, out, keep in converted.values():
+        for i, b in enumerate(rows):
+            wave[b, :keep[i]].copy_(out[i, :keep[i]])
+    return wave, lengths
+
+
 def _plain(obj):
     """OmegaConf containers -> plain python, when omegaconf is importable (it is not on the GPU box)."""
     try:
@@ -776,26 +804,61 @@ def finish_waveforms(audio, lengths, hop=0, silence_threshold_db=-60.0):
 
 
 @torch.inference_mode()
-def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0):
+def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, sample_rate=24000):
     """``trim_trailing_silence(to_waveform(mel[b:b+1, :, :len_b], vocoder))`` (reference inference.py:246) for every row of a
     ragged batch in one device pass: ragged Vocos decode, per-row peak normalisation, per-row trim lengths, then ONE copy of the
     audio and one of the [B] lengths -- one synchronisation for the whole batch.  Returns a list of B 1-D host tensors
-    (``trim=False``: normalised but not trimmed, i.e. ``to_waveform`` per row); they are views of the batch's one host buffer."""
+    (``trim=False``: normalised but not trimmed, i.e. ``to_waveform`` per row); they are views of the batch's one host buffer.
+
+    ``sample_rate``: an int, or one per row.  Rows that ask for another rate than 24 kHz are converted on the device after the
+    normalisation and the trim, which run at 24 kHz exactly as without it: the kept samples of those rows go through
+    ``resample.resample`` (one call per distinct rate, the trim length as the row length, no extra host read) ahead of the copy.
+    The band-limited output of a row normalised to a 0.95 peak may overshoot that peak slightly; nothing is re-normalised."""
     model = vocoder.model if hasattr(vocoder, "model") else vocoder
     if mel.dim() == 2:
         mel = mel[None]
     B, _, T = mel.shape
     mel_lengths = torch.as_tensor(mel_lengths).to(device=mel.device, dtype=torch.long)
     hop = model.cfg["hop"]
+    from . import resample as R
+    rates = R.rates_per_row(sample_rate, B)
     audio = model.decode(mel, mel_lengths, check=False)
     out_lengths, _ = finish_waveforms(audio, mel_lengths, hop=hop, silence_threshold_db=silence_threshold_db)
+    if any(r != SAMPLE_RATE for r in rates):
+        audio, out_lengths = _convert_rows(audio, out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1)),
+                                           rates)
     meta = torch.stack([out_lengths, mel_lengths]).cpu()              # waits for the stream: the batch's one synchronisation
     host = audio.cpu()
     keep, frames = meta[0].tolist(), meta[1].tolist()
     for b in range(B):
         if keep[b] < 0:
             raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
-    return [host[b, : (keep[b] if trim else hop * (frames[b] - 1))] for b in range(B)]
+    return [host[b, : (keep[b] if trim or rates[b] != SAMPLE_RATE else hop * (frames[b] - 1))] for b in range(B)]
+
+
+def _convert_rows(audio, lengths, rates):
+    """Rows of ``audio`` [B, L] (24 kHz, ``lengths`` [B] kept samples on the device, -1 = refused row) at the rates they ask for:
+    ``(audio' [B, L'], lengths')`` on the device.  Rows at 24 kHz are copied, the others converted with one ``resample`` call per
+    distinct rate; a refused row stays refused (-1).  Nothing is read on the host."""
+    from . import resample as R
+    B, L = audio.shape
+    dev = audio.device
+    parts = []
+    for rate in sorted(set(rates) - {SAMPLE_RATE}):
+        rows = torch.tensor([b for b in range(B) if rates[b] == rate], dtype=torch.long, device=dev)
+        out, n = R.resample(audio.index_select(0, rows), lengths.index_select(0, rows), SAMPLE_RATE, rate, check=False)
+        parts.append((rows, out, n))
+    same = [b for b in range(B) if rates[b] == SAMPLE_RATE]
+    ld = max([L] * bool(same) + [out.shape[1] for _, out, _ in parts])
+    wave = torch.zeros(B, ld, dtype=torch.float32, device=dev)
+    new_lengths = lengths.clone()
+    if same:
+        rows = torch.tensor(same, dtype=torch.long, device=dev)
+        wave[rows, :L] = audio.index_select(0, rows)
+    for rows, out, n in parts:
+        wave[rows, :out.shape[1]] = out
+        new_lengths[rows] = n
+    return wave, new_lengths
 
 
 def trim_trailing_silence(audio, silence_threshold_db=-60.0):
@@ -821,16 +884,23 @@ def trim_trailing_silence(audio, silence_threshold_db=-60.0):
 
 @torch.inference_mode()
 def pipeline(model, vocoder, text, speaker=0, voice_mix=None, n_timesteps=DEFAULT_NUM_STEPS, scale_correction=1.0,
-             length_scale=1.0, debug=False):
+             length_scale=1.0, debug=False, sample_rate=24000):
     """reference inference.py:233-257.  The reference wraps ``synthesise`` in ``torch.autocast`` (fp16 on its CUDA device);
     here the estimator's arithmetic is chosen when the model is created (``MTTS_GEMM_TERMS``: default fp32-equivalent; 1 = fp16
-    operands / fp32 accumulate, the autocast arithmetic), not per call.  The trailing-silence trim runs on the device."""
+    operands / fp32 accumulate, the autocast arithmetic), not per call.  The trailing-silence trim runs on the device.
+    ``sample_rate``: the rate of the returned waveform; anything but 24 kHz is converted on the device after the normalisation and
+    the trim (``resample.resample``; the band-limited result may overshoot the 0.95 peak slightly, nothing is re-normalised)."""
     primary = voice_mix[0][0] if voice_mix is not None else speaker
     language = next(v["lang"] for v in VOICES if v["id"] == str(primary))
     tp = process_text(text, language)
     out = model.synthesise(tp["x"], tp["x_lengths"], n_timesteps=n_timesteps, speaker=speaker, voice_mix=voice_mix,
                            scale_correction=scale_correction, length_scale=length_scale, debug=debug)
-    waveform = trim_trailing_silence(_waveform_on_device(out["mel"], vocoder).squeeze()).cpu()
+    waveform = trim_trailing_silence(_waveform_on_device(out["mel"], vocoder).squeeze())
+    if int(sample_rate) != SAMPLE_RATE and waveform.numel() > 0:
+        from . import resample as R
+        conv, _ = R.resample(waveform.reshape(1, -1), None, SAMPLE_RATE, int(sample_rate), check=False)
+        waveform = conv[0, :R.resampler(SAMPLE_RATE, int(sample_rate), conv.device).out_length(waveform.numel())]
+    waveform = waveform.cpu()
     if not debug:
         return waveform
     durs = out["phoneme_durations"].squeeze(0).tolist()

@@ -77,18 +77,21 @@ class SpeechService:
         self.max_text_length = int(max_text_length)
 
     def submit(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
-               speaker_embedding=None):
+               speaker_embedding=None, sample_rate: int = 24000):
         """``speaker_embedding``: the ``(e_enc, e_dur)`` rows of an enrolled voice (``MatchaTTSInfer.enroll_voice``); the request is
-        then spoken with them, and ``voice`` only picks the language and the duration scale correction."""
+        then spoken with them, and ``voice`` only picks the language and the duration scale correction.  ``sample_rate``: the rate
+        of the result's ``"audio"`` (8 or 16 kHz for telephony, 48 kHz for a browser); the batcher converts on the device."""
         if len(text) > self.max_text_length:
             raise ValueError(f"Text exceeds {self.max_text_length} characters")       # the handler's HTTP 400
         p = request_params(voice, speed, steps, solver)
         ids = self.phonemize(text.strip(), p.language)
         extra = {} if speaker_embedding is None else {"speaker_embedding": tuple(speaker_embedding)}
+        if int(sample_rate) != 24000:
+            extra["sample_rate"] = int(sample_rate)
         return self.batcher.submit(ids, speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver, n_timesteps=p.n_timesteps,
                                    scale_correction=p.scale_correction, length_scale=p.length_scale, **extra)
 
     async def speak(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
-                    speaker_embedding=None):
-        res = await asyncio.wrap_future(self.submit(text, voice, speed, steps, solver, speaker_embedding))
+                    speaker_embedding=None, sample_rate: int = 24000):
+        res = await asyncio.wrap_future(self.submit(text, voice, speed, steps, solver, speaker_embedding, sample_rate))
         return res["audio"] if "audio" in res else res["mel"]

@@ -5,7 +5,7 @@
     python tools/align.py --synthetic 32 [--tokens 128 --frames 1500] [--repeat 200]      # no files: random weights, planted durations
 
 FILE holds one line of whitespace-separated phoneme ids per clip (the phonemiser is outside this package: ``process_text`` of the
-reference installation produces them).  Clips must be 24 kHz mono PCM wav, read as tools/enroll.py reads them.  Prints, per clip,
+reference installation produces them).  Clips are PCM wav at any sample rate, read as tools/enroll.py reads them.  Prints, per clip,
 each token's duration in fine frames (hop 128) and milliseconds beside the predictor's, and ``scale_correction`` = aligned total /
 predicted total; the .npz holds ``durations``, ``predicted_durations``, ``scale_correction``, ``score``, ``mel_fine_lengths``.
 
@@ -145,18 +145,18 @@ def main() -> int:
         return synthetic_run(args, inf)
     if not (args.matcha and args.ids_file and args.wavs):
         ap.error("give --matcha, --ids-file and at least one wav (or --synthetic N)")
-    from enroll import read_wav
+    from enroll import read_wavs
     ids = [[int(t) for t in line.split()] for line in Path(args.ids_file).read_text().splitlines() if line.strip()]
     if len(ids) != len(args.wavs):
         ap.error(f"{args.ids_file} has {len(ids)} lines for {len(args.wavs)} clips")
     model = inf.load_matcha("matcha", args.matcha)
     dev = next(model.parameters()).device
-    clips = [read_wav(p) for p in args.wavs]
+    clips, rates = read_wavs(args.wavs)
     x = torch.zeros(len(ids), max(len(r) for r in ids), dtype=torch.long)
     for b, r in enumerate(ids):
         x[b, :len(r)] = torch.tensor(r)
     x_len = torch.tensor([len(r) for r in ids])
-    out = model.align(x.to(dev), x_len.to(dev), audio=clips, speaker=args.speaker)
+    out = model.align(x.to(dev), x_len.to(dev), audio=clips, speaker=args.speaker, sample_rate=rates)
     host = {k: v.cpu().numpy() for k, v in out.items()}
     for b, path in enumerate(args.wavs):
         n = len(ids[b])

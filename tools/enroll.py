@@ -4,7 +4,8 @@
     python tools/enroll.py --matcha CKPT --style-encoder CKPT_OR_DIR --out voice.npz clip1.wav clip2.wav ...
     python tools/enroll.py --synthetic 10          # ten synthetic 5 s clips on random weights (profiling / smoke, no files needed)
 
-Clips must be 24 kHz mono PCM wav (8 / 16 / 32 bit); they are read with the standard library's ``wave`` module.  The output .npz
+Clips are PCM wav (8 / 16 / 32 bit) at any sample rate, read with the standard library's ``wave`` module; of a multi-channel file
+channel 0 is used (the reference's ``audio[0]``), and clips that are not at 24 kHz are converted on the device.  The output .npz
 holds ``e_enc`` and ``e_dur`` ([spk_emb_dim] each): pass them as ``synthesise(speaker_embeddings=...)``, as a batcher
 request's ``speaker_embedding``, or to ``MatchaTTSInfer.add_speaker``."""
 import argparse
@@ -21,10 +22,10 @@ sys.path.insert(0, str(ROOT))
 PKG = "matcha-tts-24k_amd"
 
 
-def read_wav(path) -> torch.Tensor:
+def read_wav(path):
+    """``(samples: 1-D float32 tensor in [-1, 1], sample rate)`` of a PCM wav file; channel 0 of a multi-channel file."""
     with wave.open(str(path), "rb") as w:
-        if w.getframerate() != 24000 or w.getnchannels() != 1:
-            raise ValueError(f"{path}: need 24 kHz mono, got {w.getframerate()} Hz x {w.getnchannels()} channels (resample first)")
+        rate, channels = w.getframerate(), w.getnchannels()
         width, raw = w.getsampwidth(), w.readframes(w.getnframes())
     if width == 2:
         a = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
@@ -34,7 +35,13 @@ def read_wav(path) -> torch.Tensor:
         a = (np.frombuffer(raw, dtype=np.uint8).astype(np.float32) - 128.0) / 128.0
     else:
         raise ValueError(f"{path}: unsupported PCM sample width {width}")
-    return torch.from_numpy(a.copy())
+    return torch.from_numpy(a[::channels].copy()), int(rate)
+
+
+def read_wavs(paths):
+    """``(clips, rates)`` of several files, as the ``audio=`` / ``sample_rate=`` arguments of the model's methods take them."""
+    pairs = [read_wav(p) for p in paths]
+    return [c for c, _ in pairs], [r for _, r in pairs]
 
 
 def main() -> int:
@@ -58,14 +65,15 @@ def main() -> int:
         enc = style.StyleEncoder(**style.DEFAULT_CFG).to("cuda").eval()
         t = torch.arange(5 * 24000, dtype=torch.float32) / 24000.0
         clips = [(0.4 * torch.sin(2 * np.pi * (120.0 + 20.0 * i) * t) + 0.05 * torch.randn(t.numel())).clamp(-1, 1) for i in range(args.synthetic)]
+        rates = 24000
     else:
         if not (args.matcha and args.style_encoder and args.wavs):
             ap.error("give --matcha, --style-encoder and at least one wav (or --synthetic N)")
         model = inf.load_matcha("matcha", args.matcha)
         enc = style.load_style_encoder(args.style_encoder)
-        clips = [read_wav(p) for p in args.wavs]
+        clips, rates = read_wavs(args.wavs)
     for _ in range(max(args.repeat, 1)):
-        e_enc, e_dur = model.enroll_voice(clips, enc)
+        e_enc, e_dur = model.enroll_voice(clips, enc, sample_rate=rates)
     torch.cuda.synchronize()
     np.savez(args.out, e_enc=e_enc[0].cpu().numpy(), e_dur=e_dur[0].cpu().numpy())
     print(f"[enroll] {len(clips)} clips -> {args.out}: e_enc |max| {e_enc.abs().max().item():.4f}, e_dur |max| {e_dur.abs().max().item():.4f}")

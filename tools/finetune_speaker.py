@@ -5,7 +5,7 @@
                                      [--batch-size 16] [--out voice_ft] clip1.wav clip2.wav ...
     python tools/finetune_speaker.py --synthetic-model tiny --ids-file FILE clip1.wav ...      # random weights (trials, tests)
 
-FILE holds one line of whitespace-separated phoneme ids per clip (the phonemiser is outside this package).  Clips are 24 kHz mono
+FILE holds one line of whitespace-separated phoneme ids per clip (the phonemiser is outside this package).  Clips are any-rate
 PCM wav, read as tools/enroll.py reads them.  The start is table speaker ``--speaker`` or the rows of a ``--voice`` file (the .npz
 of tools/enroll.py: ``e_enc``, ``e_dur``).  What is trained and how follows the reference's matcha/finetune_speaker.py: everything
 frozen but the two rows, Adam on the duration + prior loss, alignment searched anew every step; dropout is off here and the
@@ -43,7 +43,7 @@ def main() -> int:
     if bool(args.matcha) == bool(args.synthetic_model):
         ap.error("give either --matcha or --synthetic-model")
     inf = importlib.import_module(PKG + ".inference")
-    from enroll import read_wav
+    from enroll import read_wavs
     ids = [[int(t) for t in line.split()] for line in Path(args.ids_file).read_text().splitlines() if line.strip()]
     if len(ids) != len(args.wavs):
         ap.error(f"{args.ids_file} has {len(ids)} lines for {len(args.wavs)} clips")
@@ -60,14 +60,14 @@ def main() -> int:
     if args.voice:
         v = np.load(args.voice)
         start = {"speaker_embeddings": (torch.from_numpy(v["e_enc"]).to(dev), torch.from_numpy(v["e_dur"]).to(dev))}
-    clips = [read_wav(p) for p in args.wavs]
+    clips, rates = read_wavs(args.wavs)
     B = len(ids)
     x = torch.zeros(B, max(len(r) for r in ids), dtype=torch.long)
     for b, r in enumerate(ids):
         x[b, :len(r)] = torch.tensor(r)
     x_len = torch.tensor([len(r) for r in ids])
     e_enc, e_dur, history = model.finetune_speaker(x.to(dev), x_len.to(dev), audio=clips, steps=args.steps, lr=args.lr,
-                                                   batch_size=args.batch_size or None, shuffle_seed=args.seed, **start)
+                                                   batch_size=args.batch_size or None, shuffle_seed=args.seed, sample_rate=rates, **start)
     print(f"{'step':>6s} {'dur_loss':>10s} {'prior_loss':>11s}")
     every = max(args.print_every, 1)
     for k, (d, p) in enumerate(zip(history["dur_loss"], history["prior_loss"])):

@@ -5,7 +5,7 @@
     python tools/score.py --matcha CKPT --ids-file FILE --style-encoder SE --enroll a.wav b.wav -- clip1.wav ...
     python tools/score.py --synthetic 32 [--tokens 128] [--repeat 20]          # no files: random weights, planted durations
 
-FILE holds one line of whitespace-separated phoneme ids per clip (the phonemiser is outside this package).  Clips are 24 kHz mono
+FILE holds one line of whitespace-separated phoneme ids per clip (the phonemiser is outside this package).  Clips are any-rate
 PCM wav, read as tools/enroll.py reads them.  The voice is table speaker ``--speaker``, or the row a style encoder gives the
 ``--enroll`` clips (``MatchaTTSInfer.enroll_voice``).  ``diff_loss`` is averaged over ``--t-grid`` times (k + 0.5) / K with ONE
 seeded noise draw, so two voices or two checkpoints are compared on the same estimate.  Prints a table of the three losses per
@@ -91,7 +91,7 @@ def main() -> int:
         ap.error("give --matcha, --ids-file and at least one wav (or --synthetic N)")
     if bool(args.enroll) != bool(args.style_encoder):
         ap.error("--enroll and --style-encoder go together")
-    from enroll import read_wav
+    from enroll import read_wavs
     ids = [[int(t) for t in line.split()] for line in Path(args.ids_file).read_text().splitlines() if line.strip()]
     if len(ids) != len(args.wavs):
         ap.error(f"{args.ids_file} has {len(ids)} lines for {len(args.wavs)} clips")
@@ -100,16 +100,17 @@ def main() -> int:
     voice = {"speaker": args.speaker}
     if args.enroll:
         style = importlib.import_module(PKG + ".style")
-        voice = {"speaker_embeddings": model.enroll_voice([read_wav(p) for p in args.enroll], style.load_style_encoder(args.style_encoder))}
-    clips = [read_wav(p) for p in args.wavs]
+        enrol_clips, enrol_rates = read_wavs(args.enroll)
+        voice = {"speaker_embeddings": model.enroll_voice(enrol_clips, style.load_style_encoder(args.style_encoder), sample_rate=enrol_rates)}
+    clips, rates = read_wavs(args.wavs)
     B = len(ids)
     x = torch.zeros(B, max(len(r) for r in ids), dtype=torch.long)
     for b, r in enumerate(ids):
         x[b, :len(r)] = torch.tensor(r)
     x_len = torch.tensor([len(r) for r in ids])
-    T = inf.fix_len_compatibility(max(c.numel() // inf.STD_RES_HOP_LENGTH + 1 for c in clips))
+    T = inf.fix_len_compatibility(max(-(-24000 * c.numel() // r) // inf.STD_RES_HOP_LENGTH + 1 for c, r in zip(clips, rates)))
     noise = torch.randn(B, model.hp.n_feats, T, generator=torch.Generator().manual_seed(args.seed))
-    out = model.score(x.to(dev), x_len.to(dev), audio=clips, t=t_grid(args.t_grid, B), noise=noise.to(dev), **voice)
+    out = model.score(x.to(dev), x_len.to(dev), audio=clips, t=t_grid(args.t_grid, B), noise=noise.to(dev), sample_rate=rates, **voice)
     host = {k: v.cpu().numpy() for k, v in out.items()}
     diff = host["diff_loss_per_utterance"].mean(0)
     print(f"{'file':40s} {'frames':>7s} {'dur_loss':>10s} {'prior_loss':>11s} {'diff_loss':>10s} {'mas/frame':>10s}")
