@@ -500,6 +500,53 @@ int mtts_groupnorm_mish(const float* d_y, const float* d_gamma, const float* d_b
 int mtts_groupnorm_mish_rows(const float* d_y, const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias,
                              int chbias_stride, int B, int T, int C, int G, float eps, float* d_out, void* d_scratch, void* stream);
 
+/* Kernel-level entries of the kernels that are not GEMMs: the Vocos tail (csrc/vocos.hip) and the solver / layout glue
+ * (csrc/norm_glue.hip).  No context, fp32 device buffers in the layout the model hands to the kernel, stream-ordered, no
+ * allocation.  Each entry decides on the host what the host can decide -- null pointers, the launcher's own shape limits, a leading
+ * dimension smaller than col_off + C -- and returns -1 (mtts_last_error) before anything is launched; otherwise it calls the
+ * launcher the model calls, unchanged.
+ * mtts_dwconv7_ln: ConvNeXtBlock front, y = LayerNorm_C(depthwise_conv_k7(x) + bias) * gamma + beta on rows [B*T, C]; d_w7 is [7][C]
+ *   (the packed layout, tap-major); C % 4 == 0, C <= 2048.  d_lengths (int64 [B] or NULL): utterance b ends at clamp(lengths[b], 0, T)
+ *   frames, taps beyond it are the conv's zero padding whatever the buffer holds; rows at or beyond it are not defined.
+ * mtts_spec_polar: in place on rows [M, ld]: columns (k, off + k), k < nbins, hold (log-magnitude, phase) and become
+ *   min(exp(m), clip) * (cos p, sin p); off >= nbins, off + nbins <= ld; no other column is touched.
+ * mtts_istft_ola: torch.istft(center=True) tail on windowed frames [B*T, n_fft]: audio [B, hop*(T-1)], sample s = sum of the frames
+ *   covering pos = s + n_fft/2 over the sum of window^2 there (kept undivided where that sum is <= 1e-11); T >= 2, hop divides n_fft.
+ *   d_lengths (or NULL): row b is the result of its first clamp(lengths[b], 0, T) frames alone, then exact zeros.
+ * mtts_ode_combine: the fixed-grid solver's state updates on rows [M, C] with leading dimensions ldy / ldk / ldo >= C: stage 0
+ *   y + dt k1; stages 1..4 torchdiffeq's rk4 (3/8 rule) in its operation order (norm_glue.hip).  d_dt_b NULL: one dt; else dt =
+ *   d_dt_b[row / T] (M % T == 0).  Stage k reads k1..k_k; d_out may be d_y (with ldo == ldy).
+ * mtts_step_tables: per-utterance stage times of one solver step (stages 1, 2 or 4): d_tv [stages*B], d_dt_b [B], row factors
+ *   d_rs_full / d_rs_half [B*T] = mask * dt, mask * (0.5 dt).
+ * mtts_time_sinusoid: out[i] = sin((scale t_i) f_j) | cos(...), j < half, [nt, 2*half]; the times come from h_t (host, nt <= 256) or
+ *   from d_t (device, any nt): exactly one of the two is non-null.
+ * mtts_rope: half-rotation RoPE in place on the q and k sections of rows [B*T, 3*H*D], first d_rope (even, <= D) dims of each head,
+ *   position = row % T; d_cos / d_sin [>= T, d_rope].
+ * mtts_cf_to_cl: dst[b*T + t, col_off + c] = src[b, c, t] (+ add[b, c, t]) for t < T, source rows T_src >= T long (0: T);
+ *   d_lengths (or NULL): rows at t >= lengths[b] are written as zero and their source is not read.  col_off + C <= ld.
+ * mtts_cl_to_cf: dst[b, c, t] = src[b*T + t, c] * scale + shift for t < T_out <= T; C <= ld.
+ * mtts_slots_to_cl / mtts_cl_to_slots: the same two moves between a slot pool [S, C, T_pool] and the rows of utterances living in
+ *   slots d_slots[b] (int32 [B]); a slot outside [0, S) is neither read (its rows are written as zero) nor written.  T <= T_pool. */
+int mtts_dwconv7_ln(const float* d_x, const float* d_w7, const float* d_bias, const float* d_gamma, const float* d_beta, float eps,
+                    int B, int T, int C, const int64_t* d_lengths, float* d_y, void* stream);
+int mtts_spec_polar(float* d_x, int M, int ld, int nbins, int off, float clip, void* stream);
+int mtts_istft_ola(const float* d_frames, const float* d_window, int B, int T, int n_fft, int hop, const int64_t* d_lengths,
+                   float* d_audio, void* stream);
+int mtts_ode_combine(int stage, float dt, const float* d_dt_b, int T, const float* d_y, int ldy, const float* d_k1, const float* d_k2,
+                     const float* d_k3, const float* d_k4, int ldk, float* d_out, int ldo, int M, int C, void* stream);
+int mtts_step_tables(const float* d_t0, const float* d_t1, const float* d_mask, int B, int T, int stages, float* d_tv, float* d_dt_b,
+                     float* d_rs_full, float* d_rs_half, void* stream);
+int mtts_time_sinusoid(const float* d_freqs, const float* h_t, const float* d_t, int nt, int half, float scale, float* d_out,
+                       void* stream);
+int mtts_rope(float* d_qkv, int B, int T, int H, int D, int d_rope, const float* d_cos, const float* d_sin, void* stream);
+int mtts_cf_to_cl(const float* d_src, const float* d_add, int B, int C, int T, int T_src, float* d_dst, int ld, int col_off,
+                  const int64_t* d_lengths, void* stream);
+int mtts_cl_to_cf(const float* d_src, int ld, int B, int C, int T, float* d_dst, int T_out, float scale, float shift, void* stream);
+int mtts_slots_to_cl(const float* d_pool, const int32_t* d_slots, int S, int T_pool, int B, int C, int T, float* d_dst, int ld,
+                     int col_off, void* stream);
+int mtts_cl_to_slots(const float* d_src, int ld, int B, int C, int T, float* d_pool, const int32_t* d_slots, int S, int T_pool,
+                     void* stream);
+
 /* ---------------------------------------------------------------- Vocos-24k head */
 
 /* Vocos.decode -- reference matcha/vocos24k/vocos_wrapper.py:8-9 (third-party vocos package; architecture sizes from

@@ -223,6 +223,17 @@ def load() -> C.CDLL:
         "mtts_groupnorm_scratch_bytes": (i64, [i32, i32, i32]),
         "mtts_groupnorm_mish": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]),
         "mtts_groupnorm_mish_rows": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp]),
+        "mtts_dwconv7_ln": (i32, [vp, vp, vp, vp, vp, f32, i32, i32, i32, vp, vp, vp]),
+        "mtts_spec_polar": (i32, [vp, i32, i32, i32, i32, f32, vp]),
+        "mtts_istft_ola": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp]),
+        "mtts_ode_combine": (i32, [i32, f32, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]),
+        "mtts_step_tables": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "mtts_time_sinusoid": (i32, [vp, vp, vp, i32, i32, f32, vp, vp]),
+        "mtts_rope": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "mtts_cf_to_cl": (i32, [vp, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp]),
+        "mtts_cl_to_cf": (i32, [vp, i32, i32, i32, i32, vp, i32, f32, f32, vp]),
+        "mtts_slots_to_cl": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp]),
+        "mtts_cl_to_slots": (i32, [vp, i32, i32, i32, i32, vp, vp, i32, i32, vp]),
         "mtts_vocos_create": (vp, [i32, i32, i32, i32, i32, i32]),
         "mtts_vocos_destroy": (None, [vp]),
         "mtts_vocos_set_tensor": (i32, [vp, C.c_char_p, vp, i64]),
@@ -1386,3 +1397,95 @@ def groupnorm_mish(y, gamma, beta, mask, B, T, G=8, eps=1e-5):
     check(lib.mtts_groupnorm_mish(ptr(y), ptr(gamma), ptr(beta), ptr(mask), B, T, Cc, G, eps, ptr(out), scratch.data_ptr(),
                                   stream_ptr()))
     return out
+
+
+# ---- the kernels that are not GEMMs (csrc/vocos.hip, csrc/norm_glue.hip): thin wrappers of their unit entries.  Buffers a kernel
+# writes can be passed in (``out=`` / ``dst``), so that a test can fill them with a sentinel first.
+def dwconv7_ln(x, w7, bias, gamma, beta, B, T, *, eps=1e-6, lengths=None, out=None):
+    """x [B*T, C] rows, w7 [7, C] (tap-major); lengths int64 [B] or None.  Returns y [B*T, C]."""
+    y = torch.empty_like(x) if out is None else out
+    check(load().mtts_dwconv7_ln(ptr(x), ptr(w7), ptr(bias), ptr(gamma), ptr(beta), float(eps), B, T, x.shape[1], ptr(lengths), ptr(y),
+                                 stream_ptr()))
+    return y
+
+
+def spec_polar(x, nbins, off, clip=1e2):
+    """In place on x [M, ld]: columns (k, off + k) hold (log-magnitude, phase) and become (Re, Im)."""
+    check(load().mtts_spec_polar(ptr(x), x.shape[0], x.shape[1], nbins, off, float(clip), stream_ptr()))
+    return x
+
+
+def istft_ola(frames, window, B, T, hop, *, lengths=None, out=None):
+    """frames [B*T, n_fft] (already windowed once), window [n_fft] -> audio [B, hop * (T - 1)]."""
+    n_fft = frames.shape[1]
+    audio = torch.empty(B, hop * (T - 1), dtype=torch.float32, device=frames.device) if out is None else out
+    check(load().mtts_istft_ola(ptr(frames), ptr(window), B, T, n_fft, hop, ptr(lengths), ptr(audio), stream_ptr()))
+    return audio
+
+
+def ode_combine(stage, dt, y, k1, k2=None, k3=None, k4=None, *, C, out, T=0):
+    """Rows [M, ld] (ld = each tensor's second dimension; k1..k4 share one); ``dt`` a float, or a device tensor [M / T] of one dt
+    per utterance.  ``out`` may be ``y``."""
+    per_utt = torch.is_tensor(dt)
+    check(load().mtts_ode_combine(stage, 0.0 if per_utt else float(dt), ptr(dt) if per_utt else None, T, ptr(y), y.shape[1], ptr(k1),
+                                  ptr(k2), ptr(k3), ptr(k4), k1.shape[1], ptr(out), out.shape[1], y.shape[0], C, stream_ptr()))
+    return out
+
+
+def step_tables(t0, t1, mask, stages, out=None):
+    """t0, t1 [B], mask [B, T] -> (tv [stages * B], dt_b [B], rs_full [B*T], rs_half [B*T]); ``out``: those four buffers."""
+    B, T = mask.shape
+    dev = mask.device
+    tv, dt_b, rs_full, rs_half = out if out is not None else (
+        torch.empty(stages * B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.float32, device=dev),
+        torch.empty(B * T, dtype=torch.float32, device=dev), torch.empty(B * T, dtype=torch.float32, device=dev))
+    check(load().mtts_step_tables(ptr(t0), ptr(t1), ptr(mask), B, T, stages, ptr(tv), ptr(dt_b), ptr(rs_full), ptr(rs_half), stream_ptr()))
+    return tv, dt_b, rs_full, rs_half
+
+
+def time_sinusoid(freqs, t, scale=1000.0, out=None):
+    """freqs [half] on the device; ``t`` a CPU tensor (the host form, at most 256 times) or a device tensor (the device form).
+    Returns [nt, 2 * half] = sin | cos."""
+    nt, half = t.numel(), freqs.numel()
+    emb = torch.empty(nt, 2 * half, dtype=torch.float32, device=freqs.device) if out is None else out
+    if t.is_cuda:
+        check(load().mtts_time_sinusoid(ptr(freqs), None, ptr(t), nt, half, float(scale), ptr(emb), stream_ptr()))
+    else:
+        t = t.detach().to(torch.float32).contiguous()
+        check(load().mtts_time_sinusoid(ptr(freqs), t.data_ptr(), None, nt, half, float(scale), ptr(emb), stream_ptr()))
+    return emb
+
+
+def rope(qkv, B, T, H, D, d_rope, cos, sin):
+    """In place on qkv [B*T, 3*H*D]; cos / sin [>= T, d_rope]."""
+    check(load().mtts_rope(ptr(qkv), B, T, H, D, d_rope, ptr(cos), ptr(sin), stream_ptr()))
+    return qkv
+
+
+def cf_to_cl(src, dst, *, T=None, col_off=0, add=None, lengths=None):
+    """src [B, C, T_src] (+ add) -> dst [B*T, ld] at columns [col_off, col_off + C); T defaults to T_src."""
+    B, Cc, T_src = src.shape
+    T = T_src if T is None else T
+    check(load().mtts_cf_to_cl(ptr(src), ptr(add), B, Cc, T, T_src, ptr(dst), dst.shape[1], col_off, ptr(lengths), stream_ptr()))
+    return dst
+
+
+def cl_to_cf(src, dst, *, T, scale=1.0, shift=0.0):
+    """src [B*T, ld] -> dst [B, C, T_out] = src * scale + shift."""
+    B, Cc, T_out = dst.shape
+    check(load().mtts_cl_to_cf(ptr(src), src.shape[1], B, Cc, T, ptr(dst), T_out, float(scale), float(shift), stream_ptr()))
+    return dst
+
+
+def slots_to_cl(pool, slots, dst, *, T, col_off=0):
+    """pool [S, C, T_pool], slots int32 [B] -> dst [B*T, ld] at columns [col_off, col_off + C)."""
+    S, Cc, T_pool = pool.shape
+    check(load().mtts_slots_to_cl(ptr(pool), ptr(slots), S, T_pool, slots.numel(), Cc, T, ptr(dst), dst.shape[1], col_off, stream_ptr()))
+    return dst
+
+
+def cl_to_slots(src, pool, slots, *, T):
+    """src [B*T, ld] -> pool [S, C, T_pool] at the slots of int32 [B]."""
+    S, Cc, T_pool = pool.shape
+    check(load().mtts_cl_to_slots(ptr(src), src.shape[1], slots.numel(), Cc, T, ptr(pool), ptr(slots), S, T_pool, stream_ptr()))
+    return pool

@@ -762,4 +762,130 @@ int mtts_groupnorm_mish_p16(const float* d_y, const float* d_gamma, const float*
     return 0;
 }
 
+// ---- the kernels that are not GEMMs: the Vocos tail (vocos.hip) and the solver / layout glue (norm_glue.hip).  Each entry refuses on
+// the host what the host can decide, then calls the launcher the model calls, unchanged.
+#define REFUSE_IF(cond, msg)                 \
+    do {                                     \
+        if (cond) { set_error(msg); return -1; } \
+    } while (0)
+
+int mtts_dwconv7_ln(const float* d_x, const float* d_w7, const float* d_bias, const float* d_gamma, const float* d_beta, float eps,
+                    int B, int T, int C, const int64_t* d_lengths, float* d_y, void* stream) {
+    REFUSE_IF(!d_x || !d_w7 || !d_bias || !d_gamma || !d_beta || !d_y, "mtts_dwconv7_ln: null buffer");
+    REFUSE_IF(B <= 0 || T <= 0, "mtts_dwconv7_ln: empty batch");
+    REFUSE_IF(C <= 0 || (C & 3) || C > 2048, "mtts_dwconv7_ln: C must be a multiple of 4, at most 2048");
+    HIP_OK(launch_dwconv7_ln(d_x, d_w7, d_bias, d_gamma, d_beta, eps, B, T, C, d_y, static_cast<hipStream_t>(stream), d_lengths));
+    return 0;
+}
+
+int mtts_spec_polar(float* d_x, int M, int ld, int nbins, int off, float clip, void* stream) {
+    REFUSE_IF(!d_x, "mtts_spec_polar: null buffer");
+    REFUSE_IF(M <= 0 || nbins <= 0, "mtts_spec_polar: empty spectrum");
+    REFUSE_IF(off < nbins || off + nbins > ld, "mtts_spec_polar: the two halves overlap or leave the row (nbins <= off, off + nbins <= ld)");
+    HIP_OK(launch_spec_polar(d_x, M, ld, nbins, off, clip, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int mtts_istft_ola(const float* d_frames, const float* d_window, int B, int T, int n_fft, int hop, const int64_t* d_lengths,
+                   float* d_audio, void* stream) {
+    REFUSE_IF(!d_frames || !d_window || !d_audio, "mtts_istft_ola: null buffer");
+    REFUSE_IF(B <= 0, "mtts_istft_ola: empty batch");
+    REFUSE_IF(T < 2, "mtts_istft_ola: need at least 2 frames");
+    REFUSE_IF(n_fft <= 0 || hop <= 0 || n_fft % hop, "mtts_istft_ola: hop must divide n_fft");
+    HIP_OK(launch_istft_ola(d_frames, d_window, B, T, n_fft, hop, d_audio, static_cast<hipStream_t>(stream), d_lengths));
+    return 0;
+}
+
+int mtts_ode_combine(int stage, float dt, const float* d_dt_b, int T, const float* d_y, int ldy, const float* d_k1, const float* d_k2,
+                     const float* d_k3, const float* d_k4, int ldk, float* d_out, int ldo, int M, int C, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    REFUSE_IF(stage < 0 || stage > 4, "mtts_ode_combine: stage is 0 .. 4");
+    REFUSE_IF(!d_y || !d_k1 || !d_out || (stage >= 2 && !d_k2) || (stage >= 3 && !d_k3) || (stage >= 4 && !d_k4),
+              "mtts_ode_combine: null buffer (stage k reads k1 .. k_k)");
+    REFUSE_IF(M <= 0 || C <= 0, "mtts_ode_combine: empty state");
+    REFUSE_IF(ldy < C || ldk < C || ldo < C, "mtts_ode_combine: a leading dimension is smaller than C");
+    REFUSE_IF(d_out == d_y && ldo != ldy, "mtts_ode_combine: in place needs ldo == ldy");
+    if (!d_dt_b) {
+        HIP_OK(launch_ode_combine(stage, dt, d_y, ldy, d_k1, d_k2, d_k3, d_k4, ldk, d_out, ldo, M, C, s));
+        return 0;
+    }
+    REFUSE_IF(T <= 0 || (M % T), "mtts_ode_combine: per-utterance dt needs T > 0 dividing M");
+    HIP_OK(launch_ode_combine_rows(stage, d_dt_b, T, d_y, ldy, d_k1, d_k2, d_k3, d_k4, ldk, d_out, ldo, M, C, s));
+    return 0;
+}
+
+int mtts_step_tables(const float* d_t0, const float* d_t1, const float* d_mask, int B, int T, int stages, float* d_tv, float* d_dt_b,
+                     float* d_rs_full, float* d_rs_half, void* stream) {
+    REFUSE_IF(!d_t0 || !d_t1 || !d_mask || !d_tv || !d_dt_b || !d_rs_full || !d_rs_half, "mtts_step_tables: null buffer");
+    REFUSE_IF(B <= 0 || T <= 0, "mtts_step_tables: empty batch");
+    REFUSE_IF(stages != 1 && stages != 2 && stages != 4, "mtts_step_tables: stages is 1 (euler), 2 (midpoint) or 4 (rk4)");
+    HIP_OK(launch_step_tables(d_t0, d_t1, d_mask, B, T, stages, d_tv, d_dt_b, d_rs_full, d_rs_half, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int mtts_time_sinusoid(const float* d_freqs, const float* h_t, const float* d_t, int nt, int half, float scale, float* d_out,
+                       void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    REFUSE_IF(!d_freqs || !d_out, "mtts_time_sinusoid: null buffer");
+    REFUSE_IF((h_t != nullptr) == (d_t != nullptr), "mtts_time_sinusoid: the times come from h_t or from d_t, one of the two");
+    REFUSE_IF(nt <= 0 || half <= 0, "mtts_time_sinusoid: empty table");
+    if (d_t) {
+        HIP_OK(launch_time_sinusoid_dev(d_freqs, d_t, nt, half, scale, d_out, s));
+        return 0;
+    }
+    REFUSE_IF(nt > MAX_EVALS, "mtts_time_sinusoid: at most 256 host times (pass more in device memory)");
+    TimeVals tv;
+    for (int i = 0; i < MAX_EVALS; ++i) tv.t[i] = i < nt ? h_t[i] : 0.f;
+    HIP_OK(launch_time_sinusoid(d_freqs, tv, nt, half, scale, d_out, s));
+    return 0;
+}
+
+int mtts_rope(float* d_qkv, int B, int T, int H, int D, int d_rope, const float* d_cos, const float* d_sin, void* stream) {
+    REFUSE_IF(!d_qkv || !d_cos || !d_sin, "mtts_rope: null buffer");
+    REFUSE_IF(B <= 0 || T <= 0 || H <= 0 || D <= 0, "mtts_rope: empty batch");
+    REFUSE_IF(d_rope <= 0 || (d_rope & 1) || d_rope > D, "mtts_rope: d_rope must be even and within the head (0 < d_rope <= D)");
+    HIP_OK(launch_rope(d_qkv, B, T, H, D, d_rope, d_cos, d_sin, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int mtts_cf_to_cl(const float* d_src, const float* d_add, int B, int C, int T, int T_src, float* d_dst, int ld, int col_off,
+                  const int64_t* d_lengths, void* stream) {
+    REFUSE_IF(!d_src || !d_dst, "mtts_cf_to_cl: null buffer");
+    REFUSE_IF(B <= 0 || C <= 0 || T <= 0, "mtts_cf_to_cl: empty batch");
+    REFUSE_IF(T_src != 0 && T_src < T, "mtts_cf_to_cl: T_src is shorter than T");
+    REFUSE_IF(col_off < 0 || col_off + C > ld, "mtts_cf_to_cl: ld is smaller than col_off + C");
+    HIP_OK(launch_cf_to_cl(d_src, d_add, B, C, T, d_dst, ld, col_off, static_cast<hipStream_t>(stream), T_src, d_lengths));
+    return 0;
+}
+
+int mtts_cl_to_cf(const float* d_src, int ld, int B, int C, int T, float* d_dst, int T_out, float scale, float shift, void* stream) {
+    REFUSE_IF(!d_src || !d_dst, "mtts_cl_to_cf: null buffer");
+    REFUSE_IF(B <= 0 || C <= 0 || T <= 0, "mtts_cl_to_cf: empty batch");
+    REFUSE_IF(T_out <= 0 || T_out > T, "mtts_cl_to_cf: T_out must be within 1 .. T");
+    REFUSE_IF(ld < C, "mtts_cl_to_cf: ld is smaller than C");
+    HIP_OK(launch_cl_to_cf(d_src, ld, B, C, T, d_dst, T_out, scale, shift, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int mtts_slots_to_cl(const float* d_pool, const int32_t* d_slots, int S, int T_pool, int B, int C, int T, float* d_dst, int ld,
+                     int col_off, void* stream) {
+    REFUSE_IF(!d_pool || !d_slots || !d_dst, "mtts_slots_to_cl: null buffer");
+    REFUSE_IF(S <= 0 || B <= 0 || C <= 0 || T <= 0, "mtts_slots_to_cl: empty batch or pool");
+    REFUSE_IF(T > T_pool, "mtts_slots_to_cl: T is longer than T_pool");
+    REFUSE_IF(col_off < 0 || col_off + C > ld, "mtts_slots_to_cl: ld is smaller than col_off + C");
+    HIP_OK(launch_slots_to_cl(d_pool, d_slots, S, T_pool, B, C, T, d_dst, ld, col_off, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int mtts_cl_to_slots(const float* d_src, int ld, int B, int C, int T, float* d_pool, const int32_t* d_slots, int S, int T_pool,
+                     void* stream) {
+    REFUSE_IF(!d_src || !d_pool || !d_slots, "mtts_cl_to_slots: null buffer");
+    REFUSE_IF(S <= 0 || B <= 0 || C <= 0 || T <= 0, "mtts_cl_to_slots: empty batch or pool");
+    REFUSE_IF(T > T_pool, "mtts_cl_to_slots: T is longer than T_pool");
+    REFUSE_IF(ld < C, "mtts_cl_to_slots: ld is smaller than C");
+    HIP_OK(launch_cl_to_slots(d_src, ld, B, C, T, d_pool, d_slots, S, T_pool, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+#undef REFUSE_IF
+
 }  // extern "C"

@@ -88,3 +88,55 @@ def test_istft_stage_against_torch_istft():
     assert out.shape == (2, hop * (T - 1)) and ref.shape == (1, hop * (T - 1))
     scale = float(ref.abs().max())
     assert (out[0] - ref[0]).abs().max() < 2e-5 * scale and torch.equal(out[0], out[1])
+
+
+# ------------------------------------------------------------------------------------------------ a second configuration
+SMALL = dict(n_mels=20, dim=68, inter=136, layers=2, n_fft=64, hop=16)
+
+
+@pytest.fixture(scope="module")
+def small():
+    """What the kernel-level entries bypass, at shapes the production head never takes: the [C,1,7] -> [7][C] repack of the depthwise
+    weight, the layer scale folded into pwconv2, the head rows re-spaced to im_off = 36 (33 bins), the DFT-basis matrix at n_fft 64,
+    hop ratio 4 at another size, a partly used second wave slot (dim 68)."""
+    if not torch.cuda.is_available():
+        pytest.fail("a HIP device is required for -m gpu tests (no CPU fallback exists)")
+    import vocos_oracle
+    syn, voc = sub("synthetic"), sub("vocoder")
+    sd = syn.make_vocos_state_dict(seed=23, **{k: v for k, v in SMALL.items() if k != "hop"})
+    model = voc.Vocos(**SMALL)
+    model.load_state_dict(sd, strict=True)
+    return vocos_oracle, sd, {k: v.double() for k, v in sd.items()}, model.to("cuda").eval()
+
+
+def small_decode(V, sd, mel):
+    with torch.inference_mode():
+        return V.decode(sd, mel, num_layers=SMALL["layers"], n_fft=SMALL["n_fft"], hop=SMALL["hop"])
+
+
+@pytest.mark.parametrize("B,T", [(2, 9), (1, 2)])
+def test_small_head_against_fp64(small, B, T):
+    V, sd, sd64, model = small
+    mel = torch.randn(B, SMALL["n_mels"], T, generator=torch.Generator().manual_seed(10 * B + T)) * 2.0 - 4.0
+    ref64, ref32 = small_decode(V, sd64, mel.double()), small_decode(V, sd, mel)
+    out = model.decode(mel.cuda()).cpu().double()
+    assert out.shape == ref64.shape == (B, SMALL["hop"] * (T - 1))
+    e_hip, e_cpu = (out - ref64).abs().max().item(), (ref32.double() - ref64).abs().max().item()
+    print(f"GLUE-PARITY vocos small B={B} T={T}: e_hip {e_hip:.3e} e_cpu32 {e_cpu:.3e}")
+    assert e_hip < 10 * e_cpu + 1e-6, (e_hip, e_cpu)
+
+
+def test_small_head_ragged_against_separate_fp64_decodes(small):
+    V, sd, sd64, model = small
+    B, T, lengths = 2, 9, [9, 4]
+    mel = torch.randn(B, SMALL["n_mels"], T, generator=torch.Generator().manual_seed(31)) * 2.0 - 4.0
+    mel[1, :, 4:] = float("nan")                               # the padded part is not read as data
+    out = model.decode(mel.cuda(), lengths).cpu().double()
+    ref64, ref32 = torch.zeros(B, SMALL["hop"] * (T - 1), dtype=torch.float64), torch.zeros(B, SMALL["hop"] * (T - 1))
+    for b, n in enumerate(lengths):
+        ref64[b, :SMALL["hop"] * (n - 1)] = small_decode(V, sd64, mel[b:b + 1, :, :n].double())[0]
+        ref32[b, :SMALL["hop"] * (n - 1)] = small_decode(V, sd, mel[b:b + 1, :, :n])[0]
+    assert (out[1, SMALL["hop"] * 3:] == 0).all()
+    e_hip, e_cpu = (out - ref64).abs().max().item(), (ref32.double() - ref64).abs().max().item()
+    print(f"GLUE-PARITY vocos small ragged: e_hip {e_hip:.3e} e_cpu32 {e_cpu:.3e}")
+    assert e_hip < 10 * e_cpu + 1e-6, (e_hip, e_cpu)
