@@ -698,6 +698,67 @@ int mtts_resample_forward(mtts_resampler* r, const float* d_in, int64_t ld_in, c
                           int64_t ld_out, int64_t* d_out_lengths, void* d_ws, int64_t ws_bytes, void* stream);
 int mtts_resample_status(const void* d_ws, void* stream);
 
+/* ---------------------------------------------------------------- corpus preparation: silence, mel statistics */
+
+/* What the reference does to a corpus before training, one file at a time on the host -- matcha/utils/measure_silence.py:66-132,
+ * matcha/utils/normalize_silence.py:86-220 and the per-file sums of matcha/utils/generate_data_statistics.py:120-131 -- for a
+ * ragged batch on the device.  Rows as for mtts_resample_forward: fp32 [B][ld] with ld % 4 == 0 and 16-byte aligned, lengths
+ * device int64 [B], checked on the device without a host read; stream-ordered, no allocation; nothing is read outside [0, len_b)
+ * of a row and nothing is written outside a row; what the host can see (null pointers, B < 1, a bad ld, a small workspace)
+ * returns -1; mtts_silence_status / mtts_mel_stats_status(d_ws, stream) -- the only entries here that wait -- report the first
+ * refused row of the latest call on that workspace through mtts_last_error.
+ *
+ * Windows.  W = mtts_silence_window(sample_rate) = (int)(0.01 * sample_rate) samples, anchored at sample 0; a clip of L samples has
+ * ceil(L / W) windows.  The last, partial window counts: its sum runs over the samples that exist and is divided by W (the
+ * reference pads with zeros).  rms[w] = (float)sqrt(q / W), q the sum of the exact squares in fp64 in a fixed shape: with VEC = 4
+ * when W % 4 == 0 and VEC = 1 otherwise, lane l of 64 adds, in ascending order, the squares of the window's samples
+ * e = VEC * (l + 64 k) + j (k = 0, 1, ...; j = 0 .. VEC - 1; e < W and inside the clip); then six steps v[l] = v[l] + v[l ^ o],
+ * o = 32, 16, 8, 4, 2, 1.  (mtts_waveform_finish's arithmetic.)  Thresholds are (float)pow(10, db / 20), compared in fp32.
+ *
+ * mtts_silence_measure: d_out int64 [B][6], in samples:
+ *   [0] content_start = W * (first window with rms >= thr_effective)
+ *   [1] content_end   = min(W * (last such window + 1), L);  both 0 for a clip without such a window
+ *   [2] leading_eff, [3] leading_abs, [4] trailing_eff, [5] trailing_abs = W * the length of the leading / trailing run of
+ *       windows with rms < thr (effective, absolute).
+ * These are the reference's numbers, quirks included: a trailing run counts the zero-padded last window, so trailing_* can exceed
+ * the silence that is there by up to W - 1 samples (a silent clip of 3000 samples at 24 kHz reports 3120 in [2..5]); a NaN window
+ * is neither "at or above" nor "below": it starts no content and ends a silent run.  L == 0 gives six zeros; a length outside
+ * [0, ld] gives six -1, the other rows are unaffected.  Two launches (windows, then one scan per clip); a clip's numbers do not
+ * depend on the batch it is in.
+ *
+ * mtts_silence_normalize: row b of d_out [B][ld_out] becomes
+ *     [lead_target zeros, or in[0 : content_start] when lead_target == -1] + in[content_start : content_end]
+ *     + [trail_target zeros, or in[content_end : L] when trail_target == -1],      then zeros up to ld_out,
+ * with (content_start, content_end) read from d_bounds [B][6] on the device (mtts_silence_measure's d_out), d_out_lengths[b] the
+ * new length and d_changed[b] = 0 when every end being normalised already has exactly its target count -- the reference's integer
+ * comparison, current_leading = content_start, current_trailing = L - content_end -- in which case the row is a copy of the
+ * input, else 1.  Samples are moved, never recomputed.  One launch gridded over (output tile, clip); d_out must not be d_in.
+ * A row whose new length exceeds ld_out, whose length is outside [0, ld_in] or whose bounds are not 0 <= start <= end <= L gets
+ * d_out_lengths[b] = -1 and zeros.  The host refuses a target that is neither -1 nor a whole multiple of W (reference :139-154).
+ *
+ * mtts_mel_stats: d_mel [B][F][T] fp32 (any F, any T), d_lengths int64 [B] frames ->
+ *   d_sums double [B][2] = (sum x, sum x * x) over f < F, t < len_b;  d_frames int64 [B] = len_b;  d_flags int32 [B] = 1 when one
+ *   of those x is NaN or Inf (the reference leaves such a file out, :52-53).  Frames at or beyond len_b are never read.
+ *   The order is a function of (f, t) only -- not of T, the batch or the grid: with C = mtts_mel_stats_chunk() = 256, chunk c of a
+ *   clip holds frames [C c, C c + C); lane i of the chunk starts from 0.0 and adds x[f][C c + i] (x * x likewise; both exact in
+ *   fp64) for f = 0 .. F - 1 in ascending order, a lane at or beyond len_b keeping 0.0; each group of 64 consecutive lanes runs
+ *   the steps v[i] = v[i] + v[i ^ o], o = 32 .. 1; the four groups meet as ((g0 + g1) + g2) + g3; the clip's sum starts from 0.0
+ *   and adds its ceil(len_b / C) chunks in ascending c.  A NumPy fp64 restatement in that order reproduces the bits.
+ *   len_b == 0 gives zeros; a len_b outside [0, T] gives zeros and d_frames[b] = -1.  Two launches. */
+int mtts_silence_window(int sample_rate);
+int64_t mtts_silence_workspace_bytes(int64_t ld, int B, int sample_rate);
+int mtts_silence_measure(const float* d_audio, int64_t ld, const int64_t* d_lengths, int B, int sample_rate, double effective_db,
+                         double absolute_db, int64_t* d_out, void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_silence_normalize(const float* d_in, int64_t ld_in, const int64_t* d_lengths, const int64_t* d_bounds, int B,
+                           int sample_rate, int64_t lead_target, int64_t trail_target, float* d_out, int64_t ld_out,
+                           int64_t* d_out_lengths, int32_t* d_changed, void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_silence_status(const void* d_ws, void* stream);
+int mtts_mel_stats_chunk(void);
+int64_t mtts_mel_stats_workspace_bytes(int B, int T);
+int mtts_mel_stats(const float* d_mel, int F, int T, const int64_t* d_lengths, int B, double* d_sums, int64_t* d_frames,
+                   int32_t* d_flags, void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_mel_stats_status(const void* d_ws, void* stream);
+
 /* ---------------------------------------------------------------- forced alignment (Monotonic Alignment Search) */
 
 /* Which fine mel frames belong to which token -- the alignment of the reference's training forward, matcha/models/matcha_tts.py:

@@ -497,4 +497,47 @@ struct WaveFinishArgs {
 constexpr int WAVE_CHUNK = 8192;       // samples per workgroup of the peak pass
 hipError_t launch_wave_finish(const WaveFinishArgs& a, hipStream_t s);
 
+// ---- corpus preparation (corpus.hip): silence bounds, silence normalisation and mel sums of a ragged batch, see include/mtts.h
+struct SilenceMeasureArgs {
+    const float* audio = nullptr;      // [B][ld], read only inside [0, len_b)
+    int64_t ld = 0;                    // row stride in samples (multiple of 4, rows 16-byte aligned)
+    const int64_t* lengths = nullptr;  // [B] samples
+    int B = 0;
+    int win = 0;                       // int(0.01 * sample_rate)
+    float thr_eff = 0.f, thr_abs = 0.f;
+    int64_t* out = nullptr;            // [B][6]: content_start, content_end, leading_eff, leading_abs, trailing_eff, trailing_abs
+    int64_t* status = nullptr;         // workspace header: first refused row + 1 (0: none), its length, ld, 0, entry (1)
+    float* rms = nullptr;              // workspace [B][nwin_max]
+    int nwin_max = 0;                  // ceil(ld / win)
+};
+struct SilenceNormArgs {
+    const float* in = nullptr;         // [B][ld_in]
+    int64_t ld_in = 0, ld_out = 0;
+    const int64_t* lengths = nullptr;  // [B]
+    const int64_t* bounds = nullptr;   // [B][6] of mtts_silence_measure (columns 0 and 1 are used)
+    int B = 0;
+    int64_t lead = -1, trail = -1;     // target samples, -1: that end stays as it is
+    float* out = nullptr;              // [B][ld_out]
+    int64_t* out_lengths = nullptr;    // [B]
+    int32_t* changed = nullptr;        // [B]
+    int64_t* status = nullptr;         // as above, entry 2, [3] = ld_out
+};
+struct MelStatsArgs {
+    const float* mel = nullptr;        // [B][F][T]
+    const int64_t* lengths = nullptr;  // [B] frames
+    int B = 0, F = 0, T = 0;
+    double* sums = nullptr;            // [B][2]: sum x, sum x^2
+    int64_t* frames = nullptr;         // [B]
+    int32_t* flags = nullptr;          // [B]: 1 when a value of the clip is NaN or Inf
+    int64_t* status = nullptr;         // as above, entry 3, [2] = T
+    double* part = nullptr;            // workspace [B][nchunks][2]
+    int32_t* part_flag = nullptr;      // workspace [B][nchunks]
+    int nchunks = 0;                   // ceil(T / MEL_STATS_CHUNK)
+};
+constexpr int MEL_STATS_CHUNK = 256;   // frames per workgroup of the mel sums: part of the documented summation order
+constexpr int SIL_NORM_TILE = 2048;    // output samples per workgroup of the silence normalisation
+hipError_t launch_silence_measure(const SilenceMeasureArgs& a, hipStream_t s);
+hipError_t launch_silence_normalize(const SilenceNormArgs& a, hipStream_t s);
+hipError_t launch_mel_stats(const MelStatsArgs& a, hipStream_t s);
+
 }  // namespace mtts

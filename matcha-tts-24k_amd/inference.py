@@ -161,7 +161,7 @@ class MatchaTTSInfer(nn.Module):
         return torch.cat(enc, 0), torch.cat(dur, 0)
 
     @torch.inference_mode()
-    def enroll_voice(self, clips, style_encoder, sample_rate=24000):
+    def enroll_voice(self, clips, style_encoder, silence=None, sample_rate=24000):
         """Speaker rows from audio -- the reference's offline chain matcha/vocos24k/mel_extractor.py (audio -> log-mel),
         matcha/utils/precompute_mels.py:100-113 (normalise with this model's mel statistics, hop 128), StyleEncoder.forward and
         matcha/add_speaker.py:40-62 (average over the clips) -- as one front-end call and one encoder call on the device.
@@ -170,7 +170,10 @@ class MatchaTTSInfer(nn.Module):
         [1, spk_emb_dim]; or a list of such lists for several voices -> [n_voices, spk_emb_dim].  The rows are what
         ``synthesise(speaker_embeddings=...)``, ``speaker_rows`` and ``add_speaker`` take.  ``sample_rate``: the clips' rate, an int
         or one int per clip (in the order of the flattened list); clips at another rate than 24 kHz are converted on the device
-        first (``resample.resample``, one call per distinct rate)."""
+        first (``resample.resample``, one call per distinct rate).  ``silence``: None, or ``(leading_s, trailing_s)`` (either may be
+        None) -- the clips' leading / trailing silence is normalised to exactly those durations on the device
+        (``corpus.normalize_silence``, the reference's matcha/utils/normalize_silence.py) after the conversion to 24 kHz and before
+        the mel front end."""
         from . import mel as M
         from .style import FINE_HOP
         if len(clips) == 0:
@@ -185,7 +188,7 @@ class MatchaTTSInfer(nn.Module):
             for c in vc:
                 flat.append(c)
                 group.append(g)
-        audio, lengths = _recordings_24k(flat, dev, sample_rate)
+        audio, lengths = recordings(flat, dev, sample_rate, silence=silence)
         n_feats = style_encoder.cfg["n_feats"]
         if n_feats != self.hp.n_feats or style_encoder.cfg["spk_emb_dim"] != self.hp.spk_emb_dim:
             raise ValueError("the style encoder's n_feats / spk_emb_dim do not match this model")
@@ -242,7 +245,7 @@ class MatchaTTSInfer(nn.Module):
 
     @torch.inference_mode()
     def align(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0, voice_mix=None,
-              speaker_embeddings=None, return_path=False, sample_rate=24000):
+              speaker_embeddings=None, return_path=False, silence=None, sample_rate=24000):
         """Forced alignment of text to a recording: per-token durations in fine frames (hop 128) by Monotonic Alignment Search of
         the text encoder's ``mu_x`` against the recording's normalised fine mel -- the alignment of the reference's training
         forward (matcha/models/matcha_tts.py:184-201), here for inference-time use: ``synthesise(durations=...)`` re-times or
@@ -251,7 +254,8 @@ class MatchaTTSInfer(nn.Module):
 
         The recording: ``audio`` -- mono clips, a list of 1-D waveforms (host or device) or a [B, L] tensor with
         ``audio_lengths``, at ``sample_rate`` (an int or one int per clip; anything but 24 kHz is converted on the device first,
-        ``resample.resample``) -- whose fine mel is extracted as ``enroll_voice`` does; or ``mel_fine`` [B, n_feats, Tm], already
+        ``resample.resample``; ``silence=(leading_s, trailing_s)`` normalises the clips' silence first, as for ``enroll_voice``) --
+        whose fine mel is extracted as ``enroll_voice`` does; or ``mel_fine`` [B, n_feats, Tm], already
         normalised with this model's mel statistics, with ``mel_fine_lengths`` (default: all Tm).  Speaker arguments as for
         ``synthesise``.  Returns ``durations`` (int32 [B, Tx]), ``predicted_durations`` (the predictor's raw
         ``(exp(logw) - 2) * mask``), ``scale_correction`` ([B]: aligned total / predicted total), ``score`` ([B]: the path's
@@ -260,7 +264,7 @@ class MatchaTTSInfer(nn.Module):
         rt = self._rt
         hip = rt.ready()
         out = self._align(x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path,
-                          sample_rate)
+                          sample_rate, silence)
         if rt.use_wide or hip.gemm_terms() not in (1, 2, 16, 17) or self.range_policy == "ignore":
             return out
         if not (hip.weights_saturate() or bool(hip.range_flags()[0].item())):       # (the stream is already drained: no second wait)
@@ -270,9 +274,9 @@ class MatchaTTSInfer(nn.Module):
                                      "arithmetic; set model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
         rt.use_wide = True                     # sticky, as in synthesise
         return self._align(x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path,
-                           sample_rate)
+                           sample_rate, silence)
 
-    def _fine_recording(self, x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="align", sample_rate=24000):
+    def _fine_recording(self, x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="align", sample_rate=24000, silence=None):
         """The recording of ``align`` / ``speaker_grad`` as ``(mel_fine [B, n_feats, Tm >= Tx], mel_fine_lengths)`` on the device: the
         fine mel of ``audio`` extracted as ``enroll_voice`` does, or the given normalised ``mel_fine``."""
         dev = x.device
@@ -286,7 +290,7 @@ class MatchaTTSInfer(nn.Module):
                 [audio] if torch.is_tensor(audio) or isinstance(audio, np.ndarray) else list(audio))
             if len(clips) != B:
                 raise ValueError(f"{who} needs one clip per utterance ({B}), got {len(clips)}")
-            wave, lengths = _recordings_24k(clips, dev, sample_rate, audio_lengths)
+            wave, lengths = recordings(clips, dev, sample_rate, audio_lengths, silence)
             mel_fine, mel_fine_lengths = M.extract(wave, lengths, FINE_HOP, self._rt.mel_mean, self._rt.mel_std, sample_rate=24000,
                                                    n_mels=self.hp.n_feats)
         else:
@@ -301,11 +305,11 @@ class MatchaTTSInfer(nn.Module):
         return mel_fine, mel_fine_lengths
 
     def _align(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path,
-               sample_rate=24000):
+               sample_rate=24000, silence=None):
         hip = self._rt.ready()
         dev = x.device
         B, Tx = x.shape
-        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, sample_rate=sample_rate)
+        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, sample_rate=sample_rate, silence=silence)
         if speaker_embeddings is not None:
             e_enc, e_dur = speaker_embeddings
         elif voice_mix is not None:
@@ -327,10 +331,10 @@ class MatchaTTSInfer(nn.Module):
 
     @torch.inference_mode()
     def speaker_grad(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0, voice_mix=None,
-                     speaker_embeddings=None, durations=None, sample_rate=24000):
+                     speaker_embeddings=None, durations=None, silence=None, sample_rate=24000):
         """Gradient of the training forward's prior and duration losses with respect to the two speaker rows, per utterance, on the
         device (``HipModel.speaker_grad``; include/mtts.h mtts_spk_grad): what the reference's matcha/finetune_speaker.py
-        back-propagates with everything but one row of each speaker table frozen.  The recording (and ``sample_rate``) as for ``align``; speaker arguments
+        back-propagates with everything but one row of each speaker table frozen.  The recording (and ``sample_rate``, ``silence``) as for ``align``; speaker arguments
         as for ``synthesise``; ``durations`` (int [B, Tx], fine frames) replaces the alignment search.
 
         Returns ``g_enc``, ``g_dur`` [B, spk_emb_dim] (gradients of the per-utterance sums ``prior_sum``, ``dur_sum`` [B]),
@@ -339,7 +343,7 @@ class MatchaTTSInfer(nn.Module):
         ``g_enc.sum(0) / mel_fine_lengths.sum()``.  One synchronisation per call; ``ValueError`` names a refused utterance."""
         rt = self._rt
         hip = rt.ready()
-        args = (x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, durations, sample_rate)
+        args = (x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, durations, sample_rate, silence)
         out = self._speaker_grad(*args)
         if rt.use_wide or hip.gemm_terms() not in (1, 2, 16, 17) or self.range_policy == "ignore":
             return out
@@ -353,11 +357,12 @@ class MatchaTTSInfer(nn.Module):
         return self._speaker_grad(*args)
 
     def _speaker_grad(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, durations,
-                      sample_rate=24000):
+                      sample_rate=24000, silence=None):
         hip = self._rt.ready()
         dev = x.device
         B, Tx = x.shape
-        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="speaker_grad", sample_rate=sample_rate)
+        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="speaker_grad", sample_rate=sample_rate,
+                                                          silence=silence)
         if speaker_embeddings is not None:
             e_enc, e_dur = speaker_embeddings
         elif voice_mix is not None:
@@ -380,13 +385,13 @@ class MatchaTTSInfer(nn.Module):
     @torch.inference_mode()
     def finetune_speaker(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0,
                          speaker_embeddings=None, steps=100, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, batch_size=None, shuffle_seed=0,
-                         sample_rate=24000):
+                         silence=None, sample_rate=24000):
         """Fine-tune one voice on its recordings: the reference's matcha/finetune_speaker.py (all parameters frozen but one row of
         ``speaker_embeddings_enc.weight`` and one of ``speaker_embeddings_dur.weight``, trained with the ordinary training loss) as
         ``steps`` device gradient calls and Adam updates of the two rows.
 
         ``x`` [N, Tx], ``x_lengths`` [N] and the recordings (``audio`` at ``sample_rate``, or ``mel_fine``, as for ``align``; converted to
-        24 kHz and to the fine mel once, before the loop) are the voice's utterances;
+        24 kHz, silence-normalised with ``silence=(leading_s, trailing_s)``, and turned into the fine mel once, before the loop) are the voice's utterances;
         the start is ``speaker`` (an id) or ``speaker_embeddings=(e_enc, e_dur)`` (e.g. of ``enroll_voice``).  Each step runs one
         ``speaker_grad`` over a batch (``batch_size`` utterances in the order of a ``shuffle_seed``-seeded permutation per epoch;
         None: all of them), every utterance with the current rows and a freshly searched alignment (as the reference's forward
@@ -406,7 +411,8 @@ class MatchaTTSInfer(nn.Module):
         N, Tx = x.shape
         if int(steps) < 1:
             raise ValueError("steps must be >= 1")
-        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="finetune_speaker", sample_rate=sample_rate)
+        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="finetune_speaker", sample_rate=sample_rate,
+                                                          silence=silence)
         x_lengths = x_lengths.to(device=dev, dtype=torch.long)
         if speaker_embeddings is not None:
             e_enc, e_dur = speaker_embeddings
@@ -450,7 +456,7 @@ class MatchaTTSInfer(nn.Module):
     @torch.inference_mode()
     def score(self, x, x_lengths, audio=None, audio_lengths=None, mel=None, mel_lengths=None, mel_fine=None, mel_fine_lengths=None,
               speaker=0, voice_mix=None, speaker_embeddings=None, t=None, noise=None, per_request_padding=False, return_frames=False,
-              sample_rate=24000):
+              silence=None, sample_rate=24000):
         """How well does this model, with this voice, explain this recording: the three numbers of the reference's training forward
         (``MatchaTTS.forward``, matcha/models/matcha_tts.py:64-164), forward pass only, on the device.
 
@@ -459,7 +465,7 @@ class MatchaTTSInfer(nn.Module):
         of ``BASECFM.compute_loss`` (flow_matching.py:65-107), one estimator evaluation at time ``t[b]`` per utterance.  The Huber
         thresholds are the checkpoint's (``hp.prior_loss_threshold``, ``hp.duration_loss_threshold``).
 
-        The recording: ``audio`` (and ``sample_rate``) as for ``align`` -- both mels are extracted (hop 256 and hop 128) and padded as the reference's
+        The recording: ``audio`` (and ``sample_rate``, ``silence``) as for ``align`` -- both mels are extracted (hop 256 and hop 128) and padded as the reference's
         collate pads them (matcha/data/text_mel_datamodule.py:481-499) -- or ``mel`` [B, n_feats, T] and ``mel_fine`` [B, n_feats,
         Tm], normalised with this model's mel statistics, with their lengths (default: the whole tensors).  Speaker arguments as
         for ``synthesise``.  ``t``: [B] (default ``torch.rand``) or a grid [K, B] -- K evaluations with the same ``noise``
@@ -474,7 +480,7 @@ class MatchaTTSInfer(nn.Module):
         rt = self._rt
         hip = rt.ready()
         dev = x.device
-        rec = self._score_recording(x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths, sample_rate)
+        rec = self._score_recording(x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths, sample_rate, silence)
         B, nf, T = rec[0].shape
         if noise is None:
             noise = torch.randn(B, nf, T, dtype=torch.float32, device=dev)
@@ -499,7 +505,7 @@ class MatchaTTSInfer(nn.Module):
         out.pop("_flags", None)
         return out
 
-    def _score_recording(self, x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths, sample_rate=24000):
+    def _score_recording(self, x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths, sample_rate=24000, silence=None):
         """(mel [B, nf, T], mel_lengths, mel_fine [B, nf, Tm], mel_fine_lengths, host coarse lengths or None) padded like the
         reference's collate: T = fix_len_compatibility(longest coarse mel), Tm = 2 T (more only if a given tensor is longer or
         there are more tokens than that)."""
@@ -516,7 +522,7 @@ class MatchaTTSInfer(nn.Module):
                 [audio] if torch.is_tensor(audio) or isinstance(audio, np.ndarray) else list(audio))
             if len(clips) != B:
                 raise ValueError(f"score needs one clip per utterance ({B}), got {len(clips)}")
-            wave, lengths = _recordings_24k(clips, dev, sample_rate, audio_lengths)
+            wave, lengths = recordings(clips, dev, sample_rate, audio_lengths, silence)
             kw = dict(sample_rate=24000, n_mels=nf)
             mel_fine, mel_fine_lengths = M.extract(wave, lengths, FINE_HOP, self._rt.mel_mean, self._rt.mel_std, **kw)
             mel, mel_lengths = M.extract(wave, lengths, STD_RES_HOP_LENGTH, self._rt.mel_mean, self._rt.mel_std, **kw)
@@ -699,6 +705,28 @@ def _recordings_24k(clips, dev, sample_rate=24000, lengths=None):
         for i, b in enumerate(rows):
             wave[b, :keep[i]].copy_(out[i, :keep[i]])
     return wave, lengths
+
+
+def _silence_normalised(wave, lengths, silence):
+    """``silence=`` of the recording entries: None returns the arguments (nothing is launched); ``(leading_s, trailing_s)`` (either
+    may be None) rebuilds every 24 kHz row of ``_recordings_24k`` with exactly that much silence around its content
+    (``corpus.normalize_silence``) and reads the new lengths, which the mel front end needs on the host."""
+    if silence is None:
+        return wave, lengths
+    from . import corpus as CP
+    if len(silence) != 2:
+        raise ValueError("silence is None or (leading seconds or None, trailing seconds or None)")
+    out, out_len, _ = CP.normalize_silence(wave, lengths, silence[0], silence[1], sample_rate=SAMPLE_RATE)   # (ValueError names a refused row)
+    return out, [int(v) for v in out_len.tolist()]
+
+
+def recordings(clips, dev, sample_rate=24000, lengths=None, silence=None):
+    """What the recording entries (``enroll_voice``, ``align``, ``score``, ``speaker_grad``, ``finetune_speaker``) make of their clips
+    before the mel front end: ``(wave [B, ld] fp32 on ``dev`` at 24 kHz, lengths: list of B ints)``.  ``clips``: 1-D waveforms (host
+    or device) at ``sample_rate`` (an int or one per clip; converted on the device), ``lengths``: samples to use of each;
+    ``silence``: None or ``(leading_s, trailing_s)``, normalised after the conversion (``corpus.normalize_silence``).  For a
+    caller that needs the lengths ahead of the call, e.g. to size ``score``'s noise."""
+    return _silence_normalised(*_recordings_24k(clips, dev, sample_rate, lengths), silence)
 
 
 def _plain(obj):

@@ -135,6 +135,8 @@ def main() -> int:
     ap.add_argument("--ids-file", help="one line of phoneme ids per clip")
     ap.add_argument("--speaker", type=int, default=0)
     ap.add_argument("--out", default="align.npz")
+    from enroll import add_silence_argument, silence_of
+    add_silence_argument(ap)
     ap.add_argument("--synthetic", type=int, default=0, help="N synthetic utterances on random weights instead of files")
     ap.add_argument("--tokens", type=int, default=128)
     ap.add_argument("--frames", type=int, default=1500)
@@ -156,7 +158,7 @@ def main() -> int:
     for b, r in enumerate(ids):
         x[b, :len(r)] = torch.tensor(r)
     x_len = torch.tensor([len(r) for r in ids])
-    out = model.align(x.to(dev), x_len.to(dev), audio=clips, speaker=args.speaker, sample_rate=rates)
+    out = model.align(x.to(dev), x_len.to(dev), audio=clips, speaker=args.speaker, silence=silence_of(args), sample_rate=rates)
     host = {k: v.cpu().numpy() for k, v in out.items()}
     for b, path in enumerate(args.wavs):
         n = len(ids[b])

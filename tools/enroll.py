@@ -3,6 +3,7 @@
 
     python tools/enroll.py --matcha CKPT --style-encoder CKPT_OR_DIR --out voice.npz clip1.wav clip2.wav ...
     python tools/enroll.py --synthetic 10          # ten synthetic 5 s clips on random weights (profiling / smoke, no files needed)
+    python tools/enroll.py ... --silence 0.2 0.8   # first give every clip exactly 0.2 s / 0.8 s of leading / trailing silence
 
 Clips are PCM wav (8 / 16 / 32 bit) at any sample rate, read with the standard library's ``wave`` module; of a multi-channel file
 channel 0 is used (the reference's ``audio[0]``), and clips that are not at 24 kHz are converted on the device.  The output .npz
@@ -44,6 +45,19 @@ def read_wavs(paths):
     return [c for c, _ in pairs], [r for _, r in pairs]
 
 
+def add_silence_argument(ap) -> None:
+    ap.add_argument("--silence", nargs=2, metavar=("LEAD", "TRAIL"),
+                    help="normalise every clip's leading / trailing silence to exactly these seconds (multiples of 0.01; 'none' leaves "
+                         "that end as it is) on the device before the mel front end, as the reference's normalize_silence.py does to its corpus")
+
+
+def silence_of(args):
+    """``--silence LEAD TRAIL`` as the ``silence=`` argument of the model's methods (None without the option)."""
+    if not args.silence:
+        return None
+    return tuple(None if v.lower() == "none" else float(v) for v in args.silence)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("wavs", nargs="*")
@@ -52,6 +66,7 @@ def main() -> int:
     ap.add_argument("--out", default="voice.npz")
     ap.add_argument("--synthetic", type=int, default=0, help="N synthetic 5 s clips on random weights instead of files")
     ap.add_argument("--repeat", type=int, default=1, help="run the enrolment this many times (profiling)")
+    add_silence_argument(ap)
     args = ap.parse_args()
     inf = importlib.import_module(PKG + ".inference")
     style = importlib.import_module(PKG + ".style")
@@ -73,7 +88,7 @@ def main() -> int:
         enc = style.load_style_encoder(args.style_encoder)
         clips, rates = read_wavs(args.wavs)
     for _ in range(max(args.repeat, 1)):
-        e_enc, e_dur = model.enroll_voice(clips, enc, sample_rate=rates)
+        e_enc, e_dur = model.enroll_voice(clips, enc, silence=silence_of(args), sample_rate=rates)
     torch.cuda.synchronize()
     np.savez(args.out, e_enc=e_enc[0].cpu().numpy(), e_dur=e_dur[0].cpu().numpy())
     print(f"[enroll] {len(clips)} clips -> {args.out}: e_enc |max| {e_enc.abs().max().item():.4f}, e_dur |max| {e_dur.abs().max().item():.4f}")

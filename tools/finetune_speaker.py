@@ -39,6 +39,8 @@ def main() -> int:
     ap.add_argument("--seed", type=int, default=0, help="seed of the batch order")
     ap.add_argument("--print-every", type=int, default=10)
     ap.add_argument("--out", default="voice_ft", help="prefix of the two .npy files")
+    from enroll import add_silence_argument, silence_of
+    add_silence_argument(ap)
     args = ap.parse_args()
     if bool(args.matcha) == bool(args.synthetic_model):
         ap.error("give either --matcha or --synthetic-model")
@@ -67,7 +69,7 @@ def main() -> int:
         x[b, :len(r)] = torch.tensor(r)
     x_len = torch.tensor([len(r) for r in ids])
     e_enc, e_dur, history = model.finetune_speaker(x.to(dev), x_len.to(dev), audio=clips, steps=args.steps, lr=args.lr,
-                                                   batch_size=args.batch_size or None, shuffle_seed=args.seed, sample_rate=rates, **start)
+                                                   batch_size=args.batch_size or None, shuffle_seed=args.seed, silence=silence_of(args), sample_rate=rates, **start)
     print(f"{'step':>6s} {'dur_loss':>10s} {'prior_loss':>11s}")
     every = max(args.print_every, 1)
     for k, (d, p) in enumerate(zip(history["dur_loss"], history["prior_loss"])):

@@ -78,6 +78,8 @@ def main() -> int:
     ap.add_argument("--t-grid", type=int, default=8, help="flow-matching times per file")
     ap.add_argument("--seed", type=int, default=0, help="seed of the one noise draw")
     ap.add_argument("--out", default="score.npz")
+    from enroll import add_silence_argument, silence_of
+    add_silence_argument(ap)
     ap.add_argument("--synthetic", type=int, default=0, help="N synthetic utterances on random weights instead of files")
     ap.add_argument("--tokens", type=int, default=128)
     ap.add_argument("--repeat", type=int, default=1, help="time the call this many times (synthetic mode)")
@@ -101,8 +103,13 @@ def main() -> int:
     if args.enroll:
         style = importlib.import_module(PKG + ".style")
         enrol_clips, enrol_rates = read_wavs(args.enroll)
-        voice = {"speaker_embeddings": model.enroll_voice(enrol_clips, style.load_style_encoder(args.style_encoder), sample_rate=enrol_rates)}
+        voice = {"speaker_embeddings": model.enroll_voice(enrol_clips, style.load_style_encoder(args.style_encoder), silence=silence_of(args),
+                                                                 sample_rate=enrol_rates)}
     clips, rates = read_wavs(args.wavs)
+    silence = silence_of(args)
+    if silence is not None:                    # here, not as score(silence=...): the noise below is drawn for the normalised lengths
+        wave, kept = inf.recordings(clips, dev, rates, silence=silence)
+        clips, rates = [wave[b, :n] for b, n in enumerate(kept)], [24000] * len(kept)
     B = len(ids)
     x = torch.zeros(B, max(len(r) for r in ids), dtype=torch.long)
     for b, r in enumerate(ids):
