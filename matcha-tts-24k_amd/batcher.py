@@ -495,8 +495,8 @@ class StepBatcher:
 
     def _note_flags(self, hip, kind: str) -> None:
         """OR this stream's latest call's header words into the batcher's sticky copy (a call clears its own flag when it begins); no
-        synchronisation.  Nothing to note on the arithmetics that cannot saturate or under ``range_policy = 'ignore'``."""
-        if not self._guarded(hip):
+        synchronisation.  Nothing to note where the model's range guard has nothing to read (``Runtime.guards``)."""
+        if not self._guarded():
             return
         w = hip.call_flags(kind)
         if w is None:
@@ -506,9 +506,8 @@ class StepBatcher:
         dst = self._flags[0:1] if kind == "enc" else self._flags[1:3]
         torch.maximum(dst, w[0:1] if kind == "enc" else w[0:2], out=dst)
 
-    def _guarded(self, hip) -> bool:
-        rt = self.model._rt
-        return not rt.use_wide and hip.gemm_terms() in (1, 2, 16, 17) and self.model.range_policy != "ignore"
+    def _guarded(self) -> bool:
+        return self.model._rt.guards(self.model.range_policy)
 
     # ------------------------------------------------------------------ leaving
     def _finish(self, finished: List[StepEntry]) -> None:
@@ -517,19 +516,18 @@ class StepBatcher:
             for e in finished:
                 e.request.future.set_result({"mel": None, "mel_length": e.y_len})
             return
+        from .modules import PAIR_TIMEOUT_ERROR, RANGE_ERROR
         model, rt = self.model, self.model._rt
         hip = rt.ready()
-        if self._guarded(hip) and self._flags is not None:
+        if self._guarded() and self._flags is not None:
             flags = self._flags.tolist()                         # the iteration's one synchronisation
             self._flags.zero_()
             if flags[2]:
-                raise RuntimeError("matcha-tts-24k_amd: a pair-form chain launch timed out waiting for its partner workgroup (another "
-                                   "kernel held CUs during the launch?); set MTTS_CHAIN_PAIR=0")
+                raise RuntimeError(PAIR_TIMEOUT_ERROR)
             if flags[0] or flags[1] or hip.weights_saturate():
                 if model.range_policy == "raise":
-                    raise FloatingPointError("matcha-tts-24k_amd: an operand left the fp16 range (|x| > 65504) in the default split "
-                                             "arithmetic; set model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
-                # rerun: the model switches to the wide arithmetic (sticky, as synthesise) and everybody who is active starts over
+                    raise FloatingPointError(RANGE_ERROR)
+                # rerun: the model switches to the wide arithmetic (sticky, as Runtime.guarded) and everybody who is active starts over
                 rt.use_wide = True
                 again = [e.request for e in self._active]
                 self._leave(list(self._active))

@@ -20,7 +20,7 @@ import torch
 import torch.nn as nn
 
 from .hparams import N_VOCAB, PathHParams, from_reference_kwargs
-from .modules import Runtime, build_trees
+from .modules import PAIR_TIMEOUT_ERROR, Runtime, build_trees
 
 # Voice table of the shipped model: id, language, per-speaker duration scale correction (reference inference.py:16-32).
 VOICES = [
@@ -101,41 +101,41 @@ class MatchaTTSInfer(nn.Module):
             mixed_dur = weight * e_dur if mixed_dur is None else mixed_dur + weight * e_dur
         return mixed_enc, mixed_dur
 
+    def _voice_rows(self, B, dev, speaker=0, voice_mix=None, speaker_embeddings=None):
+        """The ``(e_enc, e_dur)`` rows of a call's speaker arguments: ``speaker_embeddings`` as given, else the ``voice_mix``, else the
+        rows of the ``speaker`` id(s); one row for the batch or one per utterance."""
+        if speaker_embeddings is not None:      # (e_enc, e_dur) [B, spk_emb_dim] each: a batch that mixes plain voices and voice mixes
+            e_enc, e_dur = speaker_embeddings
+        elif voice_mix is not None:
+            e_enc, e_dur = self.mix_speakers(voice_mix)
+        else:
+            hip = self._rt.ready()
+            ids = torch.as_tensor(speaker, dtype=torch.long, device=dev).reshape(-1)
+            e_enc, e_dur = hip.speaker_embedding(0, ids), hip.speaker_embedding(1, ids)
+        if e_enc.shape[0] not in (1, B):
+            raise ValueError("speaker must be an int or a LongTensor with one id per utterance")
+        return e_enc, e_dur
+
     #: what to do when the default arithmetic (fp16 two-term split) met an operand beyond +-65504 (include/mtts.h "range
-    #: guard"): "rerun" the call on the full-range arithmetic (three bf16 terms), "raise", or "ignore" (no flag read, no sync)
+    #: guard"): "rerun" the call on the full-range arithmetic (three bf16 terms), "raise", or "ignore" (no flag read, no sync).
+    #: ``Runtime.guarded`` (modules.py) is the one guard of ``synthesise``, ``align``, ``score`` and ``speaker_grad``
     range_policy = "rerun"
 
     def synthesise(self, x, x_lengths, n_timesteps, speaker=0, voice_mix=None, scale_correction=1.0, length_scale=1.0,
                    debug=False, z=None, sync_max=None, per_request_padding=False, speaker_embeddings=None, durations=None):
-        """``_synthesise`` + the range guard: one read of the sticky device flag per call (a stream synchronisation)."""
-        args = (x, x_lengths, n_timesteps, speaker, voice_mix, scale_correction, length_scale, debug, z, sync_max, per_request_padding,
-                speaker_embeddings, durations)
+        """``_synthesise`` under the range guard (``Runtime.guarded``): one read of the sticky device flags per call (a stream
+        synchronisation)."""
         rt = self._rt
-        if rt.use_wide:                       # a previous call or the weights already needed the wide arithmetic
-            return self._synthesise(*args)
-        hip = rt.ready()
-        if hip.gemm_terms() not in (1, 2, 16, 17) or self.range_policy == "ignore":     # only the fp16-based arithmetics saturate (17: the text encoder's)
-            return self._synthesise(*args)
-        saturated = hip.weights_saturate()
-        out = None
-        if not saturated:
-            out = self._synthesise(*args)
+
+        def verdict(_):
+            hip = rt.ready()
             flags = torch.cat([hip.range_flags(), hip.pair_timeouts()]).tolist()       # one read, one synchronisation
-            if flags[2]:
-                raise RuntimeError("matcha-tts-24k_amd: a pair-form chain launch timed out waiting for its partner workgroup (another "
-                                   "kernel held CUs during the launch?); set MTTS_CHAIN_PAIR=0")
-            saturated = bool(flags[0] or flags[1])
-        if not saturated:
-            return out
-        if self.range_policy == "raise" or sync_max is not None:     # (a rank-local rerun would repeat sync_max's collective)
-            raise FloatingPointError("matcha-tts-24k_amd: an operand left the fp16 range (|x| > 65504) in the default split "
-                                     "arithmetic; set model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
-        if not getattr(self, "_range_warned", False):
-            print("[matcha-tts-24k_amd] an operand left the fp16 range of the default arithmetic: this model now runs on "
-                  "three-term bf16 products (full fp32 range)")
-            object.__setattr__(self, "_range_warned", True)
-        rt.use_wide = True                     # sticky: a checkpoint that overflows once will do so again
-        return self._synthesise(*args)
+            return bool(flags[0] or flags[1]), bool(flags[2])
+
+        def run():
+            return self._synthesise(x, x_lengths, n_timesteps, speaker, voice_mix, scale_correction, length_scale, debug, z, sync_max,
+                                    per_request_padding, speaker_embeddings, durations)
+        return rt.guarded(self.range_policy, run, verdict, can_rerun=sync_max is None)      # (a rank-local rerun would repeat sync_max's collective)
 
     @torch.inference_mode()
     def speaker_rows(self, voices):
@@ -260,74 +260,65 @@ class MatchaTTSInfer(nn.Module):
         ``synthesise``.  Returns ``durations`` (int32 [B, Tx]), ``predicted_durations`` (the predictor's raw
         ``(exp(logw) - 2) * mask``), ``scale_correction`` ([B]: aligned total / predicted total), ``score`` ([B]: the path's
         log-prior sum), ``mel_fine_lengths`` and, with ``return_path``, ``path`` ([B, Tx, Tm] 0/1).  One synchronisation per call
-        (the lengths' verdict and the range flag); ``ValueError`` names an utterance with fewer frames than tokens."""
+        (the lengths' verdict and the range flag, under the guard of ``Runtime.guarded``); ``ValueError`` names an utterance with
+        fewer frames than tokens."""
         rt = self._rt
-        hip = rt.ready()
-        out = self._align(x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path,
-                          sample_rate, silence)
-        if rt.use_wide or hip.gemm_terms() not in (1, 2, 16, 17) or self.range_policy == "ignore":
-            return out
-        if not (hip.weights_saturate() or bool(hip.range_flags()[0].item())):       # (the stream is already drained: no second wait)
-            return out
-        if self.range_policy == "raise":
-            raise FloatingPointError("matcha-tts-24k_amd: an operand left the fp16 range (|x| > 65504) in the default split "
-                                     "arithmetic; set model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
-        rt.use_wide = True                     # sticky, as in synthesise
-        return self._align(x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path,
-                           sample_rate, silence)
 
-    def _fine_recording(self, x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="align", sample_rate=24000, silence=None):
+        def run():
+            hip = rt.ready()
+            y, y_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, "align", sample_rate, silence)
+            e_enc, e_dur = self._voice_rows(x.shape[0], x.device, speaker, voice_mix, speaker_embeddings)
+            mu_x, logw, x_mask = self.encoder(x, x_lengths, e_enc, e_dur)
+            durations, score, path = hip.mas(x_lengths, y_lengths, mu_x=mu_x, y=y, return_path=return_path)
+            predicted = ((torch.exp(logw) - 2) * x_mask).squeeze(1)
+            out = {"durations": durations, "predicted_durations": predicted,
+                   "scale_correction": durations.sum(1).to(torch.float32) / predicted.sum(1), "score": score,
+                   "mel_fine_lengths": y_lengths}
+            if return_path:
+                out["path"] = path
+            return out
+        # (no estimator call, so no time-out word; the stream is already drained: no second wait)
+        return rt.guarded(self.range_policy, run, lambda _: (bool(rt.ready().range_flags()[0].item()), False))
+
+    @staticmethod
+    def _clips(audio, B, who):
+        """The ``audio`` argument of the recording entries as a list of ``B`` clips: a [B, L] tensor's rows, one 1-D waveform, or a list."""
+        clips = [audio[b] for b in range(audio.shape[0])] if torch.is_tensor(audio) and audio.dim() == 2 else (
+            [audio] if torch.is_tensor(audio) or isinstance(audio, np.ndarray) else list(audio))
+        if len(clips) != B:
+            raise ValueError(f"{who} needs one clip per utterance ({B}), got {len(clips)}")
+        return clips
+
+    def _recorded_mels(self, x, audio, audio_lengths, who, sample_rate, silence, *hops):
+        """The normalised mel of ``audio`` (one clip per row of ``x``) at each of ``hops``, extracted as ``enroll_voice`` does from
+        one conversion to 24 kHz: ``([(mel, mel_lengths), ...], the clips' sample counts)``."""
+        from . import mel as M
+        wave, lengths = recordings(self._clips(audio, x.shape[0], who), x.device, sample_rate, audio_lengths, silence)
+        return [M.extract(wave, lengths, hop, self._rt.mel_mean, self._rt.mel_std, sample_rate=24000, n_mels=self.hp.n_feats)
+                for hop in hops], lengths
+
+    def _mel_arg(self, name, frames, m, lengths, B, dev):
+        """A normalised mel [B, n_feats, ``frames``] as fp32 on the device, and its lengths (default: the whole tensor) as a long tensor
+        there."""
+        if m.dim() != 3 or m.shape[0] != B or m.shape[1] != self.hp.n_feats:
+            raise ValueError(f"{name} must be [{B}, {self.hp.n_feats}, {frames}], got {tuple(m.shape)}")
+        if lengths is None:
+            lengths = torch.full((B,), m.shape[2], dtype=torch.long, device=dev)
+        return m.to(dev, torch.float32), torch.as_tensor(lengths).to(device=dev, dtype=torch.long)
+
+    def _fine_recording(self, x, audio, audio_lengths, mel_fine, mel_fine_lengths, who, sample_rate=24000, silence=None):
         """The recording of ``align`` / ``speaker_grad`` as ``(mel_fine [B, n_feats, Tm >= Tx], mel_fine_lengths)`` on the device: the
         fine mel of ``audio`` extracted as ``enroll_voice`` does, or the given normalised ``mel_fine``."""
-        dev = x.device
         B, Tx = x.shape
         if (audio is None) == (mel_fine is None):
             raise ValueError(f"{who} needs either audio= or mel_fine=")
         if mel_fine is None:
-            from . import mel as M
             from .style import FINE_HOP
-            clips = [audio[b] for b in range(audio.shape[0])] if torch.is_tensor(audio) and audio.dim() == 2 else (
-                [audio] if torch.is_tensor(audio) or isinstance(audio, np.ndarray) else list(audio))
-            if len(clips) != B:
-                raise ValueError(f"{who} needs one clip per utterance ({B}), got {len(clips)}")
-            wave, lengths = recordings(clips, dev, sample_rate, audio_lengths, silence)
-            mel_fine, mel_fine_lengths = M.extract(wave, lengths, FINE_HOP, self._rt.mel_mean, self._rt.mel_std, sample_rate=24000,
-                                                   n_mels=self.hp.n_feats)
-        else:
-            if mel_fine.dim() != 3 or mel_fine.shape[0] != B or mel_fine.shape[1] != self.hp.n_feats:
-                raise ValueError(f"mel_fine must be [{B}, {self.hp.n_feats}, Tm], got {tuple(mel_fine.shape)}")
-            mel_fine = mel_fine.to(dev)
-            if mel_fine_lengths is None:
-                mel_fine_lengths = torch.full((B,), mel_fine.shape[2], dtype=torch.long, device=dev)
-        mel_fine_lengths = torch.as_tensor(mel_fine_lengths).to(device=dev, dtype=torch.long)
+            ((mel_fine, mel_fine_lengths),), _ = self._recorded_mels(x, audio, audio_lengths, who, sample_rate, silence, FINE_HOP)
+        mel_fine, mel_fine_lengths = self._mel_arg("mel_fine", "Tm", mel_fine, mel_fine_lengths, B, x.device)
         if mel_fine.shape[2] < Tx:              # (the padded shapes: the device checks each utterance's own lengths)
             mel_fine = torch.nn.functional.pad(mel_fine, (0, Tx - mel_fine.shape[2]))
         return mel_fine, mel_fine_lengths
-
-    def _align(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, return_path,
-               sample_rate=24000, silence=None):
-        hip = self._rt.ready()
-        dev = x.device
-        B, Tx = x.shape
-        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, sample_rate=sample_rate, silence=silence)
-        if speaker_embeddings is not None:
-            e_enc, e_dur = speaker_embeddings
-        elif voice_mix is not None:
-            e_enc, e_dur = self.mix_speakers(voice_mix)
-        else:
-            ids = torch.as_tensor(speaker, dtype=torch.long, device=dev).reshape(-1)
-            e_enc, e_dur = hip.speaker_embedding(0, ids), hip.speaker_embedding(1, ids)
-        if e_enc.shape[0] not in (1, B):
-            raise ValueError("speaker must be an int or a LongTensor with one id per utterance")
-        mu_x, logw, x_mask = self.encoder(x, x_lengths, e_enc, e_dur)
-        durations, score, path = hip.mas(x_lengths, mel_fine_lengths, mu_x=mu_x, y=mel_fine, return_path=return_path)
-        predicted = ((torch.exp(logw) - 2) * x_mask).squeeze(1)
-        out = {"durations": durations, "predicted_durations": predicted,
-               "scale_correction": durations.sum(1).to(torch.float32) / predicted.sum(1), "score": score,
-               "mel_fine_lengths": mel_fine_lengths}
-        if return_path:
-            out["path"] = path
-        return out
 
     @torch.inference_mode()
     def speaker_grad(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0, voice_mix=None,
@@ -340,47 +331,28 @@ class MatchaTTSInfer(nn.Module):
         Returns ``g_enc``, ``g_dur`` [B, spk_emb_dim] (gradients of the per-utterance sums ``prior_sum``, ``dur_sum`` [B]),
         ``durations`` (int32 [B, Tx]), ``mel_fine_lengths`` and the two batch losses ``dur_loss``, ``prior_loss`` as ``score``
         reports them.  The gradients of those batch losses are ``g_dur.sum(0) / x_lengths.sum()`` and
-        ``g_enc.sum(0) / mel_fine_lengths.sum()``.  One synchronisation per call; ``ValueError`` names a refused utterance."""
+        ``g_enc.sum(0) / mel_fine_lengths.sum()``.  One synchronisation per call (under the guard of ``Runtime.guarded``);
+        ``ValueError`` names a refused utterance."""
         rt = self._rt
-        hip = rt.ready()
-        args = (x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, durations, sample_rate, silence)
-        out = self._speaker_grad(*args)
-        if rt.use_wide or hip.gemm_terms() not in (1, 2, 16, 17) or self.range_policy == "ignore":
-            return out
-        flag = hip.call_flags("spk_grad")
-        if not (hip.weights_saturate() or bool(flag[0].item())):       # (the stream is already drained: no second wait)
-            return out
-        if self.range_policy == "raise":
-            raise FloatingPointError("matcha-tts-24k_amd: an operand left the fp16 range (|x| > 65504) in the default split "
-                                     "arithmetic; set model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
-        rt.use_wide = True                     # sticky, as in synthesise
-        return self._speaker_grad(*args)
-
-    def _speaker_grad(self, x, x_lengths, audio, audio_lengths, mel_fine, mel_fine_lengths, speaker, voice_mix, speaker_embeddings, durations,
-                      sample_rate=24000, silence=None):
-        hip = self._rt.ready()
         dev = x.device
-        B, Tx = x.shape
-        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="speaker_grad", sample_rate=sample_rate,
-                                                          silence=silence)
-        if speaker_embeddings is not None:
-            e_enc, e_dur = speaker_embeddings
-        elif voice_mix is not None:
-            e_enc, e_dur = self.mix_speakers(voice_mix)
-        else:
-            ids = torch.as_tensor(speaker, dtype=torch.long, device=dev).reshape(-1)
-            e_enc, e_dur = hip.speaker_embedding(0, ids), hip.speaker_embedding(1, ids)
-        e_enc, e_dur = e_enc.to(dev).reshape(-1, self.hp.spk_emb_dim), e_dur.to(dev).reshape(-1, self.hp.spk_emb_dim)
-        if e_enc.shape[0] not in (1, B):
-            raise ValueError("speaker must be an int or a LongTensor with one id per utterance")
-        x_lengths = x_lengths.to(device=dev, dtype=torch.long)
         hp = self.hp
-        out = hip.speaker_grad(x, x_lengths, e_enc, e_dur, mel_fine.to(torch.float32).contiguous(), mel_fine_lengths, hp.prior_loss_threshold,
-                               hp.duration_loss_threshold, durations=durations)
-        out["mel_fine_lengths"] = mel_fine_lengths
-        out["dur_loss"] = out["dur_sum"].sum() / x_lengths.to(torch.float32).sum()
-        out["prior_loss"] = out["prior_sum"].sum() / mel_fine_lengths.to(torch.float32).sum()
-        return out
+
+        def run():
+            hip = rt.ready()
+            y, y_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, "speaker_grad", sample_rate, silence)
+            rows = speaker_embeddings       # (given rows may come flat: shaped before the count is checked)
+            if rows is not None:
+                rows = tuple(e.to(dev).reshape(-1, hp.spk_emb_dim) for e in rows)
+            e_enc, e_dur = self._voice_rows(x.shape[0], dev, speaker, voice_mix, rows)
+            x_len = x_lengths.to(device=dev, dtype=torch.long)
+            out = hip.speaker_grad(x, x_len, e_enc, e_dur, y.contiguous(), y_lengths, hp.prior_loss_threshold, hp.duration_loss_threshold,
+                                   durations=durations)
+            out["mel_fine_lengths"] = y_lengths
+            out["dur_loss"] = out["dur_sum"].sum() / x_len.to(torch.float32).sum()
+            out["prior_loss"] = out["prior_sum"].sum() / y_lengths.to(torch.float32).sum()
+            return out
+        # (the stream is already drained: no second wait)
+        return rt.guarded(self.range_policy, run, lambda _: (bool(rt.ready().call_flags("spk_grad")[0].item()), False))
 
     @torch.inference_mode()
     def finetune_speaker(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0,
@@ -406,21 +378,17 @@ class MatchaTTSInfer(nn.Module):
         Two deviations from the reference.  It fine-tunes in train mode with dropout active; this is the dropout-free (eval)
         gradient, deterministic.  The flow-matching loss is not evaluated: it cannot move the rows, because ``mu_y`` is detached
         before ``decoder.compute_loss`` (matcha_tts.py:154-162) and the estimator has no speaker input."""
-        hip = self._rt.ready()
+        self._rt.ready()                                   # mel statistics come from the loaded checkpoint's buffers
         dev = x.device
         N, Tx = x.shape
         if int(steps) < 1:
             raise ValueError("steps must be >= 1")
-        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, who="finetune_speaker", sample_rate=sample_rate,
-                                                          silence=silence)
+        mel_fine, mel_fine_lengths = self._fine_recording(x, audio, audio_lengths, mel_fine, mel_fine_lengths, "finetune_speaker", sample_rate, silence)
         x_lengths = x_lengths.to(device=dev, dtype=torch.long)
         if speaker_embeddings is not None:
-            e_enc, e_dur = speaker_embeddings
-        else:
-            ids = torch.tensor([int(speaker)], device=dev, dtype=torch.long)
-            e_enc, e_dur = hip.speaker_embedding(0, ids), hip.speaker_embedding(1, ids)
+            speaker_embeddings = [torch.as_tensor(r).reshape(1, -1) for r in speaker_embeddings]
         E = self.hp.spk_emb_dim
-        rows = [torch.as_tensor(r).detach().to(device=dev, dtype=torch.float32).reshape(1, -1).clone() for r in (e_enc, e_dur)]
+        rows = [r.detach().to(device=dev, dtype=torch.float32).clone() for r in self._voice_rows(1, dev, int(speaker), None, speaker_embeddings)]
         if any(r.shape[1] != E for r in rows):
             raise ValueError(f"a speaker row has {E} values")
         m = [torch.zeros_like(r) for r in rows]
@@ -476,9 +444,10 @@ class MatchaTTSInfer(nn.Module):
         ``/ sum(y_fine_mask)``, ``/ (sum(y_mask) * n_feats)``; ``diff_loss`` is [K] for a grid), the same three ``*_per_utterance``
         ([B]; [K, B]), the raw sums ``dur_sum``, ``prior_sum``, ``sq_sum``, ``durations`` (int32 [B, Tx]), ``mas_score`` [B],
         ``mel_lengths``, ``mel_fine_lengths`` and, with ``return_frames``, ``prior_frame`` [B, Tm] and ``dur_err`` [B, Tx].  One
-        synchronisation per call; ``ValueError`` names an utterance with fewer frames than tokens."""
+        synchronisation per call (under the guard of ``Runtime.guarded``); ``ValueError`` names an utterance with fewer frames
+        than tokens."""
         rt = self._rt
-        hip = rt.ready()
+        rt.ready()                                         # mel statistics come from the loaded checkpoint's buffers
         dev = x.device
         rec = self._score_recording(x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths, sample_rate, silence)
         B, nf, T = rec[0].shape
@@ -486,23 +455,15 @@ class MatchaTTSInfer(nn.Module):
             noise = torch.randn(B, nf, T, dtype=torch.float32, device=dev)
         elif tuple(noise.shape) != (B, nf, T):
             raise ValueError(f"noise must be [{B}, {nf}, {T}] (the padded coarse mel), got {tuple(noise.shape)}")
+        noise = noise.to(dev)
         t = torch.rand(B, device=dev) if t is None else torch.as_tensor(t, dtype=torch.float32).to(dev)
         if t.dim() not in (1, 2) or t.shape[-1] != B:
             raise ValueError(f"t must be [{B}] or [K, {B}], got {tuple(t.shape)}")
-        args = (x, x_lengths, rec, speaker, voice_mix, speaker_embeddings, t, noise.to(dev), per_request_padding, return_frames)
-        was_wide = rt.use_wide
-        out = self._score(*args)
-        flags = out.pop("_flags")              # (host copy: the stream is already drained, no second wait)
-        if was_wide or hip.gemm_terms() not in (1, 2, 16, 17) or self.range_policy == "ignore":
-            return out
-        if not (hip.weights_saturate() or bool(flags[:2].any())):
-            return out
-        if self.range_policy == "raise":
-            raise FloatingPointError("matcha-tts-24k_amd: an operand left the fp16 range (|x| > 65504) in the default split "
-                                     "arithmetic; set model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
-        rt.use_wide = True                     # sticky, as in synthesise
-        out = self._score(*args)
-        out.pop("_flags", None)
+
+        def run():
+            return self._score(x, x_lengths, rec, speaker, voice_mix, speaker_embeddings, t, noise, per_request_padding, return_frames)
+        # the flags that _score read with its own wait (host copy: no second wait); it raises the time-out itself, under every policy
+        out, _ = rt.guarded(self.range_policy, run, lambda r: (bool(r[1][:2].any()), False))
         return out
 
     def _score_recording(self, x, audio, audio_lengths, mel, mel_lengths, mel_fine, mel_fine_lengths, sample_rate=24000, silence=None):
@@ -511,34 +472,18 @@ class MatchaTTSInfer(nn.Module):
         there are more tokens than that)."""
         dev = x.device
         B, Tx = x.shape
-        nf = self.hp.n_feats
         host_len = None
         if audio is not None:
             if mel is not None or mel_fine is not None:
                 raise ValueError("score needs either audio= or mel= and mel_fine=")
-            from . import mel as M
             from .style import FINE_HOP
-            clips = [audio[b] for b in range(audio.shape[0])] if torch.is_tensor(audio) and audio.dim() == 2 else (
-                [audio] if torch.is_tensor(audio) or isinstance(audio, np.ndarray) else list(audio))
-            if len(clips) != B:
-                raise ValueError(f"score needs one clip per utterance ({B}), got {len(clips)}")
-            wave, lengths = recordings(clips, dev, sample_rate, audio_lengths, silence)
-            kw = dict(sample_rate=24000, n_mels=nf)
-            mel_fine, mel_fine_lengths = M.extract(wave, lengths, FINE_HOP, self._rt.mel_mean, self._rt.mel_std, **kw)
-            mel, mel_lengths = M.extract(wave, lengths, STD_RES_HOP_LENGTH, self._rt.mel_mean, self._rt.mel_std, **kw)
+            ((mel_fine, mel_fine_lengths), (mel, mel_lengths)), lengths = self._recorded_mels(
+                x, audio, audio_lengths, "score", sample_rate, silence, FINE_HOP, STD_RES_HOP_LENGTH)
             host_len = [n // STD_RES_HOP_LENGTH + 1 for n in lengths]
         elif mel is None or mel_fine is None:
             raise ValueError("score needs either audio= or mel= and mel_fine=")
-        for name, m in (("mel", mel), ("mel_fine", mel_fine)):
-            if m.dim() != 3 or m.shape[0] != B or m.shape[1] != nf:
-                raise ValueError(f"{name} must be [{B}, {nf}, T], got {tuple(m.shape)}")
-        mel, mel_fine = mel.to(dev, torch.float32), mel_fine.to(dev, torch.float32)
-        if mel_lengths is None:
-            mel_lengths = torch.full((B,), mel.shape[2], dtype=torch.long, device=dev)
-        if mel_fine_lengths is None:
-            mel_fine_lengths = torch.full((B,), mel_fine.shape[2], dtype=torch.long, device=dev)
-        mel_lengths = torch.as_tensor(mel_lengths).to(device=dev, dtype=torch.long)
-        mel_fine_lengths = torch.as_tensor(mel_fine_lengths).to(device=dev, dtype=torch.long)
+        mel, mel_lengths = self._mel_arg("mel", "T", mel, mel_lengths, B, dev)
+        mel_fine, mel_fine_lengths = self._mel_arg("mel_fine", "T", mel_fine, mel_fine_lengths, B, dev)
         T = fix_len_compatibility(mel.shape[2])
         Tm = max(2 * T, mel_fine.shape[2], Tx)
         if mel.shape[2] < T:
@@ -553,15 +498,7 @@ class MatchaTTSInfer(nn.Module):
         B, Tx = x.shape
         mel, mel_lengths, mel_fine, mel_fine_lengths, host_len = rec
         nf, T = mel.shape[1], mel.shape[2]
-        if speaker_embeddings is not None:
-            e_enc, e_dur = speaker_embeddings
-        elif voice_mix is not None:
-            e_enc, e_dur = self.mix_speakers(voice_mix)
-        else:
-            ids = torch.as_tensor(speaker, dtype=torch.long, device=dev).reshape(-1)
-            e_enc, e_dur = hip.speaker_embedding(0, ids), hip.speaker_embedding(1, ids)
-        if e_enc.shape[0] not in (1, B):
-            raise ValueError("speaker must be an int or a LongTensor with one id per utterance")
+        e_enc, e_dur = self._voice_rows(B, dev, speaker, voice_mix, speaker_embeddings)
         x_lengths = x_lengths.to(device=dev, dtype=torch.long)
         hp = self.hp
         mu_x, logw, x_mask = self.encoder(x, x_lengths, e_enc, e_dur)
@@ -591,18 +528,17 @@ class MatchaTTSInfer(nn.Module):
         hip.score_status()
         flags = flags.cpu()
         if int(flags[2]):
-            raise RuntimeError("matcha-tts-24k_amd: a pair-form chain launch timed out waiting for its partner workgroup (another "
-                               "kernel held CUs during the launch?); set MTTS_CHAIN_PAIR=0")
+            raise RuntimeError(PAIR_TIMEOUT_ERROR)
         n_tok, n_fine, n_coarse = x_lengths.to(torch.float32), mel_fine_lengths.to(torch.float32), y_mask.sum((1, 2))
         out = {"dur_loss": dur_sum.sum() / n_tok.sum(), "prior_loss": prior_sum.sum() / n_fine.sum(),
                "diff_loss": sq_sum.sum(-1) / (n_coarse.sum() * nf),
                "dur_loss_per_utterance": dur_sum / n_tok, "prior_loss_per_utterance": prior_sum / n_fine,
                "diff_loss_per_utterance": sq_sum / (n_coarse * nf),
                "dur_sum": dur_sum, "prior_sum": prior_sum, "sq_sum": sq_sum, "durations": durations, "mas_score": mas_score,
-               "mel_lengths": mel_lengths, "mel_fine_lengths": mel_fine_lengths, "_flags": flags}
+               "mel_lengths": mel_lengths, "mel_fine_lengths": mel_fine_lengths}
         if return_frames:
             out["prior_frame"], out["dur_err"] = prior_frame, dur_err
-        return out
+        return out, flags
 
     @torch.inference_mode()
     def _synthesise(self, x, x_lengths, n_timesteps, speaker=0, voice_mix=None, scale_correction=1.0, length_scale=1.0,
@@ -626,15 +562,7 @@ class MatchaTTSInfer(nn.Module):
         hip = self._rt.ready()
         dev = x.device
         B = x.shape[0]
-        if speaker_embeddings is not None:      # (e_enc, e_dur) [B, spk_emb_dim] each: a batch that mixes plain voices and voice mixes
-            e_enc, e_dur = speaker_embeddings
-        elif voice_mix is not None:
-            e_enc, e_dur = self.mix_speakers(voice_mix)
-        else:
-            ids = torch.as_tensor(speaker, dtype=torch.long, device=dev).reshape(-1)
-            e_enc, e_dur = hip.speaker_embedding(0, ids), hip.speaker_embedding(1, ids)
-        if e_enc.shape[0] not in (1, B):
-            raise ValueError("speaker must be an int or a LongTensor with one id per utterance")
+        e_enc, e_dur = self._voice_rows(B, dev, speaker, voice_mix, speaker_embeddings)
 
         mu_x, logw, x_mask = self.encoder(x, x_lengths, e_enc, e_dur)
         if durations is None:

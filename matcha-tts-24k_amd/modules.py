@@ -20,6 +20,13 @@ from .synthetic import state_dict_spec
 
 _BUFFER_KINDS = ("mel_mean", "mel_std")
 
+#: ``gemm_terms()`` of the arithmetics whose operands can saturate: the fp16-based ones (17: its text encoder's)
+SATURATING_TERMS = (1, 2, 16, 17)
+RANGE_ERROR = ("matcha-tts-24k_amd: an operand left the fp16 range (|x| > 65504) in the default split arithmetic; set "
+               "model.range_policy = 'rerun' or MTTS_GEMM_TERMS=6")
+PAIR_TIMEOUT_ERROR = ("matcha-tts-24k_amd: a pair-form chain launch timed out waiting for its partner workgroup (another kernel held "
+                      "CUs during the launch?); set MTTS_CHAIN_PAIR=0")
+
 
 class ParamTree(nn.Module):
     """A bare container node; children and parameters are attached by dotted state-dict key."""
@@ -50,6 +57,7 @@ class Runtime:
         self.hip: Optional[HipModel] = None
         self.wide: Optional[HipModel] = None      # the same weights on the full-range arithmetic (range guard fallback)
         self.use_wide = False
+        self._range_warned = False                # the switch to ``wide`` is announced once per model
         self.dirty = True
         self.mel_mean, self.mel_std = hp.mel_mean, hp.mel_std
         self.cache_dir = None       # a converted checkpoint's directory: the packed weight image is cached there (checkpoint.packed_cache)
@@ -78,6 +86,37 @@ class Runtime:
                 self._load(self.wide)
             return self.wide
         return self.hip
+
+    # ---- the range guard (include/mtts.h "range guard"): the one place that holds the policy of every guarded model call
+    def guards(self, policy: str) -> bool:
+        """Whether a call on ``ready()`` can saturate and ``policy`` wants to know: False on the wide arithmetic, on an arithmetic
+        that is not fp16-based and under ``"ignore"`` -- then nothing is read and nothing synchronises."""
+        hip = self.ready()                     # (first: new weights put ``use_wide`` back)
+        return not self.use_wide and policy != "ignore" and hip.gemm_terms() in SATURATING_TERMS
+
+    def guarded(self, policy: str, run, verdict, can_rerun: bool = True):
+        """``run()`` under ``policy`` ("rerun", "raise" or "ignore"; ``MatchaTTSInfer.range_policy``).  ``run`` performs the call on
+        whatever ``ready()`` returns; ``verdict(out) -> (saturated, pair_timed_out)`` is the call's one host read of its device flags.
+        A saturated call raises ``FloatingPointError`` under "raise" or when ``can_rerun`` is false; otherwise the model switches to
+        the three-term bf16 context for good and the call runs again there.  Weights that saturate by themselves skip the narrow
+        run."""
+        if not self.guards(policy):
+            return run()
+        if not self.ready().weights_saturate():
+            out = run()
+            saturated, timed_out = verdict(out)
+            if timed_out:
+                raise RuntimeError(PAIR_TIMEOUT_ERROR)
+            if not saturated:
+                return out
+        if policy == "raise" or not can_rerun:
+            raise FloatingPointError(RANGE_ERROR)
+        if not self._range_warned:
+            print("[matcha-tts-24k_amd] an operand left the fp16 range of the default arithmetic: this model now runs on "
+                  "three-term bf16 products (full fp32 range)")
+            self._range_warned = True
+        self.use_wide = True                   # sticky: a checkpoint that overflows once will do so again
+        return run()
 
 
 class _PathModule(ParamTree):

@@ -761,6 +761,38 @@ def test_range_guard_reruns_on_full_range_arithmetic(hparams, synthetic, oracle,
     assert torch.equal(out["mel"], again["mel"])
 
 
+def test_range_guard_of_score_on_full_range_arithmetic(hparams, synthetic, dev):
+    """``score`` under the three policies on the weights of the test above (the decoder FeedForward scaled by 4e4): its one
+    estimator evaluation saturates, so `ignore` leaves the decoder's flag set, `raise` raises, and `rerun` switches the model to
+    the three-term bf16 context and returns that run's figures, without the guard's private ``_flags`` entry."""
+    hp = hparams.prod_v20(n_spks=1)
+    sd = synthetic.make_state_dict(hp, seed=7)
+    k = "decoder.estimator.mid_blocks.0.1.0.ff.net."
+    sd[k + "0.proj.weight"] = sd[k + "0.proj.weight"] * 4e4
+    sd[k + "0.proj.bias"] = sd[k + "0.proj.bias"] * 4e4
+    sd[k + "0.alpha"] = sd[k + "0.alpha"] - 10.0
+    sd[k + "2.weight"] = sd[k + "2.weight"] / 4e4
+    model = make_model(hp, sd, dev)
+    x, x_len, _ = synthetic.make_inputs(hp, 1, 16, seed=77)
+    gen = torch.Generator().manual_seed(5)
+    mel = torch.randn(1, hp.n_feats, 40, generator=gen).to(dev)
+    mel_fine = torch.randn(1, hp.n_feats, 80, generator=gen).to(dev)
+    noise = torch.randn(1, hp.n_feats, 40, generator=gen).to(dev)
+    score = lambda: model.score(x.to(dev), x_len.to(dev), mel=mel, mel_fine=mel_fine, speaker=0, t=[0.5], noise=noise)
+    model.range_policy = "ignore"
+    assert "diff_loss" in score()
+    assert bool(model.hip.range_flags()[1].item())
+    model.range_policy = "raise"
+    with pytest.raises(FloatingPointError):
+        score()
+    model.range_policy = "rerun"
+    out = score()
+    assert model.hip.gemm_terms() == 6                      # the runtime switched to the three-term bf16 context
+    assert "_flags" not in out
+    assert bool(torch.isfinite(out["diff_loss"]).all())
+    assert torch.equal(out["diff_loss"], score()["diff_loss"])
+
+
 def test_range_guard_is_quiet_on_ordinary_weights(prod, synthetic, dev):
     hp, sd, model = prod
     x, x_len, _ = synthetic.make_inputs(hp, 2, 40, seed=3)
