@@ -759,6 +759,64 @@ int mtts_mel_stats(const float* d_mel, int F, int T, const int64_t* d_lengths, i
                    int32_t* d_flags, void* d_ws, int64_t ws_bytes, void* stream);
 int mtts_mel_stats_status(const void* d_ws, void* stream);
 
+/* ---------------------------------------------------------------- encoded audio: PCM16, G.711 mu-law / A-law */
+
+/* The last stage out and the first stage in: a ragged batch of fp32 rows to the bytes a client is sent (s16le for the OpenAI
+ * route's "pcm" and "wav", G.711 for an 8 kHz telephony leg), and a ragged batch of such bytes back to fp32 for the recording
+ * entries.  One launch each, gridded over (tile of MTTS_CODEC_TILE samples, row); every row has its own format.  Every byte is
+ * defined by the arithmetic below, which a NumPy restatement reproduces bit for bit.
+ *
+ * Formats: MTTS_PCM16 (s16le, 2 bytes per sample), MTTS_ULAW, MTTS_ALAW (ITU-T G.711, 1 byte per sample).
+ *
+ * mtts_pcm_encode: d_audio [B][ld] fp32, rows as everywhere else (ld % 4 == 0, 16-byte aligned); d_lengths device int64 [B],
+ * samples; d_formats device int32 [B]; d_keys device int64 [B] or NULL (all 0); d_out uint8 [B][2 * ld], one stride for every
+ * row (a G.711 row uses the front half), 16-byte aligned; d_out_bytes device int64 [B] = len_b * bytes per sample.
+ *   q:      y = x * 32768 in fp32 (exact: a power of two); with dither on a PCM16 row y = y + d, one fp32 add;
+ *           q = rint(y), ties to even, clamped to [-32768, 32767]; NaN gives 0.  32768 is the inverse of the / 32768 of
+ *           mtts_pcm_decode and of every reader of this project: decode then encode returns each of the 65536 words unchanged.
+ *   PCM16:  the two bytes of q, low byte first.
+ *   G.711:  companding of the UNDITHERED q (dither touches PCM16 rows only), in integer operations, as CPython's
+ *           audioop.lin2ulaw / lin2alaw(.., 2) computes it.  With seg(v, e0) = the number of i in [0, 8) with v > (e0 << i) - 1:
+ *           mu-law: v = q >> 2 (arithmetic); mask = 0x7F and v = -v when v < 0, else mask = 0xFF; v = min(v, 8159) + 33;
+ *                   s = seg(v, 0x40); byte = (s == 8 ? 0x7F : (s << 4) | ((v >> (s + 1)) & 15)) ^ mask;
+ *           A-law:  v = q >> 3; mask = 0x55 and v = -v - 1 when v < 0, else mask = 0xD5; s = seg(v, 0x20);
+ *                   byte = (s == 8 ? 0x7F : (s << 4) | ((v >> (s < 2 ? 1 : s)) & 15)) ^ mask.
+ *   dither: TPDF of one LSB: d = u1 - u2, u_k = (h_k >> 8) * 2^-24, the difference exact in fp32.  h_k is a 32-bit counter-based
+ *           hash of (seed, d_keys[b], the sample's index i within its row, the stream k - 1 in {0, 1}) and of nothing else -- not of
+ *           the row index, the grid or the batch -- in uint32 arithmetic, a chain of murmur3 finalisers
+ *               fmix(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ *               h = fmix(0x9E3779B9 ^ seed_lo); h = fmix(h ^ seed_hi); h = fmix(h ^ key_lo); h = fmix(h ^ key_hi);
+ *               h_k = fmix(h ^ (2 * i + (k - 1)))        (lo / hi: the low and high 32 bits of the int64; i < 2^30)
+ *           so a row's bytes do not depend on the batch it is in, and two calls give the same bits.
+ *   tails:  bytes at or beyond d_out_bytes[b] are never written: whole groups of 4 samples are stored as 8 (PCM16) or 4 (G.711)
+ *           bytes, the last partial group of a row sample by sample.  Nothing outside [0, len_b) of a row is read.
+ *   refusals: a length outside [0, ld] or a format that is none of the three gives d_out_bytes[b] = -1 and no byte written for
+ *           that row; the other rows are unaffected.  A length that already is -1 (a row refused by mtts_waveform_finish or
+ *           mtts_resample_forward) therefore stays -1.
+ *
+ * mtts_pcm_decode: the inverse.  d_data uint8 [B][ld_bytes] (ld_bytes % 16 == 0, 16-byte aligned), d_lengths in samples,
+ * d_formats as above -> d_out fp32 [B][ld] (ld % 4 == 0), d_out_lengths int64 [B] = len_b.  PCM16: q / 32768.  G.711: the G.711
+ * linear value / 32768, with c = ~byte for mu-law: t = (((c & 15) << 3) + 132) << ((c >> 4) & 7), value = c & 0x80 ? 132 - t :
+ * t - 132; with c = byte ^ 0x55 for A-law: s = (c >> 4) & 7, t = (c & 15) << 4, t = s == 0 ? t + 8 : (t + 0x108) << (s - 1),
+ * value = c & 0x80 ? t : -t (audioop.ulaw2lin / alaw2lin(.., 2)).  Both quotients are exact.  Samples at or beyond len_b are
+ * written as zeros up to ld, as the mel front end expects of a padded row.  A length outside [0, ld], one whose bytes exceed
+ * ld_bytes, or an unknown format gives d_out_lengths[b] = -1 and leaves the row unwritten.
+ *
+ * Both: stream-ordered, no allocation, no synchronisation, no workspace.  What the host can see returns -1 (mtts_last_error):
+ * null pointers, B < 1, a bad ld, a misaligned buffer, d_out overlapping the input.  mtts_pcm_status(d_verdict, B, stream) --
+ * the one entry here that waits for the stream -- reads d_out_bytes or d_out_lengths of a call and names the first refused row
+ * through mtts_last_error.  mtts_codec_tile = MTTS_CODEC_TILE as built. */
+#define MTTS_PCM16 0
+#define MTTS_ULAW 1
+#define MTTS_ALAW 2
+#define MTTS_CODEC_TILE 2048           /* samples per workgroup */
+int mtts_codec_tile(void);
+int mtts_pcm_encode(const float* d_audio, int64_t ld, const int64_t* d_lengths, const int32_t* d_formats, const int64_t* d_keys,
+                    int B, int dither, int64_t seed, uint8_t* d_out, int64_t* d_out_bytes, void* stream);
+int mtts_pcm_decode(const uint8_t* d_data, int64_t ld_bytes, const int64_t* d_lengths, const int32_t* d_formats, int B,
+                    float* d_out, int64_t ld, int64_t* d_out_lengths, void* stream);
+int mtts_pcm_status(const int64_t* d_verdict, int B, void* stream);
+
 /* ---------------------------------------------------------------- forced alignment (Monotonic Alignment Search) */
 
 /* Which fine mel frames belong to which token -- the alignment of the reference's training forward, matcha/models/matcha_tts.py:

@@ -43,8 +43,16 @@ class Request:
     length_scale: float = 1.0
     durations: Optional[Sequence[float]] = None    # fine frames per token (e.g. ``align(...)["durations"]``) instead of the predictor's; length_scale still applies
     sample_rate: int = 24000                # rate of the result's "audio" (with a vocoder); anything else is converted on the device and named in the result
+    encoding: Optional[str] = None          # "pcm16" / "ulaw" / "alaw": the result's "audio" is then raw bytes (a 1-D uint8 tensor) encoded on the device, and named in the result
+    dither: bool = False                    # TPDF dither on a "pcm16" result
+    dither_key: int = 0                     # selects the dither sequence: a field of the request, so its bytes do not depend on who shared its batch
     future: Future = field(default_factory=Future, repr=False)
     t_submit: float = field(default_factory=time.monotonic, repr=False)
+
+    def __post_init__(self):
+        if self.encoding is not None:       # (an unknown name fails its own request here, not the batch it would have joined)
+            from .audio_codec import format_id
+            format_id(self.encoding)
 
     @property
     def group(self) -> Tuple[Any, ...]:
@@ -60,6 +68,14 @@ def duration_rows(batch: List[Request]) -> Optional[List[Optional[Sequence[float
         if r.durations is not None and len(r.durations) != len(r.ids):
             raise ValueError(f"a request's durations need one value per token ({len(r.ids)}), got {len(r.durations)}")
     return [r.durations for r in batch]
+
+
+def encoding_fields(batch: List[Request]):
+    """``(encodings, dithers, dither_keys)`` of a batch as ``waveforms_into`` takes them; three None when no request names an
+    encoding (the call is then exactly the one made before there was a choice).  Pure function: unit-tested on the CPU."""
+    if all(r.encoding is None for r in batch):
+        return None, None, None
+    return [r.encoding for r in batch], [bool(r.dither) for r in batch], [int(r.dither_key) for r in batch]
 
 
 def plan_batch(waiting: List[Request], max_batch: int, max_tokens: int) -> List[int]:
@@ -181,29 +197,48 @@ def request_inputs(model, batch: List[Request]):
     return x.to(dev), x_len.to(dev), emb
 
 
-def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_batch: bool, sample_rates: Optional[Sequence[int]] = None) -> None:
+def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_batch: bool, sample_rates: Optional[Sequence[int]] = None,
+                   encodings: Optional[Sequence[Optional[str]]] = None, dithers: Optional[Sequence[bool]] = None,
+                   dither_keys: Optional[Sequence[int]] = None) -> None:
     """``res[b]["audio"]`` for a batch of finished mels (``mel`` [B, n_feats, T], ``mel_lengths`` [B]; ``res[b]["mel"]`` the exact-length
     rows).  ``sample_rates``: one rate per request (default 24 kHz); rows that ask for another rate are converted on the device after
-    the normalisation and the trim (``inference.to_waveforms``) and carry ``res[b]["sample_rate"]`` beside ``"audio"``.  A result at
-    24 kHz keeps exactly the keys it had before there was a choice."""
+    the normalisation and the trim (``inference.to_waveforms``) and carry ``res[b]["sample_rate"]`` beside ``"audio"``.
+    ``encodings``: one name or None per request; a row that names one is encoded on the device after that (``audio_codec.encode``,
+    with the request's ``dithers`` flag and ``dither_keys`` entry), its ``"audio"`` is a 1-D uint8 tensor of raw samples and it
+    carries ``res[b]["encoding"]``.  A float result at 24 kHz keeps exactly the keys it had before there was a choice."""
     if vocoder is None:
         return
-    rates = [24000] * len(res) if sample_rates is None else [int(v) for v in sample_rates]
+    B = len(res)
+    rates = [24000] * B if sample_rates is None else [int(v) for v in sample_rates]
+    encs = [None] * B if encodings is None else list(encodings)
+    dith = [False] * B if dithers is None else [bool(v) for v in dithers]
+    keys = [0] * B if dither_keys is None else [int(v) for v in dither_keys]
+    coded = any(e is not None for e in encs)
     if wave_batch:
         from .inference import to_waveforms
-        for r, a in zip(res, to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates)):
+        extra = dict(encoding=encs, dither=dith, dither_keys=keys) if coded else {}
+        for r, a in zip(res, to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, **extra)):
             r["audio"] = a
     else:
         from .inference import _convert_rows, _waveform_on_device, trim_trailing_silence
-        for r, rate in zip(res, rates):
+        for r, rate, enc, on, key in zip(res, rates, encs, dith, keys):
             a = trim_trailing_silence(_waveform_on_device(r["mel"][None], vocoder).squeeze())
             if rate != 24000 and a.numel() > 0:
                 conv, n = _convert_rows(a.reshape(1, -1), torch.tensor([a.numel()], dtype=torch.long, device=a.device), [rate])
                 a = conv[0, :int(n[0])]
+            if enc is not None:
+                from . import audio_codec as AC
+                if a.numel() > 0:
+                    data, _ = AC.encode(a.reshape(1, -1), None, enc, dither=on, keys=[key])
+                    a = data[0, :a.numel() * AC.BYTES_PER_SAMPLE[AC.format_id(enc)]]
+                else:
+                    a = torch.zeros(0, dtype=torch.uint8)
             r["audio"] = a.cpu()
-    for r, rate in zip(res, rates):
+    for r, rate, enc in zip(res, rates, encs):
         if rate != 24000:
             r["sample_rate"] = rate
+        if enc is not None:
+            r["encoding"] = enc
 
 
 def synthesise_batch(model, batch: List[Request], vocoder=None, wave_batch: bool = True) -> List[Dict[str, Any]]:
@@ -218,7 +253,7 @@ def synthesise_batch(model, batch: List[Request], vocoder=None, wave_batch: bool
                            durations=duration_rows(batch))
     lens = out["mel_lengths"].tolist()
     res = [{"mel": out["mel"][b, :, :int(lens[b])], "mel_length": int(lens[b])} for b in range(B)]
-    waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch, [r.sample_rate for r in batch])
+    waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch, [r.sample_rate for r in batch], *encoding_fields(batch))
     return res
 
 
@@ -546,7 +581,8 @@ class StepBatcher:
                 mel[b, :, :r["mel_length"]] = r["mel"]
             lengths = torch.tensor([r["mel_length"] for r in res], dtype=torch.long, device=mel.device)
             try:
-                waveforms_into(res, mel, lengths, self.vocoder, self.wave_batch, [e.request.sample_rate for e in finished])
+                waveforms_into(res, mel, lengths, self.vocoder, self.wave_batch, [e.request.sample_rate for e in finished],
+                               *encoding_fields([e.request for e in finished]))
             except BaseException as exc:  # noqa: BLE001 - the finishers only: who is mid-solve is not affected
                 self._fail([e.request for e in finished], exc)
                 return

@@ -166,7 +166,8 @@ class MatchaTTSInfer(nn.Module):
         matcha/utils/precompute_mels.py:100-113 (normalise with this model's mel statistics, hop 128), StyleEncoder.forward and
         matcha/add_speaker.py:40-62 (average over the clips) -- as one front-end call and one encoder call on the device.
 
-        ``clips``: a list of 1-D waveforms (host or device, mono in [-1, 1]) of ONE voice -> ``(e_enc, e_dur)`` of shape
+        ``clips``: a list of 1-D waveforms (host or device, mono in [-1, 1]; or ``audio_codec.Encoded`` clips, still PCM16 / G.711
+        bytes, decoded on the device -- ``recordings``) of ONE voice -> ``(e_enc, e_dur)`` of shape
         [1, spk_emb_dim]; or a list of such lists for several voices -> [n_voices, spk_emb_dim].  The rows are what
         ``synthesise(speaker_embeddings=...)``, ``speaker_rows`` and ``add_speaker`` take.  ``sample_rate``: the clips' rate, an int
         or one int per clip (in the order of the flattened list); clips at another rate than 24 kHz are converted on the device
@@ -178,7 +179,8 @@ class MatchaTTSInfer(nn.Module):
         from .style import FINE_HOP
         if len(clips) == 0:
             raise ValueError("no clips")
-        voices = [clips] if torch.is_tensor(clips[0]) or isinstance(clips[0], np.ndarray) else list(clips)
+        from .audio_codec import Encoded
+        voices = [clips] if torch.is_tensor(clips[0]) or isinstance(clips[0], (np.ndarray, Encoded)) else list(clips)
         dev = next(self.parameters()).device
         self._rt.ready()                                   # mel statistics come from the loaded checkpoint's buffers
         flat, group = [], []
@@ -283,8 +285,9 @@ class MatchaTTSInfer(nn.Module):
     @staticmethod
     def _clips(audio, B, who):
         """The ``audio`` argument of the recording entries as a list of ``B`` clips: a [B, L] tensor's rows, one 1-D waveform, or a list."""
+        from .audio_codec import Encoded
         clips = [audio[b] for b in range(audio.shape[0])] if torch.is_tensor(audio) and audio.dim() == 2 else (
-            [audio] if torch.is_tensor(audio) or isinstance(audio, np.ndarray) else list(audio))
+            [audio] if torch.is_tensor(audio) or isinstance(audio, (np.ndarray, Encoded)) else list(audio))
         if len(clips) != B:
             raise ValueError(f"{who} needs one clip per utterance ({B}), got {len(clips)}")
         return clips
@@ -601,6 +604,7 @@ def _recordings_24k(clips, dev, sample_rate=24000, lengths=None):
     the device (``resample.resample``, the given length as the row length); rows at 24 kHz are copied.  With every clip at 24 kHz
     nothing but the copies is launched.  The converted lengths are ``ceil(24000 * len / rate)``, known without a host read."""
     from . import resample as R
+    clips, sample_rate = _decoded_clips(list(clips), dev, sample_rate)
     clips = [torch.as_tensor(c).to(torch.float32) for c in clips]
     if any(c.dim() != 1 for c in clips):
         raise ValueError("a clip is a 1-D waveform (mono)")
@@ -635,6 +639,25 @@ def _recordings_24k(clips, dev, sample_rate=24000, lengths=None):
     return wave, lengths
 
 
+def _decoded_clips(clips, dev, sample_rate):
+    """``audio_codec.Encoded`` clips among ``clips`` decoded on the device (one launch for all of them, ahead of the rate conversion),
+    and the clips' rates: ``sample_rate`` as given where it names a rate for a clip -- an int names one for every clip -- and, where it
+    is None (as a whole, or that clip's entry of a list), the clip's own ``Encoded.sample_rate`` (24 kHz for a waveform).  Without an
+    encoded clip and with every rate named, both arguments come back as they are and nothing is launched."""
+    from . import audio_codec as AC
+    at = [i for i, c in enumerate(clips) if isinstance(c, AC.Encoded)]
+    own = [clips[i].sample_rate if i in at else SAMPLE_RATE for i in range(len(clips))]
+    if sample_rate is None:
+        sample_rate = own
+    elif not isinstance(sample_rate, (int, np.integer)) and not torch.is_tensor(sample_rate):
+        sample_rate = [own[i] if r is None else r for i, r in enumerate(sample_rate)] if len(sample_rate) == len(clips) else sample_rate
+    if at:
+        wave, counts = AC.decode_clips([clips[i] for i in at], dev)
+        for k, i in enumerate(at):
+            clips[i] = wave[k, :counts[k]]
+    return clips, sample_rate
+
+
 def _silence_normalised(wave, lengths, silence):
     """``silence=`` of the recording entries: None returns the arguments (nothing is launched); ``(leading_s, trailing_s)`` (either
     may be None) rebuilds every 24 kHz row of ``_recordings_24k`` with exactly that much silence around its content
@@ -651,7 +674,9 @@ def _silence_normalised(wave, lengths, silence):
 def recordings(clips, dev, sample_rate=24000, lengths=None, silence=None):
     """What the recording entries (``enroll_voice``, ``align``, ``score``, ``speaker_grad``, ``finetune_speaker``) make of their clips
     before the mel front end: ``(wave [B, ld] fp32 on ``dev`` at 24 kHz, lengths: list of B ints)``.  ``clips``: 1-D waveforms (host
-    or device) at ``sample_rate`` (an int or one per clip; converted on the device), ``lengths``: samples to use of each;
+    or device) at ``sample_rate`` (an int or one per clip; converted on the device) or ``audio_codec.Encoded`` clips -- still bytes,
+    PCM16 / mu-law / A-law, decoded on the device in one launch; where ``sample_rate`` is None, or None for that clip, the clip's
+    own ``Encoded.sample_rate`` is used --, ``lengths``: samples to use of each;
     ``silence``: None or ``(leading_s, trailing_s)``, normalised after the conversion (``corpus.normalize_silence``).  For a
     caller that needs the lengths ahead of the call, e.g. to size ``score``'s noise."""
     return _silence_normalised(*_recordings_24k(clips, dev, sample_rate, lengths), silence)
@@ -760,7 +785,8 @@ def finish_waveforms(audio, lengths, hop=0, silence_threshold_db=-60.0):
 
 
 @torch.inference_mode()
-def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, sample_rate=24000):
+def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, *, encoding=None, dither=False, dither_keys=None,
+                 sample_rate=24000):
     """``trim_trailing_silence(to_waveform(mel[b:b+1, :, :len_b], vocoder))`` (reference inference.py:246) for every row of a
     ragged batch in one device pass: ragged Vocos decode, per-row peak normalisation, per-row trim lengths, then ONE copy of the
     audio and one of the [B] lengths -- one synchronisation for the whole batch.  Returns a list of B 1-D host tensors
@@ -769,7 +795,14 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     ``sample_rate``: an int, or one per row.  Rows that ask for another rate than 24 kHz are converted on the device after the
     normalisation and the trim, which run at 24 kHz exactly as without it: the kept samples of those rows go through
     ``resample.resample`` (one call per distinct rate, the trim length as the row length, no extra host read) ahead of the copy.
-    The band-limited output of a row normalised to a 0.95 peak may overshoot that peak slightly; nothing is re-normalised."""
+    The band-limited output of a row normalised to a 0.95 peak may overshoot that peak slightly; nothing is re-normalised.
+
+    ``encoding``: None (float32 rows, as ever), a name -- ``"pcm16"`` (s16le), ``"ulaw"``, ``"alaw"`` (G.711) -- or one per row, where
+    None leaves a row float.  The rows that name one are encoded on the device (``audio_codec.encode``: one launch after the trim
+    and the rate conversion, on their device lengths, no extra host read) and come back as 1-D uint8 host tensors: raw samples, no
+    container, views of the batch's one host buffer of bytes; the one copy is then of bytes and the single synchronisation stays.
+    ``dither`` (a bool, or one per row): TPDF dither on the PCM16 rows, the sequence of row b selected by ``dither_keys[b]`` (default
+    0) and by nothing else, so a row's bytes do not depend on the batch it is in.  The keyword-only arguments follow a ``*``."""
     model = vocoder.model if hasattr(vocoder, "model") else vocoder
     if mel.dim() == 2:
         mel = mel[None]
@@ -778,11 +811,14 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     hop = model.cfg["hop"]
     from . import resample as R
     rates = R.rates_per_row(sample_rate, B)
+    encs = _encodings_per_row(encoding, B)                             # (an unknown name raises before anything is launched)
     audio = model.decode(mel, mel_lengths, check=False)
     out_lengths, _ = finish_waveforms(audio, mel_lengths, hop=hop, silence_threshold_db=silence_threshold_db)
     if any(r != SAMPLE_RATE for r in rates):
         audio, out_lengths = _convert_rows(audio, out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1)),
                                            rates)
+    if encs is not None:
+        return _encoded_rows(audio, out_lengths, mel_lengths, hop, T, trim, rates, encs, dither, dither_keys)
     meta = torch.stack([out_lengths, mel_lengths]).cpu()              # waits for the stream: the batch's one synchronisation
     host = audio.cpu()
     keep, frames = meta[0].tolist(), meta[1].tolist()
@@ -790,6 +826,49 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
         if keep[b] < 0:
             raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
     return [host[b, : (keep[b] if trim or rates[b] != SAMPLE_RATE else hop * (frames[b] - 1))] for b in range(B)]
+
+
+def _encodings_per_row(encoding, B):
+    """``encoding=`` of ``to_waveforms`` as a list of B format ids or None per row; None when no row names one."""
+    from . import audio_codec as AC
+    if encoding is None:
+        return None
+    if isinstance(encoding, str):
+        return [AC.format_id(encoding)] * B
+    encs = [None if e is None else AC.format_id(e) for e in encoding]
+    if len(encs) != B:
+        raise ValueError(f"encoding is a name or one per row ({B}), got {len(encs)}")
+    return encs if any(e is not None for e in encs) else None
+
+
+def _encoded_rows(audio, out_lengths, mel_lengths, hop, T, trim, rates, encs, dither, dither_keys):
+    """The end of ``to_waveforms`` when rows name an encoding: one encode launch over the finished (and converted) rows on their
+    device lengths, then the batch's one synchronisation and the copy of the bytes.  Rows without an encoding take part in the
+    launch with length 0 and are returned float32 from a second copy, of the audio."""
+    from . import audio_codec as AC
+    B = audio.shape[0]
+    dev = audio.device
+    # the kept samples of every row, on the device: what the float path slices on the host
+    whole = torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1))
+    if trim:
+        keep_dev = out_lengths
+    else:
+        converted = torch.tensor([r != SAMPLE_RATE for r in rates], dtype=torch.bool, device=dev)
+        keep_dev = torch.where(converted, out_lengths, whole)
+    named = torch.tensor([e is not None for e in encs], dtype=torch.bool, device=dev)
+    fmt = [AC.PCM16 if e is None else e for e in encs]
+    on = [bool(dither)] * B if isinstance(dither, (bool, int)) else [bool(v) for v in dither]
+    data, nbytes = AC.encode(audio, torch.where(named, keep_dev, torch.zeros_like(keep_dev)), fmt,
+                             dither=on if len(set(on)) > 1 else on[0], keys=dither_keys)
+    meta = torch.stack([keep_dev, mel_lengths, nbytes]).cpu()          # waits for the stream: the batch's one synchronisation
+    keep, frames, got = (m.tolist() for m in meta)
+    for b in range(B):
+        if keep[b] < 0 or got[b] < 0:
+            raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
+    width = max(AC.BYTES_PER_SAMPLE[f] for f in fmt) * audio.shape[1]  # G.711 rows use the front half of the stride
+    host = data[:, :width].cpu() if width < data.shape[1] else data.cpu()
+    floats = audio.cpu() if not all(e is not None for e in encs) else None
+    return [floats[b, :keep[b]] if encs[b] is None else host[b, :got[b]] for b in range(B)]
 
 
 def _convert_rows(audio, lengths, rates):
@@ -840,12 +919,14 @@ def trim_trailing_silence(audio, silence_threshold_db=-60.0):
 
 @torch.inference_mode()
 def pipeline(model, vocoder, text, speaker=0, voice_mix=None, n_timesteps=DEFAULT_NUM_STEPS, scale_correction=1.0,
-             length_scale=1.0, debug=False, sample_rate=24000):
+             length_scale=1.0, debug=False, *, encoding=None, sample_rate=24000):
     """reference inference.py:233-257.  The reference wraps ``synthesise`` in ``torch.autocast`` (fp16 on its CUDA device);
     here the estimator's arithmetic is chosen when the model is created (``MTTS_GEMM_TERMS``: default fp32-equivalent; 1 = fp16
     operands / fp32 accumulate, the autocast arithmetic), not per call.  The trailing-silence trim runs on the device.
     ``sample_rate``: the rate of the returned waveform; anything but 24 kHz is converted on the device after the normalisation and
-    the trim (``resample.resample``; the band-limited result may overshoot the 0.95 peak slightly, nothing is re-normalised)."""
+    the trim (``resample.resample``; the band-limited result may overshoot the 0.95 peak slightly, nothing is re-normalised).
+    ``encoding``: None (a float32 waveform), or ``"pcm16"`` / ``"ulaw"`` / ``"alaw"``: the waveform is encoded on the device
+    (``audio_codec.encode``) and returned as a 1-D uint8 host tensor of raw samples."""
     primary = voice_mix[0][0] if voice_mix is not None else speaker
     language = next(v["lang"] for v in VOICES if v["id"] == str(primary))
     tp = process_text(text, language)
@@ -856,6 +937,12 @@ def pipeline(model, vocoder, text, speaker=0, voice_mix=None, n_timesteps=DEFAUL
         from . import resample as R
         conv, _ = R.resample(waveform.reshape(1, -1), None, SAMPLE_RATE, int(sample_rate), check=False)
         waveform = conv[0, :R.resampler(SAMPLE_RATE, int(sample_rate), conv.device).out_length(waveform.numel())]
+    if encoding is not None and waveform.numel() > 0:
+        from . import audio_codec as AC
+        data, _ = AC.encode(waveform.reshape(1, -1), None, encoding)
+        waveform = data[0, :waveform.numel() * AC.BYTES_PER_SAMPLE[AC.format_id(encoding)]]
+    elif encoding is not None:
+        waveform = torch.zeros(0, dtype=torch.uint8)
     waveform = waveform.cpu()
     if not debug:
         return waveform

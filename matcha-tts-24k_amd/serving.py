@@ -5,8 +5,10 @@ The reference handler (reference matcha/server.py:93-127) turns one POST /v1/aud
 thread, one request at a time.  ``request_params`` is that mapping (voice / voice-mix parsing, the per-voice duration scale
 correction of ``VOICES``, the speed -> length_scale clamp) as a pure function, and ``SpeechService`` is the piece a maintainer
 puts behind the same route: it phonemizes, submits to a ``FrameBudgetBatcher`` (so concurrent requests share estimator
-launches without changing anybody's audio) and awaits the trimmed waveform.  Transport, response encoding (MP3 / OGG) and the
-phonemizer stay the reference's (out of the path's scope).
+launches without changing anybody's audio) and awaits the trimmed waveform.  ``response_format`` names the plain formats of the
+route -- ``pcm`` (s16le), ``wav`` (RIFF + PCM16) -- and the two G.711 laws of a telephony leg; their samples are encoded on the device
+(``audio_codec``).  Transport, the compressed response encodings (MP3 / OGG) and the phonemizer stay the reference's (out of the
+path's scope).
 """
 from __future__ import annotations
 
@@ -20,6 +22,9 @@ from .inference import DEFAULT_NUM_STEPS, DEFAULT_ODE_SOLVER, VOICES
 LENGTH_SCALE_MIN = 0.1      # fastest (client speed 2.0 clamps here; reference server.py:34-36)
 LENGTH_SCALE_MAX = 2.0      # slowest
 MAX_TEXT_LENGTH = 1000      # reference server.py:30
+
+#: ``response_format`` -> the encoding a request asks of the batcher; "wav" is that payload behind a RIFF header
+RESPONSE_FORMATS = {"pcm": "pcm16", "wav": "pcm16", "ulaw": "ulaw", "alaw": "alaw"}
 
 _MIX = re.compile(r"^\s*(\d+)\((\d+)\)\s*$")
 
@@ -49,6 +54,27 @@ class SpeechParams:
     solver: str
 
 
+def response_encoding(response_format: Optional[str]) -> Optional[str]:
+    """The ``Request.encoding`` of a ``response_format``: None for None (a float waveform), else ``RESPONSE_FORMATS``; ``ValueError``
+    for a name that is none of them (mp3 / opus are the reference's post-waveform codecs, ``inference.convert_to_*``)."""
+    if response_format is None:
+        return None
+    if response_format not in RESPONSE_FORMATS:
+        raise ValueError(f"unknown response_format {response_format!r}: one of {sorted(RESPONSE_FORMATS)} (or None for float samples)")
+    return RESPONSE_FORMATS[response_format]
+
+
+def response_body(res, response_format: Optional[str], sample_rate: int = 24000):
+    """What ``speak`` returns for a batcher result: the ``"audio"`` (or the mel, without a vocoder) as it is when no
+    ``response_format`` was named, else ``bytes`` -- the raw encoded samples, behind a RIFF header for ``"wav"``."""
+    audio = res["audio"] if "audio" in res else res["mel"]
+    if response_format is None:
+        return audio
+    from .audio_codec import _payload_bytes, wav_bytes
+    raw = _payload_bytes(audio)
+    return wav_bytes(raw, "pcm16", sample_rate) if response_format == "wav" else raw
+
+
 def request_params(voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER) -> SpeechParams:
     """The request -> synthesis parameters of reference server.py:96-115 (and the language lookup of inference.py:235-236)."""
     if "+" in str(voice):
@@ -65,7 +91,7 @@ def request_params(voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, 
 
 
 class SpeechService:
-    """``await service.speak(text, voice, speed, steps, solver)`` -> 1-D waveform tensor on the host.
+    """``await service.speak(text, voice, speed, steps, solver)`` -> 1-D waveform tensor on the host (``bytes`` with ``response_format``).
 
     ``phonemize(text, language) -> list of phoneme ids`` is the reference's front end (``process_text``); ``batcher`` a
     ``FrameBudgetBatcher`` or a ``StepBatcher`` (same ``submit`` contract; the second schedules at the solver step, so requests with
@@ -77,10 +103,14 @@ class SpeechService:
         self.max_text_length = int(max_text_length)
 
     def submit(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
-               speaker_embedding=None, sample_rate: int = 24000):
+               speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None):
         """``speaker_embedding``: the ``(e_enc, e_dur)`` rows of an enrolled voice (``MatchaTTSInfer.enroll_voice``); the request is
         then spoken with them, and ``voice`` only picks the language and the duration scale correction.  ``sample_rate``: the rate
-        of the result's ``"audio"`` (8 or 16 kHz for telephony, 48 kHz for a browser); the batcher converts on the device."""
+        of the result's ``"audio"`` (8 or 16 kHz for telephony, 48 kHz for a browser); the batcher converts on the device.
+        ``response_format``: None (float samples), ``"pcm"`` (raw s16le), ``"wav"`` (the same samples; ``speak`` adds the RIFF
+        header), ``"ulaw"`` / ``"alaw"`` (raw G.711), all at ``sample_rate`` and encoded on the device; an unknown name raises
+        ``ValueError`` before anything is submitted."""
+        encoding = response_encoding(response_format)
         if len(text) > self.max_text_length:
             raise ValueError(f"Text exceeds {self.max_text_length} characters")       # the handler's HTTP 400
         p = request_params(voice, speed, steps, solver)
@@ -88,10 +118,13 @@ class SpeechService:
         extra = {} if speaker_embedding is None else {"speaker_embedding": tuple(speaker_embedding)}
         if int(sample_rate) != 24000:
             extra["sample_rate"] = int(sample_rate)
+        if encoding is not None:
+            extra["encoding"] = encoding
         return self.batcher.submit(ids, speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver, n_timesteps=p.n_timesteps,
                                    scale_correction=p.scale_correction, length_scale=p.length_scale, **extra)
 
     async def speak(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
-                    speaker_embedding=None, sample_rate: int = 24000):
-        res = await asyncio.wrap_future(self.submit(text, voice, speed, steps, solver, speaker_embedding, sample_rate))
-        return res["audio"] if "audio" in res else res["mel"]
+                    speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None):
+        """The waveform (a 1-D float tensor on the host), or with ``response_format`` the response body as ``bytes``."""
+        res = await asyncio.wrap_future(self.submit(text, voice, speed, steps, solver, speaker_embedding, sample_rate, response_format))
+        return response_body(res, response_format, int(sample_rate))

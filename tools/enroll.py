@@ -24,10 +24,19 @@ PKG = "matcha-tts-24k_amd"
 
 
 def read_wav(path):
-    """``(samples: 1-D float32 tensor in [-1, 1], sample rate)`` of a PCM wav file; channel 0 of a multi-channel file."""
-    with wave.open(str(path), "rb") as w:
-        rate, channels = w.getframerate(), w.getnchannels()
-        width, raw = w.getsampwidth(), w.readframes(w.getnframes())
+    """``(samples: 1-D float32 tensor in [-1, 1], sample rate)`` of a PCM wav file; channel 0 of a multi-channel file.  A file whose
+    format the stdlib ``wave`` module refuses (G.711 mu-law / A-law: "unknown format: 7") is read by ``audio_codec.read_wav`` and
+    comes back as an ``Encoded`` clip, still bytes, which the model's recording entries decode on the device."""
+    try:
+        with wave.open(str(path), "rb") as w:
+            rate, channels = w.getframerate(), w.getnchannels()
+            width, raw = w.getsampwidth(), w.readframes(w.getnframes())
+    except wave.Error as e:
+        if "unknown format" not in str(e):
+            raise
+        import importlib
+        enc = importlib.import_module(PKG + ".audio_codec").read_wav(path)
+        return enc, int(enc.sample_rate)
     if width == 2:
         a = np.frombuffer(raw, dtype="<i2").astype(np.float32) / 32768.0
     elif width == 4:
