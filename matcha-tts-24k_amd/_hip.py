@@ -9,7 +9,7 @@ import ctypes as C
 import os
 import subprocess
 from pathlib import Path
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -324,11 +324,29 @@ def check(rc: int) -> None:
         raise RuntimeError("mtts: " + load().mtts_last_error().decode("utf-8", "replace"))
 
 
+def size(n: int) -> int:
+    """A count a ``*_bytes`` / ``*_offset`` entry returned: ``n``, or the library's error raised when it is negative."""
+    if n < 0:
+        check(-1)
+    return n
+
+
+def raise_refused(fn, *args, prefix: str = "") -> None:
+    """Call a ``*_status`` entry -- the one entry of a ragged-batch call that waits for the stream -- and raise ``ValueError`` with the
+    device's verdict (the first refused row) when there is one."""
+    if fn(*args) != 0:
+        raise ValueError(prefix + load().mtts_last_error().decode("utf-8", "replace"))
+
+
+def on_device(t: torch.Tensor) -> bool:
+    return t.is_cuda
+
+
 def ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     """Device pointer of a contiguous HIP tensor (None passes NULL)."""
     if t is None:
         return None
-    if not t.is_cuda:
+    if not on_device(t):
         raise RuntimeError("mtts: tensor is not on a HIP device; the HIP path has no CPU fallback")
     if not t.is_contiguous():
         raise RuntimeError("mtts: tensor must be contiguous")
@@ -339,17 +357,91 @@ def stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+class Workspaces:
+    """GROW-ONLY scratch, one buffer per (kind, stream, device): a serving process sees a new (B, T_pad) with almost every request,
+    so buffers keyed by shape would pin HBM without bound.  The C side takes (pointer, byte count) and bump-allocates what the
+    call needs from the front.  Concurrent calls on different streams must not share scratch, hence the stream key; a buffer being
+    replaced is dropped before its successor is allocated, and its memory stays valid until the work queued on its stream has
+    drained (torch's caching allocator frees a block for re-use in stream order).  ``latest(kind)`` is the buffer of this stream's
+    latest ``kind`` call, whose header the status and flag readers look at."""
+
+    def __init__(self):
+        self._held: Dict[tuple, torch.Tensor] = {}
+        self._latest: Dict[tuple, torch.Tensor] = {}
+
+    def get(self, kind: str, need: int, device) -> torch.Tensor:
+        """This stream's ``kind`` buffer on ``device`` with at least ``need`` bytes (``need`` < 0: the library's error)."""
+        need = size(need)
+        key = (kind, stream_ptr(), torch.device(device))
+        ws = self._held.get(key)
+        if ws is None or ws.numel() < need:
+            if ws is not None and self._latest.get(key[:2]) is ws:
+                del self._latest[key[:2]]
+            ws = None
+            self._held.pop(key, None)
+            ws = self._held[key] = torch.empty(int(need), dtype=torch.uint8, device=key[2])
+        self._latest[key[:2]] = ws
+        return ws
+
+    def latest(self, kind: str) -> Optional[torch.Tensor]:
+        return self._latest.get((kind, stream_ptr()))
+
+    def note(self, kind: str, ws: torch.Tensor) -> None:
+        """Make a caller-owned buffer the latest of this stream (a captured HIP graph runs on its own scratch)."""
+        self._latest[(kind, stream_ptr())] = ws
+
+    def clear(self) -> None:
+        self._held.clear()
+        self._latest.clear()
+
+    def bytes_held(self) -> int:
+        return sum(int(w.numel()) for w in self._held.values())
+
+
+def row_lengths(lengths, B: int, default, device, name: str = "lengths") -> torch.Tensor:
+    """``lengths`` (tensor or sequence; None: ``default`` for every row) as int64 [B] on ``device``.  Nothing is read on the host."""
+    if lengths is None:
+        return torch.full((B,), default, dtype=torch.long, device=device)
+    lengths = torch.as_tensor(lengths).to(device=device, dtype=torch.long).contiguous()
+    if lengths.shape != (B,):
+        raise ValueError(f"{name} must have shape ({B},), got {tuple(lengths.shape)}")
+    return lengths
+
+
+def aligned_rows(t: torch.Tensor, quantum: int, what: str, layout: str = "[B, L]") -> Tuple[torch.Tensor, int]:
+    """``t`` [B, L] (or [L]) on the device as rows of 16-byte aligned quanta: ``(rows [B, ld], L)`` with ld = L rounded up to
+    ``quantum`` elements, zeros beyond L and a 16-byte aligned base; ``t`` itself when it already is that.  ``quantum`` 4: float32
+    samples (other dtypes are converted); 16: uint8 bytes (required)."""
+    raw = quantum == 16
+    if t.dim() == 1:
+        t = t[None]
+    if t.dim() != 2 or (raw and t.dtype != torch.uint8):
+        raise ValueError(f"{what} must be {layout}")
+    if not on_device(t):
+        raise RuntimeError(f"matcha-tts-24k_amd: {what} is not on a HIP device; there is no CPU path")
+    if not raw:
+        t = t.detach().to(torch.float32)
+    B, L = t.shape
+    if B < 1 or L < 1:
+        raise ValueError(f"{what} must have at least one row and one {'byte' if raw else 'sample'}")
+    if L % quantum or not t.is_contiguous() or t.data_ptr() % 16:
+        padded = torch.zeros(B, (L + quantum - 1) // quantum * quantum, dtype=t.dtype, device=t.device)
+        padded[:, :L].copy_(t)
+        t = padded
+    return t, L
+
+
 class DeviceComponent:
     """What the module mirrors of the library's weighted objects other than the path's context share (``vocoder.Vocos``,
     ``style.StyleEncoder``; mixed in ahead of their ``nn.Module`` base): the handle, its weight image on the device, dirty tracking and
     one grow-only workspace per stream.  A subclass gives ``_abi`` (prefix of its ``_create / _set_tensor / _weights_bytes /
     _upload_weights / _destroy`` functions), ``_what`` (its name in error texts), ``_create_args()`` and calls ``_init_component()``
-    at the end of its ``__init__``; ``_tensors()`` is what gets registered (default: the state dict)."""
+    at the end of its ``__init__``; ``_tensors()`` is what gets registered (default: the state dict); ``_ws`` is its ``Workspaces``."""
     _abi = ""
     _what = ""
 
     def _init_component(self):
-        for k, v in (("_ctx", None), ("_weights", None), ("_ws", {}), ("_dirty", True)):
+        for k, v in (("_ctx", None), ("_weights", None), ("_ws", Workspaces()), ("_dirty", True)):
             object.__setattr__(self, k, v)
 
     def _create_args(self):
@@ -382,25 +474,13 @@ class DeviceComponent:
             for k, v in self._tensors().items():
                 a = np.ascontiguousarray(v.detach().to("cpu", torch.float32).numpy())
                 check(getattr(lib, self._abi + "_set_tensor")(self._ctx, k.encode(), a.ctypes.data, a.size))
-            n = getattr(lib, self._abi + "_weights_bytes")(self._ctx)
-            if n < 0:
-                check(-1)
+            n = size(getattr(lib, self._abi + "_weights_bytes")(self._ctx))
             w = torch.empty(n, dtype=torch.uint8, device=p.device)
             check(getattr(lib, self._abi + "_upload_weights")(self._ctx, w.data_ptr(), n))
             object.__setattr__(self, "_weights", w)
             self._ws.clear()
             object.__setattr__(self, "_dirty", False)
         return lib
-
-    def _workspace(self, need: int, device) -> torch.Tensor:
-        key = stream_ptr()                          # one grow-only scratch buffer per stream (see HipModel._workspace)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = None
-            self._ws.pop(key, None)
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-            self._ws[key] = ws
-        return ws
 
     def __del__(self):
         try:
@@ -457,8 +537,7 @@ class HipModel:
         self.uid = HipModel._uids    # unique per process (id() is re-used after garbage collection)
         self.generation = 0          # bumped by every load_state_dict: whatever captured the weights' address is stale afterwards
         self.device: Optional[torch.device] = None
-        self._ws: Dict[tuple, torch.Tensor] = {}
-        self._last_ws: Dict[str, torch.Tensor] = {}     # workspace of the latest call per kind: its first word = range flag
+        self._ws = Workspaces()      # the latest buffer per kind holds that call's header: range flag, pair time-out, verdict
         self._grad_weights: Optional[torch.Tensor] = None   # backward panels of speaker_grad, uploaded on first use ...
         self._grad_generation = -1                          # ... for this weight generation
 
@@ -478,8 +557,7 @@ class HipModel:
     def weights_signature(self) -> str:
         """Everything the packed image's layout depends on (mtts_weights_signature): the key of a packed-image cache."""
         buf = C.create_string_buffer(1024)
-        if self.lib.mtts_weights_signature(self.ctx, buf, 1024) < 0:
-            check(-1)
+        size(self.lib.mtts_weights_signature(self.ctx, buf, 1024))
         return buf.value.decode()
 
     def load_state_dict(self, sd: Dict[str, torch.Tensor], device, cache_dir=None) -> None:
@@ -517,9 +595,7 @@ class HipModel:
                     self.cache_hit = True
                 except RuntimeError:
                     self.cache_hit = False       # (a stale or foreign file: pack from the tensors below and rewrite it)
-        nbytes = self.lib.mtts_weights_bytes(self.ctx)
-        if nbytes < 0:
-            check(-1)
+        nbytes = size(self.lib.mtts_weights_bytes(self.ctx))
         if cache is not None and not self.cache_hit:
             host = np.empty(nbytes, dtype=np.uint8)
             sat = C.c_int(0)
@@ -530,71 +606,48 @@ class HipModel:
         self.device = device
         self.generation += 1
         self._ws.clear()
-        self._last_ws.clear()
 
     def _workspace(self, kind: str, a: int, b: int) -> torch.Tensor:
-        """One GROW-ONLY scratch buffer per (kind, stream): a serving process sees a new (B, T_pad) with almost every request,
-        so buffers keyed by shape would pin HBM without bound.  The C side takes (pointer, byte count) and bump-allocates what
-        the call needs from the front.  Concurrent calls on different streams must not share scratch, hence the stream key;
-        a buffer being replaced stays alive until the work queued on its stream has drained (torch's caching allocator frees
-        a block for re-use in stream order)."""
+        """This stream's scratch of the encoder ("enc") or the estimator ("dec") for a (B, T) call (``Workspaces``)."""
         fn = self.lib.mtts_decoder_workspace_bytes if kind == "dec" else self.lib.mtts_encoder_workspace_bytes
-        n = fn(self.ctx, a, b)
-        if n < 0:
-            check(-1)
-        return self._grow(kind, n)
-
-    def _grow(self, kind: str, n: int) -> torch.Tensor:
-        key = (kind, stream_ptr())
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < n:
-            ws = None
-            self._ws.pop(key, None)
-            ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-            self._ws[key] = ws
-        self._last_ws[key] = ws
-        return ws
+        return self._ws.get(kind, fn(self.ctx, a, b), self.device)
 
     def range_flags(self) -> torch.Tensor:
         """Sticky range flags (include/mtts.h "range guard") of this stream's latest encoder and estimator calls as a device
         int32 tensor [2]; non-zero = an operand left the fp16 range and saturated.  Reading it (``.any().item()``) synchronises."""
         z = torch.zeros(1, dtype=torch.int32, device=self.device)
-        sp = stream_ptr()
-        parts = [self._last_ws[(k, sp)][:4].view(torch.int32) if (k, sp) in self._last_ws else z for k in ("enc", "dec")]
+        parts = [z if ws is None else ws[:4].view(torch.int32) for ws in (self._ws.latest("enc"), self._ws.latest("dec"))]
         return torch.cat(parts)
 
     def pair_timeouts(self) -> torch.Tensor:
         """Second word of this stream's latest estimator workspace header: non-zero = a workgroup of a pair-form chain launch waited in
         vain for its partner (csrc/tblock_chain.hip) -- the call's results are void.  A device int32 tensor [1]."""
-        sp = stream_ptr()
-        if ("dec", sp) not in self._last_ws:
-            return torch.zeros(1, dtype=torch.int32, device=self.device)
-        return self._last_ws[("dec", sp)][4:8].view(torch.int32)
+        ws = self._ws.latest("dec")
+        return torch.zeros(1, dtype=torch.int32, device=self.device) if ws is None else ws[4:8].view(torch.int32)
 
     def call_flags(self, kind: str) -> Optional[torch.Tensor]:
         """The first two header words (range flag, pair time-out) of this stream's latest ``kind`` ("enc" / "dec") workspace as a device
         int32 view, or None when no such call ran: what a caller accumulates over several calls without reading any of them."""
-        ws = self._last_ws.get((kind, stream_ptr()))
+        ws = self._ws.latest(kind)
         return None if ws is None else ws[:8].view(torch.int32)
 
     def weights_saturate(self) -> bool:
-        r = self.lib.mtts_weights_saturate(self.ctx)
-        if r < 0:
-            check(-1)
-        return bool(r)
+        return bool(size(self.lib.mtts_weights_saturate(self.ctx)))
 
     def decoder_workspace_bytes(self, B: int, T: int) -> int:
-        n = self.lib.mtts_decoder_workspace_bytes(self.ctx, int(B), int(T))
-        if n < 0:
-            check(-1)
-        return n
+        return size(self.lib.mtts_decoder_workspace_bytes(self.ctx, int(B), int(T)))
 
     def note_workspace(self, kind: str, ws: torch.Tensor) -> None:
         """Make ``ws`` the buffer ``range_flags`` reads for this stream (a replayed HIP graph ran on it)."""
-        self._last_ws[(kind, stream_ptr())] = ws
+        self._ws.note(kind, ws)
 
     def workspace_bytes_held(self) -> int:
-        return sum(int(w.numel()) for w in self._ws.values())
+        return self._ws.bytes_held()
+
+    def _status(self, kind: str, fn) -> None:
+        ws = self._ws.latest(kind)
+        if ws is not None:
+            raise_refused(fn, ws.data_ptr(), stream_ptr())
 
     def _f32(self, t: torch.Tensor) -> torch.Tensor:
         if not t.is_cuda:
@@ -709,12 +762,7 @@ class HipModel:
         yl = y_lengths.detach().to(device=dev, dtype=torch.int64).contiguous()
         if xl.shape != (B,) or yl.shape != (B,):
             raise ValueError("x_lengths and y_lengths need one entry per utterance")
-        n = self.lib.mtts_mas_workspace_bytes(B, Tx, Tm)
-        if n < 0:
-            check(-1)
-        if self.device is None:
-            self.device = dev
-        ws = self._grow("mas", n)
+        ws = self._ws.get("mas", self.lib.mtts_mas_workspace_bytes(B, Tx, Tm), dev)
         dur = torch.empty(B, Tx, dtype=torch.int32, device=dev)
         score = torch.empty(B, dtype=torch.float32, device=dev)
         path = torch.empty(B, Tx, Tm, dtype=torch.float32, device=dev) if return_path else None
@@ -727,9 +775,7 @@ class HipModel:
     def mas_status(self) -> None:
         """Wait for this stream's latest ``mas`` call and raise ``ValueError`` naming the first utterance whose lengths the
         device refused (mtts_mas_status)."""
-        ws = self._last_ws.get(("mas", stream_ptr()))
-        if ws is not None and self.lib.mtts_mas_status(ws.data_ptr(), stream_ptr()) != 0:
-            raise ValueError(self.lib.mtts_last_error().decode("utf-8", "replace"))
+        self._status("mas", self.lib.mtts_mas_status)
 
     def align_pool(self, mu_x, cum, y_fine_lengths, t_pad: int):
         mu_x = self._f32(mu_x)
@@ -806,12 +852,7 @@ class HipModel:
         yl = y_fine_lengths.detach().to(device=dev, dtype=torch.int64).contiguous()
         if xl.shape != (B,) or yl.shape != (B,):
             raise ValueError("x_lengths and y_fine_lengths need one entry per utterance")
-        n = self.lib.mtts_score_workspace_bytes(B, Tx, Tm)
-        if n < 0:
-            check(-1)
-        if self.device is None:
-            self.device = dev
-        ws = self._grow("score", n)
+        ws = self._ws.get("score", self.lib.mtts_score_workspace_bytes(B, Tx, Tm), dev)
         prior = torch.empty(B, dtype=torch.float32, device=dev)
         dur = torch.empty(B, dtype=torch.float32, device=dev)
         frame = torch.empty(B, Tm, dtype=torch.float32, device=dev) if return_frames else None
@@ -826,9 +867,7 @@ class HipModel:
     def score_status(self) -> None:
         """Wait for this stream's latest ``score_prior_dur`` call and raise ``ValueError`` naming the first utterance the device
         refused (mtts_score_status)."""
-        ws = self._last_ws.get(("score", stream_ptr()))
-        if ws is not None and self.lib.mtts_score_status(ws.data_ptr(), stream_ptr()) != 0:
-            raise ValueError(self.lib.mtts_last_error().decode("utf-8", "replace"))
+        self._status("score", self.lib.mtts_score_status)
 
     def speaker_grad(self, x, x_lengths, e_enc, e_dur, y_fine, y_fine_lengths, delta_prior: float, delta_dur: float, durations=None,
                      check_lengths: bool = True, return_tape: bool = False):
@@ -859,16 +898,11 @@ class HipModel:
             if dur_in.shape != (B, Tx):
                 raise ValueError(f"durations must have shape ({B}, {Tx}), got {tuple(dur_in.shape)}")
         if self._grad_weights is None or self._grad_generation != self.generation:
-            nb = self.lib.mtts_spk_grad_weights_bytes(self.ctx)
-            if nb < 0:
-                check(-1)
+            nb = size(self.lib.mtts_spk_grad_weights_bytes(self.ctx))
             buf = torch.empty(nb, dtype=torch.uint8, device=self.device)
             check(self.lib.mtts_spk_grad_upload_weights(self.ctx, buf.data_ptr(), nb))
             self._grad_weights, self._grad_generation = buf, self.generation
-        n = self.lib.mtts_spk_grad_workspace_bytes(self.ctx, B, Tx, Tm)
-        if n < 0:
-            check(-1)
-        ws = self._grow("spk_grad", n)
+        ws = self._ws.get("spk_grad", self.lib.mtts_spk_grad_workspace_bytes(self.ctx, B, Tx, Tm), self.device)
         g_enc = torch.empty(B, Sd, dtype=torch.float32, device=dev)
         g_dur = torch.empty(B, Sd, dtype=torch.float32, device=dev)
         prior = torch.empty(B, dtype=torch.float32, device=dev)
@@ -882,9 +916,7 @@ class HipModel:
         out = {"g_enc": g_enc, "g_dur": g_dur, "prior_sum": prior, "dur_sum": dsum, "durations": dur_out}
         if return_tape:
             for which, (name, shape) in enumerate((("mu_x", (B, F, Tx)), ("logw", (B, 1, Tx)), ("x_mask", (B, 1, Tx)))):
-                off = self.lib.mtts_spk_grad_tape_offset(self.ctx, B, Tx, Tm, which)
-                if off < 0:
-                    check(-1)
+                off = size(self.lib.mtts_spk_grad_tape_offset(self.ctx, B, Tx, Tm, which))
                 count = B * Tx * (F if which == 0 else 1)
                 out[name] = ws[off:off + 4 * count].view(torch.float32).view(shape)
         return out
@@ -892,16 +924,11 @@ class HipModel:
     def spk_grad_status(self) -> None:
         """Wait for this stream's latest ``speaker_grad`` call and raise ``ValueError`` naming the first utterance the device refused
         (mtts_spk_grad_status)."""
-        ws = self._last_ws.get(("spk_grad", stream_ptr()))
-        if ws is not None and self.lib.mtts_spk_grad_status(ws.data_ptr(), stream_ptr()) != 0:
-            raise ValueError(self.lib.mtts_last_error().decode("utf-8", "replace"))
+        self._status("spk_grad", self.lib.mtts_spk_grad_status)
 
     def fold_rows(self, y_max: int, align: int) -> int:
         """Rows per utterance the folded estimator needs for valid lengths up to y_max (mtts_fold_rows)."""
-        n = self.lib.mtts_fold_rows(self.ctx, int(y_max), int(align))
-        if n < 0:
-            check(-1)
-        return n
+        return size(self.lib.mtts_fold_rows(self.ctx, int(y_max), int(align)))
 
     def cfm_solve(self, x0, mu, mask, t_span, solver: str, add_mu: bool = False, t_out: Optional[int] = None,
                   out_scale: float = 1.0, out_shift: float = 0.0, y_lengths=None, y_max: Optional[int] = None,
@@ -921,7 +948,7 @@ class HipModel:
             if ws is None:
                 ws = self._workspace("dec", B, int(t_fold))
             else:
-                self._last_ws[("dec", stream_ptr())] = ws
+                self._ws.note("dec", ws)
             check(self.lib.mtts_cfm_solve_folded(self.ctx, ptr(x0), ptr(mu), ptr(y_lengths), int(y_max), int(bool(add_mu)),
                                                  ts.ctypes.data, len(ts) - 1, SOLVERS[solver], B, T, int(t_fold), ptr(out), t_out,
                                                  float(out_scale), float(out_shift), ws.data_ptr(), ws.numel(), stream_ptr()))
@@ -966,7 +993,7 @@ class HipModel:
         if ws is None:
             ws = self._workspace("dec", B, int(t_fold))
         else:
-            self._last_ws[("dec", stream_ptr())] = ws
+            self._ws.note("dec", ws)
         check(self.lib.mtts_cfm_step(self.ctx, ptr(z_pool), ptr(mu_pool), S, T_cap, ptr(slots_dev), h_slots.ctypes.data, ptr(t0), ptr(t1),
                                      ptr(y_lengths), int(y_max), SOLVERS[solver], B, int(t_fold), ws.data_ptr(), ws.numel(), stream_ptr()))
 
@@ -989,17 +1016,13 @@ class HipModel:
     def prof_records(self, max_records: int = 1 << 16):
         """[(class, ms, flops, bytes)] per launch of the event pass, in launch order."""
         buf = (C.c_double * (4 * max_records))()
-        n = self.lib.mtts_prof_records(self.ctx, buf, max_records)
-        if n < 0:
-            check(-1)
+        n = size(self.lib.mtts_prof_records(self.ctx, buf, max_records))
         return [(int(buf[4 * i]), buf[4 * i + 1], buf[4 * i + 2], buf[4 * i + 3]) for i in range(n)]
 
     def prof_tags(self, max_bytes: int = 1 << 24):
         """Kernel instantiation name of each record of ``prof_records`` ("-" where the launcher does not tag)."""
         buf = C.create_string_buffer(max_bytes)
-        n = self.lib.mtts_prof_tags(self.ctx, buf, max_bytes)
-        if n < 0:
-            check(-1)
+        n = size(self.lib.mtts_prof_tags(self.ctx, buf, max_bytes))
         return buf.value.decode().split("\n")[:n]
 
 
@@ -1215,9 +1238,7 @@ def _gemm_block(run, scratch_fn, a, w, bias, *, B, T_in, T_out, tap_off, in_stri
     g.force_bm, g.half16, g.bf16 = force_bm, int(bool(half16)), int(bool(bf16))
     flag = _flag(dev)
     g.d_range_flag = ptr(flag)
-    n = getattr(lib, scratch_fn)(C.byref(g))
-    if n < 0:
-        check(-1)
+    n = size(getattr(lib, scratch_fn)(C.byref(g)))
     scratch = torch.empty(n, dtype=torch.uint8, device=dev)
     check(run(lib, g, scratch.data_ptr()))
     return {"out": out, "out16": out16, "stats": stats, "gn_stats": gn_stats, "wave_rows": g.wave_rows, "tag": g.tag.decode(),
@@ -1242,9 +1263,7 @@ def groupnorm_mish_h16(y, gamma, beta, mask, B, T, *, G=8, chbias=None, tile_sta
     chbias [B, stride >= C] or [C].  Returns a dict: out (fp32 rows), out16 (the image widened), flag."""
     lib = load()
     Cc = y.shape[1]
-    n = lib.mtts_groupnorm_h16_scratch_bytes(B, T, Cc, G)
-    if n < 0:
-        check(-1)
+    n = size(lib.mtts_groupnorm_h16_scratch_bytes(B, T, Cc, G))
     scratch = torch.empty(n, dtype=torch.uint8, device=y.device)
     out = torch.empty_like(y) if want_f32 else None
     out16 = torch.empty_like(y)
@@ -1307,9 +1326,7 @@ def groupnorm_mish_p16(y, gamma, beta, mask, B, T, *, G=8, chbias=None, tile_sta
     chbias [B, stride >= C] or [C].  Returns a dict: out (fp32 rows), out16 (the image decoded), flag."""
     lib = load()
     Cc = y.shape[1]
-    n = lib.mtts_groupnorm_p16_scratch_bytes(B, T, Cc, G)
-    if n < 0:
-        check(-1)
+    n = size(lib.mtts_groupnorm_p16_scratch_bytes(B, T, Cc, G))
     scratch = torch.empty(n, dtype=torch.uint8, device=y.device)
     out = torch.empty_like(y) if want_f32 else None
     out16 = torch.empty_like(y)

@@ -86,17 +86,7 @@ class Encoded:
 
 
 def _status(lib, verdict: torch.Tensor) -> None:
-    if lib.mtts_pcm_status(_hip.ptr(verdict), verdict.numel(), _hip.stream_ptr()) != 0:
-        raise ValueError(lib.mtts_last_error().decode("utf-8", "replace"))
-
-
-def _lengths(lengths, B: int, full: int, device) -> torch.Tensor:
-    if lengths is None:
-        return torch.full((B,), full, dtype=torch.long, device=device)
-    lengths = torch.as_tensor(lengths).to(device=device, dtype=torch.long).contiguous()
-    if lengths.shape != (B,):
-        raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
-    return lengths
+    _hip.raise_refused(lib.mtts_pcm_status, _hip.ptr(verdict), verdict.numel(), _hip.stream_ptr())
 
 
 @torch.inference_mode()
@@ -112,23 +102,9 @@ def encode(audio: torch.Tensor, lengths, formats, dither=False, seed: int = 0, k
     launches then, each over its rows); ``seed`` per call and ``keys`` (int64 per row, default 0) select the sequence, which is a
     function of (seed, key, sample index) only: a row's bytes do not depend on the batch it is in."""
     lib = _hip.load()
-    if audio.dim() == 1:
-        audio = audio[None]
-    if audio.dim() != 2:
-        raise ValueError("audio must be [B, L]")
-    if not audio.is_cuda:
-        raise RuntimeError("matcha-tts-24k_amd: audio is not on a HIP device; there is no CPU path")
-    audio = audio.detach().to(torch.float32)
-    B, L = audio.shape
-    if B < 1 or L < 1:
-        raise ValueError("audio must have at least one row and one sample")
-    dev = audio.device
-    if L % 4 or not audio.is_contiguous() or audio.data_ptr() % 16:          # rows of 16-byte aligned quads
-        padded = torch.zeros(B, (L + 3) // 4 * 4, dtype=torch.float32, device=dev)
-        padded[:, :L].copy_(audio)
-        audio = padded
-    ld = audio.shape[1]
-    lengths = _lengths(lengths, B, L, dev)
+    audio, L = _hip.aligned_rows(audio, 4, "audio")
+    (B, ld), dev = audio.shape, audio.device
+    lengths = _hip.row_lengths(lengths, B, L, dev)
     if torch.is_tensor(formats) and formats.is_cuda:
         fmt = formats.to(torch.int32).contiguous()
         if fmt.shape != (B,):
@@ -176,23 +152,10 @@ def decode(data: torch.Tensor, lengths, formats, check: bool = True, ld: int = N
     ``/ 32768``, G.711 codes as their linear value ``/ 32768``, zeros from a row's length on.  ``check`` waits for the device's verdict
     on the lengths and raises ``ValueError`` naming the first refused row (a length whose bytes exceed the row)."""
     lib = _hip.load()
-    if data.dim() == 1:
-        data = data[None]
-    if data.dim() != 2 or data.dtype != torch.uint8:
-        raise ValueError("data must be a uint8 [B, ld_bytes] tensor")
-    if not data.is_cuda:
-        raise RuntimeError("matcha-tts-24k_amd: data is not on a HIP device; there is no CPU path")
-    B, nb = data.shape
-    if B < 1 or nb < 1:
-        raise ValueError("data must have at least one row and one byte")
-    dev = data.device
-    if nb % 16 or not data.is_contiguous() or data.data_ptr() % 16:
-        padded = torch.zeros(B, (nb + 15) // 16 * 16, dtype=torch.uint8, device=dev)
-        padded[:, :nb].copy_(data)
-        data = padded
-    ld_bytes = data.shape[1]
+    data, _ = _hip.aligned_rows(data, 16, "data", "a uint8 [B, ld_bytes] tensor")
+    (B, ld_bytes), dev = data.shape, data.device
     fmt = torch.tensor(formats_per_row(formats, B), dtype=torch.int32, device=dev)
-    lengths = _lengths(lengths, B, 0, dev)
+    lengths = _hip.row_lengths(lengths, B, 0, dev)
     ld = ld_bytes if ld is None else max(4, (int(ld) + 3) // 4 * 4)
     out = torch.zeros(B, ld, dtype=torch.float32, device=dev)
     out_lengths = torch.empty(B, dtype=torch.long, device=dev)

@@ -22,7 +22,7 @@ import torch
 from . import _hip
 
 COLUMNS = ("content_start", "content_end", "leading_eff", "leading_abs", "trailing_eff", "trailing_abs")
-_ws: Dict[Tuple[str, int, str], torch.Tensor] = {}
+_ws = _hip.Workspaces()
 
 
 def window(sample_rate: int) -> int:
@@ -42,17 +42,6 @@ def target_samples(seconds: Optional[float], sample_rate: int, label: str = "lea
     return n
 
 
-def _workspace(kind: str, need: int, device) -> torch.Tensor:
-    if need < 0:
-        _hip.check(-1)
-    key = (kind, _hip.stream_ptr(), str(device))
-    ws = _ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(int(need), dtype=torch.uint8, device=device)
-        _ws[key] = ws
-    return ws
-
-
 def _batch(audio, lengths=None, device=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Clips -> ``(wave [B, ld] fp32 on the device with ld % 4 == 0, lengths int64 [B] on the device)``.  ``audio``: a list of
     1-D waveforms (``lengths``: samples to use of each, default all) or a padded batch [B, L] (or [L]) with ``lengths`` (tensor or
@@ -60,22 +49,11 @@ def _batch(audio, lengths=None, device=None) -> Tuple[torch.Tensor, torch.Tensor
     device); device lengths are not read on the host."""
     if torch.is_tensor(audio) or isinstance(audio, np.ndarray):
         audio = torch.as_tensor(audio)
-        if audio.dim() == 1:
-            audio = audio[None]
-        if audio.dim() != 2:
+        if audio.dim() not in (1, 2):
             raise ValueError("audio must be [B, L] or a list of 1-D clips")
         if device is not None or not audio.is_cuda:
             audio = audio.to(device if device is not None else torch.device("cuda"))
-        wave = audio.detach().to(torch.float32)
-        B, L = wave.shape
-        if B < 1 or L < 1:
-            raise ValueError("audio must have at least one row and one sample")
-        if L % 4 or not wave.is_contiguous() or wave.data_ptr() % 16:
-            padded = torch.zeros(B, (L + 3) // 4 * 4, dtype=torch.float32, device=wave.device)
-            padded[:, :L].copy_(wave)
-            wave = padded
-        if lengths is None:
-            lengths = torch.full((B,), L, dtype=torch.long, device=wave.device)
+        wave, full = _hip.aligned_rows(audio, 4, "audio")
     else:
         clips = [torch.as_tensor(c) for c in audio]
         if len(clips) == 0:
@@ -84,16 +62,13 @@ def _batch(audio, lengths=None, device=None) -> Tuple[torch.Tensor, torch.Tensor
             raise ValueError("a clip is a 1-D waveform (mono)")
         if device is None:
             device = next((c.device for c in clips if c.is_cuda), torch.device("cuda"))
-        B = len(clips)
+        B, full = len(clips), None
         if lengths is None:
             lengths = [int(c.numel()) for c in clips]
         wave = torch.zeros(B, max(4, (max(int(c.numel()) for c in clips) + 3) // 4 * 4), dtype=torch.float32, device=device)
         for b, c in enumerate(clips):
             wave[b, :c.numel()].copy_(c.to(torch.float32))
-    lengths = torch.as_tensor(lengths).to(device=wave.device, dtype=torch.long).contiguous()
-    if lengths.shape != (wave.shape[0],):
-        raise ValueError(f"lengths must have shape ({wave.shape[0]},), got {tuple(lengths.shape)}")
-    return wave, lengths
+    return wave, _hip.row_lengths(lengths, wave.shape[0], full, wave.device)
 
 
 def _seconds(samples: torch.Tensor, sample_rate: int) -> torch.Tensor:
@@ -103,15 +78,14 @@ def _seconds(samples: torch.Tensor, sample_rate: int) -> torch.Tensor:
 
 
 def _status(fn, ws) -> None:
-    if fn(ws.data_ptr(), _hip.stream_ptr()) != 0:
-        raise ValueError(_hip.load().mtts_last_error().decode("utf-8", "replace"))
+    _hip.raise_refused(fn, ws.data_ptr(), _hip.stream_ptr())
 
 
 def _measure(wave: torch.Tensor, lengths: torch.Tensor, sample_rate: int, effective_db: float, absolute_db: float):
     lib = _hip.load()
     B, ld = wave.shape
     out = torch.empty(B, 6, dtype=torch.long, device=wave.device)
-    ws = _workspace("silence", lib.mtts_silence_workspace_bytes(ld, B, int(sample_rate)), wave.device)
+    ws = _ws.get("silence", lib.mtts_silence_workspace_bytes(ld, B, int(sample_rate)), wave.device)
     with torch.cuda.device(wave.device):
         _hip.check(lib.mtts_silence_measure(_hip.ptr(wave), ld, _hip.ptr(lengths), B, int(sample_rate), float(effective_db), float(absolute_db),
                                             _hip.ptr(out), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
@@ -185,15 +159,11 @@ def mel_sums(mel: torch.Tensor, mel_lengths=None, check: bool = True) -> Dict[st
     B, F, T = mel.shape
     if B < 1 or F < 1 or T < 1:
         raise ValueError("mel must have at least one clip, one band and one frame")
-    if mel_lengths is None:
-        mel_lengths = torch.full((B,), T, dtype=torch.long, device=mel.device)
-    d_len = torch.as_tensor(mel_lengths).to(device=mel.device, dtype=torch.long).contiguous()
-    if d_len.shape != (B,):
-        raise ValueError(f"mel_lengths must have shape ({B},), got {tuple(d_len.shape)}")
+    d_len = _hip.row_lengths(mel_lengths, B, T, mel.device, "mel_lengths")
     sums = torch.empty(B, 2, dtype=torch.float64, device=mel.device)
     frames = torch.empty(B, dtype=torch.long, device=mel.device)
     flags = torch.empty(B, dtype=torch.int32, device=mel.device)
-    ws = _workspace("mel_stats", lib.mtts_mel_stats_workspace_bytes(B, T), mel.device)
+    ws = _ws.get("mel_stats", lib.mtts_mel_stats_workspace_bytes(B, T), mel.device)
     with torch.cuda.device(mel.device):
         _hip.check(lib.mtts_mel_stats(_hip.ptr(mel), F, T, _hip.ptr(d_len), B, _hip.ptr(sums), _hip.ptr(frames), _hip.ptr(flags),
                                       ws.data_ptr(), ws.numel(), _hip.stream_ptr()))

@@ -251,9 +251,7 @@ int mtts_pcm_encode(const float* d_audio, int64_t ld, const int64_t* d_lengths, 
     a.dither = dither ? 1 : 0;
     const unsigned tiles = (unsigned)((ld + CODEC_TILE - 1) / CODEC_TILE);
     hipLaunchKernelGGL(pcm_encode_kernel, dim3(tiles, B), dim3(CODEC_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("pcm_encode_kernel: ") + hipGetErrorString(e)); return -1; }
-    return 0;
+    return launched("pcm_encode_kernel");
 }
 
 int mtts_pcm_decode(const uint8_t* d_data, int64_t ld_bytes, const int64_t* d_lengths, const int32_t* d_formats, int B,
@@ -276,19 +274,14 @@ int mtts_pcm_decode(const uint8_t* d_data, int64_t ld_bytes, const int64_t* d_le
     a.data = d_data; a.lengths = d_lengths; a.formats = d_formats; a.ld_bytes = ld_bytes; a.ld = ld; a.out = d_out; a.out_lengths = d_out_lengths;
     const unsigned tiles = (unsigned)((ld + CODEC_TILE - 1) / CODEC_TILE);
     hipLaunchKernelGGL(pcm_decode_kernel, dim3(tiles, B), dim3(CODEC_THREADS), 0, static_cast<hipStream_t>(stream), a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("pcm_decode_kernel: ") + hipGetErrorString(e)); return -1; }
-    return 0;
+    return launched("pcm_decode_kernel");
 }
 
 // The verdict of a call: its d_out_bytes / d_out_lengths.  The one entry of this file that waits for the stream.
 int mtts_pcm_status(const int64_t* d_verdict, int B, void* stream) {
     if (!d_verdict || B < 1 || B > 65535) { set_error("mtts_pcm_status: bad argument"); return -1; }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    std::vector<int64_t> v((size_t)B, 0);
-    hipError_t e = hipMemcpyAsync(v.data(), d_verdict, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { set_error(std::string("mtts_pcm_status: ") + hipGetErrorString(e)); return -1; }
+    std::vector<int64_t> v((size_t)B);
+    if (read_status("mtts_pcm_status", d_verdict, stream, v.data(), B)) return -1;
     for (int b = 0; b < B; ++b)
         if (v[b] < 0) {
             set_error("mtts_pcm_encode / mtts_pcm_decode: row " + std::to_string(b) + " was refused (a length outside its row, "

@@ -13,6 +13,7 @@
 // squares summed in fp64 as lane-strided partials and an xor-shuffle tree, so two runs give the same bits and a clip's numbers
 // do not depend on its batch.  Lengths are read on the device only; nothing is read outside [0, len_b) of a row.
 #include "host.h"
+#include "device_utils.h"
 
 #include <cfloat>
 
@@ -37,22 +38,13 @@ __device__ __forceinline__ int corpus_max_i(int v) {
     return v;
 }
 
-// The verdict on every row, by one workgroup of 256 threads and without atomics on memory: status[0] = first refused row + 1.
-template <class Refused, class Length>
-__device__ __forceinline__ void corpus_verdict(int B, int64_t* status, int64_t s2, int64_t s3, int64_t entry, Refused refused, Length length) {
-    __shared__ int first_bad;
-    const int tid = threadIdx.x;
-    if (tid == 0) first_bad = B;
-    __syncthreads();
-    int mine = B;
-    for (int i = B - 1 - tid; i >= 0; i -= (int)blockDim.x)
-        if (refused(i)) mine = i;
-    if (mine < B) atomicMin(&first_bad, mine);
-    __syncthreads();
-    if (tid == 0) {
-        const int i = first_bad;
+// The verdict on every row, by one workgroup: status[0] = first refused row + 1, [1] its length, [4] the entry that ran.
+template <class Refused>
+__device__ __forceinline__ void corpus_verdict(int B, const int64_t* lengths, int64_t* status, int64_t s2, int64_t s3, int64_t entry, Refused refused) {
+    const int i = first_refused_row(B, refused);
+    if (threadIdx.x == 0) {
         status[0] = i < B ? i + 1 : 0;
-        status[1] = i < B ? length(i) : 0;
+        status[1] = i < B ? lengths[i] : 0;
         status[2] = s2;
         status[3] = s3;
         status[4] = entry;
@@ -105,8 +97,7 @@ __global__ __launch_bounds__(256) void sil_scan_kernel(const SilenceMeasureArgs 
     __shared__ int part[4][6];
     const int b = blockIdx.x, tid = threadIdx.x;
     if (b == 0)
-        corpus_verdict(p.B, p.status, p.ld, 0, 1, [&](int i) { const int64_t n = p.lengths[i]; return n < 0 || n > p.ld; },
-                       [&](int i) { return p.lengths[i]; });
+        corpus_verdict(p.B, p.lengths, p.status, p.ld, 0, 1, [&](int i) { const int64_t n = p.lengths[i]; return n < 0 || n > p.ld; });
     const int64_t L = p.lengths[b];
     int64_t* o = p.out + (size_t)b * 6;
     if (L < 0 || L > p.ld) {
@@ -188,8 +179,7 @@ __device__ __forceinline__ NormPlan norm_plan(const SilenceNormArgs& a, int b) {
 __global__ __launch_bounds__(256) void sil_norm_kernel(const SilenceNormArgs a) {
     const int b = blockIdx.y, tid = threadIdx.x;
     if (blockIdx.x == 0 && b == 0)
-        corpus_verdict(a.B, a.status, a.ld_in, a.ld_out, 2, [&](int i) { return norm_plan(a, i).out_len < 0; },
-                       [&](int i) { return a.lengths[i]; });
+        corpus_verdict(a.B, a.lengths, a.status, a.ld_in, a.ld_out, 2, [&](int i) { return norm_plan(a, i).out_len < 0; });
     const NormPlan p = norm_plan(a, b);
     if (blockIdx.x == 0 && tid == 0) {
         a.out_lengths[b] = p.out_len;
@@ -263,8 +253,7 @@ __global__ __launch_bounds__(MEL_STATS_CHUNK) void mel_part_kernel(const MelStat
 // The chunks of a clip in ascending order, by one thread
 __global__ __launch_bounds__(256) void mel_total_kernel(const MelStatsArgs a) {
     if (blockIdx.x == 0)
-        corpus_verdict(a.B, a.status, a.T, 0, 3, [&](int i) { const int64_t n = a.lengths[i]; return n < 0 || n > a.T; },
-                       [&](int i) { return a.lengths[i]; });
+        corpus_verdict(a.B, a.lengths, a.status, a.T, 0, 3, [&](int i) { const int64_t n = a.lengths[i]; return n < 0 || n > a.T; });
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= a.B) return;
     const int64_t len = a.lengths[b];
@@ -302,12 +291,8 @@ static int corpus_window(int sample_rate) { return (int)(0.01 * (double)sample_r
 
 // The verdict of a call's lengths check (the header of its workspace); the caller names the entry that ran
 static int corpus_status(const char* who, const void* d_ws, void* stream) {
-    if (!d_ws) { set_error(std::string(who) + ": null workspace"); return -1; }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int64_t st[5] = {0, 0, 0, 0, 0};
-    hipError_t e = hipMemcpyAsync(st, d_ws, sizeof(st), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { set_error(std::string(who) + ": " + hipGetErrorString(e)); return -1; }
+    int64_t st[5];
+    if (read_status(who, d_ws, stream, st)) return -1;
     if (st[0] == 0) return 0;
     const std::string row = "row " + std::to_string(st[0] - 1) + " has length " + std::to_string(st[1]);
     if (st[4] == 1) set_error("mtts_silence_measure: " + row + " (need 0 <= length <= ld = " + std::to_string(st[2]) + ")");

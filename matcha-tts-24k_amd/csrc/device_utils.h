@@ -103,5 +103,24 @@ __device__ __forceinline__ float allreduce8(float v) {
     return v;
 }
 
+// ---- the ragged-batch contract: the verdict on every row of a batch, by one workgroup.
+// Returns the smallest i in [0, B) with refused(i), or B when there is none, to every thread: each thread scans its stride of
+// rows keeping its smallest find, then one LDS atomicMin per thread that found one -- no atomics on memory, and the answer does
+// not depend on the order the threads arrive in.  Uses blockDim.x threads and one LDS word.
+// PRECONDITION: every thread of the workgroup calls it, under a workgroup-uniform condition (it holds two barriers).
+template <class Refused>
+__device__ __forceinline__ int first_refused_row(int B, Refused refused) {
+    __shared__ int first;
+    if (threadIdx.x == 0) first = B;
+    __syncthreads();
+    int mine = B;
+    for (int i = B - 1 - (int)threadIdx.x; i >= 0; i -= (int)blockDim.x)
+        if (refused(i)) mine = i;
+    if (mine < B) atomicMin(&first, mine);
+    __syncthreads();
+    return first;
+}
+// a 64-bit length as a 32-bit report word, saturated symmetrically
+__device__ __forceinline__ int sat32(int64_t v) { return (int)max(min(v, (int64_t)0x7fffffff), -(int64_t)0x7fffffff); }
 
 }  // namespace mtts

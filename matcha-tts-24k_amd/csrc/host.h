@@ -1,5 +1,6 @@
 // What the host translation units share (model.hip, pack.hip, decoder.hip, encoder.hip, the host halves of vocos.hip,
-// waveform.hip and style_encoder.hip, unit_entries.hip): error and launch macros, the profiling wrappers around a launch, the
+// waveform.hip and style_encoder.hip, the ragged-batch entries, unit_entries.hip): error and launch macros, the launch check and
+// the status reader of the ragged-batch contract, the profiling wrappers around a launch, the
 // workspace carver, the packer's declaration and the weight life cycle of a component.  model.h is the data model, kernels.h the
 // kernel interface; nothing here is visible outside csrc/.
 #pragma once
@@ -23,6 +24,27 @@ namespace mtts {
         int _r = (expr);      \
         if (_r) return _r;    \
     } while (0)
+
+// ------------------------------------------------------------------------------------------------ the ragged-batch contract
+// After a launch (or any call that returns a hipError_t): 0, or -1 with the error "<what>: <hip error string>".  (Both helpers
+// are static: they add nothing to the symbols the library exports.)
+static inline int launched(const char* what, hipError_t e = hipGetLastError()) {
+    if (e == hipSuccess) return 0;
+    set_error(std::string(what) + ": " + hipGetErrorString(e));
+    return -1;
+}
+// What every *_status entry does before it words its verdict: n header words of the call's workspace to the host.  The one place
+// that waits for the stream.  `who` is the entry's name in the error texts.
+template <class T>
+static int read_status(const char* who, const void* d_ws, void* stream, T* words, size_t n) {
+    if (!d_ws) { set_error(std::string(who) + ": null workspace"); return -1; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemcpyAsync(words, d_ws, n * sizeof(T), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return launched(who, e);
+}
+template <class T, size_t N>
+static int read_status(const char* who, const void* d_ws, void* stream, T (&words)[N]) { return read_status(who, d_ws, stream, words, N); }
 
 // ------------------------------------------------------------------------------------------------ profiling wrappers
 inline int prof_begin(Component* c, int klass, double flops, double bytes, hipStream_t s) {

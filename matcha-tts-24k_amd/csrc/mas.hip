@@ -39,7 +39,7 @@
 // The lengths live on the device.  A bad utterance (Tx_b < 1, Tx_b > Tx, Tm_b > Tm, Tm_b < Tx_b) is found by the kernels: its
 // outputs are zeroed, the others are untouched, and the first such utterance is reported in the workspace header
 // (mtts_mas_status).  Lengths are clamped before they index anything.
-#include "model.h"
+#include "host.h"
 #include "device_utils.h"
 
 #include <string>
@@ -210,21 +210,12 @@ template <int K>
 __global__ __launch_bounds__(64) void mas_forward_kernel(MasArgs a) {
     constexpr int D = 64 / K;                  // frames per block
     const int b = blockIdx.x, lane = threadIdx.x;
-    if (b == 0) {                              // the verdict on every utterance's lengths, by one wave, without atomics on memory
-        __shared__ int first;
-        if (lane == 0) first = a.B;
-        __syncthreads();
-        int mine = a.B;
-        for (int i = a.B - 1 - lane; i >= 0; i -= 64)
-            if (mas_bad(a.x_len[i], a.y_len[i], a.Tx, a.Tm)) mine = i;
-        if (mine < a.B) atomicMin(&first, mine);
-        __syncthreads();
+    if (b == 0) {                              // the verdict on every utterance's lengths, by one wave
+        const int i = first_refused_row(a.B, [&](int r) { return mas_bad(a.x_len[r], a.y_len[r], a.Tx, a.Tm); });
         if (lane == 0) {
-            const int i = first;
             a.status[0] = i < a.B ? i + 1 : 0;
-            const int64_t lim = 0x7fffffff;       // (the report holds 32-bit words)
-            a.status[1] = i < a.B ? (int)max(min(a.x_len[i], lim), -lim) : 0;
-            a.status[2] = i < a.B ? (int)max(min(a.y_len[i], lim), -lim) : 0;
+            a.status[1] = i < a.B ? sat32(a.x_len[i]) : 0;
+            a.status[2] = i < a.B ? sat32(a.y_len[i]) : 0;
             a.status[3] = a.Tx;
             a.status[4] = a.Tm;
         }
@@ -351,11 +342,6 @@ static bool mas_shape_ok(const char* who, int B, int Tx, int Tm) {
     if ((int64_t)B * Tm * 1024 > ((int64_t)1 << 40) || Tm > (1 << 24)) { set_error(std::string(who) + ": batch too large"); return false; }
     return true;
 }
-static int mas_launched(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string(what) + ": " + hipGetErrorString(e)); return -1; }
-    return 0;
-}
 template <int K>
 static void mas_search(const MasArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(mas_forward_kernel<K>, dim3(a.B), dim3(64), 0, s, a);
@@ -380,7 +366,7 @@ int mtts_mas_logprior(const float* d_mu_x, const float* d_y, const int64_t* d_x_
     if (!mas_shape_ok("mtts_mas_logprior", B, Tx, Tm)) return -1;
     hipLaunchKernelGGL(mas_logprior_kernel<false>, dim3((Tm + 63) / 64, (Tx + 63) / 64, B), dim3(256), 0, static_cast<hipStream_t>(stream),
                        d_mu_x, d_y, d_x_lengths, d_y_lengths, F, Tx, Tm, d_lp, 0);
-    return mas_launched("mas_logprior_kernel");
+    return launched("mas_logprior_kernel");
 }
 
 int mtts_mas(const float* d_lp, const float* d_mu_x, const float* d_y, const int64_t* d_x_lengths, const int64_t* d_y_lengths, int B, int F,
@@ -398,11 +384,11 @@ int mtts_mas(const float* d_lp, const float* d_mu_x, const float* d_y, const int
     if (d_lp) {
         hipLaunchKernelGGL(mas_transpose_kernel, dim3((Tm + 31) / 32, p.ldx / 32, B), dim3(256), 0, s, d_lp, d_x_lengths, d_y_lengths, Tx, Tm,
                            p.ldx, lpT);
-        if (mas_launched("mas_transpose_kernel")) return -1;
+        if (launched("mas_transpose_kernel")) return -1;
     } else {
         hipLaunchKernelGGL(mas_logprior_kernel<true>, dim3((Tm + 63) / 64, p.ldx / 64, B), dim3(256), 0, s, d_mu_x, d_y, d_x_lengths,
                            d_y_lengths, F, Tx, Tm, lpT, p.ldx);
-        if (mas_launched("mas_logprior_kernel")) return -1;
+        if (launched("mas_logprior_kernel")) return -1;
     }
     MasArgs a;
     a.lpT = lpT; a.x_len = d_x_lengths; a.y_len = d_y_lengths;
@@ -417,22 +403,18 @@ int mtts_mas(const float* d_lp, const float* d_mu_x, const float* d_y, const int
         case 8: mas_search<8>(a, s); break;
         default: mas_search<16>(a, s); break;
     }
-    if (mas_launched("mas_forward_kernel / mas_backtrack_kernel")) return -1;
+    if (launched("mas_forward_kernel / mas_backtrack_kernel")) return -1;
     if (d_path) {
         hipLaunchKernelGGL(mas_path_kernel, dim3((Tm + 255) / 256, Tx, B), dim3(256), 0, s, a.start, Tx, Tm, d_path);
-        if (mas_launched("mas_path_kernel")) return -1;
+        if (launched("mas_path_kernel")) return -1;
     }
     return 0;
 }
 
 // The lengths check's verdict (the header of the call's workspace).  The one entry of this file that waits for the stream.
 int mtts_mas_status(const void* d_ws, void* stream) {
-    if (!d_ws) { set_error("mtts_mas_status: null workspace"); return -1; }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int st[5] = {0, 0, 0, 0, 0};
-    hipError_t e = hipMemcpyAsync(st, d_ws, sizeof(st), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { set_error(std::string("mtts_mas_status: ") + hipGetErrorString(e)); return -1; }
+    int st[5];
+    if (read_status("mtts_mas_status", d_ws, stream, st)) return -1;
     if (st[0] != 0) {
         set_error("mtts_mas: utterance " + std::to_string(st[0] - 1) + " has x_length = " + std::to_string(st[1]) + ", y_length = " +
                   std::to_string(st[2]) + " (need 1 <= x_length <= Tx = " + std::to_string(st[3]) + " and x_length <= y_length <= Tm = " +

@@ -23,7 +23,7 @@
 //                       goes through LDS (odd row stride), so both the global reads (along bins) and writes (along time) coalesce.
 // Every sum runs in a fixed order over one row's own data: a clip's rows do not depend on its batch (ragged batch == batch of one,
 // bit for bit).
-#include "model.h"
+#include "host.h"
 #include "device_utils.h"
 
 #include <cmath>
@@ -388,21 +388,17 @@ int mtts_melfe_forward(mtts_melfe* m, const float* d_audio, int64_t ld, const in
     a.w16 = m->d_w16; a.Np = m->Np; a.mag = static_cast<float*>(d_ws); a.nbp = m->nbp;
     const int grid = ((M + MEL_BM - 1) / MEL_BM) * (m->Np / GEMM_BN);
     hipLaunchKernelGGL(mel_dft_kernel, dim3(grid), dim3(256), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("mel_dft_kernel: ") + hipGetErrorString(e)); return -1; }
+    if (launched("mel_dft_kernel")) return -1;
     MelFbArgs f;
     f.mag = a.mag; f.lengths = d_lengths; f.ld = ld; f.B = B; f.T_max = T_max; f.hop = hop; f.n_fft = m->n_fft; f.nbp = m->nbp;
     f.n_mels = m->n_mels; f.fb_lo = m->d_lo; f.fb_off = m->d_off; f.fb_w = m->d_w; f.mel_mean = mel_mean; f.mel_std = mel_std;
     f.mel = d_mel; f.mel_lengths = d_mel_lengths;
     const size_t lds = (size_t)MEL_FB_ROWS * (m->nbp + 1) * sizeof(float);      // <= 16 * 1057 * 4 = 67,648 B at n_fft 2048
-    if (lds > 48 * 1024) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(mel_filterbank_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_error(std::string("mel_filterbank_kernel: ") + hipGetErrorString(e)); return -1; }
-    }
+    if (lds > 48 * 1024 &&
+        launched("mel_filterbank_kernel", hipFuncSetAttribute(reinterpret_cast<const void*>(mel_filterbank_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)))
+        return -1;
     hipLaunchKernelGGL(mel_filterbank_kernel, dim3((T_max + MEL_FB_ROWS - 1) / MEL_FB_ROWS, B), dim3(256), lds, s, f);
-    e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("mel_filterbank_kernel: ") + hipGetErrorString(e)); return -1; }
-    return 0;
+    return launched("mel_filterbank_kernel");
 }
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 //   * the results cross LDS once so that every lane stores 16 bytes; a row is written whole, zeros from out_len to ld_out.
 // No atomics on memory, no scratch.  A clip's samples do not depend on the batch it is in.
 #include "host.h"
+#include "device_utils.h"
 
 #include <cmath>
 #include <cstring>
@@ -62,17 +63,9 @@ __global__ __launch_bounds__(RS_THREADS) void resample_kernel(const ResampleArgs
     const int b = blockIdx.y;
     const int64_t j0 = (int64_t)blockIdx.x * RS_TILE;
 
-    if (blockIdx.x == 0 && b == 0) {             // the verdict on every row's length, by one workgroup, no atomics on memory
-        __shared__ int first_bad;
-        if (tid == 0) first_bad = a.B;
-        __syncthreads();
-        int mine = a.B;
-        for (int i = a.B - 1 - tid; i >= 0; i -= RS_THREADS)
-            if (rs_out_len(a.lengths[i], a) < 0) mine = i;
-        if (mine < a.B) atomicMin(&first_bad, mine);
-        __syncthreads();
+    if (blockIdx.x == 0 && b == 0) {             // the verdict on every row's length, by one workgroup
+        const int i = first_refused_row(a.B, [&](int r) { return rs_out_len(a.lengths[r], a) < 0; });
         if (tid == 0) {
-            const int i = first_bad;
             a.status[0] = i < a.B ? i + 1 : 0;
             a.status[1] = i < a.B ? a.lengths[i] : 0;
             a.status[2] = a.ld_in;
@@ -321,26 +314,18 @@ int mtts_resample_forward(mtts_resampler* r, const float* d_in, int64_t ld_in, c
     a.B = B; a.o = r->o; a.n = r->n; a.width = r->width; a.band = r->band; a.bstride = r->bstride; a.fmin = r->fmin;
     a.bank_words = r->bank_words; a.span_words = r->span_words;
     const size_t lds = resampler_lds_bytes(r);
-    hipError_t e;
-    if (lds > 48 * 1024) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(resample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) { set_error(std::string("resample_kernel: ") + hipGetErrorString(e)); return -1; }
-    }
+    if (lds > 48 * 1024 &&
+        launched("resample_kernel", hipFuncSetAttribute(reinterpret_cast<const void*>(resample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)))
+        return -1;
     const unsigned tiles = (unsigned)((ld_out + RS_TILE - 1) / RS_TILE);
     hipLaunchKernelGGL(resample_kernel, dim3(tiles, B), dim3(RS_THREADS), lds, static_cast<hipStream_t>(stream), a);
-    e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("resample_kernel: ") + hipGetErrorString(e)); return -1; }
-    return 0;
+    return launched("resample_kernel");
 }
 
 // The lengths check's verdict (the header of the call's workspace).  The one entry of this file that waits for the stream.
 int mtts_resample_status(const void* d_ws, void* stream) {
-    if (!d_ws) { set_error("mtts_resample_status: null workspace"); return -1; }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int64_t st[4] = {0, 0, 0, 0};
-    hipError_t e = hipMemcpyAsync(st, d_ws, sizeof(st), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { set_error(std::string("mtts_resample_status: ") + hipGetErrorString(e)); return -1; }
+    int64_t st[4];
+    if (read_status("mtts_resample_status", d_ws, stream, st)) return -1;
     if (st[0] != 0) {
         set_error("mtts_resample_forward: row " + std::to_string(st[0] - 1) + " has length " + std::to_string(st[1]) + " (need 0 <= length <= ld_in = " +
                   std::to_string(st[2]) + " and ceil(n * length / o) <= ld_out = " + std::to_string(st[3]) + ")");

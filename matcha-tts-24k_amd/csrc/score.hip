@@ -16,8 +16,8 @@
 //           ceil(ceil(Tm / 64) / 64) partials per lane + a butterfly in the last pass          (score_prior_serial_run)
 //   dur:    r = ceil(Tx / 64) terms per lane + a butterfly
 //   cfm:    r = 4 terms per thread, a butterfly, 4 wave sums, then ceil(tiles / 64) partials per lane + a butterfly
-#include "kernels.h"
-#include "model.h"
+#include "host.h"
+#include "device_utils.h"
 
 #include <string>
 
@@ -154,20 +154,11 @@ __global__ __launch_bounds__(256) void score_prior_dur_kernel(ScoreArgs a) {
 __global__ __launch_bounds__(64) void score_finish_kernel(ScoreArgs a) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b == 0) {
-        __shared__ int first;
-        if (lane == 0) first = a.B;
-        __syncthreads();
-        int mine = a.B;
-        for (int i = a.B - 1 - lane; i >= 0; i -= 64)
-            if (a.verdict[2 * i] != 0) mine = i;
-        if (mine < a.B) atomicMin(&first, mine);
-        __syncthreads();
+        const int i = first_refused_row(a.B, [&](int r) { return a.verdict[2 * r] != 0; });
         if (lane == 0) {
-            const int i = first;
-            const int64_t lim = 0x7fffffff;
             a.status[0] = i < a.B ? i + 1 : 0;
-            a.status[1] = i < a.B ? (int)max(min(a.x_len[i], lim), -lim) : 0;
-            a.status[2] = i < a.B ? (int)max(min(a.y_len[i], lim), -lim) : 0;
+            a.status[1] = i < a.B ? sat32(a.x_len[i]) : 0;
+            a.status[2] = i < a.B ? sat32(a.y_len[i]) : 0;
             a.status[3] = a.Tx;
             a.status[4] = a.Tm;
             a.status[5] = i < a.B ? a.verdict[2 * i] : 0;
@@ -369,19 +360,13 @@ int mtts_score_prior_dur(const float* d_mu_x, const float* d_logw, const int32_t
     a.partial = reinterpret_cast<float*>(ws + p.partial);
     hipLaunchKernelGGL(score_prior_dur_kernel, dim3(p.nchunks, B), dim3(256), 0, s, a);
     hipLaunchKernelGGL(score_finish_kernel, dim3(B), dim3(64), 0, s, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { set_error(std::string("score_prior_dur_kernel / score_finish_kernel: ") + hipGetErrorString(e)); return -1; }
-    return 0;
+    return launched("score_prior_dur_kernel / score_finish_kernel");
 }
 
 // The verdict of the call's device-side checks (the header of its workspace).  The one entry of this file that waits for the stream.
 int mtts_score_status(const void* d_ws, void* stream) {
-    if (!d_ws) { set_error("mtts_score_status: null workspace"); return -1; }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int st[7] = {0, 0, 0, 0, 0, 0, 0};
-    hipError_t e = hipMemcpyAsync(st, d_ws, sizeof(st), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { set_error(std::string("mtts_score_status: ") + hipGetErrorString(e)); return -1; }
+    int st[7];
+    if (read_status("mtts_score_status", d_ws, stream, st)) return -1;
     if (st[0] != 0) {
         const std::string who = "mtts_score_prior_dur: utterance " + std::to_string(st[0] - 1) + " has x_length = " + std::to_string(st[1]) +
                                 ", y_length = " + std::to_string(st[2]);

@@ -4,6 +4,7 @@
 // (VocosBackbone / ConvNeXtBlock / ISTFTHead); call site reference matcha/vocos24k/vocos_wrapper.py:8-9.
 // Behind the kernels: the head's weight packing, workspace plan, launch sequence and C ABI (mtts_vocos_*).
 #include "host.h"
+#include "device_utils.h"
 
 namespace mtts {
 
@@ -151,22 +152,12 @@ hipError_t launch_istft_ola(const float* frames, const float* window, int B, int
 }
 
 // Validation of a ragged call's lengths where they live: status[0] = 1 + the first row whose length is outside [1, T] (0: all
-// good), status[1] = that length (saturated to int32), status[2] = T.  One workgroup; the minimum makes the answer independent
-// of the order the threads arrive in.
+// good), status[1] = that length (saturated to int32), status[2] = T.  One workgroup, ahead of the decode.
 __global__ __launch_bounds__(256) void vocos_lengths_check_kernel(const int64_t* __restrict__ lengths, int B, int T, int* __restrict__ status) {
-    __shared__ int first;
-    if (threadIdx.x == 0) first = B;
-    __syncthreads();
-    for (int b = threadIdx.x; b < B; b += blockDim.x) {
-        const int64_t n = lengths[b];
-        if (n < 1 || n > (int64_t)T) atomicMin(&first, b);
-    }
-    __syncthreads();
+    const int i = first_refused_row(B, [&](int b) { const int64_t n = lengths[b]; return n < 1 || n > (int64_t)T; });
     if (threadIdx.x == 0) {
-        const bool bad = first < B;
-        const int64_t n = bad ? lengths[first] : 0;
-        status[0] = bad ? first + 1 : 0;
-        status[1] = n > 2147483647LL ? 2147483647 : (n < -2147483647LL ? -2147483647 : (int)n);
+        status[0] = i < B ? i + 1 : 0;
+        status[1] = i < B ? sat32(lengths[i]) : 0;
         status[2] = T;
     }
 }
@@ -388,11 +379,8 @@ int mtts_vocos_decode_ragged(mtts_vocos* v, const float* d_mel, const int64_t* d
 // The lengths check's verdict (the status words at the base of the ragged call's workspace).  This is the one place that waits
 // for the stream: callers that go on to mtts_waveform_finish read its out_lengths instead (-1 marks the same rows).
 int mtts_vocos_ragged_status(const void* d_ws, void* stream) {
-    if (!d_ws) { set_error("mtts_vocos_ragged_status: null workspace"); return -1; }
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    int st[3] = {0, 0, 0};
-    HIP_OK(hipMemcpyAsync(st, d_ws, sizeof(st), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
+    int st[3];
+    if (read_status("mtts_vocos_ragged_status", d_ws, stream, st)) return -1;
     if (st[0] != 0) {
         set_error("mtts_vocos_decode_ragged: lengths[" + std::to_string(st[0] - 1) + "] = " + std::to_string(st[1]) +
                   " is outside [1, T = " + std::to_string(st[2]) + "]");

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import _hip
 from .hparams import N_VOCAB, PathHParams, from_reference_kwargs
 from .modules import PAIR_TIMEOUT_ERROR, Runtime, build_trees
 
@@ -757,6 +758,9 @@ def to_waveform(mel, vocoder):
     return _waveform_on_device(mel, vocoder).cpu().squeeze()
 
 
+_finish_ws = _hip.Workspaces()      # finish_waveforms' scratch: its kernels write every word they read
+
+
 @torch.inference_mode()
 def finish_waveforms(audio, lengths, hop=0, silence_threshold_db=-60.0):
     """Peak normalisation (reference inference.py:260-264) and the trim length of ``trim_trailing_silence`` (reference
@@ -765,18 +769,12 @@ def finish_waveforms(audio, lengths, hop=0, silence_threshold_db=-60.0):
     ``hop * (frames - 1)`` samples, as ``Vocos.decode(mel, lengths)`` leaves them).  Returns device tensors
     ``(out_lengths int64 [B], scale float32 [B])``: the caller keeps ``audio[b, :out_lengths[b]]``; -1 marks a row whose length
     is outside its row."""
-    from . import _hip
     lib = _hip.load()
     if audio.dim() != 2 or audio.dtype != torch.float32 or not audio.is_cuda or not audio.is_contiguous():
         raise RuntimeError("finish_waveforms: audio must be a contiguous float32 [B, L] tensor on a HIP device")
     B, L = audio.shape
-    lengths = torch.as_tensor(lengths).to(device=audio.device, dtype=torch.long).contiguous()
-    if lengths.shape != (B,):
-        raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
-    need = lib.mtts_waveform_workspace_bytes(L, B, SAMPLE_RATE)
-    if need < 0:
-        _hip.check(-1)
-    ws = torch.empty(need, dtype=torch.uint8, device=audio.device)
+    lengths = _hip.row_lengths(lengths, B, L, audio.device)
+    ws = _finish_ws.get("finish", lib.mtts_waveform_workspace_bytes(L, B, SAMPLE_RATE), audio.device)
     scale = torch.empty(B, dtype=torch.float32, device=audio.device)
     out_lengths = torch.empty(B, dtype=torch.long, device=audio.device)
     _hip.check(lib.mtts_waveform_finish(_hip.ptr(audio), L, _hip.ptr(lengths), int(hop), B, SAMPLE_RATE, float(silence_threshold_db),

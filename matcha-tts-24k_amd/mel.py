@@ -32,7 +32,7 @@ class MelFrontEnd:
         if not self.ctx:
             raise RuntimeError("mtts_melfe_create: " + self.lib.mtts_last_error().decode())
         self.n_bins = self.lib.mtts_melfe_n_bins(self.ctx)
-        self._ws: Dict[int, torch.Tensor] = {}
+        self._ws = _hip.Workspaces()
 
     def __del__(self):
         try:
@@ -55,10 +55,7 @@ class MelFrontEnd:
         return out
 
     def workspace_bytes(self, B: int, ld: int, hop: int) -> int:
-        n = self.lib.mtts_melfe_workspace_bytes(self.ctx, int(B), int(ld), int(hop))
-        if n < 0:
-            _hip.check(-1)
-        return n
+        return _hip.size(self.lib.mtts_melfe_workspace_bytes(self.ctx, int(B), int(ld), int(hop)))
 
     @torch.inference_mode()
     def extract(self, audio: torch.Tensor, lengths, hop: int = 256, mel_mean: float = 0.0, mel_std: float = 1.0
@@ -89,11 +86,7 @@ class MelFrontEnd:
         mel = torch.empty(B, self.n_mels, t_max, dtype=torch.float32, device=audio.device)
         mel_len = torch.empty(B, dtype=torch.int64, device=audio.device)
         need = int(B) * t_max * ((self.n_bins + 31) // 32 * 32) * 4 + 256
-        key = _hip.stream_ptr()
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need or ws.device != audio.device:
-            ws = torch.empty(need, dtype=torch.uint8, device=audio.device)
-            self._ws[key] = ws
+        ws = self._ws.get("melfe", need, audio.device)
         with torch.cuda.device(audio.device):
             _hip.check(self.lib.mtts_melfe_forward(self.ctx, _hip.ptr(audio), ld, _hip.ptr(d_len), B, hop, float(mel_mean), float(mel_std),
                                                    _hip.ptr(mel), t_max, _hip.ptr(mel_len), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))

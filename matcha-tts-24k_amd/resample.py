@@ -37,7 +37,7 @@ class Resampler:
         v = [C.c_int(0) for _ in range(5)]
         _hip.check(self.lib.mtts_resample_factors(self.ctx, *[C.byref(x) for x in v]))
         self.o, self.n, self.width, self.taps, self.band = (int(x.value) for x in v)
-        self._ws: Dict[int, torch.Tensor] = {}
+        self._ws = _hip.Workspaces()
 
     def __del__(self):
         try:
@@ -68,37 +68,13 @@ class Resampler:
         ``[0, L]`` (or with more than ``L_out`` outputs) gives a zero row and ``out_lengths[b] = -1`` on the device; with ``check``
         the call waits for that verdict and raises ``ValueError`` naming the row, ``check=False`` leaves it to the caller
         (``status``)."""
-        if audio.dim() == 1:
-            audio = audio[None]
-        if audio.dim() != 2:
-            raise ValueError("audio must be [B, L]")
-        if not audio.is_cuda:
-            raise RuntimeError("matcha-tts-24k_amd: audio is not on a HIP device; there is no CPU path")
-        audio = audio.detach().to(torch.float32)
-        B, L = audio.shape
-        if B < 1 or L < 1:
-            raise ValueError("audio must have at least one row and one sample")
-        if L % 4 or not audio.is_contiguous() or audio.data_ptr() % 16:      # rows of 16-byte aligned quads
-            padded = torch.zeros(B, (L + 3) // 4 * 4, dtype=torch.float32, device=audio.device)
-            padded[:, :L].copy_(audio)
-            audio = padded
-        ld_in = audio.shape[1]
-        if lengths is None:
-            lengths = torch.full((B,), L, dtype=torch.long, device=audio.device)
-        lengths = torch.as_tensor(lengths).to(device=audio.device, dtype=torch.long).contiguous()
-        if lengths.shape != (B,):
-            raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+        audio, L = _hip.aligned_rows(audio, 4, "audio")
+        B, ld_in = audio.shape
+        lengths = _hip.row_lengths(lengths, B, L, audio.device)
         ld_out = max(4, ((self.out_length(L) if ld_out is None else int(ld_out)) + 3) // 4 * 4)
         out = torch.empty(B, ld_out, dtype=torch.float32, device=audio.device)
         out_lengths = torch.empty(B, dtype=torch.long, device=audio.device)
-        need = self.lib.mtts_resample_workspace_bytes(self.ctx, B, ld_in)
-        if need < 0:
-            _hip.check(-1)
-        key = _hip.stream_ptr()
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need or ws.device != audio.device:
-            ws = torch.empty(need, dtype=torch.uint8, device=audio.device)
-            self._ws[key] = ws
+        ws = self._ws.get("resample", self.lib.mtts_resample_workspace_bytes(self.ctx, B, ld_in), audio.device)
         with torch.cuda.device(audio.device):
             _hip.check(self.lib.mtts_resample_forward(self.ctx, _hip.ptr(audio), ld_in, _hip.ptr(lengths), B, _hip.ptr(out), ld_out,
                                                       _hip.ptr(out_lengths), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
@@ -108,9 +84,9 @@ class Resampler:
 
     def status(self) -> None:
         """Wait for this stream's latest call and raise ``ValueError`` naming the first row the device refused."""
-        ws = self._ws.get(_hip.stream_ptr())
-        if ws is not None and self.lib.mtts_resample_status(ws.data_ptr(), _hip.stream_ptr()) != 0:
-            raise ValueError(self.lib.mtts_last_error().decode("utf-8", "replace"))
+        ws = self._ws.latest("resample")
+        if ws is not None:
+            _hip.raise_refused(self.lib.mtts_resample_status, ws.data_ptr(), _hip.stream_ptr())
 
 
 _resamplers: Dict[Tuple[int, int, str], Resampler] = {}

@@ -66,11 +66,9 @@ class StyleEncoder(_hip.DeviceComponent, nn.Module):
         B, C, T = mel.shape
         if C != self.cfg["n_feats"]:
             raise ValueError(f"mel has {C} channels, the style encoder expects {self.cfg['n_feats']}")
-        if lengths is None:
-            lengths = torch.full((B,), T, dtype=torch.int64) if mel_mask is None else mel_mask.reshape(B, -1).sum(-1)
-        lengths = torch.as_tensor(lengths).to(device=mel.device, dtype=torch.int64).contiguous()
-        if lengths.shape != (B,):
-            raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
+        if lengths is None and mel_mask is not None:
+            lengths = mel_mask.reshape(B, -1).sum(-1)
+        lengths = _hip.row_lengths(lengths, B, T, mel.device)
         d_group, n_out = None, B
         if group is not None:
             d_group = torch.as_tensor(group).to(device=mel.device, dtype=torch.int32).contiguous()
@@ -80,10 +78,7 @@ class StyleEncoder(_hip.DeviceComponent, nn.Module):
         E = self.cfg["spk_emb_dim"]
         e_enc = torch.empty(n_out, E, dtype=torch.float32, device=mel.device)
         e_dur = torch.empty(n_out, E, dtype=torch.float32, device=mel.device)
-        need = lib.mtts_style_workspace_bytes(self._ctx, B, T)
-        if need < 0:
-            _hip.check(-1)
-        ws = self._workspace(need, mel.device)
+        ws = self._ws.get("forward", lib.mtts_style_workspace_bytes(self._ctx, B, T), mel.device)
         _hip.check(lib.mtts_style_forward(self._ctx, _hip.ptr(mel), _hip.ptr(lengths), B, T, _hip.ptr(d_group), n_out if d_group is not None else 0,
                                           _hip.ptr(e_enc), _hip.ptr(e_dur), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
         return e_enc, e_dur

@@ -66,21 +66,15 @@ class Vocos(_hip.DeviceComponent, ParamTree):
         B, _, T = mel.shape
         audio = torch.empty(B, self.cfg["hop"] * (T - 1), dtype=torch.float32, device=mel.device)
         if lengths is None:
-            need = lib.mtts_vocos_workspace_bytes(self._ctx, B, T)
-            ws = self._workspace(need, mel.device)
+            ws = self._ws.get("decode", lib.mtts_vocos_workspace_bytes(self._ctx, B, T), mel.device)
             _hip.check(lib.mtts_vocos_decode(self._ctx, _hip.ptr(mel), B, T, _hip.ptr(audio), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
             return audio
-        lengths = torch.as_tensor(lengths).to(device=mel.device, dtype=torch.long).contiguous()
-        if lengths.shape != (B,):
-            raise ValueError(f"lengths must have shape ({B},), got {tuple(lengths.shape)}")
-        need = lib.mtts_vocos_ragged_workspace_bytes(self._ctx, B, T)
-        if need < 0:
-            _hip.check(-1)
-        ws = self._workspace(need, mel.device)
+        lengths = _hip.row_lengths(lengths, B, T, mel.device)
+        ws = self._ws.get("decode", lib.mtts_vocos_ragged_workspace_bytes(self._ctx, B, T), mel.device)
         _hip.check(lib.mtts_vocos_decode_ragged(self._ctx, _hip.ptr(mel), _hip.ptr(lengths), B, T, _hip.ptr(audio), ws.data_ptr(),
                                                 ws.numel(), _hip.stream_ptr()))
-        if check and lib.mtts_vocos_ragged_status(ws.data_ptr(), _hip.stream_ptr()) != 0:
-            raise ValueError("mtts: " + lib.mtts_last_error().decode("utf-8", "replace"))
+        if check:
+            _hip.raise_refused(lib.mtts_vocos_ragged_status, ws.data_ptr(), _hip.stream_ptr(), prefix="mtts: ")
         return audio
 
 
