@@ -33,6 +33,7 @@ class MelFrontEnd:
             raise RuntimeError("mtts_melfe_create: " + self.lib.mtts_last_error().decode())
         self.n_bins = self.lib.mtts_melfe_n_bins(self.ctx)
         self._ws = _hip.Workspaces()
+        self._last: Dict[int, Tuple[int, int]] = {}      # stream -> (B, T_max) of its latest extract
 
     def __del__(self):
         try:
@@ -53,6 +54,18 @@ class MelFrontEnd:
         out = np.empty((self.n_bins, self.n_mels), dtype=np.float32)
         _hip.check(self.lib.mtts_melfe_filterbank(self.ctx, out.ctypes.data, out.size))
         return out
+
+    def magnitudes(self, padded: bool = False) -> torch.Tensor:
+        """|STFT| of this stream's latest ``extract`` as it lies at the start of the workspace (csrc/mel_frontend.hip: ``mag
+        [B * T_max][bins padded to 32]``): a view [B, T_max, n_bins], or [B, T_max, padded bins] with ``padded``.  Rows beyond a
+        clip's frames are zero.  Read-only, for the tests: the next ``extract`` on the stream overwrites it."""
+        ws, shape = self._ws.latest("melfe"), self._last.get(_hip.stream_ptr())
+        if ws is None or shape is None:
+            raise RuntimeError("matcha-tts-24k_amd: no extract has run on this stream")
+        B, t_max = shape
+        nbp = (self.n_bins + 31) // 32 * 32
+        mag = ws[:B * t_max * nbp * 4].view(torch.float32).view(B, t_max, nbp)
+        return mag if padded else mag[:, :, :self.n_bins]
 
     def workspace_bytes(self, B: int, ld: int, hop: int) -> int:
         return _hip.size(self.lib.mtts_melfe_workspace_bytes(self.ctx, int(B), int(ld), int(hop)))
@@ -87,6 +100,7 @@ class MelFrontEnd:
         mel_len = torch.empty(B, dtype=torch.int64, device=audio.device)
         need = int(B) * t_max * ((self.n_bins + 31) // 32 * 32) * 4 + 256
         ws = self._ws.get("melfe", need, audio.device)
+        self._last[_hip.stream_ptr()] = (B, t_max)
         with torch.cuda.device(audio.device):
             _hip.check(self.lib.mtts_melfe_forward(self.ctx, _hip.ptr(audio), ld, _hip.ptr(d_len), B, hop, float(mel_mean), float(mel_std),
                                                    _hip.ptr(mel), t_max, _hip.ptr(mel_len), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))

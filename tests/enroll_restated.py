@@ -41,12 +41,39 @@ def log_mel(y, hop, mean=0.0, std=1.0, **kw) -> torch.Tensor:
     return (torch.log(torch.clamp(mel_linear(y, hop, **kw), min=1e-7)) - mean) / std
 
 
-def style_rows(sd, mel: torch.Tensor, length: int):
-    """StyleEncoder.forward on one clip [n_feats, T] with `length` valid frames, fp64 -> (e_enc [E], e_dur [E])."""
-    sd = {k: v.double() for k, v in sd.items()}
+def stft_frames(y: torch.Tensor, hop: int, n_fft: int, dtype=torch.float64) -> torch.Tensor:
+    """1-D clip -> [len // hop + 1, n_fft]: the clip trimmed to a multiple of hop, reflect-padded by n_fft / 2 at both ends
+    (center=True), one row per frame."""
+    y = y.to(dtype)[: (y.numel() // hop) * hop]
+    padded = F.pad(y[None, None], (n_fft // 2, n_fft // 2), mode="reflect")[0, 0]
+    return padded.unfold(0, n_fft, hop)
+
+
+def stft_mag(y: torch.Tensor, hop: int, n_fft: int, basis=None) -> torch.Tensor:
+    """[len // hop + 1, bins] STFT magnitudes as a matrix product: frames times the windowed cos | -sin basis, sqrt(re^2 + im^2).
+    `basis` None: fp64 throughout with dft_basis.  A given table (the library's fp32 one): everything in that table's dtype -- the
+    same operation in the same form in fp32, whose error against the fp64 form is the unit of the device's error."""
+    b = torch.from_numpy(dft_basis(n_fft)) if basis is None else torch.as_tensor(basis)
+    z = stft_frames(y, hop, n_fft, b.dtype) @ b
+    nb = n_fft // 2 + 1
+    return torch.sqrt(z[:, :nb] ** 2 + z[:, nb:] ** 2)
+
+
+def mel_from_mag(mag: torch.Tensor, fb, mean: float = 0.0, std: float = 1.0) -> torch.Tensor:
+    """Magnitudes [T, bins] -> normalised log-mel [T, n_mels] = (log(clamp(mag @ fb, 1e-7)) - mean) / std, in fb's dtype
+    (fb [bins, n_mels]: htk_fbanks for fp64, the library's fp32 table for the fp32 form)."""
+    fb = torch.as_tensor(fb)
+    lin = mag.to(fb.dtype) @ fb
+    return (torch.log(torch.clamp(lin, min=1e-7)) - mean) / std
+
+
+def style_rows(sd, mel: torch.Tensor, length: int, dtype=torch.float64):
+    """StyleEncoder.forward on one clip [n_feats, T] with `length` valid frames -> (e_enc [E], e_dur [E]); fp64, or the same
+    operations in another dtype (fp32: the unit of the device's error)."""
+    sd = {k: v.to(dtype) for k, v in sd.items()}
     T = mel.shape[-1]
-    mask = (torch.arange(T) < length).double()[None, None, :]
-    x = mel.double()[None]
+    mask = (torch.arange(T) < length).to(dtype)[None, None, :]
+    x = mel.to(dtype)[None]
     i = 0
     while f"convs.{i}.weight" in sd:
         x = torch.relu(F.conv1d(x * mask, sd[f"convs.{i}.weight"], sd[f"convs.{i}.bias"], padding=2))

@@ -1,5 +1,7 @@
 """GPU parity of the style encoder's forward pass (mtts_style_forward through style.py) against the fp64 CPU restatement
 (F.conv1d + ReLU, masked mean, two Linear layers)."""
+import math
+
 import pytest
 import torch
 
@@ -37,10 +39,17 @@ def test_rows_match_fp64(style, cfg):
     mel = inputs(cfg[0], 200, lengths, 6)
     e_enc, e_dur = model(mel.cuda(), lengths=lengths)
     assert e_enc.shape == e_dur.shape == (4, cfg[3])
+    # the rule of tests/test_hip_kernels_frontend.py in place of the fixed 1e-4: 8 x the error of the same operations in fp32 on the
+    # CPU plus one fp32 ulp of the row's largest entry, which must itself stay under the old bound
     for b, n in enumerate(lengths):
-        r_enc, r_dur = R.style_rows(sd, torch.nan_to_num(mel[b]), n)
-        assert (e_enc[b].cpu().double() - r_enc).abs().max().item() <= 1e-4
-        assert (e_dur[b].cpu().double() - r_dur).abs().max().item() <= 1e-4
+        ref = R.style_rows(sd, torch.nan_to_num(mel[b]), n)
+        c32 = R.style_rows(sd, torch.nan_to_num(mel[b]), n, dtype=torch.float32)
+        for got, r, c in zip((e_enc[b], e_dur[b]), ref, c32):
+            top = r.abs().max().item()
+            bound = 8 * (c.double() - r).abs().max().item() + 2.0 ** (math.floor(math.log2(top)) - 23)
+            err = (got.cpu().double() - r).abs().max().item()
+            print(f"style rows {cfg} b={b}: err {err:.3e}, bound {bound:.3e} (was 1e-4)")
+            assert bound < 1e-4 and err <= bound
 
 
 def test_mask_argument_as_the_reference_passes_it(style):

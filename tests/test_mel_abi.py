@@ -65,6 +65,23 @@ def test_host_tables_equal_fp64_restatement(sr, n_fft, n_mels):
     assert ((fb > 0).sum(axis=1) <= 2).all()                 # each bin feeds at most two filters: the band-sum form is complete
 
 
+@pytest.mark.parametrize("n_fft,hop,n", [(64, 16, 48), (64, 64, 200), (512, 160, 417), (1024, 256, 768), (1024, 100, 2222), (2048, 300, 5000)])
+def test_matrix_form_of_the_stft_equals_torch_stft(n_fft, hop, n):
+    """The two-stage restatement the kernel-level tests use (frames times basis, then filterbank and log) is torch.stft's result:
+    fp64 against fp64, so the bound is a few fp64 ulps of the frame's largest magnitude."""
+    y = R.synthetic_clip(n, n_fft + hop, "noise")
+    mag = R.stft_mag(y, hop, n_fft)
+    ref = torch.stft(y.double()[: n // hop * hop], n_fft, hop_length=hop, win_length=n_fft, window=torch.hann_window(n_fft, dtype=torch.float64),
+                     center=True, pad_mode="reflect", return_complex=True).abs().T
+    assert mag.shape == ref.shape == (n // hop + 1, n_fft // 2 + 1)
+    assert ((mag - ref).abs().amax(1) / ref.amax(1)).max().item() <= 1e-13
+    fb = R.htk_fbanks(n_fft // 2 + 1, 24000, 100)
+    assert (R.mel_from_mag(mag, fb, -4.0, 2.0) - R.log_mel(y, hop, -4.0, 2.0, n_fft=n_fft).T).abs().max().item() <= 1e-9
+    # the fp32 form (the unit of the device's error) differs from fp64 by fp32 rounding, not by a definition
+    c32 = R.stft_mag(y, hop, n_fft, torch.from_numpy(R.dft_basis(n_fft)).float())
+    assert c32.dtype == torch.float32 and ((c32.double() - ref).abs().amax(1) / ref.amax(1)).max().item() <= 2e-6
+
+
 def test_frame_count_rule():
     mel = sub("mel")
     for n, hop in [(641, 128), (1024, 256), (1279, 256), (120000, 128), (120001, 128)]:
