@@ -759,6 +759,46 @@ int mtts_mel_stats(const float* d_mel, int F, int T, const int64_t* d_lengths, i
                    int32_t* d_flags, void* d_ws, int64_t ws_bytes, void* stream);
 int mtts_mel_stats_status(const void* d_ws, void* stream);
 
+/* ---------------------------------------------------------------- long texts: finished rows joined into documents */
+
+/* The last step of a text longer than one utterance: its sentences are rows of one ragged batch, and the rows mtts_waveform_finish
+ * leaves are joined here into one waveform per document, before any rate conversion or encoding.  The reference has no counterpart
+ * (its handler refuses a text above 1000 characters, server.py:31,94-96): the arithmetic below is the definition, and a torch fp32
+ * restatement in that order reproduces every word (tests/join_restated.py).  Rows as for mtts_resample_forward: fp32 [B][ld] with
+ * ld % 4 == 0 and 16-byte aligned; nothing is read on the host on the way in.
+ *   d_lengths   device int64 [B]: kept samples of row b (mtts_waveform_finish's d_out_lengths; -1 = refused upstream)
+ *   d_scale     device fp32 [B] or NULL: the gain mtts_waveform_finish applied to row b (0.95 / peak, or 1)
+ *   d_first_row device int32 [G + 1]: document g is the rows [first_row[g], first_row[g + 1]) in speaking order;
+ *               0 = first_row[0] < first_row[1] < ... < first_row[G] = B (no document is empty)
+ *   d_gap       device int64 [B]: samples of silence after row b, inside [0, gap_max]; the entry of a document's last row is not read
+ *   d_out [G][out_ld] fp32 (out_ld % 4 == 0, 16-byte aligned, not overlapping d_audio), d_out_lengths int64 [G], d_starts int64 [B].
+ * Layout (int64, a function of the document alone): starts[b] = the sum of len_r + gap_r over the rows r of b's document before b;
+ * out_lengths[g] = starts[last] + len_last.  Row g of d_out holds, for each row b of the document, len_b samples at starts[b], zeros
+ * in the gaps and zeros from out_lengths[g] to out_ld: every word is written exactly once, the buffer needs no clearing.
+ * Samples (fp32, every operation rounded once, no FMA), x = audio[b][i]:
+ *   gain:  g_doc = the minimum of scale over the document's rows (1 when d_scale is NULL), r_b = g_doc / scale[b], one division per
+ *          row; x = x * r_b unless r_b == 1.0f, when the sample is moved bit for bit.  A document therefore carries ONE gain, that
+ *          of its loudest sentence, instead of one per sentence.
+ *   fade:  F' = min(fade, len_b / 2) (integer division).  Sample i < F' of a row that is not the first of its document, and sample
+ *          len_b - 1 - i (i < F') of a row that is not the last, become x * w with w = (float)(2 i + 1) / (float)(2 F'); together
+ *          y = (x * r_b) * w.  The two ends of a document keep their samples; fade == 0 applies no weight at all.
+ * Checks, on the device, before anything is indexed with these values; the verdict is that of the other ragged-batch entries
+ * (mtts_wave_join_status(d_ws, stream), the only entry here that waits, words it through mtts_last_error):
+ *   reason 1: a len_b outside [0, ld];  reason 2: the layout breaks, or a gap is outside [0, gap_max];  reason 3: the document is
+ *   longer than out_ld.  A document with such a row is refused as a whole: out_lengths[g] = -1, its rows' starts = -1, its row of
+ *   d_out zeros; the other documents are not touched.  Where the layout breaks at document g, the documents before g stand and
+ *   those from g on are refused (their rows' starts are -1); the row reported is the first one no standing document holds (held to
+ *   B - 1).  Header words (int64): first refused row + 1 or 0, its length (saturated to 32 bits), ld, the reason, out_ld, gap_max.
+ * Two launches: one workgroup plans (a wave per document, 64 rows per step), then a gather gridded over (tile of 2048 output samples,
+ * document) with 16-byte stores; a document is spread over the grid.  Stream-ordered, no allocation.  What the host can see returns
+ * -1 and launches nothing: null pointers, B < 1, G < 1, G > B, B > 65535, an ld or out_ld that is no positive multiple of 4, a
+ * misaligned d_audio / d_out / d_ws, d_out overlapping d_audio, fade < 0, gap_max < 0, a small workspace. */
+int64_t mtts_wave_join_workspace_bytes(int64_t B, int64_t G);
+int mtts_wave_join(const float* d_audio, int64_t ld, const int64_t* d_lengths, const float* d_scale, const int32_t* d_first_row,
+                   const int64_t* d_gap, int B, int G, int64_t fade, int64_t gap_max, float* d_out, int64_t out_ld,
+                   int64_t* d_out_lengths, int64_t* d_starts, void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_wave_join_status(const void* d_ws, void* stream);
+
 /* ---------------------------------------------------------------- encoded audio: PCM16, G.711 mu-law / A-law */
 
 /* The last stage out and the first stage in: a ragged batch of fp32 rows to the bytes a client is sent (s16le for the OpenAI

@@ -98,17 +98,96 @@ def plan_batch(waiting: List[Request], max_batch: int, max_tokens: int) -> List[
     return sorted(chosen)
 
 
+@dataclass
+class Document:
+    """A text longer than one utterance: its sentences as ``rows`` (one ``Request`` each, in speaking order; what they say about the
+    output -- rate, encoding, dither -- is not looked at) and the pause after each.  The rows run as rows of ONE ragged batch and are
+    joined on the device (``inference.to_waveforms(documents=...)``); the document has one future and one result."""
+    rows: List[Request]
+    pauses_ms: Sequence[float]              # silence after each row; the last entry is ignored
+    level: str = "document"                 # "document": one gain for the whole text; "sentence": each row keeps its own
+    sample_rate: int = 24000                # of the joined "audio": the fields of the same names of a Request, once per document
+    encoding: Optional[str] = None
+    dither: bool = False
+    dither_key: int = 0
+    future: Future = field(default_factory=Future, repr=False)
+    t_submit: float = field(default_factory=time.monotonic, repr=False)
+
+    def __post_init__(self):
+        if len(self.rows) == 0:
+            raise ValueError("a document has at least one segment")
+        if any(len(r.ids) == 0 for r in self.rows):
+            raise ValueError("empty segment in a document")
+        if len(self.pauses_ms) != len(self.rows):
+            raise ValueError(f"a document's pauses need one value per segment ({len(self.rows)}), got {len(self.pauses_ms)}")
+        if any(float(p) < 0 for p in self.pauses_ms):
+            raise ValueError("a pause is not negative")
+        if self.level not in ("document", "sentence"):
+            raise ValueError(f"level is 'document' or 'sentence', got {self.level!r}")
+        if len({r.group for r in self.rows}) != 1:
+            raise ValueError("the rows of a document share solver and n_timesteps")
+        if self.encoding is not None:
+            from .audio_codec import format_id
+            format_id(self.encoding)
+
+    @property
+    def group(self) -> Tuple[Any, ...]:
+        return self.rows[0].group
+
+    def gaps(self, sample_rate: int = 24000) -> List[int]:
+        """The pauses in samples of the join (which runs at the model's 24 kHz)."""
+        return [int(round(float(p) * sample_rate / 1000.0)) for p in self.pauses_ms]
+
+
+def unit_rows(unit) -> List[Request]:
+    """The rows a unit of the queue -- a ``Request`` or a ``Document`` -- adds to a batch."""
+    return list(unit.rows) if isinstance(unit, Document) else [unit]
+
+
+def _unit_size(unit) -> Tuple[int, int]:
+    """(rows, tokens of the longest row) of a unit."""
+    if isinstance(unit, Document):
+        return len(unit.rows), max(len(r.ids) for r in unit.rows)
+    return 1, len(unit.ids)
+
+
+def plan_units(waiting: List[Any], max_batch: int, max_tokens: int) -> List[int]:
+    """``plan_batch`` over units -- a ``Request`` or a ``Document`` with its rows: indices (into ``waiting``, arrival order) of the next
+    batch.  The head unit is taken whole; then the units of its group, nearest to it in the token count of their longest row first,
+    each whole or not at all, while the rows stay within ``max_batch`` and rows x longest within ``max_tokens``.  On a queue without
+    documents this is ``plan_batch``'s answer.  Pure function: unit-tested on the CPU."""
+    if not waiting:
+        return []
+    rows, longest = _unit_size(waiting[0])
+    n0 = longest
+    same = [i for i, u in enumerate(waiting) if i > 0 and u.group == waiting[0].group]
+    same.sort(key=lambda i: (abs(_unit_size(waiting[i])[1] - n0), i))
+    chosen = [0]
+    for i in same:
+        if rows >= max_batch:
+            break
+        n, own = _unit_size(waiting[i])
+        cand = max(longest, own)
+        if rows + n > max_batch or cand * (rows + n) > max_tokens:
+            continue
+        chosen.append(i)
+        rows, longest = rows + n, cand
+    return sorted(chosen)
+
+
 class FrameBudgetBatcher:
     """``submit()`` from any thread; results arrive on the request's future as ``{"mel": [n_feats, T_b], "mel_length": T_b}``."""
 
     def __init__(self, model, max_batch: int = 32, max_tokens: int = 8192, max_wait_ms: float = 2.0,
-                 run_batch: Optional[Callable[[List[Request]], List[Dict[str, Any]]]] = None, vocoder=None):
+                 run_batch: Optional[Callable[[List[Request]], List[Dict[str, Any]]]] = None, vocoder=None, fade_ms: float = 5.0):
         """``vocoder``: a ``load_vocoder("vocos")`` object; results then also carry ``"audio"`` = the reference handler's
         ``trim_trailing_silence(to_waveform(mel, vocoder))`` (reference inference.py:246, server.py:116) of that request's own
         mel.  The whole batch goes through ``inference.to_waveforms`` (ragged decode + finish on the device, one copy, one
-        synchronisation); ``MTTS_WAVE_BATCH=0``, read here per batcher, restores the per-request loop on exact-length mels."""
+        synchronisation); ``MTTS_WAVE_BATCH=0``, read here per batcher, restores the per-request loop on exact-length mels.
+        ``fade_ms``: the fade at the joints between the sentences of a document (``submit_document``)."""
         self.model = model
         self.vocoder = vocoder
+        self.fade_ms = float(fade_ms)
         self.wave_batch = os.environ.get("MTTS_WAVE_BATCH", "1") != "0"
         self.max_batch = int(max_batch)
         self.max_tokens = int(max_tokens)
@@ -137,6 +216,32 @@ class FrameBudgetBatcher:
             self._cv.notify()
         return r.future
 
+    def submit_document(self, segments_ids: Sequence[Sequence[int]], pauses_ms: Sequence[float], **request_fields) -> Future:
+        """A text of several utterances: ``segments_ids`` the phoneme ids of each segment in speaking order, ``pauses_ms`` the silence
+        after each (the last is ignored).  ``request_fields``: the fields of a ``Request`` -- voice, solver, speeds apply to every
+        segment; ``sample_rate`` / ``encoding`` / ``dither`` / ``dither_key`` to the joined result -- and ``level`` (``Document``).
+        The segments run as rows of one ragged batch, together with whatever else is waiting, and are joined on the device.  One
+        future: ``{"audio", "segments": [(start_s, end_s)] per segment, "mel_lengths"}``, plus ``"sample_rate"`` / ``"encoding"``
+        when asked.  A document is admitted whole or not at all: more segments than ``max_batch`` or segments x longest above
+        ``max_tokens`` raises ``ValueError`` here, as does an empty segment."""
+        once = {k: request_fields.pop(k) for k in ("level", "sample_rate", "encoding", "dither", "dither_key") if k in request_fields}
+        segments = [list(ids) for ids in segments_ids]
+        if any(len(ids) == 0 for ids in segments):
+            raise ValueError("empty segment in a document")
+        d = Document(rows=[Request(ids=ids, **request_fields) for ids in segments], pauses_ms=[float(p) for p in pauses_ms], **once)
+        duration_rows(d.rows)
+        n, longest = _unit_size(d)
+        if n > self.max_batch:
+            raise ValueError(f"a document of {n} segments exceeds the batch of {self.max_batch} utterances")
+        if n * longest > self.max_tokens:
+            raise ValueError(f"a document of {n} segments of up to {longest} tokens exceeds the batch budget of {self.max_tokens}")
+        with self._cv:
+            if self._stop:
+                raise RuntimeError("batcher is closed")
+            self._waiting.append(d)
+            self._cv.notify()
+        return d.future
+
     def close(self) -> None:
         with self._cv:
             self._stop = True
@@ -159,12 +264,12 @@ class FrameBudgetBatcher:
                     return
                 # give concurrent submitters a moment to arrive, bounded by the oldest request's age
                 deadline = self._waiting[0].t_submit + self.max_wait
-                while len(self._waiting) < self.max_batch and not self._stop:
+                while sum(_unit_size(u)[0] for u in self._waiting) < self.max_batch and not self._stop:     # (rows: a document counts its own)
                     left = deadline - time.monotonic()
                     if left <= 0:
                         break
                     self._cv.wait(left)
-                take = plan_batch(self._waiting, self.max_batch, self.max_tokens)
+                take = plan_units(self._waiting, self.max_batch, self.max_tokens)
                 batch = [self._waiting[i] for i in take]
                 for i in reversed(take):
                     del self._waiting[i]
@@ -181,7 +286,7 @@ class FrameBudgetBatcher:
             self.batches_run += 1
 
     def _run_on_model(self, batch: List[Request]) -> List[Dict[str, Any]]:
-        return synthesise_batch(self.model, batch, self.vocoder, self.wave_batch)
+        return synthesise_batch(self.model, batch, self.vocoder, self.wave_batch, self.fade_ms)
 
 
 def request_inputs(model, batch: List[Request]):
@@ -241,8 +346,12 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
             r["encoding"] = enc
 
 
-def synthesise_batch(model, batch: List[Request], vocoder=None, wave_batch: bool = True) -> List[Dict[str, Any]]:
-    """One ``synthesise(per_request_padding=True)`` call for requests of one group, and their waveforms."""
+def synthesise_batch(model, batch: List[Any], vocoder=None, wave_batch: bool = True, fade_ms: float = 5.0) -> List[Dict[str, Any]]:
+    """One ``synthesise(per_request_padding=True)`` call for requests of one group, and their waveforms.  A batch that holds a
+    ``Document`` runs the rows of all its units in that one call and joins each document's rows on the device
+    (``synthesise_units``); without one this is the call it always was."""
+    if any(isinstance(u, Document) for u in batch):
+        return synthesise_units(model, batch, vocoder, fade_ms)
     B = len(batch)
     x, x_len, emb = request_inputs(model, batch)
     head = batch[0]
@@ -254,6 +363,46 @@ def synthesise_batch(model, batch: List[Request], vocoder=None, wave_batch: bool
     lens = out["mel_lengths"].tolist()
     res = [{"mel": out["mel"][b, :, :int(lens[b])], "mel_length": int(lens[b])} for b in range(B)]
     waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch, [r.sample_rate for r in batch], *encoding_fields(batch))
+    return res
+
+
+def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> List[Dict[str, Any]]:
+    """``synthesise_batch`` for a batch with documents: the units flattened to rows, one ``synthesise`` call, then
+    ``to_waveforms(documents=...)`` -- a plain request is a document of one row there (no joint, its own gain: its samples are its
+    batch-of-one samples) -- and one result per unit.  A plain request keeps exactly the keys and values it has without documents in
+    its batch; a document gets ``{"audio", "segments", "mel_lengths"}``.  The join is part of the batched tail: there is no
+    per-request loop for it, and no host-side join."""
+    if vocoder is None:
+        raise ValueError("a document needs a vocoder: its result is the joined audio")
+    from .inference import to_waveforms
+    rows = [r for u in units for r in unit_rows(u)]
+    x, x_len, emb = request_inputs(model, rows)
+    head = rows[0]
+    model.decoder.solver = head.solver
+    out = model.synthesise(x, x_len, head.n_timesteps, speaker_embeddings=emb,
+                           scale_correction=[r.scale_correction for r in rows],
+                           length_scale=[r.length_scale for r in rows], per_request_padding=True,
+                           durations=duration_rows(rows))
+    lens = [int(v) for v in out["mel_lengths"].tolist()]
+    counts = [len(unit_rows(u)) for u in units]
+    gaps = [g for u in units for g in (u.gaps() if isinstance(u, Document) else [0])]
+    encs, dith, keys = encoding_fields(units)
+    extra = {} if encs is None else dict(encoding=encs, dither=dith, dither_keys=keys)
+    audio, segments = to_waveforms(out["mel"], out["mel_lengths"], vocoder, sample_rate=[int(u.sample_rate) for u in units],
+                                   documents=counts, gaps=gaps, fade_ms=fade_ms,
+                                   level=[u.level if isinstance(u, Document) else "sentence" for u in units], return_segments=True, **extra)
+    res, b = [], 0
+    for u, n, a, seg in zip(units, counts, audio, segments):
+        if isinstance(u, Document):
+            r = {"audio": a, "segments": seg, "mel_lengths": lens[b:b + n]}
+        else:
+            r = {"mel": out["mel"][b, :, :lens[b]], "mel_length": lens[b], "audio": a}
+        if int(u.sample_rate) != 24000:
+            r["sample_rate"] = int(u.sample_rate)
+        if u.encoding is not None:
+            r["encoding"] = u.encoding
+        res.append(r)
+        b += n
     return res
 
 

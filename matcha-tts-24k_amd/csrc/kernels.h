@@ -540,4 +540,26 @@ hipError_t launch_silence_measure(const SilenceMeasureArgs& a, hipStream_t s);
 hipError_t launch_silence_normalize(const SilenceNormArgs& a, hipStream_t s);
 hipError_t launch_mel_stats(const MelStatsArgs& a, hipStream_t s);
 
+// ---- document join (wave_join.hip): finished rows of a ragged batch into one waveform per document, see include/mtts.h
+struct WaveJoinArgs {
+    const float* audio = nullptr;      // [B][ld], read only inside [0, len_b)
+    int64_t ld = 0;                    // row stride in samples (multiple of 4, rows 16-byte aligned)
+    const int64_t* lengths = nullptr;  // [B] kept samples, -1 = refused upstream
+    const float* scale = nullptr;      // [B] or null: the gain mtts_waveform_finish gave row b
+    const int32_t* first_row = nullptr;// [G + 1]: rows of document g are [first_row[g], first_row[g + 1])
+    const int64_t* gap = nullptr;      // [B] samples of silence after row b (ignored after a document's last row)
+    int B = 0, G = 0;
+    int64_t fade = 0, gap_max = 0;
+    float* out = nullptr;              // [G][out_ld]
+    int64_t out_ld = 0;
+    int64_t* out_lengths = nullptr;    // [G]
+    int64_t* starts = nullptr;         // [B]
+    int64_t* status = nullptr;         // workspace header: first refused row + 1 (0: none), its length, ld, reason, out_ld, gap_max
+    float* ratio = nullptr;            // workspace [B]: g_doc / scale[b]
+    int32_t* code = nullptr;           // workspace [B]: what row b itself was refused for (0: nothing, 1 length, 2 gap)
+};
+constexpr int JOIN_TILE = 2048;        // output samples per workgroup of the move
+constexpr int JOIN_STAGE = 256;        // rows of a document the move stages in LDS at once
+hipError_t launch_wave_join(const WaveJoinArgs& a, hipStream_t s);
+
 }  // namespace mtts

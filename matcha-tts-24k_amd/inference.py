@@ -784,7 +784,7 @@ def finish_waveforms(audio, lengths, hop=0, silence_threshold_db=-60.0):
 
 @torch.inference_mode()
 def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, *, encoding=None, dither=False, dither_keys=None,
-                 sample_rate=24000):
+                 documents=None, gaps=None, fade_ms=5.0, level="document", return_segments=False, sample_rate=24000):
     """``trim_trailing_silence(to_waveform(mel[b:b+1, :, :len_b], vocoder))`` (reference inference.py:246) for every row of a
     ragged batch in one device pass: ragged Vocos decode, per-row peak normalisation, per-row trim lengths, then ONE copy of the
     audio and one of the [B] lengths -- one synchronisation for the whole batch.  Returns a list of B 1-D host tensors
@@ -800,7 +800,23 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     and the rate conversion, on their device lengths, no extra host read) and come back as 1-D uint8 host tensors: raw samples, no
     container, views of the batch's one host buffer of bytes; the one copy is then of bytes and the single synchronisation stays.
     ``dither`` (a bool, or one per row): TPDF dither on the PCM16 rows, the sequence of row b selected by ``dither_keys[b]`` (default
-    0) and by nothing else, so a row's bytes do not depend on the batch it is in.  The keyword-only arguments follow a ``*``."""
+    0) and by nothing else, so a row's bytes do not depend on the batch it is in.  The keyword-only arguments follow a ``*``.
+
+    ``documents``: None (every row is its own result, as ever: nothing below is launched or allocated), or the rows that belong
+    together as a host list -- row counts in speaking order, or the CSR ``[0, n0, n0 + n1, ...]``; rows behind the last document are
+    documents of one row each.  The rows of a document are then joined on the device into one waveform (``join_waveforms``: once, at
+    24 kHz, after the normalisation and the trim and ahead of the rate conversion and the encoding, which see one row per document
+    and its joined device length) and the call returns one entry per DOCUMENT; ``sample_rate``, ``encoding``, ``dither`` and
+    ``dither_keys`` are then one per document.  ``gaps``: samples of silence (24 kHz) after each row, a host list of B (the entry of
+    a document's last row is ignored; default none).  ``fade_ms``: the fade at the interior joints.  ``level`` (a name, or one per
+    document): ``"document"`` gives a document one gain, that of its loudest sentence; ``"sentence"`` leaves each row the gain the
+    normalisation gave it.
+    ``return_segments``: also return, per document, ``[(start_s, end_s)]`` of its rows in seconds of the 24 kHz join (so they do
+    not depend on the output rate): ``(results, segments)``.  The single synchronisation stays."""
+    if documents is None and (gaps is not None or return_segments):
+        raise ValueError("to_waveforms: gaps and return_segments belong to documents=")
+    if any(v not in ("document", "sentence") for v in ([level] if isinstance(level, str) else level)):
+        raise ValueError(f"to_waveforms: level is 'document' or 'sentence' (or one of them per document), got {level!r}")
     model = vocoder.model if hasattr(vocoder, "model") else vocoder
     if mel.dim() == 2:
         mel = mel[None]
@@ -808,10 +824,17 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     mel_lengths = torch.as_tensor(mel_lengths).to(device=mel.device, dtype=torch.long)
     hop = model.cfg["hop"]
     from . import resample as R
-    rates = R.rates_per_row(sample_rate, B)
-    encs = _encodings_per_row(encoding, B)                             # (an unknown name raises before anything is launched)
+    csr = None if documents is None else document_csr(documents, B, pad=True)
+    n_out = B if csr is None else len(csr) - 1
+    rates = R.rates_per_row(sample_rate, n_out)
+    encs = _encodings_per_row(encoding, n_out)                         # (an unknown name raises before anything is launched)
     audio = model.decode(mel, mel_lengths, check=False)
-    out_lengths, _ = finish_waveforms(audio, mel_lengths, hop=hop, silence_threshold_db=silence_threshold_db)
+    out_lengths, scale = finish_waveforms(audio, mel_lengths, hop=hop, silence_threshold_db=silence_threshold_db)
+    if csr is not None:
+        keep = out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1))
+        fade = int(round(float(fade_ms) * SAMPLE_RATE / 1000.0))
+        return _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, _document_scales(scale, level, csr), rates, encs,
+                                 dither, dither_keys, return_segments)
     if any(r != SAMPLE_RATE for r in rates):
         audio, out_lengths = _convert_rows(audio, out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1)),
                                            rates)
@@ -824,6 +847,132 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
         if keep[b] < 0:
             raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
     return [host[b, : (keep[b] if trim or rates[b] != SAMPLE_RATE else hop * (frames[b] - 1))] for b in range(B)]
+
+
+_join_ws = _hip.Workspaces()
+
+
+def document_csr(documents, B, pad=False):
+    """``documents`` -- a host list of row counts, or the CSR ``[0, n0, n0 + n1, ...]`` (it begins with 0, which no count can be) -- as
+    the CSR list the device takes.  Counts are checked here (each at least 1, their sum ``B``); a CSR is passed on as it is, for the
+    device to judge.  ``pad``: rows behind the last document become documents of one row each."""
+    docs = [int(v) for v in (documents.tolist() if torch.is_tensor(documents) else documents)]
+    if len(docs) == 0:
+        raise ValueError("documents: no document")
+    if docs[0] == 0:
+        csr = docs
+    else:
+        if any(n < 1 for n in docs):
+            raise ValueError("documents: a document has at least one row")
+        csr = [0]
+        for n in docs:
+            csr.append(csr[-1] + n)
+        if csr[-1] > B or (csr[-1] < B and not pad):
+            raise ValueError(f"documents: the row counts add up to {csr[-1]}, the batch has {B} rows")
+    if pad and len(csr) > 1 and 0 <= csr[-1] < B:
+        csr = csr + list(range(csr[-1] + 1, B + 1))
+    if len(csr) < 2:
+        raise ValueError("documents: no document")
+    return csr
+
+
+@torch.inference_mode()
+def join_waveforms(audio, lengths, documents, gaps, fade=0, scale=None, check=True, out_ld=None):
+    """Finished rows joined into documents on the device (``mtts_wave_join``; include/mtts.h has the arithmetic): ``audio`` [B, ld]
+    float32 and ``lengths`` [B] as ``finish_waveforms`` leaves them (a tensor stays on the device; -1 = refused row), ``documents`` a
+    host list of row counts or a CSR (``document_csr``), ``gaps`` a host list of B sample counts (silence after each row; the entry
+    of a document's last row is ignored; None: none), ``fade`` samples faded at each interior joint, ``scale`` the [B] gains of
+    ``finish_waveforms`` (one gain per document) or None (every row keeps its own).  Returns device tensors ``(out [G, out_ld],
+    out_lengths int64 [G], starts int64 [B])``: document g holds ``out_lengths[g]`` samples, zeros beyond; ``starts[b]`` is where row b
+    begins inside its document.  ``out_ld`` defaults to the host-known bound ``max_g(rows_g * ld + gaps_g)``, rounded up to 4.
+    Nothing is read on the host: a document with a refused row, a bad gap or no room gets length -1 and zeros, its rows start -1;
+    with ``check`` the call waits for that verdict and raises ``ValueError`` naming the row and the reason."""
+    lib = _hip.load()
+    audio, L = _hip.aligned_rows(audio, 4, "audio")
+    B, ld = audio.shape
+    dev = audio.device
+    lengths = _hip.row_lengths(lengths, B, L, dev)
+    csr = document_csr(documents, B)
+    G = len(csr) - 1
+    gaps = [0] * B if gaps is None else [int(v) for v in (gaps.tolist() if torch.is_tensor(gaps) else gaps)]
+    if len(gaps) != B:
+        raise ValueError(f"gaps need one entry per row ({B}), got {len(gaps)}")
+    if scale is not None:
+        scale = scale.to(device=dev, dtype=torch.float32).contiguous()
+        if scale.shape != (B,):
+            raise ValueError(f"scale must have shape ({B},), got {tuple(scale.shape)}")
+    if out_ld is None:
+        out_ld = max((b - a) * ld + sum(max(v, 0) for v in gaps[max(a, 0):max(b - 1, 0)]) for a, b in zip(csr[:-1], csr[1:]))
+    out_ld = max(4, (int(out_ld) + 3) // 4 * 4)
+    first_row = torch.tensor(csr, dtype=torch.int32).to(dev)
+    gap = torch.tensor(gaps, dtype=torch.long).to(dev)
+    out = torch.empty(G, out_ld, dtype=torch.float32, device=dev)
+    out_lengths = torch.empty(G, dtype=torch.long, device=dev)
+    starts = torch.empty(B, dtype=torch.long, device=dev)
+    ws = _join_ws.get("join", lib.mtts_wave_join_workspace_bytes(B, G), dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.mtts_wave_join(_hip.ptr(audio), ld, _hip.ptr(lengths), _hip.ptr(scale), _hip.ptr(first_row), _hip.ptr(gap), B, G,
+                                      int(fade), max([0] + gaps), _hip.ptr(out), out_ld, _hip.ptr(out_lengths), _hip.ptr(starts),
+                                      ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
+    if check:
+        _hip.raise_refused(lib.mtts_wave_join_status, ws.data_ptr(), _hip.stream_ptr())
+    return out, out_lengths, starts
+
+
+def _document_scales(scale, level, csr):
+    """``scale=`` of the join for ``level`` (a name, or one per document): the rows' gains where a document takes one gain, 1 on the
+    rows of a document whose sentences keep theirs (its gain is then 1 and nothing is multiplied), None when no document takes one."""
+    G = len(csr) - 1
+    levels = [level] * G if isinstance(level, str) else list(level)
+    if len(levels) != G:
+        raise ValueError(f"level is a name or one per document ({G}), got {len(levels)}")
+    if all(v == "sentence" for v in levels):
+        return None
+    if all(v == "document" for v in levels):
+        return scale
+    own = torch.tensor([levels[g] == "sentence" for g in range(G) for _ in range(csr[g], csr[g + 1])], dtype=torch.bool, device=scale.device)
+    return torch.where(own, torch.ones_like(scale), scale)
+
+
+def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates, encs, dither, dither_keys, return_segments):
+    """The end of ``to_waveforms`` with ``documents=``: the join at 24 kHz, then the rate conversion and the encoding over one row
+    per document on the joined device lengths, then the batch's one synchronisation -- the joined lengths, the rows' starts and kept
+    lengths ride in the one ``meta`` copy -- and one copy of no more columns than the longest document has."""
+    from . import audio_codec as AC
+    G = len(csr) - 1
+    dev = audio.device
+    wave, lens, starts = join_waveforms(audio, keep, csr, gaps, fade=fade, scale=scale, check=False)
+    if any(r != SAMPLE_RATE for r in rates):
+        wave, lens = _convert_rows(wave, lens, rates)
+    words = [lens, starts, keep, mel_lengths]
+    if encs is not None:
+        named = torch.tensor([e is not None for e in encs], dtype=torch.bool, device=dev)
+        fmt = [AC.PCM16 if e is None else e for e in encs]
+        on = [bool(dither)] * G if isinstance(dither, (bool, int)) else [bool(v) for v in dither]
+        data, nbytes = AC.encode(wave, torch.where(named, lens, torch.zeros_like(lens)), fmt,
+                                 dither=on if len(set(on)) > 1 else on[0], keys=dither_keys)
+        words.append(nbytes)
+    meta = torch.cat(words).cpu().tolist()                             # waits for the stream: the batch's one synchronisation
+    B = keep.shape[0]
+    got, begin, kept, frames = meta[:G], meta[G:G + B], meta[G + B:G + 2 * B], meta[G + 2 * B:G + 3 * B]
+    for b in range(B):
+        if kept[b] < 0:
+            raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
+    for g in range(G):
+        if got[g] < 0:
+            raise ValueError(f"to_waveforms: document {g} (rows {csr[g]} to {csr[g + 1] - 1}) could not be joined")
+    width = max(got)
+    floats = wave[:, :width].cpu() if encs is None or not all(e is not None for e in encs) else None
+    if encs is None:
+        res = [floats[g, :got[g]] for g in range(G)]
+    else:
+        nb = meta[G + 3 * B:]
+        host = data[:, :max(max(nb), 1)].cpu()
+        res = [floats[g, :got[g]] if encs[g] is None else host[g, :nb[g]] for g in range(G)]
+    if not return_segments:
+        return res
+    segments = [[(begin[b] / SAMPLE_RATE, (begin[b] + kept[b]) / SAMPLE_RATE) for b in range(csr[g], csr[g + 1])] for g in range(G)]
+    return res, segments
 
 
 def _encodings_per_row(encoding, B):

@@ -22,6 +22,7 @@ from .inference import DEFAULT_NUM_STEPS, DEFAULT_ODE_SOLVER, VOICES
 LENGTH_SCALE_MIN = 0.1      # fastest (client speed 2.0 clamps here; reference server.py:34-36)
 LENGTH_SCALE_MAX = 2.0      # slowest
 MAX_TEXT_LENGTH = 1000      # reference server.py:30
+MAX_DOCUMENT_LENGTH = 20000 # characters of a text spoken as a document (submit_long); the reference has no such route
 
 #: ``response_format`` -> the encoding a request asks of the batcher; "wav" is that payload behind a RIFF header
 RESPONSE_FORMATS = {"pcm": "pcm16", "wav": "pcm16", "ulaw": "ulaw", "alaw": "alaw"}
@@ -127,4 +128,44 @@ class SpeechService:
                     speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None):
         """The waveform (a 1-D float tensor on the host), or with ``response_format`` the response body as ``bytes``."""
         res = await asyncio.wrap_future(self.submit(text, voice, speed, steps, solver, speaker_embedding, sample_rate, response_format))
+        return response_body(res, response_format, int(sample_rate))
+
+    def submit_long(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
+                    speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None,
+                    max_document_length: int = MAX_DOCUMENT_LENGTH, **split_options):
+        """A text longer than one utterance: cut into sentences (``longform.split_text(text, **split_options)``; the abbreviation set
+        is that of the voice's language unless given), each phonemized on its own -- so the phonemizer's intonation marks stay per
+        sentence --, and submitted as ONE document (``FrameBudgetBatcher.submit_document``): the sentences run as rows of one ragged
+        batch and are joined on the device with the splitter's pauses between them.  The other arguments are ``submit``'s and apply to
+        the joined result.  The future's result carries ``"audio"`` and ``"segments"`` (seconds of each sentence in the 24 kHz join).
+        A batcher without ``submit_document`` raises ``TypeError``: there is no host-side join to fall back to.  ``submit`` and its
+        cap are unchanged."""
+        encoding = response_encoding(response_format)
+        if not hasattr(self.batcher, "submit_document"):
+            raise TypeError(f"{type(self.batcher).__name__} has no submit_document: long texts need a FrameBudgetBatcher")
+        if len(text) > int(max_document_length):
+            raise ValueError(f"Text exceeds {int(max_document_length)} characters")
+        from .longform import split_text
+        p = request_params(voice, speed, steps, solver)
+        split_options.setdefault("language", p.language)
+        pieces = split_text(text, **split_options)
+        if not pieces:
+            raise ValueError("empty text")
+        ids = [self.phonemize(segment, p.language) for segment, _ in pieces]
+        extra = {} if speaker_embedding is None else {"speaker_embedding": tuple(speaker_embedding)}
+        if int(sample_rate) != 24000:
+            extra["sample_rate"] = int(sample_rate)
+        if encoding is not None:
+            extra["encoding"] = encoding
+        return self.batcher.submit_document(ids, [pause for _, pause in pieces], speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver,
+                                            n_timesteps=p.n_timesteps, scale_correction=p.scale_correction, length_scale=p.length_scale,
+                                            **extra)
+
+    async def speak_long(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
+                         speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None,
+                         max_document_length: int = MAX_DOCUMENT_LENGTH, **split_options):
+        """The joined waveform of a long text (a 1-D float tensor on the host), or with ``response_format`` the response body as
+        ``bytes`` -- ``response_body``, as ``speak``."""
+        res = await asyncio.wrap_future(self.submit_long(text, voice, speed, steps, solver, speaker_embedding, sample_rate, response_format,
+                                                         max_document_length, **split_options))
         return response_body(res, response_format, int(sample_rate))
