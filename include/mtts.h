@@ -857,6 +857,80 @@ int mtts_pcm_decode(const uint8_t* d_data, int64_t ld_bytes, const int64_t* d_le
                     float* d_out, int64_t ld, int64_t* d_out_lengths, void* stream);
 int mtts_pcm_status(const int64_t* d_verdict, int B, void* stream);
 
+/* ---------------------------------------------------------------- loudness: BS.1770 K-weighted, gated LUFS, one gain per row */
+
+/* How loud a row is, and the gain that brings it to a target: integrated loudness as in ITU-R BS.1770-4 / EBU R 128 for a ragged
+ * batch of mono rows, measured and (with `apply`) corrected in place.  The reference has no counterpart (its to_waveform only
+ * scales a row whose peak exceeds 1); the arithmetic below is the definition, and tests/loudness_restated.py restates it in NumPy
+ * fp64 in plain sample order.  Rows as for the other waveform entries: fp32 [B][ld], ld % 4 == 0, 16-byte aligned; d_lengths device
+ * int64 [B], checked on the device without a host read; nothing outside [0, len_b) of a row is read or written.
+ *
+ * Coefficients (host, fp64, any sample_rate fs with fs % 100 == 0 in [8000, 192000]; mtts_loudness_coefficients returns the ten
+ * words b0 b1 b2 a1 a2 of the shelf, then of the high-pass): the bilinear transform of the analog prototype,
+ *   shelf:     f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196, K = tan(pi f0 / fs), Vh = 10^(G / 20),
+ *              Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K K;
+ *              b = [(Vh + Vb K / Q + K K) / a0, 2 (K K - Vh) / a0, (Vh - Vb K / Q + K K) / a0], a = [1, 2 (K K - 1) / a0, (1 - K / Q + K K) / a0]
+ *   high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, the same K and a0; b = [1, -2, 1], a as above.
+ * At 48 kHz these are the table values of BS.1770 to 1e-14.  At other rates the response is that of the bilinear coefficients: a
+ * full-scale 997 Hz sine reads -3.0103 LUFS at 48 kHz, -2.984 at 24 kHz and -2.996 at 8 kHz.
+ *
+ * The cascade, per sample x (fp32, converted exactly), transposed direct form II in fp64, every operation rounded once (no FMA):
+ *   y = b0 x + s1;  s1 = (b1 x - a1 y) + s2;  s2 = b2 x - a2 y          (shelf)
+ *   z = c0 y + t1;  t1 = (c1 y - d1 z) + t2;  t2 = c2 y - d2 z          (high-pass), all four state words 0 ahead of sample 0.
+ * The recurrence is cut in time.  chunk = mtts_loudness_chunk(fs) = the largest divisor of fs / 100 that is at most 256 (240 at 24
+ * and 48 kHz, 80 at 8 kHz), so chunk edges fall on 10 ms edges.  Pass 1 runs every chunk from zero state and keeps its end state
+ * z_c; pass 2 carries s_{c+1} = M s_c + z_c along the row, M = A^chunk the 4 x 4 transition matrix of `chunk` samples of silence,
+ * built on the host in fp64 by running the cascade from the four unit states, each row of M s evaluated as
+ * ((M0 s0 + M1 s1) + M2 s2) + M3 s3, then + z; pass 3 reruns every chunk from its true entry state s_c.  Pass 2 is a two-level
+ * scan with R = MTTS_LOUDNESS_SCAN_RUN and P = M^R (built the same way over R * chunk samples): run r holds the chunks
+ * [R r, R r + R); w_r = the fold w = M w + z_c over the run from w = 0 (a chunk beyond the row's end counts as z = 0);
+ * S_0 = 0, S_{r+1} = P S_r + w_r in run order; chunk c of run r is entered with s, which starts at S_r and then becomes M s + z_c.  This equals the plain
+ * recurrence up to the rounding of M s (2e-13 absolute on a signal of rms 0.09; an fp32 recurrence is off by 1.4e-5: hence fp64).
+ * Sums: e_c = the sum of z z over the chunk's samples inside the row, in sample order from 0.0; a 100 ms segment (fs / 10 samples) is
+ * the sum of its chunks in index order from 0.0; block j = ((seg_j + seg_j+1) + seg_j+2) + seg_j+3, taken at every whole segment
+ * j <= nfull - 4, nfull = len_b / (fs / 10): 400 ms at 75 % overlap; a partial trailing segment belongs to no block.
+ *   ms_j = block_j / (4 fs / 10);  l_j = -0.691 + 10 log10(ms_j)
+ *   absolute gate: keep l_j > -70;  relative gate G = -0.691 + 10 log10(mean of the kept ms_j) - 10
+ *   L = -0.691 + 10 log10(mean of the ms_j with l_j > -70 and l_j > G);  L = -inf when no block survives.
+ *   A mean is (sum, count) over the blocks: thread t of 256 adds its blocks j = t, t + 256, ... in ascending order from 0.0, then
+ *   v[t] = v[t] + v[t + o] for o = 128, 64, .. 1.
+ *   DEVIATION from BS.1770: a row shorter than one block (nfull < 4; a TTS answer like "Yes." must still be levelled) is a single
+ *   block of its own length: ms = (the sum of its chunks' e_c in index order) / len_b, L = l when l > -70, else -inf.
+ * Peak: the SAMPLE peak max |x| over [0, len_b) (NaN samples are passed over).  True peak (oversampled) and loudness range are
+ * not computed.
+ * Gain (d_target fp32 [B] in LUFS; NaN, or a NULL d_target, means measure only):
+ *   g = (float)pow(10, ((double)target - L) / 20);  when peak * g > peak_ceiling in fp32, g = peak_ceiling / peak (one fp32 division),
+ *   lowered by one unit in the last place while peak * g still exceeds the ceiling, so that no output sample does: the ceiling acts on
+ *   the sample peak.  g = 1 exactly when L is not finite, the target is NaN, the row is empty or g is not finite.
+ * Apply (apply != 0): x = x * g, one fp32 multiply, on the samples [0, len_b) of the rows with g != 1; rows with g == 1 keep their
+ * bits and no sample at or beyond len_b is written.
+ * Outputs: d_lufs double [B] = L as measured BEFORE the gain, d_gain fp32 [B], d_peak fp32 [B] (before the gain).
+ * Every order above is a function of the row's length and fs alone: a row's L, g and samples are bit-identical whether it runs
+ * alone or in a batch, in any ld, and two calls give the same bits.
+ * Refusals (the ragged-batch contract): a length outside [0, ld] refuses that row -- d_lufs NaN, d_gain 1, d_peak 0, no sample
+ * read or written -- and the other rows are unaffected; d_lengths is not written, so a length that already is -1 (a row refused
+ * upstream) stays -1 for the stages behind.  mtts_loudness_status(d_ws, stream) -- the one entry here that waits for the stream --
+ * names the first refused row of the latest call on that workspace through mtts_last_error.  Header words (int64): first refused
+ * row + 1 or 0, its length (saturated to 32 bits), ld.
+ * Launches: (tile, row) zero-state chunks, one wave per row for the scan, (tile, row) energies, one workgroup per row for the
+ * gates, (tile, row) apply; a workgroup of the chunk passes holds MTTS_LOUDNESS_CHUNKS chunks, one per lane, its samples staged
+ * through LDS in slabs.  mtts_loudness_tile() = MTTS_LOUDNESS_TILE = the samples per such workgroup at 24 and 48 kHz (256 chunks of
+ * 240); at another rate it is MTTS_LOUDNESS_CHUNKS * mtts_loudness_chunk(fs).  Stream-ordered, no allocation, no synchronisation;
+ * one workspace of mtts_loudness_workspace_bytes(ld, B, sample_rate).  What the host can see returns -1 and launches nothing: null
+ * pointers, B outside [1, 65535], an ld that is no positive multiple of 4 or above 2^30, a bad rate, a misaligned d_audio / d_ws /
+ * d_lufs, a peak_ceiling that is not positive and finite, a small workspace. */
+#define MTTS_LOUDNESS_CHUNKS 256       /* chunks (= lanes) per workgroup of the chunk passes */
+#define MTTS_LOUDNESS_TILE 61440       /* samples per workgroup at 24 / 48 kHz */
+#define MTTS_LOUDNESS_SCAN_RUN 32      /* consecutive chunks a lane of the scan pass owns */
+int mtts_loudness_chunk(int sample_rate);
+int mtts_loudness_tile(void);
+int mtts_loudness_coefficients(int sample_rate, double* h_out);
+int64_t mtts_loudness_workspace_bytes(int64_t ld, int B, int sample_rate);
+int mtts_loudness(float* d_audio, int64_t ld, const int64_t* d_lengths, int B, int sample_rate, const float* d_target,
+                  float peak_ceiling, int apply, double* d_lufs, float* d_gain, float* d_peak, void* d_ws, int64_t ws_bytes,
+                  void* stream);
+int mtts_loudness_status(const void* d_ws, void* stream);
+
 /* ---------------------------------------------------------------- forced alignment (Monotonic Alignment Search) */
 
 /* Which fine mel frames belong to which token -- the alignment of the reference's training forward, matcha/models/matcha_tts.py:

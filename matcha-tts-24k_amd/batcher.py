@@ -46,6 +46,7 @@ class Request:
     encoding: Optional[str] = None          # "pcm16" / "ulaw" / "alaw": the result's "audio" is then raw bytes (a 1-D uint8 tensor) encoded on the device, and named in the result
     dither: bool = False                    # TPDF dither on a "pcm16" result
     dither_key: int = 0                     # selects the dither sequence: a field of the request, so its bytes do not depend on who shared its batch
+    loudness: Optional[float] = None        # target in LUFS (BS.1770 integrated loudness) the "audio" is brought to on the device at 24 kHz; the result then carries "loudness" (measured, before the gain) and "gain"
     future: Future = field(default_factory=Future, repr=False)
     t_submit: float = field(default_factory=time.monotonic, repr=False)
 
@@ -53,6 +54,9 @@ class Request:
         if self.encoding is not None:       # (an unknown name fails its own request here, not the batch it would have joined)
             from .audio_codec import format_id
             format_id(self.encoding)
+        if self.loudness is not None:       # (so does a target that is no level)
+            from .loudness import check_target
+            self.loudness = check_target(self.loudness)
 
     @property
     def group(self) -> Tuple[Any, ...]:
@@ -76,6 +80,15 @@ def encoding_fields(batch: List[Request]):
     if all(r.encoding is None for r in batch):
         return None, None, None
     return [r.encoding for r in batch], [bool(r.dither) for r in batch], [int(r.dither_key) for r in batch]
+
+
+def loudness_field(batch: List[Any]) -> Optional[List[Optional[float]]]:
+    """The loudness targets of a batch of units as ``waveforms_into`` / ``to_waveforms(loudness=...)`` take them: one entry per unit,
+    None for a unit without a target (its row runs with a NaN target and keeps its bits); None when no unit names one (the call is
+    then exactly the one made before there was a choice).  Pure function: unit-tested on the CPU."""
+    if all(u.loudness is None for u in batch):
+        return None
+    return [None if u.loudness is None else float(u.loudness) for u in batch]
 
 
 def plan_batch(waiting: List[Request], max_batch: int, max_tokens: int) -> List[int]:
@@ -110,10 +123,14 @@ class Document:
     encoding: Optional[str] = None
     dither: bool = False
     dither_key: int = 0
+    loudness: Optional[float] = None        # target in LUFS of the JOINED audio: one gain per document
     future: Future = field(default_factory=Future, repr=False)
     t_submit: float = field(default_factory=time.monotonic, repr=False)
 
     def __post_init__(self):
+        if self.loudness is not None:
+            from .loudness import check_target
+            self.loudness = check_target(self.loudness)
         if len(self.rows) == 0:
             raise ValueError("a document has at least one segment")
         if any(len(r.ids) == 0 for r in self.rows):
@@ -219,12 +236,12 @@ class FrameBudgetBatcher:
     def submit_document(self, segments_ids: Sequence[Sequence[int]], pauses_ms: Sequence[float], **request_fields) -> Future:
         """A text of several utterances: ``segments_ids`` the phoneme ids of each segment in speaking order, ``pauses_ms`` the silence
         after each (the last is ignored).  ``request_fields``: the fields of a ``Request`` -- voice, solver, speeds apply to every
-        segment; ``sample_rate`` / ``encoding`` / ``dither`` / ``dither_key`` to the joined result -- and ``level`` (``Document``).
+        segment; ``sample_rate`` / ``encoding`` / ``dither`` / ``dither_key`` / ``loudness`` to the joined result -- and ``level`` (``Document``).
         The segments run as rows of one ragged batch, together with whatever else is waiting, and are joined on the device.  One
         future: ``{"audio", "segments": [(start_s, end_s)] per segment, "mel_lengths"}``, plus ``"sample_rate"`` / ``"encoding"``
         when asked.  A document is admitted whole or not at all: more segments than ``max_batch`` or segments x longest above
         ``max_tokens`` raises ``ValueError`` here, as does an empty segment."""
-        once = {k: request_fields.pop(k) for k in ("level", "sample_rate", "encoding", "dither", "dither_key") if k in request_fields}
+        once = {k: request_fields.pop(k) for k in ("level", "sample_rate", "encoding", "dither", "dither_key", "loudness") if k in request_fields}
         segments = [list(ids) for ids in segments_ids]
         if any(len(ids) == 0 for ids in segments):
             raise ValueError("empty segment in a document")
@@ -304,13 +321,16 @@ def request_inputs(model, batch: List[Request]):
 
 def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_batch: bool, sample_rates: Optional[Sequence[int]] = None,
                    encodings: Optional[Sequence[Optional[str]]] = None, dithers: Optional[Sequence[bool]] = None,
-                   dither_keys: Optional[Sequence[int]] = None) -> None:
+                   dither_keys: Optional[Sequence[int]] = None, loudness: Optional[Sequence[Optional[float]]] = None) -> None:
     """``res[b]["audio"]`` for a batch of finished mels (``mel`` [B, n_feats, T], ``mel_lengths`` [B]; ``res[b]["mel"]`` the exact-length
     rows).  ``sample_rates``: one rate per request (default 24 kHz); rows that ask for another rate are converted on the device after
     the normalisation and the trim (``inference.to_waveforms``) and carry ``res[b]["sample_rate"]`` beside ``"audio"``.
     ``encodings``: one name or None per request; a row that names one is encoded on the device after that (``audio_codec.encode``,
     with the request's ``dithers`` flag and ``dither_keys`` entry), its ``"audio"`` is a 1-D uint8 tensor of raw samples and it
-    carries ``res[b]["encoding"]``.  A float result at 24 kHz keeps exactly the keys it had before there was a choice."""
+    carries ``res[b]["encoding"]``.  ``loudness``: one target in LUFS or None per request (``loudness_field``); a row that names one is
+    brought to it on the device at 24 kHz, ahead of the conversion and the encoder (``inference.to_waveforms(loudness=...)``), and
+    carries ``res[b]["loudness"]`` -- the LUFS measured before the gain -- and ``res[b]["gain"]``; the other rows keep their bits.
+    A float result at 24 kHz without a target keeps exactly the keys it had before there was a choice."""
     if vocoder is None:
         return
     B = len(res)
@@ -319,15 +339,28 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
     dith = [False] * B if dithers is None else [bool(v) for v in dithers]
     keys = [0] * B if dither_keys is None else [int(v) for v in dither_keys]
     coded = any(e is not None for e in encs)
+    loud = [None] * B if loudness is None else list(loudness)
+    levelled = any(v is not None for v in loud)
+    report = [None] * B
     if wave_batch:
         from .inference import to_waveforms
         extra = dict(encoding=encs, dither=dith, dither_keys=keys) if coded else {}
-        for r, a in zip(res, to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, **extra)):
+        if levelled:
+            audio, report = to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, loudness=loud, return_loudness=True, **extra)
+        else:
+            audio = to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, **extra)
+        for r, a in zip(res, audio):
             r["audio"] = a
     else:
         from .inference import _convert_rows, _waveform_on_device, trim_trailing_silence
-        for r, rate, enc, on, key in zip(res, rates, encs, dith, keys):
+        for b, (r, rate, enc, on, key) in enumerate(zip(res, rates, encs, dith, keys)):
             a = trim_trailing_silence(_waveform_on_device(r["mel"][None], vocoder).squeeze())
+            if loud[b] is not None and a.numel() > 0:
+                from . import loudness as LD
+                rows = torch.zeros(1, (a.numel() + 3) // 4 * 4, dtype=torch.float32, device=a.device)
+                rows[0, :a.numel()] = a
+                lufs, gain, _ = LD.normalize(rows, [a.numel()], loud[b], check=False)
+                a, report[b] = rows[0, :a.numel()], (float(lufs[0]), float(gain[0]))
             if rate != 24000 and a.numel() > 0:
                 conv, n = _convert_rows(a.reshape(1, -1), torch.tensor([a.numel()], dtype=torch.long, device=a.device), [rate])
                 a = conv[0, :int(n[0])]
@@ -339,11 +372,13 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
                 else:
                     a = torch.zeros(0, dtype=torch.uint8)
             r["audio"] = a.cpu()
-    for r, rate, enc in zip(res, rates, encs):
+    for r, rate, enc, target, rep in zip(res, rates, encs, loud, report):
         if rate != 24000:
             r["sample_rate"] = rate
         if enc is not None:
             r["encoding"] = enc
+        if target is not None and rep is not None:
+            r["loudness"], r["gain"] = float(rep[0]), float(rep[1])
 
 
 def synthesise_batch(model, batch: List[Any], vocoder=None, wave_batch: bool = True, fade_ms: float = 5.0) -> List[Dict[str, Any]]:
@@ -362,7 +397,8 @@ def synthesise_batch(model, batch: List[Any], vocoder=None, wave_batch: bool = T
                            durations=duration_rows(batch))
     lens = out["mel_lengths"].tolist()
     res = [{"mel": out["mel"][b, :, :int(lens[b])], "mel_length": int(lens[b])} for b in range(B)]
-    waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch, [r.sample_rate for r in batch], *encoding_fields(batch))
+    waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch, [r.sample_rate for r in batch], *encoding_fields(batch),
+                   loudness=loudness_field(batch))
     return res
 
 
@@ -388,11 +424,16 @@ def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> 
     gaps = [g for u in units for g in (u.gaps() if isinstance(u, Document) else [0])]
     encs, dith, keys = encoding_fields(units)
     extra = {} if encs is None else dict(encoding=encs, dither=dith, dither_keys=keys)
-    audio, segments = to_waveforms(out["mel"], out["mel_lengths"], vocoder, sample_rate=[int(u.sample_rate) for u in units],
-                                   documents=counts, gaps=gaps, fade_ms=fade_ms,
-                                   level=[u.level if isinstance(u, Document) else "sentence" for u in units], return_segments=True, **extra)
+    targets = loudness_field(units)
+    if targets is not None:
+        extra.update(loudness=targets, return_loudness=True)
+    out_w = to_waveforms(out["mel"], out["mel_lengths"], vocoder, sample_rate=[int(u.sample_rate) for u in units],
+                         documents=counts, gaps=gaps, fade_ms=fade_ms,
+                         level=[u.level if isinstance(u, Document) else "sentence" for u in units], return_segments=True, **extra)
+    audio, segments = out_w[0], out_w[1]
+    report = out_w[2] if targets is not None else [None] * len(units)
     res, b = [], 0
-    for u, n, a, seg in zip(units, counts, audio, segments):
+    for u, n, a, seg, rep in zip(units, counts, audio, segments, report):
         if isinstance(u, Document):
             r = {"audio": a, "segments": seg, "mel_lengths": lens[b:b + n]}
         else:
@@ -401,6 +442,8 @@ def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> 
             r["sample_rate"] = int(u.sample_rate)
         if u.encoding is not None:
             r["encoding"] = u.encoding
+        if u.loudness is not None and rep is not None:
+            r["loudness"], r["gain"] = float(rep[0]), float(rep[1])
         res.append(r)
         b += n
     return res
@@ -731,7 +774,7 @@ class StepBatcher:
             lengths = torch.tensor([r["mel_length"] for r in res], dtype=torch.long, device=mel.device)
             try:
                 waveforms_into(res, mel, lengths, self.vocoder, self.wave_batch, [e.request.sample_rate for e in finished],
-                               *encoding_fields([e.request for e in finished]))
+                               *encoding_fields([e.request for e in finished]), loudness=loudness_field([e.request for e in finished]))
             except BaseException as exc:  # noqa: BLE001 - the finishers only: who is mid-solve is not affected
                 self._fail([e.request for e in finished], exc)
                 return

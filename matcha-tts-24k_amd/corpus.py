@@ -111,6 +111,20 @@ def measure_silence(audio, lengths=None, sample_rate: int = 24000, effective_db:
 
 
 @torch.inference_mode()
+def measure_loudness(audio, lengths=None, sample_rate: int = 24000, check: bool = True) -> Dict[str, torch.Tensor]:
+    """Integrated loudness (ITU-R BS.1770 K-weighting and gates, ``loudness.measure``) and sample peak of every clip: what spots a
+    recording that is far too quiet or too hot before it is trained on.  ``audio`` / ``lengths`` as for ``measure_silence``; any
+    ``sample_rate`` that is a multiple of 100 in [8000, 192000].  Returns device tensors ``{"lufs": float64 [B], "peak": float32
+    [B]}``; -inf marks a clip with no block above the absolute gate of -70 LUFS.  Nothing is changed: the recordings keep their
+    level, since the mel statistics are computed without a level change.  A length outside ``[0, L]`` gives NaN in that row; with
+    ``check`` the call waits for that verdict and raises ``ValueError`` naming the row."""
+    from . import loudness as LD
+    wave, d_len = _batch(audio, lengths)
+    lufs, _, peak = LD._run(wave, d_len, sample_rate, None, LD.PEAK_CEILING, False, check)
+    return {"lufs": lufs, "peak": peak}
+
+
+@torch.inference_mode()
 def normalize_silence(audio, lengths=None, leading: Optional[float] = None, trailing: Optional[float] = None, threshold_db: float = -60.0,
                       sample_rate: int = 24000, check: bool = True) -> Tuple[torch.Tensor, torch.Tensor, Dict[str, torch.Tensor]]:
     """Every clip rebuilt with exactly ``leading`` / ``trailing`` seconds of zeros around its content (None leaves that end as

@@ -784,7 +784,8 @@ def finish_waveforms(audio, lengths, hop=0, silence_threshold_db=-60.0):
 
 @torch.inference_mode()
 def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, *, encoding=None, dither=False, dither_keys=None,
-                 documents=None, gaps=None, fade_ms=5.0, level="document", return_segments=False, sample_rate=24000):
+                 documents=None, gaps=None, fade_ms=5.0, level="document", return_segments=False, loudness=None, return_loudness=False,
+                 sample_rate=24000):
     """``trim_trailing_silence(to_waveform(mel[b:b+1, :, :len_b], vocoder))`` (reference inference.py:246) for every row of a
     ragged batch in one device pass: ragged Vocos decode, per-row peak normalisation, per-row trim lengths, then ONE copy of the
     audio and one of the [B] lengths -- one synchronisation for the whole batch.  Returns a list of B 1-D host tensors
@@ -812,9 +813,21 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     document): ``"document"`` gives a document one gain, that of its loudest sentence; ``"sentence"`` leaves each row the gain the
     normalisation gave it.
     ``return_segments``: also return, per document, ``[(start_s, end_s)]`` of its rows in seconds of the 24 kHz join (so they do
-    not depend on the output rate): ``(results, segments)``.  The single synchronisation stays."""
+    not depend on the output rate): ``(results, segments)``.  The single synchronisation stays.
+
+    ``loudness``: None (nothing below is launched or allocated), a target in LUFS, or one per row -- per document with
+    ``documents=`` -- where None leaves a row alone, bit for bit.  The rows that name one are brought to it on the device
+    (``loudness.normalize``: integrated loudness as in ITU-R BS.1770, one gain per row or document, limited so that the sample peak
+    stays at or under 0.95, the level the peak normalisation leaves).  The stage runs once, at 24 kHz: after the normalisation and the
+    trim, and after the join when there is one, so it sees one row per document on its device length; the rate conversion and the
+    encoder come behind it.  ``return_loudness``: also return ``[(lufs, gain)]`` per row or document -- the loudness measured BEFORE the
+    gain and the gain applied (1.0 for a row left alone); they ride in the one ``meta`` copy, so the single synchronisation stays.
+    With ``return_segments`` too the call returns ``(results, segments, loudness)``."""
     if documents is None and (gaps is not None or return_segments):
         raise ValueError("to_waveforms: gaps and return_segments belong to documents=")
+    if loudness is not None:                                           # (a target that is no level raises before anything is looked at)
+        from . import loudness as LD
+        LD.targets_per_row(loudness, 1 if isinstance(loudness, (int, float)) else len(loudness))
     if any(v not in ("document", "sentence") for v in ([level] if isinstance(level, str) else level)):
         raise ValueError(f"to_waveforms: level is 'document' or 'sentence' (or one of them per document), got {level!r}")
     model = vocoder.model if hasattr(vocoder, "model") else vocoder
@@ -828,25 +841,62 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     n_out = B if csr is None else len(csr) - 1
     rates = R.rates_per_row(sample_rate, n_out)
     encs = _encodings_per_row(encoding, n_out)                         # (an unknown name raises before anything is launched)
+    targets = _loudness_targets(loudness, n_out, return_loudness)     # (so does a target that is no level)
+    loud, report = [], []
     audio = model.decode(mel, mel_lengths, check=False)
     out_lengths, scale = finish_waveforms(audio, mel_lengths, hop=hop, silence_threshold_db=silence_threshold_db)
     if csr is not None:
         keep = out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1))
         fade = int(round(float(fade_ms) * SAMPLE_RATE / 1000.0))
-        return _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, _document_scales(scale, level, csr), rates, encs,
-                                 dither, dither_keys, return_segments)
+        res = _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, _document_scales(scale, level, csr), rates, encs,
+                                dither, dither_keys, return_segments, targets, report)
+        if not return_loudness:
+            return res
+        return (*res, report) if return_segments else (res, report)
+    if targets is not None:
+        audio, loud = _loudness_stage(audio, out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1)), targets)
     if any(r != SAMPLE_RATE for r in rates):
         audio, out_lengths = _convert_rows(audio, out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1)),
                                            rates)
     if encs is not None:
-        return _encoded_rows(audio, out_lengths, mel_lengths, hop, T, trim, rates, encs, dither, dither_keys)
-    meta = torch.stack([out_lengths, mel_lengths]).cpu()              # waits for the stream: the batch's one synchronisation
+        res = _encoded_rows(audio, out_lengths, mel_lengths, hop, T, trim, rates, encs, dither, dither_keys, loud, report)
+        return (res, report) if return_loudness else res
+    meta = torch.stack([out_lengths, mel_lengths] + loud).cpu()       # waits for the stream: the batch's one synchronisation
     host = audio.cpu()
     keep, frames = meta[0].tolist(), meta[1].tolist()
     for b in range(B):
         if keep[b] < 0:
             raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
-    return [host[b, : (keep[b] if trim or rates[b] != SAMPLE_RATE else hop * (frames[b] - 1))] for b in range(B)]
+    res = [host[b, : (keep[b] if trim or rates[b] != SAMPLE_RATE else hop * (frames[b] - 1))] for b in range(B)]
+    if not return_loudness:
+        return res
+    _loudness_report(meta[2:], report)
+    return res, report
+
+
+def _loudness_targets(loudness, n, measure):
+    """``loudness=`` of ``to_waveforms`` as n targets with NaN for "leave the row alone"; None when the stage does not run (no row
+    names a target and no measurement is asked for).  A value that is no level raises here, before anything is launched."""
+    if loudness is None and not measure:
+        return None
+    from . import loudness as LD
+    targets = LD.targets_per_row(loudness, n)
+    return [float("nan")] * n if targets is None and measure else targets
+
+
+def _loudness_stage(audio, lengths, targets):
+    """The loudness stage of ``to_waveforms``: ``audio`` [n, L] at 24 kHz on its device lengths, in place (a padded copy when L is no
+    multiple of 4).  Returns the rows and what rides in the ``meta`` copy: the bits of the measured LUFS and of the gains as int64."""
+    from . import loudness as LD
+    rows, _ = _hip.aligned_rows(audio, 4, "audio")
+    lufs, gain, _ = LD.normalize(rows, lengths, targets, SAMPLE_RATE, LD.PEAK_CEILING, check=False)
+    return rows, [lufs.view(torch.long), gain.to(torch.float64).view(torch.long)]
+
+
+def _loudness_report(words, report):
+    """``[(lufs, gain)]`` from the two int64 rows of the ``meta`` copy (a host tensor [2, n], or a flat list of 2 n words)."""
+    vals = torch.as_tensor(words, dtype=torch.long).reshape(2, -1).contiguous().view(torch.float64).tolist()
+    report.extend(zip(vals[0], vals[1]))
 
 
 _join_ws = _hip.Workspaces()
@@ -934,7 +984,8 @@ def _document_scales(scale, level, csr):
     return torch.where(own, torch.ones_like(scale), scale)
 
 
-def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates, encs, dither, dither_keys, return_segments):
+def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates, encs, dither, dither_keys, return_segments,
+                      targets=None, report=None):
     """The end of ``to_waveforms`` with ``documents=``: the join at 24 kHz, then the rate conversion and the encoding over one row
     per document on the joined device lengths, then the batch's one synchronisation -- the joined lengths, the rows' starts and kept
     lengths ride in the one ``meta`` copy -- and one copy of no more columns than the longest document has."""
@@ -942,9 +993,12 @@ def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates
     G = len(csr) - 1
     dev = audio.device
     wave, lens, starts = join_waveforms(audio, keep, csr, gaps, fade=fade, scale=scale, check=False)
+    loud = []
+    if targets is not None:                                            # one row per document, on its joined device length
+        wave, loud = _loudness_stage(wave, lens, targets)
     if any(r != SAMPLE_RATE for r in rates):
         wave, lens = _convert_rows(wave, lens, rates)
-    words = [lens, starts, keep, mel_lengths]
+    words = [lens, starts, keep, mel_lengths] + loud
     if encs is not None:
         named = torch.tensor([e is not None for e in encs], dtype=torch.bool, device=dev)
         fmt = [AC.PCM16 if e is None else e for e in encs]
@@ -955,6 +1009,10 @@ def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates
     meta = torch.cat(words).cpu().tolist()                             # waits for the stream: the batch's one synchronisation
     B = keep.shape[0]
     got, begin, kept, frames = meta[:G], meta[G:G + B], meta[G + B:G + 2 * B], meta[G + 2 * B:G + 3 * B]
+    at = G + 3 * B                                                     # what rides behind the lengths: loudness words, byte counts
+    if loud and report is not None:
+        _loudness_report(meta[at:at + 2 * G], report)
+    at += 2 * G * bool(loud)
     for b in range(B):
         if kept[b] < 0:
             raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
@@ -966,7 +1024,7 @@ def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates
     if encs is None:
         res = [floats[g, :got[g]] for g in range(G)]
     else:
-        nb = meta[G + 3 * B:]
+        nb = meta[at:]
         host = data[:, :max(max(nb), 1)].cpu()
         res = [floats[g, :got[g]] if encs[g] is None else host[g, :nb[g]] for g in range(G)]
     if not return_segments:
@@ -988,7 +1046,7 @@ def _encodings_per_row(encoding, B):
     return encs if any(e is not None for e in encs) else None
 
 
-def _encoded_rows(audio, out_lengths, mel_lengths, hop, T, trim, rates, encs, dither, dither_keys):
+def _encoded_rows(audio, out_lengths, mel_lengths, hop, T, trim, rates, encs, dither, dither_keys, loud=(), report=None):
     """The end of ``to_waveforms`` when rows name an encoding: one encode launch over the finished (and converted) rows on their
     device lengths, then the batch's one synchronisation and the copy of the bytes.  Rows without an encoding take part in the
     launch with length 0 and are returned float32 from a second copy, of the audio."""
@@ -1007,8 +1065,10 @@ def _encoded_rows(audio, out_lengths, mel_lengths, hop, T, trim, rates, encs, di
     on = [bool(dither)] * B if isinstance(dither, (bool, int)) else [bool(v) for v in dither]
     data, nbytes = AC.encode(audio, torch.where(named, keep_dev, torch.zeros_like(keep_dev)), fmt,
                              dither=on if len(set(on)) > 1 else on[0], keys=dither_keys)
-    meta = torch.stack([keep_dev, mel_lengths, nbytes]).cpu()          # waits for the stream: the batch's one synchronisation
-    keep, frames, got = (m.tolist() for m in meta)
+    meta = torch.stack([keep_dev, mel_lengths, nbytes, *loud]).cpu()   # waits for the stream: the batch's one synchronisation
+    keep, frames, got = (m.tolist() for m in meta[:3])
+    if len(loud) and report is not None:
+        _loudness_report(meta[3:], report)
     for b in range(B):
         if keep[b] < 0 or got[b] < 0:
             raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
@@ -1066,20 +1126,30 @@ def trim_trailing_silence(audio, silence_threshold_db=-60.0):
 
 @torch.inference_mode()
 def pipeline(model, vocoder, text, speaker=0, voice_mix=None, n_timesteps=DEFAULT_NUM_STEPS, scale_correction=1.0,
-             length_scale=1.0, debug=False, *, encoding=None, sample_rate=24000):
+             length_scale=1.0, debug=False, *, encoding=None, loudness=None, sample_rate=24000):
     """reference inference.py:233-257.  The reference wraps ``synthesise`` in ``torch.autocast`` (fp16 on its CUDA device);
     here the estimator's arithmetic is chosen when the model is created (``MTTS_GEMM_TERMS``: default fp32-equivalent; 1 = fp16
     operands / fp32 accumulate, the autocast arithmetic), not per call.  The trailing-silence trim runs on the device.
     ``sample_rate``: the rate of the returned waveform; anything but 24 kHz is converted on the device after the normalisation and
     the trim (``resample.resample``; the band-limited result may overshoot the 0.95 peak slightly, nothing is re-normalised).
     ``encoding``: None (a float32 waveform), or ``"pcm16"`` / ``"ulaw"`` / ``"alaw"``: the waveform is encoded on the device
-    (``audio_codec.encode``) and returned as a 1-D uint8 host tensor of raw samples."""
+    (``audio_codec.encode``) and returned as a 1-D uint8 host tensor of raw samples.
+    ``loudness``: None, or a target in LUFS the waveform is brought to on the device (``loudness.normalize``: BS.1770 integrated
+    loudness, the sample peak held at or under 0.95), at 24 kHz after the trim and ahead of the rate conversion and the encoder."""
+    from . import loudness as LD
+    target = LD.check_target(loudness)                                 # (a value that is no level raises before anything runs)
     primary = voice_mix[0][0] if voice_mix is not None else speaker
     language = next(v["lang"] for v in VOICES if v["id"] == str(primary))
     tp = process_text(text, language)
     out = model.synthesise(tp["x"], tp["x_lengths"], n_timesteps=n_timesteps, speaker=speaker, voice_mix=voice_mix,
                            scale_correction=scale_correction, length_scale=length_scale, debug=debug)
     waveform = trim_trailing_silence(_waveform_on_device(out["mel"], vocoder).squeeze())
+    if target is not None and waveform.numel() > 0:
+        n = waveform.numel()
+        rows = torch.zeros(1, (n + 3) // 4 * 4, dtype=torch.float32, device=waveform.device)
+        rows[0, :n] = waveform
+        LD.normalize(rows, [n], target, SAMPLE_RATE, check=False)
+        waveform = rows[0, :n]
     if int(sample_rate) != SAMPLE_RATE and waveform.numel() > 0:
         from . import resample as R
         conv, _ = R.resample(waveform.reshape(1, -1), None, SAMPLE_RATE, int(sample_rate), check=False)

@@ -91,6 +91,9 @@ def request_params(voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, 
     return SpeechParams(speaker, mix, language, scale_correction, length_scale, int(steps), solver)
 
 
+_SERVICE = object()      # default of ``submit_long / speak_long(loudness=)``: the service's own target
+
+
 class SpeechService:
     """``await service.speak(text, voice, speed, steps, solver)`` -> 1-D waveform tensor on the host (``bytes`` with ``response_format``).
 
@@ -98,10 +101,22 @@ class SpeechService:
     ``FrameBudgetBatcher`` or a ``StepBatcher`` (same ``submit`` contract; the second schedules at the solver step, so requests with
     different ``steps`` share launches) built with ``vocoder=`` so that results carry ``"audio"``."""
 
-    def __init__(self, batcher, phonemize: Callable[[str, str], Sequence[int]], max_text_length: int = MAX_TEXT_LENGTH):
+    def __init__(self, batcher, phonemize: Callable[[str, str], Sequence[int]], max_text_length: int = MAX_TEXT_LENGTH,
+                 loudness: Optional[float] = None):
+        """``loudness``: None, or the target in LUFS every request of this service is brought to on the device (BS.1770 integrated
+        loudness, ``loudness.normalize``; typically -16, -19 or -23).  ``levelled(target)`` gives a view of the service with another
+        target, for one request: ``await service.levelled(-16).speak(text)``."""
+        from .loudness import check_target
         self.batcher = batcher
         self.phonemize = phonemize
         self.max_text_length = int(max_text_length)
+        self.loudness = check_target(loudness)
+
+    def levelled(self, loudness: Optional[float]) -> "SpeechService":
+        """This service -- the same batcher and front end -- with ``loudness`` as its target (None: none).  A value that is no level
+        raises here, before anything is submitted.  ``submit`` and ``speak`` keep their positional signatures, so the target of a
+        single request is named this way; ``submit_long`` and ``speak_long`` also take ``loudness=`` themselves."""
+        return SpeechService(self.batcher, self.phonemize, self.max_text_length, loudness)
 
     def submit(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
                speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None):
@@ -110,7 +125,8 @@ class SpeechService:
         of the result's ``"audio"`` (8 or 16 kHz for telephony, 48 kHz for a browser); the batcher converts on the device.
         ``response_format``: None (float samples), ``"pcm"`` (raw s16le), ``"wav"`` (the same samples; ``speak`` adds the RIFF
         header), ``"ulaw"`` / ``"alaw"`` (raw G.711), all at ``sample_rate`` and encoded on the device; an unknown name raises
-        ``ValueError`` before anything is submitted."""
+        ``ValueError`` before anything is submitted.  With a loudness target (the service's, or ``levelled(target)``) the result
+        also carries ``"loudness"`` -- the LUFS measured before the gain -- and ``"gain"``."""
         encoding = response_encoding(response_format)
         if len(text) > self.max_text_length:
             raise ValueError(f"Text exceeds {self.max_text_length} characters")       # the handler's HTTP 400
@@ -121,6 +137,8 @@ class SpeechService:
             extra["sample_rate"] = int(sample_rate)
         if encoding is not None:
             extra["encoding"] = encoding
+        if self.loudness is not None:
+            extra["loudness"] = self.loudness
         return self.batcher.submit(ids, speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver, n_timesteps=p.n_timesteps,
                                    scale_correction=p.scale_correction, length_scale=p.length_scale, **extra)
 
@@ -132,15 +150,18 @@ class SpeechService:
 
     def submit_long(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
                     speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None,
-                    max_document_length: int = MAX_DOCUMENT_LENGTH, **split_options):
+                    max_document_length: int = MAX_DOCUMENT_LENGTH, *, loudness=_SERVICE, **split_options):
         """A text longer than one utterance: cut into sentences (``longform.split_text(text, **split_options)``; the abbreviation set
         is that of the voice's language unless given), each phonemized on its own -- so the phonemizer's intonation marks stay per
         sentence --, and submitted as ONE document (``FrameBudgetBatcher.submit_document``): the sentences run as rows of one ragged
         batch and are joined on the device with the splitter's pauses between them.  The other arguments are ``submit``'s and apply to
         the joined result.  The future's result carries ``"audio"`` and ``"segments"`` (seconds of each sentence in the 24 kHz join).
         A batcher without ``submit_document`` raises ``TypeError``: there is no host-side join to fall back to.  ``submit`` and its
-        cap are unchanged."""
+        cap are unchanged.  ``loudness``: the target in LUFS of the JOINED audio -- one gain per document, so its sentences keep
+        their balance -- or None; by default the service's own.  The result then carries ``"loudness"`` and ``"gain"``."""
         encoding = response_encoding(response_format)
+        from .loudness import check_target
+        target = self.loudness if loudness is _SERVICE else check_target(loudness)
         if not hasattr(self.batcher, "submit_document"):
             raise TypeError(f"{type(self.batcher).__name__} has no submit_document: long texts need a FrameBudgetBatcher")
         if len(text) > int(max_document_length):
@@ -157,15 +178,17 @@ class SpeechService:
             extra["sample_rate"] = int(sample_rate)
         if encoding is not None:
             extra["encoding"] = encoding
+        if target is not None:
+            extra["loudness"] = target
         return self.batcher.submit_document(ids, [pause for _, pause in pieces], speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver,
                                             n_timesteps=p.n_timesteps, scale_correction=p.scale_correction, length_scale=p.length_scale,
                                             **extra)
 
     async def speak_long(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
                          speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None,
-                         max_document_length: int = MAX_DOCUMENT_LENGTH, **split_options):
+                         max_document_length: int = MAX_DOCUMENT_LENGTH, *, loudness=_SERVICE, **split_options):
         """The joined waveform of a long text (a 1-D float tensor on the host), or with ``response_format`` the response body as
         ``bytes`` -- ``response_body``, as ``speak``."""
         res = await asyncio.wrap_future(self.submit_long(text, voice, speed, steps, solver, speaker_embedding, sample_rate, response_format,
-                                                         max_document_length, **split_options))
+                                                         max_document_length, loudness=loudness, **split_options))
         return response_body(res, response_format, int(sample_rate))

@@ -6,6 +6,7 @@ normalize_silence.py, generate_data_statistics.py and precompute_mels.py do, as 
     python tools/prepare_corpus.py normalize -i configs/data/corpus-24k.yaml --target_leading_silence 0.2 --target_trailing_silence 0.8
     python tools/prepare_corpus.py stats     -i configs/data/corpus-24k.yaml
     python tools/prepare_corpus.py mels      -i configs/data/corpus-24k.yaml
+    python tools/prepare_corpus.py loudness  -i configs/data/corpus-24k.yaml
     python tools/prepare_corpus.py measure --synthetic 4 [--root DIR]     # no files needed: a small corpus is written first
     python tools/prepare_corpus.py time --synthetic 32 [--seconds 10] [--repeat 20]     # per-call times, nothing is written
 
@@ -24,6 +25,9 @@ normalize  rewrites every wav in place with the standard ``wave`` module: the fi
 stats      prints the ``data_statistics:`` block for the YAML.
 mels       writes ``<mel_dir>/<rel>.npy`` (n_mels, T) and ``.fine.npy`` at half the hop, ``metadata.json`` and, if any file
            failed, ``failures.txt``, in the layout the reference's trainer reads; files that are already there are kept.
+loudness   prints integrated loudness (LUFS, ITU-R BS.1770 gating) and sample peak of every file of the train and validation
+           filelists and the corpus median, and marks files more than ``--loudness_margin`` dB from it: recordings that are far too
+           quiet or too hot.  Nothing is rewritten: the mel statistics are computed without a level change.
 time       HIP-event times of the device calls on N synthetic clips of ``--seconds`` (median, min .. max of ``--repeat``), and
            the wall time of the NumPy restatement (tests/corpus_restated.py) of the same batch; profiles/r14_corpus.md.
 """
@@ -164,6 +168,36 @@ def cmd_measure(args, cfg, corpus) -> int:
     for what, eff, ab in (("Leading silence per speaker, ms", 0, 1), ("Trailing silence per speaker, ms", 2, 3)):
         print()
         print(silence_table(what, {k: v[:, eff] for k, v in by.items()}, {k: v[:, ab] for k, v in by.items()}, *dbs))
+    return 0
+
+
+# ---------------------------------------------------------------------------------------------------------------- loudness
+def loudness_report(rows, margin: float) -> str:
+    """``rows``: [(rel, lufs, peak)].  One line per file, then the median over the files with a finite loudness; a file further than
+    ``margin`` dB from it, or with no block above the absolute gate, is marked."""
+    finite = [l for _, l, _ in rows if np.isfinite(l)]
+    median = statistics.median(finite) if finite else float("nan")
+    lines = []
+    for rel, lufs, peak in rows:
+        mark = "" if np.isfinite(lufs) and abs(lufs - median) <= margin else "   <-- silent" if not np.isfinite(lufs) else \
+            f"   <-- {lufs - median:+.1f} dB from the median"
+        lines.append(f"{rel:<24} {lufs:8.2f} LUFS   peak {peak:.4f}{mark}")
+    lines.append(f"[prepare_corpus] {len(rows)} files, {len(finite)} with a finite loudness, median {median:.2f} LUFS")
+    return "\n".join(lines)
+
+
+def cmd_loudness(args, cfg, corpus) -> int:
+    valid = cfg.get("valid_filelist_path") or None
+    items = entries([resolve(cfg["train_filelist_path"]), resolve(valid) if valid else None])
+    rows = []
+    for its, clips, rates in batches(items, args.batch):
+        for rate in sorted(set(rates)):                              # the K-weighting follows each file's own rate
+            sel = [i for i, r in enumerate(rates) if r == rate]
+            got = corpus.measure_loudness([clips[i] for i in sel], None, rate)
+            lufs, peak = got["lufs"].cpu().tolist(), got["peak"].cpu().tolist()
+            rows += [(its[i][0], lufs[k], peak[k]) for k, i in enumerate(sel)]
+    rows.sort(key=lambda r: r[0])
+    print(loudness_report(rows, args.loudness_margin))
     return 0
 
 
@@ -371,7 +405,7 @@ def cmd_time(args, corpus) -> int:
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("command", choices=["measure", "normalize", "stats", "mels", "time"])
+    ap.add_argument("command", choices=["measure", "normalize", "stats", "mels", "loudness", "time"])
     ap.add_argument("-i", "--data-config", help="data YAML (e.g. configs/data/corpus-24k.yaml)")
     ap.add_argument("--synthetic", type=int, default=0, help="write and use a synthetic corpus of N clips instead of -i")
     ap.add_argument("--root", help="where --synthetic keeps its corpus (default: a temporary directory); reused when it is already there")
@@ -381,6 +415,7 @@ def main() -> int:
     ap.add_argument("--target_leading_silence", type=float, default=None, help="seconds, a multiple of 10 ms")
     ap.add_argument("--target_trailing_silence", type=float, default=None, help="seconds, a multiple of 10 ms")
     ap.add_argument("--threshold_db", type=float, default=-60.0)
+    ap.add_argument("--loudness_margin", type=float, default=6.0, help="loudness: mark files further than this many dB from the median")
     ap.add_argument("--report", help="normalize: write per-file bounds and deltas as JSON")
     ap.add_argument("--seconds", type=float, default=10.0, help="time: length of the synthetic clips' content")
     ap.add_argument("--repeat", type=int, default=20, help="time: timed calls")
@@ -406,7 +441,7 @@ def main() -> int:
     else:
         ap.error("give -i DATA_YAML or --synthetic N")
     cfg = load_config(args.config)
-    rc = {"measure": cmd_measure, "normalize": cmd_normalize, "stats": cmd_stats, "mels": cmd_mels}[args.command](args, cfg, corpus)
+    rc = {"measure": cmd_measure, "normalize": cmd_normalize, "stats": cmd_stats, "mels": cmd_mels, "loudness": cmd_loudness}[args.command](args, cfg, corpus)
     if keep is not None:
         keep.cleanup()
     return rc

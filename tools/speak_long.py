@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A text longer than one utterance to one wav file: sentences as rows of one ragged batch, joined on the device.
 
-    python tools/speak_long.py speak --matcha CKPT --vocos CKPT TEXT.txt OUT.wav [--voice 0 --speed 1.0 --steps 4 --sample-rate 24000]
+    python tools/speak_long.py speak --matcha CKPT --vocos CKPT TEXT.txt OUT.wav [--voice 0 --speed 1.0 --steps 4 --sample-rate 24000 --loudness LUFS]
     python tools/speak_long.py speak --matcha CKPT --vocos CKPT --segments-file FILE OUT.wav
     python tools/speak_long.py time [--sentences 20 --tokens 100 --repeat 10] [--utterance | --kernels]     # random weights, no files
 
@@ -9,7 +9,8 @@
 (``process_text``) when that imports.  Where it does not, ``--segments-file`` takes the text already cut and phonemized: one
 segment per line, whitespace-separated phoneme ids, then ``|`` and the pause behind it in milliseconds (``12 7 33 | 300``), as
 tools/align.py takes ids.  The document goes through ``FrameBudgetBatcher.submit_document``; OUT.wav is RIFF PCM16 at
-``--sample-rate``, encoded on the device.  The sentences' times are printed.
+``--sample-rate``, encoded on the device.  ``--loudness LUFS`` brings the joined document to that integrated loudness (ITU-R BS.1770,
+one gain for the document, the sample peak held at 0.95) on the device, ahead of the rate conversion.  The sentences' times are printed.
 
 ``time``: a document of ``--sentences`` sentences of about ``--tokens`` tokens on random prod-shaped weights (a text of about
 sentences x tokens characters), timed per call with a host clock around calls that end in the result on the host, alternating
@@ -72,14 +73,17 @@ def speak(args) -> int:
         pauses = [ms for _, ms in pieces]
     if not ids:
         raise SystemExit("nothing to speak")
+    extra = {} if args.loudness is None else {"loudness": args.loudness}
     with bt.FrameBudgetBatcher(model, max_batch=max(32, len(ids)), max_tokens=max(8192, len(ids) * max(len(s) for s in ids)),
                                vocoder=vocoder, fade_ms=args.fade_ms) as q:
         res = q.submit_document(ids, pauses, speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver, n_timesteps=p.n_timesteps,
                                 scale_correction=p.scale_correction, length_scale=p.length_scale, sample_rate=args.sample_rate,
-                                encoding="pcm16", level=args.level).result()
+                                encoding="pcm16", level=args.level, **extra).result()
     Path(args.out).write_bytes(sv.response_body(res, "wav", args.sample_rate))
     for n, (t0, t1) in enumerate(res["segments"]):
         print(f"{n:4d}  {t0:9.3f} s .. {t1:9.3f} s")
+    if "loudness" in res:
+        print(f"loudness {res['loudness']:.2f} LUFS as synthesised, gain {res['gain']:.4f} towards {args.loudness:.2f} LUFS")
     print(f"wrote {args.out}: {res['audio'].numel() // 2} samples at {args.sample_rate} Hz, {len(ids)} sentences")
     return 0
 
@@ -205,6 +209,7 @@ def main() -> int:
     sp.add_argument("--max-chars", type=int, default=300)
     sp.add_argument("--fade-ms", type=float, default=5.0)
     sp.add_argument("--level", choices=("document", "sentence"), default="document")
+    sp.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="integrated loudness of the joined document, e.g. -16, -19, -23")
     tm = cmds.add_parser("time", help="per-call times on random weights")
     tm.add_argument("--sentences", type=int, default=20)
     tm.add_argument("--tokens", type=int, default=100)
