@@ -481,6 +481,43 @@ int mtts_groupnorm_mish_p16(const float* d_y, const float* d_gamma, const float*
                             const int* d_nrows, const int* d_nextra, const float* d_bias_stats, const float* d_out16_mask, float* d_out,
                             float* d_out16_f32, unsigned int* d_range_flag, void* d_scratch, void* stream);
 
+/* The two fused kernels (tblock_chain_kernel, conv_gn_kernel) on argument blocks, with what the plain entries above cannot pass: the
+ * range flag, image rows longer than their payload, and the RAW output images.  Every output image has pad_* extra halves per row
+ * (% 8 == 0) and MTTS_ENTRY_GUARD_ROWS rows behind its last row; the entry fills the whole image with `sentinel` (a 16-bit pattern)
+ * before the launch, so whatever the kernel did not write still holds it.  Input images with a pad get the sentinel in their pad
+ * columns too (0x7e00, an fp16 NaN, poisons any product that reads them).  d_*_image (may be NULL): [rows + guard][2 * width + pad]
+ * halves, copied from the entry's scratch after the launch.  `tag` is written by the call (as mtts_last_kernel_tag).
+ * Chain: operands as mtts_tblock_chain (h_* on the HOST); pair != 0: the pair form.  conv_gn: operands as mtts_conv_gn_rows
+ * (chbias_stride 0: one row for the batch).  Host code only: the kernels launched are the ones the model launches. */
+#define MTTS_ENTRY_GUARD_ROWS 64
+typedef struct mtts_chain_args {
+    const float* d_att; const float* d_x; int32_t M, C, inner;
+    const float* h_w_out; const float* h_b_out; const float* h_w1; const float* h_b1; const float* h_p0; const float* h_p1;
+    const float* h_w2; const float* h_b2; const float* h_w_qkv; const float* h_b_qkv; int32_t n_qkv;
+    const float* d_out_mask; int32_t qb, ch, pair;
+    int32_t pad_att, pad_x, pad_out, pad_qkv;                                        /* extra halves per image row */
+    uint32_t sentinel;
+    uint32_t* d_range_flag;                                                          /* passed to the kernel (may be NULL) */
+    float* d_x_out; float* d_qkv_out;                                                /* decoded images [M][C], [M][n_qkv] */
+    uint16_t* d_x_out_image; uint16_t* d_qkv_image;                                  /* raw images incl. pad and guard rows, or NULL */
+    char tag[124];
+} mtts_chain_args;
+int64_t mtts_tblock_chain_args_scratch_bytes(const mtts_chain_args* g);
+int mtts_tblock_chain_args_run(mtts_chain_args* g, void* d_scratch, void* stream);
+typedef struct mtts_conv_gn_args {
+    const float* d_x; int32_t B, T, C, c1; const float* d_w; void* d_wpacked; const float* d_bias; int32_t N;
+    const float* d_gamma; const float* d_beta; const float* d_mask; const float* d_chbias; int32_t chbias_stride;
+    const int32_t* d_nrows; const int32_t* d_nextra; const float* d_bias_stats; float eps;
+    int32_t pad_x, pad_out;
+    uint32_t sentinel;
+    uint32_t* d_range_flag;
+    float* d_out;                                                                    /* decoded image [B*T][N] */
+    uint16_t* d_out_image;                                                           /* raw image [B*T + guard][2 N + pad_out] or NULL */
+    char tag[124];
+} mtts_conv_gn_args;
+int64_t mtts_conv_gn_args_scratch_bytes(const mtts_conv_gn_args* g);
+int mtts_conv_gn_args_run(mtts_conv_gn_args* g, void* d_scratch, void* stream);
+
 /* Row statistics for LayerNorm over C (biased variance, eps inside rsqrt): mean[M], rstd[M]. */
 int mtts_row_stats(const float* d_x, int M, int C, int ld, float eps, float* d_mean, float* d_rstd, void* stream);
 

@@ -71,6 +71,38 @@ def _deps(src: Path, seen=None):
     return seen
 
 
+class MttsChainArgs(C.Structure):
+    """include/mtts.h mtts_chain_args, field for field."""
+    _fields_ = [
+        ("d_att", C.c_void_p), ("d_x", C.c_void_p), ("M", C.c_int32), ("C", C.c_int32), ("inner", C.c_int32),
+        ("h_w_out", C.c_void_p), ("h_b_out", C.c_void_p), ("h_w1", C.c_void_p), ("h_b1", C.c_void_p), ("h_p0", C.c_void_p), ("h_p1", C.c_void_p),
+        ("h_w2", C.c_void_p), ("h_b2", C.c_void_p), ("h_w_qkv", C.c_void_p), ("h_b_qkv", C.c_void_p), ("n_qkv", C.c_int32),
+        ("d_out_mask", C.c_void_p), ("qb", C.c_int32), ("ch", C.c_int32), ("pair", C.c_int32),
+        ("pad_att", C.c_int32), ("pad_x", C.c_int32), ("pad_out", C.c_int32), ("pad_qkv", C.c_int32),
+        ("sentinel", C.c_uint32),
+        ("d_range_flag", C.c_void_p),
+        ("d_x_out", C.c_void_p), ("d_qkv_out", C.c_void_p),
+        ("d_x_out_image", C.c_void_p), ("d_qkv_image", C.c_void_p),
+        ("tag", C.c_char * 124)]
+
+
+class MttsConvGnArgs(C.Structure):
+    """include/mtts.h mtts_conv_gn_args, field for field."""
+    _fields_ = [
+        ("d_x", C.c_void_p), ("B", C.c_int32), ("T", C.c_int32), ("C", C.c_int32), ("c1", C.c_int32), ("d_w", C.c_void_p),
+        ("d_wpacked", C.c_void_p), ("d_bias", C.c_void_p), ("N", C.c_int32),
+        ("d_gamma", C.c_void_p), ("d_beta", C.c_void_p), ("d_mask", C.c_void_p), ("d_chbias", C.c_void_p), ("chbias_stride", C.c_int32),
+        ("d_nrows", C.c_void_p), ("d_nextra", C.c_void_p), ("d_bias_stats", C.c_void_p), ("eps", C.c_float),
+        ("pad_x", C.c_int32), ("pad_out", C.c_int32),
+        ("sentinel", C.c_uint32),
+        ("d_range_flag", C.c_void_p),
+        ("d_out", C.c_void_p),
+        ("d_out_image", C.c_void_p),
+        ("tag", C.c_char * 124)]
+
+
+ENTRY_GUARD_ROWS = 64     # include/mtts.h MTTS_ENTRY_GUARD_ROWS
+
 BUILD_MODE = "not built in this process"     # what the last build() call did (printed by __graft_entry__.build)
 
 
@@ -195,6 +227,10 @@ def load() -> C.CDLL:
                                           i32, C.POINTER(C.c_float)]),
         "mtts_tblock_chain_pair_timed": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp,
                                           i32, C.POINTER(C.c_float)]),
+        "mtts_tblock_chain_args_scratch_bytes": (i64, [C.POINTER(MttsChainArgs)]),
+        "mtts_tblock_chain_args_run": (i32, [C.POINTER(MttsChainArgs), vp, vp]),
+        "mtts_conv_gn_args_scratch_bytes": (i64, [C.POINTER(MttsConvGnArgs)]),
+        "mtts_conv_gn_args_run": (i32, [C.POINTER(MttsConvGnArgs), vp, vp]),
         "mtts_chain_stream_frags_h16": (i64, [i32, i32, i32, i32]),
         "mtts_chain_stream_pack_h16": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(C.c_int)]),
         "mtts_tblock_chain_h16_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
@@ -1121,6 +1157,63 @@ def tblock_chain(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, b_qkv
     if repeat:
         return x_out, qkv, ms.value
     return x_out, qkv
+
+
+def tblock_chain_args(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, b_qkv=None, out_mask=None, qb=64, ch=128, pair=False,
+                      pad_att=0, pad_x=0, pad_out=0, pad_qkv=0, sentinel=0x7e00):
+    """The chain on its argument block (include/mtts.h mtts_chain_args): ``tblock_chain`` with the range flag, padded image rows and
+    the raw output images.  Returns a dict: x_out, qkv (decoded fp32), x_out_image [M + guard, 2 C + pad_out] and qkv_image
+    [M + guard, 2 n_qkv + pad_qkv] (int16 bits, sentinel wherever the kernel did not write), flag (device uint32 [2], zeroed before
+    the launch: range word, pair-timeout word) and tag."""
+    lib = load()
+    M, Cc = x.shape
+    inner = att.shape[1] if att is not None else 0
+    n_qkv = w_qkv.shape[0] if w_qkv is not None else 0
+    keep = [_host(t) for t in (w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv, b_qkv)]
+    g = MttsChainArgs()
+    g.d_att, g.d_x, g.M, g.C, g.inner, g.n_qkv = ptr(att), ptr(x), M, Cc, inner, n_qkv
+    for name, k in zip(("h_w_out", "h_b_out", "h_w1", "h_b1", "h_p0", "h_p1", "h_w2", "h_b2", "h_w_qkv", "h_b_qkv"), keep):
+        setattr(g, name, k[1])
+    g.d_out_mask, g.qb, g.ch, g.pair = ptr(out_mask), qb, ch, int(bool(pair))
+    g.pad_att, g.pad_x, g.pad_out, g.pad_qkv, g.sentinel = pad_att, pad_x, pad_out, pad_qkv, sentinel
+    n = size(lib.mtts_tblock_chain_args_scratch_bytes(C.byref(g)))
+    dev = x.device
+    scratch = torch.empty(n, dtype=torch.uint8, device=dev)
+    flag = torch.zeros(2, dtype=torch.int32, device=dev)
+    x_out = torch.empty(M, Cc, dtype=torch.float32, device=dev)
+    qkv = torch.empty(M, n_qkv, dtype=torch.float32, device=dev) if n_qkv else None
+    x_img = torch.empty(M + ENTRY_GUARD_ROWS, 2 * Cc + pad_out, dtype=torch.int16, device=dev)
+    q_img = torch.empty(M + ENTRY_GUARD_ROWS, 2 * n_qkv + pad_qkv, dtype=torch.int16, device=dev) if n_qkv else None
+    g.d_range_flag, g.d_x_out, g.d_qkv_out, g.d_x_out_image, g.d_qkv_image = ptr(flag), ptr(x_out), ptr(qkv), ptr(x_img), ptr(q_img)
+    check(lib.mtts_tblock_chain_args_run(C.byref(g), scratch.data_ptr(), stream_ptr()))
+    torch.cuda.synchronize()
+    return {"x_out": x_out, "qkv": qkv, "x_out_image": x_img, "qkv_image": q_img, "flag": flag, "tag": g.tag.decode()}
+
+
+def conv_gn_args(x, w, bias, gamma, beta, mask, *, B, T, c1=0, chbias=None, nrows=None, nextra=None, bias_stats=None, eps=1e-5,
+                 pad_x=0, pad_out=0, sentinel=0x7e00):
+    """The one-launch Block1D on its argument block (include/mtts.h mtts_conv_gn_args): ``conv_gn`` / ``conv_gn_rows`` (chbias [N] or
+    [B, stride >= N]) with the range flag, padded image rows and the raw output image.  Returns a dict: out (decoded fp32 [B*T, N]),
+    image [B*T + guard, 2 N + pad_out] (int16 bits), flag (device uint32 [1], zeroed before the launch) and tag."""
+    lib = load()
+    N, Cc = w.shape[0], w.shape[1]
+    dev = x.device
+    g = MttsConvGnArgs()
+    g.d_x, g.B, g.T, g.C, g.c1, g.N, g.eps = ptr(x), B, T, Cc, c1, N, float(eps)
+    wc = w.contiguous()
+    packed = torch.empty(lib.mtts_gemm_packed_bytes(N, Cc, 3), dtype=torch.uint8, device=dev)
+    g.d_w, g.d_wpacked, g.d_bias, g.d_gamma, g.d_beta, g.d_mask = ptr(wc), packed.data_ptr(), ptr(bias), ptr(gamma), ptr(beta), ptr(mask)
+    g.d_chbias, g.chbias_stride = ptr(chbias), (chbias.shape[1] if chbias is not None and chbias.dim() == 2 else 0)
+    g.d_nrows, g.d_nextra, g.d_bias_stats = ptr(nrows), ptr(nextra), ptr(bias_stats)
+    g.pad_x, g.pad_out, g.sentinel = pad_x, pad_out, sentinel
+    scratch = torch.empty(size(lib.mtts_conv_gn_args_scratch_bytes(C.byref(g))), dtype=torch.uint8, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    out = torch.empty(B * T, N, dtype=torch.float32, device=dev)
+    img = torch.empty(B * T + ENTRY_GUARD_ROWS, 2 * N + pad_out, dtype=torch.int16, device=dev)
+    g.d_range_flag, g.d_out, g.d_out_image = ptr(flag), ptr(out), ptr(img)
+    check(lib.mtts_conv_gn_args_run(C.byref(g), scratch.data_ptr(), stream_ptr()))
+    torch.cuda.synchronize()
+    return {"out": out, "image": img, "flag": flag, "tag": g.tag.decode()}
 
 
 def tblock_chain_h16(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, b_qkv=None, out_mask=None, bf16=False, qb=64, ch=128,

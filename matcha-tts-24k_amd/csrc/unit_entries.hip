@@ -418,6 +418,140 @@ int mtts_tblock_chain_pair_timed(const float* d_att, const float* d_x, int M, in
                               d_out_mask, qb, ch, d_x_out, d_qkv_out, d_scratch, stream, repeat, h_ms);
 }
 
+// ---- the two fused kernels on argument blocks (include/mtts.h mtts_chain_args, mtts_conv_gn_args): range flag, padded image rows,
+// guard rows and the raw output images.  Scratch is carved in 256-byte steps; every image is filled with the sentinel first.
+static size_t up256(size_t n) { return (n + 255) & ~size_t(255); }
+static bool bad_pad(int p) { return p < 0 || (p & 7) || p > 4096; }
+static int chain_args_check(const mtts_chain_args* g, int* n_qkv) {
+    if (!g) { set_error("mtts_tblock_chain_args: null argument block"); return -1; }
+    *n_qkv = g->h_w_qkv ? g->n_qkv : 0;
+    if (g->M <= 0 || g->M > (1 << 20) || !chain_supported(g->C, g->inner, *n_qkv) || (g->ch != 128 && g->ch != 256)) { set_error("mtts_tblock_chain_args: unsupported shape"); return -1; }
+    if (g->pair && !chain_supported_pair(g->C, g->inner, g->ch, *n_qkv)) { set_error("mtts_tblock_chain_args: unsupported shape for the pair form"); return -1; }
+    if (bad_pad(g->pad_att) || bad_pad(g->pad_x) || bad_pad(g->pad_out) || bad_pad(g->pad_qkv)) { set_error("mtts_tblock_chain_args: a row pad is a multiple of 8 halves in [0, 4096]"); return -1; }
+    if (g->sentinel > 0xffffu) { set_error("mtts_tblock_chain_args: the sentinel is a 16-bit pattern"); return -1; }
+    return 0;
+}
+int64_t mtts_tblock_chain_args_scratch_bytes(const mtts_chain_args* g) {
+    int n_qkv = 0;
+    RET_IF(chain_args_check(g, &n_qkv));
+    const int64_t M = g->M, Mg = M + MTTS_ENTRY_GUARD_ROWS, C = g->C;
+    const int64_t frags = g->pair ? 2 * chain_stream_frags_pair(g->C, g->inner, g->ch, n_qkv) : chain_stream_frags(g->C, g->inner, g->ch, n_qkv);
+    int64_t n = up256(frags * CHAIN_WAVES * 1024) + up256(4 * (18 * C + 2 * n_qkv));
+    n += up256(M * (2 * g->inner + g->pad_att) * 2) + up256(M * (2 * C + g->pad_x) * 2);
+    n += up256(Mg * (2 * C + g->pad_out) * 2) + up256(Mg * (2 * n_qkv + g->pad_qkv) * 2);
+    n += up256(2 * Mg * C * 4) + up256(2 * (M / 32 + 2) * 4);            // partial sums + flags of the pair form
+    return n + 256;
+}
+int mtts_tblock_chain_args_run(mtts_chain_args* g, void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int n_qkv = 0;
+    RET_IF(chain_args_check(g, &n_qkv));
+    g->tag[0] = 0;
+    if (!g->d_x || !g->h_w1 || !g->h_w2 || !g->h_p0 || !g->h_p1 || !d_scratch || !g->d_x_out || (g->inner && (!g->d_att || !g->h_w_out)) || (n_qkv && !g->d_qkv_out)) {
+        set_error("mtts_tblock_chain_args: null buffer");
+        return -1;
+    }
+    const int M = g->M, Mg = M + MTTS_ENTRY_GUARD_ROWS, C = g->C, inner = g->inner;
+    const bool pair = g->pair != 0;
+    const long frags = pair ? chain_stream_frags_pair(C, inner, g->ch, n_qkv) : chain_stream_frags(C, inner, g->ch, n_qkv);
+    std::vector<uint16_t> hs((size_t)frags * (pair ? 2 : 1) * CHAIN_WAVES * 512);
+    if (pair) chain_stream_pack_pair(C, inner, g->ch, n_qkv, g->h_w_out, g->h_w1, g->h_w2, g->h_w_qkv, hs.data(), nullptr);
+    else chain_stream_pack(C, inner, g->ch, n_qkv, g->h_w_out, g->h_w1, g->h_w2, g->h_w_qkv, hs.data(), nullptr);
+    const std::vector<float> hc = chain_entry_consts(C, inner, n_qkv, g->h_b_out, g->h_w1, g->h_b1, g->h_p0, g->h_p1, g->h_b2, g->h_w_qkv, g->h_b_qkv, plain_row_sum, false);
+    const int ld_att = 2 * inner + g->pad_att, ld_x = 2 * C + g->pad_x, ld_out = 2 * C + g->pad_out, ld_qkv = 2 * n_qkv + g->pad_qkv;
+    uintptr_t sc = up256(reinterpret_cast<uintptr_t>(d_scratch));
+    auto carve = [&](size_t bytes) { char* q = reinterpret_cast<char*>(sc); sc += up256(bytes); return q; };
+    void* d_stream = carve(hs.size() * 2);
+    float* d_c = reinterpret_cast<float*>(carve(hc.size() * 4));
+    _Float16* att16 = reinterpret_cast<_Float16*>(carve((size_t)M * ld_att * 2));
+    _Float16* x16 = reinterpret_cast<_Float16*>(carve((size_t)M * ld_x * 2));
+    _Float16* xo16 = reinterpret_cast<_Float16*>(carve((size_t)Mg * ld_out * 2));
+    _Float16* q16 = reinterpret_cast<_Float16*>(carve((size_t)Mg * ld_qkv * 2));
+    float* d_part = reinterpret_cast<float*>(carve(2 * (size_t)Mg * C * 4));
+    unsigned int* d_flag = reinterpret_cast<unsigned int*>(carve(2 * ((size_t)M / 32 + 2) * 4));
+    HIP_OK(hipMemcpyAsync(d_stream, hs.data(), hs.size() * 2, hipMemcpyHostToDevice, s));
+    HIP_OK(hipMemcpyAsync(d_c, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));                      // (the host vectors go out of scope)
+    const unsigned short fill = (unsigned short)g->sentinel;
+    if (inner) {
+        if (g->pad_att) HIP_OK(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(att16), fill, (size_t)M * ld_att, s));
+        HIP_OK(launch_to_p16(g->d_att, inner, nullptr, M, inner, inner, att16, ld_att, 2048.0f, s));
+    }
+    if (g->pad_x) HIP_OK(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(x16), fill, (size_t)M * ld_x, s));
+    HIP_OK(launch_to_p16(g->d_x, C, nullptr, M, C, C, x16, ld_x, 2048.0f, s));
+    HIP_OK(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(xo16), fill, (size_t)Mg * ld_out, s));
+    if (n_qkv) HIP_OK(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(q16), fill, (size_t)Mg * ld_qkv, s));
+    ChainArgs a;
+    a.M = M; a.C = C; a.inner = inner; a.att16 = att16; a.ld_att = ld_att; a.x16 = x16; a.ld_x = ld_x;
+    a.wstream = static_cast<decltype(a.wstream)>(d_stream); a.stream_frags = frags; a.consts = d_c;
+    if (n_qkv) { a.wsum_qkv = d_c + 18 * C; a.b_qkv = d_c + 18 * C + n_qkv; a.n_qkv = n_qkv; a.qkv16 = q16; a.ld_qkv = ld_qkv; }
+    a.x_out = xo16; a.ld_out = ld_out; a.x_out_mask = g->d_out_mask; a.qb = g->qb; a.ch = g->ch;
+    a.range_flag = g->d_range_flag;
+    a.pf_wgs = read_switches().chain_pf;
+    if (pair) {
+        HIP_OK(hipMemsetAsync(d_flag, 0, 2 * ((size_t)M / 32 + 2) * 4, s));
+        a.pair = 1; a.pair_part = d_part; a.pair_flag = d_flag; a.pair_epoch = 1; a.pf_wgs = a.pf_wgs ? 16 : 0;
+    }
+    g_kernel_tag = nullptr;
+    HIP_OK(launch_tblock_chain(a, s));
+    if (g_kernel_tag) { std::strncpy(g->tag, g_kernel_tag, sizeof(g->tag) - 1); g->tag[sizeof(g->tag) - 1] = 0; }
+    if (g->d_x_out_image) HIP_OK(hipMemcpyAsync(g->d_x_out_image, xo16, (size_t)Mg * ld_out * 2, hipMemcpyDeviceToDevice, s));
+    if (n_qkv && g->d_qkv_image) HIP_OK(hipMemcpyAsync(g->d_qkv_image, q16, (size_t)Mg * ld_qkv * 2, hipMemcpyDeviceToDevice, s));
+    HIP_OK(launch_from_p16(xo16, ld_out, M, C, 2048.0f, g->d_x_out, C, s));
+    if (n_qkv) HIP_OK(launch_from_p16(q16, ld_qkv, M, n_qkv, 1.0f, g->d_qkv_out, n_qkv, s));
+    return 0;
+}
+
+static int conv_gn_args_check(const mtts_conv_gn_args* g) {
+    if (!g) { set_error("mtts_conv_gn_args: null argument block"); return -1; }
+    if (g->B <= 0 || g->B > 4096 || g->C <= 0 || (g->C % 32) || g->c1 < 0 || (g->c1 % 32) || g->c1 >= g->C) { set_error("mtts_conv_gn_args: C and c1 must be multiples of 32, c1 < C"); return -1; }
+    if (!conv_gn_supported(g->T, g->N)) { set_error("mtts_conv_gn_args: unsupported shape (N = 384, 65 <= T <= 384)"); return -1; }
+    if (bad_pad(g->pad_x) || bad_pad(g->pad_out)) { set_error("mtts_conv_gn_args: a row pad is a multiple of 8 halves in [0, 4096]"); return -1; }
+    if (g->sentinel > 0xffffu) { set_error("mtts_conv_gn_args: the sentinel is a 16-bit pattern"); return -1; }
+    if (g->d_chbias && g->chbias_stride && (g->chbias_stride < g->N || (g->chbias_stride & 3))) { set_error("mtts_conv_gn_args: a bias row per utterance has at least N values (stride % 4 == 0)"); return -1; }
+    if ((g->d_nextra != nullptr) != (g->d_bias_stats != nullptr)) { set_error("mtts_conv_gn_args: nextra and bias_stats come together"); return -1; }
+    return 0;
+}
+int64_t mtts_conv_gn_args_scratch_bytes(const mtts_conv_gn_args* g) {
+    RET_IF(conv_gn_args_check(g));
+    const int64_t rows = (int64_t)g->B * g->T;
+    return up256(rows * (2 * g->C + g->pad_x) * 2) + up256((rows + MTTS_ENTRY_GUARD_ROWS) * (2 * g->N + g->pad_out) * 2) + 256;
+}
+int mtts_conv_gn_args_run(mtts_conv_gn_args* g, void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RET_IF(conv_gn_args_check(g));
+    g->tag[0] = 0;
+    if (!g->d_x || !g->d_w || !g->d_wpacked || !g->d_bias || !g->d_gamma || !g->d_beta || !g->d_mask || !d_scratch || !g->d_out) { set_error("mtts_conv_gn_args: null buffer"); return -1; }
+    const int B = g->B, T = g->T, C = g->C, c1 = g->c1, N = g->N, rows = B * T, rows_g = rows + MTTS_ENTRY_GUARD_ROWS;
+    const int Np = round_up(N, GEMM_BN), Kp = 3 * C;
+    const size_t npanel = (size_t)Np * Kp;
+    float* planes = static_cast<float*>(g->d_wpacked) + ((npanel + 63) & ~size_t(63));
+    HIP_OK(launch_pack_weight(g->d_w, N, C, 3, static_cast<float*>(g->d_wpacked), s));
+    HIP_OK(launch_split_panel_f16(static_cast<const float*>(g->d_wpacked), npanel, planes, s));
+    const int ld_x = 2 * C + g->pad_x, ld_out = 2 * N + g->pad_out;
+    uintptr_t sc = up256(reinterpret_cast<uintptr_t>(d_scratch));
+    auto carve = [&](size_t bytes) { char* q = reinterpret_cast<char*>(sc); sc += up256(bytes); return q; };
+    _Float16* a16 = reinterpret_cast<_Float16*>(carve((size_t)rows * ld_x * 2));
+    _Float16* o16 = reinterpret_cast<_Float16*>(carve((size_t)rows_g * ld_out * 2));
+    const unsigned short fill = (unsigned short)g->sentinel;
+    if (g->pad_x) HIP_OK(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(a16), fill, (size_t)rows * ld_x, s));
+    HIP_OK(launch_to_p16(g->d_x, C, nullptr, rows, C, C, a16, ld_x, 2048.0f, s));
+    HIP_OK(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(o16), fill, (size_t)rows_g * ld_out, s));
+    ConvGnArgs a;
+    a.a16_0 = a16; a.lda16_0 = ld_x; a.c0 = C - c1;
+    if (c1) { a.a16_1 = a16 + 2 * (C - c1); a.lda16_1 = ld_x; a.c1 = c1; }
+    a.w16 = planes; a.bias = g->d_bias; a.B = B; a.T = T; a.N = N;
+    a.gamma = g->d_gamma; a.beta = g->d_beta; a.mask = g->d_mask; a.chbias = g->d_chbias; a.chbias_stride = g->d_chbias ? g->chbias_stride : 0;
+    a.nrows = g->d_nrows; a.nextra = g->d_nextra; a.bias_stats = g->d_bias_stats;
+    a.eps = g->eps > 0.f ? g->eps : 1e-5f; a.out16 = o16; a.ld16 = ld_out; a.range_flag = g->d_range_flag;
+    g_kernel_tag = nullptr;
+    HIP_OK(launch_conv_gn(a, s));
+    if (g_kernel_tag) { std::strncpy(g->tag, g_kernel_tag, sizeof(g->tag) - 1); g->tag[sizeof(g->tag) - 1] = 0; }
+    if (g->d_out_image) HIP_OK(hipMemcpyAsync(g->d_out_image, o16, (size_t)rows_g * ld_out * 2, hipMemcpyDeviceToDevice, s));
+    HIP_OK(launch_from_p16(o16, ld_out, rows, N, 2048.0f, g->d_out, N, s));
+    return 0;
+}
+
 // ---- the one-plane chain of the 16-bit storage modes (tblock_chain_h16.hip): host-only stream functions and the unit entry
 int64_t mtts_chain_stream_frags_h16(int C, int inner, int ch, int n_qkv) {
     if (!chain_h16_supported(C, inner, ch, n_qkv)) { set_error("mtts_chain_stream_frags_h16: unsupported shape"); return -1; }

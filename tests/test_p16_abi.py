@@ -14,7 +14,8 @@ from conftest import ROOT, sub
 from p16_restated import heads, image_bits, p16, split
 
 NEW = ["mtts_to_p16_roundtrip", "mtts_gemm_p16_args_scratch_bytes", "mtts_gemm_p16_args_run", "mtts_attention_p16_run",
-       "mtts_groupnorm_p16_scratch_bytes", "mtts_groupnorm_mish_p16"]
+       "mtts_groupnorm_p16_scratch_bytes", "mtts_groupnorm_mish_p16",
+       "mtts_tblock_chain_args_scratch_bytes", "mtts_tblock_chain_args_run", "mtts_conv_gn_args_scratch_bytes", "mtts_conv_gn_args_run"]
 FAKE = 0x1000          # a non-null "pointer" for buffers a refused call must not touch
 
 
@@ -57,7 +58,7 @@ def test_new_entries_are_declared_exported_and_bound_with_matching_arity_and_typ
             else:
                 assert bound is want or (C.sizeof(bound) == C.sizeof(want) and (bound is C.c_float) == (want is C.c_float)), (name, decl, bound)
     assert lib.mtts_abi_version() == 2
-    for wrapper in ("gemm_p16_args", "attention_p16_run", "groupnorm_mish_p16", "to_p16_roundtrip"):
+    for wrapper in ("gemm_p16_args", "attention_p16_run", "groupnorm_mish_p16", "to_p16_roundtrip", "tblock_chain_args", "conv_gn_args"):
         assert callable(getattr(hip, wrapper))
 
 
