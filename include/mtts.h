@@ -933,8 +933,8 @@ int mtts_pcm_status(const int64_t* d_verdict, int B, void* stream);
  *   v[t] = v[t] + v[t + o] for o = 128, 64, .. 1.
  *   DEVIATION from BS.1770: a row shorter than one block (nfull < 4; a TTS answer like "Yes." must still be levelled) is a single
  *   block of its own length: ms = (the sum of its chunks' e_c in index order) / len_b, L = l when l > -70, else -inf.
- * Peak: the SAMPLE peak max |x| over [0, len_b) (NaN samples are passed over).  True peak (oversampled) and loudness range are
- * not computed.
+ * Peak: the SAMPLE peak max |x| over [0, len_b) (NaN samples are passed over).  True peak (oversampled) and loudness range:
+ * mtts_loudness_r128 below.
  * Gain (d_target fp32 [B] in LUFS; NaN, or a NULL d_target, means measure only):
  *   g = (float)pow(10, ((double)target - L) / 20);  when peak * g > peak_ceiling in fp32, g = peak_ceiling / peak (one fp32 division),
  *   lowered by one unit in the last place while peak * g still exceeds the ceiling, so that no output sample does: the ceiling acts on
@@ -967,6 +967,56 @@ int mtts_loudness(float* d_audio, int64_t ld, const int64_t* d_lengths, int B, i
                   float peak_ceiling, int apply, double* d_lufs, float* d_gain, float* d_peak, void* d_ws, int64_t ws_bytes,
                   void* stream);
 int mtts_loudness_status(const void* d_ws, void* stream);
+
+/* mtts_loudness_r128: mtts_loudness, and with it the true peak, the loudness range, the maximum momentary and the maximum short-term
+ * loudness of every row (EBU R 128 / Tech 3341 / Tech 3342), and a second ceiling on the gain, on the true peak.  d_lufs, d_peak and
+ * -- with no true-peak ceiling -- d_gain and the samples are bit for bit those of mtts_loudness on the same rows; tests/r128_restated.py
+ * restates what is new.
+ *
+ * True peak.  The row is read at F times its rate: F = 8 for fs < 48000, 4 for 48000 <= fs < 96000, 2 for fs >= 96000.  The
+ * interpolator is a Hann-windowed sinc of half-width 6 input samples, MTTS_TRUE_PEAK_TAPS = 12 taps per phase, the class of filter
+ * of BS.1770-4 Annex 2: for phase p in [1, F) and tap k in [0, 12)
+ *   d = (k - 5) - p / F;  w[p][k] = sin(pi d) / (pi d) * 0.5 (1 + cos(pi d / 6));  h[p][k] = (float)(w[p][k] / sum_k w[p][k])
+ * built on the host in fp64 (the sum in ascending k from 0.0) and rounded once to fp32, so every phase reads DC exactly.  Phase 0 is the
+ * sample itself and is not filtered.  mtts_true_peak_filter(fs, h_out, F_out) -- host only, no device needed -- writes F and the F * 12
+ * words h[p][k] (row 0: the unit impulse at tap 5).  The value at j + p / F, for every j in [0, len_b), is
+ *   v = sum_k h[p][k] x[j - 5 + k]     x = 0 outside [0, len_b); fp32; each product rounded, then added in ascending k from 0.0f
+ * and true_peak_b = the maximum over |x[j]| and every |v|, taken with fmaxf: NaN samples and NaN sums are passed over, as for the
+ * sample peak.  A maximum has no order, so a row's true peak does not depend on B, ld, the grid or the tile.  Known error of the
+ * estimator (profiles/r21_r128.md): on a steady sine anywhere up to 0.45 fs the 12-tap reading lies between 0.15 dB under and 0.07 dB
+ * over that of a 129-tap interpolation (the sample peak alone: up to 3.01 dB under); a sine that starts or stops inside the row reads
+ * up to 0.1 dB over its amplitude at that edge, where the taps see the step.
+ *
+ * Maximum momentary loudness: the maximum of l_j over the 400 ms blocks above, ungated; the single block's l for a row under
+ * 400 ms (the deviation above); -inf for an empty row.
+ * Short-term blocks (3 s): S_k = seg_k + seg_k+1 + ... + seg_k+29 in ascending index from 0.0, at every whole segment k <= nfull - 30
+ * (a 100 ms hop); ms_k = S_k / (30 fs / 10).  Maximum short-term loudness: the maximum of -0.691 + 10 log10(ms_k); -inf when nfull < 30.
+ * Loudness range (EBU Tech 3342): keep the blocks with l_k > -70; the relative gate is -0.691 + 10 log10(mean of the kept ms_k) - 20,
+ * the mean as (sum, count) in the reduction shape of the integrated gate; of the n blocks above both gates in ascending order of ms,
+ *   lo = the element at index (10 (n - 1) + 50) / 100,  hi = the element at index (95 (n - 1) + 50) / 100   (integer division)
+ *   lra = (-0.691 + 10 log10(hi)) - (-0.691 + 10 log10(lo));  lra = 0 when n == 0 or nfull < 30.
+ * The two order statistics are exact (a radix select on the bit patterns of the non-negative doubles, no tolerance) and depend on
+ * nothing but the row.
+ *
+ * Gain: the rule above (target, then the sample-peak ceiling), and then, with c_tp = (float)pow(10, true_peak_ceiling_db / 20): when
+ * true_peak * g > c_tp in fp32, g = c_tp / true_peak, lowered by one unit in the last place up to 4 times while the product still
+ * exceeds c_tp.  true_peak_ceiling_db is in dBTP, finite and <= 0; NaN means none, and g is then that of mtts_loudness bit for bit.
+ * The ceiling acts only on rows that have a target: a row without one, an empty row and a row whose L is not finite keep g == 1
+ * and their bits.
+ * Outputs beyond those of mtts_loudness: d_true_peak fp32 [B] (linear, before the gain), d_lra, d_momentary_max, d_short_term_max
+ * double [B].  A refused row gives NaN for the four loudness figures, 0 for both peaks and gain 1.  The same refusals and the same
+ * verdict header, read by mtts_loudness_status.  Launches: the chunk, scan and energy kernels of mtts_loudness, the (tile, row)
+ * true-peak pass (MTTS_TRUE_PEAK_TILE samples and a halo of 5 + 6 per workgroup, one float out), one workgroup per row for the gates
+ * and the selection, the apply pass.  One workspace of mtts_loudness_r128_workspace_bytes(ld, B, sample_rate). */
+#define MTTS_TRUE_PEAK_TILE 4096       /* samples per workgroup of the true-peak pass */
+#define MTTS_TRUE_PEAK_TAPS 12         /* taps per phase of the interpolator */
+int mtts_true_peak_tile(void);
+int mtts_true_peak_filter(int sample_rate, float* h_out, int* F_out);
+int64_t mtts_loudness_r128_workspace_bytes(int64_t ld, int B, int sample_rate);
+int mtts_loudness_r128(float* d_audio, int64_t ld, const int64_t* d_lengths, int B, int sample_rate, const float* d_target,
+                       float peak_ceiling, float true_peak_ceiling_db, int apply, double* d_lufs, float* d_gain, float* d_peak,
+                       float* d_true_peak, double* d_lra, double* d_momentary_max, double* d_short_term_max, void* d_ws,
+                       int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- forced alignment (Monotonic Alignment Search) */
 

@@ -320,6 +320,10 @@ def load() -> C.CDLL:
         "mtts_loudness_workspace_bytes": (i64, [i64, i32, i32]),
         "mtts_loudness": (i32, [vp, i64, vp, i32, i32, vp, f32, i32, vp, vp, vp, vp, i64, vp]),
         "mtts_loudness_status": (i32, [vp, vp]),
+        "mtts_true_peak_tile": (i32, []),
+        "mtts_true_peak_filter": (i32, [i32, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+        "mtts_loudness_r128_workspace_bytes": (i64, [i64, i32, i32]),
+        "mtts_loudness_r128": (i32, [vp, i64, vp, i32, i32, vp, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
         "mtts_style_create": (vp, [i32, i32, i32, i32]),
         "mtts_style_destroy": (None, [vp]),
         "mtts_style_set_tensor": (i32, [vp, C.c_char_p, vp, i64]),

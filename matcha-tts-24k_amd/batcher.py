@@ -47,6 +47,7 @@ class Request:
     dither: bool = False                    # TPDF dither on a "pcm16" result
     dither_key: int = 0                     # selects the dither sequence: a field of the request, so its bytes do not depend on who shared its batch
     loudness: Optional[float] = None        # target in LUFS (BS.1770 integrated loudness) the "audio" is brought to on the device at 24 kHz; the result then carries "loudness" (measured, before the gain) and "gain"
+    true_peak: Optional[float] = None       # ceiling in dBTP on the true peak of the levelled "audio" (needs ``loudness``); the result then also carries "true_peak" (dBTP, measured before the gain) and "lra"
     future: Future = field(default_factory=Future, repr=False)
     t_submit: float = field(default_factory=time.monotonic, repr=False)
 
@@ -57,6 +58,7 @@ class Request:
         if self.loudness is not None:       # (so does a target that is no level)
             from .loudness import check_target
             self.loudness = check_target(self.loudness)
+        self.true_peak = _checked_ceiling(self.true_peak, self.loudness)
 
     @property
     def group(self) -> Tuple[Any, ...]:
@@ -89,6 +91,41 @@ def loudness_field(batch: List[Any]) -> Optional[List[Optional[float]]]:
     if all(u.loudness is None for u in batch):
         return None
     return [None if u.loudness is None else float(u.loudness) for u in batch]
+
+
+def _checked_ceiling(true_peak, loudness):
+    """``true_peak`` of a request or a document as a float or None; it limits a gain, so one without a target is refused."""
+    if true_peak is None:
+        return None
+    from .loudness import check_true_peak
+    ceiling = check_true_peak(true_peak)
+    if loudness is None:
+        raise ValueError(f"true_peak = {true_peak!r} limits the gain towards a loudness target, and the request names none (loudness=)")
+    return ceiling
+
+
+def true_peak_field(batch: List[Any]) -> Optional[List[Optional[float]]]:
+    """The true-peak ceilings of a batch of units as ``waveforms_into`` / ``to_waveforms(true_peak=...)`` take them: one entry in dBTP
+    per unit, None for a unit that names none; None when no unit names one (the call is then exactly the one made before there was
+    a choice).  Pure function: unit-tested on the CPU."""
+    if all(u.true_peak is None for u in batch):
+        return None
+    return [None if u.true_peak is None else float(u.true_peak) for u in batch]
+
+
+def report_into(r: Dict[str, Any], rep, target, ceiling=None) -> None:
+    """What a levelled result says of its loudness stage: ``"loudness"`` (LUFS before the gain) and ``"gain"`` from ``rep`` -- a
+    ``(lufs, gain)`` pair, or the dict of ``to_waveforms(return_meter=True)`` -- and, for a unit that named a true-peak ceiling,
+    ``"true_peak"`` in dBTP (before the gain) and ``"lra"`` in LU.  Pure function: unit-tested on the CPU."""
+    if target is None or rep is None:
+        return
+    if isinstance(rep, dict):
+        r["loudness"], r["gain"] = float(rep["lufs"]), float(rep["gain"])
+        if ceiling is not None:
+            from .loudness import dbtp
+            r["true_peak"], r["lra"] = dbtp(rep["true_peak"]), float(rep["lra"])
+    else:
+        r["loudness"], r["gain"] = float(rep[0]), float(rep[1])
 
 
 def plan_batch(waiting: List[Request], max_batch: int, max_tokens: int) -> List[int]:
@@ -124,6 +161,7 @@ class Document:
     dither: bool = False
     dither_key: int = 0
     loudness: Optional[float] = None        # target in LUFS of the JOINED audio: one gain per document
+    true_peak: Optional[float] = None       # ceiling in dBTP on the true peak of the joined, levelled audio (needs ``loudness``)
     future: Future = field(default_factory=Future, repr=False)
     t_submit: float = field(default_factory=time.monotonic, repr=False)
 
@@ -131,6 +169,7 @@ class Document:
         if self.loudness is not None:
             from .loudness import check_target
             self.loudness = check_target(self.loudness)
+        self.true_peak = _checked_ceiling(self.true_peak, self.loudness)
         if len(self.rows) == 0:
             raise ValueError("a document has at least one segment")
         if any(len(r.ids) == 0 for r in self.rows):
@@ -236,12 +275,12 @@ class FrameBudgetBatcher:
     def submit_document(self, segments_ids: Sequence[Sequence[int]], pauses_ms: Sequence[float], **request_fields) -> Future:
         """A text of several utterances: ``segments_ids`` the phoneme ids of each segment in speaking order, ``pauses_ms`` the silence
         after each (the last is ignored).  ``request_fields``: the fields of a ``Request`` -- voice, solver, speeds apply to every
-        segment; ``sample_rate`` / ``encoding`` / ``dither`` / ``dither_key`` / ``loudness`` to the joined result -- and ``level`` (``Document``).
+        segment; ``sample_rate`` / ``encoding`` / ``dither`` / ``dither_key`` / ``loudness`` / ``true_peak`` to the joined result -- and ``level`` (``Document``).
         The segments run as rows of one ragged batch, together with whatever else is waiting, and are joined on the device.  One
         future: ``{"audio", "segments": [(start_s, end_s)] per segment, "mel_lengths"}``, plus ``"sample_rate"`` / ``"encoding"``
         when asked.  A document is admitted whole or not at all: more segments than ``max_batch`` or segments x longest above
         ``max_tokens`` raises ``ValueError`` here, as does an empty segment."""
-        once = {k: request_fields.pop(k) for k in ("level", "sample_rate", "encoding", "dither", "dither_key", "loudness") if k in request_fields}
+        once = {k: request_fields.pop(k) for k in ("level", "sample_rate", "encoding", "dither", "dither_key", "loudness", "true_peak") if k in request_fields}
         segments = [list(ids) for ids in segments_ids]
         if any(len(ids) == 0 for ids in segments):
             raise ValueError("empty segment in a document")
@@ -321,7 +360,8 @@ def request_inputs(model, batch: List[Request]):
 
 def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_batch: bool, sample_rates: Optional[Sequence[int]] = None,
                    encodings: Optional[Sequence[Optional[str]]] = None, dithers: Optional[Sequence[bool]] = None,
-                   dither_keys: Optional[Sequence[int]] = None, loudness: Optional[Sequence[Optional[float]]] = None) -> None:
+                   dither_keys: Optional[Sequence[int]] = None, *, true_peak: Optional[Sequence[Optional[float]]] = None,
+                   loudness: Optional[Sequence[Optional[float]]] = None) -> None:
     """``res[b]["audio"]`` for a batch of finished mels (``mel`` [B, n_feats, T], ``mel_lengths`` [B]; ``res[b]["mel"]`` the exact-length
     rows).  ``sample_rates``: one rate per request (default 24 kHz); rows that ask for another rate are converted on the device after
     the normalisation and the trim (``inference.to_waveforms``) and carry ``res[b]["sample_rate"]`` beside ``"audio"``.
@@ -330,7 +370,10 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
     carries ``res[b]["encoding"]``.  ``loudness``: one target in LUFS or None per request (``loudness_field``); a row that names one is
     brought to it on the device at 24 kHz, ahead of the conversion and the encoder (``inference.to_waveforms(loudness=...)``), and
     carries ``res[b]["loudness"]`` -- the LUFS measured before the gain -- and ``res[b]["gain"]``; the other rows keep their bits.
-    A float result at 24 kHz without a target keeps exactly the keys it had before there was a choice."""
+    ``true_peak``: one ceiling in dBTP or None per request (``true_peak_field``); a row that names one has its gain also limited by its
+    true peak (``inference.to_waveforms(true_peak=...)``) and carries ``res[b]["true_peak"]`` (dBTP, before the gain) and ``res[b]["lra"]``.
+    A float result at 24 kHz without a target keeps exactly the keys it had before there was a choice.  ``true_peak`` and ``loudness``
+    are named by every caller: they follow a ``*``, so that a positional list of levels cannot land in the wrong one."""
     if vocoder is None:
         return
     B = len(res)
@@ -341,12 +384,14 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
     coded = any(e is not None for e in encs)
     loud = [None] * B if loudness is None else list(loudness)
     levelled = any(v is not None for v in loud)
+    ceil = [None] * B if true_peak is None else list(true_peak)
+    metered = dict(true_peak=ceil, return_meter=True) if any(v is not None for v in ceil) else {}
     report = [None] * B
     if wave_batch:
         from .inference import to_waveforms
         extra = dict(encoding=encs, dither=dith, dither_keys=keys) if coded else {}
         if levelled:
-            audio, report = to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, loudness=loud, return_loudness=True, **extra)
+            audio, report = to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, loudness=loud, return_loudness=True, **metered, **extra)
         else:
             audio = to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, **extra)
         for r, a in zip(res, audio):
@@ -359,8 +404,13 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
                 from . import loudness as LD
                 rows = torch.zeros(1, (a.numel() + 3) // 4 * 4, dtype=torch.float32, device=a.device)
                 rows[0, :a.numel()] = a
-                lufs, gain, _ = LD.normalize(rows, [a.numel()], loud[b], check=False)
-                a, report[b] = rows[0, :a.numel()], (float(lufs[0]), float(gain[0]))
+                if ceil[b] is None:
+                    lufs, gain, _ = LD.normalize(rows, [a.numel()], loud[b], check=False)
+                    report[b] = (float(lufs[0]), float(gain[0]))
+                else:
+                    m = LD.normalize(rows, [a.numel()], loud[b], check=False, true_peak=ceil[b], return_meter=True)[3]
+                    report[b] = {k: float(v[0]) for k, v in m.items()}
+                a = rows[0, :a.numel()]
             if rate != 24000 and a.numel() > 0:
                 conv, n = _convert_rows(a.reshape(1, -1), torch.tensor([a.numel()], dtype=torch.long, device=a.device), [rate])
                 a = conv[0, :int(n[0])]
@@ -372,13 +422,12 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
                 else:
                     a = torch.zeros(0, dtype=torch.uint8)
             r["audio"] = a.cpu()
-    for r, rate, enc, target, rep in zip(res, rates, encs, loud, report):
+    for r, rate, enc, target, rep, c in zip(res, rates, encs, loud, report, ceil):
         if rate != 24000:
             r["sample_rate"] = rate
         if enc is not None:
             r["encoding"] = enc
-        if target is not None and rep is not None:
-            r["loudness"], r["gain"] = float(rep[0]), float(rep[1])
+        report_into(r, rep, target, c)
 
 
 def synthesise_batch(model, batch: List[Any], vocoder=None, wave_batch: bool = True, fade_ms: float = 5.0) -> List[Dict[str, Any]]:
@@ -398,7 +447,7 @@ def synthesise_batch(model, batch: List[Any], vocoder=None, wave_batch: bool = T
     lens = out["mel_lengths"].tolist()
     res = [{"mel": out["mel"][b, :, :int(lens[b])], "mel_length": int(lens[b])} for b in range(B)]
     waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch, [r.sample_rate for r in batch], *encoding_fields(batch),
-                   loudness=loudness_field(batch))
+                   loudness=loudness_field(batch), true_peak=true_peak_field(batch))
     return res
 
 
@@ -427,6 +476,8 @@ def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> 
     targets = loudness_field(units)
     if targets is not None:
         extra.update(loudness=targets, return_loudness=True)
+        if true_peak_field(units) is not None:
+            extra.update(true_peak=true_peak_field(units), return_meter=True)
     out_w = to_waveforms(out["mel"], out["mel_lengths"], vocoder, sample_rate=[int(u.sample_rate) for u in units],
                          documents=counts, gaps=gaps, fade_ms=fade_ms,
                          level=[u.level if isinstance(u, Document) else "sentence" for u in units], return_segments=True, **extra)
@@ -442,8 +493,7 @@ def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> 
             r["sample_rate"] = int(u.sample_rate)
         if u.encoding is not None:
             r["encoding"] = u.encoding
-        if u.loudness is not None and rep is not None:
-            r["loudness"], r["gain"] = float(rep[0]), float(rep[1])
+        report_into(r, rep, u.loudness, u.true_peak)
         res.append(r)
         b += n
     return res
@@ -774,7 +824,8 @@ class StepBatcher:
             lengths = torch.tensor([r["mel_length"] for r in res], dtype=torch.long, device=mel.device)
             try:
                 waveforms_into(res, mel, lengths, self.vocoder, self.wave_batch, [e.request.sample_rate for e in finished],
-                               *encoding_fields([e.request for e in finished]), loudness=loudness_field([e.request for e in finished]))
+                               *encoding_fields([e.request for e in finished]), loudness=loudness_field([e.request for e in finished]),
+                               true_peak=true_peak_field([e.request for e in finished]))
             except BaseException as exc:  # noqa: BLE001 - the finishers only: who is mid-solve is not affected
                 self._fail([e.request for e in finished], exc)
                 return

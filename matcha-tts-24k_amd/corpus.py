@@ -115,13 +115,15 @@ def measure_loudness(audio, lengths=None, sample_rate: int = 24000, check: bool 
     """Integrated loudness (ITU-R BS.1770 K-weighting and gates, ``loudness.measure``) and sample peak of every clip: what spots a
     recording that is far too quiet or too hot before it is trained on.  ``audio`` / ``lengths`` as for ``measure_silence``; any
     ``sample_rate`` that is a multiple of 100 in [8000, 192000].  Returns device tensors ``{"lufs": float64 [B], "peak": float32
-    [B]}``; -inf marks a clip with no block above the absolute gate of -70 LUFS.  Nothing is changed: the recordings keep their
+    [B]}`` and, beside them, what else ``loudness.meter`` reads: ``"true_peak"`` (float32, linear: a clip recorded too hot shows here
+    before it shows in the sample peak), ``"lra"``, ``"momentary_max"`` and ``"short_term_max"`` (float64; a clip under 3 s has range 0
+    and a short-term maximum of -inf); -inf marks a clip with no block above the absolute gate of -70 LUFS.  Nothing is changed: the recordings keep their
     level, since the mel statistics are computed without a level change.  A length outside ``[0, L]`` gives NaN in that row; with
     ``check`` the call waits for that verdict and raises ``ValueError`` naming the row."""
     from . import loudness as LD
     wave, d_len = _batch(audio, lengths)
-    lufs, _, peak = LD._run(wave, d_len, sample_rate, None, LD.PEAK_CEILING, False, check)
-    return {"lufs": lufs, "peak": peak}
+    m = LD._run(wave, d_len, sample_rate, None, LD.PEAK_CEILING, False, check, None, True)[3]
+    return {k: m[k] for k in ("lufs", "peak", "true_peak", "lra", "momentary_max", "short_term_max")}
 
 
 @torch.inference_mode()

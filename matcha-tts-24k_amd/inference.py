@@ -785,7 +785,7 @@ def finish_waveforms(audio, lengths, hop=0, silence_threshold_db=-60.0):
 @torch.inference_mode()
 def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, *, encoding=None, dither=False, dither_keys=None,
                  documents=None, gaps=None, fade_ms=5.0, level="document", return_segments=False, loudness=None, return_loudness=False,
-                 sample_rate=24000):
+                 true_peak=None, return_meter=False, sample_rate=24000):
     """``trim_trailing_silence(to_waveform(mel[b:b+1, :, :len_b], vocoder))`` (reference inference.py:246) for every row of a
     ragged batch in one device pass: ragged Vocos decode, per-row peak normalisation, per-row trim lengths, then ONE copy of the
     audio and one of the [B] lengths -- one synchronisation for the whole batch.  Returns a list of B 1-D host tensors
@@ -794,7 +794,8 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     ``sample_rate``: an int, or one per row.  Rows that ask for another rate than 24 kHz are converted on the device after the
     normalisation and the trim, which run at 24 kHz exactly as without it: the kept samples of those rows go through
     ``resample.resample`` (one call per distinct rate, the trim length as the row length, no extra host read) ahead of the copy.
-    The band-limited output of a row normalised to a 0.95 peak may overshoot that peak slightly; nothing is re-normalised.
+    The band-limited output of a row normalised to a 0.95 peak may overshoot that peak slightly; nothing is re-normalised, but
+    ``true_peak=`` (below) holds the level between the samples, which is what the conversion reconstructs, under a ceiling.
 
     ``encoding``: None (float32 rows, as ever), a name -- ``"pcm16"`` (s16le), ``"ulaw"``, ``"alaw"`` (G.711) -- or one per row, where
     None leaves a row float.  The rows that name one are encoded on the device (``audio_codec.encode``: one launch after the trim
@@ -822,12 +823,24 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     trim, and after the join when there is one, so it sees one row per document on its device length; the rate conversion and the
     encoder come behind it.  ``return_loudness``: also return ``[(lufs, gain)]`` per row or document -- the loudness measured BEFORE the
     gain and the gain applied (1.0 for a row left alone); they ride in the one ``meta`` copy, so the single synchronisation stays.
-    With ``return_segments`` too the call returns ``(results, segments, loudness)``."""
+    With ``return_segments`` too the call returns ``(results, segments, loudness)``.
+
+    ``true_peak``: None (exactly the calls above are made), a ceiling in dBTP (finite, at most 0; EBU R 128 delivery is -1), or one per
+    row -- per document with ``documents=`` -- where None names none.  The gain of a row that names one is also limited so that its TRUE
+    peak, the level between the samples as an oversampling 12-tap interpolator reads it (``loudness.normalize(true_peak=)``), stays at
+    or under the ceiling.  A ceiling on a row without a loudness target raises ``ValueError`` before anything is launched: the
+    ceiling limits a gain, and such a row has none.  ``return_meter``: the report entries (returned as with ``return_loudness``) are
+    dicts of seven figures -- ``lufs``, ``gain``, ``lra``, ``momentary_max``, ``short_term_max``, ``peak``, ``true_peak`` (``loudness.meter``;
+    the peaks linear), all measured BEFORE the gain; they ride in the same ``meta`` copy."""
     if documents is None and (gaps is not None or return_segments):
         raise ValueError("to_waveforms: gaps and return_segments belong to documents=")
     if loudness is not None:                                           # (a target that is no level raises before anything is looked at)
         from . import loudness as LD
         LD.targets_per_row(loudness, 1 if isinstance(loudness, (int, float)) else len(loudness))
+    if true_peak is not None:                                          # (so does a ceiling that is none, or one on a row without a target)
+        from . import loudness as LD
+        n = next((len(v) for v in (true_peak, loudness) if v is not None and not isinstance(v, (int, float))), 1)
+        _true_peak_ceilings(true_peak, LD.targets_per_row(loudness, n), n)
     if any(v not in ("document", "sentence") for v in ([level] if isinstance(level, str) else level)):
         raise ValueError(f"to_waveforms: level is 'document' or 'sentence' (or one of them per document), got {level!r}")
     model = vocoder.model if hasattr(vocoder, "model") else vocoder
@@ -841,7 +854,10 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     n_out = B if csr is None else len(csr) - 1
     rates = R.rates_per_row(sample_rate, n_out)
     encs = _encodings_per_row(encoding, n_out)                         # (an unknown name raises before anything is launched)
+    return_loudness = bool(return_loudness or return_meter)
     targets = _loudness_targets(loudness, n_out, return_loudness)     # (so does a target that is no level)
+    ceilings = _true_peak_ceilings(true_peak, targets, n_out)          # (and a ceiling on a row without a target)
+    stage = dict(ceilings=ceilings, meter=bool(return_meter))
     loud, report = [], []
     audio = model.decode(mel, mel_lengths, check=False)
     out_lengths, scale = finish_waveforms(audio, mel_lengths, hop=hop, silence_threshold_db=silence_threshold_db)
@@ -849,12 +865,13 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
         keep = out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1))
         fade = int(round(float(fade_ms) * SAMPLE_RATE / 1000.0))
         res = _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, _document_scales(scale, level, csr), rates, encs,
-                                dither, dither_keys, return_segments, targets, report)
+                                dither, dither_keys, return_segments, targets, report, stage)
         if not return_loudness:
             return res
         return (*res, report) if return_segments else (res, report)
     if targets is not None:
-        audio, loud = _loudness_stage(audio, out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1)), targets)
+        audio, loud = _loudness_stage(audio, out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1)), targets,
+                                      **stage)
     if any(r != SAMPLE_RATE for r in rates):
         audio, out_lengths = _convert_rows(audio, out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1)),
                                            rates)
@@ -870,7 +887,7 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     res = [host[b, : (keep[b] if trim or rates[b] != SAMPLE_RATE else hop * (frames[b] - 1))] for b in range(B)]
     if not return_loudness:
         return res
-    _loudness_report(meta[2:], report)
+    _loudness_report(meta[2:], report, len(loud))
     return res, report
 
 
@@ -884,19 +901,64 @@ def _loudness_targets(loudness, n, measure):
     return [float("nan")] * n if targets is None and measure else targets
 
 
-def _loudness_stage(audio, lengths, targets):
+def _true_peak_ceilings(true_peak, targets, n):
+    """``true_peak=`` of ``to_waveforms`` as n ceilings in dBTP or None per row; None when no row names one.  A value that is no
+    ceiling, and a ceiling on a row without a loudness target, raise here, before anything is launched."""
+    if true_peak is None:
+        return None
+    from . import loudness as LD
+    if isinstance(true_peak, (int, float)) and not isinstance(true_peak, bool):
+        c = LD.check_true_peak(true_peak)                              # one ceiling for the call: it binds the rows that have a target
+        vals = [c if t == t else None for t in (targets or [math.nan] * n)]
+        if all(v is None for v in vals):
+            raise ValueError("to_waveforms: true_peak limits the gain towards a loudness target, and no row names one (loudness=)")
+        return vals
+    vals = [LD.check_true_peak(v) for v in (true_peak.tolist() if torch.is_tensor(true_peak) else true_peak)]
+    if len(vals) != n:
+        raise ValueError(f"true_peak is a number or one per row ({n}), got {len(vals)}")
+    for b, v in enumerate(vals):
+        if v is not None and (targets is None or targets[b] != targets[b]):
+            raise ValueError(f"to_waveforms: true_peak[{b}] = {v} limits the gain towards a loudness target, and row {b} names none")
+    return vals if any(v is not None for v in vals) else None
+
+
+METER_FIGURES = ("lufs", "gain", "lra", "momentary_max", "short_term_max", "peak", "true_peak")
+
+
+def _loudness_stage(audio, lengths, targets, ceilings=None, meter=False):
     """The loudness stage of ``to_waveforms``: ``audio`` [n, L] at 24 kHz on its device lengths, in place (a padded copy when L is no
-    multiple of 4).  Returns the rows and what rides in the ``meta`` copy: the bits of the measured LUFS and of the gains as int64."""
+    multiple of 4).  Returns the rows and what rides in the ``meta`` copy: the bits of the measured LUFS and of the gains as int64 --
+    with ``meter`` of the seven ``METER_FIGURES``.  Without ``ceilings`` and ``meter`` exactly one ``mtts_loudness`` call is made; rows
+    that name different ceilings are levelled by one call per distinct ceiling, each row in the call of its own (in the others its
+    target is NaN, so it keeps its bits and is measured before its gain)."""
     from . import loudness as LD
     rows, _ = _hip.aligned_rows(audio, 4, "audio")
-    lufs, gain, _ = LD.normalize(rows, lengths, targets, SAMPLE_RATE, LD.PEAK_CEILING, check=False)
-    return rows, [lufs.view(torch.long), gain.to(torch.float64).view(torch.long)]
+    if ceilings is None and not meter:
+        lufs, gain, _ = LD.normalize(rows, lengths, targets, SAMPLE_RATE, LD.PEAK_CEILING, check=False)
+        return rows, [lufs.view(torch.long), gain.to(torch.float64).view(torch.long)]
+    ceilings = [None] * len(targets) if ceilings is None else ceilings
+    out = None
+    for c in sorted(set(ceilings), key=lambda v: (v is not None, v)):
+        mine = [v == c for v in ceilings]
+        m = LD.normalize(rows, lengths, [t if own else math.nan for t, own in zip(targets, mine)], SAMPLE_RATE, LD.PEAK_CEILING,
+                         check=False, true_peak=c, return_meter=True)[3]
+        if out is None:
+            out = m
+        else:
+            mask = torch.tensor(mine, dtype=torch.bool, device=rows.device)
+            out = {k: torch.where(mask, m[k], out[k]) for k in out}
+    names = METER_FIGURES if meter else METER_FIGURES[:2]
+    return rows, [out[k].to(torch.float64).view(torch.long) for k in names]
 
 
-def _loudness_report(words, report):
-    """``[(lufs, gain)]`` from the two int64 rows of the ``meta`` copy (a host tensor [2, n], or a flat list of 2 n words)."""
-    vals = torch.as_tensor(words, dtype=torch.long).reshape(2, -1).contiguous().view(torch.float64).tolist()
-    report.extend(zip(vals[0], vals[1]))
+def _loudness_report(words, report, k=2):
+    """``[(lufs, gain)]`` from the k = 2 int64 rows of the ``meta`` copy (a host tensor [k, n], or a flat list of k n words); dicts of
+    the ``METER_FIGURES`` when the stage left all seven of them."""
+    vals = torch.as_tensor(words, dtype=torch.long).reshape(k, -1).contiguous().view(torch.float64).tolist()
+    if k == 2:
+        report.extend(zip(vals[0], vals[1]))
+    else:
+        report.extend(dict(zip(METER_FIGURES, row)) for row in zip(*vals))
 
 
 _join_ws = _hip.Workspaces()
@@ -985,7 +1047,7 @@ def _document_scales(scale, level, csr):
 
 
 def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates, encs, dither, dither_keys, return_segments,
-                      targets=None, report=None):
+                      targets=None, report=None, stage=None):
     """The end of ``to_waveforms`` with ``documents=``: the join at 24 kHz, then the rate conversion and the encoding over one row
     per document on the joined device lengths, then the batch's one synchronisation -- the joined lengths, the rows' starts and kept
     lengths ride in the one ``meta`` copy -- and one copy of no more columns than the longest document has."""
@@ -995,7 +1057,7 @@ def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates
     wave, lens, starts = join_waveforms(audio, keep, csr, gaps, fade=fade, scale=scale, check=False)
     loud = []
     if targets is not None:                                            # one row per document, on its joined device length
-        wave, loud = _loudness_stage(wave, lens, targets)
+        wave, loud = _loudness_stage(wave, lens, targets, **(stage or {}))
     if any(r != SAMPLE_RATE for r in rates):
         wave, lens = _convert_rows(wave, lens, rates)
     words = [lens, starts, keep, mel_lengths] + loud
@@ -1011,8 +1073,8 @@ def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates
     got, begin, kept, frames = meta[:G], meta[G:G + B], meta[G + B:G + 2 * B], meta[G + 2 * B:G + 3 * B]
     at = G + 3 * B                                                     # what rides behind the lengths: loudness words, byte counts
     if loud and report is not None:
-        _loudness_report(meta[at:at + 2 * G], report)
-    at += 2 * G * bool(loud)
+        _loudness_report(meta[at:at + len(loud) * G], report, len(loud))
+    at += len(loud) * G
     for b in range(B):
         if kept[b] < 0:
             raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
@@ -1068,7 +1130,7 @@ def _encoded_rows(audio, out_lengths, mel_lengths, hop, T, trim, rates, encs, di
     meta = torch.stack([keep_dev, mel_lengths, nbytes, *loud]).cpu()   # waits for the stream: the batch's one synchronisation
     keep, frames, got = (m.tolist() for m in meta[:3])
     if len(loud) and report is not None:
-        _loudness_report(meta[3:], report)
+        _loudness_report(meta[3:], report, len(loud))
     for b in range(B):
         if keep[b] < 0 or got[b] < 0:
             raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
@@ -1126,7 +1188,7 @@ def trim_trailing_silence(audio, silence_threshold_db=-60.0):
 
 @torch.inference_mode()
 def pipeline(model, vocoder, text, speaker=0, voice_mix=None, n_timesteps=DEFAULT_NUM_STEPS, scale_correction=1.0,
-             length_scale=1.0, debug=False, *, encoding=None, loudness=None, sample_rate=24000):
+             length_scale=1.0, debug=False, *, encoding=None, loudness=None, true_peak=None, sample_rate=24000):
     """reference inference.py:233-257.  The reference wraps ``synthesise`` in ``torch.autocast`` (fp16 on its CUDA device);
     here the estimator's arithmetic is chosen when the model is created (``MTTS_GEMM_TERMS``: default fp32-equivalent; 1 = fp16
     operands / fp32 accumulate, the autocast arithmetic), not per call.  The trailing-silence trim runs on the device.
@@ -1135,9 +1197,14 @@ def pipeline(model, vocoder, text, speaker=0, voice_mix=None, n_timesteps=DEFAUL
     ``encoding``: None (a float32 waveform), or ``"pcm16"`` / ``"ulaw"`` / ``"alaw"``: the waveform is encoded on the device
     (``audio_codec.encode``) and returned as a 1-D uint8 host tensor of raw samples.
     ``loudness``: None, or a target in LUFS the waveform is brought to on the device (``loudness.normalize``: BS.1770 integrated
-    loudness, the sample peak held at or under 0.95), at 24 kHz after the trim and ahead of the rate conversion and the encoder."""
+    loudness, the sample peak held at or under 0.95), at 24 kHz after the trim and ahead of the rate conversion and the encoder.
+    ``true_peak``: None, or a ceiling in dBTP on the true peak of the levelled waveform (``loudness.normalize(true_peak=)``); it
+    needs a ``loudness`` target."""
     from . import loudness as LD
     target = LD.check_target(loudness)                                 # (a value that is no level raises before anything runs)
+    ceiling = LD.check_true_peak(true_peak)
+    if ceiling is not None and target is None:
+        raise ValueError("pipeline: true_peak limits the gain towards a loudness target, and loudness= names none")
     primary = voice_mix[0][0] if voice_mix is not None else speaker
     language = next(v["lang"] for v in VOICES if v["id"] == str(primary))
     tp = process_text(text, language)
@@ -1148,7 +1215,7 @@ def pipeline(model, vocoder, text, speaker=0, voice_mix=None, n_timesteps=DEFAUL
         n = waveform.numel()
         rows = torch.zeros(1, (n + 3) // 4 * 4, dtype=torch.float32, device=waveform.device)
         rows[0, :n] = waveform
-        LD.normalize(rows, [n], target, SAMPLE_RATE, check=False)
+        LD.normalize(rows, [n], target, SAMPLE_RATE, check=False, true_peak=ceiling)
         waveform = rows[0, :n]
     if int(sample_rate) != SAMPLE_RATE and waveform.numel() > 0:
         from . import resample as R

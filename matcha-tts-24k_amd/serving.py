@@ -94,6 +94,16 @@ def request_params(voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, 
 _SERVICE = object()      # default of ``submit_long / speak_long(loudness=)``: the service's own target
 
 
+def checked_ceiling(true_peak, loudness) -> Optional[float]:
+    """A true-peak ceiling in dBTP as a float, or None.  It limits the gain towards a loudness target, so a ceiling without one
+    raises ``ValueError``, as a value that is no ceiling does (``loudness.check_true_peak``).  Pure function: unit-tested on the CPU."""
+    from .loudness import check_true_peak
+    ceiling = check_true_peak(true_peak)
+    if ceiling is not None and loudness is None:
+        raise ValueError(f"true_peak = {true_peak!r} limits the gain towards a loudness target, and none is named (loudness=)")
+    return ceiling
+
+
 class SpeechService:
     """``await service.speak(text, voice, speed, steps, solver)`` -> 1-D waveform tensor on the host (``bytes`` with ``response_format``).
 
@@ -102,21 +112,25 @@ class SpeechService:
     different ``steps`` share launches) built with ``vocoder=`` so that results carry ``"audio"``."""
 
     def __init__(self, batcher, phonemize: Callable[[str, str], Sequence[int]], max_text_length: int = MAX_TEXT_LENGTH,
-                 loudness: Optional[float] = None):
+                 loudness: Optional[float] = None, true_peak: Optional[float] = None):
         """``loudness``: None, or the target in LUFS every request of this service is brought to on the device (BS.1770 integrated
         loudness, ``loudness.normalize``; typically -16, -19 or -23).  ``levelled(target)`` gives a view of the service with another
-        target, for one request: ``await service.levelled(-16).speak(text)``."""
+        target, for one request: ``await service.levelled(-16).speak(text)``.  ``true_peak``: None, or the ceiling in dBTP the true
+        peak of every levelled request is held under (EBU R 128 delivery: -1); it limits the gain towards the target, so it needs
+        ``loudness``.  Results then also carry ``"true_peak"`` (dBTP, before the gain) and ``"lra"``."""
         from .loudness import check_target
         self.batcher = batcher
         self.phonemize = phonemize
         self.max_text_length = int(max_text_length)
         self.loudness = check_target(loudness)
+        self.true_peak = checked_ceiling(true_peak, self.loudness)
 
-    def levelled(self, loudness: Optional[float]) -> "SpeechService":
-        """This service -- the same batcher and front end -- with ``loudness`` as its target (None: none).  A value that is no level
-        raises here, before anything is submitted.  ``submit`` and ``speak`` keep their positional signatures, so the target of a
+    def levelled(self, loudness: Optional[float], true_peak: Optional[float] = None) -> "SpeechService":
+        """This service -- the same batcher and front end -- with ``loudness`` as its target (None: none) and ``true_peak`` as its
+        true-peak ceiling in dBTP (None: none).  A value that is no level, and a ceiling without a target, raise here, before
+        anything is submitted.  ``submit`` and ``speak`` keep their positional signatures, so the target of a
         single request is named this way; ``submit_long`` and ``speak_long`` also take ``loudness=`` themselves."""
-        return SpeechService(self.batcher, self.phonemize, self.max_text_length, loudness)
+        return SpeechService(self.batcher, self.phonemize, self.max_text_length, loudness, true_peak)
 
     def submit(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
                speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None):
@@ -139,6 +153,8 @@ class SpeechService:
             extra["encoding"] = encoding
         if self.loudness is not None:
             extra["loudness"] = self.loudness
+        if self.true_peak is not None:
+            extra["true_peak"] = self.true_peak
         return self.batcher.submit(ids, speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver, n_timesteps=p.n_timesteps,
                                    scale_correction=p.scale_correction, length_scale=p.length_scale, **extra)
 
@@ -150,7 +166,7 @@ class SpeechService:
 
     def submit_long(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
                     speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None,
-                    max_document_length: int = MAX_DOCUMENT_LENGTH, *, loudness=_SERVICE, **split_options):
+                    max_document_length: int = MAX_DOCUMENT_LENGTH, *, loudness=_SERVICE, true_peak=_SERVICE, **split_options):
         """A text longer than one utterance: cut into sentences (``longform.split_text(text, **split_options)``; the abbreviation set
         is that of the voice's language unless given), each phonemized on its own -- so the phonemizer's intonation marks stay per
         sentence --, and submitted as ONE document (``FrameBudgetBatcher.submit_document``): the sentences run as rows of one ragged
@@ -158,10 +174,13 @@ class SpeechService:
         the joined result.  The future's result carries ``"audio"`` and ``"segments"`` (seconds of each sentence in the 24 kHz join).
         A batcher without ``submit_document`` raises ``TypeError``: there is no host-side join to fall back to.  ``submit`` and its
         cap are unchanged.  ``loudness``: the target in LUFS of the JOINED audio -- one gain per document, so its sentences keep
-        their balance -- or None; by default the service's own.  The result then carries ``"loudness"`` and ``"gain"``."""
+        their balance -- or None; by default the service's own.  The result then carries ``"loudness"`` and ``"gain"``.
+        ``true_peak``: the ceiling in dBTP on the true peak of the joined, levelled audio, or None; by default the service's own
+        where the document has a target.  The result then also carries ``"true_peak"`` and ``"lra"``."""
         encoding = response_encoding(response_format)
         from .loudness import check_target
         target = self.loudness if loudness is _SERVICE else check_target(loudness)
+        ceiling = (self.true_peak if target is not None else None) if true_peak is _SERVICE else checked_ceiling(true_peak, target)
         if not hasattr(self.batcher, "submit_document"):
             raise TypeError(f"{type(self.batcher).__name__} has no submit_document: long texts need a FrameBudgetBatcher")
         if len(text) > int(max_document_length):
@@ -180,15 +199,17 @@ class SpeechService:
             extra["encoding"] = encoding
         if target is not None:
             extra["loudness"] = target
+        if ceiling is not None:
+            extra["true_peak"] = ceiling
         return self.batcher.submit_document(ids, [pause for _, pause in pieces], speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver,
                                             n_timesteps=p.n_timesteps, scale_correction=p.scale_correction, length_scale=p.length_scale,
                                             **extra)
 
     async def speak_long(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
                          speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None,
-                         max_document_length: int = MAX_DOCUMENT_LENGTH, *, loudness=_SERVICE, **split_options):
+                         max_document_length: int = MAX_DOCUMENT_LENGTH, *, loudness=_SERVICE, true_peak=_SERVICE, **split_options):
         """The joined waveform of a long text (a 1-D float tensor on the host), or with ``response_format`` the response body as
         ``bytes`` -- ``response_body``, as ``speak``."""
         res = await asyncio.wrap_future(self.submit_long(text, voice, speed, steps, solver, speaker_embedding, sample_rate, response_format,
-                                                         max_document_length, loudness=loudness, **split_options))
+                                                         max_document_length, loudness=loudness, true_peak=true_peak, **split_options))
         return response_body(res, response_format, int(sample_rate))

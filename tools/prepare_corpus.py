@@ -25,7 +25,7 @@ normalize  rewrites every wav in place with the standard ``wave`` module: the fi
 stats      prints the ``data_statistics:`` block for the YAML.
 mels       writes ``<mel_dir>/<rel>.npy`` (n_mels, T) and ``.fine.npy`` at half the hop, ``metadata.json`` and, if any file
            failed, ``failures.txt``, in the layout the reference's trainer reads; files that are already there are kept.
-loudness   prints integrated loudness (LUFS, ITU-R BS.1770 gating) and sample peak of every file of the train and validation
+loudness   prints integrated loudness (LUFS, ITU-R BS.1770 gating), sample peak, true peak (dBTP) and loudness range (LU) of every file of the train and validation
            filelists and the corpus median, and marks files more than ``--loudness_margin`` dB from it: recordings that are far too
            quiet or too hot.  Nothing is rewritten: the mel statistics are computed without a level change.
 time       HIP-event times of the device calls on N synthetic clips of ``--seconds`` (median, min .. max of ``--repeat``), and
@@ -173,15 +173,17 @@ def cmd_measure(args, cfg, corpus) -> int:
 
 # ---------------------------------------------------------------------------------------------------------------- loudness
 def loudness_report(rows, margin: float) -> str:
-    """``rows``: [(rel, lufs, peak)].  One line per file, then the median over the files with a finite loudness; a file further than
+    """``rows``: [(rel, lufs, peak)] or [(rel, lufs, peak, true_peak, lra)].  One line per file -- with the longer rows also the true
+    peak in dBTP and the loudness range in LU --, then the median over the files with a finite loudness; a file further than
     ``margin`` dB from it, or with no block above the absolute gate, is marked."""
-    finite = [l for _, l, _ in rows if np.isfinite(l)]
+    finite = [r[1] for r in rows if np.isfinite(r[1])]
     median = statistics.median(finite) if finite else float("nan")
     lines = []
-    for rel, lufs, peak in rows:
+    for rel, lufs, peak, *more in rows:
         mark = "" if np.isfinite(lufs) and abs(lufs - median) <= margin else "   <-- silent" if not np.isfinite(lufs) else \
             f"   <-- {lufs - median:+.1f} dB from the median"
-        lines.append(f"{rel:<24} {lufs:8.2f} LUFS   peak {peak:.4f}{mark}")
+        r128 = f"   true peak {20.0 * np.log10(more[0]) if more[0] > 0 else -np.inf:7.2f} dBTP   range {more[1]:5.2f} LU" if more else ""
+        lines.append(f"{rel:<24} {lufs:8.2f} LUFS   peak {peak:.4f}{r128}{mark}")
     lines.append(f"[prepare_corpus] {len(rows)} files, {len(finite)} with a finite loudness, median {median:.2f} LUFS")
     return "\n".join(lines)
 
@@ -194,8 +196,8 @@ def cmd_loudness(args, cfg, corpus) -> int:
         for rate in sorted(set(rates)):                              # the K-weighting follows each file's own rate
             sel = [i for i, r in enumerate(rates) if r == rate]
             got = corpus.measure_loudness([clips[i] for i in sel], None, rate)
-            lufs, peak = got["lufs"].cpu().tolist(), got["peak"].cpu().tolist()
-            rows += [(its[i][0], lufs[k], peak[k]) for k, i in enumerate(sel)]
+            lufs, peak, tp, lra = (got[k].cpu().tolist() for k in ("lufs", "peak", "true_peak", "lra"))
+            rows += [(its[i][0], lufs[k], peak[k], tp[k], lra[k]) for k, i in enumerate(sel)]
     rows.sort(key=lambda r: r[0])
     print(loudness_report(rows, args.loudness_margin))
     return 0

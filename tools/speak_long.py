@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A text longer than one utterance to one wav file: sentences as rows of one ragged batch, joined on the device.
 
-    python tools/speak_long.py speak --matcha CKPT --vocos CKPT TEXT.txt OUT.wav [--voice 0 --speed 1.0 --steps 4 --sample-rate 24000 --loudness LUFS]
+    python tools/speak_long.py speak --matcha CKPT --vocos CKPT TEXT.txt OUT.wav [--voice 0 --speed 1.0 --steps 4 --sample-rate 24000 --loudness LUFS --true-peak DB]
     python tools/speak_long.py speak --matcha CKPT --vocos CKPT --segments-file FILE OUT.wav
     python tools/speak_long.py time [--sentences 20 --tokens 100 --repeat 10] [--utterance | --kernels]     # random weights, no files
 
@@ -74,6 +74,10 @@ def speak(args) -> int:
     if not ids:
         raise SystemExit("nothing to speak")
     extra = {} if args.loudness is None else {"loudness": args.loudness}
+    if args.true_peak is not None:
+        if args.loudness is None:
+            raise SystemExit("--true-peak limits the gain towards --loudness: name a target too")
+        extra["true_peak"] = args.true_peak
     with bt.FrameBudgetBatcher(model, max_batch=max(32, len(ids)), max_tokens=max(8192, len(ids) * max(len(s) for s in ids)),
                                vocoder=vocoder, fade_ms=args.fade_ms) as q:
         res = q.submit_document(ids, pauses, speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver, n_timesteps=p.n_timesteps,
@@ -84,6 +88,8 @@ def speak(args) -> int:
         print(f"{n:4d}  {t0:9.3f} s .. {t1:9.3f} s")
     if "loudness" in res:
         print(f"loudness {res['loudness']:.2f} LUFS as synthesised, gain {res['gain']:.4f} towards {args.loudness:.2f} LUFS")
+    if "true_peak" in res:
+        print(f"true peak {res['true_peak']:.2f} dBTP as synthesised (ceiling {args.true_peak:.2f} dBTP), loudness range {res['lra']:.2f} LU")
     print(f"wrote {args.out}: {res['audio'].numel() // 2} samples at {args.sample_rate} Hz, {len(ids)} sentences")
     return 0
 
@@ -210,6 +216,7 @@ def main() -> int:
     sp.add_argument("--fade-ms", type=float, default=5.0)
     sp.add_argument("--level", choices=("document", "sentence"), default="document")
     sp.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="integrated loudness of the joined document, e.g. -16, -19, -23")
+    sp.add_argument("--true-peak", type=float, default=None, metavar="DB", help="ceiling in dBTP on the true peak of the levelled document, e.g. -1")
     tm = cmds.add_parser("time", help="per-call times on random weights")
     tm.add_argument("--sentences", type=int, default=20)
     tm.add_argument("--tokens", type=int, default=100)
