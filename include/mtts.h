@@ -136,6 +136,24 @@ int mtts_durations_given(const float* d_dur, const float* d_x_mask, float length
                          const int32_t* d_given_rows, int B, int Tx, float* d_durations, int32_t* d_cum,
                          int64_t* d_y_fine_lengths, void* stream);
 
+/* Shaped durations: one launch for a batch that mixes predicted and given rows, with a rate and an extension per token -- what SSML
+ * calls <prosody rate> and a lengthened syllable -- ahead of the same scan.  The entries above stay as they are.
+ *   d_scale_correction, d_length_scale   device float [B] each
+ *   d_given        device float [B,Tx] (fine frames) or NULL;  d_given_rows: device int32 [B] or NULL.  Row b is GIVEN when d_given is
+ *                  there and d_given_rows is NULL or d_given_rows[b] != 0; every other row is PREDICTED from d_logw (which may be NULL
+ *                  only when every row is given)
+ *   d_token_scale  device float [B,Tx] or NULL (s = 1);  d_token_extend: device float [B,Tx], fine frames, or NULL (a = 0)
+ * fp32, every operation rounded once, no FMA; m = mask, sc / ls the row's factors:
+ *   s = NaN ? 1 : min(max(s, 0), 16);   a = NaN ? 0 : min(max(a, -4096), 4096)      (so no input gives a negative or unbounded length)
+ *   predicted:  v = (expf(logw) - 2) * m;  v = v * sc;  v = v * ls;  v = v * s;  v = v + a;  d = fmaxf(rintf(v), s == 0 ? 0 : 1) * m
+ *   given:      v = given * ls;                                      v = v * s;  v = v + a;  d = fmaxf(rintf(v), 0) * m
+ * A scale of exactly 0 (after the clamp) drops a predicted token, as a given zero does.  With s == 1 and a == 0 the two extra operations
+ * are exact and all three outputs equal those of mtts_durations_per_utterance (mtts_durations_given for given rows) bit for bit.
+ * Outputs as mtts_durations.  Returns -1 and launches nothing for a null pointer it needs, d_given_rows without d_given, B < 1, Tx < 1. */
+int mtts_durations_shaped(const float* d_logw, const float* d_x_mask, const float* d_scale_correction, const float* d_length_scale,
+                          const float* d_given, const int32_t* d_given_rows, const float* d_token_scale, const float* d_token_extend,
+                          int B, int Tx, float* d_durations, int32_t* d_cum, int64_t* d_y_fine_lengths, void* stream);
+
 /* generate_path + matmul + downsample + sequence_mask -- reference inference.py:146-167,
  * utils/model.py:7-9,24-40,57-68.  T_pad = fix_len_compatibility(max fine length) (host decides it).
  * Outputs: d_mu_y [B,n_feats,T_pad], d_y_mask [B,1,T_pad], d_y_lengths [B] int64. */
@@ -835,6 +853,62 @@ int mtts_wave_join(const float* d_audio, int64_t ld, const int64_t* d_lengths, c
                    const int64_t* d_gap, int B, int G, int64_t fade, int64_t gap_max, float* d_out, int64_t out_ld,
                    int64_t* d_out_lengths, int64_t* d_starts, void* d_ws, int64_t ws_bytes, void* stream);
 int mtts_wave_join_status(const void* d_ws, void* stream);
+
+/* ---------------------------------------------------------------- token timing: marks out, breaks in */
+
+/* When each token is spoken in the audio mtts_waveform_finish leaves, and pauses cut into that audio after chosen tokens (what SSML
+ * calls <break time>), between the trim and the join.  The reference has no counterpart: the arithmetic below is the definition, and
+ * a NumPy restatement in that order reproduces every word (tests/timing_restated.py).  All integers are int64 and a function of the
+ * row alone, so a row's marks, length and samples do not depend on what shares its batch.
+ *   d_cum        device int32 [B][Tx]: inclusive cumulative durations in fine frames (mtts_durations' d_cum)
+ *   d_x_lengths  device int64 [B]: tokens of row b, inside [1, Tx]
+ *   d_keep       device int64 [B]: kept samples of row b (mtts_waveform_finish's d_out_lengths, or hop * (frames - 1) untrimmed;
+ *                -1 = refused upstream), inside [0, keep_max] (the row stride of the audio)
+ *   fine_hop     samples per fine frame: half the vocoder hop, 128 at 24 kHz
+ *   breaks, optional (d_break_first NULL, NB 0: none), in CSR form: the breaks of row b are [break_first[b], break_first[b + 1]) of
+ *                d_break_token int32 [NB] (the break follows this token; strictly increasing within a row, inside [0, x_len)) and
+ *                d_break_pause int64 [NB] (samples, inside [0, pause_max])
+ * Boundaries of a row: e_0 = 0 and e_k = min(max(fine_hop * cum[k - 1] - fine_hop / 2, 0), keep) for k = 1 .. x_len.  Why the half
+ * frame: the mel front end the model was trained on is center=True, so fine frame f is centred on sample f * fine_hop; mtts_align_pool
+ * centres coarse frame t on fine frame 2 t, and the iSTFT centres frame t on sample t * hop = 2 t * fine_hop -- so fine frame f of the
+ * alignment is centred on sample f * fine_hop of the output too.  Token k - 1 ends with fine frame cum[k - 1] - 1 and token k begins
+ * with fine frame cum[k - 1]; e_k is the midpoint between their centres.  The marks are NOMINAL: the decoder and the vocoder have
+ * receptive fields of many frames, which smear what is heard around a boundary.
+ * Breaks: a break after token j cuts at c_j = e_{j + 1}.  A break with c_j == 0 or c_j >= keep is DROPPED, its applied pause 0 (the trim
+ * has removed what follows it); every other break is applied with its pause, a pause of 0 included (a cut without silence).
+ * Marks (d_marks int64 [B][Tx][2]): start_i = e_i + P(<i), end_i = e_{i+1} + P(<i), P(<i) the sum of the applied pauses of the breaks at
+ * tokens < i; d_out_lengths[b] = keep + P(all).  Tokens at or beyond x_len, and every token of a refused row, read -1; a refused row's
+ * length is -1.
+ * Checks, on the device, before anything is indexed with these values (the ragged-batch contract): each refuses ITS ROW ALONE.
+ *   reason 5: x_len outside [1, Tx];  1: keep outside [0, keep_max];  2: break_first does not ascend inside [0, NB], or a token index
+ *   outside [0, x_len);  3: a token index not above the one before it;  4: a pause outside [0, pause_max];  6: cum decreases between two
+ *   breaks;  7: keep + P(all) > out_max.  The workspace holds one verdict record per row; mtts_token_timing_status(d_ws, B, stream), the
+ *   only entry here that waits, copies them and words the first through mtts_last_error.
+ * One launch, one workgroup of 256 per row (the scan of the applied pauses is the duration scan's: serial chunk + block scan); no
+ * allocation.  What the host can see returns -1 and launches nothing: null pointers, breaks without tokens or pauses, B < 1,
+ * B > 65535, Tx < 1, a fine_hop that is odd or outside [2, 65536], NB outside [0, 2^27] or non-zero without d_break_first, keep_max < 0,
+ * out_max < keep_max, pause_max < 0, a misaligned or small workspace. */
+int64_t mtts_token_timing_workspace_bytes(int64_t B, int64_t NB);
+int mtts_token_timing(const int32_t* d_cum, const int64_t* d_x_lengths, const int64_t* d_keep, int B, int Tx, int fine_hop,
+                      int64_t keep_max, const int32_t* d_break_first, const int32_t* d_break_token, const int64_t* d_break_pause,
+                      int64_t NB, int64_t pause_max, int64_t out_max, int64_t* d_marks, int64_t* d_out_lengths, void* d_ws,
+                      int64_t ws_bytes, void* stream);
+int mtts_token_timing_status(const void* d_ws, int B, void* stream);
+
+/* The breaks in the audio: a gather over the lengthened rows, from the plan the latest mtts_token_timing left in d_ws (same B, NB and
+ * d_break_first).  Rows as for mtts_wave_join: fp32 [B][ld] and [B][out_ld], ld and out_ld positive multiples of 4, 16-byte aligned,
+ * not overlapping.  Row b of d_out holds the segments of audio[b][0 .. keep) between its applied cuts in order, `pause` zeros after
+ * each applied cut, then zeros from its new length to out_ld: every word is written exactly once; a refused row is zeros.
+ * Fade, the join's own rule: for a segment of n samples F' = min(fade, n / 2) (integer division); sample i < F' of a segment that lies
+ * behind a cut, and sample n - 1 - i (i < F') of a segment that lies ahead of one, become x * w, w = (float)(2 i + 1) / (float)(2 F').
+ * The two ends of the row keep their samples; fade == 0 applies no weight; every sample outside a fade is moved bit for bit.  Two
+ * breaks that cut at one position (tokens of no duration between them) add their pauses; the empty segment between them has no fade.
+ * A row without breaks is copied bit for bit.  Gridded over (tile of 2048 output samples, row), 16-byte stores.  The host passes
+ * out_ld = ld + the largest sum of requested pauses of a row, rounded up to 4: no host read is needed.  Returns -1 and launches nothing
+ * for: null pointers, B < 1, B > 65535, NB out of range, a misaligned row, an ld or out_ld that is no positive multiple of 4,
+ * fade < 0, d_out overlapping d_audio, a small workspace. */
+int mtts_wave_breaks(const float* d_audio, int64_t ld, const int32_t* d_break_first, int B, int64_t NB, int64_t fade, float* d_out,
+                     int64_t out_ld, const void* d_ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- encoded audio: PCM16, G.711 mu-law / A-law */
 

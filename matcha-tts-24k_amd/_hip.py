@@ -19,7 +19,7 @@ from .hparams import PathHParams
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = Path(os.environ["MTTS_HIP_LIB"]) if os.environ.get("MTTS_HIP_LIB") else HERE / "libmtts_hip.so"   # override: A/B of two builds
-SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "resample.hip", "audio_codec.hip", "corpus.hip", "wave_join.hip", "loudness.hip", "style_encoder.hip", "mas.hip", "score.hip", "spk_grad.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
+SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "resample.hip", "audio_codec.hip", "corpus.hip", "wave_join.hip", "timing.hip", "loudness.hip", "style_encoder.hip", "mas.hip", "score.hip", "spk_grad.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
 HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", CSRC / "host.h", HERE.parent / "include" / "mtts.h"]
 SOLVERS = {"euler": 0, "midpoint": 1, "rk4": 2}
 
@@ -197,6 +197,7 @@ def load() -> C.CDLL:
         "mtts_durations": (i32, [vp, vp, f32, f32, i32, i32, vp, vp, vp, vp]),
         "mtts_durations_per_utterance": (i32, [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
         "mtts_durations_given": (i32, [vp, vp, f32, vp, vp, i32, i32, vp, vp, vp, vp]),
+        "mtts_durations_shaped": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]),
         "mtts_align_pool": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
         "mtts_set_frame_limits": (i32, [vp, vp]),
         "mtts_decoder_workspace_bytes": (i64, [vp, i32, i32]),
@@ -314,6 +315,10 @@ def load() -> C.CDLL:
         "mtts_wave_join_workspace_bytes": (i64, [i64, i64]),
         "mtts_wave_join": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i64, i64, vp, i64, vp, vp, vp, i64, vp]),
         "mtts_wave_join_status": (i32, [vp, vp]),
+        "mtts_token_timing_workspace_bytes": (i64, [i64, i64]),
+        "mtts_token_timing": (i32, [vp, vp, vp, i32, i32, i32, i64, vp, vp, vp, i64, i64, i64, vp, vp, vp, i64, vp]),
+        "mtts_token_timing_status": (i32, [vp, i32, vp]),
+        "mtts_wave_breaks": (i32, [vp, i64, vp, i32, i64, i64, vp, i64, vp, i64, vp]),
         "mtts_loudness_chunk": (i32, [i32]),
         "mtts_loudness_tile": (i32, []),
         "mtts_loudness_coefficients": (i32, [i32, C.POINTER(C.c_double)]),
@@ -777,6 +782,54 @@ class HipModel:
                 raise ValueError("per-utterance scale factors need one value per utterance")
         check(self.lib.mtts_durations_given(ptr(given), ptr(x_mask), ls, ptr(ls_b), ptr(rows), B, Tx, ptr(dur), ptr(cum), ptr(yfl),
                                             stream_ptr()))
+        return dur, cum, yfl
+
+    def durations_shaped(self, logw, x_mask, scale_correction=1.0, length_scale=1.0, given=None, given_rows=None, token_scale=None,
+                         token_extend=None):
+        """Durations shaped per token in one launch (mtts_durations_shaped; include/mtts.h has the arithmetic): ``token_scale``
+        [B, Tx] multiplies a token's duration (a rate; exactly 0 drops the token) and ``token_extend`` [B, Tx] adds fine frames to it,
+        on predicted rows and on the rows of ``given`` [B, Tx] that ``given_rows`` [B] marks (None: all of them) alike.
+        ``scale_correction`` / ``length_scale``: floats or one per utterance.  Host values outside [0, 16] / [-4096, 4096] raise
+        ``ValueError`` before anything is launched (``timing.check_shaping``); the kernel clamps what only the device knows."""
+        x_mask = self._f32(x_mask)
+        B, _, Tx = x_mask.shape
+        dev = x_mask.device
+
+        def per_utt(v):
+            t = torch.as_tensor(v, dtype=torch.float32).reshape(-1)
+            t = t.expand(B) if t.numel() == 1 else t
+            if t.numel() != B:
+                raise ValueError("per-utterance scale factors need one value per utterance")
+            return t.to(dev).contiguous()
+
+        def per_token(v, name):
+            if v is None:
+                return None
+            from .timing import check_shaping
+            check_shaping(v, name)
+            v = self._f32(torch.as_tensor(v).to(dev))
+            if v.shape != (B, Tx):
+                raise ValueError(f"{name} must have shape ({B}, {Tx}), got {tuple(v.shape)}")
+            return v
+        s, a = per_token(token_scale, "token_scale"), per_token(token_extend, "token_extend")
+        rows = None
+        if given is not None:
+            given = self._f32(given)
+            if given.shape != (B, Tx):
+                raise ValueError(f"durations must have shape ({B}, {Tx}), got {tuple(given.shape)}")
+            if given_rows is not None:
+                rows = torch.as_tensor(given_rows).to(device=dev, dtype=torch.int32).contiguous()
+                if rows.shape != (B,):
+                    raise ValueError("given_rows needs one flag per utterance")
+        elif given_rows is not None:
+            raise ValueError("given_rows needs given=")
+        logw = None if logw is None else self._f32(logw)
+        sc, ls = per_utt(scale_correction), per_utt(length_scale)
+        dur = torch.empty(B, Tx, dtype=torch.float32, device=dev)
+        cum = torch.empty(B, Tx, dtype=torch.int32, device=dev)
+        yfl = torch.empty(B, dtype=torch.int64, device=dev)
+        check(self.lib.mtts_durations_shaped(ptr(logw), ptr(x_mask), ptr(sc), ptr(ls), ptr(given), ptr(rows), ptr(s), ptr(a), B, Tx,
+                                             ptr(dur), ptr(cum), ptr(yfl), stream_ptr()))
         return dur, cum, yfl
 
     def mas_logprior(self, mu_x, y, x_lengths, y_lengths):

@@ -48,10 +48,25 @@ class Request:
     dither_key: int = 0                     # selects the dither sequence: a field of the request, so its bytes do not depend on who shared its batch
     loudness: Optional[float] = None        # target in LUFS (BS.1770 integrated loudness) the "audio" is brought to on the device at 24 kHz; the result then carries "loudness" (measured, before the gain) and "gain"
     true_peak: Optional[float] = None       # ceiling in dBTP on the true peak of the levelled "audio" (needs ``loudness``); the result then also carries "true_peak" (dBTP, measured before the gain) and "lra"
+    token_scale: Optional[Sequence[float]] = None    # a rate per token, inside [0, 16]: its duration is multiplied by it (exactly 0 drops the token)
+    token_extend: Optional[Sequence[float]] = None   # fine frames added to each token's duration, inside [-4096, 4096]
+    breaks: Optional[Sequence[Tuple[int, float]]] = None    # [(token, pause_ms), ...]: a pause cut into the audio after that token; token indices strictly increase
+    marks: bool = False                     # the result then carries "marks": {"tokens": [(start_s, end_s)] per token (+ "words" with ``word_groups``)}, in seconds at 24 kHz
+    word_groups: Optional[Sequence[int]] = None      # the word of each token (-1: none; ``timing.word_groups``): "marks" then has "words" too
     future: Future = field(default_factory=Future, repr=False)
     t_submit: float = field(default_factory=time.monotonic, repr=False)
 
     def __post_init__(self):
+        if self.token_scale is not None or self.token_extend is not None or self.breaks is not None or self.word_groups is not None:
+            from .timing import check_breaks, check_shaping      # (a wrong field fails its own request here, not the batch it would have joined)
+            for name in ("token_scale", "token_extend", "word_groups"):
+                v = getattr(self, name)
+                if v is not None and len(v) != len(self.ids):
+                    raise ValueError(f"a request's {name} needs one value per token ({len(self.ids)}), got {len(v)}")
+            check_shaping(None if self.token_scale is None else list(self.token_scale), "token_scale")
+            check_shaping(None if self.token_extend is None else list(self.token_extend), "token_extend")
+            if self.breaks is not None:
+                self.breaks = check_breaks(self.breaks, len(self.ids), what="a request's breaks")
         if self.encoding is not None:       # (an unknown name fails its own request here, not the batch it would have joined)
             from .audio_codec import format_id
             format_id(self.encoding)
@@ -74,6 +89,47 @@ def duration_rows(batch: List[Request]) -> Optional[List[Optional[Sequence[float
         if r.durations is not None and len(r.durations) != len(r.ids):
             raise ValueError(f"a request's durations need one value per token ({len(r.ids)}), got {len(r.durations)}")
     return [r.durations for r in batch]
+
+
+def timing_fields(rows: List[Request], units: Optional[List[Any]] = None) -> Optional[Dict[str, Any]]:
+    """What a batch asks of token timing, or None when no row and no unit asks anything (the calls are then exactly those made before
+    there was a choice): ``token_scale`` / ``token_extend`` as ``synthesise`` takes them (one entry per row, None = leave it alone; None
+    when no row names one), ``breaks`` as ``to_waveforms`` takes them (None when no row has one) and ``marks``, whether a unit wants
+    its marks back.  Pure function: unit-tested on the CPU."""
+    scale = [r.token_scale for r in rows]
+    extend = [r.token_extend for r in rows]
+    breaks = [list(r.breaks) if r.breaks else None for r in rows]
+    marks = any(bool(u.marks) for u in (rows if units is None else units))
+    out = dict(token_scale=scale if any(v is not None for v in scale) else None,
+               token_extend=extend if any(v is not None for v in extend) else None,
+               breaks=breaks if any(v is not None for v in breaks) else None, marks=marks)
+    return out if marks or any(out[k] is not None for k in ("token_scale", "token_extend", "breaks")) else None
+
+
+def shaping_kwargs(timing: Optional[Dict[str, Any]]) -> Dict[str, Any]:
+    """The keyword arguments ``timing_fields`` adds to a ``synthesise`` call."""
+    if timing is None:
+        return {}
+    kw = {k: timing[k] for k in ("token_scale", "token_extend") if timing[k] is not None}
+    if timing["marks"] or timing["breaks"] is not None:
+        kw["return_timing"] = True
+    return kw
+
+
+def marks_into(r: Dict[str, Any], unit, tokens) -> None:
+    """``r["marks"]`` of a unit that asked for them: ``tokens`` are its token marks -- one list for a request, one per sentence for a
+    document -- and ``"words"`` appears when its rows bring ``word_groups``."""
+    if not unit.marks:
+        return
+    from .timing import word_marks
+    if isinstance(unit, Document):
+        r["marks"] = {"tokens": tokens}
+        if all(row.word_groups is not None for row in unit.rows):
+            r["marks"]["words"] = [word_marks(t, row.word_groups) for t, row in zip(tokens, unit.rows)]
+    else:
+        r["marks"] = {"tokens": tokens}
+        if unit.word_groups is not None:
+            r["marks"]["words"] = word_marks(tokens, unit.word_groups)
 
 
 def encoding_fields(batch: List[Request]):
@@ -162,6 +218,7 @@ class Document:
     dither_key: int = 0
     loudness: Optional[float] = None        # target in LUFS of the JOINED audio: one gain per document
     true_peak: Optional[float] = None       # ceiling in dBTP on the true peak of the joined, levelled audio (needs ``loudness``)
+    marks: bool = False                     # the result then carries "marks": {"tokens": one list per sentence (+ "words")}, in the document's timeline
     future: Future = field(default_factory=Future, repr=False)
     t_submit: float = field(default_factory=time.monotonic, repr=False)
 
@@ -276,15 +333,26 @@ class FrameBudgetBatcher:
         """A text of several utterances: ``segments_ids`` the phoneme ids of each segment in speaking order, ``pauses_ms`` the silence
         after each (the last is ignored).  ``request_fields``: the fields of a ``Request`` -- voice, solver, speeds apply to every
         segment; ``sample_rate`` / ``encoding`` / ``dither`` / ``dither_key`` / ``loudness`` / ``true_peak`` to the joined result -- and ``level`` (``Document``).
+        ``marks`` (of the joined result) asks for ``"marks"``: ``{"tokens": one list of (start_s, end_s) per segment}`` in the document's
+        timeline, ``"words"`` too when every segment brings ``word_groups``.  ``breaks`` / ``token_scale`` / ``token_extend`` /
+        ``word_groups`` differ from segment to segment: each is a list of one entry (or None) per segment, as the ``Request`` field.
         The segments run as rows of one ragged batch, together with whatever else is waiting, and are joined on the device.  One
         future: ``{"audio", "segments": [(start_s, end_s)] per segment, "mel_lengths"}``, plus ``"sample_rate"`` / ``"encoding"``
         when asked.  A document is admitted whole or not at all: more segments than ``max_batch`` or segments x longest above
         ``max_tokens`` raises ``ValueError`` here, as does an empty segment."""
-        once = {k: request_fields.pop(k) for k in ("level", "sample_rate", "encoding", "dither", "dither_key", "loudness", "true_peak") if k in request_fields}
+        once = {k: request_fields.pop(k) for k in ("level", "sample_rate", "encoding", "dither", "dither_key", "loudness", "true_peak", "marks")
+                if k in request_fields}
         segments = [list(ids) for ids in segments_ids]
         if any(len(ids) == 0 for ids in segments):
             raise ValueError("empty segment in a document")
-        d = Document(rows=[Request(ids=ids, **request_fields) for ids in segments], pauses_ms=[float(p) for p in pauses_ms], **once)
+        # what differs from sentence to sentence rides per row: a list of one entry (or None) per segment
+        per_row = {k: request_fields.pop(k) for k in ("breaks", "token_scale", "token_extend", "word_groups") if k in request_fields}
+        for k, v in per_row.items():
+            if v is not None and len(v) != len(segments):
+                raise ValueError(f"a document's {k} need one entry per segment ({len(segments)}), got {len(v)}")
+        rows = [Request(ids=ids, **request_fields, **{k: v[i] for k, v in per_row.items() if v is not None})
+                for i, ids in enumerate(segments)]
+        d = Document(rows=rows, pauses_ms=[float(p) for p in pauses_ms], **once)
         duration_rows(d.rows)
         n, longest = _unit_size(d)
         if n > self.max_batch:
@@ -360,7 +428,8 @@ def request_inputs(model, batch: List[Request]):
 
 def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_batch: bool, sample_rates: Optional[Sequence[int]] = None,
                    encodings: Optional[Sequence[Optional[str]]] = None, dithers: Optional[Sequence[bool]] = None,
-                   dither_keys: Optional[Sequence[int]] = None, *, true_peak: Optional[Sequence[Optional[float]]] = None,
+                   dither_keys: Optional[Sequence[int]] = None, *, timing: Optional[Dict[str, Any]] = None,
+                   true_peak: Optional[Sequence[Optional[float]]] = None,
                    loudness: Optional[Sequence[Optional[float]]] = None) -> None:
     """``res[b]["audio"]`` for a batch of finished mels (``mel`` [B, n_feats, T], ``mel_lengths`` [B]; ``res[b]["mel"]`` the exact-length
     rows).  ``sample_rates``: one rate per request (default 24 kHz); rows that ask for another rate are converted on the device after
@@ -373,9 +442,13 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
     ``true_peak``: one ceiling in dBTP or None per request (``true_peak_field``); a row that names one has its gain also limited by its
     true peak (``inference.to_waveforms(true_peak=...)``) and carries ``res[b]["true_peak"]`` (dBTP, before the gain) and ``res[b]["lra"]``.
     A float result at 24 kHz without a target keeps exactly the keys it had before there was a choice.  ``true_peak`` and ``loudness``
-    are named by every caller: they follow a ``*``, so that a positional list of levels cannot land in the wrong one."""
+    are named by every caller: they follow a ``*``, so that a positional list of levels cannot land in the wrong one.
+    ``timing``: None, or ``dict(token_ends=, x_lengths=, breaks=, units=)`` -- the timing plan runs in the batched tail
+    (``inference.to_waveforms(token_ends=...)``) and ``res[b]["marks"]`` is filled for the units that asked (``marks_into``)."""
     if vocoder is None:
         return
+    if timing is not None and not wave_batch:
+        raise ValueError("marks and breaks run in the batched tail: they need wave_batch=True")
     B = len(res)
     rates = [24000] * B if sample_rates is None else [int(v) for v in sample_rates]
     encs = [None] * B if encodings is None else list(encodings)
@@ -390,12 +463,19 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
     if wave_batch:
         from .inference import to_waveforms
         extra = dict(encoding=encs, dither=dith, dither_keys=keys) if coded else {}
+        if timing is not None:
+            extra.update(token_ends=timing["token_ends"], x_lengths=timing["x_lengths"], breaks=timing["breaks"], return_marks=True)
         if levelled:
-            audio, report = to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, loudness=loud, return_loudness=True, **metered, **extra)
+            out = to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, loudness=loud, return_loudness=True, **metered, **extra)
+            audio, report = out[0], out[1]
         else:
-            audio = to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, **extra)
+            out = to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, **extra)
+            audio = out[0] if timing is not None else out
         for r, a in zip(res, audio):
             r["audio"] = a
+        if timing is not None:
+            for r, u, tokens in zip(res, timing["units"], out[-1]):
+                marks_into(r, u, tokens)
     else:
         from .inference import _convert_rows, _waveform_on_device, trim_trailing_silence
         for b, (r, rate, enc, on, key) in enumerate(zip(res, rates, encs, dith, keys)):
@@ -440,14 +520,20 @@ def synthesise_batch(model, batch: List[Any], vocoder=None, wave_batch: bool = T
     x, x_len, emb = request_inputs(model, batch)
     head = batch[0]
     model.decoder.solver = head.solver
+    timing = timing_fields(batch)
+    if timing is not None and vocoder is None and (timing["marks"] or timing["breaks"] is not None):
+        raise ValueError("marks and breaks need a vocoder: they are positions in the audio")
     out = model.synthesise(x, x_len, head.n_timesteps, speaker_embeddings=emb,
                            scale_correction=[r.scale_correction for r in batch],
                            length_scale=[r.length_scale for r in batch], per_request_padding=True,
-                           durations=duration_rows(batch))
+                           durations=duration_rows(batch), **shaping_kwargs(timing))
     lens = out["mel_lengths"].tolist()
     res = [{"mel": out["mel"][b, :, :int(lens[b])], "mel_length": int(lens[b])} for b in range(B)]
+    tail = {}
+    if timing is not None and "token_ends" in out:
+        tail["timing"] = dict(token_ends=out["token_ends"], x_lengths=x_len, breaks=timing["breaks"], units=batch)
     waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch, [r.sample_rate for r in batch], *encoding_fields(batch),
-                   loudness=loudness_field(batch), true_peak=true_peak_field(batch))
+                   **tail, loudness=loudness_field(batch), true_peak=true_peak_field(batch))
     return res
 
 
@@ -464,10 +550,11 @@ def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> 
     x, x_len, emb = request_inputs(model, rows)
     head = rows[0]
     model.decoder.solver = head.solver
+    timing = timing_fields(rows, units)
     out = model.synthesise(x, x_len, head.n_timesteps, speaker_embeddings=emb,
                            scale_correction=[r.scale_correction for r in rows],
                            length_scale=[r.length_scale for r in rows], per_request_padding=True,
-                           durations=duration_rows(rows))
+                           durations=duration_rows(rows), **shaping_kwargs(timing))
     lens = [int(v) for v in out["mel_lengths"].tolist()]
     counts = [len(unit_rows(u)) for u in units]
     gaps = [g for u in units for g in (u.gaps() if isinstance(u, Document) else [0])]
@@ -478,6 +565,9 @@ def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> 
         extra.update(loudness=targets, return_loudness=True)
         if true_peak_field(units) is not None:
             extra.update(true_peak=true_peak_field(units), return_meter=True)
+    timed = timing is not None and "token_ends" in out
+    if timed:
+        extra.update(token_ends=out["token_ends"], x_lengths=x_len, breaks=timing["breaks"], return_marks=True)
     out_w = to_waveforms(out["mel"], out["mel_lengths"], vocoder, sample_rate=[int(u.sample_rate) for u in units],
                          documents=counts, gaps=gaps, fade_ms=fade_ms,
                          level=[u.level if isinstance(u, Document) else "sentence" for u in units], return_segments=True, **extra)
@@ -494,6 +584,8 @@ def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> 
         if u.encoding is not None:
             r["encoding"] = u.encoding
         report_into(r, rep, u.loudness, u.true_peak)
+        if timed:
+            marks_into(r, u, out_w[-1][len(res)] if isinstance(u, Document) else out_w[-1][len(res)][0])
         res.append(r)
         b += n
     return res
@@ -637,6 +729,9 @@ class StepBatcher:
             raise ValueError(f"utterance of {len(ids)} tokens exceeds the batch budget of {self.max_tokens}")
         r = Request(ids=list(ids), **kw)
         duration_rows([r])
+        if timing_fields([r]) is not None:
+            raise ValueError("token_scale, token_extend, breaks and marks are served by FrameBudgetBatcher: the step-level admission "
+                             "path does not take them")
         step_grid(r.n_timesteps)
         with self._cv:
             if self._stop:

@@ -184,6 +184,21 @@ int mtts_durations_given(const float* d_dur, const float* d_x_mask, float length
     return 0;
 }
 
+int mtts_durations_shaped(const float* d_logw, const float* d_x_mask, const float* d_scale_correction, const float* d_length_scale,
+                          const float* d_given, const int32_t* d_given_rows, const float* d_token_scale, const float* d_token_extend, int B,
+                          int Tx, float* d_durations, int32_t* d_cum, int64_t* d_y_fine_lengths, void* stream) {
+    if (!d_x_mask || !d_scale_correction || !d_length_scale || !d_durations || !d_cum || !d_y_fine_lengths) {
+        set_error("mtts_durations_shaped: null argument");
+        return -1;
+    }
+    if (!d_logw && !(d_given && !d_given_rows)) { set_error("mtts_durations_shaped: null d_logw (a predicted row reads it)"); return -1; }
+    if (d_given_rows && !d_given) { set_error("mtts_durations_shaped: d_given_rows without d_given"); return -1; }
+    if (B < 1 || Tx < 1) { set_error("mtts_durations_shaped: bad shape"); return -1; }
+    HIP_OK(launch_durations_shaped(d_logw, d_x_mask, d_scale_correction, d_length_scale, d_given, d_given_rows, d_token_scale, d_token_extend,
+                                   B, Tx, d_durations, d_cum, d_y_fine_lengths, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 int mtts_align_pool(const float* d_mu_x, const int32_t* d_cum, const int64_t* d_y_fine_lengths, int B, int n_feats, int Tx, int T_pad,
                     float* d_mu_y, float* d_y_mask, int64_t* d_y_lengths, void* stream) {
     HIP_OK(launch_align_pool(d_mu_x, d_cum, d_y_fine_lengths, B, n_feats, Tx, T_pad, d_mu_y, d_y_mask, d_y_lengths,

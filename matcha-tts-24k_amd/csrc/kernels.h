@@ -420,6 +420,10 @@ hipError_t launch_durations(const float* logw, const float* mask, float scale_co
 // durations the caller brings: dur = max(round(given * ls), 0) * mask on the rows given_rows marks (null: all; others keep dur), same scan
 hipError_t launch_durations_given(const float* given, const float* mask, float length_scale, const float* ls_b, const int32_t* given_rows,
                                   int B, int Tx, float* dur, int32_t* cum, int64_t* yfl, hipStream_t s);
+// shaped durations: predicted and given rows in one launch, a rate and an extension per token (include/mtts.h mtts_durations_shaped)
+hipError_t launch_durations_shaped(const float* logw, const float* mask, const float* sc_b, const float* ls_b, const float* given,
+                                   const int32_t* given_rows, const float* tscale, const float* textend, int B, int Tx, float* dur,
+                                   int32_t* cum, int64_t* yfl, hipStream_t s);
 // level mask of the U-Net: dst[b, t] = src[b, t * stride], t < T_dst (reference decoder.py:390 mask[:, :, ::2])
 hipError_t launch_mask_down(const float* src, int B, int T_src, int stride, float* dst, int T_dst, hipStream_t s);
 // Per-level frame tables of one estimator call (norm_glue.hip).  Level l has T[l] rows per utterance.
@@ -561,5 +565,42 @@ struct WaveJoinArgs {
 constexpr int JOIN_TILE = 2048;        // output samples per workgroup of the move
 constexpr int JOIN_STAGE = 256;        // rows of a document the move stages in LDS at once
 hipError_t launch_wave_join(const WaveJoinArgs& a, hipStream_t s);
+
+// ---- token timing (timing.hip): marks of every token in the finished audio, the plan of the breaks and their gather, see include/mtts.h
+struct TimingArgs {
+    const int32_t* cum = nullptr;          // [B][Tx] inclusive cumulative durations, fine frames
+    const int64_t* x_len = nullptr;        // [B] tokens
+    const int64_t* keep = nullptr;         // [B] kept samples, -1 = refused upstream
+    int B = 0, Tx = 0, fine_hop = 0;
+    int64_t keep_max = 0, out_max = 0, pause_max = 0;
+    const int32_t* break_first = nullptr;  // [B + 1] or null: the breaks of row b are [break_first[b], break_first[b + 1])
+    const int32_t* break_token = nullptr;  // [NB]: the break follows this token
+    const int64_t* break_pause = nullptr;  // [NB] samples
+    int NB = 0;
+    int64_t* marks = nullptr;              // [B][Tx][2]
+    int64_t* out_lengths = nullptr;        // [B]
+    int64_t* header = nullptr;             // workspace: B, Tx, keep_max, pause_max, out_max
+    int64_t* verdict = nullptr;            // workspace [B][2]: (reason or 0, the value it speaks of)
+    int64_t* rowinfo = nullptr;            // workspace [B][2]: (keep, new length), -1 for a refused row
+    int64_t* cut = nullptr;                // workspace [NB]: where break k cuts its row
+    int64_t* ostart = nullptr;             // workspace [NB]: where the samples behind break k begin in the lengthened row
+};
+struct WaveBreaksArgs {
+    const float* audio = nullptr;          // [B][ld], read only inside [0, keep_b)
+    int64_t ld = 0;
+    const int32_t* break_first = nullptr;
+    int B = 0;
+    int64_t fade = 0;
+    float* out = nullptr;                  // [B][out_ld]
+    int64_t out_ld = 0;
+    int NB = 0;
+    const int64_t* header = nullptr;       // the plan of mtts_token_timing (its workspace)
+    const int64_t* rowinfo = nullptr;
+    const int64_t* cut = nullptr;
+    const int64_t* ostart = nullptr;
+};
+constexpr int BREAKS_TILE = 2048;          // output samples per workgroup of the gather
+hipError_t launch_token_timing(const TimingArgs& a, hipStream_t s);
+hipError_t launch_wave_breaks(const WaveBreaksArgs& a, hipStream_t s);
 
 }  // namespace mtts

@@ -847,6 +847,59 @@ __global__ __launch_bounds__(256) void durations_given_kernel(const float* __res
     }
     durations_scan(s, tid, i0, i1, dur + (size_t)b * Tx, cum + (size_t)b * Tx, yfl + b, part);
 }
+// Shaped durations (include/mtts.h mtts_durations_shaped): one launch for a batch that mixes predicted and given rows, with a
+// rate s and an extension a (fine frames) per token.  A predicted row follows durations_kernel's own order and continues
+//   v = (expf(logw) - 2) * m; v = v * sc; v = v * ls; v = v * s; v = v + a; d = fmaxf(rintf(v), s == 0 ? 0 : 1) * m
+// a given row (given != null and given_rows null or given_rows[b] != 0)
+//   v = given * ls; v = v * s; v = v + a; d = fmaxf(rintf(v), 0) * m
+// with s clamped to [0, 16] (NaN: 1) and a to [-4096, 4096] (NaN: 0) first; then the shared scan.  With s == 1 and a == 0 the two
+// extra operations are exact, so the outputs are those of durations_kernel / durations_given_kernel bit for bit.
+__global__ __launch_bounds__(256) void durations_shaped_kernel(const float* __restrict__ logw, const float* __restrict__ mask,
+                                                               const float* __restrict__ sc_b, const float* __restrict__ ls_b,
+                                                               const float* __restrict__ given, const int32_t* __restrict__ given_rows,
+                                                               const float* __restrict__ tscale, const float* __restrict__ textend,
+                                                               int Tx, float* __restrict__ dur, int32_t* __restrict__ cum,
+                                                               int64_t* __restrict__ yfl) {
+    __shared__ int part[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float sc = sc_b[b], ls = ls_b[b];
+    const bool take = given && (!given_rows || given_rows[b] != 0);
+    const int per = (Tx + 255) / 256;
+    const int i0 = tid * per, i1 = min(Tx, i0 + per);
+    int sum = 0;
+    for (int i = i0; i < i1; ++i) {
+        const size_t at = (size_t)b * Tx + i;
+        const float m = mask[at];
+        float s = tscale ? tscale[at] : 1.0f, a = textend ? textend[at] : 0.0f;
+        s = s != s ? 1.0f : fminf(fmaxf(s, 0.0f), 16.0f);
+        a = a != a ? 0.0f : fminf(fmaxf(a, -4096.0f), 4096.0f);
+        float v, lo;
+        if (take) {
+            v = given[at] * ls;
+            lo = 0.0f;
+        } else {
+            v = (expf(logw[at]) - 2.0f) * m;
+            v = v * sc;
+            v = v * ls;
+            lo = s == 0.0f ? 0.0f : 1.0f;
+        }
+        v = v * s;
+        v = v + a;
+        const float d = fmaxf(rintf(v), lo) * m;
+        dur[at] = d;
+        sum += (int)d;
+    }
+    durations_scan(sum, tid, i0, i1, dur + (size_t)b * Tx, cum + (size_t)b * Tx, yfl + b, part);
+}
+hipError_t launch_durations_shaped(const float* logw, const float* mask, const float* sc_b, const float* ls_b, const float* given,
+                                   const int32_t* given_rows, const float* tscale, const float* textend, int B, int Tx, float* dur,
+                                   int32_t* cum, int64_t* yfl, hipStream_t s) {
+    if (!mask || !sc_b || !ls_b || !dur || !cum || !yfl || B <= 0 || Tx <= 0) return hipErrorInvalidValue;
+    if (!logw && !(given && !given_rows)) return hipErrorInvalidValue;      // a predicted row reads logw
+    hipLaunchKernelGGL(durations_shaped_kernel, dim3(B), dim3(256), 0, s, logw, mask, sc_b, ls_b, given, given_rows, tscale, textend, Tx, dur,
+                       cum, yfl);
+    return hipGetLastError();
+}
 hipError_t launch_durations_given(const float* given, const float* mask, float ls, const float* ls_b, const int32_t* given_rows, int B, int Tx,
                                   float* dur, int32_t* cum, int64_t* yfl, hipStream_t s) {
     if (!given || !mask || !dur || !cum || !yfl || B <= 0 || Tx <= 0) return hipErrorInvalidValue;

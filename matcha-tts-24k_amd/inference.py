@@ -123,7 +123,8 @@ class MatchaTTSInfer(nn.Module):
     range_policy = "rerun"
 
     def synthesise(self, x, x_lengths, n_timesteps, speaker=0, voice_mix=None, scale_correction=1.0, length_scale=1.0,
-                   debug=False, z=None, sync_max=None, per_request_padding=False, speaker_embeddings=None, durations=None):
+                   debug=False, z=None, sync_max=None, per_request_padding=False, speaker_embeddings=None, durations=None, *,
+                   token_scale=None, token_extend=None, return_timing=False):
         """``_synthesise`` under the range guard (``Runtime.guarded``): one read of the sticky device flags per call (a stream
         synchronisation)."""
         rt = self._rt
@@ -134,8 +135,12 @@ class MatchaTTSInfer(nn.Module):
             return bool(flags[0] or flags[1]), bool(flags[2])
 
         def run():
+            if token_scale is None and token_extend is None and not return_timing:
+                return self._synthesise(x, x_lengths, n_timesteps, speaker, voice_mix, scale_correction, length_scale, debug, z, sync_max,
+                                        per_request_padding, speaker_embeddings, durations)
             return self._synthesise(x, x_lengths, n_timesteps, speaker, voice_mix, scale_correction, length_scale, debug, z, sync_max,
-                                    per_request_padding, speaker_embeddings, durations)
+                                    per_request_padding, speaker_embeddings, durations, token_scale=token_scale,
+                                    token_extend=token_extend, return_timing=return_timing)
         return rt.guarded(self.range_policy, run, verdict, can_rerun=sync_max is None)      # (a rank-local rerun would repeat sync_max's collective)
 
     @torch.inference_mode()
@@ -245,6 +250,49 @@ class MatchaTTSInfer(nn.Module):
             return hip.durations_given(host.to(dev), x_mask, length_scale)
         predicted, _, _ = hip.durations(logw, x_mask, scale_correction, length_scale)
         return hip.durations_given(host.to(dev), x_mask, length_scale, given_rows=rows, out=predicted)
+
+    @staticmethod
+    def _rows_or_tensor(v, B, Tx, dev, fill, name):
+        """``token_scale`` / ``token_extend`` as a float32 [B, Tx] device tensor: a tensor as it is, or B rows (None, or up to Tx
+        values) laid over ``fill``; None stays None."""
+        if v is None:
+            return None
+        if torch.is_tensor(v):
+            v = v[None] if v.dim() == 1 else v
+            if v.shape != (B, Tx):
+                raise ValueError(f"{name} must have shape ({B}, {Tx}), got {tuple(v.shape)}")
+            return v.to(device=dev, dtype=torch.float32)
+        if len(v) != B:
+            raise ValueError(f"{name} needs one row per utterance ({B}), got {len(v)}")
+        host = torch.full((B, Tx), float(fill), dtype=torch.float32)
+        for b, row in enumerate(v):
+            if row is None:
+                continue
+            row = torch.as_tensor(row).detach().to("cpu", torch.float32).reshape(-1)
+            if row.numel() > Tx:
+                raise ValueError(f"{name}[{b}] has {row.numel()} values for {Tx} tokens")
+            host[b, :row.numel()] = row
+        return host.to(dev)
+
+    @classmethod
+    def _shaped_durations(cls, hip, given, logw, x_mask, scale_correction, length_scale, token_scale, token_extend):
+        """``hip.durations_shaped`` for ``synthesise(token_scale=, token_extend=)``: predicted rows, given rows (``durations=`` as
+        ``_given_durations`` takes it) and the shaping of both in one launch."""
+        B, _, Tx = x_mask.shape
+        dev = x_mask.device
+        s = cls._rows_or_tensor(token_scale, B, Tx, dev, 1.0, "token_scale")
+        a = cls._rows_or_tensor(token_extend, B, Tx, dev, 0.0, "token_extend")
+        rows = None
+        if given is not None and not torch.is_tensor(given):
+            if len(given) != B:
+                raise ValueError(f"durations need one row per utterance ({B}), got {len(given)}")
+            rows = [row is not None for row in given]
+            given = cls._rows_or_tensor(given, B, Tx, dev, 0.0, "durations") if any(rows) else None
+            rows = None if given is None or all(rows) else rows
+        elif given is not None:
+            given = (given[None] if given.dim() == 1 else given).to(dev)
+        return hip.durations_shaped(logw, x_mask, scale_correction, length_scale, given=given, given_rows=rows, token_scale=s,
+                                    token_extend=a)
 
     @torch.inference_mode()
     def align(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0, voice_mix=None,
@@ -546,7 +594,8 @@ class MatchaTTSInfer(nn.Module):
 
     @torch.inference_mode()
     def _synthesise(self, x, x_lengths, n_timesteps, speaker=0, voice_mix=None, scale_correction=1.0, length_scale=1.0,
-                    debug=False, z=None, sync_max=None, per_request_padding=False, speaker_embeddings=None, durations=None):
+                    debug=False, z=None, sync_max=None, per_request_padding=False, speaker_embeddings=None, durations=None, *,
+                    token_scale=None, token_extend=None, return_timing=False):
         """Text ids -> mel (reference inference.py:78-183).  Returns ``{"mel": [B, n_feats, T_valid_max]}`` (+ the
         reference's debug tensors when ``debug``).
 
@@ -562,14 +611,28 @@ class MatchaTTSInfer(nn.Module):
         ``durations``: fine frames per token to speak with instead of the duration predictor's -- a [B, Tx] tensor (e.g.
         ``align(...)["durations"]``, or this method's own debug ``phoneme_durations``, which reproduces the default call bit for
         bit), or a list of B rows where None leaves a row to the predictor (the batcher's mix).  ``scale_correction`` corrects the
-        predictor and is ignored on given rows; ``length_scale`` still multiplies.  A zero drops a token."""
+        predictor and is ignored on given rows; ``length_scale`` still multiplies.  A zero drops a token.
+        ``token_scale`` / ``token_extend`` (keyword-only): a rate and an extension in fine frames per token -- [B, Tx] tensors, or lists
+        of B rows where None leaves a row alone -- applied to predicted and given rows alike in ONE launch (``hip.durations_shaped``:
+        ``d = round(d_unrounded * scale + extend)``; a scale of exactly 0 drops the token).  Host values outside [0, 16] /
+        [-4096, 4096] raise ``ValueError`` before anything is launched.  ``return_timing``: the result also carries ``"token_ends"``
+        (the inclusive cumulative durations in fine frames, int32 [B, Tx]: what ``to_waveforms(token_ends=)`` takes) and
+        ``"durations"``.  Without the three, exactly the calls of before are made."""
+        shaped = token_scale is not None or token_extend is not None
+        if shaped:
+            from . import timing as TM
+            TM.check_shaping(token_scale, "token_scale")
+            TM.check_shaping(token_extend, "token_extend")
         hip = self._rt.ready()
         dev = x.device
         B = x.shape[0]
         e_enc, e_dur = self._voice_rows(B, dev, speaker, voice_mix, speaker_embeddings)
 
         mu_x, logw, x_mask = self.encoder(x, x_lengths, e_enc, e_dur)
-        if durations is None:
+        if shaped:
+            durations, cum, y_fine_lengths = self._shaped_durations(hip, durations, logw, x_mask, scale_correction, length_scale,
+                                                                    token_scale, token_extend)
+        elif durations is None:
             durations, cum, y_fine_lengths = hip.durations(logw, x_mask, scale_correction, length_scale)
         else:
             durations, cum, y_fine_lengths = self._given_durations(hip, durations, logw, x_mask, scale_correction, length_scale)
@@ -590,12 +653,13 @@ class MatchaTTSInfer(nn.Module):
             t_len = [fix_len_compatibility(max(int(v), 1)) for v in y_fine_lengths.tolist()]
         mel = self.decoder(mu_y, y_mask, n_timesteps, z=z, t_out=y_max_length, out_scale=self._rt.mel_std,
                            out_shift=self._rt.mel_mean, t_len=t_len, y_lengths=y_lengths, y_max=y_max_length)
+        timing = {"token_ends": cum, "durations": durations} if return_timing else {}
         if not debug:
-            return {"mel": mel, "mel_lengths": y_lengths}
+            return {"mel": mel, "mel_lengths": y_lengths, **timing}
         encoder_mel = mu_y[:, :, :y_max_length] * self._rt.mel_std + self._rt.mel_mean
         raw = ((torch.exp(logw) - 2) * x_mask).squeeze(1)
         return {"mel": mel, "encoder_mel": encoder_mel, "phoneme_durations": durations, "raw_phoneme_durations": raw,
-                "mel_lengths": y_lengths, "mu_y": mu_y, "y_mask": y_mask, "logw": logw, "mu_x": mu_x}
+                "mel_lengths": y_lengths, "mu_y": mu_y, "y_mask": y_mask, "logw": logw, "mu_x": mu_x, **timing}
 
 
 def _recordings_24k(clips, dev, sample_rate=24000, lengths=None):
@@ -785,7 +849,7 @@ def finish_waveforms(audio, lengths, hop=0, silence_threshold_db=-60.0):
 @torch.inference_mode()
 def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, *, encoding=None, dither=False, dither_keys=None,
                  documents=None, gaps=None, fade_ms=5.0, level="document", return_segments=False, loudness=None, return_loudness=False,
-                 true_peak=None, return_meter=False, sample_rate=24000):
+                 true_peak=None, return_meter=False, token_ends=None, x_lengths=None, breaks=None, return_marks=False, sample_rate=24000):
     """``trim_trailing_silence(to_waveform(mel[b:b+1, :, :len_b], vocoder))`` (reference inference.py:246) for every row of a
     ragged batch in one device pass: ragged Vocos decode, per-row peak normalisation, per-row trim lengths, then ONE copy of the
     audio and one of the [B] lengths -- one synchronisation for the whole batch.  Returns a list of B 1-D host tensors
@@ -831,7 +895,28 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     or under the ceiling.  A ceiling on a row without a loudness target raises ``ValueError`` before anything is launched: the
     ceiling limits a gain, and such a row has none.  ``return_meter``: the report entries (returned as with ``return_loudness``) are
     dicts of seven figures -- ``lufs``, ``gain``, ``lra``, ``momentary_max``, ``short_term_max``, ``peak``, ``true_peak`` (``loudness.meter``;
-    the peaks linear), all measured BEFORE the gain; they ride in the same ``meta`` copy."""
+    the peaks linear), all measured BEFORE the gain; they ride in the same ``meta`` copy.
+
+    ``token_ends`` / ``x_lengths`` / ``breaks`` / ``return_marks``: None / False (exactly the calls above are made), or token timing
+    (``timing.token_marks``, one planning launch after the normalisation and the trim, ahead of the join).  ``token_ends`` [B, Tx] and
+    ``x_lengths`` [B] are ``synthesise(return_timing=True)["token_ends"]`` and the token counts.  ``breaks``: per ROW a list of
+    ``(token, pause_ms)`` (None: none) -- a pause is cut into the row after that token (``timing.apply_breaks``, launched only when a row
+    has a break; the fade at a cut is ``fade_ms``), and the join, the loudness stage, the rate conversion and the encoder see the
+    lengthened rows through the device lengths they already take.  ``return_marks``: also return, LAST in the tuple, the marks
+    ``[(start_s, end_s)]`` per token of each row -- with ``documents=`` one list per row of each document, a row's start inside its
+    document added -- in seconds of the 24 kHz result like the segments, so they do not depend on the output rate.  The marks are copied
+    behind the batch's one synchronisation; no further wait is added."""
+    timed = token_ends is not None or breaks is not None or return_marks
+    if timed and (token_ends is None or x_lengths is None):
+        raise ValueError("to_waveforms: breaks and return_marks need token_ends= and x_lengths= (synthesise(return_timing=True))")
+    if timed:
+        from . import timing as TM
+        B_rows = 1 if mel.dim() == 2 else mel.shape[0]
+        if breaks is not None and len(breaks) != B_rows:
+            raise ValueError(f"breaks need one entry per row ({B_rows}), got {len(breaks)}")
+        break_rows = None if breaks is None else [
+            [(t, int(round(p * SAMPLE_RATE / 1000.0))) for t, p in TM.check_breaks(r, None, TM.PAUSE_MAX_MS, f"breaks[{b}]")]
+            for b, r in enumerate(breaks)]
     if documents is None and (gaps is not None or return_segments):
         raise ValueError("to_waveforms: gaps and return_segments belong to documents=")
     if loudness is not None:                                           # (a target that is no level raises before anything is looked at)
@@ -861,11 +946,47 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     loud, report = [], []
     audio = model.decode(mel, mel_lengths, check=False)
     out_lengths, scale = finish_waveforms(audio, mel_lengths, hop=hop, silence_threshold_db=silence_threshold_db)
+    if timed:
+        # the timing plan (+ the breaks gather): from here on the rows are as long as the plan says, trimmed or not
+        keep = out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1))
+        fade = int(round(float(fade_ms) * SAMPLE_RATE / 1000.0))
+        audio, L = _hip.aligned_rows(audio, 4, "audio")
+        marks, out_lengths, plan = TM.token_marks(token_ends, x_lengths, keep, break_rows, fine_hop=hop // 2, keep_max=audio.shape[1],
+                                                   check=False)
+        if plan.NB:
+            audio = TM.apply_breaks(audio, plan, fade)
+        trim = True
+        marks_host = None
+        if return_marks:
+            marks_host = torch.empty(marks.shape, dtype=marks.dtype, pin_memory=True)
+            marks_host.copy_(marks, non_blocking=True)                # complete at the batch's one synchronisation, below
+        row_starts = [] if csr is not None else None
+        try:
+            res = _finished_rows(audio, out_lengths, scale, mel_lengths, hop, T, trim, csr, gaps, fade_ms, level, rates, encs, dither,
+                                 dither_keys, return_segments, targets, report, stage, return_loudness, loud, row_starts)
+        except ValueError:
+            plan.raise_refused()                                      # the timing plan's own verdict names the row and the reason
+            raise
+        if not return_marks:
+            return res
+        per_row = TM.marks_rows(marks_host, B, row_starts)
+        if csr is not None:
+            per_row = [per_row[csr[g]:csr[g + 1]] for g in range(len(csr) - 1)]
+        return (*res, per_row) if isinstance(res, tuple) else (res, per_row)
+    return _finished_rows(audio, out_lengths, scale, mel_lengths, hop, T, trim, csr, gaps, fade_ms, level, rates, encs, dither, dither_keys,
+                          return_segments, targets, report, stage, return_loudness, loud)
+
+
+def _finished_rows(audio, out_lengths, scale, mel_lengths, hop, T, trim, csr, gaps, fade_ms, level, rates, encs, dither, dither_keys,
+                   return_segments, targets, report, stage, return_loudness, loud, row_starts=None):
+    """``to_waveforms`` behind the normalisation and the trim (and the timing plan): the join, the loudness stage, the rate conversion,
+    the encoder and the batch's one synchronisation.  ``row_starts``: a list that receives each row's start inside its document."""
+    B = audio.shape[0]
     if csr is not None:
         keep = out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1))
         fade = int(round(float(fade_ms) * SAMPLE_RATE / 1000.0))
         res = _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, _document_scales(scale, level, csr), rates, encs,
-                                dither, dither_keys, return_segments, targets, report, stage)
+                                dither, dither_keys, return_segments, targets, report, stage, row_starts)
         if not return_loudness:
             return res
         return (*res, report) if return_segments else (res, report)
@@ -1047,7 +1168,7 @@ def _document_scales(scale, level, csr):
 
 
 def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates, encs, dither, dither_keys, return_segments,
-                      targets=None, report=None, stage=None):
+                      targets=None, report=None, stage=None, row_starts=None):
     """The end of ``to_waveforms`` with ``documents=``: the join at 24 kHz, then the rate conversion and the encoding over one row
     per document on the joined device lengths, then the batch's one synchronisation -- the joined lengths, the rows' starts and kept
     lengths ride in the one ``meta`` copy -- and one copy of no more columns than the longest document has."""
@@ -1071,6 +1192,8 @@ def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates
     meta = torch.cat(words).cpu().tolist()                             # waits for the stream: the batch's one synchronisation
     B = keep.shape[0]
     got, begin, kept, frames = meta[:G], meta[G:G + B], meta[G + B:G + 2 * B], meta[G + 2 * B:G + 3 * B]
+    if row_starts is not None:
+        row_starts.extend(begin)
     at = G + 3 * B                                                     # what rides behind the lengths: loudness words, byte counts
     if loud and report is not None:
         _loudness_report(meta[at:at + len(loud) * G], report, len(loud))

@@ -112,8 +112,14 @@ class SpeechService:
     different ``steps`` share launches) built with ``vocoder=`` so that results carry ``"audio"``."""
 
     def __init__(self, batcher, phonemize: Callable[[str, str], Sequence[int]], max_text_length: int = MAX_TEXT_LENGTH,
-                 loudness: Optional[float] = None, true_peak: Optional[float] = None):
-        """``loudness``: None, or the target in LUFS every request of this service is brought to on the device (BS.1770 integrated
+                 loudness: Optional[float] = None, true_peak: Optional[float] = None, marks: bool = False,
+                 word_groups: Optional[Callable[[str, str, Sequence[int]], Sequence[int]]] = None):
+        """``marks``: every request of this service asks for token marks -- ``submit``'s future then carries ``"marks"``: ``{"tokens":
+        [(start_s, end_s)] per token}`` in seconds of the 24 kHz result (``timing.token_marks``; nominal positions) -- and
+        ``word_groups(text, language, ids)``, when given, names the word of each token (-1: none; ``timing.word_groups`` over the
+        phonemizer's separated symbols is the usual source), so that ``"marks"`` has ``"words"`` too.  ``timed()`` gives a view of the
+        service with marks on, for one request.  ``speak`` returns what it returns without them.
+        ``loudness``: None, or the target in LUFS every request of this service is brought to on the device (BS.1770 integrated
         loudness, ``loudness.normalize``; typically -16, -19 or -23).  ``levelled(target)`` gives a view of the service with another
         target, for one request: ``await service.levelled(-16).speak(text)``.  ``true_peak``: None, or the ceiling in dBTP the true
         peak of every levelled request is held under (EBU R 128 delivery: -1); it limits the gain towards the target, so it needs
@@ -124,13 +130,28 @@ class SpeechService:
         self.max_text_length = int(max_text_length)
         self.loudness = check_target(loudness)
         self.true_peak = checked_ceiling(true_peak, self.loudness)
+        self.marks = bool(marks)
+        self.word_groups = word_groups
+
+    def timed(self, marks: bool = True) -> "SpeechService":
+        """This service -- the same batcher, front end, target and ceiling -- with token marks on (or off): ``service.timed().submit(text)``
+        gives a future whose result carries ``"marks"``.  ``submit`` and ``speak`` keep their signatures, so marks for a single request
+        are asked for this way; ``submit_long`` and ``speak_long`` also take ``marks=`` themselves."""
+        return SpeechService(self.batcher, self.phonemize, self.max_text_length, self.loudness, self.true_peak, marks, self.word_groups)
+
+    def _timing_fields(self, text: str, language: str, ids) -> dict:
+        """The request fields marks add: ``marks`` and, with a ``word_groups`` callable, the word of each token."""
+        extra = {"marks": True}
+        if self.word_groups is not None:
+            extra["word_groups"] = list(self.word_groups(text, language, ids))
+        return extra
 
     def levelled(self, loudness: Optional[float], true_peak: Optional[float] = None) -> "SpeechService":
         """This service -- the same batcher and front end -- with ``loudness`` as its target (None: none) and ``true_peak`` as its
         true-peak ceiling in dBTP (None: none).  A value that is no level, and a ceiling without a target, raise here, before
         anything is submitted.  ``submit`` and ``speak`` keep their positional signatures, so the target of a
         single request is named this way; ``submit_long`` and ``speak_long`` also take ``loudness=`` themselves."""
-        return SpeechService(self.batcher, self.phonemize, self.max_text_length, loudness, true_peak)
+        return SpeechService(self.batcher, self.phonemize, self.max_text_length, loudness, true_peak, self.marks, self.word_groups)
 
     def submit(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
                speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None):
@@ -155,6 +176,8 @@ class SpeechService:
             extra["loudness"] = self.loudness
         if self.true_peak is not None:
             extra["true_peak"] = self.true_peak
+        if self.marks:
+            extra.update(self._timing_fields(text.strip(), p.language, ids))
         return self.batcher.submit(ids, speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver, n_timesteps=p.n_timesteps,
                                    scale_correction=p.scale_correction, length_scale=p.length_scale, **extra)
 
@@ -166,7 +189,8 @@ class SpeechService:
 
     def submit_long(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
                     speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None,
-                    max_document_length: int = MAX_DOCUMENT_LENGTH, *, loudness=_SERVICE, true_peak=_SERVICE, **split_options):
+                    max_document_length: int = MAX_DOCUMENT_LENGTH, *, loudness=_SERVICE, true_peak=_SERVICE, marks=_SERVICE,
+                    **split_options):
         """A text longer than one utterance: cut into sentences (``longform.split_text(text, **split_options)``; the abbreviation set
         is that of the voice's language unless given), each phonemized on its own -- so the phonemizer's intonation marks stay per
         sentence --, and submitted as ONE document (``FrameBudgetBatcher.submit_document``): the sentences run as rows of one ragged
@@ -176,7 +200,9 @@ class SpeechService:
         cap are unchanged.  ``loudness``: the target in LUFS of the JOINED audio -- one gain per document, so its sentences keep
         their balance -- or None; by default the service's own.  The result then carries ``"loudness"`` and ``"gain"``.
         ``true_peak``: the ceiling in dBTP on the true peak of the joined, levelled audio, or None; by default the service's own
-        where the document has a target.  The result then also carries ``"true_peak"`` and ``"lra"``."""
+        where the document has a target.  The result then also carries ``"true_peak"`` and ``"lra"``.
+        ``marks``: whether the result carries ``"marks"`` -- ``{"tokens": one list of (start_s, end_s) per sentence}`` in the document's
+        timeline, ``"words"`` too with the service's ``word_groups`` -- by default as the service says."""
         encoding = response_encoding(response_format)
         from .loudness import check_target
         target = self.loudness if loudness is _SERVICE else check_target(loudness)
@@ -201,15 +227,20 @@ class SpeechService:
             extra["loudness"] = target
         if ceiling is not None:
             extra["true_peak"] = ceiling
+        if self.marks if marks is _SERVICE else bool(marks):
+            extra["marks"] = True
+            if self.word_groups is not None:
+                extra["word_groups"] = [list(self.word_groups(segment, p.language, i)) for (segment, _), i in zip(pieces, ids)]
         return self.batcher.submit_document(ids, [pause for _, pause in pieces], speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver,
                                             n_timesteps=p.n_timesteps, scale_correction=p.scale_correction, length_scale=p.length_scale,
                                             **extra)
 
     async def speak_long(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
                          speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None,
-                         max_document_length: int = MAX_DOCUMENT_LENGTH, *, loudness=_SERVICE, true_peak=_SERVICE, **split_options):
+                         max_document_length: int = MAX_DOCUMENT_LENGTH, *, loudness=_SERVICE, true_peak=_SERVICE, marks=_SERVICE,
+                         **split_options):
         """The joined waveform of a long text (a 1-D float tensor on the host), or with ``response_format`` the response body as
         ``bytes`` -- ``response_body``, as ``speak``."""
         res = await asyncio.wrap_future(self.submit_long(text, voice, speed, steps, solver, speaker_embedding, sample_rate, response_format,
-                                                         max_document_length, loudness=loudness, true_peak=true_peak, **split_options))
+                                                         max_document_length, loudness=loudness, true_peak=true_peak, marks=marks, **split_options))
         return response_body(res, response_format, int(sample_rate))

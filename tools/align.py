@@ -2,6 +2,7 @@
 """Forced alignment of phoneme ids to recordings: per-token durations and the measured scale_correction of a voice.
 
     python tools/align.py --matcha CKPT --ids-file FILE [--speaker N] [--out align.npz] clip1.wav clip2.wav ...
+    python tools/align.py --marks ...                                                     # also when each token is spoken in its clip
     python tools/align.py --synthetic 32 [--tokens 128 --frames 1500] [--repeat 200]      # no files: random weights, planted durations
 
 FILE holds one line of whitespace-separated phoneme ids per clip (the phonemiser is outside this package: ``process_text`` of the
@@ -141,6 +142,7 @@ def main() -> int:
     ap.add_argument("--tokens", type=int, default=128)
     ap.add_argument("--frames", type=int, default=1500)
     ap.add_argument("--repeat", type=int, default=1, help="time the call this many times per round (synthetic mode)")
+    ap.add_argument("--marks", action="store_true", help="also print when each token is spoken in its recording (seconds at 24 kHz; timing.token_marks)")
     args = ap.parse_args()
     inf = importlib.import_module(PKG + ".inference")
     if args.synthetic:
@@ -167,6 +169,22 @@ def main() -> int:
             d = int(host["durations"][b, i])
             print(f"    token {i:4d} id {ids[b][i]:4d}: {d:4d} frames {d * HOP_MS:8.1f} ms   (predicted {host['predicted_durations'][b, i]:.2f})")
     print(f"[align] scale_correction over {len(ids)} clips: {host['durations'].sum() / host['predicted_durations'].sum():.4f}")
+    if args.marks:
+        # the marks of a recording: its measured durations through the kernel that marks synthesised audio, keep = the clip's length
+        # (with --silence the clip was reshaped on the device: its length is then that of its fine mel)
+        tm = importlib.import_module(PKG + ".timing")
+        each = rates if isinstance(rates, (list, tuple)) else [rates] * len(clips)
+        if silence_of(args) is None:
+            keep = [int(round(len(c) * 24000 / int(r))) for c, r in zip(clips, each)]
+        else:
+            keep = [tm.FINE_HOP * int(v) for v in host["mel_fine_lengths"]]
+        cum = torch.cumsum(out["durations"].to(torch.int32), 1).to(torch.int32)
+        marks, _, _ = tm.token_marks(cum, x_len, keep)
+        for b, row in enumerate(tm.marks_rows(marks.cpu())):
+            print(f"[align] {args.wavs[b]}: marks")
+            for i, (t0, t1) in enumerate(row):
+                print(f"    token {i:4d} id {ids[b][i]:4d}: {t0:9.4f} s .. {t1:9.4f} s")
+        host["marks"] = marks.cpu().numpy()
     np.savez(args.out, **host)
     return 0
 

@@ -9,7 +9,8 @@
 (``process_text``) when that imports.  Where it does not, ``--segments-file`` takes the text already cut and phonemized: one
 segment per line, whitespace-separated phoneme ids, then ``|`` and the pause behind it in milliseconds (``12 7 33 | 300``), as
 tools/align.py takes ids.  The document goes through ``FrameBudgetBatcher.submit_document``; OUT.wav is RIFF PCM16 at
-``--sample-rate``, encoded on the device.  ``--loudness LUFS`` brings the joined document to that integrated loudness (ITU-R BS.1770,
+``--sample-rate``, encoded on the device.  ``--captions FILE.vtt|.srt`` writes one cue per sentence from the result's ``segments``;
+``--marks FILE.json`` writes when each token (and, with the phonemizer here, each word) is spoken, in seconds of the 24 kHz join.  ``--loudness LUFS`` brings the joined document to that integrated loudness (ITU-R BS.1770,
 one gain for the document, the sample peak held at 0.95) on the device, ahead of the rate conversion.  The sentences' times are printed.
 
 ``time``: a document of ``--sentences`` sentences of about ``--tokens`` tokens on random prod-shaped weights (a text of about
@@ -63,14 +64,20 @@ def speak(args) -> int:
     if args.segments_file is not None:
         pieces = read_segments(args.segments_file)
         ids, pauses = [s for s, _ in pieces], [ms for _, ms in pieces]
+        texts, groups = [f"segment {n + 1}" for n in range(len(ids))], None
     else:
         try:
             inf.process_text("test", p.language)
         except RuntimeError as e:
             raise SystemExit(f"{e}\n(no phonemizer here: cut and phonemize elsewhere and pass --segments-file)")
         pieces = sub("longform").split_text(Path(args.text).read_text(), max_chars=args.max_chars, language=p.language)
-        ids = [inf.process_text(s, p.language)["x_phone_ids"] for s, _ in pieces]
+        spoken = [inf.process_text(s, p.language) for s, _ in pieces]
+        ids = [r["x_phone_ids"] for r in spoken]
         pauses = [ms for _, ms in pieces]
+        texts = [s for s, _ in pieces]
+        # one symbol per id: the words are the runs between the phonemizer's spaces
+        groups = [sub("timing").word_groups(list(r["x_phones"])) if len(r["x_phones"]) == len(r["x_phone_ids"]) else None for r in spoken]
+        groups = groups if all(g is not None for g in groups) else None
     if not ids:
         raise SystemExit("nothing to speak")
     extra = {} if args.loudness is None else {"loudness": args.loudness}
@@ -78,6 +85,12 @@ def speak(args) -> int:
         if args.loudness is None:
             raise SystemExit("--true-peak limits the gain towards --loudness: name a target too")
         extra["true_peak"] = args.true_peak
+    if args.captions is not None and Path(args.captions).suffix.lower() not in (".vtt", ".srt"):
+        raise SystemExit("--captions writes WebVTT (.vtt) or SubRip (.srt)")
+    if args.marks is not None:
+        extra["marks"] = True
+        if groups is not None:
+            extra["word_groups"] = groups
     with bt.FrameBudgetBatcher(model, max_batch=max(32, len(ids)), max_tokens=max(8192, len(ids) * max(len(s) for s in ids)),
                                vocoder=vocoder, fade_ms=args.fade_ms) as q:
         res = q.submit_document(ids, pauses, speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver, n_timesteps=p.n_timesteps,
@@ -86,6 +99,14 @@ def speak(args) -> int:
     Path(args.out).write_bytes(sv.response_body(res, "wav", args.sample_rate))
     for n, (t0, t1) in enumerate(res["segments"]):
         print(f"{n:4d}  {t0:9.3f} s .. {t1:9.3f} s")
+    if args.captions is not None:
+        tm = sub("timing")
+        cues = [(t0, t1, text) for (t0, t1), text in zip(res["segments"], texts)]
+        Path(args.captions).write_text(tm.webvtt(cues) if Path(args.captions).suffix.lower() == ".vtt" else tm.srt(cues))
+        print(f"wrote {args.captions}: {len(cues)} cues")
+    if args.marks is not None:
+        Path(args.marks).write_text(json.dumps({"sample_rate": 24000, "sentences": texts, "segments": res["segments"], **res["marks"]}))
+        print(f"wrote {args.marks}: marks of {sum(len(t) for t in res['marks']['tokens'])} tokens")
     if "loudness" in res:
         print(f"loudness {res['loudness']:.2f} LUFS as synthesised, gain {res['gain']:.4f} towards {args.loudness:.2f} LUFS")
     if "true_peak" in res:
@@ -217,6 +238,8 @@ def main() -> int:
     sp.add_argument("--level", choices=("document", "sentence"), default="document")
     sp.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="integrated loudness of the joined document, e.g. -16, -19, -23")
     sp.add_argument("--true-peak", type=float, default=None, metavar="DB", help="ceiling in dBTP on the true peak of the levelled document, e.g. -1")
+    sp.add_argument("--captions", default=None, metavar="FILE.vtt|.srt", help="one cue per sentence, from the result's segments")
+    sp.add_argument("--marks", default=None, metavar="FILE.json", help="token (and word) marks in seconds of the 24 kHz join")
     tm = cmds.add_parser("time", help="per-call times on random weights")
     tm.add_argument("--sentences", type=int, default=20)
     tm.add_argument("--tokens", type=int, default=100)
