@@ -499,6 +499,45 @@ int mtts_groupnorm_mish_p16(const float* d_y, const float* d_gamma, const float*
                             const int* d_nrows, const int* d_nextra, const float* d_bias_stats, const float* d_out16_mask, float* d_out,
                             float* d_out16_f32, unsigned int* d_range_flag, void* d_scratch, void* stream);
 
+/* ---- The fp32-ROW flow (fp32 rows in, fp32 rows out: the text encoder, the duration predictor, the estimator when the range guard
+ * reruns on full-range arithmetic, MTTS_P16=0), one unit entry per kernel with every argument the model passes.  Host code only.
+ *
+ * gemm_f32_kernel<BM, A_MASK, A_NORM, TERMS> on the argument block of mtts_gemm_h16 (half16 = bf16 = 0).  A stays fp32 rows
+ * [B*T_in][lda]; the panel is packed on the host with ktap = round_up(C, 32) and its planes are made as the model's packer makes them
+ * for `terms`: 0 fp32 panel alone, 2 the interleaved fp16 head / scaled-residual image, 6 three bfloat16 planes.  c1 > 0: a second
+ * channel segment of c1 channels, read from d_a1 [B*T_in][lda1] when given, else from the last c1 columns of d_a ((C - c1) % 32 == 0).
+ * ldc: row stride of d_out (0 = N); only columns [0, N) of an output row are written.  Honoured from the block: d_a_mask, LayerNorm
+ * statistics (arrays or partial moments), act / p0 / p1, d_res + ldr, d_out_mask, out_scale, out_T / out_stride / out_off,
+ * d_stats_out, force_bm, d_range_flag (raised by terms 2 when an A element, or by any terms when an image element, lies beyond
+ * +-65504), and d_out16_f32 + d_out16_mask: the P16 copy of the result with residual scale out_lscale (2048 or 1), decoded to fp32
+ * [out rows][N].  The RAW image, [out rows + MTTS_ENTRY_GUARD_ROWS][2 N] halves (per 32 columns 32 heads then 32 residuals), starts at
+ * the first 256-byte boundary of d_scratch and is filled with 0x7e00 before the launch.  `tag` is written, wave_rows is 0.
+ * Refused before any launch (-1, mtts_last_error): everything the launcher refuses (null buffers, C or c1 % 4, lda / lda1 / ldc / ldr,
+ * one of a_mean / a_rstd, a_part with a_mean, LayerNorm on a convolution, stats_out without N % 64 == 0, an image without N % 32 == 0
+ * or with ldc / ldr % 4 != 0, SnakeBeta without constants, terms other than 0 / 2 / 6), res16_mode / out16_preload / gn_stats / gnr
+ * (features of the P16 kernel), and output rows leaving [0, out_T). */
+int64_t mtts_gemm_f32_args_scratch_bytes(const mtts_gemm_h16_args* g);
+int mtts_gemm_f32_args_run(mtts_gemm_h16_args* g, int terms, const float* d_a1, int lda1, int ldc, float out_lscale, void* d_scratch,
+                           void* stream);
+
+/* mtts_attention_f32 with d_klen [B] (may be NULL): keys of utterance b are rows [0, klen[b]).  The instantiation is read through
+ * mtts_last_kernel_tag: "attention_f32_kernel<2|4, false, false, false, false, 64>". */
+int mtts_attention_f32_run(const float* d_qkv, const float* d_mask, const int* d_klen, int B, int T, int H, int D, float scale, int mask_mode,
+                           float* d_out, void* stream);
+
+/* gn_partial + gn_apply with the fp32 store and every argument the fp32-row estimator passes: d_chbias [B][chbias_stride] (stride 0:
+ * one row [C]), d_res [B*T][ldr] added last, d_nrows [B] (rows that enter the statistics), d_nextra [B] + d_bias_stats [G][2] (folded
+ * padding), d_stats_out [B*T][C/64][2] (LayerNorm moments of the output rows).  NULL skips a feature.  d_scratch:
+ * mtts_groupnorm_scratch_bytes. */
+int mtts_groupnorm_mish_f32_run(const float* d_y, const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias,
+                                int chbias_stride, const float* d_res, int ldr, int B, int T, int C, int G, float eps, const int* d_nrows,
+                                const int* d_nextra, const float* d_bias_stats, float* d_out, float* d_stats_out, void* d_scratch,
+                                void* stream);
+
+/* mtts_channel_layernorm on rows of wider buffers: x [B*T][ldx], y [B*T][ldy]; only columns [0, C) of a row are read and written. */
+int mtts_channel_layernorm_ld(const float* d_x, int ldx, int B, int T, int C, const float* d_gamma, const float* d_beta, float eps, int act,
+                              const float* d_film, const float* d_mask, float* d_y, int ldy, void* stream);
+
 /* The two fused kernels (tblock_chain_kernel, conv_gn_kernel) on argument blocks, with what the plain entries above cannot pass: the
  * range flag, image rows longer than their payload, and the RAW output images.  Every output image has pad_* extra halves per row
  * (% 8 == 0) and MTTS_ENTRY_GUARD_ROWS rows behind its last row; the entry fills the whole image with `sentinel` (a 16-bit pattern)

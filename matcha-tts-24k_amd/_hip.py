@@ -255,6 +255,11 @@ def load() -> C.CDLL:
         "mtts_groupnorm_p16_scratch_bytes": (i64, [i32, i32, i32, i32]),
         "mtts_groupnorm_mish_p16": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, vp, vp, vp,
                                           vp, vp]),
+        "mtts_gemm_f32_args_scratch_bytes": (i64, [C.POINTER(MttsGemmH16Args)]),
+        "mtts_gemm_f32_args_run": (i32, [C.POINTER(MttsGemmH16Args), i32, vp, i32, i32, f32, vp, vp]),
+        "mtts_attention_f32_run": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp]),
+        "mtts_groupnorm_mish_f32_run": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]),
+        "mtts_channel_layernorm_ld": (i32, [vp, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp, vp, i32, vp]),
         "mtts_row_stats": (i32, [vp, i32, i32, i32, f32, vp, vp, vp]),
         "mtts_channel_layernorm": (i32, [vp, i32, i32, i32, vp, vp, f32, i32, vp, vp, vp, vp]),
         "mtts_groupnorm_scratch_bytes": (i64, [i32, i32, i32]),
@@ -1495,6 +1500,111 @@ def groupnorm_mish_p16(y, gamma, beta, mask, B, T, *, G=8, chbias=None, tile_sta
                                       ptr(tile_stats), tile_rows, ptr(nrows), ptr(nextra), ptr(bias_stats), ptr(out16_mask),
                                       ptr(out), ptr(out16), ptr(flag), scratch.data_ptr(), stream_ptr()))
     return {"out": out, "out16": out16, "flag": int(flag.item())}
+
+
+# ---- the fp32-row flow's unit entries.  Every output buffer is filled with F32_SENTINEL and has F32_GUARD floats behind its last row,
+# so a caller can see every element a launch did not write.
+F32_GUARD = 64
+F32_SENTINEL = -7.0e33
+
+
+def rows_ptr(t):
+    """Device pointer of fp32 rows that may be a row-strided view (unit stride inside a row); None passes NULL."""
+    if t is None:
+        return None
+    if not on_device(t) or t.stride(-1) != 1:
+        raise RuntimeError("mtts: rows must be on a HIP device with unit stride inside a row")
+    return t.data_ptr()
+
+
+def guarded(rows, ld, device):
+    """flat fp32 buffer of rows * ld + F32_GUARD sentinels"""
+    return torch.full((rows * ld + F32_GUARD,), F32_SENTINEL, dtype=torch.float32, device=device)
+
+
+def gemm_f32_args(a, w, bias=None, *, terms, B, T_in, T_out=None, tap_off=None, in_stride=1, c1=0, a1=None, a_mask=None, a_mean=None,
+                  a_rstd=None, a_part=None, act=0, p0=None, p1=None, res=None, out_mask=None, out_scale=1.0, out16_mask=None, want_f32=True,
+                  want_p16=False, into=None, ldc=0, out_T=0, out_stride=1, out_off=0, stats_out=False, force_bm=0, out_lscale=2048.0):
+    """gemm_f32_kernel as the fp32-row flow launches it (include/mtts.h mtts_gemm_f32_args_run).  a [B*T_in, >= C - c1 (or C)] fp32 rows
+    (a row-strided view is passed with its stride), a1 the second segment's rows or None (the last c1 columns of a); w Linear [N, C] or
+    Conv1d [N, C, k] anywhere; res a [rows, >= N] view.  ``into``: the result of an earlier call whose buffers this launch writes into
+    (strided output rows).  Returns a dict: out ([rows, N] view of buf), buf (flat, rows * ld + guard), ld, out16 (decoded image), image
+    (raw, int16 [rows + guard rows, 2 N]), stats, stats_buf, tag, flag."""
+    lib = load()
+    dev = a.device
+    N, Cc = w.shape[0], w.shape[1]
+    ntaps = w.shape[2] if w.dim() == 3 else 1
+    T_out = T_in if T_out is None else T_out
+    rows = B * (out_T if out_T else T_out)
+    ld = ldc if ldc else N
+    taps = (C.c_int32 * ntaps)(*(tap_off if tap_off is not None else [j - ntaps // 2 for j in range(ntaps)]))
+    hw, hw_ptr = _host(w)
+    g = MttsGemmH16Args()
+    g.d_a, g.lda, g.C, g.c1, g.d_a_mask = rows_ptr(a), a.stride(0), Cc, c1, ptr(a_mask)
+    g.B, g.T_in, g.T_out, g.ntaps, g.h_tap_off, g.in_stride = B, T_in, T_out, ntaps, C.cast(taps, C.c_void_p), in_stride
+    g.d_a_mean, g.d_a_rstd, g.d_a_part, g.a_nparts = ptr(a_mean), ptr(a_rstd), ptr(a_part), a_part.shape[1] if a_part is not None else 0
+    g.h_w, g.d_bias, g.N = hw_ptr, ptr(bias), N
+    g.act, g.d_p0, g.d_p1 = act, ptr(p0), ptr(p1)
+    g.d_res, g.ldr = rows_ptr(res), res.stride(0) if res is not None else 0
+    buf = into["buf"] if into is not None else (guarded(rows, ld, dev) if want_f32 else None)
+    out16 = torch.full((rows, N), F32_SENTINEL, dtype=torch.float32, device=dev) if want_p16 else None
+    g.d_out_mask, g.out_scale, g.d_out16_mask = ptr(out_mask), float(out_scale), ptr(out16_mask)
+    g.d_out, g.d_out16_f32 = ptr(buf), ptr(out16)
+    g.out_T, g.out_stride, g.out_off = out_T, out_stride, out_off
+    stats_buf = None
+    if stats_out:
+        stats_buf = into["stats_buf"] if into is not None else guarded(rows, 2 * (N // 64), dev)
+    g.d_stats_out = ptr(stats_buf)
+    g.force_bm = force_bm
+    flag = _flag(dev)
+    g.d_range_flag = ptr(flag)
+    n = size(lib.mtts_gemm_f32_args_scratch_bytes(C.byref(g)))
+    scratch = torch.empty(n + 256, dtype=torch.uint8, device=dev)
+    check(lib.mtts_gemm_f32_args_run(C.byref(g), int(terms), rows_ptr(a1), a1.stride(0) if a1 is not None else 0, int(ldc), float(out_lscale),
+                                     scratch.data_ptr(), stream_ptr()))
+    image = None
+    if want_p16:
+        off = (-scratch.data_ptr()) % 256
+        image = scratch[off:off + (rows + 64) * 2 * N * 2].view(torch.int16).view(rows + 64, 2 * N).clone()
+    return {"out": buf[:rows * ld].view(rows, ld)[:, :N] if buf is not None else None, "buf": buf, "ld": ld, "out16": out16, "image": image,
+            "stats": stats_buf[:rows * 2 * (N // 64)].view(rows, N // 64, 2) if stats_buf is not None else None, "stats_buf": stats_buf,
+            "tag": g.tag.decode(), "flag": int(flag.item())}
+
+
+def attention_f32_run(qkv, mask, B, T, H, D, scale, mask_mode=0, *, klen=None):
+    """fp32-I/O attention with klen (include/mtts.h mtts_attention_f32_run).  Returns a dict: out ([B*T, H*D] view of buf), buf, tag."""
+    lib = load()
+    buf = guarded(B * T, H * D, qkv.device)
+    check(lib.mtts_attention_f32_run(ptr(qkv), ptr(mask), ptr(klen), B, T, H, D, float(scale), mask_mode, ptr(buf), stream_ptr()))
+    return {"out": buf[:B * T * H * D].view(B * T, H * D), "buf": buf, "tag": last_kernel_tag()}
+
+
+def groupnorm_mish_f32_run(y, gamma, beta, mask, B, T, *, G=8, chbias=None, res=None, nrows=None, nextra=None, bias_stats=None,
+                           stats_out=False, eps=1e-5):
+    """gn_partial + gn_apply with the fp32 store (include/mtts.h mtts_groupnorm_mish_f32_run).  chbias [B, stride >= C] or [C]; res a
+    [B*T, >= C] view.  Returns a dict: out ([B*T, C] view of buf), buf, stats, stats_buf."""
+    lib = load()
+    Cc = y.shape[1]
+    scratch = torch.empty(size(lib.mtts_groupnorm_scratch_bytes(B, T, G)) + 256, dtype=torch.uint8, device=y.device)
+    buf = guarded(B * T, Cc, y.device)
+    stats_buf = guarded(B * T, 2 * (Cc // 64), y.device) if stats_out else None
+    check(lib.mtts_groupnorm_mish_f32_run(ptr(y), ptr(gamma), ptr(beta), ptr(mask), rows_ptr(chbias),
+                                          chbias.stride(0) if chbias is not None and chbias.dim() == 2 else 0, rows_ptr(res),
+                                          res.stride(0) if res is not None else 0, B, T, Cc, G, float(eps), ptr(nrows), ptr(nextra),
+                                          ptr(bias_stats), ptr(buf), ptr(stats_buf), scratch.data_ptr(), stream_ptr()))
+    return {"out": buf[:B * T * Cc].view(B * T, Cc), "buf": buf,
+            "stats": stats_buf[:B * T * 2 * (Cc // 64)].view(B * T, Cc // 64, 2) if stats_out else None, "stats_buf": stats_buf}
+
+
+def channel_layernorm_ld(x, B, T, Cc, gamma, beta, *, eps=1e-5, act=0, film=None, mask=None, ldy=None):
+    """Channel LayerNorm on rows of wider buffers (include/mtts.h mtts_channel_layernorm_ld).  x a [B*T, >= C] view.  Returns a dict:
+    out ([B*T, C] view of buf), buf, ld."""
+    lib = load()
+    ldy = Cc if ldy is None else ldy
+    buf = guarded(B * T, ldy, x.device)
+    check(lib.mtts_channel_layernorm_ld(rows_ptr(x), x.stride(0), B, T, Cc, ptr(gamma), ptr(beta), float(eps), act, ptr(film), ptr(mask), ptr(buf),
+                                        ldy, stream_ptr()))
+    return {"out": buf[:B * T * ldy].view(B * T, ldy)[:, :Cc], "buf": buf, "ld": ldy}
 
 
 def attention_f32(qkv, mask, B, T, H, D, scale, mask_mode):

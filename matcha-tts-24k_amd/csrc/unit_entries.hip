@@ -1020,6 +1020,152 @@ int mtts_cl_to_slots(const float* d_src, int ld, int B, int C, int T, float* d_p
     HIP_OK(launch_cl_to_slots(d_src, ld, B, C, T, d_pool, d_slots, S, T_pool, static_cast<hipStream_t>(stream)));
     return 0;
 }
+// ---- the fp32-row flow (fp32 rows in, fp32 rows out): gemm_f32_kernel at terms 0 / 2 / 6 with every argument the encoder, the
+// duration predictor and the full-range estimator pass; attention_f32_kernel<NW, false> with klen; gn_partial + gn_apply with the
+// fp32 store.  A stays fp32 rows (no image), the panel and its planes are made on the host as the model's packer makes them.
+#define GF "mtts_gemm_f32_args_run: "
+static int gemm_f32_args_check(const mtts_gemm_h16_args* g, int terms, const float* d_a1, int lda1, int ldc, float out_lscale) {
+    REFUSE_IF(!g, GF "null argument block");
+    REFUSE_IF(!g->d_a || !g->h_w || (!g->d_out && !g->d_out16_f32), GF "null buffer");
+    REFUSE_IF(g->half16 || g->bf16, GF "launches the fp32-row instantiations only (half16 and bf16 must be 0)");
+    REFUSE_IF(terms != 0 && terms != 2 && terms != 6, GF "terms must be 0, 2 or 6");
+    REFUSE_IF(out_lscale != 2048.0f && out_lscale != 1.0f, GF "out_lscale is 2048 or 1");
+    REFUSE_IF(g->res16_mode || g->d_res16_f32 || g->out16_preload, GF "res16 and out16_preload belong to the P16 kernel");
+    REFUSE_IF(g->d_gn_stats || g->gn_groups || g->d_gn_nrows, GF "gn_stats belongs to the P16 kernel");
+    REFUSE_IF(g->d_gnr_y || g->d_gnr_stats || g->d_gnr_gamma || g->d_gnr_beta || g->d_gnr_mask || g->d_gnr_nextra || g->d_gnr_bias_stats,
+              GF "gnr (the Block1D tail) belongs to the P16 kernel");
+    REFUSE_IF(g->ntaps < 1 || g->ntaps > MAX_TAPS, GF "ntaps out of range");
+    REFUSE_IF(g->B <= 0 || g->T_in <= 0 || g->T_out <= 0 || g->N <= 0 || g->in_stride < 0, GF "bad shape");
+    const int C = g->C, c1 = g->c1, c0 = C - c1, N = g->N, L = ldc ? ldc : N;
+    REFUSE_IF(C <= 0 || c1 < 0 || c1 >= C || (c0 & 3) || (c1 & 3), GF "C and c1 must be multiples of 4, c1 < C");
+    REFUSE_IF(c1 && (c0 % GEMM_BK), GF "a second segment needs (C - c1) % 32 == 0");
+    REFUSE_IF(d_a1 && !c1, GF "d_a1 without c1");
+    REFUSE_IF((g->lda & 3) || g->lda < (d_a1 ? c0 : C), GF "lda");
+    REFUSE_IF(d_a1 && ((lda1 & 3) || lda1 < c1), GF "lda1");
+    REFUSE_IF(ldc < 0 || (g->d_out && L < N), GF "ldc");
+    REFUSE_IF(g->d_res && g->ldr < N, GF "ldr");
+    REFUSE_IF(g->d_out16_f32 && ((N % 32) || (g->d_out && (L & 3)) || (g->d_res && (g->ldr & 3))),
+              GF "a P16 copy of the result needs N % 32 == 0 and ldc, ldr % 4 == 0");
+    REFUSE_IF((g->d_a_mean == nullptr) != (g->d_a_rstd == nullptr), GF "a_mean and a_rstd come together");
+    REFUSE_IF(g->d_a_part && (g->d_a_mean || g->a_nparts <= 0), GF "a_part excludes a_mean and needs a_nparts > 0");
+    REFUSE_IF((g->d_a_mean || g->d_a_part) && (g->ntaps != 1 || g->in_stride > 1 || (g->h_tap_off && g->h_tap_off[0] != 0)),
+              GF "LayerNorm in the prologue needs a plain Linear (one tap, offset 0, stride 1)");
+    REFUSE_IF(g->d_stats_out && ((N & 63) || !g->d_out || (L & 3) || (g->d_res && (g->ldr & 3))), GF "stats_out needs N % 64 == 0, fp32 rows and ldc, ldr % 4 == 0");
+    REFUSE_IF(g->act < ACT_NONE || g->act > ACT_GELU, GF "act");
+    REFUSE_IF(g->act == ACT_SNAKE && (!g->d_p0 || !g->d_p1), GF "SnakeBeta needs p0 and p1");
+    REFUSE_IF(g->force_bm != 0 && g->force_bm != 64 && g->force_bm != 128, GF "force_bm is 0, 64 or 128");
+    const int out_T = g->out_T > 0 ? g->out_T : g->T_out, out_stride = g->out_T > 0 ? g->out_stride : 1, out_off = g->out_T > 0 ? g->out_off : 0;
+    REFUSE_IF(out_stride < 1 || out_off < 0 || (g->T_out - 1) * out_stride + out_off >= out_T, GF "output rows leave [0, out_T)");
+    REFUSE_IF(g->ntaps > 1 && !g->h_tap_off, GF "a convolution needs its tap offsets");
+    return 0;
+}
+static void gemm_f32_args_sizes(const mtts_gemm_h16_args* g, size_t* image, size_t* npanel) {
+    const size_t out_rows = (size_t)g->B * (g->out_T > 0 ? g->out_T : g->T_out);
+    *image = g->d_out16_f32 ? (out_rows + MTTS_ENTRY_GUARD_ROWS) * 2 * (size_t)g->N * 2 : 0;
+    *npanel = (size_t)round_up(g->N, GEMM_BN) * g->ntaps * round_up(g->C, GEMM_BK);
+}
+int64_t mtts_gemm_f32_args_scratch_bytes(const mtts_gemm_h16_args* g) {
+    if (!g || g->B <= 0 || g->T_in <= 0 || g->T_out <= 0 || g->N <= 0 || g->C <= 0 || g->ntaps < 1 || g->ntaps > MAX_TAPS) { set_error("mtts_gemm_f32_args_scratch_bytes: bad argument"); return -1; }
+    size_t image, npanel;
+    gemm_f32_args_sizes(g, &image, &npanel);
+    return (int64_t)(up256(image) + up256(npanel * 4) + up256(npanel * 6) + 512);
+}
+int mtts_gemm_f32_args_run(mtts_gemm_h16_args* g, int terms, const float* d_a1, int lda1, int ldc, float out_lscale, void* d_scratch, void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (g) { g->tag[0] = 0; g->wave_rows = 0; }
+    RET_IF(gemm_f32_args_check(g, terms, d_a1, lda1, ldc, out_lscale));
+    REFUSE_IF(!d_scratch, GF "null buffer");
+    const int C = g->C, c1 = g->c1, c0 = C - c1, N = g->N, ktap = round_up(C, GEMM_BK);
+    const int out_T = g->out_T > 0 ? g->out_T : g->T_out, out_stride = g->out_T > 0 ? g->out_stride : 1, out_off = g->out_T > 0 ? g->out_off : 0;
+    const size_t out_rows = (size_t)g->B * out_T;
+    size_t image, npanel;
+    gemm_f32_args_sizes(g, &image, &npanel);
+    // host: the panel, and its planes as the model's packer stores them (pack.hip add_planes)
+    std::vector<float> panel(npanel);
+    pack_weight_host(g->h_w, g->ntaps > 1 ? 1 : 0, N, C, g->ntaps, 0, nullptr, nullptr, panel.data(), ktap);
+    std::vector<uint16_t> planes(terms == 6 ? 3 * npanel : (terms == 2 ? 2 * npanel : 0));
+    if (terms == 2) split_panel_f16_host(panel.data(), npanel, planes.data());
+    if (terms == 6) split_panel_host(panel.data(), npanel, planes.data());
+    uintptr_t sc = up256(reinterpret_cast<uintptr_t>(d_scratch));
+    auto carve = [&](size_t bytes) { char* q = reinterpret_cast<char*>(sc); sc += up256(bytes); return q; };
+    _Float16* o16 = reinterpret_cast<_Float16*>(carve(image));                 // first, so a caller finds the raw image
+    float* d_panel = reinterpret_cast<float*>(carve(npanel * 4));
+    void* d_planes = carve(npanel * 6);
+    HIP_OK(hipMemcpyAsync(d_panel, panel.data(), npanel * 4, hipMemcpyHostToDevice, s));
+    if (terms) HIP_OK(hipMemcpyAsync(d_planes, planes.data(), planes.size() * 2, hipMemcpyHostToDevice, s));
+    HIP_OK(hipStreamSynchronize(s));                      // (the host vectors go out of scope)
+    if (image) HIP_OK(hipMemsetD16Async(reinterpret_cast<hipDeviceptr_t>(o16), 0x7e00, image / 2, s));
+    GemmArgs a;
+    a.a0 = g->d_a; a.lda0 = g->lda; a.c0 = c0; a.ktap = ktap; a.ntaps = g->ntaps;
+    if (c1) { a.a1 = d_a1 ? d_a1 : g->d_a + c0; a.lda1 = d_a1 ? lda1 : g->lda; a.c1 = c1; }
+    for (int j = 0; j < g->ntaps; ++j) a.tap_off[j] = g->h_tap_off ? g->h_tap_off[j] : 0;
+    a.in_stride = g->in_stride > 0 ? g->in_stride : 1; a.B = g->B; a.T_in = g->T_in; a.T_out = g->T_out;
+    a.a_mask = g->d_a_mask; a.a_mean = g->d_a_mean; a.a_rstd = g->d_a_rstd; a.a_part = g->d_a_part; a.a_nparts = g->a_nparts;
+    a.w = d_panel; a.w16 = terms ? d_planes : nullptr; a.terms = terms;
+    a.bias = g->d_bias; a.N = N; a.act = g->act; a.p0 = g->d_p0; a.p1 = g->d_p1;
+    a.res = g->d_res; a.ldr = g->ldr; a.out_mask = g->d_out_mask; a.out_scale = g->out_scale; a.out = g->d_out; a.ldc = ldc ? ldc : N;
+    if (g->d_out16_f32) { a.out16 = o16; a.ld16 = 2 * N; a.out16_mask = g->d_out16_mask; a.out_lscale = out_lscale; }
+    a.out_T = out_T; a.out_stride = out_stride; a.out_off = out_off;
+    a.stats_out = g->d_stats_out; a.force_bm = g->force_bm; a.range_flag = g->d_range_flag;
+    g_kernel_tag = nullptr;
+    HIP_OK(launch_gemm(a, s));
+    if (g_kernel_tag) { std::strncpy(g->tag, g_kernel_tag, sizeof(g->tag) - 1); g->tag[sizeof(g->tag) - 1] = 0; }
+    if (g->d_out16_f32) HIP_OK(launch_from_p16(o16, 2 * N, (int)out_rows, N, out_lscale, g->d_out16_f32, N, s));
+    return 0;
+}
+#undef GF
+
+int mtts_attention_f32_run(const float* d_qkv, const float* d_mask, const int* d_klen, int B, int T, int H, int D, float scale, int mask_mode,
+                           float* d_out, void* stream) {
+    REFUSE_IF(!d_qkv || !d_out, "mtts_attention_f32_run: null buffer");
+    REFUSE_IF(B <= 0 || T <= 0 || H <= 0, "mtts_attention_f32_run: empty batch");
+    REFUSE_IF(D <= 0 || D > 64 || (D & 3), "mtts_attention_f32_run: the head dim is a multiple of 4, at most 64");
+    REFUSE_IF(mask_mode != 0 && mask_mode != 1, "mtts_attention_f32_run: mask_mode is 0 or 1");
+    REFUSE_IF(mask_mode == 1 && !d_mask, "mtts_attention_f32_run: the boolean mask mode needs a mask");
+    AttnArgs a;
+    a.qkv = d_qkv; a.mask = d_mask; a.klen = d_klen; a.out = d_out; a.B = B; a.T = T; a.H = H; a.D = D; a.scale = scale; a.mask_mode = mask_mode;
+    g_kernel_tag = nullptr;
+    HIP_OK(launch_attention(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
+int mtts_groupnorm_mish_f32_run(const float* d_y, const float* d_gamma, const float* d_beta, const float* d_mask, const float* d_chbias,
+                                int chbias_stride, const float* d_res, int ldr, int B, int T, int C, int G, float eps, const int* d_nrows,
+                                const int* d_nextra, const float* d_bias_stats, float* d_out, float* d_stats_out, void* d_scratch,
+                                void* stream) {
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    REFUSE_IF(!d_y || !d_gamma || !d_beta || !d_mask || !d_out || !d_scratch, "mtts_groupnorm_mish_f32_run: null buffer");
+    REFUSE_IF(B <= 0 || T <= 0 || C <= 0 || G <= 0 || G > 64 || (C % G) || ((C / G) & 3) || C > 4096,
+              "mtts_groupnorm_mish_f32_run: C % G == 0 with (C / G) % 4 == 0, C <= 4096, G <= 64 and a non-empty batch");
+    REFUSE_IF(d_chbias && chbias_stride && (chbias_stride < C || (chbias_stride & 3)),
+              "mtts_groupnorm_mish_f32_run: a bias row per utterance has at least C values (stride % 4 == 0)");
+    REFUSE_IF((d_nextra != nullptr) != (d_bias_stats != nullptr), "mtts_groupnorm_mish_f32_run: nextra and bias_stats come together");
+    REFUSE_IF(d_res && (ldr < C || (ldr & 3)), "mtts_groupnorm_mish_f32_run: ldr is at least C and a multiple of 4");
+    REFUSE_IF(d_stats_out && (C & 63), "mtts_groupnorm_mish_f32_run: stats_out needs C % 64 == 0");
+    HIP_OK(launch_gn_partial(d_y, B, T, C, G, static_cast<float*>(d_scratch), s, d_nrows));
+    GnApplyArgs a;
+    a.y = d_y; a.partial = static_cast<const float*>(d_scratch); a.gamma = d_gamma; a.beta = d_beta; a.mask = d_mask;
+    a.chbias = d_chbias; a.chbias_stride = d_chbias ? chbias_stride : 0; a.res = d_res; a.ldr = ldr;
+    a.nrows = d_nrows; a.nextra = d_nextra; a.bias_stats = d_bias_stats; a.stats_out = d_stats_out;
+    a.out = d_out; a.B = B; a.T = T; a.C = C; a.G = G; a.eps = eps > 0.f ? eps : 1e-5f;
+    HIP_OK(launch_gn_apply(a, s));
+    return 0;
+}
+
+// mtts_channel_layernorm with the leading dimensions the model passes (rows of a wider buffer in, rows of a wider buffer out)
+int mtts_channel_layernorm_ld(const float* d_x, int ldx, int B, int T, int C, const float* d_gamma, const float* d_beta, float eps, int act,
+                              const float* d_film, const float* d_mask, float* d_y, int ldy, void* stream) {
+    REFUSE_IF(!d_x || !d_gamma || !d_beta || !d_y, "mtts_channel_layernorm_ld: null buffer");
+    REFUSE_IF(B <= 0 || T <= 0, "mtts_channel_layernorm_ld: empty batch");
+    REFUSE_IF(C <= 0 || (C & 3) || C > 2048, "mtts_channel_layernorm_ld: C must be a multiple of 4, at most 2048");
+    REFUSE_IF(ldx < C || (ldx & 3) || ldy < C || (ldy & 3), "mtts_channel_layernorm_ld: a leading dimension is at least C and a multiple of 4");
+    REFUSE_IF(act != ACT_NONE && act != ACT_SILU, "mtts_channel_layernorm_ld: act must be 0 (none) or 2 (SiLU)");
+    LayerNormArgs a;
+    a.x = d_x; a.ldx = ldx; a.y = d_y; a.ldy = ldy; a.M = B * T; a.C = C; a.T = T; a.gamma = d_gamma; a.beta = d_beta; a.eps = eps;
+    a.act = act; a.film = d_film; a.mask = d_mask;
+    HIP_OK(launch_layernorm(a, static_cast<hipStream_t>(stream)));
+    return 0;
+}
 #undef REFUSE_IF
 
 }  // extern "C"
