@@ -179,6 +179,16 @@ def load() -> C.CDLL:
                            "(the HIP path has no CPU fallback)")
     lib = C.CDLL(str(LIB))
     vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
+    # argument lists that several entries share, named once
+    gemm = [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, i32, vp, f32, vp, i32]   # d_a .. ldc
+    conv_gn = [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp]                    # d_x .. d_chbias
+    conv_gn_tail = [vp, vp, vp, f32, vp, vp, vp]                                            # d_nrows .. stream
+    chain = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]        # d_att .. d_out_mask
+    chain_p16 = chain + [i32, i32, vp, vp, vp, vp]                                          # qb, ch, d_x_out, d_qkv_out, d_scratch, stream
+    chain_h16 = chain + [i32, i32, i32, i32, vp, vp, vp, vp]                                # bf16, qb, ch, pf_wgs, ...
+    timed = [i32, C.POINTER(C.c_float)]                                                     # repeat, h_ms
+    gn_image = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp]  # d_y .. d_out16_mask
+    gemm_block, chain_block, conv_gn_block = C.POINTER(MttsGemmH16Args), C.POINTER(MttsChainArgs), C.POINTER(MttsConvGnArgs)
     sig = {
         "mtts_abi_version": (i32, []),
         "mtts_last_error": (C.c_char_p, []),
@@ -210,12 +220,10 @@ def load() -> C.CDLL:
         "mtts_attention_p16": (i32, [vp, vp, i32, i32, i32, i32, f32, i32, vp, vp, vp]),
         "mtts_gemm_p16_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
         "mtts_conv_gn_scratch_bytes": (i64, [i32, i32, i32, i32]),
-        "mtts_conv_gn": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp]),
-        "mtts_conv_gn_rows": (i32, [vp, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, f32, vp, vp, vp]),
-        "mtts_gemm_p16": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp,
-                                i32, vp, f32, vp, i32, vp, f32, vp, i32, vp, vp]),
-        "mtts_gemm_f32": (i32, [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp,
-                                i32, vp, f32, vp, i32, vp, i32, vp]),
+        "mtts_conv_gn": (i32, conv_gn + conv_gn_tail),
+        "mtts_conv_gn_rows": (i32, conv_gn + [i32] + conv_gn_tail),
+        "mtts_gemm_p16": (i32, gemm + [vp, f32, vp, i32, vp, vp]),
+        "mtts_gemm_f32": (i32, gemm + [vp, i32, vp]),
         "mtts_attention_f32": (i32, [vp, vp, i32, i32, i32, i32, f32, i32, vp, vp]),
         "mtts_chain_stream_frags": (i64, [i32, i32, i32, i32]),
         "mtts_chain_plan": (i32, [i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -223,40 +231,35 @@ def load() -> C.CDLL:
         "mtts_chain_stream_pack_pair": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "mtts_chain_stream_pack": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "mtts_tblock_chain_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
-        "mtts_tblock_chain": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]),
-        "mtts_tblock_chain_timed": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp,
-                                          i32, C.POINTER(C.c_float)]),
-        "mtts_tblock_chain_pair_timed": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, vp, vp, vp, vp,
-                                          i32, C.POINTER(C.c_float)]),
-        "mtts_tblock_chain_args_scratch_bytes": (i64, [C.POINTER(MttsChainArgs)]),
-        "mtts_tblock_chain_args_run": (i32, [C.POINTER(MttsChainArgs), vp, vp]),
-        "mtts_conv_gn_args_scratch_bytes": (i64, [C.POINTER(MttsConvGnArgs)]),
-        "mtts_conv_gn_args_run": (i32, [C.POINTER(MttsConvGnArgs), vp, vp]),
+        "mtts_tblock_chain": (i32, chain_p16),
+        "mtts_tblock_chain_timed": (i32, chain_p16 + timed),
+        "mtts_tblock_chain_pair_timed": (i32, chain_p16 + timed),
+        "mtts_tblock_chain_args_scratch_bytes": (i64, [chain_block]),
+        "mtts_tblock_chain_args_run": (i32, [chain_block, vp, vp]),
+        "mtts_conv_gn_args_scratch_bytes": (i64, [conv_gn_block]),
+        "mtts_conv_gn_args_run": (i32, [conv_gn_block, vp, vp]),
         "mtts_chain_stream_frags_h16": (i64, [i32, i32, i32, i32]),
         "mtts_chain_stream_pack_h16": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(C.c_int)]),
         "mtts_tblock_chain_h16_scratch_bytes": (i64, [i32, i32, i32, i32, i32]),
-        "mtts_tblock_chain_h16": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
-        "mtts_tblock_chain_h16_timed": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, vp,
-                                              i32, C.POINTER(C.c_float)]),
+        "mtts_tblock_chain_h16": (i32, chain_h16),
+        "mtts_tblock_chain_h16_timed": (i32, chain_h16 + timed),
         "mtts_last_kernel_tag": (C.c_char_p, []),
         "mtts_panel_h16_host": (i32, [vp, i64, i32, vp]),
         "mtts_to_h16_roundtrip": (i32, [vp, i32, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
-        "mtts_gemm_h16_scratch_bytes": (i64, [C.POINTER(MttsGemmH16Args)]),
-        "mtts_gemm_h16": (i32, [C.POINTER(MttsGemmH16Args), vp, vp]),
+        "mtts_gemm_h16_scratch_bytes": (i64, [gemm_block]),
+        "mtts_gemm_h16": (i32, [gemm_block, vp, vp]),
         "mtts_gemm_h16_wave_rows": (i32, [i32, i32, i32, i32]),
         "mtts_attention_h16": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, vp, vp, vp, vp]),
         "mtts_groupnorm_h16_scratch_bytes": (i64, [i32, i32, i32, i32]),
-        "mtts_groupnorm_mish_h16": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp,
-                                          vp, vp]),
+        "mtts_groupnorm_mish_h16": (i32, gn_image + [i32, vp, vp, vp, vp, vp]),
         "mtts_to_p16_roundtrip": (i32, [vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp]),
-        "mtts_gemm_p16_args_scratch_bytes": (i64, [C.POINTER(MttsGemmH16Args)]),
-        "mtts_gemm_p16_args_run": (i32, [C.POINTER(MttsGemmH16Args), i32, f32, vp, vp]),
+        "mtts_gemm_p16_args_scratch_bytes": (i64, [gemm_block]),
+        "mtts_gemm_p16_args_run": (i32, [gemm_block, i32, f32, vp, vp]),
         "mtts_attention_p16_run": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, f32, vp, vp, vp, vp]),
         "mtts_groupnorm_p16_scratch_bytes": (i64, [i32, i32, i32, i32]),
-        "mtts_groupnorm_mish_p16": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, vp, vp, vp,
-                                          vp, vp]),
-        "mtts_gemm_f32_args_scratch_bytes": (i64, [C.POINTER(MttsGemmH16Args)]),
-        "mtts_gemm_f32_args_run": (i32, [C.POINTER(MttsGemmH16Args), i32, vp, i32, i32, f32, vp, vp]),
+        "mtts_groupnorm_mish_p16": (i32, gn_image + [vp, vp, vp, vp, vp]),
+        "mtts_gemm_f32_args_scratch_bytes": (i64, [gemm_block]),
+        "mtts_gemm_f32_args_run": (i32, [gemm_block, i32, vp, i32, i32, f32, vp, vp]),
         "mtts_attention_f32_run": (i32, [vp, vp, vp, i32, i32, i32, i32, f32, i32, vp, vp]),
         "mtts_groupnorm_mish_f32_run": (i32, [vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp]),
         "mtts_channel_layernorm_ld": (i32, [vp, i32, i32, i32, i32, vp, vp, f32, i32, vp, vp, vp, i32, vp]),
@@ -1175,17 +1178,54 @@ def gemm_p16(a, w, bias=None, *, B, T_in, T_out=None, tap_off=None, in_stride=1,
     return {"out": out, "out16": out16, "stats": stats}
 
 
+def _conv_gn_call(entry, x, w, bias, gamma, beta, mask, chbias, B, T, c1, nrows, nextra, bias_stats, eps, pads=None):
+    """What the conv_gn helpers share: shapes, the packed-weight buffer, output and scratch, and the call.  ``pads`` None: the positional
+    ``entry`` (returns out); else dict(pad_x, pad_out, sentinel): the argument block (returns the block helper's dict)."""
+    lib = load()
+    N, Cc = w.shape[0], w.shape[1]
+    dev = x.device
+    wc = w.contiguous()
+    packed = torch.empty(lib.mtts_gemm_packed_bytes(N, Cc, 3), dtype=torch.uint8, device=dev)
+    out = torch.empty(B * T, N, dtype=torch.float32, device=dev)
+    if pads is None:
+        scratch = torch.empty(lib.mtts_conv_gn_scratch_bytes(B, T, Cc, N), dtype=torch.uint8, device=dev)
+        stride = [chbias.shape[1]] if entry == "mtts_conv_gn_rows" else []
+        check(getattr(lib, entry)(ptr(x), B, T, Cc, c1, ptr(wc), packed.data_ptr(), ptr(bias), N, ptr(gamma), ptr(beta), ptr(mask), ptr(chbias),
+                                  *stride, ptr(nrows), ptr(nextra), ptr(bias_stats), float(eps), ptr(out), scratch.data_ptr(), stream_ptr()))
+        return out
+    g = MttsConvGnArgs()
+    g.d_x, g.B, g.T, g.C, g.c1, g.N, g.eps = ptr(x), B, T, Cc, c1, N, float(eps)
+    g.d_w, g.d_wpacked, g.d_bias, g.d_gamma, g.d_beta, g.d_mask = ptr(wc), packed.data_ptr(), ptr(bias), ptr(gamma), ptr(beta), ptr(mask)
+    g.d_chbias, g.chbias_stride = ptr(chbias), (chbias.shape[1] if chbias is not None and chbias.dim() == 2 else 0)
+    g.d_nrows, g.d_nextra, g.d_bias_stats = ptr(nrows), ptr(nextra), ptr(bias_stats)
+    g.pad_x, g.pad_out, g.sentinel = pads["pad_x"], pads["pad_out"], pads["sentinel"]
+    scratch = torch.empty(size(lib.mtts_conv_gn_args_scratch_bytes(C.byref(g))), dtype=torch.uint8, device=dev)
+    flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    img = torch.empty(B * T + ENTRY_GUARD_ROWS, 2 * N + pads["pad_out"], dtype=torch.int16, device=dev)
+    g.d_range_flag, g.d_out, g.d_out_image = ptr(flag), ptr(out), ptr(img)
+    check(lib.mtts_conv_gn_args_run(C.byref(g), scratch.data_ptr(), stream_ptr()))
+    torch.cuda.synchronize()
+    return {"out": out, "image": img, "flag": flag, "tag": g.tag.decode()}
+
+
 def conv_gn(x, w, bias, gamma, beta, mask, *, B, T, c1=0, chbias=None, nrows=None, nextra=None, bias_stats=None, eps=1e-5):
     """One-launch Block1D (csrc/resnet_conv.hip): x [B*T, C] fp32, w Conv1d [N, C, 3]; returns Mish(GroupNorm8(conv(x))) * mask
     (+ chbias, * mask) as fp32 [B*T, N], decoded from the P16 image the kernel writes."""
-    lib = load()
-    N, Cc = w.shape[0], w.shape[1]
-    packed = torch.empty(lib.mtts_gemm_packed_bytes(N, Cc, 3), dtype=torch.uint8, device=x.device)
-    scratch = torch.empty(lib.mtts_conv_gn_scratch_bytes(B, T, Cc, N), dtype=torch.uint8, device=x.device)
-    out = torch.empty(B * T, N, dtype=torch.float32, device=x.device)
-    check(lib.mtts_conv_gn(ptr(x), B, T, Cc, c1, ptr(w.contiguous()), packed.data_ptr(), ptr(bias), N, ptr(gamma), ptr(beta), ptr(mask),
-                           ptr(chbias), ptr(nrows), ptr(nextra), ptr(bias_stats), float(eps), ptr(out), scratch.data_ptr(), stream_ptr()))
-    return out
+    return _conv_gn_call("mtts_conv_gn", x, w, bias, gamma, beta, mask, chbias, B, T, c1, nrows, nextra, bias_stats, eps)
+
+
+def conv_gn_rows(x, w, bias, gamma, beta, mask, chbias, *, B, T, c1=0, nrows=None, nextra=None, bias_stats=None, eps=1e-5):
+    """``conv_gn`` with one time-embedding bias row per utterance: chbias [B, stride >= N] (mtts_conv_gn_rows)."""
+    return _conv_gn_call("mtts_conv_gn_rows", x, w, bias, gamma, beta, mask, chbias, B, T, c1, nrows, nextra, bias_stats, eps)
+
+
+def conv_gn_args(x, w, bias, gamma, beta, mask, *, B, T, c1=0, chbias=None, nrows=None, nextra=None, bias_stats=None, eps=1e-5,
+                 pad_x=0, pad_out=0, sentinel=0x7e00):
+    """The one-launch Block1D on its argument block (include/mtts.h mtts_conv_gn_args): ``conv_gn`` / ``conv_gn_rows`` (chbias [N] or
+    [B, stride >= N]) with the range flag, padded image rows and the raw output image.  Returns a dict: out (decoded fp32 [B*T, N]),
+    image [B*T + guard, 2 N + pad_out] (int16 bits), flag (device uint32 [1], zeroed before the launch) and tag."""
+    return _conv_gn_call(None, x, w, bias, gamma, beta, mask, chbias, B, T, c1, nrows, nextra, bias_stats, eps,
+                         pads=dict(pad_x=pad_x, pad_out=pad_out, sentinel=sentinel))
 
 
 def _host(t):
@@ -1196,29 +1236,53 @@ def _host(t):
     return a, a.ctypes.data
 
 
-def tblock_chain(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, b_qkv=None, out_mask=None, qb=64, ch=128, repeat=0, pair=False):
-    """Row-local chain of a transformer block (csrc/tblock_chain.hip, include/mtts.h mtts_tblock_chain).  att [M, inner] (or None:
-    FeedForward only), x [M, C] on the device; panels / vectors anywhere (copied to the host).  Returns (x_out, qkv or None)."""
-    lib = load()
+CHAIN_PANELS = ("h_w_out", "h_b_out", "h_w1", "h_b1", "h_p0", "h_p1", "h_w2", "h_b2", "h_w_qkv", "h_b_qkv")
+
+
+def _chain_operands(att, x, panels):
+    """What the chain helpers share: shapes, the host copies of the ten panels / vectors (``CHAIN_PANELS`` order) and the outputs."""
     M, Cc = x.shape
     inner = att.shape[1] if att is not None else 0
-    n_qkv = w_qkv.shape[0] if w_qkv is not None else 0
-    n = lib.mtts_tblock_chain_scratch_bytes(M, Cc, inner, n_qkv, ch)
-    if n < 0:
-        raise RuntimeError("mtts_tblock_chain: unsupported shape")
-    scratch = torch.empty(n, dtype=torch.uint8, device=x.device)
+    n_qkv = panels[8].shape[0] if panels[8] is not None else 0
+    keep = [_host(t) for t in panels]
     x_out = torch.empty(M, Cc, dtype=torch.float32, device=x.device)
     qkv = torch.empty(M, n_qkv, dtype=torch.float32, device=x.device) if n_qkv else None
-    keep = [_host(t) for t in (w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv, b_qkv)]
-    hp = [k[1] for k in keep]
+    return M, Cc, inner, n_qkv, keep, x_out, qkv
+
+
+def _chain_call(run, scratch_bytes, what, att, x, panels, out_mask, mid, ch, repeat):
+    """A positional ``*_timed`` chain entry: ``mid`` are its arguments between d_out_mask and d_x_out.  Returns (x_out, qkv or None[, ms
+    per launch when ``repeat``])."""
+    M, Cc, inner, n_qkv, keep, x_out, qkv = _chain_operands(att, x, panels)
+    n = scratch_bytes(M, Cc, inner, n_qkv, ch)
+    if n < 0:
+        raise RuntimeError(what + ": unsupported shape")
+    scratch = torch.empty(n, dtype=torch.uint8, device=x.device)
     ms = C.c_float(0.0)
-    check((lib.mtts_tblock_chain_pair_timed if pair else lib.mtts_tblock_chain_timed)(ptr(att), ptr(x), M, Cc, inner, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8], hp[9],
-                                      n_qkv, ptr(out_mask), qb, ch, ptr(x_out), ptr(qkv), scratch.data_ptr(), stream_ptr(), repeat,
-                                      C.byref(ms)))
+    check(run(ptr(att), ptr(x), M, Cc, inner, *[k[1] for k in keep], n_qkv, ptr(out_mask), *mid, ptr(x_out), ptr(qkv), scratch.data_ptr(),
+              stream_ptr(), repeat, C.byref(ms)))
     torch.cuda.synchronize()
     if repeat:
         return x_out, qkv, ms.value
     return x_out, qkv
+
+
+def tblock_chain(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, b_qkv=None, out_mask=None, qb=64, ch=128, repeat=0, pair=False):
+    """Row-local chain of a transformer block (csrc/tblock_chain.hip, include/mtts.h mtts_tblock_chain).  att [M, inner] (or None:
+    FeedForward only), x [M, C] on the device; panels / vectors anywhere (copied to the host).  Returns (x_out, qkv or None)."""
+    lib = load()
+    return _chain_call(lib.mtts_tblock_chain_pair_timed if pair else lib.mtts_tblock_chain_timed, lib.mtts_tblock_chain_scratch_bytes,
+                       "mtts_tblock_chain", att, x, (w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv, b_qkv), out_mask, (qb, ch), ch, repeat)
+
+
+def tblock_chain_h16(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, b_qkv=None, out_mask=None, bf16=False, qb=64, ch=128,
+                     pf_wgs=0, repeat=0):
+    """The same chain in the 16-bit storage modes' arithmetic (csrc/tblock_chain_h16.hip, include/mtts.h mtts_tblock_chain_h16): the
+    fp32 operands are rounded to fp16 (or bfloat16) images, the kernel's 16-bit outputs come back widened to fp32.  Returns
+    (x_out, qkv or None[, ms per launch when ``repeat``])."""
+    lib = load()
+    return _chain_call(lib.mtts_tblock_chain_h16_timed, lib.mtts_tblock_chain_h16_scratch_bytes, "mtts_tblock_chain_h16", att, x,
+                       (w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv, b_qkv), out_mask, (int(bool(bf16)), qb, ch, pf_wgs), ch, repeat)
 
 
 def tblock_chain_args(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, b_qkv=None, out_mask=None, qb=64, ch=128, pair=False,
@@ -1228,81 +1292,22 @@ def tblock_chain_args(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, 
     [M + guard, 2 n_qkv + pad_qkv] (int16 bits, sentinel wherever the kernel did not write), flag (device uint32 [2], zeroed before
     the launch: range word, pair-timeout word) and tag."""
     lib = load()
-    M, Cc = x.shape
-    inner = att.shape[1] if att is not None else 0
-    n_qkv = w_qkv.shape[0] if w_qkv is not None else 0
-    keep = [_host(t) for t in (w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv, b_qkv)]
+    M, Cc, inner, n_qkv, keep, x_out, qkv = _chain_operands(att, x, (w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv, b_qkv))
     g = MttsChainArgs()
     g.d_att, g.d_x, g.M, g.C, g.inner, g.n_qkv = ptr(att), ptr(x), M, Cc, inner, n_qkv
-    for name, k in zip(("h_w_out", "h_b_out", "h_w1", "h_b1", "h_p0", "h_p1", "h_w2", "h_b2", "h_w_qkv", "h_b_qkv"), keep):
+    for name, k in zip(CHAIN_PANELS, keep):
         setattr(g, name, k[1])
     g.d_out_mask, g.qb, g.ch, g.pair = ptr(out_mask), qb, ch, int(bool(pair))
     g.pad_att, g.pad_x, g.pad_out, g.pad_qkv, g.sentinel = pad_att, pad_x, pad_out, pad_qkv, sentinel
-    n = size(lib.mtts_tblock_chain_args_scratch_bytes(C.byref(g)))
     dev = x.device
-    scratch = torch.empty(n, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(size(lib.mtts_tblock_chain_args_scratch_bytes(C.byref(g))), dtype=torch.uint8, device=dev)
     flag = torch.zeros(2, dtype=torch.int32, device=dev)
-    x_out = torch.empty(M, Cc, dtype=torch.float32, device=dev)
-    qkv = torch.empty(M, n_qkv, dtype=torch.float32, device=dev) if n_qkv else None
     x_img = torch.empty(M + ENTRY_GUARD_ROWS, 2 * Cc + pad_out, dtype=torch.int16, device=dev)
     q_img = torch.empty(M + ENTRY_GUARD_ROWS, 2 * n_qkv + pad_qkv, dtype=torch.int16, device=dev) if n_qkv else None
     g.d_range_flag, g.d_x_out, g.d_qkv_out, g.d_x_out_image, g.d_qkv_image = ptr(flag), ptr(x_out), ptr(qkv), ptr(x_img), ptr(q_img)
     check(lib.mtts_tblock_chain_args_run(C.byref(g), scratch.data_ptr(), stream_ptr()))
     torch.cuda.synchronize()
     return {"x_out": x_out, "qkv": qkv, "x_out_image": x_img, "qkv_image": q_img, "flag": flag, "tag": g.tag.decode()}
-
-
-def conv_gn_args(x, w, bias, gamma, beta, mask, *, B, T, c1=0, chbias=None, nrows=None, nextra=None, bias_stats=None, eps=1e-5,
-                 pad_x=0, pad_out=0, sentinel=0x7e00):
-    """The one-launch Block1D on its argument block (include/mtts.h mtts_conv_gn_args): ``conv_gn`` / ``conv_gn_rows`` (chbias [N] or
-    [B, stride >= N]) with the range flag, padded image rows and the raw output image.  Returns a dict: out (decoded fp32 [B*T, N]),
-    image [B*T + guard, 2 N + pad_out] (int16 bits), flag (device uint32 [1], zeroed before the launch) and tag."""
-    lib = load()
-    N, Cc = w.shape[0], w.shape[1]
-    dev = x.device
-    g = MttsConvGnArgs()
-    g.d_x, g.B, g.T, g.C, g.c1, g.N, g.eps = ptr(x), B, T, Cc, c1, N, float(eps)
-    wc = w.contiguous()
-    packed = torch.empty(lib.mtts_gemm_packed_bytes(N, Cc, 3), dtype=torch.uint8, device=dev)
-    g.d_w, g.d_wpacked, g.d_bias, g.d_gamma, g.d_beta, g.d_mask = ptr(wc), packed.data_ptr(), ptr(bias), ptr(gamma), ptr(beta), ptr(mask)
-    g.d_chbias, g.chbias_stride = ptr(chbias), (chbias.shape[1] if chbias is not None and chbias.dim() == 2 else 0)
-    g.d_nrows, g.d_nextra, g.d_bias_stats = ptr(nrows), ptr(nextra), ptr(bias_stats)
-    g.pad_x, g.pad_out, g.sentinel = pad_x, pad_out, sentinel
-    scratch = torch.empty(size(lib.mtts_conv_gn_args_scratch_bytes(C.byref(g))), dtype=torch.uint8, device=dev)
-    flag = torch.zeros(1, dtype=torch.int32, device=dev)
-    out = torch.empty(B * T, N, dtype=torch.float32, device=dev)
-    img = torch.empty(B * T + ENTRY_GUARD_ROWS, 2 * N + pad_out, dtype=torch.int16, device=dev)
-    g.d_range_flag, g.d_out, g.d_out_image = ptr(flag), ptr(out), ptr(img)
-    check(lib.mtts_conv_gn_args_run(C.byref(g), scratch.data_ptr(), stream_ptr()))
-    torch.cuda.synchronize()
-    return {"out": out, "image": img, "flag": flag, "tag": g.tag.decode()}
-
-
-def tblock_chain_h16(att, x, w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv=None, b_qkv=None, out_mask=None, bf16=False, qb=64, ch=128,
-                     pf_wgs=0, repeat=0):
-    """The same chain in the 16-bit storage modes' arithmetic (csrc/tblock_chain_h16.hip, include/mtts.h mtts_tblock_chain_h16): the
-    fp32 operands are rounded to fp16 (or bfloat16) images, the kernel's 16-bit outputs come back widened to fp32.  Returns
-    (x_out, qkv or None[, ms per launch when ``repeat``])."""
-    lib = load()
-    M, Cc = x.shape
-    inner = att.shape[1] if att is not None else 0
-    n_qkv = w_qkv.shape[0] if w_qkv is not None else 0
-    n = lib.mtts_tblock_chain_h16_scratch_bytes(M, Cc, inner, n_qkv, ch)
-    if n < 0:
-        raise RuntimeError("mtts_tblock_chain_h16: unsupported shape")
-    scratch = torch.empty(n, dtype=torch.uint8, device=x.device)
-    x_out = torch.empty(M, Cc, dtype=torch.float32, device=x.device)
-    qkv = torch.empty(M, n_qkv, dtype=torch.float32, device=x.device) if n_qkv else None
-    keep = [_host(t) for t in (w_out, b_out, w1, b1, p0, p1, w2, b2, w_qkv, b_qkv)]
-    hp = [k[1] for k in keep]
-    ms = C.c_float(0.0)
-    check(lib.mtts_tblock_chain_h16_timed(ptr(att), ptr(x), M, Cc, inner, hp[0], hp[1], hp[2], hp[3], hp[4], hp[5], hp[6], hp[7], hp[8], hp[9],
-                                          n_qkv, ptr(out_mask), int(bool(bf16)), qb, ch, pf_wgs, ptr(x_out), ptr(qkv), scratch.data_ptr(),
-                                          stream_ptr(), repeat, C.byref(ms)))
-    torch.cuda.synchronize()
-    if repeat:
-        return x_out, qkv, ms.value
-    return x_out, qkv
 
 
 def last_kernel_tag() -> str:
@@ -1356,26 +1361,37 @@ def gemm_h16(a, w, bias=None, *, B, T_in, T_out=None, tap_off=None, in_stride=1,
                        half16=half16)
 
 
-def _gemm_block(run, scratch_fn, a, w, bias, *, B, T_in, T_out, tap_off, in_stride, c1, a_mask, a_mean, a_rstd, a_part, act, p0, p1, res, res16,
-                inplace, out_mask, out_scale, out16_mask, want_f32, want16, out, out16, out_T, out_stride, out_off, stats_out, gn_groups,
-                gn_nrows, gnr, force_bm, bf16, half16):
-    """What gemm_h16 and gemm_p16_args share: fill the argument block (include/mtts.h mtts_gemm_h16_args), allocate outputs and scratch,
-    call ``run(lib, block, scratch_ptr)``."""
-    lib = load()
-    dev = a.device
+def _gemm_fill(a, w, bias, *, B, T_in, T_out, tap_off, in_stride, c1, a_mask, a_mean, a_rstd, a_part, act, p0, p1, res, out_mask, out_scale,
+               out16_mask, out_T, out_stride, out_off, force_bm, rows=ptr):
+    """The operand, prologue and epilogue fields of an argument block (include/mtts.h mtts_gemm_h16_args) that every GEMM helper fills the
+    same way; ``rows``: how a / res become pointers (``rows_ptr``: row-strided views).  Returns the block, what must stay alive while it is
+    used, the output rows, N and the range-flag word."""
     N, Cc = w.shape[0], w.shape[1]
     ntaps = w.shape[2] if w.dim() == 3 else 1
     T_out = T_in if T_out is None else T_out
-    rows = B * (out_T if out_T else T_out)
     taps = (C.c_int32 * ntaps)(*(tap_off if tap_off is not None else [j - ntaps // 2 for j in range(ntaps)]))
     hw, hw_ptr = _host(w)
     g = MttsGemmH16Args()
-    g.d_a, g.lda, g.C, g.c1, g.d_a_mask = ptr(a), a.stride(0), Cc, c1, ptr(a_mask)
+    g.d_a, g.lda, g.C, g.c1, g.d_a_mask = rows(a), a.stride(0), Cc, c1, ptr(a_mask)
     g.B, g.T_in, g.T_out, g.ntaps, g.h_tap_off, g.in_stride = B, T_in, T_out, ntaps, C.cast(taps, C.c_void_p), in_stride
     g.d_a_mean, g.d_a_rstd, g.d_a_part, g.a_nparts = ptr(a_mean), ptr(a_rstd), ptr(a_part), a_part.shape[1] if a_part is not None else 0
     g.h_w, g.d_bias, g.N = hw_ptr, ptr(bias), N
     g.act, g.d_p0, g.d_p1 = act, ptr(p0), ptr(p1)
-    g.d_res, g.ldr = ptr(res), res.shape[1] if res is not None else 0
+    g.d_res, g.ldr = rows(res), res.stride(0) if res is not None else 0
+    g.d_out_mask, g.out_scale, g.d_out16_mask = ptr(out_mask), float(out_scale), ptr(out16_mask)
+    g.out_T, g.out_stride, g.out_off = out_T, out_stride, out_off
+    g.force_bm = force_bm
+    flag = _flag(a.device)
+    g.d_range_flag = ptr(flag)
+    return g, (taps, hw), B * (out_T if out_T else T_out), N, flag
+
+
+def _gemm_block(run, scratch_fn, a, w, bias, *, res16, inplace, want_f32, want16, out, out16, stats_out, gn_groups, gn_nrows, gnr, bf16, half16,
+                **operands):
+    """What gemm_h16 and gemm_p16_args share: fill the argument block, allocate outputs and scratch, call ``run(lib, block, scratch_ptr)``."""
+    lib = load()
+    dev = a.device
+    g, alive, rows, N, flag = _gemm_fill(a, w, bias, **operands)
     if out is None and want_f32:
         out = torch.empty(rows, N, dtype=torch.float32, device=dev)
     preload = out16 is not None
@@ -1386,39 +1402,102 @@ def _gemm_block(run, scratch_fn, a, w, bias, *, B, T_in, T_out, tap_off, in_stri
         g.res16_mode, g.d_res16_f32 = 1, ptr(res16)
     if out16 is None and want16:
         out16 = torch.empty(rows, N, dtype=torch.float32, device=dev)
-    g.d_out_mask, g.out_scale, g.d_out16_mask = ptr(out_mask), float(out_scale), ptr(out16_mask)
     g.d_out, g.d_out16_f32, g.out16_preload = ptr(out), ptr(out16), int(preload)
-    g.out_T, g.out_stride, g.out_off = out_T, out_stride, out_off
     stats = torch.empty(rows, N // 64, 2, dtype=torch.float32, device=dev) if stats_out else None
     g.d_stats_out = ptr(stats)
     gn_stats = None
     if gn_groups:
-        gn_stats = torch.zeros(2 * ((B * T_out + 31) // 32 + 1) * (N // 64) * 2, 4, dtype=torch.float32, device=dev)
+        gn_stats = torch.zeros(2 * ((operands["B"] * g.T_out + 31) // 32 + 1) * (N // 64) * 2, 4, dtype=torch.float32, device=dev)
         g.d_gn_stats, g.gn_groups, g.d_gn_nrows = ptr(gn_stats), gn_groups, ptr(gn_nrows)
     if gnr is not None:
         g.d_gnr_y, g.d_gnr_stats, g.gnr_tile_rows, g.gnr_groups = ptr(gnr["y"]), ptr(gnr["stats"]), gnr["tile_rows"], gnr["groups"]
         g.d_gnr_gamma, g.d_gnr_beta, g.d_gnr_mask, g.gnr_eps = ptr(gnr["gamma"]), ptr(gnr["beta"]), ptr(gnr["mask"]), float(gnr.get("eps", 1e-5))
         g.d_gnr_nextra, g.d_gnr_bias_stats = ptr(gnr.get("nextra")), ptr(gnr.get("bias_stats"))
-    g.force_bm, g.half16, g.bf16 = force_bm, int(bool(half16)), int(bool(bf16))
-    flag = _flag(dev)
-    g.d_range_flag = ptr(flag)
-    n = size(getattr(lib, scratch_fn)(C.byref(g)))
-    scratch = torch.empty(n, dtype=torch.uint8, device=dev)
+    g.half16, g.bf16 = int(bool(half16)), int(bool(bf16))
+    scratch = torch.empty(size(getattr(lib, scratch_fn)(C.byref(g))), dtype=torch.uint8, device=dev)
     check(run(lib, g, scratch.data_ptr()))
     return {"out": out, "out16": out16, "stats": stats, "gn_stats": gn_stats, "wave_rows": g.wave_rows, "tag": g.tag.decode(),
             "flag": int(flag.item())}
 
 
+def _attention_call(fn, qkv, mask, B, T, H, D, scale, mask_mode, *, klen=(), mode=(), ew=0, slack=0, flag=False, guard=False):
+    """What the attention helpers share: (qkv, mask[, klen], B, T, H, D, scale, mask_mode, *mode, out[, flag][, scratch], stream).  ``ew``:
+    halves per image element (0: fp32 I/O, no scratch); ``guard``: the output is a ``guarded`` buffer.  Returns (out or buf, flag word)."""
+    dev = qkv.device
+    out = guarded(B * T, H * D, dev) if guard else torch.empty(B * T, H * D, dtype=torch.float32, device=dev)
+    fl = _flag(dev) if flag else None
+    scratch = torch.empty(8 * ew * B * T * H * D + slack, dtype=torch.uint8, device=dev) if ew else None
+    check(fn(ptr(qkv), ptr(mask), *[ptr(k) for k in klen], B, T, H, D, float(scale), mask_mode, *mode, ptr(out), *([ptr(fl)] if flag else []),
+             *([scratch.data_ptr()] if ew else []), stream_ptr()))
+    return out, fl
+
+
+def attention_f32(qkv, mask, B, T, H, D, scale, mask_mode):
+    return _attention_call(load().mtts_attention_f32, qkv, mask, B, T, H, D, scale, mask_mode)[0]
+
+
+def attention_p16(qkv, mask, B, T, H, D, scale, mask_mode):
+    return _attention_call(load().mtts_attention_p16, qkv, mask, B, T, H, D, scale, mask_mode, ew=2)[0]
+
+
+def attention_f32_run(qkv, mask, B, T, H, D, scale, mask_mode=0, *, klen=None):
+    """fp32-I/O attention with klen (include/mtts.h mtts_attention_f32_run).  Returns a dict: out ([B*T, H*D] view of buf), buf, tag."""
+    buf, _ = _attention_call(load().mtts_attention_f32_run, qkv, mask, B, T, H, D, scale, mask_mode, klen=[klen], guard=True)
+    return {"out": buf[:B * T * H * D].view(B * T, H * D), "buf": buf, "tag": last_kernel_tag()}
+
+
 def attention_h16(qkv, mask, B, T, H, D, scale, mask_mode=0, *, klen=None, bf16=False):
     """H16 attention (csrc/attention_f32.hip HALF / BF; include/mtts.h mtts_attention_h16).  Returns a dict: out, tag, flag."""
+    out, flag = _attention_call(load().mtts_attention_h16, qkv, mask, B, T, H, D, scale, mask_mode, klen=[klen], mode=[int(bool(bf16))], ew=1,
+                                slack=256, flag=True)
+    return {"out": out, "tag": last_kernel_tag(), "flag": int(flag.item())}
+
+
+def attention_p16_run(qkv, mask, B, T, H, D, scale, mask_mode=0, *, klen=None, fast16=False, out_lscale=2048.0):
+    """P16 attention as the decoder launches it (include/mtts.h mtts_attention_p16_run).  Returns a dict: out, tag, flag."""
+    out, flag = _attention_call(load().mtts_attention_p16_run, qkv, mask, B, T, H, D, scale, mask_mode, klen=[klen],
+                                mode=[int(bool(fast16)), float(out_lscale)], ew=2, slack=256, flag=True)
+    return {"out": out, "tag": last_kernel_tag(), "flag": int(flag.item())}
+
+
+def _groupnorm_call(fn, scratch_bytes, y, gamma, beta, mask, B, T, G, eps, *, chbias=None, pointer=ptr, res=(), mid=(), outs=()):
+    """What the GroupNorm + Mish helpers share: (y, gamma, beta, mask[, chbias, stride][, res, ldr], B, T, C, G, eps, *mid, *outs, scratch,
+    stream).  ``chbias``: None (the entry takes none) or a one-element list [tensor or None], [B, stride >= C] or [C]."""
+    head = []
+    for t in chbias or []:
+        head += [pointer(t), (t.stride(0) if t is not None and t.dim() == 2 else 0)]
+    for t in res:
+        head += [pointer(t), (t.stride(0) if t is not None else 0)]
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=y.device)
+    check(fn(ptr(y), ptr(gamma), ptr(beta), ptr(mask), *head, B, T, y.shape[1], G, float(eps), *mid, *[ptr(o) for o in outs], scratch.data_ptr(),
+             stream_ptr()))
+
+
+def groupnorm_mish(y, gamma, beta, mask, B, T, G=8, eps=1e-5):
     lib = load()
-    out = torch.empty(B * T, H * D, dtype=torch.float32, device=qkv.device)
-    scratch = torch.empty(8 * B * T * H * D + 256, dtype=torch.uint8, device=qkv.device)
-    flag = _flag(qkv.device)
-    check(lib.mtts_attention_h16(ptr(qkv), ptr(mask), ptr(klen), B, T, H, D, float(scale), mask_mode, int(bool(bf16)), ptr(out), ptr(flag),
-                                 scratch.data_ptr(), stream_ptr()))
-    tag = last_kernel_tag()
-    return {"out": out, "tag": tag, "flag": int(flag.item())}
+    out = torch.empty_like(y)
+    _groupnorm_call(lib.mtts_groupnorm_mish, lib.mtts_groupnorm_scratch_bytes(B, T, G), y, gamma, beta, mask, B, T, G, eps, outs=[out])
+    return out
+
+
+def groupnorm_mish_rows(y, gamma, beta, mask, chbias, B, T, G=8, eps=1e-5):
+    """``groupnorm_mish`` + the time-embedding bias: chbias [B, stride >= C] (one row per utterance) or [C] (one for the batch)."""
+    lib = load()
+    out = torch.empty_like(y)
+    _groupnorm_call(lib.mtts_groupnorm_mish_rows, lib.mtts_groupnorm_scratch_bytes(B, T, G), y, gamma, beta, mask, B, T, G, eps, chbias=[chbias],
+                    outs=[out])
+    return out
+
+
+def _groupnorm_image(fn, scratch_fn, mode, y, gamma, beta, mask, B, T, G, chbias, tile_stats, tile_rows, nrows, nextra, bias_stats, out16_mask,
+                     want_f32, eps):
+    """groupnorm_mish_h16 / groupnorm_mish_p16: an image out, widened or decoded into out16.  ``mode``: [bf16] or []."""
+    out = torch.empty_like(y) if want_f32 else None
+    out16 = torch.empty_like(y)
+    flag = _flag(y.device)
+    _groupnorm_call(fn, size(scratch_fn(B, T, y.shape[1], G)), y, gamma, beta, mask, B, T, G, eps, chbias=[chbias],
+                    mid=[ptr(tile_stats), tile_rows, ptr(nrows), ptr(nextra), ptr(bias_stats), ptr(out16_mask), *mode], outs=[out, out16, flag])
+    return {"out": out, "out16": out16, "flag": int(flag.item())}
 
 
 def groupnorm_mish_h16(y, gamma, beta, mask, B, T, *, G=8, chbias=None, tile_stats=None, tile_rows=0, nrows=None, nextra=None,
@@ -1426,17 +1505,17 @@ def groupnorm_mish_h16(y, gamma, beta, mask, B, T, *, G=8, chbias=None, tile_sta
     """GroupNorm + Mish + mask [+ chbias, mask] with an H16 image out (gn_apply_kernel's H16 store; mtts_groupnorm_mish_h16).
     chbias [B, stride >= C] or [C].  Returns a dict: out (fp32 rows), out16 (the image widened), flag."""
     lib = load()
-    Cc = y.shape[1]
-    n = size(lib.mtts_groupnorm_h16_scratch_bytes(B, T, Cc, G))
-    scratch = torch.empty(n, dtype=torch.uint8, device=y.device)
-    out = torch.empty_like(y) if want_f32 else None
-    out16 = torch.empty_like(y)
-    flag = _flag(y.device)
-    check(lib.mtts_groupnorm_mish_h16(ptr(y), ptr(gamma), ptr(beta), ptr(mask), ptr(chbias),
-                                      chbias.shape[1] if chbias is not None and chbias.dim() == 2 else 0, B, T, Cc, G, float(eps),
-                                      ptr(tile_stats), tile_rows, ptr(nrows), ptr(nextra), ptr(bias_stats), ptr(out16_mask), int(bool(bf16)),
-                                      ptr(out), ptr(out16), ptr(flag), scratch.data_ptr(), stream_ptr()))
-    return {"out": out, "out16": out16, "flag": int(flag.item())}
+    return _groupnorm_image(lib.mtts_groupnorm_mish_h16, lib.mtts_groupnorm_h16_scratch_bytes, [int(bool(bf16))], y, gamma, beta, mask, B, T, G,
+                            chbias, tile_stats, tile_rows, nrows, nextra, bias_stats, out16_mask, want_f32, eps)
+
+
+def groupnorm_mish_p16(y, gamma, beta, mask, B, T, *, G=8, chbias=None, tile_stats=None, tile_rows=0, nrows=None, nextra=None,
+                       bias_stats=None, out16_mask=None, want_f32=True, eps=1e-5):
+    """GroupNorm + Mish + mask [+ chbias, mask] with a P16 image out (gn_apply_kernel's two-plane store; mtts_groupnorm_mish_p16).
+    chbias [B, stride >= C] or [C].  Returns a dict: out (fp32 rows), out16 (the image decoded), flag."""
+    lib = load()
+    return _groupnorm_image(lib.mtts_groupnorm_mish_p16, lib.mtts_groupnorm_p16_scratch_bytes, [], y, gamma, beta, mask, B, T, G,
+                            chbias, tile_stats, tile_rows, nrows, nextra, bias_stats, out16_mask, want_f32, eps)
 
 
 def to_p16_roundtrip(x, mask=None, *, C_valid=None, ld16=None, lscale=2048.0, Cc=None):
@@ -1472,36 +1551,6 @@ def gemm_p16_args(a, w, bias=None, *, B, T_in, T_out=None, tap_off=None, in_stri
                        half16=half16)
 
 
-def attention_p16_run(qkv, mask, B, T, H, D, scale, mask_mode=0, *, klen=None, fast16=False, out_lscale=2048.0):
-    """P16 attention as the decoder launches it (include/mtts.h mtts_attention_p16_run).  Returns a dict: out, tag, flag."""
-    lib = load()
-    out = torch.empty(B * T, H * D, dtype=torch.float32, device=qkv.device)
-    scratch = torch.empty(16 * B * T * H * D + 256, dtype=torch.uint8, device=qkv.device)
-    flag = _flag(qkv.device)
-    check(lib.mtts_attention_p16_run(ptr(qkv), ptr(mask), ptr(klen), B, T, H, D, float(scale), mask_mode, int(bool(fast16)), float(out_lscale),
-                                     ptr(out), ptr(flag), scratch.data_ptr(), stream_ptr()))
-    tag = last_kernel_tag()
-    return {"out": out, "tag": tag, "flag": int(flag.item())}
-
-
-def groupnorm_mish_p16(y, gamma, beta, mask, B, T, *, G=8, chbias=None, tile_stats=None, tile_rows=0, nrows=None, nextra=None,
-                       bias_stats=None, out16_mask=None, want_f32=True, eps=1e-5):
-    """GroupNorm + Mish + mask [+ chbias, mask] with a P16 image out (gn_apply_kernel's two-plane store; mtts_groupnorm_mish_p16).
-    chbias [B, stride >= C] or [C].  Returns a dict: out (fp32 rows), out16 (the image decoded), flag."""
-    lib = load()
-    Cc = y.shape[1]
-    n = size(lib.mtts_groupnorm_p16_scratch_bytes(B, T, Cc, G))
-    scratch = torch.empty(n, dtype=torch.uint8, device=y.device)
-    out = torch.empty_like(y) if want_f32 else None
-    out16 = torch.empty_like(y)
-    flag = _flag(y.device)
-    check(lib.mtts_groupnorm_mish_p16(ptr(y), ptr(gamma), ptr(beta), ptr(mask), ptr(chbias),
-                                      chbias.shape[1] if chbias is not None and chbias.dim() == 2 else 0, B, T, Cc, G, float(eps),
-                                      ptr(tile_stats), tile_rows, ptr(nrows), ptr(nextra), ptr(bias_stats), ptr(out16_mask),
-                                      ptr(out), ptr(out16), ptr(flag), scratch.data_ptr(), stream_ptr()))
-    return {"out": out, "out16": out16, "flag": int(flag.item())}
-
-
 # ---- the fp32-row flow's unit entries.  Every output buffer is filled with F32_SENTINEL and has F32_GUARD floats behind its last row,
 # so a caller can see every element a launch did not write.
 F32_GUARD = 64
@@ -1532,32 +1581,18 @@ def gemm_f32_args(a, w, bias=None, *, terms, B, T_in, T_out=None, tap_off=None, 
     (raw, int16 [rows + guard rows, 2 N]), stats, stats_buf, tag, flag."""
     lib = load()
     dev = a.device
-    N, Cc = w.shape[0], w.shape[1]
-    ntaps = w.shape[2] if w.dim() == 3 else 1
-    T_out = T_in if T_out is None else T_out
-    rows = B * (out_T if out_T else T_out)
+    g, alive, rows, N, flag = _gemm_fill(a, w, bias, B=B, T_in=T_in, T_out=T_out, tap_off=tap_off, in_stride=in_stride, c1=c1, a_mask=a_mask,
+                                         a_mean=a_mean, a_rstd=a_rstd, a_part=a_part, act=act, p0=p0, p1=p1, res=res, out_mask=out_mask,
+                                         out_scale=out_scale, out16_mask=out16_mask, out_T=out_T, out_stride=out_stride, out_off=out_off,
+                                         force_bm=force_bm, rows=rows_ptr)
     ld = ldc if ldc else N
-    taps = (C.c_int32 * ntaps)(*(tap_off if tap_off is not None else [j - ntaps // 2 for j in range(ntaps)]))
-    hw, hw_ptr = _host(w)
-    g = MttsGemmH16Args()
-    g.d_a, g.lda, g.C, g.c1, g.d_a_mask = rows_ptr(a), a.stride(0), Cc, c1, ptr(a_mask)
-    g.B, g.T_in, g.T_out, g.ntaps, g.h_tap_off, g.in_stride = B, T_in, T_out, ntaps, C.cast(taps, C.c_void_p), in_stride
-    g.d_a_mean, g.d_a_rstd, g.d_a_part, g.a_nparts = ptr(a_mean), ptr(a_rstd), ptr(a_part), a_part.shape[1] if a_part is not None else 0
-    g.h_w, g.d_bias, g.N = hw_ptr, ptr(bias), N
-    g.act, g.d_p0, g.d_p1 = act, ptr(p0), ptr(p1)
-    g.d_res, g.ldr = rows_ptr(res), res.stride(0) if res is not None else 0
     buf = into["buf"] if into is not None else (guarded(rows, ld, dev) if want_f32 else None)
     out16 = torch.full((rows, N), F32_SENTINEL, dtype=torch.float32, device=dev) if want_p16 else None
-    g.d_out_mask, g.out_scale, g.d_out16_mask = ptr(out_mask), float(out_scale), ptr(out16_mask)
     g.d_out, g.d_out16_f32 = ptr(buf), ptr(out16)
-    g.out_T, g.out_stride, g.out_off = out_T, out_stride, out_off
     stats_buf = None
     if stats_out:
         stats_buf = into["stats_buf"] if into is not None else guarded(rows, 2 * (N // 64), dev)
     g.d_stats_out = ptr(stats_buf)
-    g.force_bm = force_bm
-    flag = _flag(dev)
-    g.d_range_flag = ptr(flag)
     n = size(lib.mtts_gemm_f32_args_scratch_bytes(C.byref(g)))
     scratch = torch.empty(n + 256, dtype=torch.uint8, device=dev)
     check(lib.mtts_gemm_f32_args_run(C.byref(g), int(terms), rows_ptr(a1), a1.stride(0) if a1 is not None else 0, int(ldc), float(out_lscale),
@@ -1571,55 +1606,42 @@ def gemm_f32_args(a, w, bias=None, *, terms, B, T_in, T_out=None, tap_off=None, 
             "tag": g.tag.decode(), "flag": int(flag.item())}
 
 
-def attention_f32_run(qkv, mask, B, T, H, D, scale, mask_mode=0, *, klen=None):
-    """fp32-I/O attention with klen (include/mtts.h mtts_attention_f32_run).  Returns a dict: out ([B*T, H*D] view of buf), buf, tag."""
-    lib = load()
-    buf = guarded(B * T, H * D, qkv.device)
-    check(lib.mtts_attention_f32_run(ptr(qkv), ptr(mask), ptr(klen), B, T, H, D, float(scale), mask_mode, ptr(buf), stream_ptr()))
-    return {"out": buf[:B * T * H * D].view(B * T, H * D), "buf": buf, "tag": last_kernel_tag()}
-
-
 def groupnorm_mish_f32_run(y, gamma, beta, mask, B, T, *, G=8, chbias=None, res=None, nrows=None, nextra=None, bias_stats=None,
                            stats_out=False, eps=1e-5):
     """gn_partial + gn_apply with the fp32 store (include/mtts.h mtts_groupnorm_mish_f32_run).  chbias [B, stride >= C] or [C]; res a
     [B*T, >= C] view.  Returns a dict: out ([B*T, C] view of buf), buf, stats, stats_buf."""
     lib = load()
     Cc = y.shape[1]
-    scratch = torch.empty(size(lib.mtts_groupnorm_scratch_bytes(B, T, G)) + 256, dtype=torch.uint8, device=y.device)
     buf = guarded(B * T, Cc, y.device)
     stats_buf = guarded(B * T, 2 * (Cc // 64), y.device) if stats_out else None
-    check(lib.mtts_groupnorm_mish_f32_run(ptr(y), ptr(gamma), ptr(beta), ptr(mask), rows_ptr(chbias),
-                                          chbias.stride(0) if chbias is not None and chbias.dim() == 2 else 0, rows_ptr(res),
-                                          res.stride(0) if res is not None else 0, B, T, Cc, G, float(eps), ptr(nrows), ptr(nextra),
-                                          ptr(bias_stats), ptr(buf), ptr(stats_buf), scratch.data_ptr(), stream_ptr()))
+    _groupnorm_call(lib.mtts_groupnorm_mish_f32_run, size(lib.mtts_groupnorm_scratch_bytes(B, T, G)) + 256, y, gamma, beta, mask, B, T, G, eps,
+                    chbias=[chbias], pointer=rows_ptr, res=[res], mid=[ptr(nrows), ptr(nextra), ptr(bias_stats)], outs=[buf, stats_buf])
     return {"out": buf[:B * T * Cc].view(B * T, Cc), "buf": buf,
             "stats": stats_buf[:B * T * 2 * (Cc // 64)].view(B * T, Cc // 64, 2) if stats_out else None, "stats_buf": stats_buf}
+
+
+def _layernorm_call(x, ldx, B, T, Cc, gamma, beta, eps, act, film, mask, y, ldy):
+    """``mtts_channel_layernorm_ld`` is ``mtts_channel_layernorm`` with leading dimensions; the plain entry keeps its own export."""
+    lib = load()
+    if ldx is None:
+        check(lib.mtts_channel_layernorm(ptr(x), B, T, Cc, ptr(gamma), ptr(beta), float(eps), act, ptr(film), ptr(mask), ptr(y), stream_ptr()))
+    else:
+        check(lib.mtts_channel_layernorm_ld(rows_ptr(x), ldx, B, T, Cc, ptr(gamma), ptr(beta), float(eps), act, ptr(film), ptr(mask), ptr(y), ldy,
+                                            stream_ptr()))
+    return y
 
 
 def channel_layernorm_ld(x, B, T, Cc, gamma, beta, *, eps=1e-5, act=0, film=None, mask=None, ldy=None):
     """Channel LayerNorm on rows of wider buffers (include/mtts.h mtts_channel_layernorm_ld).  x a [B*T, >= C] view.  Returns a dict:
     out ([B*T, C] view of buf), buf, ld."""
-    lib = load()
     ldy = Cc if ldy is None else ldy
-    buf = guarded(B * T, ldy, x.device)
-    check(lib.mtts_channel_layernorm_ld(rows_ptr(x), x.stride(0), B, T, Cc, ptr(gamma), ptr(beta), float(eps), act, ptr(film), ptr(mask), ptr(buf),
-                                        ldy, stream_ptr()))
+    buf = _layernorm_call(x, x.stride(0), B, T, Cc, gamma, beta, eps, act, film, mask, guarded(B * T, ldy, x.device), ldy)
     return {"out": buf[:B * T * ldy].view(B * T, ldy)[:, :Cc], "buf": buf, "ld": ldy}
 
 
-def attention_f32(qkv, mask, B, T, H, D, scale, mask_mode):
-    lib = load()
-    out = torch.empty(B * T, H * D, dtype=torch.float32, device=qkv.device)
-    check(lib.mtts_attention_f32(ptr(qkv), ptr(mask), B, T, H, D, float(scale), mask_mode, ptr(out), stream_ptr()))
-    return out
-
-
-def attention_p16(qkv, mask, B, T, H, D, scale, mask_mode):
-    lib = load()
-    out = torch.empty(B * T, H * D, dtype=torch.float32, device=qkv.device)
-    scratch = torch.empty(16 * B * T * H * D, dtype=torch.uint8, device=qkv.device)
-    check(lib.mtts_attention_p16(ptr(qkv), ptr(mask), B, T, H, D, float(scale), mask_mode, ptr(out), scratch.data_ptr(), stream_ptr()))
-    return out
+def channel_layernorm(x, gamma, beta, B, T, *, act=0, film=None, mask=None, eps=1e-5):
+    """x [B*T, C] rows; film [B, 2C] = gamma | beta of the DurationPredictor's speaker FiLM; mask [B*T]."""
+    return _layernorm_call(x, None, B, T, x.shape[1], gamma, beta, eps, act, film, mask, torch.empty_like(x), None)
 
 
 def row_stats(x, eps=1e-5):
@@ -1629,15 +1651,6 @@ def row_stats(x, eps=1e-5):
     rstd = torch.empty(M, dtype=torch.float32, device=x.device)
     check(lib.mtts_row_stats(ptr(x), M, Cc, Cc, eps, ptr(mean), ptr(rstd), stream_ptr()))
     return mean, rstd
-
-
-def channel_layernorm(x, gamma, beta, B, T, *, act=0, film=None, mask=None, eps=1e-5):
-    """x [B*T, C] rows; film [B, 2C] = gamma | beta of the DurationPredictor's speaker FiLM; mask [B*T]."""
-    lib = load()
-    y = torch.empty_like(x)
-    check(lib.mtts_channel_layernorm(ptr(x), B, T, x.shape[1], ptr(gamma), ptr(beta), float(eps), act, ptr(film), ptr(mask), ptr(y),
-                                     stream_ptr()))
-    return y
 
 
 def channel_layernorm_bwd(x, dy, gamma, beta, B, T, *, act=0, film=None, mask=None, gate=0, eps=1e-5):
@@ -1662,40 +1675,6 @@ def attention_rope_bwd(qkv, o, do, lengths, B, T, H, D, scale, cos, sin):
     check(lib.mtts_attention_rope_bwd(ptr(qkv), ptr(o), ptr(do), ptr(lengths), B, T, H, D, float(scale), ptr(cos), ptr(sin), ptr(dqkv),
                                       ptr(scratch), stream_ptr()))
     return dqkv
-
-
-def conv_gn_rows(x, w, bias, gamma, beta, mask, chbias, *, B, T, c1=0, nrows=None, nextra=None, bias_stats=None, eps=1e-5):
-    """``conv_gn`` with one time-embedding bias row per utterance: chbias [B, stride >= N] (mtts_conv_gn_rows)."""
-    lib = load()
-    N, Cc = w.shape[0], w.shape[1]
-    packed = torch.empty(lib.mtts_gemm_packed_bytes(N, Cc, 3), dtype=torch.uint8, device=x.device)
-    scratch = torch.empty(lib.mtts_conv_gn_scratch_bytes(B, T, Cc, N), dtype=torch.uint8, device=x.device)
-    out = torch.empty(B * T, N, dtype=torch.float32, device=x.device)
-    check(lib.mtts_conv_gn_rows(ptr(x), B, T, Cc, c1, ptr(w.contiguous()), packed.data_ptr(), ptr(bias), N, ptr(gamma), ptr(beta), ptr(mask),
-                                ptr(chbias), chbias.shape[1], ptr(nrows), ptr(nextra), ptr(bias_stats), float(eps), ptr(out),
-                                scratch.data_ptr(), stream_ptr()))
-    return out
-
-
-def groupnorm_mish_rows(y, gamma, beta, mask, chbias, B, T, G=8, eps=1e-5):
-    """``groupnorm_mish`` + the time-embedding bias: chbias [B, stride >= C] (one row per utterance) or [C] (one for the batch)."""
-    lib = load()
-    Cc = y.shape[1]
-    scratch = torch.empty(lib.mtts_groupnorm_scratch_bytes(B, T, G), dtype=torch.uint8, device=y.device)
-    out = torch.empty_like(y)
-    check(lib.mtts_groupnorm_mish_rows(ptr(y), ptr(gamma), ptr(beta), ptr(mask), ptr(chbias), chbias.shape[1] if chbias.dim() == 2 else 0,
-                                       B, T, Cc, G, eps, ptr(out), scratch.data_ptr(), stream_ptr()))
-    return out
-
-
-def groupnorm_mish(y, gamma, beta, mask, B, T, G=8, eps=1e-5):
-    lib = load()
-    Cc = y.shape[1]
-    scratch = torch.empty(lib.mtts_groupnorm_scratch_bytes(B, T, G), dtype=torch.uint8, device=y.device)
-    out = torch.empty_like(y)
-    check(lib.mtts_groupnorm_mish(ptr(y), ptr(gamma), ptr(beta), ptr(mask), B, T, Cc, G, eps, ptr(out), scratch.data_ptr(),
-                                  stream_ptr()))
-    return out
 
 
 # ---- the kernels that are not GEMMs (csrc/vocos.hip, csrc/norm_glue.hip): thin wrappers of their unit entries.  Buffers a kernel

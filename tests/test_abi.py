@@ -25,6 +25,88 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.mtts_abi_version() == 2
 
 
+def header_code():
+    """include/mtts.h without its comments"""
+    text = (ROOT / "include" / "mtts.h").read_text()
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+def c_class(decl):
+    """Class of a C parameter or return type as the header writes it: ptr / i32 / i64 / f32 / f64 / void."""
+    decl = " ".join(decl.split())
+    if "*" in decl:
+        return "ptr"
+    words = [w for w in decl.split(" ") if w != "const"]
+    for kinds, cls in ((("int64_t", "uint64_t"), "i64"), (("int", "int32_t", "uint32_t", "unsigned"), "i32"), (("float",), "f32"),
+                       (("double",), "f64"), (("void",), "void")):
+        if words[0] in kinds:
+            return cls
+    raise AssertionError(f"unknown C type in include/mtts.h: {decl!r}")
+
+
+def ctypes_class(t):
+    """The same classes for a ctypes type of the signature table (None: void)."""
+    if t is None:
+        return "void"
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer):
+        return "ptr"
+    if t is ctypes.c_float:
+        return "f32"
+    if t is ctypes.c_double:
+        return "f64"
+    assert issubclass(t, ctypes._SimpleCData) and t._type_ in "iIlLqQ", t
+    return {4: "i32", 8: "i64"}[ctypes.sizeof(t)]
+
+
+def test_every_prototype_is_exported_and_bound_with_its_types(lib):
+    """ONE check of the binding for every family: each mtts_* prototype of include/mtts.h is exported and bound with argtypes set, the
+    declared arity, the declared return class and the declared class of every argument (pointer / 32-bit integer / 64-bit integer /
+    float / double); and nothing is bound that the header does not declare."""
+    protos = re.findall(r"([A-Za-z_][\w \*]*?)\b(mtts_[a-z0-9_]+)\s*\(([^;(){}]*)\)\s*;", header_code())
+    names = [n for _, n, _ in protos]
+    assert len(names) >= 180 and len(set(names)) == len(names)
+    bound = sorted(n for n, f in vars(lib).items() if isinstance(f, ctypes._CFuncPtr) and f.argtypes is not None)
+    assert bound == sorted(names), sorted(set(bound) ^ set(names))
+    for ret, name, params in protos:
+        assert hasattr(lib, name), f"{name} declared in include/mtts.h but not exported"
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None, f"{name} is not bound with argtypes"
+        want = [c_class(p) for p in params.split(",") if p.strip() and p.strip() != "void"]
+        got = [ctypes_class(t) for t in fn.argtypes]
+        assert len(got) == len(want), (name, len(want), len(got))
+        assert got == want, (name, [(i, w, g) for i, (w, g) in enumerate(zip(want, got)) if w != g])
+        assert ctypes_class(fn.restype) == c_class(ret), (name, ret, fn.restype)
+
+
+@pytest.mark.parametrize("struct,mirror", [("mtts_config", "MttsConfig"), ("mtts_gemm_h16_args", "MttsGemmH16Args"),
+                                           ("mtts_chain_args", "MttsChainArgs"), ("mtts_conv_gn_args", "MttsConvGnArgs")])
+def test_argument_blocks_are_bound_field_for_field(struct, mirror):
+    """Every struct that crosses the boundary by value of its fields: same names in the same order, int32_t / uint32_t / float /
+    pointer / array of either, as include/mtts.h declares them."""
+    m = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), header_code(), flags=re.S)
+    assert m, struct
+    scalar = {"int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "float": ctypes.c_float, "char": ctypes.c_char}
+    want = []
+    for decl in m.group(1).split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        if "*" in decl:
+            want.append((decl.split("*")[-1].strip(), ctypes.c_void_p))
+            continue
+        kind, names = decl.split(" ", 1)
+        for n in names.split(","):
+            am = re.match(r"(\w+)\[(\d+)\]$", n.strip())
+            want.append((am.group(1), scalar[kind] * int(am.group(2))) if am else (n.strip(), scalar[kind]))
+    got = list(getattr(sub("_hip"), mirror)._fields_)
+    assert [n for n, _ in got] == [n for n, _ in want]
+    for (n, t), (_, w) in zip(got, want):
+        if issubclass(w, ctypes.Array):
+            assert issubclass(t, ctypes.Array) and t._type_ is w._type_ and t._length_ == w._length_, (n, t, w)
+        else:
+            assert t is w, (n, t, w)
+
+
 def test_no_debug_exports_and_one_reader_of_the_environment(lib):
     """The shipped library carries no diagnostic entry points (mtts_debug_hold, the stand-in for a thread inside an entry point in
     test_context_refuses_concurrent_use, is the one exception), and the C++ sources read the environment in ONE place

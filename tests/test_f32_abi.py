@@ -1,13 +1,12 @@
 """CPU checks of the unit entries of the fp32-row flow (csrc/unit_entries.hip: mtts_gemm_f32_args_run, mtts_attention_f32_run,
-mtts_groupnorm_mish_f32_run, mtts_channel_layernorm_ld; nothing runs on a GPU): the entries are declared in include/mtts.h, exported and
-bound with the declared arity and argument types; every refusal that can be decided on the host returns -1 with a message before
+mtts_groupnorm_mish_f32_run, mtts_channel_layernorm_ld; nothing runs on a GPU): the binding itself is checked for every entry in
+test_abi.py; here: every refusal that can be decided on the host returns -1 with a message before
 anything is launched (the buffers named here are never touched); the restatement the GPU file measures against
 (tests/f32_restated.py) agrees with independent torch code -- F.conv1d, F.conv_transpose1d for the two-phase interleave,
 F.group_norm + F.mish on explicitly padded rows for nextra, F.layer_norm, the oracle's sdpa_reference -- and the input classes the
 GPU file's cases claim are really present in what it launches."""
 import ctypes as C
 import math
-import re
 
 import pytest
 import torch
@@ -17,8 +16,6 @@ import f32_restated as R
 from conftest import ROOT, sub
 from p16_restated import p16, split
 
-NEW = ["mtts_gemm_f32_args_scratch_bytes", "mtts_gemm_f32_args_run", "mtts_attention_f32_run", "mtts_groupnorm_mish_f32_run",
-       "mtts_channel_layernorm_ld"]
 FAKE = 0x1000          # a non-null "pointer" for buffers a refused call must not touch
 
 
@@ -35,28 +32,9 @@ def lib(hip):
     return hip.load()
 
 
-def ctype_of(decl):
-    decl = " ".join(decl.split())
-    if "*" in decl:
-        return "pointer"
-    return {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float}[decl.rsplit(" ", 1)[0].replace("const ", "")]
-
-
 def test_new_entries_are_declared_exported_and_bound_with_matching_arity_and_types(hip, lib):
     header = (ROOT / "include" / "mtts.h").read_text()
-    for name in NEW:
-        m = re.search(r"^(int|int64_t)\s+" + name + r"\s*\(([^;()]*)\)\s*;", header, flags=re.S | re.M)
-        assert m, f"{name} is not declared in include/mtts.h"
-        args = [a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
-        fn = getattr(lib, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == len(args), (name, len(args), fn.argtypes)
-        assert fn.restype is {"int": C.c_int, "int64_t": C.c_int64}[m.group(1)]
-        for decl, bound in zip(args, fn.argtypes):
-            want = ctype_of(decl)
-            if want == "pointer":
-                assert bound is C.c_void_p or issubclass(bound, C._Pointer), (name, decl, bound)
-            else:
-                assert bound is want or (C.sizeof(bound) == C.sizeof(want) and (bound is C.c_float) == (want is C.c_float)), (name, decl, bound)
+    # (declaration, export, arity and types: test_abi.py checks them for every entry of the header)
     for wrapper in ("gemm_f32_args", "attention_f32_run", "groupnorm_mish_f32_run", "channel_layernorm_ld", "guarded", "rows_ptr"):
         assert callable(getattr(hip, wrapper))
     assert lib.mtts_last_kernel_tag() == b""           # no launcher ran on this thread

@@ -1,19 +1,16 @@
 """CPU checks of the unit entries of the 16-bit storage modes' kernels (csrc/unit_entries.hip: mtts_gemm_h16, mtts_attention_h16,
-mtts_groupnorm_mish_h16, mtts_to_h16_roundtrip and the host-only helpers; nothing runs on a GPU): the entries are declared in
-include/mtts.h, exported and bound with the declared arity; the argument block of mtts_gemm_h16 is bound field for field; every
+mtts_groupnorm_mish_h16, mtts_to_h16_roundtrip and the host-only helpers; nothing runs on a GPU): the binding itself (declared, exported,
+arity, types, the argument block field for field) is checked for every entry in test_abi.py; here: every
 refusal that can be decided on the host returns -1 with a message before anything is launched (the buffers named here are never
 touched); and the 16-bit weight plane equals torch's rounding bit for bit, ties, subnormals and the fp16 clamp included."""
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, sub
+from conftest import sub
 
-NEW = ["mtts_last_kernel_tag", "mtts_panel_h16_host", "mtts_to_h16_roundtrip", "mtts_gemm_h16_scratch_bytes", "mtts_gemm_h16",
-       "mtts_gemm_h16_wave_rows", "mtts_attention_h16", "mtts_groupnorm_h16_scratch_bytes", "mtts_groupnorm_mish_h16"]
 FAKE = 0x1000          # a non-null "pointer" for buffers a refused call must not touch
 
 
@@ -30,46 +27,12 @@ def lib(hip):
     return hip.load()
 
 
-def header():
-    return (ROOT / "include" / "mtts.h").read_text()
-
-
 def test_new_entries_are_declared_exported_and_bound_with_matching_arity(hip, lib):
-    for name in NEW:
-        m = re.search(r"^(?:int|int64_t|const char\*)\s+" + name + r"\s*\(([^;()]*)\)\s*;", header(), flags=re.S | re.M)
-        assert m, f"{name} is not declared in include/mtts.h"
-        args = [a for a in m.group(1).split(",") if a.strip() and a.strip() != "void"]
-        fn = getattr(lib, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == len(args), (name, len(args), fn.argtypes)
+    # (declaration, export, arity and types: test_abi.py checks them for every entry of the header)
     assert lib.mtts_abi_version() == 2
     for wrapper in ("gemm_h16", "attention_h16", "groupnorm_mish_h16", "to_h16_roundtrip", "panel_h16_host", "last_kernel_tag"):
         assert callable(getattr(hip, wrapper))
     assert lib.mtts_last_kernel_tag() == b""           # no launcher ran on this thread
-
-
-def test_gemm_argument_block_is_bound_field_for_field(hip):
-    m = re.search(r"typedef struct mtts_gemm_h16_args \{(.*?)\} mtts_gemm_h16_args;", header(), flags=re.S)
-    assert m
-    body = re.sub(r"/\*.*?\*/", "", m.group(1), flags=re.S)
-    want = []
-    for decl in body.split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        am = re.match(r"char (\w+)\[(\d+)\]$", decl)
-        if am:
-            want.append((am.group(1), C.c_char * int(am.group(2))))
-            continue
-        if "*" in decl:
-            want.append((decl.split("*")[-1].strip(), C.c_void_p))
-            continue
-        kind, names = decl.split(" ", 1)
-        for n in names.split(","):
-            want.append((n.strip(), {"int32_t": C.c_int32, "float": C.c_float}[kind]))
-    got = [(n, t) for n, t in hip.MttsGemmH16Args._fields_]
-    assert [n for n, _ in got] == [n for n, _ in want]
-    for (n, t), (_, w) in zip(got, want):
-        assert t is w or (C.sizeof(t) == C.sizeof(w) and w is not C.c_void_p and t is not C.c_void_p), (n, t, w)
 
 
 def gemm_block(hip, **kw):

@@ -1,7 +1,6 @@
 """Voice enrolment without a GPU: the new C entries, the host-built tables of the log-mel front end against fp64 restatements of
 their published definitions, the frame-count rule, and the style encoder's state-dict names through the converter."""
 import ctypes as C
-import re
 
 import numpy as np
 import pytest
@@ -9,10 +8,6 @@ import torch
 
 from conftest import ROOT, sub
 import enroll_restated as R
-
-NEW = ["mtts_melfe_create", "mtts_melfe_destroy", "mtts_melfe_n_bins", "mtts_melfe_basis", "mtts_melfe_filterbank",
-       "mtts_melfe_workspace_bytes", "mtts_melfe_forward", "mtts_style_create", "mtts_style_destroy", "mtts_style_set_tensor",
-       "mtts_style_weights_bytes", "mtts_style_upload_weights", "mtts_style_workspace_bytes", "mtts_style_forward"]
 
 
 @pytest.fixture(scope="module")
@@ -22,9 +17,7 @@ def lib():
 
 def test_symbols_declared_and_exported(lib):
     header = (ROOT / "include" / "mtts.h").read_text()
-    for name in NEW:
-        assert re.search(r"\b" + name + r"\s*\(", header), name
-        assert getattr(lib, name).argtypes is not None, name
+    # (declaration, export, arity and types: test_abi.py checks them for every entry of the header)
     # the documented signatures, as the binding declares them
     assert len(lib.mtts_melfe_forward.argtypes) == 14 and lib.mtts_melfe_forward.restype is C.c_int
     assert len(lib.mtts_style_forward.argtypes) == 12 and lib.mtts_style_forward.restype is C.c_int

@@ -1,21 +1,17 @@
 """CPU checks of the unit entries of the default arithmetic's two-plane (P16) kernels (csrc/unit_entries.hip: mtts_gemm_p16_args_run,
-mtts_attention_p16_run, mtts_groupnorm_mish_p16, mtts_to_p16_roundtrip; nothing runs on a GPU): the entries are declared in
-include/mtts.h, exported and bound with the declared arity and argument types; every refusal that can be decided on the host
+mtts_attention_p16_run, mtts_groupnorm_mish_p16, mtts_to_p16_roundtrip; nothing runs on a GPU): the binding itself is checked for every
+entry in test_abi.py; here: every refusal that can be decided on the host
 returns -1 with a message before anything is launched (the buffers named here are never touched); and the restatement of the
 split the GPU file measures against (tests/p16_restated.py) gives the hand-worked values: ties, 1 + 2^-11, subnormal residuals at
 lscale 1, +-65504, values beyond the range, signed zeros, and is value-idempotent."""
 import ctypes as C
-import re
 
 import pytest
 import torch
 
-from conftest import ROOT, sub
+from conftest import sub
 from p16_restated import heads, image_bits, p16, split
 
-NEW = ["mtts_to_p16_roundtrip", "mtts_gemm_p16_args_scratch_bytes", "mtts_gemm_p16_args_run", "mtts_attention_p16_run",
-       "mtts_groupnorm_p16_scratch_bytes", "mtts_groupnorm_mish_p16",
-       "mtts_tblock_chain_args_scratch_bytes", "mtts_tblock_chain_args_run", "mtts_conv_gn_args_scratch_bytes", "mtts_conv_gn_args_run"]
 FAKE = 0x1000          # a non-null "pointer" for buffers a refused call must not touch
 
 
@@ -32,31 +28,8 @@ def lib(hip):
     return hip.load()
 
 
-def header():
-    return (ROOT / "include" / "mtts.h").read_text()
-
-
-def ctype_of(decl):
-    decl = " ".join(decl.split())
-    if "*" in decl:
-        return "pointer"
-    return {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float}[decl.rsplit(" ", 1)[0].replace("const ", "")]
-
-
 def test_new_entries_are_declared_exported_and_bound_with_matching_arity_and_types(hip, lib):
-    for name in NEW:
-        m = re.search(r"^(int|int64_t)\s+" + name + r"\s*\(([^;()]*)\)\s*;", header(), flags=re.S | re.M)
-        assert m, f"{name} is not declared in include/mtts.h"
-        args = [a for a in m.group(2).split(",") if a.strip() and a.strip() != "void"]
-        fn = getattr(lib, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == len(args), (name, len(args), fn.argtypes)
-        assert fn.restype is {"int": C.c_int, "int64_t": C.c_int64}[m.group(1)]
-        for decl, bound in zip(args, fn.argtypes):
-            want = ctype_of(decl)
-            if want == "pointer":
-                assert bound is C.c_void_p or issubclass(bound, C._Pointer), (name, decl, bound)
-            else:
-                assert bound is want or (C.sizeof(bound) == C.sizeof(want) and (bound is C.c_float) == (want is C.c_float)), (name, decl, bound)
+    # (declaration, export, arity and types: test_abi.py checks them for every entry of the header)
     assert lib.mtts_abi_version() == 2
     for wrapper in ("gemm_p16_args", "attention_p16_run", "groupnorm_mish_p16", "to_p16_roundtrip", "tblock_chain_args", "conv_gn_args"):
         assert callable(getattr(hip, wrapper))

@@ -2,7 +2,6 @@
 fp64 autograd gradient (tests/spk_grad_restated.py) against central finite differences of the restated fp64 loss on the tiny model."""
 import ctypes as C
 import dataclasses
-import re
 
 import numpy as np
 import pytest
@@ -11,11 +10,6 @@ import torch
 from conftest import ROOT, sub
 import spk_grad_restated as G
 
-NEW = {"mtts_spk_grad_weights_bytes": 1, "mtts_spk_grad_upload_weights": 3, "mtts_spk_grad_workspace_bytes": 4,
-       "mtts_spk_grad_tape_offset": 5, "mtts_spk_grad": 22, "mtts_spk_grad_status": 2, "mtts_channel_layernorm_bwd": 16,
-       "mtts_attention_rope_bwd": 14}
-WIDE = {"mtts_spk_grad_weights_bytes", "mtts_spk_grad_workspace_bytes", "mtts_spk_grad_tape_offset"}
-
 
 @pytest.fixture(scope="module")
 def lib():
@@ -23,18 +17,9 @@ def lib():
 
 
 def test_symbols_declared_exported_and_bound(lib):
-    import subprocess
+    # (declaration, export, arity and types: test_abi.py checks them for every entry of the header)
     header = (ROOT / "include" / "mtts.h").read_text()
     hip = sub("_hip")
-    syms = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--dyn-syms", "--wide", str(hip.LIB)], check=True, capture_output=True,
-                          text=True).stdout
-    for name, arity in NEW.items():
-        assert re.search(r"\s" + name + r"\s*$", syms, flags=re.M), name                 # exported by the built library
-        fn = getattr(lib, name)
-        assert fn.argtypes is not None and len(fn.argtypes) == arity, name
-        decl = re.search(r"^int(?:64_t)?\s+" + name + r"\s*\(([^;]*?)\)\s*;", header, flags=re.S | re.M).group(1)
-        assert len([a for a in decl.split(",") if a.strip()]) == arity, name           # the header and the binding agree
-        assert fn.restype is (C.c_int64 if name in WIDE else C.c_int), name
     assert "MTTS_ABI_VERSION 2" in header and "MTTS_IMAGE_REVISION 6" in header        # additive: no layout or ABI bump
     assert "spk_grad.hip" in hip.SOURCES
     for method in ("speaker_grad", "spk_grad_status"):
