@@ -454,54 +454,32 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
     encs = [None] * B if encodings is None else list(encodings)
     dith = [False] * B if dithers is None else [bool(v) for v in dithers]
     keys = [0] * B if dither_keys is None else [int(v) for v in dither_keys]
-    coded = any(e is not None for e in encs)
     loud = [None] * B if loudness is None else list(loudness)
     levelled = any(v is not None for v in loud)
     ceil = [None] * B if true_peak is None else list(true_peak)
-    metered = dict(true_peak=ceil, return_meter=True) if any(v is not None for v in ceil) else {}
     report = [None] * B
     if wave_batch:
-        from .inference import to_waveforms
-        extra = dict(encoding=encs, dither=dith, dither_keys=keys) if coded else {}
+        from .waveform import tail
+        # encodings and ceilings that are all None are "stage not run" to the plan; a report alone would run the meter, so it is
+        # asked for only where a row is levelled
+        extra = {}
+        if levelled:
+            extra.update(loudness=loud, return_loudness=True, true_peak=ceil, return_meter=any(v is not None for v in ceil))
         if timing is not None:
             extra.update(token_ends=timing["token_ends"], x_lengths=timing["x_lengths"], breaks=timing["breaks"], return_marks=True)
-        if levelled:
-            out = to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, loudness=loud, return_loudness=True, **metered, **extra)
-            audio, report = out[0], out[1]
-        else:
-            out = to_waveforms(mel, mel_lengths, vocoder, sample_rate=rates, **extra)
-            audio = out[0] if timing is not None else out
-        for r, a in zip(res, audio):
+        out = tail(mel, mel_lengths, vocoder, sample_rate=rates, encoding=encs, dither=dith, dither_keys=keys, **extra)
+        report = report if out.report is None else out.report
+        for r, a in zip(res, out.rows):
             r["audio"] = a
         if timing is not None:
-            for r, u, tokens in zip(res, timing["units"], out[-1]):
+            for r, u, tokens in zip(res, timing["units"], out.marks):
                 marks_into(r, u, tokens)
     else:
-        from .inference import _convert_rows, _waveform_on_device, trim_trailing_silence
+        from .waveform import _waveform_on_device, finish_request, trim_trailing_silence
         for b, (r, rate, enc, on, key) in enumerate(zip(res, rates, encs, dith, keys)):
             a = trim_trailing_silence(_waveform_on_device(r["mel"][None], vocoder).squeeze())
-            if loud[b] is not None and a.numel() > 0:
-                from . import loudness as LD
-                rows = torch.zeros(1, (a.numel() + 3) // 4 * 4, dtype=torch.float32, device=a.device)
-                rows[0, :a.numel()] = a
-                if ceil[b] is None:
-                    lufs, gain, _ = LD.normalize(rows, [a.numel()], loud[b], check=False)
-                    report[b] = (float(lufs[0]), float(gain[0]))
-                else:
-                    m = LD.normalize(rows, [a.numel()], loud[b], check=False, true_peak=ceil[b], return_meter=True)[3]
-                    report[b] = {k: float(v[0]) for k, v in m.items()}
-                a = rows[0, :a.numel()]
-            if rate != 24000 and a.numel() > 0:
-                conv, n = _convert_rows(a.reshape(1, -1), torch.tensor([a.numel()], dtype=torch.long, device=a.device), [rate])
-                a = conv[0, :int(n[0])]
-            if enc is not None:
-                from . import audio_codec as AC
-                if a.numel() > 0:
-                    data, _ = AC.encode(a.reshape(1, -1), None, enc, dither=on, keys=[key])
-                    a = data[0, :a.numel() * AC.BYTES_PER_SAMPLE[AC.format_id(enc)]]
-                else:
-                    a = torch.zeros(0, dtype=torch.uint8)
-            r["audio"] = a.cpu()
+            r["audio"], report[b] = finish_request(a, loudness=loud[b], true_peak=ceil[b], report=True, sample_rate=rate, encoding=enc,
+                                                   dither=on, dither_key=key)
     for r, rate, enc, target, rep, c in zip(res, rates, encs, loud, report, ceil):
         if rate != 24000:
             r["sample_rate"] = rate
@@ -545,7 +523,7 @@ def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> 
     per-request loop for it, and no host-side join."""
     if vocoder is None:
         raise ValueError("a document needs a vocoder: its result is the joined audio")
-    from .inference import to_waveforms
+    from .waveform import tail
     rows = [r for u in units for r in unit_rows(u)]
     x, x_len, emb = request_inputs(model, rows)
     head = rows[0]
@@ -560,21 +538,18 @@ def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> 
     gaps = [g for u in units for g in (u.gaps() if isinstance(u, Document) else [0])]
     encs, dith, keys = encoding_fields(units)
     extra = {} if encs is None else dict(encoding=encs, dither=dith, dither_keys=keys)
-    targets = loudness_field(units)
-    if targets is not None:
-        extra.update(loudness=targets, return_loudness=True)
-        if true_peak_field(units) is not None:
-            extra.update(true_peak=true_peak_field(units), return_meter=True)
+    if loudness_field(units) is not None:
+        extra.update(loudness=loudness_field(units), return_loudness=True, true_peak=true_peak_field(units),
+                     return_meter=true_peak_field(units) is not None)
     timed = timing is not None and "token_ends" in out
     if timed:
         extra.update(token_ends=out["token_ends"], x_lengths=x_len, breaks=timing["breaks"], return_marks=True)
-    out_w = to_waveforms(out["mel"], out["mel_lengths"], vocoder, sample_rate=[int(u.sample_rate) for u in units],
-                         documents=counts, gaps=gaps, fade_ms=fade_ms,
-                         level=[u.level if isinstance(u, Document) else "sentence" for u in units], return_segments=True, **extra)
-    audio, segments = out_w[0], out_w[1]
-    report = out_w[2] if targets is not None else [None] * len(units)
+    out_w = tail(out["mel"], out["mel_lengths"], vocoder, sample_rate=[int(u.sample_rate) for u in units], documents=counts, gaps=gaps,
+                 fade_ms=fade_ms, level=[u.level if isinstance(u, Document) else "sentence" for u in units], return_segments=True,
+                 **extra)
+    report = [None] * len(units) if out_w.report is None else out_w.report
     res, b = [], 0
-    for u, n, a, seg, rep in zip(units, counts, audio, segments, report):
+    for u, n, a, seg, rep in zip(units, counts, out_w.rows, out_w.segments, report):
         if isinstance(u, Document):
             r = {"audio": a, "segments": seg, "mel_lengths": lens[b:b + n]}
         else:
@@ -585,7 +560,7 @@ def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> 
             r["encoding"] = u.encoding
         report_into(r, rep, u.loudness, u.true_peak)
         if timed:
-            marks_into(r, u, out_w[-1][len(res)] if isinstance(u, Document) else out_w[-1][len(res)][0])
+            marks_into(r, u, out_w.marks[len(res)] if isinstance(u, Document) else out_w.marks[len(res)][0])
         res.append(r)
         b += n
     return res

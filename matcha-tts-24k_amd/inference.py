@@ -22,6 +22,9 @@ import torch.nn as nn
 from . import _hip
 from .hparams import N_VOCAB, PathHParams, from_reference_kwargs
 from .modules import PAIR_TIMEOUT_ERROR, Runtime, build_trees
+# the waveform tail lives in waveform.py; its public names (and the 24 kHz constant, defined there) stay importable from here
+from .waveform import (METER_FIGURES, SAMPLE_RATE, _waveform_on_device, document_csr, finish_request, finish_waveforms,  # noqa: F401
+                       join_waveforms, to_waveforms, trim_trailing_silence)
 
 # Voice table of the shipped model: id, language, per-speaker duration scale correction (reference inference.py:16-32).
 VOICES = [
@@ -35,7 +38,6 @@ VOICES = [
     ])
 ]
 
-SAMPLE_RATE = 24000
 STD_RES_HOP_LENGTH = 256
 HIGH_RES_HOP_LENGTH = 128
 DEFAULT_ODE_SOLVER = "midpoint"
@@ -808,505 +810,9 @@ def load_vocoder(vocoder_name, checkpoint=None, state_dict=None):
     return vocoder
 
 
-def _waveform_on_device(mel, vocoder):
-    """Vocoder + peak normalisation of reference inference.py:260-264, left on the device."""
-    audio = vocoder(mel)
-    max_abs = audio.abs().max()
-    if max_abs > 1.0:
-        audio = audio / max_abs * 0.95
-    return audio
-
-
 def to_waveform(mel, vocoder):
     """reference inference.py:260-265."""
     return _waveform_on_device(mel, vocoder).cpu().squeeze()
-
-
-_finish_ws = _hip.Workspaces()      # finish_waveforms' scratch: its kernels write every word they read
-
-
-@torch.inference_mode()
-def finish_waveforms(audio, lengths, hop=0, silence_threshold_db=-60.0):
-    """Peak normalisation (reference inference.py:260-264) and the trim length of ``trim_trailing_silence`` (reference
-    inference.py:268-287) for every row of ``audio`` [B, L] on the device, in place, without a host synchronisation
-    (``mtts_waveform_finish``).  ``lengths`` [B]: valid samples per row, or frames when ``hop`` is given (row b then has
-    ``hop * (frames - 1)`` samples, as ``Vocos.decode(mel, lengths)`` leaves them).  Returns device tensors
-    ``(out_lengths int64 [B], scale float32 [B])``: the caller keeps ``audio[b, :out_lengths[b]]``; -1 marks a row whose length
-    is outside its row."""
-    lib = _hip.load()
-    if audio.dim() != 2 or audio.dtype != torch.float32 or not audio.is_cuda or not audio.is_contiguous():
-        raise RuntimeError("finish_waveforms: audio must be a contiguous float32 [B, L] tensor on a HIP device")
-    B, L = audio.shape
-    lengths = _hip.row_lengths(lengths, B, L, audio.device)
-    ws = _finish_ws.get("finish", lib.mtts_waveform_workspace_bytes(L, B, SAMPLE_RATE), audio.device)
-    scale = torch.empty(B, dtype=torch.float32, device=audio.device)
-    out_lengths = torch.empty(B, dtype=torch.long, device=audio.device)
-    _hip.check(lib.mtts_waveform_finish(_hip.ptr(audio), L, _hip.ptr(lengths), int(hop), B, SAMPLE_RATE, float(silence_threshold_db),
-                                        _hip.ptr(scale), _hip.ptr(out_lengths), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
-    return out_lengths, scale
-
-
-@torch.inference_mode()
-def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, *, encoding=None, dither=False, dither_keys=None,
-                 documents=None, gaps=None, fade_ms=5.0, level="document", return_segments=False, loudness=None, return_loudness=False,
-                 true_peak=None, return_meter=False, token_ends=None, x_lengths=None, breaks=None, return_marks=False, sample_rate=24000):
-    """``trim_trailing_silence(to_waveform(mel[b:b+1, :, :len_b], vocoder))`` (reference inference.py:246) for every row of a
-    ragged batch in one device pass: ragged Vocos decode, per-row peak normalisation, per-row trim lengths, then ONE copy of the
-    audio and one of the [B] lengths -- one synchronisation for the whole batch.  Returns a list of B 1-D host tensors
-    (``trim=False``: normalised but not trimmed, i.e. ``to_waveform`` per row); they are views of the batch's one host buffer.
-
-    ``sample_rate``: an int, or one per row.  Rows that ask for another rate than 24 kHz are converted on the device after the
-    normalisation and the trim, which run at 24 kHz exactly as without it: the kept samples of those rows go through
-    ``resample.resample`` (one call per distinct rate, the trim length as the row length, no extra host read) ahead of the copy.
-    The band-limited output of a row normalised to a 0.95 peak may overshoot that peak slightly; nothing is re-normalised, but
-    ``true_peak=`` (below) holds the level between the samples, which is what the conversion reconstructs, under a ceiling.
-
-    ``encoding``: None (float32 rows, as ever), a name -- ``"pcm16"`` (s16le), ``"ulaw"``, ``"alaw"`` (G.711) -- or one per row, where
-    None leaves a row float.  The rows that name one are encoded on the device (``audio_codec.encode``: one launch after the trim
-    and the rate conversion, on their device lengths, no extra host read) and come back as 1-D uint8 host tensors: raw samples, no
-    container, views of the batch's one host buffer of bytes; the one copy is then of bytes and the single synchronisation stays.
-    ``dither`` (a bool, or one per row): TPDF dither on the PCM16 rows, the sequence of row b selected by ``dither_keys[b]`` (default
-    0) and by nothing else, so a row's bytes do not depend on the batch it is in.  The keyword-only arguments follow a ``*``.
-
-    ``documents``: None (every row is its own result, as ever: nothing below is launched or allocated), or the rows that belong
-    together as a host list -- row counts in speaking order, or the CSR ``[0, n0, n0 + n1, ...]``; rows behind the last document are
-    documents of one row each.  The rows of a document are then joined on the device into one waveform (``join_waveforms``: once, at
-    24 kHz, after the normalisation and the trim and ahead of the rate conversion and the encoding, which see one row per document
-    and its joined device length) and the call returns one entry per DOCUMENT; ``sample_rate``, ``encoding``, ``dither`` and
-    ``dither_keys`` are then one per document.  ``gaps``: samples of silence (24 kHz) after each row, a host list of B (the entry of
-    a document's last row is ignored; default none).  ``fade_ms``: the fade at the interior joints.  ``level`` (a name, or one per
-    document): ``"document"`` gives a document one gain, that of its loudest sentence; ``"sentence"`` leaves each row the gain the
-    normalisation gave it.
-    ``return_segments``: also return, per document, ``[(start_s, end_s)]`` of its rows in seconds of the 24 kHz join (so they do
-    not depend on the output rate): ``(results, segments)``.  The single synchronisation stays.
-
-    ``loudness``: None (nothing below is launched or allocated), a target in LUFS, or one per row -- per document with
-    ``documents=`` -- where None leaves a row alone, bit for bit.  The rows that name one are brought to it on the device
-    (``loudness.normalize``: integrated loudness as in ITU-R BS.1770, one gain per row or document, limited so that the sample peak
-    stays at or under 0.95, the level the peak normalisation leaves).  The stage runs once, at 24 kHz: after the normalisation and the
-    trim, and after the join when there is one, so it sees one row per document on its device length; the rate conversion and the
-    encoder come behind it.  ``return_loudness``: also return ``[(lufs, gain)]`` per row or document -- the loudness measured BEFORE the
-    gain and the gain applied (1.0 for a row left alone); they ride in the one ``meta`` copy, so the single synchronisation stays.
-    With ``return_segments`` too the call returns ``(results, segments, loudness)``.
-
-    ``true_peak``: None (exactly the calls above are made), a ceiling in dBTP (finite, at most 0; EBU R 128 delivery is -1), or one per
-    row -- per document with ``documents=`` -- where None names none.  The gain of a row that names one is also limited so that its TRUE
-    peak, the level between the samples as an oversampling 12-tap interpolator reads it (``loudness.normalize(true_peak=)``), stays at
-    or under the ceiling.  A ceiling on a row without a loudness target raises ``ValueError`` before anything is launched: the
-    ceiling limits a gain, and such a row has none.  ``return_meter``: the report entries (returned as with ``return_loudness``) are
-    dicts of seven figures -- ``lufs``, ``gain``, ``lra``, ``momentary_max``, ``short_term_max``, ``peak``, ``true_peak`` (``loudness.meter``;
-    the peaks linear), all measured BEFORE the gain; they ride in the same ``meta`` copy.
-
-    ``token_ends`` / ``x_lengths`` / ``breaks`` / ``return_marks``: None / False (exactly the calls above are made), or token timing
-    (``timing.token_marks``, one planning launch after the normalisation and the trim, ahead of the join).  ``token_ends`` [B, Tx] and
-    ``x_lengths`` [B] are ``synthesise(return_timing=True)["token_ends"]`` and the token counts.  ``breaks``: per ROW a list of
-    ``(token, pause_ms)`` (None: none) -- a pause is cut into the row after that token (``timing.apply_breaks``, launched only when a row
-    has a break; the fade at a cut is ``fade_ms``), and the join, the loudness stage, the rate conversion and the encoder see the
-    lengthened rows through the device lengths they already take.  ``return_marks``: also return, LAST in the tuple, the marks
-    ``[(start_s, end_s)]`` per token of each row -- with ``documents=`` one list per row of each document, a row's start inside its
-    document added -- in seconds of the 24 kHz result like the segments, so they do not depend on the output rate.  The marks are copied
-    behind the batch's one synchronisation; no further wait is added."""
-    timed = token_ends is not None or breaks is not None or return_marks
-    if timed and (token_ends is None or x_lengths is None):
-        raise ValueError("to_waveforms: breaks and return_marks need token_ends= and x_lengths= (synthesise(return_timing=True))")
-    if timed:
-        from . import timing as TM
-        B_rows = 1 if mel.dim() == 2 else mel.shape[0]
-        if breaks is not None and len(breaks) != B_rows:
-            raise ValueError(f"breaks need one entry per row ({B_rows}), got {len(breaks)}")
-        break_rows = None if breaks is None else [
-            [(t, int(round(p * SAMPLE_RATE / 1000.0))) for t, p in TM.check_breaks(r, None, TM.PAUSE_MAX_MS, f"breaks[{b}]")]
-            for b, r in enumerate(breaks)]
-    if documents is None and (gaps is not None or return_segments):
-        raise ValueError("to_waveforms: gaps and return_segments belong to documents=")
-    if loudness is not None:                                           # (a target that is no level raises before anything is looked at)
-        from . import loudness as LD
-        LD.targets_per_row(loudness, 1 if isinstance(loudness, (int, float)) else len(loudness))
-    if true_peak is not None:                                          # (so does a ceiling that is none, or one on a row without a target)
-        from . import loudness as LD
-        n = next((len(v) for v in (true_peak, loudness) if v is not None and not isinstance(v, (int, float))), 1)
-        _true_peak_ceilings(true_peak, LD.targets_per_row(loudness, n), n)
-    if any(v not in ("document", "sentence") for v in ([level] if isinstance(level, str) else level)):
-        raise ValueError(f"to_waveforms: level is 'document' or 'sentence' (or one of them per document), got {level!r}")
-    model = vocoder.model if hasattr(vocoder, "model") else vocoder
-    if mel.dim() == 2:
-        mel = mel[None]
-    B, _, T = mel.shape
-    mel_lengths = torch.as_tensor(mel_lengths).to(device=mel.device, dtype=torch.long)
-    hop = model.cfg["hop"]
-    from . import resample as R
-    csr = None if documents is None else document_csr(documents, B, pad=True)
-    n_out = B if csr is None else len(csr) - 1
-    rates = R.rates_per_row(sample_rate, n_out)
-    encs = _encodings_per_row(encoding, n_out)                         # (an unknown name raises before anything is launched)
-    return_loudness = bool(return_loudness or return_meter)
-    targets = _loudness_targets(loudness, n_out, return_loudness)     # (so does a target that is no level)
-    ceilings = _true_peak_ceilings(true_peak, targets, n_out)          # (and a ceiling on a row without a target)
-    stage = dict(ceilings=ceilings, meter=bool(return_meter))
-    loud, report = [], []
-    audio = model.decode(mel, mel_lengths, check=False)
-    out_lengths, scale = finish_waveforms(audio, mel_lengths, hop=hop, silence_threshold_db=silence_threshold_db)
-    if timed:
-        # the timing plan (+ the breaks gather): from here on the rows are as long as the plan says, trimmed or not
-        keep = out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1))
-        fade = int(round(float(fade_ms) * SAMPLE_RATE / 1000.0))
-        audio, L = _hip.aligned_rows(audio, 4, "audio")
-        marks, out_lengths, plan = TM.token_marks(token_ends, x_lengths, keep, break_rows, fine_hop=hop // 2, keep_max=audio.shape[1],
-                                                   check=False)
-        if plan.NB:
-            audio = TM.apply_breaks(audio, plan, fade)
-        trim = True
-        marks_host = None
-        if return_marks:
-            marks_host = torch.empty(marks.shape, dtype=marks.dtype, pin_memory=True)
-            marks_host.copy_(marks, non_blocking=True)                # complete at the batch's one synchronisation, below
-        row_starts = [] if csr is not None else None
-        try:
-            res = _finished_rows(audio, out_lengths, scale, mel_lengths, hop, T, trim, csr, gaps, fade_ms, level, rates, encs, dither,
-                                 dither_keys, return_segments, targets, report, stage, return_loudness, loud, row_starts)
-        except ValueError:
-            plan.raise_refused()                                      # the timing plan's own verdict names the row and the reason
-            raise
-        if not return_marks:
-            return res
-        per_row = TM.marks_rows(marks_host, B, row_starts)
-        if csr is not None:
-            per_row = [per_row[csr[g]:csr[g + 1]] for g in range(len(csr) - 1)]
-        return (*res, per_row) if isinstance(res, tuple) else (res, per_row)
-    return _finished_rows(audio, out_lengths, scale, mel_lengths, hop, T, trim, csr, gaps, fade_ms, level, rates, encs, dither, dither_keys,
-                          return_segments, targets, report, stage, return_loudness, loud)
-
-
-def _finished_rows(audio, out_lengths, scale, mel_lengths, hop, T, trim, csr, gaps, fade_ms, level, rates, encs, dither, dither_keys,
-                   return_segments, targets, report, stage, return_loudness, loud, row_starts=None):
-    """``to_waveforms`` behind the normalisation and the trim (and the timing plan): the join, the loudness stage, the rate conversion,
-    the encoder and the batch's one synchronisation.  ``row_starts``: a list that receives each row's start inside its document."""
-    B = audio.shape[0]
-    if csr is not None:
-        keep = out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1))
-        fade = int(round(float(fade_ms) * SAMPLE_RATE / 1000.0))
-        res = _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, _document_scales(scale, level, csr), rates, encs,
-                                dither, dither_keys, return_segments, targets, report, stage, row_starts)
-        if not return_loudness:
-            return res
-        return (*res, report) if return_segments else (res, report)
-    if targets is not None:
-        audio, loud = _loudness_stage(audio, out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1)), targets,
-                                      **stage)
-    if any(r != SAMPLE_RATE for r in rates):
-        audio, out_lengths = _convert_rows(audio, out_lengths if trim else torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1)),
-                                           rates)
-    if encs is not None:
-        res = _encoded_rows(audio, out_lengths, mel_lengths, hop, T, trim, rates, encs, dither, dither_keys, loud, report)
-        return (res, report) if return_loudness else res
-    meta = torch.stack([out_lengths, mel_lengths] + loud).cpu()       # waits for the stream: the batch's one synchronisation
-    host = audio.cpu()
-    keep, frames = meta[0].tolist(), meta[1].tolist()
-    for b in range(B):
-        if keep[b] < 0:
-            raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
-    res = [host[b, : (keep[b] if trim or rates[b] != SAMPLE_RATE else hop * (frames[b] - 1))] for b in range(B)]
-    if not return_loudness:
-        return res
-    _loudness_report(meta[2:], report, len(loud))
-    return res, report
-
-
-def _loudness_targets(loudness, n, measure):
-    """``loudness=`` of ``to_waveforms`` as n targets with NaN for "leave the row alone"; None when the stage does not run (no row
-    names a target and no measurement is asked for).  A value that is no level raises here, before anything is launched."""
-    if loudness is None and not measure:
-        return None
-    from . import loudness as LD
-    targets = LD.targets_per_row(loudness, n)
-    return [float("nan")] * n if targets is None and measure else targets
-
-
-def _true_peak_ceilings(true_peak, targets, n):
-    """``true_peak=`` of ``to_waveforms`` as n ceilings in dBTP or None per row; None when no row names one.  A value that is no
-    ceiling, and a ceiling on a row without a loudness target, raise here, before anything is launched."""
-    if true_peak is None:
-        return None
-    from . import loudness as LD
-    if isinstance(true_peak, (int, float)) and not isinstance(true_peak, bool):
-        c = LD.check_true_peak(true_peak)                              # one ceiling for the call: it binds the rows that have a target
-        vals = [c if t == t else None for t in (targets or [math.nan] * n)]
-        if all(v is None for v in vals):
-            raise ValueError("to_waveforms: true_peak limits the gain towards a loudness target, and no row names one (loudness=)")
-        return vals
-    vals = [LD.check_true_peak(v) for v in (true_peak.tolist() if torch.is_tensor(true_peak) else true_peak)]
-    if len(vals) != n:
-        raise ValueError(f"true_peak is a number or one per row ({n}), got {len(vals)}")
-    for b, v in enumerate(vals):
-        if v is not None and (targets is None or targets[b] != targets[b]):
-            raise ValueError(f"to_waveforms: true_peak[{b}] = {v} limits the gain towards a loudness target, and row {b} names none")
-    return vals if any(v is not None for v in vals) else None
-
-
-METER_FIGURES = ("lufs", "gain", "lra", "momentary_max", "short_term_max", "peak", "true_peak")
-
-
-def _loudness_stage(audio, lengths, targets, ceilings=None, meter=False):
-    """The loudness stage of ``to_waveforms``: ``audio`` [n, L] at 24 kHz on its device lengths, in place (a padded copy when L is no
-    multiple of 4).  Returns the rows and what rides in the ``meta`` copy: the bits of the measured LUFS and of the gains as int64 --
-    with ``meter`` of the seven ``METER_FIGURES``.  Without ``ceilings`` and ``meter`` exactly one ``mtts_loudness`` call is made; rows
-    that name different ceilings are levelled by one call per distinct ceiling, each row in the call of its own (in the others its
-    target is NaN, so it keeps its bits and is measured before its gain)."""
-    from . import loudness as LD
-    rows, _ = _hip.aligned_rows(audio, 4, "audio")
-    if ceilings is None and not meter:
-        lufs, gain, _ = LD.normalize(rows, lengths, targets, SAMPLE_RATE, LD.PEAK_CEILING, check=False)
-        return rows, [lufs.view(torch.long), gain.to(torch.float64).view(torch.long)]
-    ceilings = [None] * len(targets) if ceilings is None else ceilings
-    out = None
-    for c in sorted(set(ceilings), key=lambda v: (v is not None, v)):
-        mine = [v == c for v in ceilings]
-        m = LD.normalize(rows, lengths, [t if own else math.nan for t, own in zip(targets, mine)], SAMPLE_RATE, LD.PEAK_CEILING,
-                         check=False, true_peak=c, return_meter=True)[3]
-        if out is None:
-            out = m
-        else:
-            mask = torch.tensor(mine, dtype=torch.bool, device=rows.device)
-            out = {k: torch.where(mask, m[k], out[k]) for k in out}
-    names = METER_FIGURES if meter else METER_FIGURES[:2]
-    return rows, [out[k].to(torch.float64).view(torch.long) for k in names]
-
-
-def _loudness_report(words, report, k=2):
-    """``[(lufs, gain)]`` from the k = 2 int64 rows of the ``meta`` copy (a host tensor [k, n], or a flat list of k n words); dicts of
-    the ``METER_FIGURES`` when the stage left all seven of them."""
-    vals = torch.as_tensor(words, dtype=torch.long).reshape(k, -1).contiguous().view(torch.float64).tolist()
-    if k == 2:
-        report.extend(zip(vals[0], vals[1]))
-    else:
-        report.extend(dict(zip(METER_FIGURES, row)) for row in zip(*vals))
-
-
-_join_ws = _hip.Workspaces()
-
-
-def document_csr(documents, B, pad=False):
-    """``documents`` -- a host list of row counts, or the CSR ``[0, n0, n0 + n1, ...]`` (it begins with 0, which no count can be) -- as
-    the CSR list the device takes.  Counts are checked here (each at least 1, their sum ``B``); a CSR is passed on as it is, for the
-    device to judge.  ``pad``: rows behind the last document become documents of one row each."""
-    docs = [int(v) for v in (documents.tolist() if torch.is_tensor(documents) else documents)]
-    if len(docs) == 0:
-        raise ValueError("documents: no document")
-    if docs[0] == 0:
-        csr = docs
-    else:
-        if any(n < 1 for n in docs):
-            raise ValueError("documents: a document has at least one row")
-        csr = [0]
-        for n in docs:
-            csr.append(csr[-1] + n)
-        if csr[-1] > B or (csr[-1] < B and not pad):
-            raise ValueError(f"documents: the row counts add up to {csr[-1]}, the batch has {B} rows")
-    if pad and len(csr) > 1 and 0 <= csr[-1] < B:
-        csr = csr + list(range(csr[-1] + 1, B + 1))
-    if len(csr) < 2:
-        raise ValueError("documents: no document")
-    return csr
-
-
-@torch.inference_mode()
-def join_waveforms(audio, lengths, documents, gaps, fade=0, scale=None, check=True, out_ld=None):
-    """Finished rows joined into documents on the device (``mtts_wave_join``; include/mtts.h has the arithmetic): ``audio`` [B, ld]
-    float32 and ``lengths`` [B] as ``finish_waveforms`` leaves them (a tensor stays on the device; -1 = refused row), ``documents`` a
-    host list of row counts or a CSR (``document_csr``), ``gaps`` a host list of B sample counts (silence after each row; the entry
-    of a document's last row is ignored; None: none), ``fade`` samples faded at each interior joint, ``scale`` the [B] gains of
-    ``finish_waveforms`` (one gain per document) or None (every row keeps its own).  Returns device tensors ``(out [G, out_ld],
-    out_lengths int64 [G], starts int64 [B])``: document g holds ``out_lengths[g]`` samples, zeros beyond; ``starts[b]`` is where row b
-    begins inside its document.  ``out_ld`` defaults to the host-known bound ``max_g(rows_g * ld + gaps_g)``, rounded up to 4.
-    Nothing is read on the host: a document with a refused row, a bad gap or no room gets length -1 and zeros, its rows start -1;
-    with ``check`` the call waits for that verdict and raises ``ValueError`` naming the row and the reason."""
-    lib = _hip.load()
-    audio, L = _hip.aligned_rows(audio, 4, "audio")
-    B, ld = audio.shape
-    dev = audio.device
-    lengths = _hip.row_lengths(lengths, B, L, dev)
-    csr = document_csr(documents, B)
-    G = len(csr) - 1
-    gaps = [0] * B if gaps is None else [int(v) for v in (gaps.tolist() if torch.is_tensor(gaps) else gaps)]
-    if len(gaps) != B:
-        raise ValueError(f"gaps need one entry per row ({B}), got {len(gaps)}")
-    if scale is not None:
-        scale = scale.to(device=dev, dtype=torch.float32).contiguous()
-        if scale.shape != (B,):
-            raise ValueError(f"scale must have shape ({B},), got {tuple(scale.shape)}")
-    if out_ld is None:
-        out_ld = max((b - a) * ld + sum(max(v, 0) for v in gaps[max(a, 0):max(b - 1, 0)]) for a, b in zip(csr[:-1], csr[1:]))
-    out_ld = max(4, (int(out_ld) + 3) // 4 * 4)
-    first_row = torch.tensor(csr, dtype=torch.int32).to(dev)
-    gap = torch.tensor(gaps, dtype=torch.long).to(dev)
-    out = torch.empty(G, out_ld, dtype=torch.float32, device=dev)
-    out_lengths = torch.empty(G, dtype=torch.long, device=dev)
-    starts = torch.empty(B, dtype=torch.long, device=dev)
-    ws = _join_ws.get("join", lib.mtts_wave_join_workspace_bytes(B, G), dev)
-    with torch.cuda.device(dev):
-        _hip.check(lib.mtts_wave_join(_hip.ptr(audio), ld, _hip.ptr(lengths), _hip.ptr(scale), _hip.ptr(first_row), _hip.ptr(gap), B, G,
-                                      int(fade), max([0] + gaps), _hip.ptr(out), out_ld, _hip.ptr(out_lengths), _hip.ptr(starts),
-                                      ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
-    if check:
-        _hip.raise_refused(lib.mtts_wave_join_status, ws.data_ptr(), _hip.stream_ptr())
-    return out, out_lengths, starts
-
-
-def _document_scales(scale, level, csr):
-    """``scale=`` of the join for ``level`` (a name, or one per document): the rows' gains where a document takes one gain, 1 on the
-    rows of a document whose sentences keep theirs (its gain is then 1 and nothing is multiplied), None when no document takes one."""
-    G = len(csr) - 1
-    levels = [level] * G if isinstance(level, str) else list(level)
-    if len(levels) != G:
-        raise ValueError(f"level is a name or one per document ({G}), got {len(levels)}")
-    if all(v == "sentence" for v in levels):
-        return None
-    if all(v == "document" for v in levels):
-        return scale
-    own = torch.tensor([levels[g] == "sentence" for g in range(G) for _ in range(csr[g], csr[g + 1])], dtype=torch.bool, device=scale.device)
-    return torch.where(own, torch.ones_like(scale), scale)
-
-
-def _joined_documents(audio, keep, mel_lengths, T, csr, gaps, fade, scale, rates, encs, dither, dither_keys, return_segments,
-                      targets=None, report=None, stage=None, row_starts=None):
-    """The end of ``to_waveforms`` with ``documents=``: the join at 24 kHz, then the rate conversion and the encoding over one row
-    per document on the joined device lengths, then the batch's one synchronisation -- the joined lengths, the rows' starts and kept
-    lengths ride in the one ``meta`` copy -- and one copy of no more columns than the longest document has."""
-    from . import audio_codec as AC
-    G = len(csr) - 1
-    dev = audio.device
-    wave, lens, starts = join_waveforms(audio, keep, csr, gaps, fade=fade, scale=scale, check=False)
-    loud = []
-    if targets is not None:                                            # one row per document, on its joined device length
-        wave, loud = _loudness_stage(wave, lens, targets, **(stage or {}))
-    if any(r != SAMPLE_RATE for r in rates):
-        wave, lens = _convert_rows(wave, lens, rates)
-    words = [lens, starts, keep, mel_lengths] + loud
-    if encs is not None:
-        named = torch.tensor([e is not None for e in encs], dtype=torch.bool, device=dev)
-        fmt = [AC.PCM16 if e is None else e for e in encs]
-        on = [bool(dither)] * G if isinstance(dither, (bool, int)) else [bool(v) for v in dither]
-        data, nbytes = AC.encode(wave, torch.where(named, lens, torch.zeros_like(lens)), fmt,
-                                 dither=on if len(set(on)) > 1 else on[0], keys=dither_keys)
-        words.append(nbytes)
-    meta = torch.cat(words).cpu().tolist()                             # waits for the stream: the batch's one synchronisation
-    B = keep.shape[0]
-    got, begin, kept, frames = meta[:G], meta[G:G + B], meta[G + B:G + 2 * B], meta[G + 2 * B:G + 3 * B]
-    if row_starts is not None:
-        row_starts.extend(begin)
-    at = G + 3 * B                                                     # what rides behind the lengths: loudness words, byte counts
-    if loud and report is not None:
-        _loudness_report(meta[at:at + len(loud) * G], report, len(loud))
-    at += len(loud) * G
-    for b in range(B):
-        if kept[b] < 0:
-            raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
-    for g in range(G):
-        if got[g] < 0:
-            raise ValueError(f"to_waveforms: document {g} (rows {csr[g]} to {csr[g + 1] - 1}) could not be joined")
-    width = max(got)
-    floats = wave[:, :width].cpu() if encs is None or not all(e is not None for e in encs) else None
-    if encs is None:
-        res = [floats[g, :got[g]] for g in range(G)]
-    else:
-        nb = meta[at:]
-        host = data[:, :max(max(nb), 1)].cpu()
-        res = [floats[g, :got[g]] if encs[g] is None else host[g, :nb[g]] for g in range(G)]
-    if not return_segments:
-        return res
-    segments = [[(begin[b] / SAMPLE_RATE, (begin[b] + kept[b]) / SAMPLE_RATE) for b in range(csr[g], csr[g + 1])] for g in range(G)]
-    return res, segments
-
-
-def _encodings_per_row(encoding, B):
-    """``encoding=`` of ``to_waveforms`` as a list of B format ids or None per row; None when no row names one."""
-    from . import audio_codec as AC
-    if encoding is None:
-        return None
-    if isinstance(encoding, str):
-        return [AC.format_id(encoding)] * B
-    encs = [None if e is None else AC.format_id(e) for e in encoding]
-    if len(encs) != B:
-        raise ValueError(f"encoding is a name or one per row ({B}), got {len(encs)}")
-    return encs if any(e is not None for e in encs) else None
-
-
-def _encoded_rows(audio, out_lengths, mel_lengths, hop, T, trim, rates, encs, dither, dither_keys, loud=(), report=None):
-    """The end of ``to_waveforms`` when rows name an encoding: one encode launch over the finished (and converted) rows on their
-    device lengths, then the batch's one synchronisation and the copy of the bytes.  Rows without an encoding take part in the
-    launch with length 0 and are returned float32 from a second copy, of the audio."""
-    from . import audio_codec as AC
-    B = audio.shape[0]
-    dev = audio.device
-    # the kept samples of every row, on the device: what the float path slices on the host
-    whole = torch.where(out_lengths < 0, out_lengths, hop * (mel_lengths - 1))
-    if trim:
-        keep_dev = out_lengths
-    else:
-        converted = torch.tensor([r != SAMPLE_RATE for r in rates], dtype=torch.bool, device=dev)
-        keep_dev = torch.where(converted, out_lengths, whole)
-    named = torch.tensor([e is not None for e in encs], dtype=torch.bool, device=dev)
-    fmt = [AC.PCM16 if e is None else e for e in encs]
-    on = [bool(dither)] * B if isinstance(dither, (bool, int)) else [bool(v) for v in dither]
-    data, nbytes = AC.encode(audio, torch.where(named, keep_dev, torch.zeros_like(keep_dev)), fmt,
-                             dither=on if len(set(on)) > 1 else on[0], keys=dither_keys)
-    meta = torch.stack([keep_dev, mel_lengths, nbytes, *loud]).cpu()   # waits for the stream: the batch's one synchronisation
-    keep, frames, got = (m.tolist() for m in meta[:3])
-    if len(loud) and report is not None:
-        _loudness_report(meta[3:], report, len(loud))
-    for b in range(B):
-        if keep[b] < 0 or got[b] < 0:
-            raise ValueError(f"to_waveforms: mel_lengths[{b}] = {frames[b]} is outside [1, T = {T}]")
-    width = max(AC.BYTES_PER_SAMPLE[f] for f in fmt) * audio.shape[1]  # G.711 rows use the front half of the stride
-    host = data[:, :width].cpu() if width < data.shape[1] else data.cpu()
-    floats = audio.cpu() if not all(e is not None for e in encs) else None
-    return [floats[b, :keep[b]] if encs[b] is None else host[b, :got[b]] for b in range(B)]
-
-
-def _convert_rows(audio, lengths, rates):
-    """Rows of ``audio`` [B, L] (24 kHz, ``lengths`` [B] kept samples on the device, -1 = refused row) at the rates they ask for:
-    ``(audio' [B, L'], lengths')`` on the device.  Rows at 24 kHz are copied, the others converted with one ``resample`` call per
-    distinct rate; a refused row stays refused (-1).  Nothing is read on the host."""
-    from . import resample as R
-    B, L = audio.shape
-    dev = audio.device
-    parts = []
-    for rate in sorted(set(rates) - {SAMPLE_RATE}):
-        rows = torch.tensor([b for b in range(B) if rates[b] == rate], dtype=torch.long, device=dev)
-        out, n = R.resample(audio.index_select(0, rows), lengths.index_select(0, rows), SAMPLE_RATE, rate, check=False)
-        parts.append((rows, out, n))
-    same = [b for b in range(B) if rates[b] == SAMPLE_RATE]
-    ld = max([L] * bool(same) + [out.shape[1] for _, out, _ in parts])
-    wave = torch.zeros(B, ld, dtype=torch.float32, device=dev)
-    new_lengths = lengths.clone()
-    if same:
-        rows = torch.tensor(same, dtype=torch.long, device=dev)
-        wave[rows, :L] = audio.index_select(0, rows)
-    for rows, out, n in parts:
-        wave[rows, :out.shape[1]] = out
-        new_lengths[rows] = n
-    return wave, new_lengths
-
-
-def trim_trailing_silence(audio, silence_threshold_db=-60.0):
-    """reference inference.py:268-287, window for window: 10 ms windows anchored at sample 0 (the ``len % window`` remainder is
-    never examined), RMS per window, count the run of trailing windows with ``rms < threshold`` (strict; a NaN window stops the
-    run as in the reference's loop), drop ``count * window`` samples from the END of the signal.  All full windows may go.
-    Works on a 1-D tensor on any device: the window RMS and the run length are computed where the audio lives (one scalar
-    comes back to the host), so ``pipeline`` trims before the device-to-host copy."""
-    win = int(0.01 * SAMPLE_RATE)
-    thr = 10 ** (silence_threshold_db / 20.0)
-    n_full = len(audio) // win
-    if n_full == 0:
-        return audio
-    rms = audio[: n_full * win].reshape(n_full, win).pow(2).mean(dim=1).sqrt()
-    loud = torch.logical_not(rms < thr)
-    idx = torch.arange(1, n_full + 1, device=audio.device)
-    last_loud = int((loud * idx).max())            # 1-based index of the last window that is not silent; 0 = none
-    trim = (n_full - last_loud) * win
-    if trim == 0:
-        return audio
-    return audio[:-trim]
 
 
 @torch.inference_mode()
@@ -1333,24 +839,8 @@ def pipeline(model, vocoder, text, speaker=0, voice_mix=None, n_timesteps=DEFAUL
     tp = process_text(text, language)
     out = model.synthesise(tp["x"], tp["x_lengths"], n_timesteps=n_timesteps, speaker=speaker, voice_mix=voice_mix,
                            scale_correction=scale_correction, length_scale=length_scale, debug=debug)
-    waveform = trim_trailing_silence(_waveform_on_device(out["mel"], vocoder).squeeze())
-    if target is not None and waveform.numel() > 0:
-        n = waveform.numel()
-        rows = torch.zeros(1, (n + 3) // 4 * 4, dtype=torch.float32, device=waveform.device)
-        rows[0, :n] = waveform
-        LD.normalize(rows, [n], target, SAMPLE_RATE, check=False, true_peak=ceiling)
-        waveform = rows[0, :n]
-    if int(sample_rate) != SAMPLE_RATE and waveform.numel() > 0:
-        from . import resample as R
-        conv, _ = R.resample(waveform.reshape(1, -1), None, SAMPLE_RATE, int(sample_rate), check=False)
-        waveform = conv[0, :R.resampler(SAMPLE_RATE, int(sample_rate), conv.device).out_length(waveform.numel())]
-    if encoding is not None and waveform.numel() > 0:
-        from . import audio_codec as AC
-        data, _ = AC.encode(waveform.reshape(1, -1), None, encoding)
-        waveform = data[0, :waveform.numel() * AC.BYTES_PER_SAMPLE[AC.format_id(encoding)]]
-    elif encoding is not None:
-        waveform = torch.zeros(0, dtype=torch.uint8)
-    waveform = waveform.cpu()
+    waveform, _ = finish_request(trim_trailing_silence(_waveform_on_device(out["mel"], vocoder).squeeze()), loudness=target,
+                                 true_peak=ceiling, sample_rate=sample_rate, encoding=encoding)
     if not debug:
         return waveform
     durs = out["phoneme_durations"].squeeze(0).tolist()

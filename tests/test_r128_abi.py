@@ -204,10 +204,11 @@ def test_python_entries_refuse_before_anything_is_launched():
                dict(true_peak=[None, -2.0], loudness=[-23.0, None]), dict(true_peak=0.5, loudness=-23.0), dict(true_peak="hot", loudness=-23.0)):
         with pytest.raises((TypeError, ValueError)):
             inf.to_waveforms(None, [1, 1], None, **kw)
-    assert inf._true_peak_ceilings(-1.0, [-23.0, math.nan], 2) == [-1.0, None]          # one ceiling: it binds the rows with a target
-    assert inf._true_peak_ceilings([None, -2], [-23.0, -16.0], 2) == [None, -2.0] and inf._true_peak_ceilings([None, None], None, 2) is None
+    ceilings = sub("waveform")._true_peak_ceilings
+    assert ceilings(-1.0, [-23.0, math.nan], 2) == [-1.0, None]          # one ceiling: it binds the rows with a target
+    assert ceilings([None, -2], [-23.0, -16.0], 2) == [None, -2.0] and ceilings([None, None], None, 2) is None
     with pytest.raises(ValueError, match="one per row"):
-        inf._true_peak_ceilings([-1.0], [-23.0, -23.0], 2)
+        ceilings([-1.0], [-23.0, -23.0], 2)
     with pytest.raises(ValueError, match="target"):
         inf.pipeline(None, None, "never spoken", true_peak=-1.0)
 

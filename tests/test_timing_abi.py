@@ -334,7 +334,7 @@ def test_synthesise_without_the_new_arguments_makes_the_calls_of_before():
 
 
 def test_to_waveforms_without_the_new_arguments_makes_the_calls_of_before(monkeypatch, tm):
-    inf = sub("inference")
+    inf, tail = sub("inference"), sub("waveform")
     calls = []
 
     class Head:
@@ -360,8 +360,8 @@ def test_to_waveforms_without_the_new_arguments_makes_the_calls_of_before(monkey
         calls.append(("apply_breaks", fade))
         return torch.cat([audio, torch.zeros(2, 2400)], 1)
 
-    monkeypatch.setattr(inf, "finish_waveforms", finish)
-    monkeypatch.setattr(inf._hip, "aligned_rows", lambda t, q, what, layout="": (t, t.shape[1]))
+    monkeypatch.setattr(tail, "finish_waveforms", finish)
+    monkeypatch.setattr(tail._hip, "aligned_rows", lambda t, q, what, layout="": (t, t.shape[1]))
     monkeypatch.setattr(tm, "token_marks", marks)
     monkeypatch.setattr(tm, "apply_breaks", gather)
     monkeypatch.setattr(torch, "empty", lambda *a, pin_memory=False, _e=torch.empty, **kw: _e(*a, **kw))
