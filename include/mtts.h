@@ -1007,6 +1007,59 @@ int mtts_pcm_decode(const uint8_t* d_data, int64_t ld_bytes, const int64_t* d_le
                     float* d_out, int64_t ld, int64_t* d_out_lengths, void* stream);
 int mtts_pcm_status(const int64_t* d_verdict, int B, void* stream);
 
+/* ---------------------------------------------------------------- FLAC out: lossless compressed audio, encoded on the device */
+
+/* A row becomes one complete mono, 16-bit, fixed-blocksize FLAC stream (RFC 9639): the compressed form of the "pcm" bytes above, about
+ * 0.7 of their size on speech.  The encoder is deterministic: every byte is a function of the row's samples, its rate, the block size
+ * and (seed, key), and of nothing else -- not of the batch, the row index or the grid.  tests/flac_restated.py restates it in NumPy bit
+ * for bit, beside an independent decoder.  Out of scope: decoding FLAC, LPC subframes, stereo, the MD5 signature, seek tables.
+ *
+ *   samples:  q[i] is exactly the PCM16 word mtts_pcm_encode writes for the row: the same arithmetic, the same dither as a function of
+ *             (seed, key, i) when dither is on (the same device functions, csrc/pcm_quantise.h).
+ *   header:   42 bytes.  "fLaC"; 80 00 00 22 (last metadata block, STREAMINFO, 34 bytes); then, big-endian and bit-packed: min = max
+ *             block size bs (16 bits each); min and max frame size in bytes over the row's frames (24 bits each; 0 for an empty row);
+ *             sample rate (20); channels - 1 = 0 (3); bits per sample - 1 = 15 (5); total samples (36); MD5 = 16 zero bytes, which the
+ *             format reads as "not computed".  A row of length 0 is these 42 bytes alone.
+ *   frames:   bs is one of 256, 512, 1024, 2048, 4096.  Frame f holds the samples [f * bs, min((f + 1) * bs, len)); n is its count.
+ *   frame header: FF F8 (sync, fixed block size).  Block-size code (4 bits): 1000..1100 for 256..4096 when n == bs; else 0110 and an 8-bit
+ *             n - 1 when n <= 256; else 0111 and a 16-bit n - 1.  Rate code (4 bits), first match: 0001..1011 for 88200, 176400, 192000,
+ *             8000, 16000, 22050, 24000, 32000, 44100, 48000, 96000; 1101 and 16-bit Hz when the rate <= 65535; 1110 and 16-bit tens of
+ *             Hz when the rate is a multiple of 10 and rate / 10 <= 65535; else 0000 (as STREAMINFO says).  Channel assignment 0000,
+ *             sample-size code 100, a reserved 0 bit.  The frame number in the RFC's UTF-8-like coding, 1 to 4 bytes.  The block-size
+ *             tail, the rate tail.  CRC-8 of the header so far (polynomial 0x07, initial value 0).
+ *   subframe: one.  Its header byte: a 0 bit, a 6-bit type, a wasted-bits flag of 0.
+ *             CONSTANT (000000, the value in 16 bits) when all n samples are equal.
+ *             Otherwise FIXED of order o (001ooo): o is the order in 0..4 with the smallest sum over i in [4, n) of |e_o[i]|, e_o the
+ *             o-th difference of q, ties to the lower order (so o = 0 when n <= 4).  Body: o warm-up samples of 16 bits, then the
+ *             residual: method 00 (4-bit parameters); a 4-bit partition order log2(bs / 256) when n == bs, else 0 -- a full frame has
+ *             partitions of 256 samples, the first holding 256 - o residuals; a short last frame is one partition.  Per partition a 4-bit
+ *             k, then the codes: k in 0..14 minimises cnt * (k + 1) + sum(u >> k), ties to the smaller k (15, the escape, is never used);
+ *             u = 2 r for r >= 0, -2 r - 1 otherwise; a code is u >> k zero bits, a one bit, the low k bits of u, MSB first.
+ *             VERBATIM (000001, n samples of 16 bits) when the FIXED subframe, its header byte included, has >= 8 + 16 n bits: every
+ *             frame is therefore at most 2 * bs + 16 bytes.
+ *   close:    zero bits to the byte boundary, then CRC-16 of the whole frame (polynomial 0x8005, initial value 0), big-endian.
+ *   ranges:   |e_4| <= 2^19 and u <= 2^20, so a cost over 4095 samples reaches 2^32: the order costs and sum(u >> k) are 64-bit sums
+ *             (32 bits inside a partition of 256, where they stay below 2^29).
+ *
+ * mtts_flac_encode: d_audio [B][ld] fp32 (ld % 4 == 0, 16-byte aligned), d_lengths device int64 [B], d_rates device int32 [B] (Hz),
+ * d_keys device int64 [B] or NULL (all 0), dither / seed as mtts_pcm_encode takes them -> d_out uint8 [B][out_ld], row b holding
+ * d_out_bytes[b] bytes from its start.  out_ld >= mtts_flac_row_bytes(ld, block_size) = 42 + ceil(ld / bs) * (2 * bs + 16) rounded up to
+ * 16, and a multiple of 16.  d_ws: mtts_flac_workspace_bytes(B, ld, block_size) bytes, 16-byte aligned: a fixed-stride staging slot and
+ * a byte count per frame; every word read from it was written by the same call.  Three launches (frame encode, row layout, compaction);
+ * every output byte is written once and nothing at or beyond d_out_bytes[b] is written.  Stream-ordered, no allocation, no
+ * synchronisation.
+ *   refusals: a length outside [0, ld] (one that already is -1 included), a rate outside [1, 1048575] or a row of more than 2^21 frames
+ *             gives d_out_bytes[b] = -1 and no byte written for that row; the other rows are unaffected.  mtts_pcm_status reads the
+ *             verdict as it does for the PCM entries.
+ * What the host can see returns -1 (mtts_last_error; the two size queries too): null pointers (d_keys excepted), B < 1, a bad ld, a
+ * block_size that is none of the five, a small out_ld or ws_bytes, a misaligned buffer, d_out / d_ws / d_audio overlapping. */
+#define MTTS_FLAC 3
+int64_t mtts_flac_row_bytes(int64_t ld, int block_size);
+int64_t mtts_flac_workspace_bytes(int B, int64_t ld, int block_size);
+int mtts_flac_encode(const float* d_audio, int64_t ld, const int64_t* d_lengths, const int32_t* d_rates, const int64_t* d_keys, int B,
+                     int block_size, int dither, int64_t seed, uint8_t* d_out, int64_t out_ld, int64_t* d_out_bytes, void* d_ws,
+                     int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- loudness: BS.1770 K-weighted, gated LUFS, one gain per row */
 
 /* How loud a row is, and the gain that brings it to a target: integrated loudness as in ITU-R BS.1770-4 / EBU R 128 for a ragged

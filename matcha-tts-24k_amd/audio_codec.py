@@ -1,6 +1,7 @@
 """Encoded audio in and out on MI355X (``mtts_pcm_encode`` / ``mtts_pcm_decode``): the last stage of the waveform tail -- fp32 rows to
 the bytes a client is sent, s16le for the OpenAI route's ``pcm`` / ``wav`` and G.711 mu-law / A-law for an 8 kHz telephony leg -- and
-the first stage of the recording entries, which take clips that are still bytes (``Encoded``).
+the first stage of the recording entries, which take clips that are still bytes (``Encoded``).  ``encode_flac`` is the compressed way
+out: one complete FLAC stream per row (``mtts_flac_encode``, include/mtts.h "FLAC out"), the same PCM16 words without loss.
 
 One launch per ragged batch, a format per row, lengths checked on the device.  Every byte is defined by include/mtts.h "encoded
 audio" (DESIGN.md section 4); there is no CPU path.  The RIFF container (``wav_bytes`` / ``read_wav``) is host code: a header in
@@ -18,11 +19,13 @@ import torch
 
 from . import _hip
 
-PCM16, ULAW, ALAW = 0, 1, 2
-FORMATS = {"pcm16": PCM16, "ulaw": ULAW, "alaw": ALAW}
+PCM16, ULAW, ALAW, FLAC = 0, 1, 2, 3
+FORMATS = {"pcm16": PCM16, "ulaw": ULAW, "alaw": ALAW}      # samples of a fixed size: what ``encode`` writes and ``decode`` reads
 NAMES = {v: k for k, v in FORMATS.items()}
-BYTES_PER_SAMPLE = {PCM16: 2, ULAW: 1, ALAW: 1}
+ENCODINGS = {**FORMATS, "flac": FLAC}                       # what a finished row can leave the tail as (``encoding_id``)
+BYTES_PER_SAMPLE = {PCM16: 2, ULAW: 1, ALAW: 1}             # (FLAC has none: a stream's length is ``encode_flac``'s second result)
 WAV_TAGS = {PCM16: 1, ULAW: 7, ALAW: 6}          # WAVE_FORMAT_PCM, WAVE_FORMAT_MULAW, WAVE_FORMAT_ALAW
+FLAC_BLOCK_SIZES = (256, 512, 1024, 2048, 4096)
 
 
 def __getattr__(name):
@@ -31,13 +34,26 @@ def __getattr__(name):
     raise AttributeError(name)
 
 
+def _is_flac(fmt) -> bool:
+    return fmt == "flac" if isinstance(fmt, str) else isinstance(fmt, (int, np.integer)) and not isinstance(fmt, bool) and int(fmt) == FLAC
+
+
 def format_id(fmt) -> int:
-    """``"pcm16"`` / ``"ulaw"`` / ``"alaw"`` (or the id itself) -> MTTS_PCM16 / MTTS_ULAW / MTTS_ALAW; ``ValueError`` otherwise."""
+    """``"pcm16"`` / ``"ulaw"`` / ``"alaw"`` (or the id itself) -> MTTS_PCM16 / MTTS_ULAW / MTTS_ALAW; ``ValueError`` otherwise.  FLAC
+    is none of them -- a stream has no fixed size per sample -- and its ``ValueError`` says where it is written."""
     if isinstance(fmt, str) and fmt in FORMATS:
         return FORMATS[fmt]
     if isinstance(fmt, (int, np.integer)) and not isinstance(fmt, bool) and int(fmt) in NAMES:
         return int(fmt)
+    if _is_flac(fmt):
+        raise ValueError("FLAC is no format of encode / decode / Encoded / wav_bytes, whose rows are samples of a fixed size: a FLAC "
+                         "stream is written by encode_flac -> (data, byte counts), and is not read back (decoding FLAC is out of scope)")
     raise ValueError(f"unknown audio format {fmt!r}: one of {sorted(FORMATS)}")
+
+
+def encoding_id(enc) -> int:
+    """``format_id`` with ``"flac"`` (MTTS_FLAC): the names ``to_waveforms(encoding=)`` and ``Request.encoding`` take."""
+    return FLAC if _is_flac(enc) else format_id(enc)
 
 
 def formats_per_row(formats, B: int, what: str = "formats"):
@@ -100,7 +116,10 @@ def encode(audio: torch.Tensor, lengths, formats, dither=False, seed: int = 0, k
 
     ``dither``: TPDF dither of one LSB on the PCM16 rows (G.711 rows compand the undithered value), a bool or one per row (two
     launches then, each over its rows); ``seed`` per call and ``keys`` (int64 per row, default 0) select the sequence, which is a
-    function of (seed, key, sample index) only: a row's bytes do not depend on the batch it is in."""
+    function of (seed, key, sample index) only: a row's bytes do not depend on the batch it is in.  ``"flac"`` is no format of this
+    entry -- its output has another shape -- and raises ``ValueError`` naming ``encode_flac``."""
+    if _is_flac(formats) or (isinstance(formats, (list, tuple)) and any(_is_flac(f) for f in formats)):
+        format_id("flac")                       # (raises, before anything else is looked at)
     lib = _hip.load()
     audio, L = _hip.aligned_rows(audio, 4, "audio")
     (B, ld), dev = audio.shape, audio.device
@@ -140,6 +159,71 @@ def encode(audio: torch.Tensor, lengths, formats, dither=False, seed: int = 0, k
             mask = torch.tensor(on, dtype=torch.bool, device=dev)
             zero = torch.zeros_like(lengths)
             nbytes = torch.where(mask, launch(torch.where(mask, lengths, zero), True), launch(torch.where(mask, zero, lengths), False))
+    if check:
+        _status(lib, nbytes)
+    return out, nbytes
+
+
+_flac_ws = _hip.Workspaces()                    # staging slots: every word the call reads it has written
+
+
+def flac_block_size(block_size) -> int:
+    if isinstance(block_size, bool) or not isinstance(block_size, (int, np.integer)) or int(block_size) not in FLAC_BLOCK_SIZES:
+        raise ValueError(f"a FLAC block size is one of {FLAC_BLOCK_SIZES}, got {block_size!r}")
+    return int(block_size)
+
+
+@torch.inference_mode()
+def encode_flac(audio: torch.Tensor, lengths, sample_rates, block_size: int = 4096, dither=False, seed: int = 0, keys=None,
+                check: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """audio [B, L] (or [L]) float32 on the device + lengths [B] (samples; default all L) + ``sample_rates`` (Hz: an int, one per row,
+    or a device int32 tensor) -> ``(data uint8 [B, stride], byte counts int64 [B])`` on the device: row b holds one complete mono
+    16-bit FLAC stream of ``nbytes[b]`` bytes, a file as it is (include/mtts.h "FLAC out"; ``stride = mtts_flac_row_bytes``).  It
+    holds exactly the words ``encode(..., "pcm16")`` gives for the row -- with ``dither`` (a bool, or one per row), ``seed`` and
+    ``keys`` the same dithered words -- in frames of ``block_size`` samples; an empty row is the 42 header bytes.  Bytes at or beyond
+    ``nbytes[b]`` are not written.  Nothing is read on the host: a length outside [0, L] (or one that already is -1) and a rate
+    outside [1, 1048575] give ``nbytes[b] = -1`` and an unwritten row; ``check=True`` waits for that verdict and raises ``ValueError``."""
+    lib = _hip.load()
+    bs = flac_block_size(block_size)
+    audio, L = _hip.aligned_rows(audio, 4, "audio")
+    (B, ld), dev = audio.shape, audio.device
+    lengths = _hip.row_lengths(lengths, B, L, dev)
+    if isinstance(sample_rates, (int, np.integer)) and not isinstance(sample_rates, bool):
+        sample_rates = [int(sample_rates)] * B
+    rates = torch.as_tensor(sample_rates).to(device=dev, dtype=torch.int32).contiguous()
+    if rates.shape != (B,):
+        raise ValueError(f"sample_rates is an int or one per row ({B}), got shape {tuple(rates.shape)}")
+    if keys is not None:
+        keys = torch.as_tensor(keys).to(device=dev, dtype=torch.long).contiguous()
+        if keys.shape != (B,):
+            raise ValueError(f"keys must have shape ({B},), got {tuple(keys.shape)}")
+    seed = int(seed)
+    if not -(1 << 63) <= seed < (1 << 63):
+        raise ValueError("seed must fit a signed 64-bit integer")
+    stride = _hip.size(lib.mtts_flac_row_bytes(ld, bs))
+    out = torch.empty(B, stride, dtype=torch.uint8, device=dev)
+    ws = _flac_ws.get("flac", lib.mtts_flac_workspace_bytes(B, ld, bs), dev)
+
+    def launch(row_lengths, on):
+        nbytes = torch.empty(B, dtype=torch.long, device=dev)
+        with torch.cuda.device(dev):
+            _hip.check(lib.mtts_flac_encode(_hip.ptr(audio), ld, _hip.ptr(row_lengths), _hip.ptr(rates), _hip.ptr(keys), B, bs, int(on), seed,
+                                            _hip.ptr(out), stride, _hip.ptr(nbytes), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
+        return nbytes
+
+    if isinstance(dither, (bool, int, np.bool_)):
+        nbytes = launch(lengths, bool(dither))
+    else:
+        on = [bool(v) for v in dither]
+        if len(on) != B:
+            raise ValueError(f"dither is a bool or one per row ({B}), got {len(on)}")
+        if all(on) or not any(on):
+            nbytes = launch(lengths, on[0])
+        else:
+            # one call per value over its own rows: the other rows take part refused (-1: no byte written, the header included)
+            mask = torch.tensor(on, dtype=torch.bool, device=dev)
+            off = torch.full_like(lengths, -1)
+            nbytes = torch.where(mask, launch(torch.where(mask, lengths, off), True), launch(torch.where(mask, off, lengths), False))
     if check:
         _status(lib, nbytes)
     return out, nbytes

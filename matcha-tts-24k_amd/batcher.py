@@ -43,7 +43,7 @@ class Request:
     length_scale: float = 1.0
     durations: Optional[Sequence[float]] = None    # fine frames per token (e.g. ``align(...)["durations"]``) instead of the predictor's; length_scale still applies
     sample_rate: int = 24000                # rate of the result's "audio" (with a vocoder); anything else is converted on the device and named in the result
-    encoding: Optional[str] = None          # "pcm16" / "ulaw" / "alaw": the result's "audio" is then raw bytes (a 1-D uint8 tensor) encoded on the device, and named in the result
+    encoding: Optional[str] = None          # "pcm16" / "ulaw" / "alaw": the result's "audio" is then raw bytes (a 1-D uint8 tensor) encoded on the device, and named in the result; "flac": one complete FLAC stream (audio_codec.encode_flac)
     dither: bool = False                    # TPDF dither on a "pcm16" result
     dither_key: int = 0                     # selects the dither sequence: a field of the request, so its bytes do not depend on who shared its batch
     loudness: Optional[float] = None        # target in LUFS (BS.1770 integrated loudness) the "audio" is brought to on the device at 24 kHz; the result then carries "loudness" (measured, before the gain) and "gain"
@@ -68,8 +68,8 @@ class Request:
             if self.breaks is not None:
                 self.breaks = check_breaks(self.breaks, len(self.ids), what="a request's breaks")
         if self.encoding is not None:       # (an unknown name fails its own request here, not the batch it would have joined)
-            from .audio_codec import format_id
-            format_id(self.encoding)
+            from .audio_codec import encoding_id
+            encoding_id(self.encoding)
         if self.loudness is not None:       # (so does a target that is no level)
             from .loudness import check_target
             self.loudness = check_target(self.loudness)
@@ -240,8 +240,8 @@ class Document:
         if len({r.group for r in self.rows}) != 1:
             raise ValueError("the rows of a document share solver and n_timesteps")
         if self.encoding is not None:
-            from .audio_codec import format_id
-            format_id(self.encoding)
+            from .audio_codec import encoding_id
+            encoding_id(self.encoding)
 
     @property
     def group(self) -> Tuple[Any, ...]:
@@ -435,8 +435,8 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
     rows).  ``sample_rates``: one rate per request (default 24 kHz); rows that ask for another rate are converted on the device after
     the normalisation and the trim (``inference.to_waveforms``) and carry ``res[b]["sample_rate"]`` beside ``"audio"``.
     ``encodings``: one name or None per request; a row that names one is encoded on the device after that (``audio_codec.encode``,
-    with the request's ``dithers`` flag and ``dither_keys`` entry), its ``"audio"`` is a 1-D uint8 tensor of raw samples and it
-    carries ``res[b]["encoding"]``.  ``loudness``: one target in LUFS or None per request (``loudness_field``); a row that names one is
+    with the request's ``dithers`` flag and ``dither_keys`` entry), its ``"audio"`` is a 1-D uint8 tensor of raw samples -- of one
+    FLAC stream, a file as it is, for ``"flac"`` (``audio_codec.encode_flac``) -- and it carries ``res[b]["encoding"]``.  ``loudness``: one target in LUFS or None per request (``loudness_field``); a row that names one is
     brought to it on the device at 24 kHz, ahead of the conversion and the encoder (``inference.to_waveforms(loudness=...)``), and
     carries ``res[b]["loudness"]`` -- the LUFS measured before the gain -- and ``res[b]["gain"]``; the other rows keep their bits.
     ``true_peak``: one ceiling in dBTP or None per request (``true_peak_field``); a row that names one has its gain also limited by its

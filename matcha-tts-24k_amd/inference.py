@@ -824,7 +824,8 @@ def pipeline(model, vocoder, text, speaker=0, voice_mix=None, n_timesteps=DEFAUL
     ``sample_rate``: the rate of the returned waveform; anything but 24 kHz is converted on the device after the normalisation and
     the trim (``resample.resample``; the band-limited result may overshoot the 0.95 peak slightly, nothing is re-normalised).
     ``encoding``: None (a float32 waveform), or ``"pcm16"`` / ``"ulaw"`` / ``"alaw"``: the waveform is encoded on the device
-    (``audio_codec.encode``) and returned as a 1-D uint8 host tensor of raw samples.
+    (``audio_codec.encode``) and returned as a 1-D uint8 host tensor of raw samples; ``"flac"``: as one complete FLAC stream
+    (``audio_codec.encode_flac``), a file as it is.
     ``loudness``: None, or a target in LUFS the waveform is brought to on the device (``loudness.normalize``: BS.1770 integrated
     loudness, the sample peak held at or under 0.95), at 24 kHz after the trim and ahead of the rate conversion and the encoder.
     ``true_peak``: None, or a ceiling in dBTP on the true peak of the levelled waveform (``loudness.normalize(true_peak=)``); it

@@ -7,8 +7,9 @@ correction of ``VOICES``, the speed -> length_scale clamp) as a pure function, a
 puts behind the same route: it phonemizes, submits to a ``FrameBudgetBatcher`` (so concurrent requests share estimator
 launches without changing anybody's audio) and awaits the trimmed waveform.  ``response_format`` names the plain formats of the
 route -- ``pcm`` (s16le), ``wav`` (RIFF + PCM16) -- and the two G.711 laws of a telephony leg; their samples are encoded on the device
-(``audio_codec``).  Transport, the compressed response encodings (MP3 / OGG) and the phonemizer stay the reference's (out of the
-path's scope).
+(``audio_codec``).  A service built with ``flac=True`` also answers ``response_format="flac"``: the route's lossless compressed format,
+one FLAC stream per request, encoded on the device too (``audio_codec.encode_flac``).  Transport, the lossy response encodings (MP3 /
+OGG, with their psychoacoustic models) and the phonemizer stay the reference's (out of the path's scope).
 """
 from __future__ import annotations
 
@@ -26,6 +27,8 @@ MAX_DOCUMENT_LENGTH = 20000 # characters of a text spoken as a document (submit_
 
 #: ``response_format`` -> the encoding a request asks of the batcher; "wav" is that payload behind a RIFF header
 RESPONSE_FORMATS = {"pcm": "pcm16", "wav": "pcm16", "ulaw": "ulaw", "alaw": "alaw"}
+#: what a service built with ``flac=True`` answers besides: the stream is a file as it is
+COMPRESSED_FORMATS = {"flac": "flac"}
 
 _MIX = re.compile(r"^\s*(\d+)\((\d+)\)\s*$")
 
@@ -55,19 +58,23 @@ class SpeechParams:
     solver: str
 
 
-def response_encoding(response_format: Optional[str]) -> Optional[str]:
-    """The ``Request.encoding`` of a ``response_format``: None for None (a float waveform), else ``RESPONSE_FORMATS``; ``ValueError``
-    for a name that is none of them (mp3 / opus are the reference's post-waveform codecs, ``inference.convert_to_*``)."""
+def response_encoding(response_format: Optional[str], flac: bool = False) -> Optional[str]:
+    """The ``Request.encoding`` of a ``response_format``: None for None (a float waveform), else ``RESPONSE_FORMATS`` -- with ``flac``
+    (a service that opted in) ``COMPRESSED_FORMATS`` too; ``ValueError`` for a name that is none of them (mp3 / opus are the
+    reference's post-waveform codecs, ``inference.convert_to_*``)."""
     if response_format is None:
         return None
-    if response_format not in RESPONSE_FORMATS:
-        raise ValueError(f"unknown response_format {response_format!r}: one of {sorted(RESPONSE_FORMATS)} (or None for float samples)")
-    return RESPONSE_FORMATS[response_format]
+    known = {**RESPONSE_FORMATS, **COMPRESSED_FORMATS} if flac else RESPONSE_FORMATS
+    if response_format not in known:
+        hint = " (\"flac\" is answered by a service built with flac=True)" if response_format in COMPRESSED_FORMATS else ""
+        raise ValueError(f"unknown response_format {response_format!r}: one of {sorted(known)} (or None for float samples){hint}")
+    return known[response_format]
 
 
 def response_body(res, response_format: Optional[str], sample_rate: int = 24000):
     """What ``speak`` returns for a batcher result: the ``"audio"`` (or the mel, without a vocoder) as it is when no
-    ``response_format`` was named, else ``bytes`` -- the raw encoded samples, behind a RIFF header for ``"wav"``."""
+    ``response_format`` was named, else ``bytes`` -- the raw encoded samples, behind a RIFF header for ``"wav"``; a ``"flac"`` stream as
+    it is, since it already is a file."""
     audio = res["audio"] if "audio" in res else res["mel"]
     if response_format is None:
         return audio
@@ -113,8 +120,10 @@ class SpeechService:
 
     def __init__(self, batcher, phonemize: Callable[[str, str], Sequence[int]], max_text_length: int = MAX_TEXT_LENGTH,
                  loudness: Optional[float] = None, true_peak: Optional[float] = None, marks: bool = False,
-                 word_groups: Optional[Callable[[str, str, Sequence[int]], Sequence[int]]] = None):
-        """``marks``: every request of this service asks for token marks -- ``submit``'s future then carries ``"marks"``: ``{"tokens":
+                 word_groups: Optional[Callable[[str, str, Sequence[int]], Sequence[int]]] = None, flac: bool = False):
+        """``flac``: this service also answers ``response_format="flac"`` (one FLAC stream per request, encoded on the device); without
+        it the name is refused as every unknown one is.
+        ``marks``: every request of this service asks for token marks -- ``submit``'s future then carries ``"marks"``: ``{"tokens":
         [(start_s, end_s)] per token}`` in seconds of the 24 kHz result (``timing.token_marks``; nominal positions) -- and
         ``word_groups(text, language, ids)``, when given, names the word of each token (-1: none; ``timing.word_groups`` over the
         phonemizer's separated symbols is the usual source), so that ``"marks"`` has ``"words"`` too.  ``timed()`` gives a view of the
@@ -132,12 +141,13 @@ class SpeechService:
         self.true_peak = checked_ceiling(true_peak, self.loudness)
         self.marks = bool(marks)
         self.word_groups = word_groups
+        self.flac = bool(flac)
 
     def timed(self, marks: bool = True) -> "SpeechService":
         """This service -- the same batcher, front end, target and ceiling -- with token marks on (or off): ``service.timed().submit(text)``
         gives a future whose result carries ``"marks"``.  ``submit`` and ``speak`` keep their signatures, so marks for a single request
         are asked for this way; ``submit_long`` and ``speak_long`` also take ``marks=`` themselves."""
-        return SpeechService(self.batcher, self.phonemize, self.max_text_length, self.loudness, self.true_peak, marks, self.word_groups)
+        return SpeechService(self.batcher, self.phonemize, self.max_text_length, self.loudness, self.true_peak, marks, self.word_groups, self.flac)
 
     def _timing_fields(self, text: str, language: str, ids) -> dict:
         """The request fields marks add: ``marks`` and, with a ``word_groups`` callable, the word of each token."""
@@ -151,7 +161,7 @@ class SpeechService:
         true-peak ceiling in dBTP (None: none).  A value that is no level, and a ceiling without a target, raise here, before
         anything is submitted.  ``submit`` and ``speak`` keep their positional signatures, so the target of a
         single request is named this way; ``submit_long`` and ``speak_long`` also take ``loudness=`` themselves."""
-        return SpeechService(self.batcher, self.phonemize, self.max_text_length, loudness, true_peak, self.marks, self.word_groups)
+        return SpeechService(self.batcher, self.phonemize, self.max_text_length, loudness, true_peak, self.marks, self.word_groups, self.flac)
 
     def submit(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
                speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None):
@@ -159,10 +169,11 @@ class SpeechService:
         then spoken with them, and ``voice`` only picks the language and the duration scale correction.  ``sample_rate``: the rate
         of the result's ``"audio"`` (8 or 16 kHz for telephony, 48 kHz for a browser); the batcher converts on the device.
         ``response_format``: None (float samples), ``"pcm"`` (raw s16le), ``"wav"`` (the same samples; ``speak`` adds the RIFF
-        header), ``"ulaw"`` / ``"alaw"`` (raw G.711), all at ``sample_rate`` and encoded on the device; an unknown name raises
+        header), ``"ulaw"`` / ``"alaw"`` (raw G.711), ``"flac"`` (a service built with ``flac=True``: one FLAC stream, a file as it
+        is), all at ``sample_rate`` and encoded on the device; an unknown name raises
         ``ValueError`` before anything is submitted.  With a loudness target (the service's, or ``levelled(target)``) the result
         also carries ``"loudness"`` -- the LUFS measured before the gain -- and ``"gain"``."""
-        encoding = response_encoding(response_format)
+        encoding = response_encoding(response_format, self.flac)
         if len(text) > self.max_text_length:
             raise ValueError(f"Text exceeds {self.max_text_length} characters")       # the handler's HTTP 400
         p = request_params(voice, speed, steps, solver)
@@ -203,7 +214,7 @@ class SpeechService:
         where the document has a target.  The result then also carries ``"true_peak"`` and ``"lra"``.
         ``marks``: whether the result carries ``"marks"`` -- ``{"tokens": one list of (start_s, end_s) per sentence}`` in the document's
         timeline, ``"words"`` too with the service's ``word_groups`` -- by default as the service says."""
-        encoding = response_encoding(response_format)
+        encoding = response_encoding(response_format, self.flac)
         from .loudness import check_target
         target = self.loudness if loudness is _SERVICE else check_target(loudness)
         ceiling = (self.true_peak if target is not None else None) if true_peak is _SERVICE else checked_ceiling(true_peak, target)

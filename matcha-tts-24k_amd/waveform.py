@@ -147,7 +147,7 @@ class _Plan:
     fade: int                       # samples faded at a joint and at a cut
     levels: Optional[list]          # per document
     rates: list
-    encs: Optional[list]            # format ids; None in a row that stays float (the encoder sees it as PCM16 of length 0)
+    encs: Optional[list]            # format ids; None in a row that stays float (an encoder sees the rows of another with length 0)
     dither: Optional[list]
     keys: Any
     targets: Optional[list]         # LUFS; NaN: measure the row and leave it alone
@@ -231,8 +231,8 @@ def _true_peak_ceilings(true_peak, targets, n):
 def _encodings_per_row(encoding, B):
     """``encoding=`` of ``to_waveforms`` as a list of B format ids or None per row; None when no row names one."""
     if encoding is None or isinstance(encoding, str):
-        return None if encoding is None else [AC.format_id(encoding)] * B
-    encs = [None if e is None else AC.format_id(e) for e in encoding]
+        return None if encoding is None else [AC.encoding_id(encoding)] * B
+    encs = [None if e is None else AC.encoding_id(e) for e in encoding]
     if len(encs) != B:
         raise ValueError(f"encoding is a name or one per row ({B}), got {len(encs)}")
     return encs if any(e is not None for e in encs) else None
@@ -261,12 +261,16 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     The band-limited output of a row normalised to a 0.95 peak may overshoot that peak slightly; nothing is re-normalised, but
     ``true_peak=`` (below) holds the level between the samples, which is what the conversion reconstructs, under a ceiling.
 
-    ``encoding``: None (float32 rows, as ever), a name -- ``"pcm16"`` (s16le), ``"ulaw"``, ``"alaw"`` (G.711) -- or one per row, where
-    None leaves a row float.  The rows that name one are encoded on the device (``audio_codec.encode``: one launch after the trim
+    ``encoding``: None (float32 rows, as ever), a name -- ``"pcm16"`` (s16le), ``"ulaw"``, ``"alaw"`` (G.711), ``"flac"`` (below) -- or one
+    per row, where None leaves a row float.  The rows that name one are encoded on the device (``audio_codec.encode``: one launch after the trim
     and the rate conversion, on their device lengths, no extra host read) and come back as 1-D uint8 host tensors: raw samples, no
     container, views of the batch's one host buffer of bytes; the one copy is then of bytes and the single synchronisation stays.
     ``dither`` (a bool, or one per row): TPDF dither on the PCM16 rows, the sequence of row b selected by ``dither_keys[b]`` (default
     0) and by nothing else, so a row's bytes do not depend on the batch it is in.  The keyword-only arguments follow a ``*``.
+    A ``"flac"`` row comes back as one complete FLAC stream (``audio_codec.encode_flac``: mono, 16 bits, blocks of 4096 samples, at
+    the row's converted rate), a file as it is, holding exactly the words ``"pcm16"`` gives for it -- dithered the same way when
+    ``dither`` is on.  Batches may mix the names: the PCM / G.711 launch and the FLAC call each see only their rows; the stream lengths
+    ride in the same ``meta`` copy, and only the columns of the longest stream are copied.
 
     ``documents``: None (every row is its own result, as ever: nothing below is launched or allocated), or the rows that belong
     together as a host list -- row counts in speaking order, or the CSR ``[0, n0, n0 + n1, ...]``; rows behind the last document are
@@ -348,13 +352,23 @@ def tail(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, **opt
         rows, meta["loud"] = _loudness_stage(rows, lengths, plan)
     if any(r != SAMPLE_RATE for r in plan.rates):
         rows, lengths = _convert_rows(rows, lengths, plan.rates)
+    flac = None
     if plan.encs is not None:
-        # one launch over the finished rows on their device lengths; rows without an encoding take part with length 0 and stay float
-        named = torch.tensor([e is not None for e in plan.encs], dtype=torch.bool, device=rows.device)
-        data, meta["nbytes"] = AC.encode(rows, torch.where(named, lengths, torch.zeros_like(lengths)), [AC.PCM16 if e is None else e for e in plan.encs],
-                                         dither=plan.dither if len(set(plan.dither)) > 1 else plan.dither[0], keys=plan.keys)
+        # one launch over the finished rows on their device lengths; rows without an encoding take part with length 0 and stay float.
+        # FLAC rows go through their own call (three launches), likewise: each encoder sees the other's rows with length 0
+        sampled = [e is not None and e != AC.FLAC for e in plan.encs]
+        streamed = [e == AC.FLAC for e in plan.encs]
+        dither = plan.dither if len(set(plan.dither)) > 1 else plan.dither[0]
+        if any(sampled) or not any(streamed):
+            named = torch.tensor(sampled, dtype=torch.bool, device=rows.device)
+            data, meta["nbytes"] = AC.encode(rows, torch.where(named, lengths, torch.zeros_like(lengths)), [e if on else AC.PCM16 for e, on in zip(plan.encs, sampled)],
+                                             dither=dither, keys=plan.keys)
+        if any(streamed):
+            mine = torch.tensor(streamed, dtype=torch.bool, device=rows.device)
+            flac, nbytes = AC.encode_flac(rows, torch.where(mine, lengths, torch.zeros_like(lengths)), plan.rates, dither=dither, keys=plan.keys)
+            meta["nbytes"] = torch.where(mine, nbytes, meta["nbytes"]) if data is not None else nbytes
     try:
-        out, starts = _ending(rows, lengths, plan, meta, data, T)
+        out, starts = _ending(rows, lengths, plan, meta, data, T, flac)
     except ValueError:
         verdict()                                                      # the timing plan's own verdict names the row and the reason
         raise
@@ -422,10 +436,11 @@ def _convert_rows(audio, lengths, rates):
     return wave, new_lengths
 
 
-def _ending(rows, lengths, plan, meta, data, T):
+def _ending(rows, lengths, plan, meta, data, T, flac=None):
     """The end of the tail: the ``meta`` words -- the result lengths, then the named sections the stages left -- in the batch's one
     device-to-host copy that waits for the stream, the refusals it shows, then one copy of the floats and/or one of the bytes, of
-    which the results are views.  Returns ``(Tail, starts)``: the start of every row inside its document (None without documents)."""
+    which the results are views.  ``data``: the rows ``audio_codec.encode`` wrote; ``flac``: those of ``encode_flac``, of which only
+    the columns of the longest stream are copied.  Returns ``(Tail, starts)``: the start of every row inside its document (None without documents)."""
     joined = plan.csr is not None
     words = {"got": lengths, **meta}
     flat = torch.cat(list(words.values())).cpu().tolist()              # waits for the stream: the batch's one synchronisation
@@ -439,13 +454,17 @@ def _ending(rows, lengths, plan, meta, data, T):
         if got[g] < 0:
             raise ValueError(f"to_waveforms: document {g} (rows {plan.csr[g]} to {plan.csr[g + 1] - 1}) could not be joined")
     # a joined buffer is as wide as the host's bound on a document: no more columns are copied than the longest result has
-    floats = coded = None
-    if data is None or not all(e is not None for e in plan.encs):
+    floats = coded = streams = None
+    if plan.encs is None or not all(e is not None for e in plan.encs):
         floats = rows[:, :max(got)].cpu() if joined else rows.cpu()
     if data is not None:
-        width = max(max(nb), 1) if joined else max(AC.BYTES_PER_SAMPLE[AC.PCM16 if e is None else e] for e in plan.encs) * rows.shape[1]
+        sampled = [g for g in range(plan.n) if plan.encs[g] not in (None, AC.FLAC)]
+        width = max([nb[g] for g in sampled] + [1]) if joined else max(AC.BYTES_PER_SAMPLE[AC.PCM16 if e is None else e] for e in plan.encs if e != AC.FLAC) * rows.shape[1]
         coded = data[:, :width].cpu() if width < data.shape[1] else data.cpu()
-    out = Tail([floats[g, :got[g]] if data is None or plan.encs[g] is None else coded[g, :nb[g]] for g in range(plan.n)])
+    if flac is not None:
+        streams = flac[:, :max(nb[g] for g in range(plan.n) if plan.encs[g] == AC.FLAC)].cpu()
+    pick = lambda g: floats[g, :got[g]] if plan.encs is None or plan.encs[g] is None else (streams if plan.encs[g] == AC.FLAC else coded)[g, :nb[g]]
+    out = Tail([pick(g) for g in range(plan.n)])
     if plan.segments:
         out.segments = [[(starts[b] / SAMPLE_RATE, (starts[b] + kept[b]) / SAMPLE_RATE) for b in range(plan.csr[g], plan.csr[g + 1])]
                         for g in range(plan.n)]
@@ -460,7 +479,7 @@ def finish_request(waveform, *, loudness=None, true_peak=None, report=False, sam
     """The tail of one request behind the normalisation and the trim, in the order of the batched tail: ``waveform`` 1-D float32 on
     the device at 24 kHz -> ``(host tensor, report)``.  The loudness step (``loudness`` a checked target in LUFS, its gain also limited
     by a ``true_peak`` ceiling in dBTP), the rate conversion, the encoding (``dither`` / ``dither_key`` as ``audio_codec.encode`` takes
-    them; raw uint8 samples).  ``report``: what the loudness step measured BEFORE the gain, ``(lufs, gain)`` -- the dict of
+    them; raw uint8 samples, or with ``"flac"`` one FLAC stream at the converted rate, ``audio_codec.encode_flac``).  ``report``: what the loudness step measured BEFORE the gain, ``(lufs, gain)`` -- the dict of
     ``loudness.normalize(return_meter=True)`` under a ceiling; the meter runs only then -- else None.  An empty waveform passes through."""
     rep, n, rate = None, waveform.numel(), int(sample_rate)
     if loudness is not None and n > 0:
@@ -474,7 +493,14 @@ def finish_request(waveform, *, loudness=None, true_peak=None, report=False, sam
     if rate != SAMPLE_RATE and n > 0:
         conv, _ = R.resample(waveform.reshape(1, -1), None, SAMPLE_RATE, rate, check=False)
         waveform = conv[0, :R.resampler(SAMPLE_RATE, rate, conv.device).out_length(n)]
-    if encoding is not None and n > 0:
+    if encoding is not None and AC.encoding_id(encoding) == AC.FLAC:           # a stream at any length: an empty one is its 42 header bytes
+        rows = waveform.reshape(1, -1) if n > 0 else torch.zeros(1, 4, dtype=torch.float32, device=waveform.device)
+        data, nbytes = AC.encode_flac(rows, [waveform.numel()], rate, dither=dither, keys=None if dither_key is None else [dither_key])
+        size = int(nbytes[0])
+        if size < 0:
+            raise ValueError(f"finish_request: a FLAC stream names its rate in 20 bits, sample_rate = {rate} is outside [1, 1048575]")
+        waveform = data[0, :size]
+    elif encoding is not None and n > 0:
         data, _ = AC.encode(waveform.reshape(1, -1), None, encoding, dither=dither, keys=None if dither_key is None else [dither_key])
         waveform = data[0, :waveform.numel() * AC.BYTES_PER_SAMPLE[AC.format_id(encoding)]]
     elif encoding is not None:

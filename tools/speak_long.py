@@ -8,7 +8,7 @@
 ``speak`` cuts TEXT.txt with ``longform.split_text`` and phonemizes each sentence with the reference installation's phonemizer
 (``process_text``) when that imports.  Where it does not, ``--segments-file`` takes the text already cut and phonemized: one
 segment per line, whitespace-separated phoneme ids, then ``|`` and the pause behind it in milliseconds (``12 7 33 | 300``), as
-tools/align.py takes ids.  The document goes through ``FrameBudgetBatcher.submit_document``; OUT.wav is RIFF PCM16 at
+tools/align.py takes ids.  The document goes through ``FrameBudgetBatcher.submit_document``; OUT.wav is RIFF PCM16 (an OUT.flac: FLAC) at
 ``--sample-rate``, encoded on the device.  ``--captions FILE.vtt|.srt`` writes one cue per sentence from the result's ``segments``;
 ``--marks FILE.json`` writes when each token (and, with the phonemizer here, each word) is spoken, in seconds of the 24 kHz join.  ``--loudness LUFS`` brings the joined document to that integrated loudness (ITU-R BS.1770,
 one gain for the document, the sample peak held at 0.95) on the device, ahead of the rate conversion.  The sentences' times are printed.
@@ -91,12 +91,13 @@ def speak(args) -> int:
         extra["marks"] = True
         if groups is not None:
             extra["word_groups"] = groups
+    flac = Path(args.out).suffix.lower() == ".flac"                   # OUT.flac: the document as one FLAC stream, encoded on the device
     with bt.FrameBudgetBatcher(model, max_batch=max(32, len(ids)), max_tokens=max(8192, len(ids) * max(len(s) for s in ids)),
                                vocoder=vocoder, fade_ms=args.fade_ms) as q:
         res = q.submit_document(ids, pauses, speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver, n_timesteps=p.n_timesteps,
                                 scale_correction=p.scale_correction, length_scale=p.length_scale, sample_rate=args.sample_rate,
-                                encoding="pcm16", level=args.level, **extra).result()
-    Path(args.out).write_bytes(sv.response_body(res, "wav", args.sample_rate))
+                                encoding="flac" if flac else "pcm16", level=args.level, **extra).result()
+    Path(args.out).write_bytes(sv.response_body(res, "flac" if flac else "wav", args.sample_rate))
     for n, (t0, t1) in enumerate(res["segments"]):
         print(f"{n:4d}  {t0:9.3f} s .. {t1:9.3f} s")
     if args.captions is not None:
@@ -111,7 +112,8 @@ def speak(args) -> int:
         print(f"loudness {res['loudness']:.2f} LUFS as synthesised, gain {res['gain']:.4f} towards {args.loudness:.2f} LUFS")
     if "true_peak" in res:
         print(f"true peak {res['true_peak']:.2f} dBTP as synthesised (ceiling {args.true_peak:.2f} dBTP), loudness range {res['lra']:.2f} LU")
-    print(f"wrote {args.out}: {res['audio'].numel() // 2} samples at {args.sample_rate} Hz, {len(ids)} sentences")
+    size = f"{res['audio'].numel()} bytes of FLAC" if flac else f"{res['audio'].numel() // 2} samples"
+    print(f"wrote {args.out}: {size} at {args.sample_rate} Hz, {len(ids)} sentences")
     return 0
 
 
