@@ -25,14 +25,42 @@ import os
 import threading
 import time
 from concurrent.futures import Future
-from dataclasses import dataclass, field
+from dataclasses import KW_ONLY, dataclass, field, fields
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 
 @dataclass
-class Request:
+class _Unit:
+    """What a unit of the queue -- a ``Request`` or a ``Document`` -- wants out, declared and checked once; keyword-only, so the fields of
+    a unit itself come first.  A document's rows are requests too: what THEY say here is not looked at."""
+    _: KW_ONLY
+    sample_rate: int = 24000                # rate of the result's "audio" (with a vocoder); anything else is converted on the device and named in the result
+    encoding: Optional[str] = None          # "pcm16" / "ulaw" / "alaw": the result's "audio" is then raw bytes (a 1-D uint8 tensor) encoded on the device, and named in the result; "flac": one complete FLAC stream (audio_codec.encode_flac)
+    dither: bool = False                    # TPDF dither on a "pcm16" result
+    dither_key: int = 0                     # selects the dither sequence: a field of the unit, so its bytes do not depend on who shared its batch
+    loudness: Optional[float] = None        # target in LUFS (BS.1770 integrated loudness) the "audio" -- of a document: the JOINED audio, one gain -- is brought to on the device at 24 kHz; the result then carries "loudness" (measured, before the gain) and "gain"
+    true_peak: Optional[float] = None       # ceiling in dBTP on the true peak of the levelled "audio" (needs ``loudness``); the result then also carries "true_peak" (dBTP, measured before the gain) and "lra"
+    marks: bool = False                     # the result then carries "marks": {"tokens": [(start_s, end_s)] per token -- of a document: one such list per sentence, in its timeline -- (+ "words" with ``word_groups``)}, in seconds at 24 kHz
+    future: Future = field(default_factory=Future, repr=False)
+    t_submit: float = field(default_factory=time.monotonic, repr=False)
+
+    def __post_init__(self):                # (a wrong field fails its own unit here, not the batch it would have joined)
+        if self.encoding is not None:
+            from .audio_codec import encoding_id
+            encoding_id(self.encoding)
+        if self.loudness is not None or self.true_peak is not None:
+            from .loudness import check_ceiling, check_target
+            self.loudness = check_target(self.loudness)
+            self.true_peak = check_ceiling(self.true_peak, self.loudness)
+
+
+OUTPUT_FIELDS = tuple(f.name for f in fields(_Unit) if f.repr)     # sample_rate ... marks: all but the queue's own two
+
+
+@dataclass
+class Request(_Unit):
     ids: Sequence[int]                      # phoneme ids of one utterance
     speaker: int = 0
     voice_mix: Optional[Sequence[Tuple[int, float]]] = None    # [(id, weight), ...] as reference server.py:96-101; overrides speaker
@@ -42,23 +70,14 @@ class Request:
     scale_correction: float = 1.0
     length_scale: float = 1.0
     durations: Optional[Sequence[float]] = None    # fine frames per token (e.g. ``align(...)["durations"]``) instead of the predictor's; length_scale still applies
-    sample_rate: int = 24000                # rate of the result's "audio" (with a vocoder); anything else is converted on the device and named in the result
-    encoding: Optional[str] = None          # "pcm16" / "ulaw" / "alaw": the result's "audio" is then raw bytes (a 1-D uint8 tensor) encoded on the device, and named in the result; "flac": one complete FLAC stream (audio_codec.encode_flac)
-    dither: bool = False                    # TPDF dither on a "pcm16" result
-    dither_key: int = 0                     # selects the dither sequence: a field of the request, so its bytes do not depend on who shared its batch
-    loudness: Optional[float] = None        # target in LUFS (BS.1770 integrated loudness) the "audio" is brought to on the device at 24 kHz; the result then carries "loudness" (measured, before the gain) and "gain"
-    true_peak: Optional[float] = None       # ceiling in dBTP on the true peak of the levelled "audio" (needs ``loudness``); the result then also carries "true_peak" (dBTP, measured before the gain) and "lra"
     token_scale: Optional[Sequence[float]] = None    # a rate per token, inside [0, 16]: its duration is multiplied by it (exactly 0 drops the token)
     token_extend: Optional[Sequence[float]] = None   # fine frames added to each token's duration, inside [-4096, 4096]
     breaks: Optional[Sequence[Tuple[int, float]]] = None    # [(token, pause_ms), ...]: a pause cut into the audio after that token; token indices strictly increase
-    marks: bool = False                     # the result then carries "marks": {"tokens": [(start_s, end_s)] per token (+ "words" with ``word_groups``)}, in seconds at 24 kHz
     word_groups: Optional[Sequence[int]] = None      # the word of each token (-1: none; ``timing.word_groups``): "marks" then has "words" too
-    future: Future = field(default_factory=Future, repr=False)
-    t_submit: float = field(default_factory=time.monotonic, repr=False)
 
     def __post_init__(self):
         if self.token_scale is not None or self.token_extend is not None or self.breaks is not None or self.word_groups is not None:
-            from .timing import check_breaks, check_shaping      # (a wrong field fails its own request here, not the batch it would have joined)
+            from .timing import check_breaks, check_shaping
             for name in ("token_scale", "token_extend", "word_groups"):
                 v = getattr(self, name)
                 if v is not None and len(v) != len(self.ids):
@@ -67,13 +86,7 @@ class Request:
             check_shaping(None if self.token_extend is None else list(self.token_extend), "token_extend")
             if self.breaks is not None:
                 self.breaks = check_breaks(self.breaks, len(self.ids), what="a request's breaks")
-        if self.encoding is not None:       # (an unknown name fails its own request here, not the batch it would have joined)
-            from .audio_codec import encoding_id
-            encoding_id(self.encoding)
-        if self.loudness is not None:       # (so does a target that is no level)
-            from .loudness import check_target
-            self.loudness = check_target(self.loudness)
-        self.true_peak = _checked_ceiling(self.true_peak, self.loudness)
+        super().__post_init__()
 
     @property
     def group(self) -> Tuple[Any, ...]:
@@ -91,97 +104,19 @@ def duration_rows(batch: List[Request]) -> Optional[List[Optional[Sequence[float
     return [r.durations for r in batch]
 
 
-def timing_fields(rows: List[Request], units: Optional[List[Any]] = None) -> Optional[Dict[str, Any]]:
-    """What a batch asks of token timing, or None when no row and no unit asks anything (the calls are then exactly those made before
-    there was a choice): ``token_scale`` / ``token_extend`` as ``synthesise`` takes them (one entry per row, None = leave it alone; None
-    when no row names one), ``breaks`` as ``to_waveforms`` takes them (None when no row has one) and ``marks``, whether a unit wants
-    its marks back.  Pure function: unit-tested on the CPU."""
-    scale = [r.token_scale for r in rows]
-    extend = [r.token_extend for r in rows]
-    breaks = [list(r.breaks) if r.breaks else None for r in rows]
-    marks = any(bool(u.marks) for u in (rows if units is None else units))
-    out = dict(token_scale=scale if any(v is not None for v in scale) else None,
-               token_extend=extend if any(v is not None for v in extend) else None,
-               breaks=breaks if any(v is not None for v in breaks) else None, marks=marks)
-    return out if marks or any(out[k] is not None for k in ("token_scale", "token_extend", "breaks")) else None
-
-
-def shaping_kwargs(timing: Optional[Dict[str, Any]]) -> Dict[str, Any]:
-    """The keyword arguments ``timing_fields`` adds to a ``synthesise`` call."""
-    if timing is None:
-        return {}
-    kw = {k: timing[k] for k in ("token_scale", "token_extend") if timing[k] is not None}
-    if timing["marks"] or timing["breaks"] is not None:
+def shaping_kwargs(rows: List[Request], units: Optional[List[Any]] = None) -> Dict[str, Any]:
+    """The keyword arguments token timing adds to a ``synthesise`` call over ``rows``; none when nobody asks anything (the call is then
+    exactly the one made before there was a choice).  ``token_scale`` / ``token_extend``: one entry per row (None = leave it alone), when
+    a row names one; ``return_timing`` when a row has a break or a unit (by default the rows are the units) wants its marks: the tail
+    then needs ``token_ends``.  Pure function: unit-tested on the CPU."""
+    kw = {}
+    for name in ("token_scale", "token_extend"):
+        vals = [getattr(r, name) for r in rows]
+        if any(v is not None for v in vals):
+            kw[name] = vals
+    if any(r.breaks for r in rows) or any(u.marks for u in (rows if units is None else units)):
         kw["return_timing"] = True
     return kw
-
-
-def marks_into(r: Dict[str, Any], unit, tokens) -> None:
-    """``r["marks"]`` of a unit that asked for them: ``tokens`` are its token marks -- one list for a request, one per sentence for a
-    document -- and ``"words"`` appears when its rows bring ``word_groups``."""
-    if not unit.marks:
-        return
-    from .timing import word_marks
-    if isinstance(unit, Document):
-        r["marks"] = {"tokens": tokens}
-        if all(row.word_groups is not None for row in unit.rows):
-            r["marks"]["words"] = [word_marks(t, row.word_groups) for t, row in zip(tokens, unit.rows)]
-    else:
-        r["marks"] = {"tokens": tokens}
-        if unit.word_groups is not None:
-            r["marks"]["words"] = word_marks(tokens, unit.word_groups)
-
-
-def encoding_fields(batch: List[Request]):
-    """``(encodings, dithers, dither_keys)`` of a batch as ``waveforms_into`` takes them; three None when no request names an
-    encoding (the call is then exactly the one made before there was a choice).  Pure function: unit-tested on the CPU."""
-    if all(r.encoding is None for r in batch):
-        return None, None, None
-    return [r.encoding for r in batch], [bool(r.dither) for r in batch], [int(r.dither_key) for r in batch]
-
-
-def loudness_field(batch: List[Any]) -> Optional[List[Optional[float]]]:
-    """The loudness targets of a batch of units as ``waveforms_into`` / ``to_waveforms(loudness=...)`` take them: one entry per unit,
-    None for a unit without a target (its row runs with a NaN target and keeps its bits); None when no unit names one (the call is
-    then exactly the one made before there was a choice).  Pure function: unit-tested on the CPU."""
-    if all(u.loudness is None for u in batch):
-        return None
-    return [None if u.loudness is None else float(u.loudness) for u in batch]
-
-
-def _checked_ceiling(true_peak, loudness):
-    """``true_peak`` of a request or a document as a float or None; it limits a gain, so one without a target is refused."""
-    if true_peak is None:
-        return None
-    from .loudness import check_true_peak
-    ceiling = check_true_peak(true_peak)
-    if loudness is None:
-        raise ValueError(f"true_peak = {true_peak!r} limits the gain towards a loudness target, and the request names none (loudness=)")
-    return ceiling
-
-
-def true_peak_field(batch: List[Any]) -> Optional[List[Optional[float]]]:
-    """The true-peak ceilings of a batch of units as ``waveforms_into`` / ``to_waveforms(true_peak=...)`` take them: one entry in dBTP
-    per unit, None for a unit that names none; None when no unit names one (the call is then exactly the one made before there was
-    a choice).  Pure function: unit-tested on the CPU."""
-    if all(u.true_peak is None for u in batch):
-        return None
-    return [None if u.true_peak is None else float(u.true_peak) for u in batch]
-
-
-def report_into(r: Dict[str, Any], rep, target, ceiling=None) -> None:
-    """What a levelled result says of its loudness stage: ``"loudness"`` (LUFS before the gain) and ``"gain"`` from ``rep`` -- a
-    ``(lufs, gain)`` pair, or the dict of ``to_waveforms(return_meter=True)`` -- and, for a unit that named a true-peak ceiling,
-    ``"true_peak"`` in dBTP (before the gain) and ``"lra"`` in LU.  Pure function: unit-tested on the CPU."""
-    if target is None or rep is None:
-        return
-    if isinstance(rep, dict):
-        r["loudness"], r["gain"] = float(rep["lufs"]), float(rep["gain"])
-        if ceiling is not None:
-            from .loudness import dbtp
-            r["true_peak"], r["lra"] = dbtp(rep["true_peak"]), float(rep["lra"])
-    else:
-        r["loudness"], r["gain"] = float(rep[0]), float(rep[1])
 
 
 def plan_batch(waiting: List[Request], max_batch: int, max_tokens: int) -> List[int]:
@@ -205,28 +140,17 @@ def plan_batch(waiting: List[Request], max_batch: int, max_tokens: int) -> List[
 
 
 @dataclass
-class Document:
+class Document(_Unit):
     """A text longer than one utterance: its sentences as ``rows`` (one ``Request`` each, in speaking order; what they say about the
-    output -- rate, encoding, dither -- is not looked at) and the pause after each.  The rows run as rows of ONE ragged batch and are
-    joined on the device (``inference.to_waveforms(documents=...)``); the document has one future and one result."""
+    output -- rate, encoding, dither, level, marks -- is not looked at: the document says it once, for the joined audio) and the pause
+    after each.  The rows run as rows of ONE ragged batch and are joined on the device (``inference.to_waveforms(documents=...)``);
+    the document has one future and one result."""
     rows: List[Request]
     pauses_ms: Sequence[float]              # silence after each row; the last entry is ignored
     level: str = "document"                 # "document": one gain for the whole text; "sentence": each row keeps its own
-    sample_rate: int = 24000                # of the joined "audio": the fields of the same names of a Request, once per document
-    encoding: Optional[str] = None
-    dither: bool = False
-    dither_key: int = 0
-    loudness: Optional[float] = None        # target in LUFS of the JOINED audio: one gain per document
-    true_peak: Optional[float] = None       # ceiling in dBTP on the true peak of the joined, levelled audio (needs ``loudness``)
-    marks: bool = False                     # the result then carries "marks": {"tokens": one list per sentence (+ "words")}, in the document's timeline
-    future: Future = field(default_factory=Future, repr=False)
-    t_submit: float = field(default_factory=time.monotonic, repr=False)
 
     def __post_init__(self):
-        if self.loudness is not None:
-            from .loudness import check_target
-            self.loudness = check_target(self.loudness)
-        self.true_peak = _checked_ceiling(self.true_peak, self.loudness)
+        super().__post_init__()
         if len(self.rows) == 0:
             raise ValueError("a document has at least one segment")
         if any(len(r.ids) == 0 for r in self.rows):
@@ -239,9 +163,6 @@ class Document:
             raise ValueError(f"level is 'document' or 'sentence', got {self.level!r}")
         if len({r.group for r in self.rows}) != 1:
             raise ValueError("the rows of a document share solver and n_timesteps")
-        if self.encoding is not None:
-            from .audio_codec import encoding_id
-            encoding_id(self.encoding)
 
     @property
     def group(self) -> Tuple[Any, ...]:
@@ -288,7 +209,57 @@ def plan_units(waiting: List[Any], max_batch: int, max_tokens: int) -> List[int]
     return sorted(chosen)
 
 
-class FrameBudgetBatcher:
+class _Queue:
+    """The producer side the two batchers share: the waiting units under one condition, ``submit``'s checks, ``close`` and the context
+    manager.  A batcher sets its own state, then ``_open``s -- which starts its worker, ``_loop`` -- last."""
+
+    def _open(self, model, vocoder, max_batch: int, max_tokens: int, name: str) -> None:
+        self.model = model
+        self.vocoder = vocoder
+        self.wave_batch = os.environ.get("MTTS_WAVE_BATCH", "1") != "0"      # (read here, per batcher)
+        self.max_batch = int(max_batch)
+        self.max_tokens = int(max_tokens)
+        self._waiting: List[Any] = []
+        self._cv = threading.Condition()
+        self._stop = False
+        self.batches_run = 0
+        self.busy_s = 0.0                   # wall time the worker spent inside batches (device work + its host side): a load gauge
+        self._thread = threading.Thread(target=self._loop, name=name, daemon=True)
+        self._thread.start()
+
+    def _request(self, ids: Sequence[int], fields: Dict[str, Any]) -> Request:
+        """The checked ``Request`` of a ``submit``: a wrong one fails here, not the batch it would have joined."""
+        if len(ids) == 0:
+            raise ValueError("empty utterance")
+        if len(ids) > self.max_tokens:
+            raise ValueError(f"utterance of {len(ids)} tokens exceeds the batch budget of {self.max_tokens}")
+        r = Request(ids=list(ids), **fields)
+        duration_rows([r])
+        return r
+
+    def _enqueue(self, unit) -> Future:
+        with self._cv:
+            if self._stop:
+                raise RuntimeError("batcher is closed")
+            self._waiting.append(unit)
+            self._cv.notify()
+        return unit.future
+
+    def close(self) -> None:
+        """Stop taking requests; everything submitted before is served."""
+        with self._cv:
+            self._stop = True
+            self._cv.notify()
+        self._thread.join()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class FrameBudgetBatcher(_Queue):
     """``submit()`` from any thread; results arrive on the request's future as ``{"mel": [n_feats, T_b], "mel_length": T_b}``."""
 
     def __init__(self, model, max_batch: int = 32, max_tokens: int = 8192, max_wait_ms: float = 2.0,
@@ -298,36 +269,14 @@ class FrameBudgetBatcher:
         mel.  The whole batch goes through ``inference.to_waveforms`` (ragged decode + finish on the device, one copy, one
         synchronisation); ``MTTS_WAVE_BATCH=0``, read here per batcher, restores the per-request loop on exact-length mels.
         ``fade_ms``: the fade at the joints between the sentences of a document (``submit_document``)."""
-        self.model = model
-        self.vocoder = vocoder
         self.fade_ms = float(fade_ms)
-        self.wave_batch = os.environ.get("MTTS_WAVE_BATCH", "1") != "0"
-        self.max_batch = int(max_batch)
-        self.max_tokens = int(max_tokens)
         self.max_wait = float(max_wait_ms) / 1e3
         self._run = run_batch or self._run_on_model
-        self._waiting: List[Request] = []
-        self._cv = threading.Condition()
-        self._stop = False
-        self.batches_run = 0
-        self.busy_s = 0.0                   # wall time the worker spent inside batches (device work + its host side): a load gauge
-        self._thread = threading.Thread(target=self._loop, name="mtts-batcher", daemon=True)
-        self._thread.start()
+        self._open(model, vocoder, max_batch, max_tokens, "mtts-batcher")
 
     # ------------------------------------------------------------------ producer side
     def submit(self, ids: Sequence[int], **kw) -> Future:
-        if len(ids) == 0:
-            raise ValueError("empty utterance")
-        if len(ids) > self.max_tokens:
-            raise ValueError(f"utterance of {len(ids)} tokens exceeds the batch budget of {self.max_tokens}")
-        r = Request(ids=list(ids), **kw)
-        duration_rows([r])                  # (a wrong count fails its own request here, not the batch it would have joined)
-        with self._cv:
-            if self._stop:
-                raise RuntimeError("batcher is closed")
-            self._waiting.append(r)
-            self._cv.notify()
-        return r.future
+        return self._enqueue(self._request(ids, kw))
 
     def submit_document(self, segments_ids: Sequence[Sequence[int]], pauses_ms: Sequence[float], **request_fields) -> Future:
         """A text of several utterances: ``segments_ids`` the phoneme ids of each segment in speaking order, ``pauses_ms`` the silence
@@ -340,8 +289,7 @@ class FrameBudgetBatcher:
         future: ``{"audio", "segments": [(start_s, end_s)] per segment, "mel_lengths"}``, plus ``"sample_rate"`` / ``"encoding"``
         when asked.  A document is admitted whole or not at all: more segments than ``max_batch`` or segments x longest above
         ``max_tokens`` raises ``ValueError`` here, as does an empty segment."""
-        once = {k: request_fields.pop(k) for k in ("level", "sample_rate", "encoding", "dither", "dither_key", "loudness", "true_peak", "marks")
-                if k in request_fields}
+        once = {k: request_fields.pop(k) for k in ("level", *OUTPUT_FIELDS) if k in request_fields}
         segments = [list(ids) for ids in segments_ids]
         if any(len(ids) == 0 for ids in segments):
             raise ValueError("empty segment in a document")
@@ -359,24 +307,7 @@ class FrameBudgetBatcher:
             raise ValueError(f"a document of {n} segments exceeds the batch of {self.max_batch} utterances")
         if n * longest > self.max_tokens:
             raise ValueError(f"a document of {n} segments of up to {longest} tokens exceeds the batch budget of {self.max_tokens}")
-        with self._cv:
-            if self._stop:
-                raise RuntimeError("batcher is closed")
-            self._waiting.append(d)
-            self._cv.notify()
-        return d.future
-
-    def close(self) -> None:
-        with self._cv:
-            self._stop = True
-            self._cv.notify()
-        self._thread.join()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._enqueue(d)
 
     # ------------------------------------------------------------------ worker
     def _loop(self) -> None:
@@ -426,143 +357,113 @@ def request_inputs(model, batch: List[Request]):
     return x.to(dev), x_len.to(dev), emb
 
 
-def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_batch: bool, sample_rates: Optional[Sequence[int]] = None,
-                   encodings: Optional[Sequence[Optional[str]]] = None, dithers: Optional[Sequence[bool]] = None,
-                   dither_keys: Optional[Sequence[int]] = None, *, timing: Optional[Dict[str, Any]] = None,
-                   true_peak: Optional[Sequence[Optional[float]]] = None,
-                   loudness: Optional[Sequence[Optional[float]]] = None) -> None:
-    """``res[b]["audio"]`` for a batch of finished mels (``mel`` [B, n_feats, T], ``mel_lengths`` [B]; ``res[b]["mel"]`` the exact-length
-    rows).  ``sample_rates``: one rate per request (default 24 kHz); rows that ask for another rate are converted on the device after
-    the normalisation and the trim (``inference.to_waveforms``) and carry ``res[b]["sample_rate"]`` beside ``"audio"``.
-    ``encodings``: one name or None per request; a row that names one is encoded on the device after that (``audio_codec.encode``,
-    with the request's ``dithers`` flag and ``dither_keys`` entry), its ``"audio"`` is a 1-D uint8 tensor of raw samples -- of one
-    FLAC stream, a file as it is, for ``"flac"`` (``audio_codec.encode_flac``) -- and it carries ``res[b]["encoding"]``.  ``loudness``: one target in LUFS or None per request (``loudness_field``); a row that names one is
-    brought to it on the device at 24 kHz, ahead of the conversion and the encoder (``inference.to_waveforms(loudness=...)``), and
-    carries ``res[b]["loudness"]`` -- the LUFS measured before the gain -- and ``res[b]["gain"]``; the other rows keep their bits.
-    ``true_peak``: one ceiling in dBTP or None per request (``true_peak_field``); a row that names one has its gain also limited by its
-    true peak (``inference.to_waveforms(true_peak=...)``) and carries ``res[b]["true_peak"]`` (dBTP, before the gain) and ``res[b]["lra"]``.
-    A float result at 24 kHz without a target keeps exactly the keys it had before there was a choice.  ``true_peak`` and ``loudness``
-    are named by every caller: they follow a ``*``, so that a positional list of levels cannot land in the wrong one.
-    ``timing``: None, or ``dict(token_ends=, x_lengths=, breaks=, units=)`` -- the timing plan runs in the batched tail
-    (``inference.to_waveforms(token_ends=...)``) and ``res[b]["marks"]`` is filled for the units that asked (``marks_into``)."""
-    if vocoder is None:
-        return
-    if timing is not None and not wave_batch:
-        raise ValueError("marks and breaks run in the batched tail: they need wave_batch=True")
-    B = len(res)
-    rates = [24000] * B if sample_rates is None else [int(v) for v in sample_rates]
-    encs = [None] * B if encodings is None else list(encodings)
-    dith = [False] * B if dithers is None else [bool(v) for v in dithers]
-    keys = [0] * B if dither_keys is None else [int(v) for v in dither_keys]
-    loud = [None] * B if loudness is None else list(loudness)
-    levelled = any(v is not None for v in loud)
-    ceil = [None] * B if true_peak is None else list(true_peak)
-    report = [None] * B
-    if wave_batch:
-        from .waveform import tail
-        # encodings and ceilings that are all None are "stage not run" to the plan; a report alone would run the meter, so it is
-        # asked for only where a row is levelled
-        extra = {}
-        if levelled:
-            extra.update(loudness=loud, return_loudness=True, true_peak=ceil, return_meter=any(v is not None for v in ceil))
-        if timing is not None:
-            extra.update(token_ends=timing["token_ends"], x_lengths=timing["x_lengths"], breaks=timing["breaks"], return_marks=True)
-        out = tail(mel, mel_lengths, vocoder, sample_rate=rates, encoding=encs, dither=dith, dither_keys=keys, **extra)
-        report = report if out.report is None else out.report
-        for r, a in zip(res, out.rows):
-            r["audio"] = a
-        if timing is not None:
-            for r, u, tokens in zip(res, timing["units"], out.marks):
-                marks_into(r, u, tokens)
-    else:
-        from .waveform import _waveform_on_device, finish_request, trim_trailing_silence
-        for b, (r, rate, enc, on, key) in enumerate(zip(res, rates, encs, dith, keys)):
-            a = trim_trailing_silence(_waveform_on_device(r["mel"][None], vocoder).squeeze())
-            r["audio"], report[b] = finish_request(a, loudness=loud[b], true_peak=ceil[b], report=True, sample_rate=rate, encoding=enc,
-                                                   dither=on, dither_key=key)
-    for r, rate, enc, target, rep, c in zip(res, rates, encs, loud, report, ceil):
-        if rate != 24000:
-            r["sample_rate"] = rate
-        if enc is not None:
-            r["encoding"] = enc
-        report_into(r, rep, target, c)
+def tail_options(units: List[Any], timing=None, fade_ms: float = 5.0) -> Dict[str, Any]:
+    """The keyword arguments of ``waveform.tail`` for a batch of units (``Request | Document``), one entry per unit.  A stage's keywords
+    appear only when a unit asks for that stage -- another rate, an encoding, a loudness target (a unit without one passes None: its
+    row is measured with a NaN target and keeps its bits), a true-peak ceiling -- so a batch in which nobody asks makes exactly the
+    call made before there was a choice.  ``timing``: None, or ``(token_ends, x_lengths)`` of the ``synthesise`` call that was asked for
+    them (``shaping_kwargs``): the timing plan then runs, with the rows' breaks.  Only a batch that holds a ``Document`` goes through
+    the join: a plain request is a document of one row there (no joint, its own gain: its samples are its batch-of-one samples).
+    Pure function: unit-tested on the CPU."""
+    asked = lambda name: any(getattr(u, name) is not None for u in units)
+    kw: Dict[str, Any] = {}
+    if any(int(u.sample_rate) != 24000 for u in units):
+        kw.update(sample_rate=[int(u.sample_rate) for u in units])
+    if asked("encoding"):
+        kw.update(encoding=[u.encoding for u in units], dither=[bool(u.dither) for u in units], dither_keys=[int(u.dither_key) for u in units])
+    if asked("loudness"):                   # (a report alone would run the meter: it is asked for only where a unit is levelled)
+        kw.update(loudness=[u.loudness for u in units], return_loudness=True)
+        if asked("true_peak"):
+            kw.update(true_peak=[u.true_peak for u in units], return_meter=True)
+    if timing is not None:
+        breaks = [list(r.breaks) if r.breaks else None for u in units for r in unit_rows(u)]
+        kw.update(token_ends=timing[0], x_lengths=timing[1], breaks=breaks if any(breaks) else None, return_marks=True)
+    if any(isinstance(u, Document) for u in units):
+        kw.update(documents=[len(unit_rows(u)) for u in units], gaps=[g for u in units for g in (u.gaps() if isinstance(u, Document) else [0])],
+                  level=[u.level if isinstance(u, Document) else "sentence" for u in units], fade_ms=fade_ms, return_segments=True)
+    return kw
 
 
-def synthesise_batch(model, batch: List[Any], vocoder=None, wave_batch: bool = True, fade_ms: float = 5.0) -> List[Dict[str, Any]]:
-    """One ``synthesise(per_request_padding=True)`` call for requests of one group, and their waveforms.  A batch that holds a
-    ``Document`` runs the rows of all its units in that one call and joins each document's rows on the device
-    (``synthesise_units``); without one this is the call it always was."""
-    if any(isinstance(u, Document) for u in batch):
-        return synthesise_units(model, batch, vocoder, fade_ms)
-    B = len(batch)
-    x, x_len, emb = request_inputs(model, batch)
-    head = batch[0]
-    model.decoder.solver = head.solver
-    timing = timing_fields(batch)
-    if timing is not None and vocoder is None and (timing["marks"] or timing["breaks"] is not None):
-        raise ValueError("marks and breaks need a vocoder: they are positions in the audio")
-    out = model.synthesise(x, x_len, head.n_timesteps, speaker_embeddings=emb,
-                           scale_correction=[r.scale_correction for r in batch],
-                           length_scale=[r.length_scale for r in batch], per_request_padding=True,
-                           durations=duration_rows(batch), **shaping_kwargs(timing))
-    lens = out["mel_lengths"].tolist()
-    res = [{"mel": out["mel"][b, :, :int(lens[b])], "mel_length": int(lens[b])} for b in range(B)]
-    tail = {}
-    if timing is not None and "token_ends" in out:
-        tail["timing"] = dict(token_ends=out["token_ends"], x_lengths=x_len, breaks=timing["breaks"], units=batch)
-    waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch, [r.sample_rate for r in batch], *encoding_fields(batch),
-                   **tail, loudness=loudness_field(batch), true_peak=true_peak_field(batch))
-    return res
-
-
-def synthesise_units(model, units: List[Any], vocoder, fade_ms: float = 5.0) -> List[Dict[str, Any]]:
-    """``synthesise_batch`` for a batch with documents: the units flattened to rows, one ``synthesise`` call, then
-    ``to_waveforms(documents=...)`` -- a plain request is a document of one row there (no joint, its own gain: its samples are its
-    batch-of-one samples) -- and one result per unit.  A plain request keeps exactly the keys and values it has without documents in
-    its batch; a document gets ``{"audio", "segments", "mel_lengths"}``.  The join is part of the batched tail: there is no
-    per-request loop for it, and no host-side join."""
-    if vocoder is None:
-        raise ValueError("a document needs a vocoder: its result is the joined audio")
-    from .waveform import tail
-    rows = [r for u in units for r in unit_rows(u)]
-    x, x_len, emb = request_inputs(model, rows)
-    head = rows[0]
-    model.decoder.solver = head.solver
-    timing = timing_fields(rows, units)
-    out = model.synthesise(x, x_len, head.n_timesteps, speaker_embeddings=emb,
-                           scale_correction=[r.scale_correction for r in rows],
-                           length_scale=[r.length_scale for r in rows], per_request_padding=True,
-                           durations=duration_rows(rows), **shaping_kwargs(timing))
-    lens = [int(v) for v in out["mel_lengths"].tolist()]
-    counts = [len(unit_rows(u)) for u in units]
-    gaps = [g for u in units for g in (u.gaps() if isinstance(u, Document) else [0])]
-    encs, dith, keys = encoding_fields(units)
-    extra = {} if encs is None else dict(encoding=encs, dither=dith, dither_keys=keys)
-    if loudness_field(units) is not None:
-        extra.update(loudness=loudness_field(units), return_loudness=True, true_peak=true_peak_field(units),
-                     return_meter=true_peak_field(units) is not None)
-    timed = timing is not None and "token_ends" in out
-    if timed:
-        extra.update(token_ends=out["token_ends"], x_lengths=x_len, breaks=timing["breaks"], return_marks=True)
-    out_w = tail(out["mel"], out["mel_lengths"], vocoder, sample_rate=[int(u.sample_rate) for u in units], documents=counts, gaps=gaps,
-                 fade_ms=fade_ms, level=[u.level if isinstance(u, Document) else "sentence" for u in units], return_segments=True,
-                 **extra)
-    report = [None] * len(units) if out_w.report is None else out_w.report
-    res, b = [], 0
-    for u, n, a, seg, rep in zip(units, counts, out_w.rows, out_w.segments, report):
+def results_into(res: List[Dict[str, Any]], units: List[Any], out) -> None:
+    """What a ``Tail`` leaves in the result of each unit: ``"audio"``; a document's ``"segments"``; ``"sample_rate"`` / ``"encoding"`` when
+    the unit named one; for a levelled unit ``"loudness"`` (LUFS before the gain) and ``"gain"`` from its report -- a ``(lufs, gain)`` pair
+    or the meter's dict -- and, under its own ceiling, ``"true_peak"`` (dBTP, before the gain) and ``"lra"``; ``"marks"`` when it asked:
+    ``{"tokens"}`` -- one list for a request, one per sentence for a document -- with ``"words"`` when its rows bring ``word_groups``.
+    A float result at 24 kHz that asked nothing keeps exactly the keys it had before there was a choice."""
+    from .loudness import dbtp
+    from .timing import word_marks
+    for g, (r, u) in enumerate(zip(res, units)):
+        r["audio"] = out.rows[g]
         if isinstance(u, Document):
-            r = {"audio": a, "segments": seg, "mel_lengths": lens[b:b + n]}
-        else:
-            r = {"mel": out["mel"][b, :, :lens[b]], "mel_length": lens[b], "audio": a}
+            r["segments"] = out.segments[g]
         if int(u.sample_rate) != 24000:
             r["sample_rate"] = int(u.sample_rate)
         if u.encoding is not None:
             r["encoding"] = u.encoding
-        report_into(r, rep, u.loudness, u.true_peak)
-        if timed:
-            marks_into(r, u, out_w.marks[len(res)] if isinstance(u, Document) else out_w.marks[len(res)][0])
-        res.append(r)
+        rep = None if out.report is None else out.report[g]
+        if u.loudness is not None and rep is not None:
+            metered = isinstance(rep, dict)
+            r["loudness"], r["gain"] = (float(rep["lufs"]), float(rep["gain"])) if metered else (float(rep[0]), float(rep[1]))
+            if metered and u.true_peak is not None:
+                r["true_peak"], r["lra"] = dbtp(rep["true_peak"]), float(rep["lra"])
+        if u.marks and out.marks is not None:
+            rows, tokens = unit_rows(u), out.marks[g] if out.segments is not None else [out.marks[g]]      # (behind the join: per row of the unit)
+            marks = {"tokens": tokens}
+            if all(row.word_groups is not None for row in rows):
+                marks["words"] = [word_marks(t, row.word_groups) for t, row in zip(tokens, rows)]
+            r["marks"] = marks if isinstance(u, Document) else {k: v[0] for k, v in marks.items()}
+
+
+def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_batch: bool, units: List[Any], timing=None,
+                   fade_ms: float = 5.0) -> None:
+    """The tail of a batch of finished mels (``mel`` [B, n_feats, T], ``mel_lengths`` [B]): ``res[g]["audio"]`` for every unit, in what
+    the unit asks for (``tail_options``: rate, encoding, loudness, ceiling, marks; a document's rows joined) and with the keys that say
+    so (``results_into``).  ``res[g]["mel"]``: the exact-length mel of a request.  ``wave_batch``: one ``waveform.tail`` call for the
+    batch; without it the per-request loop (``waveform.finish_request`` on each request's own mel), which knows no join and no timing.
+    Without a vocoder nothing is touched."""
+    if vocoder is None:
+        return
+    if timing is not None and not wave_batch:
+        raise ValueError("marks and breaks run in the batched tail: they need wave_batch=True")
+    if wave_batch:
+        from .waveform import tail
+        out = tail(mel, mel_lengths, vocoder, **tail_options(units, timing, fade_ms))
+    else:
+        from .waveform import Tail, _waveform_on_device, finish_request, trim_trailing_silence
+        done = [finish_request(trim_trailing_silence(_waveform_on_device(r["mel"][None], vocoder).squeeze()), loudness=u.loudness,
+                               true_peak=u.true_peak, report=True, sample_rate=int(u.sample_rate), encoding=u.encoding, dither=bool(u.dither),
+                               dither_key=int(u.dither_key)) for r, u in zip(res, units)]
+        out = Tail(rows=[a for a, _ in done], report=[rep for _, rep in done])
+    results_into(res, units, out)
+
+
+def synthesise_batch(model, units: List[Any], vocoder=None, wave_batch: bool = True, fade_ms: float = 5.0) -> List[Dict[str, Any]]:
+    """One ``synthesise(per_request_padding=True)`` call for the units of one group -- requests, and documents with their rows -- then
+    one tail (``waveforms_into``), and one result per unit: ``{"mel", "mel_length"[, "audio", ...]}`` for a request, ``{"audio",
+    "segments", "mel_lengths"[, ...]}`` for a document.  A request keeps exactly the keys and values it has without documents in its
+    batch.  The join is part of the batched tail: there is no per-request loop for it, and no host-side join."""
+    joined = any(isinstance(u, Document) for u in units)
+    if joined and vocoder is None:
+        raise ValueError("a document needs a vocoder: its result is the joined audio")
+    rows = [r for u in units for r in unit_rows(u)]
+    x, x_len, emb = request_inputs(model, rows)
+    head = rows[0]
+    model.decoder.solver = head.solver
+    shaping = shaping_kwargs(rows, units)
+    if vocoder is None and "return_timing" in shaping:
+        raise ValueError("marks and breaks need a vocoder: they are positions in the audio")
+    out = model.synthesise(x, x_len, head.n_timesteps, speaker_embeddings=emb,
+                           scale_correction=[r.scale_correction for r in rows],
+                           length_scale=[r.length_scale for r in rows], per_request_padding=True,
+                           durations=duration_rows(rows), **shaping)
+    lens = [int(v) for v in out["mel_lengths"].tolist()]
+    res, b = [], 0
+    for u in units:
+        n = len(unit_rows(u))
+        res.append({"mel_lengths": lens[b:b + n]} if isinstance(u, Document) else {"mel": out["mel"][b, :, :lens[b]], "mel_length": lens[b]})
         b += n
+    waveforms_into(res, out["mel"], out["mel_lengths"], vocoder, wave_batch or joined, units,
+                   (out["token_ends"], x_len) if "token_ends" in out else None, fade_ms)
     return res
 
 
@@ -661,7 +562,7 @@ class StepEntry:
         return self.i >= len(self.grid)
 
 
-class StepBatcher:
+class StepBatcher(_Queue):
     """Same contract as ``FrameBudgetBatcher`` -- ``submit(ids, **kw) -> Future`` of ``{"mel", "mel_length"[, "audio"]}`` -- scheduled
     at the solver step.  One worker thread drives the model.  Per iteration: admit (text encoder, durations and ``align_pool`` of the
     newcomers as one small ragged batch, then into free slots), one step for all active requests of one solver (round-robin over
@@ -672,61 +573,27 @@ class StepBatcher:
 
     def __init__(self, model, max_batch: int = 32, max_tokens: int = 16384, n_slots: Optional[int] = None, slot_frames: int = 2048,
                  run_step: Optional[Callable[[str, List[StepEntry]], None]] = None, vocoder=None):
-        self.model = model
-        self.vocoder = vocoder
-        self.wave_batch = os.environ.get("MTTS_WAVE_BATCH", "1") != "0"
-        self.max_batch = int(max_batch)
-        self.max_tokens = int(max_tokens)
         self.slot_frames = int(slot_frames)
-        self.slots = SlotBook(int(n_slots) if n_slots is not None else self.max_batch)
+        self.slots = SlotBook(int(n_slots) if n_slots is not None else int(max_batch))
         self._fake = run_step is not None
         self._run_step = run_step or self._step_on_model
         self._pool = None
         self._flags = None                  # device int32 [3]: encoder range flag, estimator range flag, pair time-out, OR-ed over calls
-        self._waiting: List[Request] = []
         self._active: List[StepEntry] = []
         self._last_solver: Optional[str] = None
-        self._cv = threading.Condition()
-        self._stop = False
-        self.batches_run = 0                # iterations that ran a step
-        self.utterance_steps = 0            # requests x steps served: utterance_steps / batches_run = mean utterances per step
+        self.utterance_steps = 0            # requests x steps served: utterance_steps / batches_run (iterations that ran a step) = mean utterances per step
         self.whole_solves = 0               # requests that did not fit a slot
-        self.busy_s = 0.0
         self.phase_s = {"admit": 0.0, "step": 0.0, "leave": 0.0}     # where busy_s went (host wall time; "leave" holds the iteration's wait)
-        self._thread = threading.Thread(target=self._loop, name="mtts-step-batcher", daemon=True)
-        self._thread.start()
+        self._open(model, vocoder, max_batch, max_tokens, "mtts-step-batcher")
 
     # ------------------------------------------------------------------ producer side
     def submit(self, ids: Sequence[int], **kw) -> Future:
-        if len(ids) == 0:
-            raise ValueError("empty utterance")
-        if len(ids) > self.max_tokens:
-            raise ValueError(f"utterance of {len(ids)} tokens exceeds the batch budget of {self.max_tokens}")
-        r = Request(ids=list(ids), **kw)
-        duration_rows([r])
-        if timing_fields([r]) is not None:
+        r = self._request(ids, kw)
+        if shaping_kwargs([r]):
             raise ValueError("token_scale, token_extend, breaks and marks are served by FrameBudgetBatcher: the step-level admission "
                              "path does not take them")
         step_grid(r.n_timesteps)
-        with self._cv:
-            if self._stop:
-                raise RuntimeError("batcher is closed")
-            self._waiting.append(r)
-            self._cv.notify()
-        return r.future
-
-    def close(self) -> None:
-        """Stop taking requests; everything submitted before is served."""
-        with self._cv:
-            self._stop = True
-            self._cv.notify()
-        self._thread.join()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        return self._enqueue(r)
 
     # ------------------------------------------------------------------ worker
     def _loop(self) -> None:
@@ -893,9 +760,7 @@ class StepBatcher:
                 mel[b, :, :r["mel_length"]] = r["mel"]
             lengths = torch.tensor([r["mel_length"] for r in res], dtype=torch.long, device=mel.device)
             try:
-                waveforms_into(res, mel, lengths, self.vocoder, self.wave_batch, [e.request.sample_rate for e in finished],
-                               *encoding_fields([e.request for e in finished]), loudness=loudness_field([e.request for e in finished]),
-                               true_peak=true_peak_field([e.request for e in finished]))
+                waveforms_into(res, mel, lengths, self.vocoder, self.wave_batch, [e.request for e in finished])
             except BaseException as exc:  # noqa: BLE001 - the finishers only: who is mid-solve is not affected
                 self._fail([e.request for e in finished], exc)
                 return

@@ -832,9 +832,7 @@ def pipeline(model, vocoder, text, speaker=0, voice_mix=None, n_timesteps=DEFAUL
     needs a ``loudness`` target."""
     from . import loudness as LD
     target = LD.check_target(loudness)                                 # (a value that is no level raises before anything runs)
-    ceiling = LD.check_true_peak(true_peak)
-    if ceiling is not None and target is None:
-        raise ValueError("pipeline: true_peak limits the gain towards a loudness target, and loudness= names none")
+    ceiling = LD.check_ceiling(true_peak, target)
     primary = voice_mix[0][0] if voice_mix is not None else speaker
     language = next(v["lang"] for v in VOICES if v["id"] == str(primary))
     tp = process_text(text, language)

@@ -67,6 +67,15 @@ def check_true_peak(value, what: str = "true_peak") -> Optional[float]:
     return v
 
 
+def check_ceiling(true_peak, loudness) -> Optional[float]:
+    """``check_true_peak`` of a unit's ceiling beside its checked target ``loudness``: the ceiling limits the gain towards a loudness
+    target, so one without a target raises ``ValueError`` too.  The one rule of every entry that takes the pair.  Host-only."""
+    ceiling = check_true_peak(true_peak)
+    if ceiling is not None and loudness is None:
+        raise ValueError(f"true_peak = {true_peak!r} limits the gain towards a loudness target, and none is named (loudness=)")
+    return ceiling
+
+
 def dbtp(x):
     """A linear peak -- a number or a tensor -- in dB relative to full scale: ``20 log10(x)``, -inf for 0."""
     if torch.is_tensor(x):

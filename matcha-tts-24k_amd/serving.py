@@ -19,6 +19,7 @@ from dataclasses import dataclass
 from typing import Callable, List, Optional, Sequence, Tuple
 
 from .inference import DEFAULT_NUM_STEPS, DEFAULT_ODE_SOLVER, VOICES
+from .loudness import check_ceiling as checked_ceiling, check_target      # (the ceiling rule under the name it has here)
 
 LENGTH_SCALE_MIN = 0.1      # fastest (client speed 2.0 clamps here; reference server.py:34-36)
 LENGTH_SCALE_MAX = 2.0      # slowest
@@ -101,16 +102,6 @@ def request_params(voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, 
 _SERVICE = object()      # default of ``submit_long / speak_long(loudness=)``: the service's own target
 
 
-def checked_ceiling(true_peak, loudness) -> Optional[float]:
-    """A true-peak ceiling in dBTP as a float, or None.  It limits the gain towards a loudness target, so a ceiling without one
-    raises ``ValueError``, as a value that is no ceiling does (``loudness.check_true_peak``).  Pure function: unit-tested on the CPU."""
-    from .loudness import check_true_peak
-    ceiling = check_true_peak(true_peak)
-    if ceiling is not None and loudness is None:
-        raise ValueError(f"true_peak = {true_peak!r} limits the gain towards a loudness target, and none is named (loudness=)")
-    return ceiling
-
-
 class SpeechService:
     """``await service.speak(text, voice, speed, steps, solver)`` -> 1-D waveform tensor on the host (``bytes`` with ``response_format``).
 
@@ -133,7 +124,6 @@ class SpeechService:
         target, for one request: ``await service.levelled(-16).speak(text)``.  ``true_peak``: None, or the ceiling in dBTP the true
         peak of every levelled request is held under (EBU R 128 delivery: -1); it limits the gain towards the target, so it needs
         ``loudness``.  Results then also carry ``"true_peak"`` (dBTP, before the gain) and ``"lra"``."""
-        from .loudness import check_target
         self.batcher = batcher
         self.phonemize = phonemize
         self.max_text_length = int(max_text_length)
@@ -149,12 +139,13 @@ class SpeechService:
         are asked for this way; ``submit_long`` and ``speak_long`` also take ``marks=`` themselves."""
         return SpeechService(self.batcher, self.phonemize, self.max_text_length, self.loudness, self.true_peak, marks, self.word_groups, self.flac)
 
-    def _timing_fields(self, text: str, language: str, ids) -> dict:
-        """The request fields marks add: ``marks`` and, with a ``word_groups`` callable, the word of each token."""
-        extra = {"marks": True}
-        if self.word_groups is not None:
-            extra["word_groups"] = list(self.word_groups(text, language, ids))
-        return extra
+    def _fields(self, speaker_embedding, sample_rate, encoding, target, ceiling, marks, word_groups: Callable[[], list]) -> dict:
+        """The fields a submission names beside its voice and speeds -- only those that differ from a ``Request``'s defaults, so a plain
+        one names none.  ``word_groups()``: the word of each token, asked for only with marks and a ``word_groups`` front end."""
+        named = dict(speaker_embedding=None if speaker_embedding is None else tuple(speaker_embedding),
+                     sample_rate=int(sample_rate) if int(sample_rate) != 24000 else None, encoding=encoding, loudness=target, true_peak=ceiling,
+                     marks=True if marks else None, word_groups=word_groups() if marks and self.word_groups is not None else None)
+        return {k: v for k, v in named.items() if v is not None}
 
     def levelled(self, loudness: Optional[float], true_peak: Optional[float] = None) -> "SpeechService":
         """This service -- the same batcher and front end -- with ``loudness`` as its target (None: none) and ``true_peak`` as its
@@ -178,17 +169,8 @@ class SpeechService:
             raise ValueError(f"Text exceeds {self.max_text_length} characters")       # the handler's HTTP 400
         p = request_params(voice, speed, steps, solver)
         ids = self.phonemize(text.strip(), p.language)
-        extra = {} if speaker_embedding is None else {"speaker_embedding": tuple(speaker_embedding)}
-        if int(sample_rate) != 24000:
-            extra["sample_rate"] = int(sample_rate)
-        if encoding is not None:
-            extra["encoding"] = encoding
-        if self.loudness is not None:
-            extra["loudness"] = self.loudness
-        if self.true_peak is not None:
-            extra["true_peak"] = self.true_peak
-        if self.marks:
-            extra.update(self._timing_fields(text.strip(), p.language, ids))
+        extra = self._fields(speaker_embedding, sample_rate, encoding, self.loudness, self.true_peak, self.marks,
+                             lambda: list(self.word_groups(text.strip(), p.language, ids)))
         return self.batcher.submit(ids, speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver, n_timesteps=p.n_timesteps,
                                    scale_correction=p.scale_correction, length_scale=p.length_scale, **extra)
 
@@ -215,7 +197,6 @@ class SpeechService:
         ``marks``: whether the result carries ``"marks"`` -- ``{"tokens": one list of (start_s, end_s) per sentence}`` in the document's
         timeline, ``"words"`` too with the service's ``word_groups`` -- by default as the service says."""
         encoding = response_encoding(response_format, self.flac)
-        from .loudness import check_target
         target = self.loudness if loudness is _SERVICE else check_target(loudness)
         ceiling = (self.true_peak if target is not None else None) if true_peak is _SERVICE else checked_ceiling(true_peak, target)
         if not hasattr(self.batcher, "submit_document"):
@@ -229,19 +210,8 @@ class SpeechService:
         if not pieces:
             raise ValueError("empty text")
         ids = [self.phonemize(segment, p.language) for segment, _ in pieces]
-        extra = {} if speaker_embedding is None else {"speaker_embedding": tuple(speaker_embedding)}
-        if int(sample_rate) != 24000:
-            extra["sample_rate"] = int(sample_rate)
-        if encoding is not None:
-            extra["encoding"] = encoding
-        if target is not None:
-            extra["loudness"] = target
-        if ceiling is not None:
-            extra["true_peak"] = ceiling
-        if self.marks if marks is _SERVICE else bool(marks):
-            extra["marks"] = True
-            if self.word_groups is not None:
-                extra["word_groups"] = [list(self.word_groups(segment, p.language, i)) for (segment, _), i in zip(pieces, ids)]
+        extra = self._fields(speaker_embedding, sample_rate, encoding, target, ceiling, self.marks if marks is _SERVICE else marks,
+                             lambda: [list(self.word_groups(segment, p.language, i)) for (segment, _), i in zip(pieces, ids)])
         return self.batcher.submit_document(ids, [pause for _, pause in pieces], speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver,
                                             n_timesteps=p.n_timesteps, scale_correction=p.scale_correction, length_scale=p.length_scale,
                                             **extra)

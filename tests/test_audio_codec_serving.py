@@ -27,14 +27,15 @@ def test_request_defaults_and_validation():
     bt = sub("batcher")
     r = bt.Request(ids=[1, 2])
     assert (r.encoding, r.dither, r.dither_key) == (None, False, 0)
-    assert bt.encoding_fields([r, bt.Request(ids=[3])]) == (None, None, None)
+    fields = lambda batch: tuple(bt.tail_options(batch).get(k) for k in ("encoding", "dither", "dither_keys"))
+    assert fields([r, bt.Request(ids=[3])]) == (None, None, None)
     mixed = [r, bt.Request(ids=[3], encoding="ulaw"), bt.Request(ids=[4], encoding="pcm16", dither=True, dither_key=77)]
-    assert bt.encoding_fields(mixed) == ([None, "ulaw", "pcm16"], [False, False, True], [0, 0, 77])
+    assert fields(mixed) == ([None, "ulaw", "pcm16"], [False, False, True], [0, 0, 77])
     with pytest.raises(ValueError):
         bt.Request(ids=[1], encoding="mp3")
     # without a vocoder nothing is touched, whatever the requests ask
     res = [{"mel": None, "mel_length": 3}]
-    bt.waveforms_into(res, None, None, None, True, [8000], ["ulaw"], [False], [0])
+    bt.waveforms_into(res, None, None, None, True, [bt.Request(ids=[1, 2, 3], sample_rate=8000, encoding="ulaw")])
     assert res == [{"mel": None, "mel_length": 3}]
 
 

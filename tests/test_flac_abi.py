@@ -205,7 +205,8 @@ def test_requests_documents_and_the_service_take_the_name():
     import torch
     bt, sv = sub("batcher"), sub("serving")
     r = bt.Request(ids=[1, 2], encoding="flac", dither=True, dither_key=4)
-    assert bt.encoding_fields([bt.Request(ids=[3]), r]) == ([None, "flac"], [False, True], [0, 4])
+    asked = bt.tail_options([bt.Request(ids=[3]), r])
+    assert (asked["encoding"], asked["dither"], asked["dither_keys"]) == ([None, "flac"], [False, True], [0, 4])
     assert bt.Document(rows=[bt.Request(ids=[1])], pauses_ms=[0.0], encoding="flac").encoding == "flac"
     with pytest.raises(ValueError):
         bt.Request(ids=[1], encoding="FLAC")

@@ -276,8 +276,8 @@ def test_batcher_request_and_service_return_encoded_audio(ac, env, synthetic):
     assert isinstance(leg, bytes) and len(leg) > 0
     # the per-request tail (MTTS_WAVE_BATCH=0) encodes too
     one, res = [{"mel": plain["mel"]}], [{"mel": plain["mel"]}]
-    bt.waveforms_into(one, plain["mel"][None], [plain["mel_length"]], vocos, False)
-    bt.waveforms_into(res, plain["mel"][None], [plain["mel_length"]], vocos, False, [24000], ["alaw"], [False], [0])
+    bt.waveforms_into(one, plain["mel"][None], [plain["mel_length"]], vocos, False, [bt.Request(ids=[1])])
+    bt.waveforms_into(res, plain["mel"][None], [plain["mel_length"]], vocos, False, [bt.Request(ids=[1], encoding="alaw")])
     assert set(one[0]) == {"mel", "audio"} and one[0]["audio"].numel() > 0
     assert res[0]["encoding"] == "alaw" and np.array_equal(res[0]["audio"].numpy(), ar.encode(one[0]["audio"].numpy(), ar.ALAW))
 

@@ -273,8 +273,9 @@ def test_batcher_service_and_per_request_tail_return_streams(ac, env, synthetic)
     again, _ = wf.finish_request(plain["audio"].cuda(), encoding="flac")
     assert torch.equal(again, flac["audio"])
     res, ref = [{"mel": pcm["mel"]}], [{"mel": pcm["mel"]}]
-    bt.waveforms_into(res, pcm["mel"][None], [pcm["mel_length"]], vocos, False, [8000], ["flac"], [True], [31])
-    bt.waveforms_into(ref, pcm["mel"][None], [pcm["mel_length"]], vocos, False, [8000], ["pcm16"], [True], [31])
+    unit = lambda encoding: bt.Request(ids=[1], sample_rate=8000, encoding=encoding, dither=True, dither_key=31)
+    bt.waveforms_into(res, pcm["mel"][None], [pcm["mel_length"]], vocos, False, [unit("flac")])
+    bt.waveforms_into(ref, pcm["mel"][None], [pcm["mel_length"]], vocos, False, [unit("pcm16")])
     assert res[0]["encoding"] == "flac" and res[0]["sample_rate"] == 8000
     assert_stream(res[0]["audio"], ref[0]["audio"], 8000)
     empty, _ = wf.finish_request(torch.zeros(0, device="cuda"), encoding="flac", sample_rate=8000)

@@ -389,11 +389,10 @@ def test_a_request_with_a_ceiling_carries_true_peak_and_lra(L, env):
     bt = sub("batcher")
     batch = [bt.Request(ids=[1], loudness=0.0, true_peak=-1.0), bt.Request(ids=[1]), bt.Request(ids=[1], loudness=-16.0),
              bt.Request(ids=[1], loudness=0.0, true_peak=-3)]
-    fields = dict(loudness=bt.loudness_field(batch), true_peak=bt.true_peak_field(batch))
     res = [{"mel": mel[b, :, :lengths[b]], "mel_length": lengths[b]} for b in range(4)]
-    bt.waveforms_into(res, mel, torch.tensor(lengths), vocos, True, **fields)
+    bt.waveforms_into(res, mel, torch.tensor(lengths), vocos, True, batch)
     one = [{"mel": mel[b, :, :lengths[b]], "mel_length": lengths[b]} for b in range(4)]
-    bt.waveforms_into(one, mel, torch.tensor(lengths), vocos, False, **fields)         # the per-request tail says the same
+    bt.waveforms_into(one, mel, torch.tensor(lengths), vocos, False, batch)            # the per-request tail says the same
     _, report = inf.to_waveforms(mel, lengths, vocos, loudness=0.0, true_peak=-1.0, return_meter=True)
     assert set(res[0]) == {"mel", "mel_length", "audio", "loudness", "gain", "true_peak", "lra"} == set(res[3])
     assert set(res[1]) == {"mel", "mel_length", "audio"} and set(res[2]) == {"mel", "mel_length", "audio", "loudness", "gain"}

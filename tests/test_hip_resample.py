@@ -237,8 +237,8 @@ def test_outbound(res, voice_env, synthetic):
     bt = sub("batcher")
     # the per-request tail (MTTS_WAVE_BATCH=0) converts too
     one24, one8 = [{"mel": mel[1, :, :33]}], [{"mel": mel[1, :, :33]}]
-    bt.waveforms_into(one24, mel[1:2, :, :33], [33], wrapper, False)
-    bt.waveforms_into(one8, mel[1:2, :, :33], [33], wrapper, False, [8000])
+    bt.waveforms_into(one24, mel[1:2, :, :33], [33], wrapper, False, [bt.Request(ids=[1])])
+    bt.waveforms_into(one8, mel[1:2, :, :33], [33], wrapper, False, [bt.Request(ids=[1], sample_rate=8000)])
     assert "sample_rate" not in one24[0] and one8[0]["sample_rate"] == 8000       # a 24 kHz result keeps the keys it always had
     assert one8[0]["audio"].numel() == res.resampler(24000, 8000, "cuda").out_length(one24[0]["audio"].numel())
     if one24[0]["audio"].numel():

@@ -19,12 +19,13 @@ def service(run, **kw):
 def test_request_and_document_fields():
     bt = sub("batcher")
     r = bt.Request(ids=[1, 2])
-    assert r.loudness is None and bt.loudness_field([r, bt.Request(ids=[3])]) is None
+    loudness_field = lambda batch: bt.tail_options(batch).get("loudness")
+    assert r.loudness is None and loudness_field([r, bt.Request(ids=[3])]) is None
     mixed = [r, bt.Request(ids=[3], loudness=-16), bt.Request(ids=[4], loudness=-23.0)]
-    assert bt.loudness_field(mixed) == [None, -16.0, -23.0]
+    assert loudness_field(mixed) == [None, -16.0, -23.0]
     assert isinstance(mixed[1].loudness, float)
     d = bt.Document(rows=[bt.Request(ids=[1]), bt.Request(ids=[2])], pauses_ms=[100, 0], loudness=-19)
-    assert d.loudness == -19.0 and bt.loudness_field([d, r]) == [-19.0, None]
+    assert d.loudness == -19.0 and loudness_field([d, r]) == [-19.0, None]
     assert bt.Document(rows=[bt.Request(ids=[1])], pauses_ms=[0]).loudness is None
     for bad in ("loud", True, [-23.0]):
         with pytest.raises(TypeError):
@@ -36,14 +37,14 @@ def test_request_and_document_fields():
             bt.Document(rows=[bt.Request(ids=[1])], pauses_ms=[0], loudness=bad)
     # what the device is handed for a mixed batch: NaN for the rows without a target
     L = sub("loudness")
-    got = L.targets_per_row(bt.loudness_field(mixed), 3)
+    got = L.targets_per_row(loudness_field(mixed), 3)
     assert math.isnan(got[0]) and got[1:] == [-16.0, -23.0]
     # without a vocoder nothing is touched, whatever the requests ask
     res = [{"mel": None, "mel_length": 3}]
-    bt.waveforms_into(res, None, None, None, True, loudness=[-23.0])
+    bt.waveforms_into(res, None, None, None, True, [bt.Request(ids=[1, 2, 3], loudness=-23.0)])
     assert res == [{"mel": None, "mel_length": 3}]
     p = inspect.signature(bt.waveforms_into).parameters
-    assert list(p)[-1] == "loudness" and p["loudness"].default is None        # no positional caller moves
+    assert "units" in p and not {"loudness", "true_peak", "sample_rates", "encodings", "dithers", "dither_keys"} & set(p)    # the fields come with the units: there is no per-field list to misplace
     inf = sub("inference")
     for fn in (inf.to_waveforms, inf.pipeline):
         p = inspect.signature(fn).parameters
@@ -63,7 +64,7 @@ def test_service_passes_the_target_on_and_results_carry_the_measurement():
         out = []
         for u in batch:
             res = {"audio": torch.zeros(5)}
-            if u.loudness is not None:      # what waveforms_into / synthesise_units leave for such a unit
+            if u.loudness is not None:      # what results_into leaves for such a unit
                 res["loudness"], res["gain"] = -20.5, 10 ** ((u.loudness + 20.5) / 20)
             out.append(res)
         return out
@@ -111,7 +112,7 @@ def test_mixed_batches_and_the_step_batcher():
     calls = []
 
     def run(batch):
-        calls.append(bt.loudness_field(batch))
+        calls.append(bt.tail_options(batch).get("loudness"))
         return [{"mel_length": len(r.ids)} for r in batch]
 
     q = bt.FrameBudgetBatcher(model=None, max_batch=4, max_tokens=4096, max_wait_ms=200.0, run_batch=run)

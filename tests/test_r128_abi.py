@@ -217,11 +217,12 @@ def test_request_document_and_service_fields():
     import torch
     bt, sv = sub("batcher"), sub("serving")
     r = bt.Request(ids=[1, 2])
-    assert r.true_peak is None and bt.true_peak_field([r, bt.Request(ids=[3], loudness=-16)]) is None
+    true_peak_field = lambda batch: bt.tail_options(batch).get("true_peak")
+    assert r.true_peak is None and true_peak_field([r, bt.Request(ids=[3], loudness=-16)]) is None
     mixed = [r, bt.Request(ids=[3], loudness=-16, true_peak=-1), bt.Request(ids=[4], loudness=-23.0)]
-    assert bt.true_peak_field(mixed) == [None, -1.0, None] and isinstance(mixed[1].true_peak, float)
+    assert true_peak_field(mixed) == [None, -1.0, None] and isinstance(mixed[1].true_peak, float)
     d = bt.Document(rows=[bt.Request(ids=[1]), bt.Request(ids=[2])], pauses_ms=[100, 0], loudness=-19, true_peak=-2.0)
-    assert bt.true_peak_field([d, r]) == [-2.0, None] and all(x.true_peak is None for x in d.rows)
+    assert true_peak_field([d, r]) == [-2.0, None] and all(x.true_peak is None for x in d.rows)
     for make in (lambda **kw: bt.Request(ids=[1], **kw), lambda **kw: bt.Document(rows=[bt.Request(ids=[1])], pauses_ms=[0], **kw)):
         with pytest.raises(ValueError, match="target"):
             make(true_peak=-1.0)                                  # a ceiling without a target
@@ -231,21 +232,25 @@ def test_request_document_and_service_fields():
             make(loudness=-23, true_peak="hot")
     # what a result carries
     rep = dict(lufs=-20.5, gain=0.75, lra=4.25, momentary_max=-18.0, short_term_max=-19.0, peak=0.5, true_peak=0.53)
+    def report_into(res, rep, target, ceiling=None):
+        unit = bt.Request(ids=[1], loudness=target, true_peak=ceiling)
+        bt.results_into([res], [unit], sub("waveform").Tail(rows=[None], report=[rep]))
+        assert res.pop("audio") is None
     res = {}
-    bt.report_into(res, rep, -23.0, -1.0)
+    report_into(res, rep, -23.0, -1.0)
     assert res == {"loudness": -20.5, "gain": 0.75, "true_peak": 20 * math.log10(0.53), "lra": 4.25}
     res = {}
-    bt.report_into(res, rep, -23.0, None)                         # in a metered batch, a unit without a ceiling keeps today's keys
+    report_into(res, rep, -23.0, None)                            # in a metered batch, a unit without a ceiling keeps today's keys
     assert res == {"loudness": -20.5, "gain": 0.75}
     res = {}
-    bt.report_into(res, (-20.5, 0.75), -23.0)
+    report_into(res, (-20.5, 0.75), -23.0)
     assert res == {"loudness": -20.5, "gain": 0.75}
-    bt.report_into(res := {}, rep, None, None)
+    report_into(res := {}, rep, None, None)
     assert res == {}
     p = inspect.signature(bt.waveforms_into).parameters
-    assert p["true_peak"].default is None and p["true_peak"].kind is inspect.Parameter.KEYWORD_ONLY
+    assert "units" in p and not {"loudness", "true_peak", "sample_rates", "encodings", "dithers", "dither_keys"} & set(p)    # no per-field list to misplace
     res = [{"mel": None, "mel_length": 3}]
-    bt.waveforms_into(res, None, None, None, True, loudness=[-23.0], true_peak=[-1.0])
+    bt.waveforms_into(res, None, None, None, True, [bt.Request(ids=[1, 2, 3], loudness=-23.0, true_peak=-1.0)])
     assert res == [{"mel": None, "mel_length": 3}]
     # the service: the ceiling reaches the batcher from every entry, and one without a target is refused before anything is submitted
     assert sv.checked_ceiling(None, None) is None and sv.checked_ceiling(-1, -23.0) == -1.0

@@ -128,7 +128,8 @@ def test_python_signatures_and_host_refusals(tm):
         p = inspect.signature(fn).parameters
         for name, default in (("token_scale", None), ("token_extend", None), ("return_timing", False)):
             assert p[name].default is default and p[name].kind is inspect.Parameter.KEYWORD_ONLY
-    assert list(inspect.signature(sub("batcher").waveforms_into).parameters)[-1] == "loudness"
+    p = inspect.signature(sub("batcher").waveforms_into).parameters
+    assert "units" in p and not {"loudness", "true_peak", "sample_rates", "encodings", "dithers", "dither_keys", "breaks"} & set(p)    # no per-field list to misplace
     mel = torch.zeros(2, 100, 8)
     for kw in (dict(return_marks=True), dict(breaks=[None, None]), dict(token_ends=torch.zeros(2, 3)), dict(return_marks=True, x_lengths=[3, 3])):
         with pytest.raises(ValueError, match="token_ends= and x_lengths="):
@@ -160,14 +161,17 @@ def test_request_and_document_fields_are_checked(bt):
                      (dict(breaks=[(1, 1e7)]), "pause"), (dict(breaks=[(1.5, 10)]), "outside")):
         with pytest.raises(ValueError, match=word):
             R(**kw)
-    assert bt.timing_fields([R(), R()]) is None and bt.shaping_kwargs(None) == {}
-    f = bt.timing_fields([R(), R(breaks=[(1, 20)]), R(token_scale=[1, 2, 1, 1])])
-    assert f == dict(token_scale=[None, None, [1, 2, 1, 1]], token_extend=None, breaks=[None, [(1, 20.0)], None], marks=False)
+    ends = ("token_ends", "x_lengths")                          # (what a synthesise call that was asked for its timing hands the tail)
+    tail_breaks = lambda units: bt.tail_options(units, ends)["breaks"]
+    assert bt.shaping_kwargs([R(), R()]) == {} and not {"token_ends", "breaks", "return_marks"} & set(bt.tail_options([R(), R()]))
+    f = [R(), R(breaks=[(1, 20)]), R(token_scale=[1, 2, 1, 1])]
+    assert tail_breaks(f) == [None, [(1, 20.0)], None] and not any(r.marks for r in f)
     assert bt.shaping_kwargs(f) == dict(token_scale=[None, None, [1, 2, 1, 1]], return_timing=True)
-    assert bt.shaping_kwargs(bt.timing_fields([R(token_extend=[0, 1, 0, 0])])) == dict(token_extend=[[0, 1, 0, 0]])
-    assert bt.timing_fields([R(marks=True)])["marks"] is True
+    assert bt.shaping_kwargs([R(token_extend=[0, 1, 0, 0])]) == dict(token_extend=[[0, 1, 0, 0]])
+    assert bt.shaping_kwargs([R(marks=True)]) == dict(return_timing=True) and tail_breaks([R(marks=True)]) is None
     d = bt.Document(rows=[R(), R(breaks=[(0, 5)])], pauses_ms=[10.0, 0.0], marks=True)
-    assert bt.timing_fields(d.rows, [d]) == dict(token_scale=None, token_extend=None, breaks=[None, [(0, 5.0)]], marks=True)
+    assert bt.shaping_kwargs(d.rows, [d]) == dict(return_timing=True) and tail_breaks([d]) == [None, [(0, 5.0)]]
+    assert bt.shaping_kwargs([R(), R()], [bt.Document(rows=[R(), R()], pauses_ms=[0, 0], marks=True)]) == dict(return_timing=True)
 
     log = []
 
