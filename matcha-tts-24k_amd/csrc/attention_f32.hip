@@ -353,6 +353,46 @@ __global__ __launch_bounds__(64 * NW, KR > AT_K ? 1 : 2) void attention_f32_kern
     if (P16) {
         if (q_in) {
             _Float16* op = p.out16 + (rowbase + qi) * (size_t)p.ldo16 + head * ((HALF ? 1 : 2) * AT_D);
+            // write-through (AttnArgs::store_wt) needs 16-byte stores: the two lanes of a query (h = 0 / 1: d 8 g4 ..+3 / 8 g4 + 4 ..+7)
+            // swap one 8-byte piece per pair of g4 and store whole 8-channel chunks, lane h those of g4 = 2 j + h.  Same values, same
+            // rounding; both lanes of a query are inside `q_in` together.
+            if (!HALF && p.store_wt) {
+                using u32x2 = __attribute__((ext_vector_type(2))) unsigned int;
+                using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        u32x2 hw[2], lw[2];
+#pragma unroll
+                        for (int k = 0; k < 2; ++k) {
+                            const int g4 = 2 * j + k;
+                            f16x4 hh, ll;
+                            range_bad |= out_of_f16_range(o[t][4 * g4] * inv, o[t][4 * g4 + 1] * inv, o[t][4 * g4 + 2] * inv, o[t][4 * g4 + 3] * inv);
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                _Float16 a, b;
+                                split_f16(o[t][4 * g4 + e] * inv, p.out_lscale, a, b);
+                                hh[e] = a;
+                                ll[e] = b;
+                            }
+                            hw[k] = __builtin_bit_cast(u32x2, hh);
+                            lw[k] = __builtin_bit_cast(u32x2, ll);
+                        }
+                        const u32x2 sh = h ? hw[0] : hw[1], sl = h ? lw[0] : lw[1], kh = h ? hw[1] : hw[0], kl = h ? lw[1] : lw[0];
+                        u32x2 gh, gl;
+#pragma unroll
+                        for (int e = 0; e < 2; ++e) {
+                            gh[e] = (unsigned int)__shfl_xor((int)sh[e], 32);
+                            gl[e] = (unsigned int)__shfl_xor((int)sl[e], 32);
+                        }
+                        const u32x4 ph = h ? u32x4{gh[0], gh[1], kh[0], kh[1]} : u32x4{kh[0], kh[1], gh[0], gh[1]};
+                        const u32x4 pl = h ? u32x4{gl[0], gl[1], kl[0], kl[1]} : u32x4{kl[0], kl[1], gl[0], gl[1]};
+                        _Float16* dst = op + t * 64 + 8 * (2 * j + h);
+                        store16(reinterpret_cast<u32x4*>(dst), ph, true);
+                        store16(reinterpret_cast<u32x4*>(dst + 32), pl, true);
+                    }
+            } else
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -396,7 +436,10 @@ __global__ __launch_bounds__(64 * NW, KR > AT_K ? 1 : 2) void attention_f32_kern
     }
 }
 
-hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
+hipError_t launch_attention(const AttnArgs& a_in, hipStream_t s) {
+    AttnArgs a = a_in;
+    // the lane-paired output stores are 16 bytes wide: rows of whole 16-byte chunks, else the image keeps its plain 8-byte stores
+    if (a.half16 || (a.ldo16 & 7) || (reinterpret_cast<uintptr_t>(a.out16) & 15)) a.store_wt = false;
     const bool p16 = a.qkv16 != nullptr;
     const int ew = a.half16 ? 1 : 2;
     if ((a.half16 && !p16) || (a.bf16 && !a.half16)) return hipErrorInvalidValue;

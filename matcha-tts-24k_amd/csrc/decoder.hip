@@ -25,6 +25,7 @@ static int run_chain(mtts_ctx* c, const ChainArgs& a0, hipStream_t s) {
     ChainArgs a = a0;
     a.range_flag = c->cur_flag;
     { int qb_unused = 0; chain_plan(a.M, a.ch, a.qb, c->sw.chain_pf, &qb_unused, &a.pf_wgs); }
+    a.store_wt = c->store_wt & (WT_CHAIN_X | WT_CHAIN_QKV);
     if (a.pair) a.pf_wgs = c->sw.chain_pf ? 16 : 0;      // two per XCD, one per half (the model admits pair grids up to 240 workgroups)
     LAUNCHB(c, 0, chain_flops(a), chain_bytes(a), s, launch_tblock_chain(a, s));
     return 0;
@@ -54,6 +55,7 @@ static int run_chain_h16(mtts_ctx* c, const ChainH16Args& a0, hipStream_t s) {
 static int run_conv_gn(Component* c, const ConvGnArgs& a0, hipStream_t s) {
     ConvGnArgs a = a0;
     a.range_flag = c->cur_flag;
+    a.store_wt = (c->store_wt & WT_CONV_GN) != 0;
     LAUNCHB(c, 0, conv_gn_flops(a), conv_gn_bytes(a), s, launch_conv_gn(a, s));
     return 0;
 }

@@ -45,6 +45,22 @@ __device__ __forceinline__ void raise_range_flag(unsigned int* flag, bool bad) {
     if (bad && flag) atomicOr(flag, 1u);
 }
 
+// 16-byte global store of an output image, in one of two flavours (wt is wave-uniform: Switches::store_wt decides per kernel family).
+// Plain: the line stays dirty in the XCD's L2 and is written back behind the kernel's last workgroup, in front of the dependent
+// launch.  Write-through (sc1): the bytes leave for memory while the rest of the epilogue runs and the line is DROPPED from this
+// L2, so the kernel's end finds nothing to write back -- and a consumer on the same XCD reads it at the cross-XCD rate.  Only whole
+// 16-byte stores go this way (an 8-byte sc1 store costs 2.7x the time per byte) and never `nt`.  The asm store is not counted by
+// the compiler: it only makes vmcnt larger than the compiler believes, so every wait it writes is stricter than needed.  `s_nop 1`
+// ends the string: the instruction behind it may write the data registers, which a 16-byte store reads over several cycles.
+// dst: V* in the generic or the global address space, 16-byte aligned.
+template <class V, class PTR>
+__device__ __forceinline__ void store16(PTR dst, const V& v, bool wt) {
+    static_assert(sizeof(V) == 16, "a 16-byte vector");
+    using u32x4_s = __attribute__((ext_vector_type(4))) unsigned int;
+    if (wt) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(__builtin_bit_cast(u32x4_s, v)) : "memory");
+    else *dst = v;
+}
+
 // sin(y)^2 for the SnakeBeta epilogue = (1 - cos(2y)) / 2 with the hardware cosine (v_cos_f32 takes revolutions; v_fract_f32
 // reduces the argument first): 4 VALU instructions instead of the ~16 of a Cody-Waite reduction with a minimax sine polynomial.
 // The FeedForward's first projection spends half of its workgroup lifetime in this epilogue (profiles/r02_kstamp.log).  Absolute

@@ -439,10 +439,10 @@ __device__ __forceinline__ void gemm_epilogue_rows8(const GemmArgs& p, const Epi
     typedef __attribute__((address_space(1))) _Float16 ghalf;
     unsigned long long q_out = (unsigned long long)p.out, q_out16 = (unsigned long long)p.out16, q_stats = (unsigned long long)p.stats_out,
                        q_om = (unsigned long long)p.out_mask, q_om16 = (unsigned long long)p.out16_mask;
-    int a_ldc = p.ldc, a_ld16 = p.ld16, a_half = p.half16 ? 1 : 0, a_nw = p.N >> 6, a_bf = p.bf16 ? 1 : 0;
+    int a_ldc = p.ldc, a_ld16 = p.ld16, a_half = p.half16 ? 1 : 0, a_nw = p.N >> 6, a_bf = p.bf16 ? 1 : 0, a_wt = p.store_wt ? 1 : 0;
     float a_scale = p.out_scale, a_lscale = p.out_lscale;
     asm volatile("" : "+s"(q_out), "+s"(q_out16), "+s"(q_stats), "+s"(q_om), "+s"(q_om16));
-    asm volatile("" : "+s"(a_ldc), "+s"(a_ld16), "+s"(a_half), "+s"(a_nw), "+s"(a_scale), "+s"(a_lscale), "+s"(a_bf));
+    asm volatile("" : "+s"(a_ldc), "+s"(a_ld16), "+s"(a_half), "+s"(a_nw), "+s"(a_scale), "+s"(a_lscale), "+s"(a_bf), "+s"(a_wt));
     gfloat* const a_out = (gfloat*)q_out;
     ghalf* const a_out16 = (ghalf*)q_out16;
     gfloat* const a_stats = (gfloat*)q_stats;
@@ -653,8 +653,8 @@ __device__ __forceinline__ void gemm_epilogue_rows8(const GemmArgs& p, const Epi
                                 lv[k] = lp;
                             }
                             ghalf* o16 = a_out16 + (size_t)L.orow[u] * a_ld16 + (nc >> 5) * 64 + (nc & 31);
-                            *(__attribute__((address_space(1))) u32x4_e*)o16 = hv;
-                            *(__attribute__((address_space(1))) u32x4_e*)(o16 + 32) = lv;
+                            store16((__attribute__((address_space(1))) u32x4_e*)o16, hv, a_wt != 0);
+                            store16((__attribute__((address_space(1))) u32x4_e*)(o16 + 32), lv, a_wt != 0);
                         }
                     }
                 }

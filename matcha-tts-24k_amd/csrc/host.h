@@ -81,6 +81,7 @@ inline int run_gemm(Component* c, const GemmArgs& a0, hipStream_t s) {
     a.range_flag = c->cur_flag;
     a.half16 = c->half_now && a.a16_0 != nullptr;
     a.bf16 = a.half16 && c->bf16;
+    a.store_wt = (c->store_wt & WT_GEMM) != 0;
     LAUNCHB(c, 0, gemm_flops(a), gemm_bytes(a), s, launch_gemm(a, s));
     return 0;
 }
@@ -89,6 +90,7 @@ inline int run_attn(Component* c, const AttnArgs& a0, hipStream_t s) {
     a.range_flag = c->cur_flag;
     a.half16 = c->half_now && a.qkv16 != nullptr;
     a.bf16 = a.half16 && c->bf16;
+    a.store_wt = (c->store_wt & WT_ATTN) != 0;
     LAUNCHB(c, 1, attn_flops(a), attn_bytes(a), s, launch_attention(a, s));
     return 0;
 }

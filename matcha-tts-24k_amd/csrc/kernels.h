@@ -23,6 +23,9 @@ extern thread_local const char* g_kernel_tag;
 static inline const char* tf(bool b) { return b ? "true" : "false"; }
 
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_SNAKE = 3, ACT_GELU = 4 };
+// Bits of Switches::store_wt (model.h): the kernel families whose P16 output images leave with write-through stores
+// (device_utils.h store16).  Each launch's argument block carries its family's bit(s) as `store_wt`.
+enum StoreWt { WT_GEMM = 1, WT_CONV_GN = 2, WT_CHAIN_X = 4, WT_CHAIN_QKV = 8, WT_ATTN = 16, WT_ALL = 31 };
 
 // C[M,N] = epi( pro(A)[M,K] . W[N,K]^T )   -- see gemm_f32.hip for the tiling.
 struct GemmArgs {
@@ -113,6 +116,7 @@ struct GemmArgs {
     // fp16-split arithmetic only: set to 1 (sticky, atomicOr) when an operand this launch splits -- an A element while staging
     // (gemm_f32.hip, terms 2) or an out16 element (epilogue) -- lies beyond +-65504 and saturates.  Null = no check.
     unsigned int* range_flag = nullptr;
+    bool store_wt = false;            // P16 kernel, two-plane images only: out16 leaves with write-through stores (StoreWt WT_GEMM)
     // diagnostic builds only (-DMTTS_KSTAMP, tools/kstamp.py): per workgroup 8 words = s_memtime at kernel start, first tile
     // landed, loop end, epilogue end, then s_memrealtime at start and end.  No output value depends on them.
     unsigned long long* kstamp = nullptr;
@@ -167,6 +171,7 @@ struct AttnArgs {
     unsigned int* range_flag = nullptr;   // P16 output: sticky flag for values beyond +-65504 (GemmArgs::range_flag)
     bool half16 = false;          // q|k|v and the output are H16 images (GemmArgs::half16): a head = 64 contiguous halves
     bool bf16 = false;            // ... holding bfloat16 instead of fp16 values (GemmArgs::bf16)
+    bool store_wt = false;        // P16 (two-plane) output: lanes l and l ^ 32 pair up for 16-byte write-through stores (StoreWt WT_ATTN)
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
 static inline double attn_flops(const AttnArgs& a) { return 4.0 * double(a.B) * a.H * double(a.T) * a.T * a.D; }
@@ -197,6 +202,7 @@ struct ConvGnArgs {
     _Float16* out16 = nullptr; int ld16 = 0;
     const float* out16_mask = nullptr;
     unsigned int* range_flag = nullptr;
+    bool store_wt = false;            // out16 leaves with write-through stores (StoreWt WT_CONV_GN)
 };
 bool conv_gn_supported(int T, int N);
 hipError_t launch_conv_gn(const ConvGnArgs& a, hipStream_t s);
@@ -245,6 +251,8 @@ struct ChainArgs {
     float* pair_part = nullptr;
     unsigned int* pair_flag = nullptr;
     unsigned int pair_epoch = 0;         // a value no earlier launch on these flags used
+    int store_wt = 0;                    // StoreWt bits WT_CHAIN_X (x_out) and WT_CHAIN_QKV (qkv16, lanes q and q ^ 1 pair up for 16-byte stores:
+                                         // needs ld_qkv % 8 == 0, else the launcher clears the bit): write-through stores
     int pf_wgs = 0;                      // extra workgroups (lowest ids) that only touch the weight stream ahead of the others; 8 = one per XCD, 16 = two (the model's default; the pair form takes 16: one per XCD and half)
     // diagnostic builds only (-DMTTS_CHAIN_STAMP, tools/chain_stamps.py): s_memtime stamps -- 16 phase stamps of workgroup 0, then
     // (start, end) per workgroup, prefetchers included.  No output value depends on them.

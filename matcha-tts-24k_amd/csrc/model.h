@@ -123,6 +123,12 @@ struct Switches {
     int chain16_qb = 0;         // MTTS_CHAIN16_QB 32 / 64 / 96: rows per workgroup of the one-plane chain (0 = by shape, chain16_plan)
     int resnet_fuse = 3;        // MTTS_RESNET_FUSE: Block1D as one conv + GroupNorm + Mish launch where it applies (resnet_conv.hip) -- bit 0 the first Block1D
                                 // of a ResNet block and the decoder's final one, bit 1 the second, bit 2 lifts the batch gate; 0 = the tiled launches
+    int store_wt = 31;          // MTTS_STORE_WT, bits of kernels.h StoreWt: the families whose P16 output images leave their epilogues with 16-byte write-through
+                                // stores (device_utils.h store16) instead of staying dirty in the L2s until the launch's end -- 1 tiled P16 GEMM, 2 conv_gn, 4 the
+                                // chain's x_out, 8 the chain's q|k|v (lanes paired for 16 bytes), 16 attention (lanes paired).  Bench steps, same box, alternated
+                                // (profiles/r26_store_wt.md): all bits against 0 -0.49 / -0.62 ms (5 of 5 and 4 of 4 pairs, rocprofv3: 0.4..1.7 us less per launch
+                                // of every family); all bits but one against all: +0.24 / +0.15 / +0.16 / +0.29 / +0.18 ms in that order; one bit alone against 0:
+                                // -0.12 / 0.00 / +0.21 / +0.05 / -0.05 ms, all inside the spread -- the bits pay together, not one by one.  Never changes a value.
 };
 Switches read_switches();
 
@@ -147,6 +153,7 @@ struct Component {
     bool fast16 = false;          // mtts_set_arithmetic(ctx, 1) / MTTS_GEMM_TERMS=1: the estimator's P16 kernels multiply the fp16 heads only
     unsigned int* cur_flag = nullptr;   // range flag of the call being enqueued: first word of its workspace (include/mtts.h)
     bool half_now = false;        // set while the estimator's launches are being enqueued in that mode
+    int store_wt = 0;             // Switches::store_wt of the context (0 for the Vocos head and the style encoder: plain stores)
     // profiling
     bool prof_on = false;
     std::vector<ProfRec> prof;

@@ -33,6 +33,7 @@ Switches read_switches() {
     w.chain16_min_rows = num("MTTS_CHAIN16_MIN_ROWS", w.chain16_min_rows);
     { const int qb = num("MTTS_CHAIN16_QB", 0); if (qb == 32 || qb == 64 || qb == 96) w.chain16_qb = qb; }
     w.resnet_fuse = num("MTTS_RESNET_FUSE", w.resnet_fuse) & 7;
+    w.store_wt = num("MTTS_STORE_WT", w.store_wt) & WT_ALL;
     return w;
 }
 
@@ -66,6 +67,7 @@ mtts_ctx* mtts_create(const mtts_config* cfg) {
     c->cfg = g;
     c->sw = read_switches();
     c->gemm_terms = c->sw.gemm_terms;
+    c->store_wt = c->sw.store_wt;
     c->fast16 = c->sw.arith16 == 1; c->half16 = c->sw.arith16 >= 16; c->bf16 = c->sw.arith16 == 17;
     if (c->sw.pair_on) {       // the pair form's residency bound assumes the whole chip: a partitioned or smaller device runs without it
         int dev = 0;

@@ -288,8 +288,8 @@ __global__ __launch_bounds__(512, 1) void conv_gn_kernel(const ConvGnArgs p) {
                 ll[e] = l;
             }
             _Float16* o16 = p.out16 + (size_t)(b * T + row) * p.ld16 + (c0g >> 5) * 64 + (c0g & 31);
-            *reinterpret_cast<f16x8s*>(o16) = hh;
-            *reinterpret_cast<f16x8s*>(o16 + 32) = ll;
+            store16(reinterpret_cast<f16x8s*>(o16), hh, p.store_wt);
+            store16(reinterpret_cast<f16x8s*>(o16 + 32), ll, p.store_wt);
         }
     }
     raise_range_flag(p.range_flag, range_bad);

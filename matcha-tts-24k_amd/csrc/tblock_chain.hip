@@ -21,7 +21,8 @@
 //     compiler-scheduled code (an epilogue, LayerNorm moments) runs, because the compiler may copy such a register before the
 //     load has landed;
 //   * products are computed TRANSPOSED, D^T[channel][row] = W . X^T (A = weight fragment, B = activation fragment): a lane then
-//     holds 4 consecutive channels of one row, so every LDS / global store of an epilogue is 8 bytes of one image line;
+//     holds 4 consecutive channels of one row, so every LDS / global store of an epilogue is 8 bytes of one image line (the q|k|v
+//     image: 16 bytes after a swap between two lanes when it leaves write-through, ChainArgs::store_wt);
 //   * LayerNorm statistics are taken from the LDS tile (one wave per row, two passes), applied after the product as
 //     rstd (x.W'^T - mean rowsum(W')) + b' exactly as gemm_p16.hip does.
 //   * what bounds it is the CU's line-fill rate (~37 B/clk): every workgroup pulls the block's whole fragment stream (7 MB) through
@@ -619,12 +620,13 @@ __global__ __launch_bounds__(64 * CHAIN_NW, 1) void tblock_chain_kernel(const Ch
     {
         constexpr int CPR = C / 4;                        // 16-byte chunks per row
         const int r_lo = pair ? half * (QB / 2) : 0, r_hi = pair ? (half + 1) * (QB / 2) : QB;      // (pair form: each half stores half the rows)
+        const bool wt_x = (p.store_wt & WT_CHAIN_X) != 0;
         for (int idx = tid + r_lo * CPR; idx < r_hi * CPR; idx += 64 * CHAIN_NW) {
             const int row = idx / CPR, cc = idx - row * CPR;
             if (m0 + row < M) {
                 f16x8 v = *reinterpret_cast<const f16x8*>(XT + (cc >> 3) * (QB * 128) + row * 128 + (((cc & 7) ^ ((row >> 1) & 7)) * 16));
                 if (p.x_out_mask && p.x_out_mask[m0 + row] == 0.f) v = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-                *reinterpret_cast<f16x8*>(p.x_out + (size_t)(m0 + row) * p.ld_out + cc * 8) = v;
+                store16(reinterpret_cast<f16x8*>(p.x_out + (size_t)(m0 + row) * p.ld_out + cc * 8), v, wt_x);
             }
         }
     }
@@ -640,6 +642,7 @@ __global__ __launch_bounds__(64 * CHAIN_NW, 1) void tblock_chain_kernel(const Ch
         const int ntiles = p.n_qkv >> 4;
         const int passes = (ntiles + CHAIN_NW * NT - 1) / (CHAIN_NW * NT);
         const bool all_stores = m0 + QB <= M;             // (uniform) no row of the tile is past the end
+        const bool wt_qkv = (p.store_wt & WT_CHAIN_QKV) != 0;
         const int p_half = (passes + 1) / 2;
         const int ps0 = pair ? (half ? p_half : 0) : 0, ps1 = pair ? (half ? passes : p_half) : passes;
         for (int ps = ps0; ps < ps1; ++ps) {
@@ -669,7 +672,20 @@ __global__ __launch_bounds__(64 * CHAIN_NW, 1) void tblock_chain_kernel(const Ch
                         }
                         u32x2 hw, lw;
                         split4(v, 1.0f, hw, lw, rmax);      // unscaled residuals: the attention kernel's operands
-                        if (all_stores || row < M) {
+                        if (wt_qkv) {
+                            // write-through needs 16-byte stores: lanes q and q ^ 1 (lane ^ 16: the same row, the neighbouring 4 channels)
+                            // pair up -- the even one stores the 8 heads, the odd one the 8 residuals 64 bytes further on -- and each first
+                            // hands the other the half it does not store (a cross-lane move, no LDS memory).  Same bits in the same places.
+                            const bool odd = (q & 1) != 0;
+                            u32x2 got;
+                            got[0] = (unsigned int)__shfl_xor((int)(odd ? hw[0] : lw[0]), 16);
+                            got[1] = (unsigned int)__shfl_xor((int)(odd ? hw[1] : lw[1]), 16);
+                            const u32x4 pk = odd ? u32x4{got[0], got[1], lw[0], lw[1]} : u32x4{hw[0], hw[1], got[0], got[1]};
+                            if (all_stores || row < M) {
+                                _Float16* dst = p.qkv16 + (size_t)row * p.ld_qkv + (col >> 5) * 64 + (col & 24) + (odd ? 32 : 0);
+                                store16(reinterpret_cast<u32x4*>(dst), pk, true);
+                            }
+                        } else if (all_stores || row < M) {
                             _Float16* dst = p.qkv16 + (size_t)row * p.ld_qkv + (col >> 5) * 64 + (col & 31);
                             *reinterpret_cast<u32x2*>(dst) = hw;
                             *reinterpret_cast<u32x2*>(dst + 32) = lw;
@@ -703,7 +719,10 @@ static hipError_t launch_chain_shape(const ChainArgs& a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_tblock_chain(const ChainArgs& a, hipStream_t s) {
+hipError_t launch_tblock_chain(const ChainArgs& a_in, hipStream_t s) {
+    ChainArgs a = a_in;
+    // the lane-paired q|k|v stores are 16 bytes wide: rows of whole 16-byte chunks, else that image keeps its plain 8-byte stores
+    if ((a.ld_qkv & 7) || (reinterpret_cast<uintptr_t>(a.qkv16) & 15)) a.store_wt &= ~WT_CHAIN_QKV;
     if (a.pf_wgs < 0 || a.pf_wgs > 64) return hipErrorInvalidValue;
     if (a.M <= 0 || !a.x16 || !a.wstream || !a.x_out || !a.consts) return hipErrorInvalidValue;
     if (!chain_supported(a.C, a.inner, a.n_qkv)) return hipErrorInvalidValue;

@@ -130,6 +130,7 @@ static int chain_run(mtts_chain_args& g, int n_qkv, const ChainMode& m, void* d_
         ah.bf16 = bf;
     } else {
         chain_fill(a, g, n_qkv, d_stream, frags, d_c, att16, ld_att, x16, ld_x, xo16, ld_out, q16, ld_qkv, m.pf_wgs);
+        a.store_wt = read_switches().store_wt & (WT_CHAIN_X | WT_CHAIN_QKV);
         if (pair) {                                       // partial sums + flags of the pair form
             float* d_part = sc.carve<float>(2 * ((size_t)M + MTTS_ENTRY_GUARD_ROWS) * C * 4);
             unsigned int* d_flag = sc.carve<unsigned int>(2 * ((size_t)M / 32 + 2) * 4);
@@ -199,6 +200,7 @@ static int conv_gn_run(mtts_conv_gn_args& g, float eps, bool block, void* d_scra
     a.gamma = g.d_gamma; a.beta = g.d_beta; a.mask = g.d_mask; a.chbias = g.d_chbias; a.chbias_stride = g.d_chbias ? g.chbias_stride : 0;
     a.nrows = g.d_nrows; a.nextra = g.d_nextra; a.bias_stats = g.d_bias_stats;
     a.eps = eps; a.out16 = o16; a.ld16 = ld_out; a.range_flag = g.d_range_flag;
+    a.store_wt = (read_switches().store_wt & WT_CONV_GN) != 0;
     g_kernel_tag = nullptr;
     HIP_OK(launch_conv_gn(a, s));
     if (block) copy_tag(g.tag);
@@ -336,6 +338,7 @@ static int gemm_image_run(mtts_gemm_h16_args* g, int ew, int fast16, float out_l
     a.terms = 2;
     if (!h16) { a.fast16 = fast16 != 0; a.out_lscale = out_lscale; }
     block_epilogue(a, g, o16, r16, ew, r);
+    a.store_wt = (read_switches().store_wt & WT_GEMM) != 0;
     g->wave_rows = gemm_p16_wave_rows(a);
     g_kernel_tag = nullptr;
     HIP_OK(launch_gemm(a, s));
@@ -361,6 +364,7 @@ static int attention_run(const float* d_qkv, const float* d_mask, int B, int T, 
     AttnArgs a;
     a.mask = d_mask; a.klen = m.klen; a.B = B; a.T = T; a.H = H; a.D = D; a.scale = scale; a.mask_mode = mask_mode;
     a.range_flag = m.range_flag;
+    a.store_wt = (read_switches().store_wt & WT_ATTN) != 0;
     _Float16* q16 = static_cast<_Float16*>(d_scratch);
     _Float16* o16 = q16 + (size_t)M * ew * C3;
     if (ew) {
@@ -531,6 +535,7 @@ int mtts_gemm_p16(const float* d_a, int lda, int B, int T_in, int C, int ntaps, 
     a.res = d_res; a.ldr = ldr; a.out_mask = d_out_mask; a.out_scale = out_scale; a.out = d_out; a.ldc = ldc;
     if (d_out16_f32) { a.out16 = o16; a.ld16 = 2 * N; a.out_lscale = out_lscale; }
     a.out_T = T_out; a.out_stride = 1; a.out_off = 0; a.force_bm = force_bm;
+    a.store_wt = (read_switches().store_wt & WT_GEMM) != 0;
     HIP_OK(launch_gemm(a, s));
     if (d_out16_f32) HIP_OK(launch_from_p16(o16, 2 * N, B * T_out, N, out_lscale, d_out16_f32, N, s));
     return 0;
