@@ -28,7 +28,7 @@ extern "C" {
 
 #define MTTS_ABI_VERSION 2
 /* bumped whenever the packed weight image changes layout (invalidates mtts_export_weights caches) */
-#define MTTS_IMAGE_REVISION 6
+#define MTTS_IMAGE_REVISION 7
 
 typedef struct mtts_ctx mtts_ctx;
 
@@ -324,13 +324,28 @@ int mtts_attention_p16(const float* d_qkv, const float* d_mask, int B, int T, in
  * halves with lane (r = lane & 15, q = lane >> 4) holding panel row n0 + r, columns k0 + 8 q .. + 7 (the A operand of
  * v_mfma_f32_16x16x32_f16).  h_dst: mtts_chain_stream_frags(...) * 8 * 512 halves. */
 int64_t mtts_chain_stream_frags(int C, int inner, int ch, int n_qkv);
-/* Threading / sharing note for the estimator entry points: between 3000 and 6000 estimator rows the transformer blocks run the PAIR
- * form of the chain launch (below), in which two workgroups wait for each other inside the kernel.  It assumes the launch has the GPU
+/* Threading / sharing note for the estimator entry points: between 3000 and 5760 estimator rows the transformer blocks of width 384
+ * (hidden chunk 256; mtts_tblock_plan) run the PAIR form of the chain launch (below), in which two workgroups wait for each other inside the kernel.  It assumes the launch has the GPU
  * to itself (one stream per device at a time); a process that shares a device between several contexts sets MTTS_CHAIN_PAIR=0.  A
  * workgroup whose partner does not arrive within ~0.5 s gives up and sets the second word of the workspace header. */
 /* The model's launch plan of a chain launch over M rows (hidden chunk ch = 128 / 256): rows per workgroup and the number of
  * prefetch workgroups (MTTS_CHAIN_PF as set at this call, default 16).  Host arithmetic only. */
 int mtts_chain_plan(int M, int ch, int* qb, int* prefetch_wgs);
+/* 1 when the chain kernel is instantiated for (width C, rows per workgroup qb, hidden chunk ch), else 0: the one table the launcher
+ * dispatches through.  Host only. */
+int mtts_chain_shape_exists(int C, int qb, int ch);
+/* How the estimator runs the row-local part of a transformer block of width C (attention width inner; n_qkv: width of the
+ * following block's q|k|v, 0 for the last block of a run) at each of the `count` row counts M, M + 1, ..: the decision
+ * mtts_decoder_forward / mtts_cfm_solve take per block and level in the default arithmetic, for a context created under these
+ * switch values (MTTS_CHAIN, MTTS_CHAIN_CH, MTTS_CHAIN_QB, MTTS_CHAIN_PF, MTTS_CHAIN_MIN_ROWS, MTTS_CHAIN_PAIR,
+ * MTTS_CHAIN_PAIR_MIN_ROWS) on a whole device.  The environment is not read.  *ch: the hidden chunk the block's streams are
+ * packed for; arrays of `count`: form[i] 0 = four tiled GEMM launches, 1 = the chain launch, 2 = its pair form; for forms 1 and 2
+ * qb[i] rows per workgroup (mtts_chain_shape_exists(C, qb[i], *ch) holds), grid_wgs[i] row-tile workgroups (pair: 16 *
+ * ceil(ceil(M / qb) / 8)), prefetch_wgs[i] prefetch workgroups; zeros for form 0.  The pair form is taken at C = 384 with hidden
+ * chunk 256 only -- the one shape it was measured at -- and only such blocks carry a pair stream in the weight image.  Host
+ * arithmetic only. */
+int mtts_tblock_plan(int C, int inner, int n_qkv, int M, int count, int chain_on, int chain_ch, int chain_qb, int chain_pf,
+                     int chain_min_rows, int pair_on, int pair_min_rows, int* ch, int* form, int* qb, int* grid_wgs, int* prefetch_wgs);
 int mtts_chain_stream_pack(int C, int inner, int ch, int n_qkv, const float* h_w_out, const float* h_w1, const float* h_w2,
                            const float* h_w_qkv, uint16_t* h_dst);
 /* pair form (below): fragments per (half, wave) and the packing of the 2 x 8 streams, [half][wave][fragment][64 lanes][8 halves];

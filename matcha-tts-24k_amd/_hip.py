@@ -227,6 +227,8 @@ def load() -> C.CDLL:
         "mtts_attention_f32": (i32, [vp, vp, i32, i32, i32, i32, f32, i32, vp, vp]),
         "mtts_chain_stream_frags": (i64, [i32, i32, i32, i32]),
         "mtts_chain_plan": (i32, [i32, i32, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "mtts_chain_shape_exists": (i32, [i32, i32, i32]),
+        "mtts_tblock_plan": (i32, [i32] * 12 + [C.POINTER(C.c_int)] * 5),
         "mtts_chain_stream_frags_pair": (i64, [i32, i32, i32, i32]),
         "mtts_chain_stream_pack_pair": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp]),
         "mtts_chain_stream_pack": (i32, [i32, i32, i32, i32, vp, vp, vp, vp, vp]),
@@ -1137,6 +1139,21 @@ class HipModel:
         buf = C.create_string_buffer(max_bytes)
         n = size(self.lib.mtts_prof_tags(self.ctx, buf, max_bytes))
         return buf.value.decode().split("\n")[:n]
+
+
+# ---------------------------------------------------------------------- host-only plans
+def tblock_plan(width: int, inner: int, n_qkv: int, M: int, count: int = 1, *, chain_on: int = 1, chain_ch: int = 256, chain_qb: int = 0,
+                chain_pf: int = 16, chain_min_rows: int = 5761, pair_on: int = 1, pair_min_rows: int = 3000):
+    """The estimator's launch form of a transformer block's row-local part at the row counts M .. M + count - 1 (mtts_tblock_plan; the
+    keyword defaults are those of csrc/model.h ``Switches``; the environment is not read).  Returns ``(ch, form, qb, grid, prefetch)``:
+    the packed hidden chunk and four int32 arrays of ``count`` -- form 0 tiled launches, 1 chain launch, 2 its pair form."""
+    lib = load()
+    out = [np.zeros(count, dtype=np.int32) for _ in range(4)]
+    ch = C.c_int(0)
+    ip = C.POINTER(C.c_int)
+    check(lib.mtts_tblock_plan(width, inner, n_qkv, M, count, chain_on, chain_ch, chain_qb, chain_pf, chain_min_rows, pair_on, pair_min_rows,
+                               C.byref(ch), *[a.ctypes.data_as(ip) for a in out]))
+    return (ch.value, *out)
 
 
 # ---------------------------------------------------------------------- single kernels (used by the parity tests)

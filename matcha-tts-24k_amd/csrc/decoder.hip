@@ -21,12 +21,36 @@ void chain_plan(int M, int ch, int qb_forced, int want, int* qb, int* pf) {
     *qb = (qb_forced == 32 || qb_forced == qb_big) ? qb_forced : (fits32 ? 32 : qb_big);
     *pf = one_round_prefetchers(M, *qb, want);
 }
+constexpr int PAIR_QB = 48;      // rows per tile of the model's pair launches
+bool tblock_pair_possible(const Switches& sw, int C, int inner, int n_qkv, int ch) {
+    return sw.pair_on && C == 384 && ch == 256 && chain_supported_pair(C, inner, ch, n_qkv) && chain_shape_exists(C, PAIR_QB, ch);
+}
+// The chain launch when the stream was packed and the batch is large enough that a workgroup per qb rows fills the chip: every
+// workgroup streams ALL of the chain's weights (~7 MB at width 384), which only pays when their cost is shared by many rows per CU
+// (DESIGN.md section 5).  Below chain_min_rows, from pair_min_rows on: the pair form -- two workgroups of one XCD per 48-row tile,
+// each streaming half of the FeedForward and of the q|k|v passes -- while all of them (and the prefetchers) are resident at once.
+// Everything else, and any shape the launcher has no kernel for: the tiled launches.
+TBlockPlan tblock_plan(const Switches& sw, int C, int inner, int n_qkv, int ch, int M, bool has_chain, bool has_pair) {
+    TBlockPlan p;
+    if (M <= 0 || !chain_supported(C, inner, n_qkv)) return p;
+    if (has_chain && M >= sw.chain_min_rows) {
+        int qb = 0, pf = 0;
+        chain_plan(M, ch, sw.chain_qb, sw.chain_pf, &qb, &pf);
+        if (!chain_shape_exists(C, qb, ch)) return p;
+        p.form = 1; p.qb = qb; p.grid = (M + qb - 1) / qb; p.pf = pf;
+        return p;
+    }
+    const int grid = 16 * (((M + PAIR_QB - 1) / PAIR_QB + 7) / 8);
+    if (has_pair && tblock_pair_possible(sw, C, inner, n_qkv, ch) && M >= sw.pair_min_rows && grid + 16 <= CHIP_CUS) {
+        p.form = 2; p.qb = PAIR_QB; p.grid = grid;
+        p.pf = sw.chain_pf ? 16 : 0;      // two per XCD, one per half (pair grids are admitted up to 240 workgroups)
+    }
+    return p;
+}
 static int run_chain(mtts_ctx* c, const ChainArgs& a0, hipStream_t s) {
     ChainArgs a = a0;
     a.range_flag = c->cur_flag;
-    { int qb_unused = 0; chain_plan(a.M, a.ch, a.qb, c->sw.chain_pf, &qb_unused, &a.pf_wgs); }
     a.store_wt = c->store_wt & (WT_CHAIN_X | WT_CHAIN_QKV);
-    if (a.pair) a.pf_wgs = c->sw.chain_pf ? 16 : 0;      // two per XCD, one per half (the model admits pair grids up to 240 workgroups)
     LAUNCHB(c, 0, chain_flops(a), chain_bytes(a), s, launch_tblock_chain(a, s));
     return 0;
 }
@@ -382,10 +406,11 @@ static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, int C, i
         p.a_mean = d.mean; p.a_rstd = d.rstd;
         return 0;
     };
-    // the row-local part as one launch (tblock_chain.hip) when the stream was packed and the batch is large enough that a
-    // workgroup per QB rows fills the chip: every workgroup streams ALL of the chain's weights (~7 MB at width 384), which
-    // only pays when their cost is shared by many rows per CU
-    const bool chain = t.chain_frags > 0 && !t.chain_h16 && d.p16 && !c->half_now && M >= c->sw.chain_min_rows && (emit_stats ? t.chain_nqkv > 0 : true);
+    // the row-local part as one launch (tblock_chain.hip), in its single-workgroup or its pair form, or as the tiled launches below:
+    // tblock_plan decides from the row count and the switches; here only what this call can use of the block's packed streams
+    const bool p16_streams = t.chain_frags > 0 && !t.chain_h16 && d.p16 && !c->half_now && (emit_stats ? t.chain_nqkv > 0 : true);
+    const TBlockPlan plan = tblock_plan(c->sw, C, inner, t.chain_nqkv, t.chain_ch, M, p16_streams,
+                                        p16_streams && t.chain_pair_frags > 0 && d.pair_flag != nullptr);
     // 16-bit storage modes: the one-plane chain (tblock_chain_h16.hip) from chain16_min_rows rows on; below, the four tiled launches
     const bool chain16 = t.chain_frags > 0 && t.chain_h16 && d.p16 && c->half_now && d.ew == 1 && M >= c->sw.chain16_min_rows &&
                          (emit_stats ? t.chain_nqkv > 0 : true);
@@ -402,11 +427,6 @@ static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, int C, i
     at.mask = d.kb(lvl); at.B = B; at.T = T; at.H = g.dec_heads; at.D = g.dec_head_dim;
     at.scale = 1.0f / sqrtf((float)g.dec_head_dim); at.mask_mode = 0; at.klen = d.nr(lvl); at.fast16 = c->fast16;
     RET_IF(run_attn(c, at, s));
-    // below that row count: the pair form -- two workgroups of one XCD per 48-row tile, each streaming half of the FeedForward
-    // and of the q|k|v passes -- while all of them (and the prefetchers) are resident at once
-    const int tiles48 = (M + 47) / 48;
-    const bool pair = !chain && !chain16 && c->sw.pair_on && t.chain_pair_frags > 0 && d.p16 && !c->half_now && d.pair_flag && M >= c->sw.pair_min_rows &&
-                      16 * ((tiles48 + 7) / 8) + 16 <= CHIP_CUS && (emit_stats ? t.chain_nqkv > 0 : true);
     // what both chain launches take (kernels.h ChainArgs / ChainH16Args), ew halves per image element
     auto bind_chain = [&](auto& a, int ew) {
         a.M = M; a.C = C; a.inner = inner;
@@ -430,12 +450,12 @@ static int transformer_block(mtts_ctx* c, DecBufs& d, const TBlockW& t, int C, i
         a.bf16 = c->bf16;
         return run_chain_h16(c, a, s);
     }
-    if (chain || pair) {                  // (image flow, P16: rows of 2 halves per channel)
+    if (plan.form) {                      // (image flow, P16: rows of 2 halves per channel)
         ChainArgs a;
         bind_chain(a, 2);
-        { int pf_unused = 0; chain_plan(M, a.ch, c->sw.chain_qb, c->sw.chain_pf, &a.qb, &pf_unused); }
-        if (pair) {
-            a.pair = 1; a.qb = 48;
+        a.qb = plan.qb; a.pf_wgs = plan.pf;
+        if (plan.form == 2) {
+            a.pair = 1;
             a.wstream = reinterpret_cast<const _Float16*>(W(c, t.chain_pair)); a.stream_frags = t.chain_pair_frags;
             a.pair_part = d.FF;              // (the tiled path's hidden image: unused by a chain launch)
             a.pair_flag = d.pair_flag;

@@ -114,6 +114,18 @@ inline int begin_call(Component* c, void* d_ws, hipStream_t s) {
 
 // Launch plan of a chain launch over M rows (decoder.hip; mtts_chain_plan reports it)
 void chain_plan(int M, int ch, int qb_forced, int want, int* qb, int* pf);
+// How a transformer block's row-local part runs in the default (P16) arithmetic -- THE launch-form decision (decoder.hip), shared by
+// transformer_block, the packer and mtts_tblock_plan.  form 0: the four tiled GEMM launches; 1: the chain launch; 2: its pair form.
+// For forms 1 and 2 (C, qb, ch) is a shape of kernels.h chain_shape_exists, grid the row-tile workgroups and pf the prefetch ones.
+struct TBlockPlan { int form = 0, qb = 0, grid = 0, pf = 0; };
+// n_qkv: width of the following block's q|k|v (0 for the last block of a run); ch: the hidden chunk the block's streams are packed
+// for (chain_packed_ch); has_chain / has_pair: that stream is in the weight image and the call can use it.
+TBlockPlan tblock_plan(const Switches& sw, int C, int inner, int n_qkv, int ch, int M, bool has_chain, bool has_pair);
+// Hidden chunk the chain streams of a width-C block are packed for under MTTS_CHAIN_CH = chain_ch
+inline int chain_packed_ch(int C, int chain_ch) { return (C == 384 && chain_ch == 256) ? 256 : 128; }
+// Whether tblock_plan can answer "pair" for such a block at some row count and thresholds: what the packer packs a pair stream for.
+// The pair form launches 48-row tiles, and it was measured at width 384 with hidden chunk 256 only (profiles/r03_pair_ab.log).
+bool tblock_pair_possible(const Switches& sw, int C, int inner, int n_qkv, int ch);
 
 // ------------------------------------------------------------------------------------------------ workspace
 struct WS {

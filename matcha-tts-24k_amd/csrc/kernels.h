@@ -269,6 +269,16 @@ long chain_stream_frags_pair(int C, int inner, int ch, int n_qkv);       // pair
 void chain_stream_pack_pair(int C, int inner, int ch, int n_qkv, const float* w_out, const float* w1, const float* w2, const float* w_qkv,
                             uint16_t* dst, bool* saturates);             // dst: 2 * 8 * chain_stream_frags_pair(...) * 512 halves
 bool chain_supported_pair(int C, int inner, int ch, int n_qkv);
+// The instantiation table of tblock_chain_kernel<C, QB, CH>, stated ONCE: launch_tblock_chain dispatches through it, chain_shape_exists
+// reads it, and the model's launch decision (host.h tblock_plan) and packer never name a (C, qb, ch) outside it.
+#define MTTS_CHAIN_SHAPES(X) \
+    X(384, 64, 128) X(384, 32, 128) X(384, 48, 256) X(384, 32, 256) X(256, 64, 128) X(256, 32, 128) X(128, 64, 128) X(128, 32, 128)
+inline bool chain_shape_exists(int C, int qb, int ch) {
+#define MTTS_CHAIN_SHAPE_IS(c_, qb_, ch_) if (C == c_ && qb == qb_ && ch == ch_) return true;
+    MTTS_CHAIN_SHAPES(MTTS_CHAIN_SHAPE_IS)
+#undef MTTS_CHAIN_SHAPE_IS
+    return false;
+}
 hipError_t launch_tblock_chain(const ChainArgs& a, hipStream_t s);
 static inline double chain_flops(const ChainArgs& a) {
     return 2.0 * double(a.M) * (double(a.C) * a.inner + 8.0 * double(a.C) * a.C + double(a.C) * a.n_qkv);

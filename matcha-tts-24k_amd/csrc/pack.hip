@@ -287,15 +287,15 @@ int pack_all(mtts_ctx* c, bool dry) {
         for (size_t k = 0; k < D.tb.size(); ++k) {
             TBlockW& t = D.tb[k];
             const int C = t.out.N, nq = ((int)(k % nb) + 1 < nb) ? D.tb[k + 1].qkv.N : 0;
-            const int ch = (C == 384 && c->sw.chain_ch == 256) ? 256 : 128;
-            if (!chain_supported(C, inner, nq) || t.ff1.N != 4 * C || t.ff1.ktap != C || t.ff2.ktap != 4 * C || t.out.ktap != inner) continue;
+            const int ch = chain_packed_ch(C, c->sw.chain_ch);
+            if (!chain_supported(C, inner, nq) || !chain_shape_exists(C, 32, ch) || t.ff1.N != 4 * C || t.ff1.ktap != C || t.ff2.ktap != 4 * C || t.out.ktap != inner) continue;
             if (nq && D.tb[k + 1].qkv.ktap != C) continue;
             t.chain_frags = chain_stream_frags(C, inner, ch, nq);
             t.chain_ch = ch;
             t.chain_nqkv = nq;
             t.next = nq ? (int)k + 1 : -1;
             t.chain = P.alloc((size_t)t.chain_frags * CHAIN_WAVES * 256);
-            if (c->sw.pair_on && chain_supported_pair(C, inner, ch, nq)) {
+            if (tblock_pair_possible(c->sw, C, inner, nq, ch)) {      // only where the launch decision can take the pair form
                 t.chain_pair_frags = chain_stream_frags_pair(C, inner, ch, nq);
                 t.chain_pair = P.alloc((size_t)t.chain_pair_frags * 2 * CHAIN_WAVES * 256);
                 if (!dry) chain_stream_pack_pair(C, inner, ch, nq, &c->image[t.out.w], &c->image[t.ff1.w], &c->image[t.ff2.w],
@@ -324,7 +324,7 @@ int pack_all(mtts_ctx* c, bool dry) {
         for (size_t k = 0; k < D.tb.size(); ++k) {
             TBlockW& t = D.tb[k];
             const int C = t.out.N, nq = ((int)(k % nb) + 1 < nb) ? D.tb[k + 1].qkv.N : 0;
-            const int ch = (C == 384 && c->sw.chain_ch == 256) ? 256 : 128;
+            const int ch = chain_packed_ch(C, c->sw.chain_ch);
             if (!chain_h16_supported(C, inner, ch, nq) || t.ff1.N != 4 * C || t.ff1.ktap != C || t.ff2.ktap != 4 * C || t.out.ktap != inner) continue;
             if (nq && D.tb[k + 1].qkv.ktap != C) continue;
             t.chain_frags = chain_h16_stream_frags(C, inner, ch, nq);

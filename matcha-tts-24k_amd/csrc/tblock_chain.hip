@@ -733,18 +733,11 @@ hipError_t launch_tblock_chain(const ChainArgs& a_in, hipStream_t s) {
         if (!chain_supported_pair(a.C, a.inner, a.ch, a.n_qkv) || !a.pair_part || !a.pair_flag || a.pair_epoch == 0 || (a.pf_wgs & 7)) return hipErrorInvalidValue;
         if (a.stream_frags != chain_stream_frags_pair(a.C, a.inner, a.ch, a.b_qkv ? a.n_qkv : 0)) return hipErrorInvalidValue;
     } else if (a.stream_frags != chain_stream_frags(a.C, a.inner, a.ch, a.b_qkv ? a.n_qkv : 0)) return hipErrorInvalidValue;
-    if (a.C == 384) {
-        if (a.ch == 128 && a.qb == 64) return launch_chain_shape<384, 64, 128>(a, s);
-        if (a.ch == 128 && a.qb == 32) return launch_chain_shape<384, 32, 128>(a, s);
-        if (a.ch == 256 && a.qb == 48) return launch_chain_shape<384, 48, 256>(a, s);
-        if (a.ch == 256 && a.qb == 32) return launch_chain_shape<384, 32, 256>(a, s);
-    } else if (a.C == 256) {
-        if (a.ch == 128 && a.qb == 64) return launch_chain_shape<256, 64, 128>(a, s);
-        if (a.ch == 128 && a.qb == 32) return launch_chain_shape<256, 32, 128>(a, s);
-    } else if (a.C == 128) {
-        if (a.ch == 128 && a.qb == 64) return launch_chain_shape<128, 64, 128>(a, s);
-        if (a.ch == 128 && a.qb == 32) return launch_chain_shape<128, 32, 128>(a, s);
-    }
+    if (!chain_shape_exists(a.C, a.qb, a.ch)) return hipErrorInvalidValue;
+    // (the table itself: kernels.h MTTS_CHAIN_SHAPES)
+#define MTTS_CHAIN_DISPATCH(c_, qb_, ch_) if (a.C == c_ && a.qb == qb_ && a.ch == ch_) return launch_chain_shape<c_, qb_, ch_>(a, s);
+    MTTS_CHAIN_SHAPES(MTTS_CHAIN_DISPATCH)
+#undef MTTS_CHAIN_DISPATCH
     return hipErrorInvalidValue;
 }
 

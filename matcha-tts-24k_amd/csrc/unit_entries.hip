@@ -613,6 +613,28 @@ int mtts_chain_plan(int M, int ch, int* qb, int* prefetch_wgs) {
     chain_plan(M, ch, 0, read_switches().chain_pf, qb, prefetch_wgs);
     return 0;
 }
+int mtts_chain_shape_exists(int C, int qb, int ch) { return chain_shape_exists(C, qb, ch) ? 1 : 0; }
+// the model's launch-form decision (decoder.hip tblock_plan) for `count` consecutive row counts, with the switches as arguments
+int mtts_tblock_plan(int C, int inner, int n_qkv, int M, int count, int chain_on, int chain_ch, int chain_qb, int chain_pf, int chain_min_rows,
+                     int pair_on, int pair_min_rows, int* ch, int* form, int* qb, int* grid_wgs, int* prefetch_wgs) {
+    if (M <= 0 || count <= 0 || count > (1 << 24) - M || inner < 0 || n_qkv < 0 || (chain_ch != 128 && chain_ch != 256) || chain_qb < 0 ||
+        chain_pf < 0 || chain_pf > 64 || !ch || !form || !qb || !grid_wgs || !prefetch_wgs) {
+        set_error("mtts_tblock_plan: bad argument");
+        return -1;
+    }
+    Switches sw;
+    sw.chain_on = chain_on != 0; sw.chain_ch = chain_ch; sw.chain_qb = chain_qb; sw.chain_pf = chain_pf; sw.chain_min_rows = chain_min_rows;
+    sw.pair_on = pair_on != 0; sw.pair_min_rows = pair_min_rows;
+    *ch = chain_packed_ch(C, chain_ch);
+    // what pack_all leaves in the image of a default-arithmetic context for such a block
+    const bool has_chain = sw.chain_on && chain_supported(C, inner, n_qkv) && chain_shape_exists(C, 32, *ch);
+    const bool has_pair = has_chain && tblock_pair_possible(sw, C, inner, n_qkv, *ch);
+    for (int i = 0; i < count; ++i) {
+        const TBlockPlan p = tblock_plan(sw, C, inner, n_qkv, *ch, M + i, has_chain, has_pair);
+        form[i] = p.form; qb[i] = p.qb; grid_wgs[i] = p.grid; prefetch_wgs[i] = p.pf;
+    }
+    return 0;
+}
 int64_t mtts_chain_stream_frags(int C, int inner, int ch, int n_qkv) {
     if (!chain_supported(C, inner, n_qkv) || (ch != 128 && ch != 256)) { set_error("mtts_chain_stream_frags: unsupported shape"); return -1; }
     return chain_stream_frags(C, inner, ch, n_qkv);

@@ -40,7 +40,7 @@ def test_new_entries_are_declared_exported_and_bound_with_matching_arity_and_typ
     for name in NEW:
         assert callable(getattr(hip, name[len("mtts_"):]))
     assert lib.mtts_abi_version() == 2
-    assert re.search(r"#define\s+MTTS_ABI_VERSION\s+2\b", header) and re.search(r"#define\s+MTTS_IMAGE_REVISION\s+6\b", header)
+    assert re.search(r"#define\s+MTTS_ABI_VERSION\s+2\b", header) and re.search(r"#define\s+MTTS_IMAGE_REVISION\s+7\b", header)
 
 
 def refused(lib, rc, needle):

@@ -96,7 +96,7 @@ def test_bindings_exist_and_match_the_header(lib):
     header = (ROOT / "include" / "mtts.h").read_text()
     # (declaration, export, arity and types: test_abi.py checks them for every entry of the header)
     assert re.search(r"#define MTTS_ABI_VERSION 2\b", header) and lib.mtts_abi_version() == 2     # entries are only added
-    assert re.search(r"#define MTTS_IMAGE_REVISION 6\b", header)
+    assert re.search(r"#define MTTS_IMAGE_REVISION 7\b", header)
     tile = int(re.search(r"#define MTTS_LOUDNESS_TILE (\d+)", header).group(1))
     chunks = int(re.search(r"#define MTTS_LOUDNESS_CHUNKS (\d+)", header).group(1))
     L = sub("loudness")

@@ -27,7 +27,7 @@ def test_symbols_declared_exported_and_bound(lib):
         if name != "mtts_score_workspace_bytes":
             assert getattr(lib, name).restype is C.c_int, name
     assert lib.mtts_abi_version() == 2
-    assert "MTTS_ABI_VERSION 2" in header and "MTTS_IMAGE_REVISION 6" in header
+    assert "MTTS_ABI_VERSION 2" in header and "MTTS_IMAGE_REVISION 7" in header
     assert "score.hip" in sub("_hip").SOURCES
     hip = sub("_hip").HipModel
     for method in ("decoder_forward_rows", "cfm_loss", "score_prior_dur", "score_status"):
