@@ -1027,7 +1027,8 @@ int mtts_pcm_status(const int64_t* d_verdict, int B, void* stream);
 /* A row becomes one complete mono, 16-bit, fixed-blocksize FLAC stream (RFC 9639): the compressed form of the "pcm" bytes above, about
  * 0.7 of their size on speech.  The encoder is deterministic: every byte is a function of the row's samples, its rate, the block size
  * and (seed, key), and of nothing else -- not of the batch, the row index or the grid.  tests/flac_restated.py restates it in NumPy bit
- * for bit, beside an independent decoder.  Out of scope: decoding FLAC, LPC subframes, stereo, the MD5 signature, seek tables.
+ * for bit, beside an independent decoder.  Out of scope: writing LPC subframes or stereo, the MD5 signature, seek tables ("FLAC in"
+ * below reads them).
  *
  *   samples:  q[i] is exactly the PCM16 word mtts_pcm_encode writes for the row: the same arithmetic, the same dither as a function of
  *             (seed, key, i) when dither is on (the same device functions, csrc/pcm_quantise.h).
@@ -1074,6 +1075,74 @@ int64_t mtts_flac_workspace_bytes(int B, int64_t ld, int block_size);
 int mtts_flac_encode(const float* d_audio, int64_t ld, const int64_t* d_lengths, const int32_t* d_rates, const int64_t* d_keys, int B,
                      int block_size, int dither, int64_t seed, uint8_t* d_out, int64_t out_ld, int64_t* d_out_bytes, void* d_ws,
                      int64_t ws_bytes, void* stream);
+
+/* ---------------------------------------------------------------- FLAC in: recordings decoded on the device */
+
+/* A ragged batch of whole native FLAC streams (RFC 9639) becomes fp32 rows: channel 0 of each stream, integers to the bit.  The frame
+ * decoder is general -- LPC, stereo decorrelation, 8 to 24 bits, metadata, any block size up to 4608 -- so files written by other
+ * encoders are read, not only the streams of mtts_flac_encode.  A row's samples depend on its bytes alone, not on the batch, the row
+ * index or the strides; the verdict is per row and nothing waits for the host.  tests/flac_in_restated.py restates the rules below
+ * in Python beside a stream writer; csrc/flac_parse.h is the parser, compiled for the host and for the device.
+ *
+ *   input:    d_data uint8 [B][ld_bytes] (ld_bytes % 16 == 0, 16-byte aligned); row b is one stream of d_nbytes[b] bytes (device int64).
+ *             An nbytes outside [0, ld_bytes] refuses the row.
+ *   metadata: "fLaC"; then metadata blocks, each a byte (last flag, 7-bit type) and a 24-bit length.  The first block is STREAMINFO
+ *             (type 0, 34 bytes) and no later block is; type 127, a block that runs off the row and a chain without a last block are
+ *             refused.  Every other block is skipped by its length, whatever it holds.  STREAMINFO must name: 8..24 bits per sample,
+ *             a rate >= 1, 16 <= min block size <= max block size <= max_block (1..8 channels follow from its 3 bits).
+ *   candidate: a byte position is a candidate when it holds a frame header: sync FF F8 / FF F9 (the low bit: variable blocking); block-
+ *             size code != 0000 (0001: 192; 0010..0101: 576 << (code - 2); 0110 / 0111: an 8- / 16-bit tail + 1; 1000..1111: 1 << code);
+ *             rate code != 1111 (0000: STREAMINFO's; 0001..1011 the eleven fixed rates; 1100: 8-bit kHz; 1101: 16-bit Hz; 1110: 16-bit
+ *             tens of Hz); channel assignment 0..7 (that many + 1 independent channels), 8 left/side, 9 side/right, 10 mid/side;
+ *             sample-size code != 011 (000: STREAMINFO's; 8, 12, -, 16, 20, 24, 32 bits); a reserved 0 bit; the coded number, UTF-8-like,
+ *             1 to 7 bytes (up to 36 bits; over-long forms are taken as they are); the block-size tail; the rate tail; the CRC-8
+ *             (polynomial 0x07) of the header so far.  And the header agrees with STREAMINFO: the same rate, the same bits per sample,
+ *             the same channel count, a block size <= STREAMINFO's maximum.  A header is at most 16 bytes.
+ *   subframe: a 0 bit; 6-bit type; wasted-bits flag, and when set a unary count w: wasted = w + 1 < the subframe's bits.  The subframe's
+ *             bits are the frame's, + 1 for a side channel, - wasted.  Types: 000000 CONSTANT; 000001 VERBATIM; 001000..001100 FIXED of
+ *             order 0..4; 1ooooo LPC of order ooooo + 1 (1..32); every other type is refused, and an order above the block size.
+ *             LPC: a 4-bit precision - 1 (1111 is refused), a 5-bit shift (two's complement; negative is refused), the coefficients.
+ *             Residual: 2-bit method (00: 4-bit Rice parameters, 01: 5-bit; 1x refused); 4-bit partition order po: 2^po must divide
+ *             the block and block >> po must be >= the predictor order (equal: the first partition is empty).  Per partition the
+ *             parameter k, or all ones: the escape, a 5-bit width 0..31 and raw two's-complement residuals.  A Rice code is q zero
+ *             bits, a one, k bits: u = q << k | low must stay below 2^32 - 1 (a residual is inside (-2^31, 2^31)); r = u >> 1 for even
+ *             u, -(u >> 1) - 1 for odd.  Restore: x[i] = r[i] + prediction, the FIXED polynomials or (sum_j c[j] x[i-1-j]) >> shift with
+ *             the sum in 64 bits (25-bit samples, 15-bit coefficients and 32 taps need 45) and an arithmetic shift; the sample is the
+ *             low 32 bits.  Then x << wasted.
+ *   frame:    a candidate is a frame when its subframes (one per channel) parse inside the row, zero to seven padding bits (not looked
+ *             at) reach a byte boundary, and the next two bytes are the CRC-16 (polynomial 0x8005) of everything before them.  Channel
+ *             0 of its samples: the first channel (independent, left/side); side + right; or (((mid << 1) | (side & 1)) + side) >> 1.
+ *             Each must lie in [-2^(bps-1), 2^(bps-1)).  Channels 2..8 are parsed for their length only.
+ *   row:      accepted when, starting at the first byte behind the metadata, frames follow one another end to start up to exactly
+ *             d_nbytes[b]; all carry the blocking bit of the first; the coded numbers are consecutive from 0 -- frame numbers when the
+ *             bit is 0, and when it is 1 sample numbers that each equal the sum of the block sizes before; with bit 0 every frame has
+ *             the first frame's block size but the last, which may be shorter; and the sample total equals STREAMINFO's and is <= ld.
+ *             Candidates off that walk are ignored (a sync pattern in a PADDING block, a whole valid frame inside a VERBATIM payload).
+ *             STREAMINFO's total 0 with no frame is an empty clip of length 0; total 0 with frames (unknown length) is refused.
+ *   output:   d_out fp32 [B][ld] (ld % 4 == 0, 16-byte aligned): sample q as q / 2^(bps-1), exact in fp32; zeros from the length up to
+ *             ld; d_out_lengths[b] the sample count; d_out_rates[b] STREAMINFO's rate.
+ *   refusals: everything else -- a CRC mismatch, a truncated or missing frame, a unary run or raw read that would pass the end of the
+ *             row (the reader returns zeros there and the row is refused), a residual outside 32 bits, more than ld / 16 + 64
+ *             candidates or 2 * ld + max_block staged samples in a row -- gives d_out_lengths[b] = -1 and d_out_rates[b] = 0; no word
+ *             of that row of d_out is written and the other rows are unaffected.  mtts_pcm_status reads the verdict as it does for
+ *             the PCM entries.
+ * Out of scope: the MD5 signature is not checked (the hash is serial per stream, and the project's own streams carry none), seek
+ * tables are not used, and Ogg FLAC, an ID3 prefix, 32-bit samples and blocks above 4608 samples are not read.
+ *
+ * mtts_flac_decode: six launches (metadata, candidate scan, plan, frame decode, walk, gather) on d_ws of
+ * mtts_flac_decode_workspace_bytes(B, ld_bytes, ld, max_block) bytes, 16-byte aligned; every word read from it was written by the same
+ * call.  Stream-ordered, no allocation, no synchronisation.  What the host can see returns -1 (mtts_last_error; the size query too):
+ * null pointers, B < 1, B > 65535, an ld_bytes that is no positive multiple of 16, an ld that is no positive multiple of 4, a max_block
+ * outside [16, 4608], a small workspace, a misaligned buffer, d_data / d_out / d_ws overlapping.
+ *
+ * mtts_flac_parse_host: the same parser and the same acceptance walk over HOST memory, one stream: channel 0's integers to
+ * out[0, out_capacity), the sample count or -1 returned, *rate / *channels / *bps from STREAMINFO (0 when refused).  It never touches
+ * the GPU: the parser is proven on the host before a kernel runs it. */
+int64_t mtts_flac_decode_workspace_bytes(int B, int64_t ld_bytes, int64_t ld, int max_block);
+int mtts_flac_decode(const uint8_t* d_data, int64_t ld_bytes, const int64_t* d_nbytes, int B, int max_block, float* d_out, int64_t ld,
+                     int64_t* d_out_lengths, int32_t* d_out_rates, void* d_ws, int64_t ws_bytes, void* stream);
+int64_t mtts_flac_parse_host(const uint8_t* data, int64_t nbytes, int max_block, int32_t* out, int64_t out_capacity, int* rate,
+                             int* channels, int* bps);
 
 /* ---------------------------------------------------------------- loudness: BS.1770 K-weighted, gated LUFS, one gain per row */
 

@@ -2,6 +2,8 @@
 the bytes a client is sent, s16le for the OpenAI route's ``pcm`` / ``wav`` and G.711 mu-law / A-law for an 8 kHz telephony leg -- and
 the first stage of the recording entries, which take clips that are still bytes (``Encoded``).  ``encode_flac`` is the compressed way
 out: one complete FLAC stream per row (``mtts_flac_encode``, include/mtts.h "FLAC out"), the same PCM16 words without loss.
+``decode_flac`` is the compressed way in: whole FLAC files (``FlacClip``, ``read_flac``) decoded on the device, channel 0, integers to
+the bit (``mtts_flac_decode``, include/mtts.h "FLAC in").
 
 One launch per ragged batch, a format per row, lengths checked on the device.  Every byte is defined by include/mtts.h "encoded
 audio" (DESIGN.md section 4); there is no CPU path.  The RIFF container (``wav_bytes`` / ``read_wav``) is host code: a header in
@@ -26,6 +28,7 @@ ENCODINGS = {**FORMATS, "flac": FLAC}                       # what a finished ro
 BYTES_PER_SAMPLE = {PCM16: 2, ULAW: 1, ALAW: 1}             # (FLAC has none: a stream's length is ``encode_flac``'s second result)
 WAV_TAGS = {PCM16: 1, ULAW: 7, ALAW: 6}          # WAVE_FORMAT_PCM, WAVE_FORMAT_MULAW, WAVE_FORMAT_ALAW
 FLAC_BLOCK_SIZES = (256, 512, 1024, 2048, 4096)
+FLAC_MAX_BLOCK = 4608                            # the largest block ``decode_flac`` reads (include/mtts.h "FLAC in")
 
 
 def __getattr__(name):
@@ -47,7 +50,7 @@ def format_id(fmt) -> int:
         return int(fmt)
     if _is_flac(fmt):
         raise ValueError("FLAC is no format of encode / decode / Encoded / wav_bytes, whose rows are samples of a fixed size: a FLAC "
-                         "stream is written by encode_flac -> (data, byte counts), and is not read back (decoding FLAC is out of scope)")
+                         "stream is written by encode_flac -> (data, byte counts) and read by read_flac / decode_flac (a FlacClip)")
     raise ValueError(f"unknown audio format {fmt!r}: one of {sorted(FORMATS)}")
 
 
@@ -251,9 +254,156 @@ def decode(data: torch.Tensor, lengths, formats, check: bool = True, ld: int = N
     return out
 
 
-def decode_clips(clips: Sequence[Encoded], dev) -> Tuple[torch.Tensor, list]:
-    """``Encoded`` clips -> ``(float32 [n, ld] on ``dev``, sample counts)`` with one copy of the bytes and one decode launch.  The
-    sample counts come from the payload sizes on the host, so nothing is waited for."""
+@dataclass
+class FlacClip:
+    """A recording that is still a FLAC file: ``data`` (``bytes`` or a 1-D uint8 tensor) is the whole native stream -- marker, metadata,
+    frames -- and the other fields are what its STREAMINFO block says (``read_flac`` fills them).  The recording entries decode channel
+    0 on the device (``decode_flac``).  Separate from ``Encoded``, whose rows are samples of a fixed size."""
+    data: Union[bytes, torch.Tensor]
+    sample_rate: int
+    samples: int
+    channels: int = 1
+    bits_per_sample: int = 16
+    max_block: int = 4608
+
+    def __post_init__(self):
+        if torch.is_tensor(self.data) and (self.data.dim() != 1 or self.data.dtype != torch.uint8):
+            raise ValueError("FlacClip.data is bytes or a 1-D uint8 tensor")
+        if not (1 <= int(self.sample_rate) <= 1048575 and 0 <= int(self.samples) < 1 << 36 and 1 <= int(self.channels) <= 8
+                and 8 <= int(self.bits_per_sample) <= 24 and 16 <= int(self.max_block) <= FLAC_MAX_BLOCK):
+            raise ValueError("FlacClip: a rate in [1, 1048575], samples in [0, 2^36), 1..8 channels, 8..24 bits and a largest block in "
+                             f"[16, {FLAC_MAX_BLOCK}] are read (include/mtts.h \"FLAC in\")")
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.data.numel()) if torch.is_tensor(self.data) else len(self.data)
+
+    def numel(self) -> int:
+        """As a waveform's ``numel()``: the samples of one channel."""
+        return int(self.samples)
+
+    def tensor(self) -> torch.Tensor:
+        """The stream as a 1-D uint8 tensor (where it lives)."""
+        if torch.is_tensor(self.data):
+            return self.data
+        return torch.frombuffer(bytearray(self.data), dtype=torch.uint8) if len(self.data) else torch.zeros(0, dtype=torch.uint8)
+
+
+def read_flac(path_or_bytes) -> FlacClip:
+    """A native FLAC file (a path, or its bytes) as a ``FlacClip``.  Only the marker and the metadata chain are read here, on the host;
+    the frames are decoded on the device.  ``ValueError`` for what include/mtts.h "FLAC in" refuses and the host can see: no ``fLaC``
+    marker (an ID3 tag or an Ogg container in front is named), no STREAMINFO block first, a reserved block type, a chain that runs off
+    the file, bits per sample outside 8..24, block sizes outside [16, 4608], a rate of 0, an unknown length with frames behind it."""
+    raw = bytes(path_or_bytes) if isinstance(path_or_bytes, (bytes, bytearray, memoryview)) else Path(path_or_bytes).read_bytes()
+    if raw[:3] == b"ID3":
+        raise ValueError("a FLAC file behind an ID3 tag is not read: strip the tag (the stream starts at 'fLaC')")
+    if raw[:4] == b"OggS":
+        raise ValueError("Ogg FLAC is not read: only native FLAC streams (starting with 'fLaC')")
+    if raw[:4] != b"fLaC":
+        raise ValueError("not a FLAC file: no 'fLaC' marker")
+    at, blocks, info = 4, 0, None
+    while True:
+        if at + 4 > len(raw):
+            raise ValueError("truncated FLAC file: the metadata chain runs off the file")
+        last, kind, size = raw[at] >> 7, raw[at] & 0x7F, int.from_bytes(raw[at + 1:at + 4], "big")
+        if blocks == 0 and (kind != 0 or size != 34):
+            raise ValueError("not a readable FLAC file: the first metadata block is not a 34-byte STREAMINFO")
+        if kind == 127 or (blocks and kind == 0):
+            raise ValueError(f"not a readable FLAC file: metadata block type {kind} at byte {at}")
+        if at + 4 + size > len(raw):
+            raise ValueError(f"truncated FLAC file: metadata block at byte {at} claims {size} bytes, {len(raw) - at - 4} are there")
+        if kind == 0:
+            info = int.from_bytes(raw[at + 4:at + 38], "big")
+        at, blocks = at + 4 + size, blocks + 1
+        if last:
+            break
+    lo, hi, rate = info >> 256, info >> 240 & 0xFFFF, info >> 172 & 0xFFFFF
+    channels, bps, total = (info >> 169 & 7) + 1, (info >> 164 & 31) + 1, info >> 128 & (1 << 36) - 1
+    if not 8 <= bps <= 24:
+        raise ValueError(f"unsupported FLAC form: {bps} bits per sample (8 to 24 are read)")
+    if lo < 16 or lo > hi or hi > FLAC_MAX_BLOCK:
+        raise ValueError(f"unsupported FLAC form: block sizes {lo}..{hi} (16 to {FLAC_MAX_BLOCK} are read)")
+    if rate < 1:
+        raise ValueError("unsupported FLAC form: a sample rate of 0")
+    if total == 0 and at < len(raw):
+        raise ValueError("unsupported FLAC form: STREAMINFO names no length (a stream that was never finished)")
+    return FlacClip(raw, int(rate), int(total), int(channels), int(bps), int(hi))
+
+
+@torch.inference_mode()
+def decode_flac(data: torch.Tensor, nbytes, ld: int = None, max_block: int = FLAC_MAX_BLOCK, check: bool = True
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """data uint8 [B, ld_bytes] (or 1-D) on the device, row b one whole FLAC stream of ``nbytes[b]`` bytes -> ``(audio float32 [B, ld],
+    lengths int64 [B], rates int32 [B])`` on the device: channel 0 of each stream as ``q / 2^(bits - 1)``, exact, zeros from a row's
+    length on (include/mtts.h "FLAC in").  ``ld``: the row capacity in samples, rounded up to a multiple of 4 (default 4 * ld_bytes); a
+    stream that holds more is refused.  ``max_block``: the largest block size accepted (16..4608).  Nothing is read on the host: a
+    refused row has ``lengths[b] = -1``, rate 0 and zeros; ``check`` waits for that verdict and raises ``ValueError`` naming the row."""
+    lib = _hip.load()
+    if isinstance(max_block, bool) or not isinstance(max_block, (int, np.integer)) or not 16 <= int(max_block) <= FLAC_MAX_BLOCK:
+        raise ValueError(f"max_block lies in [16, {FLAC_MAX_BLOCK}], got {max_block!r}")
+    data, _ = _hip.aligned_rows(data, 16, "data", "a uint8 [B, ld_bytes] tensor")
+    (B, ld_bytes), dev = data.shape, data.device
+    nbytes = _hip.row_lengths(nbytes, B, ld_bytes, dev, "nbytes")
+    ld = 4 * ld_bytes if ld is None else max(4, (int(ld) + 3) // 4 * 4)
+    out = torch.zeros(B, ld, dtype=torch.float32, device=dev)
+    lengths = torch.empty(B, dtype=torch.long, device=dev)
+    rates = torch.empty(B, dtype=torch.int32, device=dev)
+    ws = _flac_ws.get("flac_in", lib.mtts_flac_decode_workspace_bytes(B, ld_bytes, ld, int(max_block)), dev)
+    with torch.cuda.device(dev):
+        _hip.check(lib.mtts_flac_decode(_hip.ptr(data), ld_bytes, _hip.ptr(nbytes), B, int(max_block), _hip.ptr(out), ld, _hip.ptr(lengths),
+                                        _hip.ptr(rates), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
+    if check:
+        _hip.raise_refused(lib.mtts_pcm_status, _hip.ptr(lengths), B, _hip.stream_ptr(), prefix="decode_flac: a stream was refused; ")
+    return out, lengths, rates
+
+
+def _rows_of_bytes(tensors, dev) -> torch.Tensor:
+    """1-D uint8 tensors (host or device) as rows of one device buffer [n, nb], nb a multiple of 16: one copy of the host ones."""
+    nb = max(16, (max(int(t.numel()) for t in tensors) + 15) // 16 * 16)
+    host = torch.zeros(len(tensors), nb, dtype=torch.uint8)
+    on_device = []
+    for i, t in enumerate(tensors):
+        if t.is_cuda:
+            on_device.append((i, t))
+        else:
+            host[i, :t.numel()].copy_(t)
+    data = host.to(dev)
+    for i, t in on_device:
+        data[i, :t.numel()].copy_(t.to(dev))
+    return data
+
+
+def decode_clips(clips: Sequence[Union[Encoded, "FlacClip"]], dev, check: bool = False) -> Tuple[torch.Tensor, list]:
+    """``Encoded`` and ``FlacClip`` clips -> ``(float32 [n, ld] on ``dev``, sample counts)``: the ``Encoded`` ones with one copy of
+    their bytes and one decode launch, the ``FlacClip`` ones with one copy and one ``decode_flac`` call.  The sample counts come from the
+    payload sizes and from the clips' ``samples`` on the host, so nothing is waited for; a FLAC stream the device refuses (or one whose
+    STREAMINFO disagrees with the clip's fields) leaves its row zeros, and ``check=True`` waits for that verdict and raises."""
+    flac = [i for i, c in enumerate(clips) if isinstance(c, FlacClip)]
+    if not flac:
+        return _decode_encoded(clips, dev)
+    counts = [int(c.numel()) for c in clips]
+    ld = max(4, (max(counts) + 3) // 4 * 4)
+    streams = [clips[i] for i in flac]
+    data = _rows_of_bytes([c.tensor() for c in streams], dev)
+    audio, lengths, _ = decode_flac(data, [c.nbytes for c in streams], ld=max(counts[i] for i in flac),
+                                    max_block=max(c.max_block for c in streams), check=False)
+    if check:
+        want = torch.tensor([counts[i] for i in flac], dtype=torch.long, device=audio.device)
+        verdict = torch.where(lengths == want, lengths, torch.full_like(lengths, -1))
+        _hip.raise_refused(_hip.load().mtts_pcm_status, _hip.ptr(verdict), len(flac), _hip.stream_ptr(),
+                           prefix="a FLAC clip was refused (rows count the FLAC clips only); ")
+    rest = [i for i in range(len(clips)) if i not in flac]
+    if not rest:
+        return audio, counts
+    wave = torch.zeros(len(clips), ld, dtype=torch.float32, device=audio.device)
+    wave[flac, :audio.shape[1]] = audio
+    plain, _ = _decode_encoded([clips[i] for i in rest], dev)
+    wave[rest, :plain.shape[1]] = plain
+    return wave, counts
+
+
+def _decode_encoded(clips: Sequence[Encoded], dev) -> Tuple[torch.Tensor, list]:
+    """``decode_clips`` of ``Encoded`` clips alone: one copy of the bytes and one decode launch."""
     counts = [c.samples for c in clips]
     ids = [format_id(c.format) for c in clips]
     nb = max(16, (max(n * BYTES_PER_SAMPLE[f] for n, f in zip(counts, ids)) + 15) // 16 * 16)

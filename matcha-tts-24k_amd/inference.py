@@ -187,8 +187,8 @@ class MatchaTTSInfer(nn.Module):
         from .style import FINE_HOP
         if len(clips) == 0:
             raise ValueError("no clips")
-        from .audio_codec import Encoded
-        voices = [clips] if torch.is_tensor(clips[0]) or isinstance(clips[0], (np.ndarray, Encoded)) else list(clips)
+        from .audio_codec import Encoded, FlacClip
+        voices = [clips] if torch.is_tensor(clips[0]) or isinstance(clips[0], (np.ndarray, Encoded, FlacClip)) else list(clips)
         dev = next(self.parameters()).device
         self._rt.ready()                                   # mel statistics come from the loaded checkpoint's buffers
         flat, group = [], []
@@ -336,9 +336,9 @@ class MatchaTTSInfer(nn.Module):
     @staticmethod
     def _clips(audio, B, who):
         """The ``audio`` argument of the recording entries as a list of ``B`` clips: a [B, L] tensor's rows, one 1-D waveform, or a list."""
-        from .audio_codec import Encoded
+        from .audio_codec import Encoded, FlacClip
         clips = [audio[b] for b in range(audio.shape[0])] if torch.is_tensor(audio) and audio.dim() == 2 else (
-            [audio] if torch.is_tensor(audio) or isinstance(audio, (np.ndarray, Encoded)) else list(audio))
+            [audio] if torch.is_tensor(audio) or isinstance(audio, (np.ndarray, Encoded, FlacClip)) else list(audio))
         if len(clips) != B:
             raise ValueError(f"{who} needs one clip per utterance ({B}), got {len(clips)}")
         return clips
@@ -707,19 +707,21 @@ def _recordings_24k(clips, dev, sample_rate=24000, lengths=None):
 
 
 def _decoded_clips(clips, dev, sample_rate):
-    """``audio_codec.Encoded`` clips among ``clips`` decoded on the device (one launch for all of them, ahead of the rate conversion),
-    and the clips' rates: ``sample_rate`` as given where it names a rate for a clip -- an int names one for every clip -- and, where it
-    is None (as a whole, or that clip's entry of a list), the clip's own ``Encoded.sample_rate`` (24 kHz for a waveform).  Without an
-    encoded clip and with every rate named, both arguments come back as they are and nothing is launched."""
+    """``audio_codec.Encoded`` and ``audio_codec.FlacClip`` clips among ``clips`` decoded on the device (one launch for all the
+    ``Encoded`` ones, one ``decode_flac`` call for all the FLAC files, ahead of the rate conversion), and the clips' rates:
+    ``sample_rate`` as given where it names a rate for a clip -- an int names one for every clip -- and, where it is None (as a whole,
+    or that clip's entry of a list), the clip's own ``sample_rate`` (24 kHz for a waveform).  Without such a clip and with every rate
+    named, both arguments come back as they are and nothing is launched.  A FLAC file comes from outside, so its verdict is read (the
+    one wait here): a stream the device refuses raises ``ValueError``; ``Encoded`` clips alone are decoded without a wait, as before."""
     from . import audio_codec as AC
-    at = [i for i, c in enumerate(clips) if isinstance(c, AC.Encoded)]
+    at = [i for i, c in enumerate(clips) if isinstance(c, (AC.Encoded, AC.FlacClip))]
     own = [clips[i].sample_rate if i in at else SAMPLE_RATE for i in range(len(clips))]
     if sample_rate is None:
         sample_rate = own
     elif not isinstance(sample_rate, (int, np.integer)) and not torch.is_tensor(sample_rate):
         sample_rate = [own[i] if r is None else r for i, r in enumerate(sample_rate)] if len(sample_rate) == len(clips) else sample_rate
     if at:
-        wave, counts = AC.decode_clips([clips[i] for i in at], dev)
+        wave, counts = AC.decode_clips([clips[i] for i in at], dev, check=any(isinstance(clips[i], AC.FlacClip) for i in at))
         for k, i in enumerate(at):
             clips[i] = wave[k, :counts[k]]
     return clips, sample_rate
@@ -741,9 +743,10 @@ def _silence_normalised(wave, lengths, silence):
 def recordings(clips, dev, sample_rate=24000, lengths=None, silence=None):
     """What the recording entries (``enroll_voice``, ``align``, ``score``, ``speaker_grad``, ``finetune_speaker``) make of their clips
     before the mel front end: ``(wave [B, ld] fp32 on ``dev`` at 24 kHz, lengths: list of B ints)``.  ``clips``: 1-D waveforms (host
-    or device) at ``sample_rate`` (an int or one per clip; converted on the device) or ``audio_codec.Encoded`` clips -- still bytes,
-    PCM16 / mu-law / A-law, decoded on the device in one launch; where ``sample_rate`` is None, or None for that clip, the clip's
-    own ``Encoded.sample_rate`` is used --, ``lengths``: samples to use of each;
+    or device) at ``sample_rate`` (an int or one per clip; converted on the device), ``audio_codec.Encoded`` clips -- still bytes,
+    PCM16 / mu-law / A-law, decoded on the device in one launch -- or ``audio_codec.FlacClip`` files, decoded on the device in one
+    ``decode_flac`` call (channel 0); where ``sample_rate`` is None, or None for that clip, the clip's own ``sample_rate`` is used --,
+    ``lengths``: samples to use of each;
     ``silence``: None or ``(leading_s, trailing_s)``, normalised after the conversion (``corpus.normalize_silence``).  For a
     caller that needs the lengths ahead of the call, e.g. to size ``score``'s noise."""
     return _silence_normalised(*_recordings_24k(clips, dev, sample_rate, lengths), silence)

@@ -26,7 +26,12 @@ PKG = "matcha-tts-24k_amd"
 def read_wav(path):
     """``(samples: 1-D float32 tensor in [-1, 1], sample rate)`` of a PCM wav file; channel 0 of a multi-channel file.  A file whose
     format the stdlib ``wave`` module refuses (G.711 mu-law / A-law: "unknown format: 7") is read by ``audio_codec.read_wav`` and
-    comes back as an ``Encoded`` clip, still bytes, which the model's recording entries decode on the device."""
+    comes back as an ``Encoded`` clip, still bytes, which the model's recording entries decode on the device; so does a FLAC file
+    (one that starts with ``fLaC``), as an ``audio_codec.FlacClip``."""
+    with open(str(path), "rb") as f:
+        if f.read(4) == b"fLaC":
+            clip = importlib.import_module(PKG + ".audio_codec").read_flac(path)
+            return clip, int(clip.sample_rate)
     try:
         with wave.open(str(path), "rb") as w:
             rate, channels = w.getframerate(), w.getnchannels()
@@ -34,7 +39,6 @@ def read_wav(path):
     except wave.Error as e:
         if "unknown format" not in str(e):
             raise
-        import importlib
         enc = importlib.import_module(PKG + ".audio_codec").read_wav(path)
         return enc, int(enc.sample_rate)
     if width == 2:

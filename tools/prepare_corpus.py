@@ -13,7 +13,7 @@ normalize_silence.py, generate_data_statistics.py and precompute_mels.py do, as 
 The data YAML is read with ``yaml`` (the reference's keys: train_filelist_path, valid_filelist_path, sample_rate, n_fft,
 n_feats, hop_length, win_length, data_statistics {mel_mean, mel_std}, mel_dir; relative paths are relative to the working
 directory).  Filelists hold ``rel|speaker|lang|text`` lines, wavs are at ``<filelist dir>/wav/<rel>.wav`` (PCM, read with
-tools/enroll.py's ``read_wav``).  Clips are sorted by length and processed ``--batch`` at a time, so a batch holds clips of
+tools/enroll.py's ``read_wav``; a ``<rel>.flac`` beside a missing wav is read in its place, decoded on the device).  Clips are sorted by length and processed ``--batch`` at a time, so a batch holds clips of
 similar length.
 
 measure    one table per end (leading, trailing) with a row per speaker of the train filelist: count, mean and standard
@@ -71,7 +71,9 @@ def entries(filelists):
             parts = line.strip().split("|")
             if not line.strip() or len(parts) < 2:
                 continue
-            out.append((parts[0], parts[1], (fl.parent / "wav" / (parts[0] + ".wav")).resolve()))
+            wav = (fl.parent / "wav" / (parts[0] + ".wav")).resolve()
+            flac = wav.with_suffix(".flac")                        # a FLAC file stands in for a missing wav of the same name
+            out.append((parts[0], parts[1], flac if flac.exists() and not wav.exists() else wav))
     return out
 
 
@@ -238,6 +240,8 @@ def cmd_normalize(args, cfg, corpus) -> int:
             for k, (i, n) in enumerate(zip(rows, out_len.tolist())):
                 rel, _, path = its[i]
                 cs, ce = host["bounds"][k][:2]
+                if host["changed"][k] and path.suffix == ".flac":
+                    raise RuntimeError(f"{path}: normalize rewrites wav files in place; a FLAC file is read, not rewritten")
                 if host["changed"][k] and rewrite_wav(path, cs, ce, lead, trail, clips[i].numel()) != n:
                     raise RuntimeError(f"{path}: the frames written and the device's rebuilt length {n} differ")
                 report[rel] = {"changed": bool(host["changed"][k]), "content_start": cs, "content_end": ce, "length": int(clips[i].numel()),
