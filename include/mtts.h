@@ -1027,8 +1027,9 @@ int mtts_pcm_status(const int64_t* d_verdict, int B, void* stream);
 /* A row becomes one complete mono, 16-bit, fixed-blocksize FLAC stream (RFC 9639): the compressed form of the "pcm" bytes above, about
  * 0.7 of their size on speech.  The encoder is deterministic: every byte is a function of the row's samples, its rate, the block size
  * and (seed, key), and of nothing else -- not of the batch, the row index or the grid.  tests/flac_restated.py restates it in NumPy bit
- * for bit, beside an independent decoder.  Out of scope: writing LPC subframes or stereo, the MD5 signature, seek tables ("FLAC in"
- * below reads them).
+ * for bit, beside an independent decoder.  mtts_flac_encode_lpc also writes LPC subframes (the lpc paragraphs below, restated in
+ * tests/flac_lpc_restated.py): about 0.56 of the "pcm" bytes on speech at order 12.  Out of scope: writing stereo, the MD5 signature,
+ * seek tables ("FLAC in" below reads them), a search over Rice partition orders, 24-bit output.
  *
  *   samples:  q[i] is exactly the PCM16 word mtts_pcm_encode writes for the row: the same arithmetic, the same dither as a function of
  *             (seed, key, i) when dither is on (the same device functions, csrc/pcm_quantise.h).
@@ -1057,6 +1058,35 @@ int mtts_pcm_status(const int64_t* d_verdict, int B, void* stream);
  *   ranges:   |e_4| <= 2^19 and u <= 2^20, so a cost over 4095 samples reaches 2^32: the order costs and sum(u >> k) are 64-bit sums
  *             (32 bits inside a partition of 256, where they stay below 2^29).
  *
+ * With max_lpc_order = M in 1..12 (mtts_flac_encode_lpc) a frame that is not CONSTANT also tries LPC subframes.  Every step is exact
+ * in integers or one fp64 operation order (+ - * / as written, no contraction; the device's fp64 division is correctly rounded):
+ *   lpc orders:   the list 4, 8, 12, each capped at M (min(o, M)), once each, ascending, and only orders < n.  M = 1 tries {1}, M = 8
+ *             {4, 8}, M = 12 {4, 8, 12}.  No such order (n = 1): the frame is as mtts_flac_encode writes it.
+ *   lpc window:   w[i] = 255 - (255 * (2 i + 1 - n)^2) / (n * n), integer division, over the frame's own n: 1..255, and the product
+ *             stays below 2^32.  x[i] = q[i] * w[i], |x| < 2^23.
+ *   lpc autocorrelation: R[l] = sum over i in [0, n - l) of x[i] * x[i + l] for l = 0..top (the largest order tried), exact in int64 (a
+ *             product below 2^46, 4096 of them below 2^58); each R[l] converted to fp64 once.
+ *   lpc recursion: Levinson-Durbin in fp64.  err = R[0]; not (0 < err < inf): no order is tried.  For m = 1..top: s = R[m]; for j = 1..
+ *             m - 1 in that order s = s - a[j] * R[m - j]; k = s / err; a'[j] = a[j] - k * a[m - j] for j < m, a'[m] = k; err = err *
+ *             (1.0 - k * k).  The recursion stops at the first m whose err is not in (0, inf): that order and those above are not tried.
+ *   lpc quantisation: precision 12.  e = the biased exponent field of max_j |a[j]|, - 1022 (so max|a| < 2^e; zero and subnormals give a
+ *             large shift, an infinity or NaN a negative one); shift = min(15, 11 - e); a negative shift drops the order.  c[j - 1] =
+ *             clamp(rint(a[j] * 2^shift), -2048, 2047), ties to even.
+ *   lpc residual: r[i] = q[i] - ((sum over j in [0, m) of c[j] * q[i - 1 - j]) >> shift) for i >= m, an arithmetic shift; 12 taps of 12
+ *             bits on 16-bit words keep the sum below 12 * 2^11 * 2^15 < 2^31.  An order with any |r[i]| >= 2^20 is dropped, so the
+ *             ranges above hold unchanged (u < 2^21).
+ *   lpc subframe: type 1ooooo (m - 1); m warm-up words of 16 bits; a 4-bit precision - 1 = 1011; a 5-bit shift; m coefficients of 12 bits,
+ *             two's complement; then the residual exactly as FIXED writes it with m in place of o (method 00, the same partition order,
+ *             the first partition holding 256 - m residuals, k by the same cost and tie rule).
+ *   lpc choice:   exact subframe bits, header and coefficients included: the fewest win, ties go to FIXED, then to the lower order.
+ *             VERBATIM when the winner has >= 8 + 16 n bits, as before: a frame is still at most 2 * bs + 16 bytes, never longer than
+ *             the frame mtts_flac_encode writes of the same samples, and the two size queries serve both entries.
+ *   lpc subset:   orders up to 12, Rice partitions of 256 and blocks up to 4096 keep every subframe inside the limits of the RFC's streamable
+ *             subset at every rate (LPC order <= 12 up to 48 kHz, Rice partition order <= 8, blocks <= 4608 up to 48 kHz); a stream
+ *             leaves the subset only where it does without LPC, through rate code 0000.
+ *   M = 0 is mtts_flac_encode: the same launches, the same bytes.  An M outside 0..12 is a host-visible refusal.  Everything else --
+ *   arguments, sizes, refusals, three launches, determinism -- is as for mtts_flac_encode, which keeps its kernels and its bytes.
+ *
  * mtts_flac_encode: d_audio [B][ld] fp32 (ld % 4 == 0, 16-byte aligned), d_lengths device int64 [B], d_rates device int32 [B] (Hz),
  * d_keys device int64 [B] or NULL (all 0), dither / seed as mtts_pcm_encode takes them -> d_out uint8 [B][out_ld], row b holding
  * d_out_bytes[b] bytes from its start.  out_ld >= mtts_flac_row_bytes(ld, block_size) = 42 + ceil(ld / bs) * (2 * bs + 16) rounded up to
@@ -1068,13 +1098,16 @@ int mtts_pcm_status(const int64_t* d_verdict, int B, void* stream);
  *             gives d_out_bytes[b] = -1 and no byte written for that row; the other rows are unaffected.  mtts_pcm_status reads the
  *             verdict as it does for the PCM entries.
  * What the host can see returns -1 (mtts_last_error; the two size queries too): null pointers (d_keys excepted), B < 1, a bad ld, a
- * block_size that is none of the five, a small out_ld or ws_bytes, a misaligned buffer, d_out / d_ws / d_audio overlapping. */
+ * block_size that is none of the five, a max_lpc_order outside 0..12, a small out_ld or ws_bytes, a misaligned buffer, d_out / d_ws / d_audio overlapping. */
 #define MTTS_FLAC 3
 int64_t mtts_flac_row_bytes(int64_t ld, int block_size);
 int64_t mtts_flac_workspace_bytes(int B, int64_t ld, int block_size);
 int mtts_flac_encode(const float* d_audio, int64_t ld, const int64_t* d_lengths, const int32_t* d_rates, const int64_t* d_keys, int B,
                      int block_size, int dither, int64_t seed, uint8_t* d_out, int64_t out_ld, int64_t* d_out_bytes, void* d_ws,
                      int64_t ws_bytes, void* stream);
+int mtts_flac_encode_lpc(const float* d_audio, int64_t ld, const int64_t* d_lengths, const int32_t* d_rates, const int64_t* d_keys, int B,
+                         int block_size, int max_lpc_order, int dither, int64_t seed, uint8_t* d_out, int64_t out_ld, int64_t* d_out_bytes,
+                         void* d_ws, int64_t ws_bytes, void* stream);
 
 /* ---------------------------------------------------------------- FLAC in: recordings decoded on the device */
 

@@ -316,6 +316,7 @@ def load() -> C.CDLL:
         "mtts_flac_row_bytes": (i64, [i64, i32]),
         "mtts_flac_workspace_bytes": (i64, [i32, i64, i32]),
         "mtts_flac_encode": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i64, vp, i64, vp, vp, i64, vp]),
+        "mtts_flac_encode_lpc": (i32, [vp, i64, vp, vp, vp, i32, i32, i32, i32, i64, vp, i64, vp, vp, i64, vp]),
         "mtts_flac_decode_workspace_bytes": (i64, [i32, i64, i64, i32]),
         "mtts_flac_decode": (i32, [vp, i64, vp, i32, i32, vp, i64, vp, vp, vp, i64, vp]),
         "mtts_flac_parse_host": (i64, [vp, i64, i32, vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),

@@ -28,6 +28,7 @@ ENCODINGS = {**FORMATS, "flac": FLAC}                       # what a finished ro
 BYTES_PER_SAMPLE = {PCM16: 2, ULAW: 1, ALAW: 1}             # (FLAC has none: a stream's length is ``encode_flac``'s second result)
 WAV_TAGS = {PCM16: 1, ULAW: 7, ALAW: 6}          # WAVE_FORMAT_PCM, WAVE_FORMAT_MULAW, WAVE_FORMAT_ALAW
 FLAC_BLOCK_SIZES = (256, 512, 1024, 2048, 4096)
+FLAC_MAX_LPC_ORDER = 12                          # the largest ``lpc_order`` of ``encode_flac`` (include/mtts.h "FLAC out")
 FLAC_MAX_BLOCK = 4608                            # the largest block ``decode_flac`` reads (include/mtts.h "FLAC in")
 
 
@@ -176,18 +177,28 @@ def flac_block_size(block_size) -> int:
     return int(block_size)
 
 
+def flac_lpc_order(lpc_order) -> int:
+    if isinstance(lpc_order, bool) or not isinstance(lpc_order, (int, np.integer)) or not 0 <= int(lpc_order) <= FLAC_MAX_LPC_ORDER:
+        raise ValueError(f"a FLAC LPC order lies in 0..{FLAC_MAX_LPC_ORDER} (0: FIXED predictors only), got {lpc_order!r}")
+    return int(lpc_order)
+
+
 @torch.inference_mode()
 def encode_flac(audio: torch.Tensor, lengths, sample_rates, block_size: int = 4096, dither=False, seed: int = 0, keys=None,
-                check: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+                check: bool = False, lpc_order: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """audio [B, L] (or [L]) float32 on the device + lengths [B] (samples; default all L) + ``sample_rates`` (Hz: an int, one per row,
     or a device int32 tensor) -> ``(data uint8 [B, stride], byte counts int64 [B])`` on the device: row b holds one complete mono
     16-bit FLAC stream of ``nbytes[b]`` bytes, a file as it is (include/mtts.h "FLAC out"; ``stride = mtts_flac_row_bytes``).  It
     holds exactly the words ``encode(..., "pcm16")`` gives for the row -- with ``dither`` (a bool, or one per row), ``seed`` and
     ``keys`` the same dithered words -- in frames of ``block_size`` samples; an empty row is the 42 header bytes.  Bytes at or beyond
     ``nbytes[b]`` are not written.  Nothing is read on the host: a length outside [0, L] (or one that already is -1) and a rate
-    outside [1, 1048575] give ``nbytes[b] = -1`` and an unwritten row; ``check=True`` waits for that verdict and raises ``ValueError``."""
+    outside [1, 1048575] give ``nbytes[b] = -1`` and an unwritten row; ``check=True`` waits for that verdict and raises ``ValueError``.
+    ``lpc_order``: 0 writes CONSTANT / FIXED / VERBATIM subframes (``mtts_flac_encode``); 1..12 also tries linear prediction up to that
+    order per frame (``mtts_flac_encode_lpc``: the same words in fewer bytes, about 0.82 of the FIXED stream on speech at 12, for a
+    longer frame kernel); anything else raises ``ValueError``."""
     lib = _hip.load()
     bs = flac_block_size(block_size)
+    lpc = flac_lpc_order(lpc_order)
     audio, L = _hip.aligned_rows(audio, 4, "audio")
     (B, ld), dev = audio.shape, audio.device
     lengths = _hip.row_lengths(lengths, B, L, dev)
@@ -210,8 +221,9 @@ def encode_flac(audio: torch.Tensor, lengths, sample_rates, block_size: int = 40
     def launch(row_lengths, on):
         nbytes = torch.empty(B, dtype=torch.long, device=dev)
         with torch.cuda.device(dev):
-            _hip.check(lib.mtts_flac_encode(_hip.ptr(audio), ld, _hip.ptr(row_lengths), _hip.ptr(rates), _hip.ptr(keys), B, bs, int(on), seed,
-                                            _hip.ptr(out), stride, _hip.ptr(nbytes), ws.data_ptr(), ws.numel(), _hip.stream_ptr()))
+            tail = (int(on), seed, _hip.ptr(out), stride, _hip.ptr(nbytes), ws.data_ptr(), ws.numel(), _hip.stream_ptr())
+            head = (_hip.ptr(audio), ld, _hip.ptr(row_lengths), _hip.ptr(rates), _hip.ptr(keys), B, bs)
+            _hip.check(lib.mtts_flac_encode_lpc(*head, lpc, *tail) if lpc else lib.mtts_flac_encode(*head, *tail))
         return nbytes
 
     if isinstance(dither, (bool, int, np.bool_)):

@@ -40,6 +40,7 @@ class _Unit:
     encoding: Optional[str] = None          # "pcm16" / "ulaw" / "alaw": the result's "audio" is then raw bytes (a 1-D uint8 tensor) encoded on the device, and named in the result; "flac": one complete FLAC stream (audio_codec.encode_flac)
     dither: bool = False                    # TPDF dither on a "pcm16" result
     dither_key: int = 0                     # selects the dither sequence: a field of the unit, so its bytes do not depend on who shared its batch
+    flac_lpc: int = 0                       # a "flac" result also tries linear prediction up to this order (1..12; audio_codec.encode_flac(lpc_order=)): fewer bytes, the same words; a value without encoding="flac" is refused
     loudness: Optional[float] = None        # target in LUFS (BS.1770 integrated loudness) the "audio" -- of a document: the JOINED audio, one gain -- is brought to on the device at 24 kHz; the result then carries "loudness" (measured, before the gain) and "gain"
     true_peak: Optional[float] = None       # ceiling in dBTP on the true peak of the levelled "audio" (needs ``loudness``); the result then also carries "true_peak" (dBTP, measured before the gain) and "lra"
     marks: bool = False                     # the result then carries "marks": {"tokens": [(start_s, end_s)] per token -- of a document: one such list per sentence, in its timeline -- (+ "words" with ``word_groups``)}, in seconds at 24 kHz
@@ -50,6 +51,11 @@ class _Unit:
         if self.encoding is not None:
             from .audio_codec import encoding_id
             encoding_id(self.encoding)
+        if self.flac_lpc != 0 or isinstance(self.flac_lpc, bool):
+            from .audio_codec import FLAC, encoding_id, flac_lpc_order
+            flac_lpc_order(self.flac_lpc)
+            if self.encoding is None or encoding_id(self.encoding) != FLAC:
+                raise ValueError(f"flac_lpc = {self.flac_lpc} belongs to encoding=\"flac\", got encoding={self.encoding!r}")
         if self.loudness is not None or self.true_peak is not None:
             from .loudness import check_ceiling, check_target
             self.loudness = check_target(self.loudness)
@@ -281,7 +287,7 @@ class FrameBudgetBatcher(_Queue):
     def submit_document(self, segments_ids: Sequence[Sequence[int]], pauses_ms: Sequence[float], **request_fields) -> Future:
         """A text of several utterances: ``segments_ids`` the phoneme ids of each segment in speaking order, ``pauses_ms`` the silence
         after each (the last is ignored).  ``request_fields``: the fields of a ``Request`` -- voice, solver, speeds apply to every
-        segment; ``sample_rate`` / ``encoding`` / ``dither`` / ``dither_key`` / ``loudness`` / ``true_peak`` to the joined result -- and ``level`` (``Document``).
+        segment; ``sample_rate`` / ``encoding`` / ``dither`` / ``dither_key`` / ``flac_lpc`` / ``loudness`` / ``true_peak`` to the joined result -- and ``level`` (``Document``).
         ``marks`` (of the joined result) asks for ``"marks"``: ``{"tokens": one list of (start_s, end_s) per segment}`` in the document's
         timeline, ``"words"`` too when every segment brings ``word_groups``.  ``breaks`` / ``token_scale`` / ``token_extend`` /
         ``word_groups`` differ from segment to segment: each is a list of one entry (or None) per segment, as the ``Request`` field.
@@ -371,6 +377,9 @@ def tail_options(units: List[Any], timing=None, fade_ms: float = 5.0) -> Dict[st
         kw.update(sample_rate=[int(u.sample_rate) for u in units])
     if asked("encoding"):
         kw.update(encoding=[u.encoding for u in units], dither=[bool(u.dither) for u in units], dither_keys=[int(u.dither_key) for u in units])
+        orders = [int(u.flac_lpc) for u in units]
+        if any(orders):                     # per unit: a stream's bytes do not depend on who shared its batch
+            kw.update(flac_lpc=orders)
     if asked("loudness"):                   # (a report alone would run the meter: it is asked for only where a unit is levelled)
         kw.update(loudness=[u.loudness for u in units], return_loudness=True)
         if asked("true_peak"):
@@ -432,7 +441,7 @@ def waveforms_into(res: List[Dict[str, Any]], mel, mel_lengths, vocoder, wave_ba
         from .waveform import Tail, _waveform_on_device, finish_request, trim_trailing_silence
         done = [finish_request(trim_trailing_silence(_waveform_on_device(r["mel"][None], vocoder).squeeze()), loudness=u.loudness,
                                true_peak=u.true_peak, report=True, sample_rate=int(u.sample_rate), encoding=u.encoding, dither=bool(u.dither),
-                               dither_key=int(u.dither_key)) for r, u in zip(res, units)]
+                               dither_key=int(u.dither_key), **(dict(flac_lpc=int(u.flac_lpc)) if u.flac_lpc else {})) for r, u in zip(res, units)]
         out = Tail(rows=[a for a, _ in done], report=[rep for _, rep in done])
     results_into(res, units, out)
 

@@ -13,6 +13,14 @@
 // A thread owns the samples t, t + 256, ... of its frame, so pass j of a full frame is Rice partition j, one residual per thread.
 // Every loop is bounded by the block size, by the frames of a row (ld / block size, which the host checked) or by a constant; a
 // unary run is never walked: a code is its offset (from a scan of the code lengths) plus one 16-bit write.
+//
+// mtts_flac_encode_lpc launches flac_frame_kernel<true> in place of launch 1: the same frame, with LPC subframes among the candidates
+// (include/mtts.h "FLAC out", the lpc paragraphs; tests/flac_lpc_restated.py).  Between the order costs and the frame header it
+// analyses the frame -- integer window, exact int64 autocorrelation (a thread's strided samples at every lag, one wave_sum tree per
+// lag), Levinson-Durbin in fp64 run by every thread alike (no broadcast, no LDS), the candidates' quantised coefficients in
+// registers -- and behind the FIXED plan it plans each candidate in the same LDS (u is reused; only the winner's plan is kept, and
+// planned again when it was not the last).  Nothing of a candidate reaches the bitstream before its bit count beat FIXED's and
+// VERBATIM's.  flac_frame_kernel<false> is what mtts_flac_encode has always launched.
 #include "host.h"
 #include "pcm_quantise.h"
 
@@ -24,6 +32,10 @@ constexpr int FLAC_MAX_PARTS = 16;                 // 4096 / 256
 constexpr int FLAC_KS = 15;                        // Rice parameters 0..14 (15 is the escape, never used)
 constexpr int FLAC_HEADER = 42;
 constexpr int64_t FLAC_MAX_FRAMES = (int64_t)1 << 21;
+constexpr int FLAC_LPC_MAX = 12;                   // the largest LPC order written
+constexpr int FLAC_LPC_CANDS = 3;                  // orders 4, 8, 12, each capped at max_lpc_order, once each
+constexpr int FLAC_LPC_PRECISION = 12;             // bits of a quantised coefficient
+constexpr int FLAC_LPC_RANGE = 1 << 20;            // a candidate with a residual at or beyond it is dropped
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 
 struct FlacArgs {
@@ -35,6 +47,7 @@ struct FlacArgs {
     int bs, log2bs, slot;        // slot = 2 * bs + 16: bytes of a staging slot, the bound of a frame
     unsigned int seed_lo, seed_hi;
     int dither;
+    int lpc;                     // max_lpc_order, 0..12 (read by flac_frame_kernel<true> alone)
     uint8_t* out;                // [B][out_ld]
     int64_t out_ld;
     int64_t* out_bytes;          // [B]
@@ -163,8 +176,77 @@ __device__ __forceinline__ int flac_rate_code(int rate) {
     return 0;
 }
 
+// the LPC residual at sample i >= m: 12 taps of 12 bits on 16-bit words keep the sum below 12 * 2^11 * 2^15 < 2^31
+__device__ __forceinline__ int lpc_residual(const int* q, int i, const int (&c)[FLAC_LPC_MAX], int m, int shift) {
+    int s = 0;
+#pragma unroll
+    for (int j = 0; j < FLAC_LPC_MAX; ++j)
+        if (j < m) s += c[j] * q[i - 1 - j];
+    return q[i] - (s >> shift);
+}
+
+// The Rice plan of one predictor of order `order` over the frame's n words: the folded residuals into u (0 where a sample has none),
+// then sum(u >> k) for the 15 candidates over each run of 256 samples: thread (j, k) = (tid / 16, tid % 16) reads run j from LDS, 16
+// bytes at a time, its start rotated by 4 j reads so that the four runs a wave reads lie in different banks.  A run's sum stays below
+// 256 * 2^21 = 2^29: 32 bits.  A full frame's partition j is run j; a short frame is one partition of up to 4095 values, the 64-bit
+// sum of its runs (up to 2^33).  pk[p], pcost[p]: the k of partition p and its bits, the 4 of k not included; returns the bits of all
+// partitions, their 4-bit parameters included.  RANGE: ~0 instead, and nothing planned, when a |residual| reaches FLAC_LPC_RANGE.
+template <bool RANGE, class Residual>
+__device__ __forceinline__ unsigned long long rice_plan(unsigned int* u, unsigned int (*part)[16], int* pk, unsigned long long* pcost, int n,
+                                                        int order, bool full, int passes, Residual residual) {
+    const int tid = threadIdx.x;
+    int beyond = 0;
+    for (int j = 0; j < passes; ++j) {
+        const int i = j * FLAC_THREADS + tid;
+        unsigned int uu = 0;
+        if (i < n && i >= order) {
+            const int r = residual(i);
+            if (RANGE) beyond |= r >= FLAC_LPC_RANGE || r <= -FLAC_LPC_RANGE;
+            uu = r >= 0 ? 2u * (unsigned int)r : 2u * (unsigned int)(-r) - 1u;
+        }
+        u[i] = uu;
+    }
+    if (RANGE) {
+        if (__syncthreads_or(beyond)) return ~0ull;              // (the same answer in every thread)
+    } else {
+        __syncthreads();
+    }
+    {
+        const int k = tid & 15, j = tid >> 4;
+        if (k < FLAC_KS && j < passes) {
+            const u32x4* run = reinterpret_cast<const u32x4*>(u + j * FLAC_THREADS);
+            unsigned int s = 0;
+            for (int x = 0; x < FLAC_THREADS / 4; ++x) {
+                const u32x4 v = run[(x + 4 * j) & (FLAC_THREADS / 4 - 1)];
+                s += (v[0] >> k) + (v[1] >> k) + (v[2] >> k) + (v[3] >> k);
+            }
+            part[j][k] = s;
+        }
+    }
+    __syncthreads();
+    const int nparts = full ? passes : 1;
+    if (tid < nparts) {                      // k of partition tid: the fewest bits, ties to the smaller k
+        const unsigned long long cnt = full ? (unsigned long long)(FLAC_THREADS - (tid == 0 ? order : 0)) : (unsigned long long)(n - order);
+        const int j0 = full ? tid : 0, j1 = full ? tid + 1 : passes;
+        unsigned long long least = ~0ull;
+        int kbest = 0;
+        for (int k = 0; k < FLAC_KS; ++k) {
+            unsigned long long c = cnt * (k + 1);
+            for (int j = j0; j < j1; ++j) c += part[j][k];
+            if (c < least) { least = c; kbest = k; }
+        }
+        pk[tid] = kbest;
+        pcost[tid] = least;
+    }
+    __syncthreads();
+    unsigned long long total = 0;
+    for (int p = 0; p < nparts; ++p) total += 4ull + pcost[p];
+    return total;
+}
+
 extern __shared__ __attribute__((aligned(16))) unsigned int flac_lds[];
 
+template <bool LPC>
 __global__ __launch_bounds__(FLAC_THREADS) void flac_frame_kernel(const FlacArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.y;
     const int64_t f = blockIdx.x;
@@ -233,6 +315,96 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_frame_kernel(const FlacArgs
     }
     const bool constant = red[0][5] + red[1][5] + red[2][5] + red[3][5] == 0;
 
+    // ---- the LPC analysis: per candidate its order (0: none), shift and coefficients, the same in every thread
+    int lm[FLAC_LPC_CANDS] = {0, 0, 0}, lshift[FLAC_LPC_CANDS] = {0, 0, 0};
+    int lc[FLAC_LPC_CANDS][FLAC_LPC_MAX] = {};
+    if constexpr (LPC) {
+        __shared__ long long racc[FLAC_WAVES][FLAC_LPC_MAX + 1];
+        int cand[FLAC_LPC_CANDS], top = 0;       // the listed orders capped at a.lpc, once each, below n
+#pragma unroll
+        for (int ci = 0; ci < FLAC_LPC_CANDS; ++ci) {
+            const int o = 4 * (ci + 1) < a.lpc ? 4 * (ci + 1) : a.lpc;
+            cand[ci] = o > top && o < n ? o : 0;
+            top = cand[ci] ? o : top;
+        }
+        if (!constant && top > 0) {
+            // the windowed words into u (free until the first plan): w = 255 - 255 (2 i + 1 - n)^2 / n^2 (integer division) lies in
+            // 1..255, and 255 * 4095^2 < 2^32; |q w| < 2^23
+            int* x = reinterpret_cast<int*>(u);
+            const unsigned int nn = (unsigned int)n * (unsigned int)n;
+            for (int j = 0; j < passes; ++j) {
+                const int i = j * FLAC_THREADS + tid;
+                if (i < n) {
+                    const int d = 2 * i + 1 - n;
+                    x[i] = q[i] * (255 - (int)(255u * (unsigned int)(d * d) / nn));
+                }
+            }
+            __syncthreads();
+            // R[l] = sum_i x[i] x[i + l], exact: a product below 2^46, 4096 of them below 2^58
+            long long acc[FLAC_LPC_MAX + 1] = {};
+            for (int j = 0; j < passes; ++j) {
+                const int i = j * FLAC_THREADS + tid;
+                if (i < n) {
+                    const long long xi = x[i];
+#pragma unroll
+                    for (int l = 0; l <= FLAC_LPC_MAX; ++l)
+                        if (l <= top && i + l < n) acc[l] += xi * x[i + l];
+                }
+            }
+#pragma unroll
+            for (int l = 0; l <= FLAC_LPC_MAX; ++l) {
+                if (l <= top) {
+                    const long long s = wave_sum(acc[l]);
+                    if (lane == 0) racc[wave][l] = s;
+                }
+            }
+            __syncthreads();
+            double R[FLAC_LPC_MAX + 1];
+#pragma unroll
+            for (int l = 0; l <= FLAC_LPC_MAX; ++l) R[l] = l <= top ? (double)(racc[0][l] + racc[1][l] + racc[2][l] + racc[3][l]) : 0.0;
+            // Levinson-Durbin, fp64, the one operation order of the contract (no contraction: -ffp-contract=off); al[j - 1] is a_j
+            double al[FLAC_LPC_MAX] = {}, err = R[0];
+            bool alive = err > 0.0 && err < __builtin_inf();
+#pragma unroll
+            for (int m = 1; m <= FLAC_LPC_MAX; ++m) {
+                if (m <= top && alive) {
+                    double s = R[m];
+#pragma unroll
+                    for (int j = 1; j < m; ++j) s = s - al[j - 1] * R[m - j];
+                    const double k = s / err;
+                    double an[FLAC_LPC_MAX];
+#pragma unroll
+                    for (int j = 1; j < m; ++j) an[j - 1] = al[j - 1] - k * al[m - j - 1];
+#pragma unroll
+                    for (int j = 1; j < m; ++j) al[j - 1] = an[j - 1];
+                    al[m - 1] = k;
+                    err = err * (1.0 - k * k);
+                    alive = err > 0.0 && err < __builtin_inf();
+                    if (alive) {
+                        // quantise at precision 12: max|a| < 2^e with e from the exponent field, shift = min(15, 11 - e)
+                        double cmax = 0.0;
+#pragma unroll
+                        for (int j = 0; j < m; ++j) cmax = fmax(cmax, fabs(al[j]));
+                        const int e = (int)((__double_as_longlong(cmax) >> 52) & 0x7FF) - 1022;
+                        const int shift = FLAC_LPC_PRECISION - 1 - e < 15 ? FLAC_LPC_PRECISION - 1 - e : 15;
+#pragma unroll
+                        for (int ci = 0; ci < FLAC_LPC_CANDS; ++ci) {
+                            if (cand[ci] == m && shift >= 0) {
+                                lm[ci] = m;
+                                lshift[ci] = shift;
+#pragma unroll
+                                for (int j = 0; j < m; ++j) {
+                                    const double v = rint(al[j] * (double)(1 << shift));       // (ties to even)
+                                    lc[ci][j] = (int)fmin(fmax(v, -2048.0), 2047.0);
+                                }
+                            }
+                        }
+                    }
+                }
+            }
+        }
+    }
+
     // ---- the frame header (thread 0) and its length (every thread)
     const int rate = a.rates[b];
     const int rcode = flac_rate_code(rate);
@@ -270,65 +442,61 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_frame_kernel(const FlacArgs
         }
         body = 24;
     } else {
-        // ---- the folded residuals (0 where a sample has none), then sum(u >> k) for the 15 candidates over each run of 256 samples:
-        // thread (j, k) = (tid / 16, tid % 16) reads run j from LDS, 16 bytes at a time, its start rotated by 4 j reads so that the
-        // four runs a wave reads lie in different banks.  A run's sum stays below 256 * 2^21 = 2^29: 32 bits.  A full frame's
-        // partition j is run j; a short frame is one partition of up to 4095 values, the 64-bit sum of its runs (up to 2^33).
-        for (int j = 0; j < passes; ++j) {
-            const int i = j * FLAC_THREADS + tid;
-            unsigned int uu = 0;
-            if (i < n && i >= order) {
-                const int r = fixed_residual(q, i, order);
-                uu = r >= 0 ? 2u * (unsigned int)r : 2u * (unsigned int)(-r) - 1u;
-            }
-            u[i] = uu;
-        }
-        __syncthreads();
-        {
-            const int k = tid & 15, j = tid >> 4;
-            if (k < FLAC_KS && j < passes) {
-                const u32x4* run = reinterpret_cast<const u32x4*>(u + j * FLAC_THREADS);
-                unsigned int s = 0;
-                for (int x = 0; x < FLAC_THREADS / 4; ++x) {
-                    const u32x4 v = run[(x + 4 * j) & (FLAC_THREADS / 4 - 1)];
-                    s += (v[0] >> k) + (v[1] >> k) + (v[2] >> k) + (v[3] >> k);
+        // ---- FIXED's plan, then each LPC candidate's over the same LDS: the fewest bits win, ties to FIXED, then to the lower order
+        const auto fixed = [&](int i) { return fixed_residual(q, i, order); };
+        unsigned long long best_bits = 8ull + 16ull * order + 6ull + rice_plan<false>(u, part, pk, pcost, n, order, full, passes, fixed);
+        int lpc = 0, shift = 0;                  // the winner: its LPC order (0: FIXED), shift and coefficients
+        int cw[FLAC_LPC_MAX] = {};
+        if constexpr (LPC) {
+            int planned = 0;                     // the order whose plan the LDS holds (0: FIXED's)
+#pragma unroll
+            for (int ci = 0; ci < FLAC_LPC_CANDS; ++ci) {
+                if (lm[ci]) {
+                    const int m = lm[ci], sh = lshift[ci];
+                    const auto& c = lc[ci];
+                    const unsigned long long r = rice_plan<true>(u, part, pk, pcost, n, m, full, passes, [&](int i) { return lpc_residual(q, i, c, m, sh); });
+                    const unsigned long long bits_c = 8ull + 16ull * m + 9ull + (unsigned long long)(FLAC_LPC_PRECISION * m) + 6ull + r;
+                    planned = m;
+                    if (r != ~0ull && bits_c < best_bits) {
+                        best_bits = bits_c;
+                        lpc = m;
+                        shift = sh;
+#pragma unroll
+                        for (int j = 0; j < FLAC_LPC_MAX; ++j) cw[j] = c[j];
+                    }
                 }
-                part[j][k] = s;
+            }
+            if (planned != lpc && best_bits < 8ull + 16ull * n) {                  // the winner's plan again (same values)
+                if (lpc) rice_plan<false>(u, part, pk, pcost, n, lpc, full, passes, [&](int i) { return lpc_residual(q, i, cw, lpc, shift); });
+                else rice_plan<false>(u, part, pk, pcost, n, order, full, passes, fixed);
             }
         }
-        __syncthreads();
-        const int nparts = full ? passes : 1;
-        if (tid < nparts) {                      // k of partition tid: the fewest bits, ties to the smaller k
-            const unsigned long long cnt = full ? (unsigned long long)(FLAC_THREADS - (tid == 0 ? order : 0)) : (unsigned long long)(n - order);
-            const int j0 = full ? tid : 0, j1 = full ? tid + 1 : passes;
-            unsigned long long least = ~0ull;
-            int kbest = 0;
-            for (int k = 0; k < FLAC_KS; ++k) {
-                unsigned long long c = cnt * (k + 1);
-                for (int j = j0; j < j1; ++j) c += part[j][k];
-                if (c < least) { least = c; kbest = k; }
-            }
-            pk[tid] = kbest;
-            pcost[tid] = least;
-        }
-        __syncthreads();
-        unsigned long long fixed_bits = 8ull + 16ull * order + 6ull;
-        for (int p = 0; p < nparts; ++p) fixed_bits += 4ull + pcost[p];
+        const int worder = lpc ? lpc : order;    // warm-up words
+        const unsigned int pre = 8u + 16u * worder + (lpc ? 9u + (unsigned int)(FLAC_LPC_PRECISION * lpc) : 0u);      // bits before the residual
 
-        if (fixed_bits >= 8ull + 16ull * n) {    // VERBATIM: the bound of a frame, 2 * bs + 16 bytes
+        if (best_bits >= 8ull + 16ull * n) {     // VERBATIM: the bound of a frame, 2 * bs + 16 bytes
             if (tid == 0) put_bits(bits, sb, 0x02u, 8);
             for (int j = 0; j < passes; ++j) {
                 const int i = j * FLAC_THREADS + tid;
                 if (i < n) put_bits(bits, sb + 8 + 16 * i, (unsigned int)q[i] & 0xFFFFu, 16);
             }
             body = 8 + 16 * n;
-        } else {                                 // FIXED: below 8 + 16 n bits in all, so 32-bit positions hold
+        } else {                                 // FIXED or LPC: below 8 + 16 n bits in all, so 32-bit positions hold
             if (tid == 0) {
-                put_bits(bits, sb, 0x10u | (unsigned int)order << 1, 8);
-                put_bits(bits, sb + 8 + 16 * order, (unsigned int)(full ? a.log2bs - 8 : 0), 6);      // method 00, partition order
+                put_bits(bits, sb, lpc ? 0x40u | (unsigned int)(lpc - 1) << 1 : 0x10u | (unsigned int)order << 1, 8);
+                if (lpc) put_bits(bits, sb + 8 + 16 * lpc, (unsigned int)(FLAC_LPC_PRECISION - 1) << 5 | (unsigned int)shift, 9);
+                put_bits(bits, sb + pre, (unsigned int)(full ? a.log2bs - 8 : 0), 6);                 // method 00, partition order
             }
-            if (tid < order) put_bits(bits, sb + 8 + 16 * tid, (unsigned int)q[tid] & 0xFFFFu, 16);
-            unsigned int base = sb + 8 + 16 * order + 6;
+            if (tid < worder) put_bits(bits, sb + 8 + 16 * tid, (unsigned int)q[tid] & 0xFFFFu, 16);
+            if constexpr (LPC) {
+                if (tid < lpc) {                 // coefficient tid, two's complement
+                    int mine = 0;
+#pragma unroll
+                    for (int j = 0; j < FLAC_LPC_MAX; ++j) mine = tid == j ? cw[j] : mine;
+                    put_bits(bits, sb + 8 + 16 * lpc + 9 + FLAC_LPC_PRECISION * tid, (unsigned int)mine & 0xFFFu, FLAC_LPC_PRECISION);
+                }
+            }
+            unsigned int base = sb + pre + 6;
             int k = 0;
             for (int j = 0; j < passes; ++j) {
                 if (full || j == 0) {
@@ -337,7 +505,7 @@ __global__ __launch_bounds__(FLAC_THREADS) void flac_frame_kernel(const FlacArgs
                     base += 4;
                 }
                 const int i = j * FLAC_THREADS + tid;
-                const bool coded = i < n && i >= order;
+                const bool coded = i < n && i >= worder;
                 const unsigned int uu = coded ? u[i] : 0u;
                 unsigned int total;
                 const unsigned int at = block_exscan<unsigned int>(coded ? (uu >> k) + 1 + k : 0u, wsum, total);
@@ -471,6 +639,49 @@ static bool flac_overlap(const void* p, size_t np, const void* q, size_t nq) {
     return a < b + nq && b < a + np;
 }
 
+// both entries: max_lpc_order 0 is mtts_flac_encode, launch for launch
+static int flac_encode(const std::string& who, const float* d_audio, int64_t ld, const int64_t* d_lengths, const int32_t* d_rates,
+                       const int64_t* d_keys, int B, int block_size, int max_lpc_order, int dither, int64_t seed, uint8_t* d_out,
+                       int64_t out_ld, int64_t* d_out_bytes, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!d_audio || !d_lengths || !d_rates || !d_out || !d_out_bytes || !d_ws) { set_error(who + ": null argument"); return -1; }
+    if (B < 1 || B > 65535) { set_error(who + ": B must lie in [1, 65535]"); return -1; }
+    if (flac_shape_ok(who.c_str(), ld, block_size)) return -1;
+    FlacArgs a;
+    flac_shape(a, ld, block_size);
+    if (out_ld < (FLAC_HEADER + a.nfmax * a.slot + 15) / 16 * 16 || (out_ld & 15)) {
+        set_error(who + ": out_ld must be a multiple of 16, at least mtts_flac_row_bytes(ld, block_size)");
+        return -1;
+    }
+    WS ws(d_ws, (size_t)(ws_bytes < 0 ? 0 : ws_bytes));
+    flac_carve(ws, a, B);
+    if (ws.overflow) { set_error(who + ": workspace too small (mtts_flac_workspace_bytes)"); return -1; }
+    if ((reinterpret_cast<uintptr_t>(d_audio) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15) || (reinterpret_cast<uintptr_t>(d_ws) & 15)) {
+        set_error(who + ": misaligned buffer (16 bytes)");
+        return -1;
+    }
+    const size_t in_bytes = (size_t)B * ld * sizeof(float), out_bytes = (size_t)B * out_ld;
+    if (flac_overlap(d_audio, in_bytes, d_out, out_bytes) || flac_overlap(d_audio, in_bytes, d_ws, ws.off) ||
+        flac_overlap(d_out, out_bytes, d_ws, ws.off)) {
+        set_error(who + ": d_out, d_ws and d_audio must not overlap");
+        return -1;
+    }
+    a.audio = d_audio; a.lengths = d_lengths; a.rates = d_rates; a.keys = d_keys;
+    a.seed_lo = (unsigned int)((uint64_t)seed & 0xFFFFFFFFu);
+    a.seed_hi = (unsigned int)((uint64_t)seed >> 32);
+    a.dither = dither ? 1 : 0;
+    a.lpc = max_lpc_order;
+    a.out = d_out; a.out_ld = out_ld; a.out_bytes = d_out_bytes;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t lds = (size_t)2 * a.bs * sizeof(int) + a.slot;
+    if (max_lpc_order) hipLaunchKernelGGL(flac_frame_kernel<true>, dim3((unsigned)a.nfmax, B), dim3(FLAC_THREADS), lds, s, a);
+    else hipLaunchKernelGGL(flac_frame_kernel<false>, dim3((unsigned)a.nfmax, B), dim3(FLAC_THREADS), lds, s, a);
+    RET_IF(launched("flac_frame_kernel"));
+    hipLaunchKernelGGL(flac_layout_kernel, dim3(B), dim3(FLAC_THREADS), 0, s, a);
+    RET_IF(launched("flac_layout_kernel"));
+    hipLaunchKernelGGL(flac_compact_kernel, dim3((unsigned)a.nfmax, B), dim3(FLAC_THREADS), 0, s, a);
+    return launched("flac_compact_kernel");
+}
+
 extern "C" {
 
 int64_t mtts_flac_row_bytes(int64_t ld, int block_size) {
@@ -493,41 +704,16 @@ int64_t mtts_flac_workspace_bytes(int B, int64_t ld, int block_size) {
 int mtts_flac_encode(const float* d_audio, int64_t ld, const int64_t* d_lengths, const int32_t* d_rates, const int64_t* d_keys, int B,
                      int block_size, int dither, int64_t seed, uint8_t* d_out, int64_t out_ld, int64_t* d_out_bytes, void* d_ws,
                      int64_t ws_bytes, void* stream) {
-    if (!d_audio || !d_lengths || !d_rates || !d_out || !d_out_bytes || !d_ws) { set_error("mtts_flac_encode: null argument"); return -1; }
-    if (B < 1 || B > 65535) { set_error("mtts_flac_encode: B must lie in [1, 65535]"); return -1; }
-    if (flac_shape_ok("mtts_flac_encode", ld, block_size)) return -1;
-    FlacArgs a;
-    flac_shape(a, ld, block_size);
-    if (out_ld < (FLAC_HEADER + a.nfmax * a.slot + 15) / 16 * 16 || (out_ld & 15)) {
-        set_error("mtts_flac_encode: out_ld must be a multiple of 16, at least mtts_flac_row_bytes(ld, block_size)");
-        return -1;
-    }
-    WS ws(d_ws, (size_t)(ws_bytes < 0 ? 0 : ws_bytes));
-    flac_carve(ws, a, B);
-    if (ws.overflow) { set_error("mtts_flac_encode: workspace too small (mtts_flac_workspace_bytes)"); return -1; }
-    if ((reinterpret_cast<uintptr_t>(d_audio) & 15) || (reinterpret_cast<uintptr_t>(d_out) & 15) || (reinterpret_cast<uintptr_t>(d_ws) & 15)) {
-        set_error("mtts_flac_encode: misaligned buffer (16 bytes)");
-        return -1;
-    }
-    const size_t in_bytes = (size_t)B * ld * sizeof(float), out_bytes = (size_t)B * out_ld;
-    if (flac_overlap(d_audio, in_bytes, d_out, out_bytes) || flac_overlap(d_audio, in_bytes, d_ws, ws.off) ||
-        flac_overlap(d_out, out_bytes, d_ws, ws.off)) {
-        set_error("mtts_flac_encode: d_out, d_ws and d_audio must not overlap");
-        return -1;
-    }
-    a.audio = d_audio; a.lengths = d_lengths; a.rates = d_rates; a.keys = d_keys;
-    a.seed_lo = (unsigned int)((uint64_t)seed & 0xFFFFFFFFu);
-    a.seed_hi = (unsigned int)((uint64_t)seed >> 32);
-    a.dither = dither ? 1 : 0;
-    a.out = d_out; a.out_ld = out_ld; a.out_bytes = d_out_bytes;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const size_t lds = (size_t)2 * a.bs * sizeof(int) + a.slot;
-    hipLaunchKernelGGL(flac_frame_kernel, dim3((unsigned)a.nfmax, B), dim3(FLAC_THREADS), lds, s, a);
-    RET_IF(launched("flac_frame_kernel"));
-    hipLaunchKernelGGL(flac_layout_kernel, dim3(B), dim3(FLAC_THREADS), 0, s, a);
-    RET_IF(launched("flac_layout_kernel"));
-    hipLaunchKernelGGL(flac_compact_kernel, dim3((unsigned)a.nfmax, B), dim3(FLAC_THREADS), 0, s, a);
-    return launched("flac_compact_kernel");
+    return flac_encode("mtts_flac_encode", d_audio, ld, d_lengths, d_rates, d_keys, B, block_size, 0, dither, seed, d_out, out_ld, d_out_bytes,
+                       d_ws, ws_bytes, stream);
+}
+
+int mtts_flac_encode_lpc(const float* d_audio, int64_t ld, const int64_t* d_lengths, const int32_t* d_rates, const int64_t* d_keys, int B,
+                         int block_size, int max_lpc_order, int dither, int64_t seed, uint8_t* d_out, int64_t out_ld, int64_t* d_out_bytes,
+                         void* d_ws, int64_t ws_bytes, void* stream) {
+    if (max_lpc_order < 0 || max_lpc_order > FLAC_LPC_MAX) { set_error("mtts_flac_encode_lpc: max_lpc_order lies in 0..12"); return -1; }
+    return flac_encode("mtts_flac_encode_lpc", d_audio, ld, d_lengths, d_rates, d_keys, B, block_size, max_lpc_order, dither, seed, d_out,
+                       out_ld, d_out_bytes, d_ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -111,9 +111,11 @@ class SpeechService:
 
     def __init__(self, batcher, phonemize: Callable[[str, str], Sequence[int]], max_text_length: int = MAX_TEXT_LENGTH,
                  loudness: Optional[float] = None, true_peak: Optional[float] = None, marks: bool = False,
-                 word_groups: Optional[Callable[[str, str, Sequence[int]], Sequence[int]]] = None, flac: bool = False):
+                 word_groups: Optional[Callable[[str, str, Sequence[int]], Sequence[int]]] = None, flac: bool = False,
+                 flac_lpc: int = 0):
         """``flac``: this service also answers ``response_format="flac"`` (one FLAC stream per request, encoded on the device); without
-        it the name is refused as every unknown one is.
+        it the name is refused as every unknown one is.  ``flac_lpc``: 0, or the LPC order (1..12) its FLAC streams also try
+        (``Request.flac_lpc``: the same words in fewer bytes, about 0.82 of the bytes at 12); it needs ``flac=True``.
         ``marks``: every request of this service asks for token marks -- ``submit``'s future then carries ``"marks"``: ``{"tokens":
         [(start_s, end_s)] per token}`` in seconds of the 24 kHz result (``timing.token_marks``; nominal positions) -- and
         ``word_groups(text, language, ids)``, when given, names the word of each token (-1: none; ``timing.word_groups`` over the
@@ -132,18 +134,23 @@ class SpeechService:
         self.marks = bool(marks)
         self.word_groups = word_groups
         self.flac = bool(flac)
+        from .audio_codec import flac_lpc_order
+        self.flac_lpc = flac_lpc_order(flac_lpc)
+        if self.flac_lpc and not self.flac:
+            raise ValueError(f"flac_lpc = {flac_lpc} belongs to a service built with flac=True")
 
     def timed(self, marks: bool = True) -> "SpeechService":
         """This service -- the same batcher, front end, target and ceiling -- with token marks on (or off): ``service.timed().submit(text)``
         gives a future whose result carries ``"marks"``.  ``submit`` and ``speak`` keep their signatures, so marks for a single request
         are asked for this way; ``submit_long`` and ``speak_long`` also take ``marks=`` themselves."""
-        return SpeechService(self.batcher, self.phonemize, self.max_text_length, self.loudness, self.true_peak, marks, self.word_groups, self.flac)
+        return SpeechService(self.batcher, self.phonemize, self.max_text_length, self.loudness, self.true_peak, marks, self.word_groups, self.flac, self.flac_lpc)
 
     def _fields(self, speaker_embedding, sample_rate, encoding, target, ceiling, marks, word_groups: Callable[[], list]) -> dict:
         """The fields a submission names beside its voice and speeds -- only those that differ from a ``Request``'s defaults, so a plain
         one names none.  ``word_groups()``: the word of each token, asked for only with marks and a ``word_groups`` front end."""
         named = dict(speaker_embedding=None if speaker_embedding is None else tuple(speaker_embedding),
                      sample_rate=int(sample_rate) if int(sample_rate) != 24000 else None, encoding=encoding, loudness=target, true_peak=ceiling,
+                     flac_lpc=self.flac_lpc if encoding in COMPRESSED_FORMATS.values() and self.flac_lpc else None,
                      marks=True if marks else None, word_groups=word_groups() if marks and self.word_groups is not None else None)
         return {k: v for k, v in named.items() if v is not None}
 
@@ -152,7 +159,7 @@ class SpeechService:
         true-peak ceiling in dBTP (None: none).  A value that is no level, and a ceiling without a target, raise here, before
         anything is submitted.  ``submit`` and ``speak`` keep their positional signatures, so the target of a
         single request is named this way; ``submit_long`` and ``speak_long`` also take ``loudness=`` themselves."""
-        return SpeechService(self.batcher, self.phonemize, self.max_text_length, loudness, true_peak, self.marks, self.word_groups, self.flac)
+        return SpeechService(self.batcher, self.phonemize, self.max_text_length, loudness, true_peak, self.marks, self.word_groups, self.flac, self.flac_lpc)
 
     def submit(self, text: str, voice=0, speed: float = 1.0, steps: int = DEFAULT_NUM_STEPS, solver: str = DEFAULT_ODE_SOLVER,
                speaker_embedding=None, sample_rate: int = 24000, response_format: Optional[str] = None):

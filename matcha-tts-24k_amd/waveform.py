@@ -210,6 +210,20 @@ def _resolve(rows: Callable[[], int], *, encoding=None, dither=False, dither_key
                  marks=bool(return_marks))
 
 
+def _flac_orders(flac_lpc, plan):
+    """``flac_lpc=`` of ``tail`` as ``lpc_order`` per result, 0 where a row is no stream; None when every one is 0.  A value that
+    is no order, and an order where no FLAC row takes it, raise here, before anything is launched."""
+    one = not isinstance(flac_lpc, (list, tuple))
+    orders = _spread([AC.flac_lpc_order(v) for v in ([flac_lpc] if one else flac_lpc)], one, plan.n, "flac_lpc")
+    streamed = [plan.encs is not None and e == AC.FLAC for e in (plan.encs or [None] * plan.n)]
+    if one and orders[0] and not any(streamed):
+        raise ValueError(f"tail: flac_lpc = {flac_lpc} belongs to encoding=\"flac\", and no row names it")
+    if not one and any(o and not on for o, on in zip(orders, streamed)):
+        raise ValueError(f"tail: flac_lpc = {list(flac_lpc)} names an order on a row whose encoding is not \"flac\"")
+    orders = [o if on else 0 for o, on in zip(orders, streamed)]
+    return orders if any(orders) else None
+
+
 def _true_peak_ceilings(true_peak, targets, n):
     """``true_peak=`` of ``to_waveforms`` as n ceilings in dBTP or None per row; None when no row names one.  A value that is no
     ceiling, and a ceiling on a row without a loudness target, raise here, before anything is launched."""
@@ -270,7 +284,8 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
     A ``"flac"`` row comes back as one complete FLAC stream (``audio_codec.encode_flac``: mono, 16 bits, blocks of 4096 samples, at
     the row's converted rate), a file as it is, holding exactly the words ``"pcm16"`` gives for it -- dithered the same way when
     ``dither`` is on.  Batches may mix the names: the PCM / G.711 launch and the FLAC call each see only their rows; the stream lengths
-    ride in the same ``meta`` copy, and only the columns of the longest stream are copied.
+    ride in the same ``meta`` copy, and only the columns of the longest stream are copied.  (LPC subframes in those streams:
+    ``tail(..., flac_lpc=)``, which is this call with one more option.)
 
     ``documents``: None (every row is its own result, as ever: nothing below is launched or allocated), or the rows that belong
     together as a host list -- row counts in speaking order, or the CSR ``[0, n0, n0 + n1, ...]``; rows behind the last document are
@@ -322,8 +337,14 @@ def to_waveforms(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.
 def tail(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, **options) -> Tail:
     """``to_waveforms`` (``options``: its keyword-only arguments) with its result as a record in place of a tuple whose arity depends
     on the flags.  The stages, in their one order: decode, finish, [timing plan (+ breaks gather)], [join], [loudness], [rate
-    conversion], [encode], ending; a bracketed stage is not entered when the plan has no row for it."""
+    conversion], [encode], ending; a bracketed stage is not entered when the plan has no row for it.
+    One option is this entry's own: ``flac_lpc``, 0 (FIXED predictors, as ever) or 1..12 -- the FLAC rows of the call also try linear
+    prediction up to that order (``encode_flac(lpc_order=)``: the same words in fewer bytes).  One value for the call's FLAC rows
+    (without such a row it raises ``ValueError``), or one per row, 0 on every row that is no stream: the FLAC call is then made once
+    per distinct order over its own rows, so a row's bytes do not depend on its batch."""
+    flac_lpc = options.pop("flac_lpc", 0)                             # (the FLAC stage's own: the plan is what it was without it)
     plan = _resolve(lambda: 1 if mel.dim() == 2 else mel.shape[0], **options)
+    orders = _flac_orders(flac_lpc, plan)
     model = vocoder.model if hasattr(vocoder, "model") else vocoder
     mel = mel[None] if mel.dim() == 2 else mel
     (B, _, T), hop = mel.shape, model.cfg["hop"]
@@ -364,8 +385,8 @@ def tail(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, **opt
             data, meta["nbytes"] = AC.encode(rows, torch.where(named, lengths, torch.zeros_like(lengths)), [e if on else AC.PCM16 for e, on in zip(plan.encs, sampled)],
                                              dither=dither, keys=plan.keys)
         if any(streamed):
+            flac, nbytes = _flac_stage(rows, lengths, plan, streamed, dither, orders)
             mine = torch.tensor(streamed, dtype=torch.bool, device=rows.device)
-            flac, nbytes = AC.encode_flac(rows, torch.where(mine, lengths, torch.zeros_like(lengths)), plan.rates, dither=dither, keys=plan.keys)
             meta["nbytes"] = torch.where(mine, nbytes, meta["nbytes"]) if data is not None else nbytes
     try:
         out, starts = _ending(rows, lengths, plan, meta, data, T, flac)
@@ -376,6 +397,19 @@ def tail(mel, mel_lengths, vocoder, trim=True, silence_threshold_db=-60.0, **opt
         per_row = TM.marks_rows(marks_host, B, starts)
         out.marks = per_row if plan.csr is None else [per_row[a:b] for a, b in zip(plan.csr[:-1], plan.csr[1:])]
     return out
+
+
+def _flac_stage(rows, lengths, plan, streamed, dither, orders):
+    """The FLAC rows of the plan as streams: ``(data, byte counts)`` of ``audio_codec.encode_flac`` over all rows, the others taking
+    part with length 0.  One call; with ``orders`` (``_flac_orders``) one per distinct order, each over its own rows."""
+    orders = orders or [0] * plan.n
+    data = nbytes = None
+    for order in sorted({o for o, on in zip(orders, streamed) if on}):
+        mine = torch.tensor([on and o == order for o, on in zip(orders, streamed)], dtype=torch.bool, device=rows.device)
+        kw = dict(lpc_order=order) if order else {}
+        d, n = AC.encode_flac(rows, torch.where(mine, lengths, torch.zeros_like(lengths)), plan.rates, dither=dither, keys=plan.keys, **kw)
+        data, nbytes = (d, n) if data is None else (torch.where(mine[:, None], d, data), torch.where(mine, n, nbytes))
+    return data, nbytes
 
 
 def _document_scales(scale, plan):
@@ -475,13 +509,16 @@ def _ending(rows, lengths, plan, meta, data, T, flac=None):
 
 
 def finish_request(waveform, *, loudness=None, true_peak=None, report=False, sample_rate=SAMPLE_RATE, encoding=None, dither=False,
-                   dither_key=None):
+                   dither_key=None, flac_lpc=0):
     """The tail of one request behind the normalisation and the trim, in the order of the batched tail: ``waveform`` 1-D float32 on
     the device at 24 kHz -> ``(host tensor, report)``.  The loudness step (``loudness`` a checked target in LUFS, its gain also limited
     by a ``true_peak`` ceiling in dBTP), the rate conversion, the encoding (``dither`` / ``dither_key`` as ``audio_codec.encode`` takes
-    them; raw uint8 samples, or with ``"flac"`` one FLAC stream at the converted rate, ``audio_codec.encode_flac``).  ``report``: what the loudness step measured BEFORE the gain, ``(lufs, gain)`` -- the dict of
+    them; raw uint8 samples, or with ``"flac"`` one FLAC stream at the converted rate, ``audio_codec.encode_flac``, ``flac_lpc`` its ``lpc_order``: a value without ``"flac"`` raises ``ValueError``).  ``report``: what the loudness step measured BEFORE the gain, ``(lufs, gain)`` -- the dict of
     ``loudness.normalize(return_meter=True)`` under a ceiling; the meter runs only then -- else None.  An empty waveform passes through."""
     rep, n, rate = None, waveform.numel(), int(sample_rate)
+    flac_lpc = AC.flac_lpc_order(flac_lpc)
+    if flac_lpc and (encoding is None or AC.encoding_id(encoding) != AC.FLAC):
+        raise ValueError(f"finish_request: flac_lpc = {flac_lpc} belongs to encoding=\"flac\", got {encoding!r}")
     if loudness is not None and n > 0:
         rows = torch.zeros(1, (n + 3) // 4 * 4, dtype=torch.float32, device=waveform.device)
         rows[0, :n] = waveform
@@ -495,7 +532,8 @@ def finish_request(waveform, *, loudness=None, true_peak=None, report=False, sam
         waveform = conv[0, :R.resampler(SAMPLE_RATE, rate, conv.device).out_length(n)]
     if encoding is not None and AC.encoding_id(encoding) == AC.FLAC:           # a stream at any length: an empty one is its 42 header bytes
         rows = waveform.reshape(1, -1) if n > 0 else torch.zeros(1, 4, dtype=torch.float32, device=waveform.device)
-        data, nbytes = AC.encode_flac(rows, [waveform.numel()], rate, dither=dither, keys=None if dither_key is None else [dither_key])
+        data, nbytes = AC.encode_flac(rows, [waveform.numel()], rate, dither=dither, keys=None if dither_key is None else [dither_key],
+                                        **(dict(lpc_order=flac_lpc) if flac_lpc else {}))
         size = int(nbytes[0])
         if size < 0:
             raise ValueError(f"finish_request: a FLAC stream names its rate in 20 bits, sample_rate = {rate} is outside [1, 1048575]")

@@ -92,6 +92,10 @@ def speak(args) -> int:
         if groups is not None:
             extra["word_groups"] = groups
     flac = Path(args.out).suffix.lower() == ".flac"                   # OUT.flac: the document as one FLAC stream, encoded on the device
+    if args.flac_lpc:
+        if not flac:
+            raise SystemExit("--flac-lpc belongs to an OUT.flac")
+        extra["flac_lpc"] = args.flac_lpc
     with bt.FrameBudgetBatcher(model, max_batch=max(32, len(ids)), max_tokens=max(8192, len(ids) * max(len(s) for s in ids)),
                                vocoder=vocoder, fade_ms=args.fade_ms) as q:
         res = q.submit_document(ids, pauses, speaker=p.speaker, voice_mix=p.voice_mix, solver=p.solver, n_timesteps=p.n_timesteps,
@@ -238,6 +242,7 @@ def main() -> int:
     sp.add_argument("--max-chars", type=int, default=300)
     sp.add_argument("--fade-ms", type=float, default=5.0)
     sp.add_argument("--level", choices=("document", "sentence"), default="document")
+    sp.add_argument("--flac-lpc", type=int, default=0, metavar="N", help="an OUT.flac also tries linear prediction up to order N (1..12): fewer bytes")
     sp.add_argument("--loudness", type=float, default=None, metavar="LUFS", help="integrated loudness of the joined document, e.g. -16, -19, -23")
     sp.add_argument("--true-peak", type=float, default=None, metavar="DB", help="ceiling in dBTP on the true peak of the levelled document, e.g. -1")
     sp.add_argument("--captions", default=None, metavar="FILE.vtt|.srt", help="one cue per sentence, from the result's segments")
