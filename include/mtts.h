@@ -753,6 +753,54 @@ int64_t mtts_style_workspace_bytes(mtts_style* v, int B, int T);
 int mtts_style_forward(mtts_style* v, const float* d_mel, const int64_t* d_mel_lengths, int B, int T, const int32_t* d_group,
                        int n_groups, float* d_e_enc, float* d_e_dur, void* d_ws, int64_t ws_bytes, void* stream);
 
+/* Parameter gradients of the style encoder, for training it on the device (reference StyleEncoderLightningModule,
+ * matcha/models/style_encoder.py:75-160; the optimiser and the matching loss are the caller's).
+ *
+ * The parameters as ONE flat fp32 buffer in the reference's state-dict order: convs.i.weight [hidden, cin, 5], convs.i.bias [hidden]
+ * for every layer, then proj_enc.weight [E, hidden], proj_enc.bias [E], proj_dur.weight, proj_dur.bias.  mtts_style_param_count is
+ * its length in floats, mtts_style_param_offset(v, key) the first float of a tensor (-1: no such key).
+ *
+ * mtts_style_forward_taped: the launches of mtts_style_forward with d_group == NULL, one activation buffer per layer and the pooled
+ *   rows kept in d_ws (mtts_style_grad_workspace_bytes); d_e_enc / d_e_dur [B, E] equal mtts_style_forward's bit for bit.
+ *   mtts_style_grad_tape_offset(v, B, T, which): byte offset in d_ws of which = 0 the masked channels-last input rows
+ *   [B*T, round_up(n_feats, 4)], 1 .. n_layers the ReLU output of layer which - 1 [B*T, hidden], n_layers + 1 the pooled rows
+ *   [B, hidden], n_layers + 2 the prefix mask [B*T].
+ * mtts_style_backward: from that tape (same d_ws, B, T, d_mel_lengths) and upstream d_g_enc, d_g_dur [B, E], the gradient of
+ *   sum_b <g_enc_b, e_enc_b> + <g_dur_b, e_dur_b> with respect to every parameter -> d_param_grad [mtts_style_param_count], every
+ *   float written.  Projections: d W[o,c] = sum_b g[b,o] pooled[b,c] in batch order, d b[o] = sum_b g[b,o], d pooled = g W.  Pool:
+ *   d pooled / max(len_b, 1) on the frames t < len_b.  Per layer, last to first: the gate (H_l > 0) times the prefix mask, the bias
+ *   and weight gradients (mtts_conv_wgrad below), and for layers >= 1 the data gradient as a GEMM with the transposed, tap-reversed
+ *   panel in NATIVE FP32 MFMA (arithmetic 0) whatever the forward arithmetic is.  Those panels are packed on demand from the
+ *   registered tensors into a buffer of their own (mtts_style_grad_weights_bytes / mtts_style_grad_upload_weights;
+ *   mtts_style_set_tensor invalidates them) and passed as d_grad_buf.  A clip of length 0 contributes exactly zero.  Every sum has a
+ *   fixed order and there are no floating-point atomics: two calls give the same bits.  Stream-ordered, no allocation.
+ *   Both return -1 (mtts_last_error) for null pointers, B < 1, T < 1, a small workspace, weights (or backward panels) not uploaded.
+ *   The clip average (d_group) has no taped form. */
+int64_t mtts_style_param_count(mtts_style* v);
+int64_t mtts_style_param_offset(mtts_style* v, const char* key);
+int64_t mtts_style_grad_weights_bytes(mtts_style* v);
+int mtts_style_grad_upload_weights(mtts_style* v, void* d_buf, int64_t bytes);
+int64_t mtts_style_grad_workspace_bytes(mtts_style* v, int B, int T);
+int64_t mtts_style_grad_tape_offset(mtts_style* v, int B, int T, int which);
+int mtts_style_forward_taped(mtts_style* v, const float* d_mel, const int64_t* d_mel_lengths, int B, int T, float* d_e_enc,
+                             float* d_e_dur, void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_style_backward(mtts_style* v, const int64_t* d_mel_lengths, int B, int T, const float* d_g_enc, const float* d_g_dur,
+                        float* d_param_grad, void* d_grad_buf, void* d_ws, int64_t ws_bytes, void* stream);
+
+/* Kernel-level entry of the Conv1d(k5, pad 2) weight gradient (no context):
+ *   d_dw[co, ci, k] = sum over rows r = (b, t), t < len_b, of d_dz[r, co] * d_x[(b, t + k - 2), ci]     (taps outside [0, len_b) are zero)
+ * d_dz [B*T, cout] and d_x [B*T, ldx] (ldx >= cin) channels-last fp32 rows, d_lengths int64 [B] (held inside [0, T]) or NULL (every
+ * clip has T frames) -> d_dw [cout, cin, 5] in torch's layout and d_db [cout] = the column sums of d_dz (NULL: not computed).  What
+ * lies at t >= len_b is never used as data, and clips that are neighbours in memory do not see each other.  Exact fp32 FMA chains
+ * (v_mfma_f32_32x32x2_f32).  The rows are cut into chunks of mtts_conv_wgrad_chunk_rows(B, T) rows -- 256 up to 4096 rows, beyond
+ * that the multiple of 256 that gives at most 16 chunks: a function of the shape alone -- each chunk is one serial sum in row order,
+ * the partial results go to d_ws ([chunks, 5, cout, cin] then [chunks, cout]; mtts_conv_wgrad_workspace_bytes) and a second kernel
+ * adds them in chunk order.  No atomics: two calls give the same bits. */
+int mtts_conv_wgrad_chunk_rows(int B, int T);
+int64_t mtts_conv_wgrad_workspace_bytes(int B, int T, int cin, int cout);
+int mtts_conv_wgrad(const float* d_dz, const float* d_x, const int64_t* d_lengths, int B, int T, int cin, int ldx, int cout,
+                    float* d_dw, float* d_db, void* d_ws, int64_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- sample-rate conversion */
 
 /* A ragged batch of fp32 clips from orig_freq to new_freq: the windowed-sinc polyphase interpolation that
@@ -1410,6 +1458,36 @@ int mtts_spk_grad(mtts_ctx* ctx, const int64_t* d_x, const int64_t* d_x_lengths,
                   float delta_dur, int B, int Tx, int Tm, float* d_g_enc, float* d_g_dur, float* d_prior_sum, float* d_dur_sum,
                   int32_t* d_durations_out, void* d_grad_buf, void* d_ws, int64_t ws_bytes, void* stream);
 int mtts_spk_grad_status(const void* d_ws, void* stream);
+
+/* Style-encoder training's loss and its gradient with respect to the rows -- reference matcha/models/style_encoder.py:119-143: the
+ * frozen text encoder's outputs under PREDICTED rows (d_e_enc, d_e_dur [B, spk_emb_dim]) matched against its outputs under the real
+ * rows, d_mu_ref [B, n_feats, Tx] and d_logw_ref [B, Tx] as mtts_text_encoder_forward returned them (constants: the reference
+ * computes them under no_grad), with smooth-L1: per term 0.5 d^2 / beta below beta, |d| - 0.5 beta from beta on (the reference's
+ * betas: 0.002 for mu, 0.004 for logw).  The reference freezes Matcha in eval() for this training, so this is exactly its gradient.
+ *   The taped forward and the two walks back are mtts_spk_grad's (same functions, same panels in d_grad_buf); the seeds are
+ *   d ac_sum_b / d mu_x[f, x] = clamp((mu_x - mu_ref) / beta_mu, -1, 1) and the same for logw with beta_logw on x < len_b, zero
+ *   elsewhere.  d_g_enc, d_g_dur [B, spk_emb_dim]: gradients of the PER-UTTERANCE sums d_ac_sum, d_rh_sum [B]; the reference's batch
+ *   losses and gradients are the batch sums divided by sum_b len_b (for both: tokens, not tokens x channels), which the caller forms.
+ *   Every sum has a fixed order, no floating-point atomics: an utterance's rows do not depend on its batch, two calls give the same
+ *   bits.  An utterance whose length is outside [1, Tx] gets zero rows and zero sums, the others are unaffected, and
+ *   mtts_spk_grad_match_status(d_ws, stream) -- the one entry here that waits for the stream -- names it.  Returns -1
+ *   (mtts_last_error) for null pointers, B < 1, Tx > 1024, a beta <= 0, a small workspace (mtts_spk_grad_match_workspace_bytes),
+ *   backward panels that are not uploaded in d_grad_buf. */
+int64_t mtts_spk_grad_match_workspace_bytes(mtts_ctx* ctx, int B, int Tx);
+int mtts_spk_grad_match(mtts_ctx* ctx, const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur,
+                        const float* d_mu_ref, const float* d_logw_ref, float beta_mu, float beta_logw, int B, int Tx, float* d_g_enc,
+                        float* d_g_dur, float* d_ac_sum, float* d_rh_sum, void* d_grad_buf, void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_spk_grad_match_status(const void* d_ws, void* stream);
+
+/* Kernel-level entry of mtts_spk_grad_match's seed and sum kernels on given buffers (no context): d_mu / d_mu_ref [B, F, Tx],
+ * d_logw / d_logw_ref [B, Tx], d_lengths int64 [B], d_w_proj [Fd] (the duration predictor's output projection row) ->
+ * d_seed_mu [B*Tx, F] = clamp((mu - mu_ref) / beta_mu, -1, 1) as channels-last rows, d_seed_logw [B*Tx, Fd] = the logw seed times
+ * d_w_proj, both zero at x >= len_b; d_ac_sum / d_rh_sum [B] the smooth-L1 sums.  An utterance whose length is outside [1, Tx] gets
+ * zeros.  Tx <= 1024; d_scratch: mtts_match_seeds_scratch_bytes(B, F). */
+int64_t mtts_match_seeds_scratch_bytes(int B, int F);
+int mtts_match_seeds(const float* d_mu, const float* d_mu_ref, const float* d_logw, const float* d_logw_ref, const int64_t* d_lengths,
+                     const float* d_w_proj, int B, int F, int Tx, int Fd, float beta_mu, float beta_logw, float* d_seed_mu,
+                     float* d_seed_logw, float* d_ac_sum, float* d_rh_sum, void* d_scratch, void* stream);
 
 /* Kernel-level entries of the two backward kernels, fp32 rows in and out (no context).
  * mtts_channel_layernorm_bwd: backward of mtts_channel_layernorm (text_encoder.py:19-27 + SiLU / FiLM / mask as that entry): d_x the

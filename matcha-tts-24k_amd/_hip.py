@@ -19,7 +19,7 @@ from .hparams import PathHParams
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = Path(os.environ["MTTS_HIP_LIB"]) if os.environ.get("MTTS_HIP_LIB") else HERE / "libmtts_hip.so"   # override: A/B of two builds
-SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "resample.hip", "audio_codec.hip", "flac.hip", "flac_decode.hip", "corpus.hip", "wave_join.hip", "timing.hip", "loudness.hip", "style_encoder.hip", "mas.hip", "score.hip", "spk_grad.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
+SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "resample.hip", "audio_codec.hip", "flac.hip", "flac_decode.hip", "corpus.hip", "wave_join.hip", "timing.hip", "loudness.hip", "style_encoder.hip", "style_grad.hip", "mas.hip", "score.hip", "spk_grad.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
 HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", CSRC / "host.h", HERE.parent / "include" / "mtts.h"]
 SOLVERS = {"euler": 0, "midpoint": 1, "rk4": 2}
 
@@ -353,6 +353,17 @@ def load() -> C.CDLL:
         "mtts_style_upload_weights": (i32, [vp, vp, i64]),
         "mtts_style_workspace_bytes": (i64, [vp, i32, i32]),
         "mtts_style_forward": (i32, [vp, vp, vp, i32, i32, vp, i32, vp, vp, vp, i64, vp]),
+        "mtts_style_param_count": (i64, [vp]),
+        "mtts_style_param_offset": (i64, [vp, C.c_char_p]),
+        "mtts_style_grad_weights_bytes": (i64, [vp]),
+        "mtts_style_grad_upload_weights": (i32, [vp, vp, i64]),
+        "mtts_style_grad_workspace_bytes": (i64, [vp, i32, i32]),
+        "mtts_style_grad_tape_offset": (i64, [vp, i32, i32, i32]),
+        "mtts_style_forward_taped": (i32, [vp, vp, vp, i32, i32, vp, vp, vp, i64, vp]),
+        "mtts_style_backward": (i32, [vp, vp, i32, i32, vp, vp, vp, vp, vp, i64, vp]),
+        "mtts_conv_wgrad_chunk_rows": (i32, [i32, i32]),
+        "mtts_conv_wgrad_workspace_bytes": (i64, [i32, i32, i32, i32]),
+        "mtts_conv_wgrad": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp]),
         "mtts_mas_workspace_bytes": (i64, [i32, i32, i32]),
         "mtts_mas_logprior": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "mtts_mas": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]),
@@ -369,6 +380,11 @@ def load() -> C.CDLL:
         "mtts_spk_grad_tape_offset": (i64, [vp, i32, i32, i32, i32]),
         "mtts_spk_grad": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
         "mtts_spk_grad_status": (i32, [vp, vp]),
+        "mtts_spk_grad_match_workspace_bytes": (i64, [vp, i32, i32]),
+        "mtts_spk_grad_match": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+        "mtts_spk_grad_match_status": (i32, [vp, vp]),
+        "mtts_match_seeds_scratch_bytes": (i64, [i32, i32]),
+        "mtts_match_seeds": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
         "mtts_channel_layernorm_bwd": (i32, [vp, vp, i32, i32, i32, vp, vp, f32, i32, vp, vp, i32, vp, vp, vp, vp]),
         "mtts_attention_rope_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
         "mtts_gemm_terms": (i32, [vp]),
@@ -1016,11 +1032,7 @@ class HipModel:
             dur_in = durations.detach().to(device=dev, dtype=torch.int32).contiguous()
             if dur_in.shape != (B, Tx):
                 raise ValueError(f"durations must have shape ({B}, {Tx}), got {tuple(dur_in.shape)}")
-        if self._grad_weights is None or self._grad_generation != self.generation:
-            nb = size(self.lib.mtts_spk_grad_weights_bytes(self.ctx))
-            buf = torch.empty(nb, dtype=torch.uint8, device=self.device)
-            check(self.lib.mtts_spk_grad_upload_weights(self.ctx, buf.data_ptr(), nb))
-            self._grad_weights, self._grad_generation = buf, self.generation
+        self._grad_panels()
         ws = self._ws.get("spk_grad", self.lib.mtts_spk_grad_workspace_bytes(self.ctx, B, Tx, Tm), self.device)
         g_enc = torch.empty(B, Sd, dtype=torch.float32, device=dev)
         g_dur = torch.empty(B, Sd, dtype=torch.float32, device=dev)
@@ -1044,6 +1056,45 @@ class HipModel:
         """Wait for this stream's latest ``speaker_grad`` call and raise ``ValueError`` naming the first utterance the device refused
         (mtts_spk_grad_status)."""
         self._status("spk_grad", self.lib.mtts_spk_grad_status)
+
+    def _grad_panels(self) -> torch.Tensor:
+        """The backward panels of the speaker-row gradient, packed and uploaded on first use per weight generation."""
+        if self._grad_weights is None or self._grad_generation != self.generation:
+            nb = size(self.lib.mtts_spk_grad_weights_bytes(self.ctx))
+            buf = torch.empty(nb, dtype=torch.uint8, device=self.device)
+            check(self.lib.mtts_spk_grad_upload_weights(self.ctx, buf.data_ptr(), nb))
+            self._grad_weights, self._grad_generation = buf, self.generation
+        return self._grad_weights
+
+    def speaker_grad_match(self, x, x_lengths, e_enc, e_dur, mu_ref, logw_ref, beta_mu: float = 0.002, beta_logw: float = 0.004,
+                           check_lengths: bool = True):
+        """Style-encoder training's matching loss (mtts_spk_grad_match; reference style_encoder.py:119-143): the text encoder's
+        outputs under the PREDICTED rows ``e_enc``, ``e_dur`` [B, spk_emb_dim] against ``mu_ref`` [B, n_feats, Tx] and ``logw_ref``
+        [B, 1, Tx] or [B, Tx] (``text_encoder``'s outputs under the real rows), smooth-L1 with the reference's betas.  Returns a dict:
+        ``g_enc``, ``g_dur`` [B, spk_emb_dim] = gradients of the per-utterance sums ``ac_sum``, ``rh_sum`` [B].  ``check_lengths``:
+        wait for the stream and raise ``ValueError`` naming a refused utterance."""
+        B, Tx = x.shape
+        dev = x.device
+        x = x.detach().to(torch.int64).contiguous()
+        xl = x_lengths.detach().to(device=dev, dtype=torch.int64).contiguous()
+        e_enc, e_dur, mu_ref, logw_ref = self._f32(e_enc), self._f32(e_dur), self._f32(mu_ref), self._f32(logw_ref)
+        F, Sd = self.hp.n_feats, self.hp.spk_emb_dim
+        if xl.shape != (B,):
+            raise ValueError("x_lengths needs one entry per utterance")
+        if e_enc.shape != (B, Sd) or e_dur.shape != (B, Sd):
+            raise ValueError(f"the predicted rows must be [{B}, {Sd}]")
+        if mu_ref.shape != (B, F, Tx) or logw_ref.numel() != B * Tx:
+            raise ValueError(f"mu_ref must be [{B}, {F}, {Tx}] and logw_ref [{B}, {Tx}]")
+        panels = self._grad_panels()
+        ws = self._ws.get("spk_grad_match", self.lib.mtts_spk_grad_match_workspace_bytes(self.ctx, B, Tx), self.device)
+        out = {k: torch.empty(B, Sd, dtype=torch.float32, device=dev) for k in ("g_enc", "g_dur")}
+        out.update({k: torch.empty(B, dtype=torch.float32, device=dev) for k in ("ac_sum", "rh_sum")})
+        check(self.lib.mtts_spk_grad_match(self.ctx, ptr(x), ptr(xl), ptr(e_enc), ptr(e_dur), ptr(mu_ref), ptr(logw_ref), float(beta_mu),
+                                           float(beta_logw), B, Tx, ptr(out["g_enc"]), ptr(out["g_dur"]), ptr(out["ac_sum"]),
+                                           ptr(out["rh_sum"]), panels.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr()))
+        if check_lengths:
+            self._status("spk_grad_match", self.lib.mtts_spk_grad_match_status)
+        return out
 
     def fold_rows(self, y_max: int, align: int) -> int:
         """Rows per utterance the folded estimator needs for valid lengths up to y_max (mtts_fold_rows)."""

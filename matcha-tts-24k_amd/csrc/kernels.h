@@ -498,9 +498,10 @@ hipError_t launch_vocos_lengths_check(const int64_t* lengths, int B, int T, int*
 // mel [B, C, T] -> masked channels-last rows x [B*T][ld] (frames at t >= lengths[b] and channels >= C zero) + the prefix mask [B*T]
 hipError_t launch_style_prep(const float* mel, const int64_t* lengths, int B, int C, int T, float* x, int ld, float* mask, hipStream_t s);
 // masked mean over time of h [B*T][C], the two projections (pw [2E][C] = proj_enc rows then proj_dur rows, pb [2E]) and, with
-// group [B] (clip -> output row, others ignored), the mean over each group's clips: e_enc / e_dur [n_out][E]; group null: n_out == B
+// group [B] (clip -> output row, others ignored), the mean over each group's clips: e_enc / e_dur [n_out][E]; group null: n_out == B.
+// pooled_out [B][C] (optional): the masked means themselves, as the projections read them
 hipError_t launch_style_pool_proj(const float* h, const int64_t* lengths, int B, int T, int C, int E, const float* pw, const float* pb,
-                                  const int* group, int n_out, float* e_enc, float* e_dur, hipStream_t s);
+                                  const int* group, int n_out, float* e_enc, float* e_dur, hipStream_t s, float* pooled_out = nullptr);
 
 // ---- waveform finish (waveform.hip): per-row peak normalisation and trailing-silence trim lengths, see include/mtts.h
 struct WaveFinishArgs {

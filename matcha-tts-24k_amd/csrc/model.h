@@ -95,6 +95,11 @@ struct StyleW {
     std::vector<Panel> convs;      // Conv1d(k5, pad 2) of each layer
     Vec proj_w, proj_b;            // [2 E][hidden] = proj_enc rows then proj_dur rows, [2 E]
 };
+// Backward panels of the style encoder's data gradient (style_grad.hip): the transposed, tap-reversed convs of layers >= 1, packed on
+// demand into a buffer of their own (mtts_style::grad) as SpkGradW's are.
+struct StyleGradW {
+    std::vector<Panel> convT;      // [0] is empty: the first layer's input is the mel, which gets no gradient
+};
 
 // The library's run-time switches with their defaults.  read_switches() (model.hip) is the only reader of the environment:
 // mtts_create keeps its result in the context, which never looks at the environment again; the context-free test entries
@@ -193,4 +198,7 @@ struct mtts_vocos : mtts::Component {
 struct mtts_style : mtts::Component {
     int n_feats = 100, hidden = 256, layers = 4, emb = 96;
     mtts::StyleW w;
+    // parameter gradients (style_grad.hip): the backward panels' own image (native fp32 MFMA: gemm_terms 0) and their offsets
+    mtts::Component grad;
+    mtts::StyleGradW gradw;
 };

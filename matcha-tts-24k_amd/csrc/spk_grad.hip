@@ -13,6 +13,8 @@
 //   taped forward        the launch sequence of mtts_text_encoder_forward (encoder.hip), same launchers and arguments, with the
 //                        intermediates of every layer kept in buffers of their own
 //   seed_mu / seed_logw  the two Huber derivatives, token-of-frame rule and verdicts of score.hip
+//   seed_match_*         the seeds and sums of the style-training loss (mtts_spk_grad_match): smooth-L1 against the outputs under the
+//                        real rows, the same taped forward and the same walks back (SgCall)
 //   ln_bwd_kernel        channel LayerNorm backward (+ SiLU' on the way in, FiLM, row mask, ReLU gate on the way out)
 //   attn_bwd_q / _kv     RoPE attention backward: dq per query thread, dk / dv per key thread, inverse rotation at the store
 //   gate / colsum        SiLU' and ReLU gates, fixed-order sums over an utterance's tokens
@@ -30,6 +32,7 @@
 // key / query / frame / token order, a wave butterfly, four phases combined in order.  Partitions depend on absolute token indices
 // only, so an utterance's gradient does not depend on its batch or on the padded shapes.
 #include "host.h"
+#include "device_utils.h"
 
 #include <string>
 
@@ -237,6 +240,87 @@ __global__ void seed_logw_kernel(const float* __restrict__ logw, const int32_t* 
     float seed = 0.f;
     if (verdict[2 * b] == 0 && x < (int)x_len[b]) seed = sg_clamp(logw[row] - logf(2.0f + (float)dur[row]), delta);
     for (int c = threadIdx.x; c < Fd; c += blockDim.x) gd[(size_t)row * Fd + c] = seed * w_proj[c];
+}
+
+// ---------------------------------------------------------------------------------------------- matching-loss seeds (style training)
+// The reference's style-encoder loss (style_encoder.py:119-143): smooth-L1 between the frozen text encoder's outputs under predicted
+// rows and under the real rows (ref: constants), per term 0.5 d^2 / beta below beta and |d| - 0.5 beta from beta on, whose derivative
+// is clamp(d / beta, -1, 1).
+__device__ __forceinline__ float sg_smooth_l1(float d, float beta) {
+    const float ad = fabsf(d);
+    return ad < beta ? 0.5f * d * d / beta : ad - 0.5f * beta;
+}
+__device__ __forceinline__ float sg_smooth_l1_grad(float d, float beta) { return fminf(fmaxf(d / beta, -1.0f), 1.0f); }
+
+// verdict [B][2] = (1: x_length outside [1, Tx], 0) in score.hip's layout, which the walks read, and the status words
+// (1 + first refused utterance or 0, its length, Tx) for mtts_spk_grad_match_status.  One workgroup.
+__global__ __launch_bounds__(256) void match_verdict_kernel(const int64_t* __restrict__ x_len, int B, int Tx, int32_t* __restrict__ status,
+                                                            int32_t* __restrict__ verdict) {
+    for (int b = threadIdx.x; b < B; b += blockDim.x) {
+        verdict[2 * b] = (x_len[b] < 1 || x_len[b] > Tx) ? 1 : 0;
+        verdict[2 * b + 1] = 0;
+    }
+    const int i = first_refused_row(B, [&](int r) { return x_len[r] < 1 || x_len[r] > Tx; });
+    if (threadIdx.x == 0) {
+        status[0] = i < B ? i + 1 : 0;
+        status[1] = i < B ? sat32(x_len[i]) : 0;
+        status[2] = Tx;
+    }
+}
+// g[(b Tx + x) ldm + f] = clamp((mu_x - mu_ref)[b, f, x] / beta, +-1) for x < len_b (g zero-filled beforehand), and
+// part[b][f] = the smooth-L1 sum of feature f over the tokens.  Workgroup (f, b), as seed_mu_kernel; a thread adds its tokens x = tid,
+// tid + 256, ... in order, a wave butterfly, the four waves in order.
+__global__ __launch_bounds__(256) void seed_match_mu_kernel(const float* __restrict__ mu_x, const float* __restrict__ mu_ref,
+                                                            const int64_t* __restrict__ x_len, const int32_t* __restrict__ verdict, int F, int Tx,
+                                                            float beta, float* __restrict__ g, int ldm, float* __restrict__ part) {
+    __shared__ float wsum[4];
+    const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    if (verdict[2 * b] != 0) {                    // (uniform per workgroup)
+        if (tid == 0) part[(size_t)b * F + f] = 0.f;
+        return;
+    }
+    const int txb = (int)x_len[b];                // verdict 0: 1 <= x_len <= Tx
+    const float* mr = mu_x + ((size_t)b * F + f) * Tx;
+    const float* rr = mu_ref + ((size_t)b * F + f) * Tx;
+    float acc = 0.f;
+    for (int x = tid; x < txb; x += 256) {
+        const float d = mr[x] - rr[x];
+        acc += sg_smooth_l1(d, beta);
+        g[((size_t)b * Tx + x) * ldm + f] = sg_smooth_l1_grad(d, beta);
+    }
+    acc = sg_wave_sum(acc);
+    if ((tid & 63) == 0) wsum[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) part[(size_t)b * F + f] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+// as seed_logw_kernel with the matching seed: gd[row][c] = clamp((logw - logw_ref)[row] / beta, +-1) * w_proj[c] for x < len_b, else 0
+__global__ void seed_match_logw_kernel(const float* __restrict__ logw, const float* __restrict__ logw_ref, const int64_t* __restrict__ x_len,
+                                       const int32_t* __restrict__ verdict, const float* __restrict__ w_proj, int Tx, int Fd, float beta,
+                                       float* __restrict__ gd) {
+    const int row = blockIdx.x, b = row / Tx, x = row % Tx;
+    float seed = 0.f;
+    if (verdict[2 * b] == 0 && x < (int)x_len[b]) seed = sg_smooth_l1_grad(logw[row] - logw_ref[row], beta);
+    for (int c = threadIdx.x; c < Fd; c += blockDim.x) gd[(size_t)row * Fd + c] = seed * w_proj[c];
+}
+// One wave per utterance: ac_sum[b] = the features' partial sums (lane f, f + 64, ... in order, then a butterfly); rh_sum[b] = the
+// smooth-L1 sum of logw over the tokens (lane x, x + 64, ...).  Zero for a refused utterance.
+__global__ __launch_bounds__(64) void match_finish_kernel(const float* __restrict__ part, const float* __restrict__ logw,
+                                                          const float* __restrict__ logw_ref, const int64_t* __restrict__ x_len,
+                                                          const int32_t* __restrict__ verdict, int F, int Tx, float beta,
+                                                          float* __restrict__ ac_sum, float* __restrict__ rh_sum) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const bool ok = verdict[2 * b] == 0;
+    const int txb = ok ? (int)x_len[b] : 0;
+    float a = 0.f, r = 0.f;
+    if (ok)
+        for (int f = lane; f < F; f += 64) a += part[(size_t)b * F + f];
+    for (int x = lane; x < txb; x += 64) r += sg_smooth_l1(logw[(size_t)b * Tx + x] - logw_ref[(size_t)b * Tx + x], beta);
+    a = sg_wave_sum(a);
+    r = sg_wave_sum(r);
+    if (lane == 0) {
+        ac_sum[b] = a;
+        rh_sum[b] = r;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------- RoPE attention backward
@@ -598,42 +682,57 @@ int64_t mtts_spk_grad_tape_offset(mtts_ctx* c, int B, int Tx, int Tm, int which)
     return (int64_t)(which == 0 ? e.off_mu_x : which == 1 ? e.off_logw : e.off_xm);
 }
 
-int mtts_spk_grad(mtts_ctx* c, const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur,
-                  const float* d_y_fine, const int64_t* d_y_fine_lengths, const int32_t* d_durations_in, float delta_prior,
-                  float delta_dur, int B, int Tx, int Tm, float* d_g_enc, float* d_g_dur, float* d_prior_sum, float* d_dur_sum,
-                  int32_t* d_durations_out, void* d_grad_buf, void* d_ws, int64_t ws_bytes, void* stream) {
-    if (!c || !d_x || !d_x_lengths || !d_e_enc || !d_e_dur || !d_y_fine || !d_y_fine_lengths || !d_g_enc || !d_g_dur || !d_prior_sum ||
-        !d_dur_sum || !d_grad_buf || !d_ws) {
-        set_error("mtts_spk_grad: null argument");
-        return -1;
-    }
-    if (!sg_shape_ok("mtts_spk_grad", B, Tx, Tm) || !sg_layers_ok("mtts_spk_grad", c)) return -1;
-    if (!(delta_prior > 0.f) || !(delta_dur > 0.f)) { set_error("mtts_spk_grad: the Huber thresholds must be positive"); return -1; }
-    CTX_GUARD(c);
-    const mtts_config& g = c->cfg;
-    WS ws(d_ws, (size_t)ws_bytes);
-    SgBufs e;
-    plan_spk_grad(c, B, Tx, Tm, ws, e);
-    if (ws.overflow || ws_bytes < (int64_t)ws.off) { set_error("mtts_spk_grad: workspace too small (mtts_spk_grad_workspace_bytes)"); return -1; }
-    if (reinterpret_cast<uintptr_t>(d_ws) & 15) { set_error("mtts_spk_grad: workspace must be 16-byte aligned"); return -1; }
-    if (e.off_score != SG_SCORE_OFF) { set_error("mtts_spk_grad: the score workspace is not where mtts_spk_grad_status reads it"); return -1; }
-    if (!c->grad.packed || !c->grad.uploaded || c->grad.d_image != d_grad_buf) {
-        set_error("mtts_spk_grad: backward panels not uploaded (mtts_spk_grad_upload_weights into d_grad_buf)");
-        return -1;
-    }
-    RET_IF(check_ready(c));
-    const EncW& E = c->enc;
-    const SpkGradW& GW = c->gradw;
-    const Component* G = &c->grad;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int nch = g.enc_channels, Sd = g.spk_emb_dim, Hd = nch + Sd, F = g.dp_filter, M = B * Tx, nf = g.n_feats;
-    const int dh = Hd / g.enc_heads, d_rope = dh / 2, ldm = round_up(nf, 4), L = g.enc_layers;
-    if ((size_t)Tx * d_rope > (size_t)E.rope_cos.n) { set_error("Phonetic representation too long, exceeds RoPE cache size"); return -1; }
-    if (!attn_bwd_head_dim_ok(dh)) { set_error("mtts_spk_grad: the encoder's head dim must be a multiple of 8 (<= 64)"); return -1; }
-    RET_IF(begin_call(c, d_ws, s));
-    float* xm = e.xm;
+}  // extern "C"
 
-    // ================================================================ taped forward: encoder.hip's launches, buffers per layer
+// What the entries of this file share -- mtts_spk_grad (the fine-tuning losses) and mtts_spk_grad_match (the style-training losses):
+// the taped forward and the two walks back from seeded gradients, with the call's context, buffers and derived sizes.  The entries
+// differ in their seeds alone.
+namespace {
+struct SgCall {
+    mtts_ctx* c;
+    const SgBufs& e;
+    hipStream_t s;
+    int B, Tx;
+    const mtts_config& g;
+    const EncW& E;
+    const SpkGradW& GW;
+    const Component* G;
+    int nch, Sd, Hd, F, M, nf, dh, d_rope, ldm, L;
+    bool ffn_p16;
+    float* xm;
+    SgCall(mtts_ctx* ctx, const SgBufs& bufs, hipStream_t stream, int B_, int Tx_)
+        : c(ctx), e(bufs), s(stream), B(B_), Tx(Tx_), g(ctx->cfg), E(ctx->enc), GW(ctx->gradw), G(&ctx->grad) {
+        nch = g.enc_channels; Sd = g.spk_emb_dim; Hd = nch + Sd; F = g.dp_filter; M = B * Tx; nf = g.n_feats;
+        dh = Hd / g.enc_heads; d_rope = dh / 2; ldm = round_up(nf, 4); L = g.enc_layers;
+        ffn_p16 = c->sw.p16_on && c->gemm_terms == 2 && (g.enc_filter % 32) == 0;
+        xm = e.xm;
+    }
+    // what every entry checks once its workspace is planned (`who` names it in the error texts)
+    int ready(const char* who, const void* d_grad_buf) const {
+        if (!c->grad.packed || !c->grad.uploaded || c->grad.d_image != d_grad_buf) {
+            set_error(std::string(who) + ": backward panels not uploaded (mtts_spk_grad_upload_weights into d_grad_buf)");
+            return -1;
+        }
+        RET_IF(check_ready(c));
+        if ((size_t)Tx * d_rope > (size_t)E.rope_cos.n) { set_error("Phonetic representation too long, exceeds RoPE cache size"); return -1; }
+        if (!attn_bwd_head_dim_ok(dh)) { set_error(std::string(who) + ": the encoder's head dim must be a multiple of 8 (<= 64)"); return -1; }
+        return 0;
+    }
+    int tgemm(const Panel& p, const float* a0, int lda, int c0, int ntaps, const float* res, int ldr, const float* out_mask, float* out,
+              int ldc, int rowsB, int rowsT) const {
+        GemmArgs a;
+        panel_args(G, p, a); rows_plain(a, rowsB, rowsT);
+        if (ntaps > 1) taps_centered(a, ntaps);
+        a.a0 = a0; a.lda0 = lda; a.c0 = c0; a.res = res; a.ldr = ldr; a.out_mask = out_mask; a.out = out; a.ldc = ldc;
+        return run_gemm(c, a, s);
+    }
+    int forward(const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur) const;
+    int walk_prior(const int64_t* d_x_lengths, const int32_t* verdict, float* d_g_enc) const;
+    int walk_dur(const int64_t* d_x_lengths, const int32_t* verdict, float* d_g_dur) const;
+};
+
+// ================================================================ taped forward: encoder.hip's launches, buffers per layer
+int SgCall::forward(const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur) const {
     LAUNCH(c, 2, 0, s, launch_seq_mask(d_x_lengths, B, Tx, xm, s));
     LAUNCH(c, 2, 0, s, launch_embedding(d_x, W(c, E.emb.off), M, nch, sqrtf((float)nch), xm, e.X0, nch, s));
     const float* cur = e.X0;
@@ -656,7 +755,6 @@ int mtts_spk_grad(mtts_ctx* c, const int64_t* d_x, const int64_t* d_x_lengths, c
         RET_IF(run_gemm(c, a, s));
     }
     LAUNCH(c, 2, 0, s, launch_bcast_rows(d_e_enc, B, Tx, Sd, xm, e.Hin[0], Hd, nch, s));
-    const bool ffn_p16 = c->sw.p16_on && c->gemm_terms == 2 && (g.enc_filter % 32) == 0;
     for (int l = 0; l < L; ++l) {
         GemmArgs q;
         panel_args(c, E.qkv[l], q); rows_plain(q, B, Tx);
@@ -733,35 +831,11 @@ int mtts_spk_grad(mtts_ctx* c, const int64_t* d_x, const int64_t* d_x_lengths, c
         p.a0 = dcur; p.lda0 = dc; p.c0 = dc; p.a_mask = xm; p.out_mask = xm; p.out = e.logw; p.ldc = 1;
         RET_IF(run_gemm(c, p, s));
     }
+    return 0;
+}
 
-    // ================================================================ alignment (constant of the step) and the two sums
-    const int32_t* dur = d_durations_in;
-    if (!dur) {
-        int32_t* dst = d_durations_out ? d_durations_out : e.dur;
-        RET_IF(mtts_mas(nullptr, e.mu_x, d_y_fine, d_x_lengths, d_y_fine_lengths, B, nf, Tx, Tm, dst, nullptr, nullptr, e.mas,
-                        (int64_t)e.mas_bytes, stream));
-        dur = dst;
-    } else if (d_durations_out && d_durations_out != d_durations_in) {
-        hipLaunchKernelGGL(copy_i32_kernel, dim3((M + 255) / 256), dim3(256), 0, s, d_durations_in, d_durations_out, (size_t)M);
-        HIP_OK(hipGetLastError());
-    }
-    RET_IF(mtts_score_prior_dur(e.mu_x, e.logw, dur, d_y_fine, d_x_lengths, d_y_fine_lengths, B, nf, Tx, Tm, delta_prior, delta_dur,
-                                d_prior_sum, d_dur_sum, nullptr, nullptr, e.score, (int64_t)e.score_bytes, stream));
-    const int32_t* verdict = reinterpret_cast<const int32_t*>(static_cast<char*>(e.score) + SCORE_HEADER_BYTES);
-
-    // ================================================================ backward: prior sum -> e_enc
-    auto tgemm = [&](const Panel& p, const float* a0, int lda, int c0, int ntaps, const float* res, int ldr, const float* out_mask, float* out,
-                     int ldc, int rowsB, int rowsT) {
-        GemmArgs a;
-        panel_args(G, p, a); rows_plain(a, rowsB, rowsT);
-        if (ntaps > 1) taps_centered(a, ntaps);
-        a.a0 = a0; a.lda0 = lda; a.c0 = c0; a.res = res; a.ldr = ldr; a.out_mask = out_mask; a.out = out; a.ldc = ldc;
-        return run_gemm(c, a, s);
-    };
-    LAUNCH(c, 2, 0, s, launch_fill_cols(e.GMU, M, ldm, 0, ldm, 0.f, s));
-    hipLaunchKernelGGL(seed_mu_kernel, dim3(nf, B), dim3(256), 0, s, e.mu_x, d_y_fine, dur, d_x_lengths, verdict, nf, Tx, Tm, delta_prior,
-                       e.GMU, ldm);
-    HIP_OK(hipGetLastError());
+// ================================================================ backward: d sum / d mu_x rows (e.GMU, seeded) -> e_enc
+int SgCall::walk_prior(const int64_t* d_x_lengths, const int32_t* verdict, float* d_g_enc) const {
     RET_IF(tgemm(GW.pm2T, e.GMU, ldm, ldm, 1, nullptr, 0, nullptr, e.GPM, nch, B, Tx));
     LAUNCH(c, 2, 0, s, launch_gate(e.GPM, nch, M, nch, 0, e.PMpre, nch, nullptr, 0, nullptr, s));
     RET_IF(tgemm(GW.pm0T, e.GPM, nch, nch, 1, nullptr, 0, nullptr, e.GA, Hd, B, Tx));
@@ -786,11 +860,11 @@ int mtts_spk_grad(mtts_ctx* c, const int64_t* d_x, const int64_t* d_x_lengths, c
         RET_IF(tgemm(GW.qkvT[l], e.GQKV, 3 * Hd, 3 * Hd, 1, e.GB, Hd, nullptr, e.GA, Hd, B, Tx));
     }
     LAUNCH(c, 2, 0, s, launch_colsum(e.GA, Hd, nch, Sd, B, Tx, d_x_lengths, verdict, d_g_enc, Sd, 0, 0, s));
+    return 0;
+}
 
-    // ================================================================ backward: duration sum -> e_dur
-    hipLaunchKernelGGL(seed_logw_kernel, dim3(M), dim3(64), 0, s, e.logw, dur, d_x_lengths, verdict, G->d_image + GW.dp_proj.off, Tx, F,
-                       delta_dur, e.GDA);
-    HIP_OK(hipGetLastError());
+// ================================================================ backward: d sum / d (duration predictor's last rows) (e.GDA, seeded) -> e_dur
+int SgCall::walk_dur(const int64_t* d_x_lengths, const int32_t* verdict, float* d_g_dur) const {
     bool first = true;
     for (int i = g.dp_layers - 1; i >= 0; --i) {
         LAUNCH(c, 2, 0, s, launch_colsum(e.GDA, F, 0, F, B, Tx, d_x_lengths, verdict, e.DFILM, 2 * F, F, first ? 0 : 1, s));
@@ -803,6 +877,129 @@ int mtts_spk_grad(mtts_ctx* c, const int64_t* d_x, const int64_t* d_x_lengths, c
         if (i >= 1) RET_IF(tgemm(GW.dp_convT[i], e.GDB, F, F, g.dp_kernel, nullptr, 0, xm, e.GDA, F, B, Tx));
     }
     RET_IF(tgemm(GW.filmT, e.DFILM, 2 * F, 2 * F, 1, nullptr, 0, nullptr, d_g_dur, Sd, B, 1));
+    return 0;
+}
+}  // namespace
+
+extern "C" {
+
+int mtts_spk_grad(mtts_ctx* c, const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur,
+                  const float* d_y_fine, const int64_t* d_y_fine_lengths, const int32_t* d_durations_in, float delta_prior,
+                  float delta_dur, int B, int Tx, int Tm, float* d_g_enc, float* d_g_dur, float* d_prior_sum, float* d_dur_sum,
+                  int32_t* d_durations_out, void* d_grad_buf, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!c || !d_x || !d_x_lengths || !d_e_enc || !d_e_dur || !d_y_fine || !d_y_fine_lengths || !d_g_enc || !d_g_dur || !d_prior_sum ||
+        !d_dur_sum || !d_grad_buf || !d_ws) {
+        set_error("mtts_spk_grad: null argument");
+        return -1;
+    }
+    if (!sg_shape_ok("mtts_spk_grad", B, Tx, Tm) || !sg_layers_ok("mtts_spk_grad", c)) return -1;
+    if (!(delta_prior > 0.f) || !(delta_dur > 0.f)) { set_error("mtts_spk_grad: the Huber thresholds must be positive"); return -1; }
+    CTX_GUARD(c);
+    WS ws(d_ws, (size_t)ws_bytes);
+    SgBufs e;
+    plan_spk_grad(c, B, Tx, Tm, ws, e);
+    if (ws.overflow || ws_bytes < (int64_t)ws.off) { set_error("mtts_spk_grad: workspace too small (mtts_spk_grad_workspace_bytes)"); return -1; }
+    if (reinterpret_cast<uintptr_t>(d_ws) & 15) { set_error("mtts_spk_grad: workspace must be 16-byte aligned"); return -1; }
+    if (e.off_score != SG_SCORE_OFF) { set_error("mtts_spk_grad: the score workspace is not where mtts_spk_grad_status reads it"); return -1; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const SgCall k(c, e, s, B, Tx);
+    RET_IF(k.ready("mtts_spk_grad", d_grad_buf));
+    RET_IF(begin_call(c, d_ws, s));
+    RET_IF(k.forward(d_x, d_x_lengths, d_e_enc, d_e_dur));
+
+    // ================================================================ alignment (constant of the step) and the two sums
+    const int32_t* dur = d_durations_in;
+    if (!dur) {
+        int32_t* dst = d_durations_out ? d_durations_out : e.dur;
+        RET_IF(mtts_mas(nullptr, e.mu_x, d_y_fine, d_x_lengths, d_y_fine_lengths, B, k.nf, Tx, Tm, dst, nullptr, nullptr, e.mas,
+                        (int64_t)e.mas_bytes, stream));
+        dur = dst;
+    } else if (d_durations_out && d_durations_out != d_durations_in) {
+        hipLaunchKernelGGL(copy_i32_kernel, dim3((k.M + 255) / 256), dim3(256), 0, s, d_durations_in, d_durations_out, (size_t)k.M);
+        HIP_OK(hipGetLastError());
+    }
+    RET_IF(mtts_score_prior_dur(e.mu_x, e.logw, dur, d_y_fine, d_x_lengths, d_y_fine_lengths, B, k.nf, Tx, Tm, delta_prior, delta_dur,
+                                d_prior_sum, d_dur_sum, nullptr, nullptr, e.score, (int64_t)e.score_bytes, stream));
+    const int32_t* verdict = reinterpret_cast<const int32_t*>(static_cast<char*>(e.score) + SCORE_HEADER_BYTES);
+
+    // ================================================================ the two seeds, each followed by its walk back
+    LAUNCH(c, 2, 0, s, launch_fill_cols(e.GMU, k.M, k.ldm, 0, k.ldm, 0.f, s));
+    hipLaunchKernelGGL(seed_mu_kernel, dim3(k.nf, B), dim3(256), 0, s, e.mu_x, d_y_fine, dur, d_x_lengths, verdict, k.nf, Tx, Tm, delta_prior,
+                       e.GMU, k.ldm);
+    HIP_OK(hipGetLastError());
+    RET_IF(k.walk_prior(d_x_lengths, verdict, d_g_enc));
+    hipLaunchKernelGGL(seed_logw_kernel, dim3(k.M), dim3(64), 0, s, e.logw, dur, d_x_lengths, verdict, k.G->d_image + k.GW.dp_proj.off, Tx, k.F,
+                       delta_dur, e.GDA);
+    HIP_OK(hipGetLastError());
+    RET_IF(k.walk_dur(d_x_lengths, verdict, d_g_dur));
+    return 0;
+}
+
+// Style-encoder training (reference matcha/models/style_encoder.py:119-143): the frozen text encoder's outputs under PREDICTED rows
+// matched against its outputs under the real rows (d_mu_ref, d_logw_ref: constants) with smooth-L1.  The same taped forward and the same
+// two walks as mtts_spk_grad; the seeds are clamp((out - ref) / beta, -1, 1) on the tokens x < len_b.
+int64_t mtts_spk_grad_match_workspace_bytes(mtts_ctx* c, int B, int Tx) {
+    if (!c) { set_error("mtts_spk_grad_match_workspace_bytes: null context"); return -1; }
+    if (!sg_shape_ok("mtts_spk_grad_match_workspace_bytes", B, Tx, Tx) || !sg_layers_ok("mtts_spk_grad_match_workspace_bytes", c)) return -1;
+    WS ws(nullptr, 0);
+    SgBufs e;
+    plan_spk_grad(c, B, Tx, Tx, ws, e);
+    (void)ws.f((size_t)B * c->cfg.n_feats);
+    return (int64_t)ws.off + 256;
+}
+
+int mtts_spk_grad_match(mtts_ctx* c, const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur,
+                        const float* d_mu_ref, const float* d_logw_ref, float beta_mu, float beta_logw, int B, int Tx, float* d_g_enc,
+                        float* d_g_dur, float* d_ac_sum, float* d_rh_sum, void* d_grad_buf, void* d_ws, int64_t ws_bytes, void* stream) {
+    if (!c || !d_x || !d_x_lengths || !d_e_enc || !d_e_dur || !d_mu_ref || !d_logw_ref || !d_g_enc || !d_g_dur || !d_ac_sum || !d_rh_sum ||
+        !d_grad_buf || !d_ws) {
+        set_error("mtts_spk_grad_match: null argument");
+        return -1;
+    }
+    if (!sg_shape_ok("mtts_spk_grad_match", B, Tx, Tx) || !sg_layers_ok("mtts_spk_grad_match", c)) return -1;
+    if (!(beta_mu > 0.f) || !(beta_logw > 0.f)) { set_error("mtts_spk_grad_match: the smooth-L1 betas must be positive"); return -1; }
+    CTX_GUARD(c);
+    WS ws(d_ws, (size_t)ws_bytes);
+    SgBufs e;
+    plan_spk_grad(c, B, Tx, Tx, ws, e);
+    float* part = ws.f((size_t)B * c->cfg.n_feats);
+    if (ws.overflow || ws_bytes < (int64_t)ws.off) { set_error("mtts_spk_grad_match: workspace too small (mtts_spk_grad_match_workspace_bytes)"); return -1; }
+    if (reinterpret_cast<uintptr_t>(d_ws) & 15) { set_error("mtts_spk_grad_match: workspace must be 16-byte aligned"); return -1; }
+    if (e.off_score != SG_SCORE_OFF) { set_error("mtts_spk_grad_match: the status words are not where mtts_spk_grad_match_status reads them"); return -1; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const SgCall k(c, e, s, B, Tx);
+    RET_IF(k.ready("mtts_spk_grad_match", d_grad_buf));
+    RET_IF(begin_call(c, d_ws, s));
+    int32_t* status = static_cast<int32_t*>(e.score);
+    int32_t* verdict = reinterpret_cast<int32_t*>(static_cast<char*>(e.score) + SCORE_HEADER_BYTES);
+    hipLaunchKernelGGL(match_verdict_kernel, dim3(1), dim3(256), 0, s, d_x_lengths, B, Tx, status, verdict);
+    HIP_OK(hipGetLastError());
+    RET_IF(k.forward(d_x, d_x_lengths, d_e_enc, d_e_dur));
+    LAUNCH(c, 2, 0, s, launch_fill_cols(e.GMU, k.M, k.ldm, 0, k.ldm, 0.f, s));
+    hipLaunchKernelGGL(seed_match_mu_kernel, dim3(k.nf, B), dim3(256), 0, s, e.mu_x, d_mu_ref, d_x_lengths, verdict, k.nf, Tx, beta_mu, e.GMU,
+                       k.ldm, part);
+    HIP_OK(hipGetLastError());
+    RET_IF(k.walk_prior(d_x_lengths, verdict, d_g_enc));
+    hipLaunchKernelGGL(seed_match_logw_kernel, dim3(k.M), dim3(64), 0, s, e.logw, d_logw_ref, d_x_lengths, verdict,
+                       k.G->d_image + k.GW.dp_proj.off, Tx, k.F, beta_logw, e.GDA);
+    HIP_OK(hipGetLastError());
+    RET_IF(k.walk_dur(d_x_lengths, verdict, d_g_dur));
+    hipLaunchKernelGGL(match_finish_kernel, dim3(B), dim3(64), 0, s, part, e.logw, d_logw_ref, d_x_lengths, verdict, k.nf, Tx, beta_logw, d_ac_sum,
+                       d_rh_sum);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// The verdict of mtts_spk_grad_match's device-side check of the lengths.  Waits for the stream.
+int mtts_spk_grad_match_status(const void* d_ws, void* stream) {
+    if (!d_ws) { set_error("mtts_spk_grad_match_status: null workspace"); return -1; }
+    int st[4];
+    if (read_status("mtts_spk_grad_match_status", static_cast<const char*>(d_ws) + SG_SCORE_OFF, stream, st)) return -1;
+    if (st[0] != 0) {
+        set_error("mtts_spk_grad_match: utterance " + std::to_string(st[0] - 1) + " has x_length = " + std::to_string(st[1]) +
+                  " (need 1 <= x_length <= Tx = " + std::to_string(st[2]) + ")");
+        return -1;
+    }
     return 0;
 }
 
@@ -840,6 +1037,37 @@ int mtts_channel_layernorm_bwd(const float* d_x, const float* d_dy, int B, int T
         HIP_OK(launch_colsum(static_cast<const float*>(d_scratch), C, 0, C, B, T, nullptr, nullptr, d_dfilm, 2 * C, 0, 0, s));
         HIP_OK(launch_colsum(d_dy, C, 0, C, B, T, nullptr, nullptr, d_dfilm, 2 * C, C, 0, s));
     }
+    return 0;
+}
+
+// The seed and sum kernels of mtts_spk_grad_match on given buffers: d_mu / d_mu_ref [B][F][Tx], d_logw / d_logw_ref [B][Tx], d_lengths
+// int64 [B], d_w_proj [Fd] -> d_seed_mu [B Tx][F] (zero beyond an utterance), d_seed_logw [B Tx][Fd], d_ac_sum / d_rh_sum [B].
+// d_scratch: mtts_match_seeds_scratch_bytes.
+int64_t mtts_match_seeds_scratch_bytes(int B, int F) {
+    if (B < 1 || F < 1) { set_error("mtts_match_seeds_scratch_bytes: bad shape"); return -1; }
+    return (int64_t)(SCORE_HEADER_BYTES + ((size_t)B * 2 * sizeof(int32_t) + 255) / 256 * 256 + (size_t)B * F * sizeof(float));
+}
+int mtts_match_seeds(const float* d_mu, const float* d_mu_ref, const float* d_logw, const float* d_logw_ref, const int64_t* d_lengths,
+                     const float* d_w_proj, int B, int F, int Tx, int Fd, float beta_mu, float beta_logw, float* d_seed_mu, float* d_seed_logw,
+                     float* d_ac_sum, float* d_rh_sum, void* d_scratch, void* stream) {
+    if (!d_mu || !d_mu_ref || !d_logw || !d_logw_ref || !d_lengths || !d_w_proj || !d_seed_mu || !d_seed_logw || !d_ac_sum || !d_rh_sum || !d_scratch) {
+        set_error("mtts_match_seeds: null argument");
+        return -1;
+    }
+    if (B < 1 || B > 65535 || F < 1 || F > 65535 || Fd < 1 || Tx < 1 || Tx > SG_MAX_TX) { set_error("mtts_match_seeds: need B, F, Fd >= 1 and 1 <= Tx <= 1024"); return -1; }
+    if (!(beta_mu > 0.f) || !(beta_logw > 0.f)) { set_error("mtts_match_seeds: the smooth-L1 betas must be positive"); return -1; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* sc = static_cast<char*>(d_scratch);
+    int32_t* status = reinterpret_cast<int32_t*>(sc);
+    int32_t* verdict = reinterpret_cast<int32_t*>(sc + SCORE_HEADER_BYTES);
+    float* part = reinterpret_cast<float*>(sc + SCORE_HEADER_BYTES + ((size_t)B * 2 * sizeof(int32_t) + 255) / 256 * 256);
+    hipLaunchKernelGGL(match_verdict_kernel, dim3(1), dim3(256), 0, s, d_lengths, B, Tx, status, verdict);
+    HIP_OK(launch_fill_cols(d_seed_mu, B * Tx, F, 0, F, 0.f, s));
+    hipLaunchKernelGGL(seed_match_mu_kernel, dim3(F, B), dim3(256), 0, s, d_mu, d_mu_ref, d_lengths, verdict, F, Tx, beta_mu, d_seed_mu, F, part);
+    hipLaunchKernelGGL(seed_match_logw_kernel, dim3(B * Tx), dim3(64), 0, s, d_logw, d_logw_ref, d_lengths, verdict, d_w_proj, Tx, Fd, beta_logw,
+                       d_seed_logw);
+    hipLaunchKernelGGL(match_finish_kernel, dim3(B), dim3(64), 0, s, part, d_logw, d_logw_ref, d_lengths, verdict, F, Tx, beta_logw, d_ac_sum, d_rh_sum);
+    HIP_OK(hipGetLastError());
     return 0;
 }
 

@@ -49,7 +49,7 @@ hipError_t launch_style_prep(const float* mel, const int64_t* lengths, int B, in
 __global__ __launch_bounds__(1024) void style_pool_proj_kernel(const float* __restrict__ h, const int64_t* __restrict__ lengths, int B, int T,
                                                                int C, int E, const float* __restrict__ pw, const float* __restrict__ pb,
                                                                const int* __restrict__ group, float* __restrict__ e_enc,
-                                                               float* __restrict__ e_dur) {
+                                                               float* __restrict__ e_dur, float* __restrict__ pooled_out) {
     extern __shared__ float sm[];          // part [4][C] | pooled [C] | acc [2E]
     float* part = sm;
     float* pooled = sm + 4 * C;
@@ -71,6 +71,8 @@ __global__ __launch_bounds__(1024) void style_pool_proj_kernel(const float* __re
         const float inv_n = 1.0f / (float)(n > 1 ? n : 1);
         for (int c = tid; c < C; c += 1024) pooled[c] = (((part[c] + part[C + c]) + part[2 * C + c]) + part[3 * C + c]) * inv_n;
         __syncthreads();
+        if (pooled_out)                             // the taped forward (style_grad.hip) keeps the rows the projections read
+            for (int c = tid; c < C; c += 1024) pooled_out[(size_t)b * C + c] = pooled[c];
         for (int o = wave; o < 2 * E; o += 16) {
             float s = 0.f;
             for (int k = lane; k < C; k += 64) s += pooled[k] * pw[(size_t)o * C + k];
@@ -89,12 +91,12 @@ __global__ __launch_bounds__(1024) void style_pool_proj_kernel(const float* __re
     }
 }
 hipError_t launch_style_pool_proj(const float* h, const int64_t* lengths, int B, int T, int C, int E, const float* pw, const float* pb,
-                                  const int* group, int n_out, float* e_enc, float* e_dur, hipStream_t s) {
+                                  const int* group, int n_out, float* e_enc, float* e_dur, hipStream_t s, float* pooled_out) {
     if (!h || !lengths || !pw || !pb || !e_enc || !e_dur || B <= 0 || T <= 0 || C <= 0 || E <= 0 || n_out <= 0) return hipErrorInvalidValue;
     if (!group && n_out != B) return hipErrorInvalidValue;
     const size_t lds = (size_t)(5 * C + 2 * E) * sizeof(float);
     if (lds > 48 * 1024) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(style_pool_proj_kernel, dim3(n_out), dim3(1024), lds, s, h, lengths, B, T, C, E, pw, pb, group, e_enc, e_dur);
+    hipLaunchKernelGGL(style_pool_proj_kernel, dim3(n_out), dim3(1024), lds, s, h, lengths, B, T, C, E, pw, pb, group, e_enc, e_dur, pooled_out);
     return hipGetLastError();
 }
 
@@ -161,6 +163,8 @@ mtts_style* mtts_style_create(int n_feats, int hidden, int n_layers, int spk_emb
 void mtts_style_destroy(mtts_style* v) { delete v; }
 int mtts_style_set_tensor(mtts_style* v, const char* key, const float* h, int64_t numel) {
     if (!v) { set_error("null context"); return -1; }
+    v->grad.packed = false;             // the backward panels (style_grad.hip) are copies of these tensors
+    v->grad.uploaded = false;
     return set_tensor(v, key, h, numel);
 }
 int64_t mtts_style_weights_bytes(mtts_style* v) { return weights_bytes(v, style_pack); }

@@ -409,6 +409,45 @@ class MatchaTTSInfer(nn.Module):
         return rt.guarded(self.range_policy, run, lambda _: (bool(rt.ready().call_flags("spk_grad")[0].item()), False))
 
     @torch.inference_mode()
+    def style_match_grad(self, x, x_lengths, rows_pred, speaker=0, voice_mix=None, speaker_embeddings=None, beta_mu=0.002, beta_logw=0.004):
+        """The loss of the reference's style-encoder training and its gradient with respect to the predicted rows, on the device
+        (``HipModel.speaker_grad_match``; include/mtts.h mtts_spk_grad_match; reference matcha/models/style_encoder.py:119-149): the
+        frozen text encoder's ``mu_x`` and ``logw`` under ``rows_pred = (e_enc, e_dur)`` [B, spk_emb_dim] against those under the real
+        rows of ``speaker`` (speaker arguments as for ``synthesise``), smooth-L1 with the reference's betas.  The reference freezes
+        Matcha in ``eval()`` for this training: this is exactly its gradient.
+
+        Returns ``g_enc``, ``g_dur`` [B, spk_emb_dim] -- gradients of the per-utterance sums ``ac_sum``, ``rh_sum`` [B]; the
+        reference's batch losses ``acoustic_loss``, ``rhythm_loss`` (the batch sums over ``x_lengths.sum()``: tokens, not tokens x
+        channels, for both) whose gradients are ``g_enc / x_lengths.sum()`` and ``g_dur / x_lengths.sum()`` row by row; and the logged
+        ``emb_dist_enc``, ``emb_dist_dur`` (batch mean of the root-mean-square difference between predicted and real rows).  One synchronisation per call
+        (under the guard of ``Runtime.guarded``); ``ValueError`` names a refused utterance."""
+        rt = self._rt
+        dev = x.device
+        hp = self.hp
+
+        def run():
+            hip = rt.ready()
+            B = x.shape[0]
+            rows = speaker_embeddings
+            if rows is not None:
+                rows = tuple(e.to(dev).reshape(-1, hp.spk_emb_dim) for e in rows)
+            e_enc, e_dur = self._voice_rows(B, dev, speaker, voice_mix, rows)
+            e_enc, e_dur = e_enc.expand(B, -1).contiguous(), e_dur.expand(B, -1).contiguous()
+            p_enc, p_dur = (torch.as_tensor(r).to(device=dev, dtype=torch.float32).reshape(B, hp.spk_emb_dim) for r in rows_pred)
+            x_len = x_lengths.to(device=dev, dtype=torch.long)
+            mu_ref, logw_ref, _ = hip.text_encoder(x, x_len, e_enc, e_dur)
+            out = hip.speaker_grad_match(x, x_len, p_enc, p_dur, mu_ref, logw_ref, beta_mu, beta_logw)
+            tokens = x_len.to(torch.float32).sum()
+            out["acoustic_loss"] = out["ac_sum"].sum() / tokens
+            out["rhythm_loss"] = out["rh_sum"].sum() / tokens
+            out["emb_dist_enc"] = (p_enc - e_enc).pow(2).mean(dim=1).sqrt().mean()
+            out["emb_dist_dur"] = (p_dur - e_dur).pow(2).mean(dim=1).sqrt().mean()
+            out["mu_ref"], out["logw_ref"] = mu_ref, logw_ref
+            return out
+        # (the stream is already drained: no second wait)
+        return rt.guarded(self.range_policy, run, lambda _: (bool(rt.ready().call_flags("spk_grad_match")[0].item()), False))
+
+    @torch.inference_mode()
     def finetune_speaker(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0,
                          speaker_embeddings=None, steps=100, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, batch_size=None, shuffle_seed=0,
                          silence=None, sample_rate=24000):
