@@ -916,6 +916,67 @@ int mtts_mel_stats(const float* d_mel, int F, int T, const int64_t* d_lengths, i
                    int32_t* d_flags, void* d_ws, int64_t ws_bytes, void* stream);
 int mtts_mel_stats_status(const void* d_ws, void* stream);
 
+/* ---------------------------------------------------------------- pitch: F0 contours and per-clip statistics */
+
+/* How high a voice speaks and whether it rises at the end: the fundamental frequency of every frame of a ragged batch by YIN
+ * (de Cheveigne & Kawahara, JASA 111 (4), 2002), stated so that it cuts into blocks, and exact order statistics of a contour.
+ * Rows as for mtts_silence_measure: d_audio fp32 [B][ld] with ld % 4 == 0 and 16-byte aligned, d_lengths device int64 [B], judged
+ * on the device; a length outside [0, ld] gives d_frames[b] = -1 for that row (its columns hold the fill values) and leaves the
+ * other rows alone; stream-ordered, no allocation, one workspace of mtts_pitch_workspace_bytes; what the host can see (null
+ * pointers, B < 1, a bad ld, parameters outside the ranges below, a small ld_frames, a small workspace) returns -1;
+ * mtts_pitch_status(d_ws, stream) -- the only entry here that waits -- reports the first refused row of the latest call on that
+ * workspace through mtts_last_error.  A row's numbers do not depend on its batch or its place in it.
+ *
+ * Parameters.  sample_rate fs in [8000, 48000]; hop H in [8, 512] samples; fmin, fmax in Hz; threshold thr in (0, 1), compared in
+ * fp32 as (float)threshold.  Window W = 8 H; largest lag tmax = ceil(fs / fmin), smallest lag tmin = floor(fs / fmax), both from the
+ * double quotient; refused unless 2 <= tmin and tmin + 2 <= tmax <= MTTS_PITCH_MAX_LAG.  mtts_pitch_plan reports (W, tmin, tmax) or
+ * refuses the same way.
+ *
+ * Frames.  A clip of L samples has n = 0 frames when L < W + tmax, else n = (L - W - tmax) / H + 1.  Frame k reads samples
+ * [k H, k H + W + tmax) and nothing else: no padding, no read outside [0, L).  Its nominal time is (k H + (W + tmax) / 2) / fs.
+ * ld_frames must be at least max(1, frames of a clip of ld samples).
+ *
+ * Difference function, all in fp32 without fused multiply-adds.  Block b of a clip is samples [b H, b H + H); its sums are
+ *     s_b(tau) = sum_{j < H} (x[b H + j] - x[b H + j + tau])^2,   tau = 1 .. tmax:
+ *   start from 0.0f and, for j = 0, 1, .. H - 1 in that order, d = x[b H + j] - x[b H + j + tau]; s = s + d * d (three roundings).
+ *   A frame's sums are its eight blocks' in ascending order,
+ *     d_k(tau) = ((((((s_k + s_k+1) + s_k+2) + s_k+3) + s_k+4) + s_k+5) + s_k+6) + s_k+7.
+ *   Each block sum is computed once (mtts_pitch_tile() = 8 blocks per workgroup, which stages its samples once) and used by the
+ *   eight frames that hold the block; the order is a function of (b, tau, j) only -- not of the batch, the grid or the tile.
+ * Cumulative-mean normalisation.  c(tau) = sum_{u <= tau} d(u) in this shape: lag tau belongs to group g = (tau - 1) / 16, place
+ *   i = (tau - 1) % 16 (64 groups; d(u) = 0.0f beyond tmax).  Inside a group r_g(i) = (..((0.0f + d(16 g + 1)) + d(16 g + 2)).. +
+ *   d(16 g + i + 1)), and t_g = r_g(15).  The inclusive scan of t over the groups is six steps v[g] = v[g] + v[g - o] for every
+ *   g >= o at once, o = 1, 2, 4, 8, 16, 32; P_g = v[g - 1] after them, P_0 = 0.0f.  c(tau) = P_g + r_g(i).
+ *   d'(tau) = (d(tau) * (float)tau) / c(tau) when c(tau) > 0, else 1.0f (the division correctly rounded).
+ * Walk.  The first tau in [tmin, tmax) with d'(tau) < thr; from there one step to the right while tau + 1 < tmax and
+ *   d'(tau + 1) < d'(tau).  Without such a tau: the lowest-index minimum of d' over [tmin, tmax).  tau* is the lag reached.
+ * Outputs per frame.  aperiodicity = d'(tau*).  The frame is voiced when d'(tau*) < thr; f0 = (float)fs / ((float)tau* + delta)
+ *   when voiced, else 0.  With a = d'(tau* - 1), b = d'(tau*), c = d'(tau* + 1): delta = (0.5f * (a - c)) / ((a - b) + (c - b)),
+ *   the offset of the three-point parabola's vertex (0.5 (a - c) / (a - 2 b + c)), taken only when tmin < tau* < tmax - 1 and the
+ *   denominator as computed is > 0; otherwise delta = 0.  A frame that reads a NaN or an Inf sample reports f0 = 0 and aperiodicity =
+ *   NaN -- exactly the frames k with such a sample in [k H, k H + W + tmax); the other frames are unaffected.  Columns at or beyond n
+ *   (up to ld_frames) hold f0 = 0, aperiodicity = 1.  Two launches: block sums gridded over (tile of blocks, clip), then (eight
+ *   frames, clip).
+ *
+ * mtts_pitch_stats: d_f0 [B][ld_frames] and d_frames int64 [B] as mtts_pitch_track wrote them -> exact order statistics of the
+ *   voiced values (f0 > 0) of the first d_frames[b] columns, by radix select on their bit patterns.  With the m voiced values sorted
+ *   ascending as v[0 .. m): d_out_hz float [B][4] = (v[(m - 1) / 20], v[(m - 1) / 2], v[19 (m - 1) / 20], tail median) -- the 5 %,
+ *   50 % and 95 % points, integer division -- where the tail is the voiced frames with index >= (last voiced index) - tail_frames
+ *   and its median is t[(mt - 1) / 2] of its mt sorted values; d_counts int64 [B][3] = (frames, m, mt).  m == 0 gives four NaN;
+ *   mt < 3 gives a NaN tail median.  A row with d_frames[b] outside [0, ld_frames] (a row mtts_pitch_track refused) gives four NaN
+ *   and counts (-1, 0, 0), and is what mtts_pitch_status reports for this call.  One launch, one workgroup per row; the workspace
+ *   holds the verdict only (256 bytes). */
+#define MTTS_PITCH_MAX_LAG 1024
+int mtts_pitch_tile(void);
+int mtts_pitch_plan(int sample_rate, int hop, double fmin, double fmax, int* window, int* min_lag, int* max_lag);
+int64_t mtts_pitch_workspace_bytes(int64_t ld, int B, int sample_rate, int hop, double fmin, double fmax);
+int mtts_pitch_track(const float* d_audio, int64_t ld, const int64_t* d_lengths, int B, int sample_rate, int hop, double fmin,
+                     double fmax, double threshold, float* d_f0, float* d_aper, int64_t ld_frames, int64_t* d_frames, void* d_ws,
+                     int64_t ws_bytes, void* stream);
+int mtts_pitch_stats(const float* d_f0, int64_t ld_frames, const int64_t* d_frames, int B, int64_t tail_frames, float* d_out_hz,
+                     int64_t* d_counts, void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_pitch_status(const void* d_ws, void* stream);
+
 /* ---------------------------------------------------------------- long texts: finished rows joined into documents */
 
 /* The last step of a text longer than one utterance: its sentences are rows of one ragged batch, and the rows mtts_waveform_finish

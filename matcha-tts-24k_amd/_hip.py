@@ -19,7 +19,7 @@ from .hparams import PathHParams
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = Path(os.environ["MTTS_HIP_LIB"]) if os.environ.get("MTTS_HIP_LIB") else HERE / "libmtts_hip.so"   # override: A/B of two builds
-SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "resample.hip", "audio_codec.hip", "flac.hip", "flac_decode.hip", "corpus.hip", "wave_join.hip", "timing.hip", "loudness.hip", "style_encoder.hip", "style_grad.hip", "mas.hip", "score.hip", "spk_grad.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
+SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "resample.hip", "audio_codec.hip", "flac.hip", "flac_decode.hip", "corpus.hip", "pitch.hip", "wave_join.hip", "timing.hip", "loudness.hip", "style_encoder.hip", "style_grad.hip", "mas.hip", "score.hip", "spk_grad.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
 HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", CSRC / "host.h", HERE.parent / "include" / "mtts.h"]
 SOLVERS = {"euler": 0, "midpoint": 1, "rk4": 2}
 
@@ -329,6 +329,12 @@ def load() -> C.CDLL:
         "mtts_mel_stats_workspace_bytes": (i64, [i32, i32]),
         "mtts_mel_stats": (i32, [vp, i32, i32, vp, i32, vp, vp, vp, vp, i64, vp]),
         "mtts_mel_stats_status": (i32, [vp, vp]),
+        "mtts_pitch_tile": (i32, []),
+        "mtts_pitch_plan": (i32, [i32, i32, C.c_double, C.c_double, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "mtts_pitch_workspace_bytes": (i64, [i64, i32, i32, i32, C.c_double, C.c_double]),
+        "mtts_pitch_track": (i32, [vp, i64, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, i64, vp, vp, i64, vp]),
+        "mtts_pitch_stats": (i32, [vp, i64, vp, i32, i64, vp, vp, vp, i64, vp]),
+        "mtts_pitch_status": (i32, [vp, vp]),
         "mtts_wave_join_workspace_bytes": (i64, [i64, i64]),
         "mtts_wave_join": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i64, i64, vp, i64, vp, vp, vp, i64, vp]),
         "mtts_wave_join_status": (i32, [vp, vp]),

@@ -7,7 +7,9 @@ batch of clips on the device.
   ``[target leading zeros] + content + [target trailing zeros]`` (``mtts_silence_normalize``);
 * ``MelStatistics``    -- reference matcha/utils/generate_data_statistics.py:120-154: the ``mel_mean`` / ``mel_std`` every
   normalised mel of this package depends on (``mtts_mel_stats`` on the front end's un-normalised log-mel);
-* ``precompute_mels``  -- reference matcha/utils/precompute_mels.py:100-116: the normalised mel at ``hop`` and at ``hop // 2``.
+* ``precompute_mels``  -- reference matcha/utils/precompute_mels.py:100-116: the normalised mel at ``hop`` and at ``hop // 2``;
+* ``measure_pitch``    -- median F0, range and final rise of every clip (``pitch.track`` + ``pitch.stats``): what the reference's
+  documentation/pitch_raise_transfer.md needs to know about a speaker.
 
 All of them take a list of 1-D clips (host or device) or a padded batch ``[B, L]`` with ``lengths``.  Arithmetic runs in
 libmtts_hip.so (include/mtts.h "corpus preparation"); there is no CPU path.
@@ -124,6 +126,29 @@ def measure_loudness(audio, lengths=None, sample_rate: int = 24000, check: bool 
     wave, d_len = _batch(audio, lengths)
     m = LD._run(wave, d_len, sample_rate, None, LD.PEAK_CEILING, False, check, None, True)[3]
     return {k: m[k] for k in ("lufs", "peak", "true_peak", "lra", "momentary_max", "short_term_max")}
+
+
+@torch.inference_mode()
+def measure_pitch(audio, lengths=None, sample_rate: int = 24000, **params) -> Dict[str, torch.Tensor]:
+    """How high every clip speaks and whether it rises at the end: ``pitch.track`` and ``pitch.stats`` in one call -- steps 1-2 of the
+    reference's documentation/pitch_raise_transfer.md (which speakers raise a question, which stay flat).  ``audio`` / ``lengths`` as
+    for ``measure_silence``; a list may also hold ``audio_codec.Encoded`` / ``audio_codec.FlacClip`` recordings, which go through the
+    recording entries' reader (``inference.recordings``: decoded on the device, converted to 24 kHz, and measured at 24 kHz).
+    ``params``: ``hop``, ``fmin``, ``fmax``, ``threshold``, ``check`` of ``pitch.track`` and ``tail`` of ``pitch.stats``.  Returns the
+    device tensors of ``pitch.stats`` (``median_hz``, ``p05_hz``, ``p95_hz``, ``tail_median_hz``, ``voiced_fraction``, ``range_st``,
+    ``final_rise_st``, the counts) and the contour itself (``f0``, ``aperiodicity``, ``hop``, ``window``, ``max_lag``)."""
+    from . import audio_codec as AC
+    from . import pitch as P
+    tail = {k: params.pop(k) for k in ("tail",) if k in params}
+    if not (torch.is_tensor(audio) or isinstance(audio, np.ndarray)) and any(isinstance(c, (AC.Encoded, AC.FlacClip)) for c in audio):
+        from .inference import SAMPLE_RATE, recordings
+        audio = list(audio)
+        dev = next((c.device for c in audio if torch.is_tensor(c) and c.is_cuda), torch.device("cuda"))
+        audio, lengths = recordings(audio, dev, sample_rate, lengths)
+        sample_rate = SAMPLE_RATE
+    got = P.track(audio, lengths, sample_rate, **params)
+    res = P.stats(got["f0"], got["frames"], got["hop"], sample_rate, **tail)
+    return {**res, **{k: got[k] for k in ("f0", "aperiodicity", "hop", "window", "max_lag")}}
 
 
 @torch.inference_mode()

@@ -169,6 +169,20 @@ class MatchaTTSInfer(nn.Module):
         return torch.cat(enc, 0), torch.cat(dur, 0)
 
     @torch.inference_mode()
+    def speaker_delta(self, plus, minus):
+        """The direction between two groups of voices -- ``(delta_enc, delta_dur)``, each [1, spk_emb_dim]: the mean of
+        ``speaker_rows(plus)`` minus the mean of ``speaker_rows(minus)``, e.g. the speakers that raise a question against the ones that
+        stay flat (``corpus.measure_pitch``'s ``final_rise_st`` tells them apart; the reference's
+        documentation/pitch_raise_transfer.md).  With ``(e_enc, e_dur) = speaker_rows([voice])`` a voice is moved along it as
+
+            synthesise(..., speaker_embeddings=(e_enc + alpha * delta_enc, e_dur + alpha * delta_dur))
+        """
+        if len(plus) == 0 or len(minus) == 0:
+            raise ValueError("speaker_delta needs at least one voice on each side")
+        (pe, pd), (me, md) = self.speaker_rows(plus), self.speaker_rows(minus)
+        return pe.mean(0, keepdim=True) - me.mean(0, keepdim=True), pd.mean(0, keepdim=True) - md.mean(0, keepdim=True)
+
+    @torch.inference_mode()
     def enroll_voice(self, clips, style_encoder, silence=None, sample_rate=24000):
         """Speaker rows from audio -- the reference's offline chain matcha/vocos24k/mel_extractor.py (audio -> log-mel),
         matcha/utils/precompute_mels.py:100-113 (normalise with this model's mel statistics, hop 128), StyleEncoder.forward and

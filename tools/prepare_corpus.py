@@ -7,6 +7,7 @@ normalize_silence.py, generate_data_statistics.py and precompute_mels.py do, as 
     python tools/prepare_corpus.py stats     -i configs/data/corpus-24k.yaml
     python tools/prepare_corpus.py mels      -i configs/data/corpus-24k.yaml
     python tools/prepare_corpus.py loudness  -i configs/data/corpus-24k.yaml
+    python tools/prepare_corpus.py pitch     -i configs/data/corpus-24k.yaml
     python tools/prepare_corpus.py measure --synthetic 4 [--root DIR]     # no files needed: a small corpus is written first
     python tools/prepare_corpus.py time --synthetic 32 [--seconds 10] [--repeat 20]     # per-call times, nothing is written
 
@@ -28,6 +29,10 @@ mels       writes ``<mel_dir>/<rel>.npy`` (n_mels, T) and ``.fine.npy`` at half 
 loudness   prints integrated loudness (LUFS, ITU-R BS.1770 gating), sample peak, true peak (dBTP) and loudness range (LU) of every file of the train and validation
            filelists and the corpus median, and marks files more than ``--loudness_margin`` dB from it: recordings that are far too
            quiet or too hot.  Nothing is rewritten: the mel statistics are computed without a level change.
+pitch      one table row per speaker over both filelists: clips, median F0, range in semitones, and the mean final rise (median of
+           the last 0.25 s of voicing against the clip's median, in semitones) over the rows whose text ends in ``?`` and over the
+           rest, with their difference: which speakers raise a question and which stay flat (the reference's
+           documentation/pitch_raise_transfer.md, steps 1-2).
 time       HIP-event times of the device calls on N synthetic clips of ``--seconds`` (median, min .. max of ``--repeat``), and
            the wall time of the NumPy restatement (tests/corpus_restated.py) of the same batch; profiles/r14_corpus.md.
 """
@@ -205,6 +210,51 @@ def cmd_loudness(args, cfg, corpus) -> int:
     return 0
 
 
+# ---------------------------------------------------------------------------------------------------------------- pitch
+PITCH_TABLE = (("Speaker", 10, ""), ("Count", 8, "d"), ("Median Hz", 12, ".1f"), ("Range st", 12, ".2f"), ("Rise ? st", 12, ".2f"),
+               ("Rise rest st", 14, ".2f"), ("Difference st", 14, ".2f"))
+
+
+def pitch_table(rows) -> str:
+    """``rows``: [(speaker, median_hz, range_st, final_rise_st, text ends in "?")], one per clip.  One line per speaker: clips, the
+    median of the clips' medians, the mean range, the mean final rise over the questions and over the rest, and their difference;
+    clips without a voiced frame (NaN) are left out of a mean, and a mean over nothing is NaN."""
+    def mean(values):
+        v = np.asarray([x for x in values if np.isfinite(x)], dtype=np.float64)
+        return float(v.mean()) if v.size else float("nan")
+    lines = []
+    for spk in sorted({r[0] for r in rows}):
+        mine = [r for r in rows if r[0] == spk]
+        med = [r[1] for r in mine if np.isfinite(r[1])]
+        up, rest = mean(r[3] for r in mine if r[4]), mean(r[3] for r in mine if not r[4])
+        lines.append((spk, len(mine), float(np.median(med)) if med else float("nan"), mean(r[2] for r in mine), up, rest, up - rest))
+    return format_table("Pitch per speaker (final rise: last 0.25 s of voicing against the clip's median)", PITCH_TABLE, lines)
+
+
+def cmd_pitch(args, cfg, corpus) -> int:
+    valid = cfg.get("valid_filelist_path") or None
+    lists = [resolve(cfg["train_filelist_path"]), resolve(valid) if valid else None]
+    question = {}
+    for fl in lists:                                                 # rel -> the row's text ends in a question mark
+        if fl is not None and fl.is_file():
+            for line in fl.read_text(encoding="utf-8").splitlines():
+                parts = line.strip().split("|")
+                if len(parts) >= 2:
+                    question[parts[0]] = parts[-1].rstrip().endswith("?") if len(parts) >= 4 else False
+    rows = []
+    for its, clips, rates in batches(entries(lists), args.batch):
+        for rate in sorted(set(rates)):                              # hop and lags follow each file's own rate
+            sel = [i for i, r in enumerate(rates) if r == rate]
+            got = corpus.measure_pitch([clips[i] for i in sel], None, rate)
+            med, rng, rise = (got[k].cpu().tolist() for k in ("median_hz", "range_st", "final_rise_st"))
+            rows += [(its[i][1], med[k], rng[k], rise[k], question.get(its[i][0], False)) for k, i in enumerate(sel)]
+    print(f"[prepare_corpus] pitch of {len(rows)} files, {sum(r[4] for r in rows)} of them questions")
+    if rows:
+        print()
+        print(pitch_table(rows))
+    return 0
+
+
 # ---------------------------------------------------------------------------------------------------------------- normalize
 def rewrite_wav(path: Path, cs: int, ce: int, lead: int, trail: int, L: int) -> int:
     """The file's own frames [cs, ce) between ``lead`` / ``trail`` zero frames (-1: that end's own frames); returns the frame count."""
@@ -372,7 +422,8 @@ def cmd_time(args, corpus) -> int:
                      ("corpus.normalize_silence, 0.2 s / 0.8 s", lambda: corpus.normalize_silence(audio, d_len, 0.2, 0.8, check=False)),
                      ("corpus.mel_sums on the hop-256 mel", lambda: corpus.mel_sums(mel, mel_len, check=False)),
                      ("mel front end at hop 256, un-normalised", lambda: M.extract(audio, lens, 256, 0.0, 1.0)),
-                     ("corpus.precompute_mels", lambda: corpus.precompute_mels(audio, d_len, -5.5, 2.0))):
+                     ("corpus.precompute_mels", lambda: corpus.precompute_mels(audio, d_len, -5.5, 2.0)),
+                     ("corpus.measure_pitch", lambda: corpus.measure_pitch(audio, d_len, check=False))):
         print(f"| `{name}` | {timed(fn)} |")
     hip = importlib.import_module(PKG + "._hip")
     lib, ld = hip.load(), audio.shape[1]
@@ -411,7 +462,7 @@ def cmd_time(args, corpus) -> int:
 
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("command", choices=["measure", "normalize", "stats", "mels", "loudness", "time"])
+    ap.add_argument("command", choices=["measure", "normalize", "stats", "mels", "loudness", "pitch", "time"])
     ap.add_argument("-i", "--data-config", help="data YAML (e.g. configs/data/corpus-24k.yaml)")
     ap.add_argument("--synthetic", type=int, default=0, help="write and use a synthetic corpus of N clips instead of -i")
     ap.add_argument("--root", help="where --synthetic keeps its corpus (default: a temporary directory); reused when it is already there")
@@ -447,7 +498,7 @@ def main() -> int:
     else:
         ap.error("give -i DATA_YAML or --synthetic N")
     cfg = load_config(args.config)
-    rc = {"measure": cmd_measure, "normalize": cmd_normalize, "stats": cmd_stats, "mels": cmd_mels, "loudness": cmd_loudness}[args.command](args, cfg, corpus)
+    rc = {"measure": cmd_measure, "normalize": cmd_normalize, "stats": cmd_stats, "mels": cmd_mels, "loudness": cmd_loudness, "pitch": cmd_pitch}[args.command](args, cfg, corpus)
     if keep is not None:
         keep.cleanup()
     return rc
