@@ -977,6 +977,77 @@ int mtts_pitch_stats(const float* d_f0, int64_t ld_frames, const int64_t* d_fram
                      int64_t* d_counts, void* d_ws, int64_t ws_bytes, void* stream);
 int mtts_pitch_status(const void* d_ws, void* stream);
 
+/* ---------------------------------------------------------------- prosody: a path through pitch candidates, pitch and energy per token */
+
+/* Plain YIN decides every frame alone, and a frame whose odd harmonics dip is reported an octave high.  The three entries below
+ * add what a per-token pitch needs: several candidate periods per frame with a probability mass each (the idea of pYIN: Mauch &
+ * Dixon, ICASSP 2014, with a threshold prior whose CDF needs no transcendental), one shortest path per clip through them, and the
+ * fold of a contour onto token marks.  mtts_pitch_track is untouched.  Rows, refusals, status and workspaces follow the "pitch"
+ * section above; mtts_pitch_status words the verdict of these entries too.  fp32, no fused multiply-adds, divisions correctly rounded.
+ *
+ * mtts_pitch_candidates: the arguments, frame layout, block sums, d'(tau), d_frames and the workspace (mtts_pitch_workspace_bytes)
+ *   of mtts_pitch_track.  Per frame, with thr2 = 2.0f * (float)threshold:
+ *   Record-setting dips.  Scan tau ascending over tmin < tau < tmax - 1.  tau is a dip when d'(tau) < d'(tau - 1) and
+ *     d'(tau) <= d'(tau + 1).  A dip is kept when its depth b = d'(tau) is below every depth kept before it and below thr2.
+ *   Mass, under a threshold prior uniform on [0, 2 thr]: F(v) = min(max(v / thr2, 0), 1); mass = F(previous kept depth) - F(b),
+ *     where F of "no previous" is exactly 1.0f.  The frame's unvoiced mass is F(last kept depth), or 1.0f with no dip kept.
+ *   Period.  p = (float)tau + delta, delta by the parabola rule of mtts_pitch_track: (0.5f * (a - c)) / ((a - b) + (c - b)) when that
+ *     denominator as computed is > 0, else 0.
+ *   Limit.  At most MTTS_PITCH_CANDS = 8 per frame: with more kept, the 8 of greatest mass, ties to the lower lag.  Ascending lag.
+ *   Outputs.  d_period, d_mass, d_depth float [B][ld_frames][8] (unused places 0), d_count int32 [B][ld_frames], d_unvoiced_mass and
+ *     d_floor float [B][ld_frames]; floor = the lowest-index minimum of d' over [tmin, tmax), which is what YIN reports for an unvoiced
+ *     frame.  A frame that read a NaN or Inf sample: count = -1, no candidates, unvoiced mass 1, floor NaN.  Columns at or beyond the
+ *     row's frame count: count = 0, unvoiced mass = 1, floor = 1.  Two launches: block sums, then (eight frames, clip); a wave per
+ *     frame and a lane per 16 lags.  A minimum rounds nothing, so the running record is the same bits in any scan shape.
+ *
+ * mtts_pitch_viterbi: a lattice as mtts_pitch_candidates wrote it (or made by hand: no audio is read) and d_frames [B] -> one path
+ *   per clip.  States of a frame: its candidates 0 .. count - 1 (count above 8 is read as 8) and U (unvoiced), index 8, last.
+ *   Local cost: 1.0f - mass of a candidate, 1.0f - unvoiced mass of U; a frame with count < 0 has only U, at cost 0.
+ *   Transition from state r of frame k - 1 to state s of frame k: voiced to voiced (float)jump * (fabsf(p_s - p_r) / fminf(p_s, p_r))
+ *     -- an octave costs jump --, voiced to or from U (float)switch_cost, U to U 0.
+ *   Recurrence.  D_0(s) = local_0(s); D_k(s) = (min_r (D_{k-1}(r) + trans(r, s))) + local_k(s), the minimum over r ascending with
+ *     strict <, so the lowest index wins a tie; then, at every k including 0, D_k(s) <- D_k(s) - min_s D_k(s) (one rounding), so the
+ *     costs stay near 1 however long the clip is.  The end state is the lowest-index minimum of the last frame; the path is walked
+ *     back from it.
+ *   Outputs in mtts_pitch_track's format, so mtts_pitch_stats takes them unchanged: f0 = (float)fs / p of the chosen candidate or 0
+ *     for U; aperiodicity = the chosen candidate's depth, for U the frame's floor, NaN for a frame with count < 0; d_state int8
+ *     [B][ld_frames] the chosen state (8 = U).  Columns at or beyond d_frames[b]: f0 = 0, aperiodicity = 1, state = -1.  A row with
+ *     d_frames[b] outside [0, ld_frames] is refused through the verdict and holds those fill values in every column.  0 <= jump,
+ *     switch_cost <= 1e6.  One launch, one wavefront per clip: sequential in frames.  Workspace: mtts_pitch_viterbi_workspace_bytes
+ *     (the verdict and one 64-bit word of nine 4-bit back pointers per frame).
+ *
+ * mtts_pitch_fold: d_f0 [B][ld_frames] and d_frames [B] as mtts_pitch_track or mtts_pitch_viterbi wrote them with (hop H, window W,
+ *   max_lag tmax); d_marks int64 [B][Tx][2] = (start, end) of every token in samples of the clip, as mtts_token_timing writes them
+ *   ((-1, -1): no token); d_x_lengths int64 [B]; optionally the audio fp32 [B][ld] with d_lengths [B] (d_lengths alone may be given
+ *   too: it bounds the marks).
+ *   Membership.  Frame k belongs to token i when 2 start_i <= 2 k H + W + tmax < 2 end_i: the nominal centre, in integers; a token's
+ *     frames are [f(start), f(end)) with f(m) = min(n, max(0, ceil((2 m - W - tmax) / (2 H)))).
+ *   Per token.  d_counts int32 [B][Tx][2] = (frames, voiced: f0 > 0).  d_hz float [B][Tx][3] = (median, first voiced, last voiced):
+ *     the median is the exact order statistic v[(m - 1) / 2] of the token's m voiced values sorted ascending; m == 0 gives three NaN.
+ *   With audio: d_mean_square double [B][Tx] = the fp64 sum of x^2 over [start, end) divided by (double)(end - start), in an order
+ *     that is a function of (start, end) only: partial sum l = 0 .. 63 starts from 0.0 and adds x[start + l + 64 j]^2 (exact in
+ *     fp64) for j = 0, 1, .. while the index is below end; then v[l] = v[l] + v[l ^ o] for every l at once, o = 32, 16, 8, 4, 2, 1;
+ *     the sum is v[0].  0 for an empty token; NaN where a sample is not finite.
+ *   Refusals, through the verdict, touching no other row: d_frames[b] outside [0, ld_frames]; d_x_lengths[b] outside [0, Tx]; a
+ *     length below 0 (or above ld with audio); a mark outside [0, length]; start > end; a start below the end of the token before
+ *     it.  Every token of a refused row holds counts (-1, 0), three NaN and a NaN mean square.  Tokens at or beyond d_x_lengths[b],
+ *     and tokens with marks (-1, -1), hold the fill values: counts (0, 0), three NaN, mean square 0.  One launch, a wave per token;
+ *     the workspace holds the verdict only (256 bytes). */
+#define MTTS_PITCH_CANDS 8
+int mtts_pitch_candidates(const float* d_audio, int64_t ld, const int64_t* d_lengths, int B, int sample_rate, int hop, double fmin,
+                          double fmax, double threshold, float* d_period, float* d_mass, float* d_depth, int32_t* d_count,
+                          float* d_unvoiced_mass, float* d_floor, int64_t ld_frames, int64_t* d_frames, void* d_ws, int64_t ws_bytes,
+                          void* stream);
+int64_t mtts_pitch_viterbi_workspace_bytes(int64_t ld_frames, int B);
+int mtts_pitch_viterbi(const float* d_period, const float* d_mass, const float* d_depth, const int32_t* d_count,
+                       const float* d_unvoiced_mass, const float* d_floor, int64_t ld_frames, const int64_t* d_frames, int B,
+                       int sample_rate, double jump, double switch_cost, float* d_f0, float* d_aper, int8_t* d_state, void* d_ws,
+                       int64_t ws_bytes, void* stream);
+int mtts_pitch_fold(const float* d_f0, int64_t ld_frames, const int64_t* d_frames, int B, int hop, int window, int max_lag,
+                    const int64_t* d_marks, int Tx, const int64_t* d_x_lengths, const float* d_audio, int64_t ld,
+                    const int64_t* d_lengths, int32_t* d_counts, float* d_hz, double* d_mean_square, void* d_ws, int64_t ws_bytes,
+                    void* stream);
+
 /* ---------------------------------------------------------------- long texts: finished rows joined into documents */
 
 /* The last step of a text longer than one utterance: its sentences are rows of one ragged batch, and the rows mtts_waveform_finish

@@ -335,6 +335,10 @@ def load() -> C.CDLL:
         "mtts_pitch_track": (i32, [vp, i64, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, i64, vp, vp, i64, vp]),
         "mtts_pitch_stats": (i32, [vp, i64, vp, i32, i64, vp, vp, vp, i64, vp]),
         "mtts_pitch_status": (i32, [vp, vp]),
+        "mtts_pitch_candidates": (i32, [vp, i64, vp, i32, i32, i32, C.c_double, C.c_double, C.c_double, vp, vp, vp, vp, vp, vp, i64, vp, vp, i64, vp]),
+        "mtts_pitch_viterbi_workspace_bytes": (i64, [i64, i32]),
+        "mtts_pitch_viterbi": (i32, [vp, vp, vp, vp, vp, vp, i64, vp, i32, i32, C.c_double, C.c_double, vp, vp, vp, vp, i64, vp]),
+        "mtts_pitch_fold": (i32, [vp, i64, vp, i32, i32, i32, i32, vp, i32, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]),
         "mtts_wave_join_workspace_bytes": (i64, [i64, i64]),
         "mtts_wave_join": (i32, [vp, i64, vp, vp, vp, vp, i32, i32, i64, i64, vp, i64, vp, vp, vp, i64, vp]),
         "mtts_wave_join_status": (i32, [vp, vp]),

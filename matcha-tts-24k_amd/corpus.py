@@ -134,19 +134,24 @@ def measure_pitch(audio, lengths=None, sample_rate: int = 24000, **params) -> Di
     reference's documentation/pitch_raise_transfer.md (which speakers raise a question, which stay flat).  ``audio`` / ``lengths`` as
     for ``measure_silence``; a list may also hold ``audio_codec.Encoded`` / ``audio_codec.FlacClip`` recordings, which go through the
     recording entries' reader (``inference.recordings``: decoded on the device, converted to 24 kHz, and measured at 24 kHz).
-    ``params``: ``hop``, ``fmin``, ``fmax``, ``threshold``, ``check`` of ``pitch.track`` and ``tail`` of ``pitch.stats``.  Returns the
-    device tensors of ``pitch.stats`` (``median_hz``, ``p05_hz``, ``p95_hz``, ``tail_median_hz``, ``voiced_fraction``, ``range_st``,
-    ``final_rise_st``, the counts) and the contour itself (``f0``, ``aperiodicity``, ``hop``, ``window``, ``max_lag``)."""
+    ``params``: ``hop``, ``fmin``, ``fmax``, ``threshold``, ``check`` of ``pitch.track`` and ``tail`` of ``pitch.stats``;
+    ``method="viterbi"`` (with ``jump``, ``switch``) tracks with ``pitch.track_viterbi`` instead, the default ``"yin"`` makes exactly
+    the calls it always made.  Returns the device tensors of ``pitch.stats`` (``median_hz``, ``p05_hz``, ``p95_hz``,
+    ``tail_median_hz``, ``voiced_fraction``, ``range_st``, ``final_rise_st``, the counts) and the contour itself (``f0``,
+    ``aperiodicity``, ``hop``, ``window``, ``max_lag``)."""
     from . import audio_codec as AC
     from . import pitch as P
     tail = {k: params.pop(k) for k in ("tail",) if k in params}
+    track = P.METHODS.get(params.pop("method", "yin"))
+    if track is None:
+        raise ValueError(f"method must be one of {sorted(P.METHODS)}")
     if not (torch.is_tensor(audio) or isinstance(audio, np.ndarray)) and any(isinstance(c, (AC.Encoded, AC.FlacClip)) for c in audio):
         from .inference import SAMPLE_RATE, recordings
         audio = list(audio)
         dev = next((c.device for c in audio if torch.is_tensor(c) and c.is_cuda), torch.device("cuda"))
         audio, lengths = recordings(audio, dev, sample_rate, lengths)
         sample_rate = SAMPLE_RATE
-    got = P.track(audio, lengths, sample_rate, **params)
+    got = track(audio, lengths, sample_rate, **params)
     res = P.stats(got["f0"], got["frames"], got["hop"], sample_rate, **tail)
     return {**res, **{k: got[k] for k in ("f0", "aperiodicity", "hop", "window", "max_lag")}}
 

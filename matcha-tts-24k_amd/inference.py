@@ -347,6 +347,35 @@ class MatchaTTSInfer(nn.Module):
         # (no estimator call, so no time-out word; the stream is already drained: no second wait)
         return rt.guarded(self.range_policy, run, lambda _: (bool(rt.ready().range_flags()[0].item()), False))
 
+    @torch.inference_mode()
+    def prosody(self, x, x_lengths, audio=None, audio_lengths=None, speaker=0, voice_mix=None, speaker_embeddings=None, silence=None,
+                sample_rate=24000, method="viterbi", **pitch_params):
+        """Pitch and energy of every token of a recording, in one call: ``align`` (which fine frames belong to which token), then
+        ``timing.token_marks`` (keep = the clip's length at 24 kHz, as tools/align.py --marks does), ``pitch.contour`` at the fine-mel
+        hop and ``pitch.fold`` -- does this voice raise the ``?``, and does a moved voice raise it more (the reference's
+        documentation/pitch_raise_transfer.md).  The recording, ``sample_rate``, ``silence`` and the speaker arguments as for
+        ``align``; ``method`` and ``pitch_params`` (``fmin``, ``fmax``, ``threshold``, ``jump``, ``switch``) as for ``pitch.contour``.
+        Returns the tensors of ``pitch.fold`` ([B, Tx]: ``frames``, ``voiced``, ``median_hz``, ``first_hz``, ``last_hz``,
+        ``mean_square``, ``energy_db``) and ``marks`` (int64 [B, Tx, 2], samples at 24 kHz), ``durations``, ``scale_correction``, the
+        contour ``f0`` with its ``pitch_frames``, ``hop``, ``window``, ``max_lag``, and the clips' ``audio_lengths``."""
+        from . import pitch as P
+        from . import timing as TM
+        if audio is None:
+            raise ValueError("prosody needs audio=")
+        if "hop" in pitch_params:
+            raise ValueError("prosody tracks at the fine-mel hop, so that pitch frames step with the alignment's frames")
+        wave, lengths = recordings(self._clips(audio, x.shape[0], "prosody"), x.device, sample_rate, audio_lengths, silence)
+        aligned = self.align(x, x_lengths, audio=wave, audio_lengths=lengths, speaker=speaker, voice_mix=voice_mix,
+                             speaker_embeddings=speaker_embeddings)
+        cum = torch.cumsum(aligned["durations"].to(torch.int32), 1).to(torch.int32)
+        marks, kept, _ = TM.token_marks(cum, x_lengths, lengths)
+        tracked = P.contour(wave, lengths, SAMPLE_RATE, method, hop=TM.FINE_HOP, **pitch_params)
+        out = P.fold(tracked, marks, x_lengths, audio=wave, lengths=lengths)
+        out.update(marks=marks, durations=aligned["durations"], scale_correction=aligned["scale_correction"], f0=tracked["f0"],
+                   pitch_frames=tracked["frames"], hop=tracked["hop"], window=tracked["window"], max_lag=tracked["max_lag"],
+                   audio_lengths=kept)
+        return out
+
     @staticmethod
     def _clips(audio, B, who):
         """The ``audio`` argument of the recording entries as a list of ``B`` clips: a [B, L] tensor's rows, one 1-D waveform, or a list."""

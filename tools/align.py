@@ -3,6 +3,7 @@
 
     python tools/align.py --matcha CKPT --ids-file FILE [--speaker N] [--out align.npz] clip1.wav clip2.wav ...
     python tools/align.py --marks ...                                                     # also when each token is spoken in its clip
+    python tools/align.py --marks --pitch ...                                             # and each token's pitch and energy
     python tools/align.py --synthetic 32 [--tokens 128 --frames 1500] [--repeat 200]      # no files: random weights, planted durations
 
 FILE holds one line of whitespace-separated phoneme ids per clip (the phonemiser is outside this package: ``process_text`` of the
@@ -143,6 +144,7 @@ def main() -> int:
     ap.add_argument("--frames", type=int, default=1500)
     ap.add_argument("--repeat", type=int, default=1, help="time the call this many times per round (synthetic mode)")
     ap.add_argument("--marks", action="store_true", help="also print when each token is spoken in its recording (seconds at 24 kHz; timing.token_marks)")
+    ap.add_argument("--pitch", action="store_true", help="with --marks: median / first / last Hz and energy of each token (pitch.track_viterbi, pitch.fold)")
     args = ap.parse_args()
     inf = importlib.import_module(PKG + ".inference")
     if args.synthetic:
@@ -180,11 +182,26 @@ def main() -> int:
             keep = [tm.FINE_HOP * int(v) for v in host["mel_fine_lengths"]]
         cum = torch.cumsum(out["durations"].to(torch.int32), 1).to(torch.int32)
         marks, _, _ = tm.token_marks(cum, x_len, keep)
+        folded = None
+        if args.pitch:
+            # the clips as the alignment saw them (24 kHz, silence reshaped), tracked at the fine-mel hop and folded onto the marks
+            pitch = importlib.import_module(PKG + ".pitch")
+            wave, n24 = inf.recordings(list(clips), dev, rates, None, silence_of(args))
+            tracked = pitch.track_viterbi(wave, n24, 24000, hop=tm.FINE_HOP)
+            ends = torch.as_tensor(n24, device=marks.device).long()[:, None, None]     # (with --silence keep is whole frames: not past the clip)
+            inside = torch.where(marks >= 0, torch.minimum(marks, ends), marks)
+            folded = {k: v.cpu().numpy() for k, v in pitch.fold(tracked, inside, x_len, audio=wave, lengths=n24).items()}
         for b, row in enumerate(tm.marks_rows(marks.cpu())):
             print(f"[align] {args.wavs[b]}: marks")
             for i, (t0, t1) in enumerate(row):
-                print(f"    token {i:4d} id {ids[b][i]:4d}: {t0:9.4f} s .. {t1:9.4f} s")
+                tail = ""
+                if folded is not None:
+                    tail = (f"   {folded['median_hz'][b, i]:7.1f} Hz ({folded['first_hz'][b, i]:7.1f} .. {folded['last_hz'][b, i]:7.1f}), "
+                            f"{int(folded['voiced'][b, i])}/{int(folded['frames'][b, i])} voiced, {folded['energy_db'][b, i]:6.1f} dB")
+                print(f"    token {i:4d} id {ids[b][i]:4d}: {t0:9.4f} s .. {t1:9.4f} s{tail}")
         host["marks"] = marks.cpu().numpy()
+        if folded is not None:
+            host.update({"token_" + k: v for k, v in folded.items()})
     np.savez(args.out, **host)
     return 0
 

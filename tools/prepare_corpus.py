@@ -245,10 +245,12 @@ def cmd_pitch(args, cfg, corpus) -> int:
     for its, clips, rates in batches(entries(lists), args.batch):
         for rate in sorted(set(rates)):                              # hop and lags follow each file's own rate
             sel = [i for i, r in enumerate(rates) if r == rate]
-            got = corpus.measure_pitch([clips[i] for i in sel], None, rate)
+            got = corpus.measure_pitch([clips[i] for i in sel], None, rate, method="viterbi" if args.viterbi else "yin")
             med, rng, rise = (got[k].cpu().tolist() for k in ("median_hz", "range_st", "final_rise_st"))
             rows += [(its[i][1], med[k], rng[k], rise[k], question.get(its[i][0], False)) for k, i in enumerate(sel)]
     print(f"[prepare_corpus] pitch of {len(rows)} files, {sum(r[4] for r in rows)} of them questions")
+    if args.viterbi:
+        print("[prepare_corpus] tracked by the shortest path through YIN's candidates (pitch.track_viterbi)")
     if rows:
         print()
         print(pitch_table(rows))
@@ -474,6 +476,7 @@ def main() -> int:
     ap.add_argument("--threshold_db", type=float, default=-60.0)
     ap.add_argument("--loudness_margin", type=float, default=6.0, help="loudness: mark files further than this many dB from the median")
     ap.add_argument("--report", help="normalize: write per-file bounds and deltas as JSON")
+    ap.add_argument("--viterbi", action="store_true", help="pitch: smooth octave errors (pitch.track_viterbi) instead of plain YIN")
     ap.add_argument("--seconds", type=float, default=10.0, help="time: length of the synthetic clips' content")
     ap.add_argument("--repeat", type=int, default=20, help="time: timed calls")
     args = ap.parse_args()
