@@ -1636,6 +1636,31 @@ int mtts_channel_layernorm_bwd(const float* d_x, const float* d_dy, int B, int T
 int mtts_attention_rope_bwd(const float* d_qkv, const float* d_o, const float* d_do, const int64_t* d_lengths, int B, int T, int H, int D,
                             float scale, const float* d_cos, const float* d_sin, float* d_dqkv, void* d_scratch, void* stream);
 
+/* Kernel-level entries of mtts_spk_grad's seed, gate and token-sum kernels on given buffers (no context).
+ * mtts_spk_grad_seeds: the two Huber seeds, launched as mtts_spk_grad launches them: mtts_score_prior_dur into the scratch for the
+ *   verdicts, the zero fill, then the seed kernels.  d_mu_x [B, F, Tx], d_logw [B, Tx], d_durations int32 [B, Tx], d_y_fine
+ *   [B, F, Tm], both length vectors int64 [B], d_w_proj [Fd] (the duration predictor's output projection row) ->
+ *   d_seed_mu [B*Tx, round_up(F, 4)] = minus the sum over the frames of token x, in frame order, of clamp(y - mu_x, +-delta_prior)
+ *   (zeros at x >= len_b and in the padding columns), d_seed_logw [B*Tx, Fd] = clamp(logw - log(2 + dur), +-delta_dur) * d_w_proj
+ *   (zeros at x >= len_b).  An utterance that mtts_score_prior_dur refuses gets zeros; mtts_score_status(d_scratch, stream) names
+ *   it.  Tx <= 1024, Tm >= Tx, deltas > 0; d_scratch 16-byte aligned, mtts_spk_grad_seeds_scratch_bytes(B, Tx, Tm) bytes.
+ * mtts_grad_gate: in place on the gradient rows d_g [M, ldg], columns [0, C), against the forward's rows d_ref [M, ldref]: mode 0
+ *   g *= silu'(ref); mode 1 g = 0 where not (ref > 0) or d_mask[row] == 0; mode 2 the same decision on the P16 image of ref (built
+ *   in d_scratch, M * 2 C halves, residual scale 2^11, rows times d_mask, as the FFN hand-over writes it): on iff the head is
+ *   positive, or the head is zero and the residual positive.  Mode 2 needs C % 32 == 0 and ldref % 4 == 0.  d_mask [M] or NULL.
+ * mtts_token_sums: d_dst[b, dcol0 + c] (+)= sum over t < len_b of d_src[(b T + t), col0 + c] for c < C: four phases t = p, p + 4, ...
+ *   in token order, combined as ((p0 + p1) + p2) + p3.  d_len int64 [B] or NULL (T; clamped to [0, T]); d_verdict int32 [B, 2] or
+ *   NULL (first word non-zero: zero sums); accumulate 0 / 1; ld >= col0 + C, ldd >= dcol0 + C. */
+int64_t mtts_spk_grad_seeds_scratch_bytes(int B, int Tx, int Tm);
+int mtts_spk_grad_seeds(const float* d_mu_x, const float* d_logw, const int32_t* d_durations, const float* d_y_fine,
+                        const int64_t* d_x_lengths, const int64_t* d_y_fine_lengths, const float* d_w_proj, int B, int F, int Tx, int Tm,
+                        int Fd, float delta_prior, float delta_dur, float* d_seed_mu, float* d_seed_logw, void* d_scratch,
+                        int64_t scratch_bytes, void* stream);
+int mtts_grad_gate(float* d_g, int ldg, int M, int C, int mode, const float* d_ref, int ldref, const float* d_mask, void* d_scratch,
+                   void* stream);
+int mtts_token_sums(const float* d_src, int ld, int col0, int C, int B, int T, const int64_t* d_len, const int32_t* d_verdict,
+                    float* d_dst, int ldd, int dcol0, int accumulate, void* stream);
+
 /* ---------------------------------------------------------------- arithmetic and its range guard */
 
 /* Range guard of the default arithmetic.  The fp16 two-term split represents an operand x as h + l / 2^11 with h = fp16(x):

@@ -397,6 +397,10 @@ def load() -> C.CDLL:
         "mtts_match_seeds": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp]),
         "mtts_channel_layernorm_bwd": (i32, [vp, vp, i32, i32, i32, vp, vp, f32, i32, vp, vp, i32, vp, vp, vp, vp]),
         "mtts_attention_rope_bwd": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
+        "mtts_spk_grad_seeds_scratch_bytes": (i64, [i32, i32, i32]),
+        "mtts_spk_grad_seeds": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, i64, vp]),
+        "mtts_grad_gate": (i32, [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp]),
+        "mtts_token_sums": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, i32, i32, vp]),
         "mtts_gemm_terms": (i32, [vp]),
         "mtts_set_arithmetic": (i32, [vp, i32]),
         "mtts_weights_saturate": (i32, [vp]),
@@ -1760,6 +1764,33 @@ def attention_rope_bwd(qkv, o, do, lengths, B, T, H, D, scale, cos, sin):
     check(lib.mtts_attention_rope_bwd(ptr(qkv), ptr(o), ptr(do), ptr(lengths), B, T, H, D, float(scale), ptr(cos), ptr(sin), ptr(dqkv),
                                       ptr(scratch), stream_ptr()))
     return dqkv
+
+
+def spk_grad_seeds(mu_x, logw, durations, y_fine, x_lengths, y_fine_lengths, w_proj, delta_prior, delta_dur, *, seed_mu, seed_logw):
+    """The two Huber seeds of ``mtts_spk_grad`` on given buffers (mtts_spk_grad_seeds).  ``seed_mu`` (>= B*Tx*round_up(F, 4) floats) and
+    ``seed_logw`` (>= B*Tx*Fd floats) are the caller's, so that a test can fill them first.  Returns the scratch, whose header
+    ``mtts_score_status`` reads."""
+    lib = load()
+    B, F, Tx = mu_x.shape
+    Tm, Fd = y_fine.shape[2], w_proj.numel()
+    scratch = torch.zeros(size(lib.mtts_spk_grad_seeds_scratch_bytes(B, Tx, Tm)), dtype=torch.uint8, device=mu_x.device)
+    check(lib.mtts_spk_grad_seeds(ptr(mu_x), ptr(logw), ptr(durations), ptr(y_fine), ptr(x_lengths), ptr(y_fine_lengths), ptr(w_proj), B, F, Tx,
+                                  Tm, Fd, float(delta_prior), float(delta_dur), ptr(seed_mu), ptr(seed_logw), scratch.data_ptr(), scratch.numel(),
+                                  stream_ptr()))
+    return scratch
+
+
+def grad_gate(g, ldg, M, Cc, mode, ref, *, mask=None):
+    """``gate_kernel`` in place on the flat buffer ``g`` (rows of ``ldg`` floats) against ``ref`` [M, ldref] (mtts_grad_gate)."""
+    scratch = torch.empty(M * 2 * Cc, dtype=torch.float16, device=ref.device) if mode == 2 else None
+    check(load().mtts_grad_gate(ptr(g), ldg, M, Cc, mode, ptr(ref), ref.shape[1], ptr(mask), ptr(scratch), stream_ptr()))
+    return g
+
+
+def token_sums(src, col0, Cc, B, T, dst, ldd, dcol0, *, lengths=None, verdict=None, accumulate=0):
+    """``colsum_kernel`` with every argument (mtts_token_sums): ``src`` [B*T, ld] rows, ``dst`` a flat buffer of rows of ``ldd`` floats."""
+    check(load().mtts_token_sums(ptr(src), src.shape[1], col0, Cc, B, T, ptr(lengths), ptr(verdict), ptr(dst), ldd, dcol0, accumulate, stream_ptr()))
+    return dst
 
 
 # ---- the kernels that are not GEMMs (csrc/vocos.hip, csrc/norm_glue.hip): thin wrappers of their unit entries.  Buffers a kernel

@@ -1085,4 +1085,75 @@ int mtts_attention_rope_bwd(const float* d_qkv, const float* d_o, const float* d
     return 0;
 }
 
+// The two seeds of mtts_spk_grad on given buffers, launched as that entry launches them: mtts_score_prior_dur into the scratch for the
+// verdicts, the zero fill, seed_mu_kernel, seed_logw_kernel.  d_mu_x [B][F][Tx], d_logw [B][Tx], d_durations int32 [B][Tx], d_y_fine
+// [B][F][Tm], d_w_proj [Fd] -> d_seed_mu [B Tx][round_up(F, 4)], d_seed_logw [B Tx][Fd].  The scratch starts with the score workspace
+// (mtts_score_status reads the verdict there), then the two sums [B] that the score writes.
+static size_t seeds_sums_off(int B, int Tx, int Tm) { return ((size_t)mtts_score_workspace_bytes(B, Tx, Tm) + 255) / 256 * 256; }
+int64_t mtts_spk_grad_seeds_scratch_bytes(int B, int Tx, int Tm) {
+    if (!sg_shape_ok("mtts_spk_grad_seeds_scratch_bytes", B, Tx, Tm)) return -1;
+    return (int64_t)(seeds_sums_off(B, Tx, Tm) + ((size_t)2 * B * sizeof(float) + 255) / 256 * 256);
+}
+int mtts_spk_grad_seeds(const float* d_mu_x, const float* d_logw, const int32_t* d_durations, const float* d_y_fine, const int64_t* d_x_lengths,
+                        const int64_t* d_y_fine_lengths, const float* d_w_proj, int B, int F, int Tx, int Tm, int Fd, float delta_prior,
+                        float delta_dur, float* d_seed_mu, float* d_seed_logw, void* d_scratch, int64_t scratch_bytes, void* stream) {
+    if (!d_mu_x || !d_logw || !d_durations || !d_y_fine || !d_x_lengths || !d_y_fine_lengths || !d_w_proj || !d_seed_mu || !d_seed_logw ||
+        !d_scratch) {
+        set_error("mtts_spk_grad_seeds: null argument");
+        return -1;
+    }
+    if (!sg_shape_ok("mtts_spk_grad_seeds", B, Tx, Tm)) return -1;
+    if (F < 1 || F > 65535 || Fd < 1) { set_error("mtts_spk_grad_seeds: need 1 <= F <= 65535 and Fd >= 1"); return -1; }
+    if (!(delta_prior > 0.f) || !(delta_dur > 0.f)) { set_error("mtts_spk_grad_seeds: the Huber thresholds must be positive"); return -1; }
+    if (scratch_bytes < mtts_spk_grad_seeds_scratch_bytes(B, Tx, Tm)) { set_error("mtts_spk_grad_seeds: scratch too small (mtts_spk_grad_seeds_scratch_bytes)"); return -1; }
+    if (reinterpret_cast<uintptr_t>(d_scratch) & 15) { set_error("mtts_spk_grad_seeds: scratch must be 16-byte aligned"); return -1; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* sc = static_cast<char*>(d_scratch);
+    float* sums = reinterpret_cast<float*>(sc + seeds_sums_off(B, Tx, Tm));
+    RET_IF(mtts_score_prior_dur(d_mu_x, d_logw, d_durations, d_y_fine, d_x_lengths, d_y_fine_lengths, B, F, Tx, Tm, delta_prior, delta_dur, sums,
+                                sums + B, nullptr, nullptr, sc, mtts_score_workspace_bytes(B, Tx, Tm), stream));
+    const int32_t* verdict = reinterpret_cast<const int32_t*>(sc + SCORE_HEADER_BYTES);
+    const int ldm = round_up(F, 4);
+    HIP_OK(launch_fill_cols(d_seed_mu, B * Tx, ldm, 0, ldm, 0.f, s));
+    hipLaunchKernelGGL(seed_mu_kernel, dim3(F, B), dim3(256), 0, s, d_mu_x, d_y_fine, d_durations, d_x_lengths, verdict, F, Tx, Tm, delta_prior,
+                       d_seed_mu, ldm);
+    HIP_OK(hipGetLastError());
+    hipLaunchKernelGGL(seed_logw_kernel, dim3(B * Tx), dim3(64), 0, s, d_logw, d_durations, d_x_lengths, verdict, d_w_proj, Tx, Fd, delta_dur,
+                       d_seed_logw);
+    HIP_OK(hipGetLastError());
+    return 0;
+}
+
+// gate_kernel on fp32 gradient rows d_g [M][ldg] (in place) against the fp32 reference rows d_ref [M][ldref]: mode 0 SiLU', 1 the ReLU
+// gate on the fp32 rows, 2 the ReLU gate on their P16 image, which is built here as the FFN hand-over builds it (residual scale 2^11,
+// rows times d_mask) in d_scratch (M * 2 C halves).  d_mask [M] or NULL (modes 1 and 2).
+int mtts_grad_gate(float* d_g, int ldg, int M, int C, int mode, const float* d_ref, int ldref, const float* d_mask, void* d_scratch,
+                   void* stream) {
+    if (!d_g || !d_ref) { set_error("mtts_grad_gate: null argument"); return -1; }
+    if (mode < 0 || mode > 2) { set_error("mtts_grad_gate: mode must be 0 (SiLU'), 1 (ReLU on fp32 rows) or 2 (ReLU on the P16 image)"); return -1; }
+    if (M < 1 || C < 1 || ldg < C || ldref < C) { set_error("mtts_grad_gate: need M, C >= 1, ldg >= C and ldref >= C"); return -1; }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    _Float16* img = nullptr;
+    if (mode == 2) {
+        if (!d_scratch) { set_error("mtts_grad_gate: mode 2 needs d_scratch (M * 2 C halves)"); return -1; }
+        if ((C & 31) || (ldref & 3)) { set_error("mtts_grad_gate: mode 2 needs C a multiple of 32 and ldref a multiple of 4"); return -1; }
+        img = static_cast<_Float16*>(d_scratch);
+        HIP_OK(launch_to_p16(d_ref, ldref, d_mask, M, C, C, img, 2 * C, F16_RES_SCALE, s));
+    }
+    HIP_OK(launch_gate(d_g, ldg, M, C, mode, d_ref, ldref, img, 2 * C, d_mask, s));
+    return 0;
+}
+
+// launch_colsum with every argument: d_dst[b][dcol0 + c] (+)= the sum over t < len_b of d_src[(b T + t) ld + col0 + c], c < C.  d_len
+// int64 [B] or NULL (T); d_verdict int32 [B][2] or NULL (non-zero first word: the utterance's sums are zero).
+int mtts_token_sums(const float* d_src, int ld, int col0, int C, int B, int T, const int64_t* d_len, const int32_t* d_verdict, float* d_dst,
+                    int ldd, int dcol0, int accumulate, void* stream) {
+    if (!d_src || !d_dst) { set_error("mtts_token_sums: null argument"); return -1; }
+    if (B < 1 || B > 65535 || T < 1 || C < 1) { set_error("mtts_token_sums: need 1 <= B <= 65535 and T, C >= 1"); return -1; }
+    if (col0 < 0 || dcol0 < 0 || ld < col0 + C || ldd < dcol0 + C) { set_error("mtts_token_sums: need col0, dcol0 >= 0, ld >= col0 + C and ldd >= dcol0 + C"); return -1; }
+    if (accumulate != 0 && accumulate != 1) { set_error("mtts_token_sums: accumulate must be 0 or 1"); return -1; }
+    HIP_OK(launch_colsum(d_src, ld, col0, C, B, T, d_len, d_verdict, d_dst, ldd, dcol0, accumulate, static_cast<hipStream_t>(stream)));
+    return 0;
+}
+
 }  // extern "C"
