@@ -1,6 +1,7 @@
 """Own-words fp64 restatements for the style encoder's parameter gradients (csrc/style_grad.hip): the encoder itself with autograd,
 the plain definition of the Conv1d(k5, pad 2) weight gradient, and the backward pass GIVEN a tape of activations together with a
-running bound on what fp32 arithmetic in the device's summation orders may lose against it.  Nothing here calls the library."""
+running bound on what fp32 arithmetic in the device's summation orders may lose against it; and integer cases on which fp32 loses
+nothing, with the check that they are such cases.  Nothing here calls the library."""
 import math
 
 import torch
@@ -99,6 +100,161 @@ def conv_wgrad(dz, x, lengths):
     val = torch.stack([torch.einsum("bto,bti->oi", dz, xp[:, k:k + T]) for k in range(TAPS)], dim=2)
     mag = torch.stack([torch.einsum("bto,bti->oi", dz.abs(), xp[:, k:k + T].abs()) for k in range(TAPS)], dim=2)
     return val, mag
+
+
+def conv_wgrad_by_chunk(dz, x, lengths, chunk):
+    """conv_wgrad cut the way the device cuts it: chunk c holds the terms of the rows r = b T + t in [c chunk, (c + 1) chunk) -- the
+    rows of dz; a tap may read a frame of x that lies in a neighbouring chunk.
+    -> (dW [chunks, cout, cin, 5], |dW| likewise, d bias [chunks, cout], |d bias| likewise); their sums over the chunks are the whole."""
+    B, T, _ = dz.shape
+    m = prefix_mask(lengths, T)[:, :, None]
+    dz = torch.nan_to_num(dz.double()) * m
+    x = torch.nan_to_num(x.double()) * m
+    xp = F.pad(x, (0, 0, TAPS // 2, TAPS // 2))
+    chunks = -(-(B * T) // chunk)
+
+    def cut(a):                                                                                 # [B, T, c] -> [chunks, chunk, c], zero rows behind the last
+        return F.pad(a.reshape(B * T, -1), (0, 0, 0, chunks * chunk - B * T)).reshape(chunks, chunk, -1)
+    dzc = cut(dz)
+    val = torch.stack([torch.einsum("cro,cri->coi", dzc, cut(xp[:, k:k + T])) for k in range(TAPS)], dim=3)
+    mag = torch.stack([torch.einsum("cro,cri->coi", dzc.abs(), cut(xp[:, k:k + T].abs())) for k in range(TAPS)], dim=3)
+    return val, mag, dzc.sum(1), dzc.abs().sum(1)
+
+
+# ------------------------------------------------------------------------------------------------ arithmetic in which fp32 is exact
+# A sum of integers whose ABSOLUTE values add up to less than 2^24 is exact in fp32 in any order and any grouping: every partial sum
+# is an integer of magnitude below 2^24, hence a float.  On such operands a device kernel has nothing to round, and must return the
+# fp64 result itself: one dropped, doubled or mis-masked term changes an element by a whole number.
+EXACT_BELOW = 2.0 ** 24
+TAPE_LENGTHS = (0, 1, 2, 4, 8, 16, 32, 64, 128)          # 1 / max(len, 1) is a power of two: the mean pool's factor is exact as well
+
+
+def is_integer(t):
+    """Every element that is not NaN (the mark of what is never read as data) is a whole number."""
+    t = torch.as_tensor(t)
+    t = t[~torch.isnan(t)]
+    return bool(torch.isfinite(t).all() and (t == t.round()).all())
+
+
+def integer_wgrad_case(B, T, lengths, cin, cout, seed):
+    """Operands of the weight-gradient entry with integers in [-2, 2]: dz [B, T, cout], x [B, T, cin + 4] (fp32).  NaN wherever nothing
+    may be read as data: frames at t >= len_b of both, the padding columns of x."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randint(-2, 3, (B, T, cin + 4), generator=g).float()
+    dz = torch.randint(-2, 3, (B, T, cout), generator=g).float()
+    x[:, :, cin:] = float("nan")
+    for b, n in enumerate(lengths):
+        x[b, n:] = float("nan")
+        dz[b, n:] = float("nan")
+    return dz, x
+
+
+def wgrad_abs_sums(dz, x, lengths):
+    """The largest sum of absolute terms of any element of dW and of d bias (conv_wgrad's second result)."""
+    _, mag = conv_wgrad(dz, x, lengths)
+    m = prefix_mask(lengths, dz.shape[1])[:, :, None]
+    return {"dW": mag.max().item(), "d bias": (torch.nan_to_num(dz.double()) * m).abs().sum((0, 1)).max().item()}
+
+
+def integer_tape_case(cfg, B, T, lengths, seed, density=0.25):
+    """A state dict and a HAND-WRITTEN tape for the backward, all integers: cfg = (n_feats, hidden, n_layers, emb), lengths from
+    TAPE_LENGTHS.  -> (sd, x0, hs, pooled, g_enc, g_dur), fp32:
+      sd       every tensor in {-1, 0, 1}, a matrix element non-zero with probability ``density``
+      x0       [B, T, n_feats] in [-2, 2], zero beyond a clip's length
+      hs[l]    [B, T, hidden] in {0, 1, 2}, half of them 0 (the ReLU gates), zero beyond a clip's length
+      pooled   [B, hidden] in {0 .. 3}
+      g_enc, g_dur [B, emb] = max(len_b, 1) times {-1, 0, 1} (non-zero with probability ``density``): d pooled / max(len_b, 1), and
+               with it every later quantity, is an integer.
+    The tape is not the forward of anything; the backward takes it as given."""
+    n_feats, hidden, L, E = cfg
+    assert len(lengths) == B and all(n in TAPE_LENGTHS and n <= T for n in lengths), lengths
+    g = torch.Generator().manual_seed(seed)
+
+    def signs(shape, p):
+        return (2.0 * torch.randint(0, 2, shape, generator=g) - 1) * (torch.rand(shape, generator=g) < p)
+    sd = {}
+    for i in range(L):
+        sd[f"convs.{i}.weight"] = signs((hidden, n_feats if i == 0 else hidden, TAPS), density)
+        sd[f"convs.{i}.bias"] = signs((hidden,), 0.5)
+    for h in ("enc", "dur"):
+        sd[f"proj_{h}.weight"] = signs((E, hidden), density)
+        sd[f"proj_{h}.bias"] = signs((E,), 0.5)
+    m = prefix_mask(lengths, T, torch.float32)[:, :, None]
+    x0 = torch.randint(-2, 3, (B, T, n_feats), generator=g).float() * m
+    hs = [torch.randint(1, 3, (B, T, hidden), generator=g).float() * (torch.rand(B, T, hidden, generator=g) < 0.5) * m for _ in range(L)]
+    pooled = torch.randint(0, 4, (B, hidden), generator=g).float()
+    n = torch.tensor(lengths).clamp(min=1).float()[:, None]
+    return sd, x0, hs, pooled, n * signs((B, E), density), n * signs((B, E), density)
+
+
+def tape_abs_sums(sd, x0, hs, pooled, lengths, g_enc, g_dur):
+    """For every ACCUMULATED quantity of backward_from_tape's chain, the largest fp64 sum of the absolute values of the terms of any
+    of its elements: the projections' gradients, d pooled, every layer's dW and d bias, every data gradient."""
+    L = n_layers_of(sd)
+    B, T, _ = x0.shape
+    x0, pooled, g_enc, g_dur = x0.double(), pooled.double(), g_enc.double(), g_dur.double()
+    hs = [h.double() for h in hs]
+    mask = prefix_mask(lengths, T)
+    n = torch.as_tensor(lengths).clamp(min=0, max=T).double()
+    sums = {}
+    for name, g in (("proj_enc", g_enc), ("proj_dur", g_dur)):
+        sums[f"{name}.weight"] = (g.abs().t() @ pooled.abs()).max().item()
+        sums[f"{name}.bias"] = g.abs().sum(0).max().item()
+    w_all = torch.cat([sd["proj_enc.weight"], sd["proj_dur.weight"]]).double()
+    g_all = torch.cat([g_enc, g_dur], dim=1)
+    sums["d pooled"] = (g_all.abs() @ w_all.abs()).max().item()
+    dz = (g_all @ w_all)[:, None, :] / n.clamp(min=1)[:, None, None] * (hs[L - 1] > 0).double() * mask[:, :, None]
+    for l in range(L - 1, -1, -1):
+        _, mag = conv_wgrad(dz, hs[l - 1] if l else x0, lengths)
+        sums[f"convs.{l}.weight"] = mag.max().item()
+        sums[f"convs.{l}.bias"] = dz.abs().sum((0, 1)).max().item()
+        if l == 0:
+            break
+        w = sd[f"convs.{l}.weight"].double()
+        sums[f"d h{l - 1}"] = F.conv_transpose1d(dz.abs().transpose(1, 2), w.abs(), padding=2).max().item()
+        dz = F.conv_transpose1d(dz.transpose(1, 2), w, padding=2).transpose(1, 2) * (hs[l - 1] > 0).double() * mask[:, :, None]
+    return sums
+
+
+def fp32_is_exact_on(sums, *operands):
+    """The exactness precondition: integer operands, every sum of absolute terms below 2^24."""
+    return all(is_integer(t) for t in operands) and all(v < EXACT_BELOW for v in sums.values())
+
+
+# The cases of tests/test_hip_style_grad.py beyond one chunk length, here so that tests/test_style_grad_abi.py can hold their
+# preconditions without a device.
+def ragged(B, T, seed):
+    """B >= 6 lengths: T, 0, 1, 2 first, then draws from 3 .. T - 1, the last two clips full (live rows on both sides of the last clip
+    boundary and in the last chunk)."""
+    draws = torch.randint(3, T, (B,), generator=torch.Generator().manual_seed(seed)).tolist()
+    return [T, 0, 1, 2] + draws[4:B - 2] + [T, T]
+
+
+#   rows: (B, T, lengths)                                      chunk  chunks
+WGRAD_ROWS = {
+    4096: (8, 512, ragged(8, 512, 1)),                         # 256    16     the most chunks at the smallest chunk length
+    4097: (1, 4097, [4097]),                                   # 512     9     the last chunk holds one row (one clip: one length)
+    8192: (16, 512, ragged(16, 512, 2)),                       # 512    16
+    8193: (3, 2731, [2731, 2, 2731]),                          # 768    11     the last chunk: 16 slabs of 32 rows and 1 row; the clip
+                                                               #               boundaries 2731, 5462 are on no slab or chunk boundary
+    19200: (32, 600, ragged(32, 600, 3)),                      # 1280   15     the measured training shape; 600 = 18 slabs + 24 rows
+}
+WGRAD_CHANNELS = {rows: [(4, 4), (20, 32)] + ([(100, 256)] if rows in (4097, 19200) else []) for rows in WGRAD_ROWS}
+WGRAD_CASES = [(rows, cin, cout) for rows in WGRAD_ROWS for cin, cout in WGRAD_CHANNELS[rows]]
+# clips shorter than the tap span and than the bias kernel's 4-row stride: (B, T), lengths drawn from 0 .. T
+SHORT_CLIPS = [(300, 1), (200, 2), (130, 3)]
+SHORT_CASES = [(B, T, cin, cout) for B, T in SHORT_CLIPS for cin, cout in ((4, 4), (20, 32))]
+
+
+def short_lengths(B, T):
+    return torch.randint(0, T + 1, (B,), generator=torch.Generator().manual_seed(10 * T + 7)).tolist()
+
+
+#   name: (cfg, B, T, lengths) -- 4800 rows each: chunk 512, 10 chunks
+TAPE_CASES = {
+    "tiny": ((20, 32, 2, 16), 32, 150, [TAPE_LENGTHS[(4 * b + 8) % 9] for b in range(32)]),
+    "prod": ((100, 256, 4, 96), 8, 600, [128, 0, 1, 2, 64, 4, 16, 128]),
+}
 
 
 # ------------------------------------------------------------------------------------------------ the backward given a tape

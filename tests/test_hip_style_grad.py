@@ -13,6 +13,12 @@ Bounds.
   * Whole gradient: per tensor err = max|g - g64| / max|g64| <= 8 max(err32, e_fwd); err32 the same quantity for float32 CPU
     autograd, e_fwd the relative error of mtts_style_forward's rows against fp64 on the same inputs (the forward carries 22-bit
     operands); 8 = 4 for operand width x 2 for summation order.
+  * Exact cases (sections 1b and 3): small-integer operands whose sums of absolute terms stay below 2^24, checked on the inputs
+    before any device call (style_grad_restated.fp32_is_exact_on).  fp32 then has nothing to round in any order, and the device must
+    equal the fp64 restatement element for element: torch.equal, no tolerance.  At 19 200 rows the first bound above is about one
+    whole term wide (1.55e-4 sum|terms|), so only these cases see a single dropped, doubled or mis-masked row for certain; what they
+    cannot see -- where and how the kernel rounds -- stays with the bounded cases, which run at the same shapes
+    (profiles/r33_style_grad_shapes.md).
 Nothing here is taken from what the device returns.  Every figure is printed (and appended to $MTTS_STYLE_GRAD_REPORT) before it is
 asserted."""
 import os
@@ -148,6 +154,92 @@ def test_conv_wgrad_clips_adjacent_in_memory_do_not_see_each_other(hip, dev, cin
         check_wgrad(f"boundary ({cin}, {cout}) lengths={'given' if lengths else 'null'}", dw, db, dz, x, lengths, cin)
 
 
+# ------------------------------------------------------------------------------------------------ 1b. beyond one chunk length
+# The row counts of training (style_grad_restated.WGRAD_ROWS: 4096 .. 19 200 rows, chunk lengths 256 .. 1280, up to 16 chunks) and clips
+# shorter than the tap span.  At these sizes the bound above is wider than one whole term, so every shape is ALSO run on small
+# integers, where fp32 has nothing to round: there the device must give the fp64 restatement itself, chunk by chunk and in total.
+def normal_wgrad_case(B, T, lengths, cin, cout, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, T, cin + 4, generator=g)
+    dz = torch.randn(B, T, cout, generator=g)
+    x[:, :, cin:] = float("nan")
+    for b, n in enumerate(lengths):
+        x[b, n:] = float("nan")
+        dz[b, n:] = float("nan")
+    return dz, x
+
+
+def check_wgrad_exact(tag, hip, dev, B, T, lengths, cin, cout, seed):
+    """Integer operands: every chunk's partial result left in the workspace, dw and db equal the fp64 restatement exactly."""
+    full = lengths if lengths is not None else [T] * B
+    dz, x = R.integer_wgrad_case(B, T, full, cin, cout, seed)
+    sums = R.wgrad_abs_sums(dz, x[:, :, :cin], full)
+    assert R.fp32_is_exact_on(sums, dz, x), sums                                  # the condition on the inputs, before any device call
+    chunk = R.chunk_rows(B, T)
+    want_w, _, want_b, _ = R.conv_wgrad_by_chunk(dz, x[:, :, :cin], full, chunk)
+    chunks = want_w.shape[0]
+    dw, db, part = run_wgrad(hip, dev, dz, x, lengths, cin, cout)
+    n_w = chunks * 5 * cout * cin
+    part_w = part[:n_w].reshape(chunks, 5, cout, cin).permute(0, 2, 3, 1).double()
+    part_b = part[n_w:].reshape(chunks, cout).double()
+    bad_w = [c for c in range(chunks) if not torch.equal(part_w[c], want_w[c])]
+    bad_b = [c for c in range(chunks) if not torch.equal(part_b[c], want_b[c])]
+    d_w, d_b = (dw.double() - want_w.sum(0)).abs().max().item(), (db.double() - want_b.sum(0)).abs().max().item()
+    note(f"conv_wgrad integers {tag}: chunk {chunk} x {chunks}, largest sum of |terms| dW {sums['dW']:.0f} bias {sums['d bias']:.0f}, "
+         f"max|dW| {want_w.sum(0).abs().max().item():.0f}; max|dW - fp64| {d_w:g}, max|db - fp64| {d_b:g}, chunks with a wrong partial: "
+         f"dW {bad_w} bias {bad_b}")
+    assert not bad_w and not bad_b, f"wrong partial results in chunks {bad_w} (dW) {bad_b} (bias)"
+    assert torch.equal(dw.double(), want_w.sum(0)) and torch.equal(db.double(), want_b.sum(0)), "exact partials, a wrong sum over the chunks"
+    dw2, db2, part2 = run_wgrad(hip, dev, dz, x, lengths, cin, cout)
+    assert torch.equal(dw, dw2) and torch.equal(db, db2) and torch.equal(part, part2)      # two calls: the same bits
+
+
+def check_wgrad_bounded(tag, hip, dev, B, T, lengths, cin, cout, seed):
+    """Unit-normal operands: the bound of the file's head with the serial runs at the real chunk length."""
+    dz, x = normal_wgrad_case(B, T, lengths if lengths is not None else [T] * B, cin, cout, seed)
+    dw, db, part = run_wgrad(hip, dev, dz, x, lengths, cin, cout)
+    check_wgrad(tag, dw, db, dz, x, lengths, cin)
+    dw2, db2, part2 = run_wgrad(hip, dev, dz, x, lengths, cin, cout)
+    assert torch.equal(dw, dw2) and torch.equal(db, db2) and torch.equal(part, part2)
+
+
+def chunk_of(hip, B, T):
+    ch = hip.load().mtts_conv_wgrad_chunk_rows(B, T)
+    assert ch == CHUNK(B, T) == R.chunk_rows(B, T)
+    return ch
+
+
+WGRAD_IDS = [f"{rows}rows-{cin}x{cout}" for rows, cin, cout in R.WGRAD_CASES]
+
+
+@pytest.mark.parametrize("rows,cin,cout", R.WGRAD_CASES, ids=WGRAD_IDS)
+def test_conv_wgrad_training_rows_exact_on_integers(hip, dev, rows, cin, cout):
+    """4096 rows (16 chunks of 256), 4097 (the last of 9 chunks holds one row), 8192 (16 of 512), 8193 (the last chunk ends in a slab
+    of one row; clip boundaries on no slab or chunk boundary) and 19 200 = 32 x 600, the measured training step (15 chunks of 1280).
+    Lengths T, 0, 1, 2 and draws between where the batch has room for them (4097 rows are one clip; 8193 are T, 2, T)."""
+    B, T, lengths = R.WGRAD_ROWS[rows]
+    assert B * T == rows and chunk_of(hip, B, T) == {4096: 256, 4097: 512, 8192: 512, 8193: 768, 19200: 1280}[rows]
+    check_wgrad_exact(f"({cin}, {cout}) B={B} T={T}", hip, dev, B, T, lengths, cin, cout, rows + cin)
+
+
+@pytest.mark.parametrize("rows,cin,cout", R.WGRAD_CASES, ids=WGRAD_IDS)
+def test_conv_wgrad_training_rows_against_fp64(hip, dev, rows, cin, cout):
+    B, T, lengths = R.WGRAD_ROWS[rows]
+    assert B * T == rows and chunk_of(hip, B, T) == {4096: 256, 4097: 512, 8192: 512, 8193: 768, 19200: 1280}[rows]
+    check_wgrad_bounded(f"({cin}, {cout}) B={B} T={T} chunk {R.chunk_rows(B, T)}", hip, dev, B, T, lengths, cin, cout, rows + cout)
+
+
+@pytest.mark.parametrize("B,T,cin,cout", R.SHORT_CASES, ids=[f"{B}x{T}-{cin}x{cout}" for B, T, cin, cout in R.SHORT_CASES])
+def test_conv_wgrad_clips_shorter_than_the_tap_span(hip, dev, B, T, cin, cout):
+    """Clips of T = 1, 2, 3 frames, lengths drawn from 0 .. T and, with no lengths given, all full: every tap but the centre one
+    leaves a 1-frame clip, and one 4-row stride of the bias kernel crosses up to four clips.  Exact on integers, bounded on normals."""
+    assert chunk_of(hip, B, T) == 256 and B * T > 256
+    for lengths, how in ((R.short_lengths(B, T), "given"), (None, "null")):
+        tag = f"short ({cin}, {cout}) B={B} T={T} lengths={how}"
+        check_wgrad_exact(tag, hip, dev, B, T, lengths, cin, cout, B)
+        check_wgrad_bounded(tag, hip, dev, B, T, lengths, cin, cout, B + 1)
+
+
 # ------------------------------------------------------------------------------------------------ 2. the tape
 CONFIGS = {"prod": (100, 256, 4, 96), "tiny": (20, 32, 2, 16)}
 
@@ -194,9 +286,19 @@ def split(model, flat):
 def test_backward_given_the_tape_against_fp64(dev, size):
     """The restatement takes the device's own activations as constants, so no ReLU gate differs between the two sides; every element of
     every parameter tensor then stays within the carried bound."""
+    check_backward_given_the_tape(dev, size, size, [70, 33, 0, 2], 70)
+
+
+def test_backward_given_the_tape_against_fp64_at_a_training_batch(dev):
+    """The same body at tiny, B = 32, T = 150: 4800 rows, 10 chunks of 512, ragged lengths with 0 and 2 among them."""
+    lengths = R.ragged(32, 150, 4)
+    assert 0 in lengths and 2 in lengths and R.chunk_rows(32, 150) == 512
+    check_backward_given_the_tape(dev, "tiny", "tiny B=32 T=150", lengths, 150)
+
+
+def check_backward_given_the_tape(dev, size, tag, lengths, T):
     cfg = CONFIGS[size]
     model, sd = make(cfg, 7, dev)
-    lengths, T = [70, 33, 0, 2], 70
     B = len(lengths)
     mel = inputs(cfg[0], T, lengths, 8).to(dev)
     g = torch.Generator().manual_seed(9)
@@ -210,9 +312,60 @@ def test_backward_given_the_tape_against_fp64(dev, size):
     for k in R.param_names(cfg[2]):
         err = (got[k].double() - want[k]).abs()
         worst = (err / bounds[k].clamp(min=1e-300)).max().item()
-        note(f"style backward from tape [{size}] {k}: max|err| {err.max().item():.3e} of max|g| {want[k].abs().max().item():.3e}, "
+        note(f"style backward from tape [{tag}] {k}: max|err| {err.max().item():.3e} of max|g| {want[k].abs().max().item():.3e}, "
              f"worst err / bound {worst:.3f}")
         assert (err <= bounds[k]).all(), k
+
+
+def write_tape(model, cfg, B, T, x0, hs, pooled, lengths):
+    """Overwrite what forward_taped kept, in the workspace tensor the module holds, at mtts_style_grad_tape_offset: the masked input
+    rows (padding columns zero), every layer's ReLU output, the pooled rows, the prefix mask."""
+    hipm = sub("_hip")
+    ws = model._tape[3]
+    L = cfg[2]
+    ldx = (cfg[0] + 3) // 4 * 4
+    regions = {0: torch.nn.functional.pad(x0, (0, ldx - cfg[0])), L + 1: pooled, L + 2: R.prefix_mask(lengths, T, torch.float32)}
+    regions.update({1 + l: hs[l] for l in range(L)})
+    with torch.inference_mode():
+        for which, t in regions.items():
+            off = hipm.size(hipm.load().mtts_style_grad_tape_offset(model._ctx, B, T, which))
+            ws[off:off + 4 * t.numel()].view(torch.float32).copy_(t.reshape(-1).to(ws.device))
+    for which, t in regions.items():
+        assert torch.equal(model.tape(which).cpu().reshape(-1), t.reshape(-1)), which
+
+
+@pytest.mark.parametrize("size", ["prod", "tiny"])
+def test_backward_on_an_integer_tape_is_exact(dev, size):
+    """mtts_style_backward on a HAND-WRITTEN integer tape (style_grad_restated.integer_tape_case), 4800 rows in 10 chunks of 512, a
+    batch of 32 (tiny) and of 8 (prod): sparse weights in {-1, 0, 1}, integer activations, lengths in {0, 1, 2, 4 .. 128} and
+    upstream rows that are multiples of them, so that every quantity of the chain -- projection gradients, d pooled, the mean pool's
+    factor, every gate, data gradient, weight and bias gradient -- is an integer whose terms' absolute values add up to less than
+    2^24.  fp32 has nothing to round: every element of every parameter gradient equals the fp64 restatement."""
+    cfg, B, T, lengths = R.TAPE_CASES[size]
+    assert cfg == CONFIGS[size]
+    sd, x0, hs, pooled, g_enc, g_dur = R.integer_tape_case(cfg, B, T, lengths, 5)
+    sums = R.tape_abs_sums(sd, x0, hs, pooled, lengths, g_enc, g_dur)
+    assert R.fp32_is_exact_on(sums, *sd.values(), x0, *hs, pooled, g_enc, g_dur), sums     # the condition on the inputs, before any device call
+    want, _ = R.backward_from_tape(sd, x0, hs, pooled, lengths, g_enc, g_dur)
+    model = sub("style").StyleEncoder(*cfg)
+    model.load_state_dict(sd)
+    model = model.to(dev).eval()
+    model.forward_taped(torch.zeros(B, cfg[0], T, device=dev), lengths=lengths)      # allocates the workspace, uploads the weights
+    write_tape(model, cfg, B, T, x0, hs, pooled, lengths)
+    flat = model.backward(g_enc.to(dev), g_dur.to(dev))
+    again = model.backward(g_enc.to(dev), g_dur.to(dev))
+    got = split(model, flat)
+    note(f"style backward on an integer tape [{size}] B={B} T={T}: largest sum of |terms| {max(sums.values()):.0f} "
+         f"({max(sums, key=sums.get)}) of 2^24 = {R.EXACT_BELOW:.0f}")
+    wrong = []
+    for k in R.param_names(cfg[2]):
+        diff = (got[k].double() - want[k]).abs()
+        note(f"style backward on an integer tape [{size}] {k}: max|g| {want[k].abs().max().item():.0f}, elements that differ "
+             f"{int((diff != 0).sum())} of {diff.numel()}, max|g - fp64| {diff.max().item():g}")
+        if not torch.equal(got[k].double(), want[k]):
+            wrong.append(k)
+    assert not wrong, wrong
+    assert torch.equal(flat, again)
 
 
 def test_an_empty_clip_contributes_exactly_zero(dev):

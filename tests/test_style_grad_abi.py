@@ -173,7 +173,125 @@ def test_chunk_length_is_a_function_of_the_shape(lib):
     assert R.wgrad_serial_run(5, 103) == 256 + 2 and R.bias_serial_run(5, 103) == 64 + 3 + 2
 
 
+@pytest.mark.parametrize("rows,chunk,chunks", [(4096, 256, 16), (4097, 512, 9), (8192, 512, 16), (8193, 768, 11), (19200, 1280, 15)])
+def test_chunk_length_at_the_training_row_counts(lib, rows, chunk, chunks):
+    """The values the GPU cases beyond one chunk length are built on, and the serial runs their bounds use."""
+    B, T, lengths = R.WGRAD_ROWS[rows]
+    assert B * T == rows and len(lengths) == B and max(lengths) == T and lengths[-1] == T
+    for b, t in ((B, T), (1, rows)):
+        assert lib.mtts_conv_wgrad_chunk_rows(b, t) == R.chunk_rows(b, t) == chunk
+        assert -(-rows // R.chunk_rows(b, t)) == chunks
+        assert R.wgrad_serial_run(b, t) == chunk + chunks - 1 and R.bias_serial_run(b, t) == chunk // 4 + 3 + chunks - 1
+    assert lib.mtts_conv_wgrad_workspace_bytes(B, T, 20, 32) == 4 * chunks * (5 * 20 * 32 + 32)
+
+
+def test_one_training_case_has_a_clip_boundary_on_no_slab_or_chunk_boundary():
+    for rows in (8193, 19200):
+        B, T, lengths = R.WGRAD_ROWS[rows]
+        inner = [b * T for b in range(1, B) if lengths[b - 1] == T and lengths[b] > 0]       # live rows on either side
+        assert any(r % 32 and r % R.chunk_rows(B, T) for r in inner), rows
+
+
 # ------------------------------------------------------------------------------------------------ the yardsticks
+def test_integer_wgrad_cases_are_exact_in_fp32():
+    """The precondition of every exact GPU case of the weight-gradient entry: integer operands in [-2, 2], NaN where nothing may be
+    read, and no element's sum of absolute terms reaches 2^24.  The chunked form adds up to the whole, exactly."""
+    cases = [(R.WGRAD_ROWS[rows] + (cin, cout, rows + cin)) for rows, cin, cout in R.WGRAD_CASES]            # (the GPU cases' seeds)
+    cases += [(B, T, R.short_lengths(B, T), cin, cout, B) for B, T, cin, cout in R.SHORT_CASES]
+    cases += [(B, T, [T] * B, cin, cout, B) for B, T, cin, cout in R.SHORT_CASES]
+    for B, T, lengths, cin, cout, seed in cases:
+        dz, x = R.integer_wgrad_case(B, T, lengths, cin, cout, seed)
+        assert dz.shape == (B, T, cout) and x.shape == (B, T, cin + 4) and dz.dtype == x.dtype == torch.float32
+        live = R.prefix_mask(lengths, T).bool()
+        assert torch.isnan(x[:, :, cin:]).all() and torch.isnan(x[~live]).all() and torch.isnan(dz[~live]).all()
+        assert not torch.isnan(x[live][:, :cin]).any() and not torch.isnan(dz[live]).any()
+        assert x[live][:, :cin].abs().max() <= 2 and dz[live].abs().max() <= 2
+        sums = R.wgrad_abs_sums(dz, x[:, :, :cin], lengths)
+        assert R.fp32_is_exact_on(sums, dz, x) and sums["dW"] > 0, (B, T, cin, cout, sums)
+        whole, _ = R.conv_wgrad(dz, x[:, :, :cin], lengths)
+        val, mag, bias, _ = R.conv_wgrad_by_chunk(dz, x[:, :, :cin], lengths, R.chunk_rows(B, T))
+        assert val.shape[0] == -(-(B * T) // R.chunk_rows(B, T)) and R.is_integer(val) and (mag >= val.abs()).all()
+        assert torch.equal(val.sum(0), whole) and torch.equal(bias.sum(0), torch.nan_to_num(dz.double()).sum((0, 1)))
+    for B, T in R.SHORT_CLIPS:
+        assert set(R.short_lengths(B, T)) == set(range(T + 1))
+    assert not R.fp32_is_exact_on({"x": 2.0 ** 24}, torch.ones(1)) and not R.fp32_is_exact_on({"x": 1.0}, torch.tensor([0.5]))
+
+
+@pytest.mark.parametrize("T", [1, 2, 3])
+def test_triple_loop_is_the_matrix_form_on_clips_shorter_than_the_tap_span(T):
+    """Integer operands, clips of 0 .. T frames: the plain definition and the matrix form agree exactly, also chunk by chunk (chunks
+    of 4 rows: a clip boundary inside a chunk, a tap across a chunk boundary)."""
+    B, cin, cout = 11, 3, 5
+    lengths = [b % (T + 1) for b in range(B)]
+    dz, x = R.integer_wgrad_case(B, T, lengths, cin, cout, T)
+    x = x[:, :, :cin]
+    loops = R.conv_wgrad_loops(torch.nan_to_num(dz).double(), torch.nan_to_num(x).double(), lengths)
+    fast, mag = R.conv_wgrad(dz, x, lengths)
+    assert torch.equal(loops, fast) and R.is_integer(fast) and fast.abs().max() > 0
+    taps_alive = [k for k in range(5) if (fast[:, :, k] != 0).any()]
+    assert taps_alive == list(range(max(0, 3 - T), min(5, 2 + T)))              # a 1-frame clip has its centre tap alone
+    val, _, _, _ = R.conv_wgrad_by_chunk(dz, x, lengths, 4)
+    for c in range(val.shape[0]):
+        only = torch.nan_to_num(dz).double().reshape(B * T, cout).clone()
+        only[:4 * c] = 0
+        only[4 * c + 4:] = 0
+        assert torch.equal(val[c], R.conv_wgrad_loops(only.reshape(B, T, cout), torch.nan_to_num(x).double(), lengths)), c
+
+
+def tape_chain_by_autograd(sd, x0, hs, pooled, lengths, g_enc, g_dur):
+    """The chain of backward_from_tape with every step's derivative taken by torch autograd of the forward operation (F.linear,
+    F.conv1d) at the tape's activations, fp64."""
+    L = R.n_layers_of(sd)
+    T = x0.shape[1]
+    mask = R.prefix_mask(lengths, T)[:, :, None]
+    n = torch.as_tensor(lengths).double().clamp(min=1)
+    out = {}
+    pooled_leaf = pooled.double().clone().requires_grad_(True)
+    proj = {k: sd[k].double().clone().requires_grad_(True) for k in R.param_names(L)[2 * L:]}
+    e_enc = F.linear(pooled_leaf, proj["proj_enc.weight"], proj["proj_enc.bias"])
+    e_dur = F.linear(pooled_leaf, proj["proj_dur.weight"], proj["proj_dur.bias"])
+    ((e_enc * g_enc.double()).sum() + (e_dur * g_dur.double()).sum()).backward()
+    out.update({k: v.grad for k, v in proj.items()})
+    dz = pooled_leaf.grad[:, None, :] / n[:, None, None] * (hs[L - 1] > 0) * mask               # the mean pool, the ReLU, the mask
+    for l in range(L - 1, -1, -1):
+        xin = (hs[l - 1] if l else x0).double().clone().requires_grad_(True)
+        w = sd[f"convs.{l}.weight"].double().clone().requires_grad_(True)
+        b = sd[f"convs.{l}.bias"].double().clone().requires_grad_(True)
+        (F.conv1d(xin.transpose(1, 2), w, b, padding=2).transpose(1, 2) * dz).sum().backward()
+        out[f"convs.{l}.weight"], out[f"convs.{l}.bias"] = w.grad, b.grad
+        if l:
+            dz = xin.grad * (hs[l - 1] > 0) * mask
+    return out
+
+
+@pytest.mark.parametrize("cfg,B,T,lengths", [R.TAPE_CASES["tiny"], ((100, 24, 4, 96), 5, 40, [32, 0, 1, 16, 2])], ids=["tiny", "four-layers"])
+def test_backward_from_an_integer_tape_is_integer_and_autograd_exactly(cfg, B, T, lengths):
+    """The restatement the exact GPU cases of the whole backward are held to: on a hand-written integer tape every gradient is an
+    integer, equal to step-by-step autograd with no tolerance (the GPU's tiny case itself, and four layers at a small size)."""
+    sd, x0, hs, pooled, g_enc, g_dur = R.integer_tape_case(cfg, B, T, lengths, 5)
+    m = R.prefix_mask(lengths, T, torch.float32)[:, :, None]
+    assert all(set(v.unique().tolist()) <= {-1.0, 0.0, 1.0} for v in sd.values())
+    assert 0.2 < (sd["convs.1.weight"] != 0).float().mean() < 0.3
+    assert torch.equal(x0, x0 * m) and x0.abs().max() == 2 and all(torch.equal(h, h * m) and h.min() == 0 for h in hs)
+    assert all(0.4 < (h[m.expand_as(h) > 0] == 0).float().mean() < 0.6 for h in hs) and pooled.min() >= 0
+    sums = R.tape_abs_sums(sd, x0, hs, pooled, lengths, g_enc, g_dur)
+    assert len(sums) == 4 + 1 + 2 * cfg[2] + cfg[2] - 1
+    assert R.fp32_is_exact_on(sums, *sd.values(), x0, *hs, pooled, g_enc, g_dur), sums
+    got, _ = R.backward_from_tape(sd, x0, hs, pooled, lengths, g_enc, g_dur)
+    want = tape_chain_by_autograd(sd, x0, hs, pooled, lengths, g_enc, g_dur)
+    for k in R.param_names(cfg[2]):
+        assert R.is_integer(got[k]) and got[k].abs().max() > 0 and got[k].abs().max() <= sums[k], k
+        assert torch.equal(got[k], want[k]), k
+
+
+def test_the_gpu_tape_cases_are_exact_in_fp32():
+    for name, (cfg, B, T, lengths) in R.TAPE_CASES.items():
+        assert B * T == 4800 and R.chunk_rows(B, T) == 512 and 0 in lengths and 2 in lengths
+        sd, x0, hs, pooled, g_enc, g_dur = R.integer_tape_case(cfg, B, T, lengths, 5)
+        sums = R.tape_abs_sums(sd, x0, hs, pooled, lengths, g_enc, g_dur)
+        assert R.fp32_is_exact_on(sums, *sd.values(), x0, *hs, pooled, g_enc, g_dur), (name, sums)
+
+
 @pytest.mark.parametrize("cin,cout,lengths,T", [(7, 5, [9, 0, 1, 2, 4], 9), (4, 4, [3], 3)])
 def test_triple_loop_is_autograd_of_conv1d(cin, cout, lengths, T):
     """The plain definition, its matrix form, and autograd of F.conv1d on the masked input agree (fp64)."""
