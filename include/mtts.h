@@ -1585,6 +1585,7 @@ int64_t mtts_spk_grad_weights_bytes(mtts_ctx* ctx);
 int mtts_spk_grad_upload_weights(mtts_ctx* ctx, void* d_buf, int64_t bytes);
 int64_t mtts_spk_grad_workspace_bytes(mtts_ctx* ctx, int B, int Tx, int Tm);
 int64_t mtts_spk_grad_tape_offset(mtts_ctx* ctx, int B, int Tx, int Tm, int which);      /* byte offset in d_ws of 0 mu_x [B,F,Tx], 1 logw [B,Tx], 2 x_mask [B,Tx] */
+int64_t mtts_spk_grad_rows_offset(mtts_ctx* ctx, int B, int Tx, int Tm);                  /* ... of the encoder's output rows [B*Tx, enc_channels + spk_emb_dim] that proj_m and the predictor read */
 int mtts_spk_grad(mtts_ctx* ctx, const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur,
                   const float* d_y_fine, const int64_t* d_y_fine_lengths, const int32_t* d_durations_in, float delta_prior,
                   float delta_dur, int B, int Tx, int Tm, float* d_g_enc, float* d_g_dur, float* d_prior_sum, float* d_dur_sum,
@@ -1660,6 +1661,80 @@ int mtts_grad_gate(float* d_g, int ldg, int M, int C, int mode, const float* d_r
                    void* stream);
 int mtts_token_sums(const float* d_src, int ld, int col0, int C, int B, int T, const int64_t* d_len, const int32_t* d_verdict,
                     float* d_dst, int ldd, int dcol0, int accumulate, void* stream);
+
+/* ---------------------------------------------------------------- duration-predictor training (parameter gradients) */
+
+/* The gradient of the duration Huber sum with respect to every parameter of the duration predictor (encoder.proj_w.*), everything else
+ * frozen.  In the reference logw = proj_w(x.detach(), x_mask, e_dur) (text_encoder.py:404) and the duration loss (matcha_tts.py:117,128)
+ * is the only loss that reaches those tensors, so this is the reference's gradient for them -- the dropout-free (eval) one: the
+ * reference trains the predictor with p_dropout, the same deviation as mtts_spk_grad's.
+ *
+ * Parameters: ONE FLAT fp32 vector of mtts_dp_param_count(ctx) floats, the keys below encoder.proj_w. in state-dict order --
+ * spk_proj.weight [2F, Sd], spk_proj.bias [2F], then per layer i conv_layers.i.weight [F, Cin, 5], conv_layers.i.bias [F],
+ * norm_layers.i.gamma [F], norm_layers.i.beta [F] (Cin = enc_channels + spk_emb_dim for i = 0, else F), then proj.weight [F],
+ * proj.bias [1]; mtts_dp_param_offset(ctx, "conv_layers.1.weight") is a tensor's first float.  Neither needs a device.
+ *
+ * Training component: the predictor's forward panels, LayerNorm affines, output projection and the transposed, tap-reversed panels of
+ * the walk back, packed on the host from the flat vector (h_params; NULL: from the tensors registered with mtts_set_tensor) and copied
+ * into d_buf (mtts_dp_train_weights_bytes(ctx) bytes, 2.5 MB at the production size; the layout depends on the configuration
+ * alone).  The copy is a blocking one on the default stream: a call that still reads d_buf on another stream is NOT waited for --
+ * drain that stream first (the Python mirror does).  mtts_dp_train_upload is what a training step calls after every optimiser update: it touches neither the model's weight
+ * image nor the backward panels of mtts_spk_grad.  mtts_dp_train_pack writes the same bytes to host memory instead.  Native fp32 MFMA
+ * (arithmetic 0) whatever the context's arithmetic is, for mtts_spk_grad's reason.
+ *
+ * mtts_dp_grad: d_x .. d_e_dur as for mtts_text_encoder_forward; d_durations int32 [B, Tx], required (this entry runs no alignment);
+ *   d_train_buf the uploaded component; d_grad [mtts_dp_param_count], every element written; d_g_dur [B, spk_emb_dim] or NULL (the
+ *   gradient with respect to the e_dur rows, per utterance, as mtts_spk_grad's); d_dur_sum [B] the per-utterance Huber sums;
+ *   d_logw [B, Tx] or NULL.
+ *   Forward: the prenet and encoder layers run from the context's image in the context's arithmetic (the taped forward's functions: the
+ *   rows the predictor reads equal mtts_text_encoder_forward's bit for bit; proj_m is not run); the predictor runs from d_train_buf in
+ *   native fp32 with every layer's rows kept.  Its logw is therefore NOT bit-equal to mtts_text_encoder_forward's under the default
+ *   split arithmetic, by design.
+ *   Backward: seed[r] = clamp(logw - log(2 + dur), +-delta_dur) on x < len_b (mtts_spk_grad's), the walk back of mtts_spk_grad with the
+ *   panels of d_train_buf, and inside it the parameter reductions.  d_grad is the gradient of the SUM over the batch of the
+ *   per-utterance sums; the reference's loss gradient is d_grad / sum_b len_b, which the caller forms.
+ *   Summation orders.  M = B Tx rows r = b Tx + x are cut into chunks of R = mtts_conv_wgrad_chunk_rows(B, Tx) rows; rows with
+ *   x >= len_b take no part (a select).
+ *     conv_layers.i.weight / .bias: mtts_conv_wgrad with dz = the gradient at the convolution's output behind the ReLU gate, the input
+ *       = the layer's taped input (the encoder's rows for i = 0, the previous FiLM output otherwise), lengths = x_lengths;
+ *     norm_layers.i.gamma[c] = sum_r dy[r,c] gf_b[c] xhat[r,c], .beta[c] = sum_r dy[r,c] gf_b[c] (dy the gradient at the FiLM output,
+ *       gf_b utterance b's FiLM gamma, xhat the normalised row, its mean and rstd recomputed from the taped pre-norm row by lane-strided
+ *       sums and a wave butterfly): per chunk four phases p take the rows r0 + p, r0 + p + 4, ... in row order, each term (dy gf) xhat
+ *       rounded product by product before it is added, the phases combined as ((p0 + p1) + p2) + p3, the chunks added in chunk order;
+ *     proj.weight[c] = sum_r seed[r] h[r,c], proj.bias = sum_r seed[r] (h the last FiLM output): the same phases and chunks;
+ *     spk_proj.weight[o,j] = sum_b DFILM[b,o] e_dur[b,j], spk_proj.bias[o] = sum_b DFILM[b,o], in batch order from zero, DFILM [B, 2F]
+ *       the per-utterance (d gamma_b | d beta_b) that the walk accumulates over the layers (last layer first) with mtts_token_sums.
+ *   Stream-ordered, no allocation, no floating-point atomics: two calls give the same bits.  An utterance with a length outside
+ *   [1, Tx] or a negative duration adds exact zeros to every sum and gets a zero d_dur_sum and d_g_dur row; the others are unaffected,
+ *   and mtts_dp_grad_status(d_ws, stream) -- the one entry here that waits for the stream -- names it.  Context guard and range-guard
+ *   word (first word of d_ws) as the neighbouring entries.  Returns -1 (mtts_last_error) for null pointers, B < 1, Tx > 1024,
+ *   delta_dur <= 0, dp_kernel != 5, a small workspace (mtts_dp_grad_workspace_bytes), a d_train_buf that was not uploaded.
+ *   mtts_dp_grad_tape_offset: byte offset in d_ws of which = 0 the frozen encoder's output rows [B*Tx, enc_channels + spk_emb_dim],
+ *   1 the logw [B, Tx] of the latest call. */
+int64_t mtts_dp_param_count(mtts_ctx* ctx);
+int64_t mtts_dp_param_offset(mtts_ctx* ctx, const char* key);
+int64_t mtts_dp_train_weights_bytes(mtts_ctx* ctx);
+int mtts_dp_train_pack(mtts_ctx* ctx, const float* h_params, void* h_out, int64_t bytes);
+int mtts_dp_train_upload(mtts_ctx* ctx, const float* h_params, void* d_buf, int64_t bytes);
+int64_t mtts_dp_grad_workspace_bytes(mtts_ctx* ctx, int B, int Tx);
+int64_t mtts_dp_grad_tape_offset(mtts_ctx* ctx, int B, int Tx, int which);
+int mtts_dp_grad(mtts_ctx* ctx, const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur,
+                 const int32_t* d_durations, float delta_dur, int B, int Tx, void* d_train_buf, float* d_grad, float* d_g_dur,
+                 float* d_dur_sum, float* d_logw, void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_dp_grad_status(const void* d_ws, void* stream);
+
+/* Kernel-level entries of mtts_dp_grad's three parameter reductions on given buffers (no context), in the orders stated above.
+ * mtts_ln_film_wgrad: d_x the pre-norm rows and d_dy the gradient at the FiLM output [B*T, C], d_film [B, 2C] (gamma | beta),
+ *   d_lengths int64 [B] or NULL -> d_dgamma, d_dbeta [C].
+ * mtts_rows_wgrad: d_seed [B*T], d_h [B*T, C] -> d_dw [C] = sum_r seed[r] h[r, c], d_db [1] = sum_r seed[r].
+ * Both leave the chunks' partial results in d_ws (mtts_dp_unit_workspace_bytes(B, T, C) bytes).
+ * mtts_outer_batch_sum: d_g [B, O], d_e [B, J] -> d_dw [O, J] = sum_b g[b, o] e[b, j], d_db [O] = sum_b g[b, o], batch order. */
+int64_t mtts_dp_unit_workspace_bytes(int B, int T, int C);
+int mtts_ln_film_wgrad(const float* d_x, const float* d_dy, const float* d_film, const int64_t* d_lengths, int B, int T, int C, float eps,
+                       float* d_dgamma, float* d_dbeta, void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_rows_wgrad(const float* d_seed, const float* d_h, const int64_t* d_lengths, int B, int T, int C, float* d_dw, float* d_db,
+                    void* d_ws, int64_t ws_bytes, void* stream);
+int mtts_outer_batch_sum(const float* d_g, const float* d_e, int B, int O, int J, float* d_dw, float* d_db, void* stream);
 
 /* ---------------------------------------------------------------- arithmetic and its range guard */
 

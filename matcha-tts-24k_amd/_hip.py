@@ -19,7 +19,7 @@ from .hparams import PathHParams
 HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 LIB = Path(os.environ["MTTS_HIP_LIB"]) if os.environ.get("MTTS_HIP_LIB") else HERE / "libmtts_hip.so"   # override: A/B of two builds
-SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "resample.hip", "audio_codec.hip", "flac.hip", "flac_decode.hip", "corpus.hip", "pitch.hip", "wave_join.hip", "timing.hip", "loudness.hip", "style_encoder.hip", "style_grad.hip", "mas.hip", "score.hip", "spk_grad.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
+SOURCES = ["gemm_f32.hip", "attention_f32.hip", "gemm_p16.hip", "tblock_chain.hip", "tblock_chain_h16.hip", "resnet_conv.hip", "norm_glue.hip", "vocos.hip", "waveform.hip", "mel_frontend.hip", "resample.hip", "audio_codec.hip", "flac.hip", "flac_decode.hip", "corpus.hip", "pitch.hip", "wave_join.hip", "timing.hip", "loudness.hip", "style_encoder.hip", "style_grad.hip", "dp_grad.hip", "mas.hip", "score.hip", "spk_grad.hip", "model.hip", "pack.hip", "decoder.hip", "encoder.hip", "unit_entries.hip"]
 HEADERS = [CSRC / "kernels.h", CSRC / "device_utils.h", CSRC / "model.h", CSRC / "host.h", HERE.parent / "include" / "mtts.h"]
 SOLVERS = {"euler": 0, "midpoint": 1, "rk4": 2}
 
@@ -388,8 +388,22 @@ def load() -> C.CDLL:
         "mtts_spk_grad_upload_weights": (i32, [vp, vp, i64]),
         "mtts_spk_grad_workspace_bytes": (i64, [vp, i32, i32, i32]),
         "mtts_spk_grad_tape_offset": (i64, [vp, i32, i32, i32, i32]),
+        "mtts_spk_grad_rows_offset": (i64, [vp, i32, i32, i32]),
         "mtts_spk_grad": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
         "mtts_spk_grad_status": (i32, [vp, vp]),
+        "mtts_dp_param_count": (i64, [vp]),
+        "mtts_dp_param_offset": (i64, [vp, C.c_char_p]),
+        "mtts_dp_train_weights_bytes": (i64, [vp]),
+        "mtts_dp_train_pack": (i32, [vp, vp, vp, i64]),
+        "mtts_dp_train_upload": (i32, [vp, vp, vp, i64]),
+        "mtts_dp_grad_workspace_bytes": (i64, [vp, i32, i32]),
+        "mtts_dp_grad_tape_offset": (i64, [vp, i32, i32, i32]),
+        "mtts_dp_grad": (i32, [vp, vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
+        "mtts_dp_grad_status": (i32, [vp, vp]),
+        "mtts_dp_unit_workspace_bytes": (i64, [i32, i32, i32]),
+        "mtts_ln_film_wgrad": (i32, [vp, vp, vp, vp, i32, i32, i32, f32, vp, vp, vp, i64, vp]),
+        "mtts_rows_wgrad": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, i64, vp]),
+        "mtts_outer_batch_sum": (i32, [vp, vp, i32, i32, i32, vp, vp, vp]),
         "mtts_spk_grad_match_workspace_bytes": (i64, [vp, i32, i32]),
         "mtts_spk_grad_match": (i32, [vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]),
         "mtts_spk_grad_match_status": (i32, [vp, vp]),
@@ -641,6 +655,8 @@ class HipModel:
         self._ws = Workspaces()      # the latest buffer per kind holds that call's header: range flag, pair time-out, verdict
         self._grad_weights: Optional[torch.Tensor] = None   # backward panels of speaker_grad, uploaded on first use ...
         self._grad_generation = -1                          # ... for this weight generation
+        self._dp_tensors: Dict[str, torch.Tensor] = {}      # the duration predictor's tensors as loaded (host fp32): dp_params()
+        self._dp_buf: Optional[torch.Tensor] = None         # its training component on the device (dp_train_buffer)
 
     def __del__(self):
         try:
@@ -674,7 +690,9 @@ class HipModel:
             if k in ("mel_mean", "mel_std") or "rope." in k:
                 continue
             self._set(k, v)
-            if k.endswith("ff.net.0.alpha"):     # SnakeBeta parameters in the reference's own fp32 ops (transformer.py:68-75)
+            if k.startswith(self.DP_PREFIX):
+                self._dp_tensors[k] = v.detach().to("cpu", torch.float32).clone()
+            if k.endswith("ff.net.0.alpha"):    # SnakeBeta parameters in the reference's own fp32 ops (transformer.py:68-75)
                 self._set(k + "_exp", torch.exp(v.detach().float().cpu()))
             elif k.endswith("ff.net.0.beta"):
                 self._set(k[:-4] + "inv_beta", 1.0 / (torch.exp(v.detach().float().cpu()) + 0.000000001))
@@ -1064,6 +1082,9 @@ class HipModel:
                 off = size(self.lib.mtts_spk_grad_tape_offset(self.ctx, B, Tx, Tm, which))
                 count = B * Tx * (F if which == 0 else 1)
                 out[name] = ws[off:off + 4 * count].view(torch.float32).view(shape)
+            Hd = self.hp.encoder.n_channels + Sd
+            off = size(self.lib.mtts_spk_grad_rows_offset(self.ctx, B, Tx, Tm))
+            out["enc_rows"] = ws[off:off + 4 * B * Tx * Hd].view(torch.float32).view(B * Tx, Hd)
         return out
 
     def spk_grad_status(self) -> None:
@@ -1109,6 +1130,114 @@ class HipModel:
         if check_lengths:
             self._status("spk_grad_match", self.lib.mtts_spk_grad_match_status)
         return out
+
+    # ------------------------------------------------------------------ duration-predictor training (csrc/dp_grad.hip)
+    DP_PREFIX = "encoder.proj_w."
+
+    def dp_layout(self):
+        """``(key, offset, shape)`` of every duration-predictor parameter inside the flat vector, in state-dict order, keys without
+        the ``encoder.proj_w.`` prefix (mtts_dp_param_offset).  Needs no device."""
+        e, Sd = self.hp.encoder, self.hp.spk_emb_dim
+        F, k, Hd = e.dp_filter_channels, e.dp_kernel_size, e.n_channels + Sd
+        shapes = [("spk_proj.weight", (2 * F, Sd)), ("spk_proj.bias", (2 * F,))]
+        for i in range(e.dp_n_layers):
+            shapes += [(f"conv_layers.{i}.weight", (F, Hd if i == 0 else F, k)), (f"conv_layers.{i}.bias", (F,)),
+                       (f"norm_layers.{i}.gamma", (F,)), (f"norm_layers.{i}.beta", (F,))]
+        shapes += [("proj.weight", (1, F, 1)), ("proj.bias", (1,))]
+        return [(key, size(self.lib.mtts_dp_param_offset(self.ctx, key.encode())), shape) for key, shape in shapes]
+
+    def dp_param_count(self) -> int:
+        return size(self.lib.mtts_dp_param_count(self.ctx))
+
+    def dp_params(self):
+        """The duration predictor of the loaded weights as ``(flat, layout)``: one flat fp32 host vector of ``dp_param_count()`` floats
+        and ``dp_layout()``."""
+        if not self._dp_tensors:
+            raise RuntimeError("mtts: no weights loaded (load_state_dict)")
+        layout = self.dp_layout()
+        flat = torch.empty(self.dp_param_count(), dtype=torch.float32)
+        for key, off, shape in layout:
+            t = self._dp_tensors[self.DP_PREFIX + key]
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{self.DP_PREFIX + key} has shape {tuple(t.shape)}, expected {shape}")
+            flat[off:off + t.numel()] = t.reshape(-1)
+        return flat, layout
+
+    def dp_train_buffer(self, params=None) -> torch.Tensor:
+        """Pack the predictor's training component from the flat vector ``params`` (host or device; None: the registered tensors)
+        and upload it into this model's training buffer (mtts_dp_train_upload): 2.5 MB at the production size, one host round trip, nothing else is
+        repacked.  Returns the device buffer ``dp_grad`` takes."""
+        nb = size(self.lib.mtts_dp_train_weights_bytes(self.ctx))
+        if self._dp_buf is None or self._dp_buf.numel() != nb or self._dp_buf.device != self.device:
+            self._dp_buf = torch.empty(nb, dtype=torch.uint8, device=self.device)
+        torch.cuda.current_stream().synchronize()     # an earlier dp_grad on this stream may still read the buffer: the copy waits for nothing
+        host = None
+        if params is not None:
+            host = np.ascontiguousarray(params.detach().to("cpu", torch.float32).numpy().reshape(-1))
+            if host.size != self.dp_param_count():
+                raise ValueError(f"params must hold {self.dp_param_count()} floats, got {host.size}")
+        check(self.lib.mtts_dp_train_upload(self.ctx, None if host is None else host.ctypes.data, self._dp_buf.data_ptr(), nb))
+        return self._dp_buf
+
+    def dp_grad(self, x, x_lengths, e_enc, e_dur, durations, delta_dur: float, train_buf: torch.Tensor, check_lengths: bool = True,
+                return_tape: bool = False):
+        """Gradient of the batch's duration Huber sum with respect to every parameter of the duration predictor packed in
+        ``train_buf`` (mtts_dp_grad): frozen encoder forward, predictor forward from ``train_buf`` in native fp32, the walk back and the
+        parameter reductions.  Returns a dict: ``grad`` [dp_param_count] (of the SUM over the batch), ``g_dur`` [B, spk_emb_dim],
+        ``dur_sum`` [B], ``logw`` [B, 1, Tx] and, with ``return_tape``, ``enc_rows`` [B*Tx, enc_channels + spk_emb_dim], a view of
+        this call's workspace.  ``check_lengths``: wait for the stream and raise ``ValueError`` naming a refused utterance."""
+        B, Tx = x.shape
+        dev = x.device
+        x = x.detach().to(torch.int64).contiguous()
+        xl = x_lengths.detach().to(device=dev, dtype=torch.int64).contiguous()
+        e_enc, e_dur = self._f32(e_enc), self._f32(e_dur)
+        if e_enc.shape[0] != B:
+            e_enc, e_dur = e_enc.expand(B, -1).contiguous(), e_dur.expand(B, -1).contiguous()
+        Sd = self.hp.spk_emb_dim
+        if xl.shape != (B,):
+            raise ValueError("x_lengths needs one entry per utterance")
+        if e_enc.shape != (B, Sd) or e_dur.shape != (B, Sd):
+            raise ValueError(f"speaker rows must be [{B}, {Sd}]")
+        dur = durations.detach().to(device=dev, dtype=torch.int32).contiguous()
+        if dur.shape != (B, Tx):
+            raise ValueError(f"durations must have shape ({B}, {Tx}), got {tuple(dur.shape)}")
+        ws = self._ws.get("dp_grad", self.lib.mtts_dp_grad_workspace_bytes(self.ctx, B, Tx), self.device)
+        grad = torch.empty(self.dp_param_count(), dtype=torch.float32, device=dev)
+        g_dur = torch.empty(B, Sd, dtype=torch.float32, device=dev)
+        dsum = torch.empty(B, dtype=torch.float32, device=dev)
+        logw = torch.empty(B, 1, Tx, dtype=torch.float32, device=dev)
+        check(self.lib.mtts_dp_grad(self.ctx, ptr(x), ptr(xl), ptr(e_enc), ptr(e_dur), ptr(dur), float(delta_dur), B, Tx, train_buf.data_ptr(),
+                                    ptr(grad), ptr(g_dur), ptr(dsum), ptr(logw), ws.data_ptr(), ws.numel(), stream_ptr()))
+        if check_lengths:
+            self.dp_grad_status()
+        out = {"grad": grad, "g_dur": g_dur, "dur_sum": dsum, "logw": logw}
+        if return_tape:
+            Hd = self.hp.encoder.n_channels + Sd
+            off = size(self.lib.mtts_dp_grad_tape_offset(self.ctx, B, Tx, 0))
+            out["enc_rows"] = ws[off:off + 4 * B * Tx * Hd].view(torch.float32).view(B * Tx, Hd)
+        return out
+
+    def dp_grad_status(self) -> None:
+        """Wait for this stream's latest ``dp_grad`` call and raise ``ValueError`` naming the first utterance the device refused
+        (mtts_dp_grad_status)."""
+        self._status("dp_grad", self.lib.mtts_dp_grad_status)
+
+    def update_tensors(self, tensors: Dict[str, torch.Tensor]) -> None:
+        """Replace some registered tensors (full state-dict keys), then repack and upload the weight image ONCE.  ``generation`` is
+        bumped -- captured graphs and the backward panels of ``speaker_grad`` are rebuilt on their next use -- and the image no longer
+        counts as read from a packed-image cache."""
+        if self.weights is None:
+            raise RuntimeError("mtts: no weights loaded (load_state_dict)")
+        for k, v in tensors.items():
+            self._set(k, v)
+            if k.startswith(self.DP_PREFIX):
+                self._dp_tensors[k] = v.detach().to("cpu", torch.float32).clone()
+        nbytes = size(self.lib.mtts_weights_bytes(self.ctx))
+        self.weights = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        check(self.lib.mtts_upload_weights(self.ctx, self.weights.data_ptr(), nbytes))
+        self.cache_hit = False
+        self.generation += 1
+        self._ws.clear()
 
     def fold_rows(self, y_max: int, align: int) -> int:
         """Rows per utterance the folded estimator needs for valid lengths up to y_max (mtts_fold_rows)."""

@@ -91,6 +91,16 @@ struct SpkGradW {
     Vec dp_proj;                   // the duration predictor's output projection [dp_filter] (one output channel: an outer product)
 };
 
+// The duration predictor's training component (dp_grad.hip): its forward panels, LayerNorm affines and output projection, and the
+// transposed, tap-reversed panels of its walk back, packed from one flat parameter vector into a buffer of their own (mtts_ctx::dptrain).
+struct DpTrainW {
+    Panel film, filmT;             // spk_proj and its transpose
+    std::vector<Panel> conv, convT;   // convT[0] is empty: the first layer reads x.detach()
+    std::vector<Vec> gamma, beta;
+    Vec proj_w, proj_b;            // [dp_filter], [1]
+    Panel proj;                    // the same projection as a GEMM panel (the forward)
+};
+
 struct StyleW {
     std::vector<Panel> convs;      // Conv1d(k5, pad 2) of each layer
     Vec proj_w, proj_b;            // [2 E][hidden] = proj_enc rows then proj_dur rows, [2 E]
@@ -184,6 +194,10 @@ struct mtts_ctx : mtts::Component {
     // speaker-row gradient (spk_grad.hip): the backward panels' own image (native fp32 MFMA: gemm_terms 0) and their offsets
     mtts::Component grad;
     mtts::SpkGradW gradw;
+    // duration-predictor training (dp_grad.hip): the predictor's own small component (native fp32 MFMA), repacked from the flat
+    // parameter vector every step; touches neither the image above nor `grad`
+    mtts::Component dptrain;
+    mtts::DpTrainW dptw;
 };
 
 // Vocos-24k head: its own weight image and context (the reference loads it as a separate object,

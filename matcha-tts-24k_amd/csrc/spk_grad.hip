@@ -31,17 +31,14 @@
 // Every sum has a FIXED ORDER and there are no floating-point atomics (the rule of score.hip and mas.hip): a thread's serial run in
 // key / query / frame / token order, a wave butterfly, four phases combined in order.  Partitions depend on absolute token indices
 // only, so an utterance's gradient does not depend on its batch or on the padded shapes.
-#include "host.h"
+#include "spk_grad.h"
 #include "device_utils.h"
 
 #include <string>
 
 namespace mtts {
 
-constexpr int SG_MAX_TX = 1024;           // tokens, as mtts_mas / score.hip (cumulative durations in LDS)
-constexpr size_t SG_SCORE_OFF = 256;      // the score workspace (status header first) inside this call's workspace: plan_spk_grad
-                                          // carves it right behind the 256-byte call header; mtts_spk_grad refuses to run otherwise
-constexpr int SG_MAX_LAYERS = 16;         // encoder / duration-predictor layers the per-layer tape has room for
+// (SG_MAX_TX, SG_SCORE_OFF, SG_MAX_LAYERS, LnBwdArgs, SgBufs and SgCall: spk_grad.h, shared with dp_grad.hip)
 
 __device__ __forceinline__ float sg_wave_sum(float v) {
 #pragma unroll
@@ -57,19 +54,6 @@ __device__ __forceinline__ float sg_clamp(float d, float delta) { return fminf(f
 
 // ---------------------------------------------------------------------------------------------- channel LayerNorm backward
 // forward (norm_glue.hip layernorm_kernel):  xh = (x - mean) rstd;  a = xh gamma + beta;  [a = silu(a)];  [y = a fg_b + fb_b];  [y *= mask]
-struct LnBwdArgs {
-    const float* x = nullptr; int ldx = 0;        // the LayerNorm's input rows
-    const float* dy = nullptr; int lddy = 0;      // upstream gradient
-    float* dx = nullptr; int lddx = 0;
-    int M = 0, C = 0, T = 1;
-    const float* gamma = nullptr; const float* beta = nullptr;   // null: 1 / 0
-    float eps = 1e-5f;
-    int act = ACT_NONE;                           // ACT_SILU: the forward applied SiLU behind the affine
-    const float* film = nullptr;                  // [B][2C] gamma | beta of the FiLM
-    float* film_prod = nullptr;                   // [M][C]: dy * a, whose token sum is d gamma_b (d beta_b is the token sum of dy)
-    const float* mask = nullptr;                  // [M]: rows with 0 get a zero gradient
-    int gate = ACT_NONE;                          // ACT_RELU: x is a ReLU output, dx *= (x > 0)
-};
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdArgs p) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
@@ -118,7 +102,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const LnBwdArgs p) {
         out[c] = d;
     }
 }
-static hipError_t launch_ln_bwd(const LnBwdArgs& a, hipStream_t s) {
+hipError_t launch_ln_bwd(const LnBwdArgs& a, hipStream_t s) {
     if (!a.x || !a.dy || !a.dx || a.M <= 0 || a.C <= 0 || a.T <= 0 || a.ldx < a.C || a.lddy < a.C || a.lddx < a.C) return hipErrorInvalidValue;
     if (a.film_prod && !a.film) return hipErrorInvalidValue;
     hipLaunchKernelGGL(ln_bwd_kernel, dim3((a.M + 3) / 4), dim3(256), 0, s, a);
@@ -175,8 +159,8 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ s
         *d = accumulate ? *d + v : v;
     }
 }
-static hipError_t launch_colsum(const float* src, int ld, int col0, int C, int B, int T, const int64_t* len, const int32_t* verdict, float* dst,
-                                int ldd, int dcol0, int accumulate, hipStream_t s) {
+hipError_t launch_colsum(const float* src, int ld, int col0, int C, int B, int T, const int64_t* len, const int32_t* verdict, float* dst,
+                         int ldd, int dcol0, int accumulate, hipStream_t s) {
     if (!src || !dst || B <= 0 || T <= 0 || C <= 0 || ld < col0 + C || ldd < dcol0 + C) return hipErrorInvalidValue;
     hipLaunchKernelGGL(colsum_kernel, dim3((C + 63) / 64, B), dim3(256), 0, s, src, ld, col0, C, T, len, verdict, dst, ldd, dcol0, accumulate);
     return hipGetLastError();
@@ -520,7 +504,7 @@ static hipError_t launch_attn_bwd(const AttnBwdArgs& a, hipStream_t s) {
 // ---------------------------------------------------------------------------------------------- backward panels (host)
 // The transposed weight of a Linear / Conv1d(k, pad k / 2) in torch layout: w [N][C][k] -> wt [C][N][k] with the taps reversed, so
 // that the data gradient is the same centred-tap GEMM with in / out channels swapped.  Cp >= C pads the NEW input channels (zeros).
-static std::vector<float> transposed(const std::vector<float>& w, int N, int C, int k, int Np = 0) {
+std::vector<float> transposed(const float* w, int N, int C, int k, int Np) {
     Np = Np ? Np : N;
     std::vector<float> t((size_t)C * Np * k, 0.f);
     for (int n = 0; n < N; ++n)
@@ -549,7 +533,7 @@ int pack_spk_grad(mtts_ctx* c) {
     auto tpanel = [&](const std::string& key, int N, int C, int k, int Np = 0) {
         const auto* w = raw(key, (size_t)N * C * k);
         if (!w) return Panel();
-        const std::vector<float> t = transposed(*w, N, C, k, Np);
+        const std::vector<float> t = transposed(w->data(), N, C, k, Np);
         return P.panel_from(t.data(), nullptr, k == 1 ? 0 : 1, C, Np ? Np : N, k);
     };
     auto S = [](const std::string& a, int i, const std::string& b) { return a + std::to_string(i) + b; };
@@ -585,15 +569,6 @@ int pack_spk_grad(mtts_ctx* c) {
 }
 
 // ---------------------------------------------------------------------------------------------- plan
-struct SgBufs {
-    float *X0, *P1, *P2, *Y, *PMpre, *PM, *MU, *FILM, *D1, *D2, *mu_x, *logw, *xm;
-    float *Hin[SG_MAX_LAYERS + 1], *QKV[SG_MAX_LAYERS], *ATT[SG_MAX_LAYERS], *S1[SG_MAX_LAYERS], *H1[SG_MAX_LAYERS], *F1[SG_MAX_LAYERS],
-        *S2[SG_MAX_LAYERS], *DY[SG_MAX_LAYERS];       // per layer (fixed arrays: no host allocation in the launch path)
-    float *GA, *GB, *GF, *GQKV, *GATT, *stats, *GMU, *GPM, *GDA, *GDB, *FPROD, *DFILM;
-    int32_t* dur;
-    void *score, *mas;
-    size_t score_bytes = 0, mas_bytes = 0, off_score = 0, off_mu_x = 0, off_logw = 0, off_xm = 0;
-};
 static void plan_spk_grad(const mtts_ctx* c, int B, int Tx, int Tm, WS& ws, SgBufs& e) {
     const mtts_config& g = c->cfg;
     const size_t M = (size_t)B * Tx;
@@ -613,6 +588,7 @@ static void plan_spk_grad(const mtts_ctx* c, int B, int Tx, int Tm, WS& ws, SgBu
     e.FILM = ws.f((size_t)B * 2 * F); e.D1 = ws.f(M * F); e.D2 = ws.f(M * F);
     const int L = std::min(g.enc_layers, SG_MAX_LAYERS), Ld = std::min(g.dp_layers, SG_MAX_LAYERS);      // (more is refused: sg_layers_ok)
     for (int l = 0; l <= L; ++l) e.Hin[l] = ws.f(M * Hd);
+    e.off_hout = ws.off - M * Hd * sizeof(float);
     for (int l = 0; l < L; ++l) {
         e.QKV[l] = ws.f(M * 3 * Hd); e.ATT[l] = ws.f(M * Hd); e.S1[l] = ws.f(M * Hd); e.H1[l] = ws.f(M * Hd);
         e.F1[l] = ws.f(M * g.enc_filter); e.S2[l] = ws.f(M * Hd);
@@ -682,57 +658,51 @@ int64_t mtts_spk_grad_tape_offset(mtts_ctx* c, int B, int Tx, int Tm, int which)
     return (int64_t)(which == 0 ? e.off_mu_x : which == 1 ? e.off_logw : e.off_xm);
 }
 
+// Byte offset inside the workspace of the encoder's output rows of the latest call's taped forward, [B Tx][enc_channels + spk_emb_dim]:
+// what proj_m and the duration predictor read (and what mtts_dp_grad's frozen part must reproduce bit for bit).
+int64_t mtts_spk_grad_rows_offset(mtts_ctx* c, int B, int Tx, int Tm) {
+    if (!c) { set_error("mtts_spk_grad_rows_offset: null context"); return -1; }
+    if (!sg_shape_ok("mtts_spk_grad_rows_offset", B, Tx, Tm) || !sg_layers_ok("mtts_spk_grad_rows_offset", c)) return -1;
+    WS ws(nullptr, 0);
+    SgBufs e;
+    plan_spk_grad(c, B, Tx, Tm, ws, e);
+    return (int64_t)e.off_hout;
+}
+
 }  // extern "C"
 
 // What the entries of this file share -- mtts_spk_grad (the fine-tuning losses) and mtts_spk_grad_match (the style-training losses):
 // the taped forward and the two walks back from seeded gradients, with the call's context, buffers and derived sizes.  The entries
 // differ in their seeds alone.
-namespace {
-struct SgCall {
-    mtts_ctx* c;
-    const SgBufs& e;
-    hipStream_t s;
-    int B, Tx;
-    const mtts_config& g;
-    const EncW& E;
-    const SpkGradW& GW;
-    const Component* G;
-    int nch, Sd, Hd, F, M, nf, dh, d_rope, ldm, L;
-    bool ffn_p16;
-    float* xm;
-    SgCall(mtts_ctx* ctx, const SgBufs& bufs, hipStream_t stream, int B_, int Tx_)
-        : c(ctx), e(bufs), s(stream), B(B_), Tx(Tx_), g(ctx->cfg), E(ctx->enc), GW(ctx->gradw), G(&ctx->grad) {
-        nch = g.enc_channels; Sd = g.spk_emb_dim; Hd = nch + Sd; F = g.dp_filter; M = B * Tx; nf = g.n_feats;
-        dh = Hd / g.enc_heads; d_rope = dh / 2; ldm = round_up(nf, 4); L = g.enc_layers;
-        ffn_p16 = c->sw.p16_on && c->gemm_terms == 2 && (g.enc_filter % 32) == 0;
-        xm = e.xm;
+namespace mtts {
+SgCall::SgCall(mtts_ctx* ctx, const SgBufs& bufs, hipStream_t stream, int B_, int Tx_)
+    : c(ctx), e(bufs), s(stream), B(B_), Tx(Tx_), g(ctx->cfg), E(ctx->enc), GW(ctx->gradw), G(&ctx->grad) {
+    nch = g.enc_channels; Sd = g.spk_emb_dim; Hd = nch + Sd; F = g.dp_filter; M = B * Tx; nf = g.n_feats;
+    dh = Hd / g.enc_heads; d_rope = dh / 2; ldm = round_up(nf, 4); L = g.enc_layers;
+    ffn_p16 = c->sw.p16_on && c->gemm_terms == 2 && (g.enc_filter % 32) == 0;
+    xm = e.xm;
+}
+int SgCall::ready(const char* who, const void* d_grad_buf) const {
+    if (!c->grad.packed || !c->grad.uploaded || c->grad.d_image != d_grad_buf) {
+        set_error(std::string(who) + ": backward panels not uploaded (mtts_spk_grad_upload_weights into d_grad_buf)");
+        return -1;
     }
-    // what every entry checks once its workspace is planned (`who` names it in the error texts)
-    int ready(const char* who, const void* d_grad_buf) const {
-        if (!c->grad.packed || !c->grad.uploaded || c->grad.d_image != d_grad_buf) {
-            set_error(std::string(who) + ": backward panels not uploaded (mtts_spk_grad_upload_weights into d_grad_buf)");
-            return -1;
-        }
-        RET_IF(check_ready(c));
-        if ((size_t)Tx * d_rope > (size_t)E.rope_cos.n) { set_error("Phonetic representation too long, exceeds RoPE cache size"); return -1; }
-        if (!attn_bwd_head_dim_ok(dh)) { set_error(std::string(who) + ": the encoder's head dim must be a multiple of 8 (<= 64)"); return -1; }
-        return 0;
-    }
-    int tgemm(const Panel& p, const float* a0, int lda, int c0, int ntaps, const float* res, int ldr, const float* out_mask, float* out,
-              int ldc, int rowsB, int rowsT) const {
-        GemmArgs a;
-        panel_args(G, p, a); rows_plain(a, rowsB, rowsT);
-        if (ntaps > 1) taps_centered(a, ntaps);
-        a.a0 = a0; a.lda0 = lda; a.c0 = c0; a.res = res; a.ldr = ldr; a.out_mask = out_mask; a.out = out; a.ldc = ldc;
-        return run_gemm(c, a, s);
-    }
-    int forward(const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur) const;
-    int walk_prior(const int64_t* d_x_lengths, const int32_t* verdict, float* d_g_enc) const;
-    int walk_dur(const int64_t* d_x_lengths, const int32_t* verdict, float* d_g_dur) const;
-};
+    RET_IF(check_ready(c));
+    if ((size_t)Tx * d_rope > (size_t)E.rope_cos.n) { set_error("Phonetic representation too long, exceeds RoPE cache size"); return -1; }
+    if (!attn_bwd_head_dim_ok(dh)) { set_error(std::string(who) + ": the encoder's head dim must be a multiple of 8 (<= 64)"); return -1; }
+    return 0;
+}
+int SgCall::tgemm(const Component* comp, const Panel& p, const float* a0, int lda, int c0, int ntaps, const float* res, int ldr,
+                  const float* out_mask, float* out, int ldc, int rowsB, int rowsT) const {
+    GemmArgs a;
+    panel_args(comp, p, a); rows_plain(a, rowsB, rowsT);
+    if (ntaps > 1) taps_centered(a, ntaps);
+    a.a0 = a0; a.lda0 = lda; a.c0 = c0; a.res = res; a.ldr = ldr; a.out_mask = out_mask; a.out = out; a.ldc = ldc;
+    return run_gemm(c, a, s);
+}
 
 // ================================================================ taped forward: encoder.hip's launches, buffers per layer
-int SgCall::forward(const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur) const {
+int SgCall::forward_encoder(const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc) const {
     LAUNCH(c, 2, 0, s, launch_seq_mask(d_x_lengths, B, Tx, xm, s));
     LAUNCH(c, 2, 0, s, launch_embedding(d_x, W(c, E.emb.off), M, nch, sqrtf((float)nch), xm, e.X0, nch, s));
     const float* cur = e.X0;
@@ -791,6 +761,10 @@ int SgCall::forward(const int64_t* d_x, const int64_t* d_x_lengths, const float*
         n2.gamma = W(c, E.n2_g[l].off); n2.beta = W(c, E.n2_b[l].off);
         LAUNCH(c, 2, 0, s, launch_layernorm(n2, s));
     }
+    return 0;
+}
+int SgCall::forward(const int64_t* d_x, const int64_t* d_x_lengths, const float* d_e_enc, const float* d_e_dur) const {
+    RET_IF(forward_encoder(d_x, d_x_lengths, d_e_enc));
     const float* Hout = e.Hin[L];
     {
         GemmArgs a;
@@ -864,22 +838,25 @@ int SgCall::walk_prior(const int64_t* d_x_lengths, const int32_t* verdict, float
 }
 
 // ================================================================ backward: d sum / d (duration predictor's last rows) (e.GDA, seeded) -> e_dur
-int SgCall::walk_dur(const int64_t* d_x_lengths, const int32_t* verdict, float* d_g_dur) const {
+int SgCall::walk_dur(const int64_t* d_x_lengths, const int32_t* verdict, float* d_g_dur, const DurTrain* train) const {
     bool first = true;
+    const Component* PC = train ? train->comp : G;
     for (int i = g.dp_layers - 1; i >= 0; --i) {
         LAUNCH(c, 2, 0, s, launch_colsum(e.GDA, F, 0, F, B, Tx, d_x_lengths, verdict, e.DFILM, 2 * F, F, first ? 0 : 1, s));
         LnBwdArgs ln;
         ln.x = e.DY[i]; ln.ldx = F; ln.dy = e.GDA; ln.lddy = F; ln.dx = e.GDB; ln.lddx = F; ln.M = M; ln.C = F; ln.T = Tx;
-        ln.gamma = W(c, E.dp_g[i].off); ln.beta = W(c, E.dp_b[i].off); ln.film = e.FILM; ln.film_prod = e.FPROD; ln.gate = ACT_RELU;
+        ln.gamma = train ? train->gamma[i] : W(c, E.dp_g[i].off); ln.beta = train ? train->beta[i] : W(c, E.dp_b[i].off);
+        ln.film = e.FILM; ln.film_prod = e.FPROD; ln.gate = ACT_RELU;
         LAUNCH(c, 2, 0, s, launch_ln_bwd(ln, s));
+        if (train && train->reduce) RET_IF(train->reduce(train->reduce_ctx, i));
         LAUNCH(c, 2, 0, s, launch_colsum(e.FPROD, F, 0, F, B, Tx, d_x_lengths, verdict, e.DFILM, 2 * F, 0, first ? 0 : 1, s));
         first = false;
-        if (i >= 1) RET_IF(tgemm(GW.dp_convT[i], e.GDB, F, F, g.dp_kernel, nullptr, 0, xm, e.GDA, F, B, Tx));
+        if (i >= 1) RET_IF(tgemm(PC, train ? train->convT[i] : GW.dp_convT[i], e.GDB, F, F, g.dp_kernel, nullptr, 0, xm, e.GDA, F, B, Tx));
     }
-    RET_IF(tgemm(GW.filmT, e.DFILM, 2 * F, 2 * F, 1, nullptr, 0, nullptr, d_g_dur, Sd, B, 1));
+    if (d_g_dur) RET_IF(tgemm(PC, train ? train->filmT : GW.filmT, e.DFILM, 2 * F, 2 * F, 1, nullptr, 0, nullptr, d_g_dur, Sd, B, 1));
     return 0;
 }
-}  // namespace
+}  // namespace mtts
 
 extern "C" {
 

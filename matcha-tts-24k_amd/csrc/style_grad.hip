@@ -23,32 +23,15 @@
 // Fixed order: the rows are cut into chunks of conv_wgrad_chunk_rows(B, T) rows -- a function of the shape alone, never of the device --
 // each chunk's sum is one serial chain, and the chunks are added in chunk order by a second kernel.  No atomics: two calls give the same
 // bits on any partition of the device.
-#include "host.h"
+#include "conv_wgrad.h"
 
-#include <algorithm>
 #include <string>
 
 namespace mtts {
 
 constexpr int WG_SLAB = 32;          // rows staged in LDS per step (16 MFMA k-steps of 2 rows)
 constexpr int WG_TILE = 64;          // output channels x input channels per workgroup: 2 x 2 waves of 32 x 32, five taps each
-constexpr int WG_TAPS = 5;
-constexpr int WG_CHUNK_UNIT = 256;   // chunk lengths are multiples of this
-constexpr int WG_MAX_CHUNKS = 16;
-
-// Rows per chunk of the reduction over M = B T rows: 256 up to 4096 rows, then the multiple of 256 that keeps the chunks at 16 or fewer.
-static inline int conv_wgrad_chunk_rows(int64_t M) {
-    const int64_t per = (M + (int64_t)WG_CHUNK_UNIT * WG_MAX_CHUNKS - 1) / ((int64_t)WG_CHUNK_UNIT * WG_MAX_CHUNKS);
-    return (int)(WG_CHUNK_UNIT * std::max<int64_t>(per, 1));
-}
-static inline int conv_wgrad_chunks(int64_t M) {
-    const int ch = conv_wgrad_chunk_rows(M);
-    return (int)((M + ch - 1) / ch);
-}
-// floats of partial results: [chunks][5][cout][cin] then [chunks][cout]
-static inline size_t conv_wgrad_partial_floats(int64_t M, int cin, int cout) {
-    return (size_t)conv_wgrad_chunks(M) * ((size_t)WG_TAPS * cout * cin + cout);
-}
+// (WG_TAPS, the chunk constants and conv_wgrad_chunk_rows / _chunks / _partial_floats: conv_wgrad.h, shared with dp_grad.hip)
 
 __device__ __forceinline__ int wg_frames(const int64_t* __restrict__ lengths, int b, int T) {
     if (!lengths) return T;
@@ -200,8 +183,8 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ part_w, const floa
 }
 
 // The whole weight (and bias) gradient of one Conv1d(k5, pad 2): three launches.  part: conv_wgrad_partial_floats floats.
-static hipError_t launch_conv_wgrad(const float* dz, int ldz, const float* x, int ldx, const int64_t* lengths, int B, int T, int cin, int cout,
-                                    float* dw, float* db, float* part, hipStream_t s) {
+hipError_t launch_conv_wgrad(const float* dz, int ldz, const float* x, int ldx, const int64_t* lengths, int B, int T, int cin, int cout,
+                             float* dw, float* db, float* part, hipStream_t s) {
     if (!dz || !x || !dw || !part || B <= 0 || T <= 0 || cin <= 0 || cout <= 0 || ldx < cin || ldz < cout ||
         (int64_t)B * T > (int64_t)1 << 30)
         return hipErrorInvalidValue;
@@ -216,7 +199,6 @@ static hipError_t launch_conv_wgrad(const float* dz, int ldz, const float* x, in
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, part_b, chunks, cin, cout, dw, db);
     return hipGetLastError();
 }
-static double conv_wgrad_flops(int B, int T, int cin, int cout) { return 2.0 * B * T * (double)cin * cout * WG_TAPS; }
 
 // ---------------------------------------------------------------------------------------------- projections and pool, backwards
 // g = [g_enc | g_dur] per clip (2E outputs), pw [2E][C] the forward image's projection rows, pooled [B][C].

@@ -491,6 +491,48 @@ class MatchaTTSInfer(nn.Module):
         return rt.guarded(self.range_policy, run, lambda _: (bool(rt.ready().call_flags("spk_grad_match")[0].item()), False))
 
     @torch.inference_mode()
+    def duration_grad(self, x, x_lengths, durations=None, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0,
+                      voice_mix=None, speaker_embeddings=None, sample_rate=24000, silence=None, params=None):
+        """Gradient of the training forward's duration loss with respect to every parameter of the duration predictor
+        (``encoder.proj_w.*``), on the device (``HipModel.dp_grad``; include/mtts.h mtts_dp_grad).  In the reference the predictor reads
+        ``x.detach()`` and the duration Huber loss is the only loss that reaches it, so with everything else frozen this is the
+        reference's gradient for those tensors -- the dropout-free one (the reference trains with ``p_dropout``).
+
+        ``durations`` (int [B, Tx], fine frames) are the targets; without them ``align`` runs first on the recording (``audio`` at
+        ``sample_rate`` with ``silence``, or ``mel_fine``, as for ``speaker_grad``).  Speaker arguments as for ``synthesise``.
+        ``params``: the predictor as one flat vector in the layout of ``hip.dp_layout()`` (None: the model's own predictor).
+
+        Returns ``grad`` (flat, the gradient of ``dur_loss``: already divided by the token count), ``g_dur`` [B, spk_emb_dim] (gradient
+        of the per-utterance sums ``dur_sum`` [B] with respect to the ``e_dur`` rows), ``dur_loss``, ``dur_loss_per_utterance``,
+        ``durations`` (int32 [B, Tx]) and ``logw`` [B, 1, Tx] of the predictor in ``params``, computed in native fp32 (not bit-equal to
+        ``text_encoder``'s under the default arithmetic).  One synchronisation per call; ``ValueError`` names a refused utterance."""
+        rt = self._rt
+        dev = x.device
+        hp = self.hp
+        if durations is None:
+            durations = self.align(x, x_lengths, audio=audio, audio_lengths=audio_lengths, mel_fine=mel_fine, mel_fine_lengths=mel_fine_lengths,
+                                   speaker=speaker, voice_mix=voice_mix, speaker_embeddings=speaker_embeddings, silence=silence,
+                                   sample_rate=sample_rate)["durations"]
+
+        def run():
+            hip = rt.ready()
+            rows = speaker_embeddings
+            if rows is not None:
+                rows = tuple(e.to(dev).reshape(-1, hp.spk_emb_dim) for e in rows)
+            e_enc, e_dur = self._voice_rows(x.shape[0], dev, speaker, voice_mix, rows)
+            x_len = x_lengths.to(device=dev, dtype=torch.long)
+            dur = torch.as_tensor(durations).to(device=dev, dtype=torch.int32)
+            out = hip.dp_grad(x, x_len, e_enc, e_dur, dur, hp.duration_loss_threshold, hip.dp_train_buffer(params))
+            tokens = x_len.to(torch.float32).sum()
+            out["grad"] = out["grad"] / tokens
+            out["dur_loss"] = out["dur_sum"].sum() / tokens
+            out["dur_loss_per_utterance"] = out["dur_sum"] / x_len.to(torch.float32)
+            out["durations"] = dur
+            return out
+        # (the stream is already drained: no second wait)
+        return rt.guarded(self.range_policy, run, lambda _: (bool(rt.ready().call_flags("dp_grad")[0].item()), False))
+
+    @torch.inference_mode()
     def finetune_speaker(self, x, x_lengths, audio=None, audio_lengths=None, mel_fine=None, mel_fine_lengths=None, speaker=0,
                          speaker_embeddings=None, steps=100, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, batch_size=None, shuffle_seed=0,
                          silence=None, sample_rate=24000):
